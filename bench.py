@@ -6,7 +6,7 @@ genotypes, pi0 = 0.95 estimated, at 1/2/4/8 GPUs.  One "step" = one MCMC iterati
 over all p markers (device) + the host-side updates of MCMC_BayesianAlphabet.jl:196-220,294-370
 (location parameters, pi, marker-effect variance, residual variance).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ...] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workloads (BASELINE.json `configs`):
@@ -36,10 +36,15 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                   RHS of block k): algorithmic bytes per launch / average launch duration, from the HIP events
                   recorded on the sweep's stream inside the timed region; "traffic" is filled from the PMC summaries
                   under profiles/ when they were collected for exactly this configuration (traffic_source), else null;
+and, with --full only (a plain run sets up, warms up, times its steps and prints the line):
   "cpu_baseline": the CPU oracle's non-block sweep of the same sampler (the reference's per-marker sdot / scalar update /
                   saxpy order) timed on this box's host cores on a marker subsample (N = 1, rank 0 only): single thread,
                   a 16-thread team and all cores; the fastest is `value`, all are listed in `sample`;
   "via_api":      (config2, N = 1) the same chain driven through the package's runMCMC() -- the API path a user calls.
+
+--dump-outputs DIR (rank 0): after the timed steps, the chain's state as the last timed step left it -- marker effects,
+inclusion indicators, residuals, intercepts, variances, pi and the step's statistics -- as DIR/<name>.npy (float32 /
+float64, at most 64 MB in all), so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -108,14 +113,22 @@ def parse():
     ap.add_argument("--groups", type=int, default=int(os.environ.get("JWAS_BENCH_GROUPS", "-1")), choices=[-1, 0, 2, 4],
                     help="blocks per launch of the step kernel in the sparse steady state (grouped launches, jwas_hip_setup_groups); "
                          "0 = one block per launch; -1 = the host policy's default (mcmc.GROUPED_BLOCKS_PER_LAUNCH)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline does not need: the CPU baseline and the runMCMC() leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left (marker effects, residuals, variances, ...) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-markers", type=int, default=20000)
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target CPU time per thread-count leg")
     ap.add_argument("--via-api", type=int, default=-1,
-                    help="timed iterations of the runMCMC() leg (config2, 1 GPU; default 20, 0 = skip)")
+                    help="with --full: timed iterations of the runMCMC() leg (config2, 1 GPU; default 20, 0 = skip)")
     if "JWAS_BENCH_ARGV" in os.environ and "RANK" in os.environ and len(sys.argv) == 1:      # a rank started by spawn_ranks()
-        return ap.parse_args(json.loads(os.environ["JWAS_BENCH_ARGV"]))
-    return ap.parse_args()
+        a = ap.parse_args(json.loads(os.environ["JWAS_BENCH_ARGV"]))
+    else:
+        a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 _T0 = time.time()
@@ -580,10 +593,12 @@ def main():
         }
         if chain_rec is not None:
             out["chain"] = chain_rec
-        if world == 1 and not a.no_cpu_baseline:
+        if a.dump_outputs:        # before the --full legs: runMCMC() drives the same engine
+            dump_outputs(a.dump_outputs, eng, t, state, last)
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a, eng, method, t, n, p_total, min(a.cpu_sample_markers, p_loc), Y, state, refbench)
         nvia = a.via_api if a.via_api >= 0 else (20 if (wl == "config2" and world == 1 and a.pi_fixed is None and a.storage == "dense") else 0)
-        if world == 1 and nvia > 0 and bayesc and t == 1 and not refbench:
+        if world == 1 and a.full and nvia > 0 and bayesc and t == 1 and not refbench:
             out["via_api"] = via_api(eng, Y[0], n, p_total, a, nvia)
     eng.close()
     if world > 1:
@@ -598,6 +613,40 @@ def main():
 
 
 _ABANDONED_THREAD = False
+DUMP_LIMIT_BYTES = 64 << 20
+_TIMING_KEYS = ("sweep_ms", "update_kernel_ms", "update_kernel_samples", "update_kernel_bytes", "event_overhead_ms")
+
+
+def dump_outputs(folder, eng, t, state, last):
+    """What the timed path computed in its last step: this rank's marker effects (alpha, beta), indicators (delta) and
+    residuals as the device holds them, the host's intercepts / variances / pi, and the sweep's statistics (timings left
+    out).  Arrays larger than their share of the 64 MB limit keep a fixed, seeded sample of their columns."""
+    st = [eng.get_state(k) for k in range(t)]
+    arrays = {
+        "alpha": np.stack([s[0] for s in st]).astype(np.float32),
+        "beta": np.stack([s[1] for s in st]).astype(np.float32),
+        "delta": np.stack([s[2] for s in st]).astype(np.float32),
+        "residual": np.stack([eng.get_residual(k) for k in range(t)]).astype(np.float32),
+        "mu": np.asarray(state["mu"], dtype=np.float64),
+        "vare": np.asarray(state["vare"], dtype=np.float64),
+        "pi": np.asarray(state["pi"], dtype=np.float64),
+    }
+    if state.get("G") is not None:
+        arrays["var_effect"] = np.asarray(state["G"], dtype=np.float64)
+    for k, v in last.items():
+        if k not in _TIMING_KEYS:
+            arrays["stats_" + k] = np.asarray(v, dtype=np.float64)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        big = [k for k in ("alpha", "beta", "delta", "residual") if arrays[k].nbytes > (1 << 20)]
+        room = DUMP_LIMIT_BYTES - sum(v.nbytes for k, v in arrays.items() if k not in big)
+        for k in big:
+            v = arrays[k]
+            keep = max(1, min(v.shape[1], room // (len(big) * v.shape[0] * v.itemsize)))
+            arrays[k] = np.ascontiguousarray(v[:, np.sort(np.random.default_rng(0).choice(v.shape[1], size=keep, replace=False))])
+    os.makedirs(folder, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(folder, k + ".npy"), v)
 
 
 def via_api(eng, y, n, p, a, nsteps):

@@ -7,13 +7,13 @@ timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/gpu_tests.log 2>&1; echo
 tail -6 $OUT/gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -3 $OUT/smoke.log
 export JWAS_BENCH_VERBOSE=1
-timeout 400 python bench.py > $OUT/bench_config2.json 2> $OUT/bench_config2.log
-timeout 400 python bench.py --pi-fixed 0.95 --cpu-seconds 4 > $OUT/bench_config2_pifixed.json 2> $OUT/bench_config2_pifixed.log
-timeout 400 python bench.py --workload config3 --cpu-seconds 5 > $OUT/bench_config3.json 2> $OUT/bench_config3.log
-timeout 400 python bench.py --workload config4 --cpu-seconds 5 > $OUT/bench_config4.json 2> $OUT/bench_config4.log
+timeout 400 python bench.py --full > $OUT/bench_config2.json 2> $OUT/bench_config2.log
+timeout 400 python bench.py --full --pi-fixed 0.95 --cpu-seconds 4 > $OUT/bench_config2_pifixed.json 2> $OUT/bench_config2_pifixed.log
+timeout 400 python bench.py --full --workload config3 --cpu-seconds 5 > $OUT/bench_config3.json 2> $OUT/bench_config3.log
+timeout 400 python bench.py --full --workload config4 --cpu-seconds 5 > $OUT/bench_config4.json 2> $OUT/bench_config4.log
 timeout 400 python bench.py --workload config4 --mt-prior sparse --no-cpu-baseline > $OUT/bench_config4_sparse.json 2> $OUT/bench_config4_sparse.log
-timeout 400 python bench.py --workload config5shard --cpu-seconds 5 > $OUT/bench_config5shard.json 2> $OUT/bench_config5shard.log
-timeout 400 python bench.py --workload refbench --cpu-seconds 5 > $OUT/bench_refbench.json 2> $OUT/bench_refbench.log
+timeout 400 python bench.py --full --workload config5shard --cpu-seconds 5 > $OUT/bench_config5shard.json 2> $OUT/bench_config5shard.log
+timeout 400 python bench.py --full --workload refbench --cpu-seconds 5 > $OUT/bench_refbench.json 2> $OUT/bench_refbench.log
 timeout 400 python bench.py --storage packed2bit --no-cpu-baseline > $OUT/bench_config2_packed.json 2> $OUT/bench_config2_packed.log
 for f in $OUT/bench_*.json; do python - $f <<'PY'
 import json,sys

@@ -3,6 +3,7 @@ there is no GPU on the CPU test box), and the shipped package never routes throu
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -53,11 +54,10 @@ def test_memory_estimate_formula():
 
 def test_no_cpu_fallback_without_gpu():
     import jwas_jl_amd as J
-    try:
-        import torch
-        has_gpu = torch.cuda.is_available()
-    except Exception:
-        has_gpu = False
+    # asked in a child process: torch brings its own HIP runtime, and once it holds the device in this process the
+    # library's runtime finds none -- every GPU test after this one would fail
+    r = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"], capture_output=True, text=True)
+    has_gpu = r.returncode == 0 and r.stdout.strip().endswith("1")
     if has_gpu:
         pytest.skip("a GPU is present")
     with pytest.raises(J.JwasHipError, match="no CPU fallback"):

@@ -17,8 +17,9 @@ def _run(args, env_extra=None, timeout=300):
 
 
 def test_bench_refuses_more_gpus_than_the_box_has():
-    import torch
-    ndev = torch.cuda.device_count()
+    # counted in a child process: torch's own HIP runtime must not take the device in the test process (see test_abi.py)
+    ndev = int(subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"],
+                              capture_output=True, text=True, check=True).stdout.split()[-1])
     want = max(ndev, 1) + 1
     r = _run(["--gpus", str(want), "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
     assert r.returncode == 2, r.stderr[-2000:]
@@ -31,6 +32,34 @@ def test_bench_refuses_a_world_size_that_is_not_gpus():
     assert r.returncode == 2, r.stderr[-2000:]
     assert "refusing to print a line" in r.stderr
     assert "{" not in r.stdout
+
+
+def test_bench_refuses_zero_steps():
+    r = _run(["--steps", "0"])
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+    assert "{" not in r.stdout
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_plain_run(tmp_path):
+    """A plain run (no --full) prints the headline line without the extra legs; --dump-outputs writes the last timed step's
+    state as float32 / float64 .npy files, and two runs with the same arguments write the same arrays."""
+    import json
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = _run(["--steps", "3", "--warmup", "2", "--burnin", "0", "--n", "3000", "--p", "8192", "--dump-outputs", str(d)], timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and "cpu_baseline" not in out and "via_api" not in out
+        dumps.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    assert {"alpha", "delta", "residual", "mu", "vare", "pi"} <= {name[:-4] for name in dumps[0]}
+    assert dumps[0]["alpha.npy"].shape == (1, 8192) and dumps[0]["residual.npy"].shape == (1, 3000)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name, v in dumps[0].items():
+        assert v.dtype in (np.float32, np.float64), name
+        assert np.array_equal(v, dumps[1][name]), name
 
 
 @pytest.mark.gpu

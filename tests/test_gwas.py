@@ -135,13 +135,16 @@ def test_reference_gwas_test_sets_on_demo_data(tmp_path):
     assert "WPPA" in res[0].columns
 
 
-def test_window_genetic_correlation_matches_literal_restatement(tmp_path):
+def test_window_genetic_correlation_matches_literal_restatement(tmp_path, monkeypatch):
     """GWAS.jl:199-237: per sample and window cov / cor of the two traits' window genomic values."""
     X, s1, f1, mapf, chrom, pos = _case(tmp_path, seed=5)
     rng = np.random.default_rng(9)
     s2 = np.where(rng.random(s1.shape) < 0.2, rng.standard_normal(s1.shape), 0.0).astype(np.float32)
     s2[:, :5] = 0.7 * s1[:, :5]                        # some shared signal
-    f2 = str(tmp_path / "MCMC_samples_marker_effects_geno_y2.txt")
+    # the output file's name is built from BOTH input paths: relative paths keep it within NAME_MAX under a deep temp dir
+    monkeypatch.chdir(tmp_path)
+    f1 = os.path.basename(f1)
+    f2 = "MCMC_samples_marker_effects_geno_y2.txt"
     pd.DataFrame(s2, columns=[f"m{j + 1}" for j in range(s1.shape[1])]).to_csv(f2, index=False, float_format="%.9g")
     res = GWAS(X, mapf, f1, f2, window_size="1 Mb", GWAS=False, genetic_correlation=True, output_folder=str(tmp_path),
                _engine=OracleEngine("dense"))
