@@ -385,9 +385,13 @@ int  jwas_hip_get_marker_covariances(jwas_hip_ctx* ctx, float* out_p_t_t);      
  * most 1024 markers), jwas_hip_set_weights (the Float32 values, widened), jwas_hip_init_state, jwas_hip_sweep (reading
  * jwas_sweep_params.vare_f64 / var_effect_f64 / var_effect_vec_f64; nreps and independent_blocks as in a Float32 context),
  * jwas_hip_residual_sub_xalpha, jwas_hip_accumulate and jwas_hip_num_blocks are shared.  Samplers: single-trait BayesA/B/C,
- * BayesR, multi-trait sampler I; dense storage; block size x traits <= 2048.  Everything else of the Float32 surface (packed
- * storage, a second block size, output rows, window sums, shards, samplers II / constrained / per-marker covariances)
- * returns JWAS_HIP_EUNSUP on a Float64 context. */
+ * BayesR, multi-trait BayesC and BayesA/B (MTBAYESC1 / C2 / B1 / B2) under Gibbs sampler I and II, with marker-specific joint
+ * priors (jwas_sweep_params.log_prior_states_matrix, 2 traits); dense storage; block size x traits <= 2048.  Multi-trait
+ * BayesA/B keeps its p x t x t covariances in double on the device: jwas_hip_set_marker_covariances_f64 uploads them,
+ * jwas_hip_sample_marker_covariances draws them from the double beta, jwas_hip_get_marker_covariances_f64 reads them back;
+ * jwas_sweep_params.var_effect_matrix (float) is refused.  Everything else of the Float32 surface (packed storage, a second
+ * block size, output rows, window sums, shards, constraint = true: MEGABAYESC / MEGABAYESB) returns JWAS_HIP_EUNSUP on a
+ * Float64 context. */
 int  jwas_hip_set_precision(jwas_hip_ctx* ctx, int32_t bits);                     /* 32 (default) or 64 */
 int  jwas_hip_load_dense_f64(jwas_hip_ctx* ctx, const double* X_host, int64_t n, int64_t p, int64_t ld_host);
 int  jwas_hip_get_xpx_f64(jwas_hip_ctx* ctx, double* out_p);
@@ -397,6 +401,8 @@ int  jwas_hip_set_residual_f64(jwas_hip_ctx* ctx, int32_t trait, const double* r
 int  jwas_hip_get_residual_f64(jwas_hip_ctx* ctx, int32_t trait, double* r_host);
 int  jwas_hip_mul_alpha_f64(jwas_hip_ctx* ctx, int32_t trait, double* out_host);
 int  jwas_hip_get_posterior_f64(jwas_hip_ctx* ctx, int32_t trait, double* mean_alpha, double* mean_alpha2, double* mean_delta);
+int  jwas_hip_set_marker_covariances_f64(jwas_hip_ctx* ctx, const double* p_t_t);   /* p x t x t row-major */
+int  jwas_hip_get_marker_covariances_f64(jwas_hip_ctx* ctx, double* out_p_t_t);
 
 /* ---- posterior accumulators (output.jl:568-577) ---------------------------------------------- */
 int  jwas_hip_accumulate(jwas_hip_ctx* ctx, double nsamples);

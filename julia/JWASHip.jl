@@ -119,6 +119,14 @@ jwas_hip_load_dense_f64 / _set_state_f64 / _get_state_f64 / _set_residual_f64 / 
 hip_set_precision!(ctx::Ptr{Cvoid}, bits::Integer) =
     hip_check(ctx, ccall((:jwas_hip_set_precision, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32), ctx, bits))
 
+"Float64 context, multi-trait BayesA/B (init_state JWAS_HIP_MTBAYESB1 / MTBAYESB2): the p x t x t per-marker effect covariances in
+double, row-major per marker (locus_effect_variances, MTBayesABC.jl:66); the next sweeps invert and use them in place.  A drawn set
+(jwas_hip_sample_marker_covariances) is read back with hip_get_marker_covariances_f64!."
+hip_set_marker_covariances_f64!(b::HipBackend, m::Array{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_set_marker_covariances_f64, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.ctx, m))
+hip_get_marker_covariances_f64!(b::HipBackend, m::Array{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_get_marker_covariances_f64, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.ctx, m))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

@@ -35,7 +35,7 @@ SYMBOLS = [
     "jwas_hip_residual_add_scalar", "jwas_hip_comm_info", "jwas_hip_sample_marker_covariances", "jwas_hip_get_marker_covariances",
     "jwas_hip_set_precision", "jwas_hip_load_dense_f64", "jwas_hip_get_xpx_f64", "jwas_hip_set_state_f64", "jwas_hip_get_state_f64",
     "jwas_hip_set_residual_f64", "jwas_hip_get_residual_f64", "jwas_hip_mul_alpha_f64", "jwas_hip_get_posterior_f64",
-    "jwas_hip_setup_groups",
+    "jwas_hip_setup_groups", "jwas_hip_set_marker_covariances_f64", "jwas_hip_get_marker_covariances_f64",
 ]
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
 
@@ -156,6 +156,8 @@ def load():
     L.jwas_hip_get_residual_f64.argtypes = [vp, i32, vp]
     L.jwas_hip_mul_alpha_f64.argtypes = [vp, i32, vp]
     L.jwas_hip_get_posterior_f64.argtypes = [vp, i32, vp, vp, vp]
+    L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
+    L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_accumulate.argtypes = [vp, C.c_double]
     L.jwas_hip_get_posterior.argtypes = [vp, i32, vp, vp, vp]
     L.jwas_hip_load_jgb2.argtypes = [vp, C.c_char_p]

@@ -21,14 +21,16 @@
 //
 // There is no lookahead here (launch k+1 starts when block k's sampler is done): the Float64 mode is the reference's
 // "more digits" switch, not its throughput mode -- ~2 launches of a few microseconds per block on top of streaming
-// 8 n p bytes.  Methods: single-trait BayesA/B/C (RR-BLUP, BayesL via the host), BayesR, multi-trait sampler I; dense
+// 8 n p bytes.  Methods: single-trait BayesA/B/C (RR-BLUP, BayesL via the host), BayesR, multi-trait BayesC under sampler I
+// and II, multi-trait BayesA/B (one t x t effect covariance per marker, inverted once per sweep by k64_invert_marker_cov, drawn
+// on the device by k64_sample_marker_covariances) under sampler I and II, marker-specific joint priors (p x 2^t); dense
 // storage; residual weights (x'R^-1 x, X_b'R^-1 X_b, X_b'R^-1 r, r'R^-1 r); uniform blocks of any size <= 1024 and explicit
 // (ragged) partitions with within-block repetitions (fast_blocks); block size x traits <= 2048.  Arithmetic: operation for
 // operation the scalar kernels of the reference with T = Float64 (bayesabc_update_marker! BayesABC.jl:24-58, BayesR! :56-96,
-// _MTBayesABC_samplerI! :57-127); inner products are plain double sums (order: 4 x 64 lanes per slice, slices in order), so
+// _MTBayesABC_samplerI! :57-127, _MTBayesABC_samplerII! :129-210); inner products are plain double sums (order: 4 x 64 lanes per slice, slices in order), so
 // the chain agrees with a sequential double chain to ~1e-13 relative, not bit for bit.  Oracle: oracle/jwas_oracle_f64.c.
 #pragma once
-#include "kernels.hpp"
+#include "sweep.hpp"         // (chol_lower, iw_chi2, IwParams: the Float32 path's helpers, already in double)
 
 namespace jw64 {
 using namespace jw;
@@ -50,6 +52,8 @@ struct Params64 {
     const double* var_vec;      // p (BayesB)
     const double* pi_vec;       // p
     const double* pi_mat;       // p x 4
+    const double* ginv_mat;     // p x t x t per-marker G_j^-1 (multi-trait BayesA/B: k64_invert_marker_cov), else NULL
+    const double* lpr_mat;      // p x 2^t per-marker log pi(state) (marker-specific joint priors), else NULL
 };
 
 // ---- x'R^-1 x ---------------------------------------------------------------------------------
@@ -208,17 +212,123 @@ struct R64 {
     }
 };
 
+// Multi-trait sampler II (_MTBayesABC_samplerII!, MTBayesABC.jl:129-210) with T = Float64: one candidate state, the operation
+// order of the Float32 path's mt2_state (and the oracle's): lhs = D R^-1 D x'x + G^-1 (:179), rhs = (R^-1 D)'w (:180), Cholesky
+// lhs = L L', M = L^-1, inv(lhs) = M'M (:181), det = prod L_ii^2, gHat = inv(lhs) rhs (:183), q = -0.5 (log det - rhs'gHat)
+// (:184); with want_cand the candidate gHat + chol(inv(lhs)) z (:182,:185).  st: bit k = trait k in the model.
+template <int NT>
+__device__ __forceinline__ void mt2_state64(const double (&R)[NT][NT], const double (&Gi)[NT][NT], unsigned st, double dj,
+                                            const double (&w)[NT], const double (&z)[NT], bool want_cand, double& q, double (&cand)[NT])
+{
+    double lhs[NT][NT], L[NT][NT], M[NT][NT], inv[NT][NT], rhs[NT];
+#pragma unroll
+    for (int a = 0; a < NT; ++a) {
+        const double Da = ((st >> a) & 1u) ? 1.0 : 0.0;
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {
+            const double Dc = ((st >> c) & 1u) ? 1.0 : 0.0;
+            const double rl = (Da * R[a][c]) * Dc;                                  // D*Rinv*D  :159
+            lhs[a][c] = rl * dj + Gi[a][c];                                         // :179
+        }
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < NT; ++m) s = s + (R[m][a] * Da) * w[m];                 // (Rinv*D)'w :180
+        rhs[a] = s;
+    }
+    chol_lower<NT>(lhs, L);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {                                                  // M = L^-1
+        M[j][j] = 1.0 / L[j][j];
+#pragma unroll
+        for (int i = j + 1; i < NT; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = j; k < i; ++k) s = s + L[i][k] * M[k][j];
+            M[i][j] = -s / L[i][i];
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < NT; ++a)                                                    // inv(lhs) = M'M  :181
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = (a > c ? a : c); k < NT; ++k) s = s + M[k][a] * M[k][c];
+            inv[a][c] = s;
+        }
+    double det = 1.0;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) det = det * (L[j][j] * L[j][j]);
+    double quad = 0.0, gHat[NT];
+#pragma unroll
+    for (int a = 0; a < NT; ++a) {                                                  // gHat = invLhs*rhs :183
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < NT; ++c) s = s + inv[a][c] * rhs[c];
+        gHat[a] = s;
+        quad = quad + rhs[a] * s;
+    }
+    q = -0.5 * (log(det) - quad);                                                   // :184
+    if (!want_cand) return;
+    double C[NT][NT];
+    chol_lower<NT>(inv, C);                                                         // cholesky(Hermitian(invLhs)).L :182
+#pragma unroll
+    for (int a = 0; a < NT; ++a) {                                                  // gHat + L*z  :185
+        double s = gHat[a];
+#pragma unroll
+        for (int c = 0; c <= a; ++c) s = s + C[a][c] * z[c];
+        cand[a] = s;
+    }
+}
+
+// One marker under sampler II: every joint state's log density (:184-187), the categorical draw by the CDF walk (:188-198;
+// the state whose interval holds u, the last one when rounding leaves u above the total), the chosen state's candidate
+// recomputed with its draw (one shared z), alpha = D beta (:201).  The states are walked one at a time (a fully unrolled walk
+// spills at four traits); their log densities go to the lane's LDS column ld[s * 64].
+template <int NT>
+__device__ __forceinline__ void mt2_eval64(const double (&R)[NT][NT], const double (&Gi)[NT][NT], const double* __restrict__ lpr, double dj,
+                                           const double (&w)[NT], double u, const double (&z)[NT], double* ld,
+                                           double (&an)[NT], double (&bn)[NT], double (&dn)[NT])
+{
+    constexpr int NS = 1 << NT;
+    double cand[NT], q, mx = -INFINITY;
+#pragma unroll 1
+    for (int s = 0; s < NS; ++s) {
+        mt2_state64<NT>(R, Gi, (unsigned)s, dj, w, z, false, q, cand);
+        const double v = q + lpr[s];
+        ld[s * 64] = v;
+        mx = v > mx ? v : mx;
+    }
+    double den = 0.0;
+#pragma unroll 1
+    for (int s = 0; s < NS; ++s) { const double e = exp(ld[s * 64] - mx); ld[s * 64] = e; den += e; }
+    int which = NS - 1;
+    double cp = 0.0;
+#pragma unroll 1
+    for (int s = 0; s < NS; ++s) {
+        cp += ld[s * 64] / den;
+        if (u < cp) { which = s; break; }
+    }
+    mt2_state64<NT>(R, Gi, (unsigned)which, dj, w, z, true, q, cand);
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+        const double dk = ((which >> k) & 1) ? 1.0 : 0.0;
+        bn[k] = cand[k]; dn[k] = dk; an[k] = dk * cand[k];                          // diagm(delta)*beta :201
+    }
+}
+
 // ---- sampler: one workgroup of 256 threads; wave 0 runs the chain -----------------------------------------------------
 // LDS: gram [b][b] doubles (GLDS: blocks of <= 128 markers), then per marker and trait, stride bsz: rhs, the current effect,
-// the effect at block entry, beta, delta.
+// the effect at block entry, beta, delta; sampler II: then [2^NT][64] doubles, the wave's per-state log densities.
 struct Smem64 {
-    int gram_off, rhs_off, acur_off, astart_off, bcur_off, dcur_off, bytes;
-    __host__ __device__ Smem64(int b, int bsz, int NT, bool glds)
+    int gram_off, rhs_off, acur_off, astart_off, bcur_off, dcur_off, ld_off, bytes;
+    __host__ __device__ Smem64(int b, int bsz, int NT, bool glds, bool sampler2 = false)
     {
         gram_off = 0; rhs_off = glds ? b * b * 8 : 0;
         const int arr = NT * bsz * 8;
         acur_off = rhs_off + arr; astart_off = acur_off + arr; bcur_off = astart_off + arr; dcur_off = bcur_off + arr;
-        bytes = dcur_off + arr;
+        ld_off = dcur_off + arr;
+        bytes = ld_off + (sampler2 ? (1 << NT) * 64 * 8 : 0);
     }
 };
 
@@ -230,14 +340,16 @@ __global__ __launch_bounds__(256) void k64_sample(const Params64* __restrict__ P
                                                   void* __restrict__ delta, Events64* __restrict__ ev_out, unsigned long long* __restrict__ counters)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const Smem64 SM(b, bsz, NT, GLDS);
+    const Smem64 SM(b, bsz, NT, GLDS, is_sampler2(METHOD));
     double* G = reinterpret_cast<double*>(smem + SM.gram_off);       // [b][b]  (GLDS)
     double* rhs = reinterpret_cast<double*>(smem + SM.rhs_off);      // [NT][bsz]
     double* acur = reinterpret_cast<double*>(smem + SM.acur_off);
     double* astart = reinterpret_cast<double*>(smem + SM.astart_off);
     double* bcur = reinterpret_cast<double*>(smem + SM.bcur_off);
     double* dcur = reinterpret_cast<double*>(smem + SM.dcur_off);
+    double* ldst = reinterpret_cast<double*>(smem + SM.ld_off);      // [2^NT][64]  (sampler II)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr bool MT = is_mt_method(METHOD), MB = has_marker_cov(METHOD);
     if constexpr (GLDS) for (int i = tid; i < b * b; i += 256) G[i] = gram[i];
     for (int i = tid; i < NT * b; i += 256) {
         const int t = i / b, c = i - t * b;
@@ -294,9 +406,27 @@ __global__ __launch_bounds__(256) void k64_sample(const Params64* __restrict__ P
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { rm.lpi[k] = log(P->pi_mat ? P->pi_mat[4 * j + k] : P->pi4[k]); rm.gamma[k] = P->gamma[k]; }
                 rm.u = draw_uniform(key, marker, 0u); rm.z = draw_normal(key, marker, 0u);
+            } else if constexpr (is_sampler2(METHOD)) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) { z_t[t] = draw_normal(key, marker, (uint32_t)t); u_t[t] = 0.0; }     // randn(ntraits) :176
+                u_t[0] = draw_uniform(key, marker, 0u);
             } else {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) { u_t[t] = draw_uniform(key, marker, (uint32_t)t); z_t[t] = draw_normal(key, marker, (uint32_t)t); }
+            }
+            // multi-trait: R^-1, the marker's G^-1 (its own with BayesA/B, MTBayesABC.jl:86-90) and log pi(state) (its own with
+            // marker-specific priors, :22-47)
+            double Rm[MT ? NT : 1][MT ? NT : 1], Gm[MT ? NT : 1][MT ? NT : 1];
+            const double* lpr = P->log_prior;
+            if constexpr (MT) {
+#pragma unroll
+                for (int a = 0; a < NT; ++a)
+#pragma unroll
+                    for (int c = 0; c < NT; ++c) {
+                        Rm[a][c] = P->Rinv[a * NT + c];
+                        Gm[a][c] = MB ? P->ginv_mat[j * (NT * NT) + a * NT + c] : P->Ginv[a * NT + c];
+                    }
+                if (P->lpr_mat) lpr = P->lpr_mat + j * (1 << NT);
             }
             while (pending) {
                 // every pending lane evaluates ITS marker against the current rhs
@@ -310,6 +440,14 @@ __global__ __launch_bounds__(256) void k64_sample(const Params64* __restrict__ P
                     rm.eval(rhs[cl], a_cur[0], an[0], cls);
                     bn[0] = 0.0; dn[0] = (double)cls;
                     ev = an[0] != a_cur[0];
+                } else if constexpr (is_sampler2(METHOD)) {
+                    // _MTBayesABC_samplerII! (MTBayesABC.jl:170-205), T = Float64
+                    double w[NT];
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) w[t] = rhs[t * bsz + cl] + dj * a_cur[t];                       // :172
+                    mt2_eval64<NT>(Rm, Gm, lpr, dj, w, u_t[0], z_t, ldst + lane, an, bn, dn);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) ev = ev || (an[t] != a_cur[t]);
                 } else {
                     // _MTBayesABC_samplerI! (MTBayesABC.jl:76-121), T = Float64
                     double w[NT], bb[NT], dl[NT];
@@ -317,15 +455,15 @@ __global__ __launch_bounds__(256) void k64_sample(const Params64* __restrict__ P
                     for (int t = 0; t < NT; ++t) { w[t] = rhs[t * bsz + cl] + dj * a_cur[t]; bb[t] = b_cur[t]; dl[t] = d_cur[t]; an[t] = a_cur[t]; }
 #pragma unroll
                     for (int k = 0; k < NT; ++k) {
-                        const double Ginv11 = P->Ginv[k * NT + k];                               // :86
-                        const double C11 = Ginv11 + P->Rinv[k * NT + k] * dj;                    // :89
+                        const double Ginv11 = Gm[k][k];                                          // :86
+                        const double C11 = Ginv11 + Rm[k][k] * dj;                               // :89
                         double rhs0 = 0.0, c12b = 0.0, wR = 0.0;
 #pragma unroll
                         for (int m = 0; m < NT; ++m) {
-                            wR = wR + w[m] * P->Rinv[m * NT + k];                                // :96
+                            wR = wR + w[m] * Rm[m][k];                                           // :96
                             if (m == k) continue;
-                            const double C12m = P->Ginv[k * NT + m] + (dj * dl[m]) * P->Rinv[k * NT + m];      // :90
-                            rhs0 = rhs0 + P->Ginv[k * NT + m] * bb[m];                           // :93
+                            const double C12m = Gm[k][m] + (dj * dl[m]) * Rm[k][m];              // :90
+                            rhs0 = rhs0 + Gm[k][m] * bb[m];                                      // :93
                             c12b = c12b + C12m * bb[m];
                         }
                         rhs0 = -rhs0;
@@ -335,8 +473,8 @@ __global__ __launch_bounds__(256) void k64_sample(const Params64* __restrict__ P
 #pragma unroll
                         for (int m = 0; m < NT; ++m) if (m != k && dl[m] != 0.0) s0 |= 1u << m;
                         const unsigned s1 = s0 | (1u << k);
-                        const double logDelta0 = -0.5 * (log(Ginv11) - gHat0 * gHat0 * Ginv11) + P->log_prior[s0];      // :104
-                        const double logDelta1 = -0.5 * (log(C11) - gHat1 * gHat1 * C11) + P->log_prior[s1];            // :105
+                        const double logDelta0 = -0.5 * (log(Ginv11) - gHat0 * gHat0 * Ginv11) + lpr[s0];               // :104
+                        const double logDelta1 = -0.5 * (log(C11) - gHat1 * gHat1 * C11) + lpr[s1];                     // :105
                         const double probDelta1 = 1.0 / (1.0 + exp(logDelta0 - logDelta1));                          // :107
                         if (u_t[k] < probDelta1) { dl[k] = 1.0; bb[k] = gHat1 + z_t[k] * sqrt(invLhs1); an[k] = bb[k]; }      // :108-111
                         else { bb[k] = gHat0 + z_t[k] * sqrt(invLhs0); dl[k] = 0.0; an[k] = 0.0; }                         // :112-119
@@ -404,6 +542,97 @@ __global__ __launch_bounds__(256) void k64_sample(const Params64* __restrict__ P
         }
     }
     if (lane == 0) { ev_out->count = base; atomicAdd(&counters[0], (unsigned long long)base); }
+}
+
+// ---- multi-trait BayesA/B: the per-marker covariances -------------------------------------------------------------------
+// G_j^-1 for every marker, once per sweep (MTBayesABC.jl:66 Ginv = inv.(varEffects)): Gauss-Jordan with partial pivoting in
+// double, the host's inv(vare) order; a singular G_j gives NaN (the oracle's marker_ginv).  One thread per marker.
+template <int NT>
+__global__ __launch_bounds__(256) void k64_invert_marker_cov(int64_t p, const double* __restrict__ var_mat, double* __restrict__ ginv_mat)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= p) return;
+    double M[NT][2 * NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int c = 0; c < NT; ++c) { M[i][c] = var_mat[j * (NT * NT) + i * NT + c]; M[i][NT + c] = (i == c) ? 1.0 : 0.0; }
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < NT; ++c) {
+        int piv = c;
+        double best = fabs(M[c][c]);
+#pragma unroll
+        for (int i = c + 1; i < NT; ++i) if (fabs(M[i][c]) > best) { piv = i; best = fabs(M[i][c]); }
+#pragma unroll
+        for (int i = c + 1; i < NT; ++i)                    // swap rows c and piv (register arrays: static indices only)
+            if (i == piv) {
+#pragma unroll
+                for (int q = 0; q < 2 * NT; ++q) { const double tmp = M[c][q]; M[c][q] = M[i][q]; M[i][q] = tmp; }
+            }
+        ok = ok && (M[c][c] != 0.0);
+        const double d = M[c][c];
+#pragma unroll
+        for (int q = 0; q < 2 * NT; ++q) M[c][q] /= d;
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+            if (i != c) {
+                const double f = M[i][c];
+                if (f != 0.0) {
+#pragma unroll
+                    for (int q = 0; q < 2 * NT; ++q) M[i][q] -= f * M[c][q];
+                }
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int c = 0; c < NT; ++c) ginv_mat[j * (NT * NT) + i * NT + c] = ok ? M[i][NT + c] : (double)NAN;
+}
+
+// G_j ~ InverseWishart(df, scale + b_j b_j') from the double beta (variance_components.jl:181-186): the Float32 path's
+// k_sample_marker_covariances (Bartlett's decomposition, the same counters and chi-square draws) with the result kept in double.
+template <int NT>
+__global__ __launch_bounds__(256) void k64_sample_marker_covariances(IwParams Q, int64_t p, const double* __restrict__ beta, double* __restrict__ var_mat)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= p) return;
+    const uint32_t marker = Q.marker0 + (uint32_t)j;
+    double b[NT], S[NT][NT], C[NT][NT], A[NT][NT], Kt[NT][NT];
+#pragma unroll
+    for (int a = 0; a < NT; ++a) b[a] = beta[(int64_t)a * p + j];
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+#pragma unroll
+        for (int c = 0; c < NT; ++c) { S[a][c] = Q.scale[a * NT + c] + b[a] * b[c]; C[a][c] = 0.0; A[a][c] = 0.0; }
+    chol_lower<NT>(S, C);
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        A[i][i] = sqrt(iw_chi2(marker, Q.iter, 32u + 2u * (uint32_t)i, Q.seed_lo, Q.seed_hi, Q.df - (double)i));
+#pragma unroll
+        for (int k = 0; k < i; ++k) {
+            const u32x4 w = philox4x32_10(marker, Q.iter, 0x80000000u, 64u + 4u * (uint32_t)i + (uint32_t)k, Q.seed_lo, Q.seed_hi);
+            A[i][k] = sqrt(-2.0 * log(u52(w.x, w.y))) * cos(6.283185307179586476925286766559 * u52(w.z, w.w));
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {
+            double acc = C[c][i];                                       // C'[i][c]
+#pragma unroll
+            for (int k = 0; k < i; ++k) acc = acc - A[i][k] * Kt[k][c];
+            Kt[i][c] = acc / A[i][i];
+        }
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {
+            double g1 = 0.0, g2 = 0.0;
+#pragma unroll
+            for (int i = 0; i < NT; ++i) { g1 = g1 + Kt[i][a] * Kt[i][c]; g2 = g2 + Kt[i][c] * Kt[i][a]; }
+            var_mat[(j * NT + a) * NT + c] = 0.5 * (g1 + g2);
+        }
 }
 
 // ---- epilogue: apply the last block's changes (independent blocks: EVERY block's, in (block, marker) order -- the reconcile of

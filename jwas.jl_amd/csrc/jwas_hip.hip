@@ -138,6 +138,9 @@ struct jwas_hip_ctx {
         int64_t ev_all_cap = 0;
         jw64::Params64* dparams = nullptr;
         double* var_vec = nullptr;          // [p] BayesB
+        double* var_mat = nullptr;          // [p][t][t] multi-trait BayesA/B: per-marker effect covariances
+        double* ginv_mat = nullptr;         // [p][t][t] their inverses (k64_invert_marker_cov, once per sweep)
+        bool var_mat_resident = false;      // var_mat holds this chain's covariances (uploaded or drawn on the device)
         double* w = nullptr;                // [ld] residual weights R^-1 (pad rows 0; ones when unweighted)
         std::vector<int64_t> starts;        // block starts (nblocks + 1 entries, 0-based): uniform or explicit partition
         int bstride = 0;                    // largest block of the partition, rounded up to a multiple of 8
@@ -2127,8 +2130,10 @@ static int sweep_collect(jwas_hip_ctx* c, jwas_sweep_stats* S, size_t ntimed, do
 static void f64_free_state(jwas_hip_ctx* c)
 {
     auto* F = c->f64;
-    for (void* q : {(void*)F->alpha, (void*)F->beta, F->delta, (void*)F->mean_a, (void*)F->mean_a2, (void*)F->mean_d, (void*)F->var_vec}) (void)hipFree(q);
-    F->alpha = F->beta = F->mean_a = F->mean_a2 = F->mean_d = F->var_vec = nullptr; F->delta = nullptr;
+    for (void* q : {(void*)F->alpha, (void*)F->beta, F->delta, (void*)F->mean_a, (void*)F->mean_a2, (void*)F->mean_d, (void*)F->var_vec,
+                    (void*)F->var_mat, (void*)F->ginv_mat}) (void)hipFree(q);
+    F->alpha = F->beta = F->mean_a = F->mean_a2 = F->mean_d = F->var_vec = F->var_mat = F->ginv_mat = nullptr; F->delta = nullptr;
+    F->var_mat_resident = false;
 }
 
 // x'R^-1 x, the Grams X_b'R^-1 X_b of the partition in F->starts (block k at k * bstride^2, row stride = the block's size) and
@@ -2196,9 +2201,11 @@ static int f64_init_state(jwas_hip_ctx* c, int32_t method, int32_t nt)
 {
     auto* F = c->f64;
     NEED(c, F->X, JWAS_HIP_ESTATE, "no genotype matrix loaded");
-    NEED(c, method == JWAS_HIP_BAYESC || method == JWAS_HIP_BAYESB || method == JWAS_HIP_BAYESR || method == JWAS_HIP_MTBAYESC1, JWAS_HIP_EUNSUP,
-         "Float64 contexts run single-trait BayesA/B/C, BayesR and multi-trait sampler I (got method %d)", method);
-    if (method == JWAS_HIP_MTBAYESC1) NEED(c, nt >= 2 && nt <= kMaxT, JWAS_HIP_EUNSUP, "multi-trait samplers support 2..%d traits (got %d)", kMaxT, nt);
+    NEED(c, method == JWAS_HIP_BAYESC || method == JWAS_HIP_BAYESB || method == JWAS_HIP_BAYESR || method == JWAS_HIP_MTBAYESC1 ||
+            method == JWAS_HIP_MTBAYESC2 || method == JWAS_HIP_MTBAYESB1 || method == JWAS_HIP_MTBAYESB2, JWAS_HIP_EUNSUP,
+         "Float64 contexts run single-trait BayesA/B/C, BayesR and multi-trait BayesA/B/C under sampler I or II; not constraint = true "
+         "(megaBayesABC) (got method %d)", method);
+    if (is_mt_method(method)) NEED(c, nt >= 2 && nt <= kMaxT, JWAS_HIP_EUNSUP, "multi-trait samplers support 2..%d traits (got %d)", kMaxT, nt);
     else NEED(c, nt == 1, JWAS_HIP_EINVAL, "single-trait method requires ntraits == 1 (got %d)", nt);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2252,8 +2259,9 @@ static void f64_launch_block(jwas_hip_ctx* c, const double* r_in, double* r_out,
                        r_in, r_out, ev_prev, j0, b, cpg, part, bsz);
     // the block's Gram in LDS only when it FITS beside the per-marker arrays (their stride is the partition's largest block:
     // b = 128 next to a 512-marker block with two traits would ask for 168 KB); otherwise the rows come from L2
-    const bool glds = b <= jw64::kGramLds64 && jw64::Smem64(b, bsz, NT, true).bytes <= 160 * 1024;
-    const jw64::Smem64 SM(b, bsz, NT, glds);
+    const bool s2 = c->method == JWAS_HIP_MTBAYESC2 || c->method == JWAS_HIP_MTBAYESB2;
+    const bool glds = b <= jw64::kGramLds64 && jw64::Smem64(b, bsz, NT, true, s2).bytes <= 160 * 1024;
+    const jw64::Smem64 SM(b, bsz, NT, glds, s2);
     const double* G = F->gram + k * (int64_t)bsz * bsz;
 #define JW64_SAMPLE(M)                                                                                                                  \
     do {                                                                                                                                \
@@ -2266,7 +2274,12 @@ static void f64_launch_block(jwas_hip_ctx* c, const double* r_in, double* r_out,
         if (c->method == JWAS_HIP_BAYESC) JW64_SAMPLE(kBayesC);
         else if (c->method == JWAS_HIP_BAYESB) JW64_SAMPLE(kBayesB);
         else JW64_SAMPLE(kBayesR);
-    } else JW64_SAMPLE(kMTBayesC1);
+    } else {
+        if (c->method == JWAS_HIP_MTBAYESC1) JW64_SAMPLE(kMTBayesC1);
+        else if (c->method == JWAS_HIP_MTBAYESC2) JW64_SAMPLE(kMTBayesC2);
+        else if (c->method == JWAS_HIP_MTBAYESB1) JW64_SAMPLE(kMTBayesB1);
+        else JW64_SAMPLE(kMTBayesB2);
+    }
 #undef JW64_SAMPLE
 }
 
@@ -2280,7 +2293,7 @@ static hipError_t f64_set_lds_attr()
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&jw64::k64_sample<M, NT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
     if (e != hipSuccess) return e;
     if constexpr (NT == 1) { JW64_ATTR(kBayesC) JW64_ATTR(kBayesB) JW64_ATTR(kBayesR) }
-    else { JW64_ATTR(kMTBayesC1) }
+    else { JW64_ATTR(kMTBayesC1) JW64_ATTR(kMTBayesC2) JW64_ATTR(kMTBayesB1) JW64_ATTR(kMTBayesB2) }
 #undef JW64_ATTR
     return e;
 }
@@ -2291,9 +2304,20 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
     NEED(c, c->method >= 0, JWAS_HIP_ESTATE, "jwas_hip_init_state has not been called");
     NEED(c, c->block_size && F->gram, JWAS_HIP_ESTATE, "jwas_hip_setup_blocks has not been called");
     NEED(c, P->method == c->method && P->ntraits == c->ntraits, JWAS_HIP_EINVAL, "sweep method/ntraits (%d/%d) differ from init_state (%d/%d)", P->method, P->ntraits, c->method, c->ntraits);
-    NEED(c, !P->log_prior_states_matrix && !P->var_effect_matrix, JWAS_HIP_EUNSUP, "marker-specific multi-trait priors / covariances are not available in a Float64 context");
+    NEED(c, !P->var_effect_matrix, JWAS_HIP_EUNSUP, "var_effect_matrix holds float covariances; a Float64 context takes them in double "
+         "through jwas_hip_set_marker_covariances_f64 (or draws them with jwas_hip_sample_marker_covariances)");
     const int t = c->ntraits;
     NEED(c, F->bstride * t <= 2048, JWAS_HIP_EUNSUP, "Float64 contexts need block size x traits <= 2048 (got %d x %d)", F->bstride, t);
+    const bool marker_cov = has_marker_cov(c->method);
+    if (marker_cov) {       // multi-trait BayesA/B (MTBayesABC.jl:66,86-90): the limits of the Float32 path
+        NEED(c, F->var_mat && F->var_mat_resident, JWAS_HIP_EINVAL, "multi-trait BayesA/B needs per-marker effect covariances (jwas_hip_set_marker_covariances_f64, or jwas_hip_sample_marker_covariances)");
+        NEED(c, !P->independent_blocks, JWAS_HIP_EUNSUP, "independent_blocks is not available with per-marker effect covariances");
+        NEED(c, !P->log_prior_states_matrix, JWAS_HIP_EUNSUP, "marker-specific joint priors are not available with per-marker effect covariances");
+    }
+    if (P->log_prior_states_matrix) {       // MarkerSpecificPiPrior (MTBayesABC.jl:22-47)
+        NEED(c, is_mt_method(c->method), JWAS_HIP_EINVAL, "log_prior_states_matrix is for the multi-trait samplers");
+        NEED(c, t == 2, JWAS_HIP_EUNSUP, "marker-specific joint priors support 2 traits (got %d)", t);
+    }
     HIPCHK(c, hipSetDevice(c->device));
     {   // > 64 KB of dynamic LDS (the block's Gram in doubles)
         static std::atomic<unsigned long long> attr_set{0ull};
@@ -2308,7 +2332,7 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
     D.method = c->method; D.ntraits = t; D.nreps = P->nreps;
     D.iter = P->iteration; D.seed_lo = (uint32_t)P->seed; D.seed_hi = (uint32_t)(P->seed >> 32); D.marker0 = P->marker_offset;
     for (int i = 0; i < t * t; ++i) { D.vare[i] = P->vare_f64[i]; D.var_effect[i] = P->var_effect_f64[i]; }
-    if (c->method == JWAS_HIP_MTBAYESC1) {
+    if (is_mt_method(c->method)) {
         // inv(vare), inv(G) (MTBayesABC.jl:66-67) in double: Gauss-Jordan with partial pivoting (the oracle's operation order)
         auto inv_d = [&](const double* A, double* Ainv) -> int {
             double M[kMaxT][2 * kMaxT];
@@ -2326,8 +2350,20 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
             return 0;
         };
         NEED(c, inv_d(D.vare, D.Rinv) == 0, JWAS_HIP_EINVAL, "residual covariance matrix is singular");
-        NEED(c, inv_d(D.var_effect, D.Ginv) == 0, JWAS_HIP_EINVAL, "marker effect covariance matrix is singular");
-        for (int i = 0; i < (1 << t); ++i) D.log_prior[i] = P->log_prior_states[i];
+        if (!marker_cov) NEED(c, inv_d(D.var_effect, D.Ginv) == 0, JWAS_HIP_EINVAL, "marker effect covariance matrix is singular");
+        bool any_finite = false;
+        for (int i = 0; i < (1 << t); ++i) { D.log_prior[i] = P->log_prior_states[i]; any_finite = any_finite || std::isfinite(D.log_prior[i]); }
+        if (is_sampler2(c->method) && !P->log_prior_states_matrix)      // MTBayesABC.jl:190
+            NEED(c, any_finite, JWAS_HIP_EINVAL, "All MTBayesABC sampler II state probabilities are zero or invalid.");
+        if (P->log_prior_states_matrix) {
+            int rc = upload_vec(c, (void**)&c->lpr_mat, P->log_prior_states_matrix, sizeof(double) * (size_t)(1 << t) * c->p);
+            if (rc) return rc;
+            D.lpr_mat = c->lpr_mat;
+        }
+        if (marker_cov) {
+            if (!F->ginv_mat) HIPCHK(c, hipMalloc(&F->ginv_mat, sizeof(double) * (size_t)t * t * c->p));
+            D.ginv_mat = F->ginv_mat;
+        }
     } else NEED(c, D.vare[0] > 0.0, JWAS_HIP_EINVAL, "residual variance must be positive");
     if (c->method == JWAS_HIP_BAYESR) {
         NEED(c, D.var_effect[0] > 0.0, JWAS_HIP_EINVAL, "BayesR sigmaSq must be positive.");
@@ -2350,6 +2386,12 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
     HIPCHK(c, hipMemcpyAsync(F->dparams, &D, sizeof D, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->counters, 0, sizeof(unsigned long long) * kNCounters, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
+    if (marker_cov) {       // G_j^-1 once per sweep, before the first block
+        const dim3 g((unsigned)((c->p + 255) / 256)), bk(256);
+        if (t == 2) hipLaunchKernelGGL((jw64::k64_invert_marker_cov<2>), g, bk, 0, c->stream, c->p, F->var_mat, F->ginv_mat);
+        else if (t == 3) hipLaunchKernelGGL((jw64::k64_invert_marker_cov<3>), g, bk, 0, c->stream, c->p, F->var_mat, F->ginv_mat);
+        else hipLaunchKernelGGL((jw64::k64_invert_marker_cov<4>), g, bk, 0, c->stream, c->p, F->var_mat, F->ginv_mat);
+    }
     const int64_t nb = c->nblocks;
     const size_t rbuf = (size_t)kMaxT * c->ld;
     auto rb = [&](int64_t parity) { return F->r + (size_t)(parity & 1) * rbuf; };
@@ -2729,10 +2771,34 @@ int jwas_hip_sweep_sharded(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_swe
 }
 
 // ---- multi-trait BayesA/B: the per-marker effect covariances drawn on the device -------------------------------
+// Float64 context: the draws from the double beta into the double covariances (k64_sample_marker_covariances)
+static int f64_sample_marker_covariances(jwas_hip_ctx* c, double df, const double* scale, uint64_t seed, uint32_t iteration, uint32_t marker_offset)
+{
+    auto* F = c->f64;
+    NEED(c, c->method == JWAS_HIP_MTBAYESB1 || c->method == JWAS_HIP_MTBAYESB2, JWAS_HIP_ESTATE,
+         "jwas_hip_sample_marker_covariances needs init_state(JWAS_HIP_MTBAYESB1 | JWAS_HIP_MTBAYESB2, t)");
+    const int t = c->ntraits;
+    NEED(c, df > (double)(t - 1), JWAS_HIP_EINVAL, "inverse-Wishart degrees of freedom must exceed ntraits - 1 (got %g)", df);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!F->var_mat) HIPCHK(c, hipMalloc(&F->var_mat, sizeof(double) * (size_t)t * t * c->p));
+    IwParams Q;
+    std::memset(&Q, 0, sizeof Q);
+    Q.df = df;
+    for (int i = 0; i < t * t; ++i) Q.scale[i] = scale[i];
+    Q.seed_lo = (uint32_t)seed; Q.seed_hi = (uint32_t)(seed >> 32); Q.iter = iteration; Q.marker0 = marker_offset;
+    const dim3 g((unsigned)((c->p + 255) / 256)), b(256);
+    if (t == 2) hipLaunchKernelGGL((jw64::k64_sample_marker_covariances<2>), g, b, 0, c->stream, Q, c->p, F->beta, F->var_mat);
+    else if (t == 3) hipLaunchKernelGGL((jw64::k64_sample_marker_covariances<3>), g, b, 0, c->stream, Q, c->p, F->beta, F->var_mat);
+    else hipLaunchKernelGGL((jw64::k64_sample_marker_covariances<4>), g, b, 0, c->stream, Q, c->p, F->beta, F->var_mat);
+    HIPCHK(c, hipGetLastError());
+    F->var_mat_resident = true;
+    return JWAS_HIP_OK;
+}
+
 int jwas_hip_sample_marker_covariances(jwas_hip_ctx* c, double df, const double* scale, uint64_t seed, uint32_t iteration, uint32_t marker_offset)
 {
-    if (c) NOT_F64(c, "per-marker effect covariances");
     NEED(c, c && scale, JWAS_HIP_EINVAL, "NULL argument");
+    if (IS_F64(c)) return f64_sample_marker_covariances(c, df, scale, seed, iteration, marker_offset);
     NEED(c, has_marker_cov(c->method), JWAS_HIP_ESTATE, "jwas_hip_sample_marker_covariances needs init_state(JWAS_HIP_MTBAYESB1 | JWAS_HIP_MTBAYESB2 | JWAS_HIP_MEGABAYESB, t)");
     const int t = c->ntraits;
     const bool diag = is_mega(c->method);           // constraint = true: scaled inverse chi-square draws of the diagonal only
@@ -2757,9 +2823,39 @@ int jwas_hip_sample_marker_covariances(jwas_hip_ctx* c, double df, const double*
 int jwas_hip_get_marker_covariances(jwas_hip_ctx* c, float* out)
 {
     NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
+    NOT_F64(c, "jwas_hip_get_marker_covariances (use jwas_hip_get_marker_covariances_f64)");
     NEED(c, c->var_mat && c->var_mat_resident, JWAS_HIP_ESTATE, "no per-marker effect covariances are resident");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(out, c->var_mat, sizeof(float) * (size_t)c->ntraits * c->ntraits * c->p, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+// Float64 context, multi-trait BayesA/B: the p x t x t per-marker covariances in double (host <-> device)
+int jwas_hip_set_marker_covariances_f64(jwas_hip_ctx* c, const double* mat)
+{
+    NEED(c, c && mat, JWAS_HIP_EINVAL, "NULL argument");
+    ONLY_F64(c);
+    NEED(c, c->method == JWAS_HIP_MTBAYESB1 || c->method == JWAS_HIP_MTBAYESB2, JWAS_HIP_ESTATE,
+         "jwas_hip_set_marker_covariances_f64 needs init_state(JWAS_HIP_MTBAYESB1 | JWAS_HIP_MTBAYESB2, t)");
+    auto* F = c->f64;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t mb = sizeof(double) * (size_t)c->ntraits * c->ntraits * c->p;
+    if (!F->var_mat) HIPCHK(c, hipMalloc(&F->var_mat, mb));
+    HIPCHK(c, hipMemcpyAsync(F->var_mat, mat, mb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    F->var_mat_resident = true;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_get_marker_covariances_f64(jwas_hip_ctx* c, double* out)
+{
+    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
+    ONLY_F64(c);
+    auto* F = c->f64;
+    NEED(c, F->var_mat && F->var_mat_resident, JWAS_HIP_ESTATE, "no per-marker effect covariances are resident");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, F->var_mat, sizeof(double) * (size_t)c->ntraits * c->ntraits * c->p, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return JWAS_HIP_OK;
 }

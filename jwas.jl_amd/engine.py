@@ -516,11 +516,14 @@ class HipEngine:
         keep = []
         if self.method in (_lib.MTBAYESB1, _lib.MTBAYESB2, _lib.MEGABAYESB):     # multi-trait BayesA/B: one t x t effect covariance per marker
             if var_effect_matrix is not None:     # (None: the covariances resident on the device -- sample_marker_covariances)
-                vm = np.ascontiguousarray(var_effect_matrix, dtype=np.float32)
+                vm = np.ascontiguousarray(var_effect_matrix, dtype=self.dtype)
                 if vm.shape != (self.p, t, t):
                     raise ValueError(f"var_effect_matrix must be {self.p} x {t} x {t}")
-                keep.append(vm)
-                P.var_effect_matrix = vm.ctypes.data_as(C.POINTER(C.c_float))
+                if self.precision == 64:          # (a Float64 context keeps them in double: uploaded here, the sweep reads them in place)
+                    self._chk(self._L.jwas_hip_set_marker_covariances_f64(self._h, _ptr(vm)))
+                else:
+                    keep.append(vm)
+                    P.var_effect_matrix = vm.ctypes.data_as(C.POINTER(C.c_float))
         if self.method in (_lib.BAYESC, _lib.BAYESB):
             if np.ndim(pi) == 1:
                 pi_vec = pi
@@ -612,8 +615,9 @@ class HipEngine:
                                                              int(iteration), int(marker_offset)))
 
     def marker_covariances(self):
-        out = np.empty((self.p, self.ntraits, self.ntraits), dtype=np.float32)
-        self._chk(self._L.jwas_hip_get_marker_covariances(self._h, _ptr(out)))
+        """The resident p x t x t per-marker covariances (float32; float64 in a Float64 context)."""
+        out = np.empty((self.p, self.ntraits, self.ntraits), dtype=self.dtype)
+        self._chk(self._f("jwas_hip_get_marker_covariances")(self._h, _ptr(out)))
         return out
 
     # -- posterior accumulators --------------------------------------------------------------------

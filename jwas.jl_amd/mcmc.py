@@ -617,13 +617,14 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
 
     if double_precision:
         # the Float64 device context (csrc/f64_path.hpp): dense storage; single-trait BayesA/B/C (+ RR-BLUP, BayesL through
-        # them), BayesR, multi-trait BayesC sampler I; any fast_blocks partition with blocks of <= 1024 markers (uniform or
-        # explicit starts), independent_blocks, residual weights; block size x traits <= 2048
+        # them), BayesR, multi-trait BayesC and BayesA/B under sampler I and II, marker-specific joint priors; any fast_blocks
+        # partition with blocks of <= 1024 markers (uniform or explicit starts), independent_blocks, residual weights; block
+        # size x traits <= 2048
         if stream or devres:
             raise NotImplementedError("double_precision=true needs dense host genotypes (the streaming backend is Float32 only, readgenotypes.jl:246-248)")
-        if mega or mt_pervar or (t > 1 and mt_method != "MTBayesC"):
-            raise NotImplementedError("double_precision=true runs the single-trait samplers and multi-trait BayesC sampler I on the device; "
-                                      "sampler II, constraint=true and multi-trait BayesA/B stay on the reference in Float64 mode")
+        if mega:
+            raise NotImplementedError("double_precision=true runs every sampler on the device except constraint=true (megaBayesABC), "
+                                      "which stays on the reference in Float64 mode")
         if fast_blocks is not False:
             if explicit_partition is None:
                 block_size = want                      # (the Float64 context runs uniform blocks of ANY size <= 1024 as they are)
@@ -678,6 +679,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             # block size) and one partial-sum buffer per block (4 traits x row slices x block doubles)
             nb_ = -(-p // max(1, block_size))
             need += nb_ * (4 + 1024 * (4 + 4 * 8)) + 4 * 8 * (-(-n // 256)) * nb_ * block_size
+        if double_precision and mt_pervar:
+            need += p * t * t * 8 * 2                              # Float64 multi-trait BayesA/B: the covariances and their inverses in double
         if outputEBV and not out_same:                             # Mi.output_genotypes: a second dense matrix (n_out x p)
             need += 4 * ((len(out_rows) + 255) // 256 * 256) * p
         engine = HipEngine(device, precision=64 if double_precision else 32)

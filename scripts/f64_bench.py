@@ -1,5 +1,9 @@
-"""Throughput of the Float64 context (runMCMC(double_precision=true)) on one MI355X: BayesC sweeps over a synthetic
-n x p matrix of doubles.  python scripts/f64_bench.py [n] [p]"""
+"""Throughput of the Float64 context (runMCMC(double_precision=true)) on one MI355X: sweeps over a synthetic n x p matrix of
+doubles.  python scripts/f64_bench.py [n] [p] [--method M[,M...]] [--traits T[,T...]] [--sweeps K]
+  --method BayesC (default; Float64 against Float32), or the multi-trait kinds, Float64 only:
+           MT1 (BayesC, sampler I), MT2 (BayesC, sampler II), MTB1 / MTB2 (BayesB, sampler I / II: one covariance per marker,
+           redrawn on the device every sweep -- wall_ms includes that draw)"""
+import argparse
 import json
 import os
 import sys
@@ -10,8 +14,14 @@ import numpy as np
 sys.path.insert(0, ".")
 import jwas_jl_amd as J
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
-p = int(sys.argv[2]) if len(sys.argv) > 2 else 20000
+ap = argparse.ArgumentParser()
+ap.add_argument("n", type=int, nargs="?", default=20000)
+ap.add_argument("p", type=int, nargs="?", default=20000)
+ap.add_argument("--method", default="BayesC")
+ap.add_argument("--traits", default="2")
+ap.add_argument("--sweeps", type=int, default=20)
+args = ap.parse_args()
+n, p = args.n, args.p
 rng = np.random.default_rng(1)
 f = rng.uniform(0.1, 0.4, p)
 X = np.empty((n, p), dtype=np.float64, order="F")
@@ -22,7 +32,49 @@ X -= X.mean(axis=0)
 beta = np.zeros(p); q = rng.choice(p, p // 1000, replace=False); beta[q] = rng.standard_normal(q.size)
 g = X @ beta
 y = g / g.std() * np.sqrt(0.5) + rng.standard_normal(n) * np.sqrt(0.5)
+MT_KINDS = {"MT1": "MTBayesC", "MT2": "MTBayesC_II", "MTB1": "MTBayesB", "MTB2": "MTBayesB_II"}
+
+
+def bench_mt(kind, t):
+    """ms per sweep of a t-trait Float64 chain (blocks of JWAS_F64_BLOCK markers, default 512)."""
+    bs = int(os.environ.get("JWAS_F64_BLOCK", "0")) or min(512, 2048 // t)
+    e = J.HipEngine(0, precision=64)
+    e.load_dense(X)
+    e.setup_blocks(bs)
+    e.init_state(MT_KINDS[kind], t)
+    rng_t = np.random.default_rng(7)
+    for k in range(t):
+        e.set_residual((1 + 0.2 * k) * (y - y.mean()) + 0.5 * rng_t.standard_normal(n), k)
+        e.set_state(k, delta=np.ones(p))
+    R = 0.5 * np.eye(t) + 0.1
+    G = (0.5 / (0.05 * (2 * f * (1 - f)).sum())) * (0.8 * np.eye(t) + 0.2)
+    lp = np.log(np.full(1 << t, 0.05 / ((1 << t) - 1))); lp[0] = np.log(0.95)
+    ms, wall = [], []
+    for it in range(1, args.sweeps + 1):
+        kw = dict(iteration=it, seed=3, vare=R, var_effect=G, log_prior_states=lp)
+        t0 = time.time()
+        if kind.startswith("MTB"):
+            if it == 1:
+                kw["var_effect_matrix"] = np.tile(G, (p, 1, 1))
+            else:
+                e.sample_marker_covariances(t + 4.0, G * 4.0, seed=3, iteration=it - 1)
+        st = e.sweep(**kw)
+        wall.append(1e3 * (time.time() - t0))
+        ms.append(st["sweep_ms"])
+    e.close()
+    return {"block": bs, "sweep_ms_last10": float(np.mean(ms[-10:])), "wall_ms_last10": float(np.mean(wall[-10:])),
+            "state_counts": [float(v) for v in st["state_counts"]]}
+
+
 out = {}
+if args.method != "BayesC":
+    X = np.asfortranarray(X)
+    for kind in args.method.split(","):
+        for t in (int(v) for v in args.traits.split(",")):
+            out[f"{kind}_t{t}"] = bench_mt(kind, t)
+            print(json.dumps({f"{kind}_t{t}": out[f"{kind}_t{t}"]}), flush=True)
+    print(json.dumps({"n": n, "p": p, **out}))
+    sys.exit(0)
 for prec in (64, 32):
     e = J.HipEngine(0, precision=prec)
     dt = np.float64 if prec == 64 else np.float32
