@@ -389,9 +389,12 @@ int  jwas_hip_get_marker_covariances(jwas_hip_ctx* ctx, float* out_p_t_t);      
  * priors (jwas_sweep_params.log_prior_states_matrix, 2 traits); dense storage; block size x traits <= 2048.  Multi-trait
  * BayesA/B keeps its p x t x t covariances in double on the device: jwas_hip_set_marker_covariances_f64 uploads them,
  * jwas_hip_sample_marker_covariances draws them from the double beta, jwas_hip_get_marker_covariances_f64 reads them back;
- * jwas_sweep_params.var_effect_matrix (float) is refused.  Everything else of the Float32 surface (packed storage, a second
- * block size, output rows, window sums, shards, constraint = true: MEGABAYESC / MEGABAYESB) returns JWAS_HIP_EUNSUP on a
- * Float64 context. */
+ * jwas_sweep_params.var_effect_matrix (float) is refused.  The output side follows the state: jwas_hip_load_output_dense_f64 /
+ * jwas_hip_mul_alpha_output_f64 (EBVs of the output rows), jwas_hip_get_alpha_sparse_f64 (a saved sample as a sparse record)
+ * and jwas_hip_window_sums_f64 / jwas_hip_window_sums2_f64 (the window GWAS) are the twins of the Float32 calls, with double
+ * arrays; called on a Float32 context they return JWAS_HIP_ESTATE.  Everything else of the Float32 surface (packed storage, a
+ * second block size, shards, constraint = true: MEGABAYESC / MEGABAYESB, and the Float32 namesakes of the calls above) returns
+ * JWAS_HIP_EUNSUP on a Float64 context. */
 int  jwas_hip_set_precision(jwas_hip_ctx* ctx, int32_t bits);                     /* 32 (default) or 64 */
 int  jwas_hip_load_dense_f64(jwas_hip_ctx* ctx, const double* X_host, int64_t n, int64_t p, int64_t ld_host);
 int  jwas_hip_get_xpx_f64(jwas_hip_ctx* ctx, double* out_p);
@@ -399,7 +402,25 @@ int  jwas_hip_set_state_f64(jwas_hip_ctx* ctx, int32_t trait, const double* alph
 int  jwas_hip_get_state_f64(jwas_hip_ctx* ctx, int32_t trait, double* alpha, double* beta, void* delta);
 int  jwas_hip_set_residual_f64(jwas_hip_ctx* ctx, int32_t trait, const double* r_host);
 int  jwas_hip_get_residual_f64(jwas_hip_ctx* ctx, int32_t trait, double* r_host);
+/* out = X * alpha_k (n doubles; one fma per nonzero effect in marker order: getEBV, output.jl:281-306, T = Float64). */
 int  jwas_hip_mul_alpha_f64(jwas_hip_ctx* ctx, int32_t trait, double* out_host);
+/* Mi.output_genotypes in Float64 (tools4genotypes.jl:290-296 after JWAS.jl:353): n_out x p marker-major doubles with leading
+ * dimension ld_host; copied.  A second call replaces the matrix; it is freed with the context. */
+int  jwas_hip_load_output_dense_f64(jwas_hip_ctx* ctx, const double* X_out_host, int64_t n_out, int64_t p, int64_t ld_host);
+/* out = X_out * alpha_k (n_out doubles): EBV = output_genotypes * alpha of a saved sample (output.jl:281-306); row i equals the
+ * jwas_hip_mul_alpha_f64 value of the training row it was copied from, bit for bit. */
+int  jwas_hip_mul_alpha_output_f64(jwas_hip_ctx* ctx, int32_t trait, double* out_host);
+/* One saved marker-effect sample as (marker index, value) lists in marker order instead of the dense row of p values
+ * (output.jl:443-526).  *nnz is filled even when the lists do not fit `capacity` (JWAS_HIP_EINVAL: grow and call again). */
+int  jwas_hip_get_alpha_sparse_f64(jwas_hip_ctx* ctx, int32_t trait, int64_t capacity, int32_t* idx, double* val, int64_t* nnz);
+/* jwas_hip_window_sums / jwas_hip_window_sums2 with T = Float64: the reference forms X*alpha in the element type of
+ * output_genotypes (GWAS.jl:148,152-165,199-217), Float64 after double_precision=true.  Same CSR description and outputs;
+ * use_output_rows != 0: the rows of jwas_hip_load_output_dense_f64. */
+int  jwas_hip_window_sums_f64(jwas_hip_ctx* ctx, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
+                              const double* val, double* out_sum, double* out_ss);
+int  jwas_hip_window_sums2_f64(jwas_hip_ctx* ctx, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
+                               const double* val1, const double* val2, double* out_sum1, double* out_ss1, double* out_sum2,
+                               double* out_ss2, double* out_cross);
 int  jwas_hip_get_posterior_f64(jwas_hip_ctx* ctx, int32_t trait, double* mean_alpha, double* mean_alpha2, double* mean_delta);
 int  jwas_hip_set_marker_covariances_f64(jwas_hip_ctx* ctx, const double* p_t_t);   /* p x t x t row-major */
 int  jwas_hip_get_marker_covariances_f64(jwas_hip_ctx* ctx, double* out_p_t_t);

@@ -127,6 +127,32 @@ hip_set_marker_covariances_f64!(b::HipBackend, m::Array{Float64}) =
 hip_get_marker_covariances_f64!(b::HipBackend, m::Array{Float64}) =
     hip_check(b.ctx, ccall((:jwas_hip_get_marker_covariances_f64, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.ctx, m))
 
+"Float64 context, the output side (Ptr{Float64} twins of the Float32 calls): Mi.output_genotypes as a second resident matrix
+(tools4genotypes.jl:290-296), EBV = output_genotypes * alpha of a saved sample (output.jl:281-306), a saved sample as (index, value)
+lists in marker order, and the window sums of the GWAS (GWAS.jl:152-165, :199-217; outs = 2 vectors of nwin, or 5 with val2)."
+hip_load_output_dense_f64!(b::HipBackend, X::Matrix{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_load_output_dense_f64, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64),
+                           b.ctx, X, size(X, 1), size(X, 2), size(X, 1)))
+hip_mul_alpha_output_f64!(b::HipBackend, trait::Integer, out::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_mul_alpha_output_f64, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), b.ctx, trait, out))
+function hip_get_alpha_sparse_f64(b::HipBackend, trait::Integer)
+    idx, val, nnz = Vector{Int32}(undef, b.nMarkers), Vector{Float64}(undef, b.nMarkers), Ref{Int64}(0)
+    hip_check(b.ctx, ccall((:jwas_hip_get_alpha_sparse_f64, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Int64}),
+                           b.ctx, trait, b.nMarkers, idx, val, nnz))
+    return idx[1:nnz[]], val[1:nnz[]]          # 0-based marker indices
+end
+hip_window_sums_f64!(b::HipBackend, use_output_rows::Bool, wptr::Vector{Int32}, idx::Vector{Int32}, val::Vector{Float64},
+                     out_sum::Vector{Float64}, out_ss::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_window_sums_f64, LIBJWAS_HIP), Cint,
+                           (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                           b.ctx, use_output_rows, length(wptr) - 1, wptr, idx, val, out_sum, out_ss))
+hip_window_sums2_f64!(b::HipBackend, use_output_rows::Bool, wptr::Vector{Int32}, idx::Vector{Int32}, val1::Vector{Float64},
+                      val2::Vector{Float64}, outs::NTuple{5,Vector{Float64}}) =
+    hip_check(b.ctx, ccall((:jwas_hip_window_sums2_f64, LIBJWAS_HIP), Cint,
+                           (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                            Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                           b.ctx, use_output_rows, length(wptr) - 1, wptr, idx, val1, val2, outs...))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

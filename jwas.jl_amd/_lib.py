@@ -36,6 +36,8 @@ SYMBOLS = [
     "jwas_hip_set_precision", "jwas_hip_load_dense_f64", "jwas_hip_get_xpx_f64", "jwas_hip_set_state_f64", "jwas_hip_get_state_f64",
     "jwas_hip_set_residual_f64", "jwas_hip_get_residual_f64", "jwas_hip_mul_alpha_f64", "jwas_hip_get_posterior_f64",
     "jwas_hip_setup_groups", "jwas_hip_set_marker_covariances_f64", "jwas_hip_get_marker_covariances_f64",
+    "jwas_hip_load_output_dense_f64", "jwas_hip_mul_alpha_output_f64", "jwas_hip_get_alpha_sparse_f64",
+    "jwas_hip_window_sums_f64", "jwas_hip_window_sums2_f64",
 ]
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
 
@@ -156,6 +158,11 @@ def load():
     L.jwas_hip_get_residual_f64.argtypes = [vp, i32, vp]
     L.jwas_hip_mul_alpha_f64.argtypes = [vp, i32, vp]
     L.jwas_hip_get_posterior_f64.argtypes = [vp, i32, vp, vp, vp]
+    L.jwas_hip_load_output_dense_f64.argtypes = [vp, vp, i64, i64, i64]
+    L.jwas_hip_mul_alpha_output_f64.argtypes = [vp, i32, vp]
+    L.jwas_hip_get_alpha_sparse_f64.argtypes = [vp, i32, i64, vp, vp, C.POINTER(i64)]
+    L.jwas_hip_window_sums_f64.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    L.jwas_hip_window_sums2_f64.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_accumulate.argtypes = [vp, C.c_double]

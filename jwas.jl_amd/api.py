@@ -391,8 +391,11 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     rounding of the block right-hand sides; the group cross-Grams are set-up work (8 / 24 KB per marker).
 
     double_precision=True (JWAS.jl:349-366): genotypes, residual, effects and the samplers' arithmetic all Float64 -- a
-    Float64 device context (jwas_hip_set_precision; csrc/f64_path.hpp): single-trait BayesA/B/C, RR-BLUP, BayesL, BayesR and
-    multi-trait BayesC sampler I on dense storage; fast_blocks = 64 | 128."""
+    Float64 device context (jwas_hip_set_precision; csrc/f64_path.hpp): single-trait BayesA/B/C, RR-BLUP, BayesL, BayesR,
+    multi-trait BayesC and BayesA/B under sampler I and II and marker-specific joint priors on dense storage; any fast_blocks
+    partition of blocks <= 1024 markers, independent_blocks, residual weights.  Its outputs are formed on the device as well:
+    the EBVs of outputEBV(model, IDs) from a second resident Float64 matrix, saved samples read out as sparse lists.  Not in
+    Float64: constraint=true, storage=:stream, shards (explicit errors).  The sample files keep their Float32 / 9-digit format."""
     if independent_blocks and fast_blocks is False:
         raise ValueError("independent_blocks=true requires fast_blocks != false.")             # :242-244
     for flag, name in ((single_step_analysis, "single_step_analysis"),

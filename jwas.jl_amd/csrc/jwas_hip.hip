@@ -145,6 +145,10 @@ struct jwas_hip_ctx {
         std::vector<int64_t> starts;        // block starts (nblocks + 1 entries, 0-based): uniform or explicit partition
         int bstride = 0;                    // largest block of the partition, rounded up to a multiple of 8
         bool explicit_part = false;
+        double* Xout = nullptr;             // [p][ld_out] output rows (jwas_hip_load_output_dense_f64)
+        int64_t n_out = 0, ld_out = 0;
+        int32_t* cmp_idx = nullptr;         // [p] + [1] compacted nonzero effects of one trait (k64_compact_alpha)
+        double* cmp_val = nullptr;          // [p]
     };
     F64* f64 = nullptr;
 };
@@ -300,7 +304,8 @@ void jwas_hip_destroy(jwas_hip_ctx* c)
     if (c->f64) {
         auto* F = c->f64;
         for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->alpha, (void*)F->beta, F->delta, (void*)F->mean_a,
-                        (void*)F->mean_a2, (void*)F->mean_d, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->var_vec, (void*)F->w, (void*)F->ev_all}) (void)hipFree(q);
+                        (void*)F->mean_a2, (void*)F->mean_d, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->var_vec, (void*)F->w, (void*)F->ev_all,
+                        (void*)F->var_mat, (void*)F->ginv_mat, (void*)F->Xout, (void*)F->cmp_idx, (void*)F->cmp_val}) (void)hipFree(q);
         delete F;
         c->f64 = nullptr;
     }
@@ -1226,6 +1231,7 @@ int jwas_hip_mul_alpha(jwas_hip_ctx* c, int32_t trait, float* out)
 // sample has a few hundred nonzero effects among 600 000).  idx / val: caller arrays of `capacity` entries, marker order.
 int jwas_hip_get_alpha_sparse(jwas_hip_ctx* c, int32_t trait, int64_t capacity, int32_t* idx, float* val, int64_t* nnz_out)
 {
+    if (c) NOT_F64(c, "jwas_hip_get_alpha_sparse (use jwas_hip_get_alpha_sparse_f64)");
     NEED(c, c && nnz_out, JWAS_HIP_EINVAL, "NULL argument");
     NEED_TRAIT(c, trait);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1244,6 +1250,7 @@ int jwas_hip_get_alpha_sparse(jwas_hip_ctx* c, int32_t trait, int64_t capacity, 
 
 int jwas_hip_load_output_dense_f32(jwas_hip_ctx* c, const float* Xh, int64_t n_out, int64_t p, int64_t ld_host)
 {
+    if (c) NOT_F64(c, "jwas_hip_load_output_dense_f32 (use jwas_hip_load_output_dense_f64)");
     NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
     NEED(c, Xh, JWAS_HIP_EINVAL, "X_out is NULL");
     NEED(c, HAVE_STORAGE(c), JWAS_HIP_ESTATE, "no genotype matrix loaded");
@@ -1265,6 +1272,7 @@ int jwas_hip_load_output_dense_f32(jwas_hip_ctx* c, const float* Xh, int64_t n_o
 
 int jwas_hip_mul_alpha_output(jwas_hip_ctx* c, int32_t trait, float* out)
 {
+    if (c) NOT_F64(c, "jwas_hip_mul_alpha_output (use jwas_hip_mul_alpha_output_f64)");
     NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
     NEED_TRAIT(c, trait);
     NEED(c, c->Xout, JWAS_HIP_ESTATE, "jwas_hip_load_output_dense_f32 has not been called");
@@ -1295,6 +1303,7 @@ static int window_sums_impl(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nw
                             const float* val, const float* val2, double* const* outs /* 2 or 5 arrays of nwin */)
 {
     const int nv = val2 ? 5 : 2;
+    if (c) NOT_F64(c, val2 ? "jwas_hip_window_sums2 (use jwas_hip_window_sums2_f64)" : "jwas_hip_window_sums (use jwas_hip_window_sums_f64)");
     NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
     NEED(c, wptr, JWAS_HIP_EINVAL, "NULL argument");
     for (int v = 0; v < nv; ++v) NEED(c, outs[v], JWAS_HIP_EINVAL, "NULL output array");
@@ -1350,6 +1359,7 @@ int jwas_hip_window_sums2(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin
                           const float* val1, const float* val2, double* out_sum1, double* out_ss1, double* out_sum2,
                           double* out_ss2, double* out_cross)
 {
+    if (c) NOT_F64(c, "jwas_hip_window_sums2 (use jwas_hip_window_sums2_f64)");
     NEED(c, c && val2, JWAS_HIP_EINVAL, "NULL argument");
     double* outs[5] = {out_sum1, out_ss1, out_sum2, out_ss2, out_cross};
     return window_sums_impl(c, use_output_rows, nwin, wptr, idx, val1, val2, outs);
@@ -2124,7 +2134,9 @@ static int sweep_collect(jwas_hip_ctx* c, jwas_sweep_stats* S, size_t ntimed, do
 // A context becomes a Float64 context with jwas_hip_set_precision(ctx, 64) BEFORE genotypes are loaded; it then takes the
 // *_f64 data entry points (double host arrays) and the shared control entry points (setup_blocks, init_state, sweep,
 // accumulate, residual_sub_xalpha, num_blocks); everything else of the Float32 surface (packed storage, weights, explicit
-// partitions, output rows, window sums, shards) answers "not available in a Float64 context".
+// partitions, shards) answers "not available in a Float64 context".  The output side has _f64 twins: output rows
+// (jwas_hip_load_output_dense_f64 / jwas_hip_mul_alpha_output_f64), sparse samples (jwas_hip_get_alpha_sparse_f64) and the
+// window sums of the GWAS (jwas_hip_window_sums_f64 / jwas_hip_window_sums2_f64); their Float32 namesakes name them.
 // =====================================================================================================================
 
 static void f64_free_state(jwas_hip_ctx* c)
@@ -2448,6 +2460,93 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
     return sweep_collect(c, S, 0, 0.0, nullptr);
 }
 
+// The nonzero effects of trait `trait` of a Float64 context as device lists in marker order (F->cmp_idx / F->cmp_val, owned by
+// the context), compacted on the device; *nnz = their number.
+static hipError_t f64_compact_alpha(jwas_hip_ctx* c, int32_t trait, int* nnz)
+{
+    auto* F = c->f64;
+    hipError_t e = hipSuccess;
+    if (!F->cmp_idx) {
+        e = hipMalloc(&F->cmp_idx, sizeof(int32_t) * ((size_t)c->p + 1));
+        if (e == hipSuccess) e = hipMalloc(&F->cmp_val, sizeof(double) * (size_t)c->p);
+        if (e != hipSuccess) { (void)hipFree(F->cmp_idx); F->cmp_idx = nullptr; return e; }
+    }
+    hipLaunchKernelGGL(jw64::k64_compact_alpha, dim3(1), dim3(1024), 0, c->stream, c->p, F->alpha + (size_t)trait * c->p, F->cmp_idx, F->cmp_val,
+                       F->cmp_idx + c->p);
+    e = hipGetLastError();
+    int32_t cnt = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&cnt, F->cmp_idx + c->p, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    *nnz = (int)cnt;
+    return e;
+}
+
+// out[0 .. n_rows) = M alpha_trait over the nonzero effects (compact + list), M = the training or the output matrix.
+static int f64_mul_alpha_rows(jwas_hip_ctx* c, int32_t trait, const double* M, int64_t ld, int64_t n_rows, double* out, const char* who)
+{
+    double* tmp = nullptr;
+    HIPCHK(c, hipMalloc(&tmp, sizeof(double) * ld));
+    int nnz = 0;
+    hipError_t e = f64_compact_alpha(c, trait, &nnz);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(jw64::k64_mul_alpha_list, dim3((unsigned)(ld / 64)), dim3(64), 0, c->stream, M, ld, nnz, c->f64->cmp_idx, c->f64->cmp_val, tmp);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, sizeof(double) * n_rows, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(tmp);
+    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "%s: %s", who, hipGetErrorString(e));
+    return JWAS_HIP_OK;
+}
+
+// jwas_hip_window_sums(2)_f64: window_sums_impl with double effects over the Float64 matrices.
+static int f64_window_sums_impl(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
+                                const double* val, const double* val2, double* const* outs /* 2 or 5 arrays of nwin */)
+{
+    const int nv = val2 ? 5 : 2;
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    ONLY_F64(c);
+    auto* F = c->f64;
+    NEED(c, wptr, JWAS_HIP_EINVAL, "NULL argument");
+    for (int v = 0; v < nv; ++v) NEED(c, outs[v], JWAS_HIP_EINVAL, "NULL output array");
+    NEED(c, nwin >= 1, JWAS_HIP_EINVAL, "nwin must be >= 1 (got %d)", nwin);
+    NEED(c, F->X, JWAS_HIP_ESTATE, "no genotype matrix loaded");
+    NEED(c, !use_output_rows || F->Xout, JWAS_HIP_ESTATE, "jwas_hip_load_output_dense_f64 has not been called");
+    NEED(c, wptr[0] == 0, JWAS_HIP_EINVAL, "wptr[0] must be 0");
+    for (int w = 0; w < nwin; ++w) NEED(c, wptr[w + 1] >= wptr[w], JWAS_HIP_EINVAL, "wptr must be non-decreasing");
+    const int64_t nnz = wptr[nwin];
+    NEED(c, nnz == 0 || (idx && val), JWAS_HIP_EINVAL, "idx / val is NULL");
+    for (int64_t e = 0; e < nnz; ++e) NEED(c, idx[e] >= 0 && idx[e] < c->p, JWAS_HIP_EINVAL, "marker index %d out of range", idx[e]);
+    HIPCHK(c, hipSetDevice(c->device));
+    const double* M = use_output_rows ? F->Xout : F->X;
+    const int64_t ld = use_output_rows ? F->ld_out : c->ld;
+    const int nsl = (int)(ld / kSliceRows);
+    const size_t ne = (size_t)(nnz > 0 ? nnz : 1);
+    int32_t *d_wptr = nullptr, *d_idx = nullptr; double *d_val = nullptr, *d_val2 = nullptr, *d_part = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc(&d_wptr, sizeof(int32_t) * (nwin + 1));
+    if (e == hipSuccess) e = hipMalloc(&d_idx, sizeof(int32_t) * ne);
+    if (e == hipSuccess) e = hipMalloc(&d_val, sizeof(double) * ne);
+    if (e == hipSuccess && val2) e = hipMalloc(&d_val2, sizeof(double) * ne);
+    if (e == hipSuccess) e = hipMalloc(&d_part, sizeof(double) * nv * (size_t)nwin * nsl);
+    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * nv * (size_t)nwin);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_wptr, wptr, sizeof(int32_t) * (nwin + 1), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_idx, idx, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_val, val, sizeof(double) * nnz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz && val2) e = hipMemcpyAsync(d_val2, val2, sizeof(double) * nnz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        if (val2) hipLaunchKernelGGL((jw64::k64_window_partial<5>), dim3((unsigned)nsl), dim3(256), 0, c->stream, M, ld, nwin, d_wptr, d_idx, d_val, d_val2, d_part);
+        else      hipLaunchKernelGGL((jw64::k64_window_partial<2>), dim3((unsigned)nsl), dim3(256), 0, c->stream, M, ld, nwin, d_wptr, d_idx, d_val, d_val2, d_part);
+        hipLaunchKernelGGL(k_window_reduce, dim3((unsigned)((nwin + 255) / 256)), dim3(256), 0, c->stream, nwin, nsl, nv, d_part, d_out);
+        e = hipGetLastError();
+    }
+    for (int v = 0; v < nv && e == hipSuccess; ++v)
+        e = hipMemcpyAsync(outs[v], d_out + (size_t)v * nwin, sizeof(double) * nwin, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_wptr); (void)hipFree(d_idx); (void)hipFree(d_val); (void)hipFree(d_val2); (void)hipFree(d_part); (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_window_sums_f64: %s", hipGetErrorString(e));
+    return JWAS_HIP_OK;
+}
+
 extern "C" {
 
 int jwas_hip_set_precision(jwas_hip_ctx* c, int32_t bits)
@@ -2474,6 +2573,8 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->w, (void*)F->ev_all}) (void)hipFree(q);
     F->X = F->r = F->xpx = F->gram = F->partials = F->w = nullptr; F->ev = F->ev_all = nullptr; F->dparams = nullptr;
     F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0;
+    for (void* q : {(void*)F->Xout, (void*)F->cmp_idx, (void*)F->cmp_val}) (void)hipFree(q);      // (sized by the old p)
+    F->Xout = nullptr; F->n_out = F->ld_out = 0; F->cmp_idx = nullptr; F->cmp_val = nullptr;
     (void)hipFree(c->counters); (void)hipFree(c->fin_out); (void)hipFree(c->stat_out); if (c->host_buf) (void)hipHostFree(c->host_buf);
     c->counters = nullptr; c->fin_out = c->stat_out = nullptr; c->host_buf = nullptr;
     c->method = -1; c->ntraits = 0; c->block_size = 0; c->nblocks = 0;
@@ -2570,22 +2671,90 @@ int jwas_hip_get_residual_f64(jwas_hip_ctx* c, int32_t trait, double* rh)
     return JWAS_HIP_OK;
 }
 
+// getEBV's X*alpha (output.jl:281-306) with T = Float64, over the nonzero effects only: the same fma chain in marker order as
+// k64_mul_alpha, hence the same bits.
 int jwas_hip_mul_alpha_f64(jwas_hip_ctx* c, int32_t trait, double* out)
 {
     NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
     ONLY_F64(c);
     NEED_TRAIT(c, trait);
-    auto* F = c->f64;
     HIPCHK(c, hipSetDevice(c->device));
-    double* tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, sizeof(double) * c->ld));
-    hipLaunchKernelGGL(jw64::k64_mul_alpha, dim3((unsigned)c->nslices), dim3(256), 0, c->stream, F->X, c->ld, c->p, F->alpha + (size_t)trait * c->p, tmp, 1.0,
-                       (const double*)nullptr);
-    hipError_t e = hipMemcpyAsync(out, tmp, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
-    HIPCHK(c, e);
+    return f64_mul_alpha_rows(c, trait, c->f64->X, c->ld, c->n, out, "jwas_hip_mul_alpha_f64");
+}
+
+// Mi.output_genotypes = Z_out * genotypes in Float64 (tools4genotypes.jl:290-296 after JWAS.jl:353): a second resident matrix
+// next to the training rows; a second call replaces it, jwas_hip_load_dense_f64 and jwas_hip_destroy free it.
+int jwas_hip_load_output_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n_out, int64_t p, int64_t ld_host)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    ONLY_F64(c);
+    NEED(c, Xh, JWAS_HIP_EINVAL, "X_out is NULL");
+    auto* F = c->f64;
+    NEED(c, F->X, JWAS_HIP_ESTATE, "no genotype matrix loaded");
+    NEED(c, n_out >= 1, JWAS_HIP_EINVAL, "n_out must be >= 1 (got %lld)", (long long)n_out);
+    NEED(c, p == c->p, JWAS_HIP_EINVAL, "output genotypes have %lld markers, the training matrix %lld", (long long)p, (long long)c->p);
+    NEED(c, ld_host >= n_out, JWAS_HIP_EINVAL, "ld_host (%lld) must be >= n_out (%lld)", (long long)ld_host, (long long)n_out);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(F->Xout); F->Xout = nullptr; F->n_out = F->ld_out = 0;
+    const int64_t ld = round_up(n_out, kSliceRows);
+    HIPCHK(c, hipMalloc(&F->Xout, sizeof(double) * (size_t)ld * p));
+    F->n_out = n_out; F->ld_out = ld;
+    if (ld != n_out) HIPCHK(c, hipMemsetAsync(F->Xout, 0, sizeof(double) * (size_t)ld * p, c->stream));      // pad rows zero
+    HIPCHK(c, hipMemcpy2DAsync(F->Xout, sizeof(double) * ld, Xh, sizeof(double) * ld_host, sizeof(double) * n_out, (size_t)p,
+                               hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return JWAS_HIP_OK;
+}
+
+// EBV = output_genotypes * alpha for a saved sample (output.jl:281-306), T = Float64.
+int jwas_hip_mul_alpha_output_f64(jwas_hip_ctx* c, int32_t trait, double* out)
+{
+    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
+    ONLY_F64(c);
+    NEED_TRAIT(c, trait);
+    NEED(c, c->f64->Xout, JWAS_HIP_ESTATE, "jwas_hip_load_output_dense_f64 has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    return f64_mul_alpha_rows(c, trait, c->f64->Xout, c->f64->ld_out, c->f64->n_out, out, "jwas_hip_mul_alpha_output_f64");
+}
+
+// One saved marker-effect sample of a Float64 chain as a sparse record (output.jl:443-526 writes the dense text row).  idx / val:
+// caller arrays of `capacity` entries, marker order; *nnz_out is filled even when they are too short (grow and call again).
+int jwas_hip_get_alpha_sparse_f64(jwas_hip_ctx* c, int32_t trait, int64_t capacity, int32_t* idx, double* val, int64_t* nnz_out)
+{
+    NEED(c, c && nnz_out, JWAS_HIP_EINVAL, "NULL argument");
+    ONLY_F64(c);
+    NEED_TRAIT(c, trait);
+    HIPCHK(c, hipSetDevice(c->device));
+    int nnz = 0;
+    HIPCHK(c, f64_compact_alpha(c, trait, &nnz));
+    *nnz_out = nnz;
+    NEED(c, nnz <= capacity, JWAS_HIP_EINVAL, "%d nonzero effects do not fit the caller's %lld entries", nnz, (long long)capacity);
+    if (nnz > 0) {
+        NEED(c, idx && val, JWAS_HIP_EINVAL, "idx / val is NULL");
+        HIPCHK(c, hipMemcpyAsync(idx, c->f64->cmp_idx, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(val, c->f64->cmp_val, sizeof(double) * nnz, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return JWAS_HIP_OK;
+}
+
+// The window GWAS inner loop with T = Float64 (GWAS.jl:148,152-165: X*alpha in the element type of output_genotypes).
+int jwas_hip_window_sums_f64(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
+                             const double* val, double* out_sum, double* out_ss)
+{
+    double* outs[2] = {out_sum, out_ss};
+    return f64_window_sums_impl(c, use_output_rows, nwin, wptr, idx, val, nullptr, outs);
+}
+
+// ... and the window genetic covariance / correlation of two traits' samples (GWAS.jl:199-217).
+int jwas_hip_window_sums2_f64(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
+                              const double* val1, const double* val2, double* out_sum1, double* out_ss1, double* out_sum2,
+                              double* out_ss2, double* out_cross)
+{
+    NEED(c, c && val2, JWAS_HIP_EINVAL, "NULL argument");
+    double* outs[5] = {out_sum1, out_ss1, out_sum2, out_ss2, out_cross};
+    return f64_window_sums_impl(c, use_output_rows, nwin, wptr, idx, val1, val2, outs);
 }
 
 int jwas_hip_get_posterior_f64(jwas_hip_ctx* c, int32_t trait, double* ma, double* ma2, double* md)

@@ -389,13 +389,13 @@ class HipEngine:
         return out
 
     def alpha_sparse(self, trait=0):
-        """(idx int32, val float32): the nonzero effects of a trait in marker order, compacted on the device."""
+        """(idx int32, val float32 | float64): the nonzero effects of a trait in marker order, compacted on the device."""
         cap = getattr(self, "_sparse_cap", 4096)
         while True:
             idx = np.empty(cap, dtype=np.int32)
-            val = np.empty(cap, dtype=np.float32)
+            val = np.empty(cap, dtype=self.dtype)
             nnz = C.c_int64(0)
-            rc = self._L.jwas_hip_get_alpha_sparse(self._h, int(trait), cap, _ptr(idx), _ptr(val), C.byref(nnz))
+            rc = self._f("jwas_hip_get_alpha_sparse")(self._h, int(trait), cap, _ptr(idx), _ptr(val), C.byref(nnz))
             if rc == 0:
                 return idx[:nnz.value].copy(), val[:nnz.value].copy()
             if nnz.value > cap:                      # grow and retry
@@ -405,16 +405,16 @@ class HipEngine:
 
     def load_output_dense(self, X_out):
         """Rows EBVs are reported for when they differ from the training rows (Mi.output_genotypes,
-        tools4genotypes.jl:290-296).  X_out: n_out x p float32."""
+        tools4genotypes.jl:290-296).  X_out: n_out x p float32 (float64 in a Float64 context)."""
         X_out = np.asarray(X_out)
-        if X_out.dtype != np.float32:
-            raise TypeError("the HIP path stores Float32 genotypes (double_precision=false)")
+        if X_out.dtype != self.dtype:
+            raise TypeError(f"this engine stores {np.dtype(self.dtype).name} genotypes (double_precision={'true' if self.precision == 64 else 'false'})")
         if X_out.ndim != 2:
             raise ValueError("genotype matrix must be 2-D")
         if not X_out.flags.f_contiguous:
             X_out = np.asfortranarray(X_out)
         n_out, p = X_out.shape
-        self._chk(self._L.jwas_hip_load_output_dense_f32(self._h, _ptr(X_out), n_out, p, n_out))
+        self._chk((self._L.jwas_hip_load_output_dense_f64 if self.precision == 64 else self._L.jwas_hip_load_output_dense_f32)(self._h, _ptr(X_out), n_out, p, n_out))
         self.n_out = n_out
 
     def window_sums(self, wptr, idx, val, use_output_rows=False):
@@ -422,28 +422,28 @@ class HipEngine:
         description of the nonzero effects: window w = idx/val[wptr[w]:wptr[w+1]]."""
         wptr = np.ascontiguousarray(wptr, dtype=np.int32)
         idx = np.ascontiguousarray(idx, dtype=np.int32)
-        val = np.ascontiguousarray(val, dtype=np.float32)
+        val = np.ascontiguousarray(val, dtype=self.dtype)
         nwin = wptr.size - 1
         s, q = np.empty(nwin), np.empty(nwin)
-        self._chk(self._L.jwas_hip_window_sums(self._h, 1 if use_output_rows else 0, nwin, _ptr(wptr), _ptr(idx), _ptr(val), _ptr(s), _ptr(q)))
+        self._chk(self._f("jwas_hip_window_sums")(self._h, 1 if use_output_rows else 0, nwin, _ptr(wptr), _ptr(idx), _ptr(val), _ptr(s), _ptr(q)))
         return s, q
 
     def window_sums2(self, wptr, idx, val1, val2, use_output_rows=False):
         """Two effect vectors over the same markers: (sum1, ss1, sum2, ss2, cross) per window (GWAS.jl:199-217)."""
         wptr = np.ascontiguousarray(wptr, dtype=np.int32)
         idx = np.ascontiguousarray(idx, dtype=np.int32)
-        v1 = np.ascontiguousarray(val1, dtype=np.float32)
-        v2 = np.ascontiguousarray(val2, dtype=np.float32)
+        v1 = np.ascontiguousarray(val1, dtype=self.dtype)
+        v2 = np.ascontiguousarray(val2, dtype=self.dtype)
         nwin = wptr.size - 1
         outs = [np.empty(nwin) for _ in range(5)]
-        self._chk(self._L.jwas_hip_window_sums2(self._h, 1 if use_output_rows else 0, nwin, _ptr(wptr), _ptr(idx), _ptr(v1), _ptr(v2),
+        self._chk(self._f("jwas_hip_window_sums2")(self._h, 1 if use_output_rows else 0, nwin, _ptr(wptr), _ptr(idx), _ptr(v1), _ptr(v2),
                                                 *[_ptr(o) for o in outs]))
         return tuple(outs)
 
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""
-        out = np.empty(getattr(self, "n_out", 0), dtype=np.float32)
-        self._chk(self._L.jwas_hip_mul_alpha_output(self._h, int(trait), _ptr(out)))
+        out = np.empty(getattr(self, "n_out", 0), dtype=self.dtype)
+        self._chk(self._f("jwas_hip_mul_alpha_output")(self._h, int(trait), _ptr(out)))
         return out
 
     # -- the sweep -------------------------------------------------------------------------------

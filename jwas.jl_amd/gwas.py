@@ -7,7 +7,11 @@
 O(samples x n x p) over the same genotype matrix the sweep streams; here every sample is one launch over its nonzero effects
 only (`jwas_hip_window_sums`: sum and sum of squares of each window's genomic values, fp64), the windows and the summary
 statistics are assembled on the host exactly as the reference does; the window genetic covariance / correlation of two
-traits (`genetic_correlation=true`, GWAS.jl:199-237) uses `jwas_hip_window_sums2`.  Local EBVs stay on the reference."""
+traits (`genetic_correlation=true`, GWAS.jl:199-237) uses `jwas_hip_window_sums2`.  Local EBVs stay on the reference.
+
+`double_precision=True` (a device option next to `device`): the reference forms X*alpha in the element type of
+`output_genotypes` (GWAS.jl:148,212), Float64 after `runMCMC(double_precision=true)` (JWAS.jl:349-366); the genotypes are then
+loaded into a Float64 context and the effects passed as Float64 (`jwas_hip_window_sums_f64` / `_sums2_f64`)."""
 import os
 
 import numpy as np
@@ -62,7 +66,7 @@ def build_windows(chr_, pos, window_size_bp, sliding_window):
 
 
 def GWAS(*args, window_size="1 Mb", sliding_window=False, GWAS=True, threshold=0.001, genetic_correlation=False,
-         local_EBV=False, header=True, output_winVarProps=False, output_folder=".", device=0, _engine=None):
+         local_EBV=False, header=True, output_winVarProps=False, output_folder=".", device=0, double_precision=False, _engine=None):
     """GWAS(marker_effects_file; header) or GWAS(model | genotype matrix, map_file, marker_effects_file...; ...)."""
     import pandas as pd
     if len(args) == 1:
@@ -79,8 +83,9 @@ def GWAS(*args, window_size="1 Mb", sliding_window=False, GWAS=True, threshold=0
         if len(parts) != 2 or parts[1] != "Mb":
             raise ValueError('The format for window_size is "1 Mb".')
     # ---- the genotypes of the individuals the reference uses here: Mi.output_genotypes (GWAS.jl:148)
+    ftype = np.float64 if double_precision else np.float32
     if isinstance(mme, np.ndarray):
-        X, marker_ids = np.asarray(mme, dtype=np.float32), None
+        X, marker_ids = np.asarray(mme, dtype=ftype), None
     else:
         Mi = mme.M[0]
         rows = getattr(Mi, "output_rows", None)
@@ -113,8 +118,8 @@ def GWAS(*args, window_size="1 Mb", sliding_window=False, GWAS=True, threshold=0
     own = engine is None
     if own:
         from .engine import HipEngine
-        engine = HipEngine(device)
-    engine.load_dense(np.asfortranarray(X, dtype=np.float32))
+        engine = HipEngine(device, precision=64) if double_precision else HipEngine(device)
+    engine.load_dense(np.asfortranarray(X, dtype=ftype))
     n = X.shape[0]
     cs, ce = np.asarray(win["col_start"]), np.asarray(win["col_end"])
     out, props_out = [], []
@@ -125,7 +130,7 @@ def GWAS(*args, window_size="1 Mb", sliding_window=False, GWAS=True, threshold=0
             winVar = np.zeros((nsamples, nwin))
             winVarProps = np.zeros((nsamples, nwin))
             for i in range(nsamples):
-                a = samples[i].astype(np.float32)
+                a = samples[i].astype(ftype)
                 nz = np.flatnonzero(a)
                 # window 0 = all markers (genVar), then every window's own nonzero effects
                 lo, hi = np.searchsorted(nz, cs), np.searchsorted(nz, ce)
@@ -160,7 +165,7 @@ def GWAS(*args, window_size="1 Mb", sliding_window=False, GWAS=True, threshold=0
             nsamples = s1.shape[0]
             gcov, gcor = np.zeros((nsamples, nwin)), np.zeros((nsamples, nwin))
             for i in range(nsamples):
-                a1, a2 = s1[i].astype(np.float32), s2[i].astype(np.float32)
+                a1, a2 = s1[i].astype(ftype), s2[i].astype(ftype)
                 nz = np.flatnonzero((a1 != 0) | (a2 != 0))
                 lo, hi = np.searchsorted(nz, cs), np.searchsorted(nz, ce)
                 wptr = np.concatenate([[0], np.cumsum(hi - lo)]).astype(np.int32)

@@ -682,7 +682,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         if double_precision and mt_pervar:
             need += p * t * t * 8 * 2                              # Float64 multi-trait BayesA/B: the covariances and their inverses in double
         if outputEBV and not out_same:                             # Mi.output_genotypes: a second dense matrix (n_out x p)
-            need += 4 * ((len(out_rows) + 255) // 256 * 256) * p
+            need += (8 if double_precision else 4) * ((len(out_rows) + 255) // 256 * 256) * p
         engine = HipEngine(device, precision=64 if double_precision else 32)
         free = engine.device_info()["hbm_free"]
         if memory_guard != "off" and need > memory_guard_ratio * free:   # JWAS.jl:422-459 analogue for HBM
@@ -700,10 +700,11 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         engine.load_dense(np.asfortranarray(X, dtype=ftype))      # after alignment (tools4genotypes.jl:310-321); Float64 on request (JWAS.jl:353)
     X_out_host = None
     if outputEBV and not out_same:             # Mi.output_genotypes = Z_out * genotypes (tools4genotypes.jl:290-296)
-        if double_precision:                   # (the Float64 context has no second resident matrix: the EBV product runs on the host)
-            X_out_host = np.asarray(Mi.genotypes[out_rows, :], dtype=np.float64)
-        else:
-            engine.load_output_dense(np.asfortranarray(Mi.genotypes[out_rows, :]))
+        if double_precision and not (hasattr(engine, "load_output_dense") and hasattr(engine, "mul_alpha_output")):
+            X_out_host = np.asarray(Mi.genotypes[out_rows, :], dtype=np.float64)      # (an injected engine without output rows: the host forms the product)
+        else:                                  # a second resident matrix, Float64 in a Float64 run (JWAS.jl:353)
+            Xo = Mi.genotypes[out_rows, :]
+            engine.load_output_dense(np.asfortranarray(Xo, dtype=np.float64) if double_precision else np.asfortranarray(Xo))
     # A device-resident engine may come from an earlier run: its weights, Grams and block partition must be THIS run's.
     # set_weights(None) restores unit weights (and drops the resident Grams, which were X_b'R^-1 X_b); an explicit
     # partition left by the previous run is rebuilt as uniform blocks below.
@@ -1019,7 +1020,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 if Mi.estimatePi and f"pi_{name}" in files:
                     files[f"pi_{name}"].write(",".join(repr(float(v)) for v in np.atleast_1d(pi_t if mega else pi)) + "\n")
                 for kk, tr in enumerate(model.lhsVec):
-                    if hasattr(engine, "alpha_sparse") and not double_precision:
+                    if hasattr(engine, "alpha_sparse"):
                         si, sv = engine.alpha_sparse(kk)              # (idx, val) compacted on the device
                     else:
                         a_ = engine.get_state(kk)[0]

@@ -2,7 +2,12 @@
 doubles.  python scripts/f64_bench.py [n] [p] [--method M[,M...]] [--traits T[,T...]] [--sweeps K]
   --method BayesC (default; Float64 against Float32), or the multi-trait kinds, Float64 only:
            MT1 (BayesC, sampler I), MT2 (BayesC, sampler II), MTB1 / MTB2 (BayesB, sampler I / II: one covariance per marker,
-           redrawn on the device every sweep -- wall_ms includes that draw)"""
+           redrawn on the device every sweep -- wall_ms includes that draw)
+           outputs: the output side of a Float64 run, ms per saved sample and trait at ~1 % and at 100 % nonzero effects:
+           (a) the host product X_out @ alpha (numpy / BLAS on the cores this process may use), (b) k64_mul_alpha, the loop
+           over all p markers (reached through residual_sub_xalpha + a residual read-back of n doubles), (c) compact + list:
+           mul_alpha on the training matrix and mul_alpha_output on n/2 output rows; and the sample readout, sparse against
+           get_state + flatnonzero.  Medians of --reps calls after 3 warm-up calls, one process, one device."""
 import argparse
 import json
 import os
@@ -20,6 +25,7 @@ ap.add_argument("p", type=int, nargs="?", default=20000)
 ap.add_argument("--method", default="BayesC")
 ap.add_argument("--traits", default="2")
 ap.add_argument("--sweeps", type=int, default=20)
+ap.add_argument("--reps", type=int, default=11)
 args = ap.parse_args()
 n, p = args.n, args.p
 rng = np.random.default_rng(1)
@@ -66,7 +72,48 @@ def bench_mt(kind, t):
             "state_counts": [float(v) for v in st["state_counts"]]}
 
 
+def median_ms(fn, reps):
+    for _ in range(3):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter(); fn(); ts.append(1e3 * (time.perf_counter() - t0))
+    return float(np.median(ts)), float(min(ts)), float(max(ts))
+
+
+def bench_outputs():
+    rows = np.random.default_rng(5).permutation(n)[:n // 2]
+    X_out_host = np.asarray(X[rows, :], dtype=np.float64)          # what run_chain kept on the host before the output rows were resident
+    e = J.HipEngine(0, precision=64)
+    e.load_dense(X)
+    e.init_state("BayesC", 1)
+    res = {"n_out": int(rows.size), "reps": args.reps, "blas_threads": os.environ.get("OMP_NUM_THREADS", "unset")}
+    e.load_output_dense(X_out_host)
+    rng_a = np.random.default_rng(11)
+    for tag, nnz in (("1pct", max(1, p // 100)), ("100pct", p)):
+        a = np.zeros(p)
+        a[rng_a.choice(p, nnz, replace=False)] = rng_a.standard_normal(nnz) * 0.01
+        e.set_state(alpha=a)
+        r = {"nnz": nnz}
+        r["a_host_product_ms"] = median_ms(lambda: X_out_host @ e.get_state()[0], args.reps)
+        e.set_residual(np.zeros(n))
+        r["b_all_markers_loop_ms"] = median_ms(lambda: (e.sub_xalpha(), e.get_residual()), args.reps)
+        r["c_list_training_ms"] = median_ms(lambda: e.mul_alpha(), args.reps)
+        r["c_list_output_ms"] = median_ms(lambda: e.mul_alpha_output(), args.reps)
+        r["sparse_readout_ms"] = median_ms(lambda: e.alpha_sparse(), args.reps)
+        assert np.array_equal(e.mul_alpha_output(), e.mul_alpha()[rows])
+        r["dense_readout_ms"] = median_ms(lambda: np.flatnonzero(e.get_state()[0]), args.reps)
+        res[tag] = r
+        print(json.dumps({tag: r}), flush=True)
+    e.close()
+    return res
+
+
 out = {}
+if args.method == "outputs":
+    X = np.asfortranarray(X)
+    print(json.dumps({"n": n, "p": p, "outputs [median, min, max] ms": bench_outputs()}))
+    sys.exit(0)
 if args.method != "BayesC":
     X = np.asfortranarray(X)
     for kind in args.method.split(","):
