@@ -28,6 +28,8 @@
  *                              (output.jl:281-306; default output_ID = all genotyped individuals,
  *                              input_data_validation.jl:150-154)
  *   jwas_hip_window_sums       window genomic variances of a marker-effect sample (src/3.GWAS/src/GWAS.jl:152-165)
+ *   jwas_hip_gwas_begin / _sample / _local_ebv / _end
+ *                              the same over a resident session, plus the local EBVs (src/3.GWAS/src/GWAS.jl:149-173)
  *
  * Conventions: every entry point returns 0 on success and a negative JWAS_HIP_E* code on failure
  * (no exceptions cross the boundary; jwas_hip_last_error() returns the message -- the analogue of
@@ -317,6 +319,35 @@ int  jwas_hip_window_sums2(jwas_hip_ctx* ctx, int32_t use_output_rows, int32_t n
                            const float* val1, const float* val2, double* out_sum1, double* out_ss1, double* out_sum2,
                            double* out_ss2, double* out_cross);
 
+/* ---- GWAS session: window variances and local EBVs of the saved samples, resident on the device -------------------
+ * src/3.GWAS/src/GWAS.jl:149-173.  jwas_hip_gwas_begin uploads the windows once: window w is the column range
+ * [col_start[w], col_end[w]) exactly as the host's build_windows returns them (sliding windows overlap).  Every device
+ * buffer of the session is allocated here (the sample list grows on demand), never per sample.  local_ebv != 0: the
+ * session also holds an n_rows x nwin Float64 accumulator and a sample counter, both zeroed; n_rows = the training rows,
+ * or the rows of jwas_hip_load_output_dense_f32 / _f64 when use_output_rows != 0.  Dense Float32, 2-bit packed storage or
+ * a Float64 context.  A second begin restarts the session; loading genotypes ends it. */
+int  jwas_hip_gwas_begin(jwas_hip_ctx* ctx, int32_t use_output_rows, int32_t nwin, const int32_t* col_start, const int32_t* col_end,
+                         int32_t local_ebv);
+/* ONE saved sample (GWAS.jl:149-173) as the strictly ascending (idx, val) list of its nonzero effects -- a .bin record of
+ * the sample files, or what jwas_hip_get_alpha_sparse returns; the library finds every window's slice of the list.
+ * out_sum / out_ss hold nwin + 1 entries: entry 0 is "all markers" (genVar, GWAS.jl:155), entry 1 + w window w; they are
+ * bit-identical to jwas_hip_window_sums on the CSR description of the same sample.  A session with local EBVs also adds
+ * BV_w[i] = sum_j X[i, j] alpha_j of every window to its accumulator.  JWAS_HIP_EUNSUP on a Float64 context (use the
+ * _f64 twin). */
+int  jwas_hip_gwas_sample(jwas_hip_ctx* ctx, int32_t nnz, const int32_t* idx, const float* val, double* out_sum, double* out_ss);
+/* The local EBVs (GWAS.jl:149-173, :164: the mean of BV_w over the samples): out[w * n_rows + i], window-major, the mean
+ * over the *nsamples samples folded so far (zeros before the first). */
+int  jwas_hip_gwas_local_ebv(jwas_hip_ctx* ctx, double* out, int64_t* nsamples);
+/* Launch geometry of the session's partial kernel (GWAS.jl:149-173 has no counterpart; diagnostics): grid = nslices x
+ * nchunks workgroups; chunk 0 is entry 0, every other chunk holds windows_per_chunk = max(1, cld(nwin * nslices, 2048))
+ * windows. */
+int  jwas_hip_gwas_geometry(jwas_hip_ctx* ctx, int32_t* nslices, int32_t* windows_per_chunk, int32_t* nchunks);
+/* Free the session (GWAS.jl:149-173: after the last sample); jwas_hip_destroy does it too. */
+int  jwas_hip_gwas_end(jwas_hip_ctx* ctx);
+/* Device bytes of a session (GWAS.jl:149-173: localEBV is n x nwin), a pure function like jwas_hip_estimate_bytes: rows
+ * padded to 256; local_ebv adds exactly 8 * padded_rows * nwin. */
+int64_t jwas_hip_gwas_estimate_bytes(int64_t n_rows, int64_t nwin, int64_t max_nnz, int32_t local_ebv);
+
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the
  * sweep's stream (0 = off); the sums come back in jwas_sweep_stats.update_kernel_*. */
@@ -421,6 +452,9 @@ int  jwas_hip_window_sums_f64(jwas_hip_ctx* ctx, int32_t use_output_rows, int32_
 int  jwas_hip_window_sums2_f64(jwas_hip_ctx* ctx, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
                                const double* val1, const double* val2, double* out_sum1, double* out_ss1, double* out_sum2,
                                double* out_ss2, double* out_cross);
+/* jwas_hip_gwas_sample with T = Float64 (GWAS.jl:148-173): double effects over a Float64 context's matrices; bit-identical to
+ * jwas_hip_window_sums_f64.  JWAS_HIP_ESTATE on a Float32 context. */
+int  jwas_hip_gwas_sample_f64(jwas_hip_ctx* ctx, int32_t nnz, const int32_t* idx, const double* val, double* out_sum, double* out_ss);
 int  jwas_hip_get_posterior_f64(jwas_hip_ctx* ctx, int32_t trait, double* mean_alpha, double* mean_alpha2, double* mean_delta);
 int  jwas_hip_set_marker_covariances_f64(jwas_hip_ctx* ctx, const double* p_t_t);   /* p x t x t row-major */
 int  jwas_hip_get_marker_covariances_f64(jwas_hip_ctx* ctx, double* out_p_t_t);

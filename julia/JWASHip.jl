@@ -153,6 +153,34 @@ hip_window_sums2_f64!(b::HipBackend, use_output_rows::Bool, wptr::Vector{Int32},
                             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                            b.ctx, use_output_rows, length(wptr) - 1, wptr, idx, val1, val2, outs...))
 
+"GWAS session (GWAS.jl:149-173): window variances and local EBVs of the saved samples with everything resident.  `hip_gwas_begin!`
+uploads the windows (0-based column ranges [col_start, col_end), as the host's build_windows returns them) once; a sample then goes
+in as the ascending 0-based (idx, val) list of its nonzero effects and comes back as (sum, sum of squares) of nwin + 1 entries
+(entry 1 = all markers, entry 1 + w = window w; the bits of jwas_hip_window_sums); `hip_gwas_local_ebv` returns the n_rows x nwin
+mean of the windows' genomic values over the samples fed so far."
+hip_gwas_begin!(b::HipBackend, col_start::Vector{Int32}, col_end::Vector{Int32}; use_output_rows::Bool=false, local_ebv::Bool=false) =
+    hip_check(b.ctx, ccall((:jwas_hip_gwas_begin, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Int32),
+                           b.ctx, use_output_rows, length(col_start), col_start, col_end, local_ebv))
+hip_gwas_sample!(b::HipBackend, idx::Vector{Int32}, val::Vector{Float32}, out_sum::Vector{Float64}, out_ss::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_gwas_sample, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Float64}, Ptr{Float64}),
+                           b.ctx, length(idx), idx, val, out_sum, out_ss))
+hip_gwas_sample!(b::HipBackend, idx::Vector{Int32}, val::Vector{Float64}, out_sum::Vector{Float64}, out_ss::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_gwas_sample_f64, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                           b.ctx, length(idx), idx, val, out_sum, out_ss))
+function hip_gwas_local_ebv(b::HipBackend, n_rows::Integer, nwin::Integer)
+    out, ns = Matrix{Float64}(undef, n_rows, nwin), Ref{Int64}(0)       # window-major = a column per window
+    hip_check(b.ctx, ccall((:jwas_hip_gwas_local_ebv, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{Int64}), b.ctx, out, ns))
+    return out, ns[]
+end
+function hip_gwas_geometry(b::HipBackend)
+    nsl, wpc, nch = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    hip_check(b.ctx, ccall((:jwas_hip_gwas_geometry, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}), b.ctx, nsl, wpc, nch))
+    return (nslices = nsl[], windows_per_chunk = wpc[], nchunks = nch[])
+end
+hip_gwas_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_gwas_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+hip_gwas_estimate_bytes(n_rows::Integer, nwin::Integer, max_nnz::Integer, local_ebv::Bool) =
+    ccall((:jwas_hip_gwas_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int64, Int32), n_rows, nwin, max_nnz, local_ebv)
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

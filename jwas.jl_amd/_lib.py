@@ -38,6 +38,8 @@ SYMBOLS = [
     "jwas_hip_setup_groups", "jwas_hip_set_marker_covariances_f64", "jwas_hip_get_marker_covariances_f64",
     "jwas_hip_load_output_dense_f64", "jwas_hip_mul_alpha_output_f64", "jwas_hip_get_alpha_sparse_f64",
     "jwas_hip_window_sums_f64", "jwas_hip_window_sums2_f64",
+    "jwas_hip_gwas_begin", "jwas_hip_gwas_sample", "jwas_hip_gwas_sample_f64", "jwas_hip_gwas_local_ebv", "jwas_hip_gwas_geometry",
+    "jwas_hip_gwas_end", "jwas_hip_gwas_estimate_bytes",
 ]
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
 
@@ -163,6 +165,14 @@ def load():
     L.jwas_hip_get_alpha_sparse_f64.argtypes = [vp, i32, i64, vp, vp, C.POINTER(i64)]
     L.jwas_hip_window_sums_f64.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.jwas_hip_window_sums2_f64.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.jwas_hip_gwas_begin.argtypes = [vp, i32, i32, vp, vp, i32]
+    L.jwas_hip_gwas_sample.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.jwas_hip_gwas_sample_f64.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.jwas_hip_gwas_local_ebv.argtypes = [vp, vp, C.POINTER(i64)]
+    L.jwas_hip_gwas_geometry.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.jwas_hip_gwas_end.argtypes = [vp]
+    L.jwas_hip_gwas_estimate_bytes.argtypes = [i64, i64, i64, i32]
+    L.jwas_hip_gwas_estimate_bytes.restype = i64
     L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_accumulate.argtypes = [vp, C.c_double]
@@ -186,7 +196,7 @@ def load():
     L.jwas_hip_estimate_bytes_storage.restype = i64
     for name in SYMBOLS:
         fn = getattr(L, name)
-        if name not in ("jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_estimate_bytes", "jwas_hip_estimate_bytes_storage"):
+        if name not in ("jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_estimate_bytes", "jwas_hip_estimate_bytes_storage", "jwas_hip_gwas_estimate_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -839,4 +839,44 @@ __global__ __launch_bounds__(256) void k64_window_partial(const double* __restri
         __syncthreads();
     }
 }
+
+// The GWAS session's partial kernel (kernels.hpp: k_gwas_partial) with T = Float64 (GWAS.jl:149-173): grid = (ld / 256 slices,
+// entry chunks), block = 256; chunk 0 is entry 0 ("all markers"), chunk 1 + k the windows [k wpc, (k + 1) wpc); entry e owns the
+// slice [lo[e], hi[e]) of the sample's ascending (idx, val) list.  16 / 4 / 1 column loads in flight, added in list order by
+// list_terms64's fma chain, then k64_window_partial's reduction: the bits of jwas_hip_window_sums_f64.  LEBV: the running sum
+// of the local EBVs, acc[w * ld + row] += BV_w[row].
+template <bool LEBV>
+__global__ __launch_bounds__(256) void k64_gwas_partial(const double* __restrict__ X, int64_t ld, int nent, int wpc, const int32_t* __restrict__ lo,
+                                                        const int32_t* __restrict__ hi, const int32_t* __restrict__ idx, const double* __restrict__ val,
+                                                        double* __restrict__ partial, double* __restrict__ acc)
+{
+    __shared__ double red[2][4];
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double* Xrow = X + row;
+    const int w0 = blockIdx.y == 0 ? 0 : 1 + ((int)blockIdx.y - 1) * wpc;
+    const int w1 = blockIdx.y == 0 ? 1 : (w0 + wpc < nent ? w0 + wpc : nent);
+    for (int w = w0; w < w1; ++w) {
+        double bv = 0.0, unused = 0.0;
+        const int e_lo = lo[w], e_hi = hi[w];
+        int e = e_lo;
+        for (; e + 16 <= e_hi; e += 16) list_terms64<16, 2>(Xrow, ld, idx, val, nullptr, e, bv, unused);
+        for (; e + 4 <= e_hi; e += 4) list_terms64<4, 2>(Xrow, ld, idx, val, nullptr, e, bv, unused);
+        for (; e < e_hi; ++e) list_terms64<1, 2>(Xrow, ld, idx, val, nullptr, e, bv, unused);
+        if constexpr (LEBV) { if (w >= 1 && e_hi > e_lo) acc[(int64_t)(w - 1) * ld + row] += bv; }
+        double v[2];
+        v[0] = bv; v[1] = bv * bv;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
+            if (lane == 0) red[k][wave] = v[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < 2)
+            partial[((int64_t)w * gridDim.x + blockIdx.x) * 2 + threadIdx.x] =
+                ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+        __syncthreads();
+    }
+}
 }  // namespace jw64

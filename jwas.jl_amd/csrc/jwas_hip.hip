@@ -151,6 +151,20 @@ struct jwas_hip_ctx {
         double* cmp_val = nullptr;          // [p]
     };
     F64* f64 = nullptr;
+    // GWAS session (jwas_hip_gwas_begin .. jwas_hip_gwas_end; GWAS.jl:149-173): everything a saved sample needs stays resident
+    struct Gwas {
+        bool active = false, local_ebv = false, out_rows = false;
+        int nwin = 0, wpc = 1, nchunks = 0, nsl = 0;       // launch geometry: grid = (nsl, nchunks), wpc windows per chunk
+        int64_t n_rows = 0, ld = 0, nsamples = 0;
+        const void* mat = nullptr;                          // the matrix the session was begun on (a reload ends the session)
+        int32_t *cs = nullptr, *ce = nullptr;               // [nwin] column ranges
+        int32_t *lo = nullptr, *hi = nullptr;               // [nwin + 1] the sample's list slice of every entry
+        int32_t* idx = nullptr; void* val = nullptr;        // [cap] the sample's nonzero effects (float | double)
+        int64_t cap = 0;
+        double *part = nullptr, *out = nullptr;             // [nwin + 1][nsl][2] slice partials, [2][nwin + 1] sums
+        double* acc = nullptr;                              // [nwin][ld] running sum of the local EBVs (window-major)
+        double* host_out = nullptr;                         // pinned [2][nwin + 1]
+    } gw;
 };
 
 static constexpr int kStatGrid = 128;
@@ -280,8 +294,17 @@ static void free_blocks(jwas_hip_ctx* c)
     c->ipartials = nullptr; c->ev_all = nullptr; c->ev_offs = nullptr; c->idx_all = nullptr; c->delta_all = nullptr; c->ind_traits = 0;
 }
 
+static void gwas_free(jwas_hip_ctx* c)
+{
+    auto& g = c->gw;
+    for (void* q : {(void*)g.cs, (void*)g.ce, (void*)g.lo, (void*)g.hi, (void*)g.idx, g.val, (void*)g.part, (void*)g.out, (void*)g.acc}) (void)hipFree(q);
+    if (g.host_out) (void)hipHostFree(g.host_out);
+    g = jwas_hip_ctx::Gwas();
+}
+
 static void free_storage(jwas_hip_ctx* c)
 {
+    gwas_free(c);                       // (a session is bound to the matrix it was begun on)
     (void)hipFree(c->X); (void)hipFree(c->r); (void)hipFree(c->Q); (void)hipFree(c->qmean); (void)hipFree(c->w);
     c->X = c->r = nullptr; c->Q = nullptr; c->qmean = nullptr; c->packed = false; c->w = nullptr; c->weighted = false;
     (void)hipFree(c->ev); (void)hipFree(c->dparams); (void)hipFree(c->counters); (void)hipFree(c->fin_out); (void)hipFree(c->stat_out); (void)hipFree(c->sync_cnt);
@@ -1259,6 +1282,7 @@ int jwas_hip_load_output_dense_f32(jwas_hip_ctx* c, const float* Xh, int64_t n_o
     NEED(c, ld_host >= n_out, JWAS_HIP_EINVAL, "ld_host (%lld) must be >= n_out (%lld)", (long long)ld_host, (long long)n_out);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->gw.out_rows) gwas_free(c);
     (void)hipFree(c->Xout); c->Xout = nullptr; c->n_out = c->ld_out = 0;
     const int64_t ld = (n_out + kSliceRows - 1) / kSliceRows * kSliceRows;
     HIPCHK(c, hipMalloc(&c->Xout, (size_t)4 * ld * p));
@@ -1363,6 +1387,205 @@ int jwas_hip_window_sums2(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin
     NEED(c, c && val2, JWAS_HIP_EINVAL, "NULL argument");
     double* outs[5] = {out_sum1, out_ss1, out_sum2, out_ss2, out_cross};
     return window_sums_impl(c, use_output_rows, nwin, wptr, idx, val1, val2, outs);
+}
+
+// ---- the GWAS session (src/3.GWAS/src/GWAS.jl:149-173) ---------------------------------------------------------------
+// Window variances AND local EBVs of the saved samples with everything resident: the window ranges are uploaded once, a
+// sample arrives as its (idx, val) list (no per-window duplicates), no allocation per sample.
+static constexpr int kGwasTargetWG = 2048;      // 256 CUs x 8 workgroups of 4 waves: every SIMD's 8 wave slots
+
+static int64_t gwas_windows_per_chunk(int64_t nwin, int64_t nsl)
+{
+    const int64_t wpc = (nwin * nsl + kGwasTargetWG - 1) / kGwasTargetWG;
+    return wpc < 1 ? 1 : wpc;
+}
+
+int64_t jwas_hip_gwas_estimate_bytes(int64_t n_rows, int64_t nwin, int64_t max_nnz, int32_t local_ebv)
+{
+    if (n_rows < 1 || nwin < 1 || max_nnz < 0) return 0;
+    const int64_t ld = round_up(n_rows, kSliceRows), nsl = ld / kSliceRows, nent = nwin + 1;
+    int64_t bytes = 2 * 4 * nwin + 2 * 4 * nent;                 // column ranges + list slices
+    bytes += (max_nnz > 0 ? max_nnz : 1) * (4 + 8);              // idx + val (double at most)
+    bytes += 2 * 8 * nent * nsl + 2 * 8 * nent;                  // slice partials + sums
+    if (local_ebv) bytes += 8 * ld * nwin;                       // the local-EBV accumulator
+    return bytes;
+}
+
+static const void* gwas_matrix(jwas_hip_ctx* c, bool out_rows, int64_t* n_rows, int64_t* ld)
+{
+    if (IS_F64(c)) {
+        auto* F = c->f64;
+        *n_rows = out_rows ? F->n_out : c->n; *ld = out_rows ? F->ld_out : c->ld;
+        return out_rows ? (const void*)F->Xout : (const void*)F->X;
+    }
+    *n_rows = out_rows ? c->n_out : c->n; *ld = out_rows ? c->ld_out : c->ld;
+    if (out_rows) return c->Xout;
+    return c->packed ? (const void*)c->Q : (const void*)c->X;
+}
+
+int jwas_hip_gwas_begin(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* col_start, const int32_t* col_end, int32_t local_ebv)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, col_start && col_end, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, nwin >= 1, JWAS_HIP_EINVAL, "nwin must be >= 1 (got %d)", nwin);
+    NEED(c, IS_F64(c) ? c->f64->X != nullptr : HAVE_STORAGE(c), JWAS_HIP_ESTATE, "no genotype matrix loaded");
+    NEED(c, !use_output_rows || (IS_F64(c) ? c->f64->Xout != nullptr : c->Xout != nullptr), JWAS_HIP_ESTATE,
+         "%s has not been called", IS_F64(c) ? "jwas_hip_load_output_dense_f64" : "jwas_hip_load_output_dense_f32");
+    for (int w = 0; w < nwin; ++w) {
+        NEED(c, col_start[w] <= col_end[w], JWAS_HIP_EINVAL, "window %d: col_start %d > col_end %d", w, col_start[w], col_end[w]);
+        NEED(c, col_start[w] >= 0 && col_end[w] <= c->p, JWAS_HIP_EINVAL, "window %d: columns [%d, %d) outside [0, %lld]", w, col_start[w], col_end[w], (long long)c->p);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    gwas_free(c);
+    auto& g = c->gw;
+    g.mat = gwas_matrix(c, use_output_rows != 0, &g.n_rows, &g.ld);
+    g.out_rows = use_output_rows != 0; g.local_ebv = local_ebv != 0; g.nwin = nwin;
+    g.nsl = (int)(g.ld / kSliceRows);
+    g.wpc = (int)gwas_windows_per_chunk(nwin, g.nsl);
+    g.nchunks = 1 + (nwin + g.wpc - 1) / g.wpc;
+    const size_t nent = (size_t)nwin + 1;
+    g.cap = 4096;
+    hipError_t e = g.local_ebv ? hipMalloc(&g.acc, 8 * (size_t)g.ld * nwin) : hipSuccess;      // the largest first: refuse early
+    if (e == hipSuccess) e = hipMalloc(&g.cs, 4 * (size_t)nwin);
+    if (e == hipSuccess) e = hipMalloc(&g.ce, 4 * (size_t)nwin);
+    if (e == hipSuccess) e = hipMalloc(&g.lo, 4 * nent);
+    if (e == hipSuccess) e = hipMalloc(&g.hi, 4 * nent);
+    if (e == hipSuccess) e = hipMalloc(&g.idx, 4 * (size_t)g.cap);
+    if (e == hipSuccess) e = hipMalloc(&g.val, 8 * (size_t)g.cap);
+    if (e == hipSuccess) e = hipMalloc(&g.part, 16 * nent * (size_t)g.nsl);
+    if (e == hipSuccess) e = hipMalloc(&g.out, 16 * nent);
+    if (e == hipSuccess) e = hipHostMalloc(&g.host_out, 16 * nent);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        const int64_t rows = g.n_rows, ldr = g.ld;
+        gwas_free(c);
+        return fail(c, JWAS_HIP_ENOMEM, "jwas_hip_gwas_begin: %s (the session needs %.3f GB, %lld rows x %d windows x 8 bytes of it for the local EBVs)",
+                    hipGetErrorString(e), jwas_hip_gwas_estimate_bytes(rows, nwin, 4096, local_ebv) / 1e9, (long long)(local_ebv ? ldr : 0), nwin);
+    }
+    e = hipMemcpyAsync(g.cs, col_start, 4 * (size_t)nwin, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g.ce, col_end, 4 * (size_t)nwin, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && g.local_ebv) e = hipMemsetAsync(g.acc, 0, 8 * (size_t)g.ld * nwin, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { gwas_free(c); return fail(c, JWAS_HIP_EHIP, "jwas_hip_gwas_begin: %s", hipGetErrorString(e)); }
+    g.active = true;
+    return JWAS_HIP_OK;
+}
+
+static int gwas_sample_impl(jwas_hip_ctx* c, int32_t nnz, const int32_t* idx, const void* val, bool is64, double* out_sum, double* out_ss)
+{
+    auto& g = c->gw;
+    NEED(c, out_sum && out_ss, JWAS_HIP_EINVAL, "NULL output array");
+    NEED(c, nnz >= 0, JWAS_HIP_EINVAL, "nnz must be >= 0 (got %d)", nnz);
+    NEED(c, nnz == 0 || (idx && val), JWAS_HIP_EINVAL, "idx / val is NULL");
+    NEED(c, g.active, JWAS_HIP_ESTATE, "jwas_hip_gwas_begin has not been called");
+    int64_t n_rows = 0, ld = 0;
+    NEED(c, gwas_matrix(c, g.out_rows, &n_rows, &ld) == g.mat && ld == g.ld && n_rows == g.n_rows, JWAS_HIP_ESTATE,
+         "the genotypes were reloaded after jwas_hip_gwas_begin");
+    for (int32_t e = 0; e < nnz; ++e) {
+        NEED(c, idx[e] >= 0 && idx[e] < c->p, JWAS_HIP_EINVAL, "marker index %d out of range", idx[e]);
+        NEED(c, e == 0 || idx[e] > idx[e - 1], JWAS_HIP_EINVAL, "idx must be strictly ascending (entry %d: %d after %d)", e, idx[e], idx[e - 1]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (nnz > g.cap) {                                          // grow on demand (rare: a denser sample than any before)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        int64_t cap = g.cap;
+        while (cap < nnz) cap *= 2;
+        if (cap > c->p) cap = c->p;
+        int32_t* ni = nullptr; void* nv = nullptr;
+        hipError_t ea = hipMalloc(&ni, 4 * (size_t)cap);
+        if (ea == hipSuccess) ea = hipMalloc(&nv, 8 * (size_t)cap);
+        if (ea != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(ni); (void)hipFree(nv);
+            return fail(c, JWAS_HIP_ENOMEM, "jwas_hip_gwas_sample: %s (a list of %lld effects)", hipGetErrorString(ea), (long long)cap);
+        }
+        (void)hipFree(g.idx); (void)hipFree(g.val);
+        g.idx = ni; g.val = nv; g.cap = cap;
+    }
+    const int nent = g.nwin + 1;
+    const size_t vsz = is64 ? 8 : 4;
+    hipError_t e = hipSuccess;
+    if (nnz) e = hipMemcpyAsync(g.idx, idx, 4 * (size_t)nnz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(g.val, val, vsz * (size_t)nnz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_gwas_slices, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, c->stream, nent, (int)nnz, g.cs, g.ce, g.idx, g.lo, g.hi);
+        const dim3 grid((unsigned)g.nsl, (unsigned)g.nchunks);
+        if (is64) {
+            const double* M = (const double*)g.mat;
+            if (g.local_ebv) hipLaunchKernelGGL((jw64::k64_gwas_partial<true>), grid, dim3(256), 0, c->stream, M, g.ld, nent, g.wpc, g.lo, g.hi, g.idx, (const double*)g.val, g.part, g.acc);
+            else             hipLaunchKernelGGL((jw64::k64_gwas_partial<false>), grid, dim3(256), 0, c->stream, M, g.ld, nent, g.wpc, g.lo, g.hi, g.idx, (const double*)g.val, g.part, g.acc);
+        } else {
+            auto launch = [&](auto cx) {
+                if (g.local_ebv) hipLaunchKernelGGL((k_gwas_partial<decltype(cx), true>), grid, dim3(256), 0, c->stream, cx, nent, g.wpc, g.lo, g.hi, g.idx, (const float*)g.val, g.part, g.acc, g.ld);
+                else             hipLaunchKernelGGL((k_gwas_partial<decltype(cx), false>), grid, dim3(256), 0, c->stream, cx, nent, g.wpc, g.lo, g.hi, g.idx, (const float*)g.val, g.part, g.acc, g.ld);
+                return 0;
+            };
+            if (g.out_rows) launch(DenseCols{c->Xout, c->ld_out, nullptr, 0});
+            else with_cols(c, 0, launch);
+        }
+        hipLaunchKernelGGL(k_window_reduce, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, c->stream, nent, g.nsl, 2, g.part, g.out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(g.host_out, g.out, 16 * (size_t)nent, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_gwas_sample: %s", hipGetErrorString(e));
+    std::memcpy(out_sum, g.host_out, 8 * (size_t)nent);
+    std::memcpy(out_ss, g.host_out + nent, 8 * (size_t)nent);
+    g.nsamples += 1;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_gwas_sample(jwas_hip_ctx* c, int32_t nnz, const int32_t* idx, const float* val, double* out_sum, double* out_ss)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NOT_F64(c, "jwas_hip_gwas_sample (use jwas_hip_gwas_sample_f64)");
+    return gwas_sample_impl(c, nnz, idx, val, false, out_sum, out_ss);
+}
+
+int jwas_hip_gwas_sample_f64(jwas_hip_ctx* c, int32_t nnz, const int32_t* idx, const double* val, double* out_sum, double* out_ss)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    ONLY_F64(c);
+    return gwas_sample_impl(c, nnz, idx, val, true, out_sum, out_ss);
+}
+
+int jwas_hip_gwas_local_ebv(jwas_hip_ctx* c, double* out, int64_t* nsamples)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, out && nsamples, JWAS_HIP_EINVAL, "NULL argument");
+    auto& g = c->gw;
+    NEED(c, g.active, JWAS_HIP_ESTATE, "jwas_hip_gwas_begin has not been called");
+    NEED(c, g.local_ebv, JWAS_HIP_ESTATE, "the session was begun without local_ebv");
+    HIPCHK(c, hipSetDevice(c->device));
+    // window-major rows [0, n_rows) of every window's padded column; the padding rows stay on the device
+    HIPCHK(c, hipMemcpy2DAsync(out, 8 * (size_t)g.n_rows, g.acc, 8 * (size_t)g.ld, 8 * (size_t)g.n_rows, (size_t)g.nwin, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *nsamples = g.nsamples;
+    if (g.nsamples > 0) {
+        const double s = (double)g.nsamples;
+        const int64_t cnt = g.n_rows * g.nwin;
+        for (int64_t i = 0; i < cnt; ++i) out[i] /= s;
+    }
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_gwas_geometry(jwas_hip_ctx* c, int32_t* nslices, int32_t* windows_per_chunk, int32_t* nchunks)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, c->gw.active, JWAS_HIP_ESTATE, "jwas_hip_gwas_begin has not been called");
+    if (nslices) *nslices = c->gw.nsl;
+    if (windows_per_chunk) *windows_per_chunk = c->gw.wpc;
+    if (nchunks) *nchunks = c->gw.nchunks;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_gwas_end(jwas_hip_ctx* c)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    gwas_free(c);
+    return JWAS_HIP_OK;
 }
 
 }  // extern "C" (templates need C++ linkage)
@@ -2570,6 +2793,7 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     f64_free_state(c);
+    gwas_free(c);
     for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->w, (void*)F->ev_all}) (void)hipFree(q);
     F->X = F->r = F->xpx = F->gram = F->partials = F->w = nullptr; F->ev = F->ev_all = nullptr; F->dparams = nullptr;
     F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0;
@@ -2696,6 +2920,7 @@ int jwas_hip_load_output_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n_
     NEED(c, ld_host >= n_out, JWAS_HIP_EINVAL, "ld_host (%lld) must be >= n_out (%lld)", (long long)ld_host, (long long)n_out);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->gw.out_rows) gwas_free(c);
     (void)hipFree(F->Xout); F->Xout = nullptr; F->n_out = F->ld_out = 0;
     const int64_t ld = round_up(n_out, kSliceRows);
     HIPCHK(c, hipMalloc(&F->Xout, sizeof(double) * (size_t)ld * p));

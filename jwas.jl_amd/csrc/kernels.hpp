@@ -1226,6 +1226,81 @@ JW_PLAIN_KERNEL __global__ __launch_bounds__(256) void k_window_reduce(int nwin,
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The GWAS session (jwas_hip_gwas_begin / _sample / _local_ebv; GWAS.jl:149-173): one saved sample is ONE ascending
+// (idx, val) list; entry 0 of the session is "all markers" (genVar, GWAS.jl:155), entry 1 + w is window w = the
+// columns [cs[w], ce[w]).
+// k_gwas_slices: the slice [lo, hi) of the list that falls into every entry (lower bounds, numpy's searchsorted).
+// grid = cld(nent, 256), block = 256.
+// ---------------------------------------------------------------------------------------------
+JW_PLAIN_KERNEL __global__ __launch_bounds__(256) void k_gwas_slices(int nent, int nnz, const int32_t* __restrict__ cs, const int32_t* __restrict__ ce,
+                                                     const int32_t* __restrict__ idx, int32_t* __restrict__ lo, int32_t* __restrict__ hi)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nent) return;
+    if (t == 0) { lo[0] = 0; hi[0] = nnz; return; }
+    auto lower = [&](int32_t key) {
+        int a = 0, b = nnz;
+        while (a < b) { const int m = (a + b) >> 1; if (idx[m] < key) a = m + 1; else b = m; }
+        return a;
+    };
+    lo[t] = lower(cs[t - 1]);
+    hi[t] = lower(ce[t - 1]);
+}
+
+// K column loads of one row in flight, then their fma chain in list order: k_window_partial's term, bit for bit.
+template <int K, class CX>
+__device__ __forceinline__ void gwas_terms(const CX& cx, int64_t row, const int32_t* __restrict__ idx, const float* __restrict__ val, int e, double& acc)
+{
+    float x[K];
+#pragma unroll
+    for (int u = 0; u < K; ++u) x[u] = cx.load1(idx[e + u], row);
+#pragma unroll
+    for (int u = 0; u < K; ++u) acc = fma((double)val[e + u], (double)x[u], acc);
+}
+
+// k_gwas_partial: k_window_partial over a grid of row slices x entry chunks.  grid = (nslices, nchunks), block = 256 (one
+// individual per thread, so a column load is one coalesced 1 KB instruction per wave); chunk 0 is entry 0 alone (its list is
+// as long as all disjoint windows together), chunk 1 + k holds the windows [k wpc, (k + 1) wpc).  A thread keeps 16 / 4 / 1
+// column loads of an entry's list in flight and adds them in list order; the slice's (sum, sum of squares) are reduced as in
+// k_window_partial (wave shuffle tree, ((0 + 1) + 2) + 3) into partial[(entry * nslices + slice) * 2 + {0, 1}] and the slices
+// are added by k_window_reduce: the same bits as jwas_hip_window_sums.  LEBV: acc[w * ld_acc + row] += BV_w[row], the running
+// SUM of the local EBVs (GWAS.jl:159-164; divided by the sample count on read-out); one owner per element, no atomics; an
+// entry without a nonzero effect in this sample adds 0 and is skipped.
+template <class CX, bool LEBV>
+__global__ __launch_bounds__(256) void k_gwas_partial(CX cx, int nent, int wpc, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
+                                                      const int32_t* __restrict__ idx, const float* __restrict__ val,
+                                                      double* __restrict__ partial, double* __restrict__ acc, int64_t ld_acc)
+{
+    __shared__ double red[2][4];
+    const int64_t row = (int64_t)blockIdx.x * kSliceRows + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int w0 = blockIdx.y == 0 ? 0 : 1 + ((int)blockIdx.y - 1) * wpc;
+    const int w1 = blockIdx.y == 0 ? 1 : (w0 + wpc < nent ? w0 + wpc : nent);
+    for (int w = w0; w < w1; ++w) {
+        double bv = 0.0;
+        const int e_lo = lo[w], e_hi = hi[w];
+        int e = e_lo;
+        for (; e + 16 <= e_hi; e += 16) gwas_terms<16>(cx, row, idx, val, e, bv);
+        for (; e + 4 <= e_hi; e += 4) gwas_terms<4>(cx, row, idx, val, e, bv);
+        for (; e < e_hi; ++e) gwas_terms<1>(cx, row, idx, val, e, bv);
+        if constexpr (LEBV) { if (w >= 1 && e_hi > e_lo) acc[(int64_t)(w - 1) * ld_acc + row] += bv; }
+        double v[2];
+        v[0] = bv; v[1] = bv * bv;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
+            if (lane == 0) red[k][wave] = v[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < 2)
+            partial[((int64_t)w * gridDim.x + blockIdx.x) * 2 + threadIdx.x] =
+                ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+        __syncthreads();
+    }
+}
+
 // X * alpha over the nonzero effects only (marker order, the same fp64 accumulation as k_mul_alpha -> identical
 // results): with a sparse prior a saved sample has a few hundred nonzero effects among 600 000, and the loop over all
 // markers (one scalar load + branch each) costs 39 ms where the 600 useful columns cost 30 us.

@@ -440,6 +440,53 @@ class HipEngine:
                                                 *[_ptr(o) for o in outs]))
         return tuple(outs)
 
+    # -- GWAS session (jwas_hip_gwas_*; GWAS.jl:149-173) -------------------------------------------
+    @staticmethod
+    def gwas_estimate_bytes(n_rows, nwin, max_nnz, local_ebv=False):
+        """Device bytes of a session: rows padded to 256; local_ebv adds 8 * padded_rows * nwin."""
+        return _lib.load().jwas_hip_gwas_estimate_bytes(int(n_rows), int(nwin), int(max_nnz), 1 if local_ebv else 0)
+
+    def gwas_begin(self, col_start, col_end, local_ebv=False, use_output_rows=False):
+        """Open a session over the windows [col_start[w], col_end[w]) (gwas.build_windows); everything stays resident until
+        gwas_end.  local_ebv: keep the n_rows x nwin accumulator of the windows' genomic values (GWAS.jl:159-164)."""
+        cs = np.ascontiguousarray(col_start, dtype=np.int32)
+        ce = np.ascontiguousarray(col_end, dtype=np.int32)
+        if cs.shape != ce.shape or cs.ndim != 1:
+            raise ValueError("col_start and col_end must be vectors of one length")
+        self._chk(self._L.jwas_hip_gwas_begin(self._h, 1 if use_output_rows else 0, cs.size, _ptr(cs), _ptr(ce), 1 if local_ebv else 0))
+        self._gwas_nwin = cs.size
+        self._gwas_rows = getattr(self, "n_out", 0) if use_output_rows else self.n
+
+    def gwas_sample(self, idx, val):
+        """One saved sample as the ascending (idx, val) list of its nonzero effects -> (sum, ss), nwin + 1 entries each:
+        entry 0 = all markers, entry 1 + w = window w (the bits of window_sums)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=self.dtype)
+        if idx.shape != val.shape or idx.ndim != 1:
+            raise ValueError("idx and val must be vectors of one length")
+        nent = getattr(self, "_gwas_nwin", 0) + 1
+        s, q = np.empty(nent), np.empty(nent)
+        self._chk(self._f("jwas_hip_gwas_sample")(self._h, idx.size, _ptr(idx), _ptr(val), _ptr(s), _ptr(q)))
+        return s, q
+
+    def gwas_local_ebv(self):
+        """(n_rows x nwin Float64 mean of the windows' genomic values over the samples folded so far, number of samples)."""
+        nwin, rows = getattr(self, "_gwas_nwin", 0), getattr(self, "_gwas_rows", 0)
+        out = np.empty((max(nwin, 1), max(rows, 1)))
+        ns = C.c_int64(0)
+        self._chk(self._L.jwas_hip_gwas_local_ebv(self._h, _ptr(out), C.byref(ns)))
+        return out[:nwin, :rows].T, ns.value
+
+    def gwas_geometry(self):
+        """Launch geometry of the session's partial kernel: grid = nslices x nchunks, windows_per_chunk windows per chunk."""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(self._L.jwas_hip_gwas_geometry(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"nslices": a.value, "windows_per_chunk": b.value, "nchunks": c.value}
+
+    def gwas_end(self):
+        self._chk(self._L.jwas_hip_gwas_end(self._h))
+        self._gwas_nwin = self._gwas_rows = 0
+
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""
         out = np.empty(getattr(self, "n_out", 0), dtype=self.dtype)

@@ -7,7 +7,13 @@
 O(samples x n x p) over the same genotype matrix the sweep streams; here every sample is one launch over its nonzero effects
 only (`jwas_hip_window_sums`: sum and sum of squares of each window's genomic values, fp64), the windows and the summary
 statistics are assembled on the host exactly as the reference does; the window genetic covariance / correlation of two
-traits (`genetic_correlation=true`, GWAS.jl:199-237) uses `jwas_hip_window_sums2`.  Local EBVs stay on the reference.
+traits (`genetic_correlation=true`, GWAS.jl:199-237) uses `jwas_hip_window_sums2`.
+
+`local_EBV=True` (GWAS.jl:149-173): the per-individual genomic value of every window, averaged over the saved samples, written
+to `localEBV<i>.txt`.  The samples then go through a resident GWAS session (`jwas_hip_gwas_begin / _sample / _local_ebv`): the
+windows are uploaded once, every sample arrives as the ascending list of its nonzero effects (a `.bin` file record by record,
+never as a dense samples x p matrix) and the n x nwin Float64 accumulator lives on the device.  The session's window sums have
+the bits of `jwas_hip_window_sums`, so the table and `MCMC_samples_local_genomic_variance<i>.txt` do not depend on the flag.
 
 `double_precision=True` (a device option next to `device`): the reference forms X*alpha in the element type of
 `output_genotypes` (GWAS.jl:148,212), Float64 after `runMCMC(double_precision=true)` (JWAS.jl:349-366); the genotypes are then
@@ -25,6 +31,26 @@ def _read_samples(path, header=True):
     tab = pd.read_csv(path, header=0 if header else None)
     ids = [str(c) for c in tab.columns] if header else list(range(1, tab.shape[1] + 1))
     return tab.to_numpy(dtype=np.float64), ids
+
+
+def _iter_sparse(path, ftype):
+    """One saved sample after the other as the ascending (idx int32, val ftype) list of its nonzero effects.  A binary file is
+    read record by record; a text file as `_read_samples` reads it, every row compacted."""
+    if str(path).endswith(".bin"):
+        from .samples import iter_records
+        for idx, val in iter_records(path):
+            val = val.astype(ftype)
+            keep = val != 0
+            yield np.ascontiguousarray(idx[keep], dtype=np.int32), np.ascontiguousarray(val[keep])
+        return
+    samples, _ = _read_samples(path, True)
+    for i in range(samples.shape[0]):
+        a = samples[i].astype(ftype)
+        nz = np.flatnonzero(a)
+        yield nz.astype(np.int32), a[nz]
+
+
+_SESSION_METHODS = ("gwas_begin", "gwas_sample", "gwas_local_ebv", "gwas_end", "gwas_estimate_bytes", "device_info")
 
 
 def model_frequency(marker_effects_file, header=True):
@@ -74,8 +100,6 @@ def GWAS(*args, window_size="1 Mb", sliding_window=False, GWAS=True, threshold=0
     if len(args) < 3:
         raise TypeError("GWAS(model, map_file, marker_effects_file...)")
     mme, map_file, files = args[0], args[1], list(args[2:])
-    if local_EBV:
-        raise NotImplementedError("local_EBV stays on the reference")
     if genetic_correlation and len(files) != 2:
         raise ValueError("genetic_correlation=true needs exactly two marker_effects_files (one per trait).")
     if isinstance(window_size, str):
@@ -86,11 +110,13 @@ def GWAS(*args, window_size="1 Mb", sliding_window=False, GWAS=True, threshold=0
     ftype = np.float64 if double_precision else np.float32
     if isinstance(mme, np.ndarray):
         X, marker_ids = np.asarray(mme, dtype=ftype), None
+        row_ids = [str(i) for i in range(1, X.shape[0] + 1)]       # (the reference needs a model here: an array has no output_ID)
     else:
         Mi = mme.M[0]
         rows = getattr(Mi, "output_rows", None)
         X = Mi.genotypes if rows is None else Mi.genotypes[rows, :]
         marker_ids = list(Mi.markerID)
+        row_ids = [str(v) for v in (Mi.obsID if rows is None else np.asarray(Mi.obsID, dtype=object)[rows])]
     nmarkers = X.shape[1]
     if map_file is False and isinstance(window_size, (int, np.integer)):
         print(f"The map file is not provided. A fake map file is generated with {window_size} markers in each 1 Mb window.")
@@ -119,29 +145,61 @@ def GWAS(*args, window_size="1 Mb", sliding_window=False, GWAS=True, threshold=0
     if own:
         from .engine import HipEngine
         engine = HipEngine(device, precision=64) if double_precision else HipEngine(device)
+    local_EBV = bool(local_EBV) and GWAS                      # (ignored without the window GWAS, as in the reference)
+    if local_EBV:
+        missing = [m for m in _SESSION_METHODS if not hasattr(engine, m)]
+        if missing:
+            raise TypeError("local_EBV=true needs an engine with the GWAS session (" + ", ".join(missing) + " missing); "
+                            "the package has no CPU fallback")
     engine.load_dense(np.asfortranarray(X, dtype=ftype))
     n = X.shape[0]
     cs, ce = np.asarray(win["col_start"]), np.asarray(win["col_end"])
     out, props_out = [], []
     try:
         for fi, path in enumerate(files if GWAS else [], start=1):
-            samples, _ = _read_samples(path, True)
-            nsamples = samples.shape[0]
-            winVar = np.zeros((nsamples, nwin))
-            winVarProps = np.zeros((nsamples, nwin))
-            for i in range(nsamples):
-                a = samples[i].astype(ftype)
-                nz = np.flatnonzero(a)
-                # window 0 = all markers (genVar), then every window's own nonzero effects
-                lo, hi = np.searchsorted(nz, cs), np.searchsorted(nz, ce)
-                counts = hi - lo
-                wptr = np.concatenate([[0, nz.size], nz.size + np.cumsum(counts)]).astype(np.int32)
-                gather = np.concatenate([nz] + [nz[l:h] for l, h in zip(lo, hi) if h > l]) if nz.size else nz
-                s, q = engine.window_sums(wptr, gather, a[gather])
-                var = (q - s * s / n) / (n - 1)                  # var(BV) = sample variance (GWAS.jl:153,158)
-                winVar[i] = var[1:]
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    winVarProps[i] = var[1:] / var[0]
+            if local_EBV:
+                # GWAS.jl:149-173 on a resident session: windows uploaded once, one (idx, val) list per sample
+                need = engine.gwas_estimate_bytes(n, nwin, nmarkers, True)
+                free = engine.device_info()["hbm_free"]
+                if need > 0.8 * free:
+                    raise MemoryError(f"local_EBV=true needs {need / 1e9:.3f} GB on the device, {n} x {nwin} x 8 = {n * nwin * 8} bytes of it for "
+                                      f"the local EBVs of {nwin} windows, but only {free / 1e9:.3f} GB of HBM is free")
+                engine.gwas_begin(cs, ce, local_ebv=True)
+                try:
+                    rows_var, rows_prop = [], []
+                    for nz, val in _iter_sparse(path, ftype):
+                        s, q = engine.gwas_sample(nz, val)
+                        var = (q - s * s / n) / (n - 1)              # var(BV) = sample variance (GWAS.jl:153,158)
+                        rows_var.append(var[1:])
+                        with np.errstate(divide="ignore", invalid="ignore"):
+                            rows_prop.append(var[1:] / var[0])
+                    lebv, _ = engine.gwas_local_ebv()
+                finally:
+                    engine.gwas_end()
+                nsamples = len(rows_var)
+                winVar = np.array(rows_var).reshape(nsamples, nwin)
+                winVarProps = np.array(rows_prop).reshape(nsamples, nwin)
+                ltab = pd.DataFrame(np.asarray(lebv, dtype=np.float64), columns=[f"w{w}" for w in range(1, nwin + 1)])
+                ltab.insert(0, "ID", row_ids)
+                ltab.to_csv(os.path.join(output_folder, f"localEBV{fi}.txt"), index=False)     # GWAS.jl:169-173
+            else:
+                samples, _ = _read_samples(path, True)
+                nsamples = samples.shape[0]
+                winVar = np.zeros((nsamples, nwin))
+                winVarProps = np.zeros((nsamples, nwin))
+                for i in range(nsamples):
+                    a = samples[i].astype(ftype)
+                    nz = np.flatnonzero(a)
+                    # window 0 = all markers (genVar), then every window's own nonzero effects
+                    lo, hi = np.searchsorted(nz, cs), np.searchsorted(nz, ce)
+                    counts = hi - lo
+                    wptr = np.concatenate([[0, nz.size], nz.size + np.cumsum(counts)]).astype(np.int32)
+                    gather = np.concatenate([nz] + [nz[l:h] for l, h in zip(lo, hi) if h > l]) if nz.size else nz
+                    s, q = engine.window_sums(wptr, gather, a[gather])
+                    var = (q - s * s / n) / (n - 1)                  # var(BV) = sample variance (GWAS.jl:153,158)
+                    winVar[i] = var[1:]
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        winVarProps[i] = var[1:] / var[0]
             np.savetxt(os.path.join(output_folder, f"MCMC_samples_local_genomic_variance{fi}.txt"), winVar, delimiter=",")
             winVarProps[np.isnan(winVarProps)] = 0.0             # no marker in the model in that sample
             WPPA = (winVarProps > threshold).mean(axis=0)
