@@ -30,6 +30,8 @@
  *   jwas_hip_window_sums       window genomic variances of a marker-effect sample (src/3.GWAS/src/GWAS.jl:152-165)
  *   jwas_hip_gwas_begin / _sample / _local_ebv / _end
  *                              the same over a resident session, plus the local EBVs (src/3.GWAS/src/GWAS.jl:149-173)
+ *   jwas_hip_liability_*       sample_liabilities! and the threshold bounds of categorical / censored traits
+ *                              (categorical_and_censored_trait/categorical_and_censored_trait.jl:29-210)
  *
  * Conventions: every entry point returns 0 on success and a negative JWAS_HIP_E* code on failure
  * (no exceptions cross the boundary; jwas_hip_last_error() returns the message -- the analogue of
@@ -347,6 +349,60 @@ int  jwas_hip_gwas_end(jwas_hip_ctx* ctx);
 /* Device bytes of a session (GWAS.jl:149-173: localEBV is n x nwin), a pure function like jwas_hip_estimate_bytes: rows
  * padded to 256; local_ebv adds exactly 8 * padded_rows * nwin. */
 int64_t jwas_hip_gwas_estimate_bytes(int64_t n_rows, int64_t nwin, int64_t max_nnz, int32_t local_ebv);
+
+/* ---- threshold (binary / ordered categorical) and censored traits: the liabilities on the device ---------------------------
+ * categorical_and_censored_trait/categorical_and_censored_trait.jl, called from MCMC/MCMC_BayesianAlphabet.jl:186-191 BEFORE the
+ * location parameters.  The context owns, per trait, a kind (continuous / categorical / censored), the liability vector (n
+ * elements of the context's element type), the category codes and the threshold table (categorical), the bounds (censored).
+ * Everything works on the residual the context holds (jwas_hip_set_residual / _f64), whatever the genotype storage (dense
+ * Float32, 2-bit packed, a Float64 context); the state is freed by jwas_hip_liability_end, jwas_hip_destroy or loading genotypes.
+ * The truncated normals are ONE counter uniform per draw -- philox4x32_10(individual, iteration, 0x40000000 | Gibbs round,
+ * 2 + 16 * trait), no rejection loop -- so the same seed gives the same chain whatever the launch geometry.  Every entry point
+ * decides its errors before any launch: JWAS_HIP_ESTATE without a residual (jwas_hip_init_state) or before _begin,
+ * JWAS_HIP_EINVAL for codes outside 0..ncat, unsorted thresholds or lower > upper, JWAS_HIP_EUNSUP with a communicator attached
+ * (shards). */
+typedef struct jwas_liability_params {
+    uint32_t iteration;                 /* MCMC iteration (enters the RNG counter); jwas_hip_liability_init uses 0           */
+    int32_t  ngibbs;                    /* Gibbs rounds over the traits: 5 when >= 2 traits carry liabilities, else 1 (:184-188) */
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                  */
+    double   R[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];   /* residual covariance, row-major t x t (mme.R.val; 1 trait: R[0]) */
+} jwas_liability_params;
+/* Start (or restart) the liability state for the ntraits traits of jwas_hip_init_state: every trait continuous (:29-47). */
+int  jwas_hip_liability_begin(jwas_hip_ctx* ctx, int32_t ntraits);
+/* Trait `trait` is categorical (:50-70): codes[i] in 0..ncat (0 = missing: not truncated, :115-117), ncat = nthresholds - 1;
+ * thresholds = {-Inf, t1, ..., +Inf}, strictly increasing, 3 <= nthresholds <= 16.  Record i is bounded by
+ * [thresholds[code - 1], thresholds[code]] (:119-120).  The liability vector is set to the codes -- the placeholder phenotype
+ * the reference holds in mme.ySparse before the set-up draw (:54). */
+int  jwas_hip_liability_set_categorical(jwas_hip_ctx* ctx, int32_t trait, int64_t n, const int32_t* codes, int32_t nthresholds,
+                                        const double* thresholds);
+/* Trait `trait` is censored (:75-78): lower[i] <= upper[i], +-Inf allowed, lower == upper an exact record.  The liability vector
+ * is set to the placeholder add_censored_trait_column! would build (:263-296): upper if lower = -Inf, 0 if both are infinite,
+ * else lower. */
+int  jwas_hip_liability_set_censored(jwas_hip_ctx* ctx, int32_t trait, int64_t n, const double* lower, const double* upper);
+/* New thresholds of a categorical trait (:155,160), the count it was declared with. */
+int  jwas_hip_liability_set_thresholds(jwas_hip_ctx* ctx, int32_t trait, int32_t nthresholds, const double* thresholds);
+/* The set-up draw (:82-88).  The residual in the context must be y - cmean with y the placeholder CURRENTLY in the liability
+ * vector (jwas_hip_get_liabilities right after _set_*), so cmean = liability - residual.  Every liability trait k on its own
+ * (no conditioning, params->ngibbs ignored): liability = cmean + eps with eps ~ N(0, R[k][k]) truncated to
+ * [lower - cmean, upper - cmean], residual = eps; an exact record (lower == upper): liability = lower, residual = lower - cmean.
+ * Continuous traits are not touched.  jwas_hip_init_state zeroes the residual, so after it (and after _set_categorical /
+ * _set_censored) jwas_hip_liability_sample answers JWAS_HIP_ESTATE until the set-up draw has been repeated. */
+int  jwas_hip_liability_init(jwas_hip_ctx* ctx, const jwas_liability_params* params);
+/* sample_liabilities! (:166-210): ngibbs rounds over the liability traits k in order; cmean = liability - residual (:175);
+ * eps ~ N(R_12 R_22^-1 r_others, R_11 - R_12 R_22^-1 R_21) truncated to [lower - cmean, upper - cmean] (:196-202);
+ * liability = cmean + eps, residual = eps (:203-204); exact records are left alone (:201).  B = R_12 R_22^-1 and the conditional
+ * variance are formed once per call in double on the host.  Also leaves the per-category extremes jwas_hip_liability_minmax
+ * reads.  params->iteration >= 1.  Asynchronous (ordered on the context's stream). */
+int  jwas_hip_liability_sample(jwas_hip_ctx* ctx, const jwas_liability_params* params);
+/* For the thresholds i = 1 .. nthresholds - 2 of a categorical trait (:152-155): max_below[i] = the largest liability of
+ * category i, min_above[i] = the smallest of category i + 1 (records with code 0 take no part; an empty category gives
+ * -Inf / +Inf); entries 0 and nthresholds - 1 are -Inf and +Inf.  Both arrays hold nthresholds doubles.  Exact (max / min of
+ * the stored values). */
+int  jwas_hip_liability_minmax(jwas_hip_ctx* ctx, int32_t trait, double* max_below, double* min_above);
+/* The liabilities of a categorical or censored trait (mme.ySparse, output.jl:514-523) as n doubles: widened from Float32 in a
+ * Float32 context. */
+int  jwas_hip_get_liabilities(jwas_hip_ctx* ctx, int32_t trait, double* out_n);
+int  jwas_hip_liability_end(jwas_hip_ctx* ctx);
 
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the

@@ -181,6 +181,51 @@ hip_gwas_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_gwas_end, LIBJW
 hip_gwas_estimate_bytes(n_rows::Integer, nwin::Integer, max_nnz::Integer, local_ebv::Bool) =
     ccall((:jwas_hip_gwas_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int64, Int32), n_rows, nwin, max_nnz, local_ebv)
 
+"Threshold / censored traits (categorical_and_censored_trait.jl:29-210): the liabilities live on the device beside the residual.
+`hip_liability_begin!` after `jwas_hip_init_state`; `hip_liability_set_categorical!` (codes 1..ncat, 0 = missing; thresholds
+[-Inf, 0, ..., Inf]) or `hip_liability_set_censored!` per trait; upload the residual as placeholder - cmean with the placeholder
+`hip_get_liabilities` returns; `hip_liability_init!` is the set-up draw (:82-88), `hip_liability_sample!` replaces
+sample_liabilities! (:166-210), `hip_liability_minmax` gives the support of every threshold draw (:152-155), to be followed by
+`hip_liability_set_thresholds!` (:155,160)."
+struct HipLiabilityParams
+    iteration::UInt32
+    ngibbs::Int32
+    seed::UInt64
+    R::NTuple{16,Float64}
+end
+function HipLiabilityParams(iter::Integer, seed::Integer, ngibbs::Integer, R::AbstractMatrix)
+    Rt = Float64.(permutedims(R))                # row-major t x t, as the header asks
+    HipLiabilityParams(UInt32(iter), Int32(ngibbs), UInt64(seed), ntuple(i -> i <= length(Rt) ? Rt[i] : 0.0, 16))
+end
+HipLiabilityParams(iter::Integer, seed::Integer, ngibbs::Integer, R::Real) =      # single trait: mme.R.val is a scalar
+    HipLiabilityParams(iter, seed, ngibbs, fill(Float64(R), 1, 1))
+hip_liability_begin!(b::HipBackend, ntraits::Integer) =
+    hip_check(b.ctx, ccall((:jwas_hip_liability_begin, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32), b.ctx, ntraits))
+hip_liability_set_categorical!(b::HipBackend, trait::Integer, codes::Vector{Int32}, thresholds::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_liability_set_categorical, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Int32, Ptr{Float64}),
+                           b.ctx, trait - 1, length(codes), codes, length(thresholds), thresholds))
+hip_liability_set_censored!(b::HipBackend, trait::Integer, lower::Vector{Float64}, upper::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_liability_set_censored, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}),
+                           b.ctx, trait - 1, length(lower), lower, upper))
+hip_liability_set_thresholds!(b::HipBackend, trait::Integer, thresholds::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_liability_set_thresholds, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}),
+                           b.ctx, trait - 1, length(thresholds), thresholds))
+hip_liability_init!(b::HipBackend, P::HipLiabilityParams) =
+    hip_check(b.ctx, ccall((:jwas_hip_liability_init, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipLiabilityParams}), b.ctx, P))
+hip_liability_sample!(b::HipBackend, P::HipLiabilityParams) =
+    hip_check(b.ctx, ccall((:jwas_hip_liability_sample, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipLiabilityParams}), b.ctx, P))
+function hip_liability_minmax(b::HipBackend, trait::Integer, nthresholds::Integer)
+    mx = Vector{Float64}(undef, nthresholds); mn = Vector{Float64}(undef, nthresholds)
+    hip_check(b.ctx, ccall((:jwas_hip_liability_minmax, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), b.ctx, trait - 1, mx, mn))
+    return mx, mn
+end
+function hip_get_liabilities(b::HipBackend, trait::Integer)
+    out = Vector{Float64}(undef, b.nObs)
+    hip_check(b.ctx, ccall((:jwas_hip_get_liabilities, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), b.ctx, trait - 1, out))
+    return out
+end
+hip_liability_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_liability_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

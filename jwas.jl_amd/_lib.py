@@ -40,7 +40,11 @@ SYMBOLS = [
     "jwas_hip_window_sums_f64", "jwas_hip_window_sums2_f64",
     "jwas_hip_gwas_begin", "jwas_hip_gwas_sample", "jwas_hip_gwas_sample_f64", "jwas_hip_gwas_local_ebv", "jwas_hip_gwas_geometry",
     "jwas_hip_gwas_end", "jwas_hip_gwas_estimate_bytes",
+    "jwas_hip_liability_begin", "jwas_hip_liability_set_categorical", "jwas_hip_liability_set_censored",
+    "jwas_hip_liability_set_thresholds", "jwas_hip_liability_init", "jwas_hip_liability_sample", "jwas_hip_liability_minmax",
+    "jwas_hip_get_liabilities", "jwas_hip_liability_end",
 ]
+MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
 
 
@@ -79,6 +83,10 @@ class SweepStats(C.Structure):
         ("update_kernel_ms", C.c_double), ("update_kernel_samples", C.c_double), ("update_kernel_bytes", C.c_double),
         ("event_overhead_ms", C.c_double),
     ]
+
+
+class LiabilityParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("ngibbs", C.c_int32), ("seed", C.c_uint64), ("R", C.c_double * (MAX_TRAITS * MAX_TRAITS))]
 
 
 class JwasHipError(RuntimeError):
@@ -173,6 +181,15 @@ def load():
     L.jwas_hip_gwas_end.argtypes = [vp]
     L.jwas_hip_gwas_estimate_bytes.argtypes = [i64, i64, i64, i32]
     L.jwas_hip_gwas_estimate_bytes.restype = i64
+    L.jwas_hip_liability_begin.argtypes = [vp, i32]
+    L.jwas_hip_liability_set_categorical.argtypes = [vp, i32, i64, vp, i32, vp]
+    L.jwas_hip_liability_set_censored.argtypes = [vp, i32, i64, vp, vp]
+    L.jwas_hip_liability_set_thresholds.argtypes = [vp, i32, i32, vp]
+    L.jwas_hip_liability_init.argtypes = [vp, C.POINTER(LiabilityParams)]
+    L.jwas_hip_liability_sample.argtypes = [vp, C.POINTER(LiabilityParams)]
+    L.jwas_hip_liability_minmax.argtypes = [vp, i32, vp, vp]
+    L.jwas_hip_get_liabilities.argtypes = [vp, i32, vp]
+    L.jwas_hip_liability_end.argtypes = [vp]
     L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_accumulate.argtypes = [vp, C.c_double]

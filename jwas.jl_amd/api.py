@@ -9,9 +9,9 @@ Same names, argument meaning and error behaviour as reworkhow/JWAS.jl v2.3.6 (fi
     runMCMC         JWAS.jl:161-511  -> MCMC/MCMC_BayesianAlphabet.jl
 Everything that is NOT the marker sweep stays here on the host (numpy): data ingestion and QC,
 model parsing, fixed-effect Gibbs, variance-component and pi draws, output tables.  Model families
-outside the hot path (pedigree / random terms, GBLUP, RR-BLUP, BayesL, categorical / censored traits,
-SEM, RRM, single-step pre-processing, marker annotations) are rejected with an explicit error:
-they stay on the reference.
+outside the hot path (pedigree / random terms, GBLUP, SEM, RRM, single-step pre-processing) are rejected with an
+explicit error: they stay on the reference.  Categorical / censored traits run here: their liabilities are sampled
+on the device (mcmc.py step 0, csrc/liability.hpp).
 """
 import inspect
 import os
@@ -265,16 +265,22 @@ class Model:
         self.output = None
         self.output_ID = False                 # outputEBV(model, IDs); False = all genotyped individuals
         self.outputSamplesVec = []             # outputMCMCsamples(model, terms...): (trait, term) pairs
+        self.traits_type = ["continuous"] * len(traits)      # "censored" | "categorical" | "categorical(binary)" (types.jl:325)
+        self.thresholds = {}                   # trait index -> [-Inf, 0, ..., Inf] (types.jl:326)
 
 
 def build_model(model_equations, R=False, *, df=4.0, estimate_variance=True, estimate_scale=False,
-                constraint=False, genotypes=None, **unsupported):
+                constraint=False, genotypes=None, censored_trait=False, categorical_trait=False, **unsupported):
     """build_MME.jl:42-156.  Genotype terms are found the way the reference does it -- by looking the
     term name up among the caller's variables (build_MME.jl:88-120 reflects on Main) -- or through an
-    explicit `genotypes={"geno": obj}` mapping."""
+    explicit `genotypes={"geno": obj}` mapping.
+    censored_trait / categorical_trait: lists of trait names (build_MME.jl:47-48,146-152); a censored trait reads its bounds from
+    the phenotype columns <trait>_l / <trait>_u, a categorical trait is coded 1, 2, 3 ..."""
     for k in unsupported:
         raise NotImplementedError(f"build_model argument '{k}' (neural-network / censored / categorical models) "
                                   "stays on the reference path")
+    censored_trait = [] if _is_false(censored_trait) else ([censored_trait] if isinstance(censored_trait, str) else [str(v) for v in censored_trait])
+    categorical_trait = [] if _is_false(categorical_trait) else ([categorical_trait] if isinstance(categorical_trait, str) else [str(v) for v in categorical_trait])
     if not _is_false(R):                                                                      # :50-52
         Rm = np.atleast_2d(np.asarray(R, dtype=np.float64))
         ok = Rm.shape[0] == Rm.shape[1] and np.allclose(Rm, Rm.T)
@@ -285,6 +291,8 @@ def build_model(model_equations, R=False, *, df=4.0, estimate_variance=True, est
                 ok = False
         if not ok:
             raise ValueError("The covariance matrix is not positive definite.")
+        if Rm.shape[0] > 1:
+            R = (Rm + Rm.T) / 2                  # symmetric to allclose above: exactly symmetric from here on
     if not isinstance(model_equations, str) or model_equations.strip() == "":
         raise ValueError("Model equations are wrong.\n To find an example, type ?build_model and press enter.")   # :53-56
     if estimate_scale is not False:
@@ -295,6 +303,11 @@ def build_model(model_equations, R=False, *, df=4.0, estimate_variance=True, est
     if genotypes:
         scope.update(genotypes)
     eqs = [e.strip() for e in model_equations.replace("\n", ";").split(";") if e.strip()]
+    lhs_names = [e.split("=")[0].strip() for e in eqs]
+    for arg, names in (("categorical_trait", categorical_trait), ("censored_trait", censored_trait)):
+        unknown = [v for v in names if v not in lhs_names]
+        if unknown:
+            raise ValueError(f"{arg}: {unknown} not among the traits of the model {lhs_names}.")
     traits, terms, M = [], [], []
     for eq in eqs:
         lhs, rhs = [s.strip() for s in eq.split("=")]
@@ -338,7 +351,13 @@ def build_model(model_equations, R=False, *, df=4.0, estimate_variance=True, est
         Rv = False if _is_false(R) else np.asarray(R, dtype=np.float32)
         scale_R = False if _is_false(R) else np.asarray(R, dtype=np.float64) * (df - 1)
         df_R = df + nModels
-    return Model(model_equations, traits, terms, M, Variance(Rv, np.float32(df_R), scale_R, estimate_variance, estimate_scale, constraint))
+    model = Model(model_equations, traits, terms, M, Variance(Rv, np.float32(df_R), scale_R, estimate_variance, estimate_scale, constraint))
+    for k, tr in enumerate(traits):                                                           # :146-152
+        if tr in censored_trait:
+            model.traits_type[k] = "censored"
+        elif tr in categorical_trait:
+            model.traits_type[k] = "categorical"
+    return model
 
 
 def outputEBV(model, IDs):
@@ -389,6 +408,11 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     3 000 iterations on, 4 from 8 000), 0 / 2 / 4 = one / two / four 1024-marker blocks per launch of the step kernel in the
     sparse steady state of a single-trait chain (grouped launches) -- the same chain up to float32
     rounding of the block right-hand sides; the group cross-Grams are set-up work (8 / 24 KB per marker).
+
+    Categorical / censored traits (build_model(...; categorical_trait, censored_trait)): categories coded 1, 2, 3 ... (two of them
+    make a binary trait), bounds of a censored trait in the columns <trait>_l / <trait>_u; the liabilities are sampled on the
+    device before the location parameters of every iteration (mcmc.py step 0) and saved, with the thresholds, as
+    MCMC_samples_liabilities_<trait>.txt / MCMC_samples_threshold_<trait>.txt.  Every sampler, storage mode and precision.
 
     double_precision=True (JWAS.jl:349-366): genotypes, residual, effects and the samplers' arithmetic all Float64 -- a
     Float64 device context (jwas_hip_set_precision; csrc/f64_path.hpp): single-trait BayesA/B/C, RR-BLUP, BayesL, BayesR,

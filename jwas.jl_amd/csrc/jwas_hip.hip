@@ -4,6 +4,7 @@
 #include "sweep.hpp"
 #include "f64_path.hpp"
 #include "step_launch.hpp"
+#include "liability.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -165,6 +166,20 @@ struct jwas_hip_ctx {
         double* acc = nullptr;                              // [nwin][ld] running sum of the local EBVs (window-major)
         double* host_out = nullptr;                         // pinned [2][nwin + 1]
     } gw;
+    // Liability state of threshold / censored traits (jwas_hip_liability_begin .. _end; categorical_and_censored_trait.jl)
+    struct Liab {
+        bool active = false, inited = false;
+        int nt = 0, nparts = 0;
+        int kind[jwl::kMaxT] = {}, ncat[jwl::kMaxT] = {};
+        void* y[jwl::kMaxT] = {};                           // [ld] liabilities, the context's element type
+        int32_t* codes[jwl::kMaxT] = {};                    // [n] categories (0 = missing)
+        double *lower[jwl::kMaxT] = {}, *upper[jwl::kMaxT] = {};      // [n] bounds of a censored trait
+        double* thr = nullptr;                              // [kMaxT][kMaxThr] threshold tables (device) ...
+        double thr_host[jwl::kMaxT][jwl::kMaxThr] = {};     // ... and their host copy
+        double* part[jwl::kMaxT] = {};                      // [nparts][kMM] per-workgroup {max, min} of every category
+        bool part_valid[jwl::kMaxT] = {};                   // ... left by the last draw and still describing the liabilities
+        double* mm = nullptr;                               // [kMM] reduced
+    } lb;
 };
 
 static constexpr int kStatGrid = 128;
@@ -302,9 +317,19 @@ static void gwas_free(jwas_hip_ctx* c)
     g = jwas_hip_ctx::Gwas();
 }
 
+static void liab_free(jwas_hip_ctx* c)
+{
+    auto& b = c->lb;
+    for (int k = 0; k < jwl::kMaxT; ++k)
+        for (void* q : {b.y[k], (void*)b.codes[k], (void*)b.lower[k], (void*)b.upper[k], (void*)b.part[k]}) (void)hipFree(q);
+    (void)hipFree(b.thr); (void)hipFree(b.mm);
+    b = jwas_hip_ctx::Liab();
+}
+
 static void free_storage(jwas_hip_ctx* c)
 {
     gwas_free(c);                       // (a session is bound to the matrix it was begun on)
+    liab_free(c);                       // (the liabilities belong to the residual of this matrix)
     (void)hipFree(c->X); (void)hipFree(c->r); (void)hipFree(c->Q); (void)hipFree(c->qmean); (void)hipFree(c->w);
     c->X = c->r = nullptr; c->Q = nullptr; c->qmean = nullptr; c->packed = false; c->w = nullptr; c->weighted = false;
     (void)hipFree(c->ev); (void)hipFree(c->dparams); (void)hipFree(c->counters); (void)hipFree(c->fin_out); (void)hipFree(c->stat_out); (void)hipFree(c->sync_cnt);
@@ -323,7 +348,7 @@ void jwas_hip_destroy(jwas_hip_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     if (c->comm) (void)jwas_hip_comm_destroy(c);
-    free_state(c); free_blocks(c); free_storage(c);
+    free_state(c); free_blocks(c); free_storage(c);      // (free_storage: the GWAS session and the liabilities too)
     if (c->f64) {
         auto* F = c->f64;
         for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->alpha, (void*)F->beta, F->delta, (void*)F->mean_a,
@@ -1045,6 +1070,7 @@ int jwas_hip_init_state(jwas_hip_ctx* c, int32_t method, int32_t nt)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_state(c);
     c->method = method; c->ntraits = nt;
+    c->lb.inited = false;                          // (the residual is zeroed below: the liabilities no longer belong to it)
     const size_t fb = sizeof(float) * (size_t)nt * c->p;
     HIPCHK(c, hipMalloc(&c->alpha, fb));
     HIPCHK(c, hipMalloc(&c->beta, fb));
@@ -2446,6 +2472,7 @@ static int f64_init_state(jwas_hip_ctx* c, int32_t method, int32_t nt)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     f64_free_state(c);
     c->method = method; c->ntraits = nt;
+    c->lb.inited = false;                          // (the residual is zeroed below: the liabilities no longer belong to it)
     const size_t db = sizeof(double) * (size_t)nt * c->p;
     const size_t delb = method == JWAS_HIP_BAYESR ? sizeof(int32_t) * (size_t)c->p : db;
     HIPCHK(c, hipMalloc(&F->alpha, db)); HIPCHK(c, hipMalloc(&F->beta, db)); HIPCHK(c, hipMalloc(&F->delta, delb));
@@ -2794,6 +2821,7 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     HIPCHK(c, hipStreamSynchronize(c->stream));
     f64_free_state(c);
     gwas_free(c);
+    liab_free(c);
     for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->w, (void*)F->ev_all}) (void)hipFree(q);
     F->X = F->r = F->xpx = F->gram = F->partials = F->w = nullptr; F->ev = F->ev_all = nullptr; F->dparams = nullptr;
     F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0;
@@ -3289,6 +3317,285 @@ int jwas_hip_get_posterior(jwas_hip_ctx* c, int32_t trait, float* ma, float* ma2
     if (ma2) HIPCHK(c, hipMemcpyAsync(ma2, c->mean_a2 + off, nb, hipMemcpyDeviceToHost, c->stream));
     if (md) HIPCHK(c, hipMemcpyAsync(md, c->mean_d + off, nb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- threshold / censored traits: the liabilities (csrc/liability.hpp) -----------------------------------------------------
+static void* liab_residual(jwas_hip_ctx* c) { return IS_F64(c) ? (void*)c->f64->r : (void*)c->r; }
+
+#define NEED_LIAB(c)                                                                                                   \
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
+    NEED(c, c->lb.active, JWAS_HIP_ESTATE, "jwas_hip_liability_begin has not been called");                            \
+    NEED(c, liab_residual(c) && c->method >= 0 && c->ntraits == c->lb.nt, JWAS_HIP_ESTATE,                              \
+         "jwas_hip_init_state changed the number of traits after jwas_hip_liability_begin")
+#define NEED_LIAB_TRAIT(c, trait) NEED(c, trait >= 0 && trait < c->lb.nt, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->lb.nt)
+
+static int liab_check_thresholds(jwas_hip_ctx* c, int32_t nthr, const double* thr)
+{
+    NEED(c, thr, JWAS_HIP_EINVAL, "thresholds is NULL");
+    NEED(c, nthr >= 3 && nthr <= jwl::kMaxThr, JWAS_HIP_EINVAL, "nthresholds must be 3..%d, -Inf and +Inf included (got %d)", jwl::kMaxThr, nthr);
+    NEED(c, thr[0] == -INFINITY && thr[nthr - 1] == INFINITY, JWAS_HIP_EINVAL, "thresholds must start with -Inf and end with +Inf");
+    for (int i = 1; i < nthr; ++i)
+        NEED(c, thr[i] > thr[i - 1], JWAS_HIP_EINVAL, "thresholds must be strictly increasing (entry %d: %g after %g)", i, thr[i], thr[i - 1]);
+    return JWAS_HIP_OK;
+}
+
+// (re)allocate the liability vector of a trait and drop what an earlier declaration of it left
+static int liab_reset_trait(jwas_hip_ctx* c, int trait)
+{
+    auto& b = c->lb;
+    for (void* q : {(void*)b.codes[trait], (void*)b.lower[trait], (void*)b.upper[trait], (void*)b.part[trait]}) (void)hipFree(q);
+    b.codes[trait] = nullptr; b.lower[trait] = b.upper[trait] = nullptr; b.part[trait] = nullptr; b.part_valid[trait] = false;
+    b.kind[trait] = jwl::kContinuous; b.ncat[trait] = 0;
+    if (!b.y[trait]) HIPCHK(c, hipMalloc(&b.y[trait], (IS_F64(c) ? 8 : 4) * (size_t)c->ld));
+    return JWAS_HIP_OK;
+}
+
+static int liab_upload_placeholder(jwas_hip_ctx* c, int trait, const std::vector<double>& y0)
+{
+    auto& b = c->lb;
+    if (IS_F64(c)) {
+        HIPCHK(c, hipMemcpyAsync(b.y[trait], y0.data(), 8 * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {
+        std::vector<float> y32(y0.begin(), y0.end());
+        HIPCHK(c, hipMemcpyAsync(b.y[trait], y32.data(), 4 * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return JWAS_HIP_OK;
+}
+
+// n x n inverse (n <= 3) in double: Gauss-Jordan with partial pivoting, the operation sequence of inv_small
+static int inv_small_f64(const double* A, int n, double* Ainv)
+{
+    double M[kMaxT][2 * kMaxT];
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) { M[i][j] = A[i * n + j]; M[i][n + j] = (i == j); }
+    for (int col = 0; col < n; ++col) {
+        int piv = col;
+        for (int i = col + 1; i < n; ++i) if (std::fabs(M[i][col]) > std::fabs(M[piv][col])) piv = i;
+        if (M[piv][col] == 0.0) return -1;
+        if (piv != col) for (int j = 0; j < 2 * n; ++j) { double tmp = M[col][j]; M[col][j] = M[piv][j]; M[piv][j] = tmp; }
+        const double d = M[col][col];
+        for (int j = 0; j < 2 * n; ++j) M[col][j] /= d;
+        for (int i = 0; i < n; ++i) if (i != col) {
+            const double f = M[i][col];
+            if (f != 0.0) for (int j = 0; j < 2 * n; ++j) M[i][j] -= f * M[col][j];
+        }
+    }
+    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) Ainv[i * n + j] = M[i][n + j];
+    return 0;
+}
+
+template <class T>
+static void liab_launch(jwas_hip_ctx* c, const jwl::LiabArgs& A)
+{
+    const dim3 grid((unsigned)c->lb.nparts), block(256);
+    switch (c->lb.nt) {
+        case 1: hipLaunchKernelGGL((jwl::k_liability_sample<1, T>), grid, block, 0, c->stream, A); break;
+        case 2: hipLaunchKernelGGL((jwl::k_liability_sample<2, T>), grid, block, 0, c->stream, A); break;
+        case 3: hipLaunchKernelGGL((jwl::k_liability_sample<3, T>), grid, block, 0, c->stream, A); break;
+        default: hipLaunchKernelGGL((jwl::k_liability_sample<4, T>), grid, block, 0, c->stream, A); break;
+    }
+}
+
+static int liab_draw(jwas_hip_ctx* c, const jwas_liability_params* P, bool init, const char* who)
+{
+    NEED_LIAB(c);
+    NEED(c, P, JWAS_HIP_EINVAL, "params is NULL");
+    auto& b = c->lb;
+    const int t = b.nt;
+    NEED(c, init || b.inited, JWAS_HIP_ESTATE, "jwas_hip_liability_init has not been called");
+    NEED(c, init || P->iteration >= 1, JWAS_HIP_EINVAL, "%s: iteration must be >= 1 (0 is the set-up draw)", who);
+    NEED(c, init || (P->ngibbs >= 1 && P->ngibbs <= 1000), JWAS_HIP_EINVAL, "%s: ngibbs must be 1..1000 (got %d)", who, P->ngibbs);
+    int nliab = 0;
+    for (int k = 0; k < t; ++k) nliab += b.kind[k] != jwl::kContinuous;
+    NEED(c, nliab > 0, JWAS_HIP_ESTATE, "%s: no trait was declared categorical or censored", who);
+    jwl::LiabArgs A = {};
+    for (int k = 0; k < t; ++k) {
+        for (int j = 0; j < t; ++j)
+            NEED(c, std::isfinite(P->R[k * t + j]) && P->R[k * t + j] == P->R[j * t + k], JWAS_HIP_EINVAL, "%s: R must be finite and symmetric", who);
+        double var = P->R[k * t + k];
+        if (!init && t > 1) {                     // B = R_12 R_22^-1, s^2 = R_11 - R_12 R_22^-1 R_21 (:196-197), "2" = the other traits in order
+            double R22[9], R22i[9], R12[3];
+            int o[3], m = 0;
+            for (int j = 0; j < t; ++j) if (j != k) o[m++] = j;
+            for (int a = 0; a < m; ++a) { R12[a] = P->R[k * t + o[a]]; for (int e = 0; e < m; ++e) R22[a * m + e] = P->R[o[a] * t + o[e]]; }
+            NEED(c, inv_small_f64(R22, m, R22i) == 0, JWAS_HIP_EINVAL, "%s: R is singular", who);
+            for (int a = 0; a < m; ++a) {
+                double acc = 0.0;
+                for (int e = 0; e < m; ++e) acc += R12[e] * R22i[e * m + a];
+                A.B[k][o[a]] = acc;
+            }
+            for (int a = 0; a < m; ++a) var -= A.B[k][o[a]] * R12[a];
+        }
+        NEED(c, var > 0.0 && std::isfinite(var), JWAS_HIP_EINVAL, "%s: R is not positive definite (conditional variance of trait %d: %g)", who, k, var);
+        A.sd[k] = std::sqrt(var);
+    }
+    A.n = c->n; A.ld = c->ld; A.r = liab_residual(c); A.thr = b.thr;
+    for (int k = 0; k < t; ++k) {
+        A.kind[k] = b.kind[k]; A.ncat[k] = b.ncat[k];
+        A.y[k] = b.kind[k] != jwl::kContinuous ? b.y[k] : nullptr;
+        A.codes[k] = b.codes[k]; A.lower[k] = b.lower[k]; A.upper[k] = b.upper[k];
+        A.part[k] = b.kind[k] == jwl::kCategorical ? b.part[k] : nullptr;
+    }
+    A.ngibbs = init ? 1 : P->ngibbs; A.init = init ? 1 : 0;
+    A.iter = init ? 0u : P->iteration; A.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); A.seed_hi = (uint32_t)(P->seed >> 32);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (IS_F64(c)) liab_launch<double>(c, A); else liab_launch<float>(c, A);
+    HIPCHK(c, hipGetLastError());
+    for (int k = 0; k < t; ++k) b.part_valid[k] = A.part[k] != nullptr;
+    if (init) b.inited = true;
+    return JWAS_HIP_OK;
+}
+
+extern "C" {
+
+int jwas_hip_liability_begin(jwas_hip_ctx* c, int32_t ntraits)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no residual: load genotypes and call jwas_hip_init_state first");
+    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "liabilities are not driven from marker or row shards");
+    NEED(c, ntraits == c->ntraits, JWAS_HIP_EINVAL, "ntraits (%d) differs from jwas_hip_init_state's (%d)", ntraits, c->ntraits);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    liab_free(c);
+    auto& b = c->lb;
+    b.nt = ntraits;
+    b.nparts = (int)((c->n + 255) / 256);
+    HIPCHK(c, hipMalloc(&b.thr, sizeof(double) * jwl::kMaxT * jwl::kMaxThr));
+    HIPCHK(c, hipMalloc(&b.mm, sizeof(double) * jwl::kMM));
+    HIPCHK(c, hipMemset(b.thr, 0, sizeof(double) * jwl::kMaxT * jwl::kMaxThr));
+    b.active = true;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_liability_set_categorical(jwas_hip_ctx* c, int32_t trait, int64_t n, const int32_t* codes, int32_t nthr, const double* thr)
+{
+    NEED_LIAB(c);
+    NEED_LIAB_TRAIT(c, trait);
+    NEED(c, codes, JWAS_HIP_EINVAL, "codes is NULL");
+    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
+    if (int rc = liab_check_thresholds(c, nthr, thr)) return rc;
+    const int ncat = nthr - 1;
+    for (int64_t i = 0; i < n; ++i)
+        NEED(c, codes[i] >= 0 && codes[i] <= ncat, JWAS_HIP_EINVAL, "record %lld: category %d outside 0..%d", (long long)i, codes[i], ncat);
+    auto& b = c->lb;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = liab_reset_trait(c, trait)) return rc;
+    HIPCHK(c, hipMalloc(&b.codes[trait], 4 * (size_t)n));
+    HIPCHK(c, hipMalloc(&b.part[trait], sizeof(double) * (size_t)b.nparts * jwl::kMM));
+    HIPCHK(c, hipMemcpy(b.codes[trait], codes, 4 * (size_t)n, hipMemcpyHostToDevice));
+    std::memcpy(b.thr_host[trait], thr, sizeof(double) * nthr);
+    HIPCHK(c, hipMemcpy(b.thr + trait * jwl::kMaxThr, thr, sizeof(double) * nthr, hipMemcpyHostToDevice));
+    std::vector<double> y0((size_t)n);
+    for (int64_t i = 0; i < n; ++i) y0[(size_t)i] = (double)codes[i];
+    if (int rc = liab_upload_placeholder(c, trait, y0)) return rc;
+    b.kind[trait] = jwl::kCategorical; b.ncat[trait] = ncat; b.inited = false;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_liability_set_censored(jwas_hip_ctx* c, int32_t trait, int64_t n, const double* lower, const double* upper)
+{
+    NEED_LIAB(c);
+    NEED_LIAB_TRAIT(c, trait);
+    NEED(c, lower && upper, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
+    for (int64_t i = 0; i < n; ++i)
+        NEED(c, lower[i] <= upper[i] && lower[i] < INFINITY && upper[i] > -INFINITY, JWAS_HIP_EINVAL,
+             "record %lld: bounds [%g, %g] (lower > upper, NaN, or an infinite exact value)", (long long)i, lower[i], upper[i]);
+    auto& b = c->lb;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = liab_reset_trait(c, trait)) return rc;
+    HIPCHK(c, hipMalloc(&b.lower[trait], 8 * (size_t)n));
+    HIPCHK(c, hipMalloc(&b.upper[trait], 8 * (size_t)n));
+    HIPCHK(c, hipMemcpy(b.lower[trait], lower, 8 * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b.upper[trait], upper, 8 * (size_t)n, hipMemcpyHostToDevice));
+    std::vector<double> y0((size_t)n);
+    for (int64_t i = 0; i < n; ++i) y0[(size_t)i] = lower[i] == -INFINITY ? (upper[i] == INFINITY ? 0.0 : upper[i]) : lower[i];
+    if (int rc = liab_upload_placeholder(c, trait, y0)) return rc;
+    b.kind[trait] = jwl::kCensored; b.inited = false;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_liability_set_thresholds(jwas_hip_ctx* c, int32_t trait, int32_t nthr, const double* thr)
+{
+    NEED_LIAB(c);
+    NEED_LIAB_TRAIT(c, trait);
+    auto& b = c->lb;
+    NEED(c, b.kind[trait] == jwl::kCategorical, JWAS_HIP_ESTATE, "trait %d is not categorical", trait);
+    NEED(c, nthr == b.ncat[trait] + 1, JWAS_HIP_EINVAL, "trait %d has %d thresholds (got %d)", trait, b.ncat[trait] + 1, nthr);
+    if (int rc = liab_check_thresholds(c, nthr, thr)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::memcpy(b.thr_host[trait], thr, sizeof(double) * nthr);
+    // (from the context's own copy: the caller's array need not outlive the call)
+    HIPCHK(c, hipMemcpyAsync(b.thr + trait * jwl::kMaxThr, b.thr_host[trait], sizeof(double) * nthr, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_liability_init(jwas_hip_ctx* c, const jwas_liability_params* P) { return liab_draw(c, P, true, "jwas_hip_liability_init"); }
+
+int jwas_hip_liability_sample(jwas_hip_ctx* c, const jwas_liability_params* P) { return liab_draw(c, P, false, "jwas_hip_liability_sample"); }
+
+int jwas_hip_liability_minmax(jwas_hip_ctx* c, int32_t trait, double* max_below, double* min_above)
+{
+    NEED_LIAB(c);
+    NEED_LIAB_TRAIT(c, trait);
+    NEED(c, max_below && min_above, JWAS_HIP_EINVAL, "NULL argument");
+    auto& b = c->lb;
+    NEED(c, b.kind[trait] == jwl::kCategorical, JWAS_HIP_ESTATE, "trait %d is not categorical", trait);
+    const int ncat = b.ncat[trait];
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!b.part_valid[trait]) {
+        if (IS_F64(c)) hipLaunchKernelGGL((jwl::k_liability_minmax<double>), dim3((unsigned)b.nparts), dim3(256), 0, c->stream, (const double*)b.y[trait], b.codes[trait], c->n, ncat, b.part[trait]);
+        else           hipLaunchKernelGGL((jwl::k_liability_minmax<float>), dim3((unsigned)b.nparts), dim3(256), 0, c->stream, (const float*)b.y[trait], b.codes[trait], c->n, ncat, b.part[trait]);
+        b.part_valid[trait] = true;
+    }
+    hipLaunchKernelGGL(jwl::k_liability_minmax_reduce, dim3(1), dim3(256), 0, c->stream, b.part[trait], b.nparts, ncat, b.mm);
+    HIPCHK(c, hipGetLastError());
+    double mm[jwl::kMM];
+    HIPCHK(c, hipMemcpyAsync(mm, b.mm, sizeof(double) * 2 * ncat, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    max_below[0] = min_above[0] = -INFINITY;
+    max_below[ncat] = min_above[ncat] = INFINITY;
+    for (int i = 1; i < ncat; ++i) {                // threshold i separates categories i and i + 1
+        max_below[i] = mm[2 * (i - 1)];
+        min_above[i] = mm[2 * i + 1];
+    }
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_get_liabilities(jwas_hip_ctx* c, int32_t trait, double* out)
+{
+    NEED_LIAB(c);
+    NEED_LIAB_TRAIT(c, trait);
+    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
+    auto& b = c->lb;
+    NEED(c, b.kind[trait] != jwl::kContinuous, JWAS_HIP_ESTATE, "trait %d is continuous: it has no liabilities", trait);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (IS_F64(c)) {
+        HIPCHK(c, hipMemcpyAsync(out, b.y[trait], 8 * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {
+        std::vector<float> y32((size_t)c->n);
+        HIPCHK(c, hipMemcpyAsync(y32.data(), b.y[trait], 4 * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int64_t i = 0; i < c->n; ++i) out[i] = (double)y32[(size_t)i];
+    }
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_liability_end(jwas_hip_ctx* c)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    liab_free(c);
     return JWAS_HIP_OK;
 }
 

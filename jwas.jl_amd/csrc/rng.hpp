@@ -8,6 +8,9 @@
 //
 //   slot 0: the decision uniform  u = (k + 0.5) * 2^-52, k = top 52 bits of words (1,0)
 //   slot 1: the normal            z = sqrt(-2 ln u1) cos(2 pi u2), u1 from words (1,0), u2 from (3,2)
+//   slot 2: the liability uniform (liability.hpp), indexed by (INDIVIDUAL, iteration, 0x40000000 | Gibbs round, 2 + 16*trait);
+//           iteration 0 is the set-up draw.  The marker samplers' repetition words are small counts or carry the 0x80000000 bit
+//           (sampler_mt.hpp, f64_path.hpp), the synthesisers use slot 0: no tuple is shared.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

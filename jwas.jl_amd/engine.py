@@ -10,6 +10,8 @@ The host MCMC loop (jwas.jl_amd/mcmc.py) drives a *sweep engine* through this sm
     sub_xalpha(trait); mul_alpha(trait)
     sweep(**params) -> dict of reductions              BayesABC!/BayesR!/MTBayesABC!
     accumulate(k); posterior(trait)                    running posterior means
+    liability_begin / set_categorical / set_censored / set_thresholds / liability_init / liability_sample /
+    liability_minmax / liabilities / liability_end     threshold and censored traits (sample_liabilities!)
 
 HipEngine is the only engine the package ships; it raises if libjwas_hip.so or the GPU is missing.
 """
@@ -486,6 +488,72 @@ class HipEngine:
     def gwas_end(self):
         self._chk(self._L.jwas_hip_gwas_end(self._h))
         self._gwas_nwin = self._gwas_rows = 0
+
+    # -- threshold / censored traits (jwas_hip_liability_*; categorical_and_censored_trait.jl) -----------
+    def liability_begin(self, ntraits=None):
+        """Start the liability state for the traits of init_state: every trait continuous until set_categorical / set_censored."""
+        nt = self.ntraits if ntraits is None else int(ntraits)
+        self._chk(self._L.jwas_hip_liability_begin(self._h, nt))
+        self._liab_nthr = {}
+
+    def set_categorical(self, trait, codes, thresholds):
+        """codes: category per record, 1..ncat (0 = missing); thresholds: [-Inf, t1, ..., +Inf].  The liabilities become the
+        codes (the placeholder phenotype)."""
+        cd = np.ascontiguousarray(codes, dtype=np.int32)
+        th = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if cd.ndim != 1 or th.ndim != 1:
+            raise ValueError("codes and thresholds must be vectors")
+        self._chk(self._L.jwas_hip_liability_set_categorical(self._h, int(trait), cd.size, _ptr(cd), th.size, _ptr(th)))
+        self._liab_nthr[int(trait)] = th.size
+
+    def set_censored(self, trait, lower, upper):
+        """Bounds per record (+-Inf allowed; lower == upper: an exact record)."""
+        lo = np.ascontiguousarray(lower, dtype=np.float64)
+        up = np.ascontiguousarray(upper, dtype=np.float64)
+        if lo.shape != up.shape or lo.ndim != 1:
+            raise ValueError("lower and upper must be vectors of one length")
+        self._chk(self._L.jwas_hip_liability_set_censored(self._h, int(trait), lo.size, _ptr(lo), _ptr(up)))
+
+    def set_thresholds(self, trait, thresholds):
+        th = np.ascontiguousarray(thresholds, dtype=np.float64)
+        self._chk(self._L.jwas_hip_liability_set_thresholds(self._h, int(trait), th.size, _ptr(th)))
+
+    @staticmethod
+    def _liability_params(iteration, seed, ngibbs, R):
+        P = _lib.LiabilityParams()
+        P.iteration, P.ngibbs, P.seed = int(iteration), int(ngibbs), int(seed)
+        Rm = np.atleast_2d(np.asarray(R, dtype=np.float64))
+        if Rm.shape[0] != Rm.shape[1] or Rm.shape[0] > _lib.MAX_TRAITS:
+            raise ValueError("R must be a t x t matrix, t <= 4")
+        for i, v in enumerate(Rm.ravel()):
+            P.R[i] = float(v)
+        return P
+
+    def liability_init(self, *, seed, R):
+        """The set-up draw (iteration 0): liability ~ N(cmean, R_kk) truncated to the record's bounds, cmean = liability - residual."""
+        P = self._liability_params(0, seed, 1, R)
+        self._chk(self._L.jwas_hip_liability_init(self._h, C.byref(P)))
+
+    def liability_sample(self, *, iteration, seed, ngibbs, R):
+        """sample_liabilities!: redraw liabilities and residuals of the categorical / censored traits on the device."""
+        P = self._liability_params(iteration, seed, ngibbs, R)
+        self._chk(self._L.jwas_hip_liability_sample(self._h, C.byref(P)))
+
+    def liability_minmax(self, trait):
+        """(max_below, min_above) per threshold of a categorical trait: the support of the threshold draw."""
+        nthr = getattr(self, "_liab_nthr", {}).get(int(trait), _lib.MAX_THRESHOLDS)
+        a, b = np.empty(_lib.MAX_THRESHOLDS), np.empty(_lib.MAX_THRESHOLDS)
+        self._chk(self._L.jwas_hip_liability_minmax(self._h, int(trait), _ptr(a), _ptr(b)))
+        return a[:nthr].copy(), b[:nthr].copy()
+
+    def liabilities(self, trait):
+        out = np.empty(self.n, dtype=np.float64)
+        self._chk(self._L.jwas_hip_get_liabilities(self._h, int(trait), _ptr(out)))
+        return out
+
+    def liability_end(self):
+        self._chk(self._L.jwas_hip_liability_end(self._h))
+        self._liab_nthr = {}
 
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""

@@ -2,6 +2,7 @@
 that is NOT the marker sweep, driving a sweep engine (jwas.jl_amd.engine.HipEngine) for step 2.
 
 Per iteration (the reference's order, MCMC_BayesianAlphabet.jl:184-421):
+  0. categorical / censored traits: engine.liability_sample(...), then the threshold draw                (:186-191, DEVICE)
   1. location parameters: ycorr += X sol ; rhs = X'ycorr ; single-site Gibbs ; ycorr -= X sol   (:196-220, host)
   2. marker effects: engine.sweep(...)                                                      (:224-290, DEVICE)
   3. pi  ~ Beta / Dirichlet from the sweep's counts                                          (:294-317, host)
@@ -222,6 +223,60 @@ def _inverse_wishart_batch(rng, df, scale):
     return (G + G.transpose(0, 2, 1)) / 2
 
 
+LIABILITY_TYPES = ("categorical", "categorical(binary)", "censored")
+LIABILITY_METHODS = ("liability_begin", "set_categorical", "set_censored", "set_thresholds", "liability_init", "liability_sample",
+                     "liability_minmax", "liabilities", "liability_end")
+
+
+def add_censored_trait_column(model, ph, rng):
+    """add_censored_trait_column! (categorical_and_censored_trait.jl:263-296; JWAS.jl:229-235): the column <trait> from the bounds
+    <trait>_l / <trait>_u -- missing when the record is not truncated at all, the finite bound of a one-sided record, a value
+    l, l + 1, ... <= u of a two-sided one (rand(l:u)); missing bounds become -Inf / +Inf."""
+    for k, tr in enumerate(model.lhsVec):
+        if model.traits_type[k] != "censored":
+            continue
+        for c in (f"{tr}_l", f"{tr}_u"):
+            if c not in ph.columns:
+                raise ValueError(f"censored trait {tr}: the phenotype data need the columns {tr}_l and {tr}_u.")
+        lo = ph[f"{tr}_l"].to_numpy(dtype=np.float64).copy()
+        up = ph[f"{tr}_u"].to_numpy(dtype=np.float64).copy()
+        both = np.isnan(lo) & np.isnan(up)
+        lo[both], up[both] = -np.inf, np.inf
+        if np.isnan(lo).any() or np.isnan(up).any() or (lo > up).any():
+            raise ValueError(f"censored trait {tr}: every record needs lower bound <= upper bound (both missing = not observed).")
+        y = np.full(len(ph), np.nan)
+        one_l, one_u = np.isinf(lo) & ~np.isinf(up), ~np.isinf(lo) & np.isinf(up)
+        y[one_l], y[one_u] = up[one_l], lo[one_u]
+        two = ~np.isinf(lo) & ~np.isinf(up)
+        y[two] = lo[two] + np.floor(rng.random(int(two.sum())) * (np.floor(up[two] - lo[two]) + 1.0))
+        ph[tr], ph[f"{tr}_l"], ph[f"{tr}_u"] = y, lo, up
+
+
+def sample_from_conditional_inverse_wishart(rng, df, scale, binary_index):
+    """sample_from_conditional_inverse_Wishart (categorical_and_censored_trait.jl:228-260; Korsgaard et al. 1999): a draw of R in
+    which the binary traits are independent with unit variance.  `scale` is the Wishart scale inv(scale_R + SSE)."""
+    from scipy.stats import wishart
+    t = scale.shape[0]
+    i2 = list(binary_index)
+    i1 = [k for k in range(t) if k not in i2]
+    n1, n2 = len(i1), len(i2)
+    if n1 == 0:
+        return np.eye(t)
+    V11, V12, V22 = scale[np.ix_(i1, i1)], scale[np.ix_(i1, i2)], scale[np.ix_(i2, i2)]
+    V11i = np.linalg.inv(V11)
+    V22_1 = V22 - V12.T @ V11i @ V12
+    X1 = np.atleast_2d(wishart.rvs(df=df, scale=(V11 + V11.T) / 2, random_state=rng))
+    X1i = np.linalg.inv(X1)
+    mu = (V11i @ V12).ravel(order="F")
+    Sig = np.kron(V22_1, X1i)
+    X2 = rng.multivariate_normal(mu, (Sig + Sig.T) / 2).reshape((n1, n2), order="F")
+    X1i = (X1i + X1i.T) / 2                    # (inv() is symmetric up to rounding only; the device asks for an exactly symmetric R)
+    R = np.block([[X1i + X2 @ X2.T, -X2], [-X2.T, np.eye(n2)]])
+    order = np.argsort(i1 + i2)
+    R = R[np.ix_(order, order)]
+    return (R + R.T) / 2
+
+
 def _gibbs(A, x, b, rng, vare=None):
     """One sweep of the single-site Gibbs sampler on the MME (iterative_solver/solver.jl:143-162)."""
     for i in range(len(x)):
@@ -265,6 +320,18 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     idcol = df.columns[0]
     ph = df.copy()
     ph[idcol] = ph[idcol].astype(str)
+    traits_type = model.traits_type = list(getattr(model, "traits_type", None) or ["continuous"] * t)
+    has_liab = any(tt in LIABILITY_TYPES for tt in traits_type)
+    if has_liab:
+        if heterogeneous_residuals:
+            raise NotImplementedError("heterogeneous_residuals with categorical / censored traits stays on the reference")
+        if engine is not None or getattr(Mi, "storage_mode", "dense") == "device":
+            eng_ = engine if engine is not None else Mi.device_backend
+            missing_ = [m_ for m_ in LIABILITY_METHODS if not hasattr(eng_, m_)]
+            if missing_:
+                raise TypeError("categorical / censored traits need an engine with the liability step (" + ", ".join(missing_)
+                                + " missing); the package has no CPU fallback")
+        add_censored_trait_column(model, ph, rng)                        # JWAS.jl:229-235
     for tr in model.lhsVec:
         if tr not in ph.columns:
             raise ValueError(f"Phenotypes for {tr} are not found in the data.")
@@ -336,6 +403,37 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         fh.write("\n".join(ph[idcol]) + "\n")
     with open(os.path.join(output_folder, "IDs_for_individuals_with_genotypes.txt"), "w") as fh:
         fh.write("\n".join(Mi.obsID) + "\n")
+    liab_codes, liab_bounds = {}, {}
+    if has_liab:                                                          # input_data_validation.jl:255-290
+        for k, tr in enumerate(model.lhsVec):
+            if traits_type[k] == "categorical":
+                col = ph[tr].to_numpy(dtype=np.float64)
+                obs = col[np.isfinite(col)]
+                if not np.all(obs == np.floor(obs)):
+                    raise ValueError(f"For categorical trait {tr}, the categories should be integers 1, 2, 3, ...")
+                user = sorted(set(int(v) for v in obs))
+                correct = list(range(1, len(user) + 1))
+                if user != correct:
+                    raise ValueError(f"For categorical trait {tr}, the categories should be {correct} ; instead of {user}")
+                if len(user) > 15:
+                    raise NotImplementedError(f"categorical trait {tr}: at most 15 categories on the device (got {len(user)})")
+                if len(user) < 2:
+                    raise ValueError(f"For categorical trait {tr}, at least two categories must be observed")
+                if len(user) == 2:
+                    traits_type[k] = "categorical(binary)"
+                liab_codes[k] = np.where(np.isfinite(col), col, 0.0).astype(np.int32)       # 0 = missing (:54,115-117)
+            elif traits_type[k] == "censored":
+                liab_bounds[k] = (ph[f"{tr}_l"].to_numpy(dtype=np.float64), ph[f"{tr}_u"].to_numpy(dtype=np.float64))
+        for lab, typ in (("Censored traits are: ", "censored"), ("Categorical traits (>2 categories) are: ", "categorical"),
+                         ("Binary traits are: ", "categorical(binary)")):
+            names_ = [tr for tr, tt in zip(model.lhsVec, traits_type) if tt == typ]
+            if names_:
+                print(lab + str(names_))
+        if t > 1 and "categorical(binary)" in traits_type:
+            print(" - note that binary traits are assumed to be independent with unit variance.")
+    binary_index = [k for k in range(t) if traits_type[k] == "categorical(binary)"]
+    liab_traits = [k for k in range(t) if traits_type[k] in LIABILITY_TYPES]
+    ngibbs = 5 if len(liab_traits) > 1 else 1                             # categorical_and_censored_trait.jl:184-188
     Y = np.stack([ph[tr].to_numpy(dtype=ftype) for tr in model.lhsVec])       # t x n
     observed = np.isfinite(Y).T                                                     # n x t: mme.missingPattern (residual.jl:17-21)
     has_missing = not observed.all()
@@ -355,8 +453,19 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     vare0 = np.diag(phenovar) * 0.5
     R = model.R
     if R.val is False:
+        single_cat = t == 1 and traits_type[0] in ("categorical", "categorical(binary)")
+        if single_cat:                         # known to be 1.0 in a single-trait threshold model (input_data_validation.jl:333-338)
+            vare0[0, 0] = 1.0
+            R.estimate_variance = False
+        for k in (binary_index if t > 1 else []):                      # :341-349: binary traits independent with unit variance
+            vare0[k, :] = 0.0
+            vare0[:, k] = 0.0
+            vare0[k, k] = 1.0
         R.val = ftype(vare0[0, 0]) if t == 1 else vare0.astype(ftype)
         R.scale = float(R.val) * (float(R.df) - 2) / float(R.df) if t == 1 else np.asarray(R.val, dtype=np.float64) * (float(R.df) - t - 1)
+        if t > 1 and len(binary_index) == t:
+            R.constraint = True
+            R.estimate_variance = False
     if Mi.G.val is False and Mi.genetic_variance.val is False:
         Mi.genetic_variance.val = varg[0, 0] if t == 1 else varg
     pi = Mi.pi
@@ -758,12 +867,35 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     alpha0 = np.zeros((t, p), dtype=ftype)
     if Mi.alpha is not False:
         alpha0[:] = np.asarray(Mi.alpha, dtype=ftype).reshape(t, p)
+    thresholds = {}
+    if has_liab:
+        # categorical_censored_traits_setup! (categorical_and_censored_trait.jl:29-95): thresholds, bounds and the set-up draw of
+        # the liabilities; the liabilities live on the device beside the residual
+        R0_ = np.atleast_2d(np.asarray(R.val, dtype=np.float64))
+        engine.liability_begin(t)
+        for k in liab_traits:
+            if k in liab_codes:
+                ncat = int(liab_codes[k].max())
+                if traits_type[k] == "categorical(binary)":
+                    th = [-np.inf, 0.0, np.inf]                           # :65
+                elif t == 1:                                             # :58  (t1 = 0 < t2 < ... < 1)
+                    th = [-np.inf] + list(np.linspace(0.0, 1.0, ncat)[:-1]) + [np.inf]
+                else:                                                    # :60-62  (t1 = 0, t2 = 1 < t3 < ... < mu + 10 sigma, mu = 0)
+                    th = [-np.inf, 0.0] + list(np.linspace(1.0, 10.0 * R0_[k, k], ncat - 1)[:-1]) + [np.inf]
+                thresholds[k] = np.asarray(th, dtype=np.float64)
+                engine.set_categorical(k, liab_codes[k], thresholds[k])
+            else:
+                engine.set_censored(k, liab_bounds[k][0], liab_bounds[k][1])
+        model.thresholds = thresholds
     for k in range(t):
         engine.set_state(k, alpha=alpha0[k], beta=alpha0[k],
                          delta=np.ones(p, dtype=np.int32 if method == "BayesR" else ftype))
-        engine.set_residual(Y[k], k)           # sol = 0
+        # sol = 0; a liability trait starts from the placeholder phenotype the engine holds (its residual is y - cmean for THAT y)
+        engine.set_residual(engine.liabilities(k).astype(ftype) if k in liab_traits else Y[k], k)
         if alpha0[k].any():
             engine.sub_xalpha(k)
+    if has_liab:
+        engine.liability_init(seed=seed_int, R=R0_)                       # :82-88
 
     vare = ftype(R.val) if t == 1 else np.asarray(R.val, dtype=ftype)
     Gval = ftype(Mi.G.val) if t == 1 else np.asarray(Mi.G.val, dtype=ftype)
@@ -827,6 +959,11 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     bin_writers = [MarkerSampleWriter(os.path.join(output_folder, f"MCMC_samples_marker_effects_{name}_{tr}.bin"), Mi.markerID)
                    for tr in model.lhsVec]
 
+    liab_files = {}                                                     # output.jl:367-372 (no header lines, as there)
+    for k in liab_traits:
+        liab_files[("liabilities", k)] = open(os.path.join(output_folder, f"MCMC_samples_liabilities_{model.lhsVec[k]}.txt"), "w")
+        if k in thresholds:
+            liab_files[("threshold", k)] = open(os.path.join(output_folder, f"MCMC_samples_threshold_{model.lhsVec[k]}.txt"), "w")
     t_sweep = 0.0
     iter_end = []                                # perf_counter at the end of every iteration (each ends synchronised with the device)
     # The host step between two sweeps is a handful of O(n) vector operations.  A threaded BLAS runs them on every core and
@@ -845,6 +982,18 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     # ================================ the chain =================================================
     try:
         for it in range(1, chain_length + 1):
+            # 0. categorical and censored traits (MCMC_BayesianAlphabet.jl:186-191): liabilities and residuals on the device,
+            #    then the thresholds of the traits with more than two categories from the chain's rng
+            if has_liab:
+                engine.liability_sample(iteration=it, seed=seed_int, ngibbs=ngibbs, R=np.atleast_2d(np.asarray(vare, dtype=np.float64)))
+                for k in liab_traits:
+                    if traits_type[k] != "categorical":
+                        continue
+                    mx, mn = engine.liability_minmax(k)                  # categorical_and_censored_trait.jl:152-155
+                    for i in range(2 if t == 1 else 3, len(thresholds[k]) - 1):
+                        thresholds[k][i] = rng.uniform(mx[i], mn[i])
+                    engine.set_thresholds(k, thresholds[k])              # :160
+
             # 1. location parameters (host)
             if sum(q):
                 if t == 1:
@@ -991,10 +1140,15 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             if R.estimate_variance:
                 if t > 1 and R.constraint:                                  # variance_components.jl:104-109
                     vare = np.diag([(st["resid_ss"][k, k] + Rdf * R.scale[k, k]) / rng.chisquare(n + Rdf) for k in range(t)]).astype(ftype)
+                elif t > 1 and binary_index:                                # variance_components.jl:100-104
+                    S = np.asarray(R.scale, dtype=np.float64) + st["resid_ss"]
+                    vare = sample_from_conditional_inverse_wishart(rng, Rdf + n, np.linalg.inv((S + S.T) / 2), binary_index).astype(ftype)
                 elif t > 1:
                     from scipy.stats import invwishart
                     S = np.asarray(R.scale, dtype=np.float64) + st["resid_ss"]
                     vare = np.asarray(invwishart.rvs(df=Rdf + n, scale=(S + S.T) / 2, random_state=rng), dtype=ftype).reshape(t, t)
+                elif traits_type[0] in ("categorical", "categorical(binary)"):
+                    pass                                                    # fixed (MCMC_BayesianAlphabet.jl:363)
                 else:
                     vare = ftype((ftype(st["resid_ss"][0, 0]) + Rdf * R.scale) / rng.chisquare(n + Rdf))
 
@@ -1015,6 +1169,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 for key_, cols in term_cols.items():
                     files[key_].write(",".join(repr(float(sol[c])) for c in cols) + "\n")
                 files["residual_variance"].write(",".join(repr(float(v)) for v in np.atleast_1d(vare).ravel()) + "\n")
+                for (what, kk), fh in liab_files.items():                   # output.jl:514-523 (read from the device only here)
+                    row = engine.liabilities(kk) if what == "liabilities" else thresholds[kk]
+                    fh.write(",".join(repr(float(v)) for v in row) + "\n")
                 if not pervar:
                     files[f"marker_effects_variances_{name}"].write(",".join(repr(float(v)) for v in np.atleast_1d(Gval).ravel()) + "\n")
                 if Mi.estimatePi and f"pi_{name}" in files:
@@ -1057,7 +1214,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         wall = time.time() - t0
         if _blas_limit is not None:
             _blas_limit.restore_original_limits()
-        for fh in files.values():
+        for fh in list(files.values()) + list(liab_files.values()):
             fh.close()
         for w_ in bin_writers:
             w_.close()
@@ -1112,6 +1269,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                       "block_size": block_size, "n": n, "p": p, "iteration_end_s": iter_end,
                       "block_starts": (np.asarray(engine.block_starts(), dtype=np.int64) + 1).tolist() if fast_blocks is not False else None,
                       "block_repetitions": int(nreps)}
+    if has_liab:
+        engine.liability_end()
     if own_engine and not devres:
         engine.close()
     return out
