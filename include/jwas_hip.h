@@ -32,6 +32,9 @@
  *                              the same over a resident session, plus the local EBVs (src/3.GWAS/src/GWAS.jl:149-173)
  *   jwas_hip_liability_*       sample_liabilities! and the threshold bounds of categorical / censored traits
  *                              (categorical_and_censored_trait/categorical_and_censored_trait.jl:29-210)
+ *   jwas_hip_locpar_*          the non-marker location parameters: the single-site scan Gibbs(A, x, b[, vare])
+ *                              (iterative_solver/solver.jl:143-162) of MCMC/MCMC_BayesianAlphabet.jl:193-220 in residual-update
+ *                              form, and the cross-products sampleVCs reads (variance_components.jl:115-147)
  *
  * Conventions: every entry point returns 0 on success and a negative JWAS_HIP_E* code on failure
  * (no exceptions cross the boundary; jwas_hip_last_error() returns the message -- the analogue of
@@ -403,6 +406,58 @@ int  jwas_hip_liability_minmax(jwas_hip_ctx* ctx, int32_t trait, double* max_bel
  * Float32 context. */
 int  jwas_hip_get_liabilities(jwas_hip_ctx* ctx, int32_t trait, double* out_n);
 int  jwas_hip_liability_end(jwas_hip_ctx* ctx);
+
+/* ---- location parameters: intercepts, covariates, fixed and i.i.d. random class factors on the device ------------------------
+ * Step 1 of the reference's iteration (MCMC/MCMC_BayesianAlphabet.jl:193-220): ycorr += X sol, rhs = X'Ri ycorr, one scan of
+ * Gibbs(A, x, b[, vare]) (iterative_solver/solver.jl:143-162), ycorr -= X sol.  The levels of one term partition the records, so
+ * given the other terms the levels of a term are conditionally independent: a whole term is sampled at once from the residual
+ * the context holds and the residual is updated -- exactly that scan (csrc/locpar.hpp has the formulas).  The context owns the
+ * term layouts, the solution vector `sol` (doubles: the terms in the order added, a covariate or intercept one entry, a factor one
+ * per level) and its running means; all arithmetic is double in both precisions, the residual keeps the context's element type
+ * and takes one rounding per term.  Works on any genotype storage; the weights are those in force at _begin.  The state is freed
+ * by jwas_hip_locpar_end, jwas_hip_destroy or loading genotypes.  The normal of level l of term j (j counts the terms as added)
+ * is rng.hpp's Box-Muller on philox4x32_10(l, iteration, 0x20000000 | j, 3 + 16 * trait): a seed fixes the chain whatever the
+ * launch geometry, and every sum is formed in an order fixed by the term's layout (no floating-point atomics).  Every entry
+ * point decides its errors before any launch: JWAS_HIP_ESTATE without a residual (jwas_hip_init_state), before _begin, or for a
+ * term added after the first use of sol; JWAS_HIP_EINVAL for levels outside -1 .. nlevels - 1, non-finite covariates, a Gi / inv(R)
+ * that is not finite and symmetric with a positive diagonal; JWAS_HIP_EUNSUP with a communicator attached (marker or row shards)
+ * and for two terms of ONE trait in one random effect (correlated terms within a trait stay on the reference). */
+#define JWAS_HIP_LOCPAR_MAX_GROUPS 8
+typedef struct jwas_locpar_params {
+    uint32_t iteration;                 /* MCMC iteration >= 1 (enters the RNG counter)                                          */
+    int32_t  first_term, last_term;     /* the terms first_term .. last_term - 1 of the scan, in the order added; last_term < 0: to the end */
+    int32_t  reserved;
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                     */
+    double   vare;                      /* one trait: the residual variance (the lambda form, random_effects.jl:232)              */
+    double   Rinv[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];      /* several traits: inv(R), row-major t x t                   */
+    double   Gi[JWAS_HIP_LOCPAR_MAX_GROUPS * 16];                  /* random effect g: inv(G), row-major k x k at Gi + 16 g, k = its member terms in the order added */
+} jwas_locpar_params;
+typedef struct jwas_locpar_stats {
+    double utu[JWAS_HIP_LOCPAR_MAX_GROUPS * 16];                   /* random effect g: U'U of its member terms AFTER the step, row-major k x k at utu + 16 g (variance_components.jl:121-135) */
+    double step_ms;                     /* device time of the step (HIP events on the context's stream)                          */
+} jwas_locpar_stats;
+/* Start (or restart) the location-parameter state for the ntraits traits of jwas_hip_init_state: no terms, sol empty. */
+int  jwas_hip_locpar_begin(jwas_hip_ctx* ctx, int32_t ntraits);
+/* Add a one-entry term to trait `trait`: the covariate x (n finite doubles), or the intercept when x == NULL (build_MME.jl:183-290).
+ * Terms are sampled in the order they are added: add them trait by trait, term by term -- the reference's equation order. */
+int  jwas_hip_locpar_add_covariate(jwas_hip_ctx* ctx, int32_t trait, int64_t n, const double* x);
+/* Add a class factor of nlevels levels: level[i] in 0 .. nlevels - 1, or -1 for a record in no level; a level may be empty.
+ * random_group -1: a fixed term; 0 .. JWAS_HIP_LOCPAR_MAX_GROUPS - 1: member of that i.i.d. random effect (set_random,
+ * random_effects.jl:93-191) -- one term per trait, all of the same nlevels; its position among the members is its row of Gi. */
+int  jwas_hip_locpar_add_factor(jwas_hip_ctx* ctx, int32_t trait, int64_t n, const int32_t* level, int64_t nlevels, int32_t random_group);
+/* Number of entries of sol. */
+int  jwas_hip_locpar_size(jwas_hip_ctx* ctx, int64_t* out_q);
+int  jwas_hip_locpar_set_sol(jwas_hip_ctx* ctx, int64_t q, const double* sol);
+int  jwas_hip_locpar_get_sol(jwas_hip_ctx* ctx, int64_t q, double* out_sol);
+/* One scan over the terms first_term .. last_term - 1 (solver.jl:143-162 in residual-update form); stats (may be NULL) receives
+ * the cross-products of EVERY random effect after the step.  Synchronous when stats is given. */
+int  jwas_hip_locpar_step(jwas_hip_ctx* ctx, const jwas_locpar_params* params, jwas_locpar_stats* stats);
+/* Running means of sol and sol^2 on the device (output.jl:556-560): mean += (sol - mean) / nsamples. */
+int  jwas_hip_locpar_accumulate(jwas_hip_ctx* ctx, double nsamples);
+int  jwas_hip_locpar_get_means(jwas_hip_ctx* ctx, int64_t q, double* out_mean, double* out_mean2);
+/* Device bytes of the state for nterms terms with total_levels entries of sol over n records (pure; an upper bound). */
+int64_t jwas_hip_locpar_estimate_bytes(int64_t n, int64_t nterms, int64_t total_levels);
+int  jwas_hip_locpar_end(jwas_hip_ctx* ctx);
 
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the

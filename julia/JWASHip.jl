@@ -226,6 +226,77 @@ function hip_get_liabilities(b::HipBackend, trait::Integer)
 end
 hip_liability_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_liability_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
 
+"Location parameters on the device (MCMC/MCMC_BayesianAlphabet.jl:193-220; iterative_solver/solver.jl:143-162 term by term).
+`hip_locpar_begin!` after `jwas_hip_init_state` and the weights; the terms trait by trait, term by term (the equation order):
+`hip_locpar_add_covariate!` (x = nothing: the intercept) and `hip_locpar_add_factor!` (levels 1..nlevels, 0 = in no level;
+random_group 0 = fixed, g >= 1 = member of the g-th set_random effect).  `hip_locpar_step!` replaces the scan and returns the U'U
+cross-products sampleVCs reads (variance_components.jl:121-135); `hip_locpar_accumulate!` / `hip_locpar_means` keep the running
+means of output.jl:556-560 on the device."
+struct HipLocparParams
+    iteration::UInt32
+    first_term::Int32
+    last_term::Int32
+    reserved::Int32
+    seed::UInt64
+    vare::Float64
+    Rinv::NTuple{16,Float64}
+    Gi::NTuple{128,Float64}
+end
+struct HipLocparStats
+    utu::NTuple{128,Float64}
+    step_ms::Float64
+end
+"vare: the residual variance (one trait) or R (several traits, inverted here); Gi: inv(G) of every random effect, in group order.
+Both are symmetrised here, as the library refuses a matrix that is not symmetric bit for bit."
+function HipLocparParams(iter::Integer, seed::Integer, R, Gi::Vector{<:AbstractMatrix}; first_term::Integer = 0, last_term::Integer = -1)
+    # (the library asks for exactly symmetric matrices; an LU inverse is symmetric up to rounding only)
+    sym(M) = (M .+ permutedims(M)) ./ 2
+    Rt = R isa Real ? Float64[] : vec(sym(inv(Float64.(R))))
+    g = zeros(Float64, 128)
+    for (i, M) in enumerate(Gi)
+        Mt = vec(sym(Float64.(M)))
+        g[16 * (i - 1) + 1:16 * (i - 1) + length(Mt)] .= Mt
+    end
+    HipLocparParams(UInt32(iter), Int32(first_term), Int32(last_term), Int32(0), UInt64(seed), R isa Real ? Float64(R) : 0.0,
+                    ntuple(i -> i <= length(Rt) ? Rt[i] : 0.0, 16), ntuple(i -> g[i], 128))
+end
+hip_locpar_begin!(b::HipBackend, ntraits::Integer) =
+    hip_check(b.ctx, ccall((:jwas_hip_locpar_begin, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32), b.ctx, ntraits))
+hip_locpar_add_covariate!(b::HipBackend, trait::Integer, n::Integer, x::Union{Nothing,Vector{Float64}}) =
+    hip_check(b.ctx, ccall((:jwas_hip_locpar_add_covariate, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}),
+                           b.ctx, trait - 1, n, x === nothing ? C_NULL : x))
+hip_locpar_add_factor!(b::HipBackend, trait::Integer, level::Vector{Int32}, nlevels::Integer, random_group::Integer = 0) =
+    hip_check(b.ctx, ccall((:jwas_hip_locpar_add_factor, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Int64, Int32),
+                           b.ctx, trait - 1, length(level), level .- Int32(1), nlevels, random_group - 1))
+function hip_locpar_size(b::HipBackend)
+    q = Ref{Int64}(0)
+    hip_check(b.ctx, ccall((:jwas_hip_locpar_size, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{Int64}), b.ctx, q))
+    return q[]
+end
+hip_locpar_set_sol!(b::HipBackend, sol::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_locpar_set_sol, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), b.ctx, length(sol), sol))
+function hip_locpar_get_sol(b::HipBackend)
+    sol = Vector{Float64}(undef, hip_locpar_size(b))
+    hip_check(b.ctx, ccall((:jwas_hip_locpar_get_sol, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), b.ctx, length(sol), sol))
+    return sol
+end
+function hip_locpar_step!(b::HipBackend, P::HipLocparParams)
+    S = Ref{HipLocparStats}()
+    hip_check(b.ctx, ccall((:jwas_hip_locpar_step, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipLocparParams}, Ref{HipLocparStats}), b.ctx, P, S))
+    return S[]
+end
+hip_locpar_accumulate!(b::HipBackend, nsamples::Real) =
+    hip_check(b.ctx, ccall((:jwas_hip_locpar_accumulate, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Float64), b.ctx, nsamples))
+function hip_locpar_means(b::HipBackend)
+    q = hip_locpar_size(b)
+    m = Vector{Float64}(undef, q); m2 = Vector{Float64}(undef, q)
+    hip_check(b.ctx, ccall((:jwas_hip_locpar_get_means, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}), b.ctx, q, m, m2))
+    return m, m2
+end
+hip_locpar_estimate_bytes(n::Integer, nterms::Integer, total_levels::Integer) =
+    ccall((:jwas_hip_locpar_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int64), n, nterms, total_levels)
+hip_locpar_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_locpar_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

@@ -43,7 +43,11 @@ SYMBOLS = [
     "jwas_hip_liability_begin", "jwas_hip_liability_set_categorical", "jwas_hip_liability_set_censored",
     "jwas_hip_liability_set_thresholds", "jwas_hip_liability_init", "jwas_hip_liability_sample", "jwas_hip_liability_minmax",
     "jwas_hip_get_liabilities", "jwas_hip_liability_end",
+    "jwas_hip_locpar_begin", "jwas_hip_locpar_add_covariate", "jwas_hip_locpar_add_factor", "jwas_hip_locpar_size",
+    "jwas_hip_locpar_set_sol", "jwas_hip_locpar_get_sol", "jwas_hip_locpar_step", "jwas_hip_locpar_accumulate",
+    "jwas_hip_locpar_get_means", "jwas_hip_locpar_estimate_bytes", "jwas_hip_locpar_end",
 ]
+LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
 
@@ -87,6 +91,16 @@ class SweepStats(C.Structure):
 
 class LiabilityParams(C.Structure):
     _fields_ = [("iteration", C.c_uint32), ("ngibbs", C.c_int32), ("seed", C.c_uint64), ("R", C.c_double * (MAX_TRAITS * MAX_TRAITS))]
+
+
+class LocparParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("first_term", C.c_int32), ("last_term", C.c_int32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("vare", C.c_double), ("Rinv", C.c_double * (MAX_TRAITS * MAX_TRAITS)),
+                ("Gi", C.c_double * (LOCPAR_MAX_GROUPS * 16))]
+
+
+class LocparStats(C.Structure):
+    _fields_ = [("utu", C.c_double * (LOCPAR_MAX_GROUPS * 16)), ("step_ms", C.c_double)]
 
 
 class JwasHipError(RuntimeError):
@@ -190,6 +204,18 @@ def load():
     L.jwas_hip_liability_minmax.argtypes = [vp, i32, vp, vp]
     L.jwas_hip_get_liabilities.argtypes = [vp, i32, vp]
     L.jwas_hip_liability_end.argtypes = [vp]
+    L.jwas_hip_locpar_begin.argtypes = [vp, i32]
+    L.jwas_hip_locpar_add_covariate.argtypes = [vp, i32, i64, vp]
+    L.jwas_hip_locpar_add_factor.argtypes = [vp, i32, i64, vp, i64, i32]
+    L.jwas_hip_locpar_size.argtypes = [vp, C.POINTER(i64)]
+    L.jwas_hip_locpar_set_sol.argtypes = [vp, i64, vp]
+    L.jwas_hip_locpar_get_sol.argtypes = [vp, i64, vp]
+    L.jwas_hip_locpar_step.argtypes = [vp, C.POINTER(LocparParams), C.POINTER(LocparStats)]
+    L.jwas_hip_locpar_accumulate.argtypes = [vp, C.c_double]
+    L.jwas_hip_locpar_get_means.argtypes = [vp, i64, vp, vp]
+    L.jwas_hip_locpar_estimate_bytes.argtypes = [i64, i64, i64]
+    L.jwas_hip_locpar_estimate_bytes.restype = i64
+    L.jwas_hip_locpar_end.argtypes = [vp]
     L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_accumulate.argtypes = [vp, C.c_double]
@@ -213,7 +239,8 @@ def load():
     L.jwas_hip_estimate_bytes_storage.restype = i64
     for name in SYMBOLS:
         fn = getattr(L, name)
-        if name not in ("jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_estimate_bytes", "jwas_hip_estimate_bytes_storage", "jwas_hip_gwas_estimate_bytes"):
+        if name not in ("jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_estimate_bytes", "jwas_hip_estimate_bytes_storage", "jwas_hip_gwas_estimate_bytes",
+                        "jwas_hip_locpar_estimate_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -10,7 +10,8 @@ Same names, argument meaning and error behaviour as reworkhow/JWAS.jl v2.3.6 (fi
 Everything that is NOT the marker sweep stays here on the host (numpy): data ingestion and QC,
 model parsing, fixed-effect Gibbs, variance-component and pi draws, output tables.  Model families
 outside the hot path (pedigree / random terms, GBLUP, SEM, RRM, single-step pre-processing) are rejected with an
-explicit error: they stay on the reference.  Categorical / censored traits run here: their liabilities are sampled
+explicit error: they stay on the reference.  i.i.d. random effects (set_random) and large class factors run on the device
+(mcmc.py step 1, csrc/locpar.hpp).  Categorical / censored traits run here: their liabilities are sampled
 on the device (mcmc.py step 0, csrc/liability.hpp).
 """
 import inspect
@@ -267,6 +268,16 @@ class Model:
         self.outputSamplesVec = []             # outputMCMCsamples(model, terms...): (trait, term) pairs
         self.traits_type = ["continuous"] * len(traits)      # "censored" | "categorical" | "categorical(binary)" (types.jl:325)
         self.thresholds = {}                   # trait index -> [-Inf, 0, ..., Inf] (types.jl:326)
+        self.rndTrmVec = []                    # set_random(model, ...): RandomEffect (types.jl:217-226)
+
+
+class RandomEffect:
+    """types.jl:217-226 -- an i.i.d. random effect: one term name over the traits whose equation contains it."""
+
+    def __init__(self, name, term_array, traits, Gi):
+        self.name, self.term_array, self.traits = name, term_array, traits      # "x2", ["y1:x2", "y2:x2"], [0, 1]
+        self.Gi = Gi                           # Variance: val = inv(G) (False until the default prior is set), df, scale
+        self.randomType = "I"
 
 
 def build_model(model_equations, R=False, *, df=4.0, estimate_variance=True, estimate_scale=False,
@@ -373,6 +384,58 @@ def outputMCMCsamples(model, *terms):
                 model.outputSamplesVec.append((tr, trm))
 
 
+def set_random(model, randomStr, G=False, *, df=4.0, estimate_variance=True, estimate_scale=False, constraint=False,
+               Vinv=0, names=()):
+    """random_effects.jl:93-191: declare the class factor `randomStr` an i.i.d. random effect with covariance G among the k traits
+    whose equation contains it (G = False: a default prior from the data, input_data_validation.jl:352-365).  Its variance is
+    sampled every iteration (sampleVCs, variance_components.jl:115-147) unless estimate_variance=False.  Pedigree / Vinv random
+    effects and several correlated terms in one call stay on the reference."""
+    if not _is_false(G):                                                                      # :100-104
+        Gm = np.atleast_2d(np.asarray(G, dtype=np.float64))
+        ok = Gm.ndim == 2 and Gm.shape[0] == Gm.shape[1] and np.array_equal(Gm, Gm.T)
+        if ok:
+            try:
+                np.linalg.cholesky(Gm)
+            except np.linalg.LinAlgError:
+                ok = False
+        if not ok:
+            raise ValueError("The covariance matrix is not positive definite.")
+    if constraint is not False:                                                               # :108-113
+        raise ValueError("Constraint for variance of random term is not supported now.")
+    if estimate_scale is not False:
+        raise ValueError("Estimate scale for variance of random term is not supported now.")
+    if not (np.isscalar(Vinv) and Vinv == 0) or len(names) != 0:
+        raise NotImplementedError("set_random with a pedigree, Vinv or names (a random effect with a covariance structure among "
+                                  "its levels) stays on the reference; the device path runs i.i.d. random effects")
+    trms = str(randomStr).split()
+    if len(trms) != 1:
+        raise NotImplementedError("set_random with several term names in one call (correlated terms within a trait) stays on "
+                                  "the reference; call set_random once per term for independent effects")
+    trm = trms[0]
+    if trm == "ϵ":
+        raise NotImplementedError("the single-step term ϵ stays on the reference")
+    traits = [k for k, tl in enumerate(model.modelTerms) if any(mt.name == trm for mt in tl)]
+    for k in range(model.nModels):
+        if k not in traits:
+            print(f"{trm} is not found in model equation {k + 1}.")
+    if not traits:
+        raise ValueError(f"{trm} is not found in model equation.")                            # :135-137
+    if any(re_.name == trm for re_ in model.rndTrmVec):
+        raise ValueError(f"{trm} is already a random effect.")
+    k = len(traits)
+    if not _is_false(G) and Gm.shape[0] != k:                                                 # :156-158
+        raise ValueError(f"Dimensions must match. The covariance matrix (G) should be a {k} x {k} matrix.\n")
+    dfk = np.float32(df) + k                                                                  # :182-185
+    if _is_false(G):
+        Gi, scale = False, False
+    else:
+        Gi = np.linalg.inv(Gm.astype(np.float32))                                             # inv(Float32.(G)) (:162)
+        Gi = (Gi + Gi.T) / 2
+        scale = Gm * (float(dfk) - k - 1)
+    term_array = [f"{model.lhsVec[m]}:{trm}" for m in traits]
+    model.rndTrmVec.append(RandomEffect(trm, term_array, traits, Variance(Gi, dfk, scale, estimate_variance, estimate_scale, constraint)))
+
+
 def set_covariate(model, *names):
     """build_MME.jl:158-181: declare terms as continuous covariates (default is a class factor)."""
     flat = []
@@ -393,7 +456,7 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
             memory_guard="error", memory_guard_ratio=0.80, output_folder="results",
             output_samples_for_all_parameters=False,
             # device options (the analogue of storage=:stream's opt-in knobs)
-            device=0, block_size=None, gram_mode="mfma", blocks_per_launch=None, _engine=None):
+            device=0, block_size=None, gram_mode="mfma", blocks_per_launch=None, location_parameters="auto", _engine=None):
     """JWAS.jl:161-511.  Returns the reference's output Dict (output.jl:108-212) as a dict of pandas
     DataFrames and writes the same text files under `output_folder`.
 
@@ -408,6 +471,13 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     3 000 iterations on, 4 from 8 000), 0 / 2 / 4 = one / two / four 1024-marker blocks per launch of the step kernel in the
     sparse steady state of a single-trait chain (grouped launches) -- the same chain up to float32
     rounding of the block right-hand sides; the group cross-Grams are set-up work (8 / 24 KB per marker).
+
+    location_parameters (device option): where step 1, the non-marker location parameters, runs.  "host": the dense host scan
+    (intercepts, covariates and small fixed factors).  "device": term by term on the device from the resident residual
+    (csrc/locpar.hpp) -- factors of any number of levels, the i.i.d. random effects of set_random, residual weights, threshold
+    traits; not with multi-trait records that miss some traits.  "auto": "device" for a model with a set_random term or more than
+    2 048 location-parameter levels, else "host" -- the host path draws from the numpy generator, the device path from the
+    counter generator, so the choice is part of what a seed means.
 
     Categorical / censored traits (build_model(...; categorical_trait, censored_trait)): categories coded 1, 2, 3 ... (two of them
     make a binary trait), bounds of a censored trait in the columns <trait>_l / <trait>_u; the liabilities are sampled on the
@@ -430,6 +500,8 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
             raise NotImplementedError(f"runMCMC(...; {name}=...) is outside the device marker path and stays on the reference")
     if not model.M:
         raise NotImplementedError("models without a genotype term have no marker sweep: use the reference")
+    if location_parameters not in ("auto", "host", "device"):
+        raise ValueError('location_parameters must be "auto", "host" or "device".')
     if memory_guard not in ("error", "warn", "off"):
         raise ValueError("memory_guard must be :error, :warn or :off.")
     if output_samples_frequency is None:
@@ -457,5 +529,5 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
                      output_folder=output_folder, printout_frequency=printout_frequency,
                      memory_guard=memory_guard, memory_guard_ratio=memory_guard_ratio,
                      missing_phenotypes=missing_phenotypes, device=device, block_size=block_size,
-                     gram_mode=gram_mode, blocks_per_launch=blocks_per_launch, engine=_engine, printout_model_info=printout_model_info,
+                     gram_mode=gram_mode, blocks_per_launch=blocks_per_launch, location_parameters=location_parameters, engine=_engine, printout_model_info=printout_model_info,
                      output_samples_for_all_parameters=output_samples_for_all_parameters)

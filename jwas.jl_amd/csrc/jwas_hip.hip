@@ -5,6 +5,7 @@
 #include "f64_path.hpp"
 #include "step_launch.hpp"
 #include "liability.hpp"
+#include "locpar.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -180,6 +181,30 @@ struct jwas_hip_ctx {
         bool part_valid[jwl::kMaxT] = {};                   // ... left by the last draw and still describing the liabilities
         double* mm = nullptr;                               // [kMM] reduced
     } lb;
+    // Location parameters (jwas_hip_locpar_begin .. _end; MCMC_BayesianAlphabet.jl:193-220, solver.jl:143-162; csrc/locpar.hpp)
+    struct Locpar {
+        struct Term {
+            int trait = 0, group = -1, pos = 0, G = 1, npieces = 0;
+            int64_t nlevels = 0, off = 0, nin = 0;
+            double* x = nullptr;                            // [n] covariate values (NULL: ones)
+            int32_t* level = nullptr;                       // [n] level of every record, -1 = none (NULL: all records in level 0)
+            int32_t* rec = nullptr;                         // [nin] records sorted by (level, record) (NULL: 0 .. n - 1)
+            double* wx = nullptr;                           // [nin] w x in that order
+            int32_t *piece_lo = nullptr, *level_piece = nullptr;      // [npieces + 1], [nlevels + 1]
+            double* d = nullptr;                            // [nlevels] sum w x^2
+        };
+        struct Group { int nmembers = 0; int term[jwp::kMaxT] = {}; int64_t nlevels = 0; };
+        bool active = false, finalized = false;
+        int nt = 0, ngroups = 0;
+        std::vector<double> w_host;                         // [n] the residual weights in force at _begin
+        std::vector<Term> terms;
+        Group groups[jwp::kMaxGroups];
+        int64_t q = 0;                                      // entries of sol
+        double *sol = nullptr, *mean = nullptr, *mean2 = nullptr;     // [q]
+        double *part = nullptr, *delta = nullptr;           // [max npieces], [max nlevels] scratch of the running term
+        int64_t* cross_offs = nullptr;                      // [kMaxGroups][16][2] member offsets of every cross-product
+        double* cross_out = nullptr;                        // [kMaxGroups][16]
+    } lp;
 };
 
 static constexpr int kStatGrid = 128;
@@ -326,10 +351,20 @@ static void liab_free(jwas_hip_ctx* c)
     b = jwas_hip_ctx::Liab();
 }
 
+static void locpar_free(jwas_hip_ctx* c)
+{
+    auto& b = c->lp;
+    for (auto& t : b.terms)
+        for (void* q : {(void*)t.x, (void*)t.level, (void*)t.rec, (void*)t.wx, (void*)t.piece_lo, (void*)t.level_piece, (void*)t.d}) (void)hipFree(q);
+    for (void* q : {(void*)b.sol, (void*)b.mean, (void*)b.mean2, (void*)b.part, (void*)b.delta, (void*)b.cross_offs, (void*)b.cross_out}) (void)hipFree(q);
+    b = jwas_hip_ctx::Locpar();
+}
+
 static void free_storage(jwas_hip_ctx* c)
 {
     gwas_free(c);                       // (a session is bound to the matrix it was begun on)
     liab_free(c);                       // (the liabilities belong to the residual of this matrix)
+    locpar_free(c);                     // (... and so do the location parameters' term layouts)
     (void)hipFree(c->X); (void)hipFree(c->r); (void)hipFree(c->Q); (void)hipFree(c->qmean); (void)hipFree(c->w);
     c->X = c->r = nullptr; c->Q = nullptr; c->qmean = nullptr; c->packed = false; c->w = nullptr; c->weighted = false;
     (void)hipFree(c->ev); (void)hipFree(c->dparams); (void)hipFree(c->counters); (void)hipFree(c->fin_out); (void)hipFree(c->stat_out); (void)hipFree(c->sync_cnt);
@@ -2822,6 +2857,7 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     f64_free_state(c);
     gwas_free(c);
     liab_free(c);
+    locpar_free(c);
     for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->w, (void*)F->ev_all}) (void)hipFree(q);
     F->X = F->r = F->xpx = F->gram = F->partials = F->w = nullptr; F->ev = F->ev_all = nullptr; F->dparams = nullptr;
     F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0;
@@ -3596,6 +3632,334 @@ int jwas_hip_liability_end(jwas_hip_ctx* c)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     liab_free(c);
+    return JWAS_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- location parameters (csrc/locpar.hpp): MCMC_BayesianAlphabet.jl:193-220, iterative_solver/solver.jl:143-162 -------------
+#define NEED_LOCPAR(c)                                                                                                 \
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
+    NEED(c, c->lp.active, JWAS_HIP_ESTATE, "jwas_hip_locpar_begin has not been called");                               \
+    NEED(c, liab_residual(c) && c->method >= 0 && c->ntraits == c->lp.nt, JWAS_HIP_ESTATE,                              \
+         "jwas_hip_init_state changed the number of traits after jwas_hip_locpar_begin")
+
+template <class V>
+static hipError_t locpar_upload(V** dev, const std::vector<V>& host)
+{
+    hipError_t e = hipMalloc((void**)dev, sizeof(V) * std::max<size_t>(host.size(), 1));
+    if (e == hipSuccess && !host.empty()) e = hipMemcpy(*dev, host.data(), sizeof(V) * host.size(), hipMemcpyHostToDevice);
+    return e;
+}
+
+// the term's layout from level[] (NULL: every record in level 0) and x[] (NULL: ones): records sorted by (level, record), pieces of
+// at most kPiece records, the lane-group width, d = sum w x^2
+static int locpar_add_term(jwas_hip_ctx* c, int32_t trait, const double* x, const int32_t* level, int64_t nlevels, int32_t group)
+{
+    auto& b = c->lp;
+    const int64_t n = c->n;
+    jwas_hip_ctx::Locpar::Term T;
+    T.trait = trait; T.group = group; T.nlevels = nlevels;
+    std::vector<int32_t> start((size_t)nlevels + 1, 0), rec;
+    if (level) {
+        for (int64_t i = 0; i < n; ++i) if (level[i] >= 0) ++start[(size_t)level[i] + 1];
+        for (int64_t l = 0; l < nlevels; ++l) start[(size_t)l + 1] += start[(size_t)l];
+        rec.resize((size_t)start[(size_t)nlevels]);
+        std::vector<int32_t> fill(start.begin(), start.end() - 1);
+        for (int64_t i = 0; i < n; ++i) if (level[i] >= 0) rec[(size_t)fill[(size_t)level[i]]++] = (int32_t)i;      // (stable: ties by ascending record)
+    } else {
+        start[1] = (int32_t)n;
+    }
+    T.nin = start[(size_t)nlevels];
+    std::vector<double> wx((size_t)T.nin), d((size_t)nlevels, 0.0);
+    std::vector<int32_t> piece_lo, level_piece((size_t)nlevels + 1, 0);
+    for (int64_t l = 0; l < nlevels; ++l) {
+        for (int32_t j = start[(size_t)l]; j < start[(size_t)l + 1]; ++j) {
+            const int64_t i = level ? rec[(size_t)j] : j;
+            const double xi = x ? x[i] : 1.0;
+            wx[(size_t)j] = b.w_host[(size_t)i] * xi;
+            d[(size_t)l] = d[(size_t)l] + wx[(size_t)j] * xi;
+        }
+        for (int32_t j = start[(size_t)l]; j < start[(size_t)l + 1]; j += jwp::kPiece) piece_lo.push_back(j);
+        level_piece[(size_t)l + 1] = (int32_t)piece_lo.size();
+    }
+    T.npieces = (int)piece_lo.size();
+    piece_lo.push_back((int32_t)T.nin);
+    // (pieces of different levels are adjacent in the sorted order: piece p ends where piece p + 1 starts)
+    const int64_t avg = T.npieces ? (T.nin + T.npieces - 1) / T.npieces : 1;
+    T.G = 1;
+    while (T.G < 64 && T.G < avg) T.G <<= 1;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipError_t e = hipSuccess;
+    if (x) { std::vector<double> xv(x, x + n); e = locpar_upload(&T.x, xv); }
+    if (level && e == hipSuccess) {
+        std::vector<int32_t> lv(level, level + n);
+        e = locpar_upload(&T.level, lv);
+        if (e == hipSuccess) e = locpar_upload(&T.rec, rec);
+    }
+    if (e == hipSuccess) e = locpar_upload(&T.wx, wx);
+    if (e == hipSuccess) e = locpar_upload(&T.piece_lo, piece_lo);
+    if (e == hipSuccess) e = locpar_upload(&T.level_piece, level_piece);
+    if (e == hipSuccess) e = locpar_upload(&T.d, d);
+    if (e != hipSuccess) {                                  // (nothing of a term that was not added stays behind)
+        for (void* q : {(void*)T.x, (void*)T.level, (void*)T.rec, (void*)T.wx, (void*)T.piece_lo, (void*)T.level_piece, (void*)T.d}) (void)hipFree(q);
+        return fail(c, JWAS_HIP_EHIP, "uploading the term's layout failed: %s", hipGetErrorString(e));
+    }
+    T.off = b.q;
+    if (group >= 0) {
+        auto& g = b.groups[group];
+        T.pos = g.nmembers;
+        g.term[g.nmembers++] = (int)b.terms.size();
+        g.nlevels = nlevels;
+        b.ngroups = std::max(b.ngroups, group + 1);
+    }
+    b.q += nlevels;
+    b.terms.push_back(T);
+    return JWAS_HIP_OK;
+}
+
+static int locpar_check_add(jwas_hip_ctx* c, int32_t trait, int64_t n)
+{
+    NEED_LOCPAR(c);
+    NEED(c, !c->lp.finalized, JWAS_HIP_ESTATE, "terms are added before sol is first used (call jwas_hip_locpar_begin to start over)");
+    NEED(c, trait >= 0 && trait < c->lp.nt, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->lp.nt);
+    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
+    NEED(c, c->lp.terms.size() < 0x10000000u, JWAS_HIP_EINVAL, "too many terms");
+    return JWAS_HIP_OK;
+}
+
+// allocate sol, its means and the scratch of the largest term on the first use
+static int locpar_finalize(jwas_hip_ctx* c)
+{
+    auto& b = c->lp;
+    if (b.finalized) return JWAS_HIP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int64_t maxp = 1, maxl = 1;
+    for (auto& t : b.terms) { maxp = std::max<int64_t>(maxp, t.npieces); maxl = std::max(maxl, t.nlevels); }
+    const size_t qb = sizeof(double) * (size_t)std::max<int64_t>(b.q, 1);
+    for (double** v : {&b.sol, &b.mean, &b.mean2}) { HIPCHK(c, hipMalloc((void**)v, qb)); HIPCHK(c, hipMemsetAsync(*v, 0, qb, c->stream)); }
+    HIPCHK(c, hipMalloc((void**)&b.part, sizeof(double) * (size_t)maxp));
+    HIPCHK(c, hipMalloc((void**)&b.delta, sizeof(double) * (size_t)maxl));
+    std::vector<int64_t> offs((size_t)jwp::kMaxGroups * 32, 0);
+    for (int g = 0; g < b.ngroups; ++g)
+        for (int a = 0; a < b.groups[g].nmembers; ++a)
+            for (int e = 0; e < b.groups[g].nmembers; ++e) {
+                offs[(size_t)(g * 16 + a * b.groups[g].nmembers + e) * 2] = b.terms[(size_t)b.groups[g].term[a]].off;
+                offs[(size_t)(g * 16 + a * b.groups[g].nmembers + e) * 2 + 1] = b.terms[(size_t)b.groups[g].term[e]].off;
+            }
+    HIPCHK(c, locpar_upload(&b.cross_offs, offs));
+    HIPCHK(c, hipMalloc((void**)&b.cross_out, sizeof(double) * jwp::kMaxGroups * 16));
+    HIPCHK(c, hipMemsetAsync(b.cross_out, 0, sizeof(double) * jwp::kMaxGroups * 16, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    b.finalized = true;
+    return JWAS_HIP_OK;
+}
+
+extern "C" {
+
+int jwas_hip_locpar_begin(jwas_hip_ctx* c, int32_t ntraits)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no residual: load genotypes and call jwas_hip_init_state first");
+    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "location parameters are not driven from marker or row shards");
+    NEED(c, ntraits == c->ntraits, JWAS_HIP_EINVAL, "ntraits (%d) differs from jwas_hip_init_state's (%d)", ntraits, c->ntraits);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    locpar_free(c);
+    auto& b = c->lp;
+    b.nt = ntraits;
+    b.w_host.assign((size_t)c->n, 1.0);
+    if (IS_F64(c)) {
+        HIPCHK(c, hipMemcpy(b.w_host.data(), c->f64->w, sizeof(double) * (size_t)c->n, hipMemcpyDeviceToHost));
+    } else {
+        std::vector<float> w32((size_t)c->n);
+        HIPCHK(c, hipMemcpy(w32.data(), c->w, sizeof(float) * (size_t)c->n, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < c->n; ++i) b.w_host[(size_t)i] = (double)w32[(size_t)i];
+    }
+    b.active = true;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_locpar_add_covariate(jwas_hip_ctx* c, int32_t trait, int64_t n, const double* x)
+{
+    if (int rc = locpar_check_add(c, trait, n)) return rc;
+    if (x)
+        for (int64_t i = 0; i < n; ++i) NEED(c, std::isfinite(x[i]), JWAS_HIP_EINVAL, "record %lld: the covariate is not finite (%g)", (long long)i, x[i]);
+    return locpar_add_term(c, trait, x, nullptr, 1, -1);
+}
+
+int jwas_hip_locpar_add_factor(jwas_hip_ctx* c, int32_t trait, int64_t n, const int32_t* level, int64_t nlevels, int32_t group)
+{
+    if (int rc = locpar_check_add(c, trait, n)) return rc;
+    NEED(c, level, JWAS_HIP_EINVAL, "level is NULL");
+    NEED(c, nlevels >= 1 && nlevels < (int64_t)1 << 31, JWAS_HIP_EINVAL, "nlevels must be 1 .. 2^31 - 1 (got %lld)", (long long)nlevels);
+    for (int64_t i = 0; i < n; ++i)
+        NEED(c, level[i] >= -1 && level[i] < nlevels, JWAS_HIP_EINVAL, "record %lld: level %d outside -1..%lld", (long long)i, level[i], (long long)nlevels - 1);
+    NEED(c, group >= -1 && group < jwp::kMaxGroups, JWAS_HIP_EINVAL, "random_group must be -1 (fixed) or 0..%d (got %d)", jwp::kMaxGroups - 1, group);
+    if (group >= 0) {
+        const auto& g = c->lp.groups[group];
+        NEED(c, g.nmembers < jwp::kMaxT, JWAS_HIP_EINVAL, "random effect %d already has %d member terms", group, g.nmembers);
+        for (int a = 0; a < g.nmembers; ++a)
+            NEED(c, c->lp.terms[(size_t)g.term[a]].trait != trait, JWAS_HIP_EUNSUP,
+                 "random effect %d already has a term of trait %d: correlated terms within a trait stay on the reference", group, trait);
+        NEED(c, g.nmembers == 0 || g.nlevels == nlevels, JWAS_HIP_EINVAL, "the member terms of random effect %d must have the same levels (%lld, got %lld)",
+             group, (long long)g.nlevels, (long long)nlevels);
+    }
+    return locpar_add_term(c, trait, nullptr, level, nlevels, group);
+}
+
+int jwas_hip_locpar_size(jwas_hip_ctx* c, int64_t* out_q)
+{
+    NEED_LOCPAR(c);
+    NEED(c, out_q, JWAS_HIP_EINVAL, "NULL argument");
+    *out_q = c->lp.q;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_locpar_set_sol(jwas_hip_ctx* c, int64_t q, const double* sol)
+{
+    NEED_LOCPAR(c);
+    NEED(c, sol, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, q == c->lp.q, JWAS_HIP_EINVAL, "q (%lld) differs from the number of location parameters (%lld)", (long long)q, (long long)c->lp.q);
+    if (int rc = locpar_finalize(c)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->lp.sol, sol, sizeof(double) * (size_t)q, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_locpar_get_sol(jwas_hip_ctx* c, int64_t q, double* out)
+{
+    NEED_LOCPAR(c);
+    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, q == c->lp.q, JWAS_HIP_EINVAL, "q (%lld) differs from the number of location parameters (%lld)", (long long)q, (long long)c->lp.q);
+    if (int rc = locpar_finalize(c)) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, c->lp.sol, sizeof(double) * (size_t)q, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_locpar_step(jwas_hip_ctx* c, const jwas_locpar_params* P, jwas_locpar_stats* S)
+{
+    NEED_LOCPAR(c);
+    NEED(c, P, JWAS_HIP_EINVAL, "params is NULL");
+    auto& b = c->lp;
+    const int t = b.nt, nterms = (int)b.terms.size();
+    const int first = P->first_term, last = P->last_term < 0 ? nterms : P->last_term;
+    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: iteration must be >= 1");
+    NEED(c, first >= 0 && first <= last && last <= nterms, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: terms %d..%d outside 0..%d", first, last, nterms);
+    if (t == 1) {
+        NEED(c, std::isfinite(P->vare) && P->vare > 0.0, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: vare must be positive and finite (got %g)", P->vare);
+    } else {
+        for (int k = 0; k < t; ++k) {
+            NEED(c, P->Rinv[k * t + k] > 0.0, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: inv(R) needs a positive diagonal");
+            for (int j = 0; j < t; ++j)
+                NEED(c, std::isfinite(P->Rinv[k * t + j]) && P->Rinv[k * t + j] == P->Rinv[j * t + k], JWAS_HIP_EINVAL, "jwas_hip_locpar_step: inv(R) must be finite and symmetric");
+        }
+    }
+    for (int g = 0; g < b.ngroups; ++g) {
+        const int kk = b.groups[g].nmembers;
+        for (int a = 0; a < kk; ++a) {
+            NEED(c, P->Gi[16 * g + a * kk + a] > 0.0, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: Gi of random effect %d needs a positive diagonal", g);
+            for (int e = 0; e < kk; ++e)
+                NEED(c, std::isfinite(P->Gi[16 * g + a * kk + e]) && P->Gi[16 * g + a * kk + e] == P->Gi[16 * g + e * kk + a], JWAS_HIP_EINVAL,
+                     "jwas_hip_locpar_step: Gi of random effect %d must be finite and symmetric", g);
+        }
+    }
+    if (int rc = locpar_finalize(c)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool f64 = IS_F64(c);
+    const size_t esz = f64 ? 8 : 4;
+    if (S) HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
+    for (int j = first; j < last; ++j) {
+        const auto& T = b.terms[(size_t)j];
+        const int k = T.trait;
+        if (T.npieces > 0) {
+            jwp::SumArgs A = {};
+            A.r = liab_residual(c); A.ld = c->ld; A.rec = T.rec; A.wx = T.wx; A.piece_lo = T.piece_lo; A.part = b.part;
+            A.npieces = T.npieces; A.G = T.G; A.nt = t; A.trait = k;
+            for (int m = 0; m < t; ++m) A.c[m] = t == 1 ? 1.0 : P->Rinv[k * t + m];
+            const dim3 grid((unsigned)(((int64_t)T.npieces * T.G + 255) / 256)), block(256);
+            if (f64) hipLaunchKernelGGL((jwp::k_locpar_sums<double>), grid, block, 0, c->stream, A);
+            else     hipLaunchKernelGGL((jwp::k_locpar_sums<float>), grid, block, 0, c->stream, A);
+        }
+        jwp::DrawArgs D = {};
+        D.part = b.part; D.level_piece = T.level_piece; D.d = T.d; D.sol = b.sol; D.delta = b.delta; D.off = T.off;
+        D.nlevels = (int32_t)T.nlevels; D.pos = T.pos; D.npartners = 0;
+        D.ckk = t == 1 ? 1.0 : P->Rinv[k * t + k];
+        D.s = t == 1 ? P->vare : 1.0;
+        D.prior = 0.0;
+        if (T.group >= 0) {
+            const auto& g = b.groups[T.group];
+            const int kk = g.nmembers;
+            D.npartners = kk;
+            for (int m = 0; m < kk; ++m) { D.partner_off[m] = b.terms[(size_t)g.term[m]].off; D.gi[m] = P->Gi[16 * T.group + T.pos * kk + m]; }
+            D.prior = t == 1 ? P->vare * D.gi[T.pos] : D.gi[T.pos];
+        }
+        D.iter = P->iteration; D.rep = 0x20000000u | (uint32_t)j; D.slot = 3u + 16u * (uint32_t)k;
+        D.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); D.seed_hi = (uint32_t)(P->seed >> 32);
+        hipLaunchKernelGGL(jwp::k_locpar_draw, dim3((unsigned)((T.nlevels + 255) / 256)), dim3(256), 0, c->stream, D);
+        char* rk = (char*)liab_residual(c) + esz * (size_t)k * (size_t)c->ld;
+        const dim3 agrid((unsigned)((c->n + 255) / 256));
+        if (f64) hipLaunchKernelGGL((jwp::k_locpar_apply<double>), agrid, dim3(256), 0, c->stream, (double*)rk, T.x, T.level, b.delta, c->n);
+        else     hipLaunchKernelGGL((jwp::k_locpar_apply<float>), agrid, dim3(256), 0, c->stream, (float*)rk, T.x, T.level, b.delta, c->n);
+    }
+    for (int g = 0; g < b.ngroups; ++g) {
+        const int kk = b.groups[g].nmembers;
+        if (kk > 0)
+            hipLaunchKernelGGL(jwp::k_locpar_cross, dim3((unsigned)(kk * kk)), dim3(256), 0, c->stream, b.sol, b.cross_offs + (size_t)g * 32,
+                               (int32_t)b.groups[g].nlevels, b.cross_out + (size_t)g * 16);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (S) {
+        HIPCHK(c, hipEventRecord(c->ev_stop, c->stream));
+        std::memset(S, 0, sizeof *S);
+        HIPCHK(c, hipMemcpyAsync(S->utu, b.cross_out, sizeof(double) * jwp::kMaxGroups * 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+        S->step_ms = (double)ms;
+    }
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_locpar_accumulate(jwas_hip_ctx* c, double nsamples)
+{
+    NEED_LOCPAR(c);
+    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
+    if (int rc = locpar_finalize(c)) return rc;
+    auto& b = c->lp;
+    if (b.q == 0) return JWAS_HIP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(jwp::k_locpar_accumulate, dim3((unsigned)((b.q + 255) / 256)), dim3(256), 0, c->stream, b.sol, b.mean, b.mean2, b.q, nsamples);
+    HIPCHK(c, hipGetLastError());
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_locpar_get_means(jwas_hip_ctx* c, int64_t q, double* out_mean, double* out_mean2)
+{
+    NEED_LOCPAR(c);
+    NEED(c, out_mean, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, q == c->lp.q, JWAS_HIP_EINVAL, "q (%lld) differs from the number of location parameters (%lld)", (long long)q, (long long)c->lp.q);
+    if (int rc = locpar_finalize(c)) return rc;
+    HIPCHK(c, hipMemcpyAsync(out_mean, c->lp.mean, sizeof(double) * (size_t)q, hipMemcpyDeviceToHost, c->stream));
+    if (out_mean2) HIPCHK(c, hipMemcpyAsync(out_mean2, c->lp.mean2, sizeof(double) * (size_t)q, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int64_t jwas_hip_locpar_estimate_bytes(int64_t n, int64_t nterms, int64_t total_levels)
+{
+    // per term: x, w x (doubles), level, the sorted records (int32), the piece starts and piece sums of its full pieces; per entry
+    // of sol: sol, two means, d, delta, one piece sum (doubles), the level's piece range and one piece start of its own (int32)
+    return nterms * (24 * n + 12 * (n / jwp::kPiece + 2)) + total_levels * (6 * 8 + 2 * 4) + (int64_t)sizeof(double) * jwp::kMaxGroups * 16 * 3;
+}
+
+int jwas_hip_locpar_end(jwas_hip_ctx* c)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    locpar_free(c);
     return JWAS_HIP_OK;
 }
 

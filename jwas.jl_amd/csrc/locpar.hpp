@@ -1,0 +1,161 @@
+// locpar.hpp -- the non-marker location parameters (intercepts, covariates, fixed and i.i.d. random class factors) on the device.
+//
+// Step 1 of the reference's iteration (MCMC/MCMC_BayesianAlphabet.jl:193-220) adds X sol to the residual, forms X'Ri ycorr and runs
+// the single-site scan Gibbs(A, x, b[, vare]) (iterative_solver/solver.jl:143-162) over the mixed model equations, then subtracts
+// X sol again.  The levels of ONE term partition the records, so X_term' W X_term is diagonal and, given the other terms, the
+// levels of a term with a diagonal prior are conditionally independent: sampling a whole term at once and updating the residual
+// IS that scan, written in residual-update form.  The only serial dependence is term after term; a term is three short launches.
+//
+// For level l of a term of trait k (c = inv(R); one trait: c = 1), d_l = sum_{i in l} w_i x_i^2 formed once at set-up:
+//   rho_i  = sum_m c_km r_m,i                                  (one trait: r_i)
+//   S_l    = sum_{i in l} w_i x_i rho_i
+//   lhs_l  = d_l c_kk + prior                                  prior = vare Gi (one trait, the lambda form of random_effects.jl:232),
+//                                                                      Gi_kk (several traits), 0 (a fixed term)
+//   mean_l = (S_l + d_l c_kk sol_l - sum_{m != k} Gi_km u_m,l) / lhs_l
+//   sol_l' = mean_l + z sqrt(s / lhs_l)                        s = vare (one trait), 1 (several); lhs_l == 0: left alone (solver.jl:145)
+//   r_k,i  = T(double(r_k,i) - x_i (sol_l' - sol_l))            one rounding per term
+// z: rng.hpp's Box-Muller normal on the counter (level within its term, iteration, 0x20000000 | term ordinal, 3 + 16 trait).
+//
+// LAYOUT of a term (built on the host when the term is added): the records sorted by level, ties by ascending record; every level
+// cut into PIECES of at most kPiece consecutive records of that order; a lane-group width G (a power of two <= 64, from the mean
+// piece length).  k_locpar_sums gives a piece to G lanes: lane g adds records g, g + G, ... of the piece in that order, the G
+// partial sums are combined by a butterfly (__shfl_xor, offsets G/2 .. 1); k_locpar_draw adds the pieces of a level in piece
+// order.  The order of every addition is fixed by the layout alone -- no floating-point atomics, two runs give identical bits.
+//
+//   k_locpar_sums<T>      piece sums of w x rho        (T = float | double: the residual's element type; arithmetic in double)
+//   k_locpar_draw         one thread per level: S_l, the draw, sol, delta_l = sol_l' - sol_l
+//   k_locpar_apply<T>     one thread per record: r_k,i -= x_i delta[level_i]      (coalesced)
+//   k_locpar_cross        U'U of a random effect: one workgroup per pair of member terms, a fixed strided order
+//   k_locpar_accumulate   running means of sol and sol^2 (output.jl:556-560)
+#pragma once
+#include "rng.hpp"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace jwp {
+
+constexpr int kMaxT = 4;
+constexpr int kMaxGroups = 8;           // random effects per model
+constexpr int kPiece = 1024;            // records per piece
+
+struct SumArgs {
+    const void* r;                      // [nt][ld] residuals (T)
+    int64_t ld;
+    const int32_t* rec;                 // [nin] records of the term, sorted by (level, record); NULL: 0 .. n - 1 (one level)
+    const double* wx;                   // [nin] w_i x_i in that order
+    const int32_t* piece_lo;            // [npieces + 1] piece p = entries piece_lo[p] .. piece_lo[p + 1] of rec / wx
+    double* part;                       // [npieces] out
+    int32_t npieces, G, nt, trait;
+    double c[kMaxT];                    // row `trait` of inv(R) (one trait: {1})
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void k_locpar_sums(const SumArgs A)
+{
+    const int64_t gt = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int G = A.G;
+    const int64_t p = gt / G;
+    const int g = (int)(gt % G);
+    const bool valid = p < A.npieces;
+    double acc = 0.0;
+    if (valid) {
+        const int lo = A.piece_lo[p], hi = A.piece_lo[p + 1];
+        for (int j = lo + g; j < hi; j += G) {
+            const int64_t i = A.rec ? A.rec[j] : j;
+            double rho;
+            if (A.nt == 1) {
+                rho = (double)((const T*)A.r)[i];
+            } else {
+                rho = 0.0;
+                for (int m = 0; m < A.nt; ++m) rho = rho + A.c[m] * (double)((const T*)A.r)[(size_t)m * A.ld + i];
+            }
+            acc = acc + A.wx[j] * rho;
+        }
+    }
+    for (int off = G >> 1; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);      // (groups are aligned to G: never leaves one)
+    if (valid && g == 0) A.part[p] = acc;
+}
+
+struct DrawArgs {
+    const double* part;                 // [npieces]
+    const int32_t* level_piece;         // [nlevels + 1] pieces of level l: level_piece[l] .. level_piece[l + 1]
+    const double* d;                    // [nlevels]
+    double* sol;                        // the whole solution vector
+    double* delta;                      // [nlevels] out
+    int64_t off;                        // this term's first entry of sol
+    int64_t partner_off[kMaxT];         // random effect: the member terms' first entries, this term's own included (slot `pos`, skipped)
+    double gi[kMaxT];                   // ... and row `pos` of Gi
+    int32_t nlevels, npartners, pos;
+    double ckk, prior, s;               // lhs = d ckk + prior, sd = sqrt(s / lhs)
+    uint32_t iter, rep, slot, seed_lo, seed_hi;
+};
+
+__global__ __launch_bounds__(256) void k_locpar_draw(const DrawArgs A)
+{
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= A.nlevels) return;
+    double S = 0.0;
+    for (int p = A.level_piece[l]; p < A.level_piece[l + 1]; ++p) S = S + A.part[p];
+    const double dc = A.d[l] * A.ckk;
+    const double lhs = dc + A.prior;
+    const double old = A.sol[A.off + l];
+    double delta = 0.0;
+    if (lhs != 0.0) {                                                       // (solver.jl:145: zero diagonals are skipped)
+        double num = S + dc * old;
+        for (int m = 0; m < A.npartners; ++m)
+            if (m != A.pos) num = num - A.gi[m] * A.sol[A.partner_off[m] + l];
+        const double mean = num / lhs;
+        const jw::u32x4 w = jw::philox4x32_10((uint32_t)l, A.iter, A.rep, A.slot, A.seed_lo, A.seed_hi);
+        const double u1 = jw::u52(w.x, w.y), u2 = jw::u52(w.z, w.w);
+        const double z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
+        const double now = mean + z * sqrt(A.s / lhs);
+        A.sol[A.off + l] = now;
+        delta = now - old;
+    }
+    A.delta[l] = delta;
+}
+
+// r_k,i -= x_i delta[level_i]; x == NULL: 1, level == NULL: level 0 (intercept / covariate), level < 0: the record is in no level
+template <class T>
+__global__ __launch_bounds__(256) void k_locpar_apply(T* __restrict__ r, const double* __restrict__ x, const int32_t* __restrict__ level,
+                                                      const double* __restrict__ delta, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int l = level ? level[i] : 0;
+    if (l < 0) return;
+    const double dl = delta[l];
+    if (dl == 0.0) return;
+    r[i] = (T)((double)r[i] - (x ? x[i] : 1.0) * dl);
+}
+
+// out[blockIdx.x] = sum_l a[l] b[l]; pair q = blockIdx.x reads offs[2 q], offs[2 q + 1].  Thread j adds levels j, j + 256, ... in
+// that order, the 256 partial sums meet in a fixed tree.
+__global__ __launch_bounds__(256) void k_locpar_cross(const double* __restrict__ sol, const int64_t* __restrict__ offs, int32_t nlevels,
+                                                      double* __restrict__ out)
+{
+    __shared__ double sh[256];
+    const double* a = sol + offs[2 * blockIdx.x];
+    const double* b = sol + offs[2 * blockIdx.x + 1];
+    double acc = 0.0;
+    for (int l = threadIdx.x; l < nlevels; l += 256) acc = acc + a[l] * b[l];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
+}
+
+__global__ __launch_bounds__(256) void k_locpar_accumulate(const double* __restrict__ sol, double* __restrict__ mean, double* __restrict__ mean2,
+                                                           int64_t q, double nsamples)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= q) return;
+    const double v = sol[i];
+    mean[i] = mean[i] + (v - mean[i]) / nsamples;
+    mean2[i] = mean2[i] + (v * v - mean2[i]) / nsamples;
+}
+
+}  // namespace jwp

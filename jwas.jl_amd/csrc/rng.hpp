@@ -11,6 +11,10 @@
 //   slot 2: the liability uniform (liability.hpp), indexed by (INDIVIDUAL, iteration, 0x40000000 | Gibbs round, 2 + 16*trait);
 //           iteration 0 is the set-up draw.  The marker samplers' repetition words are small counts or carry the 0x80000000 bit
 //           (sampler_mt.hpp, f64_path.hpp), the synthesisers use slot 0: no tuple is shared.
+//   slot 3: the location-parameter normal (locpar.hpp), Box-Muller as slot 1, indexed by (LEVEL within its term, iteration,
+//           0x20000000 | term ordinal, 3 + 16*trait).  The tag keeps the repetition word apart from the marker samplers' small
+//           counts, the liabilities' 0x40000000 and the Wishart draws' 0x80000000 (sampler_mt.hpp:533-549, whose slots start at 64)
+//           whatever the slot.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

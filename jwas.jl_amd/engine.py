@@ -555,6 +555,85 @@ class HipEngine:
         self._chk(self._L.jwas_hip_liability_end(self._h))
         self._liab_nthr = {}
 
+    # -- location parameters (jwas_hip_locpar_*; MCMC_BayesianAlphabet.jl:193-220, solver.jl:143-162) ------
+    @staticmethod
+    def locpar_estimate_bytes(n, nterms, total_levels):
+        return _lib.load().jwas_hip_locpar_estimate_bytes(int(n), int(nterms), int(total_levels))
+
+    def locpar_begin(self, ntraits=None):
+        """Start the location-parameter state for the traits of init_state: no terms.  The residual weights are those in force now."""
+        nt = self.ntraits if ntraits is None else int(ntraits)
+        self._chk(self._L.jwas_hip_locpar_begin(self._h, nt))
+        self._locpar_groups = {}
+
+    def locpar_add_covariate(self, trait, x=None):
+        """A one-entry term of `trait`: the covariate x, or the intercept (x = None).  Terms are sampled in the order added."""
+        if x is None:
+            self._chk(self._L.jwas_hip_locpar_add_covariate(self._h, int(trait), self.n, None))
+            return
+        xv = np.ascontiguousarray(x, dtype=np.float64)
+        if xv.ndim != 1:
+            raise ValueError("x must be a vector")
+        self._chk(self._L.jwas_hip_locpar_add_covariate(self._h, int(trait), xv.size, _ptr(xv)))
+
+    def locpar_add_factor(self, trait, level, nlevels, random_group=-1):
+        """A class factor: level[i] in 0..nlevels-1 or -1 (in no level); random_group -1 = fixed, g >= 0 = member of random effect g."""
+        lv = np.ascontiguousarray(level, dtype=np.int32)
+        if lv.ndim != 1:
+            raise ValueError("level must be a vector")
+        self._chk(self._L.jwas_hip_locpar_add_factor(self._h, int(trait), lv.size, _ptr(lv), int(nlevels), int(random_group)))
+        if random_group >= 0:
+            self._locpar_groups[int(random_group)] = self._locpar_groups.get(int(random_group), 0) + 1
+
+    def locpar_size(self):
+        q = C.c_int64()
+        self._chk(self._L.jwas_hip_locpar_size(self._h, C.byref(q)))
+        return q.value
+
+    def locpar_set_sol(self, sol):
+        sv = np.ascontiguousarray(sol, dtype=np.float64)
+        self._chk(self._L.jwas_hip_locpar_set_sol(self._h, sv.size, _ptr(sv)))
+
+    def locpar_get_sol(self):
+        out = np.empty(self.locpar_size(), dtype=np.float64)
+        self._chk(self._L.jwas_hip_locpar_get_sol(self._h, out.size, _ptr(out)))
+        return out
+
+    def locpar_step(self, *, iteration, seed, vare=None, Rinv=None, Gi=(), first_term=0, last_term=-1):
+        """One scan over the terms first_term .. last_term - 1.  vare: the residual variance (one trait); Rinv: inv(R) (several
+        traits); Gi: inv(G) of every random effect, in group order.  Returns {"utu": [U'U per random effect], "step_ms"}."""
+        P, S = _lib.LocparParams(), _lib.LocparStats()
+        P.iteration, P.seed, P.first_term, P.last_term = int(iteration), int(seed), int(first_term), int(last_term)
+        P.vare = 0.0 if vare is None else float(vare)
+        if Rinv is not None:
+            for i, v in enumerate(np.atleast_2d(np.asarray(Rinv, dtype=np.float64)).ravel()):
+                P.Rinv[i] = float(v)
+        groups = getattr(self, "_locpar_groups", {})
+        if len(Gi) != len(groups):
+            raise ValueError(f"Gi must hold one matrix per random effect ({len(groups)}, got {len(Gi)})")
+        for g, M in enumerate(Gi):
+            M = np.atleast_2d(np.asarray(M, dtype=np.float64))
+            if M.shape != (groups.get(g, 0),) * 2:
+                raise ValueError(f"Gi[{g}] must be {groups.get(g, 0)} x {groups.get(g, 0)}")
+            for i, v in enumerate(M.ravel()):
+                P.Gi[16 * g + i] = float(v)
+        self._chk(self._L.jwas_hip_locpar_step(self._h, C.byref(P), C.byref(S)))
+        utu = [np.array(S.utu[16 * g:16 * g + k * k]).reshape(k, k) for g, k in sorted(groups.items())]
+        return {"utu": utu, "step_ms": S.step_ms}
+
+    def locpar_accumulate(self, nsamples):
+        self._chk(self._L.jwas_hip_locpar_accumulate(self._h, float(nsamples)))
+
+    def locpar_get_means(self):
+        """(mean, mean of squares) of sol over the accumulated samples."""
+        m, m2 = np.empty(self.locpar_size(), dtype=np.float64), np.empty(self.locpar_size(), dtype=np.float64)
+        self._chk(self._L.jwas_hip_locpar_get_means(self._h, m.size, _ptr(m), _ptr(m2)))
+        return m, m2
+
+    def locpar_end(self):
+        self._chk(self._L.jwas_hip_locpar_end(self._h))
+        self._locpar_groups = {}
+
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""
         out = np.empty(getattr(self, "n_out", 0), dtype=self.dtype)

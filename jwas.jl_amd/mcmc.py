@@ -3,7 +3,9 @@ that is NOT the marker sweep, driving a sweep engine (jwas.jl_amd.engine.HipEngi
 
 Per iteration (the reference's order, MCMC_BayesianAlphabet.jl:184-421):
   0. categorical / censored traits: engine.liability_sample(...), then the threshold draw                (:186-191, DEVICE)
-  1. location parameters: ycorr += X sol ; rhs = X'ycorr ; single-site Gibbs ; ycorr -= X sol   (:196-220, host)
+  1. location parameters: ycorr += X sol ; rhs = X'ycorr ; single-site Gibbs ; ycorr -= X sol   (:196-220, host, or DEVICE:
+     engine.locpar_step(...), term by term from the resident residual -- location_parameters="device" / "auto")
+  4c. variances of the set_random effects from the device's U'U (sampleVCs, :347-351)            (host)
   2. marker effects: engine.sweep(...)                                                      (:224-290, DEVICE)
   3. pi  ~ Beta / Dirichlet from the sweep's counts                                          (:294-317, host)
   4. marker effect variance from alpha'alpha / ssq / beta'beta                               (:321-326, host)
@@ -64,6 +66,38 @@ def _design(model, df, ids_col):
         cols.append(np.hstack(Xk) if Xk else np.zeros((len(df), 0)))
         labels.append(lab)
     return cols, labels
+
+
+LOCPAR_METHODS = ("locpar_begin", "locpar_add_covariate", "locpar_add_factor", "locpar_step", "locpar_get_sol", "locpar_accumulate",
+                  "locpar_get_means", "locpar_end")
+LOCPAR_AUTO_LEVELS = 2048               # location_parameters="auto": more levels than this run on the device
+
+
+def _location_terms(model, df):
+    """The terms of _design without the dense matrices: per trait a list of (name, kind, values) -- kind "covariate": the column
+    (None: the intercept), kind "factor": (codes, nlevels) with the levels numbered in _design's order -- and _design's labels."""
+    terms, labels = [], []
+    for tl in model.modelTerms:
+        tk, lab = [], []
+        for term in tl:
+            if term.kind == "intercept":
+                tk.append((term.name, "covariate", None))
+                lab.append((term.trait, "intercept", "intercept"))
+            elif term.kind == "covariate":
+                tk.append((term.name, "covariate", df[term.name].to_numpy(dtype=np.float64)))
+                lab.append((term.trait, term.name, term.name))
+            else:
+                if term.name not in df.columns:
+                    raise ValueError(f"{term.name} is not found in the phenotype data (genotype terms must be "
+                                     "Genotypes objects visible to build_model).")
+                lev = df[term.name].astype(str)
+                names = sorted(lev.unique())
+                index = {lv: i for i, lv in enumerate(names)}
+                tk.append((term.name, "factor", (lev.map(index).to_numpy(dtype=np.int32), len(names))))
+                lab.extend((term.trait, term.name, lv) for lv in names)
+        terms.append(tk)
+        labels.append(lab)
+    return terms, labels
 
 
 def genetic2marker(Mi, pi, method, t=1):
@@ -286,10 +320,21 @@ def _gibbs(A, x, b, rng, vare=None):
             x[i] = rng.standard_normal() * np.sqrt(invlhs * (vare if vare is not None else 1.0)) + mu
 
 
+def host_location_step(engine, Xf0, lhs, sol, w64, rng, vare, ftype):
+    """Step 1 of a single-trait iteration on the host (MCMC_BayesianAlphabet.jl:196-220): the residual comes to the host, the dense
+    design matrix Xf0 adds X sol, one scan of _gibbs on (lhs, X'R^-1 ycorr), and the residual goes back."""
+    r = engine.get_residual(0).astype(np.float64)
+    r += Xf0 @ sol
+    rhs = Xf0.T @ (w64 * r)                                             # MCMC_BayesianAlphabet.jl:211
+    _gibbs(lhs, sol, rhs, rng, float(vare))
+    r -= Xf0 @ sol
+    engine.set_residual(r.astype(ftype), 0)
+
+
 def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed, starting_value,
               fast_blocks, independent_blocks=False, heterogeneous_residuals=False, outputEBV, output_heritability=True, output_folder, printout_frequency, memory_guard, memory_guard_ratio,
               missing_phenotypes, device, block_size, gram_mode, engine, printout_model_info,
-              output_samples_for_all_parameters, double_precision=False, blocks_per_launch=None):
+              output_samples_for_all_parameters, double_precision=False, blocks_per_launch=None, location_parameters="auto"):
     import pandas as pd
     Mi = model.M[0]
     t = model.nModels
@@ -449,8 +494,10 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     w64 = np.ones(len(ph)) if invw is None else invw.astype(np.float64)
 
     # ---- default priors (input_data_validation.jl:296-350, tools4genotypes.jl:353-478, build_MME.jl:128-141)
+    rnd = list(getattr(model, "rndTrmVec", []))
     varg = np.diag(phenovar) * 0.5
-    vare0 = np.diag(phenovar) * 0.5
+    vare0 = np.diag(phenovar) * 0.5 / (1 + len(rnd))       # nongenetic_random_count (input_data_validation.jl:301-313): only a set_random term changes it
+    vare_rnd = vare0.copy()                                # ... what the random effects' default prior reads (:352-365)
     R = model.R
     if R.val is False:
         single_cat = t == 1 and traits_type[0] in ("categorical", "categorical(binary)")
@@ -461,6 +508,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             vare0[k, :] = 0.0
             vare0[:, k] = 0.0
             vare0[k, k] = 1.0
+            vare_rnd[k, k] = 1.0
         R.val = ftype(vare0[0, 0]) if t == 1 else vare0.astype(ftype)
         R.scale = float(R.val) * (float(R.df) - 2) / float(R.df) if t == 1 else np.asarray(R.val, dtype=np.float64) * (float(R.df) - t - 1)
         if t > 1 and len(binary_index) == t:
@@ -468,6 +516,12 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             R.estimate_variance = False
     if Mi.G.val is False and Mi.genetic_variance.val is False:
         Mi.genetic_variance.val = varg[0, 0] if t == 1 else varg
+    for re_ in rnd:                                                       # :352-365
+        if re_.Gi.val is False:
+            kk = len(re_.traits)
+            G0_ = np.diag([vare_rnd[m, m] for m in re_.traits])
+            re_.Gi.val = np.linalg.inv(G0_)
+            re_.Gi.scale = G0_ * (float(re_.Gi.df) - kk - 1)
     pi = Mi.pi
     if isinstance(pi, dict):
         # the reference's multi-trait Pi: Dict(state vector => probability), e.g. Dict([1.0,0.0] => 0.1, ...)
@@ -770,6 +824,34 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     from .engine import SectionSolvePolicy
     solve_policy = SectionSolvePolicy(section_solve, 4 * (p // 256))
 
+    # ---- location parameters: on the host (dense design matrices, today's path) or on the device (csrc/locpar.hpp)
+    lp_terms, labels = _location_terms(model, ph)
+    q = [len(lab) for lab in labels]
+    lp_device = location_parameters == "device" or (location_parameters == "auto" and (bool(rnd) or sum(q) > LOCPAR_AUTO_LEVELS))
+    if lp_device and t > 1 and has_missing:
+        # the reference's per-record Ri (mkRi, residual.jl:2-44) does not factor as kron(inv(R), diag(w))
+        if not rnd and location_parameters == "auto":
+            lp_device = False
+        else:
+            raise NotImplementedError("location parameters on the device need complete multi-trait records (the per-record Ri of "
+                                      "partially missing records stays on the host path, which has no random effects)")
+    if rnd and not lp_device:
+        raise NotImplementedError('set_random effects run on the device: location_parameters="host" has no random effects')
+    if lp_device:
+        eng_ = engine if engine is not None else (Mi.device_backend if devres else None)
+        missing_ = [m_ for m_ in LOCPAR_METHODS if eng_ is not None and not hasattr(eng_, m_)]
+        if missing_:
+            raise NotImplementedError("location parameters on the device need an engine with the locpar step (" + ", ".join(missing_)
+                                      + " missing); the package has no CPU fallback")
+        for g_, re_ in enumerate(rnd):
+            for m in re_.traits:
+                kind_ = [kd for nm, kd, _ in lp_terms[m] if nm == re_.name]
+                if kind_ != ["factor"]:
+                    raise NotImplementedError(f"set_random: {re_.name} must be one class factor of trait {model.lhsVec[m]} "
+                                              "(random covariates stay on the reference)")
+        if len(rnd) > 8:
+            raise NotImplementedError("at most 8 set_random effects on the device")
+
     # ---- engine (the only engine shipped is the HIP one; there is no CPU fallback)
     own_engine = engine is None
     if own_engine:
@@ -790,6 +872,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             need += nb_ * (4 + 1024 * (4 + 4 * 8)) + 4 * 8 * (-(-n // 256)) * nb_ * block_size
         if double_precision and mt_pervar:
             need += p * t * t * 8 * 2                              # Float64 multi-trait BayesA/B: the covariances and their inverses in double
+        if lp_device:                                              # the term layouts, sol and its means (jwas_hip_locpar_estimate_bytes)
+            need += HipEngine.locpar_estimate_bytes(n, sum(len(tk) for tk in lp_terms), sum(q))
         if outputEBV and not out_same:                             # Mi.output_genotypes: a second dense matrix (n_out x p)
             need += (8 if double_precision else 4) * ((len(out_rows) + 255) // 256 * 256) * p
         engine = HipEngine(device, precision=64 if double_precision else 32)
@@ -857,9 +941,19 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         engine.select_block_size(cur_bs)
     engine.init_state(mt_method if t > 1 else method, t)
 
-    # ---- fixed effects
-    Xf, labels = _design(model, ph, idcol)
-    q = [x.shape[1] for x in Xf]
+    # ---- location parameters: the terms go to the device (csrc/locpar.hpp) or the host builds its dense design matrices
+    if lp_device:
+        engine.locpar_begin(t)
+        for k in range(t):                                               # trait by trait, term by term: the reference's equation order
+            for nm, kind_, val in lp_terms[k]:
+                if kind_ == "covariate":
+                    engine.locpar_add_covariate(k, val)
+                else:
+                    grp = [g_ for g_, re_ in enumerate(rnd) if re_.name == nm and k in re_.traits]
+                    engine.locpar_add_factor(k, val[0], val[1], grp[0] if grp else -1)
+        Xf = None
+    else:
+        Xf, labels = _design(model, ph, idcol)
     sol = np.zeros(sum(q))
     off = np.cumsum([0] + q)
 
@@ -911,10 +1005,15 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     pervar = method == "BayesB" and not lasso                           # per-marker variances, no common variance to report
     if t == 1 and method in ("BayesC", "BayesB") and np.ndim(pi) == 0:
         pi = float(pi)
-    if t > 1:
+    if lp_device:
+        pass
+    elif t > 1:
         lhs_blocks = [[Xf[k].T @ (w64[:, None] * Xf[l]) for l in range(t)] for k in range(t)]    # X'RiX, Ri = kron(R^-1, diag(w))
     else:
         lhs = Xf[0].T @ (w64[:, None] * Xf[0])                          # X'R^-1 X (build_MME.jl:339)
+
+    def _gi64(re_):
+        return np.asarray(re_.Gi.val, dtype=np.float64)
 
     # ---- accumulators and sample files (output.jl:320-437)
     run_sol, run_vare = _Running(sol), _Running(vare)
@@ -959,6 +1058,14 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     bin_writers = [MarkerSampleWriter(os.path.join(output_folder, f"MCMC_samples_marker_effects_{name}_{tr}.bin"), Mi.markerID)
                    for tr in model.lhsVec]
 
+    rnd_keys, run_rnd = [], []
+    for re_ in rnd:                                                     # output.jl:348-351,401-405
+        key_ = "_".join(re_.term_array) + "_variances"
+        kk = len(re_.term_array)
+        _open(key_, [f"{re_.term_array[a]}_{re_.term_array[b]}" for a in range(kk) for b in range(kk)])
+        rnd_keys.append(key_)
+        run_rnd.append(_Running(np.zeros(kk * kk)))
+    lp_utu = None
     liab_files = {}                                                     # output.jl:367-372 (no header lines, as there)
     for k in liab_traits:
         liab_files[("liabilities", k)] = open(os.path.join(output_folder, f"MCMC_samples_liabilities_{model.lhsVec[k]}.txt"), "w")
@@ -994,15 +1101,19 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                         thresholds[k][i] = rng.uniform(mx[i], mn[i])
                     engine.set_thresholds(k, thresholds[k])              # :160
 
-            # 1. location parameters (host)
-            if sum(q):
+            # 1. location parameters: on the device (solver.jl:143-162 term by term, csrc/locpar.hpp) ...
+            if lp_device:
+                if sum(q):
+                    if t == 1:
+                        lp_st = engine.locpar_step(iteration=it, seed=seed_int, vare=float(vare), Gi=[_gi64(re_) for re_ in rnd])
+                    else:
+                        Rinv_ = np.linalg.inv(np.asarray(vare, dtype=np.float64))
+                        lp_st = engine.locpar_step(iteration=it, seed=seed_int, Rinv=(Rinv_ + Rinv_.T) / 2, Gi=[_gi64(re_) for re_ in rnd])
+                    lp_utu = lp_st["utu"]
+            # ... or on the host
+            elif sum(q):
                 if t == 1:
-                    r = engine.get_residual(0).astype(np.float64)
-                    r += Xf[0] @ sol
-                    rhs = Xf[0].T @ (w64 * r)                               # MCMC_BayesianAlphabet.jl:211
-                    _gibbs(lhs, sol, rhs, rng, float(vare))
-                    r -= Xf[0] @ sol
-                    engine.set_residual(r.astype(ftype), 0)
+                    host_location_step(engine, Xf[0], lhs, sol, w64, rng, vare, ftype)
                 else:
                     R0 = np.asarray(vare, dtype=np.float64)
                     Rinv = np.linalg.inv(R0)
@@ -1136,6 +1247,16 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 gv = Gvec.astype(np.float64) if pervar else np.atleast_1d(np.float64(Gval))
                 Mi.G.scale = float(rng.gamma(gv.size * Gdf / 2 + 1, 1.0 / (np.sum(Gdf / (2 * gv)) + 1)))
 
+            # 4c. variances of the random effects (sampleVCs, variance_components.jl:115-147; MCMC_BayesianAlphabet.jl:347-351):
+            #     G0 ~ InvWishart(df + q, scale + U'U) from the cross-products the device returned with step 1
+            for g_, re_ in enumerate(rnd):
+                if re_.Gi.estimate_variance:
+                    nlev_ = next(val[1] for nm, kd, val in lp_terms[re_.traits[0]] if nm == re_.name)
+                    S_ = np.asarray(re_.Gi.scale, dtype=np.float64) + lp_utu[g_]
+                    G0_ = _inverse_wishart_batch(rng, float(re_.Gi.df) + nlev_, ((S_ + S_.T) / 2)[None])[0]
+                    Gi_ = np.linalg.inv(G0_.astype(ftype))               # Float32.(G0) unless double_precision (:138-140)
+                    re_.Gi.val = (Gi_ + Gi_.T) / 2
+
             # 5. residual variance (variance_components.jl:60-66,82-112), re-cast to Float32 (:368-370)
             if R.estimate_variance:
                 if t > 1 and R.constraint:                                  # variance_components.jl:104-109
@@ -1155,7 +1276,16 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             # 6. save (MCMC_BayesianAlphabet.jl:399-413, output.jl:443-604)
             if it > burnin and (it - burnin) % output_samples_frequency == 0:
                 k = (it - burnin) / output_samples_frequency
-                run_sol.add(sol, k)
+                if lp_device:
+                    engine.locpar_accumulate(k)                             # (running means on the device, read once at the end)
+                    if term_cols:
+                        sol = engine.locpar_get_sol()
+                else:
+                    run_sol.add(sol, k)
+                for g_, re_ in enumerate(rnd):                              # output.jl:449-452
+                    Gv_ = np.linalg.inv(_gi64(re_)).ravel()
+                    run_rnd[g_].add(Gv_, k)
+                    files[rnd_keys[g_]].write(",".join(repr(float(v)) for v in Gv_) + "\n")
                 run_vare.add(vare, k)
                 if run_varg is not None:
                     run_varg.add(Gval, k)
@@ -1223,13 +1353,23 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     # ---- results (output.jl:108-212)
     out = {}
     rows_lp = []
+    if lp_device:
+        lp_mean, lp_mean2 = engine.locpar_get_means() if sum(q) else (np.zeros(0), np.zeros(0))
+        lp_sd = np.sqrt(np.abs(lp_mean2 - lp_mean ** 2))
+        engine.locpar_end()
+    else:
+        lp_mean, lp_sd = run_sol.mean, run_sol.sd()
     for k in range(t):
         for i, (tr, eff, lev) in enumerate(labels[k]):
-            rows_lp.append((tr, eff, lev, run_sol.mean[off[k] + i], run_sol.sd()[off[k] + i]))
+            rows_lp.append((tr, eff, lev, lp_mean[off[k] + i], lp_sd[off[k] + i]))
     out["location parameters"] = pd.DataFrame(rows_lp, columns=["Trait", "Effect", "Level", "Estimate", "SD"])
     cov = rnames if t > 1 else [model.lhsVec[0]]
     out["residual variance"] = pd.DataFrame({"Covariance": cov, "Estimate": np.atleast_1d(run_vare.mean).ravel(),
                                              "SD": np.atleast_1d(run_vare.sd()).ravel()})
+    for g_, re_ in enumerate(rnd):
+        kk = len(re_.term_array)
+        out[rnd_keys[g_]] = pd.DataFrame({"Covariance": [f"{re_.term_array[a]}_{re_.term_array[b]}" for a in range(kk) for b in range(kk)],
+                                          "Estimate": run_rnd[g_].mean, "SD": run_rnd[g_].sd()})
     frames = []
     for k, tr in enumerate(model.lhsVec):
         ma, ma2, md = engine.posterior(k)
