@@ -471,6 +471,29 @@ int  jwas_hip_sweep(jwas_hip_ctx* ctx, const jwas_sweep_params* params, jwas_swe
  * [29] ping-pong blocks staged a second time, [30] / [31] multi-trait skip and verify: blocks in which the serial wave took the
  * chain over again / 64-marker sub-blocks evaluated by a helper wave. */
 int  jwas_hip_last_sweep_counters(jwas_hip_ctx* ctx, uint64_t* out, int32_t n);
+/* Which schedule the LAST sweep ran (no reference counterpart).  The library picks among several kernel instantiations and
+ * placements per sweep -- from the block size, the previous sweep's number of effect changes and the JWAS_HIP_* switches; all of
+ * them are the same chain.  One bit per decision, so that a test can prove which variant it covered.  0 before the first sweep
+ * of a chain and on Float64 contexts (one schedule). */
+enum jwas_hip_schedule_flags {
+    JWAS_HIP_SCHED_INDEPENDENT      = 1u << 0,   /* independent blocks (jwas_sweep_params.independent_blocks) */
+    JWAS_HIP_SCHED_GROUPED          = 1u << 1,   /* grouped launches (jwas_sweep_params.group_launch took effect) */
+    JWAS_HIP_SCHED_GROUP_PP_KERNEL  = 1u << 2,   /* grouped: the instantiation with ping-pong samplers / cooperative apply compiled in
+                                                    (clear: the steady-state instantiation) */
+    JWAS_HIP_SCHED_GROUP_PINGPONG   = 1u << 3,   /* grouped: at least one launch sampled with one workgroup per block */
+    JWAS_HIP_SCHED_GROUP_COOP       = 1u << 4,   /* grouped: cooperative apply of the merged change list */
+    JWAS_HIP_SCHED_QUIET_XCD        = 1u << 5,   /* at least one step launch kept workgroup ids = 0 mod 8 off the streaming work
+                                                    (clear: every launch streamed on all eight XCDs) */
+    JWAS_HIP_SCHED_COOP_APPLY       = 1u << 6,   /* one block per launch: cooperative apply of the block's changes */
+    JWAS_HIP_SCHED_DENSE_BIG        = 1u << 7,   /* single-trait sweep under a uniform pi = 0 (the Rule D instantiation) */
+    JWAS_HIP_SCHED_DENSE_MT         = 1u << 8,   /* multi-trait: at least one block sampled by the dense-walk-only instantiation */
+    JWAS_HIP_SCHED_CORR_HELPER      = 1u << 9,   /* single-trait dense sweep: at least one block's lookahead correction formed by the
+                                                    helper workgroup */
+    JWAS_HIP_SCHED_SECTION_SOLVE    = 1u << 10,  /* Rule T section inverses were formed (jwas_sweep_params.section_solve took effect) */
+    JWAS_HIP_SCHED_COMPACT_OFF_SHIFT = 11,       /* two bits: the low two bits of JWAS_HIP_COMPACT_OFF (0: the compact candidate chain) */
+    JWAS_HIP_SCHED_COMPACT_OFF_MASK = 3u << 11
+};
+int  jwas_hip_last_sweep_schedule(jwas_hip_ctx* ctx, uint32_t* flags);
 
 /* ---- marker shards over the GPUs of one node (one context per GPU / process) -------------------------------
  * The single-site chain is sequential in the marker index; what the reference ships for parallel blocks is

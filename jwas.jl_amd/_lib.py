@@ -26,6 +26,7 @@ SYMBOLS = [
     "jwas_hip_get_state", "jwas_hip_set_residual", "jwas_hip_get_residual", "jwas_hip_residual_dev",
     "jwas_hip_residual_to_dev", "jwas_hip_residual_from_dev",
     "jwas_hip_residual_sub_xalpha", "jwas_hip_mul_alpha", "jwas_hip_load_output_dense_f32", "jwas_hip_mul_alpha_output", "jwas_hip_window_sums", "jwas_hip_window_sums2", "jwas_hip_set_kernel_timing", "jwas_hip_sweep", "jwas_hip_last_sweep_counters",
+    "jwas_hip_last_sweep_schedule",
     "jwas_hip_accumulate", "jwas_hip_get_posterior",
     "jwas_hip_load_jgb2", "jwas_hip_load_packed2bit", "jwas_hip_alloc_packed2bit", "jwas_hip_storage_info",
     "jwas_hip_set_xpx", "jwas_hip_estimate_bytes_storage", "jwas_hip_add_block_size", "jwas_hip_select_block_size",
@@ -50,6 +51,13 @@ SYMBOLS = [
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
+# enum jwas_hip_schedule_flags (jwas_hip_last_sweep_schedule): name -> bit
+SCHEDULE_FLAGS = {
+    "INDEPENDENT": 1 << 0, "GROUPED": 1 << 1, "GROUP_PP_KERNEL": 1 << 2, "GROUP_PINGPONG": 1 << 3, "GROUP_COOP": 1 << 4,
+    "QUIET_XCD": 1 << 5, "COOP_APPLY": 1 << 6, "DENSE_BIG": 1 << 7, "DENSE_MT": 1 << 8, "CORR_HELPER": 1 << 9,
+    "SECTION_SOLVE": 1 << 10,
+}
+SCHEDULE_COMPACT_OFF_SHIFT, SCHEDULE_COMPACT_OFF_MASK = 11, 3 << 11
 
 
 class SweepParams(C.Structure):
@@ -158,6 +166,7 @@ def load():
     L.jwas_hip_residual_from_dev.argtypes = [vp, i32, vp]
     L.jwas_hip_set_kernel_timing.argtypes = [vp, i32]
     L.jwas_hip_last_sweep_counters.argtypes = [vp, C.POINTER(C.c_uint64), i32]
+    L.jwas_hip_last_sweep_schedule.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.jwas_hip_residual_sub_xalpha.argtypes = [vp, i32]
     L.jwas_hip_mul_alpha.argtypes = [vp, i32, vp]
     L.jwas_hip_load_output_dense_f32.argtypes = [vp, vp, i64, i64, i64]

@@ -110,6 +110,7 @@ struct jwas_hip_ctx {
     int timing_stride = 0;
     double last_events = -1.0;          // effect changes of the previous sweep (-1: none yet)
     unsigned long long last_counters[kNCounters] = {};      // the sampler's diagnostics counters of the previous sweep
+    uint32_t last_schedule = 0;         // JWAS_HIP_SCHED_* bits of the last sweep sweep_enqueue put on the stream
     double event_overhead_ms = 0.0;     // mean HIP-event interval around an empty launch (calibration)
     std::vector<hipEvent_t> kev;        // pairs of events around sampled k_update_partial launches
     // marker-shard reconcile (jwas_hip_comm_init / jwas_hip_sweep_sharded): RCCL communicator on this context's device
@@ -1105,6 +1106,7 @@ int jwas_hip_init_state(jwas_hip_ctx* c, int32_t method, int32_t nt)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_state(c);
     c->method = method; c->ntraits = nt;
+    c->last_events = -1.0; c->last_schedule = 0;   // a new chain: its first sweep has no previous one to take a schedule from
     c->lb.inited = false;                          // (the residual is zeroed below: the liabilities no longer belong to it)
     const size_t fb = sizeof(float) * (size_t)nt * c->p;
     HIPCHK(c, hipMalloc(&c->alpha, fb));
@@ -2089,13 +2091,19 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
     }
     const int compact_off = std::getenv("JWAS_HIP_COMPACT_OFF") != nullptr ? std::atoi(std::getenv("JWAS_HIP_COMPACT_OFF")) : 0;          // (tests: the speculative rounds instead of the compact chain)
     // GROUPED LAUNCHES (jwas_sweep_params.group_launch; jwas_hip_setup_groups; sweep.hpp k_group_step): gm blocks per launch.
-    // Single-trait single-pass sweeps on uniform blocks; every other sweep ignores the flag.  JWAS_HIP_GROUPS=0 switches it off.
+    // Single-trait single-pass sweeps on uniform blocks; every other sweep ignores the flag.  JWAS_HIP_GROUPS=0 switches it off (then
+    // the chain runs one block per launch: the same trajectory within the oracle's bar, NOT the same bits -- the corrections are
+    // summed in another order; tests/test_gpu_schedule_variants.py).
     static const int groups_env = std::getenv("JWAS_HIP_GROUPS") ? std::atoi(std::getenv("JWAS_HIP_GROUPS")) : 1;
     const auto& SET = c->sets[(size_t)c->set_index];
     const bool grouped = P->group_launch != 0 && groups_env != 0 && SET.gm >= 2 && !is_mt_method(c->method) && P->nreps == 1 && !independent &&
                          !c->row_mode && c->starts.empty() && !dense_big;
     int64_t last_launch = nb;                                   // index of the sweep's last launch
+    // which of the variants below this sweep takes (jwas_hip_last_sweep_schedule): one bit per decision
+    uint32_t sched = (dense_big ? JWAS_HIP_SCHED_DENSE_BIG : 0u) | (solve_blocks > 0 ? JWAS_HIP_SCHED_SECTION_SOLVE : 0u) |
+                     (((uint32_t)compact_off << JWAS_HIP_SCHED_COMPACT_OFF_SHIFT) & JWAS_HIP_SCHED_COMPACT_OFF_MASK);
     if (independent) {
+        sched |= JWAS_HIP_SCHED_INDEPENDENT;
         int rc = sweep_independent(c, &ev_list, dense_big, dense_big_off, compact_off, P->nreps);
         if (rc) return rc;
     } else if (grouped) {
@@ -2109,10 +2117,13 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
         // of them re-reading the changed columns; taken per launch from 32 changes on) in the high-turnover sweeps -- the ones that run
         // the ping-pong samplers: config 3 25.0 -> 24.3 ms, fixed pi 25.6 -> 25.1 ms per sweep.  Same bits (the chain per row is the
         // list's order either way; bounded wait with the redundant apply as its fall-back).  JWAS_HIP_GROUP_COOP=0|1 overrides.
+        // (The switches of this block are read once per process; tests/test_gpu_schedule_variants.py runs every combination of
+        // JWAS_HIP_PINGPONG x JWAS_HIP_GROUP_COOP x JWAS_HIP_QUIET_XCD in a process of its own and compares the bits.)
         static const int gcoop_env = std::getenv("JWAS_HIP_GROUP_COOP") ? std::atoi(std::getenv("JWAS_HIP_GROUP_COOP")) : -1;
         const bool gcoop = c->sync_cnt != nullptr && !c->packed &&
                            (gcoop_env >= 0 ? gcoop_env != 0 : (bs <= 512 || c->last_events < 0 || c->last_events > 0.0125 * (double)c->p));
         if (gcoop) HIPCHK(c, hipMemsetAsync(c->sync_cnt, 0, sizeof(int) * 2 * c->nrg, c->stream));
+        sched |= JWAS_HIP_SCHED_GROUPED | (gcoop ? JWAS_HIP_SCHED_GROUP_COOP : 0u);
         const int off_w = (int)(2 * gb), off_p = off_w + 2 * bs, off_z = off_p + 2 * bs;
         for (int64_t K = 0; K <= ng; ++K) {
             UpdateArgs U;
@@ -2213,6 +2224,8 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
                 while (c->kev.size() < 2 * (ntimed + 1)) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->kev.push_back(e); }
                 HIPCHK(c, hipEventRecord(c->kev[2 * ntimed], c->stream));
             }
+            sched |= (G.pp_kernel ? JWAS_HIP_SCHED_GROUP_PP_KERNEL : 0u) | (G.pp ? JWAS_HIP_SCHED_GROUP_PINGPONG : 0u) |
+                     (U.quiet_xcd ? JWAS_HIP_SCHED_QUIET_XCD : 0u);
             HIPCHK(c, launch_group_st(step_launch_of(c), c->method, U, uidx, udel, SS, G));
             if (timed) {
                 HIPCHK(c, hipEventRecord(c->kev[2 * ntimed + 1], c->stream));
@@ -2235,6 +2248,7 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
     const char* efc = std::getenv("JWAS_HIP_COOP_APPLY");
     const int fc = efc ? std::atoi(efc) : -1;
     const bool coop = c->sync_cnt != nullptr && (fc >= 0 ? fc != 0 : (dense_big || c->last_events > 0.25 * (double)c->p));
+    if (coop) sched |= JWAS_HIP_SCHED_COOP_APPLY;
     for (int64_t k = 0; k <= nb; ++k) {
         UpdateArgs U;
         U.r_in = c->r + ((k + 1) & 1) * rstride; U.r_out = c->r + (k & 1) * rstride;
@@ -2282,6 +2296,7 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
             if (S.tsec != nullptr || (st_helper && S.b == bs && S.b_next > 0)) {       // (the helper workgroup lives on the quiet XCD: ids = 0 mod 8 do no streaming)
                 S.xch = c->xch; c->xch_epoch = (c->xch_epoch + 8) & 0x3fffffff; S.xch_epoch = c->xch_epoch;
                 U.quiet_xcd = 1;
+                if (S.tsec == nullptr) sched |= JWAS_HIP_SCHED_CORR_HELPER;
             }
             S.lines_after = (sb + 2 < nb) ? (int)(((int64_t)blk_b(c, sb + 1) * blk_b(c, sb + 2) + 31) / 32) : 0;
             S.corr_in = c->corr + (sb & 1) * (size_t)kMaxT * bs;
@@ -2303,6 +2318,7 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
             bool dmt = dense_mt;
             if (dmt && c->block_size == 256 && sb >= 0) dmt = !dense_big_off && S.b == 256;
             if (sb >= 0 && S.tsec != nullptr) dmt = true;          // Rule T lives in dense_big_mt: the dense-walk-only instantiation, whatever the last sweep did
+            sched |= (U.quiet_xcd ? JWAS_HIP_SCHED_QUIET_XCD : 0u) | (dmt && sb >= 0 ? JWAS_HIP_SCHED_DENSE_MT : 0u);
             HIPCHK(c, launch_step_any(c, U, S, sb >= 0, dense_big || dmt));
         }
         if (c->row_mode && U.b > 0) {          // the block's partial RHS summed over the ranks' individuals, before its sampler runs
@@ -2339,6 +2355,7 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
         default: hipLaunchKernelGGL((k_marker_stats<4>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, c->alpha, c->beta, c->delta, gamma_dev, c->stat_out);
     }
     HIPCHK(c, hipGetLastError());
+    c->last_schedule = sched;
     *ntimed_out = ntimed;
     *timed_bytes_out = timed_bytes;
     return JWAS_HIP_OK;
@@ -2507,6 +2524,7 @@ static int f64_init_state(jwas_hip_ctx* c, int32_t method, int32_t nt)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     f64_free_state(c);
     c->method = method; c->ntraits = nt;
+    c->last_events = -1.0; c->last_schedule = 0;   // a new chain: its first sweep has no previous one to take a schedule from
     c->lb.inited = false;                          // (the residual is zeroed below: the liabilities no longer belong to it)
     const size_t db = sizeof(double) * (size_t)nt * c->p;
     const size_t delb = method == JWAS_HIP_BAYESR ? sizeof(int32_t) * (size_t)c->p : db;
@@ -3069,6 +3087,13 @@ int jwas_hip_last_sweep_counters(jwas_hip_ctx* c, uint64_t* out, int32_t n)
 {
     NEED(c, c && out && n >= 0, JWAS_HIP_EINVAL, "NULL argument");
     for (int i = 0; i < n; ++i) out[i] = i < kNCounters ? (uint64_t)c->last_counters[i] : 0u;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_last_sweep_schedule(jwas_hip_ctx* c, uint32_t* flags)
+{
+    NEED(c, c && flags, JWAS_HIP_EINVAL, "NULL argument");
+    *flags = c->last_schedule;
     return JWAS_HIP_OK;
 }
 

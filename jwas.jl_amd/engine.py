@@ -379,6 +379,18 @@ class HipEngine:
         self._chk(self._L.jwas_hip_last_sweep_counters(self._h, out, 32))
         return [int(v) for v in out]
 
+    def last_sweep_schedule(self, names=False):
+        """Which schedule variant the last sweep ran (jwas_hip_last_sweep_schedule): the JWAS_HIP_SCHED_* mask, or with names=True
+        a dict {name: bool} of _lib.SCHEDULE_FLAGS plus "COMPACT_OFF" (0..3)."""
+        out = C.c_uint32(0)
+        self._chk(self._L.jwas_hip_last_sweep_schedule(self._h, C.byref(out)))
+        mask = int(out.value)
+        if not names:
+            return mask
+        d = {k: bool(mask & bit) for k, bit in _lib.SCHEDULE_FLAGS.items()}
+        d["COMPACT_OFF"] = (mask & _lib.SCHEDULE_COMPACT_OFF_MASK) >> _lib.SCHEDULE_COMPACT_OFF_SHIFT
+        return d
+
     def set_kernel_timing(self, stride):
         self._chk(self._L.jwas_hip_set_kernel_timing(self._h, int(stride)))
 
