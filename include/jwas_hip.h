@@ -458,6 +458,24 @@ int  jwas_hip_locpar_get_means(jwas_hip_ctx* ctx, int64_t q, double* out_mean, d
 /* Device bytes of the state for nterms terms with total_levels entries of sol over n records (pure; an upper bound). */
 int64_t jwas_hip_locpar_estimate_bytes(int64_t n, int64_t nterms, int64_t total_levels);
 int  jwas_hip_locpar_end(jwas_hip_ctx* ctx);
+/* A random effect whose levels are correlated: the polygenic effect of set_random(model, "animal", ped, G) (random_effects.jl:52,
+ * 164-172), covariance inv(V) (x) G with V the sparse A-inverse.  jwas_hip_lp_set_group_structure gives random effect
+ * `random_group` the inverse covariance V among its nlevels levels as a FULL symmetric CSR matrix (int64 row pointers, int32
+ * ascending column indices, doubles); it is called after _begin and before the effect's first member term is added, and every
+ * member must then have nlevels levels.  The data sums of a member term are the ones of any term; the prior sum_j V_lj u_j couples
+ * only neighbours in V, so the library colours the graph of V on the host (levels in ascending order, the smallest colour no
+ * neighbour holds) and samples the levels of one colour per launch, the colours in order: a systematic-scan Gibbs sampler with a
+ * fixed visiting order (csrc/locpar.hpp has the formulas and the layout; no floating-point atomics, identical bits run to run).
+ * A level without records is drawn from its prior conditional.  jwas_locpar_stats.utu of such an effect holds U' V U.
+ * JWAS_HIP_EINVAL: non-finite values, unsorted or duplicate columns, a missing or non-positive diagonal, a pattern or values that
+ * are not exactly symmetric, a member added later with another nlevels; JWAS_HIP_ESTATE: before _begin, once a member of the effect
+ * exists or sol was used; JWAS_HIP_EUNSUP: a communicator attached.  (The three entry points carry the prefix jwas_hip_lp_.) */
+int  jwas_hip_lp_set_group_structure(jwas_hip_ctx* ctx, int32_t random_group, int64_t nlevels, const int64_t* indptr,
+                                     const int32_t* indices, const double* values);
+/* The colour of every level (0 .. *out_ncolors - 1) of the structure of random effect random_group: the visiting order. */
+int  jwas_hip_lp_get_group_colors(jwas_hip_ctx* ctx, int32_t random_group, int64_t nlevels, int32_t* out_color, int32_t* out_ncolors);
+/* Device bytes of a structure of nlevels levels and nnz stored entries (pure; an upper bound). */
+int64_t jwas_hip_lp_structure_estimate_bytes(int64_t nlevels, int64_t nnz);
 
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the

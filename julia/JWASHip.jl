@@ -296,6 +296,25 @@ end
 hip_locpar_estimate_bytes(n::Integer, nterms::Integer, total_levels::Integer) =
     ccall((:jwas_hip_locpar_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int64), n, nterms, total_levels)
 hip_locpar_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_locpar_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+"The inverse covariance among the levels of the random_group-th set_random effect (the pedigree form: `Float64.(AInverse(ped))`), a
+full symmetric `SparseMatrixCSC` -- its columns ARE the rows of the CSR matrix the library takes.  After `hip_locpar_begin!`, before
+the effect's first `hip_locpar_add_factor!`.  `hip_locpar_step!` then samples the effect colour by colour and returns U'VU for it."
+function hip_locpar_set_group_structure!(b::HipBackend, random_group::Integer, V)
+    indptr = Int64.(V.colptr) .- Int64(1)
+    indices = Int32.(V.rowval) .- Int32(1)
+    values = Float64.(V.nzval)
+    hip_check(b.ctx, ccall((:jwas_hip_lp_set_group_structure, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}),
+                           b.ctx, random_group - 1, length(indptr) - 1, indptr, indices, values))
+end
+"(colours 1..ncolors of the nlevels levels, ncolors): the order `hip_locpar_step!` visits the levels of a structured effect in."
+function hip_locpar_group_colors(b::HipBackend, random_group::Integer, nlevels::Integer)
+    color = Vector{Int32}(undef, nlevels); nc = Ref{Int32}(0)
+    hip_check(b.ctx, ccall((:jwas_hip_lp_get_group_colors, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ref{Int32}),
+                           b.ctx, random_group - 1, nlevels, color, nc))
+    return color .+ Int32(1), Int(nc[])
+end
+hip_locpar_structure_estimate_bytes(nlevels::Integer, nnz::Integer) =
+    ccall((:jwas_hip_lp_structure_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64), nlevels, nnz)
 
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =

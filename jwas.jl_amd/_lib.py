@@ -47,6 +47,7 @@ SYMBOLS = [
     "jwas_hip_locpar_begin", "jwas_hip_locpar_add_covariate", "jwas_hip_locpar_add_factor", "jwas_hip_locpar_size",
     "jwas_hip_locpar_set_sol", "jwas_hip_locpar_get_sol", "jwas_hip_locpar_step", "jwas_hip_locpar_accumulate",
     "jwas_hip_locpar_get_means", "jwas_hip_locpar_estimate_bytes", "jwas_hip_locpar_end",
+    "jwas_hip_lp_set_group_structure", "jwas_hip_lp_get_group_colors", "jwas_hip_lp_structure_estimate_bytes",
 ]
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
@@ -225,6 +226,10 @@ def load():
     L.jwas_hip_locpar_estimate_bytes.argtypes = [i64, i64, i64]
     L.jwas_hip_locpar_estimate_bytes.restype = i64
     L.jwas_hip_locpar_end.argtypes = [vp]
+    L.jwas_hip_lp_set_group_structure.argtypes = [vp, i32, i64, vp, vp, vp]
+    L.jwas_hip_lp_get_group_colors.argtypes = [vp, i32, i64, vp, C.POINTER(i32)]
+    L.jwas_hip_lp_structure_estimate_bytes.argtypes = [i64, i64]
+    L.jwas_hip_lp_structure_estimate_bytes.restype = i64
     L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_accumulate.argtypes = [vp, C.c_double]
@@ -249,7 +254,7 @@ def load():
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_estimate_bytes", "jwas_hip_estimate_bytes_storage", "jwas_hip_gwas_estimate_bytes",
-                        "jwas_hip_locpar_estimate_bytes"):
+                        "jwas_hip_locpar_estimate_bytes", "jwas_hip_lp_structure_estimate_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

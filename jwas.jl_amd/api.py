@@ -269,15 +269,29 @@ class Model:
         self.traits_type = ["continuous"] * len(traits)      # "censored" | "categorical" | "categorical(binary)" (types.jl:325)
         self.thresholds = {}                   # trait index -> [-Inf, 0, ..., Inf] (types.jl:326)
         self.rndTrmVec = []                    # set_random(model, ...): RandomEffect (types.jl:217-226)
+        self.ped = False                       # set_random(model, "animal", ped, G): the Pedigree (types.jl:279)
+        self.pedTrmVec = False                 # ... and its terms, e.g. ["y1:animal", "y2:animal"] (types.jl:280)
 
 
 class RandomEffect:
-    """types.jl:217-226 -- an i.i.d. random effect: one term name over the traits whose equation contains it."""
+    """types.jl:217-226 -- a random effect: one term name over the traits whose equation contains it.  randomType "I": i.i.d.
+    levels; "A": the polygenic effect of a pedigree -- Vinv is A-inverse (CSR, doubles) and names the pedigree's IDs, its levels."""
 
-    def __init__(self, name, term_array, traits, Gi):
+    def __init__(self, name, term_array, traits, Gi, randomType="I", Vinv=0, names=()):
         self.name, self.term_array, self.traits = name, term_array, traits      # "x2", ["y1:x2", "y2:x2"], [0, 1]
         self.Gi = Gi                           # Variance: val = inv(G) (False until the default prior is set), df, scale
-        self.randomType = "I"
+        self.randomType, self.Vinv, self.names = randomType, Vinv, list(names)
+
+
+def pedigree_structure(ped):
+    """A-inverse of the pedigree (Henderson's rules with inbreeding, single_step.a_inverse) the way the reference keeps it --
+    rounded through Float32 (random_effects.jl:184) -- as an exactly symmetric scipy CSR matrix of doubles with ascending columns."""
+    from .single_step import a_inverse
+    A = a_inverse(ped).tocsr().astype(np.float32).astype(np.float64)
+    A = ((A + A.T) * 0.5).tocsr()              # (h'h is symmetric up to the order of its sums only; the library asks for exact symmetry)
+    A.sum_duplicates()
+    A.sort_indices()
+    return A
 
 
 def build_model(model_equations, R=False, *, df=4.0, estimate_variance=True, estimate_scale=False,
@@ -384,12 +398,22 @@ def outputMCMCsamples(model, *terms):
                 model.outputSamplesVec.append((tr, trm))
 
 
-def set_random(model, randomStr, G=False, *, df=4.0, estimate_variance=True, estimate_scale=False, constraint=False,
+def set_random(model, randomStr, *args, G=False, df=4.0, estimate_variance=True, estimate_scale=False, constraint=False,
                Vinv=0, names=()):
-    """random_effects.jl:93-191: declare the class factor `randomStr` an i.i.d. random effect with covariance G among the k traits
-    whose equation contains it (G = False: a default prior from the data, input_data_validation.jl:352-365).  Its variance is
-    sampled every iteration (sampleVCs, variance_components.jl:115-147) unless estimate_variance=False.  Pedigree / Vinv random
-    effects and several correlated terms in one call stay on the reference."""
+    """random_effects.jl:52,93-191.  set_random(model, "herd", G): the class factor is an i.i.d. random effect with covariance G
+    among the k traits whose equation contains it.  set_random(model, "animal", ped, G) with a single_step.Pedigree: the polygenic
+    effect, covariance A (x) G among the animals of the pedigree; its levels are the pedigree's IDs in pedigree order (one per
+    model).  G = False: a default prior from the data (input_data_validation.jl:352-365).  The variance is sampled every iteration
+    (sampleVCs, variance_components.jl:115-147) unless estimate_variance=False.  Vinv / names random effects and several
+    correlated terms in one call stay on the reference."""
+    from .single_step import Pedigree
+    ped = None
+    if args and isinstance(args[0], Pedigree):                                                # :52
+        ped, args = args[0], args[1:]
+    if len(args) > 1 or (args and not _is_false(G)):
+        raise TypeError("set_random(model, randomStr[, ped][, G]; ...)")
+    if args:
+        G = args[0]
     if not _is_false(G):                                                                      # :100-104
         Gm = np.atleast_2d(np.asarray(G, dtype=np.float64))
         ok = Gm.ndim == 2 and Gm.shape[0] == Gm.shape[1] and np.array_equal(Gm, Gm.T)
@@ -405,8 +429,8 @@ def set_random(model, randomStr, G=False, *, df=4.0, estimate_variance=True, est
     if estimate_scale is not False:
         raise ValueError("Estimate scale for variance of random term is not supported now.")
     if not (np.isscalar(Vinv) and Vinv == 0) or len(names) != 0:
-        raise NotImplementedError("set_random with a pedigree, Vinv or names (a random effect with a covariance structure among "
-                                  "its levels) stays on the reference; the device path runs i.i.d. random effects")
+        raise NotImplementedError("set_random with Vinv and names (a user-given covariance structure among the levels) stays on the "
+                                  "reference; the device path runs i.i.d. random effects and the pedigree form set_random(model, trm, ped, G)")
     trms = str(randomStr).split()
     if len(trms) != 1:
         raise NotImplementedError("set_random with several term names in one call (correlated terms within a trait) stays on "
@@ -422,6 +446,8 @@ def set_random(model, randomStr, G=False, *, df=4.0, estimate_variance=True, est
         raise ValueError(f"{trm} is not found in model equation.")                            # :135-137
     if any(re_.name == trm for re_ in model.rndTrmVec):
         raise ValueError(f"{trm} is already a random effect.")
+    if ped is not None and any(re_.randomType == "A" for re_ in model.rndTrmVec):
+        raise ValueError("a model has one pedigree (polygenic) random effect; animal + maternal effects stay on the reference")
     k = len(traits)
     if not _is_false(G) and Gm.shape[0] != k:                                                 # :156-158
         raise ValueError(f"Dimensions must match. The covariance matrix (G) should be a {k} x {k} matrix.\n")
@@ -433,7 +459,12 @@ def set_random(model, randomStr, G=False, *, df=4.0, estimate_variance=True, est
         Gi = (Gi + Gi.T) / 2
         scale = Gm * (float(dfk) - k - 1)
     term_array = [f"{model.lhsVec[m]}:{trm}" for m in traits]
-    model.rndTrmVec.append(RandomEffect(trm, term_array, traits, Variance(Gi, dfk, scale, estimate_variance, estimate_scale, constraint)))
+    var = Variance(Gi, dfk, scale, estimate_variance, estimate_scale, constraint)              # (df, scale of :168-171 and :182-183 coincide)
+    if ped is None:
+        model.rndTrmVec.append(RandomEffect(trm, term_array, traits, var))
+    else:                                                                                     # :141-143,164-172
+        model.ped, model.pedTrmVec = ped, term_array
+        model.rndTrmVec.append(RandomEffect(trm, term_array, traits, var, "A", pedigree_structure(ped), ped.ids))
 
 
 def set_covariate(model, *names):
@@ -474,7 +505,8 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
 
     location_parameters (device option): where step 1, the non-marker location parameters, runs.  "host": the dense host scan
     (intercepts, covariates and small fixed factors).  "device": term by term on the device from the resident residual
-    (csrc/locpar.hpp) -- factors of any number of levels, the i.i.d. random effects of set_random, residual weights, threshold
+    (csrc/locpar.hpp) -- factors of any number of levels, the i.i.d. random effects of set_random and its pedigree form (the polygenic
+    effect, sampled colour by colour over the graph of A-inverse; EBVs and heritability include it), residual weights, threshold
     traits; not with multi-trait records that miss some traits.  "auto": "device" for a model with a set_random term or more than
     2 048 location-parameter levels, else "host" -- the host path draws from the numpy generator, the device path from the
     counter generator, so the choice is part of what a seed means.

@@ -195,11 +195,24 @@ struct jwas_hip_ctx {
             double* d = nullptr;                            // [nlevels] sum w x^2
         };
         struct Group { int nmembers = 0; int term[jwp::kMaxT] = {}; int64_t nlevels = 0; };
+        struct Structure {                                  // jwas_hip_lp_set_group_structure: V of a random effect, coloured
+            bool set = false;
+            int64_t nlevels = 0, nnz = 0;
+            int ncolors = 0, nwg = 0;                       // nwg: workgroups of k_locpar_quad_rows
+            std::vector<int32_t> color;                     // [nlevels] colour of every level
+            std::vector<int32_t> color_lo, nshort;          // colour c: lv[color_lo[c] .. color_lo[c + 1]), its first nshort[c] the short rows
+            int64_t* rowptr = nullptr;                      // [nlevels + 1]
+            int32_t* col = nullptr;                         // [nnz]
+            double* val = nullptr;                          // [nnz]
+            int32_t* lv = nullptr;                          // [nlevels] the levels colour by colour
+            double* qpart = nullptr;                        // [nwg][kMaxPairs]
+        };
         bool active = false, finalized = false;
         int nt = 0, ngroups = 0;
         std::vector<double> w_host;                         // [n] the residual weights in force at _begin
         std::vector<Term> terms;
         Group groups[jwp::kMaxGroups];
+        Structure structs[jwp::kMaxGroups];
         int64_t q = 0;                                      // entries of sol
         double *sol = nullptr, *mean = nullptr, *mean2 = nullptr;     // [q]
         double *part = nullptr, *delta = nullptr;           // [max npieces], [max nlevels] scratch of the running term
@@ -358,6 +371,8 @@ static void locpar_free(jwas_hip_ctx* c)
     for (auto& t : b.terms)
         for (void* q : {(void*)t.x, (void*)t.level, (void*)t.rec, (void*)t.wx, (void*)t.piece_lo, (void*)t.level_piece, (void*)t.d}) (void)hipFree(q);
     for (void* q : {(void*)b.sol, (void*)b.mean, (void*)b.mean2, (void*)b.part, (void*)b.delta, (void*)b.cross_offs, (void*)b.cross_out}) (void)hipFree(q);
+    for (auto& v : b.structs)
+        for (void* q : {(void*)v.rowptr, (void*)v.col, (void*)v.val, (void*)v.lv, (void*)v.qpart}) (void)hipFree(q);
     b = jwas_hip_ctx::Locpar();
 }
 
@@ -3829,6 +3844,9 @@ int jwas_hip_locpar_add_factor(jwas_hip_ctx* c, int32_t trait, int64_t n, const 
                  "random effect %d already has a term of trait %d: correlated terms within a trait stay on the reference", group, trait);
         NEED(c, g.nmembers == 0 || g.nlevels == nlevels, JWAS_HIP_EINVAL, "the member terms of random effect %d must have the same levels (%lld, got %lld)",
              group, (long long)g.nlevels, (long long)nlevels);
+        const auto& v = c->lp.structs[group];
+        NEED(c, !v.set || v.nlevels == nlevels, JWAS_HIP_EINVAL, "random effect %d has a structure of %lld levels (the term has %lld)", group,
+             (long long)v.nlevels, (long long)nlevels);
     }
     return locpar_add_term(c, trait, nullptr, level, nlevels, group);
 }
@@ -3922,7 +3940,24 @@ int jwas_hip_locpar_step(jwas_hip_ctx* c, const jwas_locpar_params* P, jwas_locp
         }
         D.iter = P->iteration; D.rep = 0x20000000u | (uint32_t)j; D.slot = 3u + 16u * (uint32_t)k;
         D.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); D.seed_hi = (uint32_t)(P->seed >> 32);
-        hipLaunchKernelGGL(jwp::k_locpar_draw, dim3((unsigned)((T.nlevels + 255) / 256)), dim3(256), 0, c->stream, D);
+        if (T.group >= 0 && b.structs[T.group].set) {                   // a structured effect: colour by colour, one launch each
+            const auto& V = b.structs[T.group];
+            jwp::StructDrawArgs Q = {};
+            Q.part = D.part; Q.level_piece = D.level_piece; Q.d = D.d; Q.sol = D.sol; Q.delta = D.delta; Q.off = D.off;
+            Q.rowptr = V.rowptr; Q.col = V.col; Q.val = V.val;
+            Q.npartners = D.npartners; Q.pos = D.pos; Q.ckk = D.ckk; Q.s = D.s;
+            for (int m = 0; m < D.npartners; ++m) { Q.partner_off[m] = D.partner_off[m]; Q.p[m] = t == 1 ? P->vare * D.gi[m] : D.gi[m]; }
+            Q.iter = D.iter; Q.rep = D.rep; Q.slot = D.slot; Q.seed_lo = D.seed_lo; Q.seed_hi = D.seed_hi;
+            for (int col = 0; col < V.ncolors; ++col) {
+                Q.lv = V.lv + V.color_lo[(size_t)col];
+                Q.nshort = V.nshort[(size_t)col];
+                Q.nlong = V.color_lo[(size_t)col + 1] - V.color_lo[(size_t)col] - Q.nshort;
+                const unsigned wgs = (unsigned)((Q.nshort + 255) / 256 + (Q.nlong + 3) / 4);
+                hipLaunchKernelGGL(jwp::k_locpar_draw_structured, dim3(wgs), dim3(256), 0, c->stream, Q);
+            }
+        } else {
+            hipLaunchKernelGGL(jwp::k_locpar_draw, dim3((unsigned)((T.nlevels + 255) / 256)), dim3(256), 0, c->stream, D);
+        }
         char* rk = (char*)liab_residual(c) + esz * (size_t)k * (size_t)c->ld;
         const dim3 agrid((unsigned)((c->n + 255) / 256));
         if (f64) hipLaunchKernelGGL((jwp::k_locpar_apply<double>), agrid, dim3(256), 0, c->stream, (double*)rk, T.x, T.level, b.delta, c->n);
@@ -3930,7 +3965,14 @@ int jwas_hip_locpar_step(jwas_hip_ctx* c, const jwas_locpar_params* P, jwas_locp
     }
     for (int g = 0; g < b.ngroups; ++g) {
         const int kk = b.groups[g].nmembers;
-        if (kk > 0)
+        if (kk > 0 && b.structs[g].set) {                                // U' V U
+            const auto& V = b.structs[g];
+            jwp::QuadArgs Q = {};
+            Q.sol = b.sol; Q.rowptr = V.rowptr; Q.col = V.col; Q.val = V.val; Q.part = V.qpart; Q.nlevels = (int32_t)V.nlevels; Q.k = kk;
+            for (int m = 0; m < kk; ++m) Q.member_off[m] = b.terms[(size_t)b.groups[g].term[m]].off;
+            hipLaunchKernelGGL(jwp::k_locpar_quad_rows, dim3((unsigned)V.nwg), dim3(256), 0, c->stream, Q);
+            hipLaunchKernelGGL(jwp::k_locpar_quad_reduce, dim3(1), dim3(256), 0, c->stream, V.qpart, (int32_t)V.nwg, (int32_t)kk, b.cross_out + (size_t)g * 16);
+        } else if (kk > 0)
             hipLaunchKernelGGL(jwp::k_locpar_cross, dim3((unsigned)(kk * kk)), dim3(256), 0, c->stream, b.sol, b.cross_offs + (size_t)g * 32,
                                (int32_t)b.groups[g].nlevels, b.cross_out + (size_t)g * 16);
     }
@@ -3970,6 +4012,106 @@ int jwas_hip_locpar_get_means(jwas_hip_ctx* c, int64_t q, double* out_mean, doub
     if (out_mean2) HIPCHK(c, hipMemcpyAsync(out_mean2, c->lp.mean2, sizeof(double) * (size_t)q, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return JWAS_HIP_OK;
+}
+
+int jwas_hip_lp_set_group_structure(jwas_hip_ctx* c, int32_t group, int64_t nlevels, const int64_t* indptr, const int32_t* indices, const double* values)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "location parameters are not driven from marker or row shards");
+    NEED_LOCPAR(c);
+    auto& b = c->lp;
+    NEED(c, group >= 0 && group < jwp::kMaxGroups, JWAS_HIP_EINVAL, "random_group must be 0..%d (got %d)", jwp::kMaxGroups - 1, group);
+    NEED(c, !b.finalized && b.groups[group].nmembers == 0, JWAS_HIP_ESTATE,
+         "the structure of random effect %d is set before its first member term is added and before sol is first used", group);
+    NEED(c, indptr && indices && values, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, nlevels >= 1 && nlevels < (int64_t)1 << 31, JWAS_HIP_EINVAL, "nlevels must be 1 .. 2^31 - 1 (got %lld)", (long long)nlevels);
+    NEED(c, indptr[0] == 0, JWAS_HIP_EINVAL, "indptr[0] must be 0");
+    for (int64_t l = 0; l < nlevels; ++l) {
+        NEED(c, indptr[l + 1] >= indptr[l], JWAS_HIP_EINVAL, "indptr decreases at row %lld", (long long)l);
+        bool diag = false;
+        for (int64_t e = indptr[l]; e < indptr[l + 1]; ++e) {
+            NEED(c, indices[e] >= 0 && indices[e] < nlevels, JWAS_HIP_EINVAL, "row %lld: column %d outside 0..%lld", (long long)l, indices[e], (long long)nlevels - 1);
+            NEED(c, e == indptr[l] || indices[e] > indices[e - 1], JWAS_HIP_EINVAL, "row %lld: columns must be ascending without duplicates", (long long)l);
+            NEED(c, std::isfinite(values[e]), JWAS_HIP_EINVAL, "row %lld, column %d: the value is not finite", (long long)l, indices[e]);
+            if (indices[e] == l) { diag = true; NEED(c, values[e] > 0.0, JWAS_HIP_EINVAL, "row %lld: the diagonal must be positive (got %g)", (long long)l, values[e]); }
+        }
+        NEED(c, diag, JWAS_HIP_EINVAL, "row %lld has no diagonal entry", (long long)l);
+    }
+    for (int64_t l = 0; l < nlevels; ++l)                       // (every column index is in range from here on)
+        for (int64_t e = indptr[l]; e < indptr[l + 1]; ++e) {
+            const int32_t j = indices[e];
+            const int32_t* lo = indices + indptr[j];
+            const int32_t* hi = indices + indptr[j + 1];
+            const int32_t* at = std::lower_bound(lo, hi, (int32_t)l);
+            NEED(c, at != hi && *at == (int32_t)l && values[at - indices] == values[e], JWAS_HIP_EINVAL,
+                 "the structure is not symmetric at (%lld, %d)", (long long)l, j);
+        }
+    const int64_t nnz = indptr[nlevels];
+    // colours: levels in ascending order, the smallest colour no neighbour holds; then the levels of every colour, short rows first
+    jwas_hip_ctx::Locpar::Structure V;
+    V.nlevels = nlevels; V.nnz = nnz;
+    V.color.assign((size_t)nlevels, -1);
+    std::vector<int64_t> held;                                  // held[colour] == l + 1: a neighbour of l has it
+    for (int64_t l = 0; l < nlevels; ++l) {
+        for (int64_t e = indptr[l]; e < indptr[l + 1]; ++e) {
+            const int32_t cj = indices[e] != l ? V.color[(size_t)indices[e]] : -1;
+            if (cj >= 0) held[(size_t)cj] = l + 1;
+        }
+        int32_t pick = 0;
+        while (pick < (int32_t)held.size() && held[(size_t)pick] == l + 1) ++pick;
+        if (pick == (int32_t)held.size()) held.push_back(0);
+        V.color[(size_t)l] = pick;
+    }
+    V.ncolors = (int)held.size();
+    V.color_lo.assign((size_t)V.ncolors + 1, 0);
+    V.nshort.assign((size_t)V.ncolors, 0);
+    for (int64_t l = 0; l < nlevels; ++l) {
+        ++V.color_lo[(size_t)V.color[(size_t)l] + 1];
+        if (indptr[l + 1] - indptr[l] <= jwp::kLongRow) ++V.nshort[(size_t)V.color[(size_t)l]];
+    }
+    for (int q = 0; q < V.ncolors; ++q) V.color_lo[(size_t)q + 1] += V.color_lo[(size_t)q];
+    std::vector<int32_t> lv((size_t)nlevels), at_short(V.color_lo.begin(), V.color_lo.end() - 1), at_long((size_t)V.ncolors);
+    for (int q = 0; q < V.ncolors; ++q) at_long[(size_t)q] = V.color_lo[(size_t)q] + V.nshort[(size_t)q];
+    for (int64_t l = 0; l < nlevels; ++l) {
+        const size_t q = (size_t)V.color[(size_t)l];
+        lv[(size_t)(indptr[l + 1] - indptr[l] <= jwp::kLongRow ? at_short[q]++ : at_long[q]++)] = (int32_t)l;
+    }
+    V.nwg = (int)((nlevels + 255) / 256);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipError_t e = locpar_upload(&V.rowptr, std::vector<int64_t>(indptr, indptr + nlevels + 1));
+    if (e == hipSuccess) e = locpar_upload(&V.col, std::vector<int32_t>(indices, indices + nnz));
+    if (e == hipSuccess) e = locpar_upload(&V.val, std::vector<double>(values, values + nnz));
+    if (e == hipSuccess) e = locpar_upload(&V.lv, lv);
+    if (e == hipSuccess) e = hipMalloc((void**)&V.qpart, sizeof(double) * jwp::kMaxPairs * (size_t)V.nwg);
+    if (e != hipSuccess) {
+        for (void* q : {(void*)V.rowptr, (void*)V.col, (void*)V.val, (void*)V.lv, (void*)V.qpart}) (void)hipFree(q);
+        return fail(c, JWAS_HIP_EHIP, "uploading the structure failed: %s", hipGetErrorString(e));
+    }
+    auto& old = b.structs[group];                               // (a structure set twice: the later one holds)
+    for (void* q : {(void*)old.rowptr, (void*)old.col, (void*)old.val, (void*)old.lv, (void*)old.qpart}) (void)hipFree(q);
+    V.set = true;
+    old = std::move(V);
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_lp_get_group_colors(jwas_hip_ctx* c, int32_t group, int64_t nlevels, int32_t* out_color, int32_t* out_ncolors)
+{
+    NEED_LOCPAR(c);
+    NEED(c, group >= 0 && group < jwp::kMaxGroups, JWAS_HIP_EINVAL, "random_group must be 0..%d (got %d)", jwp::kMaxGroups - 1, group);
+    const auto& V = c->lp.structs[group];
+    NEED(c, V.set, JWAS_HIP_EINVAL, "random effect %d has no structure", group);
+    NEED(c, nlevels == V.nlevels, JWAS_HIP_EINVAL, "nlevels (%lld) differs from the structure's (%lld)", (long long)nlevels, (long long)V.nlevels);
+    NEED(c, out_color && out_ncolors, JWAS_HIP_EINVAL, "NULL argument");
+    std::copy(V.color.begin(), V.color.end(), out_color);
+    *out_ncolors = V.ncolors;
+    return JWAS_HIP_OK;
+}
+
+int64_t jwas_hip_lp_structure_estimate_bytes(int64_t nlevels, int64_t nnz)
+{
+    // the row pointers (int64), columns (int32) and values (double) of V, the levels colour by colour (int32), the per-workgroup
+    // sums of the quadratic forms
+    return 8 * (nlevels + 1) + 12 * nnz + 4 * nlevels + (int64_t)sizeof(double) * jwp::kMaxPairs * (nlevels / 256 + 1);
 }
 
 int64_t jwas_hip_locpar_estimate_bytes(int64_t n, int64_t nterms, int64_t total_levels)

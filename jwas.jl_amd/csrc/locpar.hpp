@@ -27,6 +27,22 @@
 //   k_locpar_apply<T>     one thread per record: r_k,i -= x_i delta[level_i]      (coalesced)
 //   k_locpar_cross        U'U of a random effect: one workgroup per pair of member terms, a fixed strided order
 //   k_locpar_accumulate   running means of sol and sol^2 (output.jl:556-560)
+//
+// A STRUCTURED random effect (jwas_hip_lp_set_group_structure: the polygenic effect of set_random(model, "animal", ped, G), whose
+// levels have covariance inv(V) (x) G, V = the sparse A-inverse).  The data sums S_l are the ones above; only the prior couples levels:
+//   lhs_l  = d_l c_kk + p_kk V_ll                              p_km = vare Gi_km (one trait), Gi_km (several)
+//   mean_l = (S_l + d_l c_kk sol_l - sum_m p_km sum_j V_lj u_m,j) / lhs_l        (the sum over j skips j == l for m == k)
+//   sol_l' = mean_l + z sqrt(s / lhs_l)                        (lhs_l > 0 always: V_ll > 0, p_kk > 0)
+// Two levels that are not neighbours in V are conditionally independent, so the graph of V is coloured on the host (levels in
+// ascending order, the smallest colour no neighbour holds) and the colours are visited in order, one launch of
+// k_locpar_draw_structured per colour: a systematic-scan Gibbs sampler with a fixed visiting order.  u_k is read from sol in
+// place -- earlier colours hold their new values, later ones their old ones; launch order is the only synchronisation.
+// LAYOUT of a colour: its levels with at most kLongRow entries in their row of V in ascending order (one THREAD each: the row is
+// added entry by entry in column order), then its levels with longer rows in ascending order (one WAVE each: lane g adds entries
+// g, g + 64, ... of the row, the 64 partial sums meet in the butterfly 32 .. 1).  Fixed by the layout: identical bits run to run.
+//   k_locpar_draw_structured    one launch per colour: S_l, the prior sums, the draw, sol, delta
+//   k_locpar_quad_rows          u_a' V u_b, a <= b: 256 rows of V per workgroup (a thread per short row, the workgroup per long row), a fixed tree
+//   k_locpar_quad_reduce        one workgroup adds the per-workgroup sums (strided, then the same tree) and fills the k x k block
 #pragma once
 #include "rng.hpp"
 #include <hip/hip_runtime.h>
@@ -37,6 +53,8 @@ namespace jwp {
 constexpr int kMaxT = 4;
 constexpr int kMaxGroups = 8;           // random effects per model
 constexpr int kPiece = 1024;            // records per piece
+constexpr int kLongRow = 32;            // a row of a structure with more entries than this gets a wave, not a thread
+constexpr int kMaxPairs = kMaxT * (kMaxT + 1) / 2;
 
 struct SumArgs {
     const void* r;                      // [nt][ld] residuals (T)
@@ -156,6 +174,183 @@ __global__ __launch_bounds__(256) void k_locpar_accumulate(const double* __restr
     const double v = sol[i];
     mean[i] = mean[i] + (v - mean[i]) / nsamples;
     mean2[i] = mean2[i] + (v * v - mean2[i]) / nsamples;
+}
+
+struct StructDrawArgs {
+    const double* part;                 // [npieces]
+    const int32_t* level_piece;         // [nlevels + 1]
+    const double* d;                    // [nlevels]
+    double* sol;
+    double* delta;                      // [nlevels] out (the levels of this colour)
+    const int64_t* rowptr;              // [nlevels + 1] the structure V: CSR, columns ascending
+    const int32_t* col;
+    const double* val;
+    const int32_t* lv;                  // the levels of this colour: nshort short rows, then nlong long rows
+    int64_t off;                        // this term's first entry of sol
+    int64_t partner_off[kMaxT];         // the member terms' first entries, this term's own included (slot `pos`)
+    double p[kMaxT];                    // row `pos` of Gi, times vare in a single-trait model
+    int32_t nshort, nlong, npartners, pos;
+    double ckk, s;
+    uint32_t iter, rep, slot, seed_lo, seed_hi;
+};
+
+// the draw of level l given the prior sums P[m] = sum_j V_lj u_m,j (own member: without j == l) and the diagonal vll
+__device__ inline void locpar_structured_finish(const StructDrawArgs& A, int l, const double* P, double vll)
+{
+    double S = 0.0;
+    for (int q = A.level_piece[l]; q < A.level_piece[l + 1]; ++q) S = S + A.part[q];
+    const double dc = A.d[l] * A.ckk;
+    const double lhs = dc + A.p[A.pos] * vll;
+    const double old = A.sol[A.off + l];
+    double num = S + dc * old;
+#pragma unroll
+    for (int m = 0; m < kMaxT; ++m)
+        if (m < A.npartners) num = num - A.p[m] * P[m];
+    const double mean = num / lhs;
+    const jw::u32x4 w = jw::philox4x32_10((uint32_t)l, A.iter, A.rep, A.slot, A.seed_lo, A.seed_hi);
+    const double u1 = jw::u52(w.x, w.y), u2 = jw::u52(w.z, w.w);
+    const double z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
+    const double now = mean + z * sqrt(A.s / lhs);
+    A.sol[A.off + l] = now;
+    A.delta[l] = now - old;
+}
+
+// grid: ceil(nshort / 256) workgroups of one thread per short row, then ceil(nlong / 4) workgroups of one wave per long row
+__global__ __launch_bounds__(256) void k_locpar_draw_structured(const StructDrawArgs A)
+{
+    const int nshort_wg = (A.nshort + 255) / 256;
+    double P[kMaxT] = {0.0, 0.0, 0.0, 0.0};
+    double vll = 0.0;
+    if ((int)blockIdx.x < nshort_wg) {
+        const int i = blockIdx.x * 256 + threadIdx.x;
+        if (i >= A.nshort) return;
+        const int l = A.lv[i];
+        for (int64_t e = A.rowptr[l]; e < A.rowptr[l + 1]; ++e) {
+            const int j = A.col[e];
+            const double v = A.val[e];
+            if (j == l) vll = v;
+#pragma unroll
+            for (int m = 0; m < kMaxT; ++m)
+                if (m < A.npartners && !(j == l && m == A.pos)) P[m] = P[m] + v * A.sol[A.partner_off[m] + j];
+        }
+        locpar_structured_finish(A, l, P, vll);
+    } else {
+        const int i = ((int)blockIdx.x - nshort_wg) * 4 + (int)(threadIdx.x >> 6);          // (wave-uniform)
+        if (i >= A.nlong) return;
+        const int lane = threadIdx.x & 63;
+        const int l = A.lv[A.nshort + i];
+        for (int64_t e = A.rowptr[l] + lane; e < A.rowptr[l + 1]; e += 64) {
+            const int j = A.col[e];
+            const double v = A.val[e];
+            if (j == l) vll = v;
+#pragma unroll
+            for (int m = 0; m < kMaxT; ++m)
+                if (m < A.npartners && !(j == l && m == A.pos)) P[m] = P[m] + v * A.sol[A.partner_off[m] + j];
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            vll = vll + __shfl_xor(vll, off, 64);                                          // (one lane holds V_ll, the others 0)
+#pragma unroll
+            for (int m = 0; m < kMaxT; ++m) P[m] = P[m] + __shfl_xor(P[m], off, 64);
+        }
+        if (lane == 0) locpar_structured_finish(A, l, P, vll);
+    }
+}
+
+struct QuadArgs {
+    const double* sol;
+    const int64_t* rowptr;
+    const int32_t* col;
+    const double* val;
+    double* part;                       // [nwg][kMaxPairs]: pair (a, b), a <= b, at locpar_pair(a, b)
+    int64_t member_off[kMaxT];
+    int32_t nlevels, k;
+};
+
+__host__ __device__ inline int locpar_pair(int a, int b) { return a * kMaxT - a * (a - 1) / 2 + (b - a); }      // a <= b < kMaxT
+
+__device__ inline double locpar_tree256(double* sh, double v)
+{
+    __syncthreads();
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// Workgroup w owns rows 256 w .. 256 w + 255.  A row of at most kLongRow entries is added by its own thread, entry by entry; a longer
+// one by the whole workgroup afterwards (the long rows in ascending order; thread j adds entries j, j + 256, ... of the row).  Every
+// thread ends with one partial sum per pair (a, b); the 256 of them meet in a fixed tree.
+__global__ __launch_bounds__(256) void k_locpar_quad_rows(const QuadArgs A)
+{
+    __shared__ double sh[256];
+    __shared__ int32_t is_long[256];
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    double acc[kMaxPairs];
+#pragma unroll
+    for (int q = 0; q < kMaxPairs; ++q) acc[q] = 0.0;
+    bool lng = false;
+    if (l < A.nlevels) {
+        const int64_t lo = A.rowptr[l], hi = A.rowptr[l + 1];
+        lng = hi - lo > kLongRow;
+        if (!lng) {
+            double Vu[kMaxT] = {0.0, 0.0, 0.0, 0.0};
+            for (int64_t e = lo; e < hi; ++e) {
+                const int j = A.col[e];
+                const double v = A.val[e];
+#pragma unroll
+                for (int m = 0; m < kMaxT; ++m)
+                    if (m < A.k) Vu[m] = Vu[m] + v * A.sol[A.member_off[m] + j];
+            }
+#pragma unroll
+            for (int a = 0; a < kMaxT; ++a)
+#pragma unroll
+                for (int b = a; b < kMaxT; ++b)
+                    if (b < A.k) acc[locpar_pair(a, b)] = A.sol[A.member_off[a] + l] * Vu[b];
+        }
+    }
+    is_long[threadIdx.x] = lng ? 1 : 0;
+    __syncthreads();
+    for (int i = 0; i < 256; ++i) {
+        if (!is_long[i]) continue;                                                         // (uniform)
+        const int row = blockIdx.x * 256 + i;
+        double Vu[kMaxT] = {0.0, 0.0, 0.0, 0.0};
+        for (int64_t e = A.rowptr[row] + threadIdx.x; e < A.rowptr[row + 1]; e += 256) {
+            const int j = A.col[e];
+            const double v = A.val[e];
+#pragma unroll
+            for (int m = 0; m < kMaxT; ++m)
+                if (m < A.k) Vu[m] = Vu[m] + v * A.sol[A.member_off[m] + j];
+        }
+#pragma unroll
+        for (int a = 0; a < kMaxT; ++a)
+#pragma unroll
+            for (int b = a; b < kMaxT; ++b)
+                if (b < A.k) acc[locpar_pair(a, b)] = acc[locpar_pair(a, b)] + A.sol[A.member_off[a] + row] * Vu[b];
+    }
+#pragma unroll
+    for (int a = 0; a < kMaxT; ++a)
+#pragma unroll
+        for (int b = a; b < kMaxT; ++b) {
+            if (b >= A.k) continue;                                                        // (uniform)
+            const double tot = locpar_tree256(sh, acc[locpar_pair(a, b)]);
+            if (threadIdx.x == 0) A.part[(size_t)blockIdx.x * kMaxPairs + locpar_pair(a, b)] = tot;
+        }
+}
+
+// out: the k x k block of utu (row-major, both triangles) from the nwg per-workgroup sums
+__global__ __launch_bounds__(256) void k_locpar_quad_reduce(const double* __restrict__ part, int32_t nwg, int32_t k, double* __restrict__ out)
+{
+    __shared__ double sh[256];
+    for (int a = 0; a < k; ++a)
+        for (int b = a; b < k; ++b) {
+            double acc = 0.0;
+            for (int w = threadIdx.x; w < nwg; w += 256) acc = acc + part[(size_t)w * kMaxPairs + locpar_pair(a, b)];
+            const double tot = locpar_tree256(sh, acc);
+            if (threadIdx.x == 0) { out[a * k + b] = tot; out[b * k + a] = tot; }
+        }
 }
 
 }  // namespace jwp

@@ -577,6 +577,7 @@ class HipEngine:
         nt = self.ntraits if ntraits is None else int(ntraits)
         self._chk(self._L.jwas_hip_locpar_begin(self._h, nt))
         self._locpar_groups = {}
+        self._locpar_struct_levels = {}
 
     def locpar_add_covariate(self, trait, x=None):
         """A one-entry term of `trait`: the covariate x, or the intercept (x = None).  Terms are sampled in the order added."""
@@ -596,6 +597,31 @@ class HipEngine:
         self._chk(self._L.jwas_hip_locpar_add_factor(self._h, int(trait), lv.size, _ptr(lv), int(nlevels), int(random_group)))
         if random_group >= 0:
             self._locpar_groups[int(random_group)] = self._locpar_groups.get(int(random_group), 0) + 1
+
+    @staticmethod
+    def locpar_structure_estimate_bytes(nlevels, nnz):
+        return _lib.load().jwas_hip_lp_structure_estimate_bytes(int(nlevels), int(nnz))
+
+    def locpar_set_group_structure(self, random_group, indptr, indices, values):
+        """Give random effect `random_group` the inverse covariance among its levels: a full symmetric CSR matrix (len(indptr) - 1
+        levels, ascending columns).  After locpar_begin, before the effect's first member term.  The library colours its graph and
+        samples a member term colour by colour (csrc/locpar.hpp); locpar_step's utu of the effect is then U' V U."""
+        ip = np.ascontiguousarray(indptr, dtype=np.int64)
+        ix = np.ascontiguousarray(indices, dtype=np.int32)
+        vv = np.ascontiguousarray(values, dtype=np.float64)
+        if ip.ndim != 1 or ip.size < 1 or ix.ndim != 1 or vv.shape != ix.shape or (ip.size and ip[-1] != ix.size):
+            raise ValueError("indptr, indices and values must describe one CSR matrix")
+        self._chk(self._L.jwas_hip_lp_set_group_structure(self._h, int(random_group), ip.size - 1, _ptr(ip), _ptr(ix), _ptr(vv)))
+        if not hasattr(self, "_locpar_struct_levels"):
+            self._locpar_struct_levels = {}
+        self._locpar_struct_levels[int(random_group)] = ip.size - 1
+
+    def locpar_group_colors(self, random_group):
+        """The colour of every level of the structure of `random_group`: the order the device visits them in."""
+        nlev = getattr(self, "_locpar_struct_levels", {}).get(int(random_group), 0)
+        out, nc = np.empty(max(nlev, 1), dtype=np.int32), C.c_int32()
+        self._chk(self._L.jwas_hip_lp_get_group_colors(self._h, int(random_group), nlev, _ptr(out), C.byref(nc)))
+        return out[:nlev].copy()
 
     def locpar_size(self):
         q = C.c_int64()

@@ -70,6 +70,7 @@ def _design(model, df, ids_col):
 
 LOCPAR_METHODS = ("locpar_begin", "locpar_add_covariate", "locpar_add_factor", "locpar_step", "locpar_get_sol", "locpar_accumulate",
                   "locpar_get_means", "locpar_end")
+LOCPAR_PED_METHODS = ("locpar_set_group_structure",)      # ... and what a pedigree random effect needs on top
 LOCPAR_AUTO_LEVELS = 2048               # location_parameters="auto": more levels than this run on the device
 
 
@@ -91,7 +92,15 @@ def _location_terms(model, df):
                     raise ValueError(f"{term.name} is not found in the phenotype data (genotype terms must be "
                                      "Genotypes objects visible to build_model).")
                 lev = df[term.name].astype(str)
-                names = sorted(lev.unique())
+                ped_ = next((re_ for re_ in getattr(model, "rndTrmVec", []) if re_.randomType == "A" and re_.name == term.name), None)
+                if ped_ is not None:                          # the levels of a polygenic effect: the pedigree's IDs, in its order
+                    names = list(ped_.names)
+                    lev = lev.str.strip()
+                    unknown = sorted(set(lev) - set(names))
+                    if unknown:
+                        raise ValueError(f"{term.name}: {unknown[:5]} {'...' if len(unknown) > 5 else ''} not found in the pedigree.")
+                else:
+                    names = sorted(lev.unique())
                 index = {lv: i for i, lv in enumerate(names)}
                 tk.append((term.name, "factor", (lev.map(index).to_numpy(dtype=np.int32), len(names))))
                 lab.extend((term.trait, term.name, lv) for lv in names)
@@ -365,6 +374,16 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     idcol = df.columns[0]
     ph = df.copy()
     ph[idcol] = ph[idcol].astype(str)
+    ped = getattr(model, "ped", False)
+    if ped is not False:                                                 # input_data_validation.jl:213-218,235-243
+        if not set(Mi.obsID) <= set(ped.ids):
+            raise ValueError("Not all genotyped individuals are found in pedigree!")
+        ph[idcol] = ph[idcol].str.strip()
+        inped = ph[idcol].isin(set(ped.ids)).to_numpy()
+        if not inped.all():
+            ph = ph.loc[inped].reset_index(drop=True)
+            print(f"In this incomplete genomic data (single-step) or PBLUP analysis, {int((~inped).sum())} phenotyped individuals are not "
+                  "included in the pedigree. These are removed from the analysis.")
     traits_type = model.traits_type = list(getattr(model, "traits_type", None) or ["continuous"] * t)
     has_liab = any(tt in LIABILITY_TYPES for tt in traits_type)
     if has_liab:
@@ -495,8 +514,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
 
     # ---- default priors (input_data_validation.jl:296-350, tools4genotypes.jl:353-478, build_MME.jl:128-141)
     rnd = list(getattr(model, "rndTrmVec", []))
-    varg = np.diag(phenovar) * 0.5
-    vare0 = np.diag(phenovar) * 0.5 / (1 + len(rnd))       # nongenetic_random_count (input_data_validation.jl:301-313): only a set_random term changes it
+    ped_count = sum(re_.randomType == "A" for re_ in rnd)    # genetic_random_count = the genotypes + the pedigree effect (:301-312)
+    varg = np.diag(phenovar) * 0.5 / (1 + ped_count)
+    vare0 = np.diag(phenovar) * 0.5 / (1 + len(rnd) - ped_count)       # nongenetic_random_count (input_data_validation.jl:301-313): only an i.i.d. set_random term changes it
     vare_rnd = vare0.copy()                                # ... what the random effects' default prior reads (:352-365)
     R = model.R
     if R.val is False:
@@ -519,7 +539,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     for re_ in rnd:                                                       # :352-365
         if re_.Gi.val is False:
             kk = len(re_.traits)
-            G0_ = np.diag([vare_rnd[m, m] for m in re_.traits])
+            G0_ = np.diag([(varg if re_.randomType == "A" else vare_rnd)[m, m] for m in re_.traits])      # :359-363
             re_.Gi.val = np.linalg.inv(G0_)
             re_.Gi.scale = G0_ * (float(re_.Gi.df) - kk - 1)
     pi = Mi.pi
@@ -851,6 +871,10 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                                               "(random covariates stay on the reference)")
         if len(rnd) > 8:
             raise NotImplementedError("at most 8 set_random effects on the device")
+        if ped_count:
+            missing_ = [m_ for m_ in LOCPAR_PED_METHODS if eng_ is not None and not hasattr(eng_, m_)]
+            if missing_:
+                raise NotImplementedError("a pedigree random effect needs an engine with " + ", ".join(missing_) + "; the package has no CPU fallback")
 
     # ---- engine (the only engine shipped is the HIP one; there is no CPU fallback)
     own_engine = engine is None
@@ -874,6 +898,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             need += p * t * t * 8 * 2                              # Float64 multi-trait BayesA/B: the covariances and their inverses in double
         if lp_device:                                              # the term layouts, sol and its means (jwas_hip_locpar_estimate_bytes)
             need += HipEngine.locpar_estimate_bytes(n, sum(len(tk) for tk in lp_terms), sum(q))
+            for re_ in rnd:                                        # A-inverse and its colours (jwas_hip_lp_structure_estimate_bytes)
+                if re_.randomType == "A":
+                    need += HipEngine.locpar_structure_estimate_bytes(re_.Vinv.shape[0], re_.Vinv.nnz)
         if outputEBV and not out_same:                             # Mi.output_genotypes: a second dense matrix (n_out x p)
             need += (8 if double_precision else 4) * ((len(out_rows) + 255) // 256 * 256) * p
         engine = HipEngine(device, precision=64 if double_precision else 32)
@@ -944,6 +971,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     # ---- location parameters: the terms go to the device (csrc/locpar.hpp) or the host builds its dense design matrices
     if lp_device:
         engine.locpar_begin(t)
+        for g_, re_ in enumerate(rnd):                                   # the structure goes up before the effect's members are added
+            if re_.randomType == "A":
+                engine.locpar_set_group_structure(g_, re_.Vinv.indptr, re_.Vinv.indices, re_.Vinv.data)
         for k in range(t):                                               # trait by trait, term by term: the reference's equation order
             for nm, kind_, val in lp_terms[k]:
                 if kind_ == "covariate":
@@ -1059,13 +1089,21 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                    for tr in model.lhsVec]
 
     rnd_keys, run_rnd = [], []
-    for re_ in rnd:                                                     # output.jl:348-351,401-405
-        key_ = "_".join(re_.term_array) + "_variances"
+    for re_ in rnd:                                                     # output.jl:348-351,401-405; the polygenic effect: :326-327,416-420
+        key_ = "polygenic_effects_variance" if re_.randomType == "A" else "_".join(re_.term_array) + "_variances"
         kk = len(re_.term_array)
         _open(key_, [f"{re_.term_array[a]}_{re_.term_array[b]}" for a in range(kk) for b in range(kk)])
         rnd_keys.append(key_)
         run_rnd.append(_Running(np.zeros(kk * kk)))
     lp_utu = None
+    # EBV = genomic + polygenic part (prediction_setup, output.jl:29-36): entry of sol of every output ID in the pedigree term of trait k
+    ped_cols = {}
+    if outputEBV:
+        for re_ in rnd:
+            if re_.randomType == "A":
+                lev_ = np.array([ped.index[i] for i in out_ids], dtype=np.int64)
+                for k in re_.traits:
+                    ped_cols[k] = off[k] + next(i for i, (_, eff, _) in enumerate(labels[k]) if eff == re_.name) + lev_
     liab_files = {}                                                     # output.jl:367-372 (no header lines, as there)
     for k in liab_traits:
         liab_files[("liabilities", k)] = open(os.path.join(output_folder, f"MCMC_samples_liabilities_{model.lhsVec[k]}.txt"), "w")
@@ -1278,7 +1316,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 k = (it - burnin) / output_samples_frequency
                 if lp_device:
                     engine.locpar_accumulate(k)                             # (running means on the device, read once at the end)
-                    if term_cols:
+                    if term_cols or ped_cols:
                         sol = engine.locpar_get_sol()
                 else:
                     run_sol.add(sol, k)
@@ -1324,6 +1362,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                         ebvs = [(X_out_host @ engine.get_state(kk)[0].astype(np.float64)).astype(ftype) for kk in range(t)]
                     else:
                         ebvs = [engine.mul_alpha(kk) if out_same else engine.mul_alpha_output(kk) for kk in range(t)]   # getEBV, output.jl:281-306
+                    for kk, cols_ in ped_cols.items():                      # the polygenic part of this sample, added on the host
+                        ebvs[kk] = (np.asarray(ebvs[kk], dtype=np.float64) + sol[cols_]).astype(ftype)
                     for kk in range(t):
                         ebv_run[kk].add(ebvs[kk], k)
                     if heritability:                                        # output.jl:498-512
@@ -1368,7 +1408,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                                              "SD": np.atleast_1d(run_vare.sd()).ravel()})
     for g_, re_ in enumerate(rnd):
         kk = len(re_.term_array)
-        out[rnd_keys[g_]] = pd.DataFrame({"Covariance": [f"{re_.term_array[a]}_{re_.term_array[b]}" for a in range(kk) for b in range(kk)],
+        out["polygenic effects covariance matrix" if re_.randomType == "A" else rnd_keys[g_]] = pd.DataFrame({"Covariance": [f"{re_.term_array[a]}_{re_.term_array[b]}" for a in range(kk) for b in range(kk)],
                                           "Estimate": run_rnd[g_].mean, "SD": run_rnd[g_].sd()})
     frames = []
     for k, tr in enumerate(model.lhsVec):
