@@ -35,6 +35,8 @@
  *   jwas_hip_locpar_*          the non-marker location parameters: the single-site scan Gibbs(A, x, b[, vare])
  *                              (iterative_solver/solver.jl:143-162) of MCMC/MCMC_BayesianAlphabet.jl:193-220 in residual-update
  *                              form, and the cross-products sampleVCs reads (variance_components.jl:115-147)
+ *   jwas_hip_mtmiss_*          multi-trait records that miss some traits: sampleMissingResiduals (residual.jl:51-73) and the
+ *                              per-record Ri of mkRi / getRi (residual.jl:2-44) in the location-parameter step
  *
  * Conventions: every entry point returns 0 on success and a negative JWAS_HIP_E* code on failure
  * (no exceptions cross the boundary; jwas_hip_last_error() returns the message -- the analogue of
@@ -476,6 +478,40 @@ int  jwas_hip_lp_set_group_structure(jwas_hip_ctx* ctx, int32_t random_group, in
 int  jwas_hip_lp_get_group_colors(jwas_hip_ctx* ctx, int32_t random_group, int64_t nlevels, int32_t* out_color, int32_t* out_ncolors);
 /* Device bytes of a structure of nlevels levels and nnz stored entries (pure; an upper bound). */
 int64_t jwas_hip_lp_structure_estimate_bytes(int64_t nlevels, int64_t nnz);
+
+/* ---- multi-trait records that miss some traits (csrc/mtmiss.hpp) ---------------------------------------------------------------
+ * The reference weights every record with the inverse of the OBSERVED block of R (mkRi / getRi, residual.jl:2-44) and redraws the
+ * residuals of its missing traits from their conditional every iteration (sampleMissingResiduals, residual.jl:51-73); after the
+ * first residual-variance draw it weights with kron(inv(R), diag(w)) again (MCMC_BayesianAlphabet.jl:357-361) and keeps imputing.
+ * A record's CODE has bit k set when trait k is observed: 1 .. 2^t - 1, t <= JWAS_HIP_MAX_TRAITS.  The caller forms the
+ * per-code tables in double, so that the device and any restatement read the same numbers; each is [2^t][t][t] doubles,
+ * row-major, unused entries 0 (o = the observed traits ascending, m = the missing ones ascending):
+ *   B[code]: |m| x |o|, R[m,o] inv(R[o,o]);   U[code]: |m| x |m|, the upper Cholesky factor of R[m,m] - R[m,o] inv(R[o,o]) R[o,m];
+ *   C[code]: t x t, inv(R[o,o]) embedded in zeros (the RZ of getRi).
+ * Imputation: e_m[c] = sum_j B[c][j] e_o[j] + sum_{a <= c} z_m[a] U[a][c] in that order, in double, rounded to the residual's
+ * element type once; z_k is rng.hpp's Box-Muller normal on philox4x32_10(record, iteration, 0x10000000, 4 + 16 * k).  Observed
+ * cells and complete records are not written.  Every entry point decides its errors before any launch: JWAS_HIP_EINVAL for a code
+ * of 0 or >= 2^t, a wrong n, a non-finite table entry; JWAS_HIP_ESTATE without a residual, before _begin, after the number of
+ * traits changed, or for record weights with one trait; JWAS_HIP_EUNSUP with a communicator attached.  The state is freed by
+ * _end, jwas_hip_destroy or loading genotypes. */
+typedef struct jwas_mtmiss_params {
+    uint32_t iteration;                 /* MCMC iteration >= 1 (enters the RNG counter)                                          */
+    uint32_t reserved;
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                     */
+    const double* B;                    /* host, [2^t][t][t]                                                                     */
+    const double* U;                    /* host, [2^t][t][t]                                                                     */
+} jwas_mtmiss_params;
+/* Store the codes of the n records (residual.jl:17-21, mme.missingPattern).  After jwas_hip_init_state. */
+int  jwas_hip_mtmiss_begin(jwas_hip_ctx* ctx, int64_t n, const int32_t* observed);
+/* Redraw the residuals of the missing cells (residual.jl:51-73).  Asynchronous (ordered on the context's stream). */
+int  jwas_hip_mtmiss_impute(jwas_hip_ctx* ctx, const jwas_mtmiss_params* params);
+/* C != NULL: every later jwas_hip_locpar_step weights record i with C[code_i] (residual.jl:2-44 instead of build_MME.jl:339's
+ * kron(inv(R), diag(w))): params->Rinv is ignored, s = 1, the Gi priors as before; the residual weights w stay in force.
+ * NULL: back to kron(inv(R), diag(w)) (MCMC_BayesianAlphabet.jl:357-361). */
+int  jwas_hip_mtmiss_set_record_weights(jwas_hip_ctx* ctx, const double* C);
+/* Device bytes of the state over n records (pure; an upper bound). */
+int64_t jwas_hip_mtmiss_estimate_bytes(int64_t n);
+int  jwas_hip_mtmiss_end(jwas_hip_ctx* ctx);
 
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the

@@ -316,6 +316,31 @@ end
 hip_locpar_structure_estimate_bytes(nlevels::Integer, nnz::Integer) =
     ccall((:jwas_hip_lp_structure_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64), nlevels, nnz)
 
+"Multi-trait records that miss some traits (residual.jl:2-73).  `hip_mtmiss_begin!` stores the code of every record (bit k-1 set =
+trait k observed); `hip_mtmiss_impute!` replaces sampleMissingResiduals given the per-code tables B and U of the current R
+([t, t, 2^t] arrays in Julia's column-major order hold the library's row-major [2^t][t][t]: index them [column, row, code + 1]);
+`hip_mtmiss_set_record_weights!` makes `hip_locpar_step!` weight every record with C[code] = the RZ of getRi (nothing: back to
+kron(inv(R), diag(w)), MCMC_BayesianAlphabet.jl:357-361)."
+struct HipMtmissParams
+    iteration::UInt32
+    reserved::UInt32
+    seed::UInt64
+    B::Ptr{Float64}
+    U::Ptr{Float64}
+end
+hip_mtmiss_begin!(b::HipBackend, observed::Vector{Int32}) =
+    hip_check(b.ctx, ccall((:jwas_hip_mtmiss_begin, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Int32}), b.ctx, length(observed), observed))
+function hip_mtmiss_impute!(b::HipBackend, iter::Integer, seed::Integer, B::Array{Float64,3}, U::Array{Float64,3})
+    GC.@preserve B U begin
+        P = HipMtmissParams(UInt32(iter), UInt32(0), UInt64(seed), pointer(B), pointer(U))
+        hip_check(b.ctx, ccall((:jwas_hip_mtmiss_impute, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipMtmissParams}), b.ctx, P))
+    end
+end
+hip_mtmiss_set_record_weights!(b::HipBackend, C::Union{Nothing,Array{Float64,3}}) =
+    hip_check(b.ctx, ccall((:jwas_hip_mtmiss_set_record_weights, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.ctx, C === nothing ? C_NULL : C))
+hip_mtmiss_estimate_bytes(n::Integer) = ccall((:jwas_hip_mtmiss_estimate_bytes, LIBJWAS_HIP), Int64, (Int64,), n)
+hip_mtmiss_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_mtmiss_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

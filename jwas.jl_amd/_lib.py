@@ -48,6 +48,8 @@ SYMBOLS = [
     "jwas_hip_locpar_set_sol", "jwas_hip_locpar_get_sol", "jwas_hip_locpar_step", "jwas_hip_locpar_accumulate",
     "jwas_hip_locpar_get_means", "jwas_hip_locpar_estimate_bytes", "jwas_hip_locpar_end",
     "jwas_hip_lp_set_group_structure", "jwas_hip_lp_get_group_colors", "jwas_hip_lp_structure_estimate_bytes",
+    "jwas_hip_mtmiss_begin", "jwas_hip_mtmiss_impute", "jwas_hip_mtmiss_set_record_weights", "jwas_hip_mtmiss_estimate_bytes",
+    "jwas_hip_mtmiss_end",
 ]
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
@@ -110,6 +112,10 @@ class LocparParams(C.Structure):
 
 class LocparStats(C.Structure):
     _fields_ = [("utu", C.c_double * (LOCPAR_MAX_GROUPS * 16)), ("step_ms", C.c_double)]
+
+
+class MtmissParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("B", C.c_void_p), ("U", C.c_void_p)]
 
 
 class JwasHipError(RuntimeError):
@@ -230,6 +236,12 @@ def load():
     L.jwas_hip_lp_get_group_colors.argtypes = [vp, i32, i64, vp, C.POINTER(i32)]
     L.jwas_hip_lp_structure_estimate_bytes.argtypes = [i64, i64]
     L.jwas_hip_lp_structure_estimate_bytes.restype = i64
+    L.jwas_hip_mtmiss_begin.argtypes = [vp, i64, vp]
+    L.jwas_hip_mtmiss_impute.argtypes = [vp, C.POINTER(MtmissParams)]
+    L.jwas_hip_mtmiss_set_record_weights.argtypes = [vp, vp]
+    L.jwas_hip_mtmiss_estimate_bytes.argtypes = [i64]
+    L.jwas_hip_mtmiss_estimate_bytes.restype = i64
+    L.jwas_hip_mtmiss_end.argtypes = [vp]
     L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_accumulate.argtypes = [vp, C.c_double]
@@ -254,7 +266,7 @@ def load():
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_estimate_bytes", "jwas_hip_estimate_bytes_storage", "jwas_hip_gwas_estimate_bytes",
-                        "jwas_hip_locpar_estimate_bytes", "jwas_hip_lp_structure_estimate_bytes"):
+                        "jwas_hip_locpar_estimate_bytes", "jwas_hip_lp_structure_estimate_bytes", "jwas_hip_mtmiss_estimate_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -507,9 +507,11 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     (intercepts, covariates and small fixed factors).  "device": term by term on the device from the resident residual
     (csrc/locpar.hpp) -- factors of any number of levels, the i.i.d. random effects of set_random and its pedigree form (the polygenic
     effect, sampled colour by colour over the graph of A-inverse; EBVs and heritability include it), residual weights, threshold
-    traits; not with multi-trait records that miss some traits.  "auto": "device" for a model with a set_random term or more than
-    2 048 location-parameter levels, else "host" -- the host path draws from the numpy generator, the device path from the
-    counter generator, so the choice is part of what a seed means.
+    traits, and multi-trait records that miss some traits (their missing residuals are imputed on the device and every record is
+    weighted with the inverse of its observed block of R until the first residual-variance draw, csrc/mtmiss.hpp).  "auto": "device"
+    for a model with a set_random term or more than 2 048 location-parameter levels, else "host" -- the host path draws from the
+    numpy generator, the device path from the counter generator, so the choice is part of what a seed means; a fixed-only model
+    with partially missing multi-trait records stays on "host" under "auto".
 
     Categorical / censored traits (build_model(...; categorical_trait, censored_trait)): categories coded 1, 2, 3 ... (two of them
     make a binary trait), bounds of a censored trait in the columns <trait>_l / <trait>_u; the liabilities are sampled on the

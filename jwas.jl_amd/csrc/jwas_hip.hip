@@ -6,6 +6,7 @@
 #include "step_launch.hpp"
 #include "liability.hpp"
 #include "locpar.hpp"
+#include "mtmiss.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -216,9 +217,18 @@ struct jwas_hip_ctx {
         int64_t q = 0;                                      // entries of sol
         double *sol = nullptr, *mean = nullptr, *mean2 = nullptr;     // [q]
         double *part = nullptr, *delta = nullptr;           // [max npieces], [max nlevels] scratch of the running term
+        double* part2 = nullptr;                            // [max npieces] the piece sums of D under per-record weights (first such step)
+        int64_t maxp = 1;
         int64_t* cross_offs = nullptr;                      // [kMaxGroups][16][2] member offsets of every cross-product
         double* cross_out = nullptr;                        // [kMaxGroups][16]
     } lp;
+    // Multi-trait records that miss some traits (jwas_hip_mtmiss_begin .. _end; residual.jl:2-73; csrc/mtmiss.hpp)
+    struct Mtmiss {
+        bool active = false, weights = false;               // weights: jwas_hip_locpar_step uses the per-record Ri
+        int nt = 0;
+        int32_t* code = nullptr;                            // [n] the pattern of every record
+        double* tab = nullptr;                              // [3][kMaxCodes * 16] the tables B, U, C (each [2^t][t][t] at its start)
+    } mt;
 };
 
 static constexpr int kStatGrid = 128;
@@ -370,14 +380,21 @@ static void locpar_free(jwas_hip_ctx* c)
     auto& b = c->lp;
     for (auto& t : b.terms)
         for (void* q : {(void*)t.x, (void*)t.level, (void*)t.rec, (void*)t.wx, (void*)t.piece_lo, (void*)t.level_piece, (void*)t.d}) (void)hipFree(q);
-    for (void* q : {(void*)b.sol, (void*)b.mean, (void*)b.mean2, (void*)b.part, (void*)b.delta, (void*)b.cross_offs, (void*)b.cross_out}) (void)hipFree(q);
+    for (void* q : {(void*)b.sol, (void*)b.mean, (void*)b.mean2, (void*)b.part, (void*)b.part2, (void*)b.delta, (void*)b.cross_offs, (void*)b.cross_out}) (void)hipFree(q);
     for (auto& v : b.structs)
         for (void* q : {(void*)v.rowptr, (void*)v.col, (void*)v.val, (void*)v.lv, (void*)v.qpart}) (void)hipFree(q);
     b = jwas_hip_ctx::Locpar();
 }
 
+static void mtmiss_free(jwas_hip_ctx* c)
+{
+    (void)hipFree(c->mt.code); (void)hipFree(c->mt.tab);
+    c->mt = jwas_hip_ctx::Mtmiss();
+}
+
 static void free_storage(jwas_hip_ctx* c)
 {
+    mtmiss_free(c);                     // (the codes describe the records of this matrix)
     gwas_free(c);                       // (a session is bound to the matrix it was begun on)
     liab_free(c);                       // (the liabilities belong to the residual of this matrix)
     locpar_free(c);                     // (... and so do the location parameters' term layouts)
@@ -2891,6 +2908,7 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     gwas_free(c);
     liab_free(c);
     locpar_free(c);
+    mtmiss_free(c);
     for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->w, (void*)F->ev_all}) (void)hipFree(q);
     F->X = F->r = F->xpx = F->gram = F->partials = F->w = nullptr; F->ev = F->ev_all = nullptr; F->dparams = nullptr;
     F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0;
@@ -3779,6 +3797,7 @@ static int locpar_finalize(jwas_hip_ctx* c)
     const size_t qb = sizeof(double) * (size_t)std::max<int64_t>(b.q, 1);
     for (double** v : {&b.sol, &b.mean, &b.mean2}) { HIPCHK(c, hipMalloc((void**)v, qb)); HIPCHK(c, hipMemsetAsync(*v, 0, qb, c->stream)); }
     HIPCHK(c, hipMalloc((void**)&b.part, sizeof(double) * (size_t)maxp));
+    b.maxp = maxp;
     HIPCHK(c, hipMalloc((void**)&b.delta, sizeof(double) * (size_t)maxl));
     std::vector<int64_t> offs((size_t)jwp::kMaxGroups * 32, 0);
     for (int g = 0; g < b.ngroups; ++g)
@@ -3890,7 +3909,10 @@ int jwas_hip_locpar_step(jwas_hip_ctx* c, const jwas_locpar_params* P, jwas_locp
     const int first = P->first_term, last = P->last_term < 0 ? nterms : P->last_term;
     NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: iteration must be >= 1");
     NEED(c, first >= 0 && first <= last && last <= nterms, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: terms %d..%d outside 0..%d", first, last, nterms);
-    if (t == 1) {
+    const bool pat = c->mt.weights;                             // the per-record Ri of jwas_hip_mtmiss_set_record_weights: Rinv is not read
+    if (pat) {
+        NEED(c, c->mt.active && c->mt.nt == t && t > 1, JWAS_HIP_ESTATE, "jwas_hip_init_state changed the number of traits after jwas_hip_mtmiss_begin");
+    } else if (t == 1) {
         NEED(c, std::isfinite(P->vare) && P->vare > 0.0, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: vare must be positive and finite (got %g)", P->vare);
     } else {
         for (int k = 0; k < t; ++k) {
@@ -3912,6 +3934,8 @@ int jwas_hip_locpar_step(jwas_hip_ctx* c, const jwas_locpar_params* P, jwas_locp
     HIPCHK(c, hipSetDevice(c->device));
     const bool f64 = IS_F64(c);
     const size_t esz = f64 ? 8 : 4;
+    if (pat && !b.part2) HIPCHK(c, hipMalloc((void**)&b.part2, sizeof(double) * (size_t)b.maxp));
+    const double* ctab = pat ? c->mt.tab + 2 * jwm::kMaxCodes * 16 : nullptr;
     if (S) HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
     for (int j = first; j < last; ++j) {
         const auto& T = b.terms[(size_t)j];
@@ -3920,16 +3944,22 @@ int jwas_hip_locpar_step(jwas_hip_ctx* c, const jwas_locpar_params* P, jwas_locp
             jwp::SumArgs A = {};
             A.r = liab_residual(c); A.ld = c->ld; A.rec = T.rec; A.wx = T.wx; A.piece_lo = T.piece_lo; A.part = b.part;
             A.npieces = T.npieces; A.G = T.G; A.nt = t; A.trait = k;
-            for (int m = 0; m < t; ++m) A.c[m] = t == 1 ? 1.0 : P->Rinv[k * t + m];
+            for (int m = 0; m < t; ++m) A.c[m] = t == 1 ? 1.0 : pat ? 0.0 : P->Rinv[k * t + m];
             const dim3 grid((unsigned)(((int64_t)T.npieces * T.G + 255) / 256)), block(256);
-            if (f64) hipLaunchKernelGGL((jwp::k_locpar_sums<double>), grid, block, 0, c->stream, A);
-            else     hipLaunchKernelGGL((jwp::k_locpar_sums<float>), grid, block, 0, c->stream, A);
+            if (pat) {
+                A.code = c->mt.code; A.ctab = ctab; A.x = T.x; A.part2 = b.part2;
+                if (f64) hipLaunchKernelGGL((jwp::k_locpar_sums<double, true>), grid, block, 0, c->stream, A);
+                else     hipLaunchKernelGGL((jwp::k_locpar_sums<float, true>), grid, block, 0, c->stream, A);
+            }
+            else if (f64) hipLaunchKernelGGL((jwp::k_locpar_sums<double>), grid, block, 0, c->stream, A);
+            else          hipLaunchKernelGGL((jwp::k_locpar_sums<float>), grid, block, 0, c->stream, A);
         }
         jwp::DrawArgs D = {};
         D.part = b.part; D.level_piece = T.level_piece; D.d = T.d; D.sol = b.sol; D.delta = b.delta; D.off = T.off;
         D.nlevels = (int32_t)T.nlevels; D.pos = T.pos; D.npartners = 0;
-        D.ckk = t == 1 ? 1.0 : P->Rinv[k * t + k];
+        D.ckk = t == 1 ? 1.0 : pat ? 0.0 : P->Rinv[k * t + k];
         D.s = t == 1 ? P->vare : 1.0;
+        D.part2 = pat ? b.part2 : nullptr;
         D.prior = 0.0;
         if (T.group >= 0) {
             const auto& g = b.groups[T.group];
@@ -3947,16 +3977,19 @@ int jwas_hip_locpar_step(jwas_hip_ctx* c, const jwas_locpar_params* P, jwas_locp
             Q.rowptr = V.rowptr; Q.col = V.col; Q.val = V.val;
             Q.npartners = D.npartners; Q.pos = D.pos; Q.ckk = D.ckk; Q.s = D.s;
             for (int m = 0; m < D.npartners; ++m) { Q.partner_off[m] = D.partner_off[m]; Q.p[m] = t == 1 ? P->vare * D.gi[m] : D.gi[m]; }
-            Q.iter = D.iter; Q.rep = D.rep; Q.slot = D.slot; Q.seed_lo = D.seed_lo; Q.seed_hi = D.seed_hi;
+            Q.iter = D.iter; Q.rep = D.rep; Q.slot = D.slot; Q.seed_lo = D.seed_lo; Q.seed_hi = D.seed_hi; Q.part2 = D.part2;
             for (int col = 0; col < V.ncolors; ++col) {
                 Q.lv = V.lv + V.color_lo[(size_t)col];
                 Q.nshort = V.nshort[(size_t)col];
                 Q.nlong = V.color_lo[(size_t)col + 1] - V.color_lo[(size_t)col] - Q.nshort;
                 const unsigned wgs = (unsigned)((Q.nshort + 255) / 256 + (Q.nlong + 3) / 4);
-                hipLaunchKernelGGL(jwp::k_locpar_draw_structured, dim3(wgs), dim3(256), 0, c->stream, Q);
+                if (pat) hipLaunchKernelGGL(jwp::k_locpar_draw_structured<true>, dim3(wgs), dim3(256), 0, c->stream, Q);
+                else     hipLaunchKernelGGL(jwp::k_locpar_draw_structured<false>, dim3(wgs), dim3(256), 0, c->stream, Q);
             }
+        } else if (pat) {
+            hipLaunchKernelGGL(jwp::k_locpar_draw<true>, dim3((unsigned)((T.nlevels + 255) / 256)), dim3(256), 0, c->stream, D);
         } else {
-            hipLaunchKernelGGL(jwp::k_locpar_draw, dim3((unsigned)((T.nlevels + 255) / 256)), dim3(256), 0, c->stream, D);
+            hipLaunchKernelGGL(jwp::k_locpar_draw<false>, dim3((unsigned)((T.nlevels + 255) / 256)), dim3(256), 0, c->stream, D);
         }
         char* rk = (char*)liab_residual(c) + esz * (size_t)k * (size_t)c->ld;
         const dim3 agrid((unsigned)((c->n + 255) / 256));
@@ -4127,6 +4160,104 @@ int jwas_hip_locpar_end(jwas_hip_ctx* c)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     locpar_free(c);
+    return JWAS_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- multi-trait records that miss some traits (csrc/mtmiss.hpp): residual.jl:2-73 ----------------------------------------------
+#define NEED_MTMISS(c)                                                                                                 \
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
+    NEED(c, c->mt.active, JWAS_HIP_ESTATE, "jwas_hip_mtmiss_begin has not been called");                               \
+    NEED(c, liab_residual(c) && c->method >= 0 && c->ntraits == c->mt.nt, JWAS_HIP_ESTATE,                              \
+         "jwas_hip_init_state changed the number of traits after jwas_hip_mtmiss_begin");                              \
+    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "missing-trait records are not driven from marker or row shards")
+
+// every entry of a [2^t][t][t] table is finite
+static bool mtmiss_table_finite(const double* tab, int t)
+{
+    for (int i = 0; i < (1 << t) * t * t; ++i) if (!std::isfinite(tab[i])) return false;
+    return true;
+}
+
+extern "C" {
+
+int jwas_hip_mtmiss_begin(jwas_hip_ctx* c, int64_t n, const int32_t* observed)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no residual: load genotypes and call jwas_hip_init_state first");
+    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "missing-trait records are not driven from marker or row shards");
+    NEED(c, observed, JWAS_HIP_EINVAL, "observed is NULL");
+    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
+    const int t = c->ntraits;
+    NEED(c, t >= 1 && t <= jwm::kMaxT, JWAS_HIP_EINVAL, "the number of traits (%d) is outside 1..%d", t, jwm::kMaxT);
+    for (int64_t i = 0; i < n; ++i)
+        NEED(c, observed[i] >= 1 && observed[i] < (1 << t), JWAS_HIP_EINVAL, "record %lld: code %d outside 1..%d", (long long)i, observed[i], (1 << t) - 1);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    mtmiss_free(c);
+    auto& b = c->mt;
+    HIPCHK(c, hipMalloc((void**)&b.code, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)));
+    HIPCHK(c, hipMalloc((void**)&b.tab, sizeof(double) * 3 * jwm::kMaxCodes * 16));
+    HIPCHK(c, hipMemcpy(b.code, observed, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(b.tab, 0, sizeof(double) * 3 * jwm::kMaxCodes * 16, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    b.nt = t;
+    b.active = true;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mtmiss_impute(jwas_hip_ctx* c, const jwas_mtmiss_params* P)
+{
+    NEED_MTMISS(c);
+    NEED(c, P && P->B && P->U, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_mtmiss_impute: iteration must be >= 1");
+    auto& b = c->mt;
+    const int t = b.nt;
+    NEED(c, mtmiss_table_finite(P->B, t) && mtmiss_table_finite(P->U, t), JWAS_HIP_EINVAL, "jwas_hip_mtmiss_impute: a table entry is not finite");
+    if (t == 1) return JWAS_HIP_OK;                             // (one trait: every record is complete)
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = sizeof(double) * (size_t)(1 << t) * t * t;
+    HIPCHK(c, hipMemcpyAsync(b.tab, P->B, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.tab + jwm::kMaxCodes * 16, P->U, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                 // (the caller's tables may go away once this returns)
+    jwm::ImputeArgs A = {};
+    A.r = liab_residual(c); A.ld = c->ld; A.n = c->n; A.code = b.code; A.B = b.tab; A.U = b.tab + jwm::kMaxCodes * 16; A.nt = t;
+    A.iter = P->iteration; A.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); A.seed_hi = (uint32_t)(P->seed >> 32);
+    const dim3 grid((unsigned)((c->n + 255) / 256));
+    if (IS_F64(c)) hipLaunchKernelGGL((jwm::k_mtmiss_impute<double>), grid, dim3(256), 0, c->stream, A);
+    else           hipLaunchKernelGGL((jwm::k_mtmiss_impute<float>), grid, dim3(256), 0, c->stream, A);
+    HIPCHK(c, hipGetLastError());
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mtmiss_set_record_weights(jwas_hip_ctx* c, const double* C)
+{
+    NEED_MTMISS(c);
+    auto& b = c->mt;
+    if (!C) { b.weights = false; return JWAS_HIP_OK; }
+    const int t = b.nt;
+    NEED(c, t > 1, JWAS_HIP_ESTATE, "per-record weights need more than one trait");
+    NEED(c, mtmiss_table_finite(C, t), JWAS_HIP_EINVAL, "jwas_hip_mtmiss_set_record_weights: a table entry is not finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(b.tab + 2 * jwm::kMaxCodes * 16, C, sizeof(double) * (size_t)(1 << t) * t * t, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    b.weights = true;
+    return JWAS_HIP_OK;
+}
+
+int64_t jwas_hip_mtmiss_estimate_bytes(int64_t n)
+{
+    // the codes (int32), the piece sums of D of the largest term (at most one piece per record), the three tables
+    return 4 * n + 8 * n + (int64_t)sizeof(double) * 3 * jwm::kMaxCodes * 16;
+}
+
+int jwas_hip_mtmiss_end(jwas_hip_ctx* c)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    mtmiss_free(c);
     return JWAS_HIP_OK;
 }
 

@@ -43,6 +43,15 @@
 //   k_locpar_draw_structured    one launch per colour: S_l, the prior sums, the draw, sol, delta
 //   k_locpar_quad_rows          u_a' V u_b, a <= b: 256 rows of V per workgroup (a thread per short row, the workgroup per long row), a fixed tree
 //   k_locpar_quad_reduce        one workgroup adds the per-workgroup sums (strided, then the same tree) and fills the k x k block
+//
+// PER-RECORD WEIGHTS (mtmiss.hpp: multi-trait records that miss some traits; mkRi / getRi, residual.jl:2-44).  Record i carries a
+// code (bit m set = trait m observed) and C[code] = inv(R[o,o]) embedded in a t x t matrix of zeros replaces inv(R):
+//   rho_i  = sum_m C[code_i]_km r_m,i
+//   S_l    = sum_{i in l} w_i x_i rho_i                        D_l = sum_{i in l} (w_i x_i) x_i C[code_i]_kk
+//   lhs_l  = D_l + prior                                       mean_l = (S_l + D_l sol_l - ...) / lhs_l,  s = 1
+// k_locpar_sums<T, true> forms the piece sums of S and of D side by side (the same piece / lane / butterfly order), the draws'
+// <true> instantiations add the pieces of D in piece order where the plain ones form d_l c_kk.  A level whose records all miss
+// trait k has D_l = 0: with no prior it is left alone.  The <false> instantiations are the plain code, unchanged.
 #pragma once
 #include "rng.hpp"
 #include <hip/hip_runtime.h>
@@ -65,9 +74,14 @@ struct SumArgs {
     double* part;                       // [npieces] out
     int32_t npieces, G, nt, trait;
     double c[kMaxT];                    // row `trait` of inv(R) (one trait: {1})
+    // per-record weights (kPat) only:
+    const int32_t* code;                // [n] the pattern of every record
+    const double* ctab;                 // [2^nt][nt][nt] C[code]
+    const double* x;                    // [n] covariate values (NULL: ones)
+    double* part2;                      // [npieces] out: piece sums of (w x) x C[code]_kk
 };
 
-template <class T>
+template <class T, bool kPat = false>
 __global__ __launch_bounds__(256) void k_locpar_sums(const SumArgs A)
 {
     const int64_t gt = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -75,13 +89,18 @@ __global__ __launch_bounds__(256) void k_locpar_sums(const SumArgs A)
     const int64_t p = gt / G;
     const int g = (int)(gt % G);
     const bool valid = p < A.npieces;
-    double acc = 0.0;
+    double acc = 0.0, acc2 = 0.0;
     if (valid) {
         const int lo = A.piece_lo[p], hi = A.piece_lo[p + 1];
         for (int j = lo + g; j < hi; j += G) {
             const int64_t i = A.rec ? A.rec[j] : j;
             double rho;
-            if (A.nt == 1) {
+            if constexpr (kPat) {
+                const double* crow = A.ctab + ((size_t)A.code[i] * A.nt + A.trait) * A.nt;
+                rho = 0.0;
+                for (int m = 0; m < A.nt; ++m) rho = rho + crow[m] * (double)((const T*)A.r)[(size_t)m * A.ld + i];
+                acc2 = acc2 + (A.wx[j] * (A.x ? A.x[i] : 1.0)) * crow[A.trait];
+            } else if (A.nt == 1) {
                 rho = (double)((const T*)A.r)[i];
             } else {
                 rho = 0.0;
@@ -92,6 +111,10 @@ __global__ __launch_bounds__(256) void k_locpar_sums(const SumArgs A)
     }
     for (int off = G >> 1; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);      // (groups are aligned to G: never leaves one)
     if (valid && g == 0) A.part[p] = acc;
+    if constexpr (kPat) {
+        for (int off = G >> 1; off >= 1; off >>= 1) acc2 = acc2 + __shfl_xor(acc2, off, 64);
+        if (valid && g == 0) A.part2[p] = acc2;
+    }
 }
 
 struct DrawArgs {
@@ -106,15 +129,23 @@ struct DrawArgs {
     int32_t nlevels, npartners, pos;
     double ckk, prior, s;               // lhs = d ckk + prior, sd = sqrt(s / lhs)
     uint32_t iter, rep, slot, seed_lo, seed_hi;
+    const double* part2;                // [npieces] per-record weights (kPat) only: the piece sums of D
 };
 
+template <bool kPat = false>
 __global__ __launch_bounds__(256) void k_locpar_draw(const DrawArgs A)
 {
     const int l = blockIdx.x * 256 + threadIdx.x;
     if (l >= A.nlevels) return;
     double S = 0.0;
     for (int p = A.level_piece[l]; p < A.level_piece[l + 1]; ++p) S = S + A.part[p];
-    const double dc = A.d[l] * A.ckk;
+    double dc;
+    if constexpr (kPat) {
+        dc = 0.0;
+        for (int p = A.level_piece[l]; p < A.level_piece[l + 1]; ++p) dc = dc + A.part2[p];
+    } else {
+        dc = A.d[l] * A.ckk;
+    }
     const double lhs = dc + A.prior;
     const double old = A.sol[A.off + l];
     double delta = 0.0;
@@ -192,14 +223,22 @@ struct StructDrawArgs {
     int32_t nshort, nlong, npartners, pos;
     double ckk, s;
     uint32_t iter, rep, slot, seed_lo, seed_hi;
+    const double* part2;                // [npieces] per-record weights (kPat) only: the piece sums of D
 };
 
 // the draw of level l given the prior sums P[m] = sum_j V_lj u_m,j (own member: without j == l) and the diagonal vll
+template <bool kPat>
 __device__ inline void locpar_structured_finish(const StructDrawArgs& A, int l, const double* P, double vll)
 {
     double S = 0.0;
     for (int q = A.level_piece[l]; q < A.level_piece[l + 1]; ++q) S = S + A.part[q];
-    const double dc = A.d[l] * A.ckk;
+    double dc;
+    if constexpr (kPat) {
+        dc = 0.0;
+        for (int q = A.level_piece[l]; q < A.level_piece[l + 1]; ++q) dc = dc + A.part2[q];
+    } else {
+        dc = A.d[l] * A.ckk;
+    }
     const double lhs = dc + A.p[A.pos] * vll;
     const double old = A.sol[A.off + l];
     double num = S + dc * old;
@@ -216,6 +255,7 @@ __device__ inline void locpar_structured_finish(const StructDrawArgs& A, int l, 
 }
 
 // grid: ceil(nshort / 256) workgroups of one thread per short row, then ceil(nlong / 4) workgroups of one wave per long row
+template <bool kPat = false>
 __global__ __launch_bounds__(256) void k_locpar_draw_structured(const StructDrawArgs A)
 {
     const int nshort_wg = (A.nshort + 255) / 256;
@@ -233,7 +273,7 @@ __global__ __launch_bounds__(256) void k_locpar_draw_structured(const StructDraw
             for (int m = 0; m < kMaxT; ++m)
                 if (m < A.npartners && !(j == l && m == A.pos)) P[m] = P[m] + v * A.sol[A.partner_off[m] + j];
         }
-        locpar_structured_finish(A, l, P, vll);
+        locpar_structured_finish<kPat>(A, l, P, vll);
     } else {
         const int i = ((int)blockIdx.x - nshort_wg) * 4 + (int)(threadIdx.x >> 6);          // (wave-uniform)
         if (i >= A.nlong) return;
@@ -252,7 +292,7 @@ __global__ __launch_bounds__(256) void k_locpar_draw_structured(const StructDraw
 #pragma unroll
             for (int m = 0; m < kMaxT; ++m) P[m] = P[m] + __shfl_xor(P[m], off, 64);
         }
-        if (lane == 0) locpar_structured_finish(A, l, P, vll);
+        if (lane == 0) locpar_structured_finish<kPat>(A, l, P, vll);
     }
 }
 

@@ -15,6 +15,9 @@
 //           0x20000000 | term ordinal, 3 + 16*trait).  The tag keeps the repetition word apart from the marker samplers' small
 //           counts, the liabilities' 0x40000000 and the Wishart draws' 0x80000000 (sampler_mt.hpp:533-549, whose slots start at 64)
 //           whatever the slot.
+//   slot 4: the normal of an imputed missing residual (mtmiss.hpp), Box-Muller as slot 1, indexed by (RECORD, iteration,
+//           0x10000000, 4 + 16*trait).  The tag 0x10000000 is no other stream's repetition word (small counts, 0x20000000 | term,
+//           0x40000000 | round, 0x80000000 | ...), and no other stream uses slot 4: neither the tag nor the slot is shared.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

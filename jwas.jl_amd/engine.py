@@ -672,6 +672,49 @@ class HipEngine:
         self._chk(self._L.jwas_hip_locpar_end(self._h))
         self._locpar_groups = {}
 
+    # -- multi-trait records that miss some traits (jwas_hip_mtmiss_*; residual.jl:2-73) ----------------------
+    @staticmethod
+    def mtmiss_estimate_bytes(n):
+        return _lib.load().jwas_hip_mtmiss_estimate_bytes(int(n))
+
+    def _mtmiss_table(self, tab, what):
+        t = self.ntraits
+        tv = np.ascontiguousarray(tab, dtype=np.float64)
+        if tv.shape != (1 << t, t, t):
+            raise ValueError(f"{what} must be a [2^t][t][t] table ({(1 << t, t, t)}, got {tv.shape})")
+        return tv
+
+    def mtmiss_begin(self, observed):
+        """observed: the code of every record (bit k set = trait k observed, 1 .. 2^t - 1), or an n x t boolean matrix.  After
+        init_state."""
+        ob = np.asarray(observed)
+        if ob.ndim == 2:
+            ob = ob.astype(np.int64) @ (1 << np.arange(ob.shape[1]))
+        cd = np.ascontiguousarray(ob, dtype=np.int32)
+        if cd.ndim != 1:
+            raise ValueError("observed must be a vector of codes or an n x t matrix")
+        self._chk(self._L.jwas_hip_mtmiss_begin(self._h, cd.size, _ptr(cd)))
+
+    def mtmiss_impute(self, *, iteration, seed, B, U):
+        """sampleMissingResiduals on the device: the residuals of the missing cells are redrawn from their conditional given the
+        observed ones.  B, U: the per-code tables [2^t][t][t] of the current R (csrc/mtmiss.hpp)."""
+        Bv, Uv = self._mtmiss_table(B, "B"), self._mtmiss_table(U, "U")
+        P = _lib.MtmissParams()
+        P.iteration, P.seed, P.B, P.U = int(iteration), int(seed), Bv.ctypes.data, Uv.ctypes.data
+        self._chk(self._L.jwas_hip_mtmiss_impute(self._h, C.byref(P)))
+
+    def mtmiss_set_record_weights(self, Ctab):
+        """Ctab [2^t][t][t]: every later locpar_step weights record i with Ctab[code_i] (its Rinv is ignored); None: back to
+        kron(inv(R), diag(w))."""
+        if Ctab is None:
+            self._chk(self._L.jwas_hip_mtmiss_set_record_weights(self._h, None))
+            return
+        Cv = self._mtmiss_table(Ctab, "C")
+        self._chk(self._L.jwas_hip_mtmiss_set_record_weights(self._h, _ptr(Cv)))
+
+    def mtmiss_end(self):
+        self._chk(self._L.jwas_hip_mtmiss_end(self._h))
+
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""
         out = np.empty(getattr(self, "n_out", 0), dtype=self.dtype)

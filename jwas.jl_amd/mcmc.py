@@ -5,6 +5,8 @@ Per iteration (the reference's order, MCMC_BayesianAlphabet.jl:184-421):
   0. categorical / censored traits: engine.liability_sample(...), then the threshold draw                (:186-191, DEVICE)
   1. location parameters: ycorr += X sol ; rhs = X'ycorr ; single-site Gibbs ; ycorr -= X sol   (:196-220, host, or DEVICE:
      engine.locpar_step(...), term by term from the resident residual -- location_parameters="device" / "auto")
+     multi-trait records that miss some traits: the host imputes their residuals first (residual.jl:51-73), or on the DEVICE
+     path engine.mtmiss_impute(...) does and locpar_step weights record by record until the first residual-variance draw
   4c. variances of the set_random effects from the device's U'U (sampleVCs, :347-351)            (host)
   2. marker effects: engine.sweep(...)                                                      (:224-290, DEVICE)
   3. pi  ~ Beta / Dirichlet from the sweep's counts                                          (:294-317, host)
@@ -71,6 +73,7 @@ def _design(model, df, ids_col):
 LOCPAR_METHODS = ("locpar_begin", "locpar_add_covariate", "locpar_add_factor", "locpar_step", "locpar_get_sol", "locpar_accumulate",
                   "locpar_get_means", "locpar_end")
 LOCPAR_PED_METHODS = ("locpar_set_group_structure",)      # ... and what a pedigree random effect needs on top
+MTMISS_METHODS = ("mtmiss_begin", "mtmiss_impute", "mtmiss_set_record_weights", "mtmiss_end")      # ... and partially missing multi-trait records
 LOCPAR_AUTO_LEVELS = 2048               # location_parameters="auto": more levels than this run on the device
 
 
@@ -214,6 +217,43 @@ def pick_block_size_mt(n_events, p, allow_1024=False):
     return 512 if n_events < MT_SPARSE_CHANGE_FRACTION * p else 256
 
 
+def _missing_pattern_matrices(R0, code):
+    """The matrices of one missing pattern (bit k of `code` set = trait k observed) under the residual covariance R0:
+    o / m: the observed / missing traits (boolean masks); Ro_inv = inv(R0[o, o]); Rc = R0[m, o];
+    C: Ro_inv embedded in a t x t matrix of zeros (the RZ of getRi, residual.jl:2-44);
+    B = Rc Ro_inv (|m| x |o|) and U = the upper Cholesky factor of R0[m, m] - Rc Ro_inv Rc' (residual.jl:63-69); both None for the
+    full pattern.  The one place these are formed: the host path, the device tables and the tests read the same doubles."""
+    t = R0.shape[0]
+    o = np.array([(code >> k) & 1 for k in range(t)], dtype=bool)
+    Ro_inv = np.linalg.inv(R0[np.ix_(o, o)])
+    RZ = np.zeros((t, t))
+    RZ[np.ix_(o, o)] = Ro_inv
+    out = {"o": o, "m": ~o, "Ro_inv": Ro_inv, "C": RZ, "Rc": None, "B": None, "U": None}
+    if not o.all():
+        m = ~o
+        Rc = R0[np.ix_(m, o)]
+        out["Rc"] = Rc
+        out["U"] = np.linalg.cholesky(R0[np.ix_(m, m)] - Rc @ Ro_inv @ Rc.T).T          # upper factor, as cholesky(...).U
+        out["B"] = (Ro_inv @ Rc.T).T
+    return out
+
+
+def missing_pattern_tables(R0):
+    """(B, U, C): the per-code tables of csrc/mtmiss.hpp for the residual covariance R0, each [2^t][t][t] (code 0 and the unused
+    entries zero; B and U in the top-left corner of their slot)."""
+    R0 = np.asarray(R0, dtype=np.float64)
+    t = R0.shape[0]
+    B, U, Ct = (np.zeros((1 << t, t, t)) for _ in range(3))
+    for code in range(1, 1 << t):
+        pm = _missing_pattern_matrices(R0, code)
+        Ct[code] = pm["C"]
+        if pm["B"] is not None:
+            nm, no = pm["B"].shape
+            B[code, :nm, :no] = pm["B"]
+            U[code, :nm, :nm] = pm["U"]
+    return B, U, Ct
+
+
 def _impute_missing_residuals(res, observed, R0, rng):
     """sampleMissingResiduals (residual.jl:52-73), in place on the per-trait residual vectors `res`: for every missing
     pattern the missing residuals are drawn from their conditional distribution given the observed ones,
@@ -225,16 +265,11 @@ def _impute_missing_residuals(res, observed, R0, rng):
     full = (1 << t) - 1
     for code in np.unique(codes):
         rows = np.nonzero(codes == code)[0]
-        o = np.array([(code >> k) & 1 for k in range(t)], dtype=bool)
-        Ro_inv = np.linalg.inv(R0[np.ix_(o, o)])
-        RZ = np.zeros((t, t))
-        RZ[np.ix_(o, o)] = Ro_inv
-        Ri_rows[rows] = RZ
+        pm = _missing_pattern_matrices(R0, int(code))
+        o, m, Ro_inv, Rc, U = pm["o"], pm["m"], pm["Ro_inv"], pm["Rc"], pm["U"]
+        Ri_rows[rows] = pm["C"]
         if code == full:
             continue
-        m = ~o
-        Rc = R0[np.ix_(m, o)]
-        U = np.linalg.cholesky(R0[np.ix_(m, m)] - Rc @ Ro_inv @ Rc.T).T          # upper factor, as cholesky(...).U
         eo = np.stack([res[k][rows] for k in np.nonzero(o)[0]], axis=1)          # rows x n_obs
         em = eo @ Ro_inv @ Rc.T + rng.standard_normal((len(rows), int(m.sum()))) @ U
         for c, k in enumerate(np.nonzero(m)[0]):
@@ -427,7 +462,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     elif stream:
         # the packed payload goes from the file straight to HBM and is never re-ordered: like the reference's stream
         # mode, phenotype IDs must match the genotype IDs exactly and in order (JWAS.jl:388-398)
-        if not complete.all() or list(ph[idcol]) != list(Mi.obsID):
+        # (a multi-trait record that misses SOME traits stays, with its missing residuals imputed every iteration: no row is dropped)
+        if not usable.all() or list(ph[idcol]) != list(Mi.obsID):
             raise ValueError("storage=:stream MVP requires exact genotype/phenotype ID match and order. "
                              "Please reorder phenotypes to match genotype IDs.")
         print("storage=:stream is enabled; genotype alignment is skipped and original ID order is used.")
@@ -848,13 +884,20 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     lp_terms, labels = _location_terms(model, ph)
     q = [len(lab) for lab in labels]
     lp_device = location_parameters == "device" or (location_parameters == "auto" and (bool(rnd) or sum(q) > LOCPAR_AUTO_LEVELS))
+    mt_device = False
     if lp_device and t > 1 and has_missing:
-        # the reference's per-record Ri (mkRi, residual.jl:2-44) does not factor as kron(inv(R), diag(w))
+        # the reference's per-record Ri (mkRi, residual.jl:2-44) does not factor as kron(inv(R), diag(w)): the device imputes the
+        # missing residuals and weights record by record (csrc/mtmiss.hpp); a fixed-only model under "auto" keeps the host scan
         if not rnd and location_parameters == "auto":
             lp_device = False
         else:
-            raise NotImplementedError("location parameters on the device need complete multi-trait records (the per-record Ri of "
-                                      "partially missing records stays on the host path, which has no random effects)")
+            eng_ = engine if engine is not None else (Mi.device_backend if devres else None)
+            missing_ = [m_ for m_ in MTMISS_METHODS if eng_ is not None and not hasattr(eng_, m_)]
+            if missing_:
+                raise NotImplementedError("location parameters on the device need complete multi-trait records (the per-record Ri of "
+                                          "partially missing records stays on the host path, which has no random effects); the engine "
+                                          "lacks " + ", ".join(missing_))
+            mt_device = True
     if rnd and not lp_device:
         raise NotImplementedError('set_random effects run on the device: location_parameters="host" has no random effects')
     if lp_device:
@@ -901,6 +944,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             for re_ in rnd:                                        # A-inverse and its colours (jwas_hip_lp_structure_estimate_bytes)
                 if re_.randomType == "A":
                     need += HipEngine.locpar_structure_estimate_bytes(re_.Vinv.shape[0], re_.Vinv.nnz)
+        if mt_device:                                              # the records' codes, the tables, the second piece sums
+            need += HipEngine.mtmiss_estimate_bytes(n)
         if outputEBV and not out_same:                             # Mi.output_genotypes: a second dense matrix (n_out x p)
             need += (8 if double_precision else 4) * ((len(out_rows) + 255) // 256 * 256) * p
         engine = HipEngine(device, precision=64 if double_precision else 32)
@@ -981,6 +1026,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 else:
                     grp = [g_ for g_, re_ in enumerate(rnd) if re_.name == nm and k in re_.traits]
                     engine.locpar_add_factor(k, val[0], val[1], grp[0] if grp else -1)
+        if mt_device:
+            engine.mtmiss_begin((observed.astype(np.int64) @ (1 << np.arange(t))).astype(np.int32))      # mme.missingPattern (residual.jl:17-21)
         Xf = None
     else:
         Xf, labels = _design(model, ph, idcol)
@@ -1140,6 +1187,12 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                     engine.set_thresholds(k, thresholds[k])              # :160
 
             # 1. location parameters: on the device (solver.jl:143-162 term by term, csrc/locpar.hpp) ...
+            if mt_device:
+                # sampleMissingResiduals (residual.jl:51-73) on the device, then the per-record Ri of mkRi / getRi until the first
+                # residual-variance draw and kron(inv(R), diag(w)) afterwards (MCMC_BayesianAlphabet.jl:357-361): the host path's switch
+                mt_B, mt_U, mt_C = missing_pattern_tables(np.asarray(vare, dtype=np.float64))
+                engine.mtmiss_impute(iteration=it, seed=seed_int, B=mt_B, U=mt_U)
+                engine.mtmiss_set_record_weights(mt_C if (it == 1 or not R.estimate_variance) else None)
             if lp_device:
                 if sum(q):
                     if t == 1:
@@ -1397,6 +1450,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         lp_mean, lp_mean2 = engine.locpar_get_means() if sum(q) else (np.zeros(0), np.zeros(0))
         lp_sd = np.sqrt(np.abs(lp_mean2 - lp_mean ** 2))
         engine.locpar_end()
+        if mt_device:
+            engine.mtmiss_end()
     else:
         lp_mean, lp_sd = run_sol.mean, run_sol.sd()
     for k in range(t):
