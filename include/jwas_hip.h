@@ -37,6 +37,9 @@
  *                              form, and the cross-products sampleVCs reads (variance_components.jl:115-147)
  *   jwas_hip_mtmiss_*          multi-trait records that miss some traits: sampleMissingResiduals (residual.jl:51-73) and the
  *                              per-record Ri of mkRi / getRi (residual.jl:2-44) in the location-parameter step
+ *   jwas_hip_annot_*           update_marker_annotation_priors!: the probit update of the annotation coefficients and the
+ *                              per-marker prior table of annotated BayesC / BayesR / 2-trait BayesC
+ *                              (MCMC/annotation_updates.jl:21-137,181-361)
  *
  * Conventions: every entry point returns 0 on success and a negative JWAS_HIP_E* code on failure
  * (no exceptions cross the boundary; jwas_hip_last_error() returns the message -- the analogue of
@@ -512,6 +515,58 @@ int  jwas_hip_mtmiss_set_record_weights(jwas_hip_ctx* ctx, const double* C);
 /* Device bytes of the state over n records (pure; an upper bound). */
 int64_t jwas_hip_mtmiss_estimate_bytes(int64_t n);
 int  jwas_hip_mtmiss_end(jwas_hip_ctx* ctx);
+
+/* ---- marker-annotation priors: the probit update from the resident delta (csrc/annot.hpp) --------------------------------------
+ * The reference regresses the inclusion indicators on marker annotations between sweeps (MCMC/annotation_updates.jl:21-137,181-361:
+ * truncated-normal liabilities, a coordinate Gibbs scan over the annotation coefficients, the rebuilt per-marker prior).  A session
+ * keeps the design matrix, the coefficients, the liabilities and the prior table on the device; a step reads the indicators the
+ * last sweep left (the context's element type; the int32 classes of BayesR) and writes the table where the next sweep reads it.
+ *   JWAS_HIP_ANNOT_BAYESC   1 step,  table = pi_vec  (p)              needs JWAS_HIP_BAYESC
+ *   JWAS_HIP_ANNOT_BAYESR   3 steps, table = pi_matrix (p x 4)        needs JWAS_HIP_BAYESR
+ *   JWAS_HIP_ANNOT_TREE     3 steps, table = log_prior_states_matrix  needs JWAS_HIP_MTBAYESC1 / 2 with two traits (states 00, 10, 01, 11)
+ * While a session is open, a sweep whose pi_vec / pi_matrix / log_prior_states_matrix is NULL reads the session's resident table
+ * (the convention of var_effect_matrix == NULL); a host pointer in that field is JWAS_HIP_EINVAL.  The limits of the marker-specific
+ * joint prior stay (two traits, block size <= 512).  All arithmetic is double in both precisions; csrc/annot.hpp has the formulas,
+ * the order of every sum (fixed by p alone: no floating-point atomics, identical bits run to run) and the RNG counters
+ * (philox4x32_10(marker | coefficient, iteration, 0x08000000 | step, 5 | 6)).  The shrinkage variance of a step's slopes is the
+ * caller's draw (annotation_updates.jl:125-137), passed into the next step.  Errors are decided before any launch: JWAS_HIP_ESTATE
+ * for _begin before jwas_hip_init_state or during a session, and for every other entry point without one; JWAS_HIP_EINVAL for a kind
+ * that does not match the context's method or trait count, a wrong p, ncols outside 1 .. JWAS_HIP_ANNOT_MAX_COLS, a first column
+ * that is not all ones, non-finite values, a variance that is not positive; JWAS_HIP_EUNSUP with a communicator attached and for
+ * the constraint = true methods (JWAS_HIP_MEGABAYES*).  The session is freed by _end, jwas_hip_init_state, jwas_hip_destroy or
+ * loading genotypes. */
+#define JWAS_HIP_ANNOT_MAX_COLS 64
+enum { JWAS_HIP_ANNOT_BAYESC = 0, JWAS_HIP_ANNOT_BAYESR = 1, JWAS_HIP_ANNOT_TREE = 2 };
+typedef struct jwas_annot_params {
+    uint32_t iteration;                 /* MCMC iteration >= 1 (enters the RNG counter)                                          */
+    uint32_t reserved;
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                     */
+    double   variance[3];               /* the shrinkage variance of every step's slopes (not read when ncols == 1)              */
+} jwas_annot_params;
+typedef struct jwas_annot_stats {
+    double  coef[3 * JWAS_HIP_ANNOT_MAX_COLS];  /* the coefficients AFTER the step: step s at coef + s * ncols                  */
+    int64_t n_active[3];                /* |A_s| of every step                                                                   */
+    double  means[4];                   /* column means of the table (the probabilities, not their logs); BayesC: means[0]       */
+    double  step_ms;                    /* device time of the step (HIP events on the context's stream)                          */
+} jwas_annot_stats;
+/* Open a session.  D_rowmajor: the p x ncols design matrix, column 0 the intercept's ones; coef: [nsteps][ncols] start values;
+ * variance: [nsteps] (checked only: every step takes its variances from its params; may be NULL); start_prior: the table the
+ * first sweep reads -- p, p x 4 or the p x 4 logs.  Liabilities and mu start at 0. */
+int  jwas_hip_annot_begin(jwas_hip_ctx* ctx, int32_t kind, int64_t p, int32_t ncols, const double* D_rowmajor, const double* coef,
+                          const double* variance, const double* start_prior);
+/* One update: every step's liabilities and coefficient scan from the resident delta, then the table.  Synchronous. */
+int  jwas_hip_annot_step(jwas_hip_ctx* ctx, const jwas_annot_params* params, jwas_annot_stats* stats);
+/* Running mean and mean of squares of the per-marker prior probabilities on the device: mean += (v - mean) / nsamples. */
+int  jwas_hip_annot_accumulate(jwas_hip_ctx* ctx, double nsamples);
+/* The resident table as the sweep reads it (nvalues = p for BayesC, 4 p otherwise). */
+int  jwas_hip_annot_get_prior(jwas_hip_ctx* ctx, int64_t nvalues, double* out);
+int  jwas_hip_annot_get_means(jwas_hip_ctx* ctx, int64_t nvalues, double* out_mean, double* out_mean2);
+/* The liabilities / mu of every step, [nsteps][p] (for tests and sample files). */
+int  jwas_hip_annot_get_liability(jwas_hip_ctx* ctx, int64_t nvalues, double* out);
+int  jwas_hip_annot_get_mu(jwas_hip_ctx* ctx, int64_t nvalues, double* out);
+/* Device bytes of a session (pure; an upper bound). */
+int64_t jwas_hip_annot_estimate_bytes(int64_t p, int32_t ncols, int32_t kind);
+int  jwas_hip_annot_end(jwas_hip_ctx* ctx);
 
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the

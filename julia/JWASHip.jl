@@ -341,6 +341,66 @@ hip_mtmiss_set_record_weights!(b::HipBackend, C::Union{Nothing,Array{Float64,3}}
 hip_mtmiss_estimate_bytes(n::Integer) = ccall((:jwas_hip_mtmiss_estimate_bytes, LIBJWAS_HIP), Int64, (Int64,), n)
 hip_mtmiss_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_mtmiss_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
 
+"Marker-annotation priors on the device (MCMC/annotation_updates.jl:21-137,181-361; csrc/annot.hpp).  `hip_annot_begin!` opens a
+session (kind 0 = annotated BayesC, 1 = BayesR, 2 = the 2-trait tree) with the p x ncols design matrix (column 1 the ones), the
+start coefficients (ncols x nsteps) and the table the first sweep reads; `hip_annot_step!` replaces update_marker_annotation_priors!
+from the resident delta and leaves the per-marker prior where the next sweep reads it: pass C_NULL for pi_vec / pi_matrix /
+log_prior_states_matrix while the session is open.  The shrinkage variances stay the caller's draw (annotation_updates.jl:125-137)."
+struct HipAnnotParams
+    iteration::UInt32
+    reserved::UInt32
+    seed::UInt64
+    variance::NTuple{3,Float64}
+end
+struct HipAnnotStats
+    coef::NTuple{192,Float64}
+    n_active::NTuple{3,Int64}
+    means::NTuple{4,Float64}
+    step_ms::Float64
+end
+function hip_annot_begin!(b::HipBackend, kind::Integer, D::Matrix{Float64}, coef::VecOrMat{Float64}, variance::Vector{Float64},
+                          start_prior::VecOrMat{Float64})
+    Dr = permutedims(D)                                   # row-major p x ncols
+    cf = vec(Matrix{Float64}(reshape(coef, size(D, 2), :)))   # column-major ncols x nsteps == the library's [nsteps][ncols]
+    sp = start_prior isa Matrix ? vec(permutedims(start_prior)) : start_prior
+    hip_check(b.ctx, ccall((:jwas_hip_annot_begin, LIBJWAS_HIP), Cint,
+                           (Ptr{Cvoid}, Int32, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                           b.ctx, kind, size(D, 1), size(D, 2), Dr, cf, variance, sp))
+end
+function hip_annot_step!(b::HipBackend, iter::Integer, seed::Integer, variance)
+    v = ntuple(i -> i <= length(variance) ? Float64(variance[i]) : 1.0, 3)
+    S = Ref{HipAnnotStats}()
+    hip_check(b.ctx, ccall((:jwas_hip_annot_step, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipAnnotParams}, Ref{HipAnnotStats}),
+                           b.ctx, HipAnnotParams(UInt32(iter), UInt32(0), UInt64(seed), v), S))
+    S[]
+end
+hip_annot_accumulate!(b::HipBackend, nsamples::Real) =
+    hip_check(b.ctx, ccall((:jwas_hip_annot_accumulate, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Float64), b.ctx, nsamples))
+function _hip_annot_get(b::HipBackend, sym::Symbol, nvalues::Integer)
+    out = Vector{Float64}(undef, nvalues)
+    if sym === :prior
+        hip_check(b.ctx, ccall((:jwas_hip_annot_get_prior, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), b.ctx, nvalues, out))
+    elseif sym === :liability
+        hip_check(b.ctx, ccall((:jwas_hip_annot_get_liability, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), b.ctx, nvalues, out))
+    else
+        hip_check(b.ctx, ccall((:jwas_hip_annot_get_mu, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), b.ctx, nvalues, out))
+    end
+    out
+end
+"The resident table as the sweep reads it, row-major (nvalues = p, or 4 p)."
+hip_annot_prior(b::HipBackend, nvalues::Integer) = _hip_annot_get(b, :prior, nvalues)
+"The liabilities / mu of every step, [nsteps][p] (nvalues = nsteps * p)."
+hip_annot_liability(b::HipBackend, nvalues::Integer) = _hip_annot_get(b, :liability, nvalues)
+hip_annot_mu(b::HipBackend, nvalues::Integer) = _hip_annot_get(b, :mu, nvalues)
+function hip_annot_means(b::HipBackend, nvalues::Integer)
+    m, m2 = Vector{Float64}(undef, nvalues), Vector{Float64}(undef, nvalues)
+    hip_check(b.ctx, ccall((:jwas_hip_annot_get_means, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}), b.ctx, nvalues, m, m2))
+    m, m2
+end
+hip_annot_estimate_bytes(p::Integer, ncols::Integer, kind::Integer) =
+    ccall((:jwas_hip_annot_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int32, Int32), p, ncols, kind)
+hip_annot_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_annot_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

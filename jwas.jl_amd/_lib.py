@@ -50,7 +50,11 @@ SYMBOLS = [
     "jwas_hip_lp_set_group_structure", "jwas_hip_lp_get_group_colors", "jwas_hip_lp_structure_estimate_bytes",
     "jwas_hip_mtmiss_begin", "jwas_hip_mtmiss_impute", "jwas_hip_mtmiss_set_record_weights", "jwas_hip_mtmiss_estimate_bytes",
     "jwas_hip_mtmiss_end",
+    "jwas_hip_annot_begin", "jwas_hip_annot_step", "jwas_hip_annot_accumulate", "jwas_hip_annot_get_prior", "jwas_hip_annot_get_means",
+    "jwas_hip_annot_get_liability", "jwas_hip_annot_get_mu", "jwas_hip_annot_estimate_bytes", "jwas_hip_annot_end",
 ]
+ANNOT_MAX_COLS = 64                     # columns of the annotation design matrix, the intercept included (JWAS_HIP_ANNOT_MAX_COLS)
+ANNOT_BAYESC, ANNOT_BAYESR, ANNOT_TREE = 0, 1, 2
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
@@ -116,6 +120,14 @@ class LocparStats(C.Structure):
 
 class MtmissParams(C.Structure):
     _fields_ = [("iteration", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("B", C.c_void_p), ("U", C.c_void_p)]
+
+
+class AnnotParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("variance", C.c_double * 3)]
+
+
+class AnnotStats(C.Structure):
+    _fields_ = [("coef", C.c_double * (3 * ANNOT_MAX_COLS)), ("n_active", C.c_int64 * 3), ("means", C.c_double * 4), ("step_ms", C.c_double)]
 
 
 class JwasHipError(RuntimeError):
@@ -242,6 +254,16 @@ def load():
     L.jwas_hip_mtmiss_estimate_bytes.argtypes = [i64]
     L.jwas_hip_mtmiss_estimate_bytes.restype = i64
     L.jwas_hip_mtmiss_end.argtypes = [vp]
+    L.jwas_hip_annot_begin.argtypes = [vp, i32, i64, i32, vp, vp, vp, vp]
+    L.jwas_hip_annot_step.argtypes = [vp, C.POINTER(AnnotParams), C.POINTER(AnnotStats)]
+    L.jwas_hip_annot_accumulate.argtypes = [vp, C.c_double]
+    L.jwas_hip_annot_get_prior.argtypes = [vp, i64, vp]
+    L.jwas_hip_annot_get_means.argtypes = [vp, i64, vp, vp]
+    L.jwas_hip_annot_get_liability.argtypes = [vp, i64, vp]
+    L.jwas_hip_annot_get_mu.argtypes = [vp, i64, vp]
+    L.jwas_hip_annot_estimate_bytes.argtypes = [i64, i32, i32]
+    L.jwas_hip_annot_estimate_bytes.restype = i64
+    L.jwas_hip_annot_end.argtypes = [vp]
     L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_accumulate.argtypes = [vp, C.c_double]
@@ -266,7 +288,8 @@ def load():
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_estimate_bytes", "jwas_hip_estimate_bytes_storage", "jwas_hip_gwas_estimate_bytes",
-                        "jwas_hip_locpar_estimate_bytes", "jwas_hip_lp_structure_estimate_bytes", "jwas_hip_mtmiss_estimate_bytes"):
+                        "jwas_hip_locpar_estimate_bytes", "jwas_hip_lp_structure_estimate_bytes", "jwas_hip_mtmiss_estimate_bytes",
+                        "jwas_hip_annot_estimate_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -487,7 +487,8 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
             memory_guard="error", memory_guard_ratio=0.80, output_folder="results",
             output_samples_for_all_parameters=False,
             # device options (the analogue of storage=:stream's opt-in knobs)
-            device=0, block_size=None, gram_mode="mfma", blocks_per_launch=None, location_parameters="auto", _engine=None):
+            device=0, block_size=None, gram_mode="mfma", blocks_per_launch=None, location_parameters="auto",
+            annotation_priors="host", _engine=None):
     """JWAS.jl:161-511.  Returns the reference's output Dict (output.jl:108-212) as a dict of pandas
     DataFrames and writes the same text files under `output_folder`.
 
@@ -513,6 +514,14 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     numpy generator, the device path from the counter generator, so the choice is part of what a seed means; a fixed-only model
     with partially missing multi-trait records stays on "host" under "auto".
 
+    annotation_priors (device option): where the probit update of the annotation coefficients between two sweeps runs (annotated
+    BayesC, BayesR and 2-trait BayesC).  "host" (the default): annotations.py from the downloaded indicators, every draw from the
+    numpy generator.  "device": csrc/annot.hpp from the resident indicators -- liabilities, the coefficient scan and the rebuilt
+    per-marker prior table stay on the device, the sweep reads the table in place, only the coefficients and a few sums come back;
+    the liabilities and the coefficients' normals come from the counter generator, the shrinkage variances stay on the numpy
+    generator.  The choice is therefore part of what a seed means, as with location_parameters.  Not with storage=:stream,
+    constraint=true or marker shards (explicit errors).
+
     Categorical / censored traits (build_model(...; categorical_trait, censored_trait)): categories coded 1, 2, 3 ... (two of them
     make a binary trait), bounds of a censored trait in the columns <trait>_l / <trait>_u; the liabilities are sampled on the
     device before the location parameters of every iteration (mcmc.py step 0) and saved, with the thresholds, as
@@ -536,6 +545,8 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
         raise NotImplementedError("models without a genotype term have no marker sweep: use the reference")
     if location_parameters not in ("auto", "host", "device"):
         raise ValueError('location_parameters must be "auto", "host" or "device".')
+    if annotation_priors not in ("host", "device"):
+        raise ValueError('annotation_priors must be "host" or "device".')
     if memory_guard not in ("error", "warn", "off"):
         raise ValueError("memory_guard must be :error, :warn or :off.")
     if output_samples_frequency is None:
@@ -563,5 +574,5 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
                      output_folder=output_folder, printout_frequency=printout_frequency,
                      memory_guard=memory_guard, memory_guard_ratio=memory_guard_ratio,
                      missing_phenotypes=missing_phenotypes, device=device, block_size=block_size,
-                     gram_mode=gram_mode, blocks_per_launch=blocks_per_launch, location_parameters=location_parameters, engine=_engine, printout_model_info=printout_model_info,
+                     gram_mode=gram_mode, blocks_per_launch=blocks_per_launch, location_parameters=location_parameters, annotation_priors=annotation_priors, engine=_engine, printout_model_info=printout_model_info,
                      output_samples_for_all_parameters=output_samples_for_all_parameters)

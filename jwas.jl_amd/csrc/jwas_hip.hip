@@ -7,6 +7,7 @@
 #include "liability.hpp"
 #include "locpar.hpp"
 #include "mtmiss.hpp"
+#include "annot.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -229,6 +230,18 @@ struct jwas_hip_ctx {
         int32_t* code = nullptr;                            // [n] the pattern of every record
         double* tab = nullptr;                              // [3][kMaxCodes * 16] the tables B, U, C (each [2^t][t][t] at its start)
     } mt;
+    // Marker-annotation priors (jwas_hip_annot_begin .. _end; MCMC/annotation_updates.jl; csrc/annot.hpp).  The table lives in
+    // pi_vec / pi_mat / lpr_mat above: where the sweep reads it.
+    struct Annot {
+        bool active = false;
+        int kind = 0, nsteps = 0, K = 0, npieces = 0;
+        double* D = nullptr;                                // [K - 1][p] the design matrix without its column of ones
+        double *liab = nullptr, *mu = nullptr;              // [nsteps][p]
+        double* e = nullptr;                                // [p] the latent residual of the running step
+        double *part = nullptr, *part4 = nullptr;           // [npieces][3] piece sums of a coefficient, [npieces][4] of the table's columns
+        double* scal = nullptr;                             // coef [3][K] | n_A [3] | column means [4] | c_k - c_k' [1] | dsq [K]
+        double *mean = nullptr, *mean2 = nullptr;           // [table size] running means of the prior probabilities
+    } an;
 };
 
 static constexpr int kStatGrid = 128;
@@ -392,8 +405,16 @@ static void mtmiss_free(jwas_hip_ctx* c)
     c->mt = jwas_hip_ctx::Mtmiss();
 }
 
+static void annot_free(jwas_hip_ctx* c)
+{
+    auto& b = c->an;
+    for (void* q : {(void*)b.D, (void*)b.liab, (void*)b.mu, (void*)b.e, (void*)b.part, (void*)b.part4, (void*)b.scal, (void*)b.mean, (void*)b.mean2}) (void)hipFree(q);
+    b = jwas_hip_ctx::Annot();
+}
+
 static void free_storage(jwas_hip_ctx* c)
 {
+    annot_free(c);                      // (the prior table below belongs to the markers of this matrix)
     mtmiss_free(c);                     // (the codes describe the records of this matrix)
     gwas_free(c);                       // (a session is bound to the matrix it was begun on)
     liab_free(c);                       // (the liabilities belong to the residual of this matrix)
@@ -1128,6 +1149,11 @@ int jwas_hip_set_gram(jwas_hip_ctx* c, int64_t blk, const float* in)
 // ---- chain state ----------------------------------------------------------------------------------
 int jwas_hip_init_state(jwas_hip_ctx* c, int32_t method, int32_t nt)
 {
+    if (c && c->an.active) {            // (an annotation session reads the indicators of the chain that ends here)
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        annot_free(c);
+    }
     if (c && IS_F64(c)) return f64_init_state(c, method, nt);
     NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
     NEED(c, HAVE_STORAGE(c), JWAS_HIP_ESTATE, "no genotype matrix loaded");
@@ -1974,9 +2000,15 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
          "sweep method/ntraits (%d/%d) differ from init_state (%d/%d)", P->method, P->ntraits, c->method, c->ntraits);
     const int t = c->ntraits;
     HIPCHK(c, hipSetDevice(c->device));
+    // an open annotation session (jwas_hip_annot_begin): its resident table stands in for the prior pointer, which must be NULL
+    NEED(c, !(c->an.active && (P->pi_vec || P->pi_matrix || P->log_prior_states_matrix)), JWAS_HIP_EINVAL,
+         "an annotation session is open: the sweep reads its resident prior table, pi_vec / pi_matrix / log_prior_states_matrix must be NULL");
+    const bool use_pi_vec = P->pi_vec || (c->an.active && c->an.kind == jwa::kBayesC);
+    const bool use_pi_mat = P->pi_matrix || (c->an.active && c->an.kind == jwa::kBayesR);
+    const bool use_lpr = P->log_prior_states_matrix || (c->an.active && c->an.kind == jwa::kTree);
 
     DevParams D;
-    c->lpr_active = is_mt_method(c->method) && !is_mega(c->method) && !has_marker_cov(c->method) && P->log_prior_states_matrix != nullptr;
+    c->lpr_active = is_mt_method(c->method) && !is_mega(c->method) && !has_marker_cov(c->method) && use_lpr;
     std::memset(&D, 0, sizeof D);
     D.method = c->method; D.ntraits = t; D.nreps = P->nreps;
     D.iter = P->iteration; D.seed_lo = (uint32_t)P->seed; D.seed_hi = (uint32_t)(P->seed >> 32); D.marker0 = P->marker_offset;
@@ -1988,7 +2020,7 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
         // variances), parked in LDS beside the marker's draws
         NEED(c, P->var_effect_matrix || c->var_mat_resident, JWAS_HIP_EINVAL, "multi-trait BayesA/B needs per-marker effect covariances (var_effect_matrix, or jwas_hip_sample_marker_covariances)");
         NEED(c, !P->independent_blocks, JWAS_HIP_EUNSUP, "independent_blocks is not available with per-marker effect covariances");
-        NEED(c, !P->log_prior_states_matrix, JWAS_HIP_EUNSUP, "marker-specific joint priors are not available with per-marker effect covariances");
+        NEED(c, !use_lpr, JWAS_HIP_EUNSUP, "marker-specific joint priors are not available with per-marker effect covariances");
         NEED(c, c->block_size * t <= 2048, JWAS_HIP_EUNSUP, "per-marker effect covariances need block_size * ntraits <= 2048 (got %d x %d)", c->block_size, t);
         const size_t mb = sizeof(float) * (size_t)t * t * c->p;
         if (P->var_effect_matrix) { int rc = upload_vec(c, (void**)&c->var_mat, P->var_effect_matrix, mb); if (rc) return rc; c->var_mat_resident = true; }
@@ -2002,13 +2034,15 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
             NEED(c, inv_small(P->var_effect, t, D.Ginv) == 0, JWAS_HIP_EINVAL, "marker effect covariance matrix is singular");
         bool any_finite = false;
         for (int i = 0; i < (1 << t); ++i) { D.log_prior[i] = P->log_prior_states[i]; any_finite = any_finite || std::isfinite(D.log_prior[i]); }
-        if ((c->method == JWAS_HIP_MTBAYESC2 || c->method == JWAS_HIP_MTBAYESB2) && !P->log_prior_states_matrix)      // MTBayesABC.jl:190
+        if ((c->method == JWAS_HIP_MTBAYESC2 || c->method == JWAS_HIP_MTBAYESB2) && !use_lpr)      // MTBayesABC.jl:190
             NEED(c, any_finite, JWAS_HIP_EINVAL, "All MTBayesABC sampler II state probabilities are zero or invalid.");
-        if (P->log_prior_states_matrix) {          // MarkerSpecificPiPrior (MTBayesABC.jl:22-47)
+        if (use_lpr) {          // MarkerSpecificPiPrior (MTBayesABC.jl:22-47)
             NEED(c, t == 2, JWAS_HIP_EUNSUP, "marker-specific joint priors support 2 traits (got %d)", t);
             NEED(c, c->block_size <= 512, JWAS_HIP_EUNSUP, "marker-specific joint priors need a block size <= 512 (got %d)", c->block_size);
-            int rc = upload_vec(c, (void**)&c->lpr_mat, P->log_prior_states_matrix, sizeof(double) * (size_t)(1 << t) * c->p);
-            if (rc) return rc;
+            if (P->log_prior_states_matrix) {
+                int rc = upload_vec(c, (void**)&c->lpr_mat, P->log_prior_states_matrix, sizeof(double) * (size_t)(1 << t) * c->p);
+                if (rc) return rc;
+            }
         }
     } else if (is_mega(c->method)) {
         // megaBayesABC! (BayesABC.jl:1-8): trait k uses vare[k,k], var_effect[k,k] (BayesA/B: the marker's own) and its own pi (pi_classes[k])
@@ -2024,16 +2058,18 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
     if (c->method == JWAS_HIP_BAYESR) {
         // bayesr_validate_priors / sigmaSq check (BayesR.jl:9-20,50)
         NEED(c, P->var_effect[0] > 0.f, JWAS_HIP_EINVAL, "BayesR sigmaSq must be positive.");
-        if (!P->pi_matrix) {
+        if (!use_pi_mat) {
             double s = 0.0;
             for (int k = 0; k < 4; ++k) { NEED(c, P->pi_classes[k] >= 0.0, JWAS_HIP_EINVAL, "BayesR pi entries must be nonnegative."); s += P->pi_classes[k]; }
             NEED(c, std::fabs(s - 1.0) <= 1e-8, JWAS_HIP_EINVAL, "BayesR pi must sum to 1.");
         }
         for (int k = 0; k < 4; ++k) { D.pi4[k] = P->pi_classes[k]; D.gamma[k] = P->gamma[k]; }
-        if (P->pi_matrix) { int rc = upload_vec(c, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; D.pi_mat = c->pi_mat; }
+        if (P->pi_matrix) { int rc = upload_vec(c, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; }
+        if (use_pi_mat) D.pi_mat = c->pi_mat;
     } else if (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) {
         D.pi = P->pi;
-        if (P->pi_vec) { int rc = upload_vec(c, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; D.pi_vec = c->pi_vec; }
+        if (P->pi_vec) { int rc = upload_vec(c, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; }
+        if (use_pi_vec) D.pi_vec = c->pi_vec;
         if (c->method == JWAS_HIP_BAYESB) {
             NEED(c, P->var_effect_vec, JWAS_HIP_EINVAL, "BayesB needs per-marker effect variances (var_effect_vec)");
             int rc = upload_vec(c, (void**)&c->var_vec, P->var_effect_vec, sizeof(float) * c->p); if (rc) return rc;
@@ -2081,7 +2117,7 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
     // A uniform prior pi = 0 (single-trait BayesA/B/C: RR-BLUP, BayesA, BayesL, the reference's own benchmark setting): the
     // kernel instantiation whose sampler follows Rule D on every path and takes dense_big_st on full 256- / 512-marker blocks
     // (sweep.hpp).  Every marker of every block changes, so the update role shares the apply work (COOP) unless told not to.
-    const bool dense_big = (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) && P->pi == 0.0 && P->pi_vec == nullptr;
+    const bool dense_big = (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) && P->pi == 0.0 && !use_pi_vec;
     // multi-trait sweeps in which most markers changed last time (the reference's default prior: every marker in the model),
     // single pass over <= 128-marker blocks: the dense-walk-only instantiation of the sampler (sampler_role_mt<.., DW>: the same
     // chain, a fraction of the code).  JWAS_HIP_DENSE_MT=0|1 overrides (tests: both instantiations give the same bits).
@@ -2091,7 +2127,7 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
     // change": config 4's chain at 22 000 changes per sweep, 19 ms on the walk against 42 ms through the speculative rounds)
     static const double dense_mt_fraction = std::getenv("JWAS_HIP_DENSE_MT_FRACTION") ? std::atof(std::getenv("JWAS_HIP_DENSE_MT_FRACTION")) : 0.1;
     // ... and full 256-marker blocks of sampler I with one shared covariance (dense_big_mt: decided per launch below)
-    const bool dense_mt256 = c->block_size == 256 && (c->method == JWAS_HIP_MTBAYESC1 || c->method == JWAS_HIP_MTBAYESB1) && !P->log_prior_states_matrix;
+    const bool dense_mt256 = c->block_size == 256 && (c->method == JWAS_HIP_MTBAYESC1 || c->method == JWAS_HIP_MTBAYESB1) && !use_lpr;
     const bool dense_mt = is_mt_method(c->method) && !is_sampler2(c->method) && (c->block_size <= 128 || dense_mt256) && P->nreps == 1 && !P->independent_blocks &&
                           (edm ? std::atoi(edm) != 0 : c->last_events >= (dense_mt256 ? dense_mt_fraction : 0.6) * (double)c->p);
     const int dense_big_off = std::getenv("JWAS_HIP_DENSE_BIG_OFF") != nullptr ? 1 : 0;      // (tests: the same chain through the general path)
@@ -2655,13 +2691,19 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
          "through jwas_hip_set_marker_covariances_f64 (or draws them with jwas_hip_sample_marker_covariances)");
     const int t = c->ntraits;
     NEED(c, F->bstride * t <= 2048, JWAS_HIP_EUNSUP, "Float64 contexts need block size x traits <= 2048 (got %d x %d)", F->bstride, t);
+    // an open annotation session (jwas_hip_annot_begin): its resident table stands in for the prior pointer, which must be NULL
+    NEED(c, !(c->an.active && (P->pi_vec || P->pi_matrix || P->log_prior_states_matrix)), JWAS_HIP_EINVAL,
+         "an annotation session is open: the sweep reads its resident prior table, pi_vec / pi_matrix / log_prior_states_matrix must be NULL");
+    const bool use_pi_vec = P->pi_vec || (c->an.active && c->an.kind == jwa::kBayesC);
+    const bool use_pi_mat = P->pi_matrix || (c->an.active && c->an.kind == jwa::kBayesR);
+    const bool use_lpr = P->log_prior_states_matrix || (c->an.active && c->an.kind == jwa::kTree);
     const bool marker_cov = has_marker_cov(c->method);
     if (marker_cov) {       // multi-trait BayesA/B (MTBayesABC.jl:66,86-90): the limits of the Float32 path
         NEED(c, F->var_mat && F->var_mat_resident, JWAS_HIP_EINVAL, "multi-trait BayesA/B needs per-marker effect covariances (jwas_hip_set_marker_covariances_f64, or jwas_hip_sample_marker_covariances)");
         NEED(c, !P->independent_blocks, JWAS_HIP_EUNSUP, "independent_blocks is not available with per-marker effect covariances");
-        NEED(c, !P->log_prior_states_matrix, JWAS_HIP_EUNSUP, "marker-specific joint priors are not available with per-marker effect covariances");
+        NEED(c, !use_lpr, JWAS_HIP_EUNSUP, "marker-specific joint priors are not available with per-marker effect covariances");
     }
-    if (P->log_prior_states_matrix) {       // MarkerSpecificPiPrior (MTBayesABC.jl:22-47)
+    if (use_lpr) {       // MarkerSpecificPiPrior (MTBayesABC.jl:22-47)
         NEED(c, is_mt_method(c->method), JWAS_HIP_EINVAL, "log_prior_states_matrix is for the multi-trait samplers");
         NEED(c, t == 2, JWAS_HIP_EUNSUP, "marker-specific joint priors support 2 traits (got %d)", t);
     }
@@ -2700,13 +2742,13 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
         if (!marker_cov) NEED(c, inv_d(D.var_effect, D.Ginv) == 0, JWAS_HIP_EINVAL, "marker effect covariance matrix is singular");
         bool any_finite = false;
         for (int i = 0; i < (1 << t); ++i) { D.log_prior[i] = P->log_prior_states[i]; any_finite = any_finite || std::isfinite(D.log_prior[i]); }
-        if (is_sampler2(c->method) && !P->log_prior_states_matrix)      // MTBayesABC.jl:190
+        if (is_sampler2(c->method) && !use_lpr)      // MTBayesABC.jl:190
             NEED(c, any_finite, JWAS_HIP_EINVAL, "All MTBayesABC sampler II state probabilities are zero or invalid.");
         if (P->log_prior_states_matrix) {
             int rc = upload_vec(c, (void**)&c->lpr_mat, P->log_prior_states_matrix, sizeof(double) * (size_t)(1 << t) * c->p);
             if (rc) return rc;
-            D.lpr_mat = c->lpr_mat;
         }
+        if (use_lpr) D.lpr_mat = c->lpr_mat;
         if (marker_cov) {
             if (!F->ginv_mat) HIPCHK(c, hipMalloc(&F->ginv_mat, sizeof(double) * (size_t)t * t * c->p));
             D.ginv_mat = F->ginv_mat;
@@ -2714,16 +2756,18 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
     } else NEED(c, D.vare[0] > 0.0, JWAS_HIP_EINVAL, "residual variance must be positive");
     if (c->method == JWAS_HIP_BAYESR) {
         NEED(c, D.var_effect[0] > 0.0, JWAS_HIP_EINVAL, "BayesR sigmaSq must be positive.");
-        if (!P->pi_matrix) {
+        if (!use_pi_mat) {
             double sum = 0.0;
             for (int k = 0; k < 4; ++k) { NEED(c, P->pi_classes[k] >= 0.0, JWAS_HIP_EINVAL, "BayesR pi entries must be nonnegative."); sum += P->pi_classes[k]; }
             NEED(c, std::fabs(sum - 1.0) <= 1e-8, JWAS_HIP_EINVAL, "BayesR pi must sum to 1.");
         }
         for (int k = 0; k < 4; ++k) { D.pi4[k] = P->pi_classes[k]; D.gamma[k] = P->gamma[k]; }
-        if (P->pi_matrix) { int rc = upload_vec(c, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; D.pi_mat = c->pi_mat; }
+        if (P->pi_matrix) { int rc = upload_vec(c, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; }
+        if (use_pi_mat) D.pi_mat = c->pi_mat;
     } else if (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) {
         D.pi = P->pi;
-        if (P->pi_vec) { int rc = upload_vec(c, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; D.pi_vec = c->pi_vec; }
+        if (P->pi_vec) { int rc = upload_vec(c, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; }
+        if (use_pi_vec) D.pi_vec = c->pi_vec;
         if (c->method == JWAS_HIP_BAYESB) {
             NEED(c, P->var_effect_vec_f64, JWAS_HIP_EINVAL, "BayesB needs per-marker effect variances (var_effect_vec_f64)");
             int rc = upload_vec(c, (void**)&F->var_vec, P->var_effect_vec_f64, sizeof(double) * c->p); if (rc) return rc;
@@ -4258,6 +4302,241 @@ int jwas_hip_mtmiss_end(jwas_hip_ctx* c)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     mtmiss_free(c);
+    return JWAS_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- marker-annotation priors (csrc/annot.hpp): MCMC/annotation_updates.jl:21-137,181-361 ----------------------------------------
+#define NEED_ANNOT(c)                                                                                                  \
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
+    NEED(c, c->an.active, JWAS_HIP_ESTATE, "jwas_hip_annot_begin has not been called")
+
+static int64_t annot_table_size(int kind, int64_t p) { return kind == jwa::kBayesC ? p : 4 * p; }
+
+static double** annot_table_slot(jwas_hip_ctx* c, int kind)
+{
+    return kind == jwa::kBayesC ? &c->pi_vec : kind == jwa::kBayesR ? &c->pi_mat : &c->lpr_mat;
+}
+
+// the indicators of trait `trait` as the sweep leaves them
+static const void* annot_delta(jwas_hip_ctx* c, int trait)
+{
+    if (IS_F64(c)) return c->method == JWAS_HIP_BAYESR ? c->f64->delta : (const void*)((const double*)c->f64->delta + (size_t)trait * c->p);
+    return (const void*)((const float*)c->delta + (size_t)trait * c->p);
+}
+
+template <class DT, int KIND>
+static void annot_launch_step(jwas_hip_ctx* c, const jwa::StepArgs& A, bool first)
+{
+    const dim3 grid((unsigned)c->an.npieces), blk(256);
+    if (first) hipLaunchKernelGGL((jwa::k_annot_liab<DT, KIND>), grid, blk, 0, c->stream, A);
+    else       hipLaunchKernelGGL((jwa::k_annot_sums<DT, KIND>), grid, blk, 0, c->stream, A);
+}
+
+static void annot_launch_any(jwas_hip_ctx* c, const jwa::StepArgs& A, bool first)
+{
+    switch (c->an.kind) {
+        case jwa::kBayesC: if (IS_F64(c)) annot_launch_step<double, jwa::kBayesC>(c, A, first); else annot_launch_step<float, jwa::kBayesC>(c, A, first); break;
+        case jwa::kBayesR: annot_launch_step<int32_t, jwa::kBayesR>(c, A, first); break;
+        default:           if (IS_F64(c)) annot_launch_step<double, jwa::kTree>(c, A, first); else annot_launch_step<float, jwa::kTree>(c, A, first); break;
+    }
+}
+
+extern "C" {
+
+int jwas_hip_annot_begin(jwas_hip_ctx* c, int32_t kind, int64_t p, int32_t ncols, const double* D_rowmajor, const double* coef,
+                         const double* variance, const double* start_prior)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no chain state: load genotypes and call jwas_hip_init_state first");
+    NEED(c, !c->an.active, JWAS_HIP_ESTATE, "an annotation session is already open (jwas_hip_annot_end first)");
+    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "annotation priors are not driven from marker or row shards");
+    NEED(c, !is_mega(c->method), JWAS_HIP_EUNSUP, "annotation priors are not available with constraint = true (megaBayesABC)");
+    NEED(c, kind >= jwa::kBayesC && kind <= jwa::kTree, JWAS_HIP_EINVAL, "unknown annotation kind %d", kind);
+    const bool fits = kind == jwa::kBayesC ? (c->method == JWAS_HIP_BAYESC && c->ntraits == 1)
+                    : kind == jwa::kBayesR ? (c->method == JWAS_HIP_BAYESR && c->ntraits == 1)
+                                           : ((c->method == JWAS_HIP_MTBAYESC1 || c->method == JWAS_HIP_MTBAYESC2) && c->ntraits == 2);
+    NEED(c, fits, JWAS_HIP_EINVAL, "annotation kind %d does not match the context's method %d with %d trait(s)", kind, c->method, c->ntraits);
+    NEED(c, p == c->p, JWAS_HIP_EINVAL, "p (%lld) differs from the number of markers (%lld)", (long long)p, (long long)c->p);
+    NEED(c, p >= 1 && p < ((int64_t)1 << 31) - jwa::kPiece, JWAS_HIP_EINVAL, "p must be 1 .. 2^31 - 1025 (got %lld)", (long long)p);
+    NEED(c, ncols >= 1 && ncols <= jwa::kMaxCols, JWAS_HIP_EINVAL, "ncols must be 1 .. %d (got %d)", jwa::kMaxCols, ncols);
+    NEED(c, D_rowmajor && coef && start_prior, JWAS_HIP_EINVAL, "NULL argument");
+    const int ns = jwa::annot_nsteps(kind), K = ncols;
+    const int64_t tab = annot_table_size(kind, p);
+    for (int i = 0; i < ns * K; ++i) NEED(c, std::isfinite(coef[i]), JWAS_HIP_EINVAL, "coefficient %d is not finite (%g)", i, coef[i]);
+    if (variance)
+        for (int s = 0; s < ns; ++s) NEED(c, std::isfinite(variance[s]) && variance[s] > 0.0, JWAS_HIP_EINVAL, "variance[%d] must be positive and finite (%g)", s, variance[s]);
+    for (int64_t i = 0; i < tab; ++i)
+        NEED(c, !std::isnan(start_prior[i]) && start_prior[i] != INFINITY, JWAS_HIP_EINVAL, "start_prior[%lld] is not a probability or its log (%g)", (long long)i, start_prior[i]);
+    std::vector<double> Dt((size_t)std::max(K - 1, 1) * (size_t)p);
+    for (int64_t i = 0; i < p; ++i) {
+        NEED(c, D_rowmajor[(size_t)i * K] == 1.0, JWAS_HIP_EINVAL, "marker %lld: column 0 of the design matrix must be the intercept's ones (%g)", (long long)i, D_rowmajor[(size_t)i * K]);
+        for (int k = 1; k < K; ++k) {
+            const double v = D_rowmajor[(size_t)i * K + k];
+            NEED(c, std::isfinite(v), JWAS_HIP_EINVAL, "marker %lld, column %d: the annotation is not finite (%g)", (long long)i, k, v);
+            Dt[(size_t)(k - 1) * p + i] = v;
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    auto& b = c->an;
+    b.kind = kind; b.nsteps = ns; b.K = K;
+    b.npieces = (int)((p + jwa::kPiece - 1) / jwa::kPiece);
+    const size_t pb = sizeof(double) * (size_t)p;
+    const size_t nscal = (size_t)jwa::kMaxSteps * K + 3 + 4 + 1 + K;
+#define ANNOT_ALLOC(ptr, bytes) do { if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { annot_free(c); return fail(c, JWAS_HIP_ENOMEM, "annotation session: device allocation of %zu bytes failed", (size_t)(bytes)); } } while (0)
+    ANNOT_ALLOC(b.D, pb * (size_t)std::max(K - 1, 1));
+    ANNOT_ALLOC(b.liab, pb * ns);
+    ANNOT_ALLOC(b.mu, pb * ns);
+    ANNOT_ALLOC(b.e, pb);
+    ANNOT_ALLOC(b.part, sizeof(double) * 3 * (size_t)b.npieces * (size_t)std::max(K - 1, 1));      // (set-up: the piece sums of every column's squares)
+    ANNOT_ALLOC(b.part4, sizeof(double) * 4 * (size_t)b.npieces);
+    ANNOT_ALLOC(b.scal, sizeof(double) * nscal);
+    ANNOT_ALLOC(b.mean, sizeof(double) * (size_t)tab);
+    ANNOT_ALLOC(b.mean2, sizeof(double) * (size_t)tab);
+    double** slot = annot_table_slot(c, kind);
+    if (!*slot) ANNOT_ALLOC(*slot, sizeof(double) * (size_t)tab);
+#undef ANNOT_ALLOC
+    HIPCHK(c, hipMemcpyAsync(b.D, Dt.data(), pb * (size_t)std::max(K - 1, 1), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.liab, 0, pb * ns, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.mu, 0, pb * ns, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.e, 0, pb, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.part, 0, sizeof(double) * 3 * (size_t)b.npieces * (size_t)std::max(K - 1, 1), c->stream));
+    HIPCHK(c, hipMemsetAsync(b.part4, 0, sizeof(double) * 4 * (size_t)b.npieces, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.scal, 0, sizeof(double) * nscal, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.mean, 0, sizeof(double) * (size_t)tab, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.mean2, 0, sizeof(double) * (size_t)tab, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.scal, coef, sizeof(double) * (size_t)ns * K, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(*slot, start_prior, sizeof(double) * (size_t)tab, hipMemcpyHostToDevice, c->stream));
+    if (K > 1) {                        // d_k over all markers, for the steps whose active set is all markers
+        double* dsq = b.scal + (size_t)jwa::kMaxSteps * K + 8;
+        hipLaunchKernelGGL(jwa::k_annot_colsq, dim3((unsigned)b.npieces, (unsigned)(K - 1)), dim3(256), 0, c->stream, b.D, p, (int32_t)b.npieces, b.part);
+        hipLaunchKernelGGL(jwa::k_annot_colsq_reduce, dim3((unsigned)(K - 1)), dim3(256), 0, c->stream, b.part, (int32_t)b.npieces, dsq);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (the caller's arrays and Dt may go away once this returns)
+    b.active = true;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_annot_step(jwas_hip_ctx* c, const jwas_annot_params* P, jwas_annot_stats* S)
+{
+    NEED_ANNOT(c);
+    NEED(c, P && S, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_annot_step: iteration must be >= 1");
+    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "annotation priors are not driven from marker or row shards");
+    auto& b = c->an;
+    const int K = b.K, ns = b.nsteps;
+    if (K > 1)
+        for (int s = 0; s < ns; ++s)
+            NEED(c, std::isfinite(P->variance[s]) && P->variance[s] > 0.0, JWAS_HIP_EINVAL, "variance[%d] must be positive and finite (%g)", s, P->variance[s]);
+    HIPCHK(c, hipSetDevice(c->device));
+    double* coef = b.scal;
+    double* nA = b.scal + (size_t)jwa::kMaxSteps * K;
+    double* means = nA + 3;
+    double* dc = means + 4;
+    double* dsq = dc + 1;
+    HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
+    for (int s = 0; s < ns; ++s) {
+        jwa::StepArgs A = {};
+        A.d1 = annot_delta(c, 0); A.d2 = b.kind == jwa::kTree ? annot_delta(c, 1) : nullptr;
+        A.D = b.D; A.coef = coef + (size_t)s * K; A.liab = b.liab + (size_t)s * c->p; A.e = b.e; A.part = b.part; A.dc = dc;
+        A.p = c->p; A.K = K; A.s = s; A.all_active = s == 0;
+        A.iter = P->iteration; A.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); A.seed_hi = (uint32_t)(P->seed >> 32);
+        jwa::DrawArgs W = {};
+        W.part = b.part; W.dsq = dsq; W.coef = coef + (size_t)s * K; W.nA = nA + s; W.dc = dc; W.var = K > 1 ? P->variance[s] : 1.0;
+        W.npieces = b.npieces; W.s = s; W.all_active = A.all_active; W.iter = A.iter; W.seed_lo = A.seed_lo; W.seed_hi = A.seed_hi;
+        for (int k = 0; k < K; ++k) {
+            A.k = k; W.k = k;
+            annot_launch_any(c, A, k == 0);
+            hipLaunchKernelGGL(jwa::k_annot_draw, dim3(1), dim3(256), 0, c->stream, W);
+        }
+    }
+    jwa::TableArgs T = {};
+    T.D = b.D; T.coef = coef; T.mu = b.mu; T.table = *annot_table_slot(c, b.kind); T.part = b.part4; T.p = c->p; T.K = K;
+    const dim3 grid((unsigned)b.npieces), blk(256);
+    if (b.kind == jwa::kBayesC)      hipLaunchKernelGGL((jwa::k_annot_table<jwa::kBayesC>), grid, blk, 0, c->stream, T);
+    else if (b.kind == jwa::kBayesR) hipLaunchKernelGGL((jwa::k_annot_table<jwa::kBayesR>), grid, blk, 0, c->stream, T);
+    else                             hipLaunchKernelGGL((jwa::k_annot_table<jwa::kTree>), grid, blk, 0, c->stream, T);
+    hipLaunchKernelGGL(jwa::k_annot_colmeans, dim3(1), dim3(256), 0, c->stream, b.part4, (int32_t)b.npieces, b.kind == jwa::kBayesC ? 1 : 4, (double)c->p, means);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_stop, c->stream));
+    std::vector<double> host((size_t)jwa::kMaxSteps * K + 7);
+    HIPCHK(c, hipMemcpyAsync(host.data(), b.scal, sizeof(double) * host.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memset(S, 0, sizeof *S);
+    for (int i = 0; i < ns * K; ++i) S->coef[i] = host[(size_t)i];
+    for (int s = 0; s < ns; ++s) S->n_active[s] = (int64_t)host[(size_t)jwa::kMaxSteps * K + s];
+    for (int q = 0; q < 4; ++q) S->means[q] = host[(size_t)jwa::kMaxSteps * K + 3 + q];
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+    S->step_ms = (double)ms;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_annot_accumulate(jwas_hip_ctx* c, double nsamples)
+{
+    NEED_ANNOT(c);
+    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
+    auto& b = c->an;
+    const int64_t q = annot_table_size(b.kind, c->p);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(jwa::k_annot_accumulate, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, c->stream, (const double*)*annot_table_slot(c, b.kind),
+                       b.mean, b.mean2, q, nsamples, (int32_t)(b.kind == jwa::kTree));
+    HIPCHK(c, hipGetLastError());
+    return JWAS_HIP_OK;
+}
+
+static int annot_download(jwas_hip_ctx* c, const double* dev, int64_t have, int64_t nvalues, double* out)
+{
+    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, nvalues == have, JWAS_HIP_EINVAL, "nvalues (%lld) differs from the session's (%lld)", (long long)nvalues, (long long)have);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, dev, sizeof(double) * (size_t)have, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_annot_get_prior(jwas_hip_ctx* c, int64_t nvalues, double* out)
+{
+    NEED_ANNOT(c);
+    return annot_download(c, *annot_table_slot(c, c->an.kind), annot_table_size(c->an.kind, c->p), nvalues, out);
+}
+
+int jwas_hip_annot_get_means(jwas_hip_ctx* c, int64_t nvalues, double* out_mean, double* out_mean2)
+{
+    NEED_ANNOT(c);
+    if (int rc = annot_download(c, c->an.mean, annot_table_size(c->an.kind, c->p), nvalues, out_mean)) return rc;
+    return out_mean2 ? annot_download(c, c->an.mean2, annot_table_size(c->an.kind, c->p), nvalues, out_mean2) : JWAS_HIP_OK;
+}
+
+int jwas_hip_annot_get_liability(jwas_hip_ctx* c, int64_t nvalues, double* out)
+{
+    NEED_ANNOT(c);
+    return annot_download(c, c->an.liab, (int64_t)c->an.nsteps * c->p, nvalues, out);
+}
+
+int jwas_hip_annot_get_mu(jwas_hip_ctx* c, int64_t nvalues, double* out)
+{
+    NEED_ANNOT(c);
+    return annot_download(c, c->an.mu, (int64_t)c->an.nsteps * c->p, nvalues, out);
+}
+
+int64_t jwas_hip_annot_estimate_bytes(int64_t p, int32_t ncols, int32_t kind)
+{
+    // D, the liabilities and mu of every step, e, the table and its two running means, the piece sums, the scalars
+    const int64_t ns = jwa::annot_nsteps(kind), K = std::max<int64_t>(ncols, 1), tab = annot_table_size(kind, p);
+    const int64_t npieces = (p + jwa::kPiece - 1) / jwa::kPiece;
+    return 8 * (std::max<int64_t>(K - 1, 1) * p + 2 * ns * p + p + 3 * tab + 3 * npieces * std::max<int64_t>(K - 1, 1) + 4 * npieces + 4 * K + 8);
+}
+
+int jwas_hip_annot_end(jwas_hip_ctx* c)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    annot_free(c);
     return JWAS_HIP_OK;
 }
 

@@ -18,6 +18,10 @@
 //   slot 4: the normal of an imputed missing residual (mtmiss.hpp), Box-Muller as slot 1, indexed by (RECORD, iteration,
 //           0x10000000, 4 + 16*trait).  The tag 0x10000000 is no other stream's repetition word (small counts, 0x20000000 | term,
 //           0x40000000 | round, 0x80000000 | ...), and no other stream uses slot 4: neither the tag nor the slot is shared.
+//   slot 5: the uniform of an annotation liability (annot.hpp), as slot 0, indexed by (MARKER, iteration, 0x08000000 | probit step, 5).
+//   slot 6: the normal of an annotation coefficient (annot.hpp), Box-Muller as slot 1, indexed by (COEFFICIENT, iteration,
+//           0x08000000 | probit step, 6).  The tag 0x08000000 is no other stream's repetition word (small counts, 0x10000000,
+//           0x20000000 | term, 0x40000000 | round, 0x80000000 | ...) and no other stream uses slots 5 and 6.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -715,6 +715,79 @@ class HipEngine:
     def mtmiss_end(self):
         self._chk(self._L.jwas_hip_mtmiss_end(self._h))
 
+    # -- marker-annotation priors (jwas_hip_annot_*; MCMC/annotation_updates.jl, csrc/annot.hpp) ----------------
+    ANNOT_KINDS = {"BayesC": _lib.ANNOT_BAYESC, "BayesR": _lib.ANNOT_BAYESR, "tree": _lib.ANNOT_TREE}
+
+    @staticmethod
+    def annot_estimate_bytes(p, ncols, kind):
+        return _lib.load().jwas_hip_annot_estimate_bytes(int(p), int(ncols), HipEngine.ANNOT_KINDS[kind])
+
+    def annot_begin(self, kind, design_matrix, coefficients, variance, start_prior):
+        """Open an annotation session.  kind: "BayesC" (1 step), "BayesR" or "tree" (3 steps; the 2-trait model).  design_matrix:
+        p x ncols with the intercept's ones in column 0; coefficients: ncols, or ncols x 3 (the layout of MarkerAnnotations);
+        variance: scalar or 3; start_prior: the table the first sweep reads (p, p x 4, or the p x 4 logs of the tree)."""
+        code = self.ANNOT_KINDS[kind]
+        ns = 1 if code == _lib.ANNOT_BAYESC else 3
+        Dm = np.ascontiguousarray(design_matrix, dtype=np.float64)
+        if Dm.ndim != 2:
+            raise ValueError("design_matrix must be p x ncols")
+        cf = np.asarray(coefficients, dtype=np.float64)
+        cf = np.ascontiguousarray(cf.reshape(Dm.shape[1], ns).T)      # -> [nsteps][ncols]
+        vr = np.ascontiguousarray(np.broadcast_to(np.asarray(variance, dtype=np.float64), (ns,)))
+        sp = np.ascontiguousarray(start_prior, dtype=np.float64)
+        if sp.size != Dm.shape[0] * (1 if ns == 1 else 4):
+            raise ValueError("start_prior must hold one row of the prior table per marker")
+        self._chk(self._L.jwas_hip_annot_begin(self._h, code, Dm.shape[0], Dm.shape[1], _ptr(Dm), _ptr(cf), _ptr(vr), _ptr(sp)))
+        self._annot = (code, ns, Dm.shape[1])
+
+    def annot_step(self, *, iteration, seed, variance):
+        """One probit update from the resident delta; the prior table is left where the next sweep(resident_priors=True) reads it.
+        Returns {"coefficients": ncols (BayesC) or ncols x 3, "n_active": per step, "means": column means of the table (BayesC: one
+        value), "step_ms"}."""
+        code, ns, K = self._annot
+        P, S = _lib.AnnotParams(), _lib.AnnotStats()
+        P.iteration, P.seed = int(iteration), int(seed)
+        for s, v in enumerate(np.broadcast_to(np.asarray(variance, dtype=np.float64), (ns,))):
+            P.variance[s] = float(v)
+        self._chk(self._L.jwas_hip_annot_step(self._h, C.byref(P), C.byref(S)))
+        cf = np.array(S.coef[:ns * K]).reshape(ns, K)
+        return {"coefficients": cf[0].copy() if ns == 1 else np.ascontiguousarray(cf.T), "n_active": np.array(S.n_active[:ns]),
+                "means": np.array(S.means[:1 if ns == 1 else 4]), "step_ms": S.step_ms}
+
+    def annot_accumulate(self, nsamples):
+        self._chk(self._L.jwas_hip_annot_accumulate(self._h, float(nsamples)))
+
+    def _annot_table_shape(self):
+        return (self.p,) if self._annot[1] == 1 else (self.p, 4)
+
+    def annot_prior(self):
+        """The resident prior table as the sweep reads it: p (BayesC), p x 4 (BayesR), the p x 4 logs (tree)."""
+        out = np.empty(self._annot_table_shape(), dtype=np.float64)
+        self._chk(self._L.jwas_hip_annot_get_prior(self._h, out.size, _ptr(out)))
+        return out
+
+    def annot_means(self):
+        """(mean, mean of squares) of the per-marker prior probabilities over the accumulated samples."""
+        m, m2 = np.empty(self._annot_table_shape(), dtype=np.float64), np.empty(self._annot_table_shape(), dtype=np.float64)
+        self._chk(self._L.jwas_hip_annot_get_means(self._h, m.size, _ptr(m), _ptr(m2)))
+        return m, m2
+
+    def _annot_steps(self, fn):
+        out = np.empty((self._annot[1], self.p), dtype=np.float64)
+        self._chk(fn(self._h, out.size, _ptr(out)))
+        return out[0].copy() if self._annot[1] == 1 else np.ascontiguousarray(out.T)
+
+    def annot_liability(self):
+        """The liabilities: p (BayesC) or p x 3."""
+        return self._annot_steps(self._L.jwas_hip_annot_get_liability)
+
+    def annot_mu(self):
+        return self._annot_steps(self._L.jwas_hip_annot_get_mu)
+
+    def annot_end(self):
+        self._chk(self._L.jwas_hip_annot_end(self._h))
+        self._annot = None
+
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""
         out = np.empty(getattr(self, "n_out", 0), dtype=self.dtype)
@@ -764,12 +837,18 @@ class HipEngine:
 
     def sweep(self, *, iteration, seed, vare, var_effect, pi=0.0, pi_classes=None, gamma=BAYESR_GAMMA,
               log_prior_states=None, var_effect_vec=None, var_effect_matrix=None, pi_vec=None, pi_matrix=None, nreps=1,
-              marker_offset=0, independent_blocks=False, section_solve=False, group_launch=False, _sharded=False):
+              marker_offset=0, independent_blocks=False, section_solve=False, group_launch=False, resident_priors=False,
+              _sharded=False):
         """One marker sweep.  Argument meaning follows BayesABC!/BayesR!/MTBayesABC!:
         vare: residual variance (scalar or t x t); var_effect: marker effect variance (BayesC scalar,
         BayesR sigmaSq, MT t x t); pi: Pr(effect = 0) scalar, or pi_vec per marker (length p, else the
-        reference's length error); pi_classes / pi_matrix: BayesR class priors (4 or p x 4)."""
+        reference's length error); pi_classes / pi_matrix: BayesR class priors (4 or p x 4).  resident_priors: the per-marker
+        prior table is the one an open annotation session keeps on the device (annot_begin / annot_step): no prior pointer
+        and no pi_classes are passed."""
         t = self.ntraits
+        if resident_priors:
+            if pi_vec is not None or pi_matrix is not None or np.ndim(pi) == 1 or np.ndim(pi_classes) == 2 or np.ndim(log_prior_states) == 2:
+                raise ValueError("resident_priors=True takes no per-marker prior: the annotation session holds it")
         P = SweepParams()
         P.method, P.ntraits, P.nreps = self.method, t, int(nreps)
         P.iteration, P.seed, P.marker_offset = int(iteration), int(seed), int(marker_offset)
@@ -836,7 +915,7 @@ class HipEngine:
                     raise ValueError("BayesR per-marker pi must have 4 columns.")
                 P.pi_matrix = pm.ctypes.data_as(C.POINTER(C.c_double))
                 keep.append(pm)
-            else:
+            elif not resident_priors:
                 pc = np.asarray(pc, dtype=np.float64)
                 if pc.shape != (4,):
                     raise ValueError(f"BayesR pi vector length {pc.size} must match the number of mixture classes (4).")
@@ -849,7 +928,7 @@ class HipEngine:
                 raise ValueError(f"megaBayesABC needs one pi per trait ({t}), got {pt.size}")
             for k in range(t):
                 P.pi_classes[k] = float(pt[k])
-        else:
+        elif not resident_priors:
             lp = np.asarray(log_prior_states, dtype=np.float64)
             if lp.ndim == 2:                      # marker-specific joint priors (MarkerSpecificPiPrior, MTBayesABC.jl:22-47)
                 if lp.shape != (self.p, 1 << t):

@@ -16,6 +16,7 @@ Per iteration (the reference's order, MCMC_BayesianAlphabet.jl:184-421):
 The host consumes only O(n) + O(p)-reducible quantities from the device.
 """
 import os
+import sys
 import time
 
 import numpy as np
@@ -74,6 +75,7 @@ LOCPAR_METHODS = ("locpar_begin", "locpar_add_covariate", "locpar_add_factor", "
                   "locpar_get_means", "locpar_end")
 LOCPAR_PED_METHODS = ("locpar_set_group_structure",)      # ... and what a pedigree random effect needs on top
 MTMISS_METHODS = ("mtmiss_begin", "mtmiss_impute", "mtmiss_set_record_weights", "mtmiss_end")      # ... and partially missing multi-trait records
+ANNOT_METHODS = ("annot_begin", "annot_step", "annot_accumulate", "annot_prior", "annot_means", "annot_end")
 LOCPAR_AUTO_LEVELS = 2048               # location_parameters="auto": more levels than this run on the device
 
 
@@ -378,7 +380,8 @@ def host_location_step(engine, Xf0, lhs, sol, w64, rng, vare, ftype):
 def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed, starting_value,
               fast_blocks, independent_blocks=False, heterogeneous_residuals=False, outputEBV, output_heritability=True, output_folder, printout_frequency, memory_guard, memory_guard_ratio,
               missing_phenotypes, device, block_size, gram_mode, engine, printout_model_info,
-              output_samples_for_all_parameters, double_precision=False, blocks_per_launch=None, location_parameters="auto"):
+              output_samples_for_all_parameters, double_precision=False, blocks_per_launch=None, location_parameters="auto",
+              annotation_priors="host"):
     import pandas as pd
     Mi = model.M[0]
     t = model.nModels
@@ -919,6 +922,19 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             if missing_:
                 raise NotImplementedError("a pedigree random effect needs an engine with " + ", ".join(missing_) + "; the package has no CPU fallback")
 
+    # ---- annotation priors: the probit update on the host (annotations.py, numpy's generator) or on the device from the
+    # resident delta (csrc/annot.hpp, the counter RNG)
+    ann_device = annotation_priors == "device" and ann is not False
+    if ann_device:
+        eng_ = engine if engine is not None else (Mi.device_backend if devres else None)
+        missing_ = [m_ for m_ in ANNOT_METHODS if eng_ is not None and not hasattr(eng_, m_)]
+        if missing_:
+            raise NotImplementedError("annotation priors on the device need an engine with the annotation step (" + ", ".join(missing_)
+                                      + " missing); the package has no CPU fallback")
+        if eng_ is not None and hasattr(eng_, "comm_info") and eng_.comm_info()[1] > 1:
+            raise NotImplementedError("annotation priors on the device are not driven from marker shards")
+        ann_kind = "tree" if t > 1 else method
+
     # ---- engine (the only engine shipped is the HIP one; there is no CPU fallback)
     own_engine = engine is None
     if own_engine:
@@ -946,6 +962,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                     need += HipEngine.locpar_structure_estimate_bytes(re_.Vinv.shape[0], re_.Vinv.nnz)
         if mt_device:                                              # the records' codes, the tables, the second piece sums
             need += HipEngine.mtmiss_estimate_bytes(n)
+        if ann_device:                                             # the design matrix, liabilities, the table's means (jwas_hip_annot_estimate_bytes)
+            need += HipEngine.annot_estimate_bytes(p, ann.design_matrix.shape[1], ann_kind)
         if outputEBV and not out_same:                             # Mi.output_genotypes: a second dense matrix (n_out x p)
             need += (8 if double_precision else 4) * ((len(out_rows) + 255) // 256 * 256) * p
         engine = HipEngine(device, precision=64 if double_precision else 32)
@@ -1067,6 +1085,12 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             engine.sub_xalpha(k)
     if has_liab:
         engine.liability_init(seed=seed_int, R=R0_)                       # :82-88
+    ann_open = False
+    if ann_device:                                                      # the session starts from annotations.py's start values
+        with np.errstate(divide="ignore"):
+            start_ = np.log(ann.snp_pi) if t > 1 else (ann.snp_pi if method == "BayesR" else np.asarray(pi, dtype=np.float64))
+        engine.annot_begin(ann_kind, ann.design_matrix, ann.coefficients, ann.variance, start_)
+        ann_open = True
 
     vare = ftype(R.val) if t == 1 else np.asarray(R.val, dtype=ftype)
     Gval = ftype(Mi.G.val) if t == 1 else np.asarray(Mi.G.val, dtype=ftype)
@@ -1245,6 +1269,10 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 kw.update(var_effect=Gval, pi=pi_t)
                 if mt_pervar:
                     kw["var_effect_matrix"] = Gmat
+            elif ann_device:                                                # the prior table of the annotation session, resident on the device
+                kw.update(var_effect=Gval, resident_priors=True)
+                if method == "BayesR" and fast_blocks is not False:         # bayesr_block_nreps (BayesR.jl:22-25)
+                    kw["nreps"] = 1 if it <= burnin else nreps
             elif t > 1:
                 with np.errstate(divide="ignore"):
                     kw.update(var_effect=Gval, log_prior_states=np.log(ann.snp_pi if ann is not False else np.asarray(pi, dtype=np.float64)))
@@ -1278,6 +1306,18 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             if Mi.estimatePi:
                 if mega:                                                    # MCMC_BayesianAlphabet.jl:300-301
                     pi_t = np.array([rng.beta(p - st["sum_delta"][k] + 1.0, st["sum_delta"][k] + 1.0) for k in range(t)])
+                elif ann_device:                                            # the same update on the device (csrc/annot.hpp)
+                    res_ = engine.annot_step(iteration=it, seed=seed_int, variance=ann.variance)
+                    ann.coefficients[...] = res_["coefficients"]
+                    if ann.design_matrix.shape[1] > 1:                      # the shrinkage variances stay on the chain's rng (annotation_updates.jl:125-137)
+                        if ann.nsteps == 1:
+                            ann.variance = A_.sample_effect_variance(ann.coefficients, rng)
+                        else:
+                            for s_ in range(ann.nsteps):
+                                if res_["n_active"][s_] > 0:
+                                    ann.variance[s_] = A_.sample_effect_variance(ann.coefficients[:, s_], rng)
+                    if ann.nsteps > 1:
+                        pi = res_["means"]
                 elif t > 1 and ann is not False:                            # annotation_updates.jl:353-361
                     pi = A_.update_bayesc_mt_tree_priors(ann, engine.get_state(0)[2], engine.get_state(1)[2], rng)
                 elif t > 1:
@@ -1380,7 +1420,10 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 run_vare.add(vare, k)
                 if run_varg is not None:
                     run_varg.add(Gval, k)
-                if run_pi is not None:
+                pi_marker_dev = ann_device and ann.nsteps == 1                # annotated BayesC on the device: the p values stay there
+                if pi_marker_dev:
+                    engine.annot_accumulate(k)
+                elif run_pi is not None:
                     run_pi.add(np.atleast_1d(pi_t if mega else pi), k)
                 engine.accumulate(k)
                 if run_scale is not None:
@@ -1396,7 +1439,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 if not pervar:
                     files[f"marker_effects_variances_{name}"].write(",".join(repr(float(v)) for v in np.atleast_1d(Gval).ravel()) + "\n")
                 if Mi.estimatePi and f"pi_{name}" in files:
-                    files[f"pi_{name}"].write(",".join(repr(float(v)) for v in np.atleast_1d(pi_t if mega else pi)) + "\n")
+                    files[f"pi_{name}"].write(",".join(repr(float(v)) for v in (engine.annot_prior() if pi_marker_dev else np.atleast_1d(pi_t if mega else pi))) + "\n")
                 for kk, tr in enumerate(model.lhsVec):
                     if hasattr(engine, "alpha_sparse"):
                         si, sv = engine.alpha_sparse(kk)              # (idx, val) compacted on the device
@@ -1441,6 +1484,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             fh.close()
         for w_ in bin_writers:
             w_.close()
+        if ann_open and sys.exc_info()[0] is not None:                  # an exception inside the chain: the session goes with the files
+            engine.annot_end()
 
 
     # ---- results (output.jl:108-212)
@@ -1474,6 +1519,10 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     if run_varg is not None:
         out[f"marker effects variance {name}"] = pd.DataFrame({"Covariance": cov, "Estimate": np.atleast_1d(run_varg.mean).ravel(),
                                                                "SD": np.atleast_1d(run_varg.sd()).ravel()})
+    if ann_open:
+        if ann.nsteps == 1:
+            run_pi.mean, run_pi.mean2 = engine.annot_means()
+        engine.annot_end()
     if run_pi is not None:
         if mega:
             lab = list(model.lhsVec)
