@@ -40,6 +40,8 @@
  *   jwas_hip_annot_*           update_marker_annotation_priors!: the probit update of the annotation coefficients and the
  *                              per-marker prior table of annotated BayesC / BayesR / 2-trait BayesC
  *                              (MCMC/annotation_updates.jl:21-137,181-361)
+ *   jwas_hip_sem_*             the structural coefficients of runMCMC(...; causal_structure): SEM_setup / get_Λ and the indirect and
+ *                              overall marker effects (structure_equation_model/SEM.jl:53-165,245-252)
  *
  * Conventions: every entry point returns 0 on success and a negative JWAS_HIP_E* code on failure
  * (no exceptions cross the boundary; jwas_hip_last_error() returns the message -- the analogue of
@@ -567,6 +569,62 @@ int  jwas_hip_annot_get_mu(jwas_hip_ctx* ctx, int64_t nvalues, double* out);
 /* Device bytes of a session (pure; an upper bound). */
 int64_t jwas_hip_annot_estimate_bytes(int64_t p, int32_t ncols, int32_t kind);
 int  jwas_hip_annot_end(jwas_hip_ctx* ctx);
+
+/* ---- structural equation models: the recursive causal structure among the traits (csrc/sem.hpp) ------------------------------------
+ * runMCMC(...; causal_structure = cs) samples the structural coefficients after the residual-variance draw of every iteration
+ * (MCMC/MCMC_BayesianAlphabet.jl:165-169,372-377,410-412; structure_equation_model/SEM.jl:53-165; Wang et al. 2020, G3).  t traits
+ * (2 <= t <= JWAS_HIP_MAX_TRAITS), n records, y (t x n) the constant phenotypes, cs the t x t strictly lower 0/1 structure
+ * (cs[i][j] = 1: trait j acts on trait i), P_i the parents of trait i ascending.  The resident residual is the reference's
+ * "Lambda ycorr", r_i = y_i - sum_{j in P_i} lambda_ij y_j - fitted_i; lambda starts at 0.  A session keeps y, S = y y' and the
+ * coefficients on the device.  One step, for every trait i with parents, all arithmetic double without contraction:
+ *     C_ji  = y_j'r_i                  j in P_i
+ *     rhs_q = (C_{P_q,i} + sum_m S_{P_q,P_m} lambda_old_m) / R_ii       (m ascending, the sum starts from C)
+ *     F_qm  = S_{P_q,P_m} / R_ii + (q == m)                              (prior lambda ~ N(0, 1), SEM.jl:134-138; only diag(R), SEM.jl:129)
+ *     F = L L',  mu = inv(F) rhs,  lambda_new = mu + inv(L') z
+ *     r_i,n = T(((double(r_i,n) + d_1 y_j1,n) + d_2 y_j2,n) + ...)       d = lambda_old - lambda_new, parents ascending
+ * z_q, the normal of the q-th parent of trait i: Box-Muller as the location parameters' (u1 from words (1, 0), u2 from (3, 2)) on
+ * philox4x32_10(q, iteration, 0x04000000 | i, 7).  The coefficient estimated from the design column (i, j) is lambda_ij: the
+ * reference maps its draw back in column order, which differs from the row order of its design from t = 4 on.
+ * Order of the sums: pieces of 1024 records, G = min(ceil(n / 1024), 512) workgroups of 256 threads (workgroup b: pieces b, b + G, ...),
+ * a thread adds its records in ascending order, a wave meets in a shuffle tree, the four waves in wave order, the G partials in
+ * ascending order in one workgroup -- a function of n alone, no floating-point atomics, identical bits from run to run.
+ * jwas_hip_sem_accumulate: indirect_k = sum_j K[k][j] alpha_j (j ascending from 0), overall_k = alpha_k + indirect_k per marker,
+ * K = sum_{m=1}^{t-1} Lambda^m from the caller (compute_indirect_effect, SEM.jl:245-252); running mean, mean of squares and frequency
+ * of non-zero of both in double, mean += (v - mean) / nsamples.
+ * Every t x t matrix of this section is row-major with stride t; only the strictly lower part is used.
+ * Errors are decided before any launch: JWAS_HIP_ESTATE for _begin before jwas_hip_init_state or without a residual, for every
+ * other entry point without a session, and after jwas_hip_init_state changed the number of traits; JWAS_HIP_EINVAL for one trait
+ * (or ntraits that differs from the context's), a wrong n, a structure that is not 0/1 and strictly lower, non-finite y, lambda or
+ * K, a lambda outside the structure, R_diag that is not positive and finite, iteration == 0, nsamples < 1, a kind or trait outside
+ * its range; JWAS_HIP_EUNSUP with a communicator attached.  _begin on an open session replaces it.  The session is freed by _end,
+ * jwas_hip_destroy or loading genotypes. */
+typedef struct jwas_sem_params {
+    uint32_t iteration;                 /* MCMC iteration >= 1 (enters the RNG counter)                                          */
+    uint32_t reserved;
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                     */
+    double   R_diag[JWAS_HIP_MAX_TRAITS];   /* the diagonal of the residual covariance                                           */
+} jwas_sem_params;
+typedef struct jwas_sem_stats {
+    double lambda[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];   /* the coefficients AFTER the step                               */
+    double mean[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];     /* mu: the mean of their full conditional                        */
+    double ypr[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];      /* C_ji = y_j'r_i at [i][j], from the residual BEFORE the step   */
+    double step_ms;                     /* device time of the step (HIP events on the context's stream)                          */
+} jwas_sem_stats;
+/* Open a session: y_t_n the phenotypes (row-major t x n), structure_t_t the causal structure. */
+int  jwas_hip_sem_begin(jwas_hip_ctx* ctx, int32_t ntraits, int64_t n, const double* y_t_n, const int32_t* structure_t_t);
+/* One update of every coefficient and of the residual.  Synchronous. */
+int  jwas_hip_sem_step(jwas_hip_ctx* ctx, const jwas_sem_params* params, jwas_sem_stats* stats);
+int  jwas_hip_sem_get_lambda(jwas_hip_ctx* ctx, double* out_t_t);
+/* The state only: the residual is not touched. */
+int  jwas_hip_sem_set_lambda(jwas_hip_ctx* ctx, const double* lambda_t_t);
+/* S = y y' as the step reads it. */
+int  jwas_hip_sem_get_gram(jwas_hip_ctx* ctx, double* out_t_t);
+int  jwas_hip_sem_accumulate(jwas_hip_ctx* ctx, const double* K_t_t, double nsamples);
+/* kind 0: indirect, 1: overall; p values each, any of the three may be NULL. */
+int  jwas_hip_sem_get_effects(jwas_hip_ctx* ctx, int32_t kind, int32_t trait, double* mean, double* mean2, double* freq);
+/* Device bytes of a session (pure; an upper bound). */
+int64_t jwas_hip_sem_estimate_bytes(int64_t n, int64_t p, int32_t ntraits);
+int  jwas_hip_sem_end(jwas_hip_ctx* ctx);
 
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the

@@ -401,6 +401,63 @@ hip_annot_estimate_bytes(p::Integer, ncols::Integer, kind::Integer) =
     ccall((:jwas_hip_annot_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int32, Int32), p, ncols, kind)
 hip_annot_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_annot_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
 
+"Structural equation models on the device (structure_equation_model/SEM.jl:53-165,245-252; csrc/sem.hpp).  `hip_sem_begin!` takes the
+phenotypes (n x t, as wArray's columns) and the causal structure; `hip_sem_step!` replaces get_Λ on the resident residual (the
+reference's Λycorr) and returns the coefficient matrix Λ (t x t, λ_ij at [i, j]); `hip_sem_accumulate!` takes K = Σ_m Λ^m
+(compute_indirect_effect) and keeps the running means of the indirect and overall marker effects."
+struct HipSemParams
+    iteration::UInt32
+    reserved::UInt32
+    seed::UInt64
+    R_diag::NTuple{4,Float64}
+end
+struct HipSemStats
+    lambda::NTuple{16,Float64}
+    mean::NTuple{16,Float64}
+    ypr::NTuple{16,Float64}
+    step_ms::Float64
+end
+# the library's matrices are row-major t x t: a Julia matrix goes over as its transpose
+_hip_sem_matrix(v, t::Integer) = permutedims(reshape(collect(v[1:t*t]), t, t))
+function hip_sem_begin!(b::HipBackend, Y::Matrix{Float64}, causal_structure::AbstractMatrix)
+    t = size(Y, 2)
+    cs = vec(permutedims(Matrix{Int32}(causal_structure)))
+    hip_check(b.ctx, ccall((:jwas_hip_sem_begin, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Int32}),
+                           b.ctx, t, size(Y, 1), Y, cs))           # column-major n x t == the library's row-major t x n
+    t
+end
+function hip_sem_step!(b::HipBackend, t::Integer, iter::Integer, seed::Integer, R::AbstractMatrix)
+    S = Ref{HipSemStats}()
+    rd = ntuple(i -> i <= t ? Float64(R[i, i]) : 1.0, 4)
+    hip_check(b.ctx, ccall((:jwas_hip_sem_step, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipSemParams}, Ref{HipSemStats}),
+                           b.ctx, HipSemParams(UInt32(iter), UInt32(0), UInt64(seed), rd), S))
+    _hip_sem_matrix(S[].lambda, t), S[]
+end
+function hip_sem_lambda(b::HipBackend, t::Integer)
+    out = Vector{Float64}(undef, t * t)
+    hip_check(b.ctx, ccall((:jwas_hip_sem_get_lambda, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.ctx, out))
+    _hip_sem_matrix(out, t)
+end
+hip_sem_set_lambda!(b::HipBackend, Λ::Matrix{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_sem_set_lambda, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.ctx, vec(permutedims(Λ))))
+function hip_sem_gram(b::HipBackend, t::Integer)
+    out = Vector{Float64}(undef, t * t)
+    hip_check(b.ctx, ccall((:jwas_hip_sem_get_gram, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.ctx, out))
+    _hip_sem_matrix(out, t)
+end
+hip_sem_accumulate!(b::HipBackend, K::Matrix{Float64}, nsamples::Real) =
+    hip_check(b.ctx, ccall((:jwas_hip_sem_accumulate, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64), b.ctx, vec(permutedims(K)), nsamples))
+"(mean, mean of squares, frequency of non-zero) per marker of trait `trait` (1-based); kind 0 = indirect, 1 = overall."
+function hip_sem_effects(b::HipBackend, kind::Integer, trait::Integer, p::Integer)
+    m, m2, f = Vector{Float64}(undef, p), Vector{Float64}(undef, p), Vector{Float64}(undef, p)
+    hip_check(b.ctx, ccall((:jwas_hip_sem_get_effects, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                           b.ctx, kind, trait - 1, m, m2, f))
+    m, m2, f
+end
+hip_sem_estimate_bytes(n::Integer, p::Integer, ntraits::Integer) =
+    ccall((:jwas_hip_sem_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int32), n, p, ntraits)
+hip_sem_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_sem_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

@@ -52,6 +52,8 @@ SYMBOLS = [
     "jwas_hip_mtmiss_end",
     "jwas_hip_annot_begin", "jwas_hip_annot_step", "jwas_hip_annot_accumulate", "jwas_hip_annot_get_prior", "jwas_hip_annot_get_means",
     "jwas_hip_annot_get_liability", "jwas_hip_annot_get_mu", "jwas_hip_annot_estimate_bytes", "jwas_hip_annot_end",
+    "jwas_hip_sem_begin", "jwas_hip_sem_step", "jwas_hip_sem_get_lambda", "jwas_hip_sem_set_lambda", "jwas_hip_sem_get_gram",
+    "jwas_hip_sem_accumulate", "jwas_hip_sem_get_effects", "jwas_hip_sem_estimate_bytes", "jwas_hip_sem_end",
 ]
 ANNOT_MAX_COLS = 64                     # columns of the annotation design matrix, the intercept included (JWAS_HIP_ANNOT_MAX_COLS)
 ANNOT_BAYESC, ANNOT_BAYESR, ANNOT_TREE = 0, 1, 2
@@ -128,6 +130,15 @@ class AnnotParams(C.Structure):
 
 class AnnotStats(C.Structure):
     _fields_ = [("coef", C.c_double * (3 * ANNOT_MAX_COLS)), ("n_active", C.c_int64 * 3), ("means", C.c_double * 4), ("step_ms", C.c_double)]
+
+
+class SemParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("R_diag", C.c_double * MAX_TRAITS)]
+
+
+class SemStats(C.Structure):
+    _fields_ = [("lambda_", C.c_double * (MAX_TRAITS * MAX_TRAITS)), ("mean", C.c_double * (MAX_TRAITS * MAX_TRAITS)),
+                ("ypr", C.c_double * (MAX_TRAITS * MAX_TRAITS)), ("step_ms", C.c_double)]
 
 
 class JwasHipError(RuntimeError):
@@ -264,6 +275,16 @@ def load():
     L.jwas_hip_annot_estimate_bytes.argtypes = [i64, i32, i32]
     L.jwas_hip_annot_estimate_bytes.restype = i64
     L.jwas_hip_annot_end.argtypes = [vp]
+    L.jwas_hip_sem_begin.argtypes = [vp, i32, i64, vp, vp]
+    L.jwas_hip_sem_step.argtypes = [vp, C.POINTER(SemParams), C.POINTER(SemStats)]
+    L.jwas_hip_sem_get_lambda.argtypes = [vp, vp]
+    L.jwas_hip_sem_set_lambda.argtypes = [vp, vp]
+    L.jwas_hip_sem_get_gram.argtypes = [vp, vp]
+    L.jwas_hip_sem_accumulate.argtypes = [vp, vp, C.c_double]
+    L.jwas_hip_sem_get_effects.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.jwas_hip_sem_estimate_bytes.argtypes = [i64, i64, i32]
+    L.jwas_hip_sem_estimate_bytes.restype = i64
+    L.jwas_hip_sem_end.argtypes = [vp]
     L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
     L.jwas_hip_accumulate.argtypes = [vp, C.c_double]
@@ -289,7 +310,7 @@ def load():
         fn = getattr(L, name)
         if name not in ("jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_estimate_bytes", "jwas_hip_estimate_bytes_storage", "jwas_hip_gwas_estimate_bytes",
                         "jwas_hip_locpar_estimate_bytes", "jwas_hip_lp_structure_estimate_bytes", "jwas_hip_mtmiss_estimate_bytes",
-                        "jwas_hip_annot_estimate_bytes"):
+                        "jwas_hip_annot_estimate_bytes", "jwas_hip_sem_estimate_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -522,6 +522,16 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     generator.  The choice is therefore part of what a seed means, as with location_parameters.  Not with storage=:stream,
     constraint=true or marker shards (explicit errors).
 
+    causal_structure (JWAS.jl:144-147,328-337; structure_equation_model/SEM.jl): a t x t strictly lower 0/1 matrix, entry [i, j] = 1
+    when trait j acts on trait i -- the recursive structural equation model of Wang et al. 2020.  The structural coefficients are
+    sampled on the device after the residual-variance draw of every iteration (csrc/sem.hpp); the residual the chain runs on is
+    the reference's "Lambda ycorr".  missing_phenotypes = false and R.constraint = true are forced as in the reference.  Outputs:
+    structure_coefficient_MCMC_samples.txt (vec(Lambda) column-major per saved sample, no header; in the output folder, where the
+    reference writes to the working directory), MCMC_samples_indirect_marker_effects_* / MCMC_samples_overall_marker_effects_*,
+    direct_ / indirect_ / overall_marker_effects_<genotypes>.txt, and the tables "indirect marker effects <genotypes>", "overall
+    marker effects <genotypes>", "structure coefficients".  Every sampler, storage mode and precision; not with categorical or
+    censored traits, heterogeneous_residuals, marker shards or marker starting values (explicit errors).
+
     Categorical / censored traits (build_model(...; categorical_trait, censored_trait)): categories coded 1, 2, 3 ... (two of them
     make a binary trait), bounds of a censored trait in the columns <trait>_l / <trait>_u; the liabilities are sampled on the
     device before the location parameters of every iteration (mcmc.py step 0) and saved, with the thresholds, as
@@ -535,8 +545,7 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     Float64: constraint=true, storage=:stream, shards (explicit errors).  The sample files keep their Float32 / 9-digit format."""
     if independent_blocks and fast_blocks is False:
         raise ValueError("independent_blocks=true requires fast_blocks != false.")             # :242-244
-    for flag, name in ((single_step_analysis, "single_step_analysis"),
-                       (causal_structure, "causal_structure"), (RRM, "RRM"),
+    for flag, name in ((single_step_analysis, "single_step_analysis"), (RRM, "RRM"),
                        (update_priors_frequency, "update_priors_frequency"),
                        (prediction_equation, "prediction_equation")):
         if not _is_false(flag) and flag != 0:
@@ -549,6 +558,25 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
         raise ValueError('annotation_priors must be "host" or "device".')
     if memory_guard not in ("error", "warn", "off"):
         raise ValueError("memory_guard must be :error, :warn or :off.")
+    if _is_false(causal_structure):
+        causal_structure = False
+    else:                                                                                     # JWAS.jl:328-337
+        causal_structure = np.asarray(causal_structure, dtype=np.float64)
+        tt = model.nModels
+        if tt == 1:
+            raise ValueError("Causal strutures are only allowed in multi-trait analysis")      # input_data_validation.jl:131-133
+        if causal_structure.ndim != 2 or causal_structure.shape != (tt, tt):
+            raise ValueError(f"causal_structure must be a {tt} x {tt} matrix (one row and column per trait).")
+        if not np.all((causal_structure == 0.0) | (causal_structure == 1.0)):
+            raise ValueError("causal_structure must hold 0 and 1 only.")
+        if np.any(np.triu(causal_structure, 1) != 0.0):
+            raise ValueError("The causal structue needs to be a lower triangular matrix.")     # :334-336
+        if np.any(np.diag(causal_structure) != 0.0):
+            raise ValueError("causal_structure must have a zero diagonal (a trait does not act on itself).")
+        if tt > 4:
+            raise NotImplementedError("causal_structure runs with at most 4 traits on the device")
+        missing_phenotypes = False          # no missing phenotypes and a diagonal residual covariance, for identifiability (:331-333)
+        model.R.constraint = True
     if output_samples_frequency is None:
         output_samples_frequency = chain_length // 1000 if chain_length > 1000 else 1          # :168
     if int(output_samples_frequency) <= 0:
@@ -574,5 +602,5 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
                      output_folder=output_folder, printout_frequency=printout_frequency,
                      memory_guard=memory_guard, memory_guard_ratio=memory_guard_ratio,
                      missing_phenotypes=missing_phenotypes, device=device, block_size=block_size,
-                     gram_mode=gram_mode, blocks_per_launch=blocks_per_launch, location_parameters=location_parameters, annotation_priors=annotation_priors, engine=_engine, printout_model_info=printout_model_info,
+                     gram_mode=gram_mode, blocks_per_launch=blocks_per_launch, location_parameters=location_parameters, annotation_priors=annotation_priors, causal_structure=causal_structure, engine=_engine, printout_model_info=printout_model_info,
                      output_samples_for_all_parameters=output_samples_for_all_parameters)

@@ -8,6 +8,7 @@
 #include "locpar.hpp"
 #include "mtmiss.hpp"
 #include "annot.hpp"
+#include "sem.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -242,6 +243,17 @@ struct jwas_hip_ctx {
         double* scal = nullptr;                             // coef [3][K] | n_A [3] | column means [4] | c_k - c_k' [1] | dsq [K]
         double *mean = nullptr, *mean2 = nullptr;           // [table size] running means of the prior probabilities
     } an;
+    // Structural equation model (jwas_hip_sem_begin .. _end; structure_equation_model/SEM.jl; csrc/sem.hpp)
+    struct Sem {
+        bool active = false;
+        int nt = 0, G = 0;
+        uint32_t mask = 0, ymask = 0, rmask = 0;            // bit cell(i, j): cs[i][j]; bit k: trait k is a parent / has parents
+        double* y = nullptr;                                // [nt][n] the phenotypes
+        double* part = nullptr;                             // [G][kGramCells] workgroup partials (the step uses kMaxPairs of every row)
+        double* S = nullptr;                                // [16] y y'
+        double* rec = nullptr;                              // [kRecSize] lambda | d | mu | C
+        double* acc = nullptr;                              // [2][3][nt][p] indirect | overall: mean, mean of squares, frequency
+    } sm;
 };
 
 static constexpr int kStatGrid = 128;
@@ -412,8 +424,16 @@ static void annot_free(jwas_hip_ctx* c)
     b = jwas_hip_ctx::Annot();
 }
 
+static void sem_free(jwas_hip_ctx* c)
+{
+    auto& b = c->sm;
+    for (void* q : {(void*)b.y, (void*)b.part, (void*)b.S, (void*)b.rec, (void*)b.acc}) (void)hipFree(q);
+    b = jwas_hip_ctx::Sem();
+}
+
 static void free_storage(jwas_hip_ctx* c)
 {
+    sem_free(c);                        // (the phenotypes belong to the records, the accumulators to the markers of this matrix)
     annot_free(c);                      // (the prior table below belongs to the markers of this matrix)
     mtmiss_free(c);                     // (the codes describe the records of this matrix)
     gwas_free(c);                       // (a session is bound to the matrix it was begun on)
@@ -4537,6 +4557,205 @@ int jwas_hip_annot_end(jwas_hip_ctx* c)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     annot_free(c);
+    return JWAS_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- structural equation models (csrc/sem.hpp): structure_equation_model/SEM.jl:53-165,245-252 ----------------------------------
+#define NEED_SEM(c)                                                                                                    \
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
+    NEED(c, c->sm.active, JWAS_HIP_ESTATE, "jwas_hip_sem_begin has not been called");                                  \
+    NEED(c, liab_residual(c) && c->method >= 0 && c->ntraits == c->sm.nt, JWAS_HIP_ESTATE,                              \
+         "jwas_hip_init_state changed the number of traits after jwas_hip_sem_begin");                                 \
+    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "structural equation models are not driven from marker or row shards")
+
+// the 4 x 4 device layout <-> the caller's t x t
+static void sem_pack(const double* dev16, int t, double* out) { for (int i = 0; i < t; ++i) for (int j = 0; j < t; ++j) out[i * t + j] = dev16[i * jws::kMaxT + j]; }
+
+extern "C" {
+
+int jwas_hip_sem_begin(jwas_hip_ctx* c, int32_t ntraits, int64_t n, const double* y, const int32_t* cs)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no residual: load genotypes and call jwas_hip_init_state first");
+    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "structural equation models are not driven from marker or row shards");
+    NEED(c, ntraits >= 2, JWAS_HIP_EINVAL, "Causal strutures are only allowed in multi-trait analysis (got %d trait)", ntraits);
+    NEED(c, ntraits <= jws::kMaxT && ntraits == c->ntraits, JWAS_HIP_EINVAL, "ntraits (%d) differs from the context's (%d)", ntraits, c->ntraits);
+    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
+    NEED(c, y && cs, JWAS_HIP_EINVAL, "NULL argument");
+    const int t = ntraits;
+    uint32_t mask = 0, ymask = 0, rmask = 0;
+    for (int i = 0; i < t; ++i)
+        for (int j = 0; j < t; ++j) {
+            const int v = cs[i * t + j];
+            NEED(c, v == 0 || v == 1, JWAS_HIP_EINVAL, "causal structure [%d][%d] = %d is not 0 or 1", i, j, v);
+            NEED(c, v == 0 || i > j, JWAS_HIP_EINVAL, "The causal structue needs to be a lower triangular matrix. ([%d][%d] is set)", i, j);
+            if (v) { mask |= 1u << jws::cell(i, j); ymask |= 1u << j; rmask |= 1u << i; }
+        }
+    for (int64_t i = 0; i < (int64_t)t * n; ++i)
+        NEED(c, std::isfinite(y[i]), JWAS_HIP_EINVAL, "phenotype %lld of trait %lld is not finite (%g)", (long long)(i % n), (long long)(i / n), y[i]);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    sem_free(c);
+    auto& b = c->sm;
+    b.nt = t; b.G = jws::sem_grid(n); b.mask = mask; b.ymask = ymask; b.rmask = rmask;
+    const size_t accb = sizeof(double) * 6 * (size_t)t * (size_t)c->p;
+#define SEM_ALLOC(ptr, bytes) do { if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { sem_free(c); return fail(c, JWAS_HIP_ENOMEM, "SEM session: device allocation of %zu bytes failed", (size_t)(bytes)); } } while (0)
+    SEM_ALLOC(b.y, sizeof(double) * (size_t)t * (size_t)n);
+    SEM_ALLOC(b.part, sizeof(double) * (size_t)b.G * jws::kGramCells);
+    SEM_ALLOC(b.S, sizeof(double) * 16);
+    SEM_ALLOC(b.rec, sizeof(double) * jws::kRecSize);
+    SEM_ALLOC(b.acc, accb);
+#undef SEM_ALLOC
+    HIPCHK(c, hipMemcpyAsync(b.y, y, sizeof(double) * (size_t)t * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.rec, 0, sizeof(double) * jws::kRecSize, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.acc, 0, accb, c->stream));
+    hipLaunchKernelGGL(jws::k_sem_gram, dim3((unsigned)b.G), dim3(256), 0, c->stream, (const double*)b.y, n, (int32_t)t, b.part);
+    hipLaunchKernelGGL(jws::k_sem_gram_sum, dim3(1), dim3(64), 0, c->stream, (const double*)b.part, (int32_t)b.G, b.S);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (the caller's arrays may go away once this returns)
+    b.active = true;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_sem_step(jwas_hip_ctx* c, const jwas_sem_params* P, jwas_sem_stats* S)
+{
+    NEED_SEM(c);
+    NEED(c, P && S, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_sem_step: iteration must be >= 1");
+    auto& b = c->sm;
+    const int t = b.nt;
+    for (int i = 0; i < t; ++i)
+        NEED(c, std::isfinite(P->R_diag[i]) && P->R_diag[i] > 0.0, JWAS_HIP_EINVAL, "R_diag[%d] must be positive and finite (%g)", i, P->R_diag[i]);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
+    jws::DotArgs D = {};
+    D.r = liab_residual(c); D.y = b.y; D.part = b.part; D.n = c->n; D.ld = c->ld; D.mask = b.mask; D.ymask = b.ymask; D.rmask = b.rmask; D.nt = t;
+    jws::DrawArgs W = {};
+    W.part = b.part; W.S = b.S; W.rec = b.rec; W.G = b.G; W.nt = t; W.mask = b.mask;
+    for (int i = 0; i < t; ++i) W.Rdiag[i] = P->R_diag[i];
+    W.iter = P->iteration; W.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); W.seed_hi = (uint32_t)(P->seed >> 32);
+    jws::ApplyArgs A = {};
+    A.r = liab_residual(c); A.y = b.y; A.d = b.rec + jws::kRecD; A.n = c->n; A.ld = c->ld; A.mask = b.mask; A.ymask = b.ymask; A.rmask = b.rmask; A.nt = t;
+    if (b.mask) {                                               // (a structure without an edge: nothing to sample)
+        const dim3 grid((unsigned)b.G), rows((unsigned)((c->n + 255) / 256));
+        if (IS_F64(c)) hipLaunchKernelGGL((jws::k_sem_dots<double>), grid, dim3(256), 0, c->stream, D);
+        else           hipLaunchKernelGGL((jws::k_sem_dots<float>), grid, dim3(256), 0, c->stream, D);
+        hipLaunchKernelGGL(jws::k_sem_draw, dim3(1), dim3(64), 0, c->stream, W);
+        if (IS_F64(c)) hipLaunchKernelGGL((jws::k_sem_apply<double>), rows, dim3(256), 0, c->stream, A);
+        else           hipLaunchKernelGGL((jws::k_sem_apply<float>), rows, dim3(256), 0, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(c->ev_stop, c->stream));
+    double host[jws::kRecSize];
+    HIPCHK(c, hipMemcpyAsync(host, b.rec, sizeof host, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memset(S, 0, sizeof *S);
+    sem_pack(host + jws::kRecLambda, t, S->lambda);
+    sem_pack(host + jws::kRecMu, t, S->mean);
+    sem_pack(host + jws::kRecC, t, S->ypr);
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+    S->step_ms = (double)ms;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_sem_get_lambda(jwas_hip_ctx* c, double* out)
+{
+    NEED_SEM(c);
+    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    double host[16];
+    HIPCHK(c, hipMemcpyAsync(host, c->sm.rec + jws::kRecLambda, sizeof host, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    sem_pack(host, c->sm.nt, out);
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_sem_set_lambda(jwas_hip_ctx* c, const double* in)
+{
+    NEED_SEM(c);
+    NEED(c, in, JWAS_HIP_EINVAL, "NULL argument");
+    const int t = c->sm.nt;
+    double host[16] = {0.0};
+    for (int i = 0; i < t; ++i)
+        for (int j = 0; j < t; ++j) {
+            const double v = in[i * t + j];
+            NEED(c, std::isfinite(v), JWAS_HIP_EINVAL, "lambda[%d][%d] is not finite (%g)", i, j, v);
+            const bool edge = i > j && ((c->sm.mask >> jws::cell(i, j)) & 1u);
+            NEED(c, edge || v == 0.0, JWAS_HIP_EINVAL, "lambda[%d][%d] = %g lies outside the causal structure", i, j, v);
+            host[i * jws::kMaxT + j] = v;
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(c->sm.rec + jws::kRecLambda, host, sizeof host, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_sem_get_gram(jwas_hip_ctx* c, double* out)
+{
+    NEED_SEM(c);
+    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    double host[16];
+    HIPCHK(c, hipMemcpyAsync(host, c->sm.S, sizeof host, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    sem_pack(host, c->sm.nt, out);
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_sem_accumulate(jwas_hip_ctx* c, const double* K, double nsamples)
+{
+    NEED_SEM(c);
+    NEED(c, K, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
+    const int t = c->sm.nt;
+    jws::AccArgs A = {};
+    for (int i = 0; i < t; ++i)
+        for (int j = 0; j < t; ++j) {
+            NEED(c, std::isfinite(K[i * t + j]), JWAS_HIP_EINVAL, "K[%d][%d] is not finite (%g)", i, j, K[i * t + j]);
+            A.K[i * jws::kMaxT + j] = K[i * t + j];
+        }
+    A.alpha = IS_F64(c) ? (const void*)c->f64->alpha : (const void*)c->alpha;
+    A.acc = c->sm.acc; A.nsamples = nsamples; A.p = c->p; A.nt = t;
+    HIPCHK(c, hipSetDevice(c->device));
+    const dim3 grid((unsigned)((c->p + 255) / 256));
+    if (IS_F64(c)) hipLaunchKernelGGL((jws::k_sem_accumulate<double>), grid, dim3(256), 0, c->stream, A);
+    else           hipLaunchKernelGGL((jws::k_sem_accumulate<float>), grid, dim3(256), 0, c->stream, A);
+    HIPCHK(c, hipGetLastError());
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_sem_get_effects(jwas_hip_ctx* c, int32_t kind, int32_t trait, double* mean, double* mean2, double* freq)
+{
+    NEED_SEM(c);
+    NEED(c, kind == 0 || kind == 1, JWAS_HIP_EINVAL, "kind must be 0 (indirect) or 1 (overall), got %d", kind);
+    NEED(c, trait >= 0 && trait < c->sm.nt, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->sm.nt);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t stat = (size_t)c->sm.nt * c->p, nb = sizeof(double) * (size_t)c->p;
+    const double* base = c->sm.acc + (size_t)kind * 3 * stat + (size_t)trait * c->p;
+    if (mean) HIPCHK(c, hipMemcpyAsync(mean, base, nb, hipMemcpyDeviceToHost, c->stream));
+    if (mean2) HIPCHK(c, hipMemcpyAsync(mean2, base + stat, nb, hipMemcpyDeviceToHost, c->stream));
+    if (freq) HIPCHK(c, hipMemcpyAsync(freq, base + 2 * stat, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int64_t jwas_hip_sem_estimate_bytes(int64_t n, int64_t p, int32_t ntraits)
+{
+    // the phenotypes, the six accumulators per marker and trait, the workgroup partials, S and the record
+    const int64_t t = std::max<int64_t>(ntraits, 1);
+    return 8 * (t * n + 6 * t * p + (int64_t)jws::kMaxGrid * jws::kGramCells + 16 + jws::kRecSize);
+}
+
+int jwas_hip_sem_end(jwas_hip_ctx* c)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, c->sm.active, JWAS_HIP_ESTATE, "jwas_hip_sem_begin has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    sem_free(c);
     return JWAS_HIP_OK;
 }
 

@@ -22,6 +22,10 @@
 //   slot 6: the normal of an annotation coefficient (annot.hpp), Box-Muller as slot 1, indexed by (COEFFICIENT, iteration,
 //           0x08000000 | probit step, 6).  The tag 0x08000000 is no other stream's repetition word (small counts, 0x10000000,
 //           0x20000000 | term, 0x40000000 | round, 0x80000000 | ...) and no other stream uses slots 5 and 6.
+//   slot 7: the normal of a structural coefficient (sem.hpp), Box-Muller as slot 3, indexed by (ORDINAL OF THE PARENT among the
+//           parents of its trait, iteration, 0x04000000 | trait, 7).  The tag 0x04000000 is no other stream's repetition word
+//           (small counts, 0x08000000 | step, 0x10000000, 0x20000000 | term, 0x40000000 | round, 0x80000000 | ...) and no other
+//           stream uses slot 7.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -788,6 +788,76 @@ class HipEngine:
         self._chk(self._L.jwas_hip_annot_end(self._h))
         self._annot = None
 
+    # -- structural equation models (jwas_hip_sem_*; structure_equation_model/SEM.jl, csrc/sem.hpp) ----------------
+    @staticmethod
+    def sem_estimate_bytes(n, p, ntraits):
+        return _lib.load().jwas_hip_sem_estimate_bytes(int(n), int(p), int(ntraits))
+
+    def sem_begin(self, y, structure):
+        """Open a session.  y: the t x n phenotypes (constant); structure: the t x t strictly lower 0/1 causal structure
+        (structure[i, j] = 1: trait j acts on trait i).  After init_state and set_residual; the coefficients start at 0."""
+        yv = np.ascontiguousarray(y, dtype=np.float64)
+        cs = np.asarray(structure)
+        if yv.ndim != 2 or cs.shape != (yv.shape[0], yv.shape[0]):
+            raise ValueError("y must be t x n and structure t x t")
+        if not np.all(np.isfinite(cs) & (cs == np.round(cs))):
+            raise ValueError("structure must hold 0 / 1")
+        cv = np.ascontiguousarray(cs, dtype=np.int32)
+        self._chk(self._L.jwas_hip_sem_begin(self._h, yv.shape[0], yv.shape[1], _ptr(yv), _ptr(cv)))
+        self._sem_t = yv.shape[0]
+
+    def sem_step(self, *, iteration, seed, R_diag):
+        """One draw of every structural coefficient from the resident residual, which is updated in place.  Returns {"lambda",
+        "mean" (of the full conditional), "ypr" ([i, j] = y_j'r_i before the step): t x t, "step_ms"}."""
+        t = self._sem_t
+        P, S = _lib.SemParams(), _lib.SemStats()
+        P.iteration, P.seed = int(iteration), int(seed)
+        rd = np.asarray(R_diag, dtype=np.float64).reshape(-1)
+        if rd.size != t:
+            raise ValueError(f"R_diag must hold one value per trait ({t})")
+        for k in range(t):
+            P.R_diag[k] = float(rd[k])
+        self._chk(self._L.jwas_hip_sem_step(self._h, C.byref(P), C.byref(S)))
+        return {"lambda": np.array(S.lambda_[:t * t]).reshape(t, t), "mean": np.array(S.mean[:t * t]).reshape(t, t),
+                "ypr": np.array(S.ypr[:t * t]).reshape(t, t), "step_ms": S.step_ms}
+
+    def _sem_matrix(self, fn):
+        out = np.empty((self._sem_t, self._sem_t), dtype=np.float64)
+        self._chk(fn(self._h, _ptr(out)))
+        return out
+
+    def sem_get_lambda(self):
+        return self._sem_matrix(self._L.jwas_hip_sem_get_lambda)
+
+    def sem_set_lambda(self, lam):
+        """The state only: the residual is not touched."""
+        lv = np.ascontiguousarray(lam, dtype=np.float64)
+        if lv.shape != (self._sem_t, self._sem_t):
+            raise ValueError("lambda must be t x t")
+        self._chk(self._L.jwas_hip_sem_set_lambda(self._h, _ptr(lv)))
+
+    def sem_get_gram(self):
+        """S = y y' as the step reads it."""
+        return self._sem_matrix(self._L.jwas_hip_sem_get_gram)
+
+    def sem_accumulate(self, K, nsamples):
+        """Running means of the indirect (K alpha) and overall (alpha + K alpha) marker effects; K = sum_m Lambda^m, t x t."""
+        Kv = np.ascontiguousarray(K, dtype=np.float64)
+        if Kv.shape != (self._sem_t, self._sem_t):
+            raise ValueError("K must be t x t")
+        self._chk(self._L.jwas_hip_sem_accumulate(self._h, _ptr(Kv), float(nsamples)))
+
+    def sem_get_effects(self, kind, trait):
+        """(mean, mean of squares, frequency of non-zero) per marker; kind: "indirect" or "overall"."""
+        code = {"indirect": 0, "overall": 1}[kind]
+        out = [np.empty(self.p, dtype=np.float64) for _ in range(3)]
+        self._chk(self._L.jwas_hip_sem_get_effects(self._h, code, int(trait), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
+        return tuple(out)
+
+    def sem_end(self):
+        self._chk(self._L.jwas_hip_sem_end(self._h))
+        self._sem_t = None
+
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""
         out = np.empty(getattr(self, "n_out", 0), dtype=self.dtype)

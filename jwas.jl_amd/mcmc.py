@@ -12,6 +12,7 @@ Per iteration (the reference's order, MCMC_BayesianAlphabet.jl:184-421):
   3. pi  ~ Beta / Dirichlet from the sweep's counts                                          (:294-317, host)
   4. marker effect variance from alpha'alpha / ssq / beta'beta                               (:321-326, host)
   5. residual variance from r'r                                                              (:363-370, host)
+  5b. causal_structure: the structural coefficients among the traits, engine.sem_step(...)   (:372-377, DEVICE)
   6. every output_samples_frequency after burn-in: running means (device for markers)       (:399-413)
 The host consumes only O(n) + O(p)-reducible quantities from the device.
 """
@@ -75,6 +76,7 @@ LOCPAR_METHODS = ("locpar_begin", "locpar_add_covariate", "locpar_add_factor", "
                   "locpar_get_means", "locpar_end")
 LOCPAR_PED_METHODS = ("locpar_set_group_structure",)      # ... and what a pedigree random effect needs on top
 MTMISS_METHODS = ("mtmiss_begin", "mtmiss_impute", "mtmiss_set_record_weights", "mtmiss_end")      # ... and partially missing multi-trait records
+SEM_METHODS = ("sem_begin", "sem_step", "sem_accumulate", "sem_get_effects", "sem_end")      # ... and a causal structure among the traits
 ANNOT_METHODS = ("annot_begin", "annot_step", "annot_accumulate", "annot_prior", "annot_means", "annot_end")
 LOCPAR_AUTO_LEVELS = 2048               # location_parameters="auto": more levels than this run on the device
 
@@ -303,6 +305,33 @@ def _inverse_wishart_batch(rng, df, scale):
     return (G + G.transpose(0, 2, 1)) / 2
 
 
+def indirect_matrix(lam):
+    """K = sum_{m=1}^{t-1} Lambda^m (compute_indirect_effect, SEM.jl:245-252): row k holds what every trait's direct marker effects
+    contribute to trait k through the causal paths."""
+    lam = np.asarray(lam, dtype=np.float64)
+    K, P = np.zeros_like(lam), np.eye(lam.shape[0])
+    for _ in range(lam.shape[0] - 1):
+        P = P @ lam
+        K = K + P
+    return K
+
+
+def indirect_overall_rows(K, direct):
+    """One saved sample's indirect and overall marker effects from the sparse direct ones: direct = [(idx, val)] per trait.
+    Returns (the union of the indices ascending, indirect [t][nnz], overall [t][nnz]) in double, with the device's order of
+    operations: indirect_k = sum_j K[k, j] alpha_j (j ascending from 0), overall_k = alpha_k + indirect_k."""
+    t = len(direct)
+    u = np.unique(np.concatenate([np.asarray(si, dtype=np.int64) for si, _ in direct])) if t else np.zeros(0, dtype=np.int64)
+    A = np.zeros((t, u.size))
+    for k, (si, sv) in enumerate(direct):
+        A[k, np.searchsorted(u, si)] = np.asarray(sv, dtype=np.float64)
+    ind = np.zeros((t, u.size))
+    for k in range(t):
+        for j in range(t):
+            ind[k] = ind[k] + K[k, j] * A[j]
+    return u.astype(np.int32), ind, A + ind
+
+
 LIABILITY_TYPES = ("categorical", "categorical(binary)", "censored")
 LIABILITY_METHODS = ("liability_begin", "set_categorical", "set_censored", "set_thresholds", "liability_init", "liability_sample",
                      "liability_minmax", "liabilities", "liability_end")
@@ -381,10 +410,11 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
               fast_blocks, independent_blocks=False, heterogeneous_residuals=False, outputEBV, output_heritability=True, output_folder, printout_frequency, memory_guard, memory_guard_ratio,
               missing_phenotypes, device, block_size, gram_mode, engine, printout_model_info,
               output_samples_for_all_parameters, double_precision=False, blocks_per_launch=None, location_parameters="auto",
-              annotation_priors="host"):
+              annotation_priors="host", causal_structure=False):
     import pandas as pd
     Mi = model.M[0]
     t = model.nModels
+    sem = causal_structure is not False                                 # the recursive structural equation model (SEM.jl)
     method = Mi.method
     # runMCMC(double_precision=true) (JWAS.jl:349-366): genotypes, G, alpha -> Float64; everything the chain holds follows.
     # ftype is the element type of the run (the reference's Float32 default, or Float64).
@@ -424,6 +454,20 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                   "included in the pedigree. These are removed from the analysis.")
     traits_type = model.traits_type = list(getattr(model, "traits_type", None) or ["continuous"] * t)
     has_liab = any(tt in LIABILITY_TYPES for tt in traits_type)
+    if sem:
+        if has_liab:
+            raise NotImplementedError("causal_structure with categorical / censored traits stays on the reference")
+        if heterogeneous_residuals:
+            raise NotImplementedError("causal_structure with heterogeneous_residuals stays on the reference")
+        if Mi.alpha is not False:
+            raise NotImplementedError("causal_structure with marker starting values stays on the reference")
+        eng_ = engine if engine is not None else (Mi.device_backend if getattr(Mi, "storage_mode", "dense") == "device" else None)
+        missing_ = [m_ for m_ in SEM_METHODS if eng_ is not None and not hasattr(eng_, m_)]
+        if missing_:
+            raise NotImplementedError("causal_structure needs an engine with the structural-coefficient step (" + ", ".join(missing_)
+                                      + " missing); the package has no CPU fallback")
+        if eng_ is not None and hasattr(eng_, "comm_info") and eng_.comm_info()[1] > 1:
+            raise NotImplementedError("causal_structure is not driven from marker shards")
     if has_liab:
         if heterogeneous_residuals:
             raise NotImplementedError("heterogeneous_residuals with categorical / censored traits stays on the reference")
@@ -540,6 +584,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     Y = np.stack([ph[tr].to_numpy(dtype=ftype) for tr in model.lhsVec])       # t x n
     observed = np.isfinite(Y).T                                                     # n x t: mme.missingPattern (residual.jl:17-21)
     has_missing = not observed.all()
+    if sem and has_missing:                                               # SEM.jl:51: no missing phenotypes in SEM
+        raise ValueError("causal_structure needs complete records: some training records miss the phenotype of a trait.")
     phenovar = np.array([np.var(Y[k][observed[:, k]].astype(np.float64), ddof=1) for k in range(t)])
     Y = np.where(np.isfinite(Y), Y, ftype(0)).astype(ftype)               # imputed before first use (residual.jl:52-73)
     invw = None
@@ -964,6 +1010,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             need += HipEngine.mtmiss_estimate_bytes(n)
         if ann_device:                                             # the design matrix, liabilities, the table's means (jwas_hip_annot_estimate_bytes)
             need += HipEngine.annot_estimate_bytes(p, ann.design_matrix.shape[1], ann_kind)
+        if sem:                                                    # the phenotypes, the indirect / overall accumulators (jwas_hip_sem_estimate_bytes)
+            need += HipEngine.sem_estimate_bytes(n, p, t)
         if outputEBV and not out_same:                             # Mi.output_genotypes: a second dense matrix (n_out x p)
             need += (8 if double_precision else 4) * ((len(out_rows) + 255) // 256 * 256) * p
         engine = HipEngine(device, precision=64 if double_precision else 32)
@@ -1091,6 +1139,17 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             start_ = np.log(ann.snp_pi) if t > 1 else (ann.snp_pi if method == "BayesR" else np.asarray(pi, dtype=np.float64))
         engine.annot_begin(ann_kind, ann.design_matrix, ann.coefficients, ann.variance, start_)
         ann_open = True
+    sem_open = False
+    if sem:
+        # SEM_setup (SEM.jl:53-62): the coefficients start at 0, so the residual just set IS the reference's "Lambda ycorr"
+        sem_cs = np.asarray(causal_structure, dtype=np.int32)
+        sem_edges = [(i, j) for i in range(t) for j in range(i) if sem_cs[i, j]]
+        engine.sem_begin(Y.astype(np.float64), sem_cs)
+        sem_open = True
+        sem_lam = np.zeros((t, t))
+        run_lam = _Running(sem_lam)
+        # (the reference writes this file to the working directory, SEM.jl:59-60; here it lives with the other samples)
+        sem_file = open(os.path.join(output_folder, "structure_coefficient_MCMC_samples.txt"), "w")
 
     vare = ftype(R.val) if t == 1 else np.asarray(R.val, dtype=ftype)
     Gval = ftype(Mi.G.val) if t == 1 else np.asarray(Mi.G.val, dtype=ftype)
@@ -1158,6 +1217,14 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     from .samples import MarkerSampleWriter
     bin_writers = [MarkerSampleWriter(os.path.join(output_folder, f"MCMC_samples_marker_effects_{name}_{tr}.bin"), Mi.markerID)
                    for tr in model.lhsVec]
+    sem_writers = {}
+    if sem:                                                             # SEM.jl:187-316 (the reference's files name the term "genotypes")
+        for kind_ in ("indirect", "overall"):
+            sem_writers[kind_] = [MarkerSampleWriter(os.path.join(output_folder, f"MCMC_samples_{kind_}_marker_effects_{name}_{tr}.bin"), Mi.markerID)
+                                  for tr in model.lhsVec]
+            if write_marker_samples:
+                for tr in model.lhsVec:
+                    _open(f"{kind_}_marker_effects_{name}_{tr}", Mi.markerID)
 
     rnd_keys, run_rnd = [], []
     for re_ in rnd:                                                     # output.jl:348-351,401-405; the polygenic effect: :326-327,416-420
@@ -1404,6 +1471,11 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 else:
                     vare = ftype((ftype(st["resid_ss"][0, 0]) + Rdf * R.scale) / rng.chisquare(n + Rdf))
 
+            # 5b. causal relationships among the phenotypes (MCMC_BayesianAlphabet.jl:372-377; get_Λ, SEM.jl:124-165): on the device
+            #     from the resident residual, which moves to the new coefficients in place; only diag(R) is read (SEM.jl:129)
+            if sem:
+                sem_lam = engine.sem_step(iteration=it, seed=seed_int, R_diag=np.diag(np.asarray(vare, dtype=np.float64)))["lambda"]
+
             # 6. save (MCMC_BayesianAlphabet.jl:399-413, output.jl:443-604)
             if it > burnin and (it - burnin) % output_samples_frequency == 0:
                 k = (it - burnin) / output_samples_frequency
@@ -1440,6 +1512,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                     files[f"marker_effects_variances_{name}"].write(",".join(repr(float(v)) for v in np.atleast_1d(Gval).ravel()) + "\n")
                 if Mi.estimatePi and f"pi_{name}" in files:
                     files[f"pi_{name}"].write(",".join(repr(float(v)) for v in (engine.annot_prior() if pi_marker_dev else np.atleast_1d(pi_t if mega else pi))) + "\n")
+                sem_direct = []
                 for kk, tr in enumerate(model.lhsVec):
                     if hasattr(engine, "alpha_sparse"):
                         si, sv = engine.alpha_sparse(kk)              # (idx, val) compacted on the device
@@ -1447,12 +1520,31 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                         a_ = engine.get_state(kk)[0]
                         si = np.flatnonzero(a_).astype(np.int32); sv = a_[si]
                     bin_writers[kk].append(si, sv)
+                    sem_direct.append((si, sv))
                     if write_marker_samples:
                         a = np.zeros(p, dtype=ftype)
                         a[si] = sv
                         fh = files[f"marker_effects_{name}_{tr}"]
                         a.tofile(fh, sep=",", format="%.9g")          # text at C speed; 9 significant digits round-trip Float32
                         fh.write("\n")
+                if sem:
+                    # compute_indirect_effect (SEM.jl:245-252): K = sum_m Lambda^m; the device keeps the running means of K alpha and
+                    # alpha + K alpha, the host forms this sample's rows from the sparse direct effects it has just read
+                    sem_K = indirect_matrix(sem_lam)
+                    engine.sem_accumulate(sem_K, k)
+                    run_lam.add(sem_lam, k)
+                    sem_file.write(",".join(repr(float(v)) for v in sem_lam.ravel(order="F")) + "\n")      # vec(Λ), MCMC_BayesianAlphabet.jl:410-412
+                    u_idx, ind_, ov_ = indirect_overall_rows(sem_K, sem_direct)
+                    for kind_, rows_ in (("indirect", ind_), ("overall", ov_)):
+                        for kk, tr in enumerate(model.lhsVec):
+                            nz_ = rows_[kk] != 0.0
+                            sem_writers[kind_][kk].append(u_idx[nz_], rows_[kk][nz_])
+                            if write_marker_samples:
+                                a = np.zeros(p, dtype=ftype)
+                                a[u_idx] = rows_[kk]
+                                fh = files[f"{kind_}_marker_effects_{name}_{tr}"]
+                                a.tofile(fh, sep=",", format="%.9g")
+                                fh.write("\n")
                 if outputEBV:
                     if X_out_host is not None:
                         ebvs = [(X_out_host @ engine.get_state(kk)[0].astype(np.float64)).astype(ftype) for kk in range(t)]
@@ -1482,8 +1574,12 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             _blas_limit.restore_original_limits()
         for fh in list(files.values()) + list(liab_files.values()):
             fh.close()
-        for w_ in bin_writers:
+        for w_ in bin_writers + [w2_ for ws_ in sem_writers.values() for w2_ in ws_]:
             w_.close()
+        if sem_open:
+            sem_file.close()
+            if sys.exc_info()[0] is not None:                           # an exception inside the chain: the session goes with the files
+                engine.sem_end()
         if ann_open and sys.exc_info()[0] is not None:                  # an exception inside the chain: the session goes with the files
             engine.annot_end()
 
@@ -1516,6 +1612,19 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         sd = np.sqrt(np.abs(ma2.astype(np.float64) - ma.astype(np.float64) ** 2))
         frames.append(pd.DataFrame({"Trait": tr, "Marker_ID": Mi.markerID, "Estimate": ma, "SD": sd, "Model_Frequency": md}))
     out[f"marker effects {name}"] = pd.concat(frames, ignore_index=True)
+    if sem_open:                                                         # generate_marker_effect (SEM.jl:318-368; JWAS.jl:496-507)
+        out[f"marker effects {name}"].to_csv(os.path.join(output_folder, f"direct_marker_effects_{name}.txt"), index=False)
+        for kind_ in ("indirect", "overall"):
+            frames = []
+            for k, tr in enumerate(model.lhsVec):
+                m_, m2_, fr_ = engine.sem_get_effects(kind_, k)
+                frames.append(pd.DataFrame({"Trait": tr, "Marker_ID": Mi.markerID, "Estimate": m_, "SD": np.sqrt(np.abs(m2_ - m_ ** 2)),
+                                            "Model_Frequency": fr_}))
+            out[f"{kind_} marker effects {name}"] = pd.concat(frames, ignore_index=True)
+        lam_sd = run_lam.sd()
+        out["structure coefficients"] = pd.DataFrame({"Trait": [model.lhsVec[i] for i, _ in sem_edges], "Parent": [model.lhsVec[j] for _, j in sem_edges],
+                                                      "Estimate": [run_lam.mean[i, j] for i, j in sem_edges], "SD": [lam_sd[i, j] for i, j in sem_edges]})
+        engine.sem_end()
     if run_varg is not None:
         out[f"marker effects variance {name}"] = pd.DataFrame({"Covariance": cov, "Estimate": np.atleast_1d(run_varg.mean).ravel(),
                                                                "SD": np.atleast_1d(run_varg.sd()).ravel()})
