@@ -161,9 +161,9 @@ def _table_bounds(kind, D, coef, Cb):
     return np.stack([b / v + 4 * U * np.abs(np.log(v)) for v, b in rows], axis=1)
 
 
-@pytest.mark.parametrize("kind", ["BayesC", "BayesR", "tree"])
-@pytest.mark.parametrize("precision", [32, 64])
-@pytest.mark.parametrize("p", [1003, 2085])
+# p = 263 229: 258 pieces of 1024 markers, so annot_ordered_sum's threads 0 and 1 take a second trip over the pieces
+@pytest.mark.parametrize("p,precision,kind", [(p, prec, kind) for kind in ("BayesC", "BayesR", "tree") for prec in (32, 64) for p in (1003, 2085)]
+                         + [(263_229, 64, kind) for kind in ("BayesC", "BayesR", "tree")])
 def test_step_parity_from_a_common_state(kind, precision, p):
     hip, ref = _engines(kind, precision, p)
     ns = 1 if kind == "BayesC" else 3

@@ -141,6 +141,13 @@ def test_f64_marker_covariance_draws_match_the_oracle(t):
         want = O.sample_marker_covariances(beta, t + 4.5, scale, 9, 7, marker0=100)
         assert got.dtype == np.float64
         np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-12)
+        # df = t + 0.5: the last row's chi-square has a = 0.75 < 1 and takes the boost branch exp(log u / a)
+        hip.sample_marker_covariances(t + 0.5, scale, seed=9, iteration=7, marker_offset=100)
+        got = hip.marker_covariances()
+        want = O.sample_marker_covariances(beta, t + 0.5, scale, 9, 7, marker0=100)
+        print(f"f64 marker covariances t{t} df={t + 0.5} (boost branch): equal after rounding to float {(got.astype(np.float32) == want).mean():.4f}, "
+              f"worst relative difference {np.max(np.abs(got - want) / np.abs(want)):.2e}")
+        np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-12)
     finally:
         hip.close()
 

@@ -250,12 +250,21 @@ def test_distribution_of_a_million_draws(name, a, b):
         hip.close()
 
 
-@pytest.mark.parametrize("precision", [32, 64])
-def test_minmax_equals_numpy(precision):
-    n = 1000 + 77                                               # not a multiple of 256
+@pytest.mark.parametrize("precision,n", [(32, 1077), (64, 1077), (32, 65_869), (64, 65_869)], ids=["32", "64", "32-65869", "64-65869"])
+def test_minmax_equals_numpy(precision, n):
+    """n = 1077: not a multiple of 256.  n = 65 869: 258 workgroups, so k_liability_minmax_reduce's threads 0 and 1 take a second
+    trip over the partials; category 4 has members only at records >= 65 536 (its extremes are in the partials 256 and 257 alone)
+    and the single-member category 3 lies there too."""
     rng = np.random.default_rng(8)
-    codes = rng.choice(np.array([0, 1, 2, 4], dtype=np.int32), size=n, p=[0.1, 0.3, 0.3, 0.3])
-    codes[513] = 3                                              # a category with a single member
+    if n <= 65_536:
+        codes = rng.choice(np.array([0, 1, 2, 4], dtype=np.int32), size=n, p=[0.1, 0.3, 0.3, 0.3])
+        single = 513
+    else:
+        codes = rng.choice(np.array([0, 1, 2], dtype=np.int32), size=n, p=[0.1, 0.45, 0.45])
+        codes[65_536:] = rng.choice(np.array([0, 1, 2, 4], dtype=np.int32), size=n - 65_536, p=[0.1, 0.3, 0.3, 0.3])
+        single = 65_700
+        assert (n + 255) // 256 == 258 and (codes[65_536:] == 4).sum() > 50
+    codes[single] = 3                                           # a category with a single member
     th = np.array([-np.inf, 0.0, 0.7, 1.3, np.inf])
     hip, _ = _engines(precision, n, 1)
     try:
@@ -274,8 +283,9 @@ def test_minmax_equals_numpy(precision):
             y = hip.liabilities(0)
             want = LR.category_minmax(y, codes, 5)
             assert np.array_equal(mx, want[0]) and np.array_equal(mn, want[1])
-            assert mx[3] == y[513] and mn[2] == y[513]
+            assert mx[3] == y[single] and mn[2] == y[single]
             assert mx[0] == -np.inf and mn[0] == -np.inf and mx[4] == np.inf and mn[4] == np.inf
+            assert np.isfinite(mx[1:4]).all() and np.isfinite(mn[1:4]).all() and mn[3] == y[codes == 4].min()
     finally:
         hip.close()
 

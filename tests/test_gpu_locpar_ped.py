@@ -203,6 +203,69 @@ def test_quadratic_forms():
         hip.close()
 
 
+def _synthetic_structure(q):
+    """A sparse symmetric positive definite q x q matrix that is no pedigree's: tridiagonal, plus three rows (and columns) of about 40,
+    300 and 700 entries -- each longer than the rows a single thread adds, the longest among the last 256 rows; strictly
+    diagonally dominant."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(q)
+    off = sp.diags([np.full(q - 1, -0.3)], [1], shape=(q, q), format="lil")
+    for row, cnt in ((100, 40), (30_000, 300), (q - 100, 700)):
+        cols = rng.choice(q, cnt, replace=False)
+        cols = cols[np.abs(cols - row) > 1]
+        lo, hi = cols[cols < row], cols[cols > row]
+        off[lo, row] = rng.uniform(-0.02, 0.02, len(lo))
+        off[row, hi] = rng.uniform(-0.02, 0.02, len(hi))
+    off = sp.triu(off.tocsr(), 1)
+    V = off + off.T
+    V = (V + sp.diags(1.0 + np.asarray(abs(V).sum(axis=1)).ravel())).tocsr()
+    V.sort_indices()
+    return V
+
+
+@pytest.mark.parametrize("t", [1, 3])
+def test_quadratic_forms_over_more_than_256_workgroups(t):
+    """test_quadratic_forms' bound at 65 836 levels: 258 workgroups of k_locpar_quad_rows, so k_locpar_quad_reduce's threads 0 and 1
+    take a second trip over the per-workgroup sums.  Against scipy.sparse in float64."""
+    import jwas_jl_amd as J
+    q, n = 65_836, 1003
+    V = _synthetic_structure(q)
+    nnz_l = np.diff(V.indptr)
+    assert (q + 255) // 256 == 258 and abs(V - V.T).max() == 0 and [c // 10 for c in sorted(nnz_l)[-3:]] == [4, 30, 70] and PR.LONG_ROW < 40
+    assert nnz_l[65_536:].max() == nnz_l.max()
+    rng = np.random.default_rng(5 + t)
+    hip = J.HipEngine(0, precision=64)
+    try:
+        hip.load_dense(_genotypes(n, 64)); hip.setup_blocks(64, "f64"); hip.init_state("BayesC" if t == 1 else "MTBayesC", t)
+        for k in range(t):
+            hip.set_residual(rng.standard_normal(n) * 1.3, k)
+        hip.locpar_begin(t)
+        hip.locpar_set_group_structure(0, V.indptr, V.indices, V.data)
+        lev = _records(q, n, rng)
+        for k in range(t):
+            hip.locpar_add_factor(k, lev, q, 0)
+        assert hip.locpar_size() == t * q
+        kw = dict(vare=1.7) if t == 1 else dict(Rinv=np.linalg.inv(_spd(t, rng, 0.8)))
+        if t > 1:
+            kw["Rinv"] = (kw["Rinv"] + kw["Rinv"].T) / 2
+        kw["Gi"] = [_spd(t, rng, 2.0)]
+        hip.locpar_set_sol(rng.standard_normal(t * q))
+        worst = 0.0
+        for it in (1, 2):
+            st = hip.locpar_step(iteration=it, seed=9, **kw)
+            Um = hip.locpar_get_sol().reshape(t, q)
+            want, lim = Um @ (V @ Um.T), 2 * (V.nnz + q) * U * (np.abs(Um) @ (abs(V) @ np.abs(Um).T))
+            tail = Um[:, 65_536:] @ (V[65_536:] @ Um.T)                        # what the rows of the last two workgroups contribute
+            assert np.all(np.abs(np.diag(tail)) > lim.diagonal())               # (a reduction that stops at 256 sums cannot pass)
+            got = st["utu"][0]
+            assert got.shape == (t, t) and np.array_equal(got, got.T)
+            worst = max(worst, float(np.max(np.abs(got - want) / lim)))
+            assert np.all(np.abs(got - want) <= lim)
+        print(f"locpar-ratio quadratic forms over 258 workgroups t{t}: {worst:.3f}")
+    finally:
+        hip.close()
+
+
 @pytest.mark.parametrize("precision", [64, 32])
 def test_same_seed_same_bits_and_running_means(precision):
     outs = []

@@ -1473,6 +1473,14 @@ def test_marker_covariance_draws_device_vs_oracle(hip, t):
     assert np.array_equal(hip.marker_covariances(), Gh)
     hip.sample_marker_covariances(df, scale, seed=11, iteration=5, marker_offset=1000)
     assert not np.array_equal(hip.marker_covariances(), Gh)
+    # df = t + 0.5: the last row's chi-square has a = 0.75 < 1 and takes the boost branch exp(log u / a)
+    hip.sample_marker_covariances(t + 0.5, scale, seed=11, iteration=4, marker_offset=1000)
+    Gb = hip.marker_covariances()
+    Gbo = O.sample_marker_covariances(beta, t + 0.5, scale, 11, 4, 1000)
+    print(f"marker covariances t{t} df={t + 0.5} (boost branch): bit-equal share {(Gb == Gbo).mean():.4f}, "
+          f"worst relative difference {np.max(np.abs(Gb - Gbo) / np.abs(Gbo)):.2e}")
+    assert np.isfinite(Gb).all() and np.array_equal(Gb, Gb.transpose(0, 2, 1))
+    np.testing.assert_allclose(Gb, Gbo, rtol=2e-6, atol=0)
     # mean of the draws (b = 0: E[G] = scale / (df - t - 1))
     for k in range(t):
         hip.set_state(k, beta=np.zeros(p, dtype=np.float32))

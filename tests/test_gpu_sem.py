@@ -48,12 +48,16 @@ def _structure(t, name):
 
 
 CASES = [(prec, 1003, t, s) for prec in (64, 32) for t, s in ((2, "full"), (3, "full"), (3, "edge"), (3, "noparents"), (4, "full"), (4, "t4"))] \
-    + [(64, 20011, 3, "full"), (32, 20011, 3, "full"), (64, 20011, 4, "t4")]
+    + [(64, 20011, 3, "full"), (32, 20011, 3, "full"), (64, 20011, 4, "t4")] \
+    + [(64, 525_389, 4, "full"), (32, 525_389, 3, "full")]     # n > 512 x 1024: k_sem_dots' capped grid takes a second trip
 
 
 @functools.lru_cache(maxsize=None)
 def _genotypes(n, precision):
-    return np.asfortranarray(make_dataset(n=n, p=64, ncausal=4, seed=5)["X"].astype(np.float64 if precision == 64 else np.float32))
+    dtype = np.float64 if precision == 64 else np.float32
+    if n > 100_000:                      # (the design plays no part in a structural-equation step: a small matrix, tiled)
+        return np.asfortranarray(np.tile(_genotypes(1003, precision), (-(-n // 1003), 1))[:n].astype(dtype))
+    return np.asfortranarray(make_dataset(n=n, p=64, ncausal=4, seed=5)["X"].astype(dtype))
 
 
 @functools.lru_cache(maxsize=None)
@@ -88,7 +92,7 @@ def _abs_gram(y):
 
 
 # ---- 1. the Gram matrix -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,t", [(1003, 2), (1003, 3), (1003, 4), (20011, 3), (20011, 4)])
+@pytest.mark.parametrize("n,t", [(1003, 2), (1003, 3), (1003, 4), (20011, 3), (20011, 4), (525_389, 4)])      # (the last: k_sem_gram's second trip)
 def test_gram(n, t):
     hip, ref, y, r0, lam0 = _setup(64, n, t, _structure(t, "full"))
     try:
