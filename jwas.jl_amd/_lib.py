@@ -16,45 +16,6 @@ MAX_STATES = 16
 BAYESC, BAYESB, BAYESR, MTBAYESC1, MTBAYESC2, MEGABAYESC, MTBAYESB1, MTBAYESB2, MEGABAYESB = 0, 1, 2, 3, 4, 5, 6, 7, 8
 GRAM_F64, GRAM_MFMA = 0, 1
 
-# every symbol include/jwas_hip.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    "jwas_hip_create", "jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_set_stream",
-    "jwas_hip_device_info", "jwas_hip_load_dense_f32", "jwas_hip_alloc_dense_f32",
-    "jwas_hip_dense_layout", "jwas_hip_get_columns", "jwas_hip_estimate_bytes",
-    "jwas_hip_synth_genotypes", "jwas_hip_setup_blocks", "jwas_hip_get_xpx", "jwas_hip_get_gram",
-    "jwas_hip_set_gram", "jwas_hip_num_blocks", "jwas_hip_init_state", "jwas_hip_set_state",
-    "jwas_hip_get_state", "jwas_hip_set_residual", "jwas_hip_get_residual", "jwas_hip_residual_dev",
-    "jwas_hip_residual_to_dev", "jwas_hip_residual_from_dev",
-    "jwas_hip_residual_sub_xalpha", "jwas_hip_mul_alpha", "jwas_hip_load_output_dense_f32", "jwas_hip_mul_alpha_output", "jwas_hip_window_sums", "jwas_hip_window_sums2", "jwas_hip_set_kernel_timing", "jwas_hip_sweep", "jwas_hip_last_sweep_counters",
-    "jwas_hip_last_sweep_schedule",
-    "jwas_hip_accumulate", "jwas_hip_get_posterior",
-    "jwas_hip_load_jgb2", "jwas_hip_load_packed2bit", "jwas_hip_alloc_packed2bit", "jwas_hip_storage_info",
-    "jwas_hip_set_xpx", "jwas_hip_estimate_bytes_storage", "jwas_hip_add_block_size", "jwas_hip_select_block_size",
-    "jwas_hip_set_weights", "jwas_hip_set_weights_f64", "jwas_hip_synth_single_step", "jwas_hip_setup_blocks_explicit",
-    "jwas_hip_comm_row_shards", "jwas_hip_comm_init_loopback", "jwas_hip_update_geometry", "jwas_hip_set_cross_gram",
-    "jwas_hip_set_columns", "jwas_hip_get_alpha_sparse", "jwas_hip_comm_unique_id", "jwas_hip_comm_init", "jwas_hip_comm_destroy", "jwas_hip_sweep_sharded",
-    "jwas_hip_residual_add_scalar", "jwas_hip_comm_info", "jwas_hip_sample_marker_covariances", "jwas_hip_get_marker_covariances",
-    "jwas_hip_set_precision", "jwas_hip_load_dense_f64", "jwas_hip_get_xpx_f64", "jwas_hip_set_state_f64", "jwas_hip_get_state_f64",
-    "jwas_hip_set_residual_f64", "jwas_hip_get_residual_f64", "jwas_hip_mul_alpha_f64", "jwas_hip_get_posterior_f64",
-    "jwas_hip_setup_groups", "jwas_hip_set_marker_covariances_f64", "jwas_hip_get_marker_covariances_f64",
-    "jwas_hip_load_output_dense_f64", "jwas_hip_mul_alpha_output_f64", "jwas_hip_get_alpha_sparse_f64",
-    "jwas_hip_window_sums_f64", "jwas_hip_window_sums2_f64",
-    "jwas_hip_gwas_begin", "jwas_hip_gwas_sample", "jwas_hip_gwas_sample_f64", "jwas_hip_gwas_local_ebv", "jwas_hip_gwas_geometry",
-    "jwas_hip_gwas_end", "jwas_hip_gwas_estimate_bytes",
-    "jwas_hip_liability_begin", "jwas_hip_liability_set_categorical", "jwas_hip_liability_set_censored",
-    "jwas_hip_liability_set_thresholds", "jwas_hip_liability_init", "jwas_hip_liability_sample", "jwas_hip_liability_minmax",
-    "jwas_hip_get_liabilities", "jwas_hip_liability_end",
-    "jwas_hip_locpar_begin", "jwas_hip_locpar_add_covariate", "jwas_hip_locpar_add_factor", "jwas_hip_locpar_size",
-    "jwas_hip_locpar_set_sol", "jwas_hip_locpar_get_sol", "jwas_hip_locpar_step", "jwas_hip_locpar_accumulate",
-    "jwas_hip_locpar_get_means", "jwas_hip_locpar_estimate_bytes", "jwas_hip_locpar_end",
-    "jwas_hip_lp_set_group_structure", "jwas_hip_lp_get_group_colors", "jwas_hip_lp_structure_estimate_bytes",
-    "jwas_hip_mtmiss_begin", "jwas_hip_mtmiss_impute", "jwas_hip_mtmiss_set_record_weights", "jwas_hip_mtmiss_estimate_bytes",
-    "jwas_hip_mtmiss_end",
-    "jwas_hip_annot_begin", "jwas_hip_annot_step", "jwas_hip_annot_accumulate", "jwas_hip_annot_get_prior", "jwas_hip_annot_get_means",
-    "jwas_hip_annot_get_liability", "jwas_hip_annot_get_mu", "jwas_hip_annot_estimate_bytes", "jwas_hip_annot_end",
-    "jwas_hip_sem_begin", "jwas_hip_sem_step", "jwas_hip_sem_get_lambda", "jwas_hip_sem_set_lambda", "jwas_hip_sem_get_gram",
-    "jwas_hip_sem_accumulate", "jwas_hip_sem_get_effects", "jwas_hip_sem_estimate_bytes", "jwas_hip_sem_end",
-]
 ANNOT_MAX_COLS = 64                     # columns of the annotation design matrix, the intercept included (JWAS_HIP_ANNOT_MAX_COLS)
 ANNOT_BAYESC, ANNOT_BAYESR, ANNOT_TREE = 0, 1, 2
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
@@ -150,6 +111,146 @@ class JwasHipError(RuntimeError):
         self.message = message
 
 
+_vp, _i32, _i64, _u64, _f64p, _INT, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.POINTER(C.c_double), C.c_int, C.POINTER
+
+# every entry point include/jwas_hip.h declares: name -> (restype, argtypes).  SYMBOLS and load()'s declarations derive from it
+# (tests/test_abi.py checks the names against the header and the library's exports).
+PROTOTYPES = {
+    "jwas_hip_create": (_INT, [C.c_int, _P(_vp)]),
+    "jwas_hip_destroy": (None, [_vp]),
+    "jwas_hip_last_error": (C.c_char_p, [_vp]),
+    "jwas_hip_set_stream": (_INT, [_vp, _vp]),
+    "jwas_hip_device_info": (_INT, [_vp, _P(C.c_int), _P(_i64), _P(_i64)]),
+    "jwas_hip_load_dense_f32": (_INT, [_vp, _vp, _i64, _i64, _i64]),
+    "jwas_hip_alloc_dense_f32": (_INT, [_vp, _i64, _i64]),
+    "jwas_hip_dense_layout": (_INT, [_vp, _P(_i64), _P(_i64), _P(_i64), _P(_vp)]),
+    "jwas_hip_get_columns": (_INT, [_vp, _i64, _i64, _vp]),
+    "jwas_hip_estimate_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "jwas_hip_synth_genotypes": (_INT, [_vp, _u64, _i32, _i32, _i64]),
+    "jwas_hip_setup_blocks": (_INT, [_vp, _i32, _i32]),
+    "jwas_hip_get_xpx": (_INT, [_vp, _vp]),
+    "jwas_hip_get_gram": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_set_gram": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_num_blocks": (_INT, [_vp, _P(_i64), _P(_i32)]),
+    "jwas_hip_init_state": (_INT, [_vp, _i32, _i32]),
+    "jwas_hip_set_state": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_get_state": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_set_residual": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_get_residual": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_residual_dev": (_INT, [_vp, _P(_vp), _P(_i64)]),
+    "jwas_hip_residual_to_dev": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_residual_from_dev": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_residual_sub_xalpha": (_INT, [_vp, _i32]),
+    "jwas_hip_mul_alpha": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_load_output_dense_f32": (_INT, [_vp, _vp, _i64, _i64, _i64]),
+    "jwas_hip_mul_alpha_output": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_window_sums": (_INT, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "jwas_hip_window_sums2": (_INT, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jwas_hip_set_kernel_timing": (_INT, [_vp, _i32]),
+    "jwas_hip_sweep": (_INT, [_vp, _P(SweepParams), _P(SweepStats)]),
+    "jwas_hip_last_sweep_counters": (_INT, [_vp, _P(_u64), _i32]),
+    "jwas_hip_last_sweep_schedule": (_INT, [_vp, _P(C.c_uint32)]),
+    "jwas_hip_accumulate": (_INT, [_vp, C.c_double]),
+    "jwas_hip_get_posterior": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_load_jgb2": (_INT, [_vp, C.c_char_p]),
+    "jwas_hip_load_packed2bit": (_INT, [_vp, _vp, _i64, _i64, _i64, _vp, _i32]),
+    "jwas_hip_alloc_packed2bit": (_INT, [_vp, _i64, _i64, _i32]),
+    "jwas_hip_storage_info": (_INT, [_vp, _P(_i32), _P(_i64), _P(_i64), _P(_i64)]),
+    "jwas_hip_set_xpx": (_INT, [_vp, _vp]),
+    "jwas_hip_estimate_bytes_storage": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "jwas_hip_add_block_size": (_INT, [_vp, _i32, _i32]),
+    "jwas_hip_select_block_size": (_INT, [_vp, _i32]),
+    "jwas_hip_set_weights": (_INT, [_vp, _vp]),
+    "jwas_hip_set_weights_f64": (_INT, [_vp, _vp]),
+    "jwas_hip_synth_single_step": (_INT, [_vp, _u64, _i64, _i32, _i64]),
+    "jwas_hip_setup_blocks_explicit": (_INT, [_vp, _P(_i64), _i64, _i32]),
+    "jwas_hip_comm_row_shards": (_INT, [_vp, _i32]),
+    "jwas_hip_comm_init_loopback": (_INT, [_vp, _i32, _i32, _i32]),
+    "jwas_hip_update_geometry": (_INT, [_vp, _P(_i32), _P(_i32), _P(_i32)]),
+    "jwas_hip_set_cross_gram": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_set_columns": (_INT, [_vp, _i64, _i64, _vp, _i64]),
+    "jwas_hip_get_alpha_sparse": (_INT, [_vp, _i32, _i64, _vp, _vp, _P(_i64)]),
+    "jwas_hip_comm_unique_id": (_INT, [_vp]),
+    "jwas_hip_comm_init": (_INT, [_vp, _vp, _i32, _i32]),
+    "jwas_hip_comm_destroy": (_INT, [_vp]),
+    "jwas_hip_sweep_sharded": (_INT, [_vp, _P(SweepParams), _P(SweepStats)]),
+    "jwas_hip_residual_add_scalar": (_INT, [_vp, _i32, C.c_double]),
+    "jwas_hip_comm_info": (_INT, [_vp, _P(_i32), _P(_i32)]),
+    "jwas_hip_sample_marker_covariances": (_INT, [_vp, C.c_double, _f64p, _u64, C.c_uint32, C.c_uint32]),
+    "jwas_hip_get_marker_covariances": (_INT, [_vp, _vp]),
+    "jwas_hip_set_precision": (_INT, [_vp, _i32]),
+    "jwas_hip_load_dense_f64": (_INT, [_vp, _vp, _i64, _i64, _i64]),
+    "jwas_hip_get_xpx_f64": (_INT, [_vp, _vp]),
+    "jwas_hip_set_state_f64": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_get_state_f64": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_set_residual_f64": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_get_residual_f64": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_mul_alpha_f64": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_get_posterior_f64": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_setup_groups": (_INT, [_vp, _i32, _i32]),
+    "jwas_hip_set_marker_covariances_f64": (_INT, [_vp, _vp]),
+    "jwas_hip_get_marker_covariances_f64": (_INT, [_vp, _vp]),
+    "jwas_hip_load_output_dense_f64": (_INT, [_vp, _vp, _i64, _i64, _i64]),
+    "jwas_hip_mul_alpha_output_f64": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_get_alpha_sparse_f64": (_INT, [_vp, _i32, _i64, _vp, _vp, _P(_i64)]),
+    "jwas_hip_window_sums_f64": (_INT, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "jwas_hip_window_sums2_f64": (_INT, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "jwas_hip_gwas_begin": (_INT, [_vp, _i32, _i32, _vp, _vp, _i32]),
+    "jwas_hip_gwas_sample": (_INT, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "jwas_hip_gwas_sample_f64": (_INT, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "jwas_hip_gwas_local_ebv": (_INT, [_vp, _vp, _P(_i64)]),
+    "jwas_hip_gwas_geometry": (_INT, [_vp, _P(_i32), _P(_i32), _P(_i32)]),
+    "jwas_hip_gwas_end": (_INT, [_vp]),
+    "jwas_hip_gwas_estimate_bytes": (_i64, [_i64, _i64, _i64, _i32]),
+    "jwas_hip_liability_begin": (_INT, [_vp, _i32]),
+    "jwas_hip_liability_set_categorical": (_INT, [_vp, _i32, _i64, _vp, _i32, _vp]),
+    "jwas_hip_liability_set_censored": (_INT, [_vp, _i32, _i64, _vp, _vp]),
+    "jwas_hip_liability_set_thresholds": (_INT, [_vp, _i32, _i32, _vp]),
+    "jwas_hip_liability_init": (_INT, [_vp, _P(LiabilityParams)]),
+    "jwas_hip_liability_sample": (_INT, [_vp, _P(LiabilityParams)]),
+    "jwas_hip_liability_minmax": (_INT, [_vp, _i32, _vp, _vp]),
+    "jwas_hip_get_liabilities": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_liability_end": (_INT, [_vp]),
+    "jwas_hip_locpar_begin": (_INT, [_vp, _i32]),
+    "jwas_hip_locpar_add_covariate": (_INT, [_vp, _i32, _i64, _vp]),
+    "jwas_hip_locpar_add_factor": (_INT, [_vp, _i32, _i64, _vp, _i64, _i32]),
+    "jwas_hip_locpar_size": (_INT, [_vp, _P(_i64)]),
+    "jwas_hip_locpar_set_sol": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_locpar_get_sol": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_locpar_step": (_INT, [_vp, _P(LocparParams), _P(LocparStats)]),
+    "jwas_hip_locpar_accumulate": (_INT, [_vp, C.c_double]),
+    "jwas_hip_locpar_get_means": (_INT, [_vp, _i64, _vp, _vp]),
+    "jwas_hip_locpar_estimate_bytes": (_i64, [_i64, _i64, _i64]),
+    "jwas_hip_locpar_end": (_INT, [_vp]),
+    "jwas_hip_lp_set_group_structure": (_INT, [_vp, _i32, _i64, _vp, _vp, _vp]),
+    "jwas_hip_lp_get_group_colors": (_INT, [_vp, _i32, _i64, _vp, _P(_i32)]),
+    "jwas_hip_lp_structure_estimate_bytes": (_i64, [_i64, _i64]),
+    "jwas_hip_mtmiss_begin": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_mtmiss_impute": (_INT, [_vp, _P(MtmissParams)]),
+    "jwas_hip_mtmiss_set_record_weights": (_INT, [_vp, _vp]),
+    "jwas_hip_mtmiss_estimate_bytes": (_i64, [_i64]),
+    "jwas_hip_mtmiss_end": (_INT, [_vp]),
+    "jwas_hip_annot_begin": (_INT, [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "jwas_hip_annot_step": (_INT, [_vp, _P(AnnotParams), _P(AnnotStats)]),
+    "jwas_hip_annot_accumulate": (_INT, [_vp, C.c_double]),
+    "jwas_hip_annot_get_prior": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_annot_get_means": (_INT, [_vp, _i64, _vp, _vp]),
+    "jwas_hip_annot_get_liability": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_annot_get_mu": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_annot_estimate_bytes": (_i64, [_i64, _i32, _i32]),
+    "jwas_hip_annot_end": (_INT, [_vp]),
+    "jwas_hip_sem_begin": (_INT, [_vp, _i32, _i64, _vp, _vp]),
+    "jwas_hip_sem_step": (_INT, [_vp, _P(SemParams), _P(SemStats)]),
+    "jwas_hip_sem_get_lambda": (_INT, [_vp, _vp]),
+    "jwas_hip_sem_set_lambda": (_INT, [_vp, _vp]),
+    "jwas_hip_sem_get_gram": (_INT, [_vp, _vp]),
+    "jwas_hip_sem_accumulate": (_INT, [_vp, _vp, C.c_double]),
+    "jwas_hip_sem_get_effects": (_INT, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "jwas_hip_sem_estimate_bytes": (_i64, [_i64, _i64, _i32]),
+    "jwas_hip_sem_end": (_INT, [_vp]),
+}
+SYMBOLS = list(PROTOTYPES)
+
 _lib = None
 
 
@@ -163,154 +264,8 @@ def load():
             f"{LIB_PATH} not found: build it with jwas.jl_amd/csrc/build.sh (hipcc, gfx950). "
             "The MI355X path has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, u64, f32p, f64p = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_double)
-    L.jwas_hip_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.jwas_hip_destroy.argtypes = [vp]
-    L.jwas_hip_destroy.restype = None
-    L.jwas_hip_last_error.argtypes = [vp]
-    L.jwas_hip_last_error.restype = C.c_char_p
-    L.jwas_hip_set_stream.argtypes = [vp, vp]
-    L.jwas_hip_device_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(i64)]
-    L.jwas_hip_load_dense_f32.argtypes = [vp, vp, i64, i64, i64]
-    L.jwas_hip_alloc_dense_f32.argtypes = [vp, i64, i64]
-    L.jwas_hip_dense_layout.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(vp)]
-    L.jwas_hip_get_columns.argtypes = [vp, i64, i64, vp]
-    L.jwas_hip_set_columns.argtypes = [vp, i64, i64, vp, i64]
-    L.jwas_hip_get_alpha_sparse.argtypes = [vp, i32, i64, vp, vp, C.POINTER(i64)]
-    L.jwas_hip_estimate_bytes.argtypes = [i64, i64, i32, i32]
-    L.jwas_hip_estimate_bytes.restype = i64
-    L.jwas_hip_synth_genotypes.argtypes = [vp, u64, i32, i32, i64]
-    L.jwas_hip_synth_single_step.argtypes = [vp, u64, i64, i32, i64]
-    L.jwas_hip_setup_blocks.argtypes = [vp, i32, i32]
-    L.jwas_hip_get_xpx.argtypes = [vp, vp]
-    L.jwas_hip_get_gram.argtypes = [vp, i64, vp]
-    L.jwas_hip_set_gram.argtypes = [vp, i64, vp]
-    L.jwas_hip_num_blocks.argtypes = [vp, C.POINTER(i64), C.POINTER(i32)]
-    L.jwas_hip_init_state.argtypes = [vp, i32, i32]
-    L.jwas_hip_set_state.argtypes = [vp, i32, vp, vp, vp]
-    L.jwas_hip_get_state.argtypes = [vp, i32, vp, vp, vp]
-    L.jwas_hip_set_residual.argtypes = [vp, i32, vp]
-    L.jwas_hip_get_residual.argtypes = [vp, i32, vp]
-    L.jwas_hip_residual_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
-    L.jwas_hip_residual_to_dev.argtypes = [vp, i32, vp]
-    L.jwas_hip_residual_from_dev.argtypes = [vp, i32, vp]
-    L.jwas_hip_set_kernel_timing.argtypes = [vp, i32]
-    L.jwas_hip_last_sweep_counters.argtypes = [vp, C.POINTER(C.c_uint64), i32]
-    L.jwas_hip_last_sweep_schedule.argtypes = [vp, C.POINTER(C.c_uint32)]
-    L.jwas_hip_residual_sub_xalpha.argtypes = [vp, i32]
-    L.jwas_hip_mul_alpha.argtypes = [vp, i32, vp]
-    L.jwas_hip_load_output_dense_f32.argtypes = [vp, vp, i64, i64, i64]
-    L.jwas_hip_mul_alpha_output.argtypes = [vp, i32, vp]
-    L.jwas_hip_window_sums.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
-    L.jwas_hip_window_sums2.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.jwas_hip_sweep.argtypes = [vp, C.POINTER(SweepParams), C.POINTER(SweepStats)]
-    L.jwas_hip_sweep_sharded.argtypes = [vp, C.POINTER(SweepParams), C.POINTER(SweepStats)]
-    L.jwas_hip_comm_unique_id.argtypes = [vp]
-    L.jwas_hip_comm_init.argtypes = [vp, vp, i32, i32]
-    L.jwas_hip_comm_destroy.argtypes = [vp]
-    L.jwas_hip_comm_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    L.jwas_hip_residual_add_scalar.argtypes = [vp, i32, C.c_double]
-    L.jwas_hip_sample_marker_covariances.argtypes = [vp, C.c_double, f64p, u64, C.c_uint32, C.c_uint32]
-    L.jwas_hip_get_marker_covariances.argtypes = [vp, vp]
-    L.jwas_hip_set_precision.argtypes = [vp, i32]
-    L.jwas_hip_load_dense_f64.argtypes = [vp, vp, i64, i64, i64]
-    L.jwas_hip_get_xpx_f64.argtypes = [vp, vp]
-    L.jwas_hip_set_state_f64.argtypes = [vp, i32, vp, vp, vp]
-    L.jwas_hip_get_state_f64.argtypes = [vp, i32, vp, vp, vp]
-    L.jwas_hip_set_residual_f64.argtypes = [vp, i32, vp]
-    L.jwas_hip_get_residual_f64.argtypes = [vp, i32, vp]
-    L.jwas_hip_mul_alpha_f64.argtypes = [vp, i32, vp]
-    L.jwas_hip_get_posterior_f64.argtypes = [vp, i32, vp, vp, vp]
-    L.jwas_hip_load_output_dense_f64.argtypes = [vp, vp, i64, i64, i64]
-    L.jwas_hip_mul_alpha_output_f64.argtypes = [vp, i32, vp]
-    L.jwas_hip_get_alpha_sparse_f64.argtypes = [vp, i32, i64, vp, vp, C.POINTER(i64)]
-    L.jwas_hip_window_sums_f64.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
-    L.jwas_hip_window_sums2_f64.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.jwas_hip_gwas_begin.argtypes = [vp, i32, i32, vp, vp, i32]
-    L.jwas_hip_gwas_sample.argtypes = [vp, i32, vp, vp, vp, vp]
-    L.jwas_hip_gwas_sample_f64.argtypes = [vp, i32, vp, vp, vp, vp]
-    L.jwas_hip_gwas_local_ebv.argtypes = [vp, vp, C.POINTER(i64)]
-    L.jwas_hip_gwas_geometry.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    L.jwas_hip_gwas_end.argtypes = [vp]
-    L.jwas_hip_gwas_estimate_bytes.argtypes = [i64, i64, i64, i32]
-    L.jwas_hip_gwas_estimate_bytes.restype = i64
-    L.jwas_hip_liability_begin.argtypes = [vp, i32]
-    L.jwas_hip_liability_set_categorical.argtypes = [vp, i32, i64, vp, i32, vp]
-    L.jwas_hip_liability_set_censored.argtypes = [vp, i32, i64, vp, vp]
-    L.jwas_hip_liability_set_thresholds.argtypes = [vp, i32, i32, vp]
-    L.jwas_hip_liability_init.argtypes = [vp, C.POINTER(LiabilityParams)]
-    L.jwas_hip_liability_sample.argtypes = [vp, C.POINTER(LiabilityParams)]
-    L.jwas_hip_liability_minmax.argtypes = [vp, i32, vp, vp]
-    L.jwas_hip_get_liabilities.argtypes = [vp, i32, vp]
-    L.jwas_hip_liability_end.argtypes = [vp]
-    L.jwas_hip_locpar_begin.argtypes = [vp, i32]
-    L.jwas_hip_locpar_add_covariate.argtypes = [vp, i32, i64, vp]
-    L.jwas_hip_locpar_add_factor.argtypes = [vp, i32, i64, vp, i64, i32]
-    L.jwas_hip_locpar_size.argtypes = [vp, C.POINTER(i64)]
-    L.jwas_hip_locpar_set_sol.argtypes = [vp, i64, vp]
-    L.jwas_hip_locpar_get_sol.argtypes = [vp, i64, vp]
-    L.jwas_hip_locpar_step.argtypes = [vp, C.POINTER(LocparParams), C.POINTER(LocparStats)]
-    L.jwas_hip_locpar_accumulate.argtypes = [vp, C.c_double]
-    L.jwas_hip_locpar_get_means.argtypes = [vp, i64, vp, vp]
-    L.jwas_hip_locpar_estimate_bytes.argtypes = [i64, i64, i64]
-    L.jwas_hip_locpar_estimate_bytes.restype = i64
-    L.jwas_hip_locpar_end.argtypes = [vp]
-    L.jwas_hip_lp_set_group_structure.argtypes = [vp, i32, i64, vp, vp, vp]
-    L.jwas_hip_lp_get_group_colors.argtypes = [vp, i32, i64, vp, C.POINTER(i32)]
-    L.jwas_hip_lp_structure_estimate_bytes.argtypes = [i64, i64]
-    L.jwas_hip_lp_structure_estimate_bytes.restype = i64
-    L.jwas_hip_mtmiss_begin.argtypes = [vp, i64, vp]
-    L.jwas_hip_mtmiss_impute.argtypes = [vp, C.POINTER(MtmissParams)]
-    L.jwas_hip_mtmiss_set_record_weights.argtypes = [vp, vp]
-    L.jwas_hip_mtmiss_estimate_bytes.argtypes = [i64]
-    L.jwas_hip_mtmiss_estimate_bytes.restype = i64
-    L.jwas_hip_mtmiss_end.argtypes = [vp]
-    L.jwas_hip_annot_begin.argtypes = [vp, i32, i64, i32, vp, vp, vp, vp]
-    L.jwas_hip_annot_step.argtypes = [vp, C.POINTER(AnnotParams), C.POINTER(AnnotStats)]
-    L.jwas_hip_annot_accumulate.argtypes = [vp, C.c_double]
-    L.jwas_hip_annot_get_prior.argtypes = [vp, i64, vp]
-    L.jwas_hip_annot_get_means.argtypes = [vp, i64, vp, vp]
-    L.jwas_hip_annot_get_liability.argtypes = [vp, i64, vp]
-    L.jwas_hip_annot_get_mu.argtypes = [vp, i64, vp]
-    L.jwas_hip_annot_estimate_bytes.argtypes = [i64, i32, i32]
-    L.jwas_hip_annot_estimate_bytes.restype = i64
-    L.jwas_hip_annot_end.argtypes = [vp]
-    L.jwas_hip_sem_begin.argtypes = [vp, i32, i64, vp, vp]
-    L.jwas_hip_sem_step.argtypes = [vp, C.POINTER(SemParams), C.POINTER(SemStats)]
-    L.jwas_hip_sem_get_lambda.argtypes = [vp, vp]
-    L.jwas_hip_sem_set_lambda.argtypes = [vp, vp]
-    L.jwas_hip_sem_get_gram.argtypes = [vp, vp]
-    L.jwas_hip_sem_accumulate.argtypes = [vp, vp, C.c_double]
-    L.jwas_hip_sem_get_effects.argtypes = [vp, i32, i32, vp, vp, vp]
-    L.jwas_hip_sem_estimate_bytes.argtypes = [i64, i64, i32]
-    L.jwas_hip_sem_estimate_bytes.restype = i64
-    L.jwas_hip_sem_end.argtypes = [vp]
-    L.jwas_hip_set_marker_covariances_f64.argtypes = [vp, vp]
-    L.jwas_hip_get_marker_covariances_f64.argtypes = [vp, vp]
-    L.jwas_hip_accumulate.argtypes = [vp, C.c_double]
-    L.jwas_hip_get_posterior.argtypes = [vp, i32, vp, vp, vp]
-    L.jwas_hip_load_jgb2.argtypes = [vp, C.c_char_p]
-    L.jwas_hip_load_packed2bit.argtypes = [vp, vp, i64, i64, i64, vp, i32]
-    L.jwas_hip_alloc_packed2bit.argtypes = [vp, i64, i64, i32]
-    L.jwas_hip_storage_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.jwas_hip_set_xpx.argtypes = [vp, vp]
-    L.jwas_hip_set_weights.argtypes = [vp, vp]
-    L.jwas_hip_set_weights_f64.argtypes = [vp, vp]
-    L.jwas_hip_add_block_size.argtypes = [vp, i32, i32]
-    L.jwas_hip_setup_blocks_explicit.argtypes = [vp, C.POINTER(C.c_int64), i64, i32]
-    L.jwas_hip_comm_row_shards.argtypes = [vp, i32]
-    L.jwas_hip_update_geometry.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    L.jwas_hip_set_cross_gram.argtypes = [vp, i64, vp]
-    L.jwas_hip_comm_init_loopback.argtypes = [vp, i32, i32, i32]
-    L.jwas_hip_select_block_size.argtypes = [vp, i32]
-    L.jwas_hip_setup_groups.argtypes = [vp, i32, i32]
-    L.jwas_hip_estimate_bytes_storage.argtypes = [i64, i64, i32, i32, i32]
-    L.jwas_hip_estimate_bytes_storage.restype = i64
-    for name in SYMBOLS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(L, name)
-        if name not in ("jwas_hip_destroy", "jwas_hip_last_error", "jwas_hip_estimate_bytes", "jwas_hip_estimate_bytes_storage", "jwas_hip_gwas_estimate_bytes",
-                        "jwas_hip_locpar_estimate_bytes", "jwas_hip_lp_structure_estimate_bytes", "jwas_hip_mtmiss_estimate_bytes",
-                        "jwas_hip_annot_estimate_bytes", "jwas_hip_sem_estimate_bytes"):
-            fn.restype = C.c_int
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L

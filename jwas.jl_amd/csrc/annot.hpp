@@ -10,7 +10,7 @@
 // so a lane reads consecutive markers.  All arithmetic is double, -ffp-contract=off.  Step s, with its coefficients c_0 .. c_K-1:
 //   (a) mu_i = c_0 + sum_{k >= 1} D_ik c_k                        k ascending, multiply then add
 //   (b) i in A_s:  u = u52(philox4x32_10(i, iteration, 0x08000000 | s, 5)),
-//                  e_i = truncated_std_normal(lo, hi, u)  (liability.hpp),  (lo, hi) = (-mu_i, +Inf) if z_i, (-Inf, -mu_i) otherwise,
+//                  e_i = truncated_std_normal(lo, hi, u)  (device_util.hpp),  (lo, hi) = (-mu_i, +Inf) if z_i, (-Inf, -mu_i) otherwise,
 //                  liability_i = mu_i + e_i, forced onto its side of 0 (max(., 0) if z_i, min(., 0) otherwise)
 //       i not in A_s:  e_i = 0, the stored liability is kept
 //   (c) the coefficient scan in residual-update form, k = 0 .. K - 1 in order.  n_A = |A_s|, S_k = sum_A D_ik e_i,
@@ -41,7 +41,7 @@
 //   k_annot_colmeans          one workgroup: the column means
 //   k_annot_accumulate        running mean and mean of squares of the per-marker prior (output.jl:597-601's form)
 #pragma once
-#include "liability.hpp"
+#include "device_util.hpp"
 #include "rng.hpp"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,30 +54,9 @@ constexpr int kMaxSteps = 3;
 constexpr uint32_t kTag = 0x08000000u;
 constexpr double kEps = 0x1.0p-52;
 
-enum { kBayesC = 0, kBayesR = 1, kTree = 2 };
+// (the kinds kBayesC, kBayesR, kTree: device_util.hpp)
 
 __host__ __device__ inline int annot_nsteps(int kind) { return kind == kBayesC ? 1 : 3; }
-
-// the 256 values of a workgroup in a fixed tree; every thread returns the total
-__device__ inline double annot_tree256(double* sh, double v)
-{
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-// part[0], part[stride], ... (n of them): thread j adds entries j, j + 256, ... in that order, then the tree
-__device__ inline double annot_ordered_sum(double* sh, const double* __restrict__ part, int stride, int n)
-{
-    double acc = 0.0;
-    for (int q = threadIdx.x; q < n; q += 256) acc = acc + part[(size_t)q * stride];
-    return annot_tree256(sh, acc);
-}
 
 template <class DT, int KIND>
 __device__ __forceinline__ void annot_response(const DT* __restrict__ d1, const DT* __restrict__ d2, int64_t i, int s, bool& act, bool& z)
@@ -132,7 +111,7 @@ __global__ __launch_bounds__(256) void k_annot_liab(const StepArgs A)
             const double mu = annot_mu(A.D, A.coef, A.K, A.p, i);
             const jw::u32x4 w = jw::philox4x32_10((uint32_t)i, A.iter, kTag | (uint32_t)A.s, 5u, A.seed_lo, A.seed_hi);
             const double u = jw::u52(w.x, w.y);
-            e = jwl::truncated_std_normal(z ? -mu : -INFINITY, z ? INFINITY : -mu, u);
+            e = jwu::truncated_std_normal(z ? -mu : -INFINITY, z ? INFINITY : -mu, u);
             const double l = mu + e;
             A.liab[i] = z ? fmax(l, 0.0) : fmin(l, 0.0);
             S = S + e;
@@ -140,7 +119,7 @@ __global__ __launch_bounds__(256) void k_annot_liab(const StepArgs A)
         }
         A.e[i] = e;
     }
-    const double St = annot_tree256(sh, S), ct = annot_tree256(sh, cnt);
+    const double St = jwu::tree256(sh, S), ct = jwu::tree256(sh, cnt);
     if (threadIdx.x == 0) { A.part[(size_t)blockIdx.x * 3] = St; A.part[(size_t)blockIdx.x * 3 + 2] = ct; }
 }
 
@@ -166,10 +145,10 @@ __global__ __launch_bounds__(256) void k_annot_sums(const StepArgs A)
         S = S + x * e;
         d = d + x * x;
     }
-    const double St = annot_tree256(sh, S);
+    const double St = jwu::tree256(sh, S);
     if (threadIdx.x == 0) A.part[(size_t)blockIdx.x * 3] = St;
     if (!A.all_active) {                                                    // (uniform)
-        const double dt = annot_tree256(sh, d);
+        const double dt = jwu::tree256(sh, d);
         if (threadIdx.x == 0) A.part[(size_t)blockIdx.x * 3 + 1] = dt;
     }
 }
@@ -189,14 +168,14 @@ struct DrawArgs {
 __global__ __launch_bounds__(256) void k_annot_draw(const DrawArgs A)
 {
     __shared__ double sh[256];
-    const double S = annot_ordered_sum(sh, A.part, 3, A.npieces);
+    const double S = jwu::ordered_sum256(sh, A.part, 3, A.npieces);
     double d, cnt;
     if (A.k == 0) {
-        cnt = annot_ordered_sum(sh, A.part + 2, 3, A.npieces);
+        cnt = jwu::ordered_sum256(sh, A.part + 2, 3, A.npieces);
         d = cnt;
     } else {
         cnt = *A.nA;
-        d = A.all_active ? A.dsq[A.k] : annot_ordered_sum(sh, A.part + 1, 3, A.npieces);       // (uniform)
+        d = A.all_active ? A.dsq[A.k] : jwu::ordered_sum256(sh, A.part + 1, 3, A.npieces);       // (uniform)
     }
     if (threadIdx.x != 0) return;
     if (A.k == 0) *A.nA = cnt;
@@ -223,7 +202,7 @@ __global__ __launch_bounds__(256) void k_annot_colsq(const double* __restrict__ 
         if (i >= p) break;
         d = d + Dk[i] * Dk[i];
     }
-    const double dt = annot_tree256(sh, d);
+    const double dt = jwu::tree256(sh, d);
     if (threadIdx.x == 0) out[(size_t)blockIdx.y * npieces + blockIdx.x] = dt;
 }
 
@@ -231,7 +210,7 @@ __global__ __launch_bounds__(256) void k_annot_colsq(const double* __restrict__ 
 __global__ __launch_bounds__(256) void k_annot_colsq_reduce(const double* __restrict__ part, int32_t npieces, double* __restrict__ dsq)
 {
     __shared__ double sh[256];
-    const double tot = annot_ordered_sum(sh, part + (size_t)blockIdx.x * npieces, 1, npieces);
+    const double tot = jwu::ordered_sum256(sh, part + (size_t)blockIdx.x * npieces, 1, npieces);
     if (threadIdx.x == 0) dsq[blockIdx.x + 1] = tot;
 }
 
@@ -266,7 +245,7 @@ __global__ __launch_bounds__(256) void k_annot_table(const TableArgs A)
         for (int s = 0; s < NS; ++s) {
             const double mu = annot_mu(A.D, A.coef + (size_t)s * A.K, A.K, A.p, i);
             A.mu[(size_t)s * A.p + i] = mu;
-            P[s] = jwl::upper_tail(-mu);                                    // Phi(mu)
+            P[s] = jwu::upper_tail(-mu);                                    // Phi(mu)
         }
         if constexpr (KIND == kBayesC) {
             const double pi = annot_clip(1.0 - P[0]);
@@ -289,7 +268,7 @@ __global__ __launch_bounds__(256) void k_annot_table(const TableArgs A)
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        const double tot = annot_tree256(sh, acc[c]);
+        const double tot = jwu::tree256(sh, acc[c]);
         if (threadIdx.x == 0) A.part[(size_t)blockIdx.x * 4 + c] = tot;
     }
 }
@@ -299,7 +278,7 @@ __global__ __launch_bounds__(256) void k_annot_colmeans(const double* __restrict
 {
     __shared__ double sh[256];
     for (int c = 0; c < ncols; ++c) {
-        const double tot = annot_ordered_sum(sh, part + c, 4, npieces);
+        const double tot = jwu::ordered_sum256(sh, part + c, 4, npieces);
         if (threadIdx.x == 0) means[c] = tot / p;
     }
 }
@@ -311,8 +290,8 @@ __global__ __launch_bounds__(256) void k_annot_accumulate(const double* __restri
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= q) return;
     const double v = is_log ? exp(table[i]) : table[i];
-    mean[i] = mean[i] + (v - mean[i]) / nsamples;
-    mean2[i] = mean2[i] + (v * v - mean2[i]) / nsamples;
+    mean[i] = jwu::running_mean(mean[i], v, nsamples);
+    mean2[i] = jwu::running_mean(mean2[i], v * v, nsamples);
 }
 
 }  // namespace jwa

@@ -1,14 +1,11 @@
-// jwas_hip.hip -- context, memory and the C ABI of libjwas_hip.so (see include/jwas_hip.h).
+// jwas_hip.hip -- context, memory, the sweep and the GWAS session behind the C ABI of libjwas_hip.so (see include/jwas_hip.h).
+// The context itself and the shared host plumbing: ctx.hpp; the other sessions: session_*.hip, one unit each.
 // gfx950 only.  No CPU fallback: every entry point either runs the HIP path or returns an error.
 #include "../../include/jwas_hip.h"
+#include "ctx.hpp"
 #include "sweep.hpp"
 #include "f64_path.hpp"
 #include "step_launch.hpp"
-#include "liability.hpp"
-#include "locpar.hpp"
-#include "mtmiss.hpp"
-#include "annot.hpp"
-#include "sem.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -28,239 +25,13 @@ using namespace jw;
 
 static_assert(JWAS_HIP_MAX_TRAITS == kMaxT, "trait limit mismatch");
 static_assert(JWAS_HIP_MAX_STATES == kMaxStates, "state limit mismatch");
-
-struct jwas_hip_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::string err;
-
-    int64_t n = 0, p = 0, ld = 0;
-    int nslices = 0;                    // 256-row slices
-    int upd_nslices = 0;                // slices of the UPDATE role: = nslices (dense), 1024-row slices on 2-bit packed storage (update_role_wide)
-    int nrg = 0, ncg = 1;               // k_update_partial grid: row groups x column groups
-    int spg = 8;                        // slices per row group
-    float* X = nullptr;                 // dense fp32 storage ...
-    uint8_t* Q = nullptr;               // ... or the reference's 2-bit packed storage [p][ld/4] + per-marker means
-    float* qmean = nullptr;
-    bool packed = false;
-    int centered = 1;
-    float* w = nullptr;                 // [ld] residual weights R^-1 (ones unless jwas_hip_set_weights; pad rows 0)
-    bool weighted = false;
-
-    // Active block configuration (a view of one entry of `sets`; several block sizes can be resident so the host
-    // can pick per sweep: big blocks when few markers change, smaller ones when many do).
-    struct BlockSet {
-        int bs; int64_t nblocks; float *gram, *cross, *corr; double* partials;
-        // grouped launches (jwas_hip_setup_groups; k_group_step): gm = 2 or 4 blocks per launch (0: not set up); gcross[0]: cross-Grams
-        // of consecutive PAIRS of blocks (2 bs markers: pair q at q (2 bs)^2, rows = markers of pair q-1), gcross[1] (gm = 4): of
-        // consecutive groups of four; gcbuf: the corrections [2][gm bs] cG | [2][bs] cW | [2 bs] cP | [bs] zeros; gidx / gdelta:
-        // [2][gm bs] the merged change lists of a group (ping-pong; header lines: ctx.ev[parity])
-        int gm; float* gcross[2]; float* gcbuf; int32_t* gidx; float* gdelta;
-        unsigned long long* gpp;        // tagged hand-over words of the ping-pong samplers (SamplerArgs::pp_*, GroupArgs::pp_*): (6 + 3 gm) bs + 8
-    };
-    unsigned pp_epoch = 0;              // tag of the last ping-pong launch (31 bits, never 0: a word of the zeroed buffer matches no launch)
-    int set_index = 0;                  // entry of `sets` that is selected
-    std::vector<BlockSet> sets;
-    std::vector<int64_t> starts;        // explicit block starts (nblocks + 1 entries, last = p), empty = uniform blocks
-    int64_t* d_starts = nullptr;        // ... on the device
-    int block_size = 0;
-    int64_t nblocks = 0;
-    float* xpx = nullptr;
-    float* gram = nullptr;
-    float* cross = nullptr;             // cross-Grams X_{b-1}'X_b, block b at offset b*bs*bs (block 0 unused)
-    float* corr = nullptr;              // [2][kMaxT][bs] lookahead corrections (ping-pong: read by launch k, written for k+1)
-
-    int method = -1, ntraits = 0;
-    float* r = nullptr;                 // [2][kMaxT][ld] ping-pong; buffer 0 is current between sweeps
-    float *alpha = nullptr, *beta = nullptr;
-    void* delta = nullptr;
-    float *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;
-
-    double* partials = nullptr;
-    Events* ev = nullptr;               // [2]
-    // independent-block mode (allocated on first use)
-    double* ipartials = nullptr;        // [nblocks][t][nrg][bs]
-    Events* ev_all = nullptr;           // [nblocks] per-block change lists
-    int32_t* ev_offs = nullptr;         // [nblocks + 1] exclusive scan of the counts; [nblocks] = total
-    int32_t* idx_all = nullptr;         // [p] compacted change list, (block, marker) order
-    float* delta_all = nullptr;         // [kMaxT][p]
-    int ind_traits = 0;
-    DevParams* dparams = nullptr;
-    unsigned long long* counters = nullptr;
-    double* fin_out = nullptr;          // [nslices][kMaxT*kMaxT + kMaxT]
-    int* sync_cnt = nullptr;            // [2][nrg] arrival counters of the update role's cooperative dense apply
-    double* stat_out = nullptr;         // [kStatGrid][kNStat]
-    double* host_buf = nullptr;         // pinned staging for fin_out + stat_out + counters
-    double* prep_d = nullptr;           // [kPrepD][p] per-sweep marker constants (k_prepare)
-    float*  prep_f = nullptr;           // [kPrepF][p]
-    double* mt2_tab = nullptr;          // sampler II, <= 3 traits: [2^t * (t(t+1)/2 + 1)][p] state tables
-    float*  tsec = nullptr;             // Rule T (section_solve): the section inverses of the current sweep, [sections][(64 t)^2]
-    size_t  tsec_cap = 0;               // ... capacity in floats
-    unsigned long long* xch = nullptr;  // Rule T: [kMaxT][256] {value, tag} words: the sampler workgroup's hand-over to the helper workgroup
-    int     xch_epoch = 0;              // ... grows by 8 per launch
-    float*  Xout = nullptr;             // output (EBV) rows: [p][ld_out] fp32, Mi.output_genotypes (tools4genotypes.jl:290-296)
-    int64_t n_out = 0, ld_out = 0;
-    float*  var_vec = nullptr;
-    float*  var_mat = nullptr;          // p x t x t per-marker effect covariances (multi-trait BayesA/B), uploaded per sweep
-    float*  ginv_mat = nullptr;         // their inverses (k_prepare)
-    bool    var_mat_resident = false;   // var_mat holds this chain's per-marker covariances (uploaded or drawn on the device)
-    double* pi_vec = nullptr;
-    double* pi_mat = nullptr;
-    double* lpr_mat = nullptr;          // p x 2^t marker-specific multi-trait log priors
-    bool    lpr_active = false;         // ... in use by the current sweep
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    int timing_stride = 0;
-    double last_events = -1.0;          // effect changes of the previous sweep (-1: none yet)
-    unsigned long long last_counters[kNCounters] = {};      // the sampler's diagnostics counters of the previous sweep
-    uint32_t last_schedule = 0;         // JWAS_HIP_SCHED_* bits of the last sweep sweep_enqueue put on the stream
-    double event_overhead_ms = 0.0;     // mean HIP-event interval around an empty launch (calibration)
-    std::vector<hipEvent_t> kev;        // pairs of events around sampled k_update_partial launches
-    // marker-shard reconcile (jwas_hip_comm_init / jwas_hip_sweep_sharded): RCCL communicator on this context's device
-    int32_t* cmp_idx = nullptr;         // [p] + [1] compacted nonzero effects of one trait (k_compact_alpha)
-    float* cmp_val = nullptr;           // [p]
-    void* comm = nullptr;               // ncclComm_t
-    int comm_rank = 0, comm_world = 1;
-    float* r_snap = nullptr;            // [kMaxT][ld] residual snapshot of the running sweep
-    double* shard_buf = nullptr;        // [kMaxT*ld + kShardStats] delta r (fp64) + packed marker statistics: ONE all-reduce
-    // exact ROW shards (jwas_hip_comm_row_shards): this context holds a slice of the individuals and ALL markers; x'x, the
-    // Grams and every block's partial RHS are summed over the ranks, the sampler then runs replicated
-    bool row_mode = false;
-    int loop_slot = -1;                 // >= 0: loopback transport (ranks = contexts of one process on different host threads)
-    double* row_buf = nullptr;          // [32] small exchanges
-    // Float64 mode (runMCMC(double_precision=true); csrc/f64_path.hpp): its own storage / state, created by jwas_hip_set_precision
-    struct F64 {
-        double* X = nullptr;                // [p][ld]
-        double* r = nullptr;                // [kMaxT][ld]
-        double* xpx = nullptr;              // [p]
-        double* gram = nullptr;             // [nblocks][bs][bs]
-        double *alpha = nullptr, *beta = nullptr;      // [t][p]
-        void* delta = nullptr;              // double [t][p], or int32 [p] (BayesR classes)
-        double *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;
-        double* partials = nullptr;         // [kMaxT][nslices][bstride]  (independent blocks: one such set per block)
-        size_t partials_cap = 0;            // ... in doubles
-        jw64::Events64* ev = nullptr;       // [2]  (independent blocks: ev_all, one per block)
-        jw64::Events64* ev_all = nullptr;
-        int64_t ev_all_cap = 0;
-        jw64::Params64* dparams = nullptr;
-        double* var_vec = nullptr;          // [p] BayesB
-        double* var_mat = nullptr;          // [p][t][t] multi-trait BayesA/B: per-marker effect covariances
-        double* ginv_mat = nullptr;         // [p][t][t] their inverses (k64_invert_marker_cov, once per sweep)
-        bool var_mat_resident = false;      // var_mat holds this chain's covariances (uploaded or drawn on the device)
-        double* w = nullptr;                // [ld] residual weights R^-1 (pad rows 0; ones when unweighted)
-        std::vector<int64_t> starts;        // block starts (nblocks + 1 entries, 0-based): uniform or explicit partition
-        int bstride = 0;                    // largest block of the partition, rounded up to a multiple of 8
-        bool explicit_part = false;
-        double* Xout = nullptr;             // [p][ld_out] output rows (jwas_hip_load_output_dense_f64)
-        int64_t n_out = 0, ld_out = 0;
-        int32_t* cmp_idx = nullptr;         // [p] + [1] compacted nonzero effects of one trait (k64_compact_alpha)
-        double* cmp_val = nullptr;          // [p]
-    };
-    F64* f64 = nullptr;
-    // GWAS session (jwas_hip_gwas_begin .. jwas_hip_gwas_end; GWAS.jl:149-173): everything a saved sample needs stays resident
-    struct Gwas {
-        bool active = false, local_ebv = false, out_rows = false;
-        int nwin = 0, wpc = 1, nchunks = 0, nsl = 0;       // launch geometry: grid = (nsl, nchunks), wpc windows per chunk
-        int64_t n_rows = 0, ld = 0, nsamples = 0;
-        const void* mat = nullptr;                          // the matrix the session was begun on (a reload ends the session)
-        int32_t *cs = nullptr, *ce = nullptr;               // [nwin] column ranges
-        int32_t *lo = nullptr, *hi = nullptr;               // [nwin + 1] the sample's list slice of every entry
-        int32_t* idx = nullptr; void* val = nullptr;        // [cap] the sample's nonzero effects (float | double)
-        int64_t cap = 0;
-        double *part = nullptr, *out = nullptr;             // [nwin + 1][nsl][2] slice partials, [2][nwin + 1] sums
-        double* acc = nullptr;                              // [nwin][ld] running sum of the local EBVs (window-major)
-        double* host_out = nullptr;                         // pinned [2][nwin + 1]
-    } gw;
-    // Liability state of threshold / censored traits (jwas_hip_liability_begin .. _end; categorical_and_censored_trait.jl)
-    struct Liab {
-        bool active = false, inited = false;
-        int nt = 0, nparts = 0;
-        int kind[jwl::kMaxT] = {}, ncat[jwl::kMaxT] = {};
-        void* y[jwl::kMaxT] = {};                           // [ld] liabilities, the context's element type
-        int32_t* codes[jwl::kMaxT] = {};                    // [n] categories (0 = missing)
-        double *lower[jwl::kMaxT] = {}, *upper[jwl::kMaxT] = {};      // [n] bounds of a censored trait
-        double* thr = nullptr;                              // [kMaxT][kMaxThr] threshold tables (device) ...
-        double thr_host[jwl::kMaxT][jwl::kMaxThr] = {};     // ... and their host copy
-        double* part[jwl::kMaxT] = {};                      // [nparts][kMM] per-workgroup {max, min} of every category
-        bool part_valid[jwl::kMaxT] = {};                   // ... left by the last draw and still describing the liabilities
-        double* mm = nullptr;                               // [kMM] reduced
-    } lb;
-    // Location parameters (jwas_hip_locpar_begin .. _end; MCMC_BayesianAlphabet.jl:193-220, solver.jl:143-162; csrc/locpar.hpp)
-    struct Locpar {
-        struct Term {
-            int trait = 0, group = -1, pos = 0, G = 1, npieces = 0;
-            int64_t nlevels = 0, off = 0, nin = 0;
-            double* x = nullptr;                            // [n] covariate values (NULL: ones)
-            int32_t* level = nullptr;                       // [n] level of every record, -1 = none (NULL: all records in level 0)
-            int32_t* rec = nullptr;                         // [nin] records sorted by (level, record) (NULL: 0 .. n - 1)
-            double* wx = nullptr;                           // [nin] w x in that order
-            int32_t *piece_lo = nullptr, *level_piece = nullptr;      // [npieces + 1], [nlevels + 1]
-            double* d = nullptr;                            // [nlevels] sum w x^2
-        };
-        struct Group { int nmembers = 0; int term[jwp::kMaxT] = {}; int64_t nlevels = 0; };
-        struct Structure {                                  // jwas_hip_lp_set_group_structure: V of a random effect, coloured
-            bool set = false;
-            int64_t nlevels = 0, nnz = 0;
-            int ncolors = 0, nwg = 0;                       // nwg: workgroups of k_locpar_quad_rows
-            std::vector<int32_t> color;                     // [nlevels] colour of every level
-            std::vector<int32_t> color_lo, nshort;          // colour c: lv[color_lo[c] .. color_lo[c + 1]), its first nshort[c] the short rows
-            int64_t* rowptr = nullptr;                      // [nlevels + 1]
-            int32_t* col = nullptr;                         // [nnz]
-            double* val = nullptr;                          // [nnz]
-            int32_t* lv = nullptr;                          // [nlevels] the levels colour by colour
-            double* qpart = nullptr;                        // [nwg][kMaxPairs]
-        };
-        bool active = false, finalized = false;
-        int nt = 0, ngroups = 0;
-        std::vector<double> w_host;                         // [n] the residual weights in force at _begin
-        std::vector<Term> terms;
-        Group groups[jwp::kMaxGroups];
-        Structure structs[jwp::kMaxGroups];
-        int64_t q = 0;                                      // entries of sol
-        double *sol = nullptr, *mean = nullptr, *mean2 = nullptr;     // [q]
-        double *part = nullptr, *delta = nullptr;           // [max npieces], [max nlevels] scratch of the running term
-        double* part2 = nullptr;                            // [max npieces] the piece sums of D under per-record weights (first such step)
-        int64_t maxp = 1;
-        int64_t* cross_offs = nullptr;                      // [kMaxGroups][16][2] member offsets of every cross-product
-        double* cross_out = nullptr;                        // [kMaxGroups][16]
-    } lp;
-    // Multi-trait records that miss some traits (jwas_hip_mtmiss_begin .. _end; residual.jl:2-73; csrc/mtmiss.hpp)
-    struct Mtmiss {
-        bool active = false, weights = false;               // weights: jwas_hip_locpar_step uses the per-record Ri
-        int nt = 0;
-        int32_t* code = nullptr;                            // [n] the pattern of every record
-        double* tab = nullptr;                              // [3][kMaxCodes * 16] the tables B, U, C (each [2^t][t][t] at its start)
-    } mt;
-    // Marker-annotation priors (jwas_hip_annot_begin .. _end; MCMC/annotation_updates.jl; csrc/annot.hpp).  The table lives in
-    // pi_vec / pi_mat / lpr_mat above: where the sweep reads it.
-    struct Annot {
-        bool active = false;
-        int kind = 0, nsteps = 0, K = 0, npieces = 0;
-        double* D = nullptr;                                // [K - 1][p] the design matrix without its column of ones
-        double *liab = nullptr, *mu = nullptr;              // [nsteps][p]
-        double* e = nullptr;                                // [p] the latent residual of the running step
-        double *part = nullptr, *part4 = nullptr;           // [npieces][3] piece sums of a coefficient, [npieces][4] of the table's columns
-        double* scal = nullptr;                             // coef [3][K] | n_A [3] | column means [4] | c_k - c_k' [1] | dsq [K]
-        double *mean = nullptr, *mean2 = nullptr;           // [table size] running means of the prior probabilities
-    } an;
-    // Structural equation model (jwas_hip_sem_begin .. _end; structure_equation_model/SEM.jl; csrc/sem.hpp)
-    struct Sem {
-        bool active = false;
-        int nt = 0, G = 0;
-        uint32_t mask = 0, ymask = 0, rmask = 0;            // bit cell(i, j): cs[i][j]; bit k: trait k is a parent / has parents
-        double* y = nullptr;                                // [nt][n] the phenotypes
-        double* part = nullptr;                             // [G][kGramCells] workgroup partials (the step uses kMaxPairs of every row)
-        double* S = nullptr;                                // [16] y y'
-        double* rec = nullptr;                              // [kRecSize] lambda | d | mu | C
-        double* acc = nullptr;                              // [2][3][nt][p] indirect | overall: mean, mean of squares, frequency
-    } sm;
-};
+static_assert(jwas_hip_ctx::kCounters == kNCounters, "counter count mismatch");
 
 static constexpr int kStatGrid = 128;
 static int row_allreduce(jwas_hip_ctx* c, void* dev, size_t count, bool f64);      // exact row shards: sum over the ranks
 static thread_local std::string g_create_error;
 
-static int fail(jwas_hip_ctx* ctx, int code, const char* fmt, ...)
+int fail(jwas_hip_ctx* ctx, int code, const char* fmt, ...)      // (declared in ctx.hpp: the one definition every unit calls)
 {
     char buf[512];
     va_list ap;
@@ -271,42 +42,6 @@ static int fail(jwas_hip_ctx* ctx, int code, const char* fmt, ...)
     return code;
 }
 
-#define HIPCHK(ctx, call)                                                                          \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail((ctx), JWAS_HIP_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                       \
-    } while (0)
-
-#define NEED(ctx, cond, code, ...)                                                                 \
-    do { if (!(cond)) return fail((ctx), (code), __VA_ARGS__); } while (0)
-
-static int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-// t x t inverse: double Gauss-Jordan with partial pivoting, rounded to float (stands in for Julia's
-// inv(::Matrix{Float32}), MTBayesABC.jl:66-67).  Same operation sequence as the oracle's.
-static int inv_small(const float* A, int t, float* Ainv)
-{
-    double M[kMaxT][2 * kMaxT];
-    for (int i = 0; i < t; ++i)
-        for (int j = 0; j < t; ++j) { M[i][j] = A[i * t + j]; M[i][t + j] = (i == j); }
-    for (int c = 0; c < t; ++c) {
-        int piv = c;
-        for (int i = c + 1; i < t; ++i) if (std::fabs(M[i][c]) > std::fabs(M[piv][c])) piv = i;
-        if (M[piv][c] == 0.0) return -1;
-        if (piv != c) for (int j = 0; j < 2 * t; ++j) { double tmp = M[c][j]; M[c][j] = M[piv][j]; M[piv][j] = tmp; }
-        const double d = M[c][c];
-        for (int j = 0; j < 2 * t; ++j) M[c][j] /= d;
-        for (int i = 0; i < t; ++i) if (i != c) {
-            const double f = M[i][c];
-            if (f != 0.0) for (int j = 0; j < 2 * t; ++j) M[i][j] -= f * M[c][j];
-        }
-    }
-    for (int i = 0; i < t; ++i) for (int j = 0; j < t; ++j) Ainv[i * t + j] = (float)M[i][t + j];
-    return 0;
-}
-
 // Run f(cols) with the accessor of the context's storage (columns from j_off on).
 template <class F>
 static auto with_cols(jwas_hip_ctx* c, int64_t j_off, F&& f)
@@ -315,9 +50,6 @@ static auto with_cols(jwas_hip_ctx* c, int64_t j_off, F&& f)
     return f(DenseCols{c->X + j_off * c->ld, c->ld, c->w, (int32_t)c->weighted});
 }
 #define HAVE_STORAGE(c) ((c)->X != nullptr || (c)->Q != nullptr)
-#define IS_F64(c) ((c)->f64 != nullptr)
-#define NOT_F64(c, what) NEED(c, !IS_F64(c), JWAS_HIP_EUNSUP, "%s is not available in a Float64 context (double_precision=true)", what)
-#define ONLY_F64(c) NEED(c, IS_F64(c), JWAS_HIP_ESTATE, "this entry point needs a Float64 context (jwas_hip_set_precision(ctx, 64))")
 static int f64_setup_blocks(jwas_hip_ctx* c, int32_t bs);
 static int f64_setup_blocks_explicit(jwas_hip_ctx* c, const int64_t* starts, int64_t nblocks);
 static int f64_set_weights(jwas_hip_ctx* c, const float* rinv32, const double* rinv64);
@@ -389,46 +121,6 @@ static void gwas_free(jwas_hip_ctx* c)
     for (void* q : {(void*)g.cs, (void*)g.ce, (void*)g.lo, (void*)g.hi, (void*)g.idx, g.val, (void*)g.part, (void*)g.out, (void*)g.acc}) (void)hipFree(q);
     if (g.host_out) (void)hipHostFree(g.host_out);
     g = jwas_hip_ctx::Gwas();
-}
-
-static void liab_free(jwas_hip_ctx* c)
-{
-    auto& b = c->lb;
-    for (int k = 0; k < jwl::kMaxT; ++k)
-        for (void* q : {b.y[k], (void*)b.codes[k], (void*)b.lower[k], (void*)b.upper[k], (void*)b.part[k]}) (void)hipFree(q);
-    (void)hipFree(b.thr); (void)hipFree(b.mm);
-    b = jwas_hip_ctx::Liab();
-}
-
-static void locpar_free(jwas_hip_ctx* c)
-{
-    auto& b = c->lp;
-    for (auto& t : b.terms)
-        for (void* q : {(void*)t.x, (void*)t.level, (void*)t.rec, (void*)t.wx, (void*)t.piece_lo, (void*)t.level_piece, (void*)t.d}) (void)hipFree(q);
-    for (void* q : {(void*)b.sol, (void*)b.mean, (void*)b.mean2, (void*)b.part, (void*)b.part2, (void*)b.delta, (void*)b.cross_offs, (void*)b.cross_out}) (void)hipFree(q);
-    for (auto& v : b.structs)
-        for (void* q : {(void*)v.rowptr, (void*)v.col, (void*)v.val, (void*)v.lv, (void*)v.qpart}) (void)hipFree(q);
-    b = jwas_hip_ctx::Locpar();
-}
-
-static void mtmiss_free(jwas_hip_ctx* c)
-{
-    (void)hipFree(c->mt.code); (void)hipFree(c->mt.tab);
-    c->mt = jwas_hip_ctx::Mtmiss();
-}
-
-static void annot_free(jwas_hip_ctx* c)
-{
-    auto& b = c->an;
-    for (void* q : {(void*)b.D, (void*)b.liab, (void*)b.mu, (void*)b.e, (void*)b.part, (void*)b.part4, (void*)b.scal, (void*)b.mean, (void*)b.mean2}) (void)hipFree(q);
-    b = jwas_hip_ctx::Annot();
-}
-
-static void sem_free(jwas_hip_ctx* c)
-{
-    auto& b = c->sm;
-    for (void* q : {(void*)b.y, (void*)b.part, (void*)b.S, (void*)b.rec, (void*)b.acc}) (void)hipFree(q);
-    b = jwas_hip_ctx::Sem();
 }
 
 static void free_storage(jwas_hip_ctx* c)
@@ -3475,1287 +3167,6 @@ int jwas_hip_get_posterior(jwas_hip_ctx* c, int32_t trait, float* ma, float* ma2
     if (ma2) HIPCHK(c, hipMemcpyAsync(ma2, c->mean_a2 + off, nb, hipMemcpyDeviceToHost, c->stream));
     if (md) HIPCHK(c, hipMemcpyAsync(md, c->mean_d + off, nb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-}  // extern "C"
-
-// ---- threshold / censored traits: the liabilities (csrc/liability.hpp) -----------------------------------------------------
-static void* liab_residual(jwas_hip_ctx* c) { return IS_F64(c) ? (void*)c->f64->r : (void*)c->r; }
-
-#define NEED_LIAB(c)                                                                                                   \
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
-    NEED(c, c->lb.active, JWAS_HIP_ESTATE, "jwas_hip_liability_begin has not been called");                            \
-    NEED(c, liab_residual(c) && c->method >= 0 && c->ntraits == c->lb.nt, JWAS_HIP_ESTATE,                              \
-         "jwas_hip_init_state changed the number of traits after jwas_hip_liability_begin")
-#define NEED_LIAB_TRAIT(c, trait) NEED(c, trait >= 0 && trait < c->lb.nt, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->lb.nt)
-
-static int liab_check_thresholds(jwas_hip_ctx* c, int32_t nthr, const double* thr)
-{
-    NEED(c, thr, JWAS_HIP_EINVAL, "thresholds is NULL");
-    NEED(c, nthr >= 3 && nthr <= jwl::kMaxThr, JWAS_HIP_EINVAL, "nthresholds must be 3..%d, -Inf and +Inf included (got %d)", jwl::kMaxThr, nthr);
-    NEED(c, thr[0] == -INFINITY && thr[nthr - 1] == INFINITY, JWAS_HIP_EINVAL, "thresholds must start with -Inf and end with +Inf");
-    for (int i = 1; i < nthr; ++i)
-        NEED(c, thr[i] > thr[i - 1], JWAS_HIP_EINVAL, "thresholds must be strictly increasing (entry %d: %g after %g)", i, thr[i], thr[i - 1]);
-    return JWAS_HIP_OK;
-}
-
-// (re)allocate the liability vector of a trait and drop what an earlier declaration of it left
-static int liab_reset_trait(jwas_hip_ctx* c, int trait)
-{
-    auto& b = c->lb;
-    for (void* q : {(void*)b.codes[trait], (void*)b.lower[trait], (void*)b.upper[trait], (void*)b.part[trait]}) (void)hipFree(q);
-    b.codes[trait] = nullptr; b.lower[trait] = b.upper[trait] = nullptr; b.part[trait] = nullptr; b.part_valid[trait] = false;
-    b.kind[trait] = jwl::kContinuous; b.ncat[trait] = 0;
-    if (!b.y[trait]) HIPCHK(c, hipMalloc(&b.y[trait], (IS_F64(c) ? 8 : 4) * (size_t)c->ld));
-    return JWAS_HIP_OK;
-}
-
-static int liab_upload_placeholder(jwas_hip_ctx* c, int trait, const std::vector<double>& y0)
-{
-    auto& b = c->lb;
-    if (IS_F64(c)) {
-        HIPCHK(c, hipMemcpyAsync(b.y[trait], y0.data(), 8 * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else {
-        std::vector<float> y32(y0.begin(), y0.end());
-        HIPCHK(c, hipMemcpyAsync(b.y[trait], y32.data(), 4 * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return JWAS_HIP_OK;
-}
-
-// n x n inverse (n <= 3) in double: Gauss-Jordan with partial pivoting, the operation sequence of inv_small
-static int inv_small_f64(const double* A, int n, double* Ainv)
-{
-    double M[kMaxT][2 * kMaxT];
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) { M[i][j] = A[i * n + j]; M[i][n + j] = (i == j); }
-    for (int col = 0; col < n; ++col) {
-        int piv = col;
-        for (int i = col + 1; i < n; ++i) if (std::fabs(M[i][col]) > std::fabs(M[piv][col])) piv = i;
-        if (M[piv][col] == 0.0) return -1;
-        if (piv != col) for (int j = 0; j < 2 * n; ++j) { double tmp = M[col][j]; M[col][j] = M[piv][j]; M[piv][j] = tmp; }
-        const double d = M[col][col];
-        for (int j = 0; j < 2 * n; ++j) M[col][j] /= d;
-        for (int i = 0; i < n; ++i) if (i != col) {
-            const double f = M[i][col];
-            if (f != 0.0) for (int j = 0; j < 2 * n; ++j) M[i][j] -= f * M[col][j];
-        }
-    }
-    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) Ainv[i * n + j] = M[i][n + j];
-    return 0;
-}
-
-template <class T>
-static void liab_launch(jwas_hip_ctx* c, const jwl::LiabArgs& A)
-{
-    const dim3 grid((unsigned)c->lb.nparts), block(256);
-    switch (c->lb.nt) {
-        case 1: hipLaunchKernelGGL((jwl::k_liability_sample<1, T>), grid, block, 0, c->stream, A); break;
-        case 2: hipLaunchKernelGGL((jwl::k_liability_sample<2, T>), grid, block, 0, c->stream, A); break;
-        case 3: hipLaunchKernelGGL((jwl::k_liability_sample<3, T>), grid, block, 0, c->stream, A); break;
-        default: hipLaunchKernelGGL((jwl::k_liability_sample<4, T>), grid, block, 0, c->stream, A); break;
-    }
-}
-
-static int liab_draw(jwas_hip_ctx* c, const jwas_liability_params* P, bool init, const char* who)
-{
-    NEED_LIAB(c);
-    NEED(c, P, JWAS_HIP_EINVAL, "params is NULL");
-    auto& b = c->lb;
-    const int t = b.nt;
-    NEED(c, init || b.inited, JWAS_HIP_ESTATE, "jwas_hip_liability_init has not been called");
-    NEED(c, init || P->iteration >= 1, JWAS_HIP_EINVAL, "%s: iteration must be >= 1 (0 is the set-up draw)", who);
-    NEED(c, init || (P->ngibbs >= 1 && P->ngibbs <= 1000), JWAS_HIP_EINVAL, "%s: ngibbs must be 1..1000 (got %d)", who, P->ngibbs);
-    int nliab = 0;
-    for (int k = 0; k < t; ++k) nliab += b.kind[k] != jwl::kContinuous;
-    NEED(c, nliab > 0, JWAS_HIP_ESTATE, "%s: no trait was declared categorical or censored", who);
-    jwl::LiabArgs A = {};
-    for (int k = 0; k < t; ++k) {
-        for (int j = 0; j < t; ++j)
-            NEED(c, std::isfinite(P->R[k * t + j]) && P->R[k * t + j] == P->R[j * t + k], JWAS_HIP_EINVAL, "%s: R must be finite and symmetric", who);
-        double var = P->R[k * t + k];
-        if (!init && t > 1) {                     // B = R_12 R_22^-1, s^2 = R_11 - R_12 R_22^-1 R_21 (:196-197), "2" = the other traits in order
-            double R22[9], R22i[9], R12[3];
-            int o[3], m = 0;
-            for (int j = 0; j < t; ++j) if (j != k) o[m++] = j;
-            for (int a = 0; a < m; ++a) { R12[a] = P->R[k * t + o[a]]; for (int e = 0; e < m; ++e) R22[a * m + e] = P->R[o[a] * t + o[e]]; }
-            NEED(c, inv_small_f64(R22, m, R22i) == 0, JWAS_HIP_EINVAL, "%s: R is singular", who);
-            for (int a = 0; a < m; ++a) {
-                double acc = 0.0;
-                for (int e = 0; e < m; ++e) acc += R12[e] * R22i[e * m + a];
-                A.B[k][o[a]] = acc;
-            }
-            for (int a = 0; a < m; ++a) var -= A.B[k][o[a]] * R12[a];
-        }
-        NEED(c, var > 0.0 && std::isfinite(var), JWAS_HIP_EINVAL, "%s: R is not positive definite (conditional variance of trait %d: %g)", who, k, var);
-        A.sd[k] = std::sqrt(var);
-    }
-    A.n = c->n; A.ld = c->ld; A.r = liab_residual(c); A.thr = b.thr;
-    for (int k = 0; k < t; ++k) {
-        A.kind[k] = b.kind[k]; A.ncat[k] = b.ncat[k];
-        A.y[k] = b.kind[k] != jwl::kContinuous ? b.y[k] : nullptr;
-        A.codes[k] = b.codes[k]; A.lower[k] = b.lower[k]; A.upper[k] = b.upper[k];
-        A.part[k] = b.kind[k] == jwl::kCategorical ? b.part[k] : nullptr;
-    }
-    A.ngibbs = init ? 1 : P->ngibbs; A.init = init ? 1 : 0;
-    A.iter = init ? 0u : P->iteration; A.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); A.seed_hi = (uint32_t)(P->seed >> 32);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (IS_F64(c)) liab_launch<double>(c, A); else liab_launch<float>(c, A);
-    HIPCHK(c, hipGetLastError());
-    for (int k = 0; k < t; ++k) b.part_valid[k] = A.part[k] != nullptr;
-    if (init) b.inited = true;
-    return JWAS_HIP_OK;
-}
-
-extern "C" {
-
-int jwas_hip_liability_begin(jwas_hip_ctx* c, int32_t ntraits)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no residual: load genotypes and call jwas_hip_init_state first");
-    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "liabilities are not driven from marker or row shards");
-    NEED(c, ntraits == c->ntraits, JWAS_HIP_EINVAL, "ntraits (%d) differs from jwas_hip_init_state's (%d)", ntraits, c->ntraits);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    liab_free(c);
-    auto& b = c->lb;
-    b.nt = ntraits;
-    b.nparts = (int)((c->n + 255) / 256);
-    HIPCHK(c, hipMalloc(&b.thr, sizeof(double) * jwl::kMaxT * jwl::kMaxThr));
-    HIPCHK(c, hipMalloc(&b.mm, sizeof(double) * jwl::kMM));
-    HIPCHK(c, hipMemset(b.thr, 0, sizeof(double) * jwl::kMaxT * jwl::kMaxThr));
-    b.active = true;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_liability_set_categorical(jwas_hip_ctx* c, int32_t trait, int64_t n, const int32_t* codes, int32_t nthr, const double* thr)
-{
-    NEED_LIAB(c);
-    NEED_LIAB_TRAIT(c, trait);
-    NEED(c, codes, JWAS_HIP_EINVAL, "codes is NULL");
-    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
-    if (int rc = liab_check_thresholds(c, nthr, thr)) return rc;
-    const int ncat = nthr - 1;
-    for (int64_t i = 0; i < n; ++i)
-        NEED(c, codes[i] >= 0 && codes[i] <= ncat, JWAS_HIP_EINVAL, "record %lld: category %d outside 0..%d", (long long)i, codes[i], ncat);
-    auto& b = c->lb;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (int rc = liab_reset_trait(c, trait)) return rc;
-    HIPCHK(c, hipMalloc(&b.codes[trait], 4 * (size_t)n));
-    HIPCHK(c, hipMalloc(&b.part[trait], sizeof(double) * (size_t)b.nparts * jwl::kMM));
-    HIPCHK(c, hipMemcpy(b.codes[trait], codes, 4 * (size_t)n, hipMemcpyHostToDevice));
-    std::memcpy(b.thr_host[trait], thr, sizeof(double) * nthr);
-    HIPCHK(c, hipMemcpy(b.thr + trait * jwl::kMaxThr, thr, sizeof(double) * nthr, hipMemcpyHostToDevice));
-    std::vector<double> y0((size_t)n);
-    for (int64_t i = 0; i < n; ++i) y0[(size_t)i] = (double)codes[i];
-    if (int rc = liab_upload_placeholder(c, trait, y0)) return rc;
-    b.kind[trait] = jwl::kCategorical; b.ncat[trait] = ncat; b.inited = false;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_liability_set_censored(jwas_hip_ctx* c, int32_t trait, int64_t n, const double* lower, const double* upper)
-{
-    NEED_LIAB(c);
-    NEED_LIAB_TRAIT(c, trait);
-    NEED(c, lower && upper, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
-    for (int64_t i = 0; i < n; ++i)
-        NEED(c, lower[i] <= upper[i] && lower[i] < INFINITY && upper[i] > -INFINITY, JWAS_HIP_EINVAL,
-             "record %lld: bounds [%g, %g] (lower > upper, NaN, or an infinite exact value)", (long long)i, lower[i], upper[i]);
-    auto& b = c->lb;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (int rc = liab_reset_trait(c, trait)) return rc;
-    HIPCHK(c, hipMalloc(&b.lower[trait], 8 * (size_t)n));
-    HIPCHK(c, hipMalloc(&b.upper[trait], 8 * (size_t)n));
-    HIPCHK(c, hipMemcpy(b.lower[trait], lower, 8 * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(b.upper[trait], upper, 8 * (size_t)n, hipMemcpyHostToDevice));
-    std::vector<double> y0((size_t)n);
-    for (int64_t i = 0; i < n; ++i) y0[(size_t)i] = lower[i] == -INFINITY ? (upper[i] == INFINITY ? 0.0 : upper[i]) : lower[i];
-    if (int rc = liab_upload_placeholder(c, trait, y0)) return rc;
-    b.kind[trait] = jwl::kCensored; b.inited = false;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_liability_set_thresholds(jwas_hip_ctx* c, int32_t trait, int32_t nthr, const double* thr)
-{
-    NEED_LIAB(c);
-    NEED_LIAB_TRAIT(c, trait);
-    auto& b = c->lb;
-    NEED(c, b.kind[trait] == jwl::kCategorical, JWAS_HIP_ESTATE, "trait %d is not categorical", trait);
-    NEED(c, nthr == b.ncat[trait] + 1, JWAS_HIP_EINVAL, "trait %d has %d thresholds (got %d)", trait, b.ncat[trait] + 1, nthr);
-    if (int rc = liab_check_thresholds(c, nthr, thr)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::memcpy(b.thr_host[trait], thr, sizeof(double) * nthr);
-    // (from the context's own copy: the caller's array need not outlive the call)
-    HIPCHK(c, hipMemcpyAsync(b.thr + trait * jwl::kMaxThr, b.thr_host[trait], sizeof(double) * nthr, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_liability_init(jwas_hip_ctx* c, const jwas_liability_params* P) { return liab_draw(c, P, true, "jwas_hip_liability_init"); }
-
-int jwas_hip_liability_sample(jwas_hip_ctx* c, const jwas_liability_params* P) { return liab_draw(c, P, false, "jwas_hip_liability_sample"); }
-
-int jwas_hip_liability_minmax(jwas_hip_ctx* c, int32_t trait, double* max_below, double* min_above)
-{
-    NEED_LIAB(c);
-    NEED_LIAB_TRAIT(c, trait);
-    NEED(c, max_below && min_above, JWAS_HIP_EINVAL, "NULL argument");
-    auto& b = c->lb;
-    NEED(c, b.kind[trait] == jwl::kCategorical, JWAS_HIP_ESTATE, "trait %d is not categorical", trait);
-    const int ncat = b.ncat[trait];
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!b.part_valid[trait]) {
-        if (IS_F64(c)) hipLaunchKernelGGL((jwl::k_liability_minmax<double>), dim3((unsigned)b.nparts), dim3(256), 0, c->stream, (const double*)b.y[trait], b.codes[trait], c->n, ncat, b.part[trait]);
-        else           hipLaunchKernelGGL((jwl::k_liability_minmax<float>), dim3((unsigned)b.nparts), dim3(256), 0, c->stream, (const float*)b.y[trait], b.codes[trait], c->n, ncat, b.part[trait]);
-        b.part_valid[trait] = true;
-    }
-    hipLaunchKernelGGL(jwl::k_liability_minmax_reduce, dim3(1), dim3(256), 0, c->stream, b.part[trait], b.nparts, ncat, b.mm);
-    HIPCHK(c, hipGetLastError());
-    double mm[jwl::kMM];
-    HIPCHK(c, hipMemcpyAsync(mm, b.mm, sizeof(double) * 2 * ncat, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    max_below[0] = min_above[0] = -INFINITY;
-    max_below[ncat] = min_above[ncat] = INFINITY;
-    for (int i = 1; i < ncat; ++i) {                // threshold i separates categories i and i + 1
-        max_below[i] = mm[2 * (i - 1)];
-        min_above[i] = mm[2 * i + 1];
-    }
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_get_liabilities(jwas_hip_ctx* c, int32_t trait, double* out)
-{
-    NEED_LIAB(c);
-    NEED_LIAB_TRAIT(c, trait);
-    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
-    auto& b = c->lb;
-    NEED(c, b.kind[trait] != jwl::kContinuous, JWAS_HIP_ESTATE, "trait %d is continuous: it has no liabilities", trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (IS_F64(c)) {
-        HIPCHK(c, hipMemcpyAsync(out, b.y[trait], 8 * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else {
-        std::vector<float> y32((size_t)c->n);
-        HIPCHK(c, hipMemcpyAsync(y32.data(), b.y[trait], 4 * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int64_t i = 0; i < c->n; ++i) out[i] = (double)y32[(size_t)i];
-    }
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_liability_end(jwas_hip_ctx* c)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    liab_free(c);
-    return JWAS_HIP_OK;
-}
-
-}  // extern "C"
-
-// ---- location parameters (csrc/locpar.hpp): MCMC_BayesianAlphabet.jl:193-220, iterative_solver/solver.jl:143-162 -------------
-#define NEED_LOCPAR(c)                                                                                                 \
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
-    NEED(c, c->lp.active, JWAS_HIP_ESTATE, "jwas_hip_locpar_begin has not been called");                               \
-    NEED(c, liab_residual(c) && c->method >= 0 && c->ntraits == c->lp.nt, JWAS_HIP_ESTATE,                              \
-         "jwas_hip_init_state changed the number of traits after jwas_hip_locpar_begin")
-
-template <class V>
-static hipError_t locpar_upload(V** dev, const std::vector<V>& host)
-{
-    hipError_t e = hipMalloc((void**)dev, sizeof(V) * std::max<size_t>(host.size(), 1));
-    if (e == hipSuccess && !host.empty()) e = hipMemcpy(*dev, host.data(), sizeof(V) * host.size(), hipMemcpyHostToDevice);
-    return e;
-}
-
-// the term's layout from level[] (NULL: every record in level 0) and x[] (NULL: ones): records sorted by (level, record), pieces of
-// at most kPiece records, the lane-group width, d = sum w x^2
-static int locpar_add_term(jwas_hip_ctx* c, int32_t trait, const double* x, const int32_t* level, int64_t nlevels, int32_t group)
-{
-    auto& b = c->lp;
-    const int64_t n = c->n;
-    jwas_hip_ctx::Locpar::Term T;
-    T.trait = trait; T.group = group; T.nlevels = nlevels;
-    std::vector<int32_t> start((size_t)nlevels + 1, 0), rec;
-    if (level) {
-        for (int64_t i = 0; i < n; ++i) if (level[i] >= 0) ++start[(size_t)level[i] + 1];
-        for (int64_t l = 0; l < nlevels; ++l) start[(size_t)l + 1] += start[(size_t)l];
-        rec.resize((size_t)start[(size_t)nlevels]);
-        std::vector<int32_t> fill(start.begin(), start.end() - 1);
-        for (int64_t i = 0; i < n; ++i) if (level[i] >= 0) rec[(size_t)fill[(size_t)level[i]]++] = (int32_t)i;      // (stable: ties by ascending record)
-    } else {
-        start[1] = (int32_t)n;
-    }
-    T.nin = start[(size_t)nlevels];
-    std::vector<double> wx((size_t)T.nin), d((size_t)nlevels, 0.0);
-    std::vector<int32_t> piece_lo, level_piece((size_t)nlevels + 1, 0);
-    for (int64_t l = 0; l < nlevels; ++l) {
-        for (int32_t j = start[(size_t)l]; j < start[(size_t)l + 1]; ++j) {
-            const int64_t i = level ? rec[(size_t)j] : j;
-            const double xi = x ? x[i] : 1.0;
-            wx[(size_t)j] = b.w_host[(size_t)i] * xi;
-            d[(size_t)l] = d[(size_t)l] + wx[(size_t)j] * xi;
-        }
-        for (int32_t j = start[(size_t)l]; j < start[(size_t)l + 1]; j += jwp::kPiece) piece_lo.push_back(j);
-        level_piece[(size_t)l + 1] = (int32_t)piece_lo.size();
-    }
-    T.npieces = (int)piece_lo.size();
-    piece_lo.push_back((int32_t)T.nin);
-    // (pieces of different levels are adjacent in the sorted order: piece p ends where piece p + 1 starts)
-    const int64_t avg = T.npieces ? (T.nin + T.npieces - 1) / T.npieces : 1;
-    T.G = 1;
-    while (T.G < 64 && T.G < avg) T.G <<= 1;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipError_t e = hipSuccess;
-    if (x) { std::vector<double> xv(x, x + n); e = locpar_upload(&T.x, xv); }
-    if (level && e == hipSuccess) {
-        std::vector<int32_t> lv(level, level + n);
-        e = locpar_upload(&T.level, lv);
-        if (e == hipSuccess) e = locpar_upload(&T.rec, rec);
-    }
-    if (e == hipSuccess) e = locpar_upload(&T.wx, wx);
-    if (e == hipSuccess) e = locpar_upload(&T.piece_lo, piece_lo);
-    if (e == hipSuccess) e = locpar_upload(&T.level_piece, level_piece);
-    if (e == hipSuccess) e = locpar_upload(&T.d, d);
-    if (e != hipSuccess) {                                  // (nothing of a term that was not added stays behind)
-        for (void* q : {(void*)T.x, (void*)T.level, (void*)T.rec, (void*)T.wx, (void*)T.piece_lo, (void*)T.level_piece, (void*)T.d}) (void)hipFree(q);
-        return fail(c, JWAS_HIP_EHIP, "uploading the term's layout failed: %s", hipGetErrorString(e));
-    }
-    T.off = b.q;
-    if (group >= 0) {
-        auto& g = b.groups[group];
-        T.pos = g.nmembers;
-        g.term[g.nmembers++] = (int)b.terms.size();
-        g.nlevels = nlevels;
-        b.ngroups = std::max(b.ngroups, group + 1);
-    }
-    b.q += nlevels;
-    b.terms.push_back(T);
-    return JWAS_HIP_OK;
-}
-
-static int locpar_check_add(jwas_hip_ctx* c, int32_t trait, int64_t n)
-{
-    NEED_LOCPAR(c);
-    NEED(c, !c->lp.finalized, JWAS_HIP_ESTATE, "terms are added before sol is first used (call jwas_hip_locpar_begin to start over)");
-    NEED(c, trait >= 0 && trait < c->lp.nt, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->lp.nt);
-    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
-    NEED(c, c->lp.terms.size() < 0x10000000u, JWAS_HIP_EINVAL, "too many terms");
-    return JWAS_HIP_OK;
-}
-
-// allocate sol, its means and the scratch of the largest term on the first use
-static int locpar_finalize(jwas_hip_ctx* c)
-{
-    auto& b = c->lp;
-    if (b.finalized) return JWAS_HIP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    int64_t maxp = 1, maxl = 1;
-    for (auto& t : b.terms) { maxp = std::max<int64_t>(maxp, t.npieces); maxl = std::max(maxl, t.nlevels); }
-    const size_t qb = sizeof(double) * (size_t)std::max<int64_t>(b.q, 1);
-    for (double** v : {&b.sol, &b.mean, &b.mean2}) { HIPCHK(c, hipMalloc((void**)v, qb)); HIPCHK(c, hipMemsetAsync(*v, 0, qb, c->stream)); }
-    HIPCHK(c, hipMalloc((void**)&b.part, sizeof(double) * (size_t)maxp));
-    b.maxp = maxp;
-    HIPCHK(c, hipMalloc((void**)&b.delta, sizeof(double) * (size_t)maxl));
-    std::vector<int64_t> offs((size_t)jwp::kMaxGroups * 32, 0);
-    for (int g = 0; g < b.ngroups; ++g)
-        for (int a = 0; a < b.groups[g].nmembers; ++a)
-            for (int e = 0; e < b.groups[g].nmembers; ++e) {
-                offs[(size_t)(g * 16 + a * b.groups[g].nmembers + e) * 2] = b.terms[(size_t)b.groups[g].term[a]].off;
-                offs[(size_t)(g * 16 + a * b.groups[g].nmembers + e) * 2 + 1] = b.terms[(size_t)b.groups[g].term[e]].off;
-            }
-    HIPCHK(c, locpar_upload(&b.cross_offs, offs));
-    HIPCHK(c, hipMalloc((void**)&b.cross_out, sizeof(double) * jwp::kMaxGroups * 16));
-    HIPCHK(c, hipMemsetAsync(b.cross_out, 0, sizeof(double) * jwp::kMaxGroups * 16, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.finalized = true;
-    return JWAS_HIP_OK;
-}
-
-extern "C" {
-
-int jwas_hip_locpar_begin(jwas_hip_ctx* c, int32_t ntraits)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no residual: load genotypes and call jwas_hip_init_state first");
-    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "location parameters are not driven from marker or row shards");
-    NEED(c, ntraits == c->ntraits, JWAS_HIP_EINVAL, "ntraits (%d) differs from jwas_hip_init_state's (%d)", ntraits, c->ntraits);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    locpar_free(c);
-    auto& b = c->lp;
-    b.nt = ntraits;
-    b.w_host.assign((size_t)c->n, 1.0);
-    if (IS_F64(c)) {
-        HIPCHK(c, hipMemcpy(b.w_host.data(), c->f64->w, sizeof(double) * (size_t)c->n, hipMemcpyDeviceToHost));
-    } else {
-        std::vector<float> w32((size_t)c->n);
-        HIPCHK(c, hipMemcpy(w32.data(), c->w, sizeof(float) * (size_t)c->n, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < c->n; ++i) b.w_host[(size_t)i] = (double)w32[(size_t)i];
-    }
-    b.active = true;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_locpar_add_covariate(jwas_hip_ctx* c, int32_t trait, int64_t n, const double* x)
-{
-    if (int rc = locpar_check_add(c, trait, n)) return rc;
-    if (x)
-        for (int64_t i = 0; i < n; ++i) NEED(c, std::isfinite(x[i]), JWAS_HIP_EINVAL, "record %lld: the covariate is not finite (%g)", (long long)i, x[i]);
-    return locpar_add_term(c, trait, x, nullptr, 1, -1);
-}
-
-int jwas_hip_locpar_add_factor(jwas_hip_ctx* c, int32_t trait, int64_t n, const int32_t* level, int64_t nlevels, int32_t group)
-{
-    if (int rc = locpar_check_add(c, trait, n)) return rc;
-    NEED(c, level, JWAS_HIP_EINVAL, "level is NULL");
-    NEED(c, nlevels >= 1 && nlevels < (int64_t)1 << 31, JWAS_HIP_EINVAL, "nlevels must be 1 .. 2^31 - 1 (got %lld)", (long long)nlevels);
-    for (int64_t i = 0; i < n; ++i)
-        NEED(c, level[i] >= -1 && level[i] < nlevels, JWAS_HIP_EINVAL, "record %lld: level %d outside -1..%lld", (long long)i, level[i], (long long)nlevels - 1);
-    NEED(c, group >= -1 && group < jwp::kMaxGroups, JWAS_HIP_EINVAL, "random_group must be -1 (fixed) or 0..%d (got %d)", jwp::kMaxGroups - 1, group);
-    if (group >= 0) {
-        const auto& g = c->lp.groups[group];
-        NEED(c, g.nmembers < jwp::kMaxT, JWAS_HIP_EINVAL, "random effect %d already has %d member terms", group, g.nmembers);
-        for (int a = 0; a < g.nmembers; ++a)
-            NEED(c, c->lp.terms[(size_t)g.term[a]].trait != trait, JWAS_HIP_EUNSUP,
-                 "random effect %d already has a term of trait %d: correlated terms within a trait stay on the reference", group, trait);
-        NEED(c, g.nmembers == 0 || g.nlevels == nlevels, JWAS_HIP_EINVAL, "the member terms of random effect %d must have the same levels (%lld, got %lld)",
-             group, (long long)g.nlevels, (long long)nlevels);
-        const auto& v = c->lp.structs[group];
-        NEED(c, !v.set || v.nlevels == nlevels, JWAS_HIP_EINVAL, "random effect %d has a structure of %lld levels (the term has %lld)", group,
-             (long long)v.nlevels, (long long)nlevels);
-    }
-    return locpar_add_term(c, trait, nullptr, level, nlevels, group);
-}
-
-int jwas_hip_locpar_size(jwas_hip_ctx* c, int64_t* out_q)
-{
-    NEED_LOCPAR(c);
-    NEED(c, out_q, JWAS_HIP_EINVAL, "NULL argument");
-    *out_q = c->lp.q;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_locpar_set_sol(jwas_hip_ctx* c, int64_t q, const double* sol)
-{
-    NEED_LOCPAR(c);
-    NEED(c, sol, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, q == c->lp.q, JWAS_HIP_EINVAL, "q (%lld) differs from the number of location parameters (%lld)", (long long)q, (long long)c->lp.q);
-    if (int rc = locpar_finalize(c)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->lp.sol, sol, sizeof(double) * (size_t)q, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_locpar_get_sol(jwas_hip_ctx* c, int64_t q, double* out)
-{
-    NEED_LOCPAR(c);
-    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, q == c->lp.q, JWAS_HIP_EINVAL, "q (%lld) differs from the number of location parameters (%lld)", (long long)q, (long long)c->lp.q);
-    if (int rc = locpar_finalize(c)) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->lp.sol, sizeof(double) * (size_t)q, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_locpar_step(jwas_hip_ctx* c, const jwas_locpar_params* P, jwas_locpar_stats* S)
-{
-    NEED_LOCPAR(c);
-    NEED(c, P, JWAS_HIP_EINVAL, "params is NULL");
-    auto& b = c->lp;
-    const int t = b.nt, nterms = (int)b.terms.size();
-    const int first = P->first_term, last = P->last_term < 0 ? nterms : P->last_term;
-    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: iteration must be >= 1");
-    NEED(c, first >= 0 && first <= last && last <= nterms, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: terms %d..%d outside 0..%d", first, last, nterms);
-    const bool pat = c->mt.weights;                             // the per-record Ri of jwas_hip_mtmiss_set_record_weights: Rinv is not read
-    if (pat) {
-        NEED(c, c->mt.active && c->mt.nt == t && t > 1, JWAS_HIP_ESTATE, "jwas_hip_init_state changed the number of traits after jwas_hip_mtmiss_begin");
-    } else if (t == 1) {
-        NEED(c, std::isfinite(P->vare) && P->vare > 0.0, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: vare must be positive and finite (got %g)", P->vare);
-    } else {
-        for (int k = 0; k < t; ++k) {
-            NEED(c, P->Rinv[k * t + k] > 0.0, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: inv(R) needs a positive diagonal");
-            for (int j = 0; j < t; ++j)
-                NEED(c, std::isfinite(P->Rinv[k * t + j]) && P->Rinv[k * t + j] == P->Rinv[j * t + k], JWAS_HIP_EINVAL, "jwas_hip_locpar_step: inv(R) must be finite and symmetric");
-        }
-    }
-    for (int g = 0; g < b.ngroups; ++g) {
-        const int kk = b.groups[g].nmembers;
-        for (int a = 0; a < kk; ++a) {
-            NEED(c, P->Gi[16 * g + a * kk + a] > 0.0, JWAS_HIP_EINVAL, "jwas_hip_locpar_step: Gi of random effect %d needs a positive diagonal", g);
-            for (int e = 0; e < kk; ++e)
-                NEED(c, std::isfinite(P->Gi[16 * g + a * kk + e]) && P->Gi[16 * g + a * kk + e] == P->Gi[16 * g + e * kk + a], JWAS_HIP_EINVAL,
-                     "jwas_hip_locpar_step: Gi of random effect %d must be finite and symmetric", g);
-        }
-    }
-    if (int rc = locpar_finalize(c)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool f64 = IS_F64(c);
-    const size_t esz = f64 ? 8 : 4;
-    if (pat && !b.part2) HIPCHK(c, hipMalloc((void**)&b.part2, sizeof(double) * (size_t)b.maxp));
-    const double* ctab = pat ? c->mt.tab + 2 * jwm::kMaxCodes * 16 : nullptr;
-    if (S) HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
-    for (int j = first; j < last; ++j) {
-        const auto& T = b.terms[(size_t)j];
-        const int k = T.trait;
-        if (T.npieces > 0) {
-            jwp::SumArgs A = {};
-            A.r = liab_residual(c); A.ld = c->ld; A.rec = T.rec; A.wx = T.wx; A.piece_lo = T.piece_lo; A.part = b.part;
-            A.npieces = T.npieces; A.G = T.G; A.nt = t; A.trait = k;
-            for (int m = 0; m < t; ++m) A.c[m] = t == 1 ? 1.0 : pat ? 0.0 : P->Rinv[k * t + m];
-            const dim3 grid((unsigned)(((int64_t)T.npieces * T.G + 255) / 256)), block(256);
-            if (pat) {
-                A.code = c->mt.code; A.ctab = ctab; A.x = T.x; A.part2 = b.part2;
-                if (f64) hipLaunchKernelGGL((jwp::k_locpar_sums<double, true>), grid, block, 0, c->stream, A);
-                else     hipLaunchKernelGGL((jwp::k_locpar_sums<float, true>), grid, block, 0, c->stream, A);
-            }
-            else if (f64) hipLaunchKernelGGL((jwp::k_locpar_sums<double>), grid, block, 0, c->stream, A);
-            else          hipLaunchKernelGGL((jwp::k_locpar_sums<float>), grid, block, 0, c->stream, A);
-        }
-        jwp::DrawArgs D = {};
-        D.part = b.part; D.level_piece = T.level_piece; D.d = T.d; D.sol = b.sol; D.delta = b.delta; D.off = T.off;
-        D.nlevels = (int32_t)T.nlevels; D.pos = T.pos; D.npartners = 0;
-        D.ckk = t == 1 ? 1.0 : pat ? 0.0 : P->Rinv[k * t + k];
-        D.s = t == 1 ? P->vare : 1.0;
-        D.part2 = pat ? b.part2 : nullptr;
-        D.prior = 0.0;
-        if (T.group >= 0) {
-            const auto& g = b.groups[T.group];
-            const int kk = g.nmembers;
-            D.npartners = kk;
-            for (int m = 0; m < kk; ++m) { D.partner_off[m] = b.terms[(size_t)g.term[m]].off; D.gi[m] = P->Gi[16 * T.group + T.pos * kk + m]; }
-            D.prior = t == 1 ? P->vare * D.gi[T.pos] : D.gi[T.pos];
-        }
-        D.iter = P->iteration; D.rep = 0x20000000u | (uint32_t)j; D.slot = 3u + 16u * (uint32_t)k;
-        D.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); D.seed_hi = (uint32_t)(P->seed >> 32);
-        if (T.group >= 0 && b.structs[T.group].set) {                   // a structured effect: colour by colour, one launch each
-            const auto& V = b.structs[T.group];
-            jwp::StructDrawArgs Q = {};
-            Q.part = D.part; Q.level_piece = D.level_piece; Q.d = D.d; Q.sol = D.sol; Q.delta = D.delta; Q.off = D.off;
-            Q.rowptr = V.rowptr; Q.col = V.col; Q.val = V.val;
-            Q.npartners = D.npartners; Q.pos = D.pos; Q.ckk = D.ckk; Q.s = D.s;
-            for (int m = 0; m < D.npartners; ++m) { Q.partner_off[m] = D.partner_off[m]; Q.p[m] = t == 1 ? P->vare * D.gi[m] : D.gi[m]; }
-            Q.iter = D.iter; Q.rep = D.rep; Q.slot = D.slot; Q.seed_lo = D.seed_lo; Q.seed_hi = D.seed_hi; Q.part2 = D.part2;
-            for (int col = 0; col < V.ncolors; ++col) {
-                Q.lv = V.lv + V.color_lo[(size_t)col];
-                Q.nshort = V.nshort[(size_t)col];
-                Q.nlong = V.color_lo[(size_t)col + 1] - V.color_lo[(size_t)col] - Q.nshort;
-                const unsigned wgs = (unsigned)((Q.nshort + 255) / 256 + (Q.nlong + 3) / 4);
-                if (pat) hipLaunchKernelGGL(jwp::k_locpar_draw_structured<true>, dim3(wgs), dim3(256), 0, c->stream, Q);
-                else     hipLaunchKernelGGL(jwp::k_locpar_draw_structured<false>, dim3(wgs), dim3(256), 0, c->stream, Q);
-            }
-        } else if (pat) {
-            hipLaunchKernelGGL(jwp::k_locpar_draw<true>, dim3((unsigned)((T.nlevels + 255) / 256)), dim3(256), 0, c->stream, D);
-        } else {
-            hipLaunchKernelGGL(jwp::k_locpar_draw<false>, dim3((unsigned)((T.nlevels + 255) / 256)), dim3(256), 0, c->stream, D);
-        }
-        char* rk = (char*)liab_residual(c) + esz * (size_t)k * (size_t)c->ld;
-        const dim3 agrid((unsigned)((c->n + 255) / 256));
-        if (f64) hipLaunchKernelGGL((jwp::k_locpar_apply<double>), agrid, dim3(256), 0, c->stream, (double*)rk, T.x, T.level, b.delta, c->n);
-        else     hipLaunchKernelGGL((jwp::k_locpar_apply<float>), agrid, dim3(256), 0, c->stream, (float*)rk, T.x, T.level, b.delta, c->n);
-    }
-    for (int g = 0; g < b.ngroups; ++g) {
-        const int kk = b.groups[g].nmembers;
-        if (kk > 0 && b.structs[g].set) {                                // U' V U
-            const auto& V = b.structs[g];
-            jwp::QuadArgs Q = {};
-            Q.sol = b.sol; Q.rowptr = V.rowptr; Q.col = V.col; Q.val = V.val; Q.part = V.qpart; Q.nlevels = (int32_t)V.nlevels; Q.k = kk;
-            for (int m = 0; m < kk; ++m) Q.member_off[m] = b.terms[(size_t)b.groups[g].term[m]].off;
-            hipLaunchKernelGGL(jwp::k_locpar_quad_rows, dim3((unsigned)V.nwg), dim3(256), 0, c->stream, Q);
-            hipLaunchKernelGGL(jwp::k_locpar_quad_reduce, dim3(1), dim3(256), 0, c->stream, V.qpart, (int32_t)V.nwg, (int32_t)kk, b.cross_out + (size_t)g * 16);
-        } else if (kk > 0)
-            hipLaunchKernelGGL(jwp::k_locpar_cross, dim3((unsigned)(kk * kk)), dim3(256), 0, c->stream, b.sol, b.cross_offs + (size_t)g * 32,
-                               (int32_t)b.groups[g].nlevels, b.cross_out + (size_t)g * 16);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (S) {
-        HIPCHK(c, hipEventRecord(c->ev_stop, c->stream));
-        std::memset(S, 0, sizeof *S);
-        HIPCHK(c, hipMemcpyAsync(S->utu, b.cross_out, sizeof(double) * jwp::kMaxGroups * 16, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-        S->step_ms = (double)ms;
-    }
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_locpar_accumulate(jwas_hip_ctx* c, double nsamples)
-{
-    NEED_LOCPAR(c);
-    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
-    if (int rc = locpar_finalize(c)) return rc;
-    auto& b = c->lp;
-    if (b.q == 0) return JWAS_HIP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(jwp::k_locpar_accumulate, dim3((unsigned)((b.q + 255) / 256)), dim3(256), 0, c->stream, b.sol, b.mean, b.mean2, b.q, nsamples);
-    HIPCHK(c, hipGetLastError());
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_locpar_get_means(jwas_hip_ctx* c, int64_t q, double* out_mean, double* out_mean2)
-{
-    NEED_LOCPAR(c);
-    NEED(c, out_mean, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, q == c->lp.q, JWAS_HIP_EINVAL, "q (%lld) differs from the number of location parameters (%lld)", (long long)q, (long long)c->lp.q);
-    if (int rc = locpar_finalize(c)) return rc;
-    HIPCHK(c, hipMemcpyAsync(out_mean, c->lp.mean, sizeof(double) * (size_t)q, hipMemcpyDeviceToHost, c->stream));
-    if (out_mean2) HIPCHK(c, hipMemcpyAsync(out_mean2, c->lp.mean2, sizeof(double) * (size_t)q, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_lp_set_group_structure(jwas_hip_ctx* c, int32_t group, int64_t nlevels, const int64_t* indptr, const int32_t* indices, const double* values)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "location parameters are not driven from marker or row shards");
-    NEED_LOCPAR(c);
-    auto& b = c->lp;
-    NEED(c, group >= 0 && group < jwp::kMaxGroups, JWAS_HIP_EINVAL, "random_group must be 0..%d (got %d)", jwp::kMaxGroups - 1, group);
-    NEED(c, !b.finalized && b.groups[group].nmembers == 0, JWAS_HIP_ESTATE,
-         "the structure of random effect %d is set before its first member term is added and before sol is first used", group);
-    NEED(c, indptr && indices && values, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, nlevels >= 1 && nlevels < (int64_t)1 << 31, JWAS_HIP_EINVAL, "nlevels must be 1 .. 2^31 - 1 (got %lld)", (long long)nlevels);
-    NEED(c, indptr[0] == 0, JWAS_HIP_EINVAL, "indptr[0] must be 0");
-    for (int64_t l = 0; l < nlevels; ++l) {
-        NEED(c, indptr[l + 1] >= indptr[l], JWAS_HIP_EINVAL, "indptr decreases at row %lld", (long long)l);
-        bool diag = false;
-        for (int64_t e = indptr[l]; e < indptr[l + 1]; ++e) {
-            NEED(c, indices[e] >= 0 && indices[e] < nlevels, JWAS_HIP_EINVAL, "row %lld: column %d outside 0..%lld", (long long)l, indices[e], (long long)nlevels - 1);
-            NEED(c, e == indptr[l] || indices[e] > indices[e - 1], JWAS_HIP_EINVAL, "row %lld: columns must be ascending without duplicates", (long long)l);
-            NEED(c, std::isfinite(values[e]), JWAS_HIP_EINVAL, "row %lld, column %d: the value is not finite", (long long)l, indices[e]);
-            if (indices[e] == l) { diag = true; NEED(c, values[e] > 0.0, JWAS_HIP_EINVAL, "row %lld: the diagonal must be positive (got %g)", (long long)l, values[e]); }
-        }
-        NEED(c, diag, JWAS_HIP_EINVAL, "row %lld has no diagonal entry", (long long)l);
-    }
-    for (int64_t l = 0; l < nlevels; ++l)                       // (every column index is in range from here on)
-        for (int64_t e = indptr[l]; e < indptr[l + 1]; ++e) {
-            const int32_t j = indices[e];
-            const int32_t* lo = indices + indptr[j];
-            const int32_t* hi = indices + indptr[j + 1];
-            const int32_t* at = std::lower_bound(lo, hi, (int32_t)l);
-            NEED(c, at != hi && *at == (int32_t)l && values[at - indices] == values[e], JWAS_HIP_EINVAL,
-                 "the structure is not symmetric at (%lld, %d)", (long long)l, j);
-        }
-    const int64_t nnz = indptr[nlevels];
-    // colours: levels in ascending order, the smallest colour no neighbour holds; then the levels of every colour, short rows first
-    jwas_hip_ctx::Locpar::Structure V;
-    V.nlevels = nlevels; V.nnz = nnz;
-    V.color.assign((size_t)nlevels, -1);
-    std::vector<int64_t> held;                                  // held[colour] == l + 1: a neighbour of l has it
-    for (int64_t l = 0; l < nlevels; ++l) {
-        for (int64_t e = indptr[l]; e < indptr[l + 1]; ++e) {
-            const int32_t cj = indices[e] != l ? V.color[(size_t)indices[e]] : -1;
-            if (cj >= 0) held[(size_t)cj] = l + 1;
-        }
-        int32_t pick = 0;
-        while (pick < (int32_t)held.size() && held[(size_t)pick] == l + 1) ++pick;
-        if (pick == (int32_t)held.size()) held.push_back(0);
-        V.color[(size_t)l] = pick;
-    }
-    V.ncolors = (int)held.size();
-    V.color_lo.assign((size_t)V.ncolors + 1, 0);
-    V.nshort.assign((size_t)V.ncolors, 0);
-    for (int64_t l = 0; l < nlevels; ++l) {
-        ++V.color_lo[(size_t)V.color[(size_t)l] + 1];
-        if (indptr[l + 1] - indptr[l] <= jwp::kLongRow) ++V.nshort[(size_t)V.color[(size_t)l]];
-    }
-    for (int q = 0; q < V.ncolors; ++q) V.color_lo[(size_t)q + 1] += V.color_lo[(size_t)q];
-    std::vector<int32_t> lv((size_t)nlevels), at_short(V.color_lo.begin(), V.color_lo.end() - 1), at_long((size_t)V.ncolors);
-    for (int q = 0; q < V.ncolors; ++q) at_long[(size_t)q] = V.color_lo[(size_t)q] + V.nshort[(size_t)q];
-    for (int64_t l = 0; l < nlevels; ++l) {
-        const size_t q = (size_t)V.color[(size_t)l];
-        lv[(size_t)(indptr[l + 1] - indptr[l] <= jwp::kLongRow ? at_short[q]++ : at_long[q]++)] = (int32_t)l;
-    }
-    V.nwg = (int)((nlevels + 255) / 256);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipError_t e = locpar_upload(&V.rowptr, std::vector<int64_t>(indptr, indptr + nlevels + 1));
-    if (e == hipSuccess) e = locpar_upload(&V.col, std::vector<int32_t>(indices, indices + nnz));
-    if (e == hipSuccess) e = locpar_upload(&V.val, std::vector<double>(values, values + nnz));
-    if (e == hipSuccess) e = locpar_upload(&V.lv, lv);
-    if (e == hipSuccess) e = hipMalloc((void**)&V.qpart, sizeof(double) * jwp::kMaxPairs * (size_t)V.nwg);
-    if (e != hipSuccess) {
-        for (void* q : {(void*)V.rowptr, (void*)V.col, (void*)V.val, (void*)V.lv, (void*)V.qpart}) (void)hipFree(q);
-        return fail(c, JWAS_HIP_EHIP, "uploading the structure failed: %s", hipGetErrorString(e));
-    }
-    auto& old = b.structs[group];                               // (a structure set twice: the later one holds)
-    for (void* q : {(void*)old.rowptr, (void*)old.col, (void*)old.val, (void*)old.lv, (void*)old.qpart}) (void)hipFree(q);
-    V.set = true;
-    old = std::move(V);
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_lp_get_group_colors(jwas_hip_ctx* c, int32_t group, int64_t nlevels, int32_t* out_color, int32_t* out_ncolors)
-{
-    NEED_LOCPAR(c);
-    NEED(c, group >= 0 && group < jwp::kMaxGroups, JWAS_HIP_EINVAL, "random_group must be 0..%d (got %d)", jwp::kMaxGroups - 1, group);
-    const auto& V = c->lp.structs[group];
-    NEED(c, V.set, JWAS_HIP_EINVAL, "random effect %d has no structure", group);
-    NEED(c, nlevels == V.nlevels, JWAS_HIP_EINVAL, "nlevels (%lld) differs from the structure's (%lld)", (long long)nlevels, (long long)V.nlevels);
-    NEED(c, out_color && out_ncolors, JWAS_HIP_EINVAL, "NULL argument");
-    std::copy(V.color.begin(), V.color.end(), out_color);
-    *out_ncolors = V.ncolors;
-    return JWAS_HIP_OK;
-}
-
-int64_t jwas_hip_lp_structure_estimate_bytes(int64_t nlevels, int64_t nnz)
-{
-    // the row pointers (int64), columns (int32) and values (double) of V, the levels colour by colour (int32), the per-workgroup
-    // sums of the quadratic forms
-    return 8 * (nlevels + 1) + 12 * nnz + 4 * nlevels + (int64_t)sizeof(double) * jwp::kMaxPairs * (nlevels / 256 + 1);
-}
-
-int64_t jwas_hip_locpar_estimate_bytes(int64_t n, int64_t nterms, int64_t total_levels)
-{
-    // per term: x, w x (doubles), level, the sorted records (int32), the piece starts and piece sums of its full pieces; per entry
-    // of sol: sol, two means, d, delta, one piece sum (doubles), the level's piece range and one piece start of its own (int32)
-    return nterms * (24 * n + 12 * (n / jwp::kPiece + 2)) + total_levels * (6 * 8 + 2 * 4) + (int64_t)sizeof(double) * jwp::kMaxGroups * 16 * 3;
-}
-
-int jwas_hip_locpar_end(jwas_hip_ctx* c)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    locpar_free(c);
-    return JWAS_HIP_OK;
-}
-
-}  // extern "C"
-
-// ---- multi-trait records that miss some traits (csrc/mtmiss.hpp): residual.jl:2-73 ----------------------------------------------
-#define NEED_MTMISS(c)                                                                                                 \
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
-    NEED(c, c->mt.active, JWAS_HIP_ESTATE, "jwas_hip_mtmiss_begin has not been called");                               \
-    NEED(c, liab_residual(c) && c->method >= 0 && c->ntraits == c->mt.nt, JWAS_HIP_ESTATE,                              \
-         "jwas_hip_init_state changed the number of traits after jwas_hip_mtmiss_begin");                              \
-    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "missing-trait records are not driven from marker or row shards")
-
-// every entry of a [2^t][t][t] table is finite
-static bool mtmiss_table_finite(const double* tab, int t)
-{
-    for (int i = 0; i < (1 << t) * t * t; ++i) if (!std::isfinite(tab[i])) return false;
-    return true;
-}
-
-extern "C" {
-
-int jwas_hip_mtmiss_begin(jwas_hip_ctx* c, int64_t n, const int32_t* observed)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no residual: load genotypes and call jwas_hip_init_state first");
-    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "missing-trait records are not driven from marker or row shards");
-    NEED(c, observed, JWAS_HIP_EINVAL, "observed is NULL");
-    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
-    const int t = c->ntraits;
-    NEED(c, t >= 1 && t <= jwm::kMaxT, JWAS_HIP_EINVAL, "the number of traits (%d) is outside 1..%d", t, jwm::kMaxT);
-    for (int64_t i = 0; i < n; ++i)
-        NEED(c, observed[i] >= 1 && observed[i] < (1 << t), JWAS_HIP_EINVAL, "record %lld: code %d outside 1..%d", (long long)i, observed[i], (1 << t) - 1);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    mtmiss_free(c);
-    auto& b = c->mt;
-    HIPCHK(c, hipMalloc((void**)&b.code, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)));
-    HIPCHK(c, hipMalloc((void**)&b.tab, sizeof(double) * 3 * jwm::kMaxCodes * 16));
-    HIPCHK(c, hipMemcpy(b.code, observed, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemsetAsync(b.tab, 0, sizeof(double) * 3 * jwm::kMaxCodes * 16, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.nt = t;
-    b.active = true;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_mtmiss_impute(jwas_hip_ctx* c, const jwas_mtmiss_params* P)
-{
-    NEED_MTMISS(c);
-    NEED(c, P && P->B && P->U, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_mtmiss_impute: iteration must be >= 1");
-    auto& b = c->mt;
-    const int t = b.nt;
-    NEED(c, mtmiss_table_finite(P->B, t) && mtmiss_table_finite(P->U, t), JWAS_HIP_EINVAL, "jwas_hip_mtmiss_impute: a table entry is not finite");
-    if (t == 1) return JWAS_HIP_OK;                             // (one trait: every record is complete)
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t bytes = sizeof(double) * (size_t)(1 << t) * t * t;
-    HIPCHK(c, hipMemcpyAsync(b.tab, P->B, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.tab + jwm::kMaxCodes * 16, P->U, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                 // (the caller's tables may go away once this returns)
-    jwm::ImputeArgs A = {};
-    A.r = liab_residual(c); A.ld = c->ld; A.n = c->n; A.code = b.code; A.B = b.tab; A.U = b.tab + jwm::kMaxCodes * 16; A.nt = t;
-    A.iter = P->iteration; A.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); A.seed_hi = (uint32_t)(P->seed >> 32);
-    const dim3 grid((unsigned)((c->n + 255) / 256));
-    if (IS_F64(c)) hipLaunchKernelGGL((jwm::k_mtmiss_impute<double>), grid, dim3(256), 0, c->stream, A);
-    else           hipLaunchKernelGGL((jwm::k_mtmiss_impute<float>), grid, dim3(256), 0, c->stream, A);
-    HIPCHK(c, hipGetLastError());
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_mtmiss_set_record_weights(jwas_hip_ctx* c, const double* C)
-{
-    NEED_MTMISS(c);
-    auto& b = c->mt;
-    if (!C) { b.weights = false; return JWAS_HIP_OK; }
-    const int t = b.nt;
-    NEED(c, t > 1, JWAS_HIP_ESTATE, "per-record weights need more than one trait");
-    NEED(c, mtmiss_table_finite(C, t), JWAS_HIP_EINVAL, "jwas_hip_mtmiss_set_record_weights: a table entry is not finite");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(b.tab + 2 * jwm::kMaxCodes * 16, C, sizeof(double) * (size_t)(1 << t) * t * t, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.weights = true;
-    return JWAS_HIP_OK;
-}
-
-int64_t jwas_hip_mtmiss_estimate_bytes(int64_t n)
-{
-    // the codes (int32), the piece sums of D of the largest term (at most one piece per record), the three tables
-    return 4 * n + 8 * n + (int64_t)sizeof(double) * 3 * jwm::kMaxCodes * 16;
-}
-
-int jwas_hip_mtmiss_end(jwas_hip_ctx* c)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    mtmiss_free(c);
-    return JWAS_HIP_OK;
-}
-
-}  // extern "C"
-
-// ---- marker-annotation priors (csrc/annot.hpp): MCMC/annotation_updates.jl:21-137,181-361 ----------------------------------------
-#define NEED_ANNOT(c)                                                                                                  \
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
-    NEED(c, c->an.active, JWAS_HIP_ESTATE, "jwas_hip_annot_begin has not been called")
-
-static int64_t annot_table_size(int kind, int64_t p) { return kind == jwa::kBayesC ? p : 4 * p; }
-
-static double** annot_table_slot(jwas_hip_ctx* c, int kind)
-{
-    return kind == jwa::kBayesC ? &c->pi_vec : kind == jwa::kBayesR ? &c->pi_mat : &c->lpr_mat;
-}
-
-// the indicators of trait `trait` as the sweep leaves them
-static const void* annot_delta(jwas_hip_ctx* c, int trait)
-{
-    if (IS_F64(c)) return c->method == JWAS_HIP_BAYESR ? c->f64->delta : (const void*)((const double*)c->f64->delta + (size_t)trait * c->p);
-    return (const void*)((const float*)c->delta + (size_t)trait * c->p);
-}
-
-template <class DT, int KIND>
-static void annot_launch_step(jwas_hip_ctx* c, const jwa::StepArgs& A, bool first)
-{
-    const dim3 grid((unsigned)c->an.npieces), blk(256);
-    if (first) hipLaunchKernelGGL((jwa::k_annot_liab<DT, KIND>), grid, blk, 0, c->stream, A);
-    else       hipLaunchKernelGGL((jwa::k_annot_sums<DT, KIND>), grid, blk, 0, c->stream, A);
-}
-
-static void annot_launch_any(jwas_hip_ctx* c, const jwa::StepArgs& A, bool first)
-{
-    switch (c->an.kind) {
-        case jwa::kBayesC: if (IS_F64(c)) annot_launch_step<double, jwa::kBayesC>(c, A, first); else annot_launch_step<float, jwa::kBayesC>(c, A, first); break;
-        case jwa::kBayesR: annot_launch_step<int32_t, jwa::kBayesR>(c, A, first); break;
-        default:           if (IS_F64(c)) annot_launch_step<double, jwa::kTree>(c, A, first); else annot_launch_step<float, jwa::kTree>(c, A, first); break;
-    }
-}
-
-extern "C" {
-
-int jwas_hip_annot_begin(jwas_hip_ctx* c, int32_t kind, int64_t p, int32_t ncols, const double* D_rowmajor, const double* coef,
-                         const double* variance, const double* start_prior)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no chain state: load genotypes and call jwas_hip_init_state first");
-    NEED(c, !c->an.active, JWAS_HIP_ESTATE, "an annotation session is already open (jwas_hip_annot_end first)");
-    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "annotation priors are not driven from marker or row shards");
-    NEED(c, !is_mega(c->method), JWAS_HIP_EUNSUP, "annotation priors are not available with constraint = true (megaBayesABC)");
-    NEED(c, kind >= jwa::kBayesC && kind <= jwa::kTree, JWAS_HIP_EINVAL, "unknown annotation kind %d", kind);
-    const bool fits = kind == jwa::kBayesC ? (c->method == JWAS_HIP_BAYESC && c->ntraits == 1)
-                    : kind == jwa::kBayesR ? (c->method == JWAS_HIP_BAYESR && c->ntraits == 1)
-                                           : ((c->method == JWAS_HIP_MTBAYESC1 || c->method == JWAS_HIP_MTBAYESC2) && c->ntraits == 2);
-    NEED(c, fits, JWAS_HIP_EINVAL, "annotation kind %d does not match the context's method %d with %d trait(s)", kind, c->method, c->ntraits);
-    NEED(c, p == c->p, JWAS_HIP_EINVAL, "p (%lld) differs from the number of markers (%lld)", (long long)p, (long long)c->p);
-    NEED(c, p >= 1 && p < ((int64_t)1 << 31) - jwa::kPiece, JWAS_HIP_EINVAL, "p must be 1 .. 2^31 - 1025 (got %lld)", (long long)p);
-    NEED(c, ncols >= 1 && ncols <= jwa::kMaxCols, JWAS_HIP_EINVAL, "ncols must be 1 .. %d (got %d)", jwa::kMaxCols, ncols);
-    NEED(c, D_rowmajor && coef && start_prior, JWAS_HIP_EINVAL, "NULL argument");
-    const int ns = jwa::annot_nsteps(kind), K = ncols;
-    const int64_t tab = annot_table_size(kind, p);
-    for (int i = 0; i < ns * K; ++i) NEED(c, std::isfinite(coef[i]), JWAS_HIP_EINVAL, "coefficient %d is not finite (%g)", i, coef[i]);
-    if (variance)
-        for (int s = 0; s < ns; ++s) NEED(c, std::isfinite(variance[s]) && variance[s] > 0.0, JWAS_HIP_EINVAL, "variance[%d] must be positive and finite (%g)", s, variance[s]);
-    for (int64_t i = 0; i < tab; ++i)
-        NEED(c, !std::isnan(start_prior[i]) && start_prior[i] != INFINITY, JWAS_HIP_EINVAL, "start_prior[%lld] is not a probability or its log (%g)", (long long)i, start_prior[i]);
-    std::vector<double> Dt((size_t)std::max(K - 1, 1) * (size_t)p);
-    for (int64_t i = 0; i < p; ++i) {
-        NEED(c, D_rowmajor[(size_t)i * K] == 1.0, JWAS_HIP_EINVAL, "marker %lld: column 0 of the design matrix must be the intercept's ones (%g)", (long long)i, D_rowmajor[(size_t)i * K]);
-        for (int k = 1; k < K; ++k) {
-            const double v = D_rowmajor[(size_t)i * K + k];
-            NEED(c, std::isfinite(v), JWAS_HIP_EINVAL, "marker %lld, column %d: the annotation is not finite (%g)", (long long)i, k, v);
-            Dt[(size_t)(k - 1) * p + i] = v;
-        }
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    auto& b = c->an;
-    b.kind = kind; b.nsteps = ns; b.K = K;
-    b.npieces = (int)((p + jwa::kPiece - 1) / jwa::kPiece);
-    const size_t pb = sizeof(double) * (size_t)p;
-    const size_t nscal = (size_t)jwa::kMaxSteps * K + 3 + 4 + 1 + K;
-#define ANNOT_ALLOC(ptr, bytes) do { if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { annot_free(c); return fail(c, JWAS_HIP_ENOMEM, "annotation session: device allocation of %zu bytes failed", (size_t)(bytes)); } } while (0)
-    ANNOT_ALLOC(b.D, pb * (size_t)std::max(K - 1, 1));
-    ANNOT_ALLOC(b.liab, pb * ns);
-    ANNOT_ALLOC(b.mu, pb * ns);
-    ANNOT_ALLOC(b.e, pb);
-    ANNOT_ALLOC(b.part, sizeof(double) * 3 * (size_t)b.npieces * (size_t)std::max(K - 1, 1));      // (set-up: the piece sums of every column's squares)
-    ANNOT_ALLOC(b.part4, sizeof(double) * 4 * (size_t)b.npieces);
-    ANNOT_ALLOC(b.scal, sizeof(double) * nscal);
-    ANNOT_ALLOC(b.mean, sizeof(double) * (size_t)tab);
-    ANNOT_ALLOC(b.mean2, sizeof(double) * (size_t)tab);
-    double** slot = annot_table_slot(c, kind);
-    if (!*slot) ANNOT_ALLOC(*slot, sizeof(double) * (size_t)tab);
-#undef ANNOT_ALLOC
-    HIPCHK(c, hipMemcpyAsync(b.D, Dt.data(), pb * (size_t)std::max(K - 1, 1), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.liab, 0, pb * ns, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.mu, 0, pb * ns, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.e, 0, pb, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.part, 0, sizeof(double) * 3 * (size_t)b.npieces * (size_t)std::max(K - 1, 1), c->stream));
-    HIPCHK(c, hipMemsetAsync(b.part4, 0, sizeof(double) * 4 * (size_t)b.npieces, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.scal, 0, sizeof(double) * nscal, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.mean, 0, sizeof(double) * (size_t)tab, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.mean2, 0, sizeof(double) * (size_t)tab, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.scal, coef, sizeof(double) * (size_t)ns * K, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(*slot, start_prior, sizeof(double) * (size_t)tab, hipMemcpyHostToDevice, c->stream));
-    if (K > 1) {                        // d_k over all markers, for the steps whose active set is all markers
-        double* dsq = b.scal + (size_t)jwa::kMaxSteps * K + 8;
-        hipLaunchKernelGGL(jwa::k_annot_colsq, dim3((unsigned)b.npieces, (unsigned)(K - 1)), dim3(256), 0, c->stream, b.D, p, (int32_t)b.npieces, b.part);
-        hipLaunchKernelGGL(jwa::k_annot_colsq_reduce, dim3((unsigned)(K - 1)), dim3(256), 0, c->stream, b.part, (int32_t)b.npieces, dsq);
-        HIPCHK(c, hipGetLastError());
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // (the caller's arrays and Dt may go away once this returns)
-    b.active = true;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_annot_step(jwas_hip_ctx* c, const jwas_annot_params* P, jwas_annot_stats* S)
-{
-    NEED_ANNOT(c);
-    NEED(c, P && S, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_annot_step: iteration must be >= 1");
-    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "annotation priors are not driven from marker or row shards");
-    auto& b = c->an;
-    const int K = b.K, ns = b.nsteps;
-    if (K > 1)
-        for (int s = 0; s < ns; ++s)
-            NEED(c, std::isfinite(P->variance[s]) && P->variance[s] > 0.0, JWAS_HIP_EINVAL, "variance[%d] must be positive and finite (%g)", s, P->variance[s]);
-    HIPCHK(c, hipSetDevice(c->device));
-    double* coef = b.scal;
-    double* nA = b.scal + (size_t)jwa::kMaxSteps * K;
-    double* means = nA + 3;
-    double* dc = means + 4;
-    double* dsq = dc + 1;
-    HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
-    for (int s = 0; s < ns; ++s) {
-        jwa::StepArgs A = {};
-        A.d1 = annot_delta(c, 0); A.d2 = b.kind == jwa::kTree ? annot_delta(c, 1) : nullptr;
-        A.D = b.D; A.coef = coef + (size_t)s * K; A.liab = b.liab + (size_t)s * c->p; A.e = b.e; A.part = b.part; A.dc = dc;
-        A.p = c->p; A.K = K; A.s = s; A.all_active = s == 0;
-        A.iter = P->iteration; A.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); A.seed_hi = (uint32_t)(P->seed >> 32);
-        jwa::DrawArgs W = {};
-        W.part = b.part; W.dsq = dsq; W.coef = coef + (size_t)s * K; W.nA = nA + s; W.dc = dc; W.var = K > 1 ? P->variance[s] : 1.0;
-        W.npieces = b.npieces; W.s = s; W.all_active = A.all_active; W.iter = A.iter; W.seed_lo = A.seed_lo; W.seed_hi = A.seed_hi;
-        for (int k = 0; k < K; ++k) {
-            A.k = k; W.k = k;
-            annot_launch_any(c, A, k == 0);
-            hipLaunchKernelGGL(jwa::k_annot_draw, dim3(1), dim3(256), 0, c->stream, W);
-        }
-    }
-    jwa::TableArgs T = {};
-    T.D = b.D; T.coef = coef; T.mu = b.mu; T.table = *annot_table_slot(c, b.kind); T.part = b.part4; T.p = c->p; T.K = K;
-    const dim3 grid((unsigned)b.npieces), blk(256);
-    if (b.kind == jwa::kBayesC)      hipLaunchKernelGGL((jwa::k_annot_table<jwa::kBayesC>), grid, blk, 0, c->stream, T);
-    else if (b.kind == jwa::kBayesR) hipLaunchKernelGGL((jwa::k_annot_table<jwa::kBayesR>), grid, blk, 0, c->stream, T);
-    else                             hipLaunchKernelGGL((jwa::k_annot_table<jwa::kTree>), grid, blk, 0, c->stream, T);
-    hipLaunchKernelGGL(jwa::k_annot_colmeans, dim3(1), dim3(256), 0, c->stream, b.part4, (int32_t)b.npieces, b.kind == jwa::kBayesC ? 1 : 4, (double)c->p, means);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_stop, c->stream));
-    std::vector<double> host((size_t)jwa::kMaxSteps * K + 7);
-    HIPCHK(c, hipMemcpyAsync(host.data(), b.scal, sizeof(double) * host.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memset(S, 0, sizeof *S);
-    for (int i = 0; i < ns * K; ++i) S->coef[i] = host[(size_t)i];
-    for (int s = 0; s < ns; ++s) S->n_active[s] = (int64_t)host[(size_t)jwa::kMaxSteps * K + s];
-    for (int q = 0; q < 4; ++q) S->means[q] = host[(size_t)jwa::kMaxSteps * K + 3 + q];
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-    S->step_ms = (double)ms;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_annot_accumulate(jwas_hip_ctx* c, double nsamples)
-{
-    NEED_ANNOT(c);
-    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
-    auto& b = c->an;
-    const int64_t q = annot_table_size(b.kind, c->p);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(jwa::k_annot_accumulate, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, c->stream, (const double*)*annot_table_slot(c, b.kind),
-                       b.mean, b.mean2, q, nsamples, (int32_t)(b.kind == jwa::kTree));
-    HIPCHK(c, hipGetLastError());
-    return JWAS_HIP_OK;
-}
-
-static int annot_download(jwas_hip_ctx* c, const double* dev, int64_t have, int64_t nvalues, double* out)
-{
-    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, nvalues == have, JWAS_HIP_EINVAL, "nvalues (%lld) differs from the session's (%lld)", (long long)nvalues, (long long)have);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, dev, sizeof(double) * (size_t)have, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_annot_get_prior(jwas_hip_ctx* c, int64_t nvalues, double* out)
-{
-    NEED_ANNOT(c);
-    return annot_download(c, *annot_table_slot(c, c->an.kind), annot_table_size(c->an.kind, c->p), nvalues, out);
-}
-
-int jwas_hip_annot_get_means(jwas_hip_ctx* c, int64_t nvalues, double* out_mean, double* out_mean2)
-{
-    NEED_ANNOT(c);
-    if (int rc = annot_download(c, c->an.mean, annot_table_size(c->an.kind, c->p), nvalues, out_mean)) return rc;
-    return out_mean2 ? annot_download(c, c->an.mean2, annot_table_size(c->an.kind, c->p), nvalues, out_mean2) : JWAS_HIP_OK;
-}
-
-int jwas_hip_annot_get_liability(jwas_hip_ctx* c, int64_t nvalues, double* out)
-{
-    NEED_ANNOT(c);
-    return annot_download(c, c->an.liab, (int64_t)c->an.nsteps * c->p, nvalues, out);
-}
-
-int jwas_hip_annot_get_mu(jwas_hip_ctx* c, int64_t nvalues, double* out)
-{
-    NEED_ANNOT(c);
-    return annot_download(c, c->an.mu, (int64_t)c->an.nsteps * c->p, nvalues, out);
-}
-
-int64_t jwas_hip_annot_estimate_bytes(int64_t p, int32_t ncols, int32_t kind)
-{
-    // D, the liabilities and mu of every step, e, the table and its two running means, the piece sums, the scalars
-    const int64_t ns = jwa::annot_nsteps(kind), K = std::max<int64_t>(ncols, 1), tab = annot_table_size(kind, p);
-    const int64_t npieces = (p + jwa::kPiece - 1) / jwa::kPiece;
-    return 8 * (std::max<int64_t>(K - 1, 1) * p + 2 * ns * p + p + 3 * tab + 3 * npieces * std::max<int64_t>(K - 1, 1) + 4 * npieces + 4 * K + 8);
-}
-
-int jwas_hip_annot_end(jwas_hip_ctx* c)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    annot_free(c);
-    return JWAS_HIP_OK;
-}
-
-}  // extern "C"
-
-// ---- structural equation models (csrc/sem.hpp): structure_equation_model/SEM.jl:53-165,245-252 ----------------------------------
-#define NEED_SEM(c)                                                                                                    \
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");                                                                        \
-    NEED(c, c->sm.active, JWAS_HIP_ESTATE, "jwas_hip_sem_begin has not been called");                                  \
-    NEED(c, liab_residual(c) && c->method >= 0 && c->ntraits == c->sm.nt, JWAS_HIP_ESTATE,                              \
-         "jwas_hip_init_state changed the number of traits after jwas_hip_sem_begin");                                 \
-    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "structural equation models are not driven from marker or row shards")
-
-// the 4 x 4 device layout <-> the caller's t x t
-static void sem_pack(const double* dev16, int t, double* out) { for (int i = 0; i < t; ++i) for (int j = 0; j < t; ++j) out[i * t + j] = dev16[i * jws::kMaxT + j]; }
-
-extern "C" {
-
-int jwas_hip_sem_begin(jwas_hip_ctx* c, int32_t ntraits, int64_t n, const double* y, const int32_t* cs)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, liab_residual(c) && c->method >= 0, JWAS_HIP_ESTATE, "no residual: load genotypes and call jwas_hip_init_state first");
-    NEED(c, !c->comm && !c->row_mode && c->loop_slot < 0, JWAS_HIP_EUNSUP, "structural equation models are not driven from marker or row shards");
-    NEED(c, ntraits >= 2, JWAS_HIP_EINVAL, "Causal strutures are only allowed in multi-trait analysis (got %d trait)", ntraits);
-    NEED(c, ntraits <= jws::kMaxT && ntraits == c->ntraits, JWAS_HIP_EINVAL, "ntraits (%d) differs from the context's (%d)", ntraits, c->ntraits);
-    NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of records (%lld)", (long long)n, (long long)c->n);
-    NEED(c, y && cs, JWAS_HIP_EINVAL, "NULL argument");
-    const int t = ntraits;
-    uint32_t mask = 0, ymask = 0, rmask = 0;
-    for (int i = 0; i < t; ++i)
-        for (int j = 0; j < t; ++j) {
-            const int v = cs[i * t + j];
-            NEED(c, v == 0 || v == 1, JWAS_HIP_EINVAL, "causal structure [%d][%d] = %d is not 0 or 1", i, j, v);
-            NEED(c, v == 0 || i > j, JWAS_HIP_EINVAL, "The causal structue needs to be a lower triangular matrix. ([%d][%d] is set)", i, j);
-            if (v) { mask |= 1u << jws::cell(i, j); ymask |= 1u << j; rmask |= 1u << i; }
-        }
-    for (int64_t i = 0; i < (int64_t)t * n; ++i)
-        NEED(c, std::isfinite(y[i]), JWAS_HIP_EINVAL, "phenotype %lld of trait %lld is not finite (%g)", (long long)(i % n), (long long)(i / n), y[i]);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    sem_free(c);
-    auto& b = c->sm;
-    b.nt = t; b.G = jws::sem_grid(n); b.mask = mask; b.ymask = ymask; b.rmask = rmask;
-    const size_t accb = sizeof(double) * 6 * (size_t)t * (size_t)c->p;
-#define SEM_ALLOC(ptr, bytes) do { if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { sem_free(c); return fail(c, JWAS_HIP_ENOMEM, "SEM session: device allocation of %zu bytes failed", (size_t)(bytes)); } } while (0)
-    SEM_ALLOC(b.y, sizeof(double) * (size_t)t * (size_t)n);
-    SEM_ALLOC(b.part, sizeof(double) * (size_t)b.G * jws::kGramCells);
-    SEM_ALLOC(b.S, sizeof(double) * 16);
-    SEM_ALLOC(b.rec, sizeof(double) * jws::kRecSize);
-    SEM_ALLOC(b.acc, accb);
-#undef SEM_ALLOC
-    HIPCHK(c, hipMemcpyAsync(b.y, y, sizeof(double) * (size_t)t * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.rec, 0, sizeof(double) * jws::kRecSize, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.acc, 0, accb, c->stream));
-    hipLaunchKernelGGL(jws::k_sem_gram, dim3((unsigned)b.G), dim3(256), 0, c->stream, (const double*)b.y, n, (int32_t)t, b.part);
-    hipLaunchKernelGGL(jws::k_sem_gram_sum, dim3(1), dim3(64), 0, c->stream, (const double*)b.part, (int32_t)b.G, b.S);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // (the caller's arrays may go away once this returns)
-    b.active = true;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_sem_step(jwas_hip_ctx* c, const jwas_sem_params* P, jwas_sem_stats* S)
-{
-    NEED_SEM(c);
-    NEED(c, P && S, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_sem_step: iteration must be >= 1");
-    auto& b = c->sm;
-    const int t = b.nt;
-    for (int i = 0; i < t; ++i)
-        NEED(c, std::isfinite(P->R_diag[i]) && P->R_diag[i] > 0.0, JWAS_HIP_EINVAL, "R_diag[%d] must be positive and finite (%g)", i, P->R_diag[i]);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
-    jws::DotArgs D = {};
-    D.r = liab_residual(c); D.y = b.y; D.part = b.part; D.n = c->n; D.ld = c->ld; D.mask = b.mask; D.ymask = b.ymask; D.rmask = b.rmask; D.nt = t;
-    jws::DrawArgs W = {};
-    W.part = b.part; W.S = b.S; W.rec = b.rec; W.G = b.G; W.nt = t; W.mask = b.mask;
-    for (int i = 0; i < t; ++i) W.Rdiag[i] = P->R_diag[i];
-    W.iter = P->iteration; W.seed_lo = (uint32_t)(P->seed & 0xFFFFFFFFu); W.seed_hi = (uint32_t)(P->seed >> 32);
-    jws::ApplyArgs A = {};
-    A.r = liab_residual(c); A.y = b.y; A.d = b.rec + jws::kRecD; A.n = c->n; A.ld = c->ld; A.mask = b.mask; A.ymask = b.ymask; A.rmask = b.rmask; A.nt = t;
-    if (b.mask) {                                               // (a structure without an edge: nothing to sample)
-        const dim3 grid((unsigned)b.G), rows((unsigned)((c->n + 255) / 256));
-        if (IS_F64(c)) hipLaunchKernelGGL((jws::k_sem_dots<double>), grid, dim3(256), 0, c->stream, D);
-        else           hipLaunchKernelGGL((jws::k_sem_dots<float>), grid, dim3(256), 0, c->stream, D);
-        hipLaunchKernelGGL(jws::k_sem_draw, dim3(1), dim3(64), 0, c->stream, W);
-        if (IS_F64(c)) hipLaunchKernelGGL((jws::k_sem_apply<double>), rows, dim3(256), 0, c->stream, A);
-        else           hipLaunchKernelGGL((jws::k_sem_apply<float>), rows, dim3(256), 0, c->stream, A);
-        HIPCHK(c, hipGetLastError());
-    }
-    HIPCHK(c, hipEventRecord(c->ev_stop, c->stream));
-    double host[jws::kRecSize];
-    HIPCHK(c, hipMemcpyAsync(host, b.rec, sizeof host, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memset(S, 0, sizeof *S);
-    sem_pack(host + jws::kRecLambda, t, S->lambda);
-    sem_pack(host + jws::kRecMu, t, S->mean);
-    sem_pack(host + jws::kRecC, t, S->ypr);
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-    S->step_ms = (double)ms;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_sem_get_lambda(jwas_hip_ctx* c, double* out)
-{
-    NEED_SEM(c);
-    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    double host[16];
-    HIPCHK(c, hipMemcpyAsync(host, c->sm.rec + jws::kRecLambda, sizeof host, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    sem_pack(host, c->sm.nt, out);
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_sem_set_lambda(jwas_hip_ctx* c, const double* in)
-{
-    NEED_SEM(c);
-    NEED(c, in, JWAS_HIP_EINVAL, "NULL argument");
-    const int t = c->sm.nt;
-    double host[16] = {0.0};
-    for (int i = 0; i < t; ++i)
-        for (int j = 0; j < t; ++j) {
-            const double v = in[i * t + j];
-            NEED(c, std::isfinite(v), JWAS_HIP_EINVAL, "lambda[%d][%d] is not finite (%g)", i, j, v);
-            const bool edge = i > j && ((c->sm.mask >> jws::cell(i, j)) & 1u);
-            NEED(c, edge || v == 0.0, JWAS_HIP_EINVAL, "lambda[%d][%d] = %g lies outside the causal structure", i, j, v);
-            host[i * jws::kMaxT + j] = v;
-        }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->sm.rec + jws::kRecLambda, host, sizeof host, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_sem_get_gram(jwas_hip_ctx* c, double* out)
-{
-    NEED_SEM(c);
-    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    double host[16];
-    HIPCHK(c, hipMemcpyAsync(host, c->sm.S, sizeof host, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    sem_pack(host, c->sm.nt, out);
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_sem_accumulate(jwas_hip_ctx* c, const double* K, double nsamples)
-{
-    NEED_SEM(c);
-    NEED(c, K, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
-    const int t = c->sm.nt;
-    jws::AccArgs A = {};
-    for (int i = 0; i < t; ++i)
-        for (int j = 0; j < t; ++j) {
-            NEED(c, std::isfinite(K[i * t + j]), JWAS_HIP_EINVAL, "K[%d][%d] is not finite (%g)", i, j, K[i * t + j]);
-            A.K[i * jws::kMaxT + j] = K[i * t + j];
-        }
-    A.alpha = IS_F64(c) ? (const void*)c->f64->alpha : (const void*)c->alpha;
-    A.acc = c->sm.acc; A.nsamples = nsamples; A.p = c->p; A.nt = t;
-    HIPCHK(c, hipSetDevice(c->device));
-    const dim3 grid((unsigned)((c->p + 255) / 256));
-    if (IS_F64(c)) hipLaunchKernelGGL((jws::k_sem_accumulate<double>), grid, dim3(256), 0, c->stream, A);
-    else           hipLaunchKernelGGL((jws::k_sem_accumulate<float>), grid, dim3(256), 0, c->stream, A);
-    HIPCHK(c, hipGetLastError());
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_sem_get_effects(jwas_hip_ctx* c, int32_t kind, int32_t trait, double* mean, double* mean2, double* freq)
-{
-    NEED_SEM(c);
-    NEED(c, kind == 0 || kind == 1, JWAS_HIP_EINVAL, "kind must be 0 (indirect) or 1 (overall), got %d", kind);
-    NEED(c, trait >= 0 && trait < c->sm.nt, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->sm.nt);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t stat = (size_t)c->sm.nt * c->p, nb = sizeof(double) * (size_t)c->p;
-    const double* base = c->sm.acc + (size_t)kind * 3 * stat + (size_t)trait * c->p;
-    if (mean) HIPCHK(c, hipMemcpyAsync(mean, base, nb, hipMemcpyDeviceToHost, c->stream));
-    if (mean2) HIPCHK(c, hipMemcpyAsync(mean2, base + stat, nb, hipMemcpyDeviceToHost, c->stream));
-    if (freq) HIPCHK(c, hipMemcpyAsync(freq, base + 2 * stat, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int64_t jwas_hip_sem_estimate_bytes(int64_t n, int64_t p, int32_t ntraits)
-{
-    // the phenotypes, the six accumulators per marker and trait, the workgroup partials, S and the record
-    const int64_t t = std::max<int64_t>(ntraits, 1);
-    return 8 * (t * n + 6 * t * p + (int64_t)jws::kMaxGrid * jws::kGramCells + 16 + jws::kRecSize);
-}
-
-int jwas_hip_sem_end(jwas_hip_ctx* c)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, c->sm.active, JWAS_HIP_ESTATE, "jwas_hip_sem_begin has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    sem_free(c);
     return JWAS_HIP_OK;
 }
 

@@ -24,15 +24,14 @@
 //   z is clamped into [lo, hi]; the liability is clamped into [L, U] after cmean + eps is rounded.
 // The uniform: philox4x32_10(individual, iteration, 0x40000000 | Gibbs round, 2 + 16 * trait) -- see rng.hpp.
 #pragma once
+#include "device_util.hpp"
 #include "rng.hpp"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace jwl {
 
-constexpr int kMaxT = 4;
-constexpr int kMaxThr = 16;             // thresholds per trait, -Inf and +Inf included: at most 15 categories
-constexpr int kMaxCat = kMaxThr - 1;
+constexpr int kMaxCat = kMaxThr - 1;       // (kMaxT, kMaxThr: device_util.hpp; at most 15 categories)
 constexpr int kMM = 2 * kMaxCat;        // doubles per workgroup and trait: {max, min} of every category
 
 enum { kContinuous = 0, kCategorical = 1, kCensored = 2 };
@@ -52,32 +51,6 @@ struct LiabArgs {
     double B[kMaxT][kMaxT];             // row k: R_12 R_22^-1 of trait k against the others (B[k][k] = 0)
     double sd[kMaxT];                   // sqrt(R_11 - R_12 R_22^-1 R_21)
 };
-
-__device__ __forceinline__ double upper_tail(double x) { return 0.5 * erfc(x * 0.70710678118654752440); }
-
-// standard normal truncated to [lo, hi], lo < hi, from one uniform u in (0, 1); lo + hi >= 0 (or NaN)
-__device__ __forceinline__ double tn_upper(double lo, double hi, double u)
-{
-    const double a = upper_tail(lo);
-    double z;
-    if (a >= 2.2250738585072014e-308) {
-        const double b = upper_tail(hi);
-        const double q = fmax(a - u * (a - b), 4.9406564584124654e-324);       // (u (a - b) may round to a: never q = 0, z = Inf)
-        z = 1.41421356237309504880 * erfcinv(2.0 * q);
-    } else {
-        z = lo - log1p(-u * (1.0 - exp(-lo * (hi - lo)))) / lo;
-    }
-    return fmin(fmax(z, lo), hi);
-}
-
-// (not inlined: ONE copy of erfc / erfcinv / log1p / exp in the kernel instead of one per trait of the unrolled loop -- inlined,
-// every instantiation took all 256 VGPRs and NT >= 3 spilled)
-__device__ __noinline__ double truncated_std_normal(double lo, double hi, double u)
-{
-    const bool mirror = lo + hi < 0.0;
-    const double z = tn_upper(mirror ? -hi : lo, mirror ? -lo : hi, u);
-    return mirror ? -z : z;
-}
 
 __device__ __forceinline__ double liab_uniform(uint32_t i, uint32_t iter, uint32_t round, uint32_t trait, uint32_t k0, uint32_t k1)
 {
@@ -149,7 +122,7 @@ __global__ __launch_bounds__(256) void k_liability_sample(const LiabArgs A)
                 const double s = A.sd[k];
                 const double lo = ((L[k] - cm[k]) - m) / s, hi = ((U[k] - cm[k]) - m) / s;
                 const double u = liab_uniform((uint32_t)i, A.iter, (uint32_t)round, (uint32_t)k, A.seed_lo, A.seed_hi);
-                const double eps = m + s * truncated_std_normal(lo, hi, u);
+                const double eps = m + s * jwu::truncated_std_normal(lo, hi, u);
                 y[k] = fmin(fmax(cm[k] + eps, L[k]), U[k]);
                 r[k] = eps;
             }

@@ -53,15 +53,14 @@
 // <true> instantiations add the pieces of D in piece order where the plain ones form d_l c_kk.  A level whose records all miss
 // trait k has D_l = 0: with no prior it is left alone.  The <false> instantiations are the plain code, unchanged.
 #pragma once
+#include "device_util.hpp"
 #include "rng.hpp"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace jwp {
 
-constexpr int kMaxT = 4;
-constexpr int kMaxGroups = 8;           // random effects per model
-constexpr int kPiece = 1024;            // records per piece
+constexpr int kPiece = 1024;            // records per piece  (kMaxT, kMaxGroups: device_util.hpp)
 constexpr int kLongRow = 32;            // a row of a structure with more entries than this gets a wave, not a thread
 constexpr int kMaxPairs = kMaxT * (kMaxT + 1) / 2;
 
@@ -188,13 +187,8 @@ __global__ __launch_bounds__(256) void k_locpar_cross(const double* __restrict__
     const double* b = sol + offs[2 * blockIdx.x + 1];
     double acc = 0.0;
     for (int l = threadIdx.x; l < nlevels; l += 256) acc = acc + a[l] * b[l];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
+    const double tot = jwu::tree256(sh, acc);
+    if (threadIdx.x == 0) out[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(256) void k_locpar_accumulate(const double* __restrict__ sol, double* __restrict__ mean, double* __restrict__ mean2,
@@ -203,8 +197,8 @@ __global__ __launch_bounds__(256) void k_locpar_accumulate(const double* __restr
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= q) return;
     const double v = sol[i];
-    mean[i] = mean[i] + (v - mean[i]) / nsamples;
-    mean2[i] = mean2[i] + (v * v - mean2[i]) / nsamples;
+    mean[i] = jwu::running_mean(mean[i], v, nsamples);
+    mean2[i] = jwu::running_mean(mean2[i], v * v, nsamples);
 }
 
 struct StructDrawArgs {
@@ -247,8 +241,7 @@ __device__ inline void locpar_structured_finish(const StructDrawArgs& A, int l, 
         if (m < A.npartners) num = num - A.p[m] * P[m];
     const double mean = num / lhs;
     const jw::u32x4 w = jw::philox4x32_10((uint32_t)l, A.iter, A.rep, A.slot, A.seed_lo, A.seed_hi);
-    const double u1 = jw::u52(w.x, w.y), u2 = jw::u52(w.z, w.w);
-    const double z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
+    const double z = jwu::normal_from(w);
     const double now = mean + z * sqrt(A.s / lhs);
     A.sol[A.off + l] = now;
     A.delta[l] = now - old;
@@ -308,18 +301,6 @@ struct QuadArgs {
 
 __host__ __device__ inline int locpar_pair(int a, int b) { return a * kMaxT - a * (a - 1) / 2 + (b - a); }      // a <= b < kMaxT
 
-__device__ inline double locpar_tree256(double* sh, double v)
-{
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 // Workgroup w owns rows 256 w .. 256 w + 255.  A row of at most kLongRow entries is added by its own thread, entry by entry; a longer
 // one by the whole workgroup afterwards (the long rows in ascending order; thread j adds entries j, j + 256, ... of the row).  Every
 // thread ends with one partial sum per pair (a, b); the 256 of them meet in a fixed tree.
@@ -375,7 +356,7 @@ __global__ __launch_bounds__(256) void k_locpar_quad_rows(const QuadArgs A)
 #pragma unroll
         for (int b = a; b < kMaxT; ++b) {
             if (b >= A.k) continue;                                                        // (uniform)
-            const double tot = locpar_tree256(sh, acc[locpar_pair(a, b)]);
+            const double tot = jwu::tree256(sh, acc[locpar_pair(a, b)]);
             if (threadIdx.x == 0) A.part[(size_t)blockIdx.x * kMaxPairs + locpar_pair(a, b)] = tot;
         }
 }
@@ -386,9 +367,7 @@ __global__ __launch_bounds__(256) void k_locpar_quad_reduce(const double* __rest
     __shared__ double sh[256];
     for (int a = 0; a < k; ++a)
         for (int b = a; b < k; ++b) {
-            double acc = 0.0;
-            for (int w = threadIdx.x; w < nwg; w += 256) acc = acc + part[(size_t)w * kMaxPairs + locpar_pair(a, b)];
-            const double tot = locpar_tree256(sh, acc);
+            const double tot = jwu::ordered_sum256(sh, part + locpar_pair(a, b), kMaxPairs, nwg);
             if (threadIdx.x == 0) { out[a * k + b] = tot; out[b * k + a] = tot; }
         }
 }

@@ -18,16 +18,14 @@
 // registers.  No floating-point atomics, no waits between workgroups: a record is one thread's, launch order is the only
 // synchronisation.
 #pragma once
-#include "locpar.hpp"
+#include "device_util.hpp"
 #include "rng.hpp"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace jwm {
 
-constexpr int kMaxT = jwp::kMaxT;
-constexpr int kMaxCodes = 1 << kMaxT;
-constexpr uint32_t kRepTag = 0x10000000u;
+constexpr uint32_t kRepTag = 0x10000000u;      // (kMaxT, kMaxCodes: device_util.hpp)
 constexpr uint32_t kSlot = 4u;
 
 struct ImputeArgs {

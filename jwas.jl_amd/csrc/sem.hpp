@@ -28,6 +28,7 @@
 //
 // Matrices on the device are 4 x 4 row-major (stride kMaxT) whatever t.  Launch order is the only synchronisation between workgroups.
 #pragma once
+#include "device_util.hpp"
 #include "rng.hpp"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -291,9 +292,9 @@ struct AccArgs {
 __device__ __forceinline__ void sem_running(double* __restrict__ acc, size_t stat_stride, size_t at, double v, double ns)
 {
     const double m = acc[at], m2 = acc[stat_stride + at], f = acc[2 * stat_stride + at];
-    acc[at] = m + (v - m) / ns;
-    acc[stat_stride + at] = m2 + (v * v - m2) / ns;
-    acc[2 * stat_stride + at] = f + ((v != 0.0 ? 1.0 : 0.0) - f) / ns;
+    acc[at] = jwu::running_mean(m, v, ns);
+    acc[stat_stride + at] = jwu::running_mean(m2, v * v, ns);
+    acc[2 * stat_stride + at] = jwu::running_mean(f, v != 0.0 ? 1.0 : 0.0, ns);
 }
 
 // one thread per marker

@@ -1,0 +1,45 @@
+"""Generates tests/golden/session_golden.json: what every device session (tests/session_golden_cases.py) computes with the library
+of the commit the fixture pins -- the parent of the commit that moved the sessions out of csrc/jwas_hip.hip.  Run once on the GPU
+with that commit's library:
+
+    python tests/golden/make_session_golden.py --commit HASH [--lib path/to/libjwas_hip.so] [--out FILE]
+
+HASH names the commit whose library is loaded; the fixture records it.
+
+tests/test_gpu_session_golden.py replays the same calls on the current library and requires equal values and digests."""
+import argparse
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.join(HERE, "..", ".."), os.path.join(HERE, "..")]
+import session_golden_cases as G  # noqa: E402
+from jwas_jl_amd import _lib  # noqa: E402
+
+
+def rocm_version():
+    try:
+        import torch
+        return str(torch.version.hip)
+    except Exception:
+        return "unknown"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--commit", required=True)
+    ap.add_argument("--lib", default="")
+    ap.add_argument("--out", default=os.path.join(HERE, "session_golden.json"))
+    args = ap.parse_args()
+    if args.lib:
+        _lib.LIB_PATH = os.path.abspath(args.lib)
+    blob = {"commit": args.commit, "rocm": rocm_version(), "cases": {f"{name}/{prec}": G.run_case(name, prec) for name in G.CASES for prec in G.PRECISIONS}}
+    with open(args.out, "w") as fh:
+        json.dump(blob, fh, separators=(",", ":"), sort_keys=True)
+        fh.write("\n")
+    print("wrote", args.out, os.path.getsize(args.out), "bytes")
+
+
+if __name__ == "__main__":
+    main()

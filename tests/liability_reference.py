@@ -251,7 +251,7 @@ class _LiabilityMixin:
         self._llo[trait], self._lup[trait] = bounds_from_thresholds(self._lthr[trait], self._lcodes[trait])
 
     def _liab_draw(self, iteration, seed, ngibbs, R, init):
-        # what jwas_hip_liability_init / _sample refuse (liab_draw in csrc/jwas_hip.hip), refused here too
+        # what jwas_hip_liability_init / _sample refuse (liab_draw in csrc/session_liability.hip), refused here too
         Rm = np.atleast_2d(np.asarray(R, dtype=np.float64))
         t = self.ntraits
         if all(k == CONTINUOUS for k in self._lk):

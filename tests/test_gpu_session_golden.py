@@ -1,0 +1,43 @@
+"""Every device session computes what the parent commit computed, bit for bit.
+
+The sessions' host code moved out of csrc/jwas_hip.hip into one unit each on shared plumbing (csrc/ctx.hpp), and their kernels onto
+shared device helpers (csrc/device_util.hpp), with the order of every floating-point operation kept.  tests/golden/session_golden.json
+holds what the parent commit's library returned for the calls of tests/session_golden_cases.py (written by
+tests/golden/make_session_golden.py on the GPU): the small outputs in full, SHA-256 digests of the large ones, and the code and message
+of the guards.  The replay must be EQUAL: there is no tolerance, the reference is the parent's own output."""
+import json
+import os
+
+import pytest
+
+import session_golden_cases as G
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with open(os.path.join(ROOT, "tests", "golden", "session_golden.json")) as fh:
+        return json.load(fh)
+
+
+def test_fixture_covers_every_case(golden):
+    assert sorted(golden["cases"]) == sorted(f"{name}/{prec}" for name in G.CASES for prec in G.PRECISIONS)
+    assert golden["rocm"] and len(golden["commit"]) == 40                   # (the commit whose library wrote it)
+
+
+@pytest.mark.parametrize("precision", G.PRECISIONS)
+@pytest.mark.parametrize("name", G.CASES)
+def test_session_is_the_parent_commits_bit_for_bit(golden, name, precision):
+    want = golden["cases"][f"{name}/{precision}"]
+    got = G.run_case(name, precision)
+    assert got["inputs"] == want["inputs"], "the generated inputs differ from the fixture's (numpy's generator, not the library)"
+    assert sorted(got["values"]) == sorted(want["values"]) and sorted(got["digests"]) == sorted(want["digests"])
+    for key in sorted(want["values"]):
+        assert got["values"][key] == want["values"][key], (key, got["values"][key], want["values"][key])      # (the doubles' reprs)
+    for key in sorted(want["digests"]):
+        assert got["digests"][key] == want["digests"][key], key
+    assert got["errors"] == want["errors"]
+    assert len(got["errors"]) == (2 if precision == 32 else 1) and all(code != 0 and msg for code, msg in got["errors"])
