@@ -42,6 +42,8 @@
  *                              (MCMC/annotation_updates.jl:21-137,181-361)
  *   jwas_hip_sem_*             the structural coefficients of runMCMC(...; causal_structure): SEM_setup / get_Λ and the indirect and
  *                              overall marker effects (structure_equation_model/SEM.jl:53-165,245-252)
+ *   jwas_hip_rrm_*             the marker sweep of runMCMC(...; RRM = Phi): BayesABCRRM!, get_mΦΦarray and the running means of
+ *                              MCMC_BayesianAlphabet_RRM (RRM/RRM.jl:43-57,101-158; RRM/MCMC_BayesianAlphabet_RRM.jl:123-144,212-218)
  *
  * Conventions: every entry point returns 0 on success and a negative JWAS_HIP_E* code on failure
  * (no exceptions cross the boundary; jwas_hip_last_error() returns the message -- the analogue of
@@ -625,6 +627,70 @@ int  jwas_hip_sem_get_effects(jwas_hip_ctx* ctx, int32_t kind, int32_t trait, do
 /* Device bytes of a session (pure; an upper bound). */
 int64_t jwas_hip_sem_estimate_bytes(int64_t n, int64_t p, int32_t ntraits);
 int  jwas_hip_sem_end(jwas_hip_ctx* ctx);
+
+/* ---- random regression models: every marker carries c regression coefficients (csrc/rrm.hpp) ----------------------------------------
+ * runMCMC(...; RRM = Phi) fits longitudinal records: n individuals with up to T records each, one per time point, Phi (T x c) the
+ * covariates of the time points (RRM/RRM.jl, RRM/MCMC_BayesianAlphabet_RRM.jl).  The session keeps a residual W (T x n doubles,
+ * exactly 0 at every cell without a record -- the reference's yfull, RRM.jl:12-20,151), the coefficients alpha, beta, delta (c x p)
+ * and their running means, all in double whatever the context's element type; the genotypes are the context's (dense Float32 or
+ * Float64).  Per marker, in marker order (BayesABCRRM!, RRM.jl:101-158):
+ *   xw = sum_i x_ij sum_t m_it phi_t W_it + M_j alpha_j,     M_j = sum_i x_ij^2 sum_t m_it phi_t phi_t'   (get_mΦΦarray, RRM.jl:43-57)
+ *   every state delta in {0,1}^c (bit q of the state index = coefficient q): lhs = D M_j D / vare + inv(G), rhs = D xw / vare,
+ *   logDelta = -0.5 (log det lhs - rhs'inv(lhs) rhs) + log pi(state);  state ~ Categorical(softmax(logDelta)) from ONE uniform (CDF walk
+ *   in state-index order, the last state when rounding leaves u above the total);  beta = inv(lhs) rhs + chol(inv(lhs)) z with one
+ *   shared z (the reference draws one MvNormal per candidate and picks by dictionary position, RRM.jl:123-141: the law is the same,
+ *   the stream is not);  alpha = D beta;  W_it += m_it x_ij phi_t'(alpha_old - alpha).
+ * The device runs the exact block form of this chain: per block of <= 256 markers the right-hand sides from the residual at block
+ * entry, corrected inside the block through a block Gram tensor G_jk = sum_i x_ij x_ik sum_t m_it phi_t phi_t' (c (c + 1) / 2
+ * doubles per marker pair of a block: 8 p b c (c + 1) / 2 bytes), the residual brought up to date at the next block's entry.
+ * Draws: philox4x32_10(marker, iteration, 0x02000000, slot), slot 8 the uniform, slot 9 + 16 q the normal of coefficient q; they
+ * do not depend on the block size.  No floating-point atomics: every sum has a fixed order, the same seed gives the same bits.
+ * Limits: 2 <= c <= 4, 1 <= T <= 64, block size <= 256 (0: 64), uniform blocks.
+ * Errors: JWAS_HIP_ESTATE without loaded genotypes or, for every other entry point, without an open session; JWAS_HIP_EUNSUP on 2-bit
+ * packed storage (the reference refuses RRM on storage=:stream, input_data_validation.jl:97-98), with residual weights and on marker
+ * or row shards; JWAS_HIP_EINVAL for c, T, n, the block size out of range, a record bit at or above T, non-finite Phi, vare or G, a
+ * G that is not symmetric positive definite, a NaN or +Inf log prior.  A failed _begin opens nothing; _begin on an open session
+ * replaces it.  The session is freed by _end, jwas_hip_destroy or loading genotypes. */
+typedef struct jwas_rrm_params {
+    uint32_t iteration;                 /* MCMC iteration >= 1 (enters the RNG counter)                                          */
+    uint32_t reserved;
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                     */
+    double   vare;                      /* the residual variance (a scalar: RRM.jl:81)                                           */
+    double   G[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];      /* c x c row-major in the first c c entries                      */
+    double   log_pi[JWAS_HIP_MAX_STATES];                       /* log pi(state), 2^c entries (-Inf: the state is excluded)      */
+} jwas_rrm_params;
+typedef struct jwas_rrm_stats {
+    double state_counts[JWAS_HIP_MAX_STATES];                   /* markers per state after the sweep (samplePi, Pi.jl)           */
+    double beta_ss[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];  /* beta'beta, c x c row-major in the first c c entries           */
+    double alpha_ss;                    /* sum of squares of all coefficients                                                    */
+    double resid_ss;                    /* sum W^2 after the sweep                                                               */
+    double n_changed;                   /* markers whose coefficients moved                                                      */
+    double step_ms;                     /* device time of the sweep (HIP events on the context's stream)                         */
+} jwas_rrm_stats;
+/* Open a session: phi_T_c row-major T x c, mask_n one word per individual (bit t: a record at time t).  Builds M_j and the Grams
+ * (get_mΦΦarray, RRM.jl:43-57, and its block extension). */
+int  jwas_hip_rrm_begin(jwas_hip_ctx* ctx, int32_t T, int32_t c, int64_t n, const double* phi_T_c, const uint64_t* mask_n, int32_t block_size);
+/* The residual, row-major T x n (yfull, MCMC_BayesianAlphabet_RRM.jl:62-73,123,144).  _set forces the cells without a record to 0. */
+int  jwas_hip_rrm_set_residual(jwas_hip_ctx* ctx, int64_t nvalues, const double* W_T_n);
+int  jwas_hip_rrm_get_residual(jwas_hip_ctx* ctx, int64_t nvalues, double* out_T_n);
+/* alpha, beta, delta, each row-major c x p; any may be NULL (Mi.α, Mi.β, Mi.δ: MCMC_BayesianAlphabet_RRM.jl:52-57). */
+int  jwas_hip_rrm_set_state(jwas_hip_ctx* ctx, const double* alpha, const double* beta, const double* delta);
+int  jwas_hip_rrm_get_state(jwas_hip_ctx* ctx, double* alpha, double* beta, double* delta);
+/* One sweep over all markers (BayesABCRRM!, RRM.jl:101-158).  Synchronous. */
+int  jwas_hip_rrm_sweep(jwas_hip_ctx* ctx, const jwas_rrm_params* params, jwas_rrm_stats* stats);
+/* Running mean, mean of squares and model frequency of every coefficient (MCMC_BayesianAlphabet_RRM.jl:214-218). */
+int  jwas_hip_rrm_accumulate(jwas_hip_ctx* ctx, double nsamples);
+/* ... of coefficient q: p values each, any may be NULL. */
+int  jwas_hip_rrm_get_posterior(jwas_hip_ctx* ctx, int32_t q, double* mean, double* mean2, double* freq);
+/* out_n = X alpha_q, the genomic values of coefficient q (getEBV, output.jl:281-306). */
+int  jwas_hip_rrm_mul_alpha(jwas_hip_ctx* ctx, int32_t q, double* out_n);
+/* M_j, p x c (c + 1) / 2 doubles (lower cells, cell(a, b) = a (a + 1) / 2 + b), and the Gram tensor of one block,
+ * b x b x c (c + 1) / 2 with b the block's markers (mΦΦArray, RRM.jl:43-57). */
+int  jwas_hip_rrm_get_m(jwas_hip_ctx* ctx, int64_t nvalues, double* out);
+int  jwas_hip_rrm_get_gram(jwas_hip_ctx* ctx, int64_t block, int64_t nvalues, double* out);
+/* Device bytes of a session (pure; an upper bound). */
+int64_t jwas_hip_rrm_estimate_bytes(int64_t n, int64_t p, int32_t T, int32_t c, int32_t block_size);
+int  jwas_hip_rrm_end(jwas_hip_ctx* ctx);
 
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the

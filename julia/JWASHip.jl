@@ -458,6 +458,93 @@ hip_sem_estimate_bytes(n::Integer, p::Integer, ntraits::Integer) =
     ccall((:jwas_hip_sem_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int32), n, p, ntraits)
 hip_sem_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_sem_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
 
+"Random regression models on the device (RRM/RRM.jl:43-57,101-158; RRM/MCMC_BayesianAlphabet_RRM.jl; csrc/rrm.hpp).  `hip_rrm_begin!`
+takes Φ (T x c), the T x n record indicator (yfull's non-zeros, RRM.jl:12-20) and the block size and builds mΦΦArray and the block
+Gram tensor; `hip_rrm_set_residual!` / `hip_rrm_residual` move yfull (n x T in Julia, wArray's columns); `hip_rrm_sweep!` replaces
+BayesABCRRM! and returns the statistics samplePi and sample_variance need.  Limits: 2 <= c <= 4, T <= 64, blocks <= 256 markers,
+dense genotypes, no residual weights, no shards.  The state index of `log_pi` and `state_counts` has bit q-1 set when coefficient q
+is in the model."
+struct HipRrmParams
+    iteration::UInt32
+    reserved::UInt32
+    seed::UInt64
+    vare::Float64
+    G::NTuple{16,Float64}
+    log_pi::NTuple{16,Float64}
+end
+struct HipRrmStats
+    state_counts::NTuple{16,Float64}
+    beta_ss::NTuple{16,Float64}
+    alpha_ss::Float64
+    resid_ss::Float64
+    n_changed::Float64
+    step_ms::Float64
+end
+function hip_rrm_begin!(b::HipBackend, Φ::Matrix{Float64}, observed::AbstractMatrix{Bool}, block_size::Integer=64)
+    T, c = size(Φ)
+    n = size(observed, 2)
+    mask = zeros(UInt64, n)
+    for i in 1:n, t in 1:T
+        observed[t, i] && (mask[i] |= UInt64(1) << (t - 1))
+    end
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_begin, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Ptr{UInt64}, Int32),
+                           b.ctx, T, c, n, vec(permutedims(Φ)), mask, block_size))
+    (T, c)
+end
+# yfull as an n x T Julia matrix == the library's row-major T x n
+hip_rrm_set_residual!(b::HipBackend, W::Matrix{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_set_residual, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), b.ctx, length(W), W))
+function hip_rrm_residual(b::HipBackend, n::Integer, T::Integer)
+    W = Matrix{Float64}(undef, n, T)
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_get_residual, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), b.ctx, length(W), W))
+    W
+end
+# alpha, beta, delta as p x c Julia matrices (alphaArray's columns) == the library's row-major c x p
+hip_rrm_set_state!(b::HipBackend, α::Matrix{Float64}, β::Matrix{Float64}, δ::Matrix{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_set_state, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.ctx, α, β, δ))
+function hip_rrm_state(b::HipBackend, p::Integer, c::Integer)
+    α, β, δ = Matrix{Float64}(undef, p, c), Matrix{Float64}(undef, p, c), Matrix{Float64}(undef, p, c)
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_get_state, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.ctx, α, β, δ))
+    α, β, δ
+end
+function hip_rrm_sweep!(b::HipBackend, c::Integer, iter::Integer, seed::Integer, vare::Real, G::AbstractMatrix, log_pi::AbstractVector)
+    S = Ref{HipRrmStats}()
+    Gt = ntuple(i -> i <= c * c ? Float64(G[(i - 1) ÷ c + 1, (i - 1) % c + 1]) : 0.0, 16)
+    lp = ntuple(i -> i <= 2^c ? Float64(log_pi[i]) : -Inf, 16)
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_sweep, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipRrmParams}, Ref{HipRrmStats}),
+                           b.ctx, HipRrmParams(UInt32(iter), UInt32(0), UInt64(seed), Float64(vare), Gt, lp), S))
+    S[]
+end
+hip_rrm_accumulate!(b::HipBackend, nsamples::Real) =
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_accumulate, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Float64), b.ctx, nsamples))
+"(meanAlpha, meanAlpha2, meanDelta) of coefficient `q` (1-based), p values each."
+function hip_rrm_posterior(b::HipBackend, q::Integer, p::Integer)
+    m, m2, f = Vector{Float64}(undef, p), Vector{Float64}(undef, p), Vector{Float64}(undef, p)
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_get_posterior, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                           b.ctx, q - 1, m, m2, f))
+    m, m2, f
+end
+"X α_q: the genomic values of coefficient `q` (1-based) of the n individuals (getEBV)."
+function hip_rrm_mul_alpha(b::HipBackend, q::Integer, n::Integer)
+    out = Vector{Float64}(undef, n)
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_mul_alpha, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), b.ctx, q - 1, out))
+    out
+end
+"mΦΦArray as c(c+1)/2 x p lower cells (cell(a, b) = a(a+1)/2 + b, 0-based), and the Gram tensor of block `k` (1-based) of `nb` markers."
+function hip_rrm_m(b::HipBackend, p::Integer, c::Integer)
+    out = Matrix{Float64}(undef, c * (c + 1) ÷ 2, p)
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_get_m, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), b.ctx, length(out), out))
+    out
+end
+function hip_rrm_gram(b::HipBackend, k::Integer, nb::Integer, c::Integer)
+    out = Array{Float64,3}(undef, c * (c + 1) ÷ 2, nb, nb)
+    hip_check(b.ctx, ccall((:jwas_hip_rrm_get_gram, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}), b.ctx, k - 1, length(out), out))
+    out
+end
+hip_rrm_estimate_bytes(n::Integer, p::Integer, T::Integer, c::Integer, block_size::Integer=64) =
+    ccall((:jwas_hip_rrm_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int32, Int32, Int32), n, p, T, c, block_size)
+hip_rrm_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_rrm_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

@@ -19,6 +19,7 @@ GRAM_F64, GRAM_MFMA = 0, 1
 ANNOT_MAX_COLS = 64                     # columns of the annotation design matrix, the intercept included (JWAS_HIP_ANNOT_MAX_COLS)
 ANNOT_BAYESC, ANNOT_BAYESR, ANNOT_TREE = 0, 1, 2
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
+RRM_MIN_COEFF, RRM_MAX_COEFF, RRM_MAX_TIMES, RRM_MAX_BLOCK = 2, 4, 64, 256      # csrc/rrm.hpp
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
 # enum jwas_hip_schedule_flags (jwas_hip_last_sweep_schedule): name -> bit
@@ -100,6 +101,16 @@ class SemParams(C.Structure):
 class SemStats(C.Structure):
     _fields_ = [("lambda_", C.c_double * (MAX_TRAITS * MAX_TRAITS)), ("mean", C.c_double * (MAX_TRAITS * MAX_TRAITS)),
                 ("ypr", C.c_double * (MAX_TRAITS * MAX_TRAITS)), ("step_ms", C.c_double)]
+
+
+class RrmParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("vare", C.c_double),
+                ("G", C.c_double * (MAX_TRAITS * MAX_TRAITS)), ("log_pi", C.c_double * MAX_STATES)]
+
+
+class RrmStats(C.Structure):
+    _fields_ = [("state_counts", C.c_double * MAX_STATES), ("beta_ss", C.c_double * (MAX_TRAITS * MAX_TRAITS)), ("alpha_ss", C.c_double),
+                ("resid_ss", C.c_double), ("n_changed", C.c_double), ("step_ms", C.c_double)]
 
 
 class JwasHipError(RuntimeError):
@@ -248,6 +259,19 @@ PROTOTYPES = {
     "jwas_hip_sem_get_effects": (_INT, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "jwas_hip_sem_estimate_bytes": (_i64, [_i64, _i64, _i32]),
     "jwas_hip_sem_end": (_INT, [_vp]),
+    "jwas_hip_rrm_begin": (_INT, [_vp, _i32, _i32, _i64, _vp, _vp, _i32]),
+    "jwas_hip_rrm_set_residual": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_rrm_get_residual": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_rrm_set_state": (_INT, [_vp, _vp, _vp, _vp]),
+    "jwas_hip_rrm_get_state": (_INT, [_vp, _vp, _vp, _vp]),
+    "jwas_hip_rrm_sweep": (_INT, [_vp, _P(RrmParams), _P(RrmStats)]),
+    "jwas_hip_rrm_accumulate": (_INT, [_vp, C.c_double]),
+    "jwas_hip_rrm_get_posterior": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_rrm_mul_alpha": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_rrm_get_m": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_rrm_get_gram": (_INT, [_vp, _i64, _i64, _vp]),
+    "jwas_hip_rrm_estimate_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "jwas_hip_rrm_end": (_INT, [_vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 

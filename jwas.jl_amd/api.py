@@ -9,8 +9,8 @@ Same names, argument meaning and error behaviour as reworkhow/JWAS.jl v2.3.6 (fi
     runMCMC         JWAS.jl:161-511  -> MCMC/MCMC_BayesianAlphabet.jl
 Everything that is NOT the marker sweep stays here on the host (numpy): data ingestion and QC,
 model parsing, fixed-effect Gibbs, variance-component and pi draws, output tables.  Model families
-outside the hot path (pedigree / random terms, GBLUP, SEM, RRM, single-step pre-processing) are rejected with an
-explicit error: they stay on the reference.  i.i.d. random effects (set_random) and large class factors run on the device
+outside the hot path (GBLUP, single-step analysis, prediction equations) are rejected with an
+explicit error: they stay on the reference.  Random regression models (RRM=Phi) have a driver of their own (rrm.py, csrc/rrm.hpp).  i.i.d. random effects (set_random) and large class factors run on the device
 (mcmc.py step 1, csrc/locpar.hpp).  Categorical / censored traits run here: their liabilities are sampled
 on the device (mcmc.py step 0, csrc/liability.hpp).
 """
@@ -21,6 +21,7 @@ import numpy as np
 
 from .mcmc import run_chain
 from .gwas import GWAS  # noqa: F401  (src/3.GWAS/src/GWAS.jl)
+from .rrm import generatefullPhi  # noqa: F401  (RRM/RRM.jl:24-39)
 
 # RR-BLUP: every marker is in the model with one common effect variance -- the same full conditionals as BayesC with
 # pi = 0 fixed (BayesL! with gammaArray = [1.0], BayesC0L.jl:20-47, vs bayesabc_update_marker! with probDelta1 = 1;
@@ -522,6 +523,14 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     generator.  The choice is therefore part of what a seed means, as with location_parameters.  Not with storage=:stream,
     constraint=true or marker shards (explicit errors).
 
+    RRM (JWAS.jl:177,464-475; RRM/RRM.jl, RRM/MCMC_BayesianAlphabet_RRM.jl): a T x c numeric matrix Phi, one row per distinct time point
+    (ascending; generatefullPhi builds normalised Legendre columns) -- the random regression model for longitudinal records: the
+    first column of df holds the IDs, the column `time` the time point of every record, every marker carries c coefficients.  A
+    driver of its own (rrm.py) with the marker sweep on the device (csrc/rrm.hpp): one trait, BayesC, estimatePi true or false,
+    both precisions, 2 <= c <= 4, T <= 64, uniform blocks (block_size <= 256, default 64), location parameters on the host.  The
+    coefficients are the "traits" "1" ... "c" of the outputs: marker effects <genotypes>, pi_<genotypes>, residual variance,
+    EBV_1 ... EBV_c, genetic_variance (no heritability, as in the reference).  Any other non-false value stays on the reference.
+
     causal_structure (JWAS.jl:144-147,328-337; structure_equation_model/SEM.jl): a t x t strictly lower 0/1 matrix, entry [i, j] = 1
     when trait j acts on trait i -- the recursive structural equation model of Wang et al. 2020.  The structural coefficients are
     sampled on the device after the residual-variance draw of every iteration (csrc/sem.hpp); the residual the chain runs on is
@@ -545,6 +554,20 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     Float64: constraint=true, storage=:stream, shards (explicit errors).  The sample files keep their Float32 / 9-digit format."""
     if independent_blocks and fast_blocks is False:
         raise ValueError("independent_blocks=true requires fast_blocks != false.")             # :242-244
+    from . import rrm as _rrm
+    rrm_phi = None
+    if _rrm.is_phi(RRM):                                                                       # JWAS.jl:464-475
+        for flag, name in ((single_step_analysis, "single_step_analysis"), (update_priors_frequency, "update_priors_frequency"),
+                           (prediction_equation, "prediction_equation")):
+            if not _is_false(flag) and flag != 0:
+                raise NotImplementedError(f"runMCMC(...; {name}=...) is outside the device marker path and stays on the reference")
+        if location_parameters not in ("auto", "host", "device"):
+            raise ValueError('location_parameters must be "auto", "host" or "device".')
+        rrm_phi = _rrm.validate(model, df, RRM, fast_blocks=fast_blocks, independent_blocks=independent_blocks,
+                                causal_structure=False if _is_false(causal_structure) else causal_structure,
+                                location_parameters=location_parameters, heterogeneous_residuals=heterogeneous_residuals,
+                                starting_value=starting_value, block_size=block_size, engine=_engine)
+        RRM = False
     for flag, name in ((single_step_analysis, "single_step_analysis"), (RRM, "RRM"),
                        (update_priors_frequency, "update_priors_frequency"),
                        (prediction_equation, "prediction_equation")):
@@ -593,6 +616,12 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
         output_folder = myfolder + str(folderi)
         folderi += 1
     os.makedirs(output_folder)
+    if rrm_phi is not None:
+        return _rrm.run_rrm(model, df, rrm_phi, chain_length=int(chain_length), burnin=int(burnin),
+                            output_samples_frequency=int(output_samples_frequency), seed=seed, double_precision=bool(double_precision),
+                            outputEBV=outputEBV, output_heritability=bool(output_heritability), output_folder=output_folder,
+                            printout_frequency=printout_frequency, device=device, block_size=block_size, engine=_engine,
+                            printout_model_info=printout_model_info)
     return run_chain(model, df, chain_length=int(chain_length), burnin=int(burnin),
                      output_samples_frequency=int(output_samples_frequency), seed=seed,
                      starting_value=starting_value, fast_blocks=fast_blocks,

@@ -165,6 +165,7 @@ struct jwas_hip_ctx {
         std::vector<int64_t> starts;        // block starts (nblocks + 1 entries, 0-based): uniform or explicit partition
         int bstride = 0;                    // largest block of the partition, rounded up to a multiple of 8
         bool explicit_part = false;
+        bool weighted = false;              // w differs from ones (jwas_hip_set_weights_f64)
         double* Xout = nullptr;             // [p][ld_out] output rows (jwas_hip_load_output_dense_f64)
         int64_t n_out = 0, ld_out = 0;
         int32_t* cmp_idx = nullptr;         // [p] + [1] compacted nonzero effects of one trait (k64_compact_alpha)
@@ -274,6 +275,27 @@ struct jwas_hip_ctx {
         double* rec = nullptr;                              // [kRecSize] lambda | d | mu | C
         double* acc = nullptr;                              // [2][3][nt][p] indirect | overall: mean, mean of squares, frequency
     } sm;
+    // Random regression model (jwas_hip_rrm_begin .. _end; RRM/RRM.jl, RRM/MCMC_BayesianAlphabet_RRM.jl; csrc/rrm.hpp): a sweep of its
+    // own with its own residual and state, all double, on the context's genotypes
+    struct Rrm {
+        bool active = false;
+        int T = 0, C = 0, bs = 0;                           // time points, coefficients per marker, block size
+        int64_t nblocks = 0;
+        DevOwner mem;
+        std::vector<uint64_t> mask_host;                    // [n] bit t: the individual has a record at time t
+        uint64_t* mask = nullptr;                           // [ld] (pad rows 0)
+        double* phi = nullptr;                              // [T][C]
+        double* O = nullptr;                                // [cells][ld] O_i = sum_t m_it phi_t phi_t'
+        double* W = nullptr;                                // [T][ld] the residual, 0 at every unobserved cell
+        double* M = nullptr;                                // [p][cells]
+        double* gram = nullptr;                             // [nblocks][bs][bs][cells]
+        double *alpha = nullptr, *beta = nullptr, *delta = nullptr;               // [C][p]
+        double *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;          // [C][p]
+        double* partials = nullptr;                         // [nslices][bs C]
+        double* stat = nullptr;                             // [kStSize] the sweep's statistics | [nslices] sum W^2 per slice
+        double* row = nullptr;                              // [ld] X alpha_q
+        void* ev = nullptr;                                 // jwr::Events: the change list of the last sampled block
+    } rr;
 };
 
 // ---- errors ------------------------------------------------------------------------------------------------------------------------
@@ -330,6 +352,7 @@ JW_LOCAL void locpar_free(jwas_hip_ctx* c);
 JW_LOCAL void mtmiss_free(jwas_hip_ctx* c);
 JW_LOCAL void annot_free(jwas_hip_ctx* c);
 JW_LOCAL void sem_free(jwas_hip_ctx* c);
+JW_LOCAL void rrm_free(jwas_hip_ctx* c);
 
 // `words` ("liabilities", "annotation priors", ...) are not driven from a context that holds a marker or row shard
 static inline int refuse_shards(jwas_hip_ctx* c, const char* words)

@@ -1,4 +1,4 @@
-// device_util.hpp -- what the session kernels (liability.hpp, locpar.hpp, mtmiss.hpp, annot.hpp, sem.hpp) share.  It defines no
+// device_util.hpp -- what the session kernels (liability.hpp, locpar.hpp, mtmiss.hpp, annot.hpp, sem.hpp, rrm.hpp) share.  It defines no
 // kernel, so any number of units may include it; the host context (ctx.hpp) includes it for the limits below.  Every helper fixes
 // an ORDER of floating-point operations: with -ffp-contract=off its callers compute the bits of the expression written out.
 #pragma once

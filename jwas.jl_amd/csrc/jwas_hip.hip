@@ -126,6 +126,7 @@ static void gwas_free(jwas_hip_ctx* c)
 static void free_storage(jwas_hip_ctx* c)
 {
     sem_free(c);                        // (the phenotypes belong to the records, the accumulators to the markers of this matrix)
+    rrm_free(c);                        // (its Grams, masks and state are those of this matrix)
     annot_free(c);                      // (the prior table below belongs to the markers of this matrix)
     mtmiss_free(c);                     // (the codes describe the records of this matrix)
     gwas_free(c);                       // (a session is bound to the matrix it was begun on)
@@ -2331,6 +2332,7 @@ static int f64_set_weights(jwas_hip_ctx* c, const float* rinv32, const double* r
         NEED(c, std::isfinite(v) && v > 0.0, JWAS_HIP_EINVAL, "residual weights must be positive and finite (row %lld: %g)", (long long)i, v);
         wv[(size_t)i] = v;
     }
+    F->weighted = std::any_of(wv.begin(), wv.begin() + c->n, [](double v) { return v != 1.0; });
     HIPCHK(c, hipMemcpy(F->w, wv.data(), sizeof(double) * (size_t)c->ld, hipMemcpyHostToDevice));
     if (!F->starts.empty()) return f64_build_blocks(c);
     return JWAS_HIP_OK;
@@ -2665,9 +2667,10 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     liab_free(c);
     locpar_free(c);
     mtmiss_free(c);
+    rrm_free(c);
     for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->w, (void*)F->ev_all}) (void)hipFree(q);
     F->X = F->r = F->xpx = F->gram = F->partials = F->w = nullptr; F->ev = F->ev_all = nullptr; F->dparams = nullptr;
-    F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0;
+    F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0; F->weighted = false;
     for (void* q : {(void*)F->Xout, (void*)F->cmp_idx, (void*)F->cmp_val}) (void)hipFree(q);      // (sized by the old p)
     F->Xout = nullptr; F->n_out = F->ld_out = 0; F->cmp_idx = nullptr; F->cmp_val = nullptr;
     (void)hipFree(c->counters); (void)hipFree(c->fin_out); (void)hipFree(c->stat_out); if (c->host_buf) (void)hipHostFree(c->host_buf);

@@ -26,6 +26,9 @@
 //           parents of its trait, iteration, 0x04000000 | trait, 7).  The tag 0x04000000 is no other stream's repetition word
 //           (small counts, 0x08000000 | step, 0x10000000, 0x20000000 | term, 0x40000000 | round, 0x80000000 | ...) and no other
 //           stream uses slot 7.
+//   slots 8, 9: the random-regression sweep (rrm.hpp), indexed by (MARKER, iteration, 0x02000000, slot): slot 8 the decision uniform of
+//           the joint inclusion state (as slot 0), slot 9 + 16 q the normal of coefficient q (Box-Muller as slot 1).  The tag
+//           0x02000000 is no other stream's repetition word and no other stream uses slots 8 and 9 (+ 16 q: 25, 41, 57).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

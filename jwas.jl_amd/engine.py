@@ -87,6 +87,7 @@ class HipEngine:
         self._keep = []   # host arrays referenced by the last sweep call
         self._weighted = False          # non-unit residual weights on the device (set_weights)
         self._explicit_starts = None    # explicit block partition resident (setup_blocks_explicit)
+        self._rrm = None                # (T, c, block size) of an open random-regression session
 
     # -- plumbing --------------------------------------------------------------------------------
     def _chk(self, rc):
@@ -857,6 +858,117 @@ class HipEngine:
     def sem_end(self):
         self._chk(self._L.jwas_hip_sem_end(self._h))
         self._sem_t = None
+
+    # -- random regression models (jwas_hip_rrm_*; RRM/RRM.jl, RRM/MCMC_BayesianAlphabet_RRM.jl, csrc/rrm.hpp) ----------------
+    @staticmethod
+    def rrm_estimate_bytes(n, p, ntimes, ncoeff, block_size=64):
+        return _lib.load().jwas_hip_rrm_estimate_bytes(int(n), int(p), int(ntimes), int(ncoeff), int(block_size))
+
+    def rrm_begin(self, Phi, observed, block_size=64):
+        """Open a session on the loaded genotypes.  Phi: T x c; observed: T x n booleans (True: the individual has a record at that
+        time point).  Builds M_j and the block Gram tensor; the residual starts at 0, alpha and beta at 0, delta at 1."""
+        ph = np.ascontiguousarray(Phi, dtype=np.float64)
+        ob = np.asarray(observed)
+        if ph.ndim != 2 or ob.ndim != 2 or ob.shape[0] != ph.shape[0]:
+            raise ValueError("Phi must be T x c and observed T x n")
+        T, c = ph.shape
+        mask = np.zeros(ob.shape[1], dtype=np.uint64)
+        for t in range(min(T, 64)):
+            mask |= ob[t].astype(bool).astype(np.uint64) << np.uint64(t)
+        self._chk(self._L.jwas_hip_rrm_begin(self._h, T, c, ob.shape[1], _ptr(ph), _ptr(mask), int(block_size)))
+        self._rrm = (T, c, int(block_size) if block_size else 64)
+
+    def rrm_set_residual(self, W):
+        """W: T x n doubles; the cells without a record are forced to 0."""
+        T, c, _ = self._rrm
+        Wv = np.ascontiguousarray(W, dtype=np.float64)
+        if Wv.shape != (T, self.n):
+            raise ValueError(f"the residual must be {T} x {self.n}")
+        self._chk(self._L.jwas_hip_rrm_set_residual(self._h, Wv.size, _ptr(Wv)))
+
+    def rrm_get_residual(self):
+        T, c, _ = self._rrm
+        out = np.empty((T, self.n), dtype=np.float64)
+        self._chk(self._L.jwas_hip_rrm_get_residual(self._h, out.size, _ptr(out)))
+        return out
+
+    def rrm_set_state(self, alpha=None, beta=None, delta=None):
+        """alpha, beta, delta: c x p doubles each, any may be None.  The state only: the residual is not touched."""
+        T, c, _ = self._rrm
+        arrs = []
+        for a in (alpha, beta, delta):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (c, self.p):
+                    raise ValueError(f"state arrays must be {c} x {self.p}")
+            arrs.append(a)
+        self._chk(self._L.jwas_hip_rrm_set_state(self._h, _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2])))
+
+    def rrm_get_state(self):
+        T, c, _ = self._rrm
+        out = [np.empty((c, self.p), dtype=np.float64) for _ in range(3)]
+        self._chk(self._L.jwas_hip_rrm_get_state(self._h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
+        return tuple(out)
+
+    def rrm_sweep(self, *, iteration, seed, vare, G, log_pi):
+        """One sweep over all markers.  G: c x c; log_pi: 2^c values, state index bit q = coefficient q.  Returns {"state_counts",
+        "beta_ss" (c x c), "alpha_ss", "resid_ss", "n_changed", "step_ms"}."""
+        T, c, _ = self._rrm
+        P, S = _lib.RrmParams(), _lib.RrmStats()
+        P.iteration, P.seed, P.vare = int(iteration), int(seed), float(vare)
+        Gv = np.asarray(G, dtype=np.float64)
+        lp = np.asarray(log_pi, dtype=np.float64).reshape(-1)
+        if Gv.shape != (c, c) or lp.size != 1 << c:
+            raise ValueError(f"G must be {c} x {c} and log_pi hold {1 << c} values")
+        for i, v in enumerate(Gv.ravel()):
+            P.G[i] = float(v)
+        for i, v in enumerate(lp):
+            P.log_pi[i] = float(v)
+        self._chk(self._L.jwas_hip_rrm_sweep(self._h, C.byref(P), C.byref(S)))
+        return {"state_counts": np.array(S.state_counts[:1 << c]), "beta_ss": np.array(S.beta_ss[:c * c]).reshape(c, c), "alpha_ss": S.alpha_ss,
+                "resid_ss": S.resid_ss, "n_changed": S.n_changed, "step_ms": S.step_ms}
+
+    def rrm_accumulate(self, nsamples):
+        self._chk(self._L.jwas_hip_rrm_accumulate(self._h, float(nsamples)))
+
+    def rrm_posterior(self, q):
+        """(mean, mean of squares, model frequency) of coefficient q, p values each."""
+        out = [np.empty(self.p, dtype=np.float64) for _ in range(3)]
+        self._chk(self._L.jwas_hip_rrm_get_posterior(self._h, int(q), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
+        return tuple(out)
+
+    def rrm_mul_alpha(self, q):
+        out = np.empty(self.n, dtype=np.float64)
+        self._chk(self._L.jwas_hip_rrm_mul_alpha(self._h, int(q), _ptr(out)))
+        return out
+
+    @staticmethod
+    def _rrm_full(cells, c):
+        """lower cells (a (a + 1) / 2 + b) on the last axis -> symmetric c x c"""
+        out = np.empty(cells.shape[:-1] + (c, c), dtype=np.float64)
+        for a in range(c):
+            for b in range(a + 1):
+                out[..., a, b] = out[..., b, a] = cells[..., a * (a + 1) // 2 + b]
+        return out
+
+    def rrm_m(self):
+        """M_j as p x c x c."""
+        T, c, _ = self._rrm
+        out = np.empty((self.p, c * (c + 1) // 2), dtype=np.float64)
+        self._chk(self._L.jwas_hip_rrm_get_m(self._h, out.size, _ptr(out)))
+        return self._rrm_full(out, c)
+
+    def rrm_gram(self, block):
+        """The Gram tensor of one block as b x b x c x c: [j, k] = sum_i x_ij x_ik O_i."""
+        T, c, bs = self._rrm
+        b = min(bs, self.p - int(block) * bs)
+        out = np.empty((max(b, 0), max(b, 0), c * (c + 1) // 2), dtype=np.float64)
+        self._chk(self._L.jwas_hip_rrm_get_gram(self._h, int(block), out.size, _ptr(out)))
+        return self._rrm_full(out, c)
+
+    def rrm_end(self):
+        self._chk(self._L.jwas_hip_rrm_end(self._h))
+        self._rrm = None
 
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""
