@@ -299,6 +299,14 @@ int  jwas_hip_residual_dev(jwas_hip_ctx* ctx, void** r_dev, int64_t* ld_dev);
  * all-reduce of the residual delta. */
 int  jwas_hip_residual_to_dev(jwas_hip_ctx* ctx, int32_t trait, void* dst_dev);
 int  jwas_hip_residual_from_dev(jwas_hip_ctx* ctx, int32_t trait, const void* src_dev);
+/* Several genotype categories in one model (MCMC_BayesianAlphabet.jl:224-226: `for Mi in mme.M` samples every category from the
+ * one ycorr): each category is a context of its own, and the residual changes hands between them.  Copies all ntraits residual
+ * vectors of src, pad rows included, into dst's resident residual, device to device, Float32 or Float64 contexts alike.  Ordered by
+ * events, without a host round trip or a host wait: the copy is queued on dst's stream and runs after everything queued on src's
+ * stream; src's stream in turn waits for the copy before it runs anything queued later.  A copy, not an alias: lifetimes stay per
+ * context.  JWAS_HIP_EINVAL unless device, precision, n, leading dimension and ntraits agree; JWAS_HIP_ESTATE unless both contexts
+ * hold genotypes and have had jwas_hip_init_state; dst == src is a no-op.  Errors are reported on dst. */
+int  jwas_hip_residual_handover(jwas_hip_ctx* dst, jwas_hip_ctx* src);
 /* r_k[i] = fl32(fl64(r_k[i]) + shift) for the n individuals: the residual correction of a location parameter whose design
  * column is all ones (the intercept step of the host's single-site Gibbs pass, solver.jl:143-162) without a host copy of
  * the residual -- with jwas_sweep_stats.resid_sum the intercept update needs no O(n) host traffic at all.  Asynchronous

@@ -109,6 +109,11 @@ hip_set_residual!(b::HipBackend, trait::Integer, r::Vector{Float32}) =
 hip_get_residual!(b::HipBackend, trait::Integer, r::Vector{Float32}) =
     hip_check(b.ctx, ccall((:jwas_hip_get_residual, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}), b.ctx, trait, r))
 
+"Several genotype categories (`for Mi in mme.M`, MCMC_BayesianAlphabet.jl:224-226): one backend per category; the residual of `src`
+(all traits) becomes `dst`'s, device to device, ordered on the two streams without a host wait."
+hip_residual_handover!(dst::HipBackend, src::HipBackend) =
+    hip_check(dst.ctx, ccall((:jwas_hip_residual_handover, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), dst.ctx, src.ctx))
+
 "Grouped launches for the selected block size: 2 or 4 consecutive blocks per launch of the step kernel (0 frees the buffers); the sweeps
 whose HipSweepParams carry group_launch = 1 then use them.  Worth its set-up time from a few thousand iterations on (INTEGRATION.md)."
 hip_setup_groups!(b::HipBackend, blocks_per_launch::Integer) =

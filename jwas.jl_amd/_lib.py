@@ -151,6 +151,7 @@ PROTOTYPES = {
     "jwas_hip_residual_dev": (_INT, [_vp, _P(_vp), _P(_i64)]),
     "jwas_hip_residual_to_dev": (_INT, [_vp, _i32, _vp]),
     "jwas_hip_residual_from_dev": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_residual_handover": (_INT, [_vp, _vp]),
     "jwas_hip_residual_sub_xalpha": (_INT, [_vp, _i32]),
     "jwas_hip_mul_alpha": (_INT, [_vp, _i32, _vp]),
     "jwas_hip_load_output_dense_f32": (_INT, [_vp, _vp, _i64, _i64, _i64]),

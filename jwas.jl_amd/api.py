@@ -10,7 +10,8 @@ Same names, argument meaning and error behaviour as reworkhow/JWAS.jl v2.3.6 (fi
 Everything that is NOT the marker sweep stays here on the host (numpy): data ingestion and QC,
 model parsing, fixed-effect Gibbs, variance-component and pi draws, output tables.  Model families
 outside the hot path (GBLUP, single-step analysis, prediction equations) are rejected with an
-explicit error: they stay on the reference.  Random regression models (RRM=Phi) have a driver of their own (rrm.py, csrc/rrm.hpp).  i.i.d. random effects (set_random) and large class factors run on the device
+explicit error: they stay on the reference.  Models with several genotype categories (y = intercept + geno1 + geno2) have a driver of
+their own (multigeno.py: one device context per category, the residual handed over between them).  Random regression models (RRM=Phi) have a driver of their own (rrm.py, csrc/rrm.hpp).  i.i.d. random effects (set_random) and large class factors run on the device
 (mcmc.py step 1, csrc/locpar.hpp).  Categorical / censored traits run here: their liabilities are sampled
 on the device (mcmc.py step 0, csrc/liability.hpp).
 """
@@ -350,8 +351,8 @@ def build_model(model_equations, R=False, *, df=4.0, estimate_variance=True, est
             else:
                 tl.append(ModelTerm(lhs, name))
         terms.append(tl)
-    if len(M) > 1:
-        raise NotImplementedError("one genotype category per model on the device path (reference: 'now only work for one geno')")
+    if len({Mi.name for Mi in M}) != len(M):
+        raise ValueError("every genotype category needs a term name of its own")
     nModels = len(traits)
     if not _is_false(R) and np.atleast_2d(np.asarray(R)).shape[0] != nModels:                 # :67-69
         raise ValueError(f"The residual covariance matrix is not a {nModels} by {nModels} matrix.")
@@ -523,6 +524,20 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     generator.  The choice is therefore part of what a seed means, as with location_parameters.  Not with storage=:stream,
     constraint=true or marker shards (explicit errors).
 
+    Several genotype categories (build_model("y = intercept + geno1 + geno2"); `for Mi in mme.M`, MCMC_BayesianAlphabet.jl:224-337): a
+    driver of its own (multigeno.py).  Every category is a device context with its own method, Pi, variances, block size and outputs
+    ("marker effects <name>", "pi_<name>", MCMC_samples_marker_effects_<name>_<trait>.txt, ..._variances_<name>.txt, ...pi_<name>.txt);
+    the one residual moves between the contexts on the device (jwas_hip_residual_handover) and category i draws from the counters
+    after those of the categories before it.  EBVs, genetic_variance and heritability are those of the sum over the categories;
+    the default genetic variance is var(y) / 2 / (number of categories) each.  Single-trait BayesA/B/C/R, RR-BLUP, BayesL chosen
+    per category; multi-trait (2-4 traits, complete records) BayesC under samplers I and II and RR-BLUP; dense or storage=:stream
+    per category; Float32, or double_precision=True with every category dense Float64; heterogeneous_residuals; outputEBV(model, IDs)
+    for dense categories; location parameters on the host.  `_engine`: a list with one engine per category.  All categories must
+    hold the same individuals ("genotypic information is not provided for same individuals").  Not with fast_blocks,
+    independent_blocks, location_parameters="device", set_random, categorical / censored traits, causal_structure, RRM, annotations,
+    marker starting values, constraint=true, multi-trait BayesA/B/L, missing traits, device_genotypes or marker shards (explicit
+    errors); the adaptive block-size switching, grouped launches and the section solve are off in this driver.
+
     RRM (JWAS.jl:177,464-475; RRM/RRM.jl, RRM/MCMC_BayesianAlphabet_RRM.jl): a T x c numeric matrix Phi, one row per distinct time point
     (ascending; generatefullPhi builds normalised Legendre columns) -- the random regression model for longitudinal records: the
     first column of df holds the IDs, the column `time` the time point of every record, every marker carries c coefficients.  A
@@ -555,6 +570,18 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     if independent_blocks and fast_blocks is False:
         raise ValueError("independent_blocks=true requires fast_blocks != false.")             # :242-244
     from . import rrm as _rrm
+    multigeno = len(model.M) > 1              # several genotype categories: a driver of its own (multigeno.py), validated before anything is written
+    if multigeno:
+        from . import multigeno as _mg
+        for flag, name in ((single_step_analysis, "single_step_analysis"), (update_priors_frequency, "update_priors_frequency"),
+                           (prediction_equation, "prediction_equation")):
+            if not _is_false(flag) and flag != 0:
+                raise NotImplementedError(f"runMCMC(...; {name}=...) is outside the device marker path and stays on the reference")
+        if location_parameters not in ("auto", "host", "device"):
+            raise ValueError('location_parameters must be "auto", "host" or "device".')
+        _engine = _mg.validate(model, df, fast_blocks=fast_blocks, independent_blocks=independent_blocks,
+                               location_parameters=location_parameters, causal_structure=causal_structure, RRM=RRM,
+                               starting_value=starting_value, double_precision=bool(double_precision), engines=_engine)
     rrm_phi = None
     if _rrm.is_phi(RRM):                                                                       # JWAS.jl:464-475
         for flag, name in ((single_step_analysis, "single_step_analysis"), (update_priors_frequency, "update_priors_frequency"),
@@ -616,6 +643,14 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
         output_folder = myfolder + str(folderi)
         folderi += 1
     os.makedirs(output_folder)
+    if multigeno:
+        return _mg.run_multigeno(model, df, chain_length=int(chain_length), burnin=int(burnin),
+                                 output_samples_frequency=int(output_samples_frequency), seed=seed,
+                                 heterogeneous_residuals=bool(heterogeneous_residuals), double_precision=bool(double_precision),
+                                 outputEBV=outputEBV, output_heritability=bool(output_heritability), output_folder=output_folder,
+                                 printout_frequency=printout_frequency, memory_guard=memory_guard, memory_guard_ratio=memory_guard_ratio,
+                                 device=device, block_size=block_size, gram_mode=gram_mode, engines=_engine,
+                                 printout_model_info=printout_model_info, output_samples_for_all_parameters=output_samples_for_all_parameters)
     if rrm_phi is not None:
         return _rrm.run_rrm(model, df, rrm_phi, chain_length=int(chain_length), burnin=int(burnin),
                             output_samples_frequency=int(output_samples_frequency), seed=seed, double_precision=bool(double_precision),

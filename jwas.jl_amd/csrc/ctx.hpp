@@ -123,6 +123,7 @@ struct jwas_hip_ctx {
     double* lpr_mat = nullptr;          // p x 2^t marker-specific multi-trait log priors
     bool    lpr_active = false;         // ... in use by the current sweep
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    hipEvent_t ev_hand = nullptr;       // jwas_hip_residual_handover: recorded on this context's stream only (no timing)
     int timing_stride = 0;
     double last_events = -1.0;          // effect changes of the previous sweep (-1: none yet)
     static constexpr int kCounters = 32;                    // = jw::kNCounters of kernels.hpp (jwas_hip.hip asserts it)

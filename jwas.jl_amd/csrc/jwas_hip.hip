@@ -83,6 +83,7 @@ int jwas_hip_create(int device, jwas_hip_ctx** out)
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(nullptr, JWAS_HIP_EHIP, "hipStreamCreate failed"); }
     c->own_stream = true;
     if (hipEventCreate(&c->ev_start) != hipSuccess || hipEventCreate(&c->ev_stop) != hipSuccess) { delete c; return fail(nullptr, JWAS_HIP_EHIP, "hipEventCreate failed"); }
+    if (hipEventCreateWithFlags(&c->ev_hand, hipEventDisableTiming) != hipSuccess) { delete c; return fail(nullptr, JWAS_HIP_EHIP, "hipEventCreate failed"); }
     *out = c;
     return JWAS_HIP_OK;
 }
@@ -161,6 +162,7 @@ void jwas_hip_destroy(jwas_hip_ctx* c)
     }
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
+    if (c->ev_hand) (void)hipEventDestroy(c->ev_hand);
     for (hipEvent_t e : c->kev) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -979,6 +981,32 @@ int jwas_hip_residual_from_dev(jwas_hip_ctx* c, int32_t trait, const void* src)
     NEED_TRAIT(c, trait);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(c->r + (size_t)trait * c->ld, src, sizeof(float) * c->n, hipMemcpyDeviceToDevice, c->stream));
+    return JWAS_HIP_OK;
+}
+
+// The residual changes hands between two contexts of one model (several genotype categories: MCMC_BayesianAlphabet.jl:224-226 reads
+// the one ycorr for every Mi): all ntraits vectors of src, pad rows included, into dst's resident residual, device to device.  Ordered by
+// events, no host round trip and no host wait: the copy is queued on dst's stream behind everything queued on src's, and src's stream
+// waits for the copy, so what either context queues next sees the other's side finished.  A copy, not an alias.
+int jwas_hip_residual_handover(jwas_hip_ctx* dst, jwas_hip_ctx* src)
+{
+    NEED(dst, dst, JWAS_HIP_EINVAL, "dst is NULL");
+    NEED(dst, src, JWAS_HIP_EINVAL, "src is NULL");
+    NEED(dst, residual_ptr(dst) && dst->method >= 0, JWAS_HIP_ESTATE, "dst: load genotypes and call jwas_hip_init_state first");
+    NEED(dst, residual_ptr(src) && src->method >= 0, JWAS_HIP_ESTATE, "src: load genotypes and call jwas_hip_init_state first");
+    NEED(dst, dst->device == src->device, JWAS_HIP_EINVAL, "the contexts are on different devices (%d, %d)", dst->device, src->device);
+    NEED(dst, IS_F64(dst) == IS_F64(src), JWAS_HIP_EINVAL, "the contexts differ in precision");
+    NEED(dst, dst->n == src->n && dst->ld == src->ld, JWAS_HIP_EINVAL, "the contexts differ in n or leading dimension (%lld / %lld, %lld / %lld)",
+         (long long)dst->n, (long long)dst->ld, (long long)src->n, (long long)src->ld);
+    NEED(dst, dst->ntraits == src->ntraits, JWAS_HIP_EINVAL, "the contexts differ in the number of traits (%d, %d)", dst->ntraits, src->ntraits);
+    if (dst == src) return JWAS_HIP_OK;
+    HIPCHK(dst, hipSetDevice(dst->device));
+    const size_t bytes = (IS_F64(dst) ? sizeof(double) : sizeof(float)) * (size_t)dst->ntraits * (size_t)dst->ld;
+    HIPCHK(dst, hipEventRecord(src->ev_hand, src->stream));
+    HIPCHK(dst, hipStreamWaitEvent(dst->stream, src->ev_hand, 0));
+    HIPCHK(dst, hipMemcpyAsync(residual_ptr(dst), residual_ptr(src), bytes, hipMemcpyDeviceToDevice, dst->stream));
+    HIPCHK(dst, hipEventRecord(dst->ev_hand, dst->stream));
+    HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_hand, 0));
     return JWAS_HIP_OK;
 }
 

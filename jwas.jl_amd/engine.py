@@ -370,6 +370,11 @@ class HipEngine:
     def residual_from_dev(self, src_ptr, trait=0):
         self._chk(self._L.jwas_hip_residual_from_dev(self._h, int(trait), C.c_void_p(int(src_ptr))))
 
+    def residual_handover(self, src_engine):
+        """This engine's resident residual := src_engine's (all traits, device to device, ordered by events on the two streams:
+        jwas_hip_residual_handover) -- the one residual of a model with several genotype categories moving to the next category."""
+        self._chk(self._L.jwas_hip_residual_handover(self._h, src_engine._h))
+
     def residual_add_scalar(self, shift, trait=0):
         """r_trait += shift on the device (the intercept's residual correction; no host copy of the residual)."""
         self._chk(self._L.jwas_hip_residual_add_scalar(self._h, int(trait), float(shift)))
