@@ -44,6 +44,9 @@
  *                              overall marker effects (structure_equation_model/SEM.jl:53-165,245-252)
  *   jwas_hip_rrm_*             the marker sweep of runMCMC(...; RRM = Phi): BayesABCRRM!, get_mΦΦarray and the running means of
  *                              MCMC_BayesianAlphabet_RRM (RRM/RRM.jl:43-57,101-158; RRM/MCMC_BayesianAlphabet_RRM.jl:123-144,212-218)
+ *   jwas_hip_mega_*            constraint = true with up to 64 traits: megaBayesABC! / megaBayesC0!, t independent single-trait
+ *                              chains over one genotype matrix (markers/BayesianAlphabet/BayesABC.jl:1-58), and
+ *                              sampleMissingResiduals under a diagonal R (residual.jl:51-73)
  *
  * Conventions: every entry point returns 0 on success and a negative JWAS_HIP_E* code on failure
  * (no exceptions cross the boundary; jwas_hip_last_error() returns the message -- the analogue of
@@ -699,6 +702,77 @@ int  jwas_hip_rrm_get_gram(jwas_hip_ctx* ctx, int64_t block, int64_t nvalues, do
 /* Device bytes of a session (pure; an upper bound). */
 int64_t jwas_hip_rrm_estimate_bytes(int64_t n, int64_t p, int32_t T, int32_t c, int32_t block_size);
 int  jwas_hip_rrm_end(jwas_hip_ctx* ctx);
+
+/* ---- mega-trait models: constraint = true with up to 64 traits (csrc/mega.hpp) --------------------------------------------------------
+ * megaBayesABC! (markers/BayesianAlphabet/BayesABC.jl:1-8) runs T independent single-trait chains over ONE genotype matrix; the
+ * sweep entry point above stops at JWAS_HIP_MAX_TRAITS.  A session keeps per trait k a residual r_k (n doubles), alpha_k, beta_k,
+ * delta_k (p each) and their running means, and once for all traits x'x and the within-block Grams G_ij = x_i'x_j (8 p b bytes),
+ * all in double whatever the context's element type; the genotypes are the context's (dense Float32 or Float64).  One marker of
+ * one trait, markers in order (bayesabc_update_marker!, BayesABC.jl:24-58), with vare_k, the trait's effect variance v_k and pi_k:
+ *   rhs = (x'r + x'x alpha) / vare,  lhs = x'x / vare + 1 / v,  gHat = rhs / lhs,
+ *   logDelta1 = -0.5 (log lhs + log v - gHat rhs) + log(1 - pi),  logDelta0 = log pi,  probDelta1 = 1 / (1 + exp(logDelta0 - logDelta1)),
+ *   u < probDelta1: delta = 1, beta = alpha = gHat + z / sqrt(lhs);  else delta = 0, alpha = 0, beta = z sqrt(v)   (BayesABC.jl:54);
+ *   pi = 0 (RR-BLUP, megaBayesC0!) includes every marker.
+ * The device runs the exact block form: per block of <= 256 markers the right-hand sides of ALL traits from the residuals at block
+ * entry in one pass over the block's genotypes (a small GEMM X_b'R), corrected inside the block through the Gram, the residuals
+ * brought up to date at the next block's entry.  Draws: philox4x32_10(marker, iteration, 0x01000000 | trait_id, slot), slot 10 the
+ * uniform, slot 11 the normal; (record, iteration, 0x01000000 | trait_id, 12) the normal of a missing cell; trait_id = first_trait +
+ * k.  No sum of trait k depends on T: trait k of a T-trait session is bit-equal to a one-trait session with first_trait = k.  No
+ * floating-point atomics: the same seed gives the same bits.
+ * Limits: 1 <= T <= 64 (JWAS_HIP_MEGA_MAX_TRAITS), block size <= 256 (0: 64), uniform blocks, first_trait + T <= 2^24.
+ * Errors: JWAS_HIP_ESTATE without loaded genotypes or, for every other entry point, without an open session; JWAS_HIP_EUNSUP on 2-bit
+ * packed storage, with residual weights and on marker or row shards; JWAS_HIP_EINVAL for T, the block size or first_trait out of
+ * range, a trait index outside [0, T), a wrong length, non-finite values, vare or var_effect not positive and finite, pi outside
+ * [0, 1].  A failed _begin opens nothing; _begin on an open session replaces it.  The session is freed by _end, jwas_hip_destroy or
+ * loading genotypes. */
+#define JWAS_HIP_MEGA_MAX_TRAITS 64
+#define JWAS_HIP_MEGA_MAX_BLOCK 256
+typedef struct jwas_mega_params {
+    uint32_t iteration;                 /* MCMC iteration >= 1 (enters the RNG counter)                                          */
+    uint32_t reserved;
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                     */
+    const double* vare;                 /* [T] vare[k,k]                                                                         */
+    const double* var_effect;           /* [T] the marker-effect variance of every trait (_sweep only; _impute ignores it)       */
+    const double* pi;                   /* [T] Pr(delta = 0) of every trait (_sweep only)                                        */
+} jwas_mega_params;
+typedef struct jwas_mega_stats {        /* every pointer: T doubles of the caller (any may be NULL)                              */
+    double* sum_delta;                  /* markers in the model (samplePi, MCMC_BayesianAlphabet.jl:299)                         */
+    double* beta_ss;                    /* beta'beta (sample_marker_effect_variance, constraint branch)                          */
+    double* alpha_ss;                   /* alpha'alpha                                                                           */
+    double* resid_ss;                   /* sum r^2 after the sweep (variance_components.jl:104-109)                              */
+    double* resid_sum;                  /* sum r                                                                                 */
+    double* n_changed;                  /* markers whose effect moved                                                            */
+    double  step_ms;                    /* device time of the sweep (HIP events on the context's stream)                         */
+} jwas_mega_stats;
+/* Open a session of ntraits traits on the loaded genotypes: x'x and the block Grams; residuals, alpha and beta 0, delta 1
+ * (BayesABC.jl:1-8: one BayesABC! per trait). */
+int  jwas_hip_mega_begin(jwas_hip_ctx* ctx, int32_t ntraits, int32_t block_size, int32_t first_trait);
+/* missing_T_n: row-major T x n bytes, nonzero where the record misses the trait (mme.missingPattern negated, residual.jl:17-21);
+ * NULL: complete records. */
+int  jwas_hip_mega_set_missing(jwas_hip_ctx* ctx, int64_t nvalues, const uint8_t* missing_T_n);
+/* The residual of one trait, n doubles (wArray[i], MCMC_BayesianAlphabet.jl:131-157). */
+int  jwas_hip_mega_set_residual(jwas_hip_ctx* ctx, int32_t trait, const double* r_n);
+int  jwas_hip_mega_get_residual(jwas_hip_ctx* ctx, int32_t trait, double* out_n);
+/* alpha, beta, delta of one trait, p doubles each; any may be NULL (genotypes.α[i], β[i], δ[i]). */
+int  jwas_hip_mega_set_state(jwas_hip_ctx* ctx, int32_t trait, const double* alpha, const double* beta, const double* delta);
+int  jwas_hip_mega_get_state(jwas_hip_ctx* ctx, int32_t trait, double* alpha, double* beta, double* delta);
+/* Every missing cell redrawn from N(0, vare_k) (sampleMissingResiduals, residual.jl:51-73, with a diagonal R). */
+int  jwas_hip_mega_impute(jwas_hip_ctx* ctx, const jwas_mega_params* params);
+/* One sweep over all markers of all traits (megaBayesABC!, BayesABC.jl:1-8,24-58).  Synchronous. */
+int  jwas_hip_mega_sweep(jwas_hip_ctx* ctx, const jwas_mega_params* params, jwas_mega_stats* stats);
+/* Running mean, mean of squares and model frequency of every effect (output.jl:556-577). */
+int  jwas_hip_mega_accumulate(jwas_hip_ctx* ctx, double nsamples);
+/* ... of one trait: p values each, any may be NULL. */
+int  jwas_hip_mega_get_posterior(jwas_hip_ctx* ctx, int32_t trait, double* mean, double* mean2, double* freq);
+/* out = X alpha_k (getEBV, output.jl:281-306): n doubles over the context's rows, or n_out over the rows of the second resident
+ * matrix (Mi.output_genotypes) when use_output_rows != 0. */
+int  jwas_hip_mega_mul_alpha(jwas_hip_ctx* ctx, int32_t trait, int32_t use_output_rows, double* out);
+/* The Gram of one block, b x b doubles with b the block's markers, and (out_xpx != NULL) the block's x'x, b doubles
+ * (GibbsMats, tools4genotypes.jl:28-36). */
+int  jwas_hip_mega_get_gram(jwas_hip_ctx* ctx, int64_t block, int64_t nvalues, double* out_gram, double* out_xpx);
+/* Device bytes of a session (pure; an upper bound). */
+int64_t jwas_hip_mega_estimate_bytes(int64_t n, int64_t p, int32_t ntraits, int32_t block_size);
+int  jwas_hip_mega_end(jwas_hip_ctx* ctx);
 
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the

@@ -550,6 +550,86 @@ hip_rrm_estimate_bytes(n::Integer, p::Integer, T::Integer, c::Integer, block_siz
     ccall((:jwas_hip_rrm_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int32, Int32, Int32), n, p, T, c, block_size)
 hip_rrm_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_rrm_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
 
+"Mega-trait models on the device: constraint = true with up to 64 traits (markers/BayesianAlphabet/BayesABC.jl:1-58; csrc/mega.hpp).
+`hip_mega_begin!` opens a session of t independent single-trait chains on the loaded genotypes (x'x and the block Grams);
+`hip_mega_set_residual!` / `hip_mega_residual` move one wArray[i]; `hip_mega_impute!` stands for sampleMissingResiduals under a
+diagonal R; `hip_mega_sweep!` replaces the Threads.@threads loop of megaBayesABC! and returns what samplePi, the constrained
+sample_marker_effect_variance and sample_variance read, one value per trait.  Traits are 1-based here.  Limits: t <= 64, blocks <= 256
+markers, dense genotypes, no residual weights, no shards."
+struct HipMegaParams
+    iteration::UInt32
+    reserved::UInt32
+    seed::UInt64
+    vare::Ptr{Float64}
+    var_effect::Ptr{Float64}
+    pi::Ptr{Float64}
+end
+struct HipMegaStats
+    sum_delta::Ptr{Float64}
+    beta_ss::Ptr{Float64}
+    alpha_ss::Ptr{Float64}
+    resid_ss::Ptr{Float64}
+    resid_sum::Ptr{Float64}
+    n_changed::Ptr{Float64}
+    step_ms::Float64
+end
+hip_mega_begin!(b::HipBackend, ntraits::Integer, block_size::Integer=256, first_trait::Integer=0) =
+    hip_check(b.ctx, ccall((:jwas_hip_mega_begin, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int32, Int32), b.ctx, ntraits, block_size, first_trait))
+# missing: n x t Bool in Julia (mme.missingPattern negated) == the library's row-major t x n bytes
+hip_mega_set_missing!(b::HipBackend, missing::AbstractMatrix{Bool}) = (m = Matrix{UInt8}(missing);
+    hip_check(b.ctx, ccall((:jwas_hip_mega_set_missing, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{UInt8}), b.ctx, length(m), m)))
+hip_mega_set_residual!(b::HipBackend, trait::Integer, r::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_mega_set_residual, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), b.ctx, trait - 1, r))
+function hip_mega_residual(b::HipBackend, trait::Integer, n::Integer)
+    r = Vector{Float64}(undef, n)
+    hip_check(b.ctx, ccall((:jwas_hip_mega_get_residual, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), b.ctx, trait - 1, r))
+    return r
+end
+hip_mega_set_state!(b::HipBackend, trait::Integer, α::Vector{Float64}, β::Vector{Float64}, δ::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_mega_set_state, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.ctx, trait - 1, α, β, δ))
+function hip_mega_state(b::HipBackend, trait::Integer, p::Integer)
+    α, β, δ = (Vector{Float64}(undef, p) for _ in 1:3)
+    hip_check(b.ctx, ccall((:jwas_hip_mega_get_state, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.ctx, trait - 1, α, β, δ))
+    return α, β, δ
+end
+function hip_mega_impute!(b::HipBackend, iter::Integer, seed::Integer, vare::Vector{Float64})
+    GC.@preserve vare begin
+        P = HipMegaParams(UInt32(iter), UInt32(0), UInt64(seed), pointer(vare), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL))
+        hip_check(b.ctx, ccall((:jwas_hip_mega_impute, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipMegaParams}), b.ctx, Ref(P)))
+    end
+end
+function hip_mega_sweep!(b::HipBackend, iter::Integer, seed::Integer, vare::Vector{Float64}, var_effect::Vector{Float64}, pi::Vector{Float64})
+    t = length(vare)
+    out = [zeros(Float64, t) for _ in 1:6]      # sum_delta, beta_ss, alpha_ss, resid_ss, resid_sum, n_changed
+    S = Ref(HipMegaStats(pointer.(out)..., 0.0))
+    GC.@preserve vare var_effect pi out begin
+        P = HipMegaParams(UInt32(iter), UInt32(0), UInt64(seed), pointer(vare), pointer(var_effect), pointer(pi))
+        hip_check(b.ctx, ccall((:jwas_hip_mega_sweep, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipMegaParams}, Ref{HipMegaStats}), b.ctx, Ref(P), S))
+    end
+    return (sum_delta=out[1], beta_ss=out[2], alpha_ss=out[3], resid_ss=out[4], resid_sum=out[5], n_changed=out[6], step_ms=S[].step_ms)
+end
+hip_mega_accumulate!(b::HipBackend, nsamples::Real) =
+    hip_check(b.ctx, ccall((:jwas_hip_mega_accumulate, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Float64), b.ctx, nsamples))
+function hip_mega_posterior(b::HipBackend, trait::Integer, p::Integer)
+    m, m2, f = (Vector{Float64}(undef, p) for _ in 1:3)
+    hip_check(b.ctx, ccall((:jwas_hip_mega_get_posterior, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.ctx, trait - 1, m, m2, f))
+    return m, m2, f
+end
+"X α_i over the training rows, or (output_rows) over the rows of hip_load_output_dense: n_rows values."
+function hip_mega_mul_alpha(b::HipBackend, trait::Integer, n_rows::Integer; output_rows::Bool=false)
+    out = Vector{Float64}(undef, n_rows)
+    hip_check(b.ctx, ccall((:jwas_hip_mega_mul_alpha, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), b.ctx, trait - 1, output_rows, out))
+    return out
+end
+function hip_mega_gram(b::HipBackend, k::Integer, nb::Integer)
+    G, xpx = Matrix{Float64}(undef, nb, nb), Vector{Float64}(undef, nb)
+    hip_check(b.ctx, ccall((:jwas_hip_mega_get_gram, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}), b.ctx, k - 1, length(G), G, xpx))
+    return G, xpx
+end
+hip_mega_estimate_bytes(n::Integer, p::Integer, ntraits::Integer, block_size::Integer=256) =
+    ccall((:jwas_hip_mega_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int32, Int32), n, p, ntraits, block_size)
+hip_mega_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_mega_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

@@ -20,6 +20,7 @@ ANNOT_MAX_COLS = 64                     # columns of the annotation design matri
 ANNOT_BAYESC, ANNOT_BAYESR, ANNOT_TREE = 0, 1, 2
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
 RRM_MIN_COEFF, RRM_MAX_COEFF, RRM_MAX_TIMES, RRM_MAX_BLOCK = 2, 4, 64, 256      # csrc/rrm.hpp
+MEGA_MAX_TRAITS, MEGA_MAX_BLOCK, MEGA_TRAIT_TILE = 64, 256, 8                   # csrc/mega.hpp (JWAS_HIP_MEGA_MAX_TRAITS, _MAX_BLOCK, kTT)
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
 # enum jwas_hip_schedule_flags (jwas_hip_last_sweep_schedule): name -> bit
@@ -111,6 +112,16 @@ class RrmParams(C.Structure):
 class RrmStats(C.Structure):
     _fields_ = [("state_counts", C.c_double * MAX_STATES), ("beta_ss", C.c_double * (MAX_TRAITS * MAX_TRAITS)), ("alpha_ss", C.c_double),
                 ("resid_ss", C.c_double), ("n_changed", C.c_double), ("step_ms", C.c_double)]
+
+
+class MegaParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("vare", C.c_void_p), ("var_effect", C.c_void_p),
+                ("pi", C.c_void_p)]
+
+
+class MegaStats(C.Structure):
+    _fields_ = [("sum_delta", C.c_void_p), ("beta_ss", C.c_void_p), ("alpha_ss", C.c_void_p), ("resid_ss", C.c_void_p), ("resid_sum", C.c_void_p),
+                ("n_changed", C.c_void_p), ("step_ms", C.c_double)]
 
 
 class JwasHipError(RuntimeError):
@@ -273,6 +284,20 @@ PROTOTYPES = {
     "jwas_hip_rrm_get_gram": (_INT, [_vp, _i64, _i64, _vp]),
     "jwas_hip_rrm_estimate_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
     "jwas_hip_rrm_end": (_INT, [_vp]),
+    "jwas_hip_mega_begin": (_INT, [_vp, _i32, _i32, _i32]),
+    "jwas_hip_mega_set_missing": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_mega_set_residual": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_mega_get_residual": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_mega_set_state": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_mega_get_state": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_mega_impute": (_INT, [_vp, _P(MegaParams)]),
+    "jwas_hip_mega_sweep": (_INT, [_vp, _P(MegaParams), _P(MegaStats)]),
+    "jwas_hip_mega_accumulate": (_INT, [_vp, C.c_double]),
+    "jwas_hip_mega_get_posterior": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_mega_mul_alpha": (_INT, [_vp, _i32, _i32, _vp]),
+    "jwas_hip_mega_get_gram": (_INT, [_vp, _i64, _i64, _vp, _vp]),
+    "jwas_hip_mega_estimate_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "jwas_hip_mega_end": (_INT, [_vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 

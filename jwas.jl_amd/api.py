@@ -538,6 +538,23 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     marker starting values, constraint=true, multi-trait BayesA/B/L, missing traits, device_genotypes or marker shards (explicit
     errors); the adaptive block-size switching, grouped launches and the section solve are off in this driver.
 
+    More than 4 traits (5 to 64; megaBayesABC! / megaBayesC0!, markers/BayesianAlphabet/BayesABC.jl:1-8): a driver of its own
+    (megatrait.py) with the marker sweep of all traits in one pass over the genotypes on the device (csrc/mega.hpp).  The model
+    needs constraint=True in BOTH get_genotypes and build_model (zero genetic and residual covariances: t independent single-trait
+    chains), one genotype category, BayesC (estimatePi true or false; Pi a scalar or one value per trait) or RR-BLUP, dense
+    storage, Float32 or double_precision=True; records may miss some traits (their residuals are redrawn on the device every
+    iteration); location parameters on the host; block_size <= 256 (default 256).  Outputs as a multi-trait constraint=true run of
+    1 to 4 traits writes them: marker effects <genotypes>, pi_<genotypes> (one per trait), marker effects variance <genotypes>,
+    residual variance, EBV_<trait>, genetic_variance, heritability, the MCMC_samples_* files and the sparse .bin marker samples;
+    outputEBV(model, IDs) covers genotyped individuals without records.  Everything else with more than 4 traits raises
+    NotImplementedError naming the argument before anything is written: no constraint=True on either side (the joint 2^t-state
+    samplers), BayesA/B/L/R, annotations, storage=:stream, fast_blocks, independent_blocks, heterogeneous_residuals,
+    location_parameters="device", set_random, categorical / censored traits, causal_structure, RRM, several genotype categories,
+    starting values, shards, more than 64 traits.  Speed (scripts/mega_bench.py, 20 000 x 100 000, pi = 0.95, one MI355X): 25.3 ms per
+    sweep at 8 traits and 39.4 at 64, against 14.8 ms per FOUR traits on the existing MegaBayesC sweep -- 1.17 and 6.0 times as fast
+    per trait; below about 7 traits the session is slower per trait than that sweep (0.65 of its speed at 4): NOTES.md, "Mega-trait
+    models".
+
     RRM (JWAS.jl:177,464-475; RRM/RRM.jl, RRM/MCMC_BayesianAlphabet_RRM.jl): a T x c numeric matrix Phi, one row per distinct time point
     (ascending; generatefullPhi builds normalised Legendre columns) -- the random regression model for longitudinal records: the
     first column of df holds the IDs, the column `time` the time point of every record, every marker carries c coefficients.  A
@@ -570,6 +587,12 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     if independent_blocks and fast_blocks is False:
         raise ValueError("independent_blocks=true requires fast_blocks != false.")             # :242-244
     from . import rrm as _rrm
+    from . import megatrait as _mt
+    megatrait = _mt.routes(model)             # more than 4 traits: a driver of its own (megatrait.py), validated before anything is written
+    if megatrait:
+        _mt.validate(model, df, fast_blocks=fast_blocks, independent_blocks=independent_blocks, causal_structure=causal_structure, RRM=RRM,
+                     location_parameters=location_parameters, heterogeneous_residuals=heterogeneous_residuals, starting_value=starting_value,
+                     block_size=block_size, single_step_analysis=single_step_analysis, annotation_priors=annotation_priors, engine=_engine)
     multigeno = len(model.M) > 1              # several genotype categories: a driver of its own (multigeno.py), validated before anything is written
     if multigeno:
         from . import multigeno as _mg
@@ -651,6 +674,13 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
                                  printout_frequency=printout_frequency, memory_guard=memory_guard, memory_guard_ratio=memory_guard_ratio,
                                  device=device, block_size=block_size, gram_mode=gram_mode, engines=_engine,
                                  printout_model_info=printout_model_info, output_samples_for_all_parameters=output_samples_for_all_parameters)
+    if megatrait:
+        return _mt.run_megatrait(model, df, chain_length=int(chain_length), burnin=int(burnin),
+                                 output_samples_frequency=int(output_samples_frequency), seed=seed, double_precision=bool(double_precision),
+                                 outputEBV=outputEBV, output_heritability=bool(output_heritability), output_folder=output_folder,
+                                 printout_frequency=printout_frequency, missing_phenotypes=missing_phenotypes, device=device,
+                                 block_size=block_size, engine=_engine, printout_model_info=printout_model_info,
+                                 output_samples_for_all_parameters=output_samples_for_all_parameters)
     if rrm_phi is not None:
         return _rrm.run_rrm(model, df, rrm_phi, chain_length=int(chain_length), burnin=int(burnin),
                             output_samples_frequency=int(output_samples_frequency), seed=seed, double_precision=bool(double_precision),

@@ -297,6 +297,28 @@ struct jwas_hip_ctx {
         double* row = nullptr;                              // [ld] X alpha_q
         void* ev = nullptr;                                 // jwr::Events: the change list of the last sampled block
     } rr;
+    // Mega-trait model (jwas_hip_mega_begin .. _end; markers/BayesianAlphabet/BayesABC.jl:1-58; csrc/mega.hpp): T independent
+    // single-trait chains over the context's genotypes, a sweep of its own with its own residuals and state, all double
+    struct Mega {
+        bool active = false;
+        int nt = 0, bs = 0;                                 // traits, block size
+        uint32_t first_trait = 0;                           // the trait id of trait 0 in the RNG counter
+        int64_t nblocks = 0, mask_words = 0, row_cap = 0;
+        DevOwner mem;
+        std::vector<uint8_t> miss_host;                     // [nt][n] 1: the cell is missing (empty: none)
+        uint32_t* mask = nullptr;                           // [nt][ld / 32] bit i: record i misses the trait
+        double* R = nullptr;                                // [nt][ld] the residuals (pad rows 0)
+        double* xpx = nullptr;                              // [p]
+        double* gram = nullptr;                             // [nblocks][bs][bs]
+        double *alpha = nullptr, *beta = nullptr, *delta = nullptr;               // [nt][p]
+        double *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;          // [nt][p]
+        double* partials = nullptr;                         // [nslices][nt][bs]
+        double* par = nullptr;                              // [kParSize][nt] the per-trait parameters of the running sweep
+        double* stat = nullptr;                             // [nt][kStSize] | [nt][nslices][2] sum r^2, sum r per slice
+        double* row = nullptr;                              // [row_cap] X alpha_k
+        void* ev = nullptr;                                 // jwg::Events: the change lists of the last sampled block
+        std::vector<double> par_host;                       // what par was filled from (kept until the sweep has finished)
+    } mg;
 };
 
 // ---- errors ------------------------------------------------------------------------------------------------------------------------
@@ -354,6 +376,7 @@ JW_LOCAL void mtmiss_free(jwas_hip_ctx* c);
 JW_LOCAL void annot_free(jwas_hip_ctx* c);
 JW_LOCAL void sem_free(jwas_hip_ctx* c);
 JW_LOCAL void rrm_free(jwas_hip_ctx* c);
+JW_LOCAL void mega_free(jwas_hip_ctx* c);
 
 // `words` ("liabilities", "annotation priors", ...) are not driven from a context that holds a marker or row shard
 static inline int refuse_shards(jwas_hip_ctx* c, const char* words)

@@ -1,0 +1,382 @@
+// mega.hpp -- mega-trait models on the device: constraint=true with up to 64 traits, the sweep of megaBayesABC! / megaBayesC0!
+// (markers/BayesianAlphabet/BayesABC.jl:1-8): T independent single-trait chains over ONE genotype matrix.
+//
+// n individuals (genotype rows, the context's dense Float32 or Float64 matrix X, [p][ld], pad rows 0), T traits.  Per trait k:
+// the residual r_k [ld] (pad rows 0), alpha_k, beta_k, delta_k [p] and their running means; vare_k = vare[k,k], v_k the trait's
+// marker-effect variance, pi_k the trait's exclusion probability.  Shared by all traits, fixed at set-up (double):
+//   xpx_j = x_j'x_j                       G_ij = x_i'x_j for the marker pairs WITHIN a block (G_jj and xpx_j are the same sum)
+// One marker of one trait, markers in order (bayesabc_update_marker!, BayesABC.jl:24-58):
+//   rhs = (x_j'r + xpx_j alpha_j) / vare,   lhs = xpx_j / vare + 1 / v,   gHat = rhs / lhs
+//   logDelta1 = -0.5 (log lhs + log v - gHat rhs) + log(1 - pi),   logDelta0 = log pi,   probDelta1 = 1 / (1 + exp(logDelta0 - logDelta1))
+//   u < probDelta1:  delta = 1, beta = gHat + z sqrt(1 / lhs), alpha = beta;   else  delta = 0, beta = z sqrt(v), alpha = 0
+//   r += x_j (alpha_old - alpha_new).   pi = 0 (RR-BLUP, megaBayesC0!): logDelta0 = -Inf, exp(-Inf) = 0, probDelta1 = 1 -- no NaN.
+//
+// EXACT BLOCK FORM (as rrm.hpp).  For a block B: s_j[k] = x_j'r_k for all j in B and all k from the residual at block entry; when
+// marker j of trait k changes by d = alpha_old - alpha_new, s_i[k] += G_ij d for every i in B; at block exit r_k += sum_j x_j d_jk.
+// Per block two stream-ordered launches, no lookahead:
+//   k_mega_update_partial  grid (row slices, trait tiles): one 256-row slice and kTT = 8 traits per workgroup.  Phase 1, one row per
+//                          thread: the previous block's change list of every trait of the tile is applied to the row in list order
+//                          (r = r + x * d), the row's values go to LDS [trait][row].  Phase 2, a split-K GEMM over the rows: the
+//                          slice's b x kTT tile of X_b'R.  The 256 threads are `parts` = 256 / bp row parts x bp markers (bp = 64,
+//                          128 or 256, the smallest that holds the block); a thread adds its part's rows in ascending order into
+//                          one accumulator per trait (x read four rows at a time, the residual broadcast from LDS), the parts meet
+//                          in LDS in ascending order.
+//   k_mega_sample          one workgroup per trait: s = the slice partials in ascending slice order (one marker per thread); wave 0
+//                          walks the block 64 markers at a time by speculative evaluation (every pending lane tests its marker
+//                          against the current s, the first changed marker commits, its Gram row -- b doubles, read from L2 --
+//                          corrects s); the trait's change list and statistics.
+//   k_mega_finish          grid (row slices, traits): the last change list, then sum r^2 and sum r of the slice.
+//   k_mega_impute          grid (row chunks, traits): a missing cell (bit mask [T][ld / 32]) is redrawn from N(0, vare_k) -- with a
+//                          diagonal R the conditional law of a missing residual whatever the record's other traits
+//                          (sampleMissingResiduals, residual.jl:51-73, with Rc = 0).  Observed cells and pad rows are never written.
+//
+// ORDER OF EVERY SUM (no floating-point atomics: the same seed gives the same bits; NO sum of trait k depends on T or on the
+// position of the trait inside its tile).  A slice partial: a thread adds the rows of its part ascending, the parts are added
+// ascending ((p0 + p1) + p2) + p3.  s: the slices ascending.  xpx_j and G_ij: a thread adds rows tid, tid + 256, ... ascending, a
+// wave meets in a shuffle tree (32 .. 1), the four waves in wave order.  Statistics of a trait: per lane in marker order, a shuffle
+// tree, the blocks in stream order.  sum r^2 and sum r: per slice the shuffle tree and the four waves in order, then (on the host)
+// the slices ascending.
+//
+// DRAWS: philox4x32_10(marker, iteration, 0x01000000 | trait_id, slot): slot 10 the decision uniform (u52 of words (1, 0)), slot 11
+// the effect normal (Box-Muller, jwu::normal_from); philox4x32_10(record, iteration, 0x01000000 | trait_id, 12) the normal of a
+// missing cell.  trait_id = first_trait + k: trait k of a T-trait session draws what trait 0 of a one-trait session with
+// first_trait = k draws.  They do not depend on the block size.
+#pragma once
+#include "device_util.hpp"
+#include "rng.hpp"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace jwg {
+
+constexpr int kMaxT = 64;                       // traits of a session
+constexpr int kMaxBlock = 256;                  // markers of a block
+constexpr int kTT = 8;                          // traits per workgroup of k_mega_update_partial
+constexpr int kRows = 256;                      // rows per slice (= the context's)
+constexpr uint32_t kTag = 0x01000000u;
+constexpr uint32_t kMaxTraitId = 0x01000000u;   // first_trait + T <= this: the tag's low 24 bits
+constexpr uint32_t kSlotU = 10u, kSlotZ = 11u, kSlotMiss = 12u;
+// the device record of a trait's statistics
+constexpr int kStDelta = 0, kStBeta = 1, kStAlpha = 2, kStChanged = 3, kStSize = 4;
+// the per-trait parameters of a sweep: par[q * T + k]
+constexpr int kParVare = 0, kParVar = 1, kParLogPi = 2, kParLogPiComp = 3, kParSize = 4;
+
+// The change lists of a block: per trait the markers whose effect moved and d = alpha_old - alpha_new.
+struct Events {
+    int32_t count[kMaxT];
+    int32_t idx[kMaxT][kMaxBlock];
+    double d[kMaxT][kMaxBlock];
+};
+
+// acc[0 .. N) of the 256 threads of a workgroup -> out[0 .. N): shuffle tree within a wave, the four waves in wave order.
+template <int N>
+__device__ __forceinline__ void block_reduce(const double (&acc)[N], double* sh, double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        double v = acc[q];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
+        if (lane == 0) sh[wave * N + q] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < N) out[threadIdx.x] = ((sh[threadIdx.x] + sh[N + threadIdx.x]) + sh[2 * N + threadIdx.x]) + sh[3 * N + threadIdx.x];
+}
+
+// four consecutive rows of a column as doubles (the column starts on a 16-byte boundary: ld is a multiple of 256)
+__device__ __forceinline__ void load4(const float* __restrict__ x, double (&v)[4])
+{
+    const float4 f = *reinterpret_cast<const float4*>(x);
+    v[0] = (double)f.x; v[1] = (double)f.y; v[2] = (double)f.z; v[3] = (double)f.w;
+}
+__device__ __forceinline__ void load4(const double* __restrict__ x, double (&v)[4])
+{
+    const double2 a = *reinterpret_cast<const double2*>(x), b = *reinterpret_cast<const double2*>(x + 2);
+    v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
+}
+
+// ---- set-up ------------------------------------------------------------------------------------------------------------------------
+// The Grams of the blocks: gram[(blk bs + a) bs + k] = sum_i x_ia x_ik for the markers a, k of block blk.  grid = (bs, nblocks):
+// workgroup (a, blk) forms the pairs k >= a and writes both (a, k) and (k, a): symmetric bit for bit; the pair (a, a) is also xpx.
+template <class real>
+__global__ __launch_bounds__(256) void k_mega_gram(const real* __restrict__ X, int64_t ld, int64_t p, int32_t bs, double* __restrict__ gram,
+                                                   double* __restrict__ xpx)
+{
+    __shared__ double sh[4];
+    __shared__ double outv[1];
+    const int a = blockIdx.x;
+    const int64_t j0 = (int64_t)blockIdx.y * bs;
+    const int b = (int)((p - j0) < bs ? (p - j0) : bs);
+    if (a >= b) return;
+    const real* __restrict__ xa = X + (j0 + a) * ld;
+    double* __restrict__ G = gram + (int64_t)blockIdx.y * bs * bs;
+    for (int k = a; k < b; ++k) {
+        const real* __restrict__ xk = X + (j0 + k) * ld;
+        double acc[1] = {0.0};
+        for (int64_t i = threadIdx.x; i < ld; i += 256) acc[0] = acc[0] + (double)xa[i] * (double)xk[i];
+        block_reduce<1>(acc, sh, outv);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double v = outv[0];
+            G[(int64_t)a * bs + k] = v;
+            G[(int64_t)k * bs + a] = v;
+            if (k == a) xpx[j0 + a] = v;
+        }
+        __syncthreads();
+    }
+}
+
+// ---- the block right-hand sides -----------------------------------------------------------------------------------------------------
+struct UpdateArgs {
+    const void* X;                      // [p][ld] genotypes (real)
+    double* R;                          // [T][ld]
+    const Events* ev;                   // the previous block's change lists (NULL: none)
+    double* partials;                   // [nslices][T][bs]
+    int64_t ld, j0;
+    int32_t T, b, bs;
+};
+
+// grid = (nslices, ceil(T / kTT)) workgroups of 256 threads
+template <class real>
+__global__ __launch_bounds__(256) void k_mega_update_partial(const UpdateArgs A)
+{
+    __shared__ double Rs[kTT][kRows];   // the tile's residual, [trait][row]
+    __shared__ double red[kTT][kRows];  // the parts' sums, [trait][part * bp + marker]
+    const real* __restrict__ X = (const real*)A.X;
+    const int tid = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * kRows, row = row0 + tid;
+    const int k0 = (int)blockIdx.y * kTT;
+    // phase 1: the previous block's change lists, one row per thread
+#pragma unroll
+    for (int kk = 0; kk < kTT; ++kk) {
+        const int k = k0 + kk;
+        double r = 0.0;
+        if (k < A.T) {
+            r = A.R[(int64_t)k * A.ld + row];
+            const int nev = A.ev ? A.ev->count[k] : 0;
+            for (int e = 0; e < nev; ++e) r = r + (double)X[(int64_t)A.ev->idx[k][e] * A.ld + row] * A.ev->d[k][e];
+            if (nev > 0) A.R[(int64_t)k * A.ld + row] = r;
+        }
+        Rs[kk][tid] = r;
+    }
+    __syncthreads();
+    // phase 2: the slice's tile of X_b'R
+    const int bp = A.b <= 64 ? 64 : (A.b <= 128 ? 128 : 256), parts = kRows / bp, len = kRows / parts;
+    const int m = tid & (bp - 1), part = tid / bp;
+    double acc[kTT];
+#pragma unroll
+    for (int kk = 0; kk < kTT; ++kk) acc[kk] = 0.0;
+    if (m < A.b) {
+        const int i0 = part * len;
+        const real* __restrict__ x = X + (A.j0 + m) * A.ld + row0 + i0;
+        for (int i = 0; i < len; i += 4) {
+            double xv[4];
+            load4(x + i, xv);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int kk = 0; kk < kTT; ++kk) acc[kk] = acc[kk] + xv[u] * Rs[kk][i0 + i + u];
+        }
+    }
+    if (parts > 1) {
+#pragma unroll
+        for (int kk = 0; kk < kTT; ++kk) red[kk][tid] = acc[kk];
+        __syncthreads();
+        if (part == 0) {
+#pragma unroll
+            for (int kk = 0; kk < kTT; ++kk) {
+                double s = red[kk][m];
+                for (int q = 1; q < parts; ++q) s = s + red[kk][q * bp + m];
+                acc[kk] = s;
+            }
+        }
+    }
+    if (part == 0 && m < A.b) {
+#pragma unroll
+        for (int kk = 0; kk < kTT; ++kk)
+            if (k0 + kk < A.T) A.partials[((int64_t)blockIdx.x * A.T + k0 + kk) * A.bs + m] = acc[kk];
+    }
+}
+
+struct FinishArgs {
+    const void* X;
+    double* R;
+    const Events* ev;
+    double* fin;                        // [T][nslices][2]: sum r^2, sum r of the slice
+    int64_t ld;
+    int32_t T;
+};
+
+// grid = (nslices, T): after the last block its change list, then the slice's sums
+template <class real>
+__global__ __launch_bounds__(256) void k_mega_finish(const FinishArgs A)
+{
+    __shared__ double sh[8];
+    const real* __restrict__ X = (const real*)A.X;
+    const int64_t row = (int64_t)blockIdx.x * kRows + threadIdx.x;
+    const int k = blockIdx.y;
+    double r = A.R[(int64_t)k * A.ld + row];
+    const int nev = A.ev ? A.ev->count[k] : 0;
+    for (int e = 0; e < nev; ++e) r = r + (double)X[(int64_t)A.ev->idx[k][e] * A.ld + row] * A.ev->d[k][e];
+    if (nev > 0) A.R[(int64_t)k * A.ld + row] = r;
+    const double acc[2] = {r * r, r};
+    block_reduce<2>(acc, sh, A.fin + ((int64_t)k * gridDim.x + blockIdx.x) * 2);
+}
+
+// ---- one block of one trait ----------------------------------------------------------------------------------------------------------
+struct SampleArgs {
+    const double* partials;             // [nslices][T][bs]
+    const double* gram;                 // this block's [bs][bs]
+    const double* xpx;                  // [p]
+    const double* par;                  // [kParSize][T]
+    double *alpha, *beta, *delta;       // [T][p]
+    Events* ev;                         // out
+    double* stat;                       // [T][kStSize], accumulated over the blocks of a sweep
+    int64_t j0, p;
+    int32_t nslices, b, bs, T;
+    uint32_t iter, seed_lo, seed_hi, first_trait;
+};
+
+// grid = T workgroups of 256 threads: every thread adds the slice partials of one marker, then wave 0 runs the trait's chain
+__global__ __launch_bounds__(256) void k_mega_sample(const SampleArgs A)
+{
+    __shared__ double s_s[kMaxBlock], s_a0[kMaxBlock];
+    const int lane = threadIdx.x & 63, k = blockIdx.x;
+    const int b = A.b, bs = A.bs;
+    double* __restrict__ alpha = A.alpha + (int64_t)k * A.p;
+    double* __restrict__ beta = A.beta + (int64_t)k * A.p;
+    double* __restrict__ delta = A.delta + (int64_t)k * A.p;
+    for (int i = threadIdx.x; i < b; i += 256) {
+        const double* __restrict__ part = A.partials + (int64_t)k * bs + i;
+        const int64_t stride = (int64_t)A.T * bs;
+        double s = 0.0;
+#pragma unroll 8
+        for (int sl = 0; sl < A.nslices; ++sl) s = s + part[sl * stride];      // (ascending; the loads of a batch are in flight together)
+        s_s[i] = s;
+        s_a0[i] = alpha[A.j0 + i];
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    const double vare = A.par[kParVare * A.T + k], v = A.par[kParVar * A.T + k];
+    const double lp0 = A.par[kParLogPi * A.T + k], lpc = A.par[kParLogPiComp * A.T + k];
+    const double ie = 1.0 / vare, iv = 1.0 / v, logv = log(v), sdv = sqrt(v);
+    const uint32_t tag = kTag | (A.first_trait + (uint32_t)k);
+    double st_acc[kStSize];
+#pragma unroll
+    for (int i = 0; i < kStSize; ++i) st_acc[i] = 0.0;
+    const int nsub = (b + 63) / 64;
+    int base = 0;
+#pragma unroll 1
+    for (int s = 0; s < nsub; ++s) {
+        const int kq = 64 * s + lane;
+        const bool valid = kq < b;
+        const int kl = valid ? kq : 0;
+        const int64_t j = A.j0 + kl;
+        const double xx = A.xpx[j];
+        const double z = jwu::normal_from(jw::philox4x32_10((uint32_t)j, A.iter, tag, kSlotZ, A.seed_lo, A.seed_hi));
+        const jw::u32x4 wu = jw::philox4x32_10((uint32_t)j, A.iter, tag, kSlotU, A.seed_lo, A.seed_hi);
+        const double u = jw::u52(wu.x, wu.y);
+        const double lhs = xx * ie + iv, invLhs = 1.0 / lhs, loglhs = log(lhs), sdl = sqrt(invLhs);
+        double a_cur = s_a0[kl], b_cur = beta[j], d_cur = delta[j];
+        unsigned long long pending = __ballot(valid);
+        while (pending) {
+            const double rhs = (s_s[kl] + xx * a_cur) * ie;
+            const double gHat = rhs * invLhs;
+            const double ld1 = -0.5 * (loglhs + logv - gHat * rhs) + lpc;
+            const double prob = 1.0 / (1.0 + exp(lp0 - ld1));
+            const bool inc = u < prob;
+            const double bn = inc ? gHat + z * sdl : z * sdv;
+            const double an = inc ? bn : 0.0, dn = inc ? 1.0 : 0.0;
+            const bool ch = an != a_cur;
+            const unsigned long long mm = __ballot(ch && valid) & pending;
+            const int kw = mm ? (int)__builtin_ctzll(mm) : 64;
+            // lanes before the winner are final with what they just evaluated (their effects do not move)
+            const unsigned long long done = (kw >= 64) ? pending : (pending & ((kw == 63) ? ~0ull : ((2ull << kw) - 1ull)));
+            if ((done >> lane) & 1ull) { b_cur = bn; d_cur = dn; }
+            if (kw >= 64) break;
+            // the winner commits; its Gram row corrects s of the whole block: s_i += G_i,ce d
+            const int ce = 64 * s + kw;
+            const double Dl = a_cur - an;
+            const double D = __shfl(Dl, kw, 64);
+            if (lane == kw) a_cur = an;
+            const double* __restrict__ grow = A.gram + (int64_t)ce * bs;
+            __builtin_amdgcn_wave_barrier();                // (one wave: its LDS accesses execute in program order)
+            for (int k2 = lane; k2 < b; k2 += 64) s_s[k2] = s_s[k2] + grow[k2] * D;
+            __builtin_amdgcn_wave_barrier();
+            pending &= ~done;
+        }
+        // the sub-block is final: state, change list, statistics
+        const bool changed = valid && (a_cur != s_a0[kl]);
+        const unsigned long long cm = __ballot(changed);
+        if (changed) {
+            const int e = base + __popcll(cm & ((1ull << lane) - 1ull));
+            A.ev->idx[k][e] = (int32_t)j;
+            A.ev->d[k][e] = s_a0[kl] - a_cur;
+        }
+        base += __popcll(cm);
+        if (valid) {
+            alpha[j] = a_cur; beta[j] = b_cur; delta[j] = d_cur;
+            st_acc[kStDelta] = st_acc[kStDelta] + d_cur;
+            st_acc[kStBeta] = st_acc[kStBeta] + b_cur * b_cur;
+            st_acc[kStAlpha] = st_acc[kStAlpha] + a_cur * a_cur;
+            if (changed) st_acc[kStChanged] = st_acc[kStChanged] + 1.0;
+        }
+    }
+    // the block's statistics join the sweep's: shuffle tree, lane 0 adds (the blocks of a sweep run in stream order)
+#pragma unroll
+    for (int i = 0; i < kStSize; ++i) {
+        double t = st_acc[i];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) t = t + __shfl_down(t, off, 64);
+        st_acc[i] = t;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < kStSize; ++i) A.stat[k * kStSize + i] = A.stat[k * kStSize + i] + st_acc[i];
+        A.ev->count[k] = base;
+    }
+}
+
+// ---- missing cells ---------------------------------------------------------------------------------------------------------------------
+// grid = (ceil(n / 256), T): r_k[i] = z sqrt(vare_k) where bit i of the trait's mask is set; nothing else is written
+__global__ __launch_bounds__(256) void k_mega_impute(const uint32_t* __restrict__ mask, int64_t words, int64_t n, int64_t ld, const double* __restrict__ vare,
+                                                     uint32_t iter, uint32_t seed_lo, uint32_t seed_hi, uint32_t first_trait, double* __restrict__ R)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int k = blockIdx.y;
+    if (i >= n) return;
+    if (!((mask[(int64_t)k * words + (i >> 5)] >> (i & 31)) & 1u)) return;
+    const double z = jwu::normal_from(jw::philox4x32_10((uint32_t)i, iter, kTag | (first_trait + (uint32_t)k), kSlotMiss, seed_lo, seed_hi));
+    R[(int64_t)k * ld + i] = z * sqrt(vare[k]);
+}
+
+// ---- outputs --------------------------------------------------------------------------------------------------------------------------
+// running mean, mean of squares and model frequency of every effect (output.jl:556-560): one thread per (trait, marker)
+__global__ __launch_bounds__(256) void k_mega_accumulate(const double* __restrict__ alpha, const double* __restrict__ delta, int64_t tp, double ns,
+                                                         double* __restrict__ mean_a, double* __restrict__ mean_a2, double* __restrict__ mean_d)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= tp) return;
+    const double a = alpha[i];
+    mean_a[i] = jwu::running_mean(mean_a[i], a, ns);
+    mean_a2[i] = jwu::running_mean(mean_a2[i], a * a, ns);
+    mean_d[i] = jwu::running_mean(mean_d[i], delta[i], ns);
+}
+
+// out[i] = sum_j x_ij alpha_j (j ascending, zero effects skipped): one thread per row of X (the context's matrix or its output rows)
+template <class real>
+__global__ __launch_bounds__(256) void k_mega_mul_alpha(const real* __restrict__ X, int64_t ld, int64_t n, int64_t p, const double* __restrict__ alpha,
+                                                        double* __restrict__ out)
+{
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    double s = 0.0;
+    for (int64_t j = 0; j < p; ++j) {
+        const double a = alpha[j];
+        if (a != 0.0) s = s + (double)X[j * ld + row] * a;
+    }
+    out[row] = s;
+}
+
+}  // namespace jwg

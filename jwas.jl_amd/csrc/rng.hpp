@@ -29,6 +29,12 @@
 //   slots 8, 9: the random-regression sweep (rrm.hpp), indexed by (MARKER, iteration, 0x02000000, slot): slot 8 the decision uniform of
 //           the joint inclusion state (as slot 0), slot 9 + 16 q the normal of coefficient q (Box-Muller as slot 1).  The tag
 //           0x02000000 is no other stream's repetition word and no other stream uses slots 8 and 9 (+ 16 q: 25, 41, 57).
+//   slots 10, 11, 12: the mega-trait sweep (mega.hpp).  (MARKER, iteration, 0x01000000 | trait_id, 10) the decision uniform (as slot 0)
+//           and (..., 11) the effect normal (Box-Muller as slot 1); (RECORD, iteration, 0x01000000 | trait_id, 12) the normal of a missing
+//           residual cell.  trait_id = first_trait + trait < 2^24 (checked at jwas_hip_mega_begin), so the word has bit 24 set and
+//           no higher bit: it is no other stream's repetition word (small counts below 2^24, 0x02000000, 0x04000000 | trait,
+//           0x08000000 | step, 0x10000000, 0x20000000 | term, 0x40000000 | round, 0x80000000 | ...), and no other stream uses
+//           slots 10, 11 and 12 (the others' are 0 .. 4 + 16 trait, 5 .. 8, 9 + 16 q, and 64 upwards for the Wishart draws).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,0 +1,341 @@
+// session_mega.hip -- mega-trait models (mega.hpp), jwas_hip_mega_begin .. _end: megaBayesABC! / megaBayesC0!
+// (markers/BayesianAlphabet/BayesABC.jl:1-58) for up to 64 traits and sampleMissingResiduals under a diagonal R (residual.jl:51-73).
+#include "ctx.hpp"
+#include "mega.hpp"
+
+static_assert(jwg::kMaxT == JWAS_HIP_MEGA_MAX_TRAITS && jwg::kMaxBlock == JWAS_HIP_MEGA_MAX_BLOCK, "the header's limits are mega.hpp's");
+
+static bool mega_weighted(jwas_hip_ctx* c) { return IS_F64(c) ? c->f64->weighted : c->weighted; }
+
+static int need_mega(jwas_hip_ctx* c)
+{
+    if (int rc = session_guard(c, &jwas_hip_ctx::mg, "jwas_hip_mega_begin")) return rc;
+    NEED(c, !mega_weighted(c), JWAS_HIP_EUNSUP, "mega-trait models do not run with residual weights");
+    return refuse_shards(c, "mega-trait models");
+}
+
+static int need_trait(jwas_hip_ctx* c, int32_t trait)
+{
+    if (int rc = need_mega(c)) return rc;
+    NEED(c, trait >= 0 && trait < c->mg.nt, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->mg.nt);
+    return JWAS_HIP_OK;
+}
+
+void mega_free(jwas_hip_ctx* c) { DevOwner::reset(c->mg); }
+
+static const void* mega_genotypes(jwas_hip_ctx* c) { return IS_F64(c) ? (const void*)c->f64->X : (const void*)c->X; }
+
+static int64_t mega_bytes(int64_t n, int64_t p, int T, int bs)
+{
+    const int64_t ld = round_up(n, jwg::kRows), nsl = ld / jwg::kRows, nblocks = (p + bs - 1) / bs;
+    return 8 * ((int64_t)T * ld + p + nblocks * bs * bs + 6 * (int64_t)T * p + nsl * T * bs + (int64_t)jwg::kParSize * T +
+                (int64_t)T * (jwg::kStSize + 2 * nsl) + ld) + 4 * (int64_t)T * (ld / 32) + (int64_t)sizeof(jwg::Events);
+}
+
+// the per-trait parameters of a sweep or an imputation: checked, then par_host = vare | var_effect | log pi | log(1 - pi)
+static int mega_params(jwas_hip_ctx* c, const jwas_mega_params* P, bool sweep, const char* who)
+{
+    auto& b = c->mg;
+    NEED(c, P, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "%s: iteration must be >= 1", who);
+    NEED(c, P->vare && (!sweep || (P->var_effect && P->pi)), JWAS_HIP_EINVAL, "%s: NULL parameter array", who);
+    const int T = b.nt;
+    b.par_host.assign((size_t)jwg::kParSize * T, 1.0);
+    for (int k = 0; k < T; ++k) {
+        NEED(c, std::isfinite(P->vare[k]) && P->vare[k] > 0.0, JWAS_HIP_EINVAL, "vare[%d] must be positive and finite (%g)", k, P->vare[k]);
+        b.par_host[(size_t)jwg::kParVare * T + k] = P->vare[k];
+        if (!sweep) continue;
+        NEED(c, std::isfinite(P->var_effect[k]) && P->var_effect[k] > 0.0, JWAS_HIP_EINVAL, "var_effect[%d] must be positive and finite (%g)", k, P->var_effect[k]);
+        NEED(c, P->pi[k] >= 0.0 && P->pi[k] <= 1.0, JWAS_HIP_EINVAL, "pi[%d] must be in [0,1] (%g)", k, P->pi[k]);
+        b.par_host[(size_t)jwg::kParVar * T + k] = P->var_effect[k];
+        b.par_host[(size_t)jwg::kParLogPi * T + k] = std::log(P->pi[k]);                    // pi = 0: -Inf, every marker is included
+        b.par_host[(size_t)jwg::kParLogPiComp * T + k] = std::log(1.0 - P->pi[k]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(b.par, b.par_host.data(), sizeof(double) * b.par_host.size(), hipMemcpyHostToDevice, c->stream));
+    return JWAS_HIP_OK;
+}
+
+extern "C" {
+
+int jwas_hip_mega_begin(jwas_hip_ctx* c, int32_t T, int32_t block_size, int32_t first_trait)
+{
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, !c->packed, JWAS_HIP_EUNSUP, "mega-trait models need dense genotypes (2-bit packed storage is not supported)");
+    NEED(c, mega_genotypes(c) && c->n > 0 && c->p > 0, JWAS_HIP_ESTATE, "no genotype matrix loaded");
+    if (int rc = refuse_shards(c, "mega-trait models")) return rc;
+    NEED(c, !mega_weighted(c), JWAS_HIP_EUNSUP, "mega-trait models do not run with residual weights");
+    NEED(c, T >= 1 && T <= jwg::kMaxT, JWAS_HIP_EINVAL, "the number of traits must be in [1,%d] (got %d)", jwg::kMaxT, T);
+    NEED(c, block_size >= 0 && block_size <= jwg::kMaxBlock, JWAS_HIP_EINVAL, "block size must be in [1,%d] (0: 64), got %d", jwg::kMaxBlock, block_size);
+    NEED(c, first_trait >= 0 && (int64_t)first_trait + T <= (int64_t)jwg::kMaxTraitId, JWAS_HIP_EINVAL,
+         "first_trait must be >= 0 and first_trait + T <= %u (got %d)", jwg::kMaxTraitId, first_trait);
+    if (int rc = session_drop(c, mega_free)) return rc;
+    auto& b = c->mg;
+    const int bs = block_size ? block_size : 64;
+    const int64_t p = c->p, ld = c->ld;
+    b.nt = T; b.bs = bs; b.nblocks = (p + bs - 1) / bs; b.first_trait = (uint32_t)first_trait; b.mask_words = ld / 32; b.row_cap = ld;
+    auto alloc = [&](auto** ptr, size_t bytes) { return alloc_or_nomem(c, b.mem, ptr, bytes, "mega-trait session", mega_free); };
+    const size_t tp = sizeof(double) * (size_t)T * (size_t)p, gramb = sizeof(double) * (size_t)b.nblocks * bs * bs;
+    const size_t maskb = sizeof(uint32_t) * (size_t)T * (size_t)b.mask_words, statb = sizeof(double) * (size_t)T * (size_t)(jwg::kStSize + 2 * c->nslices);
+    jwg::Events* ev = nullptr;
+    if (int rc = alloc(&b.mask, maskb)) return rc;
+    if (int rc = alloc(&b.R, sizeof(double) * (size_t)T * ld)) return rc;
+    if (int rc = alloc(&b.xpx, sizeof(double) * (size_t)p)) return rc;
+    if (int rc = alloc(&b.gram, gramb)) return rc;
+    for (double** q : {&b.alpha, &b.beta, &b.delta, &b.mean_a, &b.mean_a2, &b.mean_d})
+        if (int rc = alloc(q, tp)) return rc;
+    if (int rc = alloc(&b.partials, sizeof(double) * (size_t)c->nslices * T * bs)) return rc;
+    if (int rc = alloc(&b.par, sizeof(double) * (size_t)jwg::kParSize * T)) return rc;
+    if (int rc = alloc(&b.stat, statb)) return rc;
+    if (int rc = alloc(&b.row, sizeof(double) * (size_t)ld)) return rc;
+    if (int rc = alloc(&ev, sizeof(jwg::Events))) return rc;
+    b.ev = ev;
+    HIPCHK(c, hipMemsetAsync(b.mask, 0, maskb, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.R, 0, sizeof(double) * (size_t)T * ld, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.gram, 0, gramb, c->stream));
+    for (double* q : {b.alpha, b.beta, b.mean_a, b.mean_a2, b.mean_d}) HIPCHK(c, hipMemsetAsync(q, 0, tp, c->stream));
+    {   // delta starts at ones (Mi.δ, MCMC_BayesianAlphabet.jl:85-117)
+        std::vector<double> ones((size_t)T * (size_t)p, 1.0);
+        HIPCHK(c, hipMemcpyAsync(b.delta, ones.data(), tp, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    HIPCHK(c, hipMemsetAsync(ev, 0, sizeof(jwg::Events), c->stream));
+    with_real(c, [&](auto real) {
+        using real_t = decltype(real);
+        // (the grid's y extent is 65 535 blocks at most: the blocks go in trips)
+        for (int64_t k0 = 0; k0 < b.nblocks; k0 += 32768) {
+            const int64_t nb = std::min<int64_t>(32768, b.nblocks - k0);
+            hipLaunchKernelGGL((jwg::k_mega_gram<real_t>), dim3((unsigned)bs, (unsigned)nb), dim3(256), 0, c->stream,
+                               (const real_t*)mega_genotypes(c) + k0 * bs * ld, ld, p - k0 * bs, (int32_t)bs, b.gram + k0 * bs * bs, b.xpx + k0 * bs);
+        }
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    b.active = true;
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_set_missing(jwas_hip_ctx* c, int64_t nvalues, const uint8_t* missing)
+{
+    if (int rc = need_mega(c)) return rc;
+    auto& b = c->mg;
+    const int64_t n = c->n;
+    std::vector<uint32_t> words((size_t)b.nt * (size_t)b.mask_words, 0u);
+    if (missing) {
+        NEED(c, nvalues == (int64_t)b.nt * n, JWAS_HIP_EINVAL, "nvalues (%lld) differs from T n (%lld)", (long long)nvalues, (long long)((int64_t)b.nt * n));
+        for (int k = 0; k < b.nt; ++k)
+            for (int64_t i = 0; i < n; ++i)
+                if (missing[(size_t)k * n + i]) words[(size_t)k * b.mask_words + (size_t)(i >> 5)] |= 1u << (i & 31);
+        b.miss_host.assign(missing, missing + (size_t)b.nt * n);
+    } else {
+        b.miss_host.clear();
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(b.mask, words.data(), sizeof(uint32_t) * words.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_set_residual(jwas_hip_ctx* c, int32_t trait, const double* r)
+{
+    if (int rc = need_trait(c, trait)) return rc;
+    NEED(c, r, JWAS_HIP_EINVAL, "NULL argument");
+    for (int64_t i = 0; i < c->n; ++i) NEED(c, std::isfinite(r[i]), JWAS_HIP_EINVAL, "the residual of record %lld is not finite (%g)", (long long)i, r[i]);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(c->mg.R + (size_t)trait * c->ld, r, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_get_residual(jwas_hip_ctx* c, int32_t trait, double* out)
+{
+    if (int rc = need_trait(c, trait)) return rc;
+    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    return to_host(c, out, c->mg.R + (size_t)trait * c->ld, sizeof(double) * (size_t)c->n);
+}
+
+int jwas_hip_mega_set_state(jwas_hip_ctx* c, int32_t trait, const double* alpha, const double* beta, const double* delta)
+{
+    if (int rc = need_trait(c, trait)) return rc;
+    auto& b = c->mg;
+    const size_t cnt = (size_t)c->p, at = (size_t)trait * cnt;
+    for (const double* src : {alpha, beta, delta})
+        if (src)
+            for (size_t i = 0; i < cnt; ++i) NEED(c, std::isfinite(src[i]), JWAS_HIP_EINVAL, "state value %zu is not finite (%g)", i, src[i]);
+    if (delta)
+        for (size_t i = 0; i < cnt; ++i) NEED(c, delta[i] == 0.0 || delta[i] == 1.0, JWAS_HIP_EINVAL, "delta[%zu] = %g is not 0 or 1", i, delta[i]);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (alpha) HIPCHK(c, hipMemcpyAsync(b.alpha + at, alpha, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
+    if (beta) HIPCHK(c, hipMemcpyAsync(b.beta + at, beta, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
+    if (delta) HIPCHK(c, hipMemcpyAsync(b.delta + at, delta, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_get_state(jwas_hip_ctx* c, int32_t trait, double* alpha, double* beta, double* delta)
+{
+    if (int rc = need_trait(c, trait)) return rc;
+    auto& b = c->mg;
+    const size_t nb = sizeof(double) * (size_t)c->p, at = (size_t)trait * (size_t)c->p;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (alpha) HIPCHK(c, hipMemcpyAsync(alpha, b.alpha + at, nb, hipMemcpyDeviceToHost, c->stream));
+    if (beta) HIPCHK(c, hipMemcpyAsync(beta, b.beta + at, nb, hipMemcpyDeviceToHost, c->stream));
+    if (delta) HIPCHK(c, hipMemcpyAsync(delta, b.delta + at, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_impute(jwas_hip_ctx* c, const jwas_mega_params* P)
+{
+    if (int rc = need_mega(c)) return rc;
+    if (int rc = mega_params(c, P, false, "jwas_hip_mega_impute")) return rc;
+    auto& b = c->mg;
+    if (!b.miss_host.empty()) {
+        uint32_t lo, hi;
+        split_seed(P->seed, lo, hi);
+        hipLaunchKernelGGL(jwg::k_mega_impute, dim3((unsigned)((c->n + 255) / 256), (unsigned)b.nt), dim3(256), 0, c->stream, (const uint32_t*)b.mask, b.mask_words,
+                           c->n, c->ld, (const double*)b.par, P->iteration, lo, hi, b.first_trait, b.R);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_sweep(jwas_hip_ctx* c, const jwas_mega_params* P, jwas_mega_stats* S)
+{
+    if (int rc = need_mega(c)) return rc;
+    NEED(c, S, JWAS_HIP_EINVAL, "NULL argument");
+    if (int rc = mega_params(c, P, true, "jwas_hip_mega_sweep")) return rc;
+    auto& b = c->mg;
+    const int T = b.nt, nsl = c->nslices;
+    const size_t nstat = (size_t)T * (size_t)(jwg::kStSize + 2 * nsl);
+    if (int rc = step_timer_begin(c)) return rc;
+    HIPCHK(c, hipMemsetAsync(b.stat, 0, sizeof(double) * nstat, c->stream));
+    jwg::UpdateArgs U = {};
+    U.X = mega_genotypes(c); U.R = b.R; U.partials = b.partials; U.ld = c->ld; U.T = T; U.bs = b.bs;
+    jwg::SampleArgs A = {};
+    A.partials = b.partials; A.xpx = b.xpx; A.par = b.par; A.alpha = b.alpha; A.beta = b.beta; A.delta = b.delta; A.ev = (jwg::Events*)b.ev;
+    A.stat = b.stat; A.p = c->p; A.nslices = nsl; A.bs = b.bs; A.T = T; A.iter = P->iteration; A.first_trait = b.first_trait;
+    split_seed(P->seed, A.seed_lo, A.seed_hi);
+    jwg::FinishArgs F = {};
+    F.X = mega_genotypes(c); F.R = b.R; F.ev = (const jwg::Events*)b.ev; F.fin = b.stat + (size_t)T * jwg::kStSize; F.ld = c->ld; F.T = T;
+    const dim3 tiles((unsigned)nsl, (unsigned)((T + jwg::kTT - 1) / jwg::kTT));
+    with_real(c, [&](auto real) {
+        using real_t = decltype(real);
+        for (int64_t k = 0; k < b.nblocks; ++k) {
+            const int64_t j0 = k * b.bs;
+            U.ev = k ? (const jwg::Events*)b.ev : nullptr; U.j0 = j0; U.b = (int32_t)std::min<int64_t>(b.bs, c->p - j0);
+            A.gram = b.gram + k * (int64_t)b.bs * b.bs; A.j0 = j0; A.b = U.b;
+            hipLaunchKernelGGL((jwg::k_mega_update_partial<real_t>), tiles, dim3(256), 0, c->stream, U);
+            hipLaunchKernelGGL(jwg::k_mega_sample, dim3((unsigned)T), dim3(256), 0, c->stream, A);
+        }
+        hipLaunchKernelGGL((jwg::k_mega_finish<real_t>), dim3((unsigned)nsl, (unsigned)T), dim3(256), 0, c->stream, F);
+    });
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> host(nstat);
+    double ms = 0.0;
+    if (int rc = step_timer_end(c, host.data(), b.stat, sizeof(double) * nstat, &ms)) return rc;
+    S->step_ms = ms;
+    for (int k = 0; k < T; ++k) {
+        const double* st = host.data() + (size_t)k * jwg::kStSize;
+        if (S->sum_delta) S->sum_delta[k] = st[jwg::kStDelta];
+        if (S->beta_ss) S->beta_ss[k] = st[jwg::kStBeta];
+        if (S->alpha_ss) S->alpha_ss[k] = st[jwg::kStAlpha];
+        if (S->n_changed) S->n_changed[k] = st[jwg::kStChanged];
+        const double* fin = host.data() + (size_t)T * jwg::kStSize + (size_t)k * nsl * 2;
+        double ss = 0.0, sm = 0.0;
+        for (int sl = 0; sl < nsl; ++sl) { ss += fin[2 * sl]; sm += fin[2 * sl + 1]; }       // slices in order
+        if (S->resid_ss) S->resid_ss[k] = ss;
+        if (S->resid_sum) S->resid_sum[k] = sm;
+    }
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_accumulate(jwas_hip_ctx* c, double nsamples)
+{
+    if (int rc = need_mega(c)) return rc;
+    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
+    auto& b = c->mg;
+    const int64_t tp = (int64_t)b.nt * c->p;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(jwg::k_mega_accumulate, dim3((unsigned)((tp + 255) / 256)), dim3(256), 0, c->stream, (const double*)b.alpha, (const double*)b.delta, tp,
+                       nsamples, b.mean_a, b.mean_a2, b.mean_d);
+    HIPCHK(c, hipGetLastError());
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_get_posterior(jwas_hip_ctx* c, int32_t trait, double* mean, double* mean2, double* freq)
+{
+    if (int rc = need_trait(c, trait)) return rc;
+    auto& b = c->mg;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nb = sizeof(double) * (size_t)c->p, at = (size_t)trait * (size_t)c->p;
+    if (mean) HIPCHK(c, hipMemcpyAsync(mean, b.mean_a + at, nb, hipMemcpyDeviceToHost, c->stream));
+    if (mean2) HIPCHK(c, hipMemcpyAsync(mean2, b.mean_a2 + at, nb, hipMemcpyDeviceToHost, c->stream));
+    if (freq) HIPCHK(c, hipMemcpyAsync(freq, b.mean_d + at, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_mul_alpha(jwas_hip_ctx* c, int32_t trait, int32_t use_output_rows, double* out)
+{
+    if (int rc = need_trait(c, trait)) return rc;
+    auto& b = c->mg;
+    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
+    const void* X = mega_genotypes(c);
+    int64_t n = c->n, ld = c->ld;
+    if (use_output_rows) {
+        X = IS_F64(c) ? (const void*)c->f64->Xout : (const void*)c->Xout;
+        NEED(c, X, JWAS_HIP_ESTATE, "no output rows loaded (jwas_hip_load_output_dense_f32 / _f64)");
+        n = IS_F64(c) ? c->f64->n_out : c->n_out;
+        ld = IS_F64(c) ? c->f64->ld_out : c->ld_out;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (ld > b.row_cap) {                                   // the output rows may outnumber the training rows
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        b.mem.free_one(b.row);
+        b.row_cap = 0;
+        if (int rc = alloc_or_nomem(c, b.mem, &b.row, sizeof(double) * (size_t)ld, "mega-trait session", mega_free)) return rc;
+        b.row_cap = ld;
+    }
+    with_real(c, [&](auto real) {
+        using real_t = decltype(real);
+        hipLaunchKernelGGL((jwg::k_mega_mul_alpha<real_t>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const real_t*)X, ld, n, c->p,
+                           (const double*)(b.alpha + (size_t)trait * (size_t)c->p), b.row);
+    });
+    HIPCHK(c, hipGetLastError());
+    return to_host(c, out, b.row, sizeof(double) * (size_t)n);
+}
+
+int jwas_hip_mega_get_gram(jwas_hip_ctx* c, int64_t block, int64_t nvalues, double* out, double* out_xpx)
+{
+    if (int rc = need_mega(c)) return rc;
+    auto& b = c->mg;
+    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, block >= 0 && block < b.nblocks, JWAS_HIP_EINVAL, "block %lld outside [0,%lld)", (long long)block, (long long)b.nblocks);
+    const int64_t nb = std::min<int64_t>(b.bs, c->p - block * b.bs);
+    NEED(c, nvalues == nb * nb, JWAS_HIP_EINVAL, "nvalues (%lld) differs from b b (%lld)", (long long)nvalues, (long long)(nb * nb));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy2DAsync(out, sizeof(double) * (size_t)nb, b.gram + block * b.bs * b.bs, sizeof(double) * (size_t)b.bs, sizeof(double) * (size_t)nb, (size_t)nb,
+                               hipMemcpyDeviceToHost, c->stream));
+    if (out_xpx) HIPCHK(c, hipMemcpyAsync(out_xpx, b.xpx + block * b.bs, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+int64_t jwas_hip_mega_estimate_bytes(int64_t n, int64_t p, int32_t T, int32_t block_size)
+{
+    // the residuals, x'x, the Grams (8 p b for whole blocks), the state and its running means, the slice partials, the per-trait
+    // parameters and statistics, a row vector, the missing-cell bit mask and the change lists
+    return mega_bytes(std::max<int64_t>(n, 1), std::max<int64_t>(p, 1), std::min(std::max(T, 1), jwg::kMaxT),
+                      block_size > 0 ? std::min(block_size, jwg::kMaxBlock) : 64);
+}
+
+int jwas_hip_mega_end(jwas_hip_ctx* c)
+{
+    if (int rc = session_guard(c, &jwas_hip_ctx::mg, "jwas_hip_mega_begin")) return rc;
+    return session_drop(c, mega_free);
+}
+
+}  // extern "C"

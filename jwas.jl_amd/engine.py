@@ -88,6 +88,7 @@ class HipEngine:
         self._weighted = False          # non-unit residual weights on the device (set_weights)
         self._explicit_starts = None    # explicit block partition resident (setup_blocks_explicit)
         self._rrm = None                # (T, c, block size) of an open random-regression session
+        self._mega = None               # (traits, block size) of an open mega-trait session
 
     # -- plumbing --------------------------------------------------------------------------------
     def _chk(self, rc):
@@ -974,6 +975,125 @@ class HipEngine:
     def rrm_end(self):
         self._chk(self._L.jwas_hip_rrm_end(self._h))
         self._rrm = None
+
+    # -- mega-trait models (jwas_hip_mega_*; markers/BayesianAlphabet/BayesABC.jl:1-58, csrc/mega.hpp) ------------------------
+    @staticmethod
+    def mega_estimate_bytes(n, p, ntraits, block_size=64):
+        return _lib.load().jwas_hip_mega_estimate_bytes(int(n), int(p), int(ntraits), int(block_size))
+
+    def mega_begin(self, ntraits, block_size=64, first_trait=0):
+        """Open a session of `ntraits` independent single-trait chains on the loaded genotypes: x'x and the block Grams; the
+        residuals, alpha and beta start at 0, delta at 1.  first_trait: the RNG trait id of trait 0."""
+        self._chk(self._L.jwas_hip_mega_begin(self._h, int(ntraits), int(block_size), int(first_trait)))
+        self._mega = (int(ntraits), int(block_size) if block_size else 64)
+
+    def mega_set_missing(self, missing):
+        """missing: T x n booleans, True where the record misses the trait (None: complete records)."""
+        T, _ = self._mega
+        if missing is None:
+            self._chk(self._L.jwas_hip_mega_set_missing(self._h, 0, None))
+            return
+        m = np.ascontiguousarray(np.asarray(missing).astype(bool), dtype=np.uint8)
+        if m.shape != (T, self.n):
+            raise ValueError(f"the missing pattern must be {T} x {self.n}")
+        self._chk(self._L.jwas_hip_mega_set_missing(self._h, m.size, _ptr(m)))
+
+    def mega_set_residual(self, R, trait=None):
+        """R: T x n doubles (trait=None), or the n values of one trait."""
+        T, _ = self._mega
+        Rv = np.ascontiguousarray(R, dtype=np.float64)
+        if Rv.shape != ((T, self.n) if trait is None else (self.n,)):
+            raise ValueError(f"the residual must be {T} x {self.n}, or {self.n} values for one trait")
+        for k in (range(T) if trait is None else [int(trait)]):
+            self._chk(self._L.jwas_hip_mega_set_residual(self._h, k, _ptr(Rv[k] if trait is None else Rv)))
+
+    def mega_get_residual(self, trait=None):
+        T, _ = self._mega
+        out = np.empty((T, self.n) if trait is None else (1, self.n), dtype=np.float64)
+        for i, k in enumerate(range(T) if trait is None else [int(trait)]):
+            self._chk(self._L.jwas_hip_mega_get_residual(self._h, k, _ptr(out[i])))
+        return out if trait is None else out[0]
+
+    def mega_set_state(self, alpha=None, beta=None, delta=None):
+        """alpha, beta, delta: T x p doubles each, any may be None.  The state only: the residuals are not touched."""
+        T, _ = self._mega
+        arrs = []
+        for a in (alpha, beta, delta):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (T, self.p):
+                    raise ValueError(f"state arrays must be {T} x {self.p}")
+            arrs.append(a)
+        for k in range(T):
+            self._chk(self._L.jwas_hip_mega_set_state(self._h, k, *[_ptr(a[k]) if a is not None else None for a in arrs]))
+
+    def mega_get_state(self, trait=None):
+        T, _ = self._mega
+        ks = range(T) if trait is None else [int(trait)]
+        out = [np.empty((len(ks), self.p), dtype=np.float64) for _ in range(3)]
+        for i, k in enumerate(ks):
+            self._chk(self._L.jwas_hip_mega_get_state(self._h, k, _ptr(out[0][i]), _ptr(out[1][i]), _ptr(out[2][i])))
+        return tuple(out) if trait is None else tuple(o[0] for o in out)
+
+    def _mega_params(self, iteration, seed, vare, var_effect=None, pi=None):
+        T, _ = self._mega
+        P = _lib.MegaParams()
+        P.iteration, P.seed = int(iteration), int(seed)
+        keep = []
+        for name, v in (("vare", vare), ("var_effect", var_effect), ("pi", pi)):
+            if v is None:
+                continue
+            a = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            if a.size != T:
+                raise ValueError(f"{name} must hold one value per trait ({T})")
+            keep.append(a)
+            setattr(P, name, a.ctypes.data)
+        return P, keep
+
+    def mega_impute(self, *, iteration, seed, vare):
+        """Every missing cell redrawn from N(0, vare_k)."""
+        P, keep = self._mega_params(iteration, seed, vare)
+        self._chk(self._L.jwas_hip_mega_impute(self._h, C.byref(P)))
+
+    def mega_sweep(self, *, iteration, seed, vare, var_effect, pi):
+        """One sweep over all markers of all traits.  vare, var_effect, pi: one value per trait.  Returns {"sum_delta", "beta_ss",
+        "alpha_ss", "resid_ss", "resid_sum", "n_changed"} (T values each) and "step_ms"."""
+        T, _ = self._mega
+        P, keep = self._mega_params(iteration, seed, vare, var_effect, pi)
+        S = _lib.MegaStats()
+        out = {k: np.zeros(T) for k in ("sum_delta", "beta_ss", "alpha_ss", "resid_ss", "resid_sum", "n_changed")}
+        for k, a in out.items():
+            setattr(S, k, a.ctypes.data)
+        self._chk(self._L.jwas_hip_mega_sweep(self._h, C.byref(P), C.byref(S)))
+        out["step_ms"] = S.step_ms
+        return out
+
+    def mega_accumulate(self, nsamples):
+        self._chk(self._L.jwas_hip_mega_accumulate(self._h, float(nsamples)))
+
+    def mega_posterior(self, trait):
+        """(mean, mean of squares, model frequency) of one trait's effects, p values each."""
+        out = [np.empty(self.p, dtype=np.float64) for _ in range(3)]
+        self._chk(self._L.jwas_hip_mega_get_posterior(self._h, int(trait), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
+        return tuple(out)
+
+    def mega_mul_alpha(self, trait, output_rows=False):
+        """X alpha_k over the training rows, or over the rows of load_output_dense."""
+        out = np.empty(getattr(self, "n_out", 0) if output_rows else self.n, dtype=np.float64)
+        self._chk(self._L.jwas_hip_mega_mul_alpha(self._h, int(trait), 1 if output_rows else 0, _ptr(out)))
+        return out
+
+    def mega_gram(self, block):
+        """(G, x'x) of one block: b x b and b doubles."""
+        T, bs = self._mega
+        b = max(min(bs, self.p - int(block) * bs), 0)
+        G, xpx = np.empty((b, b), dtype=np.float64), np.empty(b, dtype=np.float64)
+        self._chk(self._L.jwas_hip_mega_get_gram(self._h, int(block), G.size, _ptr(G), _ptr(xpx)))
+        return G, xpx
+
+    def mega_end(self):
+        self._chk(self._L.jwas_hip_mega_end(self._h))
+        self._mega = None
 
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""

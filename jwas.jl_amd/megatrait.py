@@ -1,0 +1,358 @@
+"""Mega-trait models: runMCMC on a model with 5 to 64 traits and constraint=true on both sides -- the host side of the reference's
+megaBayesABC! / megaBayesC0! path (markers/BayesianAlphabet/BayesABC.jl:1-8; MCMC_BayesianAlphabet.jl:233-234,261-262): t independent
+single-trait chains over one genotype matrix, with the marker sweep of ALL traits in one pass over the genotypes on the device
+(csrc/mega.hpp, HipEngine.mega_*).  A driver of its own beside rrm.py and multigeno.py; mcmc.py keeps every model of 1 to 4 traits.
+
+Per iteration, the order of mcmc.py:
+  1. missing residuals: engine.mega_impute -- N(0, vare_kk) per missing cell, sampleMissingResiduals under a diagonal R          (DEVICE)
+  2. location parameters, trait by trait, on the downloaded residual (MCMC_BayesianAlphabet.jl:196-220)                            (host)
+  3. marker effects of every trait: engine.mega_sweep                                                                             (DEVICE)
+  4. one pi per trait: samplePi(sum(delta_i), p) (MCMC_BayesianAlphabet.jl:299)                                                    (host)
+  5. the diagonal marker-effect and residual variances (variance_components.jl:104-109 and the constraint branch of
+     sample_marker_effect_variance)                                                                                               (host)
+  6. every output_samples_frequency after burn-in: running means (device for the markers), the sample files
+BayesC (estimatePi true or false) and RR-BLUP; Float32 or double_precision=True (the session's arithmetic is double in both; the
+genotypes are stored in the context's element type); dense storage; complete records or records that miss some traits.  Everything
+else raises (validate), before anything is written.
+
+Speed (scripts/mega_bench.py, one MI355X, 20 000 x 100 000 Float32, pi = 0.95, blocks of 256): 22.9 ms per sweep at 4 traits, 25.3 at 8,
+26.0 at 16, 31.3 at 32, 39.4 at 64, against 14.8 ms per 4 traits on the existing MegaBayesC sweep -- per trait the session is SLOWER
+than that path below about 7 traits (0.65 of its speed at 4; interpolated between the measured 4 and 8, the two meet between 6 and
+7 traits), 1.17 times as fast at 8 and 6.0 times at 64.  A model of 5 traits therefore pays about a quarter more per sweep here
+than 5/4 of a four-trait sweep on the old kernel; it gets one run and one set of outputs instead of two."""
+import os
+import time
+
+import numpy as np
+
+from ._lib import MEGA_MAX_BLOCK, MEGA_MAX_TRAITS
+from .mcmc import _Running, _design, _gibbs
+
+MEGA_METHODS = ("mega_begin", "mega_set_missing", "mega_set_residual", "mega_get_residual", "mega_get_state", "mega_impute", "mega_sweep",
+                "mega_accumulate", "mega_posterior", "mega_mul_alpha", "mega_end")
+MIN_TRAITS = 5                           # models of 1 to 4 traits stay on mcmc.py
+DEFAULT_BLOCK = 256                      # the fastest of 64 / 128 / 256 at every number of traits measured (NOTES.md, "Mega-trait models")
+
+
+def routes(model):
+    """The models this driver takes or refuses: more than 4 traits."""
+    return model.nModels >= MIN_TRAITS
+
+
+def _not_false(x):
+    return not (x is False or x is None)
+
+
+def validate(model, df, *, fast_blocks=False, independent_blocks=False, causal_structure=False, RRM=False, location_parameters="auto",
+             heterogeneous_residuals=False, starting_value=False, block_size=None, single_step_analysis=False, annotation_priors="host",
+             engine=None):
+    """Everything the device path does not run with more than 4 traits raises here, naming the argument, before any device work or
+    folder creation."""
+    t = model.nModels
+    if t > MEGA_MAX_TRAITS:
+        raise NotImplementedError(f"the device path runs at most {MEGA_MAX_TRAITS} traits (the model has {t} traits)")
+    if not model.M:
+        raise NotImplementedError("models without a genotype term have no marker sweep: use the reference")
+    if len(model.M) > 1:
+        raise NotImplementedError(f"several genotype categories with more than 4 traits ({t}) stay on the reference")
+    Mi = model.M[0]
+    if not (bool(Mi.G.constraint) and bool(model.R.constraint)):
+        raise NotImplementedError(f"models with more than 4 traits ({t}) run on the device with constraint=True only (independent single-trait "
+                                  "chains, megaBayesABC!): set constraint=True in BOTH get_genotypes and build_model; the joint "
+                                  "2^t-state samplers stay on the reference")
+    if Mi.method not in ("BayesC", "RR-BLUP"):
+        raise NotImplementedError(f"method={Mi.method} with more than 4 traits stays on the reference (the device runs BayesC and RR-BLUP)")
+    if Mi.annotations is not False:
+        raise NotImplementedError("annotations with more than 4 traits stay on the reference")
+    if annotation_priors != "host":
+        raise NotImplementedError('annotation_priors="device" does not apply to models with more than 4 traits')
+    mode = getattr(Mi, "storage_mode", "dense")
+    if mode == "stream":
+        raise NotImplementedError("storage=:stream with more than 4 traits stays on the reference (dense storage only)")
+    if mode == "device":
+        raise NotImplementedError("device_genotypes with more than 4 traits is not supported: pass the genotypes through get_genotypes")
+    if independent_blocks:
+        raise NotImplementedError("independent_blocks with more than 4 traits stays on the reference")
+    if fast_blocks is not False:
+        raise NotImplementedError("fast_blocks with more than 4 traits stays on the reference (megaBayesABC! is one plain pass per iteration)")
+    if heterogeneous_residuals:
+        raise NotImplementedError("heterogeneous_residuals (residual weights) with more than 4 traits stays on the reference")
+    if location_parameters == "device":
+        raise NotImplementedError('location_parameters="device" with more than 4 traits is not supported: they are sampled on the host')
+    if getattr(model, "rndTrmVec", []):
+        raise NotImplementedError("set_random effects with more than 4 traits stay on the reference")
+    if any(tt != "continuous" for tt in model.traits_type):
+        raise NotImplementedError("categorical_trait / censored_trait with more than 4 traits stay on the reference")
+    if _not_false(causal_structure):
+        raise NotImplementedError("causal_structure runs with at most 4 traits on the device")
+    if _not_false(RRM):
+        raise NotImplementedError("RRM runs with one trait; with more than 4 traits it stays on the reference")
+    if _not_false(single_step_analysis):
+        raise NotImplementedError("single_step_analysis with more than 4 traits stays on the reference")
+    if Mi.alpha is not False or _not_false(starting_value):
+        raise NotImplementedError("starting_value (marker or location-parameter starting values) with more than 4 traits stays on the reference")
+    if isinstance(Mi.pi, dict):
+        raise NotImplementedError("a Dict Pi over the joint states does not apply to constraint=True with more than 4 traits: pass one Pi, or one per trait")
+    if np.ndim(Mi.pi) > 0 and np.size(Mi.pi) != t:
+        raise ValueError(f"Pi must be a scalar or hold one value per trait ({t}), got {np.size(Mi.pi)} values.")
+    if block_size is not None and not 1 <= int(block_size) <= MEGA_MAX_BLOCK:
+        raise ValueError(f"block_size must be in [1, {MEGA_MAX_BLOCK}] for models with more than 4 traits.")
+    if engine is not None:
+        missing = [m for m in MEGA_METHODS if not hasattr(engine, m)]
+        if missing:
+            raise NotImplementedError("models with more than 4 traits need an engine with the mega-trait sweep (" + ", ".join(missing)
+                                      + " missing); the package has no CPU fallback")
+        if hasattr(engine, "comm_info") and engine.comm_info()[1] > 1:
+            raise NotImplementedError("models with more than 4 traits are not driven from marker or row shards")
+
+
+def constraint_priors(model, phenovar, ftype=np.float32):
+    """The starting values and the priors of the diagonal variances: the defaults of input_data_validation.jl:296-350 and
+    tools4genotypes.jl:353-478, then R_constraint! and G_constraint! (input_data_validation.jl:530-559).  Returns a dict of
+    per-trait vectors: vare, R_df, R_scale, G, G_df, G_scale, pi."""
+    Mi, R, t = model.M[0], model.R, model.nModels
+    phenovar = np.asarray(phenovar, dtype=np.float64)
+    if R.val is False or R.val is None:                                  # input_data_validation.jl:296-350
+        R.val = np.diag(phenovar * 0.5).astype(ftype)
+        R.scale = np.asarray(R.val, dtype=np.float64) * (float(R.df) - t - 1)
+    if Mi.G.val is False and Mi.genetic_variance.val is False:
+        Mi.genetic_variance.val = np.diag(phenovar * 0.5)
+    method, pi = Mi.method, Mi.pi
+    if method == "RR-BLUP":                                              # input_data_validation.jl:24-31
+        pi, Mi.estimatePi = 0.0, False
+    pi_t = np.full(t, float(pi)) if np.ndim(pi) == 0 else np.asarray(pi, dtype=np.float64).reshape(-1).copy()
+    if np.any(pi_t < 0.0) or np.any(pi_t >= 1.0):
+        raise ValueError("Pi must be in [0, 1).")
+    if Mi.G.val is False:                                                # genetic2marker, tools4genotypes.jl:426-438: the diagonal of
+        Vg = np.atleast_2d(np.asarray(Mi.genetic_variance.val, dtype=np.float64))      # Vg ./ (sum2pq Pr(delta_i = 1, delta_j = 1))
+        if Vg.shape != (t, t):
+            raise ValueError(f"The genomic covariance matrix is not a {t} by {t} matrix.")
+        Mi.G.val = np.diag(np.diag(Vg) / (Mi.sum2pq * (1.0 - pi_t)))
+        if not np.all(np.isfinite(np.diag(Mi.G.val))) or np.any(np.diag(Mi.G.val) <= 0):
+            raise ValueError("Marker effects covariance matrix is not postive definite! Please modify the argument: Pi.")
+    Gdf = float(Mi.G.df)
+    Mi.G.scale = np.asarray(Mi.G.val, dtype=np.float64) * (Gdf - t - 1)                                   # tools4genotypes.jl:414-418
+    Rdf = float(R.df) - t                                                # R_constraint!
+    R.scale = np.diag(np.diag(np.asarray(R.scale, dtype=np.float64)) / (Rdf - 1)) * (Rdf - 2) / Rdf
+    R.val = np.diag(np.diag(np.asarray(R.val, dtype=ftype)))
+    Gdf -= t                                                             # G_constraint!
+    Mi.G.scale = np.diag(np.diag(np.asarray(Mi.G.scale, dtype=np.float64)) / (Gdf - 1)) * (Gdf - 2) / Gdf
+    Mi.G.val = np.diag(np.diag(np.asarray(Mi.G.val, dtype=ftype)))
+    return {"vare": np.diag(R.val).astype(np.float64), "R_df": Rdf, "R_scale": np.diag(R.scale).copy(),
+            "G": np.diag(Mi.G.val).astype(np.float64), "G_df": Gdf, "G_scale": np.diag(Mi.G.scale).copy(), "pi": pi_t}
+
+
+def run_megatrait(model, df, *, chain_length, burnin, output_samples_frequency, seed, double_precision, outputEBV, output_heritability,
+                  output_folder, printout_frequency, missing_phenotypes=True, device=0, block_size=None, engine=None, printout_model_info=True,
+                  output_samples_for_all_parameters=False):
+    import pandas as pd
+    from .samples import MarkerSampleWriter
+    Mi = model.M[0]
+    t = model.nModels
+    ftype = np.float64 if double_precision else np.float32
+    if not double_precision and getattr(Mi.genotypes, "dtype", None) == np.float64:
+        raise NotImplementedError("Float64 genotypes (get_genotypes(double_precision=true)) run with runMCMC(double_precision=true)")
+    seed_int = 0 if seed is False else int(seed)
+    rng = np.random.default_rng(seed_int)
+    name = Mi.name
+    traits = list(model.lhsVec)
+    bs = int(block_size) if block_size is not None else DEFAULT_BLOCK
+
+    # ---- align phenotypes and genotypes (input_data_validation.jl:198-294, tools4genotypes.jl:288-323)
+    idcol = df.columns[0]
+    ph = df.copy()
+    ph[idcol] = ph[idcol].astype(str)
+    for tr in traits:
+        if tr not in ph.columns:
+            raise ValueError(f"Phenotypes for {tr} are not found in the data.")
+    Yall = np.stack([ph[tr].to_numpy(dtype=np.float64) for tr in traits])
+    anyobs = np.isfinite(Yall).any(axis=0)
+    if not np.isfinite(Yall[:, anyobs]).all() and not missing_phenotypes:
+        raise ValueError("phenotypes are missing for some traits of some individuals; missing_phenotypes=false does not allow that")
+    geno_index = {g: i for i, g in enumerate(Mi.obsID)}
+    keep = anyobs & ph[idcol].isin(geno_index).to_numpy()                # records without any phenotype are removed (:396-404)
+    ph = ph.loc[keep].reset_index(drop=True)
+    if len(ph) == 0:
+        raise ValueError("no individual has both phenotypes and genotypes")
+    rows = np.array([geno_index[i] for i in ph[idcol]], dtype=np.int64)
+    X = np.asfortranarray(np.asarray(Mi.genotypes)[rows, :].astype(ftype))
+    n, p = X.shape
+    out_ids, out_rows, out_same = None, None, True
+    if outputEBV:                                                        # check_outputID, input_data_validation.jl:143-196
+        want = list(Mi.obsID) if getattr(model, "output_ID", False) is False else list(model.output_ID)
+        if not all(i in geno_index for i in want):
+            print("Testing individuals are not a subset of genotyped individuals (complete genomic data,non-single-step). "
+                  "Only output EBV for tesing individuals with genotypes.")
+            want = [i for i in want if i in geno_index]
+        out_ids = want
+        out_same = out_ids == list(ph[idcol])
+        if not out_same:
+            out_rows = np.array([geno_index[i] for i in out_ids], dtype=np.int64)
+    Mi.output_rows = out_rows if (outputEBV and not out_same) else rows
+    with open(os.path.join(output_folder, "IDs_for_individuals_with_phenotypes.txt"), "w") as fh:
+        fh.write("\n".join(ph[idcol]) + "\n")
+    with open(os.path.join(output_folder, "IDs_for_individuals_with_genotypes.txt"), "w") as fh:
+        fh.write("\n".join(Mi.obsID) + "\n")
+    Y = np.stack([ph[tr].to_numpy(dtype=np.float64) for tr in traits])  # t x n
+    observed = np.isfinite(Y)
+    has_missing = not observed.all()
+    phenovar = np.array([np.var(Y[k][observed[k]].astype(ftype).astype(np.float64), ddof=1) for k in range(t)])
+    Y = np.where(observed, Y, 0.0).astype(ftype).astype(np.float64)      # imputed before first use (residual.jl:52-73)
+
+    # ---- priors
+    pr = constraint_priors(model, phenovar, ftype)
+    vare, Gval, pi_t = pr["vare"].copy(), pr["G"].copy(), pr["pi"].copy()
+    Rdf, Rscale, Gdf, Gscale = pr["R_df"], pr["R_scale"], pr["G_df"], pr["G_scale"]
+    if printout_model_info:
+        print(f"Mega-trait analysis: {t} traits, constraint=true (independent single-trait chains over one genotype matrix).")
+        print("The mean of the prior for the marker effects variances is:")
+        print(np.round(Gval, 6))
+
+    # ---- location parameters on the host, trait by trait
+    Xf, labels = _design(model, ph, idcol)
+    q = [x.shape[1] for x in Xf]
+    off = np.concatenate([[0], np.cumsum(q)]).astype(int)
+    sol = np.zeros(int(off[-1]))
+    lhs = [x.T @ x for x in Xf]
+
+    # ---- the device session
+    own_engine = engine is None
+    if own_engine:
+        from .engine import HipEngine
+        engine = HipEngine(device, precision=64 if double_precision else 32)
+    engine.load_dense(X)
+    if outputEBV and not out_same:
+        engine.load_output_dense(np.asfortranarray(np.asarray(Mi.genotypes)[out_rows, :].astype(ftype)))
+    engine.mega_begin(t, bs, 0)
+    if has_missing:
+        engine.mega_set_missing(~observed)
+    engine.mega_set_residual(Y)                                          # ycorr = y: every starting value is zero
+
+    # ---- accumulators and sample files (output.jl:320-437)
+    run_sol, run_vare, run_varg = _Running(sol), _Running(np.diag(vare)), _Running(np.diag(Gval))
+    run_pi = _Running(pi_t) if Mi.estimatePi else None
+    ebv_run = [_Running(np.zeros(len(out_ids))) for _ in range(t)] if outputEBV else None
+    files = {}
+
+    def _open(key, header):
+        fh = open(os.path.join(output_folder, f"MCMC_samples_{key}.txt"), "w")
+        fh.write(",".join(header) + "\n")
+        files[key] = fh
+
+    rnames = [f"{a}_{b}" for a in traits for b in traits]
+    _open("residual_variance", rnames)
+    _open(f"marker_effects_variances_{name}", rnames)
+    if Mi.estimatePi:
+        _open(f"pi_{name}", [f"pi{i + 1}" for i in range(t)])
+    heritability = bool(outputEBV and output_heritability)               # output.jl:358-362,426-432
+    h2_samples, gv_samples = [], []
+    if heritability:
+        _open("genetic_variance", rnames)
+        _open("heritability", traits)
+    term_cols = {}                                                       # outputMCMCsamples (output.jl:76-95,443-460)
+    for tr, trm in getattr(model, "outputSamplesVec", []):
+        k = traits.index(tr)
+        cols = [off[k] + i for i, (_, eff, _) in enumerate(labels[k]) if eff == trm]
+        if cols:
+            term_cols[f"{tr}.{trm}"] = cols
+            _open(f"{tr}.{trm}", [f"{tr}:{trm}:{labels[k][c - off[k]][2]}" for c in cols])
+    write_marker_samples = output_samples_for_all_parameters or p <= 20000
+    if write_marker_samples:
+        for tr in traits:
+            _open(f"marker_effects_{name}_{tr}", Mi.markerID)
+    bin_writers = [MarkerSampleWriter(os.path.join(output_folder, f"MCMC_samples_marker_effects_{name}_{tr}.bin"), Mi.markerID) for tr in traits]
+    t_sweep, t0 = 0.0, time.time()
+    try:
+        for it in range(1, chain_length + 1):
+            if has_missing:                                              # 1. missing residuals (DEVICE)
+                engine.mega_impute(iteration=it, seed=seed_int, vare=vare)
+            if off[-1]:                                                  # 2. location parameters, trait by trait
+                Rres = engine.mega_get_residual()
+                for k in range(t):
+                    if q[k]:
+                        sk = sol[off[k]:off[k + 1]]
+                        r = Rres[k] + Xf[k] @ sk
+                        _gibbs(lhs[k], sk, Xf[k].T @ r, rng, float(vare[k]))
+                        Rres[k] = r - Xf[k] @ sk
+                engine.mega_set_residual(Rres)
+            st = engine.mega_sweep(iteration=it, seed=seed_int, vare=vare, var_effect=Gval, pi=pi_t)      # 3. marker effects (DEVICE)
+            t_sweep += st["step_ms"]
+            if Mi.estimatePi:                                            # 4. samplePi per trait
+                pi_t = np.array([rng.beta(p - st["sum_delta"][k] + 1.0, st["sum_delta"][k] + 1.0) for k in range(t)])
+            if Mi.G.estimate_variance:                                   # 5. diagonal variances (variance_components.jl:104-109)
+                Gval = np.array([(st["beta_ss"][k] + Gdf * Gscale[k]) / rng.chisquare(p + Gdf) for k in range(t)]).astype(ftype).astype(np.float64)
+            if model.R.estimate_variance:
+                vare = np.array([(st["resid_ss"][k] + Rdf * Rscale[k]) / rng.chisquare(n + Rdf) for k in range(t)]).astype(ftype).astype(np.float64)
+            if it > burnin and (it - burnin) % output_samples_frequency == 0:      # 6. save
+                ks = (it - burnin) / output_samples_frequency
+                run_sol.add(sol, ks)
+                run_vare.add(np.diag(vare), ks)
+                run_varg.add(np.diag(Gval), ks)
+                if run_pi is not None:
+                    run_pi.add(pi_t, ks)
+                    files[f"pi_{name}"].write(",".join(repr(float(v)) for v in pi_t) + "\n")
+                engine.mega_accumulate(ks)
+                for key_, cols in term_cols.items():
+                    files[key_].write(",".join(repr(float(sol[c])) for c in cols) + "\n")
+                files["residual_variance"].write(",".join(repr(float(v)) for v in np.diag(vare).ravel()) + "\n")
+                files[f"marker_effects_variances_{name}"].write(",".join(repr(float(v)) for v in np.diag(Gval).ravel()) + "\n")
+                alpha = engine.mega_get_state()[0]
+                for k, tr in enumerate(traits):
+                    a = alpha[k].astype(ftype)
+                    si = np.flatnonzero(a).astype(np.int32)
+                    bin_writers[k].append(si, a[si])
+                    if write_marker_samples:
+                        fh = files[f"marker_effects_{name}_{tr}"]
+                        a.tofile(fh, sep=",", format="%.17g" if double_precision else "%.9g")
+                        fh.write("\n")
+                if outputEBV:                                            # getEBV, output.jl:281-306
+                    ebvs = [np.asarray(engine.mega_mul_alpha(k, output_rows=not out_same), dtype=np.float64) for k in range(t)]
+                    for k in range(t):
+                        ebv_run[k].add(ebvs[k], ks)
+                    if heritability:                                     # output.jl:498-512 (constraint: the diagonal)
+                        gv = np.diag(np.diag(np.atleast_2d(np.cov(np.stack(ebvs, axis=1), rowvar=False))))
+                        h2 = np.diag(gv) / (np.diag(gv) + vare)
+                        gv_samples.append(gv.ravel())
+                        h2_samples.append(h2)
+                        files["genetic_variance"].write(",".join(repr(float(v)) for v in gv.ravel()) + "\n")
+                        files["heritability"].write(",".join(repr(float(v)) for v in h2) + "\n")
+            if it % printout_frequency == 0 and it > burnin:
+                print(f"\nPosterior means at iteration: {it}")
+                print(f"Residual variance: {np.round(np.diag(run_vare.mean), 6)}")
+    finally:
+        wall = time.time() - t0
+        for fh in files.values():
+            fh.close()
+        for w_ in bin_writers:
+            w_.close()
+
+    # ---- results (output.jl:108-212)
+    out = {}
+    sd_sol = run_sol.sd()
+    out["location parameters"] = pd.DataFrame([(tr, eff, lev, run_sol.mean[off[k] + i], sd_sol[off[k] + i])
+                                               for k in range(t) for i, (tr, eff, lev) in enumerate(labels[k])],
+                                              columns=["Trait", "Effect", "Level", "Estimate", "SD"])
+    out["residual variance"] = pd.DataFrame({"Covariance": rnames, "Estimate": run_vare.mean.ravel(), "SD": run_vare.sd().ravel()})
+    frames = []
+    for k, tr in enumerate(traits):
+        ma, ma2, md = engine.mega_posterior(k)
+        frames.append(pd.DataFrame({"Trait": tr, "Marker_ID": Mi.markerID, "Estimate": ma, "SD": np.sqrt(np.abs(ma2 - ma ** 2)), "Model_Frequency": md}))
+    out[f"marker effects {name}"] = pd.concat(frames, ignore_index=True)
+    out[f"marker effects variance {name}"] = pd.DataFrame({"Covariance": rnames, "Estimate": run_varg.mean.ravel(), "SD": run_varg.sd().ravel()})
+    if run_pi is not None:
+        out[f"pi_{name}"] = pd.DataFrame({"π": traits, "Estimate": run_pi.mean, "SD": run_pi.sd()})
+    if outputEBV:
+        for k, tr in enumerate(traits):
+            m = ebv_run[k].mean
+            out[f"EBV_{tr}"] = pd.DataFrame({"ID": out_ids, "EBV": m, "PEV": np.abs(ebv_run[k].mean2 - m ** 2)})
+    if heritability and gv_samples:                                      # output.jl:196-209 (mean and std of the samples)
+        for key, samples, names in (("genetic_variance", np.array(gv_samples), rnames), ("heritability", np.array(h2_samples), traits)):
+            out[key] = pd.DataFrame({"Covariance": names, "Estimate": samples.mean(axis=0),
+                                     "SD": samples.std(axis=0, ddof=1) if len(samples) > 1 else np.full(samples.shape[1], np.nan)})
+    for key, tab in out.items():                                         # JWAS.jl:480-482
+        tab.to_csv(os.path.join(output_folder, key.replace(" ", "_") + ".txt"), index=False)
+    out["_timing"] = {"wall_s": wall, "device_sweep_ms_total": t_sweep, "iterations": chain_length, "block_size": bs, "n": n, "p": p, "ntraits": t}
+    engine.mega_end()
+    if own_engine:
+        engine.close()
+    return out
