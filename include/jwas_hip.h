@@ -774,6 +774,56 @@ int  jwas_hip_mega_get_gram(jwas_hip_ctx* ctx, int64_t block, int64_t nvalues, d
 int64_t jwas_hip_mega_estimate_bytes(int64_t n, int64_t p, int32_t ntraits, int32_t block_size);
 int  jwas_hip_mega_end(jwas_hip_ctx* ctx);
 
+/* ---- single-step analysis: imputing the genotypes of non-genotyped relatives (single_step/SSBR.jl:83-159) --------------------
+ * runMCMC(...; single_step_analysis=true, pedigree=ped) orders the pedigree as [non-genotyped; genotyped] (calc_Ai, SSBR.jl:71-79)
+ * and imputes, 1000 markers at a time, M_n = A^nn \ (-A^ng M_g) (impute_genotypes, SSBR.jl:83-135); the rows of [M_n; M_g] of the
+ * phenotyped individuals become the matrix the sweep runs on, those of the output IDs the output matrix, both cast to the
+ * genotypes' element type (SSBR.jl:137-138).  The session below does that on the device as a sparse solve with many right-hand
+ * sides (csrc/ssbr.hpp): one thread per marker column walks the rows of L, then of U, in place; a thread reads only what it wrote
+ * itself, so there is nothing to wait for.  A session of its own: it needs no genotype matrix to begin, and touches the context's
+ * matrices only in jwas_hip_ss_impute.
+ *
+ * jwas_hip_ss_begin (SSBR.jl:71-79,94): the factors of A^nn as the host's sparse LU left them, Pr A^nn Pc = L U.  n_n / g: the
+ * numbers of non-genotyped / genotyped individuals of the pedigree.  L and U: CSR over n_n rows, int64 row pointers, int32
+ * columns STRICTLY ASCENDING within a row, double values; L unit lower triangular with its diagonal stored (the last entry of every
+ * row, exactly 1), U upper triangular with its diagonal stored (the first entry, finite and not 0).  perm_r[i] = the position of
+ * row i of A^nn in the permuted system, x[i] = z[perm_c[i]] brings the solution back (scipy.sparse.linalg.splu's perm_r / perm_c).
+ * Ai_ng: A^ng as CSR, n_n rows, g columns.  budget_bytes: what the session may allocate -- it sizes the markers per chunk, ldc =
+ * the largest multiple of 64 (at most 65 536) with jwas_hip_ss_estimate_bytes(.., ldc) <= budget_bytes, returned in *ldc_out
+ * (the work matrix is 8 n_n ldc bytes, the two genotyped blocks 16 g ldc).  Everything is validated before any allocation or
+ * launch: JWAS_HIP_EINVAL for unsorted or duplicate columns, indices out of range, non-finite values, a zero or non-finite U
+ * diagonal, permutations that are not permutations, L not unit lower triangular, U not upper triangular; JWAS_HIP_ENOMEM when the
+ * budget does not pay for one chunk of 64 markers; JWAS_HIP_EUNSUP on a context with a communicator (marker or row shards).  A
+ * second call replaces the session.  The arrays are copied. */
+int  jwas_hip_ss_begin(jwas_hip_ctx* ctx, int64_t n_n, int64_t g, const int64_t* L_rowptr, const int32_t* L_col, const double* L_val,
+                       const int64_t* U_rowptr, const int32_t* U_col, const double* U_val, const int32_t* perm_r, const int32_t* perm_c,
+                       const int64_t* Ai_ng_rowptr, const int32_t* Ai_ng_col, const double* Ai_ng_val, int64_t budget_bytes, int64_t* ldc_out);
+/* The rows a chunk is written to (Z and Zo of SSBR.jl:110-111,129-130).  target 0: the context's dense sweep matrix (rows = the
+ * records of the phenotype file, duplicates allowed), target 1: its output matrix (jwas_hip_load_output_dense_f32 / _f64; rows = the
+ * output IDs).  prow[r] = the row of [M_n; M_g] (pedigree order, 0 .. n_n + g - 1) behind row r of the target; nrows must be the
+ * target's number of rows (JWAS_HIP_EINVAL), the target must exist (JWAS_HIP_ESTATE).  Copied. */
+int  jwas_hip_ss_set_rows(jwas_hip_ctx* ctx, int32_t target, int64_t nrows, const int32_t* prow);
+/* One chunk (SSBR.jl:122-131): Mg = the g x count block of the genotyped individuals (pedigree order) for markers [j0, j0 + count),
+ * column-major with leading dimension ldg, in the context's element type (float, or double in a Float64 context).  Uploaded,
+ * transposed into double, solved, and the rows of every target that has been set are written to columns [j0, j0 + count) of that
+ * matrix in its element type (data_type.(Mpheno), SSBR.jl:137-138); the pad rows of those columns are zero, other columns are not
+ * touched.  Both targets have the sweep matrix's markers (an output matrix is loaded next to a sweep matrix): without a sweep matrix
+ * the call returns JWAS_HIP_ESTATE.  count <= ldc (JWAS_HIP_EINVAL); no target, a target replaced by a matrix of another size, or a sweep matrix whose
+ * blocks have been set up (x'x and the Grams depend on it): JWAS_HIP_ESTATE.  Synchronous. */
+int  jwas_hip_ss_impute(jwas_hip_ctx* ctx, int64_t j0, int64_t count, const void* Mg, int64_t ldg);
+/* Columns [j0, j0 + count) of a target as they lie in device memory: ld x count values in the context's element type, ALL ld rows --
+ * the n rows and the pad rows behind them (ld = n rounded up to 256; JWAS_HIP_EINVAL when `ld` is not the target's).  For tests: the
+ * other column readers return the n rows only, and the unweighted Gram tiles sum over all ld rows, so pad rows must be exactly 0. */
+int  jwas_hip_ss_get_columns(jwas_hip_ctx* ctx, int32_t target, int64_t j0, int64_t count, int64_t ld, void* out);
+/* The same path for a few columns, in double from end to end: out (nrows x count, column-major) = rows prow of [A^nn \ (-A^ng Mg); Mg].
+ * How J is obtained -- the column whose genotyped entries are all -1 (make_JVecs, SSBR.jl:146-159) -- and how tests see the solve
+ * before the cast to Float32.  Touches no matrix of the context. */
+int  jwas_hip_ss_solve_host(jwas_hip_ctx* ctx, int64_t count, const double* Mg_f64, int64_t ldg, int64_t nrows, const int32_t* prow, double* out_f64);
+/* Device bytes of a session with `markers_per_chunk` (rounded up to a multiple of 64) columns per chunk, the target row lists
+ * (4 bytes per row) aside: 24 (n_n + 1) + 12 (nnz_l + nnz_u + nnz_a) + 8 n_n + 8 ldc (n_n + 2 g).  Pure. */
+int64_t jwas_hip_ss_estimate_bytes(int64_t n_n, int64_t g, int64_t nnz_l, int64_t nnz_u, int64_t nnz_a, int64_t markers_per_chunk);
+int  jwas_hip_ss_end(jwas_hip_ctx* ctx);
+
 /* ---- the sweep ------------------------------------------------------------------------------ */
 /* Time every `stride`-th k_block_step launch of subsequent sweeps with HIP events on the
  * sweep's stream (0 = off); the sums come back in jwas_sweep_stats.update_kernel_*. */

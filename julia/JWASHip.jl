@@ -630,6 +630,45 @@ hip_mega_estimate_bytes(n::Integer, p::Integer, ntraits::Integer, block_size::In
     ccall((:jwas_hip_mega_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int32, Int32), n, p, ntraits, block_size)
 hip_mega_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_mega_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
 
+"""
+Single-step analysis (single_step/SSBR.jl:83-159): the imputation M_n = A^nn \\ (-A^ng M_g) on the device.  `hip_ss_begin!` takes the
+factors of A^nn as CSR with 0-based int32 columns ascending within a row (L with its unit diagonal last, U with its diagonal first),
+the permutations of Pr A^nn Pc = L U (0-based) and A^ng as CSR; it returns the markers per chunk the byte budget pays for.
+`hip_ss_set_rows!` names the rows (0-based, pedigree order [non-genotyped; genotyped]) behind the rows of target 0 (the sweep
+matrix) or 1 (the output matrix); `hip_ss_impute!` solves one chunk and writes it into both; `hip_ss_solve_host` returns a few
+columns in Float64 (the J vector of make_JVecs).
+"""
+function hip_ss_begin!(b::HipBackend, n_n::Integer, g::Integer, Lp::Vector{Int64}, Lc::Vector{Int32}, Lv::Vector{Float64},
+                       Up::Vector{Int64}, Uc::Vector{Int32}, Uv::Vector{Float64}, perm_r::Vector{Int32}, perm_c::Vector{Int32},
+                       Ap::Vector{Int64}, Ac::Vector{Int32}, Av::Vector{Float64}, budget_bytes::Integer)
+    ldc = Ref{Int64}(0)
+    hip_check(b.ctx, ccall((:jwas_hip_ss_begin, LIBJWAS_HIP), Cint,
+                           (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
+                            Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int64}),
+                           b.ctx, n_n, g, Lp, Lc, Lv, Up, Uc, Uv, perm_r, perm_c, Ap, Ac, Av, budget_bytes, ldc))
+    return ldc[]
+end
+hip_ss_set_rows!(b::HipBackend, target::Integer, prow::Vector{Int32}) =
+    hip_check(b.ctx, ccall((:jwas_hip_ss_set_rows, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}), b.ctx, target, length(prow), prow))
+"Mg: the g x count block of the genotyped individuals in the context's element type; j0 is 1-based."
+hip_ss_impute!(b::HipBackend, j0::Integer, Mg::StridedMatrix{T}) where {T<:Union{Float32,Float64}} =
+    hip_check(b.ctx, ccall((:jwas_hip_ss_impute, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64), b.ctx, j0 - 1, size(Mg, 2), Mg, stride(Mg, 2)))
+"Columns j0 .. j0 + count - 1 (1-based) of a target with all `ld` rows, pad rows included (for tests)."
+function hip_ss_get_columns(b::HipBackend, ::Type{T}, target::Integer, j0::Integer, count::Integer, ld::Integer) where {T<:Union{Float32,Float64}}
+    out = Matrix{T}(undef, ld, count)
+    hip_check(b.ctx, ccall((:jwas_hip_ss_get_columns, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Int64, Int64, Ptr{Cvoid}), b.ctx, target, j0 - 1, count, ld, out))
+    return out
+end
+function hip_ss_solve_host(b::HipBackend, Mg::StridedMatrix{Float64}, prow::Vector{Int32})
+    out = Matrix{Float64}(undef, length(prow), size(Mg, 2))
+    hip_check(b.ctx, ccall((:jwas_hip_ss_solve_host, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int64, Ptr{Int32}, Ptr{Float64}),
+                           b.ctx, size(Mg, 2), Mg, stride(Mg, 2), length(prow), prow, out))
+    return out
+end
+hip_ss_estimate_bytes(n_n::Integer, g::Integer, nnz_l::Integer, nnz_u::Integer, nnz_a::Integer, markers_per_chunk::Integer) =
+    ccall((:jwas_hip_ss_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int64, Int64, Int64, Int64), n_n, g, nnz_l, nnz_u, nnz_a, markers_per_chunk)
+hip_ss_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_ss_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
 "ycorr .+= shift on the device: the residual correction of an all-ones design column (intercept step, solver.jl:143-162)."
 hip_residual_add_scalar!(b::HipBackend, trait::Integer, shift::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_residual_add_scalar, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Cdouble), b.ctx, trait, shift))

@@ -21,6 +21,7 @@ ANNOT_BAYESC, ANNOT_BAYESR, ANNOT_TREE = 0, 1, 2
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
 RRM_MIN_COEFF, RRM_MAX_COEFF, RRM_MAX_TIMES, RRM_MAX_BLOCK = 2, 4, 64, 256      # csrc/rrm.hpp
 MEGA_MAX_TRAITS, MEGA_MAX_BLOCK, MEGA_TRAIT_TILE = 64, 256, 8                   # csrc/mega.hpp (JWAS_HIP_MEGA_MAX_TRAITS, _MAX_BLOCK, kTT)
+SS_CHUNK_GRANULE, SS_MAX_CHUNK = 64, 65536                                      # csrc/ssbr.hpp (kChunkGranule, kMaxChunk)
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
 # enum jwas_hip_schedule_flags (jwas_hip_last_sweep_schedule): name -> bit
@@ -298,6 +299,13 @@ PROTOTYPES = {
     "jwas_hip_mega_get_gram": (_INT, [_vp, _i64, _i64, _vp, _vp]),
     "jwas_hip_mega_estimate_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "jwas_hip_mega_end": (_INT, [_vp]),
+    "jwas_hip_ss_begin": (_INT, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
+    "jwas_hip_ss_set_rows": (_INT, [_vp, _i32, _i64, _vp]),
+    "jwas_hip_ss_impute": (_INT, [_vp, _i64, _i64, _vp, _i64]),
+    "jwas_hip_ss_get_columns": (_INT, [_vp, _i32, _i64, _i64, _i64, _vp]),
+    "jwas_hip_ss_solve_host": (_INT, [_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "jwas_hip_ss_estimate_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "jwas_hip_ss_end": (_INT, [_vp]),
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -9,8 +9,9 @@ Same names, argument meaning and error behaviour as reworkhow/JWAS.jl v2.3.6 (fi
     runMCMC         JWAS.jl:161-511  -> MCMC/MCMC_BayesianAlphabet.jl
 Everything that is NOT the marker sweep stays here on the host (numpy): data ingestion and QC,
 model parsing, fixed-effect Gibbs, variance-component and pi draws, output tables.  Model families
-outside the hot path (GBLUP, single-step analysis, prediction equations) are rejected with an
-explicit error: they stay on the reference.  Models with several genotype categories (y = intercept + geno1 + geno2) have a driver of
+outside the hot path (GBLUP, prediction equations) are rejected with an
+explicit error: they stay on the reference.  Single-step analyses (single_step_analysis=True with a pedigree) have a driver of their own
+(ssbr.py: the imputation on the device, csrc/ssbr.hpp, then this chain with the terms J and ϵ).  Models with several genotype categories (y = intercept + geno1 + geno2) have a driver of
 their own (multigeno.py: one device context per category, the residual handed over between them).  Random regression models (RRM=Phi) have a driver of their own (rrm.py, csrc/rrm.hpp).  i.i.d. random effects (set_random) and large class factors run on the device
 (mcmc.py step 1, csrc/locpar.hpp).  Categorical / censored traits run here: their liabilities are sampled
 on the device (mcmc.py step 0, csrc/liability.hpp).
@@ -277,7 +278,9 @@ class Model:
 
 class RandomEffect:
     """types.jl:217-226 -- a random effect: one term name over the traits whose equation contains it.  randomType "I": i.i.d.
-    levels; "A": the polygenic effect of a pedigree -- Vinv is A-inverse (CSR, doubles) and names the pedigree's IDs, its levels."""
+    levels; "A": the polygenic effect of a pedigree -- Vinv is A-inverse (CSR, doubles) and names the pedigree's IDs, its levels; "V": an
+    effect with a given Vinv over its own level names, records of the level "missing" in none -- the single-step ϵ (ssbr.py; built internally,
+    set_random does not make one)."""
 
     def __init__(self, name, term_array, traits, Gi, randomType="I", Vinv=0, names=()):
         self.name, self.term_array, self.traits = name, term_array, traits      # "x2", ["y1:x2", "y2:x2"], [0, 1]
@@ -490,7 +493,7 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
             output_samples_for_all_parameters=False,
             # device options (the analogue of storage=:stream's opt-in knobs)
             device=0, block_size=None, gram_mode="mfma", blocks_per_launch=None, location_parameters="auto",
-            annotation_priors="host", _engine=None):
+            annotation_priors="host", fitting_J_vector=True, _engine=None):
     """JWAS.jl:161-511.  Returns the reference's output Dict (output.jl:108-212) as a dict of pandas
     DataFrames and writes the same text files under `output_folder`.
 
@@ -555,6 +558,19 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     per trait; below about 7 traits the session is slower per trait than that sweep (0.65 of its speed at 4): NOTES.md, "Mega-trait
     models".
 
+    single_step_analysis=True, pedigree=ped (a single_step.Pedigree), fitting_J_vector=True (JWAS.jl:173; single_step/SSBR.jl): single-step
+    Bayesian regression over genotyped and non-genotyped relatives -- a driver of its own (ssbr.py).  The genotypes of the non-genotyped
+    pedigree members are imputed on the device (csrc/ssbr.hpp: a sparse solve on the host's LU of A^nn, one thread per marker), the
+    model gains the covariate J and the imputation residual ϵ (a random effect with Vinv = A^nn over the non-genotyped individuals,
+    prior covariance = the genetic variance, which must be given) per trait, and the chain runs on the resident imputed matrix with
+    the location parameters on the device.  EBVs for every pedigree member (or the outputEBV(model, IDs) list within the pedigree):
+    Mout alpha + J sol[J] + sol[ϵ]; "location parameters" lists J and ϵ, their samples go to MCMC_samples_<trait>.J.txt / .ϵ.txt, ϵ's
+    variance to MCMC_samples_<trait>:ϵ_..._variances.txt; no heritability table.  1 to 4 traits with complete records, every sampler,
+    both precisions, residual weights, i.i.d. set_random effects.  Not with storage=:stream (the reference's error), device_genotypes,
+    location_parameters="host", a set_random pedigree effect in the same model, categorical / censored traits, marker starting
+    values, causal_structure, RRM, several genotype categories, more than 4 traits or shards (explicit errors).  Without
+    pedigree=... the flag stays refused.
+
     RRM (JWAS.jl:177,464-475; RRM/RRM.jl, RRM/MCMC_BayesianAlphabet_RRM.jl): a T x c numeric matrix Phi, one row per distinct time point
     (ascending; generatefullPhi builds normalised Legendre columns) -- the random regression model for longitudinal records: the
     first column of df holds the IDs, the column `time` the time point of every record, every marker carries c coefficients.  A
@@ -618,7 +634,8 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
                                 location_parameters=location_parameters, heterogeneous_residuals=heterogeneous_residuals,
                                 starting_value=starting_value, block_size=block_size, engine=_engine)
         RRM = False
-    for flag, name in ((single_step_analysis, "single_step_analysis"), (RRM, "RRM"),
+    single_step = not _is_false(single_step_analysis) and single_step_analysis != 0 and not _is_false(pedigree)
+    for flag, name in ((False if single_step else single_step_analysis, "single_step_analysis"), (RRM, "RRM"),
                        (update_priors_frequency, "update_priors_frequency"),
                        (prediction_equation, "prediction_equation")):
         if not _is_false(flag) and flag != 0:
@@ -650,6 +667,13 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
             raise NotImplementedError("causal_structure runs with at most 4 traits on the device")
         missing_phenotypes = False          # no missing phenotypes and a diagonal residual covariance, for identifiability (:331-333)
         model.R.constraint = True
+    ss_plan = None
+    if single_step:                           # a driver of its own (ssbr.py), validated before anything is written
+        from . import ssbr as _ss
+        if causal_structure is not False:
+            raise NotImplementedError("runMCMC(...; single_step_analysis=..., causal_structure=...) stays on the reference")
+        ss_plan = _ss.validate(model, df, pedigree, fitting_J_vector=fitting_J_vector, location_parameters=location_parameters,
+                               double_precision=bool(double_precision), outputEBV=bool(outputEBV), engine=_engine)
     if output_samples_frequency is None:
         output_samples_frequency = chain_length // 1000 if chain_length > 1000 else 1          # :168
     if int(output_samples_frequency) <= 0:
@@ -687,6 +711,18 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
                             outputEBV=outputEBV, output_heritability=bool(output_heritability), output_folder=output_folder,
                             printout_frequency=printout_frequency, device=device, block_size=block_size, engine=_engine,
                             printout_model_info=printout_model_info)
+    if ss_plan is not None:
+        return _ss.run_single_step(model, df, pedigree, ss_plan, double_precision=bool(double_precision), device=device, engine=_engine,
+                                   memory_guard=memory_guard, memory_guard_ratio=memory_guard_ratio,
+                                   chain_kwargs=dict(chain_length=int(chain_length), burnin=int(burnin),
+                                                     output_samples_frequency=int(output_samples_frequency), seed=seed, starting_value=starting_value,
+                                                     fast_blocks=fast_blocks, independent_blocks=bool(independent_blocks),
+                                                     heterogeneous_residuals=bool(heterogeneous_residuals), outputEBV=outputEBV,
+                                                     output_heritability=bool(output_heritability), output_folder=output_folder,
+                                                     printout_frequency=printout_frequency, missing_phenotypes=missing_phenotypes, block_size=block_size,
+                                                     gram_mode=gram_mode, blocks_per_launch=blocks_per_launch, annotation_priors=annotation_priors,
+                                                     printout_model_info=printout_model_info,
+                                                     output_samples_for_all_parameters=output_samples_for_all_parameters))
     return run_chain(model, df, chain_length=int(chain_length), burnin=int(burnin),
                      output_samples_frequency=int(output_samples_frequency), seed=seed,
                      starting_value=starting_value, fast_blocks=fast_blocks,

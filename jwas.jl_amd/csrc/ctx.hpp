@@ -319,6 +319,22 @@ struct jwas_hip_ctx {
         void* ev = nullptr;                                 // jwg::Events: the change lists of the last sampled block
         std::vector<double> par_host;                       // what par was filled from (kept until the sweep has finished)
     } mg;
+    // Single-step imputation (jwas_hip_ss_begin .. _end; single_step/SSBR.jl:83-159; csrc/ssbr.hpp): the factors of A^nn, A^ng and the
+    // chunk buffers of a sparse solve with many right-hand sides.  It is bound to no matrix: the targets are checked at every chunk.
+    struct Ssbr {
+        bool active = false;
+        int64_t nn = 0, g = 0, ldc = 0;                     // non-genotyped, genotyped, markers per chunk
+        int64_t nnz_l = 0, nnz_u = 0, nnz_a = 0;
+        DevOwner mem;
+        int64_t *Lp = nullptr, *Up = nullptr, *Ap = nullptr;          // [nn + 1]
+        int32_t *Lc = nullptr, *Uc = nullptr, *Ac = nullptr;
+        double *Lv = nullptr, *Uv = nullptr, *Av = nullptr;
+        int32_t *rsrc = nullptr, *perm_c = nullptr;         // [nn] the inverse of perm_r, perm_c
+        double *Gt = nullptr, *W = nullptr;                 // [g][ldc], [nn][ldc]
+        void* stage = nullptr;                              // [ldc][g] doubles: the uploaded block before its transpose
+        int32_t* prow[2] = {};                              // the rows of [M_n; M_g] behind the rows of target 0 (sweep matrix), 1 (output)
+        int64_t nrows[2] = {};                              // (0: the target is not set)
+    } ss;
 };
 
 // ---- errors ------------------------------------------------------------------------------------------------------------------------
@@ -377,6 +393,7 @@ JW_LOCAL void annot_free(jwas_hip_ctx* c);
 JW_LOCAL void sem_free(jwas_hip_ctx* c);
 JW_LOCAL void rrm_free(jwas_hip_ctx* c);
 JW_LOCAL void mega_free(jwas_hip_ctx* c);
+JW_LOCAL void ss_free(jwas_hip_ctx* c);
 
 // `words` ("liabilities", "annotation priors", ...) are not driven from a context that holds a marker or row shard
 static inline int refuse_shards(jwas_hip_ctx* c, const char* words)

@@ -153,6 +153,7 @@ void jwas_hip_destroy(jwas_hip_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     if (c->comm) (void)jwas_hip_comm_destroy(c);
     free_state(c); free_blocks(c); free_storage(c);      // (free_storage: the GWAS session and the liabilities too)
+    ss_free(c);                         // (the single-step imputation session is bound to no matrix: it goes with the context)
     if (c->f64) {
         auto* F = c->f64;
         for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->alpha, (void*)F->beta, F->delta, (void*)F->mean_a,

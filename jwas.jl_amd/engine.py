@@ -32,6 +32,18 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _csr_arrays(M):
+    """(indptr int64, indices int32, data float64) of a sparse matrix as CSR with sorted columns; a triple goes through as it is."""
+    if isinstance(M, (tuple, list)):
+        ptr, col, val = M
+    else:
+        M = M.tocsr().copy()
+        M.sum_duplicates()
+        M.sort_indices()
+        ptr, col, val = M.indptr, M.indices, M.data
+    return np.ascontiguousarray(ptr, dtype=np.int64), np.ascontiguousarray(col, dtype=np.int32), np.ascontiguousarray(val, dtype=np.float64)
+
+
 class SectionSolvePolicy:
     """When the host sets jwas_sweep_params.section_solve (Rule T) along a chain.  A multi-trait sampler-I chain that starts from
     the reference's default prior (every marker in the model) drifts, with Pi estimated, towards sparser joint states; once
@@ -89,6 +101,7 @@ class HipEngine:
         self._explicit_starts = None    # explicit block partition resident (setup_blocks_explicit)
         self._rrm = None                # (T, c, block size) of an open random-regression session
         self._mega = None               # (traits, block size) of an open mega-trait session
+        self._ss = None                 # (non-genotyped, genotyped, markers per chunk) of an open single-step imputation session
 
     # -- plumbing --------------------------------------------------------------------------------
     def _chk(self, rc):
@@ -1094,6 +1107,70 @@ class HipEngine:
     def mega_end(self):
         self._chk(self._L.jwas_hip_mega_end(self._h))
         self._mega = None
+
+    # -- single-step analysis: the imputation solve (SSBR.jl:83-159; csrc/ssbr.hpp) -----------------
+    @staticmethod
+    def ss_estimate_bytes(n_n, g, nnz_l, nnz_u, nnz_a, markers_per_chunk):
+        return _lib.load().jwas_hip_ss_estimate_bytes(int(n_n), int(g), int(nnz_l), int(nnz_u), int(nnz_a), int(markers_per_chunk))
+
+    def ss_begin(self, factors, Ai_ng, budget_bytes=None, markers_per_chunk=None, g=None):
+        """factors: scipy's SuperLU object of Ai_nn (splu), or (L, U, perm_r, perm_c); Ai_ng: n_n x g sparse.  A scipy matrix goes as CSR
+        with sorted columns; an (indptr, indices, data) triple goes as it is.  The markers per chunk come from budget_bytes, or from
+        markers_per_chunk (the budget of exactly that chunk); returned.  g: the number of genotyped individuals when Ai_ng is a triple."""
+        L, U, perm_r, perm_c = (factors.L, factors.U, factors.perm_r, factors.perm_c) if hasattr(factors, "perm_r") else factors
+        (lp, lc, lv), (up, uc, uv), (ap, ac, av) = (_csr_arrays(M) for M in (L, U, Ai_ng))
+        perm_r, perm_c = (np.ascontiguousarray(v, dtype=np.int32) for v in (perm_r, perm_c))
+        n_n = len(lp) - 1
+        if len(up) - 1 != n_n or len(ap) - 1 != n_n or perm_r.shape != (n_n,) or perm_c.shape != (n_n,):
+            raise ValueError(f"L, U, Ai_ng and the permutations must all have {n_n} rows")
+        if g is None:
+            g = int(Ai_ng.shape[1]) if hasattr(Ai_ng, "shape") else int(ac.max(initial=-1)) + 1
+        if budget_bytes is None:
+            budget_bytes = self.ss_estimate_bytes(n_n, g, len(lc), len(uc), len(ac), 1000 if markers_per_chunk is None else markers_per_chunk)
+        ldc = C.c_int64(0)
+        self._chk(self._L.jwas_hip_ss_begin(self._h, n_n, g, _ptr(lp), _ptr(lc), _ptr(lv), _ptr(up), _ptr(uc), _ptr(uv), _ptr(perm_r), _ptr(perm_c),
+                                            _ptr(ap), _ptr(ac), _ptr(av), int(budget_bytes), C.byref(ldc)))
+        self._ss = (n_n, g, ldc.value)
+        return ldc.value
+
+    def ss_set_rows(self, target, prow):
+        """target "sweep" / 0: the dense sweep matrix; "output" / 1: the matrix of load_output_dense.  prow: rows of [M_n; M_g]."""
+        prow = np.ascontiguousarray(prow, dtype=np.int32)
+        self._chk(self._L.jwas_hip_ss_set_rows(self._h, {"sweep": 0, "output": 1}.get(target, target), prow.size, _ptr(prow)))
+
+    def ss_impute(self, j0, Mg):
+        """Mg: g x count, the genotyped individuals' block of markers [j0, j0 + count) in pedigree order, the engine's dtype."""
+        Mg = np.asfortranarray(Mg, dtype=self.dtype)
+        ss = getattr(self, "_ss", None)
+        if Mg.ndim != 2 or (ss and Mg.shape[0] != ss[1]):
+            raise ValueError("the genotyped block must be g x count")
+        self._chk(self._L.jwas_hip_ss_impute(self._h, int(j0), Mg.shape[1], _ptr(Mg), Mg.shape[0]))
+        self.block_size = 0
+
+    def ss_get_columns(self, target, j0, count):
+        """Columns [j0, j0 + count) of a target with ALL rows of its leading dimension (the n rows, then the pad rows): ld x count."""
+        tg = {"sweep": 0, "output": 1}.get(target, target)
+        ld = -(-(self.n if tg == 0 else getattr(self, "n_out", 0)) // 256) * 256
+        out = np.empty((ld, int(count)), dtype=self.dtype, order="F")
+        self._chk(self._L.jwas_hip_ss_get_columns(self._h, tg, int(j0), int(count), ld, _ptr(out)))
+        return out
+
+    def ss_solve_host(self, Mg, prow):
+        """Rows prow of [Ai_nn \\ (-Ai_ng Mg); Mg] in Float64: len(prow) x count."""
+        Mg = np.asfortranarray(Mg, dtype=np.float64)
+        if Mg.ndim == 1:
+            Mg = Mg.reshape(-1, 1, order="F")
+        ss = getattr(self, "_ss", None)
+        if Mg.ndim != 2 or (ss and Mg.shape[0] != ss[1]):
+            raise ValueError("the genotyped block must be g x count")
+        prow = np.ascontiguousarray(prow, dtype=np.int32)
+        out = np.empty((prow.size, Mg.shape[1]), dtype=np.float64, order="F")
+        self._chk(self._L.jwas_hip_ss_solve_host(self._h, Mg.shape[1], _ptr(Mg), Mg.shape[0], prow.size, _ptr(prow), _ptr(out)))
+        return out
+
+    def ss_end(self):
+        self._chk(self._L.jwas_hip_ss_end(self._h))
+        self._ss = None
 
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""

@@ -99,17 +99,17 @@ def _location_terms(model, df):
                     raise ValueError(f"{term.name} is not found in the phenotype data (genotype terms must be "
                                      "Genotypes objects visible to build_model).")
                 lev = df[term.name].astype(str)
-                ped_ = next((re_ for re_ in getattr(model, "rndTrmVec", []) if re_.randomType == "A" and re_.name == term.name), None)
+                ped_ = next((re_ for re_ in getattr(model, "rndTrmVec", []) if re_.randomType in ("A", "V") and re_.name == term.name), None)
                 if ped_ is not None:                          # the levels of a polygenic effect: the pedigree's IDs, in its order
                     names = list(ped_.names)
                     lev = lev.str.strip()
-                    unknown = sorted(set(lev) - set(names))
+                    unknown = sorted(set(lev) - set(names) - ({"missing"} if ped_.randomType == "V" else set()))      # (a Vinv effect: "missing" = in no level, SSBR.jl:28-31)
                     if unknown:
                         raise ValueError(f"{term.name}: {unknown[:5]} {'...' if len(unknown) > 5 else ''} not found in the pedigree.")
                 else:
                     names = sorted(lev.unique())
                 index = {lv: i for i, lv in enumerate(names)}
-                tk.append((term.name, "factor", (lev.map(index).to_numpy(dtype=np.int32), len(names))))
+                tk.append((term.name, "factor", (lev.map(index).fillna(-1).to_numpy(dtype=np.int32), len(names))))
                 lab.extend((term.trait, term.name, lv) for lv in names)
         terms.append(tk)
         labels.append(lab)
@@ -410,7 +410,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
               fast_blocks, independent_blocks=False, heterogeneous_residuals=False, outputEBV, output_heritability=True, output_folder, printout_frequency, memory_guard, memory_guard_ratio,
               missing_phenotypes, device, block_size, gram_mode, engine, printout_model_info,
               output_samples_for_all_parameters, double_precision=False, blocks_per_launch=None, location_parameters="auto",
-              annotation_priors="host", causal_structure=False):
+              annotation_priors="host", causal_structure=False, single_step=None):
+    """single_step: ssbr.SingleStep (None: not a single-step analysis) -- the imputed matrices are resident on the engine, the output IDs
+    and the J / ϵ parts of the EBVs come from it (ssbr.py)."""
     import pandas as pd
     Mi = model.M[0]
     t = model.nModels
@@ -528,7 +530,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     # ---- individuals EBVs are reported for (check_outputID, input_data_validation.jl:143-196): all genotyped
     # individuals unless outputEBV(model, IDs) named a list; IDs without genotypes are dropped with the reference's note
     out_ids, out_rows, out_same = None, None, True
-    if outputEBV:
+    if outputEBV and single_step is not None:      # the pedigree's IDs or the caller's list within it (:173,187-195); its matrix is resident (ssbr.py)
+        out_ids, out_same = list(single_step.out_ids), False
+    elif outputEBV:
         want = list(Mi.obsID) if getattr(model, "output_ID", False) is False else list(model.output_ID)
         known = set(Mi.obsID)
         if not all(i in known for i in want):
@@ -601,7 +605,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     rnd = list(getattr(model, "rndTrmVec", []))
     ped_count = sum(re_.randomType == "A" for re_ in rnd)    # genetic_random_count = the genotypes + the pedigree effect (:301-312)
     varg = np.diag(phenovar) * 0.5 / (1 + ped_count)
-    vare0 = np.diag(phenovar) * 0.5 / (1 + len(rnd) - ped_count)       # nongenetic_random_count (input_data_validation.jl:301-313): only an i.i.d. set_random term changes it
+    vare0 = np.diag(phenovar) * 0.5 / (1 + sum(re_.randomType != "A" and re_.name != "ϵ" for re_ in rnd))       # nongenetic_random_count (input_data_validation.jl:301-313): only an i.i.d. set_random term changes it
     vare_rnd = vare0.copy()                                # ... what the random effects' default prior reads (:352-365)
     R = model.R
     if R.val is False:
@@ -888,7 +892,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         # them), BayesR, multi-trait BayesC and BayesA/B under sampler I and II, marker-specific joint priors; any fast_blocks
         # partition with blocks of <= 1024 markers (uniform or explicit starts), independent_blocks, residual weights; block
         # size x traits <= 2048
-        if stream or devres:
+        if stream or (devres and single_step is None):      # (a single-step run imputes into a Float64 context's own matrix: ssbr.py)
             raise NotImplementedError("double_precision=true needs dense host genotypes (the streaming backend is Float32 only, readgenotypes.jl:246-248)")
         if mega:
             raise NotImplementedError("double_precision=true runs every sampler on the device except constraint=true (megaBayesABC), "
@@ -963,7 +967,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                                               "(random covariates stay on the reference)")
         if len(rnd) > 8:
             raise NotImplementedError("at most 8 set_random effects on the device")
-        if ped_count:
+        if any(re_.randomType in ("A", "V") for re_ in rnd):
             missing_ = [m_ for m_ in LOCPAR_PED_METHODS if eng_ is not None and not hasattr(eng_, m_)]
             if missing_:
                 raise NotImplementedError("a pedigree random effect needs an engine with " + ", ".join(missing_) + "; the package has no CPU fallback")
@@ -1004,7 +1008,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         if lp_device:                                              # the term layouts, sol and its means (jwas_hip_locpar_estimate_bytes)
             need += HipEngine.locpar_estimate_bytes(n, sum(len(tk) for tk in lp_terms), sum(q))
             for re_ in rnd:                                        # A-inverse and its colours (jwas_hip_lp_structure_estimate_bytes)
-                if re_.randomType == "A":
+                if re_.randomType in ("A", "V"):
                     need += HipEngine.locpar_structure_estimate_bytes(re_.Vinv.shape[0], re_.Vinv.nnz)
         if mt_device:                                              # the records' codes, the tables, the second piece sums
             need += HipEngine.mtmiss_estimate_bytes(n)
@@ -1030,7 +1034,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     else:
         engine.load_dense(np.asfortranarray(X, dtype=ftype))      # after alignment (tools4genotypes.jl:310-321); Float64 on request (JWAS.jl:353)
     X_out_host = None
-    if outputEBV and not out_same:             # Mi.output_genotypes = Z_out * genotypes (tools4genotypes.jl:290-296)
+    if outputEBV and not out_same and single_step is None:      # Mi.output_genotypes = Z_out * genotypes (tools4genotypes.jl:290-296)
         if double_precision and not (hasattr(engine, "load_output_dense") and hasattr(engine, "mul_alpha_output")):
             X_out_host = np.asarray(Mi.genotypes[out_rows, :], dtype=np.float64)      # (an injected engine without output rows: the host forms the product)
         else:                                  # a second resident matrix, Float64 in a Float64 run (JWAS.jl:353)
@@ -1083,7 +1087,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     if lp_device:
         engine.locpar_begin(t)
         for g_, re_ in enumerate(rnd):                                   # the structure goes up before the effect's members are added
-            if re_.randomType == "A":
+            if re_.randomType in ("A", "V"):
                 engine.locpar_set_group_structure(g_, re_.Vinv.indptr, re_.Vinv.indices, re_.Vinv.data)
         for k in range(t):                                               # trait by trait, term by term: the reference's equation order
             for nm, kind_, val in lp_terms[k]:
@@ -1196,7 +1200,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     if Mi.estimatePi and (np.size(pi) <= 20000 or output_samples_for_all_parameters):   # (marker-level pi: p values per sample)
         npi = t if mega else np.size(pi)
         _open(f"pi_{name}", [f"pi{i + 1}" for i in range(npi)] if npi > 1 else ["pi"])
-    heritability = bool(outputEBV and output_heritability)              # output.jl:358-362,426-432
+    heritability = bool(outputEBV and output_heritability) and single_step is None      # output.jl:358-362,426-432 (not in a single-step analysis: :196,358,426,498)
     if heritability:
         _open("genetic_variance", rnames if t > 1 else [model.lhsVec[0]])
         _open("heritability", list(model.lhsVec))
@@ -1242,6 +1246,13 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 lev_ = np.array([ped.index[i] for i in out_ids], dtype=np.int64)
                 for k in re_.traits:
                     ped_cols[k] = off[k] + next(i for i, (_, eff, _) in enumerate(labels[k]) if eff == re_.name) + lev_
+    # single-step EBV = Mout alpha + J_out sol[J] + Zo sol[ϵ] (getEBV over mme.output_X, output.jl:281-306; SSBR.jl:39-47): per trait the
+    # (columns of sol, coefficients) of every output ID
+    ss_cols = {}
+    if outputEBV and single_step is not None:
+        for k in range(t):
+            for trm, cols_, coef_ in single_step.ebv_terms(labels[k]):
+                ss_cols.setdefault(k, []).append((off[k] + cols_, coef_))
     liab_files = {}                                                     # output.jl:367-372 (no header lines, as there)
     for k in liab_traits:
         liab_files[("liabilities", k)] = open(os.path.join(output_folder, f"MCMC_samples_liabilities_{model.lhsVec[k]}.txt"), "w")
@@ -1481,7 +1492,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 k = (it - burnin) / output_samples_frequency
                 if lp_device:
                     engine.locpar_accumulate(k)                             # (running means on the device, read once at the end)
-                    if term_cols or ped_cols:
+                    if term_cols or ped_cols or ss_cols:
                         sol = engine.locpar_get_sol()
                 else:
                     run_sol.add(sol, k)
@@ -1552,6 +1563,11 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                         ebvs = [engine.mul_alpha(kk) if out_same else engine.mul_alpha_output(kk) for kk in range(t)]   # getEBV, output.jl:281-306
                     for kk, cols_ in ped_cols.items():                      # the polygenic part of this sample, added on the host
                         ebvs[kk] = (np.asarray(ebvs[kk], dtype=np.float64) + sol[cols_]).astype(ftype)
+                    for kk, parts_ in ss_cols.items():                      # the J and ϵ parts of this sample, added on the host
+                        e_ = np.asarray(ebvs[kk], dtype=np.float64)
+                        for cols_, coef_ in parts_:
+                            e_ = e_ + coef_ * sol[cols_]
+                        ebvs[kk] = e_.astype(ftype)
                     for kk in range(t):
                         ebv_run[kk].add(ebvs[kk], k)
                     if heritability:                                        # output.jl:498-512

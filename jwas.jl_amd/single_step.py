@@ -10,8 +10,9 @@ individuals marker chunk by marker chunk,
 then align [M_n; M_g] to the phenotyped individuals.  The result is the dense REAL-VALUED n_pheno x p matrix the sweep
 runs on (SSBR.jl:137-138) -- 672 GB at config 5, which is why it is produced and uploaded chunk by chunk here and never
 exists on the host as a whole: every chunk is solved on the host (one sparse LU of A^nn, reused) and written straight into
-the device matrix (jwas_hip_set_columns).  The epsilon / J model terms of SSBRrun (SSBR.jl:23-53) are host-model terms
-outside the marker path and stay on the reference.
+the device matrix (jwas_hip_set_columns) -- or, with solver="device", solved on the device from the same factorisation
+(csrc/ssbr.hpp), where only the g x chunk blocks of the genotyped individuals are uploaded.  The epsilon / J model terms of SSBRrun
+(SSBR.jl:23-53) and the whole analysis, runMCMC(single_step_analysis=True, pedigree=ped), are ssbr.py.
 """
 import numpy as np
 
@@ -139,14 +140,20 @@ def a_inverse(ped, order=None):
     return (h.T @ h).tocsc()
 
 
-def impute_genotypes(geno, ped, pheno_ids, engine=None, markers_per_chunk=1000, return_host=False):
+def impute_genotypes(geno, ped, pheno_ids, engine=None, markers_per_chunk=1000, return_host=False, solver="host"):
     """impute_genotypes (SSBR.jl:83-142).  `geno`: Genotypes of the genotyped individuals (dense, processed by
     get_genotypes); `ped`: Pedigree; `pheno_ids`: the individuals of the phenotype file, in its order.  Returns a
     Genotypes object whose n_pheno x p matrix is resident on `engine` (a HipEngine; api.device_genotypes semantics) --
-    or, with return_host=True (small problems, tests), whose `genotypes` is the host matrix."""
+    or, with return_host=True (small problems, tests), whose `genotypes` is the host matrix.
+    solver: "host" (the default) solves every chunk with SuperLU on the host and uploads it; "device" sends one factorisation to the
+    engine's imputation session (engine.ss_*, csrc/ssbr.hpp) and then only the g x chunk blocks of the genotyped individuals."""
     import scipy.sparse as sp
     import scipy.sparse.linalg as spla
     from .api import Genotypes, Variance
+    if solver not in ("host", "device"):
+        raise ValueError('solver must be "host" or "device".')
+    if solver == "device" and (return_host or engine is None):
+        raise ValueError('impute_genotypes(solver="device") imputes into the matrix resident on `engine`')
     gset = set(geno.obsID)
     for g in geno.obsID:
         if g not in ped.index:
@@ -164,7 +171,6 @@ def impute_genotypes(geno, ped, pheno_ids, engine=None, markers_per_chunk=1000, 
     Ai_nn, Ai_ng = Ai[:nn, :nn].tocsc(), Ai[:nn, nn:].tocsr()
     gidx = {g: i for i, g in enumerate(geno.obsID)}
     Mg_rows = np.array([gidx[ped.ids[i]] for i in gen], dtype=np.int64)            # Z * genotypes (:88-89)
-    lu = spla.splu(Ai_nn) if nn else None
     where = {int(i): k for k, i in enumerate(order)}
     prow = np.array([where[ped.index[v]] for v in pheno_ids], dtype=np.int64)      # rows of [M_n; M_g] per phenotyped individual
     n_ph, p = len(pheno_ids), geno.nMarkers
@@ -174,15 +180,28 @@ def impute_genotypes(geno, ped, pheno_ids, engine=None, markers_per_chunk=1000, 
         if engine is None:
             raise ValueError("impute_genotypes needs a HipEngine to hold the imputed matrix (or return_host=True)")
         engine.alloc_dense(n_ph, p)
-    for j0 in range(0, p, markers_per_chunk):                                      # :112-131
-        j1 = min(p, j0 + markers_per_chunk)
-        Mg = np.asarray(G[Mg_rows, j0:j1], dtype=np.float64)
-        Mn = lu.solve(-(Ai_ng @ Mg)) if nn else np.zeros((0, j1 - j0))
-        chunk = np.vstack([Mn, Mg])[prow].astype(np.float32)                       # Z * Mped_chunk, data_type.(...) (:128,:137-138)
-        if return_host:
-            host[:, j0:j1] = chunk
-        else:
-            engine.set_columns(j0, chunk)
+    if solver == "device":
+        from .ssbr import factorize
+        if not nn:
+            raise ValueError("every pedigree member is genotyped: there is nothing to impute")
+        ldc = engine.ss_begin(factorize(Ai_nn), Ai_ng, markers_per_chunk=markers_per_chunk)
+        try:
+            engine.ss_set_rows("sweep", prow)
+            for j0 in range(0, p, ldc):
+                engine.ss_impute(j0, np.asfortranarray(G[Mg_rows, j0:min(p, j0 + ldc)], dtype=np.float32))
+        finally:
+            engine.ss_end()
+    else:
+        lu = spla.splu(Ai_nn) if nn else None
+        for j0 in range(0, p, markers_per_chunk):                                  # :112-131
+            j1 = min(p, j0 + markers_per_chunk)
+            Mg = np.asarray(G[Mg_rows, j0:j1], dtype=np.float64)
+            Mn = lu.solve(-(Ai_ng @ Mg)) if nn else np.zeros((0, j1 - j0))
+            chunk = np.vstack([Mn, Mg])[prow].astype(np.float32)                   # Z * Mped_chunk, data_type.(...) (:128,:137-138)
+            if return_host:
+                host[:, j0:j1] = chunk
+            else:
+                engine.set_columns(j0, chunk)
     out = Genotypes(pheno_ids, geno.markerID, n_ph, p, geno.alleleFreq, geno.sum2pq, geno.centered,
                     host if return_host else np.zeros((n_ph, 0), dtype=np.float32))
     if not return_host:
