@@ -16,11 +16,15 @@ Per iteration (the reference's order, MCMC_BayesianAlphabet.jl:184-421):
   6. every output_samples_frequency after burn-in: running means (device for markers)       (:399-413)
 The host consumes only O(n) + O(p)-reducible quantities from the device.
 """
+import contextlib
 import os
-import sys
 import time
 
 import numpy as np
+
+from .chain_output import (GeneticVarianceSamples, Running, SampleFiles, covariance_table, ebv_tables, host_blas_limit, location_table,
+                           marker_effects_table, pi_labels, pi_table, print_posterior_means, resolve_output_ids, sparse_effects,
+                           term_sample_columns, write_id_files, write_tables)
 
 BAYESR_GAMMA = np.array([0.0, 0.01, 0.1, 1.0])
 DEVICE_BLOCK_SIZES = (64, 128, 256, 512, 1024)
@@ -28,22 +32,6 @@ DEVICE_BLOCK_SIZES = (64, 128, 256, 512, 1024)
 
 def _supported_block(b):
     return min(DEVICE_BLOCK_SIZES, key=lambda s: abs(s - b))
-
-
-class _Running:
-    """mean += (x-mean)/k ; mean2 += (x^2-mean2)/k   (output.jl:556-560)"""
-
-    def __init__(self, like):
-        self.mean = np.zeros_like(np.asarray(like, dtype=np.float64))
-        self.mean2 = np.zeros_like(self.mean)
-
-    def add(self, x, k):
-        x = np.asarray(x, dtype=np.float64)
-        self.mean += (x - self.mean) / k
-        self.mean2 += (x * x - self.mean2) / k
-
-    def sd(self):
-        return np.sqrt(np.abs(self.mean2 - self.mean ** 2))          # output.jl:112,133
 
 
 def _design(model, df, ids_col):
@@ -386,6 +374,17 @@ def sample_from_conditional_inverse_wishart(rng, df, scale, binary_index):
     return (R + R.T) / 2
 
 
+@contextlib.contextmanager
+def _on_error(*calls):
+    """An exception inside the block: `calls` run, then it propagates."""
+    try:
+        yield
+    except BaseException:
+        for call in calls:
+            call()
+        raise
+
+
 def _gibbs(A, x, b, rng, vare=None):
     """One sweep of the single-site Gibbs sampler on the MME (iterative_solver/solver.jl:143-162)."""
     for i in range(len(x)):
@@ -413,7 +412,6 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
               annotation_priors="host", causal_structure=False, single_step=None):
     """single_step: ssbr.SingleStep (None: not a single-step analysis) -- the imputed matrices are resident on the engine, the output IDs
     and the J / ϵ parts of the EBVs come from it (ssbr.py)."""
-    import pandas as pd
     Mi = model.M[0]
     t = model.nModels
     sem = causal_structure is not False                                 # the recursive structural equation model (SEM.jl)
@@ -533,14 +531,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     if outputEBV and single_step is not None:      # the pedigree's IDs or the caller's list within it (:173,187-195); its matrix is resident (ssbr.py)
         out_ids, out_same = list(single_step.out_ids), False
     elif outputEBV:
-        want = list(Mi.obsID) if getattr(model, "output_ID", False) is False else list(model.output_ID)
-        known = set(Mi.obsID)
-        if not all(i in known for i in want):
-            print("Testing individuals are not a subset of genotyped individuals (complete genomic data,non-single-step). "
-                  "Only output EBV for tesing individuals with genotypes.")
-            want = [i for i in want if i in known]
-        out_ids = want
-        out_same = out_ids == list(ph[idcol])             # exactly the training rows, same order: X itself
+        out_ids, out_same = resolve_output_ids(model, Mi.obsID, ph[idcol])      # (out_same: exactly the training rows, same order: X itself)
         if not out_same:
             if stream or devres:
                 raise NotImplementedError("storage=:stream reports EBVs for the genotyped individuals in file order "
@@ -550,10 +541,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     if not stream and not devres:
         # rows of Mi.genotypes behind Mi.output_genotypes (tools4genotypes.jl:290-296); GWAS() reads them (GWAS.jl:148)
         Mi.output_rows = out_rows if (outputEBV and not out_same) else rows
-    with open(os.path.join(output_folder, "IDs_for_individuals_with_phenotypes.txt"), "w") as fh:
-        fh.write("\n".join(ph[idcol]) + "\n")
-    with open(os.path.join(output_folder, "IDs_for_individuals_with_genotypes.txt"), "w") as fh:
-        fh.write("\n".join(Mi.obsID) + "\n")
+    write_id_files(output_folder, ph[idcol], Mi.obsID)
     liab_codes, liab_bounds = {}, {}
     if has_liab:                                                          # input_data_validation.jl:255-290
         for k, tr in enumerate(model.lhsVec):
@@ -1151,9 +1139,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         engine.sem_begin(Y.astype(np.float64), sem_cs)
         sem_open = True
         sem_lam = np.zeros((t, t))
-        run_lam = _Running(sem_lam)
-        # (the reference writes this file to the working directory, SEM.jl:59-60; here it lives with the other samples)
-        sem_file = open(os.path.join(output_folder, "structure_coefficient_MCMC_samples.txt"), "w")
+        run_lam = Running(sem_lam)
 
     vare = ftype(R.val) if t == 1 else np.asarray(R.val, dtype=ftype)
     Gval = ftype(Mi.G.val) if t == 1 else np.asarray(Mi.G.val, dtype=ftype)
@@ -1180,63 +1166,20 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         return np.asarray(re_.Gi.val, dtype=np.float64)
 
     # ---- accumulators and sample files (output.jl:320-437)
-    run_sol, run_vare = _Running(sol), _Running(vare)
-    run_varg = _Running(Gval) if not pervar else None
-    run_pi = _Running(np.atleast_1d(np.asarray(pi_t if mega else pi, dtype=np.float64))) if Mi.estimatePi else None
-    ebv_run = [_Running(np.zeros(len(out_ids))) for _ in range(t)] if outputEBV else None
-    run_scale = _Running(np.atleast_1d(np.float64(Mi.G.scale))) if (Mi.G.estimate_scale and t == 1) else None
+    run_sol, run_vare = Running(sol), Running(vare)
+    run_varg = Running(Gval) if not pervar else None
+    run_pi = Running(np.atleast_1d(np.asarray(pi_t if mega else pi, dtype=np.float64))) if Mi.estimatePi else None
+    ebv_run = [Running(np.zeros(len(out_ids))) for _ in range(t)] if outputEBV else None
+    run_scale = Running(np.atleast_1d(np.float64(Mi.G.scale))) if (Mi.G.estimate_scale and t == 1) else None
     name = Mi.name
-    files = {}
-
-    def _open(key, header):
-        fh = open(os.path.join(output_folder, f"MCMC_samples_{key}.txt"), "w")
-        fh.write(",".join(header) + "\n")
-        files[key] = fh
-
-    rnames = [f"{a}_{b}" for a in model.lhsVec for b in model.lhsVec]
-    _open("residual_variance", rnames if t > 1 else [model.lhsVec[0]])
-    if not pervar:
-        _open(f"marker_effects_variances_{name}", rnames if t > 1 else ["1"])
-    if Mi.estimatePi and (np.size(pi) <= 20000 or output_samples_for_all_parameters):   # (marker-level pi: p values per sample)
-        npi = t if mega else np.size(pi)
-        _open(f"pi_{name}", [f"pi{i + 1}" for i in range(npi)] if npi > 1 else ["pi"])
-    heritability = bool(outputEBV and output_heritability) and single_step is None      # output.jl:358-362,426-432 (not in a single-step analysis: :196,358,426,498)
-    if heritability:
-        _open("genetic_variance", rnames if t > 1 else [model.lhsVec[0]])
-        _open("heritability", list(model.lhsVec))
-        h2_samples, gv_samples = [], []
-    term_cols = {}                                                      # outputMCMCsamples (output.jl:76-95,443-460)
-    for tr, trm in getattr(model, "outputSamplesVec", []):
-        k = model.lhsVec.index(tr)
-        cols = [off[k] + i for i, (_, eff, _) in enumerate(labels[k]) if eff == trm]
-        if cols:
-            term_cols[f"{tr}.{trm}"] = cols
-            _open(f"{tr}.{trm}", [f"{tr}:{trm}:{labels[k][c - off[k]][2]}" for c in cols])
+    cov = [f"{a}_{b}" for a in model.lhsVec for b in model.lhsVec] if t > 1 else [model.lhsVec[0]]
+    term_cols = term_sample_columns(model, labels, off)
     write_marker_samples = output_samples_for_all_parameters or p <= 20000
-    if write_marker_samples:
-        for k, tr in enumerate(model.lhsVec):
-            _open(f"marker_effects_{name}_{tr}", Mi.markerID)
-    # every saved sample also goes to a binary file of sparse records -- the nonzero effects compacted on the device
-    # (samples.py); the text row of p values (output.jl:467) only for small p or on request
-    from .samples import MarkerSampleWriter
-    bin_writers = [MarkerSampleWriter(os.path.join(output_folder, f"MCMC_samples_marker_effects_{name}_{tr}.bin"), Mi.markerID)
-                   for tr in model.lhsVec]
-    sem_writers = {}
-    if sem:                                                             # SEM.jl:187-316 (the reference's files name the term "genotypes")
-        for kind_ in ("indirect", "overall"):
-            sem_writers[kind_] = [MarkerSampleWriter(os.path.join(output_folder, f"MCMC_samples_{kind_}_marker_effects_{name}_{tr}.bin"), Mi.markerID)
-                                  for tr in model.lhsVec]
-            if write_marker_samples:
-                for tr in model.lhsVec:
-                    _open(f"{kind_}_marker_effects_{name}_{tr}", Mi.markerID)
-
-    rnd_keys, run_rnd = [], []
-    for re_ in rnd:                                                     # output.jl:348-351,401-405; the polygenic effect: :326-327,416-420
-        key_ = "polygenic_effects_variance" if re_.randomType == "A" else "_".join(re_.term_array) + "_variances"
-        kk = len(re_.term_array)
-        _open(key_, [f"{re_.term_array[a]}_{re_.term_array[b]}" for a in range(kk) for b in range(kk)])
-        rnd_keys.append(key_)
-        run_rnd.append(_Running(np.zeros(kk * kk)))
+    rnd_keys = ["polygenic_effects_variance" if re_.randomType == "A" else "_".join(re_.term_array) + "_variances" for re_ in rnd]
+    rnd_cov = [[f"{a}_{b}" for a in re_.term_array for b in re_.term_array] for re_ in rnd]
+    run_rnd = [Running(np.zeros(len(names_))) for names_ in rnd_cov]
+    genvar, bin_writers = None, {}
+    files = SampleFiles(output_folder)
     lp_utu = None
     # EBV = genomic + polygenic part (prediction_setup, output.jl:29-36): entry of sol of every output ID in the pedigree term of trait k
     ped_cols = {}
@@ -1253,28 +1196,38 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         for k in range(t):
             for trm, cols_, coef_ in single_step.ebv_terms(labels[k]):
                 ss_cols.setdefault(k, []).append((off[k] + cols_, coef_))
-    liab_files = {}                                                     # output.jl:367-372 (no header lines, as there)
-    for k in liab_traits:
-        liab_files[("liabilities", k)] = open(os.path.join(output_folder, f"MCMC_samples_liabilities_{model.lhsVec[k]}.txt"), "w")
-        if k in thresholds:
-            liab_files[("threshold", k)] = open(os.path.join(output_folder, f"MCMC_samples_threshold_{model.lhsVec[k]}.txt"), "w")
     t_sweep = 0.0
     iter_end = []                                # perf_counter at the end of every iteration (each ends synchronised with the device)
-    # The host step between two sweeps is a handful of O(n) vector operations.  A threaded BLAS runs them on every core and
-    # its workers keep spinning afterwards: in a container with a CPU quota that burns the quota and stalls the NEXT device
-    # call until the scheduler's next 100 ms period (measured: 78-100 ms per iteration instead of 21 at 50k x 600k).
-    # JWAS_HOST_BLAS_THREADS overrides (0 = leave the BLAS alone).
-    _blas_limit = None
-    try:
-        nthr = int(os.environ.get("JWAS_HOST_BLAS_THREADS", "1"))
-        if nthr > 0:
-            from threadpoolctl import threadpool_limits
-            _blas_limit = threadpool_limits(limits=nthr, user_api="blas")
-    except Exception:                            # threadpoolctl missing: nothing to limit with
-        _blas_limit = None
+    # an exception inside the chain: the open sessions go with the files
+    ends = ([engine.sem_end] if sem_open else []) + ([engine.annot_end] if ann_open else [])
     t0 = time.time()
     # ================================ the chain =================================================
-    try:
+    with host_blas_limit(), files, _on_error(*ends):
+        files.open("residual_variance", cov)                            # output.jl:320-437
+        if not pervar:
+            files.open(f"marker_effects_variances_{name}", cov if t > 1 else ["1"])
+        if Mi.estimatePi and (np.size(pi) <= 20000 or output_samples_for_all_parameters):   # (marker-level pi: p values per sample)
+            npi = t if mega else np.size(pi)
+            files.open(f"pi_{name}", [f"pi{i + 1}" for i in range(npi)] if npi > 1 else ["pi"])
+        for key_, (_, header) in term_cols.items():
+            files.open(key_, header)
+        # every saved sample goes to a binary file of sparse records -- the nonzero effects compacted on the device (samples.py);
+        # the text row of p values (output.jl:467) only for small p or on request
+        for kind_ in ("", "indirect_", "overall_") if sem else ("",):   # SEM.jl:187-316 (the reference's files name the term "genotypes")
+            bin_writers[kind_] = [files.marker_writer(f"{kind_}marker_effects_{name}_{tr}", Mi.markerID) for tr in model.lhsVec]
+            if write_marker_samples:
+                for tr in model.lhsVec:
+                    files.open(f"{kind_}marker_effects_{name}_{tr}", Mi.markerID)
+        if sem:      # (the reference writes this file to the working directory, SEM.jl:59-60; here it lives with the other samples)
+            files.open_bare("structure_coefficient", "structure_coefficient_MCMC_samples.txt")
+        for key_, names_ in zip(rnd_keys, rnd_cov):                     # output.jl:348-351,401-405; the polygenic effect: :326-327,416-420
+            files.open(key_, names_)
+        for k in liab_traits:                                           # output.jl:367-372 (no header lines, as there)
+            files.open_bare(f"liabilities_{model.lhsVec[k]}")
+            if k in thresholds:
+                files.open_bare(f"threshold_{model.lhsVec[k]}")
+        if outputEBV and output_heritability and single_step is None:   # output.jl:358-362,426-432 (not in a single-step analysis: :196,358,426,498)
+            genvar = GeneticVarianceSamples(files, cov, list(model.lhsVec))
         for it in range(1, chain_length + 1):
             # 0. categorical and censored traits (MCMC_BayesianAlphabet.jl:186-191): liabilities and residuals on the device,
             #    then the thresholds of the traits with more than two categories from the chain's rng
@@ -1499,7 +1452,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 for g_, re_ in enumerate(rnd):                              # output.jl:449-452
                     Gv_ = np.linalg.inv(_gi64(re_)).ravel()
                     run_rnd[g_].add(Gv_, k)
-                    files[rnd_keys[g_]].write(",".join(repr(float(v)) for v in Gv_) + "\n")
+                    files.row(rnd_keys[g_], Gv_)
                 run_vare.add(vare, k)
                 if run_varg is not None:
                     run_varg.add(Gval, k)
@@ -1513,49 +1466,38 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                     run_scale.add(np.atleast_1d(np.float64(Mi.G.scale)), k)
                 if ann is not False:
                     A_.accumulate(ann, k)
-                for key_, cols in term_cols.items():
-                    files[key_].write(",".join(repr(float(sol[c])) for c in cols) + "\n")
-                files["residual_variance"].write(",".join(repr(float(v)) for v in np.atleast_1d(vare).ravel()) + "\n")
-                for (what, kk), fh in liab_files.items():                   # output.jl:514-523 (read from the device only here)
-                    row = engine.liabilities(kk) if what == "liabilities" else thresholds[kk]
-                    fh.write(",".join(repr(float(v)) for v in row) + "\n")
+                for key_, (cols, _) in term_cols.items():
+                    files.row(key_, sol[cols])
+                files.row("residual_variance", np.atleast_1d(vare).ravel())
+                for kk in liab_traits:                                      # output.jl:514-523 (read from the device only here)
+                    files.row(f"liabilities_{model.lhsVec[kk]}", engine.liabilities(kk))
+                    if kk in thresholds:
+                        files.row(f"threshold_{model.lhsVec[kk]}", thresholds[kk])
                 if not pervar:
-                    files[f"marker_effects_variances_{name}"].write(",".join(repr(float(v)) for v in np.atleast_1d(Gval).ravel()) + "\n")
+                    files.row(f"marker_effects_variances_{name}", np.atleast_1d(Gval).ravel())
                 if Mi.estimatePi and f"pi_{name}" in files:
-                    files[f"pi_{name}"].write(",".join(repr(float(v)) for v in (engine.annot_prior() if pi_marker_dev else np.atleast_1d(pi_t if mega else pi))) + "\n")
+                    files.row(f"pi_{name}", engine.annot_prior() if pi_marker_dev else np.atleast_1d(pi_t if mega else pi))
                 sem_direct = []
                 for kk, tr in enumerate(model.lhsVec):
-                    if hasattr(engine, "alpha_sparse"):
-                        si, sv = engine.alpha_sparse(kk)              # (idx, val) compacted on the device
-                    else:
-                        a_ = engine.get_state(kk)[0]
-                        si = np.flatnonzero(a_).astype(np.int32); sv = a_[si]
-                    bin_writers[kk].append(si, sv)
+                    si, sv = sparse_effects(engine, kk)
+                    bin_writers[""][kk].append(si, sv)
                     sem_direct.append((si, sv))
-                    if write_marker_samples:
-                        a = np.zeros(p, dtype=ftype)
-                        a[si] = sv
-                        fh = files[f"marker_effects_{name}_{tr}"]
-                        a.tofile(fh, sep=",", format="%.9g")          # text at C speed; 9 significant digits round-trip Float32
-                        fh.write("\n")
+                    if write_marker_samples:                                # run_chain: nine digits also under double_precision
+                        files.sparse_effects_row(f"marker_effects_{name}_{tr}", si, sv, p, ftype, "%.9g")
                 if sem:
                     # compute_indirect_effect (SEM.jl:245-252): K = sum_m Lambda^m; the device keeps the running means of K alpha and
                     # alpha + K alpha, the host forms this sample's rows from the sparse direct effects it has just read
                     sem_K = indirect_matrix(sem_lam)
                     engine.sem_accumulate(sem_K, k)
                     run_lam.add(sem_lam, k)
-                    sem_file.write(",".join(repr(float(v)) for v in sem_lam.ravel(order="F")) + "\n")      # vec(Λ), MCMC_BayesianAlphabet.jl:410-412
+                    files.row("structure_coefficient", sem_lam.ravel(order="F"))      # vec(Λ), MCMC_BayesianAlphabet.jl:410-412
                     u_idx, ind_, ov_ = indirect_overall_rows(sem_K, sem_direct)
-                    for kind_, rows_ in (("indirect", ind_), ("overall", ov_)):
+                    for kind_, rows_ in (("indirect_", ind_), ("overall_", ov_)):
                         for kk, tr in enumerate(model.lhsVec):
                             nz_ = rows_[kk] != 0.0
-                            sem_writers[kind_][kk].append(u_idx[nz_], rows_[kk][nz_])
+                            bin_writers[kind_][kk].append(u_idx[nz_], rows_[kk][nz_])
                             if write_marker_samples:
-                                a = np.zeros(p, dtype=ftype)
-                                a[u_idx] = rows_[kk]
-                                fh = files[f"{kind_}_marker_effects_{name}_{tr}"]
-                                a.tofile(fh, sep=",", format="%.9g")
-                                fh.write("\n")
+                                files.sparse_effects_row(f"{kind_}marker_effects_{name}_{tr}", u_idx, rows_[kk], p, ftype, "%.9g")
                 if outputEBV:
                     if X_out_host is not None:
                         ebvs = [(X_out_host @ engine.get_state(kk)[0].astype(np.float64)).astype(ftype) for kk in range(t)]
@@ -1570,39 +1512,14 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                         ebvs[kk] = e_.astype(ftype)
                     for kk in range(t):
                         ebv_run[kk].add(ebvs[kk], k)
-                    if heritability:                                        # output.jl:498-512
-                        E = np.stack(ebvs, axis=1).astype(np.float64)
-                        gv = np.atleast_2d(np.cov(E, rowvar=False))
-                        if t > 1 and Mi.G.constraint:
-                            gv = np.diag(np.diag(gv))
-                        vr = np.atleast_2d(np.asarray(vare, dtype=np.float64))
-                        h2 = np.diag(gv) / (np.diag(gv) + np.diag(vr))
-                        gv_samples.append(gv.ravel()); h2_samples.append(h2)
-                        files["genetic_variance"].write(",".join(repr(float(v)) for v in gv.ravel()) + "\n")
-                        files["heritability"].write(",".join(repr(float(v)) for v in h2) + "\n")
+                    if genvar is not None:                                  # output.jl:498-512 (the EBVs in the element type of the run)
+                        genvar.add(ebvs, np.diag(np.atleast_2d(np.asarray(vare, dtype=np.float64))), diagonal_only=t > 1 and Mi.G.constraint)
             iter_end.append(time.perf_counter())
             if it % printout_frequency == 0 and it > burnin:
-                print(f"\nPosterior means at iteration: {it}")
-                print(f"Residual variance: {np.round(run_vare.mean, 6)}")
-    finally:                                     # also on an exception inside the chain: give the BLAS its threads back, close the files
-        wall = time.time() - t0
-        if _blas_limit is not None:
-            _blas_limit.restore_original_limits()
-        for fh in list(files.values()) + list(liab_files.values()):
-            fh.close()
-        for w_ in bin_writers + [w2_ for ws_ in sem_writers.values() for w2_ in ws_]:
-            w_.close()
-        if sem_open:
-            sem_file.close()
-            if sys.exc_info()[0] is not None:                           # an exception inside the chain: the session goes with the files
-                engine.sem_end()
-        if ann_open and sys.exc_info()[0] is not None:                  # an exception inside the chain: the session goes with the files
-            engine.annot_end()
-
+                print_posterior_means(it, run_vare.mean)
+    wall = time.time() - t0
 
     # ---- results (output.jl:108-212)
-    out = {}
-    rows_lp = []
     if lp_device:
         lp_mean, lp_mean2 = engine.locpar_get_means() if sum(q) else (np.zeros(0), np.zeros(0))
         lp_sd = np.sqrt(np.abs(lp_mean2 - lp_mean ** 2))
@@ -1611,39 +1528,24 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             engine.mtmiss_end()
     else:
         lp_mean, lp_sd = run_sol.mean, run_sol.sd()
-    for k in range(t):
-        for i, (tr, eff, lev) in enumerate(labels[k]):
-            rows_lp.append((tr, eff, lev, lp_mean[off[k] + i], lp_sd[off[k] + i]))
-    out["location parameters"] = pd.DataFrame(rows_lp, columns=["Trait", "Effect", "Level", "Estimate", "SD"])
-    cov = rnames if t > 1 else [model.lhsVec[0]]
-    out["residual variance"] = pd.DataFrame({"Covariance": cov, "Estimate": np.atleast_1d(run_vare.mean).ravel(),
-                                             "SD": np.atleast_1d(run_vare.sd()).ravel()})
+    out = {"location parameters": location_table(labels, off, lp_mean, lp_sd), "residual variance": covariance_table(cov, run_vare)}
     for g_, re_ in enumerate(rnd):
-        kk = len(re_.term_array)
-        out["polygenic effects covariance matrix" if re_.randomType == "A" else rnd_keys[g_]] = pd.DataFrame({"Covariance": [f"{re_.term_array[a]}_{re_.term_array[b]}" for a in range(kk) for b in range(kk)],
-                                          "Estimate": run_rnd[g_].mean, "SD": run_rnd[g_].sd()})
-    frames = []
-    for k, tr in enumerate(model.lhsVec):
-        ma, ma2, md = engine.posterior(k)
-        sd = np.sqrt(np.abs(ma2.astype(np.float64) - ma.astype(np.float64) ** 2))
-        frames.append(pd.DataFrame({"Trait": tr, "Marker_ID": Mi.markerID, "Estimate": ma, "SD": sd, "Model_Frequency": md}))
-    out[f"marker effects {name}"] = pd.concat(frames, ignore_index=True)
+        out["polygenic effects covariance matrix" if re_.randomType == "A" else rnd_keys[g_]] = covariance_table(rnd_cov[g_], run_rnd[g_])
+    # run_chain: the SD from the moments cast to Float64 (the engine returns them in the element type of the run)
+    out[f"marker effects {name}"] = marker_effects_table([(tr, Mi.markerID) + tuple(engine.posterior(k)) for k, tr in enumerate(model.lhsVec)],
+                                                         sd_in_double=True)
     if sem_open:                                                         # generate_marker_effect (SEM.jl:318-368; JWAS.jl:496-507)
-        out[f"marker effects {name}"].to_csv(os.path.join(output_folder, f"direct_marker_effects_{name}.txt"), index=False)
-        for kind_ in ("indirect", "overall"):
-            frames = []
-            for k, tr in enumerate(model.lhsVec):
-                m_, m2_, fr_ = engine.sem_get_effects(kind_, k)
-                frames.append(pd.DataFrame({"Trait": tr, "Marker_ID": Mi.markerID, "Estimate": m_, "SD": np.sqrt(np.abs(m2_ - m_ ** 2)),
-                                            "Model_Frequency": fr_}))
-            out[f"{kind_} marker effects {name}"] = pd.concat(frames, ignore_index=True)
+        write_tables({f"direct marker effects {name}": out[f"marker effects {name}"]}, output_folder)
+        for kind_ in ("indirect", "overall"):                            # (the session's moments are doubles)
+            out[f"{kind_} marker effects {name}"] = marker_effects_table(
+                [(tr, Mi.markerID) + tuple(engine.sem_get_effects(kind_, k)) for k, tr in enumerate(model.lhsVec)], sd_in_double=False)
+        import pandas as pd
         lam_sd = run_lam.sd()
         out["structure coefficients"] = pd.DataFrame({"Trait": [model.lhsVec[i] for i, _ in sem_edges], "Parent": [model.lhsVec[j] for _, j in sem_edges],
                                                       "Estimate": [run_lam.mean[i, j] for i, j in sem_edges], "SD": [lam_sd[i, j] for i, j in sem_edges]})
         engine.sem_end()
     if run_varg is not None:
-        out[f"marker effects variance {name}"] = pd.DataFrame({"Covariance": cov, "Estimate": np.atleast_1d(run_varg.mean).ravel(),
-                                                               "SD": np.atleast_1d(run_varg.sd()).ravel()})
+        out[f"marker effects variance {name}"] = covariance_table(cov, run_varg)
     if ann_open:
         if ann.nsteps == 1:
             run_pi.mean, run_pi.mean2 = engine.annot_means()
@@ -1651,29 +1553,20 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     if run_pi is not None:
         if mega:
             lab = list(model.lhsVec)
-        elif t > 1:
-            lab = ["".join(str((s >> k) & 1) for k in range(t)) for s in range(1 << t)]
-        elif method == "BayesR":
-            lab = ["class1", "class2", "class3", "class4"]
-        elif np.size(run_pi.mean) > 1:
+        elif t == 1 and method != "BayesR" and np.size(run_pi.mean) > 1:
             lab = list(Mi.markerID)                                      # annotated BayesC: marker-level pi
         else:
-            lab = ["π"]
-        out[f"pi_{name}"] = pd.DataFrame({"π": lab, "Estimate": run_pi.mean, "SD": run_pi.sd()})
+            lab = pi_labels(t, method)
+        out[f"pi_{name}"] = pi_table(run_pi, lab)
     if ann is not False:
         out[f"annotation coefficients {name}"] = A_.coefficients_table(ann, method)
     if run_scale is not None:                                            # output.jl:148-150
-        out[f"ScaleEffectVar{name}"] = pd.DataFrame({"Covariance": [model.lhsVec[0]], "Estimate": run_scale.mean, "SD": run_scale.sd()})
+        out[f"ScaleEffectVar{name}"] = covariance_table([model.lhsVec[0]], run_scale)
     if outputEBV:
-        for k, tr in enumerate(model.lhsVec):
-            m = ebv_run[k].mean
-            out[f"EBV_{tr}"] = pd.DataFrame({"ID": out_ids, "EBV": m, "PEV": np.abs(ebv_run[k].mean2 - m ** 2)})
-    if heritability and gv_samples:                                      # output.jl:196-209 (mean and std of the samples)
-        for key, samples, names in (("genetic_variance", np.array(gv_samples), cov), ("heritability", np.array(h2_samples), list(model.lhsVec))):
-            out[key] = pd.DataFrame({"Covariance": names, "Estimate": samples.mean(axis=0),
-                                     "SD": samples.std(axis=0, ddof=1) if len(samples) > 1 else np.full(samples.shape[1], np.nan)})
-    for key, tab in out.items():                                         # JWAS.jl:480-482
-        tab.to_csv(os.path.join(output_folder, key.replace(" ", "_") + ".txt"), index=False)
+        out.update(ebv_tables(model.lhsVec, out_ids, ebv_run))
+    if genvar is not None:                                               # output.jl:196-209 (mean and std of the samples)
+        out.update(genvar.tables())
+    write_tables(out, output_folder)
     out["_timing"] = {"wall_s": wall, "device_sweep_ms_total": t_sweep, "iterations": chain_length,
                       "block_size": block_size, "n": n, "p": p, "iteration_end_s": iter_end,
                       "block_starts": (np.asarray(engine.block_starts(), dtype=np.int64) + 1).tolist() if fast_blocks is not False else None,

@@ -20,13 +20,15 @@ Speed (scripts/mega_bench.py, one MI355X, 20 000 x 100 000 Float32, pi = 0.95, b
 than that path below about 7 traits (0.65 of its speed at 4; interpolated between the measured 4 and 8, the two meet between 6 and
 7 traits), 1.17 times as fast at 8 and 6.0 times at 64.  A model of 5 traits therefore pays about a quarter more per sweep here
 than 5/4 of a four-trait sweep on the old kernel; it gets one run and one set of outputs instead of two."""
-import os
 import time
 
 import numpy as np
 
 from ._lib import MEGA_MAX_BLOCK, MEGA_MAX_TRAITS
-from .mcmc import _Running, _design, _gibbs
+from .chain_output import (GeneticVarianceSamples, Running, SampleFiles, covariance_table, ebv_tables, location_table,
+                           marker_effects_table, pi_table, print_posterior_means, resolve_output_ids, term_sample_columns, write_id_files,
+                           write_tables)
+from .mcmc import _design, _gibbs
 
 MEGA_METHODS = ("mega_begin", "mega_set_missing", "mega_set_residual", "mega_get_residual", "mega_get_state", "mega_impute", "mega_sweep",
                 "mega_accumulate", "mega_posterior", "mega_mul_alpha", "mega_end")
@@ -145,8 +147,6 @@ def constraint_priors(model, phenovar, ftype=np.float32):
 def run_megatrait(model, df, *, chain_length, burnin, output_samples_frequency, seed, double_precision, outputEBV, output_heritability,
                   output_folder, printout_frequency, missing_phenotypes=True, device=0, block_size=None, engine=None, printout_model_info=True,
                   output_samples_for_all_parameters=False):
-    import pandas as pd
-    from .samples import MarkerSampleWriter
     Mi = model.M[0]
     t = model.nModels
     ftype = np.float64 if double_precision else np.float32
@@ -178,21 +178,12 @@ def run_megatrait(model, df, *, chain_length, burnin, output_samples_frequency, 
     X = np.asfortranarray(np.asarray(Mi.genotypes)[rows, :].astype(ftype))
     n, p = X.shape
     out_ids, out_rows, out_same = None, None, True
-    if outputEBV:                                                        # check_outputID, input_data_validation.jl:143-196
-        want = list(Mi.obsID) if getattr(model, "output_ID", False) is False else list(model.output_ID)
-        if not all(i in geno_index for i in want):
-            print("Testing individuals are not a subset of genotyped individuals (complete genomic data,non-single-step). "
-                  "Only output EBV for tesing individuals with genotypes.")
-            want = [i for i in want if i in geno_index]
-        out_ids = want
-        out_same = out_ids == list(ph[idcol])
+    if outputEBV:
+        out_ids, out_same = resolve_output_ids(model, Mi.obsID, ph[idcol])
         if not out_same:
             out_rows = np.array([geno_index[i] for i in out_ids], dtype=np.int64)
     Mi.output_rows = out_rows if (outputEBV and not out_same) else rows
-    with open(os.path.join(output_folder, "IDs_for_individuals_with_phenotypes.txt"), "w") as fh:
-        fh.write("\n".join(ph[idcol]) + "\n")
-    with open(os.path.join(output_folder, "IDs_for_individuals_with_genotypes.txt"), "w") as fh:
-        fh.write("\n".join(Mi.obsID) + "\n")
+    write_id_files(output_folder, ph[idcol], Mi.obsID)
     Y = np.stack([ph[tr].to_numpy(dtype=np.float64) for tr in traits])  # t x n
     observed = np.isfinite(Y)
     has_missing = not observed.all()
@@ -229,40 +220,30 @@ def run_megatrait(model, df, *, chain_length, burnin, output_samples_frequency, 
     engine.mega_set_residual(Y)                                          # ycorr = y: every starting value is zero
 
     # ---- accumulators and sample files (output.jl:320-437)
-    run_sol, run_vare, run_varg = _Running(sol), _Running(np.diag(vare)), _Running(np.diag(Gval))
-    run_pi = _Running(pi_t) if Mi.estimatePi else None
-    ebv_run = [_Running(np.zeros(len(out_ids))) for _ in range(t)] if outputEBV else None
-    files = {}
-
-    def _open(key, header):
-        fh = open(os.path.join(output_folder, f"MCMC_samples_{key}.txt"), "w")
-        fh.write(",".join(header) + "\n")
-        files[key] = fh
-
+    # run_megatrait: the variances are vectors here; the accumulators, files and tables hold them as the diagonal of a t x t matrix
+    run_sol, run_vare, run_varg = Running(sol), Running(np.diag(vare)), Running(np.diag(Gval))
+    run_pi = Running(pi_t) if Mi.estimatePi else None
+    ebv_run = [Running(np.zeros(len(out_ids))) for _ in range(t)] if outputEBV else None
     rnames = [f"{a}_{b}" for a in traits for b in traits]
-    _open("residual_variance", rnames)
-    _open(f"marker_effects_variances_{name}", rnames)
-    if Mi.estimatePi:
-        _open(f"pi_{name}", [f"pi{i + 1}" for i in range(t)])
-    heritability = bool(outputEBV and output_heritability)               # output.jl:358-362,426-432
-    h2_samples, gv_samples = [], []
-    if heritability:
-        _open("genetic_variance", rnames)
-        _open("heritability", traits)
-    term_cols = {}                                                       # outputMCMCsamples (output.jl:76-95,443-460)
-    for tr, trm in getattr(model, "outputSamplesVec", []):
-        k = traits.index(tr)
-        cols = [off[k] + i for i, (_, eff, _) in enumerate(labels[k]) if eff == trm]
-        if cols:
-            term_cols[f"{tr}.{trm}"] = cols
-            _open(f"{tr}.{trm}", [f"{tr}:{trm}:{labels[k][c - off[k]][2]}" for c in cols])
+    term_cols = term_sample_columns(model, labels, off)
     write_marker_samples = output_samples_for_all_parameters or p <= 20000
-    if write_marker_samples:
-        for tr in traits:
-            _open(f"marker_effects_{name}_{tr}", Mi.markerID)
-    bin_writers = [MarkerSampleWriter(os.path.join(output_folder, f"MCMC_samples_marker_effects_{name}_{tr}.bin"), Mi.markerID) for tr in traits]
+    fmt = "%.17g" if double_precision else "%.9g"                        # run_megatrait: the marker rows follow the precision of the run
+    genvar = None
+    files = SampleFiles(output_folder)
     t_sweep, t0 = 0.0, time.time()
-    try:
+    with files:
+        files.open("residual_variance", rnames)
+        files.open(f"marker_effects_variances_{name}", rnames)
+        if Mi.estimatePi:
+            files.open(f"pi_{name}", [f"pi{i + 1}" for i in range(t)])
+        if outputEBV and output_heritability:                            # output.jl:358-362,426-432
+            genvar = GeneticVarianceSamples(files, rnames, traits)
+        for key_, (_, header) in term_cols.items():
+            files.open(key_, header)
+        if write_marker_samples:
+            for tr in traits:
+                files.open(f"marker_effects_{name}_{tr}", Mi.markerID)
+        bin_writers = [files.marker_writer(f"marker_effects_{name}_{tr}", Mi.markerID) for tr in traits]
         for it in range(1, chain_length + 1):
             if has_missing:                                              # 1. missing residuals (DEVICE)
                 engine.mega_impute(iteration=it, seed=seed_int, vare=vare)
@@ -290,67 +271,43 @@ def run_megatrait(model, df, *, chain_length, burnin, output_samples_frequency, 
                 run_varg.add(np.diag(Gval), ks)
                 if run_pi is not None:
                     run_pi.add(pi_t, ks)
-                    files[f"pi_{name}"].write(",".join(repr(float(v)) for v in pi_t) + "\n")
+                    files.row(f"pi_{name}", pi_t)
                 engine.mega_accumulate(ks)
-                for key_, cols in term_cols.items():
-                    files[key_].write(",".join(repr(float(sol[c])) for c in cols) + "\n")
-                files["residual_variance"].write(",".join(repr(float(v)) for v in np.diag(vare).ravel()) + "\n")
-                files[f"marker_effects_variances_{name}"].write(",".join(repr(float(v)) for v in np.diag(Gval).ravel()) + "\n")
+                for key_, (cols, _) in term_cols.items():
+                    files.row(key_, sol[cols])
+                files.row("residual_variance", np.diag(vare).ravel())
+                files.row(f"marker_effects_variances_{name}", np.diag(Gval).ravel())
                 alpha = engine.mega_get_state()[0]
                 for k, tr in enumerate(traits):
                     a = alpha[k].astype(ftype)
                     si = np.flatnonzero(a).astype(np.int32)
                     bin_writers[k].append(si, a[si])
                     if write_marker_samples:
-                        fh = files[f"marker_effects_{name}_{tr}"]
-                        a.tofile(fh, sep=",", format="%.17g" if double_precision else "%.9g")
-                        fh.write("\n")
+                        files.effects_row(f"marker_effects_{name}_{tr}", a, fmt)
                 if outputEBV:                                            # getEBV, output.jl:281-306
                     ebvs = [np.asarray(engine.mega_mul_alpha(k, output_rows=not out_same), dtype=np.float64) for k in range(t)]
                     for k in range(t):
                         ebv_run[k].add(ebvs[k], ks)
-                    if heritability:                                     # output.jl:498-512 (constraint: the diagonal)
-                        gv = np.diag(np.diag(np.atleast_2d(np.cov(np.stack(ebvs, axis=1), rowvar=False))))
-                        h2 = np.diag(gv) / (np.diag(gv) + vare)
-                        gv_samples.append(gv.ravel())
-                        h2_samples.append(h2)
-                        files["genetic_variance"].write(",".join(repr(float(v)) for v in gv.ravel()) + "\n")
-                        files["heritability"].write(",".join(repr(float(v)) for v in h2) + "\n")
+                    if genvar is not None:                               # output.jl:498-512 (constraint: the diagonal)
+                        genvar.add(ebvs, vare, diagonal_only=True)
             if it % printout_frequency == 0 and it > burnin:
-                print(f"\nPosterior means at iteration: {it}")
-                print(f"Residual variance: {np.round(np.diag(run_vare.mean), 6)}")
-    finally:
-        wall = time.time() - t0
-        for fh in files.values():
-            fh.close()
-        for w_ in bin_writers:
-            w_.close()
+                print_posterior_means(it, np.diag(run_vare.mean))
+    wall = time.time() - t0
 
     # ---- results (output.jl:108-212)
-    out = {}
-    sd_sol = run_sol.sd()
-    out["location parameters"] = pd.DataFrame([(tr, eff, lev, run_sol.mean[off[k] + i], sd_sol[off[k] + i])
-                                               for k in range(t) for i, (tr, eff, lev) in enumerate(labels[k])],
-                                              columns=["Trait", "Effect", "Level", "Estimate", "SD"])
-    out["residual variance"] = pd.DataFrame({"Covariance": rnames, "Estimate": run_vare.mean.ravel(), "SD": run_vare.sd().ravel()})
-    frames = []
-    for k, tr in enumerate(traits):
-        ma, ma2, md = engine.mega_posterior(k)
-        frames.append(pd.DataFrame({"Trait": tr, "Marker_ID": Mi.markerID, "Estimate": ma, "SD": np.sqrt(np.abs(ma2 - ma ** 2)), "Model_Frequency": md}))
-    out[f"marker effects {name}"] = pd.concat(frames, ignore_index=True)
-    out[f"marker effects variance {name}"] = pd.DataFrame({"Covariance": rnames, "Estimate": run_varg.mean.ravel(), "SD": run_varg.sd().ravel()})
+    out = {"location parameters": location_table(labels, off, run_sol.mean, run_sol.sd()),
+           "residual variance": covariance_table(rnames, run_vare)}
+    # run_megatrait: the SD from the moments as the session returns them (doubles)
+    out[f"marker effects {name}"] = marker_effects_table([(tr, Mi.markerID) + tuple(engine.mega_posterior(k)) for k, tr in enumerate(traits)],
+                                                         sd_in_double=False)
+    out[f"marker effects variance {name}"] = covariance_table(rnames, run_varg)
     if run_pi is not None:
-        out[f"pi_{name}"] = pd.DataFrame({"π": traits, "Estimate": run_pi.mean, "SD": run_pi.sd()})
+        out[f"pi_{name}"] = pi_table(run_pi, traits)
     if outputEBV:
-        for k, tr in enumerate(traits):
-            m = ebv_run[k].mean
-            out[f"EBV_{tr}"] = pd.DataFrame({"ID": out_ids, "EBV": m, "PEV": np.abs(ebv_run[k].mean2 - m ** 2)})
-    if heritability and gv_samples:                                      # output.jl:196-209 (mean and std of the samples)
-        for key, samples, names in (("genetic_variance", np.array(gv_samples), rnames), ("heritability", np.array(h2_samples), traits)):
-            out[key] = pd.DataFrame({"Covariance": names, "Estimate": samples.mean(axis=0),
-                                     "SD": samples.std(axis=0, ddof=1) if len(samples) > 1 else np.full(samples.shape[1], np.nan)})
-    for key, tab in out.items():                                         # JWAS.jl:480-482
-        tab.to_csv(os.path.join(output_folder, key.replace(" ", "_") + ".txt"), index=False)
+        out.update(ebv_tables(traits, out_ids, ebv_run))
+    if genvar is not None:
+        out.update(genvar.tables())
+    write_tables(out, output_folder)
     out["_timing"] = {"wall_s": wall, "device_sweep_ms_total": t_sweep, "iterations": chain_length, "block_size": bs, "n": n, "p": p, "ntraits": t}
     engine.mega_end()
     if own_engine:

@@ -19,12 +19,14 @@ block start at p1 in every bit; without it category 2 would reuse category 1's d
 Block size per category: block_size if given, else the non-adaptive default run_chain computes for that p and storage.  The adaptive
 512 / 1024 switching, grouped launches, ping-pong pairs and the section solve stay off here (a performance follow-up).  Everything outside
 the scope below raises NotImplementedError in validate(), before any device work."""
-import os
 import time
 
 import numpy as np
 
-from .mcmc import _Running, _design, _gibbs, genetic2marker, host_location_step
+from .chain_output import (GeneticVarianceSamples, Running, SampleFiles, covariance_table, ebv_tables, host_blas_limit, location_table,
+                           marker_effects_table, pi_labels, pi_table, print_posterior_means, resolve_output_ids, sparse_effects,
+                           term_sample_columns, write_id_files, write_tables)
+from .mcmc import _design, _gibbs, genetic2marker, host_location_step
 
 MAX_TRAITS = 4
 
@@ -278,7 +280,6 @@ def run_multigeno(model, df, *, chain_length, burnin, output_samples_frequency, 
                   double_precision=False, outputEBV=True, output_heritability=True, output_folder, printout_frequency,
                   memory_guard="error", memory_guard_ratio=0.80, device=0, block_size=None, gram_mode="mfma", engines=None,
                   printout_model_info=True, output_samples_for_all_parameters=False):
-    import pandas as pd
     M = model.M
     C, t = len(M), model.nModels
     ftype = np.float64 if double_precision else np.float32
@@ -315,15 +316,8 @@ def run_multigeno(model, df, *, chain_length, burnin, output_samples_frequency, 
     n = len(rows)
     identity = n == len(obsID) and np.array_equal(rows, np.arange(n))
     out_ids, out_rows, out_same = None, None, True
-    if outputEBV:                                                        # check_outputID (input_data_validation.jl:143-196)
-        want = obsID if getattr(model, "output_ID", False) is False else list(model.output_ID)
-        known = set(obsID)
-        if not all(i in known for i in want):
-            print("Testing individuals are not a subset of genotyped individuals (complete genomic data,non-single-step). "
-                  "Only output EBV for tesing individuals with genotypes.")
-            want = [i for i in want if i in known]
-        out_ids = want
-        out_same = out_ids == list(ph[idcol])
+    if outputEBV:
+        out_ids, out_same = resolve_output_ids(model, obsID, ph[idcol])
         if not out_same:
             if any_stream:
                 raise NotImplementedError("storage=:stream reports EBVs for the genotyped individuals in file order "
@@ -333,10 +327,7 @@ def run_multigeno(model, df, *, chain_length, burnin, output_samples_frequency, 
     for Mi in M:
         if getattr(Mi, "storage_mode", "dense") == "dense":
             Mi.output_rows = out_rows if (outputEBV and not out_same) else rows
-    with open(os.path.join(output_folder, "IDs_for_individuals_with_phenotypes.txt"), "w") as fh:
-        fh.write("\n".join(ph[idcol]) + "\n")
-    with open(os.path.join(output_folder, "IDs_for_individuals_with_genotypes.txt"), "w") as fh:
-        fh.write("\n".join(obsID) + "\n")
+    write_id_files(output_folder, ph[idcol], obsID)
     Y = np.stack([ph[tr].to_numpy(dtype=ftype) for tr in model.lhsVec])       # t x n
     phenovar = np.array([np.var(Y[k].astype(np.float64), ddof=1) for k in range(t)])
     invw = None
@@ -420,58 +411,35 @@ def run_multigeno(model, df, *, chain_length, burnin, output_samples_frequency, 
         vare = ftype(R.val) if t == 1 else np.asarray(R.val, dtype=ftype)
 
         # ---- accumulators and sample files (output.jl:320-437)
-        run_sol, run_vare = _Running(sol), _Running(vare)
-        files, writers = {}, []
-
-        def _open(key, header):
-            fh = open(os.path.join(output_folder, f"MCMC_samples_{key}.txt"), "w")
-            fh.write(",".join(header) + "\n")
-            files[key] = fh
-
-        rnames = [f"{a}_{b}" for a in model.lhsVec for b in model.lhsVec]
-        _open("residual_variance", rnames if t > 1 else [model.lhsVec[0]])
-        from .samples import MarkerSampleWriter
-        for c in cats:
-            Mi = c.Mi
-            c.run_varg = _Running(c.Gval) if not c.pervar else None
-            c.run_pi = _Running(np.atleast_1d(np.asarray(c.pi, dtype=np.float64))) if Mi.estimatePi else None
-            c.run_scale = _Running(np.atleast_1d(np.float64(Mi.G.scale))) if (Mi.G.estimate_scale and t == 1) else None
-            if not c.pervar:
-                _open(f"marker_effects_variances_{c.name}", rnames if t > 1 else ["1"])
-            if Mi.estimatePi:
-                npi = np.size(c.pi)
-                _open(f"pi_{c.name}", [f"pi{i + 1}" for i in range(npi)] if npi > 1 else ["pi"])
-            c.text = output_samples_for_all_parameters or c.p <= 20000
-            if c.text:
-                for tr in model.lhsVec:
-                    _open(f"marker_effects_{c.name}_{tr}", Mi.markerID)
-            c.writers = [MarkerSampleWriter(os.path.join(output_folder, f"MCMC_samples_marker_effects_{c.name}_{tr}.bin"), Mi.markerID)
-                         for tr in model.lhsVec]
-            writers += c.writers
-        heritability = bool(outputEBV and output_heritability)
-        h2_samples, gv_samples = [], []
-        if heritability:
-            _open("genetic_variance", rnames if t > 1 else [model.lhsVec[0]])
-            _open("heritability", list(model.lhsVec))
-        term_cols = {}                                                   # outputMCMCsamples (output.jl:76-95,443-460)
-        for tr, trm in getattr(model, "outputSamplesVec", []):
-            k = model.lhsVec.index(tr)
-            cols = [off[k] + i for i, (_, eff, _) in enumerate(labels[k]) if eff == trm]
-            if cols:
-                term_cols[f"{tr}.{trm}"] = cols
-                _open(f"{tr}.{trm}", [f"{tr}:{trm}:{labels[k][c_ - off[k]][2]}" for c_ in cols])
-        ebv_run = [_Running(np.zeros(len(out_ids))) for _ in range(t)] if outputEBV else None
+        run_sol, run_vare = Running(sol), Running(vare)
+        ebv_run = [Running(np.zeros(len(out_ids))) for _ in range(t)] if outputEBV else None
+        cov = [f"{a}_{b}" for a in model.lhsVec for b in model.lhsVec] if t > 1 else [model.lhsVec[0]]
+        term_cols = term_sample_columns(model, labels, off)
+        genvar = None
+        files = SampleFiles(output_folder)
         t_sweep, t0 = 0.0, time.time()
-        _blas_limit = None
-        try:
-            nthr = int(os.environ.get("JWAS_HOST_BLAS_THREADS", "1"))
-            if nthr > 0:
-                from threadpoolctl import threadpool_limits
-                _blas_limit = threadpool_limits(limits=nthr, user_api="blas")
-        except Exception:
-            _blas_limit = None
         # ================================ the chain =================================================
-        try:
+        with host_blas_limit(), files:
+            files.open("residual_variance", cov)
+            for c in cats:
+                Mi = c.Mi
+                c.run_varg = Running(c.Gval) if not c.pervar else None
+                c.run_pi = Running(np.atleast_1d(np.asarray(c.pi, dtype=np.float64))) if Mi.estimatePi else None
+                c.run_scale = Running(np.atleast_1d(np.float64(Mi.G.scale))) if (Mi.G.estimate_scale and t == 1) else None
+                if not c.pervar:
+                    files.open(f"marker_effects_variances_{c.name}", cov if t > 1 else ["1"])
+                if Mi.estimatePi:
+                    npi = np.size(c.pi)
+                    files.open(f"pi_{c.name}", [f"pi{i + 1}" for i in range(npi)] if npi > 1 else ["pi"])
+                c.text = output_samples_for_all_parameters or c.p <= 20000
+                if c.text:
+                    for tr in model.lhsVec:
+                        files.open(f"marker_effects_{c.name}_{tr}", Mi.markerID)
+                c.writers = [files.marker_writer(f"marker_effects_{c.name}_{tr}", Mi.markerID) for tr in model.lhsVec]
+            if outputEBV and output_heritability:
+                genvar = GeneticVarianceSamples(files, cov, list(model.lhsVec))
+            for key_, (_, header) in term_cols.items():
+                files.open(key_, header)
             for it in range(1, chain_length + 1):
                 # 1. location parameters (MCMC_BayesianAlphabet.jl:196-220), from the residual where it is
                 if sum(q):
@@ -505,34 +473,26 @@ def run_multigeno(model, df, *, chain_length, burnin, output_samples_frequency, 
                     k = (it - burnin) / output_samples_frequency
                     run_sol.add(sol, k)
                     run_vare.add(vare, k)
-                    for key_, cols in term_cols.items():
-                        files[key_].write(",".join(repr(float(sol[c_])) for c_ in cols) + "\n")
-                    files["residual_variance"].write(",".join(repr(float(v)) for v in np.atleast_1d(vare).ravel()) + "\n")
+                    for key_, (cols, _) in term_cols.items():
+                        files.row(key_, sol[cols])
+                    files.row("residual_variance", np.atleast_1d(vare).ravel())
                     ebvs = [np.zeros(len(out_ids)) for _ in range(t)] if outputEBV else None
                     for i, c in enumerate(cats):
                         eng = c.engine
                         eng.accumulate(k)
                         if c.run_varg is not None:
                             c.run_varg.add(c.Gval, k)
-                            files[f"marker_effects_variances_{c.name}"].write(",".join(repr(float(v)) for v in np.atleast_1d(c.Gval).ravel()) + "\n")
+                            files.row(f"marker_effects_variances_{c.name}", np.atleast_1d(c.Gval).ravel())
                         if c.run_pi is not None:
                             c.run_pi.add(np.atleast_1d(c.pi), k)
-                            files[f"pi_{c.name}"].write(",".join(repr(float(v)) for v in np.atleast_1d(c.pi)) + "\n")
+                            files.row(f"pi_{c.name}", np.atleast_1d(c.pi))
                         if c.run_scale is not None:
                             c.run_scale.add(np.atleast_1d(np.float64(c.Mi.G.scale)), k)
                         for kk, tr in enumerate(model.lhsVec):
-                            if hasattr(eng, "alpha_sparse"):
-                                si, sv = eng.alpha_sparse(kk)
-                            else:
-                                a_ = eng.get_state(kk)[0]
-                                si = np.flatnonzero(a_).astype(np.int32); sv = a_[si]
+                            si, sv = sparse_effects(eng, kk)
                             c.writers[kk].append(si, sv)
-                            if c.text:
-                                a = np.zeros(c.p, dtype=ftype)
-                                a[si] = sv
-                                fh = files[f"marker_effects_{c.name}_{tr}"]
-                                a.tofile(fh, sep=",", format="%.9g")
-                                fh.write("\n")
+                            if c.text:                                   # run_multigeno: nine digits also under double_precision
+                                files.sparse_effects_row(f"marker_effects_{c.name}_{tr}", si, sv, c.p, ftype, "%.9g")
                             if outputEBV:                                # getEBV: sum over the categories (output.jl:300-304), in double
                                 if X_out_host[i] is not None:
                                     e_ = X_out_host[i] @ eng.get_state(kk)[0].astype(np.float64)
@@ -542,64 +502,30 @@ def run_multigeno(model, df, *, chain_length, burnin, output_samples_frequency, 
                     if outputEBV:
                         for kk in range(t):
                             ebv_run[kk].add(ebvs[kk], k)
-                        if heritability:                                 # output.jl:498-512, from the total
-                            gv = np.atleast_2d(np.cov(np.stack(ebvs, axis=1), rowvar=False))
-                            vr = np.atleast_2d(np.asarray(vare, dtype=np.float64))
-                            h2 = np.diag(gv) / (np.diag(gv) + np.diag(vr))
-                            gv_samples.append(gv.ravel()); h2_samples.append(h2)
-                            files["genetic_variance"].write(",".join(repr(float(v)) for v in gv.ravel()) + "\n")
-                            files["heritability"].write(",".join(repr(float(v)) for v in h2) + "\n")
+                        if genvar is not None:                           # output.jl:498-512, from the total
+                            genvar.add(ebvs, np.diag(np.atleast_2d(np.asarray(vare, dtype=np.float64))))
                 if it % printout_frequency == 0 and it > burnin:
-                    print(f"\nPosterior means at iteration: {it}")
-                    print(f"Residual variance: {np.round(run_vare.mean, 6)}")
-        finally:
-            wall = time.time() - t0
-            if _blas_limit is not None:
-                _blas_limit.restore_original_limits()
-            for fh in files.values():
-                fh.close()
-            for w_ in writers:
-                w_.close()
+                    print_posterior_means(it, run_vare.mean)
+        wall = time.time() - t0
 
         # ---- results (output.jl:108-212)
-        out = {}
-        lp_sd = run_sol.sd()
-        out["location parameters"] = pd.DataFrame([(tr, eff, lev, run_sol.mean[off[k] + i], lp_sd[off[k] + i])
-                                                   for k in range(t) for i, (tr, eff, lev) in enumerate(labels[k])],
-                                                  columns=["Trait", "Effect", "Level", "Estimate", "SD"])
-        cov = rnames if t > 1 else [model.lhsVec[0]]
-        out["residual variance"] = pd.DataFrame({"Covariance": cov, "Estimate": np.atleast_1d(run_vare.mean).ravel(),
-                                                 "SD": np.atleast_1d(run_vare.sd()).ravel()})
+        out = {"location parameters": location_table(labels, off, run_sol.mean, run_sol.sd()),
+               "residual variance": covariance_table(cov, run_vare)}
         for c in cats:
-            frames = []
-            for k, tr in enumerate(model.lhsVec):
-                ma, ma2, md = c.engine.posterior(k)
-                sd = np.sqrt(np.abs(ma2.astype(np.float64) - ma.astype(np.float64) ** 2))
-                frames.append(pd.DataFrame({"Trait": tr, "Marker_ID": c.Mi.markerID, "Estimate": ma, "SD": sd, "Model_Frequency": md}))
-            out[f"marker effects {c.name}"] = pd.concat(frames, ignore_index=True)
+            # run_multigeno: the SD from the moments cast to Float64 (as run_chain)
+            out[f"marker effects {c.name}"] = marker_effects_table([(tr, c.Mi.markerID) + tuple(c.engine.posterior(k)) for k, tr in enumerate(model.lhsVec)],
+                                                                   sd_in_double=True)
             if c.run_varg is not None:
-                out[f"marker effects variance {c.name}"] = pd.DataFrame({"Covariance": cov, "Estimate": np.atleast_1d(c.run_varg.mean).ravel(),
-                                                                         "SD": np.atleast_1d(c.run_varg.sd()).ravel()})
+                out[f"marker effects variance {c.name}"] = covariance_table(cov, c.run_varg)
             if c.run_pi is not None:
-                if t > 1:
-                    lab = ["".join(str((s >> k) & 1) for k in range(t)) for s in range(1 << t)]
-                elif c.method == "BayesR":
-                    lab = ["class1", "class2", "class3", "class4"]
-                else:
-                    lab = ["π"]
-                out[f"pi_{c.name}"] = pd.DataFrame({"π": lab, "Estimate": c.run_pi.mean, "SD": c.run_pi.sd()})
+                out[f"pi_{c.name}"] = pi_table(c.run_pi, pi_labels(t, c.method))
             if c.run_scale is not None:
-                out[f"ScaleEffectVar{c.name}"] = pd.DataFrame({"Covariance": [model.lhsVec[0]], "Estimate": c.run_scale.mean, "SD": c.run_scale.sd()})
+                out[f"ScaleEffectVar{c.name}"] = covariance_table([model.lhsVec[0]], c.run_scale)
         if outputEBV:
-            for k, tr in enumerate(model.lhsVec):
-                m = ebv_run[k].mean
-                out[f"EBV_{tr}"] = pd.DataFrame({"ID": out_ids, "EBV": m, "PEV": np.abs(ebv_run[k].mean2 - m ** 2)})
-        if heritability and gv_samples:
-            for key, samples, names_ in (("genetic_variance", np.array(gv_samples), cov), ("heritability", np.array(h2_samples), list(model.lhsVec))):
-                out[key] = pd.DataFrame({"Covariance": names_, "Estimate": samples.mean(axis=0),
-                                         "SD": samples.std(axis=0, ddof=1) if len(samples) > 1 else np.full(samples.shape[1], np.nan)})
-        for key, tab in out.items():                                     # JWAS.jl:480-482
-            tab.to_csv(os.path.join(output_folder, key.replace(" ", "_") + ".txt"), index=False)
+            out.update(ebv_tables(model.lhsVec, out_ids, ebv_run))
+        if genvar is not None:
+            out.update(genvar.tables())
+        write_tables(out, output_folder)
         out["_timing"] = {"wall_s": wall, "device_sweep_ms_total": t_sweep, "iterations": chain_length,
                           "block_size": [c.block_size for c in cats], "marker_offset": [c.offset for c in cats],
                           "n": n, "p": [c.p for c in cats]}

@@ -14,13 +14,14 @@ Per iteration, the reference's order (MCMC_BayesianAlphabet_RRM.jl:109-236):
   6. every output_samples_frequency after burn-in: running means (device for the markers), the sample files  (:194-236)
 One trait, BayesC, estimatePi true or false, both precisions (the session's arithmetic is double in both; the genotypes are stored
 in the context's element type).  Everything else raises (validate)."""
-import os
 import time
 
 import numpy as np
 
 from ._lib import RRM_MAX_BLOCK, RRM_MAX_COEFF, RRM_MAX_TIMES, RRM_MIN_COEFF
-from .mcmc import _Running, _design, _gibbs, genetic2marker
+from .chain_output import (GeneticVarianceSamples, Running, SampleFiles, covariance_table, ebv_tables, location_table,
+                           marker_effects_table, pi_table, print_posterior_means, state_labels, write_tables)
+from .mcmc import _design, _gibbs, genetic2marker
 
 RRM_METHODS = ("rrm_begin", "rrm_set_residual", "rrm_get_residual", "rrm_sweep", "rrm_accumulate", "rrm_posterior", "rrm_mul_alpha", "rrm_end")
 
@@ -222,7 +223,7 @@ def run_rrm(model, df, Phi, *, chain_length, burnin, output_samples_frequency, s
 
     # ---- location parameters on the host (MCMC_BayesianAlphabet_RRM.jl:113-116)
     Xf, labels = _design(model, df, idcol)
-    Xf0, lab0 = Xf[0], labels[0]
+    Xf0 = Xf[0]
     q = Xf0.shape[1]
     sol = np.zeros(q)
     lhs = Xf0.T @ Xf0
@@ -245,32 +246,25 @@ def run_rrm(model, df, Phi, *, chain_length, burnin, output_samples_frequency, s
     engine.rrm_set_residual(W0)
 
     # ---- accumulators and sample files (output.jl:320-437)
-    run_sol, run_vare, run_varg = _Running(sol), _Running(vare), _Running(Gval)
-    run_pi = _Running(pi) if Mi.estimatePi else None
-    files = {}
-
-    def _open(key, header):
-        fh = open(os.path.join(output_folder, f"MCMC_samples_{key}.txt"), "w")
-        fh.write(",".join(header) + "\n")
-        files[key] = fh
-
+    run_sol, run_vare, run_varg = Running(sol), Running(vare), Running(Gval)
+    run_pi = Running(pi) if Mi.estimatePi else None
+    ebv_run = [Running(np.zeros(len(out_ids))) for _ in range(c)] if outputEBV else None
     cnames = [f"{a}_{b}" for a in coef_names for b in coef_names]
-    state_labels = ["".join(str((s >> k) & 1) for k in range(c)) for s in range(1 << c)]
-    _open("residual_variance", ["1"])
-    _open(f"marker_effects_variances_{name}", cnames)
-    _open(f"pi_{name}", state_labels)
-    for cn in coef_names:
-        _open(f"marker_effects_{name}_{cn}", Mi.markerID)
-    genvar = bool(outputEBV and output_heritability)
-    gv_samples = []
-    if outputEBV:
-        for cn in coef_names:
-            _open(f"EBV_{cn}", out_ids)
-        if genvar:
-            _open("genetic_variance", cnames)                            # (no heritability for RRM: output.jl:360-364)
-    ebv_run = [_Running(np.zeros(len(out_ids))) for _ in range(c)] if outputEBV else None
+    fmt = "%.17g" if double_precision else "%.9g"                        # run_rrm: the marker rows follow the precision of the run
+    genvar = None
+    files = SampleFiles(output_folder)
     t_sweep, t0 = 0.0, time.time()
-    try:
+    with files:
+        files.open("residual_variance", ["1"])                           # run_rrm: the column is named "1" (the other drivers: the trait)
+        files.open(f"marker_effects_variances_{name}", cnames)
+        files.open(f"pi_{name}", state_labels(c))
+        for cn in coef_names:
+            files.open(f"marker_effects_{name}_{cn}", Mi.markerID)
+        if outputEBV:
+            for cn in coef_names:
+                files.open(f"EBV_{cn}", out_ids)
+            if output_heritability:
+                genvar = GeneticVarianceSamples(files, cnames)           # (no heritability for RRM: output.jl:360-364)
         for it in range(1, chain_length + 1):
             if q:                                                        # 1. location parameters
                 W = engine.rrm_get_residual()
@@ -297,55 +291,37 @@ def run_rrm(model, df, Phi, *, chain_length, burnin, output_samples_frequency, s
                 if run_pi is not None:
                     run_pi.add(pi, k)
                 engine.rrm_accumulate(k)
-                files["residual_variance"].write(repr(float(vare)) + "\n")
-                files[f"marker_effects_variances_{name}"].write(",".join(repr(float(v)) for v in Gval.ravel()) + "\n")
-                files[f"pi_{name}"].write(",".join(repr(float(v)) for v in pi) + "\n")
+                files.row("residual_variance", [vare])
+                files.row(f"marker_effects_variances_{name}", Gval.ravel())
+                files.row(f"pi_{name}", pi)
                 alpha = engine.rrm_get_state()[0]
                 for qq, cn in enumerate(coef_names):
-                    fh = files[f"marker_effects_{name}_{cn}"]
-                    alpha[qq].astype(ftype).tofile(fh, sep=",", format="%.17g" if double_precision else "%.9g")
-                    fh.write("\n")
+                    files.effects_row(f"marker_effects_{name}_{cn}", alpha[qq].astype(ftype), fmt)
                 if outputEBV:
                     ebvs = [np.asarray(engine.rrm_mul_alpha(qq), dtype=np.float64)[out_rows] for qq in range(c)]
                     for qq, cn in enumerate(coef_names):
                         ebv_run[qq].add(ebvs[qq], k)
-                        files[f"EBV_{cn}"].write(",".join(repr(float(v)) for v in ebvs[qq]) + "\n")
-                    if genvar:
-                        gvm = np.atleast_2d(np.cov(np.stack(ebvs, axis=1), rowvar=False))
-                        gv_samples.append(gvm.ravel())
-                        files["genetic_variance"].write(",".join(repr(float(v)) for v in gvm.ravel()) + "\n")
+                        files.row(f"EBV_{cn}", ebvs[qq])
+                    if genvar is not None:
+                        genvar.add(ebvs)
             if it % printout_frequency == 0 and it > burnin:
-                print(f"\nPosterior means at iteration: {it}")
-                print(f"Residual variance: {np.round(run_vare.mean, 6)}")
-    finally:
-        wall = time.time() - t0
-        for fh in files.values():
-            fh.close()
+                print_posterior_means(it, run_vare.mean)
+    wall = time.time() - t0
 
     # ---- results (output.jl:108-212)
-    out = {}
-    sd_sol = run_sol.sd()
-    out["location parameters"] = pd.DataFrame([(tr, eff, lev, run_sol.mean[i], sd_sol[i]) for i, (tr, eff, lev) in enumerate(lab0)],
-                                              columns=["Trait", "Effect", "Level", "Estimate", "SD"])
-    out["residual variance"] = pd.DataFrame({"Covariance": ["1"], "Estimate": np.atleast_1d(run_vare.mean), "SD": np.atleast_1d(run_vare.sd())})
-    frames = []
-    for qq, cn in enumerate(coef_names):
-        ma, ma2, md = engine.rrm_posterior(qq)
-        frames.append(pd.DataFrame({"Trait": cn, "Marker_ID": Mi.markerID, "Estimate": ma, "SD": np.sqrt(np.abs(ma2 - ma ** 2)), "Model_Frequency": md}))
-    out[f"marker effects {name}"] = pd.concat(frames, ignore_index=True)
-    out[f"marker effects variance {name}"] = pd.DataFrame({"Covariance": cnames, "Estimate": run_varg.mean.ravel(), "SD": run_varg.sd().ravel()})
+    out = {"location parameters": location_table(labels, [0], run_sol.mean, run_sol.sd()),
+           "residual variance": covariance_table(["1"], run_vare)}
+    # run_rrm: the SD from the moments as the session returns them (doubles)
+    out[f"marker effects {name}"] = marker_effects_table([(cn, Mi.markerID) + tuple(engine.rrm_posterior(qq)) for qq, cn in enumerate(coef_names)],
+                                                         sd_in_double=False)
+    out[f"marker effects variance {name}"] = covariance_table(cnames, run_varg)
     if run_pi is not None:
-        out[f"pi_{name}"] = pd.DataFrame({"π": state_labels, "Estimate": run_pi.mean, "SD": run_pi.sd()})
+        out[f"pi_{name}"] = pi_table(run_pi, state_labels(c))
     if outputEBV:
-        for qq, cn in enumerate(coef_names):
-            m = ebv_run[qq].mean
-            out[f"EBV_{cn}"] = pd.DataFrame({"ID": out_ids, "EBV": m, "PEV": np.abs(ebv_run[qq].mean2 - m ** 2)})
-        if genvar and gv_samples:
-            samples = np.array(gv_samples)
-            out["genetic_variance"] = pd.DataFrame({"Covariance": cnames, "Estimate": samples.mean(axis=0),
-                                                    "SD": samples.std(axis=0, ddof=1) if len(samples) > 1 else np.full(samples.shape[1], np.nan)})
-    for key, tab in out.items():                                         # JWAS.jl:480-482
-        tab.to_csv(os.path.join(output_folder, key.replace(" ", "_") + ".txt"), index=False)
+        out.update(ebv_tables(coef_names, out_ids, ebv_run))
+        if genvar is not None:
+            out.update(genvar.tables())
+    write_tables(out, output_folder)
     out["_timing"] = {"wall_s": wall, "device_sweep_ms_total": t_sweep, "iterations": chain_length, "block_size": int(block_size) if block_size is not None else 64,
                       "n": n, "p": p, "ntimes": T, "ncoeff": c, "nrecords": nobs}
     engine.rrm_end()
