@@ -2693,6 +2693,9 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     f64_free_state(c);
+    annot_free(c);                      // (the prior tables below belong to the markers of the old matrix)
+    (void)hipFree(c->pi_vec); (void)hipFree(c->pi_mat); (void)hipFree(c->lpr_mat);      // (sized by the old p: upload_vec allocates once)
+    c->pi_vec = c->pi_mat = c->lpr_mat = nullptr;
     gwas_free(c);
     liab_free(c);
     locpar_free(c);

@@ -292,3 +292,133 @@ def test_runmcmc_double_precision_default_fast_blocks_at_50000_records(tmp_path)
     assert out["_timing"]["block_starts"][:3] == [1, 224, 447]
     est = np.asarray(out["marker effects geno"]["Estimate"])
     assert est.dtype == np.float64 and np.corrcoef(est, beta)[0, 1] > 0.9
+
+
+# ---- the Float64 block chain beyond the plain pass: BayesR and multi-trait sampler I under repetitions, weights, ragged
+# partitions and independent blocks (references: tests/f64_bayesr_reference.py, tests/f64_mt_reference.py) --------------------
+def _weights64(n, seed=2):
+    w = 1.0 + np.random.default_rng(seed).uniform(0, 1.5, n)            # Float64 weights that no Float32 holds
+    assert (w != w.astype(np.float32)).any()
+    return w
+
+
+BAYESR_BLOCK_CASES = {
+    # name: (n, p, partition, nreps, weighted, independent, per-marker priors)
+    "reps5_block64": (300, 64 * 2 + 21, 64, 5, False, False, False),
+    "reps0_block64": (300, 64 * 2 + 21, 64, 0, False, False, False),
+    "reps5_block223": (300, 223 + 40, 223, 5, False, False, False),
+    "reps0_block223": (300, 223 + 40, 223, 0, False, False, False),
+    "weights": (450, 128 + 57, 128, 1, True, False, False),
+    "independent": (450, 96 * 2 + 57, 96, 1, False, True, False),
+    "weights_independent_reps3": (450, 96 * 2 + 57, 96, 3, True, True, False),
+    "ragged_partition_reps0": (380, 300, np.array([0, 5, 70, 71, 135, 290]), 0, False, False, False),
+    "ragged_partition_weights_independent": (380, 300, np.array([0, 5, 70, 71, 135, 290]), 2, True, True, False),
+    "prior_matrix_reps3": (300, 64 * 2 + 21, 64, 3, False, False, True),
+}
+
+
+@pytest.mark.parametrize("case", list(BAYESR_BLOCK_CASES))
+def test_f64_bayesr_block_chain_parity(case):
+    """k64_sample<kBayesR> with rep > 0 (the repetition is part of the draw's key), weighted Grams and right-hand sides,
+    ragged partitions and the independent-block reconcile -- what runMCMC(method="BayesR", double_precision=true,
+    fast_blocks=...) sends after burn-in -- against the Float64 block restatement of BayesR!."""
+    import jwas_jl_amd as J
+    from f64_bayesr_reference import BayesROracleEngine64
+    n, p, part, nreps, weighted, independent, prior_matrix = BAYESR_BLOCK_CASES[case]
+    d = make_dataset(n=n, p=p, ncausal=8, seed=61)
+    X = np.asfortranarray(d["X"].astype(np.float64))
+    hip, ref = J.HipEngine(0, precision=64), BayesROracleEngine64()
+    try:
+        w = _weights64(n) if weighted else None
+        for e in (ref, hip):
+            e.load_dense(X); e.set_weights(w)
+            if np.ndim(part):
+                e.setup_blocks_explicit(part)
+            else:
+                e.setup_blocks(part)
+            e.init_state("BayesR", 1)
+            e.set_residual(d["y"] - d["y"].mean())
+            e.set_state(0, delta=np.ones(p, dtype=np.int32))
+        kw = dict(vare=0.5, var_effect=0.05, pi_classes=np.array([0.9, 0.05, 0.03, 0.02]), nreps=nreps, independent_blocks=independent)
+        if prior_matrix:
+            kw["pi_matrix"] = np.random.default_rng(0).dirichlet([20, 2, 1, 1], size=p)
+        for it in range(1, 6):
+            so = ref.sweep(iteration=it, seed=9, **kw)
+            sh = hip.sweep(iteration=it, seed=9, **kw)
+            assert np.array_equal(so["class_counts"], sh["class_counts"]) and so["n_events"] == sh["n_events"], f"iteration {it}"
+            assert so["bayesr_nnz"] == sh["bayesr_nnz"]
+            np.testing.assert_allclose(sh["bayesr_ssq"], so["bayesr_ssq"], rtol=1e-9)
+            np.testing.assert_allclose(sh["resid_ss"], so["resid_ss"], rtol=1e-9)
+        assert so["bayesr_nnz"] > 0
+        _compare(ref, hip, 1)
+    finally:
+        hip.close()
+
+
+@pytest.mark.parametrize("t,part,nreps,weighted,independent", [(2, np.array([0, 5, 70, 71, 135]), 3, True, False),
+                                                               (3, 64, 1, True, True),
+                                                               (2, np.array([0, 40, 41, 160]), 3, False, True),
+                                                               (3, np.array([0, 9, 100]), 3, True, False)])
+def test_f64_multitrait_sampler1_block_chain_parity(t, part, nreps, weighted, independent):
+    """Multi-trait sampler I in Float64 under residual weights, explicit partitions, repetitions and independent blocks,
+    against the Float64 restatement of the block chain."""
+    import jwas_jl_amd as J
+    from f64_mt_reference import RestatementEngine64
+    n, p = 330, 64 * 2 + 41
+    d = make_dataset(n=n, p=p, ncausal=8, seed=70 + t)
+    X = np.asfortranarray(d["X"].astype(np.float64))
+    rng = np.random.default_rng(t)
+    hip, ref = J.HipEngine(0, precision=64), RestatementEngine64()
+    try:
+        w = _weights64(n) if weighted else None
+        y = d["y"] - d["y"].mean()
+        for e in (ref, hip):
+            e.load_dense(X); e.set_weights(w)
+            if np.ndim(part):
+                e.setup_blocks_explicit(part)
+            else:
+                e.setup_blocks(part)
+            e.init_state("MTBayesC", t)
+        for k in range(t):
+            yk = (1 + 0.3 * k) * y + 0.2 * rng.standard_normal(n)
+            for e in (ref, hip):
+                e.set_residual(yk, k)
+                e.set_state(k, delta=np.ones(p))
+        A = rng.standard_normal((t, t)); B = rng.standard_normal((t, t))
+        kw = dict(vare=(A @ A.T / t + np.eye(t)) * 0.5, var_effect=(B @ B.T / t + np.eye(t)) * 0.003,
+                  log_prior_states=np.log(rng.dirichlet(np.ones(1 << t))), nreps=nreps, independent_blocks=independent)
+        for it in range(1, 6):
+            so = ref.sweep(iteration=it, seed=4, **kw)
+            sh = hip.sweep(iteration=it, seed=4, **kw)
+            assert np.array_equal(so["state_counts"], sh["state_counts"]) and so["n_events"] == sh["n_events"], f"iteration {it}"
+            np.testing.assert_allclose(sh["resid_ss"], so["resid_ss"], rtol=1e-9)
+        _compare(ref, hip, t)
+    finally:
+        hip.close()
+
+
+@pytest.mark.parametrize("heterogeneous", [False, True])
+def test_runmcmc_bayesr_double_precision_fast_blocks_gpu_vs_restatement(tmp_path, heterogeneous):
+    """runMCMC(method="BayesR", double_precision=true, fast_blocks=64): 12 outer iterations, 64 repetitions per block after
+    burn-in (bayesr_block_nreps, BayesR.jl:22-25), with and without heterogeneous residuals -- the device against the same
+    host loop on the block restatement; the bars of test_runmcmc_double_precision_gpu_vs_oracle."""
+    from f64_bayesr_reference import BayesROracleEngine64
+    d = make_dataset(n=300, p=500, ncausal=6, seed=31, center=False)
+    ids = [f"i{i}" for i in range(300)]
+    gdf = pd.DataFrame(d["raw"], columns=[f"m{j}" for j in range(500)])
+    gdf.insert(0, "ID", ids)
+    ph = pd.DataFrame({"ID": ids, "y1": d["y"]})
+    if heterogeneous:
+        ph["weights"] = 1.0 / _weights64(300, seed=6)
+    outs = {}
+    for tag, eng in (("ref", BayesROracleEngine64()), ("hip", None)):
+        geno = api.get_genotypes(gdf, method="BayesR", Pi=0.0, double_precision=True)
+        model = api.build_model("y1 = intercept + geno")
+        outs[tag] = api.runMCMC(model, ph, chain_length=64 * 12, burnin=2, seed=11, double_precision=True, fast_blocks=64,
+                                heterogeneous_residuals=heterogeneous, output_folder=str(tmp_path / tag), _engine=eng)
+        assert outs[tag]["_timing"]["iterations"] == 12
+    eo, eh = outs["ref"]["marker effects geno"], outs["hip"]["marker effects geno"]
+    np.testing.assert_allclose(eh["Estimate"], eo["Estimate"], atol=1e-8)
+    np.testing.assert_allclose(eh["Model_Frequency"], eo["Model_Frequency"], atol=1e-12)
+    np.testing.assert_allclose(outs["hip"]["EBV_y1"]["EBV"], outs["ref"]["EBV_y1"]["EBV"], atol=1e-7)
+    assert float(outs["hip"]["residual variance"]["Estimate"][0]) == pytest.approx(float(outs["ref"]["residual variance"]["Estimate"][0]), rel=1e-9)
