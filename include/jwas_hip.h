@@ -770,6 +770,51 @@ int  jwas_hip_mega_mul_alpha(jwas_hip_ctx* ctx, int32_t trait, int32_t use_outpu
 /* The Gram of one block, b x b doubles with b the block's markers, and (out_xpx != NULL) the block's x'x, b doubles
  * (GibbsMats, tools4genotypes.jl:28-36). */
 int  jwas_hip_mega_get_gram(jwas_hip_ctx* ctx, int64_t block, int64_t nvalues, double* out_gram, double* out_xpx);
+/* ---- several chains of one model in a session: BayesR and the potential scale reduction factor ------------------------------------
+ * K chains of one single-trait model are K traits whose record is the same: chain k is trait k of the session, with the Philox
+ * trait id first_trait + k.  BayesC and RR-BLUP chains run on jwas_hip_mega_sweep; BayesR chains on jwas_hip_mega_sweep_r, the
+ * same block walk under the 4-class law (markers/BayesianAlphabet/BayesR.jl:56-96), all in double.  Per chain vare, sigma2 =
+ * var_effect, gamma[4] with gamma_1 = 0, pi[4]; one marker:
+ *   rhs = (x'r + x'x alpha) / vare;  c = 2..4: v_c = gamma_c sigma2, lhs_c = x'x / vare + 1 / v_c, bHat_c = rhs / lhs_c,
+ *   lp_c = 0.5 (log(1 / lhs_c) - log v_c + bHat_c rhs) + log pi_c;  lp_1 = log pi_1;  probs by the max-shifted log-sum-exp;
+ *   the class by the CDF walk `while cp <= u` on the uniform of slot 10; class 1: alpha = 0, else alpha = bHat_c + z sqrt(1 / lhs_c)
+ *   with the normal of slot 11; delta = the class, 1..4; beta = alpha.
+ * gamma and pi are row-major [4][T]: value c of chain k at [c * T + k].  The statistics are summed in the order of the BayesC
+ * statistics (lane order, the shuffle tree, the blocks in stream order): chain k of a K-chain session is bit-equal to a one-chain
+ * session with first_trait = k.  jwas_hip_mega_set_state checks delta against {0, 1}: a BayesR chain is started from the session's
+ * own starting state or from alpha alone (the law reads no delta).  The first _sweep_r and the first _psrf of a session allocate
+ * 8 (18 T + 2 T ceil(n / 256)) and 8 p bytes beyond jwas_hip_mega_estimate_bytes.
+ * Errors: as the session's; JWAS_HIP_EINVAL also for class probabilities of a chain that do not sum to 1 within 1e-8 or lie
+ * outside [0, 1], gamma_1 != 0, another gamma or sigma2 not positive and finite; _psrf: fewer than 2 chains or nsamples < 2. */
+typedef struct jwas_mega_r_params {
+    uint32_t iteration;                 /* MCMC iteration >= 1 (enters the RNG counter)                                          */
+    uint32_t reserved;
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                     */
+    const double* vare;                 /* [T] the residual variance of every chain                                              */
+    const double* var_effect;           /* [T] sigma2 of every chain                                                             */
+    const double* gamma;                /* [4][T] the class multipliers (gamma[0][k] = 0)                                        */
+    const double* pi;                   /* [4][T] the class probabilities                                                        */
+} jwas_mega_r_params;
+typedef struct jwas_mega_r_stats {      /* every pointer: doubles of the caller (any may be NULL)                                */
+    double* class_counts;               /* [4][T] markers per class (the Dirichlet update of pi)                                 */
+    double* ssq;                        /* [T] sum alpha_j^2 / gamma_class(j) over the markers outside class 1                   */
+    double* nnz;                        /* [T] the number of those markers                                                       */
+    double* alpha_ss;                   /* [T] alpha'alpha                                                                       */
+    double* resid_ss;                   /* [T] sum r^2 after the sweep                                                           */
+    double* resid_sum;                  /* [T] sum r                                                                             */
+    double* n_changed;                  /* [T] markers whose effect moved                                                        */
+    double  step_ms;                    /* device time of the sweep                                                              */
+} jwas_mega_r_stats;
+/* One BayesR sweep over all markers of all chains.  Synchronous. */
+int  jwas_hip_mega_sweep_r(jwas_hip_ctx* ctx, const jwas_mega_r_params* params, jwas_mega_r_stats* stats);
+/* jwas_hip_mega_accumulate for BayesR chains: the model frequency is the frequency of class > 1. */
+int  jwas_hip_mega_accumulate_r(jwas_hip_ctx* ctx, double nsamples);
+/* The potential scale reduction factor of every marker effect (Gelman and Rubin) from the running means m_k and means of squares
+ * q_k of the session's T >= 2 chains after nsamples >= 2 accumulated samples, p doubles:
+ *   s_k^2 = N / (N - 1) (q_k - m_k^2),  W = mean_k s_k^2,  B / N = sum_k (m_k - mean m)^2 / (T - 1),
+ *   V = (N - 1) / N W + B / N,  out = sqrt(V / W);  NaN where W = 0 (the marker never entered the model in any chain).
+ * The chains are added in ascending order; a pure function of the accumulators. */
+int  jwas_hip_mega_psrf(jwas_hip_ctx* ctx, double nsamples, double* out_p);
 /* Device bytes of a session (pure; an upper bound). */
 int64_t jwas_hip_mega_estimate_bytes(int64_t n, int64_t p, int32_t ntraits, int32_t block_size);
 int  jwas_hip_mega_end(jwas_hip_ctx* ctx);

@@ -610,6 +610,45 @@ function hip_mega_sweep!(b::HipBackend, iter::Integer, seed::Integer, vare::Vect
 end
 hip_mega_accumulate!(b::HipBackend, nsamples::Real) =
     hip_check(b.ctx, ccall((:jwas_hip_mega_accumulate, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Float64), b.ctx, nsamples))
+# Several chains of one model: BayesR chains (BayesR.jl:56-96 in double) and the potential scale reduction factor of the chains.
+# gamma, pi: 4 x t in the library's row-major layout, that is a t x 4 Julia matrix.
+struct HipMegaRParams
+    iteration::UInt32
+    reserved::UInt32
+    seed::UInt64
+    vare::Ptr{Float64}
+    var_effect::Ptr{Float64}
+    gamma::Ptr{Float64}
+    pi::Ptr{Float64}
+end
+struct HipMegaRStats
+    class_counts::Ptr{Float64}
+    ssq::Ptr{Float64}
+    nnz::Ptr{Float64}
+    alpha_ss::Ptr{Float64}
+    resid_ss::Ptr{Float64}
+    resid_sum::Ptr{Float64}
+    n_changed::Ptr{Float64}
+    step_ms::Float64
+end
+function hip_mega_sweep_r!(b::HipBackend, iter::Integer, seed::Integer, vare::Vector{Float64}, var_effect::Vector{Float64}, gamma::Matrix{Float64}, pi::Matrix{Float64})
+    t = length(vare)
+    counts = zeros(Float64, t, 4)
+    out = [zeros(Float64, t) for _ in 1:6]      # ssq, nnz, alpha_ss, resid_ss, resid_sum, n_changed
+    S = Ref(HipMegaRStats(pointer(counts), pointer.(out)..., 0.0))
+    GC.@preserve vare var_effect gamma pi counts out begin
+        P = HipMegaRParams(UInt32(iter), UInt32(0), UInt64(seed), pointer(vare), pointer(var_effect), pointer(gamma), pointer(pi))
+        hip_check(b.ctx, ccall((:jwas_hip_mega_sweep_r, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipMegaRParams}, Ref{HipMegaRStats}), b.ctx, Ref(P), S))
+    end
+    return (class_counts=counts, ssq=out[1], nnz=out[2], alpha_ss=out[3], resid_ss=out[4], resid_sum=out[5], n_changed=out[6], step_ms=S[].step_ms)
+end
+hip_mega_accumulate_r!(b::HipBackend, nsamples::Real) =
+    hip_check(b.ctx, ccall((:jwas_hip_mega_accumulate_r, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Float64), b.ctx, nsamples))
+function hip_mega_psrf(b::HipBackend, nsamples::Real, p::Integer)
+    out = Vector{Float64}(undef, p)
+    hip_check(b.ctx, ccall((:jwas_hip_mega_psrf, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Float64, Ptr{Float64}), b.ctx, nsamples, out))
+    return out
+end
 function hip_mega_posterior(b::HipBackend, trait::Integer, p::Integer)
     m, m2, f = (Vector{Float64}(undef, p) for _ in 1:3)
     hip_check(b.ctx, ccall((:jwas_hip_mega_get_posterior, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.ctx, trait - 1, m, m2, f))

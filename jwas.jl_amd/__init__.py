@@ -7,7 +7,7 @@ registers this package under that name).
 from ._lib import JwasHipError, LIB_PATH  # noqa: F401
 from .engine import HipEngine, BAYESR_GAMMA  # noqa: F401
 
-__all__ = ["HipEngine", "JwasHipError", "BAYESR_GAMMA", "LIB_PATH"]
+__all__ = ["HipEngine", "JwasHipError", "BAYESR_GAMMA", "LIB_PATH", "PSRF"]
 
 
 def __getattr__(name):
@@ -18,6 +18,9 @@ def __getattr__(name):
     if name == "GWAS":
         from . import gwas
         return gwas.GWAS
+    if name == "PSRF":
+        from . import diagnostics
+        return diagnostics.PSRF
     if name in ("prepare_streaming_genotypes", "load_streaming_backend"):
         from . import streaming
         return getattr(streaming, name)

@@ -125,6 +125,16 @@ class MegaStats(C.Structure):
                 ("n_changed", C.c_void_p), ("step_ms", C.c_double)]
 
 
+class MegaRParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("vare", C.c_void_p), ("var_effect", C.c_void_p),
+                ("gamma", C.c_void_p), ("pi", C.c_void_p)]
+
+
+class MegaRStats(C.Structure):
+    _fields_ = [("class_counts", C.c_void_p), ("ssq", C.c_void_p), ("nnz", C.c_void_p), ("alpha_ss", C.c_void_p), ("resid_ss", C.c_void_p),
+                ("resid_sum", C.c_void_p), ("n_changed", C.c_void_p), ("step_ms", C.c_double)]
+
+
 class JwasHipError(RuntimeError):
     """Raised for any non-zero status of the C ABI (the analogue of the reference's error(...))."""
 
@@ -294,6 +304,9 @@ PROTOTYPES = {
     "jwas_hip_mega_impute": (_INT, [_vp, _P(MegaParams)]),
     "jwas_hip_mega_sweep": (_INT, [_vp, _P(MegaParams), _P(MegaStats)]),
     "jwas_hip_mega_accumulate": (_INT, [_vp, C.c_double]),
+    "jwas_hip_mega_sweep_r": (_INT, [_vp, _P(MegaRParams), _P(MegaRStats)]),
+    "jwas_hip_mega_accumulate_r": (_INT, [_vp, C.c_double]),
+    "jwas_hip_mega_psrf": (_INT, [_vp, C.c_double, _vp]),
     "jwas_hip_mega_get_posterior": (_INT, [_vp, _i32, _vp, _vp, _vp]),
     "jwas_hip_mega_mul_alpha": (_INT, [_vp, _i32, _i32, _vp]),
     "jwas_hip_mega_get_gram": (_INT, [_vp, _i64, _i64, _vp, _vp]),

@@ -493,7 +493,7 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
             output_samples_for_all_parameters=False,
             # device options (the analogue of storage=:stream's opt-in knobs)
             device=0, block_size=None, gram_mode="mfma", blocks_per_launch=None, location_parameters="auto",
-            annotation_priors="host", fitting_J_vector=True, _engine=None):
+            annotation_priors="host", fitting_J_vector=True, chains=1, first_chain=0, bayesr_gamma=None, _engine=None):
     """JWAS.jl:161-511.  Returns the reference's output Dict (output.jl:108-212) as a dict of pandas
     DataFrames and writes the same text files under `output_folder`.
 
@@ -594,6 +594,21 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     device before the location parameters of every iteration (mcmc.py step 0) and saved, with the thresholds, as
     MCMC_samples_liabilities_<trait>.txt / MCMC_samples_threshold_<trait>.txt.  Every sampler, storage mode and precision.
 
+    chains=K, first_chain=0, bayesr_gamma=None (device options; chains.py): K in 2..64 chains of ONE single-trait model with different
+    seeds in one device session (the genotypes uploaded once, one pass over them per sweep for all chains; csrc/mega.hpp) and the
+    potential scale reduction factor of Gelman and Rubin over the chains.  chains=1 (the default) is the single-chain path,
+    untouched.  BayesC (estimatePi true or false), RR-BLUP and BayesR (the default gamma, or bayesr_gamma = four multipliers starting
+    with 0); one genotype category, dense Float32 or double_precision=True, block_size <= 256 (default 256), location parameters
+    on the host, outputEBV(model, IDs).  Chain k draws on the device with the counter id first_chain + k and on the host from
+    default_rng([seed, first_chain + k]): chain k of a K-chain run equals that chain run alone (chains=2, first_chain=k takes its
+    first chain).  All chains start from the reference's starting state (no over-dispersed starts).  Outputs: chain_<id>/ with the
+    reference's files of every chain, PSRF.txt (every marker effect on the device, pi and the variances on the host),
+    PSRF_summary.txt, the usual tables pooled over the chains; the returned dict also holds "chains", "PSRF", "PSRF_summary".
+    Everything else (BayesA/B/L, fast_blocks, independent_blocks, heterogeneous_residuals, set_random, categorical / censored traits,
+    annotations, starting values, storage=:stream, device_genotypes, shards, single_step_analysis, RRM, causal_structure,
+    location_parameters="device", several traits or categories) raises NotImplementedError naming the argument before anything
+    is written.  Against K sequential runs: NOTES.md, "Several chains in one session".
+
     double_precision=True (JWAS.jl:349-366): genotypes, residual, effects and the samplers' arithmetic all Float64 -- a
     Float64 device context (jwas_hip_set_precision; csrc/f64_path.hpp): single-trait BayesA/B/C, RR-BLUP, BayesL, BayesR,
     multi-trait BayesC and BayesA/B under sampler I and II and marker-specific joint priors on dense storage; any fast_blocks
@@ -604,6 +619,36 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
         raise ValueError("independent_blocks=true requires fast_blocks != false.")             # :242-244
     from . import rrm as _rrm
     from . import megatrait as _mt
+    if not (isinstance(chains, (int, np.integer)) and not isinstance(chains, bool) and int(chains) == 1):
+        from . import chains as _ch             # several chains of one model: a driver of its own (chains.py), validated before anything is written
+        nchains = _ch.check_chains(chains)
+        for flag, name in ((update_priors_frequency, "update_priors_frequency"), (prediction_equation, "prediction_equation")):
+            if not _is_false(flag) and flag != 0:
+                raise NotImplementedError(f"runMCMC(...; {name}=...) is outside the device marker path and stays on the reference")
+        if location_parameters not in ("auto", "host", "device"):
+            raise ValueError('location_parameters must be "auto", "host" or "device".')
+        _ch.validate(model, df, chains=nchains, first_chain=first_chain, fast_blocks=fast_blocks, independent_blocks=independent_blocks,
+                     causal_structure=causal_structure, RRM=RRM, location_parameters=location_parameters,
+                     heterogeneous_residuals=heterogeneous_residuals, starting_value=starting_value, block_size=block_size,
+                     single_step_analysis=single_step_analysis, annotation_priors=annotation_priors, bayesr_gamma=bayesr_gamma, engine=_engine)
+        if output_samples_frequency is None:
+            output_samples_frequency = chain_length // 1000 if chain_length > 1000 else 1      # :168
+        if int(output_samples_frequency) <= 0:
+            raise ValueError("output_samples_frequency should be an integer > 0.")
+        myfolder, folderi = output_folder, 1
+        while os.path.exists(output_folder):                            # an existing output folder is never overwritten (JWAS.jl:255-262)
+            print(f"The folder {output_folder} already exists.")
+            output_folder = myfolder + str(folderi)
+            folderi += 1
+        os.makedirs(output_folder)
+        return _ch.run_chains(model, df, chains=nchains, first_chain=int(first_chain), chain_length=int(chain_length), burnin=int(burnin),
+                              output_samples_frequency=int(output_samples_frequency), seed=seed, double_precision=bool(double_precision),
+                              outputEBV=outputEBV, output_heritability=bool(output_heritability), output_folder=output_folder,
+                              printout_frequency=chain_length + 1 if printout_frequency is None else printout_frequency, device=device,
+                              block_size=block_size, bayesr_gamma=bayesr_gamma, engine=_engine, printout_model_info=printout_model_info,
+                              output_samples_for_all_parameters=output_samples_for_all_parameters)
+    if first_chain != 0 or bayesr_gamma is not None:
+        raise ValueError("first_chain and bayesr_gamma apply to runMCMC(...; chains=K) with K >= 2.")
     megatrait = _mt.routes(model)             # more than 4 traits: a driver of its own (megatrait.py), validated before anything is written
     if megatrait:
         _mt.validate(model, df, fast_blocks=fast_blocks, independent_blocks=independent_blocks, causal_structure=causal_structure, RRM=RRM,

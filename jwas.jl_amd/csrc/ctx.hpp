@@ -318,6 +318,10 @@ struct jwas_hip_ctx {
         double* row = nullptr;                              // [row_cap] X alpha_k
         void* ev = nullptr;                                 // jwg::Events: the change lists of the last sampled block
         std::vector<double> par_host;                       // what par was filled from (kept until the sweep has finished)
+        // BayesR chains (jwas_hip_mega_sweep_r) and the PSRF of the chains: allocated at their first call
+        double* par_r = nullptr;                            // [kParRSize][nt]
+        double* stat_r = nullptr;                           // [nt][kStRSize] | [nt][nslices][2]
+        double* psrf = nullptr;                             // [p]
     } mg;
     // Single-step imputation (jwas_hip_ss_begin .. _end; single_step/SSBR.jl:83-159; csrc/ssbr.hpp): the factors of A^nn, A^ng and the
     // chunk buffers of a sparse solve with many right-hand sides.  It is bound to no matrix: the targets are checked at every chunk.

@@ -25,6 +25,8 @@
 //                          walks the block 64 markers at a time by speculative evaluation (every pending lane tests its marker
 //                          against the current s, the first changed marker commits, its Gram row -- b doubles, read from L2 --
 //                          corrects s); the trait's change list and statistics.
+//   k_mega_sample_r        the same walk under the 4-class law of BayesR (below, beside the kernel): K chains of one model are K
+//                          traits with the same record.
 //   k_mega_finish          grid (row slices, traits): the last change list, then sum r^2 and sum r of the slice.
 //   k_mega_impute          grid (row chunks, traits): a missing cell (bit mask [T][ld / 32]) is redrawn from N(0, vare_k) -- with a
 //                          diagonal R the conditional law of a missing residual whatever the record's other traits
@@ -338,6 +340,155 @@ __global__ __launch_bounds__(256) void k_mega_sample(const SampleArgs A)
     }
 }
 
+// ---- one block of one BayesR chain ------------------------------------------------------------------------------------------------------
+// The 4-class law of BayesR (markers/BayesianAlphabet/BayesR.jl:56-96), all in double, on the walk of k_mega_sample.  Per chain
+// vare, sigma2, gamma[4] (gamma_1 = 0) and log pi[4]; one marker:
+//   rhs = (s + xpx alpha) / vare;  class c = 2..4: v_c = gamma_c sigma2, lhs_c = xpx / vare + 1 / v_c, bHat_c = rhs / lhs_c,
+//   lp_c = 0.5 (log(1 / lhs_c) - log v_c + bHat_c rhs) + log pi_c;  lp_1 = log pi_1
+//   probs_c = exp(lp_c - (mx + log sum_c exp(lp_c - mx))), mx = max lp (the sum over c ascending)
+//   the class: cp = probs_1, while cp <= u the next class is added (rand(Categorical), the CDF walk)
+//   class 1: alpha = 0;  class c: alpha = bHat_c + z sqrt(1 / lhs_c);  delta = the class, 1..4;  beta = alpha
+// Draws: slot 10 the uniform, slot 11 the normal, trait_id = first_trait + k, as k_mega_sample.
+constexpr int kClasses = 4;
+// the device record of a BayesR chain's statistics
+constexpr int kStRCount = 0, kStRSsq = 4, kStRNnz = 5, kStRAlpha = 6, kStRChanged = 7, kStRSize = 8;
+// the per-chain parameters of a BayesR sweep: par[q * T + k]
+constexpr int kParRVare = 0, kParRVar = 1, kParRGamma = 2, kParRLogPi = 6, kParRSize = 10;
+
+// grid = T workgroups of 256 threads; SampleArgs with par [kParRSize][T] and stat [T][kStRSize]
+__global__ __launch_bounds__(256) void k_mega_sample_r(const SampleArgs A)
+{
+    __shared__ double s_s[kMaxBlock], s_a0[kMaxBlock];
+    const int lane = threadIdx.x & 63, k = blockIdx.x;
+    const int b = A.b, bs = A.bs;
+    double* __restrict__ alpha = A.alpha + (int64_t)k * A.p;
+    double* __restrict__ beta = A.beta + (int64_t)k * A.p;
+    double* __restrict__ delta = A.delta + (int64_t)k * A.p;
+    for (int i = threadIdx.x; i < b; i += 256) {
+        const double* __restrict__ part = A.partials + (int64_t)k * bs + i;
+        const int64_t stride = (int64_t)A.T * bs;
+        double s = 0.0;
+#pragma unroll 8
+        for (int sl = 0; sl < A.nslices; ++sl) s = s + part[sl * stride];      // (ascending, as k_mega_sample)
+        s_s[i] = s;
+        s_a0[i] = alpha[A.j0 + i];
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    const double vare = A.par[kParRVare * A.T + k], sig = A.par[kParRVar * A.T + k], ie = 1.0 / vare;
+    const double lp1 = A.par[kParRLogPi * A.T + k];
+    double gam[3], iv[3], logv[3], lpi[3];                   // the classes 2..4
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double g = A.par[(kParRGamma + 1 + c) * A.T + k], vc = g * sig;
+        gam[c] = g; iv[c] = 1.0 / vc; logv[c] = log(vc);
+        lpi[c] = A.par[(kParRLogPi + 1 + c) * A.T + k];
+    }
+    const uint32_t tag = kTag | (A.first_trait + (uint32_t)k);
+    double st_acc[kStRSize];
+#pragma unroll
+    for (int i = 0; i < kStRSize; ++i) st_acc[i] = 0.0;
+    const int nsub = (b + 63) / 64;
+    int base = 0;
+#pragma unroll 1
+    for (int s = 0; s < nsub; ++s) {
+        const int kq = 64 * s + lane;
+        const bool valid = kq < b;
+        const int kl = valid ? kq : 0;
+        const int64_t j = A.j0 + kl;
+        const double xx = A.xpx[j];
+        const double z = jwu::normal_from(jw::philox4x32_10((uint32_t)j, A.iter, tag, kSlotZ, A.seed_lo, A.seed_hi));
+        const jw::u32x4 wu = jw::philox4x32_10((uint32_t)j, A.iter, tag, kSlotU, A.seed_lo, A.seed_hi);
+        const double u = jw::u52(wu.x, wu.y);
+        double invLhs[3], lconst[3], sdl[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double lhs = xx * ie + iv[c];
+            invLhs[c] = 1.0 / lhs;
+            lconst[c] = log(invLhs[c]) - logv[c];
+            sdl[c] = sqrt(invLhs[c]);
+        }
+        double a_cur = s_a0[kl], d_cur = delta[j];
+        unsigned long long pending = __ballot(valid);
+        while (pending) {
+            const double rhs = (s_s[kl] + xx * a_cur) * ie;
+            double bh[3], lp[3], mx = lp1;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                bh[c] = rhs * invLhs[c];
+                lp[c] = 0.5 * (lconst[c] + bh[c] * rhs) + lpi[c];
+                mx = lp[c] > mx ? lp[c] : mx;
+            }
+            const double se = ((exp(lp1 - mx) + exp(lp[0] - mx)) + exp(lp[1] - mx)) + exp(lp[2] - mx);
+            const double ln = mx + log(se);
+            // the CDF walk: the class is the first whose cumulated probability exceeds u (the last class takes the rest)
+            double cp = exp(lp1 - ln);
+            int cls = 0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (cls == c && cp <= u) { cls = c + 1; cp = cp + exp(lp[c] - ln); }
+            }
+            const double bsel = cls == 1 ? bh[0] : (cls == 2 ? bh[1] : bh[2]);
+            const double ssel = cls == 1 ? sdl[0] : (cls == 2 ? sdl[1] : sdl[2]);
+            const double an = cls == 0 ? 0.0 : bsel + z * ssel;
+            const double dn = (double)(cls + 1);
+            const bool ch = an != a_cur;
+            const unsigned long long mm = __ballot(ch && valid) & pending;
+            const int kw = mm ? (int)__builtin_ctzll(mm) : 64;
+            // lanes before the winner are final with what they just evaluated (their effects do not move)
+            const unsigned long long done = (kw >= 64) ? pending : (pending & ((kw == 63) ? ~0ull : ((2ull << kw) - 1ull)));
+            if ((done >> lane) & 1ull) d_cur = dn;
+            if (kw >= 64) break;
+            // the winner commits; its Gram row corrects s of the whole block: s_i += G_i,ce d
+            const int ce = 64 * s + kw;
+            const double Dl = a_cur - an;
+            const double D = __shfl(Dl, kw, 64);
+            if (lane == kw) a_cur = an;
+            const double* __restrict__ grow = A.gram + (int64_t)ce * bs;
+            __builtin_amdgcn_wave_barrier();                // (one wave: its LDS accesses execute in program order)
+            for (int k2 = lane; k2 < b; k2 += 64) s_s[k2] = s_s[k2] + grow[k2] * D;
+            __builtin_amdgcn_wave_barrier();
+            pending &= ~done;
+        }
+        // the sub-block is final: state, change list, statistics
+        const bool changed = valid && (a_cur != s_a0[kl]);
+        const unsigned long long cm = __ballot(changed);
+        if (changed) {
+            const int e = base + __popcll(cm & ((1ull << lane) - 1ull));
+            A.ev->idx[k][e] = (int32_t)j;
+            A.ev->d[k][e] = s_a0[kl] - a_cur;
+        }
+        base += __popcll(cm);
+        if (valid) {
+            alpha[j] = a_cur; beta[j] = a_cur; delta[j] = d_cur;
+            const double a2 = a_cur * a_cur;
+#pragma unroll
+            for (int c = 0; c < kClasses; ++c)
+                if (d_cur == (double)(c + 1)) st_acc[kStRCount + c] = st_acc[kStRCount + c] + 1.0;
+            if (d_cur > 1.0) {
+                const double gs = d_cur == 2.0 ? gam[0] : (d_cur == 3.0 ? gam[1] : gam[2]);
+                st_acc[kStRSsq] = st_acc[kStRSsq] + a2 / gs;
+                st_acc[kStRNnz] = st_acc[kStRNnz] + 1.0;
+            }
+            st_acc[kStRAlpha] = st_acc[kStRAlpha] + a2;
+            if (changed) st_acc[kStRChanged] = st_acc[kStRChanged] + 1.0;
+        }
+    }
+    // the block's statistics join the sweep's: shuffle tree, lane 0 adds (the blocks of a sweep run in stream order)
+#pragma unroll
+    for (int i = 0; i < kStRSize; ++i) {
+        double t = st_acc[i];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) t = t + __shfl_down(t, off, 64);
+        st_acc[i] = t;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < kStRSize; ++i) A.stat[k * kStRSize + i] = A.stat[k * kStRSize + i] + st_acc[i];
+        A.ev->count[k] = base;
+    }
+}
+
 // ---- missing cells ---------------------------------------------------------------------------------------------------------------------
 // grid = (ceil(n / 256), T): r_k[i] = z sqrt(vare_k) where bit i of the trait's mask is set; nothing else is written
 __global__ __launch_bounds__(256) void k_mega_impute(const uint32_t* __restrict__ mask, int64_t words, int64_t n, int64_t ld, const double* __restrict__ vare,
@@ -362,6 +513,45 @@ __global__ __launch_bounds__(256) void k_mega_accumulate(const double* __restric
     mean_a[i] = jwu::running_mean(mean_a[i], a, ns);
     mean_a2[i] = jwu::running_mean(mean_a2[i], a * a, ns);
     mean_d[i] = jwu::running_mean(mean_d[i], delta[i], ns);
+}
+
+// ... of BayesR chains: delta holds the class 1..4, the model frequency is that of class > 1
+__global__ __launch_bounds__(256) void k_mega_accumulate_r(const double* __restrict__ alpha, const double* __restrict__ delta, int64_t tp, double ns,
+                                                           double* __restrict__ mean_a, double* __restrict__ mean_a2, double* __restrict__ mean_d)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= tp) return;
+    const double a = alpha[i];
+    mean_a[i] = jwu::running_mean(mean_a[i], a, ns);
+    mean_a2[i] = jwu::running_mean(mean_a2[i], a * a, ns);
+    mean_d[i] = jwu::running_mean(mean_d[i], delta[i] > 1.0 ? 1.0 : 0.0, ns);
+}
+
+// The potential scale reduction factor of every marker effect (Gelman and Rubin) from the running means m_k and means of squares q_k
+// of K chains after N saved samples: s_k^2 = N / (N - 1) (q_k - m_k^2), W = mean_k s_k^2, B / N = sum_k (m_k - mean m)^2 / (K - 1),
+// V = (N - 1) / N W + B / N, out = sqrt(V / W); W == 0 (the marker never entered the model in any chain): NaN.  One thread per marker,
+// the chains added in ascending order; at most kPsrfBlocks workgroups, the markers beyond them in further trips of the same threads.
+constexpr int kPsrfBlocks = 64;
+__global__ __launch_bounds__(256) void k_mega_psrf(const double* __restrict__ mean_a, const double* __restrict__ mean_a2, int64_t p, int32_t K, double N,
+                                                   double* __restrict__ out)
+{
+    const double f = N / (N - 1.0), g = (N - 1.0) / N;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p; j += (int64_t)gridDim.x * 256) {
+        double sm = 0.0, sw = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double m = mean_a[(int64_t)k * p + j];
+            sm = sm + m;
+            sw = sw + f * (mean_a2[(int64_t)k * p + j] - m * m);
+        }
+        const double mbar = sm / (double)K, W = sw / (double)K;
+        double sb = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double e = mean_a[(int64_t)k * p + j] - mbar;
+            sb = sb + e * e;
+        }
+        const double V = g * W + sb / (double)(K - 1);
+        out[j] = W == 0.0 ? __builtin_nan("") : sqrt(V / W);
+    }
 }
 
 // out[i] = sum_j x_ij alpha_j (j ascending, zero effects skipped): one thread per row of X (the context's matrix or its output rows)

@@ -1,5 +1,7 @@
 // session_mega.hip -- mega-trait models (mega.hpp), jwas_hip_mega_begin .. _end: megaBayesABC! / megaBayesC0!
 // (markers/BayesianAlphabet/BayesABC.jl:1-58) for up to 64 traits and sampleMissingResiduals under a diagonal R (residual.jl:51-73).
+// Several chains of one model are traits of the same session: jwas_hip_mega_sweep_r (the 4-class BayesR law, BayesR.jl:56-96),
+// jwas_hip_mega_accumulate_r and jwas_hip_mega_psrf (the potential scale reduction factor over the chains).
 #include "ctx.hpp"
 #include "mega.hpp"
 
@@ -263,6 +265,123 @@ int jwas_hip_mega_accumulate(jwas_hip_ctx* c, double nsamples)
                        nsamples, b.mean_a, b.mean_a2, b.mean_d);
     HIPCHK(c, hipGetLastError());
     return JWAS_HIP_OK;
+}
+
+// the per-chain parameters of a BayesR sweep: checked, then par_host = vare | sigma2 | gamma[4] | log pi[4]
+static int mega_params_r(jwas_hip_ctx* c, const jwas_mega_r_params* P)
+{
+    auto& b = c->mg;
+    NEED(c, P, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, P->iteration >= 1, JWAS_HIP_EINVAL, "jwas_hip_mega_sweep_r: iteration must be >= 1");
+    NEED(c, P->vare && P->var_effect && P->gamma && P->pi, JWAS_HIP_EINVAL, "jwas_hip_mega_sweep_r: NULL parameter array");
+    const int T = b.nt;
+    b.par_host.assign((size_t)jwg::kParRSize * T, 1.0);
+    for (int k = 0; k < T; ++k) {
+        NEED(c, std::isfinite(P->vare[k]) && P->vare[k] > 0.0, JWAS_HIP_EINVAL, "vare[%d] must be positive and finite (%g)", k, P->vare[k]);
+        NEED(c, std::isfinite(P->var_effect[k]) && P->var_effect[k] > 0.0, JWAS_HIP_EINVAL, "var_effect[%d] must be positive and finite (%g)", k, P->var_effect[k]);
+        b.par_host[(size_t)jwg::kParRVare * T + k] = P->vare[k];
+        b.par_host[(size_t)jwg::kParRVar * T + k] = P->var_effect[k];
+        double sum = 0.0;
+        for (int q = 0; q < jwg::kClasses; ++q) {
+            const double g = P->gamma[(size_t)q * T + k], pq = P->pi[(size_t)q * T + k];
+            if (q == 0) NEED(c, g == 0.0, JWAS_HIP_EINVAL, "gamma[0][%d] must be 0: class 1 is the null class (%g)", k, g);
+            else NEED(c, std::isfinite(g) && g > 0.0, JWAS_HIP_EINVAL, "gamma[%d][%d] must be positive and finite (%g)", q, k, g);
+            NEED(c, pq >= 0.0 && pq <= 1.0, JWAS_HIP_EINVAL, "pi[%d][%d] must be in [0,1] (%g)", q, k, pq);
+            sum += pq;
+            b.par_host[(size_t)(jwg::kParRGamma + q) * T + k] = g;
+            b.par_host[(size_t)(jwg::kParRLogPi + q) * T + k] = std::log(pq);              // pi = 0: -Inf, the class is never drawn
+        }
+        NEED(c, std::fabs(sum - 1.0) <= 1e-8, JWAS_HIP_EINVAL, "the class probabilities of chain %d sum to %.17g, not 1", k, sum);
+    }
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_sweep_r(jwas_hip_ctx* c, const jwas_mega_r_params* P, jwas_mega_r_stats* S)
+{
+    if (int rc = need_mega(c)) return rc;
+    NEED(c, S, JWAS_HIP_EINVAL, "NULL argument");
+    if (int rc = mega_params_r(c, P)) return rc;
+    auto& b = c->mg;
+    const int T = b.nt, nsl = c->nslices;
+    const size_t nstat = (size_t)T * (size_t)(jwg::kStRSize + 2 * nsl);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!b.par_r) {
+        if (int rc = alloc_or_nomem(c, b.mem, &b.par_r, sizeof(double) * (size_t)jwg::kParRSize * T, "mega-trait session", mega_free)) return rc;
+        if (int rc = alloc_or_nomem(c, b.mem, &b.stat_r, sizeof(double) * nstat, "mega-trait session", mega_free)) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(b.par_r, b.par_host.data(), sizeof(double) * b.par_host.size(), hipMemcpyHostToDevice, c->stream));
+    if (int rc = step_timer_begin(c)) return rc;
+    HIPCHK(c, hipMemsetAsync(b.stat_r, 0, sizeof(double) * nstat, c->stream));
+    jwg::UpdateArgs U = {};
+    U.X = mega_genotypes(c); U.R = b.R; U.partials = b.partials; U.ld = c->ld; U.T = T; U.bs = b.bs;
+    jwg::SampleArgs A = {};
+    A.partials = b.partials; A.xpx = b.xpx; A.par = b.par_r; A.alpha = b.alpha; A.beta = b.beta; A.delta = b.delta; A.ev = (jwg::Events*)b.ev;
+    A.stat = b.stat_r; A.p = c->p; A.nslices = nsl; A.bs = b.bs; A.T = T; A.iter = P->iteration; A.first_trait = b.first_trait;
+    split_seed(P->seed, A.seed_lo, A.seed_hi);
+    jwg::FinishArgs F = {};
+    F.X = mega_genotypes(c); F.R = b.R; F.ev = (const jwg::Events*)b.ev; F.fin = b.stat_r + (size_t)T * jwg::kStRSize; F.ld = c->ld; F.T = T;
+    const dim3 tiles((unsigned)nsl, (unsigned)((T + jwg::kTT - 1) / jwg::kTT));
+    with_real(c, [&](auto real) {
+        using real_t = decltype(real);
+        for (int64_t k = 0; k < b.nblocks; ++k) {
+            const int64_t j0 = k * b.bs;
+            U.ev = k ? (const jwg::Events*)b.ev : nullptr; U.j0 = j0; U.b = (int32_t)std::min<int64_t>(b.bs, c->p - j0);
+            A.gram = b.gram + k * (int64_t)b.bs * b.bs; A.j0 = j0; A.b = U.b;
+            hipLaunchKernelGGL((jwg::k_mega_update_partial<real_t>), tiles, dim3(256), 0, c->stream, U);
+            hipLaunchKernelGGL(jwg::k_mega_sample_r, dim3((unsigned)T), dim3(256), 0, c->stream, A);
+        }
+        hipLaunchKernelGGL((jwg::k_mega_finish<real_t>), dim3((unsigned)nsl, (unsigned)T), dim3(256), 0, c->stream, F);
+    });
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> host(nstat);
+    double ms = 0.0;
+    if (int rc = step_timer_end(c, host.data(), b.stat_r, sizeof(double) * nstat, &ms)) return rc;
+    S->step_ms = ms;
+    for (int k = 0; k < T; ++k) {
+        const double* st = host.data() + (size_t)k * jwg::kStRSize;
+        if (S->class_counts)
+            for (int q = 0; q < jwg::kClasses; ++q) S->class_counts[(size_t)q * T + k] = st[jwg::kStRCount + q];
+        if (S->ssq) S->ssq[k] = st[jwg::kStRSsq];
+        if (S->nnz) S->nnz[k] = st[jwg::kStRNnz];
+        if (S->alpha_ss) S->alpha_ss[k] = st[jwg::kStRAlpha];
+        if (S->n_changed) S->n_changed[k] = st[jwg::kStRChanged];
+        const double* fin = host.data() + (size_t)T * jwg::kStRSize + (size_t)k * nsl * 2;
+        double ss = 0.0, sm = 0.0;
+        for (int sl = 0; sl < nsl; ++sl) { ss += fin[2 * sl]; sm += fin[2 * sl + 1]; }       // slices in order
+        if (S->resid_ss) S->resid_ss[k] = ss;
+        if (S->resid_sum) S->resid_sum[k] = sm;
+    }
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_accumulate_r(jwas_hip_ctx* c, double nsamples)
+{
+    if (int rc = need_mega(c)) return rc;
+    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
+    auto& b = c->mg;
+    const int64_t tp = (int64_t)b.nt * c->p;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(jwg::k_mega_accumulate_r, dim3((unsigned)((tp + 255) / 256)), dim3(256), 0, c->stream, (const double*)b.alpha, (const double*)b.delta, tp,
+                       nsamples, b.mean_a, b.mean_a2, b.mean_d);
+    HIPCHK(c, hipGetLastError());
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_psrf(jwas_hip_ctx* c, double nsamples, double* out)
+{
+    if (int rc = need_mega(c)) return rc;
+    auto& b = c->mg;
+    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, b.nt >= 2, JWAS_HIP_EINVAL, "the potential scale reduction factor needs at least 2 chains (the session has %d)", b.nt);
+    NEED(c, std::isfinite(nsamples) && nsamples >= 2.0, JWAS_HIP_EINVAL, "nsamples must be >= 2 (got %g)", nsamples);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!b.psrf)
+        if (int rc = alloc_or_nomem(c, b.mem, &b.psrf, sizeof(double) * (size_t)c->p, "mega-trait session", mega_free)) return rc;
+    const unsigned blocks = (unsigned)std::min<int64_t>(jwg::kPsrfBlocks, (c->p + 255) / 256);
+    hipLaunchKernelGGL(jwg::k_mega_psrf, dim3(blocks), dim3(256), 0, c->stream, (const double*)b.mean_a, (const double*)b.mean_a2, c->p, (int32_t)b.nt, nsamples,
+                       b.psrf);
+    HIPCHK(c, hipGetLastError());
+    return to_host(c, out, b.psrf, sizeof(double) * (size_t)c->p);
 }
 
 int jwas_hip_mega_get_posterior(jwas_hip_ctx* c, int32_t trait, double* mean, double* mean2, double* freq)

@@ -1084,6 +1084,49 @@ class HipEngine:
     def mega_accumulate(self, nsamples):
         self._chk(self._L.jwas_hip_mega_accumulate(self._h, float(nsamples)))
 
+    def mega_sweep_r(self, *, iteration, seed, vare, var_effect, gamma, pi):
+        """One BayesR sweep over all markers of all chains of the session (BayesR.jl:56-96 in double).  vare, var_effect (sigma2):
+        one value per chain; gamma, pi: 4 x T (a vector of 4 serves every chain).  Returns {"class_counts" (4 x T), "ssq", "nnz",
+        "alpha_ss", "resid_ss", "resid_sum", "n_changed"} (T values each) and "step_ms"."""
+        T, _ = self._mega
+        P = _lib.MegaRParams()
+        P.iteration, P.seed = int(iteration), int(seed)
+        keep = []
+        for name, v in (("vare", vare), ("var_effect", var_effect)):
+            a = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            if a.size != T:
+                raise ValueError(f"{name} must hold one value per chain ({T})")
+            keep.append(a)
+            setattr(P, name, a.ctypes.data)
+        for name, v in (("gamma", gamma), ("pi", pi)):
+            a = np.asarray(v, dtype=np.float64)
+            if a.shape == (4,):
+                a = np.repeat(a[:, None], T, axis=1)
+            if a.shape != (4, T):
+                raise ValueError(f"{name} must be 4 values or 4 x {T}")
+            a = np.ascontiguousarray(a)
+            keep.append(a)
+            setattr(P, name, a.ctypes.data)
+        S = _lib.MegaRStats()
+        out = {k: np.zeros(T) for k in ("ssq", "nnz", "alpha_ss", "resid_ss", "resid_sum", "n_changed")}
+        out["class_counts"] = np.zeros((4, T))
+        for k, a in out.items():
+            setattr(S, k, a.ctypes.data)
+        self._chk(self._L.jwas_hip_mega_sweep_r(self._h, C.byref(P), C.byref(S)))
+        out["step_ms"] = S.step_ms
+        return out
+
+    def mega_accumulate_r(self, nsamples):
+        """mega_accumulate for BayesR chains: the model frequency is that of class > 1."""
+        self._chk(self._L.jwas_hip_mega_accumulate_r(self._h, float(nsamples)))
+
+    def mega_psrf(self, nsamples):
+        """The potential scale reduction factor of every marker effect over the session's chains after `nsamples` accumulated
+        samples (p values; NaN where no chain ever had the marker in the model)."""
+        out = np.empty(self.p, dtype=np.float64)
+        self._chk(self._L.jwas_hip_mega_psrf(self._h, float(nsamples), _ptr(out)))
+        return out
+
     def mega_posterior(self, trait):
         """(mean, mean of squares, model frequency) of one trait's effects, p values each."""
         out = [np.empty(self.p, dtype=np.float64) for _ in range(3)]
