@@ -819,6 +819,56 @@ int  jwas_hip_mega_psrf(jwas_hip_ctx* ctx, double nsamples, double* out_p);
 int64_t jwas_hip_mega_estimate_bytes(int64_t n, int64_t p, int32_t ntraits, int32_t block_size);
 int  jwas_hip_mega_end(jwas_hip_ctx* ctx);
 
+/* ---- GBLUP: the genomic relationship matrix and the sampler on pseudo-markers (csrc/gblup.hpp) -------------------------------------
+ * The relationship matrix of the context's dense n x p matrix X (Float32 or Float64, as loaded): with divisor[j] = sqrt(2 p_j (1 - p_j))
+ * in the matrix's element type (the host takes the square root; the device divides, so Z = X ./ divisor is the host's Z bit for bit),
+ *   K = (Z Z' + 1e-5 I) / p      (readgenotypes.jl:406-407; + 1e-5 and / p in the matrix's precision),
+ * n x n values of the element type, row-major and symmetric bit for bit, formed in a device buffer that lives for the call.  Float32:
+ * v_mfma_f32_32x32x2_f32 over fp32 chunks of JWAS_HIP_GRM_CHUNK markers folded into doubles; Float64: v_mfma_f64_16x16x4_f64.
+ * Errors: JWAS_HIP_ESTATE without genotypes; JWAS_HIP_EUNSUP on 2-bit packed storage and on shards; JWAS_HIP_EINVAL for a divisor
+ * that is not positive and finite. */
+#define JWAS_HIP_GRM_CHUNK 64
+int  jwas_hip_grm(jwas_hip_ctx* ctx, const void* divisor_p, void* K_host);
+/* Device bytes of that call beyond the loaded matrix (pure). */
+int64_t jwas_hip_grm_estimate_bytes(int64_t n, int64_t p, int32_t precision_bits);
+/* The sampler (markers/BayesianAlphabet/GBLUP.jl): the context's dense matrix is n x n, column i the i-th eigenvector l_i of the
+ * relationship matrix, D_i > 0 its eigenvalue; pseudo-marker i has the prior variance D_i G.  A step works on the context's own
+ * residual r_k and effects alpha_k (jwas_hip_init_state with T traits, T <= 4), in double with one rounding to the element type
+ * on store, the matrix read once per pass for all traits:
+ *   r+_k = r_k + L alpha_k;   s_ik = l_i' r+_k;   the draw;   r_k = r+_k - L alpha_k.
+ *   diagonal != 0 (one trait, or constraint = true; GBLUP!, megaGBLUP!):  lhs = 1 + vare_kk / (G_kk D_i),
+ *       alpha_ik = s_ik / lhs + z sqrt(vare_kk / lhs)
+ *   diagonal == 0 (MTGBLUP!):  lhs_i = inv(vare) + inv(G) / D_i,  S = inv(lhs_i),  alpha_i = S inv(vare) s_i + chol_lower(S) z_i
+ * Draws: philox4x32_10(pseudo-marker, iteration, 0x03000000, 13 + 16 q) the normal of coefficient q = first_trait + k (both modes).
+ * No sum of trait k depends on T and there are no floating-point atomics: trait k of a diagonal T-trait step is bit-equal to a
+ * one-trait step with first_trait = k, and two runs give the same bits.  beta is set to alpha; delta and the running means are the context's.
+ * Errors: JWAS_HIP_ESTATE without a residual (jwas_hip_init_state) or, after _begin, without an open session or with another number
+ * of traits; JWAS_HIP_EINVAL for p != n, more than 4 traits, a D that is not positive and finite, variances that are not positive
+ * (definite) and finite; JWAS_HIP_EUNSUP with residual weights, 2-bit packed storage or shards.  The session is freed by _end,
+ * jwas_hip_destroy or loading genotypes. */
+typedef struct jwas_gblup_params {
+    uint32_t iteration;                 /* MCMC iteration >= 1 (enters the RNG counter)                                          */
+    int32_t  diagonal;                  /* != 0: trait by trait from the diagonals of vare and G                                 */
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                     */
+    uint32_t first_trait;               /* trait k draws with coefficient q = first_trait + k; first_trait + T <= 4              */
+    uint32_t reserved;
+    double   vare[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];      /* T x T, row-major                                         */
+    double   G[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];         /* T x T the genetic (co)variance                            */
+} jwas_gblup_params;
+typedef struct jwas_gblup_stats {
+    double alpha_ss[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];    /* T x T: sum_i alpha_ik alpha_il / D_i                     */
+    double resid_ss[JWAS_HIP_MAX_TRAITS * JWAS_HIP_MAX_TRAITS];    /* T x T: sum r_k r_l after the step                        */
+    double resid_sum[JWAS_HIP_MAX_TRAITS];                         /* sum r_k                                                  */
+    double step_ms;                     /* device time of the step                                                               */
+} jwas_gblup_stats;
+int  jwas_hip_gblup_begin(jwas_hip_ctx* ctx, const double* D_n);
+int  jwas_hip_gblup_step(jwas_hip_ctx* ctx, const jwas_gblup_params* params, jwas_gblup_stats* stats);
+/* The right-hand sides s of the last step: n x T doubles, row-major. */
+int  jwas_hip_gblup_get_rhs(jwas_hip_ctx* ctx, int64_t nvalues, double* out);
+/* Device bytes of a session (pure; an upper bound). */
+int64_t jwas_hip_gblup_estimate_bytes(int64_t n, int32_t ntraits, int32_t precision_bits);
+int  jwas_hip_gblup_end(jwas_hip_ctx* ctx);
+
 /* ---- single-step analysis: imputing the genotypes of non-genotyped relatives (single_step/SSBR.jl:83-159) --------------------
  * runMCMC(...; single_step_analysis=true, pedigree=ped) orders the pedigree as [non-genotyped; genotyped] (calc_Ai, SSBR.jl:71-79)
  * and imputes, 1000 markers at a time, M_n = A^nn \ (-A^ng M_g) (impute_genotypes, SSBR.jl:83-135); the rows of [M_n; M_g] of the

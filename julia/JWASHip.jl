@@ -670,6 +670,55 @@ hip_mega_estimate_bytes(n::Integer, p::Integer, ntraits::Integer, block_size::In
 hip_mega_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_mega_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
 
 """
+GBLUP (markers/readgenotypes.jl:403-408, markers/BayesianAlphabet/GBLUP.jl; csrc/gblup.hpp).  `hip_grm` returns the relationship
+matrix (Z Z' + 1e-5 I) / p of the loaded dense matrix, Z = X ./ divisor with divisor = sqrt.(2p .* (1 .- p)) in the matrix's element
+type.  After GBLUP_setup has loaded L = eigen(G).vectors as the dense matrix and called jwas_hip_init_state, `hip_gblup_begin!` takes
+D = abs.(eigen(G).values) and `hip_gblup_step!` replaces GBLUP! / megaGBLUP! (diagonal = true) / MTGBLUP! on the resident residual and
+effects; it returns sum_i alpha_i alpha_i' / D_i (the variance draw), sum r r' and sum r.  vare and G are t x t, row-major.
+"""
+struct HipGblupParams
+    iteration::UInt32
+    diagonal::Int32
+    seed::UInt64
+    first_trait::UInt32
+    reserved::UInt32
+    vare::NTuple{16,Float64}
+    G::NTuple{16,Float64}
+end
+struct HipGblupStats
+    alpha_ss::NTuple{16,Float64}
+    resid_ss::NTuple{16,Float64}
+    resid_sum::NTuple{4,Float64}
+    step_ms::Float64
+end
+function hip_grm(b::HipBackend, divisor::Vector{T}, n::Integer) where {T<:Union{Float32,Float64}}
+    K = Matrix{T}(undef, n, n)
+    hip_check(b.ctx, ccall((:jwas_hip_grm, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), b.ctx, divisor, K))
+    return K
+end
+hip_grm_estimate_bytes(n::Integer, p::Integer, bits::Integer=32) =
+    ccall((:jwas_hip_grm_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int32), n, p, bits)
+hip_gblup_begin!(b::HipBackend, D::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_gblup_begin, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.ctx, D))
+function hip_gblup_step!(b::HipBackend, iter::Integer, seed::Integer, vare::Matrix{Float64}, G::Matrix{Float64}; diagonal::Bool=false, first_trait::Integer=0)
+    t = size(vare, 1)
+    pad(M) = ntuple(i -> i <= t * t ? Float64(permutedims(M)[i]) : 0.0, 16)
+    P = HipGblupParams(UInt32(iter), Int32(diagonal || t == 1), UInt64(seed), UInt32(first_trait), UInt32(0), pad(vare), pad(G))
+    S = Ref(HipGblupStats(ntuple(_ -> 0.0, 16), ntuple(_ -> 0.0, 16), ntuple(_ -> 0.0, 4), 0.0))
+    hip_check(b.ctx, ccall((:jwas_hip_gblup_step, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipGblupParams}, Ref{HipGblupStats}), b.ctx, Ref(P), S))
+    sq(v) = permutedims(reshape(collect(v[1:t * t]), t, t))
+    return (alpha_ss = sq(S[].alpha_ss), resid_ss = sq(S[].resid_ss), resid_sum = collect(S[].resid_sum[1:t]), step_ms = S[].step_ms)
+end
+function hip_gblup_rhs(b::HipBackend, n::Integer, t::Integer)
+    out = Matrix{Float64}(undef, t, n)                       # (row-major n x t on the C side)
+    hip_check(b.ctx, ccall((:jwas_hip_gblup_get_rhs, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), b.ctx, length(out), out))
+    return permutedims(out)
+end
+hip_gblup_estimate_bytes(n::Integer, ntraits::Integer, bits::Integer=32) =
+    ccall((:jwas_hip_gblup_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int32, Int32), n, ntraits, bits)
+hip_gblup_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_gblup_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
+"""
 Single-step analysis (single_step/SSBR.jl:83-159): the imputation M_n = A^nn \\ (-A^ng M_g) on the device.  `hip_ss_begin!` takes the
 factors of A^nn as CSR with 0-based int32 columns ascending within a row (L with its unit diagonal last, U with its diagonal first),
 the permutations of Pr A^nn Pc = L U (0-based) and A^ng as CSR; it returns the markers per chunk the byte budget pays for.

@@ -21,7 +21,8 @@ ANNOT_BAYESC, ANNOT_BAYESR, ANNOT_TREE = 0, 1, 2
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
 RRM_MIN_COEFF, RRM_MAX_COEFF, RRM_MAX_TIMES, RRM_MAX_BLOCK = 2, 4, 64, 256      # csrc/rrm.hpp
 MEGA_MAX_TRAITS, MEGA_MAX_BLOCK, MEGA_TRAIT_TILE = 64, 256, 8                   # csrc/mega.hpp (JWAS_HIP_MEGA_MAX_TRAITS, _MAX_BLOCK, kTT)
-SS_CHUNK_GRANULE, SS_MAX_CHUNK = 64, 65536                                      # csrc/ssbr.hpp (kChunkGranule, kMaxChunk)
+GRM_CHUNK = 64                          # markers per fp32 accumulation chunk of jwas_hip_grm (JWAS_HIP_GRM_CHUNK, csrc/gblup.hpp kGrmChunk)
+SS_CHUNK_GRANULE, SS_MAX_CHUNK = 64, 65536                                     # csrc/ssbr.hpp (kChunkGranule, kMaxChunk)
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
 STORAGE_DENSE_F32, STORAGE_PACKED2BIT = 0, 1
 # enum jwas_hip_schedule_flags (jwas_hip_last_sweep_schedule): name -> bit
@@ -123,6 +124,15 @@ class MegaParams(C.Structure):
 class MegaStats(C.Structure):
     _fields_ = [("sum_delta", C.c_void_p), ("beta_ss", C.c_void_p), ("alpha_ss", C.c_void_p), ("resid_ss", C.c_void_p), ("resid_sum", C.c_void_p),
                 ("n_changed", C.c_void_p), ("step_ms", C.c_double)]
+
+
+class GblupParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("diagonal", C.c_int32), ("seed", C.c_uint64), ("first_trait", C.c_uint32), ("reserved", C.c_uint32),
+                ("vare", C.c_double * 16), ("G", C.c_double * 16)]
+
+
+class GblupStats(C.Structure):
+    _fields_ = [("alpha_ss", C.c_double * 16), ("resid_ss", C.c_double * 16), ("resid_sum", C.c_double * 4), ("step_ms", C.c_double)]
 
 
 class MegaRParams(C.Structure):
@@ -312,6 +322,13 @@ PROTOTYPES = {
     "jwas_hip_mega_get_gram": (_INT, [_vp, _i64, _i64, _vp, _vp]),
     "jwas_hip_mega_estimate_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "jwas_hip_mega_end": (_INT, [_vp]),
+    "jwas_hip_grm": (_INT, [_vp, _vp, _vp]),
+    "jwas_hip_grm_estimate_bytes": (_i64, [_i64, _i64, _i32]),
+    "jwas_hip_gblup_begin": (_INT, [_vp, _vp]),
+    "jwas_hip_gblup_step": (_INT, [_vp, _P(GblupParams), _P(GblupStats)]),
+    "jwas_hip_gblup_get_rhs": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_gblup_estimate_bytes": (_i64, [_i64, _i32, _i32]),
+    "jwas_hip_gblup_end": (_INT, [_vp]),
     "jwas_hip_ss_begin": (_INT, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "jwas_hip_ss_set_rows": (_INT, [_vp, _i32, _i64, _vp]),
     "jwas_hip_ss_impute": (_INT, [_vp, _i64, _i64, _vp, _i64]),

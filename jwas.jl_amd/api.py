@@ -9,8 +9,9 @@ Same names, argument meaning and error behaviour as reworkhow/JWAS.jl v2.3.6 (fi
     runMCMC         JWAS.jl:161-511  -> MCMC/MCMC_BayesianAlphabet.jl
 Everything that is NOT the marker sweep stays here on the host (numpy): data ingestion and QC,
 model parsing, fixed-effect Gibbs, variance-component and pi draws, output tables.  Model families
-outside the hot path (GBLUP, prediction equations) are rejected with an
-explicit error: they stay on the reference.  Single-step analyses (single_step_analysis=True with a pedigree) have a driver of their own
+outside the hot path (prediction equations) are rejected with an
+explicit error: they stay on the reference.  GBLUP runs from a relationship matrix (genomic_relationship_matrix forms it on the device,
+get_genotypes(K, G, method="GBLUP") takes it; gblup.py, csrc/gblup.hpp).  Single-step analyses (single_step_analysis=True with a pedigree) have a driver of their own
 (ssbr.py: the imputation on the device, csrc/ssbr.hpp, then this chain with the terms J and ϵ).  Models with several genotype categories (y = intercept + geno1 + geno2) have a driver of
 their own (multigeno.py: one device context per category, the residual handed over between them).  Random regression models (RRM=Phi) have a driver of their own (rrm.py, csrc/rrm.hpp).  i.i.d. random effects (set_random) and large class factors run on the device
 (mcmc.py step 1, csrc/locpar.hpp).  Categorical / censored traits run here: their liabilities are sampled
@@ -114,11 +115,57 @@ def get_genotypes(file, G=False, *, method="BayesC", Pi=0.0, estimatePi=True,
                 raise ValueError("length of starting values is wrong.")
             g.alpha = sv
         return g
-    if method not in SUPPORTED_METHODS:
+    if method != "GBLUP" and method not in SUPPORTED_METHODS:
         raise NotImplementedError(f"method {method} is not on the device path (supported: {SUPPORTED_METHODS}); "
                                   "GBLUP / RR-BLUP / BayesL stay on the reference")
 
     data_type = np.float64 if double_precision else np.float32           # readgenotypes.jl:298: Float64 genotypes on request
+    obsID, markerID, genotypes = _read_genotype_table(file, separator, header, data_type)
+    if method == "GBLUP":                                                                     # :352-366
+        from . import gblup as _gb
+        if not _gb.is_relationship_matrix(genotypes):
+            raise NotImplementedError(f"method GBLUP is not on the device path (supported: {SUPPORTED_METHODS}) for a genotype covariate "
+                                      "matrix: form the relationship matrix with genomic_relationship_matrix(...) and pass it")
+        return _gb.relationship_genotypes(Genotypes, Variance, obsID, genotypes, G, G_is_marker_variance=G_is_marker_variance, df=df,
+                                          estimate_variance=estimate_variance, estimate_scale=estimate_scale, constraint=constraint,
+                                          starting_value=starting_value, Pi=Pi, estimatePi=estimatePi)
+
+    nObs, nMarkers = genotypes.shape
+    from . import annotations as _ann
+    annotation_matrix = _ann.validate_annotations_input(annotations, nMarkers, method)       # :56-70, one row per RAW marker
+    if annotation_matrix is not False and estimatePi is False:                                # :152-158
+        print(f"estimatePi=false is ignored when annotations are provided; Annotated {method} requires estimatePi=true.")
+        estimatePi = True
+    genotypes, markerID, p, sum2pq, annotation_matrix = _impute_center_qc(genotypes, markerID, data_type, quality_control, MAF, missing_value, center,
+                                                                          annotation_matrix)
+    nObs, nMarkers = genotypes.shape
+
+    g = Genotypes(obsID, markerID, nObs, nMarkers, p, sum2pq, center, genotypes)
+    g.G = Variance(G if G_is_marker_variance else False, df, False, estimate_variance, estimate_scale, constraint)   # :424
+    g.genetic_variance = Variance(False if G_is_marker_variance else G, df, False, estimate_variance, estimate_scale, constraint)
+    g.method, g.estimatePi, g.pi = method, estimatePi, Pi
+    g.multi_trait_sampler = multi_trait_sampler
+    if annotation_matrix is not False:                                                        # :111-150
+        if method == "BayesC" and not isinstance(Pi, dict):
+            if np.ndim(Pi) == 1:
+                if len(Pi) != nMarkers:
+                    raise ValueError(f"Annotated BayesC starting Pi vector length {len(Pi)} must match the number of markers ({nMarkers}).")
+                g.pi = np.array(Pi, dtype=np.float64)
+            else:
+                g.pi = np.full(nMarkers, float(Pi))
+        g.annotations = _ann.build_marker_annotations(annotation_matrix, method, Pi)
+    print("Genotype informatin:")
+    print(f"#markers: {nMarkers}; #individuals: {nObs}")
+    if not _is_false(starting_value):                                                         # :438-446
+        sv = np.asarray(starting_value, dtype=data_type).reshape(-1)
+        if sv.size % nMarkers != 0:
+            raise ValueError("length of starting values is wrong.")
+        g.alpha = sv
+    return g
+
+
+def _read_genotype_table(file, separator, header, data_type):
+    """(obsID, markerID, genotypes) of a delimited text file, a DataFrame or a 2-D array (readgenotypes.jl:300-348)."""
     try:
         import pandas as pd
     except ImportError:                                              # pragma: no cover
@@ -145,12 +192,13 @@ def get_genotypes(file, G=False, *, method="BayesC", Pi=0.0, estimatePi=True,
     else:
         raise TypeError("The data type is not supported.")                                    # :346-348
 
+    return obsID, markerID, genotypes
+
+
+def _impute_center_qc(genotypes, markerID, data_type, quality_control, MAF, missing_value, center, annotation_matrix=False):
+    """The host steps between reading and the Genotypes object (readgenotypes.jl:372-401): missing values to column means, centring,
+    allele frequencies, the MAF / fixed-locus filter.  Returns (genotypes, markerID, p, sum2pq, annotation_matrix)."""
     nObs, nMarkers = genotypes.shape
-    from . import annotations as _ann
-    annotation_matrix = _ann.validate_annotations_input(annotations, nMarkers, method)       # :56-70, one row per RAW marker
-    if annotation_matrix is not False and estimatePi is False:                                # :152-158
-        print(f"estimatePi=false is ignored when annotations are provided; Annotated {method} requires estimatePi=true.")
-        estimatePi = True
     if quality_control:                                                                       # :372-382
         mv = data_type(missing_value)
         for j in range(nMarkers):
@@ -174,31 +222,41 @@ def get_genotypes(file, G=False, *, method="BayesC", Pi=0.0, estimatePi=True,
         if annotation_matrix is not False:
             annotation_matrix = annotation_matrix[select, :]
         print(f"{int((~select).sum())} loci which are fixed or have minor allele frequency < {MAF} are removed.")
-    nObs, nMarkers = genotypes.shape
     sum2pq = float((2.0 * p.astype(data_type) * (1.0 - p.astype(data_type))).sum(dtype=data_type))   # :401
+    return genotypes, markerID, p, sum2pq, annotation_matrix
 
-    g = Genotypes(obsID, markerID, nObs, nMarkers, p, sum2pq, center, genotypes)
-    g.G = Variance(G if G_is_marker_variance else False, df, False, estimate_variance, estimate_scale, constraint)   # :424
-    g.genetic_variance = Variance(False if G_is_marker_variance else G, df, False, estimate_variance, estimate_scale, constraint)
-    g.method, g.estimatePi, g.pi = method, estimatePi, Pi
-    g.multi_trait_sampler = multi_trait_sampler
-    if annotation_matrix is not False:                                                        # :111-150
-        if method == "BayesC" and not isinstance(Pi, dict):
-            if np.ndim(Pi) == 1:
-                if len(Pi) != nMarkers:
-                    raise ValueError(f"Annotated BayesC starting Pi vector length {len(Pi)} must match the number of markers ({nMarkers}).")
-                g.pi = np.array(Pi, dtype=np.float64)
-            else:
-                g.pi = np.full(nMarkers, float(Pi))
-        g.annotations = _ann.build_marker_annotations(annotation_matrix, method, Pi)
-    print("Genotype informatin:")
-    print(f"#markers: {nMarkers}; #individuals: {nObs}")
-    if not _is_false(starting_value):                                                         # :438-446
-        sv = np.asarray(starting_value, dtype=data_type).reshape(-1)
-        if sv.size % nMarkers != 0:
-            raise ValueError("length of starting values is wrong.")
-        g.alpha = sv
-    return g
+
+def genomic_relationship_matrix(file, *, separator=",", header=True, center=True, quality_control=True, MAF=0.01, missing_value=9.0,
+                                double_precision=False, device=0, _engine=None):
+    """The genomic relationship matrix of a genotype covariate matrix, formed on the device (readgenotypes.jl:403-408):
+    K = (Z Z' + 1e-5 I) / nMarkers with Z = genotypes ./ sqrt(2 p (1 - p)) after get_genotypes' host steps (missing values, centring,
+    the MAF filter).  `file` as in get_genotypes.  Returns a DataFrame with an ID column and one column per individual: what
+    get_genotypes(K, G, method="GBLUP") takes.  `_engine` (private) lets the test-suite inject an engine."""
+    import pandas as pd
+    data_type = np.float64 if double_precision else np.float32
+    obsID, markerID, genotypes = _read_genotype_table(file, separator, header, data_type)
+    genotypes, markerID, p, _, _ = _impute_center_qc(genotypes, markerID, data_type, quality_control, MAF, missing_value, center)
+    if genotypes.shape[1] == 0:
+        raise ValueError("no marker is left after quality control")
+    divisor = np.sqrt(data_type(2.0) * p * (data_type(1.0) - p)).astype(data_type)
+    if not np.all(np.isfinite(divisor) & (divisor > 0)):
+        raise ValueError("genomic_relationship_matrix needs 0 < p < 1 for every marker (a fixed locus has 2p(1-p) = 0); use quality_control=True")
+    own = _engine is None
+    engine = _engine
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(device, precision=64 if double_precision else 32)
+    if not hasattr(engine, "grm"):
+        raise NotImplementedError("genomic_relationship_matrix needs an engine with grm; the package has no CPU fallback")
+    try:
+        engine.load_dense(np.asfortranarray(genotypes, dtype=data_type))
+        K = engine.grm(divisor)
+    finally:
+        if own:
+            engine.close()
+    out = pd.DataFrame(K, columns=[str(i) for i in obsID])
+    out.insert(0, "ID", [str(i) for i in obsID])
+    return out
 
 
 def device_genotypes(engine, G=False, *, method="BayesC", Pi=0.0, estimatePi=True, G_is_marker_variance=False, df=4.0,
@@ -493,7 +551,7 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
             output_samples_for_all_parameters=False,
             # device options (the analogue of storage=:stream's opt-in knobs)
             device=0, block_size=None, gram_mode="mfma", blocks_per_launch=None, location_parameters="auto",
-            annotation_priors="host", fitting_J_vector=True, chains=1, first_chain=0, bayesr_gamma=None, _engine=None):
+            annotation_priors="host", fitting_J_vector=True, chains=1, first_chain=0, bayesr_gamma=None, gblup_eigen="auto", _engine=None):
     """JWAS.jl:161-511.  Returns the reference's output Dict (output.jl:108-212) as a dict of pandas
     DataFrames and writes the same text files under `output_folder`.
 
@@ -609,6 +667,18 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     location_parameters="device", several traits or categories) raises NotImplementedError naming the argument before anything
     is written.  Against K sequential runs: NOTES.md, "Several chains in one session".
 
+    GBLUP (get_genotypes(K, G, method="GBLUP") with K a relationship matrix, e.g. from genomic_relationship_matrix; GBLUP.jl, gblup.py,
+    csrc/gblup.hpp): the sampler on pseudo-markers inside this chain -- K aligned to the records and eigendecomposed (gblup_eigen="auto" |
+    "host" | "device": numpy.linalg.eigh in the run's precision, or torch.linalg.eigh on the GPU in a child process, solved in Float64;
+    "auto" takes the device from 8 192 records when it is usable), the eigenvectors resident on the device, per iteration three passes
+    over them for all traits.  One trait, 2 to 4 traits jointly or with constraint=true (complete records), Float32 or
+    double_precision=True (as in get_genotypes), location parameters on host or device, i.i.d. set_random effects, outputEBV(model,
+    IDs) within K's IDs.  Outputs as RR-BLUP with the pseudo-markers "1" ... "n"; the variance samples go to
+    MCMC_samples_genetic_variance(REML)_<genotypes>.txt.  Raises before anything is written: single_step_analysis ("SSGBLUP is not
+    available"), G given as marker variance, fast_blocks, independent_blocks, heterogeneous_residuals, annotations, categorical /
+    censored traits, causal_structure, RRM, chains, several genotype categories, records that miss some traits, pedigree random effects,
+    shards, device_genotypes, an engine without the gblup_* methods.
+
     double_precision=True (JWAS.jl:349-366): genotypes, residual, effects and the samplers' arithmetic all Float64 -- a
     Float64 device context (jwas_hip_set_precision; csrc/f64_path.hpp): single-trait BayesA/B/C, RR-BLUP, BayesL, BayesR,
     multi-trait BayesC and BayesA/B under sampler I and II and marker-specific joint priors on dense storage; any fast_blocks
@@ -619,6 +689,13 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
         raise ValueError("independent_blocks=true requires fast_blocks != false.")             # :242-244
     from . import rrm as _rrm
     from . import megatrait as _mt
+    from . import gblup as _gb
+    if _gb.routes(model):                     # GBLUP: mcmc.run_chain with the pseudo-marker step (gblup.py), validated before anything is written
+        _gb.validate(model, df, single_step_analysis=single_step_analysis, fast_blocks=fast_blocks, independent_blocks=independent_blocks,
+                     heterogeneous_residuals=heterogeneous_residuals, causal_structure=causal_structure, RRM=RRM, chains=chains,
+                     engine=_engine, gblup_eigen=gblup_eigen, double_precision=bool(double_precision))
+    elif gblup_eigen not in ("auto", "host", "device"):
+        raise ValueError('gblup_eigen must be "auto", "host" or "device".')
     if not (isinstance(chains, (int, np.integer)) and not isinstance(chains, bool) and int(chains) == 1):
         from . import chains as _ch             # several chains of one model: a driver of its own (chains.py), validated before anything is written
         nchains = _ch.check_chains(chains)
@@ -778,4 +855,4 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
                      memory_guard=memory_guard, memory_guard_ratio=memory_guard_ratio,
                      missing_phenotypes=missing_phenotypes, device=device, block_size=block_size,
                      gram_mode=gram_mode, blocks_per_launch=blocks_per_launch, location_parameters=location_parameters, annotation_priors=annotation_priors, causal_structure=causal_structure, engine=_engine, printout_model_info=printout_model_info,
-                     output_samples_for_all_parameters=output_samples_for_all_parameters)
+                     output_samples_for_all_parameters=output_samples_for_all_parameters, gblup_eigen=gblup_eigen)

@@ -339,6 +339,20 @@ struct jwas_hip_ctx {
         int32_t* prow[2] = {};                              // the rows of [M_n; M_g] behind the rows of target 0 (sweep matrix), 1 (output)
         int64_t nrows[2] = {};                              // (0: the target is not set)
     } ss;
+    // GBLUP (jwas_hip_gblup_begin .. _end; markers/BayesianAlphabet/GBLUP.jl; csrc/gblup.hpp): the context's dense n x n matrix holds the
+    // eigenvectors of the relationship matrix; a step runs on the context's own residual and effects
+    struct Gblup {
+        bool active = false;
+        int nt = 0, nparts = 0, len = 0, nwg = 0;           // traits; column parts of a pass and their length; workgroups of the sampler
+        const void* mat = nullptr;                          // the matrix the session was begun on
+        DevOwner mem;
+        double* D = nullptr;                                // [n] eigenvalues
+        void* rplus = nullptr;                              // [nt][ld] r + L alpha, the context's element type
+        double* s = nullptr;                                // [n][nt] the right-hand sides of the last step
+        double* part = nullptr;                             // [nparts][nt][ld] column-part sums of L alpha
+        double* par = nullptr;                              // [kParSize] the parameters of the running step
+        double* stat = nullptr;                             // [nwg][nt nt] | [nslices][nt nt + nt]
+    } gb;
 };
 
 // ---- errors ------------------------------------------------------------------------------------------------------------------------
@@ -398,6 +412,7 @@ JW_LOCAL void sem_free(jwas_hip_ctx* c);
 JW_LOCAL void rrm_free(jwas_hip_ctx* c);
 JW_LOCAL void mega_free(jwas_hip_ctx* c);
 JW_LOCAL void ss_free(jwas_hip_ctx* c);
+JW_LOCAL void gblup_free(jwas_hip_ctx* c);
 
 // `words` ("liabilities", "annotation priors", ...) are not driven from a context that holds a marker or row shard
 static inline int refuse_shards(jwas_hip_ctx* c, const char* words)

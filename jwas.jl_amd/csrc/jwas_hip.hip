@@ -129,6 +129,7 @@ static void free_storage(jwas_hip_ctx* c)
     sem_free(c);                        // (the phenotypes belong to the records, the accumulators to the markers of this matrix)
     rrm_free(c);                        // (its Grams, masks and state are those of this matrix)
     mega_free(c);                       // (likewise)
+    gblup_free(c);                      // (its matrix is the eigenvector matrix that goes)
     annot_free(c);                      // (the prior table below belongs to the markers of this matrix)
     mtmiss_free(c);                     // (the codes describe the records of this matrix)
     gwas_free(c);                       // (a session is bound to the matrix it was begun on)
@@ -2702,6 +2703,7 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     mtmiss_free(c);
     rrm_free(c);
     mega_free(c);
+    gblup_free(c);
     for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->w, (void*)F->ev_all}) (void)hipFree(q);
     F->X = F->r = F->xpx = F->gram = F->partials = F->w = nullptr; F->ev = F->ev_all = nullptr; F->dparams = nullptr;
     F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0; F->weighted = false;

@@ -35,6 +35,10 @@
 //           no higher bit: it is no other stream's repetition word (small counts below 2^24, 0x02000000, 0x04000000 | trait,
 //           0x08000000 | step, 0x10000000, 0x20000000 | term, 0x40000000 | round, 0x80000000 | ...), and no other stream uses
 //           slots 10, 11 and 12 (the others' are 0 .. 4 + 16 trait, 5 .. 8, 9 + 16 q, and 64 upwards for the Wishart draws).
+//   slot 13: the GBLUP sampler (gblup.hpp).  (PSEUDO-MARKER, iteration, 0x03000000, 13 + 16 q) the normal of coefficient q < 4 (Box-Muller
+//           as slot 1): slots 13, 29, 45, 61.  The word 0x03000000 is no other stream's repetition word (the mega-trait sweep owns
+//           0x01000000 | id with id < 2^24, which stops at 0x01FFFFFF; the random-regression sweep owns exactly 0x02000000), and no
+//           other stream uses slot 13 + 16 q.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1215,6 +1215,59 @@ class HipEngine:
         self._chk(self._L.jwas_hip_ss_end(self._h))
         self._ss = None
 
+    # -- GBLUP: the relationship matrix and the sampler on pseudo-markers (jwas_hip_grm, jwas_hip_gblup_*; csrc/gblup.hpp) --------
+    GRM_CHUNK = _lib.GRM_CHUNK          # markers per fp32 accumulation chunk of grm() in a Float32 context
+
+    @staticmethod
+    def grm_estimate_bytes(n, p, precision=32):
+        return _lib.load().jwas_hip_grm_estimate_bytes(int(n), int(p), int(precision))
+
+    def grm(self, divisor):
+        """K = (Z Z' + 1e-5 I) / p with Z = X ./ divisor of the loaded dense matrix (readgenotypes.jl:406-407): n x n in the engine's
+        dtype, symmetric bit for bit.  divisor: p values, sqrt(2 p_j (1 - p_j)) in the engine's dtype."""
+        d = np.ascontiguousarray(divisor, dtype=self.dtype)
+        if d.shape != (self.p,):
+            raise ValueError(f"divisor must have length {self.p}")
+        K = np.empty((self.n, self.n), dtype=self.dtype)
+        self._chk(self._L.jwas_hip_grm(self._h, _ptr(d), _ptr(K)))
+        return K
+
+    @staticmethod
+    def gblup_estimate_bytes(n, ntraits=1, precision=32):
+        return _lib.load().jwas_hip_gblup_estimate_bytes(int(n), int(ntraits), int(precision))
+
+    def gblup_begin(self, D):
+        """Open a GBLUP session on the loaded n x n matrix of eigenvectors (column i the i-th) with the eigenvalues D > 0; the
+        residual and the effects are the context's (init_state first)."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        if D.shape != (self.p,):
+            raise ValueError(f"D must have length {self.p}")
+        self._chk(self._L.jwas_hip_gblup_begin(self._h, _ptr(D)))
+
+    def gblup_step(self, *, iteration, seed, vare, G, diagonal=False, first_trait=0):
+        """One step of GBLUP! / megaGBLUP! (diagonal) / MTGBLUP! on the resident residual and effects.  vare, G: T x T (scalars for one
+        trait); trait k draws the normals of coefficient first_trait + k.  Returns {"alpha_ss": sum_i alpha_i alpha_i' / D_i, "resid_ss", "resid_sum", "step_ms"}."""
+        T = self.ntraits
+        P, S = _lib.GblupParams(), _lib.GblupStats()
+        P.iteration, P.seed, P.diagonal, P.first_trait = int(iteration), int(seed), int(bool(diagonal) or T == 1), int(first_trait)
+        for name, v in (("vare", vare), ("G", G)):
+            a = np.asarray(v, dtype=np.float64).reshape(-1)
+            if a.size != T * T:
+                raise ValueError(f"{name} must be {T} x {T}")
+            getattr(P, name)[:T * T] = a.tolist()
+        self._chk(self._L.jwas_hip_gblup_step(self._h, C.byref(P), C.byref(S)))
+        return {"alpha_ss": np.array(S.alpha_ss[:T * T]).reshape(T, T), "resid_ss": np.array(S.resid_ss[:T * T]).reshape(T, T),
+                "resid_sum": np.array(S.resid_sum[:T]), "step_ms": S.step_ms}
+
+    def gblup_rhs(self):
+        """The right-hand sides s_ik = l_i'(r_k + L alpha_k) of the last step: n x T doubles."""
+        out = np.empty((self.n, self.ntraits), dtype=np.float64)
+        self._chk(self._L.jwas_hip_gblup_get_rhs(self._h, out.size, _ptr(out)))
+        return out
+
+    def gblup_end(self):
+        self._chk(self._L.jwas_hip_gblup_end(self._h))
+
     def mul_alpha_output(self, trait=0):
         """EBV = output_genotypes * alpha (output.jl:281-306)."""
         out = np.empty(getattr(self, "n_out", 0), dtype=self.dtype)

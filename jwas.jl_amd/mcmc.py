@@ -409,7 +409,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
               fast_blocks, independent_blocks=False, heterogeneous_residuals=False, outputEBV, output_heritability=True, output_folder, printout_frequency, memory_guard, memory_guard_ratio,
               missing_phenotypes, device, block_size, gram_mode, engine, printout_model_info,
               output_samples_for_all_parameters, double_precision=False, blocks_per_launch=None, location_parameters="auto",
-              annotation_priors="host", causal_structure=False, single_step=None):
+              annotation_priors="host", causal_structure=False, single_step=None, gblup_eigen="auto"):
     """single_step: ssbr.SingleStep (None: not a single-step analysis) -- the imputed matrices are resident on the engine, the output IDs
     and the J / ϵ parts of the EBVs come from it (ssbr.py)."""
     Mi = model.M[0]
@@ -422,7 +422,10 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     if not double_precision and getattr(Mi, "genotypes", None) is not None and getattr(Mi.genotypes, "dtype", None) == np.float64:
         raise NotImplementedError("Float64 genotypes (get_genotypes(double_precision=true)) run with runMCMC(double_precision=true); "
                                   "the mixed Float64 / Float32 chain stays on the reference")
-    if t > 1 and method not in ("BayesC", "RR-BLUP", "BayesB", "BayesA"):
+    gblup = method == "GBLUP"                                           # the sampler on pseudo-markers (GBLUP.jl; gblup.py, csrc/gblup.hpp)
+    if gblup:
+        from . import gblup as _gb
+    if t > 1 and method not in ("BayesC", "RR-BLUP", "BayesB", "BayesA", "GBLUP"):
         raise NotImplementedError("multi-trait device path implements BayesC (Gibbs samplers I, II and the constraint=true "
                                   "megaBayesABC! path) and BayesA/B (the same three); other methods stay on the reference")
     mega = t > 1 and bool(Mi.G.constraint)                              # megaBayesABC! (MCMC_BayesianAlphabet.jl:233-234)
@@ -523,8 +526,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         if len(ph) == 0:
             raise ValueError("no individual has both phenotypes and genotypes")
         rows = np.array([geno_index[i] for i in ph[idcol]], dtype=np.int64)
-        X = Mi.genotypes if (len(rows) == Mi.nObs and np.array_equal(rows, np.arange(Mi.nObs))) else np.asfortranarray(Mi.genotypes[rows, :])
-        n, p = X.shape
+        X = None if gblup else Mi.genotypes if (len(rows) == Mi.nObs and np.array_equal(rows, np.arange(Mi.nObs))) else np.asfortranarray(Mi.genotypes[rows, :])
+        n, p = (len(rows), len(rows)) if gblup else X.shape            # (GBLUP: nMarkers = nObs; the eigenvectors come below)
     # ---- individuals EBVs are reported for (check_outputID, input_data_validation.jl:143-196): all genotyped
     # individuals unless outputEBV(model, IDs) named a list; IDs without genotypes are dropped with the reference's note
     out_ids, out_rows, out_same = None, None, True
@@ -542,6 +545,11 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         # rows of Mi.genotypes behind Mi.output_genotypes (tools4genotypes.jl:290-296); GWAS() reads them (GWAS.jl:148)
         Mi.output_rows = out_rows if (outputEBV and not out_same) else rows
     write_id_files(output_folder, ph[idcol], Mi.obsID)
+    if gblup:
+        # GBLUP_setup (GBLUP.jl:9-31) in place of the block set-up: K aligned to the records, K = L D L', the pseudo-markers' names,
+        # the output matrix K[out, records] L diag(1 / D); X = L is what goes to the device
+        gb = _gb.prepare(Mi, rows, out_rows if (outputEBV and not out_same) else None, ftype, gblup_eigen=gblup_eigen, device=device)
+        X = gb.L
     liab_codes, liab_bounds = {}, {}
     if has_liab:                                                          # input_data_validation.jl:255-290
         for k, tr in enumerate(model.lhsVec):
@@ -668,6 +676,15 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         # the device's BayesC update with pi = 0 (every marker included) is RR-BLUP's full conditional (api.SUPPORTED_METHODS)
         method, Mi.estimatePi = "BayesC", False
         pi = 0.0 if t == 1 else np.eye(1, 1 << t, (1 << t) - 1).ravel()
+    if gblup:                                                          # input_data_validation.jl:24-31; tools4genotypes.jl:409-410
+        if not (np.isscalar(Mi.pi) and (Mi.pi is False or Mi.pi == 0.0)):
+            print("GBLUP runs with π = false.")
+        elif Mi.estimatePi:
+            print("GBLUP runs with estimatePi = false.")
+        # every pseudo-marker is in the model: the state, the running means and the outputs are RR-BLUP's (the device's BayesC state)
+        method, Mi.estimatePi = "BayesC", False
+        pi = 0.0 if t == 1 else np.eye(1, 1 << t, (1 << t) - 1).ravel()
+        Mi.G.val = np.float64(Mi.genetic_variance.val) if t == 1 else np.asarray(Mi.genetic_variance.val, dtype=np.float64)
     if t == 2 and getattr(Mi, "annotations", False) is not False and not mega:
         # start-row validation of the annotated 2-trait model comes first (finalize_marker_annotation_setup!,
         # annotation_setup.jl:101-121, runs at build_model time in the reference)
@@ -882,7 +899,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         # size x traits <= 2048
         if stream or (devres and single_step is None):      # (a single-step run imputes into a Float64 context's own matrix: ssbr.py)
             raise NotImplementedError("double_precision=true needs dense host genotypes (the streaming backend is Float32 only, readgenotypes.jl:246-248)")
-        if mega:
+        if mega and not gblup:
             raise NotImplementedError("double_precision=true runs every sampler on the device except constraint=true (megaBayesABC), "
                                       "which stays on the reference in Float64 mode")
         if fast_blocks is not False:
@@ -900,6 +917,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
         adaptive_mt = False
         adaptive_mts = False
         mt_1024 = False
+
+    if gblup:                                  # no blocks: nothing of the block policies applies
+        adaptive = adaptive_mt = adaptive_mts = mt_1024 = section_solve = False
 
     # grouped launches (engine.setup_groups): the adaptive policy's 1024-marker sweeps of a single-trait chain (dense or 2-bit packed
     # storage), when the chain is long enough to pay for the group cross-Grams; an explicitly partitioned / row-sharded run keeps
@@ -1004,6 +1024,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             need += HipEngine.annot_estimate_bytes(p, ann.design_matrix.shape[1], ann_kind)
         if sem:                                                    # the phenotypes, the indirect / overall accumulators (jwas_hip_sem_estimate_bytes)
             need += HipEngine.sem_estimate_bytes(n, p, t)
+        if gblup:                                                  # r + L alpha, the right-hand sides, the column-part sums (jwas_hip_gblup_estimate_bytes)
+            need += HipEngine.gblup_estimate_bytes(n, t, 64 if double_precision else 32)
         if outputEBV and not out_same:                             # Mi.output_genotypes: a second dense matrix (n_out x p)
             need += (8 if double_precision else 4) * ((len(out_rows) + 255) // 256 * 256) * p
         engine = HipEngine(device, precision=64 if double_precision else 32)
@@ -1024,16 +1046,18 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     X_out_host = None
     if outputEBV and not out_same and single_step is None:      # Mi.output_genotypes = Z_out * genotypes (tools4genotypes.jl:290-296)
         if double_precision and not (hasattr(engine, "load_output_dense") and hasattr(engine, "mul_alpha_output")):
-            X_out_host = np.asarray(Mi.genotypes[out_rows, :], dtype=np.float64)      # (an injected engine without output rows: the host forms the product)
+            X_out_host = np.asarray(gb.Xout if gblup else Mi.genotypes[out_rows, :], dtype=np.float64)      # (an injected engine without output rows: the host forms the product)
         else:                                  # a second resident matrix, Float64 in a Float64 run (JWAS.jl:353)
-            Xo = Mi.genotypes[out_rows, :]
+            Xo = gb.Xout if gblup else Mi.genotypes[out_rows, :]
             engine.load_output_dense(np.asfortranarray(Xo, dtype=np.float64) if double_precision else np.asfortranarray(Xo))
     # A device-resident engine may come from an earlier run: its weights, Grams and block partition must be THIS run's.
     # set_weights(None) restores unit weights (and drops the resident Grams, which were X_b'R^-1 X_b); an explicit
     # partition left by the previous run is rebuilt as uniform blocks below.
     if invw is not None or getattr(engine, "_weighted", False):
         engine.set_weights(invw)               # x'R^-1 x, X_b'R^-1 X_b, X_b'R^-1 r on the device (GibbsMats with Rinv)
-    if explicit_partition is not None:
+    if gblup:
+        pass                                   # (no Grams: the session opens below, once the state exists)
+    elif explicit_partition is not None:
         engine.setup_blocks_explicit(explicit_partition, gram_mode)
     elif devres and invw is None and engine.block_size and getattr(engine, "_explicit_starts", None) is None:
         resident = set(engine.resident_block_sizes())
@@ -1069,7 +1093,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             print(f"NOTICE: ping-pong pairs not set up ({ex}); the 512-marker sweeps run one block per launch.")
             pair_m = 0
         engine.select_block_size(cur_bs)
-    engine.init_state(mt_method if t > 1 else method, t)
+    engine.init_state(("MTBayesC" if gblup else mt_method) if t > 1 else method, t)
+    if gblup:
+        engine.gblup_begin(gb.D)
 
     # ---- location parameters: the terms go to the device (csrc/locpar.hpp) or the host builds its dense design matrices
     if lp_device:
@@ -1199,7 +1225,7 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     t_sweep = 0.0
     iter_end = []                                # perf_counter at the end of every iteration (each ends synchronised with the device)
     # an exception inside the chain: the open sessions go with the files
-    ends = ([engine.sem_end] if sem_open else []) + ([engine.annot_end] if ann_open else [])
+    ends = ([engine.sem_end] if sem_open else []) + ([engine.annot_end] if ann_open else []) + ([engine.gblup_end] if gblup else [])
     t0 = time.time()
     # ================================ the chain =================================================
     with host_blas_limit(), files, _on_error(*ends):
@@ -1323,7 +1349,10 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 kw.update(var_effect=Gval, pi=pi)
             if (group_m or pair_m) and engine.blocks_per_launch() >= 2:
                 kw["group_launch"] = True
-            st = engine.sweep(**kw)
+            if gblup:                                                       # GBLUP! / megaGBLUP! / MTGBLUP! (MCMC_BayesianAlphabet.jl:280-289)
+                st = _gb.step(engine, iteration=it, seed=seed_int, vare=vare, G=Gval, t=t, diagonal=mega)
+            else:
+                st = engine.sweep(**kw)
             solve_policy.observe(it, engine, ran=bool(kw.get("section_solve")))
             t_sweep += st["sweep_ms"]
             if adaptive:
@@ -1362,8 +1391,10 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                     pi = float(rng.beta(p - st["sum_delta"][0] + 1.0, st["sum_delta"][0] + 1.0))
 
             # 4. marker effect variance (variance_components.jl:151-189), re-cast to Float32 (:323-325)
-            if Mi.G.estimate_variance:
-                if mega and mt_pervar:                                      # one scaled inverse chi-square per marker and trait
+            if Mi.G.estimate_variance and gblup:                           # invweights = 1 ./ D, nloci = nObs (variance_components.jl:153-176)
+                Gval = _gb.draw_genetic_variance(rng, st["alpha_ss"], n, Gdf, Mi.G.scale, t, mega, ftype)
+            elif Mi.G.estimate_variance:
+                if mega and mt_pervar:                                     # one scaled inverse chi-square per marker and trait
                     sc = np.diag(Gdf * np.diag(np.asarray(Mi.G.scale, dtype=np.float64)))      # (variance_components.jl:112-117,181-186)
                     if hasattr(engine, "sample_marker_covariances"):        # on the device, from the resident beta
                         engine.sample_marker_covariances(Gdf + 1.0, sc, seed=seed_int, iteration=it)
@@ -1518,6 +1549,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
             if it % printout_frequency == 0 and it > burnin:
                 print_posterior_means(it, run_vare.mean)
     wall = time.time() - t0
+    if gblup:
+        engine.gblup_end()
+        _gb.rename_variance_file(output_folder, name)                    # MCMC_BayesianAlphabet.jl:434-439
 
     # ---- results (output.jl:108-212)
     if lp_device:
