@@ -24,6 +24,7 @@ needs() {      # does unit $1 have to be compiled?
     local sweep="kernels.hpp rng.hpp sweep.hpp update_role.hpp sampler_common.hpp sampler_st.hpp sampler_mt.hpp step_launch.hpp"
     case $1 in
         jwas_hip)  deps="$deps $ctx $sweep f64_path.hpp" ;;
+        session_rrm|session_mega) deps="$deps $ctx marker_state.hpp ${1#session_}.hpp" ;;
         session_*) deps="$deps $ctx ${1#session_}.hpp" ;;
         *)         deps="$deps $sweep step_launch_impl.hpp" ;;
     esac

@@ -42,6 +42,13 @@ struct JW_LOCAL DevOwner {
     void release() { for (void* q : ptrs) (void)hipFree(q); ptrs.clear(); }
 };
 
+// The marker state of a session with a sweep of its own (Rrm, Mega): alpha, beta, delta and their running means (of alpha, alpha^2
+// and the model frequency), each [rows][p] doubles.  Plain data; marker_state.hpp has what is done with it.
+struct MarkerState {
+    double *alpha = nullptr, *beta = nullptr, *delta = nullptr;
+    double *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;
+};
+
 struct jwas_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -290,8 +297,7 @@ struct jwas_hip_ctx {
         double* W = nullptr;                                // [T][ld] the residual, 0 at every unobserved cell
         double* M = nullptr;                                // [p][cells]
         double* gram = nullptr;                             // [nblocks][bs][bs][cells]
-        double *alpha = nullptr, *beta = nullptr, *delta = nullptr;               // [C][p]
-        double *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;          // [C][p]
+        MarkerState ms;                                     // [C][p]
         double* partials = nullptr;                         // [nslices][bs C]
         double* stat = nullptr;                             // [kStSize] the sweep's statistics | [nslices] sum W^2 per slice
         double* row = nullptr;                              // [ld] X alpha_q
@@ -310,8 +316,7 @@ struct jwas_hip_ctx {
         double* R = nullptr;                                // [nt][ld] the residuals (pad rows 0)
         double* xpx = nullptr;                              // [p]
         double* gram = nullptr;                             // [nblocks][bs][bs]
-        double *alpha = nullptr, *beta = nullptr, *delta = nullptr;               // [nt][p]
-        double *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;          // [nt][p]
+        MarkerState ms;                                     // [nt][p]
         double* partials = nullptr;                         // [nslices][nt][bs]
         double* par = nullptr;                              // [kParSize][nt] the per-trait parameters of the running sweep
         double* stat = nullptr;                             // [nt][kStSize] | [nt][nslices][2] sum r^2, sum r per slice

@@ -1,6 +1,7 @@
-// device_util.hpp -- what the session kernels (liability.hpp, locpar.hpp, mtmiss.hpp, annot.hpp, sem.hpp, rrm.hpp) share.  It defines no
-// kernel, so any number of units may include it; the host context (ctx.hpp) includes it for the limits below.  Every helper fixes
-// an ORDER of floating-point operations: with -ffp-contract=off its callers compute the bits of the expression written out.
+// device_util.hpp -- what the session kernels (liability.hpp, locpar.hpp, mtmiss.hpp, annot.hpp, sem.hpp, rrm.hpp, mega.hpp, gblup.hpp,
+// marker_state.hpp) share.  It defines no kernel, so any number of units may include it; the host context (ctx.hpp) includes it for
+// the limits below.  Every helper fixes an ORDER of floating-point operations: with -ffp-contract=off its callers compute the bits
+// of the expression written out.
 #pragma once
 #include "rng.hpp"
 #include <hip/hip_runtime.h>
@@ -45,6 +46,86 @@ __device__ inline double ordered_sum256(double* sh, const double* __restrict__ p
 
 // the mean of ns values from the mean m of the first ns - 1 and the last value v (output.jl:556-560's form)
 __device__ __forceinline__ double running_mean(double m, double v, double ns) { return m + (v - m) / ns; }
+
+// a wave's sum by the shuffle tree (32 .. 1): lane 0 holds the total
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
+    return v;
+}
+
+// acc[0 .. N) of the 256 threads of a workgroup -> out[0 .. N): shuffle tree (32 .. 1) within a wave, the four waves in wave order,
+// ((w0 + w1) + w2) + w3.  sh: 4 N doubles of LDS; the caller separates two uses with a barrier.
+template <int N>
+__device__ __forceinline__ void block_reduce(const double (&acc)[N], double* sh, double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        const double v = wave_sum(acc[q]);
+        if (lane == 0) sh[wave * N + q] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < N) out[threadIdx.x] = ((sh[threadIdx.x] + sh[N + threadIdx.x]) + sh[2 * N + threadIdx.x]) + sh[3 * N + threadIdx.x];
+}
+
+// four consecutive rows of a column as doubles (the column starts on a 16-byte boundary: ld is a multiple of 256)
+__device__ __forceinline__ void load4(const float* __restrict__ x, double (&v)[4])
+{
+    const float4 f = *reinterpret_cast<const float4*>(x);
+    v[0] = (double)f.x; v[1] = (double)f.y; v[2] = (double)f.z; v[3] = (double)f.w;
+}
+__device__ __forceinline__ void load4(const double* __restrict__ x, double (&v)[4])
+{
+    const double2 a = *reinterpret_cast<const double2*>(x), b = *reinterpret_cast<const double2*>(x + 2);
+    v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
+}
+
+// lower Cholesky factor of an SPD N x N matrix, row by row: L_ab = (A_ab - sum_{k < b} L_ak L_bk, k ascending) / L_bb, the diagonal a
+// square root (the operation order of sampler_mt.hpp's chol_lower, which the main sweep keeps for itself)
+template <int N>
+__device__ __forceinline__ void chol_lower(const double (&A)[N][N], double (&L)[N][N])
+{
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+#pragma unroll
+        for (int b = 0; b < N; ++b) L[a][b] = 0.0;
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+#pragma unroll
+        for (int b = 0; b <= a; ++b) {
+            double s = A[a][b];
+#pragma unroll
+            for (int k = 0; k < b; ++k) s = s - L[a][k] * L[b][k];
+            L[a][b] = a == b ? sqrt(s) : s / L[b][b];
+        }
+    }
+}
+
+// ---- the speculative walk of a block by one wave (mega.hpp, rrm.hpp): every pending lane evaluates its marker, the first whose effect
+// changes wins and commits ---------------------------------------------------------------------------------------------------------
+// the first pending lane that voted `changed` (64: none)
+__device__ __forceinline__ int first_changed(bool changed, unsigned long long pending)
+{
+    const unsigned long long mm = __ballot(changed) & pending;
+    return mm ? (int)__builtin_ctzll(mm) : 64;
+}
+
+// the pending lanes up to and including the winner kw: final with what they just evaluated (kw = 64: all of them)
+__device__ __forceinline__ unsigned long long final_lanes(unsigned long long pending, int kw)
+{
+    return (kw >= 64) ? pending : (pending & ((kw == 63) ? ~0ull : ((2ull << kw) - 1ull)));
+}
+
+// the change list's entry of this lane: base + the changed lanes below it; base advances by the wave's changed lanes
+__device__ __forceinline__ int list_entry(bool changed, int lane, int& base)
+{
+    const unsigned long long cm = __ballot(changed);
+    const int e = base + __popcll(cm & ((1ull << lane) - 1ull));
+    base += __popcll(cm);
+    return e;
+}
 
 // ---- the truncated standard normal of liability.hpp (its header comment has the cases) -------------------------------------------
 __device__ __forceinline__ double upper_tail(double x) { return 0.5 * erfc(x * 0.70710678118654752440); }

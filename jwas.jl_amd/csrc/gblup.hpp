@@ -226,34 +226,6 @@ __global__ __launch_bounds__(256) void k_grm<double>(const double* __restrict__ 
 }
 
 // ---- the sampler's passes --------------------------------------------------------------------------------------------------------------
-// four consecutive rows of a column as doubles (the column starts on a 16-byte boundary: ld is a multiple of 256)
-__device__ __forceinline__ void load4(const float* __restrict__ x, double (&v)[4])
-{
-    const float4 f = *reinterpret_cast<const float4*>(x);
-    v[0] = (double)f.x; v[1] = (double)f.y; v[2] = (double)f.z; v[3] = (double)f.w;
-}
-__device__ __forceinline__ void load4(const double* __restrict__ x, double (&v)[4])
-{
-    const double2 a = *reinterpret_cast<const double2*>(x), b = *reinterpret_cast<const double2*>(x + 2);
-    v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-}
-
-// acc[0 .. N) of the 256 threads of a workgroup -> out[0 .. N): shuffle tree within a wave, the four waves in wave order.  sh: 4 N
-template <int N>
-__device__ __forceinline__ void block_reduce(const double (&acc)[N], double* sh, double* __restrict__ out)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
-        if (lane == 0) sh[wave * N + q] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < N) out[threadIdx.x] = ((sh[threadIdx.x] + sh[N + threadIdx.x]) + sh[2 * N + threadIdx.x]) + sh[3 * N + threadIdx.x];
-}
-
 // part[(part T + k) ld + row] = sum over the part's columns j (ascending) of L[row, j] alpha_k[j].  grid = (nslices, nparts)
 template <class real, int T>
 __global__ __launch_bounds__(256) void k_gblup_mul(const real* __restrict__ L, int64_t ld, int64_t n, int32_t len, const real* __restrict__ alpha,
@@ -310,7 +282,7 @@ __global__ __launch_bounds__(256) void k_gblup_sub(const real* __restrict__ rplu
         for (int l = 0; l < T; ++l) acc[k * T + l] = v[k] * v[l];
         acc[T * T + k] = v[k];
     }
-    block_reduce<T * T + T>(acc, sh, fin + (int64_t)blockIdx.x * (T * T + T));
+    jwu::block_reduce<T * T + T>(acc, sh, fin + (int64_t)blockIdx.x * (T * T + T));
 }
 
 // s[i T + k] = l_i' r+_k: one wave per column.  grid = ceil(n / 4) workgroups of 4 waves
@@ -326,11 +298,11 @@ __global__ __launch_bounds__(256) void k_gblup_rhs(const real* __restrict__ L, i
     for (int k = 0; k < T; ++k) acc[k] = 0.0;
     for (int64_t row = 4 * lane; row < ld; row += 256) {
         double x[4];
-        load4(col + row, x);
+        jwu::load4(col + row, x);
 #pragma unroll
         for (int k = 0; k < T; ++k) {
             double w[4];
-            load4(rplus + (int64_t)k * ld + row, w);
+            jwu::load4(rplus + (int64_t)k * ld + row, w);
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc[k] = acc[k] + x[u] * w[u];
         }
@@ -383,26 +355,6 @@ __device__ __forceinline__ void inv_small_dev(const double (&A)[T][T], double (&
         for (int j = 0; j < T; ++j) Ainv[i][j] = M[i][T + j];
 }
 
-// lower Cholesky factor of an SPD T x T matrix (the operation order of sampler_mt.hpp's and rrm.hpp's chol_lower)
-template <int T>
-__device__ __forceinline__ void chol_lower(const double (&A)[T][T], double (&C)[T][T])
-{
-#pragma unroll
-    for (int a = 0; a < T; ++a)
-#pragma unroll
-        for (int b = 0; b < T; ++b) C[a][b] = 0.0;
-#pragma unroll
-    for (int a = 0; a < T; ++a) {
-#pragma unroll
-        for (int b = 0; b <= a; ++b) {
-            double s = A[a][b];
-#pragma unroll
-            for (int k = 0; k < b; ++k) s = s - C[a][k] * C[b][k];
-            C[a][b] = a == b ? sqrt(s) : s / C[b][b];
-        }
-    }
-}
-
 struct SampleArgs {
     const double* s;                    // [n][T]
     const double* D;                    // [n]
@@ -452,7 +404,7 @@ __global__ __launch_bounds__(256) void k_gblup_sample(const SampleArgs A)
                 w[k] = t;
             }
             inv_small_dev<T>(lhs, S);
-            chol_lower<T>(S, C);
+            jwu::chol_lower<T>(S, C);
 #pragma unroll
             for (int k = 0; k < T; ++k) {
                 double mu = 0.0;
@@ -475,7 +427,7 @@ __global__ __launch_bounds__(256) void k_gblup_sample(const SampleArgs A)
     for (int k = 0; k < T; ++k)
 #pragma unroll
         for (int l = 0; l < T; ++l) acc[k * T + l] = (a[k] * a[l]) / di;
-    block_reduce<T * T>(acc, sh, A.stat + (int64_t)blockIdx.x * (T * T));
+    jwu::block_reduce<T * T>(acc, sh, A.stat + (int64_t)blockIdx.x * (T * T));
 }
 
 }  // namespace jwb

@@ -25,7 +25,7 @@
 //                          walks the block 64 markers at a time by speculative evaluation (every pending lane tests its marker
 //                          against the current s, the first changed marker commits, its Gram row -- b doubles, read from L2 --
 //                          corrects s); the trait's change list and statistics.
-//   k_mega_sample_r        the same walk under the 4-class law of BayesR (below, beside the kernel): K chains of one model are K
+//   k_mega_sample_r        the same walk (mega_walk) under the 4-class law of BayesR (LawR, below): K chains of one model are K
 //                          traits with the same record.
 //   k_mega_finish          grid (row slices, traits): the last change list, then sum r^2 and sum r of the slice.
 //   k_mega_impute          grid (row chunks, traits): a missing cell (bit mask [T][ld / 32]) is redrawn from N(0, vare_k) -- with a
@@ -70,34 +70,6 @@ struct Events {
     double d[kMaxT][kMaxBlock];
 };
 
-// acc[0 .. N) of the 256 threads of a workgroup -> out[0 .. N): shuffle tree within a wave, the four waves in wave order.
-template <int N>
-__device__ __forceinline__ void block_reduce(const double (&acc)[N], double* sh, double* __restrict__ out)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
-        if (lane == 0) sh[wave * N + q] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < N) out[threadIdx.x] = ((sh[threadIdx.x] + sh[N + threadIdx.x]) + sh[2 * N + threadIdx.x]) + sh[3 * N + threadIdx.x];
-}
-
-// four consecutive rows of a column as doubles (the column starts on a 16-byte boundary: ld is a multiple of 256)
-__device__ __forceinline__ void load4(const float* __restrict__ x, double (&v)[4])
-{
-    const float4 f = *reinterpret_cast<const float4*>(x);
-    v[0] = (double)f.x; v[1] = (double)f.y; v[2] = (double)f.z; v[3] = (double)f.w;
-}
-__device__ __forceinline__ void load4(const double* __restrict__ x, double (&v)[4])
-{
-    const double2 a = *reinterpret_cast<const double2*>(x), b = *reinterpret_cast<const double2*>(x + 2);
-    v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-}
-
 // ---- set-up ------------------------------------------------------------------------------------------------------------------------
 // The Grams of the blocks: gram[(blk bs + a) bs + k] = sum_i x_ia x_ik for the markers a, k of block blk.  grid = (bs, nblocks):
 // workgroup (a, blk) forms the pairs k >= a and writes both (a, k) and (k, a): symmetric bit for bit; the pair (a, a) is also xpx.
@@ -117,7 +89,7 @@ __global__ __launch_bounds__(256) void k_mega_gram(const real* __restrict__ X, i
         const real* __restrict__ xk = X + (j0 + k) * ld;
         double acc[1] = {0.0};
         for (int64_t i = threadIdx.x; i < ld; i += 256) acc[0] = acc[0] + (double)xa[i] * (double)xk[i];
-        block_reduce<1>(acc, sh, outv);
+        jwu::block_reduce<1>(acc, sh, outv);
         __syncthreads();
         if (threadIdx.x == 0) {
             const double v = outv[0];
@@ -174,7 +146,7 @@ __global__ __launch_bounds__(256) void k_mega_update_partial(const UpdateArgs A)
         const real* __restrict__ x = X + (A.j0 + m) * A.ld + row0 + i0;
         for (int i = 0; i < len; i += 4) {
             double xv[4];
-            load4(x + i, xv);
+            jwu::load4(x + i, xv);
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -223,7 +195,7 @@ __global__ __launch_bounds__(256) void k_mega_finish(const FinishArgs A)
     for (int e = 0; e < nev; ++e) r = r + (double)X[(int64_t)A.ev->idx[k][e] * A.ld + row] * A.ev->d[k][e];
     if (nev > 0) A.R[(int64_t)k * A.ld + row] = r;
     const double acc[2] = {r * r, r};
-    block_reduce<2>(acc, sh, A.fin + ((int64_t)k * gridDim.x + blockIdx.x) * 2);
+    jwu::block_reduce<2>(acc, sh, A.fin + ((int64_t)k * gridDim.x + blockIdx.x) * 2);
 }
 
 // ---- one block of one trait ----------------------------------------------------------------------------------------------------------
@@ -240,8 +212,132 @@ struct SampleArgs {
     uint32_t iter, seed_lo, seed_hi, first_trait;
 };
 
-// grid = T workgroups of 256 threads: every thread adds the slice partials of one marker, then wave 0 runs the trait's chain
-__global__ __launch_bounds__(256) void k_mega_sample(const SampleArgs A)
+// The law of one marker under megaBayesABC! (this file's header): what k_mega_sample gives the walk.
+struct LawC {
+    static constexpr int kStats = kStSize;
+    static constexpr bool kBetaIsAlpha = false;
+    double ie, iv, logv, sdv, lp0, lpc;         // of the trait
+    double invLhs, loglhs, sdl;                 // of the marker
+    __device__ __forceinline__ LawC(const double* __restrict__ par, int T, int k)
+    {
+        const double vare = par[kParVare * T + k], v = par[kParVar * T + k];
+        lp0 = par[kParLogPi * T + k]; lpc = par[kParLogPiComp * T + k];
+        ie = 1.0 / vare; iv = 1.0 / v; logv = log(v); sdv = sqrt(v);
+    }
+    __device__ __forceinline__ void marker(double xx)
+    {
+        const double lhs = xx * ie + iv;
+        invLhs = 1.0 / lhs; loglhs = log(lhs); sdl = sqrt(invLhs);
+    }
+    // s = x_j'r, the marker's current effect a -> the candidate (alpha, beta, delta)
+    __device__ __forceinline__ void draw(double s, double xx, double a, double u, double z, double& an, double& bn, double& dn) const
+    {
+        const double rhs = (s + xx * a) * ie;
+        const double gHat = rhs * invLhs;
+        const double ld1 = -0.5 * (loglhs + logv - gHat * rhs) + lpc;
+        const double prob = 1.0 / (1.0 + exp(lp0 - ld1));
+        const bool inc = u < prob;
+        bn = inc ? gHat + z * sdl : z * sdv;
+        an = inc ? bn : 0.0;
+        dn = inc ? 1.0 : 0.0;
+    }
+    __device__ __forceinline__ void record(double (&st)[kStats], double a, double b, double d, bool changed) const
+    {
+        st[kStDelta] = st[kStDelta] + d;
+        st[kStBeta] = st[kStBeta] + b * b;
+        st[kStAlpha] = st[kStAlpha] + a * a;
+        if (changed) st[kStChanged] = st[kStChanged] + 1.0;
+    }
+};
+
+// The 4-class law of BayesR (markers/BayesianAlphabet/BayesR.jl:56-96), all in double: what k_mega_sample_r gives the walk.  Per chain
+// vare, sigma2, gamma[4] (gamma_1 = 0) and log pi[4]; one marker:
+//   rhs = (s + xpx alpha) / vare;  class c = 2..4: v_c = gamma_c sigma2, lhs_c = xpx / vare + 1 / v_c, bHat_c = rhs / lhs_c,
+//   lp_c = 0.5 (log(1 / lhs_c) - log v_c + bHat_c rhs) + log pi_c;  lp_1 = log pi_1
+//   probs_c = exp(lp_c - (mx + log sum_c exp(lp_c - mx))), mx = max lp (the sum over c ascending)
+//   the class: cp = probs_1, while cp <= u the next class is added (rand(Categorical), the CDF walk)
+//   class 1: alpha = 0;  class c: alpha = bHat_c + z sqrt(1 / lhs_c);  delta = the class, 1..4;  beta = alpha
+// Draws: slot 10 the uniform, slot 11 the normal, trait_id = first_trait + k, as under LawC.
+constexpr int kClasses = 4;
+// the device record of a BayesR chain's statistics
+constexpr int kStRCount = 0, kStRSsq = 4, kStRNnz = 5, kStRAlpha = 6, kStRChanged = 7, kStRSize = 8;
+// the per-chain parameters of a BayesR sweep: par[q * T + k]
+constexpr int kParRVare = 0, kParRVar = 1, kParRGamma = 2, kParRLogPi = 6, kParRSize = 10;
+
+struct LawR {
+    static constexpr int kStats = kStRSize;
+    static constexpr bool kBetaIsAlpha = true;
+    double ie, lp1, gam[3], iv[3], logv[3], lpi[3];         // of the chain (the arrays: the classes 2..4)
+    double invLhs[3], lconst[3], sdl[3];                    // of the marker
+    __device__ __forceinline__ LawR(const double* __restrict__ par, int T, int k)
+    {
+        const double vare = par[kParRVare * T + k], sig = par[kParRVar * T + k];
+        ie = 1.0 / vare;
+        lp1 = par[kParRLogPi * T + k];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double g = par[(kParRGamma + 1 + c) * T + k], vc = g * sig;
+            gam[c] = g; iv[c] = 1.0 / vc; logv[c] = log(vc);
+            lpi[c] = par[(kParRLogPi + 1 + c) * T + k];
+        }
+    }
+    __device__ __forceinline__ void marker(double xx)
+    {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double lhs = xx * ie + iv[c];
+            invLhs[c] = 1.0 / lhs;
+            lconst[c] = log(invLhs[c]) - logv[c];
+            sdl[c] = sqrt(invLhs[c]);
+        }
+    }
+    __device__ __forceinline__ void draw(double s, double xx, double a, double u, double z, double& an, double& bn, double& dn) const
+    {
+        const double rhs = (s + xx * a) * ie;
+        double bh[3], lp[3], mx = lp1;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            bh[c] = rhs * invLhs[c];
+            lp[c] = 0.5 * (lconst[c] + bh[c] * rhs) + lpi[c];
+            mx = lp[c] > mx ? lp[c] : mx;
+        }
+        const double se = ((exp(lp1 - mx) + exp(lp[0] - mx)) + exp(lp[1] - mx)) + exp(lp[2] - mx);
+        const double ln = mx + log(se);
+        // the CDF walk: the class is the first whose cumulated probability exceeds u (the last class takes the rest)
+        double cp = exp(lp1 - ln);
+        int cls = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (cls == c && cp <= u) { cls = c + 1; cp = cp + exp(lp[c] - ln); }
+        }
+        const double bsel = cls == 1 ? bh[0] : (cls == 2 ? bh[1] : bh[2]);
+        const double sd2 = sdl[0], sd3 = sdl[1], sd4 = sdl[2];      // (values, not members: a choice among members stays in memory)
+        const double ssel = cls == 1 ? sd2 : (cls == 2 ? sd3 : sd4);
+        an = cls == 0 ? 0.0 : bsel + z * ssel;
+        bn = an;
+        dn = (double)(cls + 1);
+    }
+    __device__ __forceinline__ void record(double (&st)[kStats], double a, double, double d, bool changed) const
+    {
+        const double a2 = a * a;
+#pragma unroll
+        for (int c = 0; c < kClasses; ++c)
+            if (d == (double)(c + 1)) st[kStRCount + c] = st[kStRCount + c] + 1.0;
+        if (d > 1.0) {
+            const double g2 = gam[0], g3 = gam[1], g4 = gam[2];
+            const double gs = d == 2.0 ? g2 : (d == 3.0 ? g3 : g4);
+            st[kStRSsq] = st[kStRSsq] + a2 / gs;
+            st[kStRNnz] = st[kStRNnz] + 1.0;
+        }
+        st[kStRAlpha] = st[kStRAlpha] + a2;
+        if (changed) st[kStRChanged] = st[kStRChanged] + 1.0;
+    }
+};
+
+// One block of one trait under `Law`: every thread adds the slice partials of one marker, then wave 0 runs the trait's chain.
+// A.par is the law's [.][T] table, A.stat its [T][Law::kStats] record.
+template <class Law>
+__device__ __forceinline__ void mega_walk(const SampleArgs& A)
 {
     __shared__ double s_s[kMaxBlock], s_a0[kMaxBlock];
     const int lane = threadIdx.x & 63, k = blockIdx.x;
@@ -260,13 +356,11 @@ __global__ __launch_bounds__(256) void k_mega_sample(const SampleArgs A)
     }
     __syncthreads();
     if (threadIdx.x >= 64) return;
-    const double vare = A.par[kParVare * A.T + k], v = A.par[kParVar * A.T + k];
-    const double lp0 = A.par[kParLogPi * A.T + k], lpc = A.par[kParLogPiComp * A.T + k];
-    const double ie = 1.0 / vare, iv = 1.0 / v, logv = log(v), sdv = sqrt(v);
+    Law law(A.par, A.T, k);
     const uint32_t tag = kTag | (A.first_trait + (uint32_t)k);
-    double st_acc[kStSize];
+    double st_acc[Law::kStats];
 #pragma unroll
-    for (int i = 0; i < kStSize; ++i) st_acc[i] = 0.0;
+    for (int i = 0; i < Law::kStats; ++i) st_acc[i] = 0.0;
     const int nsub = (b + 63) / 64;
     int base = 0;
 #pragma unroll 1
@@ -279,22 +373,15 @@ __global__ __launch_bounds__(256) void k_mega_sample(const SampleArgs A)
         const double z = jwu::normal_from(jw::philox4x32_10((uint32_t)j, A.iter, tag, kSlotZ, A.seed_lo, A.seed_hi));
         const jw::u32x4 wu = jw::philox4x32_10((uint32_t)j, A.iter, tag, kSlotU, A.seed_lo, A.seed_hi);
         const double u = jw::u52(wu.x, wu.y);
-        const double lhs = xx * ie + iv, invLhs = 1.0 / lhs, loglhs = log(lhs), sdl = sqrt(invLhs);
-        double a_cur = s_a0[kl], b_cur = beta[j], d_cur = delta[j];
+        law.marker(xx);
+        double a_cur = s_a0[kl], b_cur = Law::kBetaIsAlpha ? 0.0 : beta[j], d_cur = delta[j];
         unsigned long long pending = __ballot(valid);
         while (pending) {
-            const double rhs = (s_s[kl] + xx * a_cur) * ie;
-            const double gHat = rhs * invLhs;
-            const double ld1 = -0.5 * (loglhs + logv - gHat * rhs) + lpc;
-            const double prob = 1.0 / (1.0 + exp(lp0 - ld1));
-            const bool inc = u < prob;
-            const double bn = inc ? gHat + z * sdl : z * sdv;
-            const double an = inc ? bn : 0.0, dn = inc ? 1.0 : 0.0;
-            const bool ch = an != a_cur;
-            const unsigned long long mm = __ballot(ch && valid) & pending;
-            const int kw = mm ? (int)__builtin_ctzll(mm) : 64;
+            double an, bn, dn;
+            law.draw(s_s[kl], xx, a_cur, u, z, an, bn, dn);
+            const int kw = jwu::first_changed(an != a_cur && valid, pending);
             // lanes before the winner are final with what they just evaluated (their effects do not move)
-            const unsigned long long done = (kw >= 64) ? pending : (pending & ((kw == 63) ? ~0ull : ((2ull << kw) - 1ull)));
+            const unsigned long long done = jwu::final_lanes(pending, kw);
             if ((done >> lane) & 1ull) { b_cur = bn; d_cur = dn; }
             if (kw >= 64) break;
             // the winner commits; its Gram row corrects s of the whole block: s_i += G_i,ce d
@@ -310,184 +397,31 @@ __global__ __launch_bounds__(256) void k_mega_sample(const SampleArgs A)
         }
         // the sub-block is final: state, change list, statistics
         const bool changed = valid && (a_cur != s_a0[kl]);
-        const unsigned long long cm = __ballot(changed);
+        const int e = jwu::list_entry(changed, lane, base);
         if (changed) {
-            const int e = base + __popcll(cm & ((1ull << lane) - 1ull));
             A.ev->idx[k][e] = (int32_t)j;
             A.ev->d[k][e] = s_a0[kl] - a_cur;
         }
-        base += __popcll(cm);
         if (valid) {
-            alpha[j] = a_cur; beta[j] = b_cur; delta[j] = d_cur;
-            st_acc[kStDelta] = st_acc[kStDelta] + d_cur;
-            st_acc[kStBeta] = st_acc[kStBeta] + b_cur * b_cur;
-            st_acc[kStAlpha] = st_acc[kStAlpha] + a_cur * a_cur;
-            if (changed) st_acc[kStChanged] = st_acc[kStChanged] + 1.0;
+            alpha[j] = a_cur; beta[j] = Law::kBetaIsAlpha ? a_cur : b_cur; delta[j] = d_cur;
+            law.record(st_acc, a_cur, b_cur, d_cur, changed);
         }
     }
     // the block's statistics join the sweep's: shuffle tree, lane 0 adds (the blocks of a sweep run in stream order)
 #pragma unroll
-    for (int i = 0; i < kStSize; ++i) {
-        double t = st_acc[i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) t = t + __shfl_down(t, off, 64);
-        st_acc[i] = t;
-    }
+    for (int i = 0; i < Law::kStats; ++i) st_acc[i] = jwu::wave_sum(st_acc[i]);
     if (lane == 0) {
 #pragma unroll
-        for (int i = 0; i < kStSize; ++i) A.stat[k * kStSize + i] = A.stat[k * kStSize + i] + st_acc[i];
+        for (int i = 0; i < Law::kStats; ++i) A.stat[k * Law::kStats + i] = A.stat[k * Law::kStats + i] + st_acc[i];
         A.ev->count[k] = base;
     }
 }
 
-// ---- one block of one BayesR chain ------------------------------------------------------------------------------------------------------
-// The 4-class law of BayesR (markers/BayesianAlphabet/BayesR.jl:56-96), all in double, on the walk of k_mega_sample.  Per chain
-// vare, sigma2, gamma[4] (gamma_1 = 0) and log pi[4]; one marker:
-//   rhs = (s + xpx alpha) / vare;  class c = 2..4: v_c = gamma_c sigma2, lhs_c = xpx / vare + 1 / v_c, bHat_c = rhs / lhs_c,
-//   lp_c = 0.5 (log(1 / lhs_c) - log v_c + bHat_c rhs) + log pi_c;  lp_1 = log pi_1
-//   probs_c = exp(lp_c - (mx + log sum_c exp(lp_c - mx))), mx = max lp (the sum over c ascending)
-//   the class: cp = probs_1, while cp <= u the next class is added (rand(Categorical), the CDF walk)
-//   class 1: alpha = 0;  class c: alpha = bHat_c + z sqrt(1 / lhs_c);  delta = the class, 1..4;  beta = alpha
-// Draws: slot 10 the uniform, slot 11 the normal, trait_id = first_trait + k, as k_mega_sample.
-constexpr int kClasses = 4;
-// the device record of a BayesR chain's statistics
-constexpr int kStRCount = 0, kStRSsq = 4, kStRNnz = 5, kStRAlpha = 6, kStRChanged = 7, kStRSize = 8;
-// the per-chain parameters of a BayesR sweep: par[q * T + k]
-constexpr int kParRVare = 0, kParRVar = 1, kParRGamma = 2, kParRLogPi = 6, kParRSize = 10;
+// grid = T workgroups of 256 threads; par [kParSize][T], stat [T][kStSize]
+__global__ __launch_bounds__(256) void k_mega_sample(const SampleArgs A) { mega_walk<LawC>(A); }
 
-// grid = T workgroups of 256 threads; SampleArgs with par [kParRSize][T] and stat [T][kStRSize]
-__global__ __launch_bounds__(256) void k_mega_sample_r(const SampleArgs A)
-{
-    __shared__ double s_s[kMaxBlock], s_a0[kMaxBlock];
-    const int lane = threadIdx.x & 63, k = blockIdx.x;
-    const int b = A.b, bs = A.bs;
-    double* __restrict__ alpha = A.alpha + (int64_t)k * A.p;
-    double* __restrict__ beta = A.beta + (int64_t)k * A.p;
-    double* __restrict__ delta = A.delta + (int64_t)k * A.p;
-    for (int i = threadIdx.x; i < b; i += 256) {
-        const double* __restrict__ part = A.partials + (int64_t)k * bs + i;
-        const int64_t stride = (int64_t)A.T * bs;
-        double s = 0.0;
-#pragma unroll 8
-        for (int sl = 0; sl < A.nslices; ++sl) s = s + part[sl * stride];      // (ascending, as k_mega_sample)
-        s_s[i] = s;
-        s_a0[i] = alpha[A.j0 + i];
-    }
-    __syncthreads();
-    if (threadIdx.x >= 64) return;
-    const double vare = A.par[kParRVare * A.T + k], sig = A.par[kParRVar * A.T + k], ie = 1.0 / vare;
-    const double lp1 = A.par[kParRLogPi * A.T + k];
-    double gam[3], iv[3], logv[3], lpi[3];                   // the classes 2..4
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double g = A.par[(kParRGamma + 1 + c) * A.T + k], vc = g * sig;
-        gam[c] = g; iv[c] = 1.0 / vc; logv[c] = log(vc);
-        lpi[c] = A.par[(kParRLogPi + 1 + c) * A.T + k];
-    }
-    const uint32_t tag = kTag | (A.first_trait + (uint32_t)k);
-    double st_acc[kStRSize];
-#pragma unroll
-    for (int i = 0; i < kStRSize; ++i) st_acc[i] = 0.0;
-    const int nsub = (b + 63) / 64;
-    int base = 0;
-#pragma unroll 1
-    for (int s = 0; s < nsub; ++s) {
-        const int kq = 64 * s + lane;
-        const bool valid = kq < b;
-        const int kl = valid ? kq : 0;
-        const int64_t j = A.j0 + kl;
-        const double xx = A.xpx[j];
-        const double z = jwu::normal_from(jw::philox4x32_10((uint32_t)j, A.iter, tag, kSlotZ, A.seed_lo, A.seed_hi));
-        const jw::u32x4 wu = jw::philox4x32_10((uint32_t)j, A.iter, tag, kSlotU, A.seed_lo, A.seed_hi);
-        const double u = jw::u52(wu.x, wu.y);
-        double invLhs[3], lconst[3], sdl[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double lhs = xx * ie + iv[c];
-            invLhs[c] = 1.0 / lhs;
-            lconst[c] = log(invLhs[c]) - logv[c];
-            sdl[c] = sqrt(invLhs[c]);
-        }
-        double a_cur = s_a0[kl], d_cur = delta[j];
-        unsigned long long pending = __ballot(valid);
-        while (pending) {
-            const double rhs = (s_s[kl] + xx * a_cur) * ie;
-            double bh[3], lp[3], mx = lp1;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                bh[c] = rhs * invLhs[c];
-                lp[c] = 0.5 * (lconst[c] + bh[c] * rhs) + lpi[c];
-                mx = lp[c] > mx ? lp[c] : mx;
-            }
-            const double se = ((exp(lp1 - mx) + exp(lp[0] - mx)) + exp(lp[1] - mx)) + exp(lp[2] - mx);
-            const double ln = mx + log(se);
-            // the CDF walk: the class is the first whose cumulated probability exceeds u (the last class takes the rest)
-            double cp = exp(lp1 - ln);
-            int cls = 0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (cls == c && cp <= u) { cls = c + 1; cp = cp + exp(lp[c] - ln); }
-            }
-            const double bsel = cls == 1 ? bh[0] : (cls == 2 ? bh[1] : bh[2]);
-            const double ssel = cls == 1 ? sdl[0] : (cls == 2 ? sdl[1] : sdl[2]);
-            const double an = cls == 0 ? 0.0 : bsel + z * ssel;
-            const double dn = (double)(cls + 1);
-            const bool ch = an != a_cur;
-            const unsigned long long mm = __ballot(ch && valid) & pending;
-            const int kw = mm ? (int)__builtin_ctzll(mm) : 64;
-            // lanes before the winner are final with what they just evaluated (their effects do not move)
-            const unsigned long long done = (kw >= 64) ? pending : (pending & ((kw == 63) ? ~0ull : ((2ull << kw) - 1ull)));
-            if ((done >> lane) & 1ull) d_cur = dn;
-            if (kw >= 64) break;
-            // the winner commits; its Gram row corrects s of the whole block: s_i += G_i,ce d
-            const int ce = 64 * s + kw;
-            const double Dl = a_cur - an;
-            const double D = __shfl(Dl, kw, 64);
-            if (lane == kw) a_cur = an;
-            const double* __restrict__ grow = A.gram + (int64_t)ce * bs;
-            __builtin_amdgcn_wave_barrier();                // (one wave: its LDS accesses execute in program order)
-            for (int k2 = lane; k2 < b; k2 += 64) s_s[k2] = s_s[k2] + grow[k2] * D;
-            __builtin_amdgcn_wave_barrier();
-            pending &= ~done;
-        }
-        // the sub-block is final: state, change list, statistics
-        const bool changed = valid && (a_cur != s_a0[kl]);
-        const unsigned long long cm = __ballot(changed);
-        if (changed) {
-            const int e = base + __popcll(cm & ((1ull << lane) - 1ull));
-            A.ev->idx[k][e] = (int32_t)j;
-            A.ev->d[k][e] = s_a0[kl] - a_cur;
-        }
-        base += __popcll(cm);
-        if (valid) {
-            alpha[j] = a_cur; beta[j] = a_cur; delta[j] = d_cur;
-            const double a2 = a_cur * a_cur;
-#pragma unroll
-            for (int c = 0; c < kClasses; ++c)
-                if (d_cur == (double)(c + 1)) st_acc[kStRCount + c] = st_acc[kStRCount + c] + 1.0;
-            if (d_cur > 1.0) {
-                const double gs = d_cur == 2.0 ? gam[0] : (d_cur == 3.0 ? gam[1] : gam[2]);
-                st_acc[kStRSsq] = st_acc[kStRSsq] + a2 / gs;
-                st_acc[kStRNnz] = st_acc[kStRNnz] + 1.0;
-            }
-            st_acc[kStRAlpha] = st_acc[kStRAlpha] + a2;
-            if (changed) st_acc[kStRChanged] = st_acc[kStRChanged] + 1.0;
-        }
-    }
-    // the block's statistics join the sweep's: shuffle tree, lane 0 adds (the blocks of a sweep run in stream order)
-#pragma unroll
-    for (int i = 0; i < kStRSize; ++i) {
-        double t = st_acc[i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) t = t + __shfl_down(t, off, 64);
-        st_acc[i] = t;
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < kStRSize; ++i) A.stat[k * kStRSize + i] = A.stat[k * kStRSize + i] + st_acc[i];
-        A.ev->count[k] = base;
-    }
-}
+// ... of T BayesR chains: par [kParRSize][T], stat [T][kStRSize]
+__global__ __launch_bounds__(256) void k_mega_sample_r(const SampleArgs A) { mega_walk<LawR>(A); }
 
 // ---- missing cells ---------------------------------------------------------------------------------------------------------------------
 // grid = (ceil(n / 256), T): r_k[i] = z sqrt(vare_k) where bit i of the trait's mask is set; nothing else is written
@@ -502,31 +436,7 @@ __global__ __launch_bounds__(256) void k_mega_impute(const uint32_t* __restrict_
     R[(int64_t)k * ld + i] = z * sqrt(vare[k]);
 }
 
-// ---- outputs --------------------------------------------------------------------------------------------------------------------------
-// running mean, mean of squares and model frequency of every effect (output.jl:556-560): one thread per (trait, marker)
-__global__ __launch_bounds__(256) void k_mega_accumulate(const double* __restrict__ alpha, const double* __restrict__ delta, int64_t tp, double ns,
-                                                         double* __restrict__ mean_a, double* __restrict__ mean_a2, double* __restrict__ mean_d)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= tp) return;
-    const double a = alpha[i];
-    mean_a[i] = jwu::running_mean(mean_a[i], a, ns);
-    mean_a2[i] = jwu::running_mean(mean_a2[i], a * a, ns);
-    mean_d[i] = jwu::running_mean(mean_d[i], delta[i], ns);
-}
-
-// ... of BayesR chains: delta holds the class 1..4, the model frequency is that of class > 1
-__global__ __launch_bounds__(256) void k_mega_accumulate_r(const double* __restrict__ alpha, const double* __restrict__ delta, int64_t tp, double ns,
-                                                           double* __restrict__ mean_a, double* __restrict__ mean_a2, double* __restrict__ mean_d)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= tp) return;
-    const double a = alpha[i];
-    mean_a[i] = jwu::running_mean(mean_a[i], a, ns);
-    mean_a2[i] = jwu::running_mean(mean_a2[i], a * a, ns);
-    mean_d[i] = jwu::running_mean(mean_d[i], delta[i] > 1.0 ? 1.0 : 0.0, ns);
-}
-
+// ---- outputs (the running means and X alpha: marker_state.hpp) -----------------------------------------------------------------------------
 // The potential scale reduction factor of every marker effect (Gelman and Rubin) from the running means m_k and means of squares q_k
 // of K chains after N saved samples: s_k^2 = N / (N - 1) (q_k - m_k^2), W = mean_k s_k^2, B / N = sum_k (m_k - mean m)^2 / (K - 1),
 // V = (N - 1) / N W + B / N, out = sqrt(V / W); W == 0 (the marker never entered the model in any chain): NaN.  One thread per marker,
@@ -552,21 +462,6 @@ __global__ __launch_bounds__(256) void k_mega_psrf(const double* __restrict__ me
         const double V = g * W + sb / (double)(K - 1);
         out[j] = W == 0.0 ? __builtin_nan("") : sqrt(V / W);
     }
-}
-
-// out[i] = sum_j x_ij alpha_j (j ascending, zero effects skipped): one thread per row of X (the context's matrix or its output rows)
-template <class real>
-__global__ __launch_bounds__(256) void k_mega_mul_alpha(const real* __restrict__ X, int64_t ld, int64_t n, int64_t p, const double* __restrict__ alpha,
-                                                        double* __restrict__ out)
-{
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= n) return;
-    double s = 0.0;
-    for (int64_t j = 0; j < p; ++j) {
-        const double a = alpha[j];
-        if (a != 0.0) s = s + (double)X[j * ld + row] * a;
-    }
-    out[row] = s;
 }
 
 }  // namespace jwg

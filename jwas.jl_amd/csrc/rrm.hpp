@@ -71,23 +71,6 @@ struct Events {
     double g[kMaxBlock * kMaxT];                // [e * T + t]
 };
 
-// acc[0 .. N) of the 256 threads of a workgroup -> out[0 .. N): shuffle tree within a wave, the four waves in wave order.
-// sh: 4 N doubles; the caller separates two uses with a barrier.
-template <int N>
-__device__ __forceinline__ void block_reduce(const double (&acc)[N], double* sh, double* __restrict__ out)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
-        if (lane == 0) sh[wave * N + q] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < N) out[threadIdx.x] = ((sh[threadIdx.x] + sh[N + threadIdx.x]) + sh[2 * N + threadIdx.x]) + sh[3 * N + threadIdx.x];
-}
-
 // Eight per-lane values (one per column) -> lane l holds the wave's sum of column (l >> 3) & 7 in every lane of its 8-lane group.
 __device__ __forceinline__ double transposed_sum8(const double (&v)[8], int lane)
 {
@@ -145,7 +128,7 @@ __global__ __launch_bounds__(256) void k_rrm_m(const real* __restrict__ X, int64
 #pragma unroll
         for (int q = 0; q < NC; ++q) acc[q] = acc[q] + xx * O[(int64_t)q * ld + i];
     }
-    block_reduce<NC>(acc, sh, M + (int64_t)blockIdx.x * NC);
+    jwu::block_reduce<NC>(acc, sh, M + (int64_t)blockIdx.x * NC);
 }
 
 // The Gram tensor of the blocks: gram[(blk bs + a) bs + k][cell] = sum_i x_ia x_ik O_i[cell] for the markers a, k of block blk.
@@ -173,7 +156,7 @@ __global__ __launch_bounds__(256) void k_rrm_gram(const real* __restrict__ X, in
 #pragma unroll
             for (int q = 0; q < NC; ++q) acc[q] = acc[q] + xx * O[(int64_t)q * ld + i];
         }
-        block_reduce<NC>(acc, sh, outv);
+        jwu::block_reduce<NC>(acc, sh, outv);
         __syncthreads();
         if ((int)threadIdx.x < NC) {
             const double v = outv[threadIdx.x];
@@ -298,29 +281,10 @@ __global__ __launch_bounds__(256) void k_rrm_finish(const FinishArgs A)
             }
         }
     }
-    block_reduce<1>(acc, sh, A.wss + blockIdx.x);
+    jwu::block_reduce<1>(acc, sh, A.wss + blockIdx.x);
 }
 
 // ---- one marker -----------------------------------------------------------------------------------------------------------------------
-template <int C>
-__device__ __forceinline__ void chol_lower(const double (&A)[C][C], double (&L)[C][C])
-{
-#pragma unroll
-    for (int a = 0; a < C; ++a)
-#pragma unroll
-        for (int b = 0; b < C; ++b) L[a][b] = 0.0;
-#pragma unroll
-    for (int a = 0; a < C; ++a) {
-#pragma unroll
-        for (int b = 0; b <= a; ++b) {
-            double s = A[a][b];
-#pragma unroll
-            for (int k = 0; k < b; ++k) s = s - L[a][k] * L[b][k];
-            L[a][b] = a == b ? sqrt(s) : s / L[b][b];
-        }
-    }
-}
-
 // One candidate state: q = -0.5 (log det lhs - rhs'mu); with want_cand the candidate mu + chol(inv(lhs)) z.
 template <int C>
 __device__ __forceinline__ void rrm_state(const double (&Mj)[C][C], const double (&Gi)[C][C], unsigned st, double ie, const double (&xw)[C],
@@ -337,7 +301,7 @@ __device__ __forceinline__ void rrm_state(const double (&Mj)[C][C], const double
         }
         rhs[a] = (Da * xw[a]) * ie;
     }
-    chol_lower<C>(lhs, L);
+    jwu::chol_lower<C>(lhs, L);
 #pragma unroll
     for (int a = 0; a < C; ++a)
 #pragma unroll
@@ -377,7 +341,7 @@ __device__ __forceinline__ void rrm_state(const double (&Mj)[C][C], const double
     q = -0.5 * (log(det) - quad);
     if (!want_cand) return;
     double K[C][C];
-    chol_lower<C>(inv, K);
+    jwu::chol_lower<C>(inv, K);
 #pragma unroll
     for (int a = 0; a < C; ++a) {
         double s = mu[a];
@@ -507,10 +471,9 @@ __global__ __launch_bounds__(256) void k_rrm_sample(const SampleArgs A)
                     an[q] = dn[q] * cand[q];
                     ch = ch || (an[q] != a_cur[q]);
                 }
-                const unsigned long long mm = __ballot(ch && valid) & pending;
-                const int kw = mm ? (int)__builtin_ctzll(mm) : 64;
+                const int kw = jwu::first_changed(ch && valid, pending);
                 // lanes before the winner are final with what they just evaluated (their coefficients do not move)
-                const unsigned long long done = (kw >= 64) ? pending : (pending & ((kw == 63) ? ~0ull : ((2ull << kw) - 1ull)));
+                const unsigned long long done = jwu::final_lanes(pending, kw);
                 if ((done >> lane) & 1ull) {
 #pragma unroll
                     for (int q = 0; q < C; ++q) { b_cur[q] = cand[q]; d_cur[q] = dn[q]; }
@@ -549,9 +512,8 @@ __global__ __launch_bounds__(256) void k_rrm_sample(const SampleArgs A)
                 if (d_cur[q] != 0.0) stv |= 1u << q;
             }
             changed = changed && valid;
-            const unsigned long long cm = __ballot(changed);
+            const int e = jwu::list_entry(changed, lane, base);
             if (changed) {
-                const int e = base + __popcll(cm & ((1ull << lane) - 1ull));
                 A.ev->idx[e] = (int32_t)(A.j0 + k);
 #pragma unroll
                 for (int q = 0; q < C; ++q) {
@@ -560,7 +522,6 @@ __global__ __launch_bounds__(256) void k_rrm_sample(const SampleArgs A)
                     s_dl[e * C + q] = dd;
                 }
             }
-            base += __popcll(cm);
             if (valid) {
 #pragma unroll
                 for (int q = 0; q < C; ++q) {
@@ -578,19 +539,9 @@ __global__ __launch_bounds__(256) void k_rrm_sample(const SampleArgs A)
         }
         // the block's statistics join the sweep's: shuffle tree, lane 0 adds (the blocks of a sweep run in stream order)
 #pragma unroll
-        for (int i = 0; i < NC + 2; ++i) {
-            double v = st_acc[i];
+        for (int i = 0; i < NC + 2; ++i) st_acc[i] = jwu::wave_sum(st_acc[i]);
 #pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
-            st_acc[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            double v = cnt[i];
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
-            cnt[i] = v;
-        }
+        for (int i = 0; i < NS; ++i) cnt[i] = jwu::wave_sum(cnt[i]);
         if (lane == 0) {
 #pragma unroll
             for (int i = 0; i < NS; ++i) A.stat[kStCounts + i] = A.stat[kStCounts + i] + cnt[i];
@@ -612,34 +563,6 @@ __global__ __launch_bounds__(256) void k_rrm_sample(const SampleArgs A)
         for (int q = 1; q < C; ++q) g = g + s_phi[t * C + q] * s_dl[e * C + q];
         A.ev->g[f] = g;
     }
-}
-
-// ---- outputs --------------------------------------------------------------------------------------------------------------------------
-// running mean, mean of squares and model frequency of every coefficient (output.jl:556-560): one thread per (coefficient, marker)
-__global__ __launch_bounds__(256) void k_rrm_accumulate(const double* __restrict__ alpha, const double* __restrict__ delta, int64_t cp, double ns,
-                                                        double* __restrict__ mean_a, double* __restrict__ mean_a2, double* __restrict__ mean_d)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= cp) return;
-    const double a = alpha[i];
-    mean_a[i] = jwu::running_mean(mean_a[i], a, ns);
-    mean_a2[i] = jwu::running_mean(mean_a2[i], a * a, ns);
-    mean_d[i] = jwu::running_mean(mean_d[i], delta[i], ns);
-}
-
-// out[i] = sum_j x_ij alpha_j (j ascending, zero coefficients skipped): one thread per row
-template <class real>
-__global__ __launch_bounds__(256) void k_rrm_mul_alpha(const real* __restrict__ X, int64_t ld, int64_t n, int64_t p, const double* __restrict__ alpha,
-                                                       double* __restrict__ out)
-{
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= n) return;
-    double s = 0.0;
-    for (int64_t j = 0; j < p; ++j) {
-        const double a = alpha[j];
-        if (a != 0.0) s = s + (double)X[j * ld + row] * a;
-    }
-    out[row] = s;
 }
 
 }  // namespace jwr

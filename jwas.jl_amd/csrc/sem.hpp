@@ -54,22 +54,6 @@ inline int sem_grid(int64_t n)
     return (int)(g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g);
 }
 
-// acc[0 .. N) of the 256 threads of a workgroup -> out[0 .. N): shuffle tree within a wave, the four waves in wave order
-template <int N>
-__device__ __forceinline__ void sem_block_reduce(const double (&acc)[N], double* sh, double* __restrict__ out)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
-        if (lane == 0) sh[wave * N + q] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < N) out[threadIdx.x] = ((sh[threadIdx.x] + sh[N + threadIdx.x]) + sh[2 * N + threadIdx.x]) + sh[3 * N + threadIdx.x];
-}
-
 struct DotArgs {
     const void* r;                      // [nt][ld] residuals (T)
     const double* y;                    // [nt][n]
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(256) void k_sem_dots(const DotArgs A)
                     if ((A.mask >> cell(i, j)) & 1u) acc[cell(i, j)] = acc[cell(i, j)] + yv[j] * rv[i];
         }
     }
-    sem_block_reduce<kMaxPairs>(acc, sh, A.part + (size_t)blockIdx.x * kMaxPairs);
+    jwu::block_reduce<kMaxPairs>(acc, sh, A.part + (size_t)blockIdx.x * kMaxPairs);
 }
 
 // S = y y' at begin: the same reduction over the cells (j, k), k <= j < nt; part: [G][kGramCells]
@@ -130,7 +114,7 @@ __global__ __launch_bounds__(256) void k_sem_gram(const double* __restrict__ y, 
                 for (int k = 0; k <= j; ++k) acc[gcell(j, k)] = acc[gcell(j, k)] + yv[j] * yv[k];
         }
     }
-    sem_block_reduce<kGramCells>(acc, sh, part + (size_t)blockIdx.x * kGramCells);
+    jwu::block_reduce<kGramCells>(acc, sh, part + (size_t)blockIdx.x * kGramCells);
 }
 
 // one workgroup of 64 threads: the G partials of every cell in ascending workgroup order, S symmetric 4 x 4

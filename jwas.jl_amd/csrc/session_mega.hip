@@ -3,6 +3,7 @@
 // Several chains of one model are traits of the same session: jwas_hip_mega_sweep_r (the 4-class BayesR law, BayesR.jl:56-96),
 // jwas_hip_mega_accumulate_r and jwas_hip_mega_psrf (the potential scale reduction factor over the chains).
 #include "ctx.hpp"
+#include "marker_state.hpp"
 #include "mega.hpp"
 
 static_assert(jwg::kMaxT == JWAS_HIP_MEGA_MAX_TRAITS && jwg::kMaxBlock == JWAS_HIP_MEGA_MAX_BLOCK, "the header's limits are mega.hpp's");
@@ -53,8 +54,59 @@ static int mega_params(jwas_hip_ctx* c, const jwas_mega_params* P, bool sweep, c
         b.par_host[(size_t)jwg::kParLogPi * T + k] = std::log(P->pi[k]);                    // pi = 0: -Inf, every marker is included
         b.par_host[(size_t)jwg::kParLogPiComp * T + k] = std::log(1.0 - P->pi[k]);
     }
+    return JWAS_HIP_OK;
+}
+
+// par_host -> the device table `par` (par_host stays until the sweep has finished)
+static int mega_upload_params(jwas_hip_ctx* c, double* par)
+{
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(b.par, b.par_host.data(), sizeof(double) * b.par_host.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(par, c->mg.par_host.data(), sizeof(double) * c->mg.par_host.size(), hipMemcpyHostToDevice, c->stream));
+    return JWAS_HIP_OK;
+}
+
+// One sweep over the blocks under the law of `sample` (jwg::k_mega_sample, _r): par_host goes to `par`; per block the right-hand
+// sides and the walk, after the last block its change list and the residual sums.  host: the device record [T][rec] | [T][nslices][2];
+// resid_ss, resid_sum (NULL: not wanted): sum r^2 and sum r of every trait, the slices added in ascending order.
+static int mega_run_sweep(jwas_hip_ctx* c, uint32_t iteration, uint64_t seed, double* par, double* stat, int rec, void (*sample)(const jwg::SampleArgs),
+                          std::vector<double>& host, double* step_ms, double* resid_ss, double* resid_sum)
+{
+    auto& b = c->mg;
+    const int T = b.nt, nsl = c->nslices;
+    const size_t nstat = (size_t)T * (size_t)(rec + 2 * nsl);
+    if (int rc = mega_upload_params(c, par)) return rc;
+    if (int rc = step_timer_begin(c)) return rc;
+    HIPCHK(c, hipMemsetAsync(stat, 0, sizeof(double) * nstat, c->stream));
+    jwg::UpdateArgs U = {};
+    U.X = mega_genotypes(c); U.R = b.R; U.partials = b.partials; U.ld = c->ld; U.T = T; U.bs = b.bs;
+    jwg::SampleArgs A = {};
+    A.partials = b.partials; A.xpx = b.xpx; A.par = par; A.alpha = b.ms.alpha; A.beta = b.ms.beta; A.delta = b.ms.delta; A.ev = (jwg::Events*)b.ev;
+    A.stat = stat; A.p = c->p; A.nslices = nsl; A.bs = b.bs; A.T = T; A.iter = iteration; A.first_trait = b.first_trait;
+    split_seed(seed, A.seed_lo, A.seed_hi);
+    jwg::FinishArgs F = {};
+    F.X = mega_genotypes(c); F.R = b.R; F.ev = (const jwg::Events*)b.ev; F.fin = stat + (size_t)T * rec; F.ld = c->ld; F.T = T;
+    const dim3 tiles((unsigned)nsl, (unsigned)((T + jwg::kTT - 1) / jwg::kTT));
+    with_real(c, [&](auto real) {
+        using real_t = decltype(real);
+        for (int64_t k = 0; k < b.nblocks; ++k) {
+            const int64_t j0 = k * b.bs;
+            U.ev = k ? (const jwg::Events*)b.ev : nullptr; U.j0 = j0; U.b = (int32_t)std::min<int64_t>(b.bs, c->p - j0);
+            A.gram = b.gram + k * (int64_t)b.bs * b.bs; A.j0 = j0; A.b = U.b;
+            hipLaunchKernelGGL((jwg::k_mega_update_partial<real_t>), tiles, dim3(256), 0, c->stream, U);
+            hipLaunchKernelGGL(sample, dim3((unsigned)T), dim3(256), 0, c->stream, A);
+        }
+        hipLaunchKernelGGL((jwg::k_mega_finish<real_t>), dim3((unsigned)nsl, (unsigned)T), dim3(256), 0, c->stream, F);
+    });
+    HIPCHK(c, hipGetLastError());
+    host.resize(nstat);
+    if (int rc = step_timer_end(c, host.data(), stat, sizeof(double) * nstat, step_ms)) return rc;
+    for (int k = 0; k < T; ++k) {
+        const double* fin = host.data() + (size_t)T * rec + (size_t)k * nsl * 2;
+        double ss = 0.0, sm = 0.0;
+        for (int sl = 0; sl < nsl; ++sl) { ss += fin[2 * sl]; sm += fin[2 * sl + 1]; }       // slices in order
+        if (resid_ss) resid_ss[k] = ss;
+        if (resid_sum) resid_sum[k] = sm;
+    }
     return JWAS_HIP_OK;
 }
 
@@ -77,15 +129,14 @@ int jwas_hip_mega_begin(jwas_hip_ctx* c, int32_t T, int32_t block_size, int32_t 
     const int64_t p = c->p, ld = c->ld;
     b.nt = T; b.bs = bs; b.nblocks = (p + bs - 1) / bs; b.first_trait = (uint32_t)first_trait; b.mask_words = ld / 32; b.row_cap = ld;
     auto alloc = [&](auto** ptr, size_t bytes) { return alloc_or_nomem(c, b.mem, ptr, bytes, "mega-trait session", mega_free); };
-    const size_t tp = sizeof(double) * (size_t)T * (size_t)p, gramb = sizeof(double) * (size_t)b.nblocks * bs * bs;
+    const size_t gramb = sizeof(double) * (size_t)b.nblocks * bs * bs;
     const size_t maskb = sizeof(uint32_t) * (size_t)T * (size_t)b.mask_words, statb = sizeof(double) * (size_t)T * (size_t)(jwg::kStSize + 2 * c->nslices);
     jwg::Events* ev = nullptr;
     if (int rc = alloc(&b.mask, maskb)) return rc;
     if (int rc = alloc(&b.R, sizeof(double) * (size_t)T * ld)) return rc;
     if (int rc = alloc(&b.xpx, sizeof(double) * (size_t)p)) return rc;
     if (int rc = alloc(&b.gram, gramb)) return rc;
-    for (double** q : {&b.alpha, &b.beta, &b.delta, &b.mean_a, &b.mean_a2, &b.mean_d})
-        if (int rc = alloc(q, tp)) return rc;
+    if (int rc = marker_state_begin(c, b.ms, b.mem, T, "mega-trait session", mega_free)) return rc;
     if (int rc = alloc(&b.partials, sizeof(double) * (size_t)c->nslices * T * bs)) return rc;
     if (int rc = alloc(&b.par, sizeof(double) * (size_t)jwg::kParSize * T)) return rc;
     if (int rc = alloc(&b.stat, statb)) return rc;
@@ -95,12 +146,6 @@ int jwas_hip_mega_begin(jwas_hip_ctx* c, int32_t T, int32_t block_size, int32_t 
     HIPCHK(c, hipMemsetAsync(b.mask, 0, maskb, c->stream));
     HIPCHK(c, hipMemsetAsync(b.R, 0, sizeof(double) * (size_t)T * ld, c->stream));
     HIPCHK(c, hipMemsetAsync(b.gram, 0, gramb, c->stream));
-    for (double* q : {b.alpha, b.beta, b.mean_a, b.mean_a2, b.mean_d}) HIPCHK(c, hipMemsetAsync(q, 0, tp, c->stream));
-    {   // delta starts at ones (Mi.δ, MCMC_BayesianAlphabet.jl:85-117)
-        std::vector<double> ones((size_t)T * (size_t)p, 1.0);
-        HIPCHK(c, hipMemcpyAsync(b.delta, ones.data(), tp, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
     HIPCHK(c, hipMemsetAsync(ev, 0, sizeof(jwg::Events), c->stream));
     with_real(c, [&](auto real) {
         using real_t = decltype(real);
@@ -160,32 +205,13 @@ int jwas_hip_mega_get_residual(jwas_hip_ctx* c, int32_t trait, double* out)
 int jwas_hip_mega_set_state(jwas_hip_ctx* c, int32_t trait, const double* alpha, const double* beta, const double* delta)
 {
     if (int rc = need_trait(c, trait)) return rc;
-    auto& b = c->mg;
-    const size_t cnt = (size_t)c->p, at = (size_t)trait * cnt;
-    for (const double* src : {alpha, beta, delta})
-        if (src)
-            for (size_t i = 0; i < cnt; ++i) NEED(c, std::isfinite(src[i]), JWAS_HIP_EINVAL, "state value %zu is not finite (%g)", i, src[i]);
-    if (delta)
-        for (size_t i = 0; i < cnt; ++i) NEED(c, delta[i] == 0.0 || delta[i] == 1.0, JWAS_HIP_EINVAL, "delta[%zu] = %g is not 0 or 1", i, delta[i]);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (alpha) HIPCHK(c, hipMemcpyAsync(b.alpha + at, alpha, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
-    if (beta) HIPCHK(c, hipMemcpyAsync(b.beta + at, beta, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
-    if (delta) HIPCHK(c, hipMemcpyAsync(b.delta + at, delta, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
+    return marker_state_set(c, c->mg.ms, trait, 1, alpha, beta, delta);
 }
 
 int jwas_hip_mega_get_state(jwas_hip_ctx* c, int32_t trait, double* alpha, double* beta, double* delta)
 {
     if (int rc = need_trait(c, trait)) return rc;
-    auto& b = c->mg;
-    const size_t nb = sizeof(double) * (size_t)c->p, at = (size_t)trait * (size_t)c->p;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (alpha) HIPCHK(c, hipMemcpyAsync(alpha, b.alpha + at, nb, hipMemcpyDeviceToHost, c->stream));
-    if (beta) HIPCHK(c, hipMemcpyAsync(beta, b.beta + at, nb, hipMemcpyDeviceToHost, c->stream));
-    if (delta) HIPCHK(c, hipMemcpyAsync(delta, b.delta + at, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
+    return marker_state_get(c, c->mg.ms, trait, 1, alpha, beta, delta);
 }
 
 int jwas_hip_mega_impute(jwas_hip_ctx* c, const jwas_mega_params* P)
@@ -193,6 +219,7 @@ int jwas_hip_mega_impute(jwas_hip_ctx* c, const jwas_mega_params* P)
     if (int rc = need_mega(c)) return rc;
     if (int rc = mega_params(c, P, false, "jwas_hip_mega_impute")) return rc;
     auto& b = c->mg;
+    if (int rc = mega_upload_params(c, b.par)) return rc;
     if (!b.miss_host.empty()) {
         uint32_t lo, hi;
         split_seed(P->seed, lo, hi);
@@ -201,69 +228,6 @@ int jwas_hip_mega_impute(jwas_hip_ctx* c, const jwas_mega_params* P)
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_mega_sweep(jwas_hip_ctx* c, const jwas_mega_params* P, jwas_mega_stats* S)
-{
-    if (int rc = need_mega(c)) return rc;
-    NEED(c, S, JWAS_HIP_EINVAL, "NULL argument");
-    if (int rc = mega_params(c, P, true, "jwas_hip_mega_sweep")) return rc;
-    auto& b = c->mg;
-    const int T = b.nt, nsl = c->nslices;
-    const size_t nstat = (size_t)T * (size_t)(jwg::kStSize + 2 * nsl);
-    if (int rc = step_timer_begin(c)) return rc;
-    HIPCHK(c, hipMemsetAsync(b.stat, 0, sizeof(double) * nstat, c->stream));
-    jwg::UpdateArgs U = {};
-    U.X = mega_genotypes(c); U.R = b.R; U.partials = b.partials; U.ld = c->ld; U.T = T; U.bs = b.bs;
-    jwg::SampleArgs A = {};
-    A.partials = b.partials; A.xpx = b.xpx; A.par = b.par; A.alpha = b.alpha; A.beta = b.beta; A.delta = b.delta; A.ev = (jwg::Events*)b.ev;
-    A.stat = b.stat; A.p = c->p; A.nslices = nsl; A.bs = b.bs; A.T = T; A.iter = P->iteration; A.first_trait = b.first_trait;
-    split_seed(P->seed, A.seed_lo, A.seed_hi);
-    jwg::FinishArgs F = {};
-    F.X = mega_genotypes(c); F.R = b.R; F.ev = (const jwg::Events*)b.ev; F.fin = b.stat + (size_t)T * jwg::kStSize; F.ld = c->ld; F.T = T;
-    const dim3 tiles((unsigned)nsl, (unsigned)((T + jwg::kTT - 1) / jwg::kTT));
-    with_real(c, [&](auto real) {
-        using real_t = decltype(real);
-        for (int64_t k = 0; k < b.nblocks; ++k) {
-            const int64_t j0 = k * b.bs;
-            U.ev = k ? (const jwg::Events*)b.ev : nullptr; U.j0 = j0; U.b = (int32_t)std::min<int64_t>(b.bs, c->p - j0);
-            A.gram = b.gram + k * (int64_t)b.bs * b.bs; A.j0 = j0; A.b = U.b;
-            hipLaunchKernelGGL((jwg::k_mega_update_partial<real_t>), tiles, dim3(256), 0, c->stream, U);
-            hipLaunchKernelGGL(jwg::k_mega_sample, dim3((unsigned)T), dim3(256), 0, c->stream, A);
-        }
-        hipLaunchKernelGGL((jwg::k_mega_finish<real_t>), dim3((unsigned)nsl, (unsigned)T), dim3(256), 0, c->stream, F);
-    });
-    HIPCHK(c, hipGetLastError());
-    std::vector<double> host(nstat);
-    double ms = 0.0;
-    if (int rc = step_timer_end(c, host.data(), b.stat, sizeof(double) * nstat, &ms)) return rc;
-    S->step_ms = ms;
-    for (int k = 0; k < T; ++k) {
-        const double* st = host.data() + (size_t)k * jwg::kStSize;
-        if (S->sum_delta) S->sum_delta[k] = st[jwg::kStDelta];
-        if (S->beta_ss) S->beta_ss[k] = st[jwg::kStBeta];
-        if (S->alpha_ss) S->alpha_ss[k] = st[jwg::kStAlpha];
-        if (S->n_changed) S->n_changed[k] = st[jwg::kStChanged];
-        const double* fin = host.data() + (size_t)T * jwg::kStSize + (size_t)k * nsl * 2;
-        double ss = 0.0, sm = 0.0;
-        for (int sl = 0; sl < nsl; ++sl) { ss += fin[2 * sl]; sm += fin[2 * sl + 1]; }       // slices in order
-        if (S->resid_ss) S->resid_ss[k] = ss;
-        if (S->resid_sum) S->resid_sum[k] = sm;
-    }
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_mega_accumulate(jwas_hip_ctx* c, double nsamples)
-{
-    if (int rc = need_mega(c)) return rc;
-    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
-    auto& b = c->mg;
-    const int64_t tp = (int64_t)b.nt * c->p;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(jwg::k_mega_accumulate, dim3((unsigned)((tp + 255) / 256)), dim3(256), 0, c->stream, (const double*)b.alpha, (const double*)b.delta, tp,
-                       nsamples, b.mean_a, b.mean_a2, b.mean_d);
-    HIPCHK(c, hipGetLastError());
     return JWAS_HIP_OK;
 }
 
@@ -296,47 +260,46 @@ static int mega_params_r(jwas_hip_ctx* c, const jwas_mega_r_params* P)
     return JWAS_HIP_OK;
 }
 
+int jwas_hip_mega_sweep(jwas_hip_ctx* c, const jwas_mega_params* P, jwas_mega_stats* S)
+{
+    if (int rc = need_mega(c)) return rc;
+    NEED(c, S, JWAS_HIP_EINVAL, "NULL argument");
+    if (int rc = mega_params(c, P, true, "jwas_hip_mega_sweep")) return rc;
+    auto& b = c->mg;
+    std::vector<double> host;
+    if (int rc = mega_run_sweep(c, P->iteration, P->seed, b.par, b.stat, jwg::kStSize, jwg::k_mega_sample, host, &S->step_ms, S->resid_ss, S->resid_sum)) return rc;
+    for (int k = 0; k < b.nt; ++k) {
+        const double* st = host.data() + (size_t)k * jwg::kStSize;
+        if (S->sum_delta) S->sum_delta[k] = st[jwg::kStDelta];
+        if (S->beta_ss) S->beta_ss[k] = st[jwg::kStBeta];
+        if (S->alpha_ss) S->alpha_ss[k] = st[jwg::kStAlpha];
+        if (S->n_changed) S->n_changed[k] = st[jwg::kStChanged];
+    }
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_mega_accumulate(jwas_hip_ctx* c, double nsamples)
+{
+    if (int rc = need_mega(c)) return rc;
+    return marker_state_accumulate<false>(c, c->mg.ms, c->mg.nt, nsamples);
+}
+
 int jwas_hip_mega_sweep_r(jwas_hip_ctx* c, const jwas_mega_r_params* P, jwas_mega_r_stats* S)
 {
     if (int rc = need_mega(c)) return rc;
     NEED(c, S, JWAS_HIP_EINVAL, "NULL argument");
     if (int rc = mega_params_r(c, P)) return rc;
     auto& b = c->mg;
-    const int T = b.nt, nsl = c->nslices;
-    const size_t nstat = (size_t)T * (size_t)(jwg::kStRSize + 2 * nsl);
+    const int T = b.nt;
     HIPCHK(c, hipSetDevice(c->device));
     if (!b.par_r) {
         if (int rc = alloc_or_nomem(c, b.mem, &b.par_r, sizeof(double) * (size_t)jwg::kParRSize * T, "mega-trait session", mega_free)) return rc;
-        if (int rc = alloc_or_nomem(c, b.mem, &b.stat_r, sizeof(double) * nstat, "mega-trait session", mega_free)) return rc;
+        if (int rc = alloc_or_nomem(c, b.mem, &b.stat_r, sizeof(double) * (size_t)T * (size_t)(jwg::kStRSize + 2 * c->nslices), "mega-trait session", mega_free))
+            return rc;
     }
-    HIPCHK(c, hipMemcpyAsync(b.par_r, b.par_host.data(), sizeof(double) * b.par_host.size(), hipMemcpyHostToDevice, c->stream));
-    if (int rc = step_timer_begin(c)) return rc;
-    HIPCHK(c, hipMemsetAsync(b.stat_r, 0, sizeof(double) * nstat, c->stream));
-    jwg::UpdateArgs U = {};
-    U.X = mega_genotypes(c); U.R = b.R; U.partials = b.partials; U.ld = c->ld; U.T = T; U.bs = b.bs;
-    jwg::SampleArgs A = {};
-    A.partials = b.partials; A.xpx = b.xpx; A.par = b.par_r; A.alpha = b.alpha; A.beta = b.beta; A.delta = b.delta; A.ev = (jwg::Events*)b.ev;
-    A.stat = b.stat_r; A.p = c->p; A.nslices = nsl; A.bs = b.bs; A.T = T; A.iter = P->iteration; A.first_trait = b.first_trait;
-    split_seed(P->seed, A.seed_lo, A.seed_hi);
-    jwg::FinishArgs F = {};
-    F.X = mega_genotypes(c); F.R = b.R; F.ev = (const jwg::Events*)b.ev; F.fin = b.stat_r + (size_t)T * jwg::kStRSize; F.ld = c->ld; F.T = T;
-    const dim3 tiles((unsigned)nsl, (unsigned)((T + jwg::kTT - 1) / jwg::kTT));
-    with_real(c, [&](auto real) {
-        using real_t = decltype(real);
-        for (int64_t k = 0; k < b.nblocks; ++k) {
-            const int64_t j0 = k * b.bs;
-            U.ev = k ? (const jwg::Events*)b.ev : nullptr; U.j0 = j0; U.b = (int32_t)std::min<int64_t>(b.bs, c->p - j0);
-            A.gram = b.gram + k * (int64_t)b.bs * b.bs; A.j0 = j0; A.b = U.b;
-            hipLaunchKernelGGL((jwg::k_mega_update_partial<real_t>), tiles, dim3(256), 0, c->stream, U);
-            hipLaunchKernelGGL(jwg::k_mega_sample_r, dim3((unsigned)T), dim3(256), 0, c->stream, A);
-        }
-        hipLaunchKernelGGL((jwg::k_mega_finish<real_t>), dim3((unsigned)nsl, (unsigned)T), dim3(256), 0, c->stream, F);
-    });
-    HIPCHK(c, hipGetLastError());
-    std::vector<double> host(nstat);
-    double ms = 0.0;
-    if (int rc = step_timer_end(c, host.data(), b.stat_r, sizeof(double) * nstat, &ms)) return rc;
-    S->step_ms = ms;
+    std::vector<double> host;
+    if (int rc = mega_run_sweep(c, P->iteration, P->seed, b.par_r, b.stat_r, jwg::kStRSize, jwg::k_mega_sample_r, host, &S->step_ms, S->resid_ss, S->resid_sum))
+        return rc;
     for (int k = 0; k < T; ++k) {
         const double* st = host.data() + (size_t)k * jwg::kStRSize;
         if (S->class_counts)
@@ -345,11 +308,6 @@ int jwas_hip_mega_sweep_r(jwas_hip_ctx* c, const jwas_mega_r_params* P, jwas_meg
         if (S->nnz) S->nnz[k] = st[jwg::kStRNnz];
         if (S->alpha_ss) S->alpha_ss[k] = st[jwg::kStRAlpha];
         if (S->n_changed) S->n_changed[k] = st[jwg::kStRChanged];
-        const double* fin = host.data() + (size_t)T * jwg::kStRSize + (size_t)k * nsl * 2;
-        double ss = 0.0, sm = 0.0;
-        for (int sl = 0; sl < nsl; ++sl) { ss += fin[2 * sl]; sm += fin[2 * sl + 1]; }       // slices in order
-        if (S->resid_ss) S->resid_ss[k] = ss;
-        if (S->resid_sum) S->resid_sum[k] = sm;
     }
     return JWAS_HIP_OK;
 }
@@ -357,14 +315,7 @@ int jwas_hip_mega_sweep_r(jwas_hip_ctx* c, const jwas_mega_r_params* P, jwas_meg
 int jwas_hip_mega_accumulate_r(jwas_hip_ctx* c, double nsamples)
 {
     if (int rc = need_mega(c)) return rc;
-    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
-    auto& b = c->mg;
-    const int64_t tp = (int64_t)b.nt * c->p;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(jwg::k_mega_accumulate_r, dim3((unsigned)((tp + 255) / 256)), dim3(256), 0, c->stream, (const double*)b.alpha, (const double*)b.delta, tp,
-                       nsamples, b.mean_a, b.mean_a2, b.mean_d);
-    HIPCHK(c, hipGetLastError());
-    return JWAS_HIP_OK;
+    return marker_state_accumulate<true>(c, c->mg.ms, c->mg.nt, nsamples);
 }
 
 int jwas_hip_mega_psrf(jwas_hip_ctx* c, double nsamples, double* out)
@@ -378,7 +329,7 @@ int jwas_hip_mega_psrf(jwas_hip_ctx* c, double nsamples, double* out)
     if (!b.psrf)
         if (int rc = alloc_or_nomem(c, b.mem, &b.psrf, sizeof(double) * (size_t)c->p, "mega-trait session", mega_free)) return rc;
     const unsigned blocks = (unsigned)std::min<int64_t>(jwg::kPsrfBlocks, (c->p + 255) / 256);
-    hipLaunchKernelGGL(jwg::k_mega_psrf, dim3(blocks), dim3(256), 0, c->stream, (const double*)b.mean_a, (const double*)b.mean_a2, c->p, (int32_t)b.nt, nsamples,
+    hipLaunchKernelGGL(jwg::k_mega_psrf, dim3(blocks), dim3(256), 0, c->stream, (const double*)b.ms.mean_a, (const double*)b.ms.mean_a2, c->p, (int32_t)b.nt, nsamples,
                        b.psrf);
     HIPCHK(c, hipGetLastError());
     return to_host(c, out, b.psrf, sizeof(double) * (size_t)c->p);
@@ -387,14 +338,7 @@ int jwas_hip_mega_psrf(jwas_hip_ctx* c, double nsamples, double* out)
 int jwas_hip_mega_get_posterior(jwas_hip_ctx* c, int32_t trait, double* mean, double* mean2, double* freq)
 {
     if (int rc = need_trait(c, trait)) return rc;
-    auto& b = c->mg;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = sizeof(double) * (size_t)c->p, at = (size_t)trait * (size_t)c->p;
-    if (mean) HIPCHK(c, hipMemcpyAsync(mean, b.mean_a + at, nb, hipMemcpyDeviceToHost, c->stream));
-    if (mean2) HIPCHK(c, hipMemcpyAsync(mean2, b.mean_a2 + at, nb, hipMemcpyDeviceToHost, c->stream));
-    if (freq) HIPCHK(c, hipMemcpyAsync(freq, b.mean_d + at, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
+    return marker_state_posterior(c, c->mg.ms, trait, mean, mean2, freq);
 }
 
 int jwas_hip_mega_mul_alpha(jwas_hip_ctx* c, int32_t trait, int32_t use_output_rows, double* out)
@@ -418,13 +362,7 @@ int jwas_hip_mega_mul_alpha(jwas_hip_ctx* c, int32_t trait, int32_t use_output_r
         if (int rc = alloc_or_nomem(c, b.mem, &b.row, sizeof(double) * (size_t)ld, "mega-trait session", mega_free)) return rc;
         b.row_cap = ld;
     }
-    with_real(c, [&](auto real) {
-        using real_t = decltype(real);
-        hipLaunchKernelGGL((jwg::k_mega_mul_alpha<real_t>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const real_t*)X, ld, n, c->p,
-                           (const double*)(b.alpha + (size_t)trait * (size_t)c->p), b.row);
-    });
-    HIPCHK(c, hipGetLastError());
-    return to_host(c, out, b.row, sizeof(double) * (size_t)n);
+    return marker_state_mul_alpha(c, b.ms, trait, X, ld, n, b.row, out);
 }
 
 int jwas_hip_mega_get_gram(jwas_hip_ctx* c, int64_t block, int64_t nvalues, double* out, double* out_xpx)

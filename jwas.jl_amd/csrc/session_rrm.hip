@@ -1,6 +1,7 @@
 // session_rrm.hip -- random regression models (rrm.hpp), jwas_hip_rrm_begin .. _end: RRM/RRM.jl:43-57,101-158 and the marker part of
 // RRM/MCMC_BayesianAlphabet_RRM.jl.
 #include "ctx.hpp"
+#include "marker_state.hpp"
 #include "rrm.hpp"
 #include <type_traits>
 
@@ -58,7 +59,7 @@ int jwas_hip_rrm_begin(jwas_hip_ctx* c, int32_t T, int32_t C, int64_t n, const d
     b.T = T; b.C = C; b.bs = bs; b.nblocks = (p + bs - 1) / bs;
     b.mask_host.assign(mask, mask + n);
     auto alloc = [&](auto** ptr, size_t bytes) { return alloc_or_nomem(c, b.mem, ptr, bytes, "RRM session", rrm_free); };
-    const size_t cp = sizeof(double) * (size_t)C * (size_t)p, gramb = sizeof(double) * (size_t)b.nblocks * bs * bs * cells;
+    const size_t gramb = sizeof(double) * (size_t)b.nblocks * bs * bs * cells;
     jwr::Events* ev = nullptr;
     if (int rc = alloc(&b.mask, sizeof(uint64_t) * (size_t)ld)) return rc;
     if (int rc = alloc(&b.phi, sizeof(double) * (size_t)T * C)) return rc;
@@ -66,8 +67,7 @@ int jwas_hip_rrm_begin(jwas_hip_ctx* c, int32_t T, int32_t C, int64_t n, const d
     if (int rc = alloc(&b.W, sizeof(double) * (size_t)T * ld)) return rc;
     if (int rc = alloc(&b.M, sizeof(double) * (size_t)p * cells)) return rc;
     if (int rc = alloc(&b.gram, gramb)) return rc;
-    for (double** q : {&b.alpha, &b.beta, &b.delta, &b.mean_a, &b.mean_a2, &b.mean_d})
-        if (int rc = alloc(q, cp)) return rc;
+    if (int rc = marker_state_begin(c, b.ms, b.mem, C, "RRM session", rrm_free)) return rc;      // (Mi.δ = 1, MCMC_BayesianAlphabet_RRM.jl:53)
     if (int rc = alloc(&b.partials, sizeof(double) * (size_t)c->nslices * bs * C)) return rc;
     if (int rc = alloc(&b.stat, sizeof(double) * (size_t)(jwr::kStSize + c->nslices))) return rc;
     if (int rc = alloc(&b.row, sizeof(double) * (size_t)ld)) return rc;
@@ -78,12 +78,6 @@ int jwas_hip_rrm_begin(jwas_hip_ctx* c, int32_t T, int32_t C, int64_t n, const d
     HIPCHK(c, hipMemcpyAsync(b.phi, phi, sizeof(double) * (size_t)T * C, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(b.W, 0, sizeof(double) * (size_t)T * ld, c->stream));
     HIPCHK(c, hipMemsetAsync(b.gram, 0, gramb, c->stream));
-    for (double* q : {b.alpha, b.beta, b.mean_a, b.mean_a2, b.mean_d}) HIPCHK(c, hipMemsetAsync(q, 0, cp, c->stream));
-    {   // delta starts at ones (Mi.δ, MCMC_BayesianAlphabet_RRM.jl:53)
-        std::vector<double> ones((size_t)C * (size_t)p, 1.0);
-        HIPCHK(c, hipMemcpyAsync(b.delta, ones.data(), cp, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
     HIPCHK(c, hipMemsetAsync(ev, 0, sizeof(jwr::Events), c->stream));
     hipLaunchKernelGGL(jwr::k_rrm_o, dim3((unsigned)c->nslices), dim3(256), 0, c->stream, (const uint64_t*)b.mask, (const double*)b.phi, T, C, ld, b.O);
     with_real_c(c, C, [&](auto real, auto cc) {
@@ -140,32 +134,13 @@ int jwas_hip_rrm_get_residual(jwas_hip_ctx* c, int64_t nvalues, double* out)
 int jwas_hip_rrm_set_state(jwas_hip_ctx* c, const double* alpha, const double* beta, const double* delta)
 {
     if (int rc = need_rrm(c)) return rc;
-    auto& b = c->rr;
-    const size_t cnt = (size_t)b.C * (size_t)c->p;
-    for (const double* src : {alpha, beta, delta})
-        if (src)
-            for (size_t i = 0; i < cnt; ++i) NEED(c, std::isfinite(src[i]), JWAS_HIP_EINVAL, "state value %zu is not finite (%g)", i, src[i]);
-    if (delta)
-        for (size_t i = 0; i < cnt; ++i) NEED(c, delta[i] == 0.0 || delta[i] == 1.0, JWAS_HIP_EINVAL, "delta[%zu] = %g is not 0 or 1", i, delta[i]);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (alpha) HIPCHK(c, hipMemcpyAsync(b.alpha, alpha, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
-    if (beta) HIPCHK(c, hipMemcpyAsync(b.beta, beta, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
-    if (delta) HIPCHK(c, hipMemcpyAsync(b.delta, delta, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
+    return marker_state_set(c, c->rr.ms, 0, c->rr.C, alpha, beta, delta);
 }
 
 int jwas_hip_rrm_get_state(jwas_hip_ctx* c, double* alpha, double* beta, double* delta)
 {
     if (int rc = need_rrm(c)) return rc;
-    auto& b = c->rr;
-    const size_t nb = sizeof(double) * (size_t)b.C * (size_t)c->p;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (alpha) HIPCHK(c, hipMemcpyAsync(alpha, b.alpha, nb, hipMemcpyDeviceToHost, c->stream));
-    if (beta) HIPCHK(c, hipMemcpyAsync(beta, b.beta, nb, hipMemcpyDeviceToHost, c->stream));
-    if (delta) HIPCHK(c, hipMemcpyAsync(delta, b.delta, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
+    return marker_state_get(c, c->rr.ms, 0, c->rr.C, alpha, beta, delta);
 }
 
 int jwas_hip_rrm_sweep(jwas_hip_ctx* c, const jwas_rrm_params* P, jwas_rrm_stats* S)
@@ -205,7 +180,7 @@ int jwas_hip_rrm_sweep(jwas_hip_ctx* c, const jwas_rrm_params* P, jwas_rrm_stats
     jwr::UpdateArgs U = {};
     U.X = rrm_genotypes(c); U.mask = b.mask; U.phi = b.phi; U.W = b.W; U.partials = b.partials; U.ld = c->ld; U.T = b.T; U.bs = b.bs;
     jwr::SampleArgs A = {};
-    A.partials = b.partials; A.M = b.M; A.phi = b.phi; A.alpha = b.alpha; A.beta = b.beta; A.delta = b.delta; A.ev = (jwr::Events*)b.ev;
+    A.partials = b.partials; A.M = b.M; A.phi = b.phi; A.alpha = b.ms.alpha; A.beta = b.ms.beta; A.delta = b.ms.delta; A.ev = (jwr::Events*)b.ev;
     A.stat = b.stat; A.ie = 1.0 / P->vare; A.p = c->p; A.nslices = c->nslices; A.bs = b.bs; A.T = b.T; A.iter = P->iteration;
     split_seed(P->seed, A.seed_lo, A.seed_hi);
     for (int i = 0; i < C * C; ++i) A.Ginv[i] = Gi[i];
@@ -243,28 +218,14 @@ int jwas_hip_rrm_sweep(jwas_hip_ctx* c, const jwas_rrm_params* P, jwas_rrm_stats
 int jwas_hip_rrm_accumulate(jwas_hip_ctx* c, double nsamples)
 {
     if (int rc = need_rrm(c)) return rc;
-    NEED(c, nsamples >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1 (got %g)", nsamples);
-    auto& b = c->rr;
-    const int64_t cp = (int64_t)b.C * c->p;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(jwr::k_rrm_accumulate, dim3((unsigned)((cp + 255) / 256)), dim3(256), 0, c->stream, (const double*)b.alpha, (const double*)b.delta, cp,
-                       nsamples, b.mean_a, b.mean_a2, b.mean_d);
-    HIPCHK(c, hipGetLastError());
-    return JWAS_HIP_OK;
+    return marker_state_accumulate<false>(c, c->rr.ms, c->rr.C, nsamples);
 }
 
 int jwas_hip_rrm_get_posterior(jwas_hip_ctx* c, int32_t q, double* mean, double* mean2, double* freq)
 {
     if (int rc = need_rrm(c)) return rc;
-    auto& b = c->rr;
-    NEED(c, q >= 0 && q < b.C, JWAS_HIP_EINVAL, "coefficient %d outside [0,%d)", q, b.C);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = sizeof(double) * (size_t)c->p, at = (size_t)q * (size_t)c->p;
-    if (mean) HIPCHK(c, hipMemcpyAsync(mean, b.mean_a + at, nb, hipMemcpyDeviceToHost, c->stream));
-    if (mean2) HIPCHK(c, hipMemcpyAsync(mean2, b.mean_a2 + at, nb, hipMemcpyDeviceToHost, c->stream));
-    if (freq) HIPCHK(c, hipMemcpyAsync(freq, b.mean_d + at, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
+    NEED(c, q >= 0 && q < c->rr.C, JWAS_HIP_EINVAL, "coefficient %d outside [0,%d)", q, c->rr.C);
+    return marker_state_posterior(c, c->rr.ms, q, mean, mean2, freq);
 }
 
 int jwas_hip_rrm_mul_alpha(jwas_hip_ctx* c, int32_t q, double* out)
@@ -274,13 +235,7 @@ int jwas_hip_rrm_mul_alpha(jwas_hip_ctx* c, int32_t q, double* out)
     NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
     NEED(c, q >= 0 && q < b.C, JWAS_HIP_EINVAL, "coefficient %d outside [0,%d)", q, b.C);
     HIPCHK(c, hipSetDevice(c->device));
-    with_real(c, [&](auto real) {
-        using real_t = decltype(real);
-        hipLaunchKernelGGL((jwr::k_rrm_mul_alpha<real_t>), dim3((unsigned)c->nslices), dim3(256), 0, c->stream, (const real_t*)rrm_genotypes(c), c->ld, c->n, c->p,
-                           (const double*)(b.alpha + (size_t)q * (size_t)c->p), b.row);
-    });
-    HIPCHK(c, hipGetLastError());
-    return to_host(c, out, b.row, sizeof(double) * (size_t)c->n);
+    return marker_state_mul_alpha(c, b.ms, q, rrm_genotypes(c), c->ld, c->n, b.row, out);
 }
 
 int jwas_hip_rrm_get_m(jwas_hip_ctx* c, int64_t nvalues, double* out)

@@ -2,9 +2,11 @@
 of the commit the fixture pins -- the parent of the commit that moved the sessions out of csrc/jwas_hip.hip.  Run once on the GPU
 with that commit's library:
 
-    python tests/golden/make_session_golden.py --commit HASH [--lib path/to/libjwas_hip.so] [--out FILE]
+    python tests/golden/make_session_golden.py --commit HASH [--lib path/to/libjwas_hip.so] [--cases block] [--out FILE]
 
-HASH names the commit whose library is loaded; the fixture records it.
+HASH names the commit whose library is loaded; the fixture records it.  --cases block writes tests/golden/block_session_golden.json
+instead: the sessions with a block sweep of their own (BLOCK_CASES), pinned to the parent of the commit that gave them one copy of
+their shared code.
 
 tests/test_gpu_session_golden.py replays the same calls on the current library and requires equal values and digests."""
 import argparse
@@ -16,6 +18,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.join(HERE, "..", ".."), os.path.join(HERE, "..")]
 import session_golden_cases as G  # noqa: E402
 from jwas_jl_amd import _lib  # noqa: E402
+
+
+FIXTURES = {"session": (G.CASES, "session_golden.json"), "block": (G.BLOCK_CASES, "block_session_golden.json")}
 
 
 def rocm_version():
@@ -30,11 +35,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--commit", required=True)
     ap.add_argument("--lib", default="")
-    ap.add_argument("--out", default=os.path.join(HERE, "session_golden.json"))
+    ap.add_argument("--cases", choices=sorted(FIXTURES), default="session")
+    ap.add_argument("--out", default="")
     args = ap.parse_args()
+    cases, default_out = FIXTURES[args.cases]
+    args.out = args.out or os.path.join(HERE, default_out)
     if args.lib:
         _lib.LIB_PATH = os.path.abspath(args.lib)
-    blob = {"commit": args.commit, "rocm": rocm_version(), "cases": {f"{name}/{prec}": G.run_case(name, prec) for name in G.CASES for prec in G.PRECISIONS}}
+    blob = {"commit": args.commit, "rocm": rocm_version(), "cases": {f"{name}/{prec}": G.run_case(name, prec) for name in cases for prec in G.PRECISIONS}}
     with open(args.out, "w") as fh:
         json.dump(blob, fh, separators=(",", ":"), sort_keys=True)
         fh.write("\n")

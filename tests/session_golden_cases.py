@@ -1,5 +1,7 @@
 """The replayed calls behind tests/golden/session_golden.json: one small run of every device session (liabilities, location
-parameters, missing traits, annotation priors, structural equation models), each in a Float32 and a Float64 context.
+parameters, missing traits, annotation priors, structural equation models), each in a Float32 and a Float64 context -- and, as
+BLOCK_CASES behind tests/golden/block_session_golden.json, of the sessions that sweep blocks of markers themselves (mega-trait models,
+several BayesR chains, random regression, GBLUP).
 
 run_case(name, precision) returns what the fixture records for that run:
 
@@ -287,8 +289,179 @@ def _sem(precision, rec):
         hip.close()
 
 
+# ---- the sessions with a block sweep of their own (tests/golden/block_session_golden.json) ---------------------------------------------
+# n = 700 (three 256-row slices, the last ragged), p = 150 with blocks of 64 (three blocks, the last of 22 markers)
+def _genotypes(precision, n, p, rec, seed):
+    import jwas_jl_amd as J
+    rng = np.random.default_rng(seed)
+    X = np.asfortranarray(rng.integers(0, 3, (n, p)).astype(np.float64 if precision == 64 else np.float32))
+    rec.given(X)
+    hip = J.HipEngine(0, precision=precision)
+    hip.load_dense(X)
+    return hip, rng
+
+
+def _stats(rec, tag, st):
+    for key in sorted(st):
+        if key != "step_ms":
+            rec.small(f"{tag}_{key}", st[key])
+
+
+def _state(rec, tag, state):
+    for nm, v in zip(("alpha", "beta", "delta"), state):
+        rec.large(f"{tag}{nm}", v)
+
+
+# mega-trait: T = 9 (two trait tiles of 8, the second with one trait), first_trait = 3, missing cells, pi[0] = 0 (megaBayesC0!), 900
+# output rows (more than the 768 padded training rows: the row buffer grows); then a session of one 150-marker block (bp = 256)
+def _mega(precision, rec):
+    n, p, T = 700, 150, 9
+    hip, rng = _genotypes(precision, n, p, rec, 606)
+    try:
+        Xout = np.asfortranarray(rng.integers(0, 3, (900, p)).astype(hip.dtype))
+        R0 = rng.standard_normal((T, n)) * 1.3 + 0.2
+        missing = rng.random((T, n)) < 0.1
+        rec.given(Xout, R0, missing)
+        vare = 0.5 + 0.125 * np.arange(T)
+        var_effect = 0.02 + 0.005 * np.arange(T)
+        pi = np.array([0.0, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 0.95])
+        hip.load_output_dense(Xout)
+        hip.mega_begin(T, block_size=64, first_trait=3)
+        hip.mega_set_missing(missing)
+        hip.mega_set_residual(R0)
+        hip.mega_impute(iteration=1, seed=41, vare=vare)
+        rec.large("imputed", hip.mega_get_residual())
+        for it in (1, 2, 3):
+            _stats(rec, f"sweep{it}", hip.mega_sweep(iteration=it, seed=41, vare=vare, var_effect=var_effect, pi=pi))
+            hip.mega_accumulate(it)
+        _state(rec, "", hip.mega_get_state())
+        rec.large("residual", hip.mega_get_residual())
+        for k in range(T):
+            for nm, v in zip(("mean", "mean2", "freq"), hip.mega_posterior(k)):
+                rec.large(f"posterior{k}_{nm}", v)
+        rec.large("mul_alpha8", hip.mega_mul_alpha(8))
+        G, xpx = hip.mega_gram(2)
+        rec.large("gram2", G)
+        rec.large("xpx2", xpx)
+        rec.large("mul_alpha0_output_rows", hip.mega_mul_alpha(0, output_rows=True))
+        hip.mega_begin(T, block_size=200, first_trait=3)
+        hip.mega_set_residual(R0)
+        _stats(rec, "one_block", hip.mega_sweep(iteration=1, seed=41, vare=vare, var_effect=var_effect, pi=pi))
+        _state(rec, "one_block_", hip.mega_get_state())
+        rec.large("one_block_residual", hip.mega_get_residual())
+        hip.mega_end()
+        rec.error(hip.mega_posterior, 0)
+        rec.sharded(hip, hip.mega_begin, T, 64, 3)
+    finally:
+        hip.close()
+
+
+# K = 3 BayesR chains of one model: pi differs per chain, class 3 has probability 0 in chain 1
+def _mega_chains(precision, rec):
+    n, p, K = 700, 150, 3
+    hip, rng = _genotypes(precision, n, p, rec, 707)
+    try:
+        r0 = rng.standard_normal(n) * 1.3 + 0.2
+        rec.given(r0)
+        vare, sigma2 = [0.5, 0.625, 0.75], [0.05, 0.0625, 0.075]
+        gamma = [0.0, 0.01, 0.1, 1.0]
+        pi = np.array([[0.9, 0.05, 0.03, 0.02], [0.8, 0.15, 0.0, 0.05], [0.7, 0.1, 0.1, 0.1]]).T
+        hip.mega_begin(K, block_size=64, first_trait=3)
+        hip.mega_set_residual(np.tile(r0, (K, 1)))
+        for it in (1, 2, 3):
+            _stats(rec, f"sweep{it}", hip.mega_sweep_r(iteration=it, seed=43, vare=vare, var_effect=sigma2, gamma=gamma, pi=pi))
+            hip.mega_accumulate_r(it)
+        _state(rec, "", hip.mega_get_state())
+        rec.large("residual", hip.mega_get_residual())
+        for k in range(K):
+            for nm, v in zip(("mean", "mean2", "freq"), hip.mega_posterior(k)):
+                rec.large(f"posterior{k}_{nm}", v)
+        rec.large("psrf", hip.mega_psrf(3))
+        hip.mega_end()
+        rec.error(hip.mega_psrf, 3)
+        rec.sharded(hip, hip.mega_begin, K, 64, 3)
+    finally:
+        hip.close()
+
+
+# random regression: T = 5 time points, c = 2, 3, 4 coefficients (every instantiation of the sampler), one state with prior 0
+def _rrm(c):
+    def run(precision, rec):
+        n, p, T = 700, 150, 5
+        hip, rng = _genotypes(precision, n, p, rec, 808)
+        try:
+            Phi = rng.uniform(-1.0, 1.0, (T, c))
+            observed = rng.random((T, n)) < 0.8
+            W0 = rng.standard_normal((T, n)) * 1.3 + 0.2
+            rec.given(Phi, observed, W0)
+            G = 0.0625 * np.eye(c) + 0.015625
+            log_pi = -1.0 - 0.25 * np.arange(1 << c)
+            log_pi[2] = -np.inf
+            hip.rrm_begin(Phi, observed, block_size=64)
+            hip.rrm_set_residual(W0)
+            for it in (1, 2, 3):
+                _stats(rec, f"sweep{it}", hip.rrm_sweep(iteration=it, seed=47, vare=0.75, G=G, log_pi=log_pi))
+                hip.rrm_accumulate(it)
+            _state(rec, "", hip.rrm_get_state())
+            rec.large("residual", hip.rrm_get_residual())
+            for q in range(c):
+                for nm, v in zip(("mean", "mean2", "freq"), hip.rrm_posterior(q)):
+                    rec.large(f"posterior{q}_{nm}", v)
+            rec.large("mul_alpha", hip.rrm_mul_alpha(c - 1))
+            rec.large("m", hip.rrm_m())
+            rec.large("gram2", hip.rrm_gram(2))
+            hip.rrm_end()
+            rec.error(hip.rrm_posterior, 0)
+            rec.sharded(hip, hip.rrm_begin, Phi, observed, 64)
+        finally:
+            hip.close()
+    return run
+
+
+# GBLUP: n = 300, a random dense n x n matrix in the place of the eigenvectors (the replay pins bits; a LAPACK factorisation here would
+# tie the inputs to the BLAS build).  The diagonal three-trait step draws with first_trait = 1: first_trait + T <= 4 is the entry
+# point's own limit.
+def _gblup(t, diagonal, first_trait):
+    def run(precision, rec):
+        n = 300
+        rng = np.random.default_rng(909)
+        dtype = np.float64 if precision == 64 else np.float32
+        L = np.asfortranarray((rng.standard_normal((n, n)) / 16.0).astype(dtype))
+        D = rng.uniform(0.05, 4.0, n)
+        r0 = (rng.standard_normal((t, n)) * 1.3 + 0.2).astype(dtype)
+        rec.given(L, D, r0)
+        vare = (np.diag([0.75, 1.0, 1.25]) + 0.125)[:t, :t]
+        G = (np.diag([0.5, 0.375, 0.625]) + 0.0625)[:t, :t]
+        import jwas_jl_amd as J
+        hip = J.HipEngine(0, precision=precision)
+        try:
+            hip.load_dense(L)
+            hip.init_state("BayesC" if t == 1 else "MTBayesC", t)
+            hip.gblup_begin(D)
+            for k in range(t):
+                hip.set_residual(r0[k], k)
+            for it in (1, 2):
+                _stats(rec, f"step{it}", hip.gblup_step(iteration=it, seed=53, vare=vare, G=G, diagonal=diagonal, first_trait=first_trait))
+                rec.large(f"rhs{it}", hip.gblup_rhs())
+            for k in range(t):
+                alpha, beta, _ = hip.get_state(k)
+                rec.large(f"alpha{k}", alpha)
+                rec.large(f"beta{k}", beta)
+            _residuals(hip, rec, t, "")
+            hip.gblup_end()
+            rec.error(hip.gblup_rhs)
+            rec.sharded(hip, hip.gblup_begin, D)
+        finally:
+            hip.close()
+    return run
+
+
+BLOCK_CASES = ("mega", "mega_chains", "rrm_c2", "rrm_c3", "rrm_c4", "gblup_t1", "gblup_t3_joint", "gblup_t3_diag")
+
 _RUN = {"liability": _liability, "locpar": _locpar, "mtmiss": _mtmiss, "sem": _sem,
-        "annot_BayesC": _annot("BayesC"), "annot_BayesR": _annot("BayesR"), "annot_tree": _annot("tree")}
+        "annot_BayesC": _annot("BayesC"), "annot_BayesR": _annot("BayesR"), "annot_tree": _annot("tree"),
+        "mega": _mega, "mega_chains": _mega_chains, "rrm_c2": _rrm(2), "rrm_c3": _rrm(3), "rrm_c4": _rrm(4),
+        "gblup_t1": _gblup(1, True, 0), "gblup_t3_joint": _gblup(3, False, 0), "gblup_t3_diag": _gblup(3, True, 1)}
 
 
 def run_case(name, precision):

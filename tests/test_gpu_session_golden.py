@@ -4,7 +4,11 @@ The sessions' host code moved out of csrc/jwas_hip.hip into one unit each on sha
 shared device helpers (csrc/device_util.hpp), with the order of every floating-point operation kept.  tests/golden/session_golden.json
 holds what the parent commit's library returned for the calls of tests/session_golden_cases.py (written by
 tests/golden/make_session_golden.py on the GPU): the small outputs in full, SHA-256 digests of the large ones, and the code and message
-of the guards.  The replay must be EQUAL: there is no tolerance, the reference is the parent's own output."""
+of the guards.  The replay must be EQUAL: there is no tolerance, the reference is the parent's own output.
+
+tests/golden/block_session_golden.json does the same for the sessions that sweep blocks of markers themselves (mega-trait models, several
+BayesR chains, random regression, GBLUP; G.BLOCK_CASES): written by the parent of the commit that gave them one copy of their shared
+device helpers (csrc/device_util.hpp), marker state (csrc/marker_state.hpp) and block walk (csrc/mega.hpp)."""
 import json
 import os
 
@@ -17,21 +21,38 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def golden():
-    with open(os.path.join(ROOT, "tests", "golden", "session_golden.json")) as fh:
+def _load(fixture):
+    with open(os.path.join(ROOT, "tests", "golden", fixture)) as fh:
         return json.load(fh)
 
 
-def test_fixture_covers_every_case(golden):
-    assert sorted(golden["cases"]) == sorted(f"{name}/{prec}" for name in G.CASES for prec in G.PRECISIONS)
+@pytest.fixture(scope="module")
+def golden():
+    return _load("session_golden.json")
+
+
+@pytest.fixture(scope="module")
+def block_golden():
+    return _load("block_session_golden.json")
+
+
+def _covers(golden, cases):
+    assert sorted(golden["cases"]) == sorted(f"{name}/{prec}" for name in cases for prec in G.PRECISIONS)
     assert golden["rocm"] and len(golden["commit"]) == 40                   # (the commit whose library wrote it)
 
 
+def test_fixture_covers_every_case(golden):
+    _covers(golden, G.CASES)
+
+
+def test_block_fixture_covers_every_case(block_golden):
+    _covers(block_golden, G.BLOCK_CASES)
+
+
 @pytest.mark.parametrize("precision", G.PRECISIONS)
-@pytest.mark.parametrize("name", G.CASES)
-def test_session_is_the_parent_commits_bit_for_bit(golden, name, precision):
-    want = golden["cases"][f"{name}/{precision}"]
+@pytest.mark.parametrize("name", G.CASES + G.BLOCK_CASES)
+def test_session_is_the_parent_commits_bit_for_bit(golden, block_golden, name, precision):
+    want = (block_golden if name in G.BLOCK_CASES else golden)["cases"][f"{name}/{precision}"]
     got = G.run_case(name, precision)
     assert got["inputs"] == want["inputs"], "the generated inputs differ from the fixture's (numpy's generator, not the library)"
     assert sorted(got["values"]) == sorted(want["values"]) and sorted(got["digests"]) == sorted(want["digests"])
