@@ -49,7 +49,38 @@ struct MarkerState {
     double *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;
 };
 
-struct jwas_hip_ctx {
+// What exists once per precision, under one name in both: the Float32 context holds a Side<float> (as its base: c->alpha), a Float64
+// context a Side<double> besides (c->f64->alpha); side<T>(c) picks one.  Two owners: chain_mem for what jwas_hip_init_state replaces,
+// load_mem for what a load of genotypes replaces; dropping is release() and a value reset, so no member can be forgotten in a free list.
+template <class T>
+struct ChainState {
+    DevOwner chain_mem;
+    T *alpha = nullptr, *beta = nullptr;        // [t][p]
+    void* delta = nullptr;                      // T [t][p], or int32 [p] (BayesR classes)
+    T *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;
+    T* var_vec = nullptr;                       // [p] BayesB
+    T* var_mat = nullptr;                       // [p][t][t] per-marker effect covariances (multi-trait BayesA/B)
+    T* ginv_mat = nullptr;                      // [p][t][t] their inverses
+    bool var_mat_resident = false;              // var_mat holds this chain's covariances (uploaded or drawn on the device)
+    void drop_chain() { chain_mem.release(); *this = ChainState(); }
+};
+template <class T>
+struct Side : ChainState<T> {
+    typedef T real;
+    DevOwner load_mem;
+    T* X = nullptr;                             // [p][ld] dense genotypes, marker-major (NULL: none, or 2-bit packed storage)
+    T* r = nullptr;                             // [2][kMaxT][ld] residuals, ping-pong; buffer 0 is current between sweeps
+    T* w = nullptr;                             // [ld] residual weights R^-1 (ones unless jwas_hip_set_weights; pad rows 0)
+    bool weighted = false;                      // w differs from ones
+    T* xpx = nullptr;                           // [p]
+    T* Xout = nullptr;                          // [p][ld_out] output (EBV) rows: Mi.output_genotypes (tools4genotypes.jl:290-296)
+    int64_t n_out = 0, ld_out = 0;
+    int32_t* cmp_idx = nullptr;                 // [p] + [1] compacted nonzero effects of one trait (k_compact_alpha) and their number
+    T* cmp_val = nullptr;                       // [p]
+    void drop() { this->chain_mem.release(); load_mem.release(); *this = Side(); }
+};
+
+struct jwas_hip_ctx : Side<float> {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -60,13 +91,10 @@ struct jwas_hip_ctx {
     int upd_nslices = 0;                // slices of the UPDATE role: = nslices (dense), 1024-row slices on 2-bit packed storage (update_role_wide)
     int nrg = 0, ncg = 1;               // k_update_partial grid: row groups x column groups
     int spg = 8;                        // slices per row group
-    float* X = nullptr;                 // dense fp32 storage ...
-    uint8_t* Q = nullptr;               // ... or the reference's 2-bit packed storage [p][ld/4] + per-marker means
+    uint8_t* Q = nullptr;               // the reference's 2-bit packed storage [p][ld/4] + per-marker means, in the place of the dense X
     float* qmean = nullptr;
     bool packed = false;
     int centered = 1;
-    float* w = nullptr;                 // [ld] residual weights R^-1 (ones unless jwas_hip_set_weights; pad rows 0)
-    bool weighted = false;
 
     // Active block configuration (a view of one entry of `sets`; several block sizes can be resident so the host
     // can pick per sweep: big blocks when few markers change, smaller ones when many do).
@@ -86,17 +114,11 @@ struct jwas_hip_ctx {
     int64_t* d_starts = nullptr;        // ... on the device
     int block_size = 0;
     int64_t nblocks = 0;
-    float* xpx = nullptr;
     float* gram = nullptr;
     float* cross = nullptr;             // cross-Grams X_{b-1}'X_b, block b at offset b*bs*bs (block 0 unused)
     float* corr = nullptr;              // [2][kMaxT][bs] lookahead corrections (ping-pong: read by launch k, written for k+1)
 
     int method = -1, ntraits = 0;
-    float* r = nullptr;                 // [2][kMaxT][ld] ping-pong; buffer 0 is current between sweeps
-    float *alpha = nullptr, *beta = nullptr;
-    void* delta = nullptr;
-    float *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;
-
     double* partials = nullptr;
     jw::Events* ev = nullptr;               // [2]
     // independent-block mode (allocated on first use)
@@ -119,12 +141,6 @@ struct jwas_hip_ctx {
     size_t  tsec_cap = 0;               // ... capacity in floats
     unsigned long long* xch = nullptr;  // Rule T: [kMaxT][256] {value, tag} words: the sampler workgroup's hand-over to the helper workgroup
     int     xch_epoch = 0;              // ... grows by 8 per launch
-    float*  Xout = nullptr;             // output (EBV) rows: [p][ld_out] fp32, Mi.output_genotypes (tools4genotypes.jl:290-296)
-    int64_t n_out = 0, ld_out = 0;
-    float*  var_vec = nullptr;
-    float*  var_mat = nullptr;          // p x t x t per-marker effect covariances (multi-trait BayesA/B), uploaded per sweep
-    float*  ginv_mat = nullptr;         // their inverses (k_prepare)
-    bool    var_mat_resident = false;   // var_mat holds this chain's per-marker covariances (uploaded or drawn on the device)
     double* pi_vec = nullptr;
     double* pi_mat = nullptr;
     double* lpr_mat = nullptr;          // p x 2^t marker-specific multi-trait log priors
@@ -139,8 +155,6 @@ struct jwas_hip_ctx {
     double event_overhead_ms = 0.0;     // mean HIP-event interval around an empty launch (calibration)
     std::vector<hipEvent_t> kev;        // pairs of events around sampled k_update_partial launches
     // marker-shard reconcile (jwas_hip_comm_init / jwas_hip_sweep_sharded): RCCL communicator on this context's device
-    int32_t* cmp_idx = nullptr;         // [p] + [1] compacted nonzero effects of one trait (k_compact_alpha)
-    float* cmp_val = nullptr;           // [p]
     void* comm = nullptr;               // ncclComm_t
     int comm_rank = 0, comm_world = 1;
     float* r_snap = nullptr;            // [kMaxT][ld] residual snapshot of the running sweep
@@ -151,33 +165,17 @@ struct jwas_hip_ctx {
     int loop_slot = -1;                 // >= 0: loopback transport (ranks = contexts of one process on different host threads)
     double* row_buf = nullptr;          // [32] small exchanges
     // Float64 mode (runMCMC(double_precision=true); csrc/f64_path.hpp): its own storage / state, created by jwas_hip_set_precision
-    struct F64 {
-        double* X = nullptr;                // [p][ld]
-        double* r = nullptr;                // [kMaxT][ld]
-        double* xpx = nullptr;              // [p]
+    struct F64 : Side<double> {
         double* gram = nullptr;             // [nblocks][bs][bs]
-        double *alpha = nullptr, *beta = nullptr;      // [t][p]
-        void* delta = nullptr;              // double [t][p], or int32 [p] (BayesR classes)
-        double *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;
         double* partials = nullptr;         // [kMaxT][nslices][bstride]  (independent blocks: one such set per block)
         size_t partials_cap = 0;            // ... in doubles
         jw64::Events64* ev = nullptr;       // [2]  (independent blocks: ev_all, one per block)
         jw64::Events64* ev_all = nullptr;
         int64_t ev_all_cap = 0;
         jw64::Params64* dparams = nullptr;
-        double* var_vec = nullptr;          // [p] BayesB
-        double* var_mat = nullptr;          // [p][t][t] multi-trait BayesA/B: per-marker effect covariances
-        double* ginv_mat = nullptr;         // [p][t][t] their inverses (k64_invert_marker_cov, once per sweep)
-        bool var_mat_resident = false;      // var_mat holds this chain's covariances (uploaded or drawn on the device)
-        double* w = nullptr;                // [ld] residual weights R^-1 (pad rows 0; ones when unweighted)
         std::vector<int64_t> starts;        // block starts (nblocks + 1 entries, 0-based): uniform or explicit partition
         int bstride = 0;                    // largest block of the partition, rounded up to a multiple of 8
         bool explicit_part = false;
-        bool weighted = false;              // w differs from ones (jwas_hip_set_weights_f64)
-        double* Xout = nullptr;             // [p][ld_out] output rows (jwas_hip_load_output_dense_f64)
-        int64_t n_out = 0, ld_out = 0;
-        int32_t* cmp_idx = nullptr;         // [p] + [1] compacted nonzero effects of one trait (k64_compact_alpha)
-        double* cmp_val = nullptr;          // [p]
     };
     F64* f64 = nullptr;
     // GWAS session (jwas_hip_gwas_begin .. jwas_hip_gwas_end; GWAS.jl:149-173): everything a saved sample needs stays resident
@@ -378,10 +376,37 @@ JW_LOCAL int fail(jwas_hip_ctx* ctx, int code, const char* fmt, ...);      // (j
 #define NOT_F64(c, what) NEED(c, !IS_F64(c), JWAS_HIP_EUNSUP, "%s is not available in a Float64 context (double_precision=true)", what)
 #define ONLY_F64(c) NEED(c, IS_F64(c), JWAS_HIP_ESTATE, "this entry point needs a Float64 context (jwas_hip_set_precision(ctx, 64))")
 
+#define HAVE_STORAGE(c) ((c)->X != nullptr || (c)->Q != nullptr)      // (of a Float32 context)
+#define NEED_TRAIT(c, trait)                                                                       \
+    NEED(c, c->method >= 0, JWAS_HIP_ESTATE, "jwas_hip_init_state has not been called");           \
+    NEED(c, trait >= 0 && trait < c->ntraits, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->ntraits)
+
 static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-// the resident residual [kMaxT][ld], in the context's element type (NULL: no genotypes loaded)
-static inline void* residual_ptr(jwas_hip_ctx* c) { return IS_F64(c) ? (void*)c->f64->r : (void*)c->r; }
+// f(T{}) with T the context's element type: one launch of k<T> instead of a float / double pair
+template <class F>
+static void with_real(jwas_hip_ctx* c, F&& f) { if (IS_F64(c)) f(double{}); else f(float{}); }
+
+// the context's half of element type T (double: of a Float64 context only)
+template <class T> static inline Side<T>& side(jwas_hip_ctx* c);
+template <> inline Side<float>& side<float>(jwas_hip_ctx* c) { return *c; }
+template <> inline Side<double>& side<double>(jwas_hip_ctx* c) { return *c->f64; }
+
+// f(S) with S the half of the context's own precision
+template <class F>
+static auto on_side(jwas_hip_ctx* c, F&& f) { return IS_F64(c) ? f(side<double>(c)) : f(side<float>(c)); }
+
+// Members of that half as the sessions read them, in the context's element type.
+static inline void* residual_ptr(jwas_hip_ctx* c) { return on_side(c, [](auto& S) { return (void*)S.r; }); }      // [kMaxT][ld] (NULL: no genotypes loaded)
+static inline const void* genotypes_ptr(jwas_hip_ctx* c) { return on_side(c, [](auto& S) { return (const void*)S.X; }); }      // the dense matrix (NULL: none, or packed)
+static inline bool is_weighted(jwas_hip_ctx* c) { return on_side(c, [](auto& S) { return S.weighted; }); }
+static inline void* alpha_ptr(jwas_hip_ctx* c) { return on_side(c, [](auto& S) { return (void*)S.alpha; }); }
+static inline void* beta_ptr(jwas_hip_ctx* c) { return on_side(c, [](auto& S) { return (void*)S.beta; }); }
+// the output rows (NULL: none loaded), their number and leading dimension
+static inline const void* output_rows_ptr(jwas_hip_ctx* c, int64_t* n_out, int64_t* ld_out)
+{
+    return on_side(c, [&](auto& S) { *n_out = S.n_out; *ld_out = S.ld_out; return (const void*)S.Xout; });
+}
 
 // t x t inverse (t <= JWAS_HIP_MAX_TRAITS): Gauss-Jordan in double with partial pivoting, rounded to the element type at the end (float: it
 // stands in for Julia's inv(::Matrix{Float32}), MTBayesABC.jl:66-67).  Same operation sequence as the oracle's.
@@ -418,6 +443,7 @@ JW_LOCAL void rrm_free(jwas_hip_ctx* c);
 JW_LOCAL void mega_free(jwas_hip_ctx* c);
 JW_LOCAL void ss_free(jwas_hip_ctx* c);
 JW_LOCAL void gblup_free(jwas_hip_ctx* c);
+JW_LOCAL void gwas_free(jwas_hip_ctx* c);                                  // (output.hip: the GWAS session)
 
 // `words` ("liabilities", "annotation priors", ...) are not driven from a context that holds a marker or row shard
 static inline int refuse_shards(jwas_hip_ctx* c, const char* words)
@@ -473,10 +499,6 @@ static int alloc_or_nomem(jwas_hip_ctx* c, DevOwner& owner, T** p, size_t bytes,
 }
 
 static inline void split_seed(uint64_t seed, uint32_t& lo, uint32_t& hi) { lo = (uint32_t)(seed & 0xFFFFFFFFu); hi = (uint32_t)(seed >> 32); }
-
-// f(T{}) with T the context's element type: one launch of k<T> instead of a float / double pair
-template <class F>
-static void with_real(jwas_hip_ctx* c, F&& f) { if (IS_F64(c)) f(double{}); else f(float{}); }
 
 // dev -> host on the context's stream, then wait for it
 static inline int to_host(jwas_hip_ctx* c, void* out, const void* dev, size_t bytes)

@@ -711,172 +711,4 @@ __global__ __launch_bounds__(256) void k64_marker_stats(int method, int64_t p, c
         for (int i = 0; i < kNStat; ++i) out[(int64_t)blockIdx.x * kNStat + i] = v[i];
 }
 
-// ---- running posterior means (output.jl:556-560) -----------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k64_accumulate(int64_t count, int delta_is_class, double k, const double* __restrict__ alpha,
-                                                      const void* __restrict__ delta, double* __restrict__ ma, double* __restrict__ ma2, double* __restrict__ md)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const double a = alpha[i];
-    const double d = delta_is_class ? (reinterpret_cast<const int32_t*>(delta)[i] > 1 ? 1.0 : 0.0) : reinterpret_cast<const double*>(delta)[i];
-    ma[i] += (a - ma[i]) / k;
-    ma2[i] += (a * a - ma2[i]) / k;
-    md[i] += (d - md[i]) / k;
-}
-
-// ---- out = X alpha (getEBV, output.jl:281-306); r -= X alpha (initial ycorr) ---------------------------------------------
-__global__ __launch_bounds__(256) void k64_mul_alpha(const double* __restrict__ X, int64_t ld, int64_t p, const double* __restrict__ alpha,
-                                                     double* __restrict__ out, double sign, const double* __restrict__ base)
-{
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    double acc = base ? base[row] : 0.0;
-    for (int64_t j = 0; j < p; ++j) {
-        const double a = alpha[j];
-        if (a != 0.0) acc = fma(sign * a, X[j * ld + row], acc);
-    }
-    out[row] = acc;
-}
-
-// ---- the output side of a Float64 chain: sparse samples, EBVs over the nonzero effects, window sums ------------------------
-// The nonzero effects of one trait as (index, value) lists in marker order: k_compact_alpha with double values.  grid = 1,
-// block = 1024: the workgroup walks the p effects 1024 at a time with a running offset (ballot + wave prefix); idx / val
-// hold p entries, *count the number written.
-__global__ __launch_bounds__(1024) void k64_compact_alpha(int64_t p, const double* __restrict__ alpha, int32_t* __restrict__ idx,
-                                                          double* __restrict__ val, int32_t* __restrict__ count)
-{
-    __shared__ int wsum[16];
-    __shared__ int base_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
-    for (int64_t j0 = 0; j0 < p; j0 += 1024) {
-        const int64_t j = j0 + tid;
-        const double a = j < p ? alpha[j] : 0.0;
-        const bool nz = a != 0.0;
-        const unsigned long long m = __ballot(nz);
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int pre = base_s, tot = 0;
-        for (int w = 0; w < 16; ++w) { if (w < wave) pre += wsum[w]; tot += wsum[w]; }
-        if (nz) {
-            const int pos = pre + __popcll(m & ((1ull << lane) - 1ull));
-            idx[pos] = (int32_t)j; val[pos] = a;
-        }
-        __syncthreads();
-        if (tid == 0) base_s += tot;
-        __syncthreads();
-    }
-    if (tid == 0) *count = base_s;
-}
-
-// K column loads of one row in flight, then their fma chain in list order (acc = fma(val[e], x, acc): k64_mul_alpha's term).
-template <int K, int NV>
-__device__ __forceinline__ void list_terms64(const double* __restrict__ Xrow, int64_t ld, const int32_t* __restrict__ idx, const double* __restrict__ val,
-                                             const double* __restrict__ val2, int e, double& acc, double& acc2)
-{
-    double x[K];
-#pragma unroll
-    for (int u = 0; u < K; ++u) x[u] = Xrow[(int64_t)idx[e + u] * ld];
-#pragma unroll
-    for (int u = 0; u < K; ++u) {
-        acc = fma(val[e + u], x[u], acc);
-        if constexpr (NV == 5) acc2 = fma(val2[e + u], x[u], acc2);
-    }
-}
-
-// out[row] = sum_e val[e] X[idx[e], row] over the compacted list, in marker order: the fma chain of k64_mul_alpha (sign = 1,
-// no base) without the p - nnz loads and branches it spends on zero effects -> the same bits.  One row per thread; X is the
-// training or the output matrix (leading dimension ld, a multiple of 64; grid = ld / 64, so every row is inside the padded
-// column).  16 column loads are in flight per thread (then 4, then 1 for the list's tail) and are added in list order: with
-// n / 64 waves on the whole device, a load -> fma chain of depth one leaves the memory system idle.
-__global__ __launch_bounds__(64) void k64_mul_alpha_list(const double* __restrict__ X, int64_t ld, int nnz, const int32_t* __restrict__ idx,
-                                                         const double* __restrict__ val, double* __restrict__ out)
-{
-    const int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    const double* Xrow = X + row;
-    double acc = 0.0, unused = 0.0;
-    int e = 0;
-    for (; e + 16 <= nnz; e += 16) list_terms64<16, 2>(Xrow, ld, idx, val, nullptr, e, acc, unused);
-    for (; e + 4 <= nnz; e += 4) list_terms64<4, 2>(Xrow, ld, idx, val, nullptr, e, acc, unused);
-    for (; e < nnz; ++e) list_terms64<1, 2>(Xrow, ld, idx, val, nullptr, e, acc, unused);
-    out[row] = acc;
-}
-
-// Window genomic values of one marker-effect sample (GWAS.jl:152-165, :199-217) with T = Float64: k_window_partial with double
-// genotypes and effects.  Window w holds the effects idx / val[wptr[w] .. wptr[w+1]); BV_w[i] = sum_j X[i, idx_j] val_j in list
-// order (8 column loads in flight, one for a window's tail).  grid = ld / 256 slices, block = 256 (one individual per thread); partial[(w * nslices +
-// slice) * NV + v]: NV = 2: (sum, sum of squares); NV = 5: two effect vectors over the same markers: (sum1, ss1, sum2, ss2, sum
-// of products).  The lanes of a wave are added by shuffles, the four waves as ((0 + 1) + 2) + 3 and the slices in order by
-// k_window_reduce (its partials are double in both precisions): the association of the Float32 kernels, no atomics.
-template <int NV>
-__global__ __launch_bounds__(256) void k64_window_partial(const double* __restrict__ X, int64_t ld, int nwin, const int32_t* __restrict__ wptr,
-                                                          const int32_t* __restrict__ idx, const double* __restrict__ val,
-                                                          const double* __restrict__ val2, double* __restrict__ partial)
-{
-    __shared__ double red[NV][4];
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double* Xrow = X + row;
-    for (int w = 0; w < nwin; ++w) {
-        double bv = 0.0, bv2 = 0.0;
-        const int e_hi = wptr[w + 1];
-        int e = wptr[w];
-        for (; e + 8 <= e_hi; e += 8) list_terms64<8, NV>(Xrow, ld, idx, val, val2, e, bv, bv2);
-        for (; e < e_hi; ++e) list_terms64<1, NV>(Xrow, ld, idx, val, val2, e, bv, bv2);
-        double v[NV];
-        v[0] = bv; v[1] = bv * bv;
-        if constexpr (NV == 5) { v[2] = bv2; v[3] = bv2 * bv2; v[4] = bv * bv2; }
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-            if (lane == 0) red[k][wave] = v[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < NV)
-            partial[((int64_t)w * gridDim.x + blockIdx.x) * NV + threadIdx.x] =
-                ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
-        __syncthreads();
-    }
-}
-
-// The GWAS session's partial kernel (kernels.hpp: k_gwas_partial) with T = Float64 (GWAS.jl:149-173): grid = (ld / 256 slices,
-// entry chunks), block = 256; chunk 0 is entry 0 ("all markers"), chunk 1 + k the windows [k wpc, (k + 1) wpc); entry e owns the
-// slice [lo[e], hi[e]) of the sample's ascending (idx, val) list.  16 / 4 / 1 column loads in flight, added in list order by
-// list_terms64's fma chain, then k64_window_partial's reduction: the bits of jwas_hip_window_sums_f64.  LEBV: the running sum
-// of the local EBVs, acc[w * ld + row] += BV_w[row].
-template <bool LEBV>
-__global__ __launch_bounds__(256) void k64_gwas_partial(const double* __restrict__ X, int64_t ld, int nent, int wpc, const int32_t* __restrict__ lo,
-                                                        const int32_t* __restrict__ hi, const int32_t* __restrict__ idx, const double* __restrict__ val,
-                                                        double* __restrict__ partial, double* __restrict__ acc)
-{
-    __shared__ double red[2][4];
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double* Xrow = X + row;
-    const int w0 = blockIdx.y == 0 ? 0 : 1 + ((int)blockIdx.y - 1) * wpc;
-    const int w1 = blockIdx.y == 0 ? 1 : (w0 + wpc < nent ? w0 + wpc : nent);
-    for (int w = w0; w < w1; ++w) {
-        double bv = 0.0, unused = 0.0;
-        const int e_lo = lo[w], e_hi = hi[w];
-        int e = e_lo;
-        for (; e + 16 <= e_hi; e += 16) list_terms64<16, 2>(Xrow, ld, idx, val, nullptr, e, bv, unused);
-        for (; e + 4 <= e_hi; e += 4) list_terms64<4, 2>(Xrow, ld, idx, val, nullptr, e, bv, unused);
-        for (; e < e_hi; ++e) list_terms64<1, 2>(Xrow, ld, idx, val, nullptr, e, bv, unused);
-        if constexpr (LEBV) { if (w >= 1 && e_hi > e_lo) acc[(int64_t)(w - 1) * ld + row] += bv; }
-        double v[2];
-        v[0] = bv; v[1] = bv * bv;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-            if (lane == 0) red[k][wave] = v[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < 2)
-            partial[((int64_t)w * gridDim.x + blockIdx.x) * 2 + threadIdx.x] =
-                ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
-        __syncthreads();
-    }
-}
 }  // namespace jw64

@@ -1,9 +1,11 @@
-// jwas_hip.hip -- context, memory, the sweep and the GWAS session behind the C ABI of libjwas_hip.so (see include/jwas_hip.h).
-// The context itself and the shared host plumbing: ctx.hpp; the other sessions: session_*.hip, one unit each.
+// jwas_hip.hip -- context, memory, blocks and the sweep behind the C ABI of libjwas_hip.so (see include/jwas_hip.h).
+// The context itself and the shared host plumbing: ctx.hpp; the output side of both precisions and the GWAS session: output.hip; the
+// other sessions: session_*.hip, one unit each.
 // gfx950 only.  No CPU fallback: every entry point either runs the HIP path or returns an error.
 #include "../../include/jwas_hip.h"
 #include "ctx.hpp"
 #include "sweep.hpp"
+#include "output.hpp"      // (with_cols: the view of the Float32 storage)
 #include "f64_path.hpp"
 #include "step_launch.hpp"
 
@@ -42,14 +44,6 @@ int fail(jwas_hip_ctx* ctx, int code, const char* fmt, ...)      // (declared in
     return code;
 }
 
-// Run f(cols) with the accessor of the context's storage (columns from j_off on).
-template <class F>
-static auto with_cols(jwas_hip_ctx* c, int64_t j_off, F&& f)
-{
-    if (c->packed) return f(PackedCols{c->Q + j_off * (c->ld >> 2), c->ld, c->qmean + j_off, c->n, c->centered, c->w, (int32_t)c->weighted});
-    return f(DenseCols{c->X + j_off * c->ld, c->ld, c->w, (int32_t)c->weighted});
-}
-#define HAVE_STORAGE(c) ((c)->X != nullptr || (c)->Q != nullptr)
 static int f64_setup_blocks(jwas_hip_ctx* c, int32_t bs);
 static int f64_setup_blocks_explicit(jwas_hip_ctx* c, const int64_t* starts, int64_t nblocks);
 static int f64_set_weights(jwas_hip_ctx* c, const float* rinv32, const double* rinv64);
@@ -90,38 +84,26 @@ int jwas_hip_create(int device, jwas_hip_ctx** out)
 
 static void free_state(jwas_hip_ctx* c)
 {
-    (void)hipFree(c->alpha); (void)hipFree(c->beta); (void)hipFree(c->delta);
-    (void)hipFree(c->mean_a); (void)hipFree(c->mean_a2); (void)hipFree(c->mean_d);
+    c->drop_chain();
     (void)hipFree(c->prep_d); (void)hipFree(c->prep_f); c->prep_d = nullptr; c->prep_f = nullptr;
     (void)hipFree(c->mt2_tab); c->mt2_tab = nullptr;
     (void)hipFree(c->tsec); c->tsec = nullptr; c->tsec_cap = 0;
     (void)hipFree(c->xch); c->xch = nullptr;
-    (void)hipFree(c->cmp_idx); (void)hipFree(c->cmp_val); c->cmp_idx = nullptr; c->cmp_val = nullptr;
-    c->alpha = c->beta = nullptr; c->delta = nullptr; c->mean_a = c->mean_a2 = c->mean_d = nullptr;
-    (void)hipFree(c->var_mat); (void)hipFree(c->ginv_mat); c->var_mat = nullptr; c->ginv_mat = nullptr; c->var_mat_resident = false;
 }
 
 static void free_blocks(jwas_hip_ctx* c)
 {
-    (void)hipFree(c->xpx);
+    c->load_mem.free_one(c->xpx);
     for (auto& b : c->sets) {
         (void)hipFree(b.gram); (void)hipFree(b.cross); (void)hipFree(b.corr); (void)hipFree(b.partials);
         (void)hipFree(b.gcross[0]); (void)hipFree(b.gcross[1]); (void)hipFree(b.gcbuf); (void)hipFree(b.gidx); (void)hipFree(b.gdelta); (void)hipFree(b.gpp);
     }
     c->sets.clear();
-    c->xpx = c->gram = c->cross = c->corr = nullptr; c->partials = nullptr;
+    c->gram = c->cross = c->corr = nullptr; c->partials = nullptr;
     c->block_size = 0; c->nblocks = 0;
     c->starts.clear(); (void)hipFree(c->d_starts); c->d_starts = nullptr;
     (void)hipFree(c->ipartials); (void)hipFree(c->ev_all); (void)hipFree(c->ev_offs); (void)hipFree(c->idx_all); (void)hipFree(c->delta_all);
     c->ipartials = nullptr; c->ev_all = nullptr; c->ev_offs = nullptr; c->idx_all = nullptr; c->delta_all = nullptr; c->ind_traits = 0;
-}
-
-static void gwas_free(jwas_hip_ctx* c)
-{
-    auto& g = c->gw;
-    for (void* q : {(void*)g.cs, (void*)g.ce, (void*)g.lo, (void*)g.hi, (void*)g.idx, g.val, (void*)g.part, (void*)g.out, (void*)g.acc}) (void)hipFree(q);
-    if (g.host_out) (void)hipHostFree(g.host_out);
-    g = jwas_hip_ctx::Gwas();
 }
 
 static void free_storage(jwas_hip_ctx* c)
@@ -135,16 +117,15 @@ static void free_storage(jwas_hip_ctx* c)
     gwas_free(c);                       // (a session is bound to the matrix it was begun on)
     liab_free(c);                       // (the liabilities belong to the residual of this matrix)
     locpar_free(c);                     // (... and so do the location parameters' term layouts)
-    (void)hipFree(c->X); (void)hipFree(c->r); (void)hipFree(c->Q); (void)hipFree(c->qmean); (void)hipFree(c->w);
-    c->X = c->r = nullptr; c->Q = nullptr; c->qmean = nullptr; c->packed = false; c->w = nullptr; c->weighted = false;
+    c->drop();                          // (genotypes, residual, weights, output rows, the chain's state)
+    (void)hipFree(c->Q); (void)hipFree(c->qmean);
+    c->Q = nullptr; c->qmean = nullptr; c->packed = false;
     (void)hipFree(c->ev); (void)hipFree(c->dparams); (void)hipFree(c->counters); (void)hipFree(c->fin_out); (void)hipFree(c->stat_out); (void)hipFree(c->sync_cnt);
     c->sync_cnt = nullptr; c->ev = nullptr; c->dparams = nullptr; c->counters = nullptr; c->fin_out = c->stat_out = nullptr;
     if (c->host_buf) (void)hipHostFree(c->host_buf);
     c->host_buf = nullptr;
-    (void)hipFree(c->var_vec); (void)hipFree(c->pi_vec); (void)hipFree(c->pi_mat); (void)hipFree(c->lpr_mat);
-    (void)hipFree(c->var_mat); (void)hipFree(c->ginv_mat); c->var_mat = c->ginv_mat = nullptr;
-    c->var_vec = nullptr; c->pi_vec = c->pi_mat = c->lpr_mat = nullptr;
-    (void)hipFree(c->Xout); c->Xout = nullptr; c->n_out = c->ld_out = 0;
+    (void)hipFree(c->pi_vec); (void)hipFree(c->pi_mat); (void)hipFree(c->lpr_mat);
+    c->pi_vec = c->pi_mat = c->lpr_mat = nullptr;
 }
 
 void jwas_hip_destroy(jwas_hip_ctx* c)
@@ -157,9 +138,8 @@ void jwas_hip_destroy(jwas_hip_ctx* c)
     ss_free(c);                         // (the single-step imputation session is bound to no matrix: it goes with the context)
     if (c->f64) {
         auto* F = c->f64;
-        for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->alpha, (void*)F->beta, F->delta, (void*)F->mean_a,
-                        (void*)F->mean_a2, (void*)F->mean_d, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->var_vec, (void*)F->w, (void*)F->ev_all,
-                        (void*)F->var_mat, (void*)F->ginv_mat, (void*)F->Xout, (void*)F->cmp_idx, (void*)F->cmp_val}) (void)hipFree(q);
+        F->drop();
+        for (void* q : {(void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->ev_all}) (void)hipFree(q);
         delete F;
         c->f64 = nullptr;
     }
@@ -275,15 +255,15 @@ static int alloc_storage(jwas_hip_ctx* c, int64_t n, int64_t p, bool packed = fa
     if (packed) {
         HIPCHK(c, hipMalloc(&c->Q, need));
         HIPCHK(c, hipMalloc(&c->qmean, sizeof(float) * p));
-    } else HIPCHK(c, hipMalloc(&c->X, need));
+    } else HIPCHK(c, c->load_mem.alloc(&c->X, need));
     {   // unit residual weights by default
         std::vector<float> ones((size_t)c->ld, 0.f);
         std::fill(ones.begin(), ones.begin() + n, 1.f);
-        HIPCHK(c, hipMalloc(&c->w, sizeof(float) * c->ld));
+        HIPCHK(c, c->load_mem.alloc(&c->w, sizeof(float) * c->ld));
         HIPCHK(c, hipMemcpy(c->w, ones.data(), sizeof(float) * c->ld, hipMemcpyHostToDevice));
         c->weighted = false;
     }
-    HIPCHK(c, hipMalloc(&c->r, sizeof(float) * 2 * kMaxT * c->ld));
+    HIPCHK(c, c->load_mem.alloc(&c->r, sizeof(float) * 2 * kMaxT * c->ld));
     HIPCHK(c, hipMemsetAsync(c->r, 0, sizeof(float) * 2 * kMaxT * c->ld, c->stream));
     HIPCHK(c, hipMalloc(&c->ev, sizeof(Events) * 2));
     HIPCHK(c, hipMemsetAsync(c->ev, 0, sizeof(Events) * 2, c->stream));
@@ -643,7 +623,7 @@ int jwas_hip_setup_blocks(jwas_hip_ctx* c, int32_t bs, int32_t gram_mode)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_blocks(c);
-    HIPCHK(c, hipMalloc(&c->xpx, sizeof(float) * c->p));
+    HIPCHK(c, c->load_mem.alloc(&c->xpx, sizeof(float) * c->p));
     with_cols(c, 0, [&](auto cx) {
         hipLaunchKernelGGL((k_xpx<decltype(cx)>), dim3((unsigned)c->p), dim3(256), 0, c->stream, cx, c->xpx);
         return 0;
@@ -680,7 +660,7 @@ int jwas_hip_setup_blocks_explicit(jwas_hip_ctx* c, const int64_t* starts, int64
     c->starts.push_back(c->p);
     HIPCHK(c, hipMalloc(&c->d_starts, sizeof(int64_t) * c->starts.size()));
     HIPCHK(c, hipMemcpy(c->d_starts, c->starts.data(), sizeof(int64_t) * c->starts.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&c->xpx, sizeof(float) * c->p));
+    HIPCHK(c, c->load_mem.alloc(&c->xpx, sizeof(float) * c->p));
     with_cols(c, 0, [&](auto cx) {
         hipLaunchKernelGGL((k_xpx<decltype(cx)>), dim3((unsigned)c->p), dim3(256), 0, c->stream, cx, c->xpx);
         return 0;
@@ -790,17 +770,6 @@ int jwas_hip_num_blocks(jwas_hip_ctx* c, int64_t* nb, int32_t* bs)
     return JWAS_HIP_OK;
 }
 
-int jwas_hip_get_xpx(jwas_hip_ctx* c, float* out)
-{
-    if (c) NOT_F64(c, "jwas_hip_get_xpx (use jwas_hip_get_xpx_f64)");
-    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, c->xpx, JWAS_HIP_ESTATE, "jwas_hip_setup_blocks has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->xpx, sizeof(float) * c->p, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
 int jwas_hip_set_xpx(jwas_hip_ctx* c, const float* in)
 {
     NEED(c, c && in, JWAS_HIP_EINVAL, "NULL argument");
@@ -885,12 +854,12 @@ int jwas_hip_init_state(jwas_hip_ctx* c, int32_t method, int32_t nt)
     c->last_events = -1.0; c->last_schedule = 0;   // a new chain: its first sweep has no previous one to take a schedule from
     c->lb.inited = false;                          // (the residual is zeroed below: the liabilities no longer belong to it)
     const size_t fb = sizeof(float) * (size_t)nt * c->p;
-    HIPCHK(c, hipMalloc(&c->alpha, fb));
-    HIPCHK(c, hipMalloc(&c->beta, fb));
-    HIPCHK(c, hipMalloc(&c->delta, fb));          // int32 and float are both 4 bytes
-    HIPCHK(c, hipMalloc(&c->mean_a, fb));
-    HIPCHK(c, hipMalloc(&c->mean_a2, fb));
-    HIPCHK(c, hipMalloc(&c->mean_d, fb));
+    HIPCHK(c, c->chain_mem.alloc(&c->alpha, fb));
+    HIPCHK(c, c->chain_mem.alloc(&c->beta, fb));
+    HIPCHK(c, c->chain_mem.alloc(&c->delta, fb));          // int32 and float are both 4 bytes
+    HIPCHK(c, c->chain_mem.alloc(&c->mean_a, fb));
+    HIPCHK(c, c->chain_mem.alloc(&c->mean_a2, fb));
+    HIPCHK(c, c->chain_mem.alloc(&c->mean_d, fb));
     HIPCHK(c, hipMalloc(&c->prep_d, sizeof(double) * kPrepD * (size_t)c->p));
     HIPCHK(c, hipMalloc(&c->prep_f, sizeof(float) * kPrepF * (size_t)c->p));
     if (method == JWAS_HIP_MTBAYESC2 && nt <= 3)
@@ -902,60 +871,6 @@ int jwas_hip_init_state(jwas_hip_ctx* c, int32_t method, int32_t nt)
     HIPCHK(c, hipMemsetAsync(c->mean_a2, 0, fb, c->stream));
     HIPCHK(c, hipMemsetAsync(c->mean_d, 0, fb, c->stream));
     HIPCHK(c, hipMemsetAsync(c->r, 0, sizeof(float) * 2 * kMaxT * c->ld, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-#define NEED_TRAIT(c, trait)                                                                       \
-    NEED(c, c->method >= 0, JWAS_HIP_ESTATE, "jwas_hip_init_state has not been called");           \
-    NEED(c, trait >= 0 && trait < c->ntraits, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->ntraits)
-
-int jwas_hip_set_state(jwas_hip_ctx* c, int32_t trait, const float* a, const float* b, const void* d)
-{
-    if (c) NOT_F64(c, "jwas_hip_set_state (use jwas_hip_set_state_f64)");
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = sizeof(float) * c->p, off = (size_t)trait * c->p;
-    if (a) HIPCHK(c, hipMemcpyAsync(c->alpha + off, a, nb, hipMemcpyHostToDevice, c->stream));
-    if (b) HIPCHK(c, hipMemcpyAsync(c->beta + off, b, nb, hipMemcpyHostToDevice, c->stream));
-    if (d) HIPCHK(c, hipMemcpyAsync((float*)c->delta + off, d, nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_get_state(jwas_hip_ctx* c, int32_t trait, float* a, float* b, void* d)
-{
-    if (c) NOT_F64(c, "jwas_hip_get_state (use jwas_hip_get_state_f64)");
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = sizeof(float) * c->p, off = (size_t)trait * c->p;
-    if (a) HIPCHK(c, hipMemcpyAsync(a, c->alpha + off, nb, hipMemcpyDeviceToHost, c->stream));
-    if (b) HIPCHK(c, hipMemcpyAsync(b, c->beta + off, nb, hipMemcpyDeviceToHost, c->stream));
-    if (d) HIPCHK(c, hipMemcpyAsync(d, (float*)c->delta + off, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_set_residual(jwas_hip_ctx* c, int32_t trait, const float* rh)
-{
-    if (c) NOT_F64(c, "jwas_hip_set_residual (use jwas_hip_set_residual_f64)");
-    NEED(c, c && rh, JWAS_HIP_EINVAL, "NULL argument");
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->r + (size_t)trait * c->ld, rh, sizeof(float) * c->n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_get_residual(jwas_hip_ctx* c, int32_t trait, float* rh)
-{
-    if (c) NOT_F64(c, "jwas_hip_get_residual (use jwas_hip_get_residual_f64)");
-    NEED(c, c && rh, JWAS_HIP_EINVAL, "NULL argument");
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(rh, c->r + (size_t)trait * c->ld, sizeof(float) * c->n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return JWAS_HIP_OK;
 }
@@ -1034,425 +949,6 @@ int jwas_hip_residual_add_scalar(jwas_hip_ctx* c, int32_t trait, double shift)
     return JWAS_HIP_OK;
 }
 
-int jwas_hip_residual_sub_xalpha(jwas_hip_ctx* c, int32_t trait)
-{
-    if (c && IS_F64(c)) {
-        NEED_TRAIT(c, trait);
-        HIPCHK(c, hipSetDevice(c->device));
-        double* rk = c->f64->r + (size_t)trait * c->ld;
-        hipLaunchKernelGGL(jw64::k64_mul_alpha, dim3((unsigned)c->nslices), dim3(256), 0, c->stream, c->f64->X, c->ld, c->p,
-                           c->f64->alpha + (size_t)trait * c->p, rk, -1.0, (const double*)rk);
-        HIPCHK(c, hipGetLastError());
-        return JWAS_HIP_OK;
-    }
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    with_cols(c, 0, [&](auto cx) {
-        hipLaunchKernelGGL((k_sub_xalpha<decltype(cx)>), dim3(c->nslices), dim3(256), 0, c->stream, cx, c->p,
-                           c->alpha + (size_t)trait * c->p, c->r + (size_t)trait * c->ld);
-        return 0;
-    });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-// The nonzero effects of trait `trait` as device lists (marker order), compacted on the device; *nnz = -1: dense enough
-// that the plain loop over all markers is the better kernel.  The lists live in the context (not to be freed).
-static hipError_t compact_alpha(jwas_hip_ctx* c, int32_t trait, int* nnz)
-{
-    hipError_t e = hipSuccess;
-    if (!c->cmp_idx) {
-        e = hipMalloc(&c->cmp_idx, sizeof(int32_t) * ((size_t)c->p + 1));
-        if (e == hipSuccess) e = hipMalloc(&c->cmp_val, sizeof(float) * (size_t)c->p);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_compact_alpha, dim3(1), dim3(1024), 0, c->stream, c->p, c->alpha + (size_t)trait * c->p,
-                       c->cmp_idx, c->cmp_val, c->cmp_idx + c->p);
-    e = hipGetLastError();
-    int32_t cnt = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&cnt, c->cmp_idx + c->p, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    *nnz = (int)cnt;
-    return e;
-}
-static hipError_t sparse_alpha(jwas_hip_ctx* c, int32_t trait, int32_t** d_idx, float** d_val, int* nnz)
-{
-    hipError_t e = compact_alpha(c, trait, nnz);
-    *d_idx = c->cmp_idx; *d_val = c->cmp_val;
-    if (e == hipSuccess && (int64_t)*nnz * 4 > c->p) *nnz = -1;          // dense
-    return e;
-}
-
-int jwas_hip_mul_alpha(jwas_hip_ctx* c, int32_t trait, float* out)
-{
-    if (c) NOT_F64(c, "jwas_hip_mul_alpha (use jwas_hip_mul_alpha_f64)");
-    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    float* tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, sizeof(float) * c->ld));
-    int32_t* d_idx = nullptr; float* d_val = nullptr; int nnz = -1;
-    hipError_t e0 = sparse_alpha(c, trait, &d_idx, &d_val, &nnz);
-    if (e0 != hipSuccess) { (void)hipFree(tmp); return fail(c, JWAS_HIP_EHIP, "jwas_hip_mul_alpha: %s", hipGetErrorString(e0)); }
-    with_cols(c, 0, [&](auto cx) {
-        if (nnz >= 0)
-            hipLaunchKernelGGL((k_mul_alpha_list<decltype(cx)>), dim3(c->nslices), dim3(256), 0, c->stream, cx, nnz, d_idx, d_val, tmp);
-        else
-            hipLaunchKernelGGL((k_mul_alpha<decltype(cx)>), dim3(c->nslices), dim3(256), 0, c->stream, cx, c->p,
-                               c->alpha + (size_t)trait * c->p, tmp);
-        return 0;
-    });
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, sizeof(float) * c->n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_mul_alpha: %s", hipGetErrorString(e));
-    return JWAS_HIP_OK;
-}
-
-// Output rows: the reference keeps Mi.output_genotypes = Z_out * genotypes for mme.output_ID (all genotyped individuals by
-// default, input_data_validation.jl:150-154; tools4genotypes.jl:290-296) next to the training rows and forms
-// EBV = output_genotypes * alpha for every saved sample (output.jl:281-306).
-// One saved marker-effect sample as a sparse record (output.jl:443-526 writes the dense text row; with a sparse prior a
-// sample has a few hundred nonzero effects among 600 000).  idx / val: caller arrays of `capacity` entries, marker order.
-int jwas_hip_get_alpha_sparse(jwas_hip_ctx* c, int32_t trait, int64_t capacity, int32_t* idx, float* val, int64_t* nnz_out)
-{
-    if (c) NOT_F64(c, "jwas_hip_get_alpha_sparse (use jwas_hip_get_alpha_sparse_f64)");
-    NEED(c, c && nnz_out, JWAS_HIP_EINVAL, "NULL argument");
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    int nnz = 0;
-    HIPCHK(c, compact_alpha(c, trait, &nnz));
-    *nnz_out = nnz;
-    NEED(c, nnz <= capacity, JWAS_HIP_EINVAL, "%d nonzero effects do not fit the caller's %lld entries", nnz, (long long)capacity);
-    if (nnz > 0) {
-        NEED(c, idx && val, JWAS_HIP_EINVAL, "idx / val is NULL");
-        HIPCHK(c, hipMemcpyAsync(idx, c->cmp_idx, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(val, c->cmp_val, sizeof(float) * nnz, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_load_output_dense_f32(jwas_hip_ctx* c, const float* Xh, int64_t n_out, int64_t p, int64_t ld_host)
-{
-    if (c) NOT_F64(c, "jwas_hip_load_output_dense_f32 (use jwas_hip_load_output_dense_f64)");
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, Xh, JWAS_HIP_EINVAL, "X_out is NULL");
-    NEED(c, HAVE_STORAGE(c), JWAS_HIP_ESTATE, "no genotype matrix loaded");
-    NEED(c, n_out >= 1, JWAS_HIP_EINVAL, "n_out must be >= 1 (got %lld)", (long long)n_out);
-    NEED(c, p == c->p, JWAS_HIP_EINVAL, "output genotypes have %lld markers, the training matrix %lld", (long long)p, (long long)c->p);
-    NEED(c, ld_host >= n_out, JWAS_HIP_EINVAL, "ld_host (%lld) must be >= n_out (%lld)", (long long)ld_host, (long long)n_out);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->gw.out_rows) gwas_free(c);
-    (void)hipFree(c->Xout); c->Xout = nullptr; c->n_out = c->ld_out = 0;
-    const int64_t ld = (n_out + kSliceRows - 1) / kSliceRows * kSliceRows;
-    HIPCHK(c, hipMalloc(&c->Xout, (size_t)4 * ld * p));
-    c->n_out = n_out; c->ld_out = ld;
-    if (ld != n_out) HIPCHK(c, hipMemsetAsync(c->Xout, 0, (size_t)4 * ld * p, c->stream));
-    HIPCHK(c, hipMemcpy2DAsync(c->Xout, (size_t)4 * ld, Xh, (size_t)4 * ld_host, (size_t)4 * n_out, (size_t)p,
-                               hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_mul_alpha_output(jwas_hip_ctx* c, int32_t trait, float* out)
-{
-    if (c) NOT_F64(c, "jwas_hip_mul_alpha_output (use jwas_hip_mul_alpha_output_f64)");
-    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
-    NEED_TRAIT(c, trait);
-    NEED(c, c->Xout, JWAS_HIP_ESTATE, "jwas_hip_load_output_dense_f32 has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    float* tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, sizeof(float) * c->ld_out));
-    DenseCols cx{c->Xout, c->ld_out, nullptr, 0};
-    int32_t* d_idx = nullptr; float* d_val = nullptr; int nnz = -1;
-    hipError_t e0 = sparse_alpha(c, trait, &d_idx, &d_val, &nnz);
-    if (e0 != hipSuccess) { (void)hipFree(tmp); return fail(c, JWAS_HIP_EHIP, "jwas_hip_mul_alpha_output: %s", hipGetErrorString(e0)); }
-    if (nnz >= 0)
-        hipLaunchKernelGGL((k_mul_alpha_list<DenseCols>), dim3((unsigned)(c->ld_out / kSliceRows)), dim3(256), 0, c->stream, cx, nnz, d_idx, d_val, tmp);
-    else
-        hipLaunchKernelGGL((k_mul_alpha<DenseCols>), dim3((unsigned)(c->ld_out / kSliceRows)), dim3(256), 0, c->stream, cx, c->p,
-                           c->alpha + (size_t)trait * c->p, tmp);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, sizeof(float) * c->n_out, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_mul_alpha_output: %s", hipGetErrorString(e));
-    return JWAS_HIP_OK;
-}
-
-// Window genomic variances of one saved marker-effect sample: the O(samples x n x p) inner loop of the reference's
-// window-based GWAS (src/3.GWAS/src/GWAS.jl:152-165: genVar = var(X*alpha), var_w = var(X[:, w] * alpha[w])) as one
-// launch over the nonzero effects only.  The caller derives var = (ss - sum^2/n) / (n - 1).
-static int window_sums_impl(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
-                            const float* val, const float* val2, double* const* outs /* 2 or 5 arrays of nwin */)
-{
-    const int nv = val2 ? 5 : 2;
-    if (c) NOT_F64(c, val2 ? "jwas_hip_window_sums2 (use jwas_hip_window_sums2_f64)" : "jwas_hip_window_sums (use jwas_hip_window_sums_f64)");
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, wptr, JWAS_HIP_EINVAL, "NULL argument");
-    for (int v = 0; v < nv; ++v) NEED(c, outs[v], JWAS_HIP_EINVAL, "NULL output array");
-    NEED(c, nwin >= 1, JWAS_HIP_EINVAL, "nwin must be >= 1 (got %d)", nwin);
-    NEED(c, HAVE_STORAGE(c), JWAS_HIP_ESTATE, "no genotype matrix loaded");
-    NEED(c, !use_output_rows || c->Xout, JWAS_HIP_ESTATE, "jwas_hip_load_output_dense_f32 has not been called");
-    NEED(c, wptr[0] == 0, JWAS_HIP_EINVAL, "wptr[0] must be 0");
-    for (int w = 0; w < nwin; ++w) NEED(c, wptr[w + 1] >= wptr[w], JWAS_HIP_EINVAL, "wptr must be non-decreasing");
-    const int64_t nnz = wptr[nwin];
-    NEED(c, nnz == 0 || (idx && val), JWAS_HIP_EINVAL, "idx / val is NULL");
-    for (int64_t e = 0; e < nnz; ++e) NEED(c, idx[e] >= 0 && idx[e] < c->p, JWAS_HIP_EINVAL, "marker index %d out of range", idx[e]);
-    HIPCHK(c, hipSetDevice(c->device));
-    const int nsl = (int)(use_output_rows ? c->ld_out / kSliceRows : c->nslices);
-    const size_t ne = (size_t)(nnz > 0 ? nnz : 1);
-    int32_t *d_wptr = nullptr, *d_idx = nullptr; float *d_val = nullptr, *d_val2 = nullptr; double *d_part = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc(&d_wptr, sizeof(int32_t) * (nwin + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_idx, sizeof(int32_t) * ne);
-    if (e == hipSuccess) e = hipMalloc(&d_val, sizeof(float) * ne);
-    if (e == hipSuccess && val2) e = hipMalloc(&d_val2, sizeof(float) * ne);
-    if (e == hipSuccess) e = hipMalloc(&d_part, sizeof(double) * nv * (size_t)nwin * nsl);
-    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * nv * (size_t)nwin);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_wptr, wptr, sizeof(int32_t) * (nwin + 1), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_idx, idx, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_val, val, sizeof(float) * nnz, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz && val2) e = hipMemcpyAsync(d_val2, val2, sizeof(float) * nnz, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        auto launch = [&](auto cx) {
-            if (val2) hipLaunchKernelGGL((k_window_partial<decltype(cx), 5>), dim3((unsigned)nsl), dim3(256), 0, c->stream, cx, nwin, d_wptr, d_idx, d_val, d_val2, d_part);
-            else      hipLaunchKernelGGL((k_window_partial<decltype(cx), 2>), dim3((unsigned)nsl), dim3(256), 0, c->stream, cx, nwin, d_wptr, d_idx, d_val, d_val2, d_part);
-            return 0;
-        };
-        if (use_output_rows) launch(DenseCols{c->Xout, c->ld_out, nullptr, 0});
-        else with_cols(c, 0, launch);
-        hipLaunchKernelGGL(k_window_reduce, dim3((unsigned)((nwin + 255) / 256)), dim3(256), 0, c->stream, nwin, nsl, nv, d_part, d_out);
-        e = hipGetLastError();
-    }
-    for (int v = 0; v < nv && e == hipSuccess; ++v)
-        e = hipMemcpyAsync(outs[v], d_out + (size_t)v * nwin, sizeof(double) * nwin, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_wptr); (void)hipFree(d_idx); (void)hipFree(d_val); (void)hipFree(d_val2); (void)hipFree(d_part); (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_window_sums: %s", hipGetErrorString(e));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_window_sums(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
-                         const float* val, double* out_sum, double* out_ss)
-{
-    double* outs[2] = {out_sum, out_ss};
-    return window_sums_impl(c, use_output_rows, nwin, wptr, idx, val, nullptr, outs);
-}
-
-int jwas_hip_window_sums2(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
-                          const float* val1, const float* val2, double* out_sum1, double* out_ss1, double* out_sum2,
-                          double* out_ss2, double* out_cross)
-{
-    if (c) NOT_F64(c, "jwas_hip_window_sums2 (use jwas_hip_window_sums2_f64)");
-    NEED(c, c && val2, JWAS_HIP_EINVAL, "NULL argument");
-    double* outs[5] = {out_sum1, out_ss1, out_sum2, out_ss2, out_cross};
-    return window_sums_impl(c, use_output_rows, nwin, wptr, idx, val1, val2, outs);
-}
-
-// ---- the GWAS session (src/3.GWAS/src/GWAS.jl:149-173) ---------------------------------------------------------------
-// Window variances AND local EBVs of the saved samples with everything resident: the window ranges are uploaded once, a
-// sample arrives as its (idx, val) list (no per-window duplicates), no allocation per sample.
-static constexpr int kGwasTargetWG = 2048;      // 256 CUs x 8 workgroups of 4 waves: every SIMD's 8 wave slots
-
-static int64_t gwas_windows_per_chunk(int64_t nwin, int64_t nsl)
-{
-    const int64_t wpc = (nwin * nsl + kGwasTargetWG - 1) / kGwasTargetWG;
-    return wpc < 1 ? 1 : wpc;
-}
-
-int64_t jwas_hip_gwas_estimate_bytes(int64_t n_rows, int64_t nwin, int64_t max_nnz, int32_t local_ebv)
-{
-    if (n_rows < 1 || nwin < 1 || max_nnz < 0) return 0;
-    const int64_t ld = round_up(n_rows, kSliceRows), nsl = ld / kSliceRows, nent = nwin + 1;
-    int64_t bytes = 2 * 4 * nwin + 2 * 4 * nent;                 // column ranges + list slices
-    bytes += (max_nnz > 0 ? max_nnz : 1) * (4 + 8);              // idx + val (double at most)
-    bytes += 2 * 8 * nent * nsl + 2 * 8 * nent;                  // slice partials + sums
-    if (local_ebv) bytes += 8 * ld * nwin;                       // the local-EBV accumulator
-    return bytes;
-}
-
-static const void* gwas_matrix(jwas_hip_ctx* c, bool out_rows, int64_t* n_rows, int64_t* ld)
-{
-    if (IS_F64(c)) {
-        auto* F = c->f64;
-        *n_rows = out_rows ? F->n_out : c->n; *ld = out_rows ? F->ld_out : c->ld;
-        return out_rows ? (const void*)F->Xout : (const void*)F->X;
-    }
-    *n_rows = out_rows ? c->n_out : c->n; *ld = out_rows ? c->ld_out : c->ld;
-    if (out_rows) return c->Xout;
-    return c->packed ? (const void*)c->Q : (const void*)c->X;
-}
-
-int jwas_hip_gwas_begin(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* col_start, const int32_t* col_end, int32_t local_ebv)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, col_start && col_end, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, nwin >= 1, JWAS_HIP_EINVAL, "nwin must be >= 1 (got %d)", nwin);
-    NEED(c, IS_F64(c) ? c->f64->X != nullptr : HAVE_STORAGE(c), JWAS_HIP_ESTATE, "no genotype matrix loaded");
-    NEED(c, !use_output_rows || (IS_F64(c) ? c->f64->Xout != nullptr : c->Xout != nullptr), JWAS_HIP_ESTATE,
-         "%s has not been called", IS_F64(c) ? "jwas_hip_load_output_dense_f64" : "jwas_hip_load_output_dense_f32");
-    for (int w = 0; w < nwin; ++w) {
-        NEED(c, col_start[w] <= col_end[w], JWAS_HIP_EINVAL, "window %d: col_start %d > col_end %d", w, col_start[w], col_end[w]);
-        NEED(c, col_start[w] >= 0 && col_end[w] <= c->p, JWAS_HIP_EINVAL, "window %d: columns [%d, %d) outside [0, %lld]", w, col_start[w], col_end[w], (long long)c->p);
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    gwas_free(c);
-    auto& g = c->gw;
-    g.mat = gwas_matrix(c, use_output_rows != 0, &g.n_rows, &g.ld);
-    g.out_rows = use_output_rows != 0; g.local_ebv = local_ebv != 0; g.nwin = nwin;
-    g.nsl = (int)(g.ld / kSliceRows);
-    g.wpc = (int)gwas_windows_per_chunk(nwin, g.nsl);
-    g.nchunks = 1 + (nwin + g.wpc - 1) / g.wpc;
-    const size_t nent = (size_t)nwin + 1;
-    g.cap = 4096;
-    hipError_t e = g.local_ebv ? hipMalloc(&g.acc, 8 * (size_t)g.ld * nwin) : hipSuccess;      // the largest first: refuse early
-    if (e == hipSuccess) e = hipMalloc(&g.cs, 4 * (size_t)nwin);
-    if (e == hipSuccess) e = hipMalloc(&g.ce, 4 * (size_t)nwin);
-    if (e == hipSuccess) e = hipMalloc(&g.lo, 4 * nent);
-    if (e == hipSuccess) e = hipMalloc(&g.hi, 4 * nent);
-    if (e == hipSuccess) e = hipMalloc(&g.idx, 4 * (size_t)g.cap);
-    if (e == hipSuccess) e = hipMalloc(&g.val, 8 * (size_t)g.cap);
-    if (e == hipSuccess) e = hipMalloc(&g.part, 16 * nent * (size_t)g.nsl);
-    if (e == hipSuccess) e = hipMalloc(&g.out, 16 * nent);
-    if (e == hipSuccess) e = hipHostMalloc(&g.host_out, 16 * nent);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        const int64_t rows = g.n_rows, ldr = g.ld;
-        gwas_free(c);
-        return fail(c, JWAS_HIP_ENOMEM, "jwas_hip_gwas_begin: %s (the session needs %.3f GB, %lld rows x %d windows x 8 bytes of it for the local EBVs)",
-                    hipGetErrorString(e), jwas_hip_gwas_estimate_bytes(rows, nwin, 4096, local_ebv) / 1e9, (long long)(local_ebv ? ldr : 0), nwin);
-    }
-    e = hipMemcpyAsync(g.cs, col_start, 4 * (size_t)nwin, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(g.ce, col_end, 4 * (size_t)nwin, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && g.local_ebv) e = hipMemsetAsync(g.acc, 0, 8 * (size_t)g.ld * nwin, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { gwas_free(c); return fail(c, JWAS_HIP_EHIP, "jwas_hip_gwas_begin: %s", hipGetErrorString(e)); }
-    g.active = true;
-    return JWAS_HIP_OK;
-}
-
-static int gwas_sample_impl(jwas_hip_ctx* c, int32_t nnz, const int32_t* idx, const void* val, bool is64, double* out_sum, double* out_ss)
-{
-    auto& g = c->gw;
-    NEED(c, out_sum && out_ss, JWAS_HIP_EINVAL, "NULL output array");
-    NEED(c, nnz >= 0, JWAS_HIP_EINVAL, "nnz must be >= 0 (got %d)", nnz);
-    NEED(c, nnz == 0 || (idx && val), JWAS_HIP_EINVAL, "idx / val is NULL");
-    NEED(c, g.active, JWAS_HIP_ESTATE, "jwas_hip_gwas_begin has not been called");
-    int64_t n_rows = 0, ld = 0;
-    NEED(c, gwas_matrix(c, g.out_rows, &n_rows, &ld) == g.mat && ld == g.ld && n_rows == g.n_rows, JWAS_HIP_ESTATE,
-         "the genotypes were reloaded after jwas_hip_gwas_begin");
-    for (int32_t e = 0; e < nnz; ++e) {
-        NEED(c, idx[e] >= 0 && idx[e] < c->p, JWAS_HIP_EINVAL, "marker index %d out of range", idx[e]);
-        NEED(c, e == 0 || idx[e] > idx[e - 1], JWAS_HIP_EINVAL, "idx must be strictly ascending (entry %d: %d after %d)", e, idx[e], idx[e - 1]);
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    if (nnz > g.cap) {                                          // grow on demand (rare: a denser sample than any before)
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        int64_t cap = g.cap;
-        while (cap < nnz) cap *= 2;
-        if (cap > c->p) cap = c->p;
-        int32_t* ni = nullptr; void* nv = nullptr;
-        hipError_t ea = hipMalloc(&ni, 4 * (size_t)cap);
-        if (ea == hipSuccess) ea = hipMalloc(&nv, 8 * (size_t)cap);
-        if (ea != hipSuccess) {
-            (void)hipGetLastError(); (void)hipFree(ni); (void)hipFree(nv);
-            return fail(c, JWAS_HIP_ENOMEM, "jwas_hip_gwas_sample: %s (a list of %lld effects)", hipGetErrorString(ea), (long long)cap);
-        }
-        (void)hipFree(g.idx); (void)hipFree(g.val);
-        g.idx = ni; g.val = nv; g.cap = cap;
-    }
-    const int nent = g.nwin + 1;
-    const size_t vsz = is64 ? 8 : 4;
-    hipError_t e = hipSuccess;
-    if (nnz) e = hipMemcpyAsync(g.idx, idx, 4 * (size_t)nnz, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(g.val, val, vsz * (size_t)nnz, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_gwas_slices, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, c->stream, nent, (int)nnz, g.cs, g.ce, g.idx, g.lo, g.hi);
-        const dim3 grid((unsigned)g.nsl, (unsigned)g.nchunks);
-        if (is64) {
-            const double* M = (const double*)g.mat;
-            if (g.local_ebv) hipLaunchKernelGGL((jw64::k64_gwas_partial<true>), grid, dim3(256), 0, c->stream, M, g.ld, nent, g.wpc, g.lo, g.hi, g.idx, (const double*)g.val, g.part, g.acc);
-            else             hipLaunchKernelGGL((jw64::k64_gwas_partial<false>), grid, dim3(256), 0, c->stream, M, g.ld, nent, g.wpc, g.lo, g.hi, g.idx, (const double*)g.val, g.part, g.acc);
-        } else {
-            auto launch = [&](auto cx) {
-                if (g.local_ebv) hipLaunchKernelGGL((k_gwas_partial<decltype(cx), true>), grid, dim3(256), 0, c->stream, cx, nent, g.wpc, g.lo, g.hi, g.idx, (const float*)g.val, g.part, g.acc, g.ld);
-                else             hipLaunchKernelGGL((k_gwas_partial<decltype(cx), false>), grid, dim3(256), 0, c->stream, cx, nent, g.wpc, g.lo, g.hi, g.idx, (const float*)g.val, g.part, g.acc, g.ld);
-                return 0;
-            };
-            if (g.out_rows) launch(DenseCols{c->Xout, c->ld_out, nullptr, 0});
-            else with_cols(c, 0, launch);
-        }
-        hipLaunchKernelGGL(k_window_reduce, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, c->stream, nent, g.nsl, 2, g.part, g.out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(g.host_out, g.out, 16 * (size_t)nent, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_gwas_sample: %s", hipGetErrorString(e));
-    std::memcpy(out_sum, g.host_out, 8 * (size_t)nent);
-    std::memcpy(out_ss, g.host_out + nent, 8 * (size_t)nent);
-    g.nsamples += 1;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_gwas_sample(jwas_hip_ctx* c, int32_t nnz, const int32_t* idx, const float* val, double* out_sum, double* out_ss)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NOT_F64(c, "jwas_hip_gwas_sample (use jwas_hip_gwas_sample_f64)");
-    return gwas_sample_impl(c, nnz, idx, val, false, out_sum, out_ss);
-}
-
-int jwas_hip_gwas_sample_f64(jwas_hip_ctx* c, int32_t nnz, const int32_t* idx, const double* val, double* out_sum, double* out_ss)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    ONLY_F64(c);
-    return gwas_sample_impl(c, nnz, idx, val, true, out_sum, out_ss);
-}
-
-int jwas_hip_gwas_local_ebv(jwas_hip_ctx* c, double* out, int64_t* nsamples)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, out && nsamples, JWAS_HIP_EINVAL, "NULL argument");
-    auto& g = c->gw;
-    NEED(c, g.active, JWAS_HIP_ESTATE, "jwas_hip_gwas_begin has not been called");
-    NEED(c, g.local_ebv, JWAS_HIP_ESTATE, "the session was begun without local_ebv");
-    HIPCHK(c, hipSetDevice(c->device));
-    // window-major rows [0, n_rows) of every window's padded column; the padding rows stay on the device
-    HIPCHK(c, hipMemcpy2DAsync(out, 8 * (size_t)g.n_rows, g.acc, 8 * (size_t)g.ld, 8 * (size_t)g.n_rows, (size_t)g.nwin, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *nsamples = g.nsamples;
-    if (g.nsamples > 0) {
-        const double s = (double)g.nsamples;
-        const int64_t cnt = g.n_rows * g.nwin;
-        for (int64_t i = 0; i < cnt; ++i) out[i] /= s;
-    }
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_gwas_geometry(jwas_hip_ctx* c, int32_t* nslices, int32_t* windows_per_chunk, int32_t* nchunks)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, c->gw.active, JWAS_HIP_ESTATE, "jwas_hip_gwas_begin has not been called");
-    if (nslices) *nslices = c->gw.nsl;
-    if (windows_per_chunk) *windows_per_chunk = c->gw.wpc;
-    if (nchunks) *nchunks = c->gw.nchunks;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_gwas_end(jwas_hip_ctx* c)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    gwas_free(c);
-    return JWAS_HIP_OK;
-}
-
 }  // extern "C" (templates need C++ linkage)
 
 // ---- the sweep --------------------------------------------------------------------------------------
@@ -1483,9 +979,10 @@ static hipError_t launch_step_any(jwas_hip_ctx* c, const UpdateArgs& U, const Sa
     }
 }
 
-static int upload_vec(jwas_hip_ctx* c, void** dev, const void* host, size_t bytes)
+// *dev (allocated at its first use: by `owner`, or owner == NULL: by the context's own free list) := host
+static int upload_vec(jwas_hip_ctx* c, DevOwner* owner, void** dev, const void* host, size_t bytes)
 {
-    if (!*dev) HIPCHK(c, hipMalloc(dev, bytes));
+    if (!*dev) HIPCHK(c, owner ? owner->alloc(dev, bytes) : hipMalloc(dev, bytes));
     HIPCHK(c, hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, c->stream));
     return JWAS_HIP_OK;
 }
@@ -1767,8 +1264,8 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
         NEED(c, !use_lpr, JWAS_HIP_EUNSUP, "marker-specific joint priors are not available with per-marker effect covariances");
         NEED(c, c->block_size * t <= 2048, JWAS_HIP_EUNSUP, "per-marker effect covariances need block_size * ntraits <= 2048 (got %d x %d)", c->block_size, t);
         const size_t mb = sizeof(float) * (size_t)t * t * c->p;
-        if (P->var_effect_matrix) { int rc = upload_vec(c, (void**)&c->var_mat, P->var_effect_matrix, mb); if (rc) return rc; c->var_mat_resident = true; }
-        if (!c->ginv_mat) HIPCHK(c, hipMalloc(&c->ginv_mat, mb));
+        if (P->var_effect_matrix) { int rc = upload_vec(c, &c->chain_mem, (void**)&c->var_mat, P->var_effect_matrix, mb); if (rc) return rc; c->var_mat_resident = true; }
+        if (!c->ginv_mat) HIPCHK(c, c->chain_mem.alloc(&c->ginv_mat, mb));
         D.var_mat = c->var_mat; D.ginv_mat = c->ginv_mat;
         for (int i = 0; i < t * t; ++i) D.Ginv[i] = (i / t == i % t) ? 1.f : 0.f;       // (unused)
     }
@@ -1784,7 +1281,7 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
             NEED(c, t == 2, JWAS_HIP_EUNSUP, "marker-specific joint priors support 2 traits (got %d)", t);
             NEED(c, c->block_size <= 512, JWAS_HIP_EUNSUP, "marker-specific joint priors need a block size <= 512 (got %d)", c->block_size);
             if (P->log_prior_states_matrix) {
-                int rc = upload_vec(c, (void**)&c->lpr_mat, P->log_prior_states_matrix, sizeof(double) * (size_t)(1 << t) * c->p);
+                int rc = upload_vec(c, nullptr, (void**)&c->lpr_mat, P->log_prior_states_matrix, sizeof(double) * (size_t)(1 << t) * c->p);
                 if (rc) return rc;
             }
         }
@@ -1808,15 +1305,15 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
             NEED(c, std::fabs(s - 1.0) <= 1e-8, JWAS_HIP_EINVAL, "BayesR pi must sum to 1.");
         }
         for (int k = 0; k < 4; ++k) { D.pi4[k] = P->pi_classes[k]; D.gamma[k] = P->gamma[k]; }
-        if (P->pi_matrix) { int rc = upload_vec(c, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; }
+        if (P->pi_matrix) { int rc = upload_vec(c, nullptr, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; }
         if (use_pi_mat) D.pi_mat = c->pi_mat;
     } else if (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) {
         D.pi = P->pi;
-        if (P->pi_vec) { int rc = upload_vec(c, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; }
+        if (P->pi_vec) { int rc = upload_vec(c, nullptr, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; }
         if (use_pi_vec) D.pi_vec = c->pi_vec;
         if (c->method == JWAS_HIP_BAYESB) {
             NEED(c, P->var_effect_vec, JWAS_HIP_EINVAL, "BayesB needs per-marker effect variances (var_effect_vec)");
-            int rc = upload_vec(c, (void**)&c->var_vec, P->var_effect_vec, sizeof(float) * c->p); if (rc) return rc;
+            int rc = upload_vec(c, &c->chain_mem, (void**)&c->var_vec, P->var_effect_vec, sizeof(float) * c->p); if (rc) return rc;
             D.var_vec = c->var_vec;
         } else NEED(c, P->var_effect[0] > 0.f, JWAS_HIP_EINVAL, "marker effect variance must be positive");
     }
@@ -2247,19 +1744,11 @@ static int sweep_collect(jwas_hip_ctx* c, jwas_sweep_stats* S, size_t ntimed, do
 // A context becomes a Float64 context with jwas_hip_set_precision(ctx, 64) BEFORE genotypes are loaded; it then takes the
 // *_f64 data entry points (double host arrays) and the shared control entry points (setup_blocks, init_state, sweep,
 // accumulate, residual_sub_xalpha, num_blocks); everything else of the Float32 surface (packed storage, weights, explicit
-// partitions, shards) answers "not available in a Float64 context".  The output side has _f64 twins: output rows
-// (jwas_hip_load_output_dense_f64 / jwas_hip_mul_alpha_output_f64), sparse samples (jwas_hip_get_alpha_sparse_f64) and the
-// window sums of the GWAS (jwas_hip_window_sums_f64 / jwas_hip_window_sums2_f64); their Float32 namesakes name them.
+// partitions, shards) answers "not available in a Float64 context".  What both precisions hold under one name is the context's
+// Side<float> and this mode's Side<double> (ctx.hpp); below is what only this mode has: its blocks, its weights, its chain state's
+// layout and its sweep.  The output side (transfer, X alpha, output rows, sparse samples, window sums, the GWAS session) is
+// csrc/output.hip: one body per entry point, the *_f64 twin its second instantiation.
 // =====================================================================================================================
-
-static void f64_free_state(jwas_hip_ctx* c)
-{
-    auto* F = c->f64;
-    for (void* q : {(void*)F->alpha, (void*)F->beta, F->delta, (void*)F->mean_a, (void*)F->mean_a2, (void*)F->mean_d, (void*)F->var_vec,
-                    (void*)F->var_mat, (void*)F->ginv_mat}) (void)hipFree(q);
-    F->alpha = F->beta = F->mean_a = F->mean_a2 = F->mean_d = F->var_vec = F->var_mat = F->ginv_mat = nullptr; F->delta = nullptr;
-    F->var_mat_resident = false;
-}
 
 // x'R^-1 x, the Grams X_b'R^-1 X_b of the partition in F->starts (block k at k * bstride^2, row stride = the block's size) and
 // the partial-sum buffer.
@@ -2268,13 +1757,14 @@ static int f64_build_blocks(jwas_hip_ctx* c)
     auto* F = c->f64;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(F->xpx); (void)hipFree(F->gram); (void)hipFree(F->partials); F->xpx = F->gram = F->partials = nullptr; F->partials_cap = 0;
+    F->load_mem.free_one(F->xpx);
+    (void)hipFree(F->gram); (void)hipFree(F->partials); F->gram = F->partials = nullptr; F->partials_cap = 0;
     const int64_t nb = (int64_t)F->starts.size() - 1;
     int mx = 0;
     for (int64_t k = 0; k < nb; ++k) mx = std::max<int>(mx, (int)(F->starts[(size_t)k + 1] - F->starts[(size_t)k]));
     F->bstride = (mx + 7) / 8 * 8;
     c->nblocks = nb;
-    HIPCHK(c, hipMalloc(&F->xpx, sizeof(double) * c->p));
+    HIPCHK(c, F->load_mem.alloc(&F->xpx, sizeof(double) * c->p));
     HIPCHK(c, hipMalloc(&F->gram, sizeof(double) * (size_t)nb * F->bstride * F->bstride));
     F->partials_cap = (size_t)kMaxT * c->nslices * F->bstride;
     HIPCHK(c, hipMalloc(&F->partials, sizeof(double) * F->partials_cap));
@@ -2334,14 +1824,14 @@ static int f64_init_state(jwas_hip_ctx* c, int32_t method, int32_t nt)
     else NEED(c, nt == 1, JWAS_HIP_EINVAL, "single-trait method requires ntraits == 1 (got %d)", nt);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    f64_free_state(c);
+    F->drop_chain();
     c->method = method; c->ntraits = nt;
     c->last_events = -1.0; c->last_schedule = 0;   // a new chain: its first sweep has no previous one to take a schedule from
     c->lb.inited = false;                          // (the residual is zeroed below: the liabilities no longer belong to it)
     const size_t db = sizeof(double) * (size_t)nt * c->p;
     const size_t delb = method == JWAS_HIP_BAYESR ? sizeof(int32_t) * (size_t)c->p : db;
-    HIPCHK(c, hipMalloc(&F->alpha, db)); HIPCHK(c, hipMalloc(&F->beta, db)); HIPCHK(c, hipMalloc(&F->delta, delb));
-    HIPCHK(c, hipMalloc(&F->mean_a, db)); HIPCHK(c, hipMalloc(&F->mean_a2, db)); HIPCHK(c, hipMalloc(&F->mean_d, db));
+    HIPCHK(c, F->chain_mem.alloc(&F->alpha, db)); HIPCHK(c, F->chain_mem.alloc(&F->beta, db)); HIPCHK(c, F->chain_mem.alloc(&F->delta, delb));
+    HIPCHK(c, F->chain_mem.alloc(&F->mean_a, db)); HIPCHK(c, F->chain_mem.alloc(&F->mean_a2, db)); HIPCHK(c, F->chain_mem.alloc(&F->mean_d, db));
     for (void* q : {(void*)F->alpha, (void*)F->beta, (void*)F->mean_a, (void*)F->mean_a2, (void*)F->mean_d}) HIPCHK(c, hipMemsetAsync(q, 0, db, c->stream));
     HIPCHK(c, hipMemsetAsync(F->delta, 0, delb, c->stream));
     HIPCHK(c, hipMemsetAsync(F->r, 0, sizeof(double) * 2 * kMaxT * c->ld, c->stream));
@@ -2490,12 +1980,12 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
         if (is_sampler2(c->method) && !use_lpr)      // MTBayesABC.jl:190
             NEED(c, any_finite, JWAS_HIP_EINVAL, "All MTBayesABC sampler II state probabilities are zero or invalid.");
         if (P->log_prior_states_matrix) {
-            int rc = upload_vec(c, (void**)&c->lpr_mat, P->log_prior_states_matrix, sizeof(double) * (size_t)(1 << t) * c->p);
+            int rc = upload_vec(c, nullptr, (void**)&c->lpr_mat, P->log_prior_states_matrix, sizeof(double) * (size_t)(1 << t) * c->p);
             if (rc) return rc;
         }
         if (use_lpr) D.lpr_mat = c->lpr_mat;
         if (marker_cov) {
-            if (!F->ginv_mat) HIPCHK(c, hipMalloc(&F->ginv_mat, sizeof(double) * (size_t)t * t * c->p));
+            if (!F->ginv_mat) HIPCHK(c, F->chain_mem.alloc(&F->ginv_mat, sizeof(double) * (size_t)t * t * c->p));
             D.ginv_mat = F->ginv_mat;
         }
     } else NEED(c, D.vare[0] > 0.0, JWAS_HIP_EINVAL, "residual variance must be positive");
@@ -2507,15 +1997,15 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
             NEED(c, std::fabs(sum - 1.0) <= 1e-8, JWAS_HIP_EINVAL, "BayesR pi must sum to 1.");
         }
         for (int k = 0; k < 4; ++k) { D.pi4[k] = P->pi_classes[k]; D.gamma[k] = P->gamma[k]; }
-        if (P->pi_matrix) { int rc = upload_vec(c, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; }
+        if (P->pi_matrix) { int rc = upload_vec(c, nullptr, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; }
         if (use_pi_mat) D.pi_mat = c->pi_mat;
     } else if (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) {
         D.pi = P->pi;
-        if (P->pi_vec) { int rc = upload_vec(c, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; }
+        if (P->pi_vec) { int rc = upload_vec(c, nullptr, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; }
         if (use_pi_vec) D.pi_vec = c->pi_vec;
         if (c->method == JWAS_HIP_BAYESB) {
             NEED(c, P->var_effect_vec_f64, JWAS_HIP_EINVAL, "BayesB needs per-marker effect variances (var_effect_vec_f64)");
-            int rc = upload_vec(c, (void**)&F->var_vec, P->var_effect_vec_f64, sizeof(double) * c->p); if (rc) return rc;
+            int rc = upload_vec(c, &F->chain_mem, (void**)&F->var_vec, P->var_effect_vec_f64, sizeof(double) * c->p); if (rc) return rc;
             D.var_vec = F->var_vec;
         } else NEED(c, D.var_effect[0] > 0.0, JWAS_HIP_EINVAL, "marker effect variance must be positive");
     }
@@ -2584,93 +2074,6 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
     return sweep_collect(c, S, 0, 0.0, nullptr);
 }
 
-// The nonzero effects of trait `trait` of a Float64 context as device lists in marker order (F->cmp_idx / F->cmp_val, owned by
-// the context), compacted on the device; *nnz = their number.
-static hipError_t f64_compact_alpha(jwas_hip_ctx* c, int32_t trait, int* nnz)
-{
-    auto* F = c->f64;
-    hipError_t e = hipSuccess;
-    if (!F->cmp_idx) {
-        e = hipMalloc(&F->cmp_idx, sizeof(int32_t) * ((size_t)c->p + 1));
-        if (e == hipSuccess) e = hipMalloc(&F->cmp_val, sizeof(double) * (size_t)c->p);
-        if (e != hipSuccess) { (void)hipFree(F->cmp_idx); F->cmp_idx = nullptr; return e; }
-    }
-    hipLaunchKernelGGL(jw64::k64_compact_alpha, dim3(1), dim3(1024), 0, c->stream, c->p, F->alpha + (size_t)trait * c->p, F->cmp_idx, F->cmp_val,
-                       F->cmp_idx + c->p);
-    e = hipGetLastError();
-    int32_t cnt = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&cnt, F->cmp_idx + c->p, sizeof cnt, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    *nnz = (int)cnt;
-    return e;
-}
-
-// out[0 .. n_rows) = M alpha_trait over the nonzero effects (compact + list), M = the training or the output matrix.
-static int f64_mul_alpha_rows(jwas_hip_ctx* c, int32_t trait, const double* M, int64_t ld, int64_t n_rows, double* out, const char* who)
-{
-    double* tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, sizeof(double) * ld));
-    int nnz = 0;
-    hipError_t e = f64_compact_alpha(c, trait, &nnz);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(jw64::k64_mul_alpha_list, dim3((unsigned)(ld / 64)), dim3(64), 0, c->stream, M, ld, nnz, c->f64->cmp_idx, c->f64->cmp_val, tmp);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, sizeof(double) * n_rows, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "%s: %s", who, hipGetErrorString(e));
-    return JWAS_HIP_OK;
-}
-
-// jwas_hip_window_sums(2)_f64: window_sums_impl with double effects over the Float64 matrices.
-static int f64_window_sums_impl(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
-                                const double* val, const double* val2, double* const* outs /* 2 or 5 arrays of nwin */)
-{
-    const int nv = val2 ? 5 : 2;
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    ONLY_F64(c);
-    auto* F = c->f64;
-    NEED(c, wptr, JWAS_HIP_EINVAL, "NULL argument");
-    for (int v = 0; v < nv; ++v) NEED(c, outs[v], JWAS_HIP_EINVAL, "NULL output array");
-    NEED(c, nwin >= 1, JWAS_HIP_EINVAL, "nwin must be >= 1 (got %d)", nwin);
-    NEED(c, F->X, JWAS_HIP_ESTATE, "no genotype matrix loaded");
-    NEED(c, !use_output_rows || F->Xout, JWAS_HIP_ESTATE, "jwas_hip_load_output_dense_f64 has not been called");
-    NEED(c, wptr[0] == 0, JWAS_HIP_EINVAL, "wptr[0] must be 0");
-    for (int w = 0; w < nwin; ++w) NEED(c, wptr[w + 1] >= wptr[w], JWAS_HIP_EINVAL, "wptr must be non-decreasing");
-    const int64_t nnz = wptr[nwin];
-    NEED(c, nnz == 0 || (idx && val), JWAS_HIP_EINVAL, "idx / val is NULL");
-    for (int64_t e = 0; e < nnz; ++e) NEED(c, idx[e] >= 0 && idx[e] < c->p, JWAS_HIP_EINVAL, "marker index %d out of range", idx[e]);
-    HIPCHK(c, hipSetDevice(c->device));
-    const double* M = use_output_rows ? F->Xout : F->X;
-    const int64_t ld = use_output_rows ? F->ld_out : c->ld;
-    const int nsl = (int)(ld / kSliceRows);
-    const size_t ne = (size_t)(nnz > 0 ? nnz : 1);
-    int32_t *d_wptr = nullptr, *d_idx = nullptr; double *d_val = nullptr, *d_val2 = nullptr, *d_part = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc(&d_wptr, sizeof(int32_t) * (nwin + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_idx, sizeof(int32_t) * ne);
-    if (e == hipSuccess) e = hipMalloc(&d_val, sizeof(double) * ne);
-    if (e == hipSuccess && val2) e = hipMalloc(&d_val2, sizeof(double) * ne);
-    if (e == hipSuccess) e = hipMalloc(&d_part, sizeof(double) * nv * (size_t)nwin * nsl);
-    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * nv * (size_t)nwin);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_wptr, wptr, sizeof(int32_t) * (nwin + 1), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_idx, idx, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_val, val, sizeof(double) * nnz, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz && val2) e = hipMemcpyAsync(d_val2, val2, sizeof(double) * nnz, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        if (val2) hipLaunchKernelGGL((jw64::k64_window_partial<5>), dim3((unsigned)nsl), dim3(256), 0, c->stream, M, ld, nwin, d_wptr, d_idx, d_val, d_val2, d_part);
-        else      hipLaunchKernelGGL((jw64::k64_window_partial<2>), dim3((unsigned)nsl), dim3(256), 0, c->stream, M, ld, nwin, d_wptr, d_idx, d_val, d_val2, d_part);
-        hipLaunchKernelGGL(k_window_reduce, dim3((unsigned)((nwin + 255) / 256)), dim3(256), 0, c->stream, nwin, nsl, nv, d_part, d_out);
-        e = hipGetLastError();
-    }
-    for (int v = 0; v < nv && e == hipSuccess; ++v)
-        e = hipMemcpyAsync(outs[v], d_out + (size_t)v * nwin, sizeof(double) * nwin, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_wptr); (void)hipFree(d_idx); (void)hipFree(d_val); (void)hipFree(d_val2); (void)hipFree(d_part); (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_window_sums_f64: %s", hipGetErrorString(e));
-    return JWAS_HIP_OK;
-}
-
 extern "C" {
 
 int jwas_hip_set_precision(jwas_hip_ctx* c, int32_t bits)
@@ -2693,7 +2096,6 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     auto* F = c->f64;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    f64_free_state(c);
     annot_free(c);                      // (the prior tables below belong to the markers of the old matrix)
     (void)hipFree(c->pi_vec); (void)hipFree(c->pi_mat); (void)hipFree(c->lpr_mat);      // (sized by the old p: upload_vec allocates once)
     c->pi_vec = c->pi_mat = c->lpr_mat = nullptr;
@@ -2704,18 +2106,17 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     rrm_free(c);
     mega_free(c);
     gblup_free(c);
-    for (void* q : {(void*)F->X, (void*)F->r, (void*)F->xpx, (void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->w, (void*)F->ev_all}) (void)hipFree(q);
-    F->X = F->r = F->xpx = F->gram = F->partials = F->w = nullptr; F->ev = F->ev_all = nullptr; F->dparams = nullptr;
-    F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0; F->weighted = false;
-    for (void* q : {(void*)F->Xout, (void*)F->cmp_idx, (void*)F->cmp_val}) (void)hipFree(q);      // (sized by the old p)
-    F->Xout = nullptr; F->n_out = F->ld_out = 0; F->cmp_idx = nullptr; F->cmp_val = nullptr;
+    F->drop();                          // (genotypes, residual, weights, x'x, output rows and the lists sized by the old p, the chain's state)
+    for (void* q : {(void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->ev_all}) (void)hipFree(q);
+    F->gram = F->partials = nullptr; F->ev = F->ev_all = nullptr; F->dparams = nullptr;
+    F->partials_cap = 0; F->ev_all_cap = 0; F->starts.clear(); F->bstride = 0;
     (void)hipFree(c->counters); (void)hipFree(c->fin_out); (void)hipFree(c->stat_out); if (c->host_buf) (void)hipHostFree(c->host_buf);
     c->counters = nullptr; c->fin_out = c->stat_out = nullptr; c->host_buf = nullptr;
     c->method = -1; c->ntraits = 0; c->block_size = 0; c->nblocks = 0;
     c->n = n; c->p = p; c->ld = round_up(n, kSliceRows); c->nslices = (int)(c->ld / kSliceRows);
-    HIPCHK(c, hipMalloc(&F->X, sizeof(double) * (size_t)c->ld * p));
-    HIPCHK(c, hipMalloc(&F->r, sizeof(double) * 2 * (size_t)kMaxT * c->ld));                // two buffers: a sweep's launches alternate
-    HIPCHK(c, hipMalloc(&F->w, sizeof(double) * (size_t)c->ld));
+    HIPCHK(c, F->load_mem.alloc(&F->X, sizeof(double) * (size_t)c->ld * p));
+    HIPCHK(c, F->load_mem.alloc(&F->r, sizeof(double) * 2 * (size_t)kMaxT * c->ld));                // two buffers: a sweep's launches alternate
+    HIPCHK(c, F->load_mem.alloc(&F->w, sizeof(double) * (size_t)c->ld));
     {
         std::vector<double> ones((size_t)c->ld, 0.0);
         for (int64_t i = 0; i < n; ++i) ones[(size_t)i] = 1.0;
@@ -2736,178 +2137,32 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     return JWAS_HIP_OK;
 }
 
-int jwas_hip_get_xpx_f64(jwas_hip_ctx* c, double* out)
-{
-    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
-    ONLY_F64(c);
-    NEED(c, c->f64->xpx, JWAS_HIP_ESTATE, "jwas_hip_setup_blocks has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->f64->xpx, sizeof(double) * c->p, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_set_state_f64(jwas_hip_ctx* c, int32_t trait, const double* a, const double* b, const void* d)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    ONLY_F64(c);
-    NEED_TRAIT(c, trait);
-    auto* F = c->f64;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = sizeof(double) * c->p, off = (size_t)trait * c->p;
-    if (a) HIPCHK(c, hipMemcpyAsync(F->alpha + off, a, nb, hipMemcpyHostToDevice, c->stream));
-    if (b) HIPCHK(c, hipMemcpyAsync(F->beta + off, b, nb, hipMemcpyHostToDevice, c->stream));
-    if (d) {
-        if (c->method == JWAS_HIP_BAYESR) HIPCHK(c, hipMemcpyAsync(F->delta, d, sizeof(int32_t) * c->p, hipMemcpyHostToDevice, c->stream));
-        else HIPCHK(c, hipMemcpyAsync((double*)F->delta + off, d, nb, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_get_state_f64(jwas_hip_ctx* c, int32_t trait, double* a, double* b, void* d)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    ONLY_F64(c);
-    NEED_TRAIT(c, trait);
-    auto* F = c->f64;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = sizeof(double) * c->p, off = (size_t)trait * c->p;
-    if (a) HIPCHK(c, hipMemcpyAsync(a, F->alpha + off, nb, hipMemcpyDeviceToHost, c->stream));
-    if (b) HIPCHK(c, hipMemcpyAsync(b, F->beta + off, nb, hipMemcpyDeviceToHost, c->stream));
-    if (d) {
-        if (c->method == JWAS_HIP_BAYESR) HIPCHK(c, hipMemcpyAsync(d, F->delta, sizeof(int32_t) * c->p, hipMemcpyDeviceToHost, c->stream));
-        else HIPCHK(c, hipMemcpyAsync(d, (double*)F->delta + off, nb, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_set_residual_f64(jwas_hip_ctx* c, int32_t trait, const double* rh)
-{
-    NEED(c, c && rh, JWAS_HIP_EINVAL, "NULL argument");
-    ONLY_F64(c);
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->f64->r + (size_t)trait * c->ld, rh, sizeof(double) * c->n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_get_residual_f64(jwas_hip_ctx* c, int32_t trait, double* rh)
-{
-    NEED(c, c && rh, JWAS_HIP_EINVAL, "NULL argument");
-    ONLY_F64(c);
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(rh, c->f64->r + (size_t)trait * c->ld, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-// getEBV's X*alpha (output.jl:281-306) with T = Float64, over the nonzero effects only: the same fma chain in marker order as
-// k64_mul_alpha, hence the same bits.
-int jwas_hip_mul_alpha_f64(jwas_hip_ctx* c, int32_t trait, double* out)
-{
-    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
-    ONLY_F64(c);
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    return f64_mul_alpha_rows(c, trait, c->f64->X, c->ld, c->n, out, "jwas_hip_mul_alpha_f64");
-}
-
-// Mi.output_genotypes = Z_out * genotypes in Float64 (tools4genotypes.jl:290-296 after JWAS.jl:353): a second resident matrix
-// next to the training rows; a second call replaces it, jwas_hip_load_dense_f64 and jwas_hip_destroy free it.
-int jwas_hip_load_output_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n_out, int64_t p, int64_t ld_host)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    ONLY_F64(c);
-    NEED(c, Xh, JWAS_HIP_EINVAL, "X_out is NULL");
-    auto* F = c->f64;
-    NEED(c, F->X, JWAS_HIP_ESTATE, "no genotype matrix loaded");
-    NEED(c, n_out >= 1, JWAS_HIP_EINVAL, "n_out must be >= 1 (got %lld)", (long long)n_out);
-    NEED(c, p == c->p, JWAS_HIP_EINVAL, "output genotypes have %lld markers, the training matrix %lld", (long long)p, (long long)c->p);
-    NEED(c, ld_host >= n_out, JWAS_HIP_EINVAL, "ld_host (%lld) must be >= n_out (%lld)", (long long)ld_host, (long long)n_out);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->gw.out_rows) gwas_free(c);
-    (void)hipFree(F->Xout); F->Xout = nullptr; F->n_out = F->ld_out = 0;
-    const int64_t ld = round_up(n_out, kSliceRows);
-    HIPCHK(c, hipMalloc(&F->Xout, sizeof(double) * (size_t)ld * p));
-    F->n_out = n_out; F->ld_out = ld;
-    if (ld != n_out) HIPCHK(c, hipMemsetAsync(F->Xout, 0, sizeof(double) * (size_t)ld * p, c->stream));      // pad rows zero
-    HIPCHK(c, hipMemcpy2DAsync(F->Xout, sizeof(double) * ld, Xh, sizeof(double) * ld_host, sizeof(double) * n_out, (size_t)p,
-                               hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-// EBV = output_genotypes * alpha for a saved sample (output.jl:281-306), T = Float64.
-int jwas_hip_mul_alpha_output_f64(jwas_hip_ctx* c, int32_t trait, double* out)
-{
-    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
-    ONLY_F64(c);
-    NEED_TRAIT(c, trait);
-    NEED(c, c->f64->Xout, JWAS_HIP_ESTATE, "jwas_hip_load_output_dense_f64 has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    return f64_mul_alpha_rows(c, trait, c->f64->Xout, c->f64->ld_out, c->f64->n_out, out, "jwas_hip_mul_alpha_output_f64");
-}
-
-// One saved marker-effect sample of a Float64 chain as a sparse record (output.jl:443-526 writes the dense text row).  idx / val:
-// caller arrays of `capacity` entries, marker order; *nnz_out is filled even when they are too short (grow and call again).
-int jwas_hip_get_alpha_sparse_f64(jwas_hip_ctx* c, int32_t trait, int64_t capacity, int32_t* idx, double* val, int64_t* nnz_out)
-{
-    NEED(c, c && nnz_out, JWAS_HIP_EINVAL, "NULL argument");
-    ONLY_F64(c);
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    int nnz = 0;
-    HIPCHK(c, f64_compact_alpha(c, trait, &nnz));
-    *nnz_out = nnz;
-    NEED(c, nnz <= capacity, JWAS_HIP_EINVAL, "%d nonzero effects do not fit the caller's %lld entries", nnz, (long long)capacity);
-    if (nnz > 0) {
-        NEED(c, idx && val, JWAS_HIP_EINVAL, "idx / val is NULL");
-        HIPCHK(c, hipMemcpyAsync(idx, c->f64->cmp_idx, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(val, c->f64->cmp_val, sizeof(double) * nnz, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return JWAS_HIP_OK;
-}
-
-// The window GWAS inner loop with T = Float64 (GWAS.jl:148,152-165: X*alpha in the element type of output_genotypes).
-int jwas_hip_window_sums_f64(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
-                             const double* val, double* out_sum, double* out_ss)
-{
-    double* outs[2] = {out_sum, out_ss};
-    return f64_window_sums_impl(c, use_output_rows, nwin, wptr, idx, val, nullptr, outs);
-}
-
-// ... and the window genetic covariance / correlation of two traits' samples (GWAS.jl:199-217).
-int jwas_hip_window_sums2_f64(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const int32_t* wptr, const int32_t* idx,
-                              const double* val1, const double* val2, double* out_sum1, double* out_ss1, double* out_sum2,
-                              double* out_ss2, double* out_cross)
-{
-    NEED(c, c && val2, JWAS_HIP_EINVAL, "NULL argument");
-    double* outs[5] = {out_sum1, out_ss1, out_sum2, out_ss2, out_cross};
-    return f64_window_sums_impl(c, use_output_rows, nwin, wptr, idx, val1, val2, outs);
-}
-
-int jwas_hip_get_posterior_f64(jwas_hip_ctx* c, int32_t trait, double* ma, double* ma2, double* md)
-{
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    ONLY_F64(c);
-    NEED_TRAIT(c, trait);
-    auto* F = c->f64;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = sizeof(double) * c->p, off = (size_t)trait * c->p;
-    if (ma) HIPCHK(c, hipMemcpyAsync(ma, F->mean_a + off, nb, hipMemcpyDeviceToHost, c->stream));
-    if (ma2) HIPCHK(c, hipMemcpyAsync(ma2, F->mean_a2 + off, nb, hipMemcpyDeviceToHost, c->stream));
-    if (md) HIPCHK(c, hipMemcpyAsync(md, F->mean_d + off, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
 }  // extern "C"
+
+// the launch of jwas_hip_sample_marker_covariances on one half of the context
+static void launch_marker_covariances(int t, dim3 g, hipStream_t st, const IwParams& Q, int64_t p, const float* beta, float* var_mat)
+{
+    if (t == 2) hipLaunchKernelGGL((k_sample_marker_covariances<2>), g, dim3(256), 0, st, Q, p, beta, var_mat);
+    else if (t == 3) hipLaunchKernelGGL((k_sample_marker_covariances<3>), g, dim3(256), 0, st, Q, p, beta, var_mat);
+    else hipLaunchKernelGGL((k_sample_marker_covariances<4>), g, dim3(256), 0, st, Q, p, beta, var_mat);
+}
+static void launch_marker_covariances(int t, dim3 g, hipStream_t st, const IwParams& Q, int64_t p, const double* beta, double* var_mat)
+{
+    if (t == 2) hipLaunchKernelGGL((jw64::k64_sample_marker_covariances<2>), g, dim3(256), 0, st, Q, p, beta, var_mat);
+    else if (t == 3) hipLaunchKernelGGL((jw64::k64_sample_marker_covariances<3>), g, dim3(256), 0, st, Q, p, beta, var_mat);
+    else hipLaunchKernelGGL((jw64::k64_sample_marker_covariances<4>), g, dim3(256), 0, st, Q, p, beta, var_mat);
+}
+template <class T>
+static int draw_marker_covariances(jwas_hip_ctx* c, Side<T>& S, const IwParams& Q)
+{
+    const int t = c->ntraits;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!S.var_mat) HIPCHK(c, S.chain_mem.alloc(&S.var_mat, sizeof(T) * (size_t)t * t * c->p));
+    launch_marker_covariances(t, dim3((unsigned)((c->p + 255) / 256)), c->stream, Q, c->p, (const T*)S.beta, S.var_mat);
+    HIPCHK(c, hipGetLastError());
+    S.var_mat_resident = true;
+    return JWAS_HIP_OK;
+}
 
 extern "C" {
 
@@ -3082,131 +2337,24 @@ int jwas_hip_sweep_sharded(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_swe
 }
 
 // ---- multi-trait BayesA/B: the per-marker effect covariances drawn on the device -------------------------------
-// Float64 context: the draws from the double beta into the double covariances (k64_sample_marker_covariances)
-static int f64_sample_marker_covariances(jwas_hip_ctx* c, double df, const double* scale, uint64_t seed, uint32_t iteration, uint32_t marker_offset)
-{
-    auto* F = c->f64;
-    NEED(c, c->method == JWAS_HIP_MTBAYESB1 || c->method == JWAS_HIP_MTBAYESB2, JWAS_HIP_ESTATE,
-         "jwas_hip_sample_marker_covariances needs init_state(JWAS_HIP_MTBAYESB1 | JWAS_HIP_MTBAYESB2, t)");
-    const int t = c->ntraits;
-    NEED(c, df > (double)(t - 1), JWAS_HIP_EINVAL, "inverse-Wishart degrees of freedom must exceed ntraits - 1 (got %g)", df);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!F->var_mat) HIPCHK(c, hipMalloc(&F->var_mat, sizeof(double) * (size_t)t * t * c->p));
-    IwParams Q;
-    std::memset(&Q, 0, sizeof Q);
-    Q.df = df;
-    for (int i = 0; i < t * t; ++i) Q.scale[i] = scale[i];
-    Q.seed_lo = (uint32_t)seed; Q.seed_hi = (uint32_t)(seed >> 32); Q.iter = iteration; Q.marker0 = marker_offset;
-    const dim3 g((unsigned)((c->p + 255) / 256)), b(256);
-    if (t == 2) hipLaunchKernelGGL((jw64::k64_sample_marker_covariances<2>), g, b, 0, c->stream, Q, c->p, F->beta, F->var_mat);
-    else if (t == 3) hipLaunchKernelGGL((jw64::k64_sample_marker_covariances<3>), g, b, 0, c->stream, Q, c->p, F->beta, F->var_mat);
-    else hipLaunchKernelGGL((jw64::k64_sample_marker_covariances<4>), g, b, 0, c->stream, Q, c->p, F->beta, F->var_mat);
-    HIPCHK(c, hipGetLastError());
-    F->var_mat_resident = true;
-    return JWAS_HIP_OK;
-}
-
+// G_j ~ InverseWishart(df, scale + b_j b_j') for every marker from the resident beta (variance_components.jl:181-186).  A Float32
+// context also draws for constraint = true (MEGABAYESB: scaled inverse chi-square draws of the diagonal only); a Float64 context
+// has no such sampler.
 int jwas_hip_sample_marker_covariances(jwas_hip_ctx* c, double df, const double* scale, uint64_t seed, uint32_t iteration, uint32_t marker_offset)
 {
     NEED(c, c && scale, JWAS_HIP_EINVAL, "NULL argument");
-    if (IS_F64(c)) return f64_sample_marker_covariances(c, df, scale, seed, iteration, marker_offset);
-    NEED(c, has_marker_cov(c->method), JWAS_HIP_ESTATE, "jwas_hip_sample_marker_covariances needs init_state(JWAS_HIP_MTBAYESB1 | JWAS_HIP_MTBAYESB2 | JWAS_HIP_MEGABAYESB, t)");
-    const int t = c->ntraits;
-    const bool diag = is_mega(c->method);           // constraint = true: scaled inverse chi-square draws of the diagonal only
-    NEED(c, df > (diag ? 0.0 : (double)(t - 1)), JWAS_HIP_EINVAL, "inverse-Wishart degrees of freedom must exceed ntraits - 1 (got %g)", df);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t mb = sizeof(float) * (size_t)t * t * c->p;
-    if (!c->var_mat) HIPCHK(c, hipMalloc(&c->var_mat, mb));
+    if (IS_F64(c))
+        NEED(c, c->method == JWAS_HIP_MTBAYESB1 || c->method == JWAS_HIP_MTBAYESB2, JWAS_HIP_ESTATE,
+             "jwas_hip_sample_marker_covariances needs init_state(JWAS_HIP_MTBAYESB1 | JWAS_HIP_MTBAYESB2, t)");
+    else
+        NEED(c, has_marker_cov(c->method), JWAS_HIP_ESTATE, "jwas_hip_sample_marker_covariances needs init_state(JWAS_HIP_MTBAYESB1 | JWAS_HIP_MTBAYESB2 | JWAS_HIP_MEGABAYESB, t)");
     IwParams Q;
     std::memset(&Q, 0, sizeof Q);
-    Q.df = df; Q.diagonal = diag ? 1 : 0;
-    for (int i = 0; i < t * t; ++i) Q.scale[i] = scale[i];
+    Q.df = df; Q.diagonal = is_mega(c->method) ? 1 : 0;
+    NEED(c, df > (Q.diagonal ? 0.0 : (double)(c->ntraits - 1)), JWAS_HIP_EINVAL, "inverse-Wishart degrees of freedom must exceed ntraits - 1 (got %g)", df);
+    for (int i = 0; i < c->ntraits * c->ntraits; ++i) Q.scale[i] = scale[i];
     Q.seed_lo = (uint32_t)seed; Q.seed_hi = (uint32_t)(seed >> 32); Q.iter = iteration; Q.marker0 = marker_offset;
-    const dim3 g((unsigned)((c->p + 255) / 256)), b(256);
-    if (t == 2) hipLaunchKernelGGL((k_sample_marker_covariances<2>), g, b, 0, c->stream, Q, c->p, c->beta, c->var_mat);
-    else if (t == 3) hipLaunchKernelGGL((k_sample_marker_covariances<3>), g, b, 0, c->stream, Q, c->p, c->beta, c->var_mat);
-    else hipLaunchKernelGGL((k_sample_marker_covariances<4>), g, b, 0, c->stream, Q, c->p, c->beta, c->var_mat);
-    HIPCHK(c, hipGetLastError());
-    c->var_mat_resident = true;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_get_marker_covariances(jwas_hip_ctx* c, float* out)
-{
-    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
-    NOT_F64(c, "jwas_hip_get_marker_covariances (use jwas_hip_get_marker_covariances_f64)");
-    NEED(c, c->var_mat && c->var_mat_resident, JWAS_HIP_ESTATE, "no per-marker effect covariances are resident");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->var_mat, sizeof(float) * (size_t)c->ntraits * c->ntraits * c->p, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-// Float64 context, multi-trait BayesA/B: the p x t x t per-marker covariances in double (host <-> device)
-int jwas_hip_set_marker_covariances_f64(jwas_hip_ctx* c, const double* mat)
-{
-    NEED(c, c && mat, JWAS_HIP_EINVAL, "NULL argument");
-    ONLY_F64(c);
-    NEED(c, c->method == JWAS_HIP_MTBAYESB1 || c->method == JWAS_HIP_MTBAYESB2, JWAS_HIP_ESTATE,
-         "jwas_hip_set_marker_covariances_f64 needs init_state(JWAS_HIP_MTBAYESB1 | JWAS_HIP_MTBAYESB2, t)");
-    auto* F = c->f64;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t mb = sizeof(double) * (size_t)c->ntraits * c->ntraits * c->p;
-    if (!F->var_mat) HIPCHK(c, hipMalloc(&F->var_mat, mb));
-    HIPCHK(c, hipMemcpyAsync(F->var_mat, mat, mb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    F->var_mat_resident = true;
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_get_marker_covariances_f64(jwas_hip_ctx* c, double* out)
-{
-    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
-    ONLY_F64(c);
-    auto* F = c->f64;
-    NEED(c, F->var_mat && F->var_mat_resident, JWAS_HIP_ESTATE, "no per-marker effect covariances are resident");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, F->var_mat, sizeof(double) * (size_t)c->ntraits * c->ntraits * c->p, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
-}
-
-// ---- posterior accumulators ---------------------------------------------------------------------------
-int jwas_hip_accumulate(jwas_hip_ctx* c, double k)
-{
-    if (c && IS_F64(c)) {
-        NEED(c, c->method >= 0, JWAS_HIP_ESTATE, "jwas_hip_init_state has not been called");
-        NEED(c, k >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1");
-        HIPCHK(c, hipSetDevice(c->device));
-        const int64_t count = (int64_t)c->ntraits * c->p;
-        hipLaunchKernelGGL(jw64::k64_accumulate, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, count, (int)(c->method == JWAS_HIP_BAYESR), k,
-                           c->f64->alpha, c->f64->delta, c->f64->mean_a, c->f64->mean_a2, c->f64->mean_d);
-        HIPCHK(c, hipGetLastError());
-        return JWAS_HIP_OK;
-    }
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, c->method >= 0, JWAS_HIP_ESTATE, "jwas_hip_init_state has not been called");
-    NEED(c, k >= 1.0, JWAS_HIP_EINVAL, "nsamples must be >= 1");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t count = (int64_t)c->ntraits * c->p;
-    hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, count,
-                       (int)(c->method == JWAS_HIP_BAYESR), k, c->alpha, c->delta, c->mean_a, c->mean_a2, c->mean_d);
-    HIPCHK(c, hipGetLastError());
-    return JWAS_HIP_OK;
-}
-
-int jwas_hip_get_posterior(jwas_hip_ctx* c, int32_t trait, float* ma, float* ma2, float* md)
-{
-    if (c) NOT_F64(c, "jwas_hip_get_posterior (use jwas_hip_get_posterior_f64)");
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED_TRAIT(c, trait);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = sizeof(float) * c->p, off = (size_t)trait * c->p;
-    if (ma) HIPCHK(c, hipMemcpyAsync(ma, c->mean_a + off, nb, hipMemcpyDeviceToHost, c->stream));
-    if (ma2) HIPCHK(c, hipMemcpyAsync(ma2, c->mean_a2 + off, nb, hipMemcpyDeviceToHost, c->stream));
-    if (md) HIPCHK(c, hipMemcpyAsync(md, c->mean_d + off, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
+    return on_side(c, [&](auto& S) { return draw_marker_covariances(c, S, Q); });
 }
 
 }  // extern "C"

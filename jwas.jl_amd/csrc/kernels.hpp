@@ -856,23 +856,6 @@ __global__ __launch_bounds__(256) void k_marker_stats(int method, int64_t p, con
         for (int i = 0; i < kNStat; ++i) out[(int64_t)blockIdx.x * kNStat + i] = v[i];
 }
 
-// running posterior means (output.jl:568-577)
-JW_PLAIN_KERNEL __global__ __launch_bounds__(256) void k_accumulate(int64_t count, int delta_is_class, double k,
-                                                    const float* __restrict__ alpha, const void* __restrict__ delta_v,
-                                                    float* __restrict__ mean_a, float* __restrict__ mean_a2,
-                                                    float* __restrict__ mean_d)
-{
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= count) return;
-    const float a = alpha[j];
-    mean_a[j]  = (float)((double)mean_a[j] + ((double)(a - mean_a[j])) / k);
-    const float a2 = a * a;
-    mean_a2[j] = (float)((double)mean_a2[j] + ((double)(a2 - mean_a2[j])) / k);
-    const float ind = delta_is_class ? (reinterpret_cast<const int32_t*>(delta_v)[j] > 1 ? 1.f : 0.f)
-                                     : reinterpret_cast<const float*>(delta_v)[j];
-    mean_d[j]  = (float)((double)mean_d[j] + ((double)(ind - mean_d[j])) / k);
-}
-
 // ---------------------------------------------------------------------------------------------
 // storage-layer precompute
 // ---------------------------------------------------------------------------------------------
@@ -1147,214 +1130,6 @@ __global__ __launch_bounds__(256) void k_cross_mfma128(CX cx, int64_t p, int bsi
                 const int gc = tj * 128 + wn * 64 + 32 * y + (lane & 31);
                 if (ga < bA && gc < b) G[(int64_t)ga * b + gc] = (float)v;
             }
-}
-
-// ---------------------------------------------------------------------------------------------
-// X * alpha (EBV, output.jl:302) and r -= X*alpha0 (MCMC_BayesianAlphabet.jl:142)
-// grid = nslices, block = 256: one row per thread, columns in marker order.
-// ---------------------------------------------------------------------------------------------
-template <class CX>
-__global__ __launch_bounds__(256) void k_mul_alpha(CX cx, int64_t p,
-                                                   const float* __restrict__ alpha, float* __restrict__ out)
-{
-    const int64_t row = (int64_t)blockIdx.x * kSliceRows + threadIdx.x;
-    double s = 0.0;
-    // dense effects (the sparse case goes through k_mul_alpha_list): 16 independent column loads in flight per thread;
-    // a zero effect contributes fma(0, x, s) = s exactly, so nothing is skipped and nothing branches
-    constexpr int kUn = 16;
-    int64_t j = 0;
-    for (; j + kUn <= p; j += kUn) {
-        float x[kUn];
-#pragma unroll
-        for (int u = 0; u < kUn; ++u) x[u] = cx.load1(j + u, row);
-#pragma unroll
-        for (int u = 0; u < kUn; ++u) s = fma((double)alpha[j + u], (double)x[u], s);
-    }
-    for (; j < p; ++j) s = fma((double)alpha[j], (double)cx.load1(j, row), s);
-    out[row] = (float)s;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Window genomic values of one marker-effect sample (GWAS.jl:152-165): window w holds the nonzero effects
-// idx[wptr[w] .. wptr[w+1]) with values val[..]; BV_w[i] = sum_j X[i, idx_j] * val_j (fp64-accumulated, fixed order).
-// grid = nslices, block = 256 (one individual per thread); partial[(w * nslices + slice) * 2 + {0,1}] = the slice's
-// sum of BV_w and of BV_w^2.  k_window_reduce then adds the slices in fixed order (deterministic, no atomics).
-// ---------------------------------------------------------------------------------------------
-// NV = 2: (sum, sum of squares) of one effect vector;  NV = 5: two effect vectors over the same markers (two traits'
-// samples): (sum1, ss1, sum2, ss2, sum of products) -- the window genetic covariance / correlation of GWAS.jl:199-217.
-template <class CX, int NV>
-__global__ __launch_bounds__(256) void k_window_partial(CX cx, int nwin, const int32_t* __restrict__ wptr,
-                                                        const int32_t* __restrict__ idx, const float* __restrict__ val,
-                                                        const float* __restrict__ val2, double* __restrict__ partial)
-{
-    __shared__ double red[NV][4];
-    const int64_t row = (int64_t)blockIdx.x * kSliceRows + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int w = 0; w < nwin; ++w) {
-        double bv = 0.0, bv2 = 0.0;
-        for (int e = wptr[w]; e < wptr[w + 1]; ++e) {
-            const double x = (double)cx.load1(idx[e], row);
-            bv = fma((double)val[e], x, bv);
-            if constexpr (NV == 5) bv2 = fma((double)val2[e], x, bv2);
-        }
-        double v[NV];
-        v[0] = bv; v[1] = bv * bv;
-        if constexpr (NV == 5) { v[2] = bv2; v[3] = bv2 * bv2; v[4] = bv * bv2; }
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-            if (lane == 0) red[k][wave] = v[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < NV)
-            partial[((int64_t)w * gridDim.x + blockIdx.x) * NV + threadIdx.x] =
-                ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
-        __syncthreads();
-    }
-}
-// out[v * nwin + w] = sum over the slices (fixed order) of value v of window w
-JW_PLAIN_KERNEL __global__ __launch_bounds__(256) void k_window_reduce(int nwin, int nslices, int nv, const double* __restrict__ partial,
-                                                       double* __restrict__ out)
-{
-    const int w = blockIdx.x * 256 + threadIdx.x;
-    if (w >= nwin) return;
-    for (int v = 0; v < nv; ++v) {
-        double s = 0.0;
-        for (int k = 0; k < nslices; ++k) s += partial[((int64_t)w * nslices + k) * nv + v];
-        out[(int64_t)v * nwin + w] = s;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The GWAS session (jwas_hip_gwas_begin / _sample / _local_ebv; GWAS.jl:149-173): one saved sample is ONE ascending
-// (idx, val) list; entry 0 of the session is "all markers" (genVar, GWAS.jl:155), entry 1 + w is window w = the
-// columns [cs[w], ce[w]).
-// k_gwas_slices: the slice [lo, hi) of the list that falls into every entry (lower bounds, numpy's searchsorted).
-// grid = cld(nent, 256), block = 256.
-// ---------------------------------------------------------------------------------------------
-JW_PLAIN_KERNEL __global__ __launch_bounds__(256) void k_gwas_slices(int nent, int nnz, const int32_t* __restrict__ cs, const int32_t* __restrict__ ce,
-                                                     const int32_t* __restrict__ idx, int32_t* __restrict__ lo, int32_t* __restrict__ hi)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= nent) return;
-    if (t == 0) { lo[0] = 0; hi[0] = nnz; return; }
-    auto lower = [&](int32_t key) {
-        int a = 0, b = nnz;
-        while (a < b) { const int m = (a + b) >> 1; if (idx[m] < key) a = m + 1; else b = m; }
-        return a;
-    };
-    lo[t] = lower(cs[t - 1]);
-    hi[t] = lower(ce[t - 1]);
-}
-
-// K column loads of one row in flight, then their fma chain in list order: k_window_partial's term, bit for bit.
-template <int K, class CX>
-__device__ __forceinline__ void gwas_terms(const CX& cx, int64_t row, const int32_t* __restrict__ idx, const float* __restrict__ val, int e, double& acc)
-{
-    float x[K];
-#pragma unroll
-    for (int u = 0; u < K; ++u) x[u] = cx.load1(idx[e + u], row);
-#pragma unroll
-    for (int u = 0; u < K; ++u) acc = fma((double)val[e + u], (double)x[u], acc);
-}
-
-// k_gwas_partial: k_window_partial over a grid of row slices x entry chunks.  grid = (nslices, nchunks), block = 256 (one
-// individual per thread, so a column load is one coalesced 1 KB instruction per wave); chunk 0 is entry 0 alone (its list is
-// as long as all disjoint windows together), chunk 1 + k holds the windows [k wpc, (k + 1) wpc).  A thread keeps 16 / 4 / 1
-// column loads of an entry's list in flight and adds them in list order; the slice's (sum, sum of squares) are reduced as in
-// k_window_partial (wave shuffle tree, ((0 + 1) + 2) + 3) into partial[(entry * nslices + slice) * 2 + {0, 1}] and the slices
-// are added by k_window_reduce: the same bits as jwas_hip_window_sums.  LEBV: acc[w * ld_acc + row] += BV_w[row], the running
-// SUM of the local EBVs (GWAS.jl:159-164; divided by the sample count on read-out); one owner per element, no atomics; an
-// entry without a nonzero effect in this sample adds 0 and is skipped.
-template <class CX, bool LEBV>
-__global__ __launch_bounds__(256) void k_gwas_partial(CX cx, int nent, int wpc, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
-                                                      const int32_t* __restrict__ idx, const float* __restrict__ val,
-                                                      double* __restrict__ partial, double* __restrict__ acc, int64_t ld_acc)
-{
-    __shared__ double red[2][4];
-    const int64_t row = (int64_t)blockIdx.x * kSliceRows + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int w0 = blockIdx.y == 0 ? 0 : 1 + ((int)blockIdx.y - 1) * wpc;
-    const int w1 = blockIdx.y == 0 ? 1 : (w0 + wpc < nent ? w0 + wpc : nent);
-    for (int w = w0; w < w1; ++w) {
-        double bv = 0.0;
-        const int e_lo = lo[w], e_hi = hi[w];
-        int e = e_lo;
-        for (; e + 16 <= e_hi; e += 16) gwas_terms<16>(cx, row, idx, val, e, bv);
-        for (; e + 4 <= e_hi; e += 4) gwas_terms<4>(cx, row, idx, val, e, bv);
-        for (; e < e_hi; ++e) gwas_terms<1>(cx, row, idx, val, e, bv);
-        if constexpr (LEBV) { if (w >= 1 && e_hi > e_lo) acc[(int64_t)(w - 1) * ld_acc + row] += bv; }
-        double v[2];
-        v[0] = bv; v[1] = bv * bv;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-            if (lane == 0) red[k][wave] = v[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < 2)
-            partial[((int64_t)w * gridDim.x + blockIdx.x) * 2 + threadIdx.x] =
-                ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
-        __syncthreads();
-    }
-}
-
-// X * alpha over the nonzero effects only (marker order, the same fp64 accumulation as k_mul_alpha -> identical
-// results): with a sparse prior a saved sample has a few hundred nonzero effects among 600 000, and the loop over all
-// markers (one scalar load + branch each) costs 39 ms where the 600 useful columns cost 30 us.
-template <class CX>
-__global__ __launch_bounds__(256) void k_mul_alpha_list(CX cx, int nnz, const int32_t* __restrict__ idx,
-                                                        const float* __restrict__ val, float* __restrict__ out)
-{
-    const int64_t row = (int64_t)blockIdx.x * kSliceRows + threadIdx.x;
-    double s = 0.0;
-    for (int e = 0; e < nnz; ++e) s = fma((double)val[e], (double)cx.load1(idx[e], row), s);
-    out[row] = (float)s;
-}
-
-// The nonzero effects of one trait as (index, value) lists in marker order.  grid = 1, block = 1024: the workgroup walks
-// the p effects 1024 at a time with a running offset (ballot + wave prefix), ~30 us at p = 600 000.
-JW_PLAIN_KERNEL __global__ __launch_bounds__(1024) void k_compact_alpha(int64_t p, const float* __restrict__ alpha, int32_t* __restrict__ idx,
-                                                        float* __restrict__ val, int32_t* __restrict__ count)
-{
-    __shared__ int wsum[16];
-    __shared__ int base_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
-    for (int64_t j0 = 0; j0 < p; j0 += 1024) {
-        const int64_t j = j0 + tid;
-        const float a = j < p ? alpha[j] : 0.f;
-        const bool nz = a != 0.f;
-        const unsigned long long m = __ballot(nz);
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int pre = base_s, tot = 0;
-        for (int w = 0; w < 16; ++w) { if (w < wave) pre += wsum[w]; tot += wsum[w]; }
-        if (nz) {
-            const int pos = pre + __popcll(m & ((1ull << lane) - 1ull));
-            idx[pos] = (int32_t)j; val[pos] = a;
-        }
-        __syncthreads();
-        if (tid == 0) base_s += tot;
-        __syncthreads();
-    }
-    if (tid == 0) *count = base_s;
-}
-
-template <class CX>
-__global__ __launch_bounds__(256) void k_sub_xalpha(CX cx, int64_t p,
-                                                    const float* __restrict__ alpha, float* __restrict__ r)
-{
-    const int64_t row = (int64_t)blockIdx.x * kSliceRows + threadIdx.x;
-    float rv = r[row];
-    for (int64_t j = 0; j < p; ++j) {
-        const float a = alpha[j];
-        if (a != 0.f) rv = fmaf(-a, cx.load1(j, row), rv);
-    }
-    r[row] = rv;
 }
 
 // ---------------------------------------------------------------------------------------------

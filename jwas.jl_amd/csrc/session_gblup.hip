@@ -6,11 +6,6 @@
 
 static_assert(jwb::kMaxT == JWAS_HIP_MAX_TRAITS && jwb::kGrmChunk == JWAS_HIP_GRM_CHUNK, "the header's limits are gblup.hpp's");
 
-static bool gblup_weighted(jwas_hip_ctx* c) { return IS_F64(c) ? c->f64->weighted : c->weighted; }
-static const void* gblup_matrix(jwas_hip_ctx* c) { return IS_F64(c) ? (const void*)c->f64->X : (const void*)c->X; }
-static void* gblup_alpha(jwas_hip_ctx* c) { return IS_F64(c) ? (void*)c->f64->alpha : (void*)c->alpha; }
-static void* gblup_beta(jwas_hip_ctx* c) { return IS_F64(c) ? (void*)c->f64->beta : (void*)c->beta; }
-
 void gblup_free(jwas_hip_ctx* c) { DevOwner::reset(c->gb); }
 
 // what jwas_hip_grm and jwas_hip_gblup_begin ask of the storage
@@ -18,15 +13,15 @@ static int need_dense(jwas_hip_ctx* c, const char* words)
 {
     NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
     NEED(c, !c->packed, JWAS_HIP_EUNSUP, "%s need dense genotypes (2-bit packed storage is not supported)", words);
-    NEED(c, gblup_matrix(c) && c->n > 0 && c->p > 0, JWAS_HIP_ESTATE, "no genotype matrix loaded");
+    NEED(c, genotypes_ptr(c) && c->n > 0 && c->p > 0, JWAS_HIP_ESTATE, "no genotype matrix loaded");
     return refuse_shards(c, words);
 }
 
 static int need_gblup(jwas_hip_ctx* c)
 {
     if (int rc = session_guard(c, &jwas_hip_ctx::gb, "jwas_hip_gblup_begin", "GBLUP steps")) return rc;
-    NEED(c, c->gb.mat == gblup_matrix(c), JWAS_HIP_ESTATE, "the genotypes were reloaded after jwas_hip_gblup_begin");
-    NEED(c, !gblup_weighted(c), JWAS_HIP_EUNSUP, "GBLUP does not run with residual weights");
+    NEED(c, c->gb.mat == genotypes_ptr(c), JWAS_HIP_ESTATE, "the genotypes were reloaded after jwas_hip_gblup_begin");
+    NEED(c, !is_weighted(c), JWAS_HIP_EUNSUP, "GBLUP does not run with residual weights");
     return JWAS_HIP_OK;
 }
 
@@ -64,10 +59,10 @@ template <class real, int T>
 static void gblup_launch(jwas_hip_ctx* c, const jwb::SampleArgs& A)
 {
     auto& b = c->gb;
-    const real* L = (const real*)gblup_matrix(c);
+    const real* L = (const real*)genotypes_ptr(c);
     real* r = (real*)residual_ptr(c);
     real* rplus = (real*)b.rplus;
-    const real* alpha = (const real*)gblup_alpha(c);
+    const real* alpha = (const real*)alpha_ptr(c);
     const int64_t n = c->n, ld = c->ld;
     const dim3 grid((unsigned)c->nslices, (unsigned)b.nparts);
     double* fin = b.stat + (size_t)b.nwg * T * T;
@@ -105,7 +100,7 @@ int jwas_hip_grm(jwas_hip_ctx* c, const void* divisor, void* K_host)
     if (e == hipSuccess) {
         with_real(c, [&](auto real) {
             using real_t = decltype(real);
-            hipLaunchKernelGGL((jwb::k_grm<real_t>), dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, c->stream, (const real_t*)gblup_matrix(c), c->ld, n, p,
+            hipLaunchKernelGGL((jwb::k_grm<real_t>), dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, c->stream, (const real_t*)genotypes_ptr(c), c->ld, n, p,
                                (const real_t*)d_div, (real_t*)d_K);
         });
         e = hipGetLastError();
@@ -126,7 +121,7 @@ int jwas_hip_gblup_begin(jwas_hip_ctx* c, const double* D)
 {
     if (int rc = need_dense(c, "GBLUP steps")) return rc;
     if (int rc = begin_guard(c, "GBLUP steps")) return rc;
-    NEED(c, !gblup_weighted(c), JWAS_HIP_EUNSUP, "GBLUP does not run with residual weights");
+    NEED(c, !is_weighted(c), JWAS_HIP_EUNSUP, "GBLUP does not run with residual weights");
     NEED(c, D, JWAS_HIP_EINVAL, "NULL argument");
     NEED(c, c->p == c->n, JWAS_HIP_EINVAL, "GBLUP needs the n x n matrix of eigenvectors (the loaded matrix is %lld x %lld)", (long long)c->n, (long long)c->p);
     NEED(c, c->ntraits >= 1 && c->ntraits <= jwb::kMaxT, JWAS_HIP_EINVAL, "GBLUP runs 1 to %d traits (the state has %d)", jwb::kMaxT, c->ntraits);
@@ -136,7 +131,7 @@ int jwas_hip_gblup_begin(jwas_hip_ctx* c, const double* D)
     auto& b = c->gb;
     const int T = c->ntraits;
     const size_t el = IS_F64(c) ? 8 : 4;
-    b.nt = T; b.nwg = (int)((n + 255) / 256); b.mat = gblup_matrix(c);
+    b.nt = T; b.nwg = (int)((n + 255) / 256); b.mat = genotypes_ptr(c);
     gblup_parts(n, c->nslices, b.nparts, b.len);
     auto alloc = [&](auto** ptr, size_t bytes) { return alloc_or_nomem(c, b.mem, ptr, bytes, "GBLUP session", gblup_free); };
     if (int rc = alloc(&b.D, sizeof(double) * (size_t)n)) return rc;
@@ -182,7 +177,7 @@ int jwas_hip_gblup_step(jwas_hip_ctx* c, const jwas_gblup_params* P, jwas_gblup_
     HIPCHK(c, hipMemcpyAsync(b.par, par, sizeof(par), hipMemcpyHostToDevice, c->stream));
     if (int rc = step_timer_begin(c)) return rc;
     jwb::SampleArgs A = {};
-    A.s = b.s; A.D = b.D; A.par = b.par; A.alpha = gblup_alpha(c); A.beta = gblup_beta(c); A.stat = b.stat; A.n = c->n; A.iter = P->iteration; A.first = P->first_trait;
+    A.s = b.s; A.D = b.D; A.par = b.par; A.alpha = alpha_ptr(c); A.beta = beta_ptr(c); A.stat = b.stat; A.n = c->n; A.iter = P->iteration; A.first = P->first_trait;
     A.diagonal = diagonal ? 1 : 0;
     split_seed(P->seed, A.seed_lo, A.seed_hi);
     with_real(c, [&](auto real) {

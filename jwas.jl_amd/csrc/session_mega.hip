@@ -8,12 +8,10 @@
 
 static_assert(jwg::kMaxT == JWAS_HIP_MEGA_MAX_TRAITS && jwg::kMaxBlock == JWAS_HIP_MEGA_MAX_BLOCK, "the header's limits are mega.hpp's");
 
-static bool mega_weighted(jwas_hip_ctx* c) { return IS_F64(c) ? c->f64->weighted : c->weighted; }
-
 static int need_mega(jwas_hip_ctx* c)
 {
     if (int rc = session_guard(c, &jwas_hip_ctx::mg, "jwas_hip_mega_begin")) return rc;
-    NEED(c, !mega_weighted(c), JWAS_HIP_EUNSUP, "mega-trait models do not run with residual weights");
+    NEED(c, !is_weighted(c), JWAS_HIP_EUNSUP, "mega-trait models do not run with residual weights");
     return refuse_shards(c, "mega-trait models");
 }
 
@@ -25,8 +23,6 @@ static int need_trait(jwas_hip_ctx* c, int32_t trait)
 }
 
 void mega_free(jwas_hip_ctx* c) { DevOwner::reset(c->mg); }
-
-static const void* mega_genotypes(jwas_hip_ctx* c) { return IS_F64(c) ? (const void*)c->f64->X : (const void*)c->X; }
 
 static int64_t mega_bytes(int64_t n, int64_t p, int T, int bs)
 {
@@ -78,13 +74,13 @@ static int mega_run_sweep(jwas_hip_ctx* c, uint32_t iteration, uint64_t seed, do
     if (int rc = step_timer_begin(c)) return rc;
     HIPCHK(c, hipMemsetAsync(stat, 0, sizeof(double) * nstat, c->stream));
     jwg::UpdateArgs U = {};
-    U.X = mega_genotypes(c); U.R = b.R; U.partials = b.partials; U.ld = c->ld; U.T = T; U.bs = b.bs;
+    U.X = genotypes_ptr(c); U.R = b.R; U.partials = b.partials; U.ld = c->ld; U.T = T; U.bs = b.bs;
     jwg::SampleArgs A = {};
     A.partials = b.partials; A.xpx = b.xpx; A.par = par; A.alpha = b.ms.alpha; A.beta = b.ms.beta; A.delta = b.ms.delta; A.ev = (jwg::Events*)b.ev;
     A.stat = stat; A.p = c->p; A.nslices = nsl; A.bs = b.bs; A.T = T; A.iter = iteration; A.first_trait = b.first_trait;
     split_seed(seed, A.seed_lo, A.seed_hi);
     jwg::FinishArgs F = {};
-    F.X = mega_genotypes(c); F.R = b.R; F.ev = (const jwg::Events*)b.ev; F.fin = stat + (size_t)T * rec; F.ld = c->ld; F.T = T;
+    F.X = genotypes_ptr(c); F.R = b.R; F.ev = (const jwg::Events*)b.ev; F.fin = stat + (size_t)T * rec; F.ld = c->ld; F.T = T;
     const dim3 tiles((unsigned)nsl, (unsigned)((T + jwg::kTT - 1) / jwg::kTT));
     with_real(c, [&](auto real) {
         using real_t = decltype(real);
@@ -116,9 +112,9 @@ int jwas_hip_mega_begin(jwas_hip_ctx* c, int32_t T, int32_t block_size, int32_t 
 {
     NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
     NEED(c, !c->packed, JWAS_HIP_EUNSUP, "mega-trait models need dense genotypes (2-bit packed storage is not supported)");
-    NEED(c, mega_genotypes(c) && c->n > 0 && c->p > 0, JWAS_HIP_ESTATE, "no genotype matrix loaded");
+    NEED(c, genotypes_ptr(c) && c->n > 0 && c->p > 0, JWAS_HIP_ESTATE, "no genotype matrix loaded");
     if (int rc = refuse_shards(c, "mega-trait models")) return rc;
-    NEED(c, !mega_weighted(c), JWAS_HIP_EUNSUP, "mega-trait models do not run with residual weights");
+    NEED(c, !is_weighted(c), JWAS_HIP_EUNSUP, "mega-trait models do not run with residual weights");
     NEED(c, T >= 1 && T <= jwg::kMaxT, JWAS_HIP_EINVAL, "the number of traits must be in [1,%d] (got %d)", jwg::kMaxT, T);
     NEED(c, block_size >= 0 && block_size <= jwg::kMaxBlock, JWAS_HIP_EINVAL, "block size must be in [1,%d] (0: 64), got %d", jwg::kMaxBlock, block_size);
     NEED(c, first_trait >= 0 && (int64_t)first_trait + T <= (int64_t)jwg::kMaxTraitId, JWAS_HIP_EINVAL,
@@ -153,7 +149,7 @@ int jwas_hip_mega_begin(jwas_hip_ctx* c, int32_t T, int32_t block_size, int32_t 
         for (int64_t k0 = 0; k0 < b.nblocks; k0 += 32768) {
             const int64_t nb = std::min<int64_t>(32768, b.nblocks - k0);
             hipLaunchKernelGGL((jwg::k_mega_gram<real_t>), dim3((unsigned)bs, (unsigned)nb), dim3(256), 0, c->stream,
-                               (const real_t*)mega_genotypes(c) + k0 * bs * ld, ld, p - k0 * bs, (int32_t)bs, b.gram + k0 * bs * bs, b.xpx + k0 * bs);
+                               (const real_t*)genotypes_ptr(c) + k0 * bs * ld, ld, p - k0 * bs, (int32_t)bs, b.gram + k0 * bs * bs, b.xpx + k0 * bs);
         }
     });
     HIPCHK(c, hipGetLastError());
@@ -346,13 +342,11 @@ int jwas_hip_mega_mul_alpha(jwas_hip_ctx* c, int32_t trait, int32_t use_output_r
     if (int rc = need_trait(c, trait)) return rc;
     auto& b = c->mg;
     NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
-    const void* X = mega_genotypes(c);
+    const void* X = genotypes_ptr(c);
     int64_t n = c->n, ld = c->ld;
     if (use_output_rows) {
-        X = IS_F64(c) ? (const void*)c->f64->Xout : (const void*)c->Xout;
+        X = output_rows_ptr(c, &n, &ld);
         NEED(c, X, JWAS_HIP_ESTATE, "no output rows loaded (jwas_hip_load_output_dense_f32 / _f64)");
-        n = IS_F64(c) ? c->f64->n_out : c->n_out;
-        ld = IS_F64(c) ? c->f64->ld_out : c->ld_out;
     }
     HIPCHK(c, hipSetDevice(c->device));
     if (ld > b.row_cap) {                                   // the output rows may outnumber the training rows

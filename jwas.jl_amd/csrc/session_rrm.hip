@@ -8,13 +8,11 @@
 static int need_rrm(jwas_hip_ctx* c)
 {
     if (int rc = session_guard(c, &jwas_hip_ctx::rr, "jwas_hip_rrm_begin")) return rc;
-    NEED(c, !(IS_F64(c) ? c->f64->weighted : c->weighted), JWAS_HIP_EUNSUP, "random regression models do not run with residual weights");
+    NEED(c, !is_weighted(c), JWAS_HIP_EUNSUP, "random regression models do not run with residual weights");
     return refuse_shards(c, "random regression models");
 }
 
 void rrm_free(jwas_hip_ctx* c) { DevOwner::reset(c->rr); }
-
-static const void* rrm_genotypes(jwas_hip_ctx* c) { return IS_F64(c) ? (const void*)c->f64->X : (const void*)c->X; }
 
 // f(real{}, integral_constant<C>{}) with the context's element type and the session's number of coefficients
 template <class F>
@@ -40,9 +38,9 @@ int jwas_hip_rrm_begin(jwas_hip_ctx* c, int32_t T, int32_t C, int64_t n, const d
 {
     NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
     NEED(c, !c->packed, JWAS_HIP_EUNSUP, "random regression models need dense genotypes (the reference refuses RRM on storage=:stream)");
-    NEED(c, rrm_genotypes(c) && c->n > 0 && c->p > 0, JWAS_HIP_ESTATE, "no genotype matrix loaded");
+    NEED(c, genotypes_ptr(c) && c->n > 0 && c->p > 0, JWAS_HIP_ESTATE, "no genotype matrix loaded");
     if (int rc = refuse_shards(c, "random regression models")) return rc;
-    NEED(c, !(IS_F64(c) ? c->f64->weighted : c->weighted), JWAS_HIP_EUNSUP, "random regression models do not run with residual weights");
+    NEED(c, !is_weighted(c), JWAS_HIP_EUNSUP, "random regression models do not run with residual weights");
     NEED(c, C >= jwr::kMinC && C <= jwr::kMaxC, JWAS_HIP_EINVAL, "the number of regression coefficients must be in [%d,%d] (got %d)", jwr::kMinC, jwr::kMaxC, C);
     NEED(c, T >= 1 && T <= jwr::kMaxT, JWAS_HIP_EINVAL, "the number of time points must be in [1,%d] (got %d)", jwr::kMaxT, T);
     NEED(c, n == c->n, JWAS_HIP_EINVAL, "n (%lld) differs from the number of genotyped individuals (%lld)", (long long)n, (long long)c->n);
@@ -83,12 +81,12 @@ int jwas_hip_rrm_begin(jwas_hip_ctx* c, int32_t T, int32_t C, int64_t n, const d
     with_real_c(c, C, [&](auto real, auto cc) {
         using real_t = decltype(real);
         constexpr int CC = decltype(cc)::value;
-        hipLaunchKernelGGL((jwr::k_rrm_m<real_t, CC>), dim3((unsigned)p), dim3(256), 0, c->stream, (const real_t*)rrm_genotypes(c), ld, (const double*)b.O, b.M);
+        hipLaunchKernelGGL((jwr::k_rrm_m<real_t, CC>), dim3((unsigned)p), dim3(256), 0, c->stream, (const real_t*)genotypes_ptr(c), ld, (const double*)b.O, b.M);
         // (the grid's y extent is 65 535 blocks at most: the blocks go in trips)
         for (int64_t k0 = 0; k0 < b.nblocks; k0 += 32768) {
             const int64_t nb = std::min<int64_t>(32768, b.nblocks - k0);
             hipLaunchKernelGGL((jwr::k_rrm_gram<real_t, CC>), dim3((unsigned)bs, (unsigned)nb), dim3(256), 0, c->stream,
-                               (const real_t*)rrm_genotypes(c) + k0 * bs * ld, ld, (const double*)b.O, p - k0 * bs, (int32_t)bs, b.gram + k0 * bs * bs * cells);
+                               (const real_t*)genotypes_ptr(c) + k0 * bs * ld, ld, (const double*)b.O, p - k0 * bs, (int32_t)bs, b.gram + k0 * bs * bs * cells);
         }
     });
     HIPCHK(c, hipGetLastError());
@@ -178,7 +176,7 @@ int jwas_hip_rrm_sweep(jwas_hip_ctx* c, const jwas_rrm_params* P, jwas_rrm_stats
     if (int rc = step_timer_begin(c)) return rc;
     HIPCHK(c, hipMemsetAsync(b.stat, 0, sizeof(double) * (size_t)(jwr::kStSize + c->nslices), c->stream));
     jwr::UpdateArgs U = {};
-    U.X = rrm_genotypes(c); U.mask = b.mask; U.phi = b.phi; U.W = b.W; U.partials = b.partials; U.ld = c->ld; U.T = b.T; U.bs = b.bs;
+    U.X = genotypes_ptr(c); U.mask = b.mask; U.phi = b.phi; U.W = b.W; U.partials = b.partials; U.ld = c->ld; U.T = b.T; U.bs = b.bs;
     jwr::SampleArgs A = {};
     A.partials = b.partials; A.M = b.M; A.phi = b.phi; A.alpha = b.ms.alpha; A.beta = b.ms.beta; A.delta = b.ms.delta; A.ev = (jwr::Events*)b.ev;
     A.stat = b.stat; A.ie = 1.0 / P->vare; A.p = c->p; A.nslices = c->nslices; A.bs = b.bs; A.T = b.T; A.iter = P->iteration;
@@ -186,7 +184,7 @@ int jwas_hip_rrm_sweep(jwas_hip_ctx* c, const jwas_rrm_params* P, jwas_rrm_stats
     for (int i = 0; i < C * C; ++i) A.Ginv[i] = Gi[i];
     for (int s = 0; s < NS; ++s) A.lpi[s] = P->log_pi[s];
     jwr::FinishArgs F = {};
-    F.X = rrm_genotypes(c); F.mask = b.mask; F.W = b.W; F.ev = (const jwr::Events*)b.ev; F.wss = b.stat + jwr::kStSize; F.ld = c->ld; F.T = b.T;
+    F.X = genotypes_ptr(c); F.mask = b.mask; F.W = b.W; F.ev = (const jwr::Events*)b.ev; F.wss = b.stat + jwr::kStSize; F.ld = c->ld; F.T = b.T;
     const dim3 slices((unsigned)c->nslices);
     with_real_c(c, C, [&](auto real, auto cc) {
         using real_t = decltype(real);
@@ -235,7 +233,7 @@ int jwas_hip_rrm_mul_alpha(jwas_hip_ctx* c, int32_t q, double* out)
     NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
     NEED(c, q >= 0 && q < b.C, JWAS_HIP_EINVAL, "coefficient %d outside [0,%d)", q, b.C);
     HIPCHK(c, hipSetDevice(c->device));
-    return marker_state_mul_alpha(c, b.ms, q, rrm_genotypes(c), c->ld, c->n, b.row, out);
+    return marker_state_mul_alpha(c, b.ms, q, genotypes_ptr(c), c->ld, c->n, b.row, out);
 }
 
 int jwas_hip_rrm_get_m(jwas_hip_ctx* c, int64_t nvalues, double* out)

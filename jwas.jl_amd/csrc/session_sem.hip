@@ -133,7 +133,7 @@ int jwas_hip_sem_accumulate(jwas_hip_ctx* c, const double* K, double nsamples)
             NEED(c, std::isfinite(K[i * t + j]), JWAS_HIP_EINVAL, "K[%d][%d] is not finite (%g)", i, j, K[i * t + j]);
             A.K[i * jws::kMaxT + j] = K[i * t + j];
         }
-    A.alpha = IS_F64(c) ? (const void*)c->f64->alpha : (const void*)c->alpha;
+    A.alpha = alpha_ptr(c);
     A.acc = c->sm.acc; A.nsamples = nsamples; A.p = c->p; A.nt = t;
     HIPCHK(c, hipSetDevice(c->device));
     const dim3 grid((unsigned)((c->p + 255) / 256));

@@ -77,11 +77,9 @@ static void* ss_target(jwas_hip_ctx* c, int target, int64_t* n, int64_t* ld)
 {
     if (target == 0) {
         *n = c->n; *ld = c->ld;
-        return c->packed ? nullptr : (IS_F64(c) ? (void*)c->f64->X : (void*)c->X);
+        return c->packed ? nullptr : const_cast<void*>(genotypes_ptr(c));
     }
-    if (IS_F64(c)) { *n = c->f64->n_out; *ld = c->f64->ld_out; return (void*)c->f64->Xout; }
-    *n = c->n_out; *ld = c->ld_out;
-    return (void*)c->Xout;
+    return const_cast<void*>(output_rows_ptr(c, n, ld));
 }
 
 extern "C" {

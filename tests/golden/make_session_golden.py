@@ -2,11 +2,12 @@
 of the commit the fixture pins -- the parent of the commit that moved the sessions out of csrc/jwas_hip.hip.  Run once on the GPU
 with that commit's library:
 
-    python tests/golden/make_session_golden.py --commit HASH [--lib path/to/libjwas_hip.so] [--cases block] [--out FILE]
+    python tests/golden/make_session_golden.py --commit HASH [--lib path/to/libjwas_hip.so] [--cases block|output] [--out FILE]
 
 HASH names the commit whose library is loaded; the fixture records it.  --cases block writes tests/golden/block_session_golden.json
 instead: the sessions with a block sweep of their own (BLOCK_CASES), pinned to the parent of the commit that gave them one copy of
-their shared code.
+their shared code.  --cases output writes tests/golden/output_side_golden.json: the output side of a context (OUTPUT_CASES), pinned to the
+parent of the commit that gave its Float32 and Float64 halves one body (csrc/output.hip).
 
 tests/test_gpu_session_golden.py replays the same calls on the current library and requires equal values and digests."""
 import argparse
@@ -20,7 +21,12 @@ import session_golden_cases as G  # noqa: E402
 from jwas_jl_amd import _lib  # noqa: E402
 
 
-FIXTURES = {"session": (G.CASES, "session_golden.json"), "block": (G.BLOCK_CASES, "block_session_golden.json")}
+def _both(cases):
+    return [(name, prec) for name in cases for prec in G.PRECISIONS]
+
+
+FIXTURES = {"session": (_both(G.CASES), "session_golden.json"), "block": (_both(G.BLOCK_CASES), "block_session_golden.json"),
+            "output": (G.output_keys(), "output_side_golden.json")}
 
 
 def rocm_version():
@@ -42,7 +48,7 @@ def main():
     args.out = args.out or os.path.join(HERE, default_out)
     if args.lib:
         _lib.LIB_PATH = os.path.abspath(args.lib)
-    blob = {"commit": args.commit, "rocm": rocm_version(), "cases": {f"{name}/{prec}": G.run_case(name, prec) for name in cases for prec in G.PRECISIONS}}
+    blob = {"commit": args.commit, "rocm": rocm_version(), "cases": {f"{name}/{prec}": G.run_case(name, prec) for name, prec in cases}}
     with open(args.out, "w") as fh:
         json.dump(blob, fh, separators=(",", ":"), sort_keys=True)
         fh.write("\n")

@@ -1,7 +1,9 @@
 """The replayed calls behind tests/golden/session_golden.json: one small run of every device session (liabilities, location
 parameters, missing traits, annotation priors, structural equation models), each in a Float32 and a Float64 context -- and, as
 BLOCK_CASES behind tests/golden/block_session_golden.json, of the sessions that sweep blocks of markers themselves (mega-trait models,
-several BayesR chains, random regression, GBLUP).
+several BayesR chains, random regression, GBLUP) -- and, as OUTPUT_CASES behind tests/golden/output_side_golden.json, of the output side
+of a context: state, residual and posterior transfer, X alpha on training and output rows, sparse samples, window sums, the GWAS session,
+marker covariances, in both precisions and on packed storage, with their guards.
 
 run_case(name, precision) returns what the fixture records for that run:
 
@@ -456,12 +458,303 @@ def _gblup(t, diagonal, first_trait):
     return run
 
 
+# ---- the output side (tests/golden/output_side_golden.json): state, residual and posterior transfer, X alpha, output rows, sparse
+# samples, window sums, the GWAS session, marker covariances ------------------------------------------------------------------------------
+# n = 300 training rows (two 256-row slices, 212 pad rows), 70 output rows (one slice), p = 1 100 (two trips of the 1 024-wide
+# compaction walk, a 76-marker tail).  Effect vectors: empty, 37 nonzeros (two batches of 16, one of 4, one single: every branch of the
+# batched list), 400 nonzeros (4 nnz > p: the Float32 dense branch).
+OUT_N, OUT_ROWS, OUT_P = 300, 70, 1100
+OUT_NNZ = (("empty", 0), ("sparse", 37), ("dense", 400))
+
+
+def _out_engine(precision, rec, seed, method=None, t=1, p=OUT_P, output_rows=True):
+    hip, rng = _genotypes(precision, OUT_N, p, rec, seed)
+    if output_rows:
+        Xout = np.asfortranarray(rng.integers(0, 3, (OUT_ROWS, p)).astype(hip.dtype))
+        rec.given(Xout)
+        hip.load_output_dense(Xout)
+    hip.setup_blocks(64, "f64")
+    if method:
+        hip.init_state(method, t)
+    return hip, rng
+
+
+def _effects(rng, p, nnz, dtype):
+    """(ascending idx, val, the dense vector): nnz nonzero effects among p markers."""
+    idx = np.sort(rng.choice(p, nnz, replace=False)).astype(np.int32)
+    val = (rng.standard_normal(nnz) + 2.0).astype(dtype)                 # (never zero)
+    a = np.zeros(p, dtype=dtype)
+    a[idx] = val
+    return idx, val, a
+
+
+def _raw(hip, rec, name, *args):
+    """One entry point through the bare C ABI: records (code, message)."""
+    import ctypes as C
+    rc = getattr(hip._L, name)(hip._h, *[a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray) else a for a in args])
+    rec.errors.append([int(rc), hip._L.jwas_hip_last_error(hip._h).decode() if rc else ""])
+    return rc
+
+
+def _out_context(method, t):
+    def run(precision, rec):
+        import ctypes as C
+        hip, rng = _out_engine(precision, rec, 1001, method, t)
+        try:
+            n, p = hip.n, hip.p
+            r0 = (rng.standard_normal((t, n)) * 1.3 + 0.2).astype(hip.dtype)
+            rec.given(r0)
+            rec.large("xpx", hip.xpx())
+            for k in range(t):
+                hip.set_residual(r0[k], k)
+                rec.large(f"residual_round_trip{k}", hip.get_residual(k))
+                for tag, nnz in OUT_NNZ:
+                    idx, val, a = _effects(rng, p, nnz, hip.dtype)
+                    b = rng.standard_normal(p).astype(hip.dtype)
+                    d = rng.integers(1, 5, p).astype(np.int32) if method == "BayesR" else (a != 0).astype(hip.dtype)
+                    rec.given(a, b, d)
+                    hip.set_state(k, alpha=a, beta=b, delta=d)
+                    _state(rec, f"{tag}{k}_", hip.get_state(k))
+                    rec.large(f"{tag}{k}_mul_alpha", hip.mul_alpha(k))
+                    rec.large(f"{tag}{k}_mul_alpha_output", hip.mul_alpha_output(k))
+                    si, sv = hip.alpha_sparse(k)
+                    assert np.array_equal(si, idx) and np.array_equal(sv, val), "alpha_sparse is not the list that was set"
+                    rec.large(f"{tag}{k}_sparse_idx", si)
+                    rec.large(f"{tag}{k}_sparse_val", sv)
+                    if tag == "sparse" and k == 0:                       # a capacity that is too small: the error, nnz_out still filled
+                        ci, cv, cn = np.zeros(10, dtype=np.int32), np.zeros(10, dtype=hip.dtype), C.c_int64(-1)
+                        _raw(hip, rec, "jwas_hip_get_alpha_sparse" + ("_f64" if precision == 64 else ""), k, 10, ci, cv, C.byref(cn))
+                        rec.small("sparse_nnz_out_when_too_small", [cn.value])
+                    hip.sub_xalpha(k)
+                    rec.large(f"{tag}{k}_residual_sub_xalpha", hip.get_residual(k))
+            for ns in (1, 2, 3):
+                for k in range(t):
+                    _, _, a = _effects(rng, p, 37 * ns, hip.dtype)
+                    d = rng.integers(1, 5, p).astype(np.int32) if method == "BayesR" else (a != 0).astype(hip.dtype)
+                    rec.given(a, d)
+                    hip.set_state(k, alpha=a, delta=d)
+                hip.accumulate(ns)
+            for k in range(t):
+                for nm, v in zip(("mean", "mean2", "freq"), hip.posterior(k)):
+                    rec.large(f"posterior{k}_{nm}", v)
+        finally:
+            hip.close()
+    return run
+
+
+# window sums: windows of 0, 1, 7, 8, 9 and 20 list entries (the empty window, the batch boundary of 8, a tail)
+def _out_windows(precision, rec):
+    hip, rng = _out_engine(precision, rec, 1002)
+    try:
+        counts = [0, 1, 7, 8, 9, 20]
+        wptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        idx = rng.choice(hip.p, int(wptr[-1]), replace=False).astype(np.int32)
+        v1, v2 = (rng.standard_normal(idx.size).astype(hip.dtype) for _ in range(2))
+        rec.given(wptr, idx, v1, v2)
+        for rows, out in (("training", False), ("output", True)):
+            rec.small(f"{rows}_sums", np.concatenate(hip.window_sums(wptr, idx, v1, use_output_rows=out)))
+            rec.small(f"{rows}_sums2", np.concatenate(hip.window_sums2(wptr, idx, v1, v2, use_output_rows=out)))
+    finally:
+        hip.close()
+
+
+def _gwas_windows(p, width):
+    cs = np.arange(0, p, width, dtype=np.int32)
+    ce = np.minimum(cs + width, p).astype(np.int32)
+    return np.concatenate([cs, [p // 2]]).astype(np.int32), np.concatenate([ce, [p // 2]]).astype(np.int32)      # (the last one empty)
+
+
+def _gwas_session(hip, rec, tag, cs, ce, samples, local_ebv, out_rows):
+    """One session over `samples`; every sample's sums must equal window_sums' over the same lists (entry 0 = all markers)."""
+    hip.gwas_begin(cs, ce, local_ebv=local_ebv, use_output_rows=out_rows)
+    rec.small(f"{tag}_geometry", [hip.gwas_geometry()[k] for k in ("nslices", "windows_per_chunk", "nchunks")])
+    for i, (idx, val) in enumerate(samples):
+        s, q = hip.gwas_sample(idx, val)
+        rec.small(f"{tag}_sample{i}", np.concatenate([s, q]))
+        lo, hi = np.searchsorted(idx, cs), np.searchsorted(idx, ce)
+        pieces = [np.arange(idx.size)] + [np.arange(a, b) for a, b in zip(lo, hi)]
+        wptr = np.concatenate([[0], np.cumsum([x.size for x in pieces])]).astype(np.int32)
+        sel = np.concatenate(pieces).astype(np.int64)
+        ws, wq = hip.window_sums(wptr, idx[sel], val[sel], use_output_rows=out_rows)
+        assert np.array_equal(ws, s) and np.array_equal(wq, q), f"{tag}: the session's sums of sample {i} differ from window_sums'"
+    if local_ebv:
+        ebv, ns = hip.gwas_local_ebv()
+        rec.large(f"{tag}_local_ebv", ebv)
+        rec.small(f"{tag}_nsamples", [ns])
+    hip.gwas_end()
+
+
+def _out_gwas(precision, rec):
+    hip, rng = _out_engine(precision, rec, 1003)
+    try:
+        cs, ce = _gwas_windows(hip.p, 100)
+        samples = [_effects(rng, hip.p, nnz, hip.dtype)[:2] for nnz in (37, 0, 400)]
+        rec.given(cs, ce, *[x for s in samples for x in s])
+        for out_rows in (False, True):
+            for local_ebv in (True, False):
+                _gwas_session(hip, rec, f"{'output' if out_rows else 'training'}_{'ebv' if local_ebv else 'plain'}", cs, ce, samples, local_ebv, out_rows)
+    finally:
+        hip.close()
+    # p = 4 500, a sample of 4 200 nonzeros: the session's list grows past its first 4 096 entries
+    hip, rng = _out_engine(precision, rec, 1004, p=4500, output_rows=False)
+    try:
+        cs, ce = _gwas_windows(hip.p, 500)
+        samples = [_effects(rng, hip.p, nnz, hip.dtype)[:2] for nnz in (37, 4200, 37)]
+        rec.given(cs, ce, *[x for s in samples for x in s])
+        _gwas_session(hip, rec, "grown", cs, ce, samples, True, False)
+    finally:
+        hip.close()
+
+
+# per-marker effect covariances: MTBayesB at t = 2, 3 (Float32: sample, get; Float64: set, get, sample, get); MEGABAYESB, Float32 only,
+# draws the diagonal
+def _out_markercov(method, t):
+    def run(precision, rec):
+        hip, rng = _genotypes(precision, 24, OUT_P, rec, 1005)
+        try:
+            hip.init_state(method, t)
+            for k in range(t):
+                b = rng.standard_normal(hip.p).astype(hip.dtype)
+                rec.given(b)
+                hip.set_state(k, beta=b)
+            scale = (np.diag([0.5, 0.375, 0.625]) + 0.0625)[:t, :t]
+            if precision == 64:
+                V = np.ascontiguousarray(rng.uniform(0.5, 2.0, (hip.p, t, t)))
+                rec.given(V)
+                _raw(hip, rec, "jwas_hip_set_marker_covariances_f64", V)
+                assert rec.errors.pop() == [0, ""]
+                rec.large("set_then_get", hip.marker_covariances())
+            for it in (1, 2):
+                hip.sample_marker_covariances(t + 3.0, scale, seed=59, iteration=it, marker_offset=100)
+                rec.large(f"drawn{it}", hip.marker_covariances())
+        finally:
+            hip.close()
+    return run
+
+
+# 2-bit packed storage (Float32 only): the PackedCols view under mul_alpha, window_sums and the GWAS session
+def _out_packed(precision, rec):
+    import jwas_jl_amd as J
+    from jwas_jl_amd import streaming as S
+    rng = np.random.default_rng(1006)
+    codes = rng.integers(0, 4, (OUT_N, OUT_P)).astype(np.uint8)          # (3 = missing)
+    means = rng.uniform(0.2, 1.8, OUT_P).astype(np.float32)
+    rec.given(codes, means)
+    hip = J.HipEngine(0)
+    try:
+        hip.load_packed2bit(S.pack_2bit(codes), OUT_N, means, centered=True)
+        hip.setup_blocks(64, "f64")
+        hip.init_state("BayesC")
+        samples = []
+        for tag, nnz in OUT_NNZ:
+            idx, val, a = _effects(rng, hip.p, nnz, hip.dtype)
+            rec.given(a)
+            samples.append((idx, val))
+            hip.set_state(0, alpha=a)
+            rec.large(f"{tag}_mul_alpha", hip.mul_alpha(0))
+        counts = [0, 1, 7, 8, 9, 20]
+        wptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        idx = rng.choice(hip.p, int(wptr[-1]), replace=False).astype(np.int32)
+        v1, v2 = (rng.standard_normal(idx.size).astype(hip.dtype) for _ in range(2))
+        rec.given(wptr, idx, v1, v2)
+        rec.small("sums", np.concatenate(hip.window_sums(wptr, idx, v1)))
+        rec.small("sums2", np.concatenate(hip.window_sums2(wptr, idx, v1, v2)))
+        cs, ce = _gwas_windows(hip.p, 100)
+        _gwas_session(hip, rec, "ebv", cs, ce, [samples[1], samples[0], samples[2]], True, False)
+    finally:
+        hip.close()
+
+
+# the guards: every entry point of the other precision, a trait out of range, calls before init_state, output rows that do not exist, a
+# GWAS sample after a reload.  Through the bare C ABI with buffers large enough for a call that a broken guard lets through.
+_OUT_TWINS = ("get_xpx", "set_state", "get_state", "set_residual", "get_residual", "mul_alpha", "get_alpha_sparse", "mul_alpha_output",
+              "window_sums", "window_sums2", "gwas_sample", "get_marker_covariances", "get_posterior")
+
+
+def _out_guards(precision, rec):
+    import ctypes as C
+    import jwas_jl_amd as J
+    hip, rng = _out_engine(precision, rec, 1007, "BayesC", 1, output_rows=False)
+    X2 = np.asfortranarray(rng.integers(0, 3, (OUT_N, OUT_P)).astype(hip.dtype))
+    Xout = np.asfortranarray(rng.integers(0, 3, (OUT_ROWS, OUT_P)).astype(hip.dtype))
+    rec.given(X2, Xout)
+    other, own = ("", "_f64") if precision == 64 else ("_f64", "")
+    B = [np.zeros(16 * OUT_P) for _ in range(5)]                         # (8 bytes x 16 p each: any output of either precision fits)
+    I = np.zeros(OUT_P, dtype=np.int32)
+    wptr, nnz = np.array([0, 0], dtype=np.int32), C.c_int64(0)
+
+    def surface(sfx, trait):                                             # the entry points that take a trait
+        f = lambda nm: f"jwas_hip_{nm}{sfx}"
+        _raw(hip, rec, f("set_state"), trait, B[0], B[1], B[2])
+        _raw(hip, rec, f("get_state"), trait, B[0], B[1], B[2])
+        _raw(hip, rec, f("set_residual"), trait, B[0])
+        _raw(hip, rec, f("get_residual"), trait, B[0])
+        _raw(hip, rec, f("mul_alpha"), trait, B[0])
+        _raw(hip, rec, f("get_alpha_sparse"), trait, OUT_P, I, B[0], C.byref(nnz))
+        _raw(hip, rec, f("mul_alpha_output"), trait, B[0])
+        _raw(hip, rec, f("get_posterior"), trait, B[0], B[1], B[2])
+    try:
+        surface(other, 0)                                                # the other precision's entry points
+        _raw(hip, rec, "jwas_hip_get_xpx" + other, B[0])
+        _raw(hip, rec, "jwas_hip_load_output_dense_f" + ("32" if precision == 64 else "64"), Xout, OUT_ROWS, OUT_P, OUT_ROWS)
+        _raw(hip, rec, "jwas_hip_window_sums" + other, 0, 1, wptr, I, B[0], B[1], B[2])
+        _raw(hip, rec, "jwas_hip_window_sums2" + other, 0, 1, wptr, I, B[0], B[1], B[2], B[3], B[4], B[0], B[1])
+        _raw(hip, rec, "jwas_hip_gwas_sample" + other, 0, I, B[0], B[1], B[2])
+        _raw(hip, rec, "jwas_hip_get_marker_covariances" + other, B[0])
+        if precision == 32:
+            _raw(hip, rec, "jwas_hip_set_marker_covariances_f64", B[0])
+        for trait in (1, -1):                                            # a trait out of range
+            surface(own, trait)
+            _raw(hip, rec, "jwas_hip_residual_sub_xalpha", trait)
+        # output rows that do not exist
+        _raw(hip, rec, "jwas_hip_mul_alpha_output" + own, 0, B[0])
+        _raw(hip, rec, "jwas_hip_window_sums" + own, 1, 1, wptr, I, B[0], B[1], B[2])
+        _raw(hip, rec, "jwas_hip_window_sums2" + own, 1, 1, wptr, I, B[0], B[1], B[2], B[3], B[4], B[0], B[1])
+        cs, ce = _gwas_windows(hip.p, 100)
+        rec.error(hip.gwas_begin, cs, ce, use_output_rows=True)
+        # arguments and sessions
+        rec.error(hip.accumulate, 0.5)
+        rec.error(hip.marker_covariances)
+        rec.error(hip.sample_marker_covariances, 4.0, np.eye(1), seed=1, iteration=1)
+        rec.error(hip.gwas_sample, I[:0], B[0][:0].astype(hip.dtype))    # no session
+        hip.gwas_begin(cs, ce)
+        rec.error(hip.gwas_local_ebv)                                    # begun without local_ebv
+        rec.error(hip.gwas_sample, np.array([5, 5], dtype=np.int32), np.ones(2, dtype=hip.dtype))      # not ascending
+        rec.error(hip.gwas_sample, np.array([OUT_P], dtype=np.int32), np.ones(1, dtype=hip.dtype))     # out of range
+        hip.load_dense(X2)                                               # a reload ends the session
+        rec.error(hip.gwas_sample, I[:0], B[0][:0].astype(hip.dtype))
+        hip.load_output_dense(Xout)
+        hip.gwas_begin(cs, ce, use_output_rows=True)
+        hip.load_output_dense(Xout)                                      # ... and so do new output rows
+        rec.error(hip.gwas_sample, I[:0], B[0][:0].astype(hip.dtype))
+        # before init_state (the reload above ended the chain)
+        surface(own, 0)
+        _raw(hip, rec, "jwas_hip_residual_sub_xalpha", 0)
+        rec.error(hip.accumulate, 1)
+    finally:
+        hip.close()
+
+
+OUTPUT_CASES = ("out_BayesC", "out_MTBayesC", "out_BayesR", "out_windows", "out_gwas", "out_markercov_t2", "out_markercov_t3",
+                "out_markercov_mega", "out_packed", "out_guards")
+OUTPUT_F32_ONLY = ("out_markercov_mega", "out_packed")
+
+
+def output_keys():
+    """(name, precision) of every record of tests/golden/output_side_golden.json."""
+    return [(name, prec) for name in OUTPUT_CASES for prec in PRECISIONS if prec == 32 or name not in OUTPUT_F32_ONLY]
+
+
 BLOCK_CASES = ("mega", "mega_chains", "rrm_c2", "rrm_c3", "rrm_c4", "gblup_t1", "gblup_t3_joint", "gblup_t3_diag")
 
 _RUN = {"liability": _liability, "locpar": _locpar, "mtmiss": _mtmiss, "sem": _sem,
         "annot_BayesC": _annot("BayesC"), "annot_BayesR": _annot("BayesR"), "annot_tree": _annot("tree"),
         "mega": _mega, "mega_chains": _mega_chains, "rrm_c2": _rrm(2), "rrm_c3": _rrm(3), "rrm_c4": _rrm(4),
-        "gblup_t1": _gblup(1, True, 0), "gblup_t3_joint": _gblup(3, False, 0), "gblup_t3_diag": _gblup(3, True, 1)}
+        "gblup_t1": _gblup(1, True, 0), "gblup_t3_joint": _gblup(3, False, 0), "gblup_t3_diag": _gblup(3, True, 1),
+        "out_BayesC": _out_context("BayesC", 1), "out_MTBayesC": _out_context("MTBayesC", 3), "out_BayesR": _out_context("BayesR", 1),
+        "out_windows": _out_windows, "out_gwas": _out_gwas, "out_markercov_t2": _out_markercov("MTBayesB", 2),
+        "out_markercov_t3": _out_markercov("MTBayesB", 3), "out_markercov_mega": _out_markercov("MegaBayesB", 3), "out_packed": _out_packed,
+        "out_guards": _out_guards}
 
 
 def run_case(name, precision):

@@ -8,7 +8,11 @@ of the guards.  The replay must be EQUAL: there is no tolerance, the reference i
 
 tests/golden/block_session_golden.json does the same for the sessions that sweep blocks of markers themselves (mega-trait models, several
 BayesR chains, random regression, GBLUP; G.BLOCK_CASES): written by the parent of the commit that gave them one copy of their shared
-device helpers (csrc/device_util.hpp), marker state (csrc/marker_state.hpp) and block walk (csrc/mega.hpp)."""
+device helpers (csrc/device_util.hpp), marker state (csrc/marker_state.hpp) and block walk (csrc/mega.hpp).
+
+tests/golden/output_side_golden.json does it for the output side of a context (G.OUTPUT_CASES: state, residual and posterior transfer,
+X alpha, output rows, sparse samples, window sums, the GWAS session, marker covariances, and their guards): written by the parent of the
+commit that gave the Float32 and Float64 halves of that surface one kernel and one host body each (csrc/output.hpp, csrc/output.hip)."""
 import json
 import os
 
@@ -62,3 +66,35 @@ def test_session_is_the_parent_commits_bit_for_bit(golden, block_golden, name, p
         assert got["digests"][key] == want["digests"][key], key
     assert got["errors"] == want["errors"]
     assert len(got["errors"]) == (2 if precision == 32 else 1) and all(code != 0 and msg for code, msg in got["errors"])
+
+
+@pytest.fixture(scope="module")
+def output_golden():
+    return _load("output_side_golden.json")
+
+
+# the guard records of every output case: the sparse list that does not fit the caller's arrays in each context case, and the guards
+# case itself -- 14 (Float64 context) or 15 (Float32: set_marker_covariances_f64 too) entry points of the other precision, 2 x 9 calls
+# with a trait out of range, 4 without output rows, 9 on arguments and sessions, 10 before init_state
+OUTPUT_GUARDS = {"out_BayesC": 1, "out_MTBayesC": 1, "out_BayesR": 1, "out_guards": {32: 15 + 18 + 4 + 9 + 10, 64: 14 + 18 + 4 + 9 + 10}}
+
+
+def test_output_fixture_covers_every_case(output_golden):
+    assert sorted(output_golden["cases"]) == sorted(f"{name}/{prec}" for name, prec in G.output_keys())
+    assert output_golden["rocm"] and len(output_golden["commit"]) == 40
+
+
+@pytest.mark.parametrize("name,precision", G.output_keys())
+def test_output_side_is_the_parent_commits_bit_for_bit(output_golden, name, precision):
+    want = output_golden["cases"][f"{name}/{precision}"]
+    got = G.run_case(name, precision)
+    assert got["inputs"] == want["inputs"], "the generated inputs differ from the fixture's (numpy's generator, not the library)"
+    assert sorted(got["values"]) == sorted(want["values"]) and sorted(got["digests"]) == sorted(want["digests"])
+    for key in sorted(want["values"]):
+        assert got["values"][key] == want["values"][key], (key, got["values"][key], want["values"][key])
+    for key in sorted(want["digests"]):
+        assert got["digests"][key] == want["digests"][key], key
+    assert got["errors"] == want["errors"]
+    nguards = OUTPUT_GUARDS.get(name, 0)
+    assert len(got["errors"]) == (nguards[precision] if isinstance(nguards, dict) else nguards)
+    assert all(code != 0 and msg for code, msg in got["errors"])
