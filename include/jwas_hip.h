@@ -819,6 +819,66 @@ int  jwas_hip_mega_psrf(jwas_hip_ctx* ctx, double nsamples, double* out_p);
 int64_t jwas_hip_mega_estimate_bytes(int64_t n, int64_t p, int32_t ntraits, int32_t block_size);
 int  jwas_hip_mega_end(jwas_hip_ctx* ctx);
 
+/* ---- unconstrained multi-trait BayesC with 5 to 8 traits: Gibbs sampler I (csrc/mtjoint.hpp) -------------------------------------------
+ * _MTBayesABC_samplerI! (markers/BayesianAlphabet/MTBayesABC.jl:57-127) with a full T x T marker-effect covariance G common to all
+ * markers, a full residual covariance R and Pi over the 2^T joint inclusion states, complete records; the sweep entry point above
+ * stops at JWAS_HIP_MAX_TRAITS.  The session keeps what a mega-trait session keeps (residuals, alpha, beta, delta, their running
+ * means, x'x and the within-block Grams, all double whatever the context's element type) and runs the same exact block form.  One
+ * marker, with w_k = x'r_k + x'x alpha_k for every k at the marker's entry, Rinv = inv(R), Ginv = inv(G), then k = 0 .. T-1 in order:
+ *   Ginv11 = Ginv[k][k],  C11 = Ginv11 + Rinv[k][k] x'x,
+ *   gHat0 = -(sum_{l != k} Ginv[k][l] beta_l) / Ginv11,
+ *   gHat1 = (sum_l w_l Rinv[l][k] - sum_{l != k} (Ginv[k][l] + x'x delta_l Rinv[k][l]) beta_l) / C11,
+ *   logDelta0 = -0.5 (log Ginv11 - gHat0^2 Ginv11) + log pi[d0],  logDelta1 = -0.5 (log C11 - gHat1^2 C11) + log pi[d1]
+ *     (d0 / d1: the marker's joint state, bit l = delta_l, with bit k cleared / set),  probDelta1 = 1 / (1 + exp(logDelta0 - logDelta1)),
+ *   u < probDelta1: delta_k = 1, beta_k = alpha_k = gHat1 + z / sqrt(C11);  else delta_k = 0, alpha_k = 0, beta_k = gHat0 + z / sqrt(Ginv11);
+ *   after the marker r_k += x (alpha_k,old - alpha_k,new).  A state with log pi = -Inf is never entered.
+ * Draws: philox4x32_10(marker, iteration, 0x05000000 | trait, slot), slot 14 the uniform, slot 15 the normal.  No floating-point
+ * atomics: the same seed gives the same bits.
+ * Limits: 5 <= T <= 8, block size <= 256 (0: 64), uniform blocks.
+ * Errors: JWAS_HIP_ESTATE without loaded genotypes or, for every other entry point, without an open session; JWAS_HIP_EUNSUP on 2-bit
+ * packed storage, with residual weights and on marker or row shards; JWAS_HIP_EINVAL for T or the block size out of range, a trait
+ * index outside [0, T), non-finite values, rinv or ginv not finite, not symmetric or not positive definite, npi != 2^T, a log pi
+ * that is NaN or above 0, or no state of positive probability.  A failed _begin opens nothing; _begin on an open session replaces
+ * it.  The session is freed by _end, jwas_hip_destroy or loading genotypes. */
+#define JWAS_HIP_MTJ_MIN_TRAITS 5
+#define JWAS_HIP_MTJ_MAX_TRAITS 8
+typedef struct jwas_mtj_params {
+    uint32_t iteration;                 /* MCMC iteration >= 1 (enters the RNG counter)                                          */
+    uint32_t reserved;
+    uint64_t seed;                      /* runMCMC(seed=...)                                                                     */
+    const double* rinv;                 /* [T][T] inv(vare), row-major                                                           */
+    const double* ginv;                 /* [T][T] inv(G)                                                                         */
+    const double* log_pi;               /* [npi] log Pr(joint state), state = sum_k delta_k 2^k; -Inf: probability 0             */
+    int64_t npi;                        /* 2^T                                                                                   */
+} jwas_mtj_params;
+typedef struct jwas_mtj_stats {         /* every pointer: doubles of the caller (any may be NULL)                                */
+    double* state_counts;               /* [2^T] markers per joint state (the Dirichlet update of Pi)                            */
+    double* beta_ss;                    /* [T][T] sum_j beta_j beta_j' (symmetric bit for bit)                                   */
+    double* alpha_ss;                   /* [T] alpha_k'alpha_k                                                                   */
+    double* resid_cp;                   /* [T][T] sum_i r_k[i] r_l[i] after the sweep (symmetric bit for bit)                    */
+    double* resid_sum;                  /* [T] sum r_k                                                                           */
+    double  n_changed;                  /* markers with an effect that moved                                                     */
+    double  step_ms;                    /* device time of the sweep (HIP events on the context's stream)                         */
+} jwas_mtj_stats;
+/* Open a session of ntraits traits on the loaded genotypes: x'x and the block Grams; residuals, alpha and beta 0, delta 1. */
+int  jwas_hip_mtj_begin(jwas_hip_ctx* ctx, int32_t ntraits, int32_t block_size);
+int  jwas_hip_mtj_set_residual(jwas_hip_ctx* ctx, int32_t trait, const double* r_n);
+int  jwas_hip_mtj_get_residual(jwas_hip_ctx* ctx, int32_t trait, double* out_n);
+/* alpha, beta, delta of one trait, p doubles each; any may be NULL. */
+int  jwas_hip_mtj_set_state(jwas_hip_ctx* ctx, int32_t trait, const double* alpha, const double* beta, const double* delta);
+int  jwas_hip_mtj_get_state(jwas_hip_ctx* ctx, int32_t trait, double* alpha, double* beta, double* delta);
+/* The Gram of one block, b x b doubles, and (out_xpx != NULL) the block's x'x, b doubles. */
+int  jwas_hip_mtj_gram(jwas_hip_ctx* ctx, int64_t block, int64_t nvalues, double* out_gram, double* out_xpx);
+/* One sweep over all markers (MTBayesABC.jl:75-126).  Synchronous. */
+int  jwas_hip_mtj_sweep(jwas_hip_ctx* ctx, const jwas_mtj_params* params, jwas_mtj_stats* stats);
+/* Running mean, mean of squares and model frequency of every effect (output.jl:556-577). */
+int  jwas_hip_mtj_accumulate(jwas_hip_ctx* ctx, double nsamples);
+/* ... of one trait: p values each, any may be NULL. */
+int  jwas_hip_mtj_posterior(jwas_hip_ctx* ctx, int32_t trait, double* mean, double* mean2, double* freq);
+/* out = X alpha_k over the context's rows, or over the output rows when use_output_rows != 0 (getEBV, output.jl:281-306). */
+int  jwas_hip_mtj_mul_alpha(jwas_hip_ctx* ctx, int32_t trait, int32_t use_output_rows, double* out);
+int  jwas_hip_mtj_end(jwas_hip_ctx* ctx);
+
 /* ---- GBLUP: the genomic relationship matrix and the sampler on pseudo-markers (csrc/gblup.hpp) -------------------------------------
  * The relationship matrix of the context's dense n x p matrix X (Float32 or Float64, as loaded): with divisor[j] = sqrt(2 p_j (1 - p_j))
  * in the matrix's element type (the host takes the square root; the device divides, so Z = X ./ divisor is the host's Z bit for bit),

@@ -669,6 +669,74 @@ hip_mega_estimate_bytes(n::Integer, p::Integer, ntraits::Integer, block_size::In
     ccall((:jwas_hip_mega_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int32, Int32), n, p, ntraits, block_size)
 hip_mega_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_mega_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
 
+"Unconstrained multi-trait BayesC with 5 to 8 traits on the device: Gibbs sampler I (_MTBayesABC_samplerI!,
+markers/BayesianAlphabet/MTBayesABC.jl:57-127; csrc/mtjoint.hpp) with a full G common to all markers, a full R and Pi over the 2^t
+joint states.  `hip_mtj_sweep!` takes Rinv = inv(vare), Ginv = inv(G) (t x t, symmetric) and log.(pi) over the states in the order
+state = 1 + sum_k δ_k 2^(k-1), and returns what the Dirichlet and the two inverse-Wishart draws read.  Traits are 1-based here.
+Limits: 5 <= t <= 8, blocks <= 256 markers, dense genotypes, complete records, no residual weights, no shards."
+struct HipMtjParams
+    iteration::UInt32
+    reserved::UInt32
+    seed::UInt64
+    rinv::Ptr{Float64}
+    ginv::Ptr{Float64}
+    log_pi::Ptr{Float64}
+    npi::Int64
+end
+struct HipMtjStats
+    state_counts::Ptr{Float64}
+    beta_ss::Ptr{Float64}
+    alpha_ss::Ptr{Float64}
+    resid_cp::Ptr{Float64}
+    resid_sum::Ptr{Float64}
+    n_changed::Float64
+    step_ms::Float64
+end
+hip_mtj_begin!(b::HipBackend, ntraits::Integer, block_size::Integer=256) =
+    hip_check(b.ctx, ccall((:jwas_hip_mtj_begin, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int32), b.ctx, ntraits, block_size))
+hip_mtj_set_residual!(b::HipBackend, trait::Integer, r::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_mtj_set_residual, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), b.ctx, trait - 1, r))
+function hip_mtj_residual(b::HipBackend, trait::Integer, n::Integer)
+    r = Vector{Float64}(undef, n)
+    hip_check(b.ctx, ccall((:jwas_hip_mtj_get_residual, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), b.ctx, trait - 1, r))
+    return r
+end
+hip_mtj_set_state!(b::HipBackend, trait::Integer, α::Vector{Float64}, β::Vector{Float64}, δ::Vector{Float64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_mtj_set_state, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.ctx, trait - 1, α, β, δ))
+function hip_mtj_state(b::HipBackend, trait::Integer, p::Integer)
+    α, β, δ = (Vector{Float64}(undef, p) for _ in 1:3)
+    hip_check(b.ctx, ccall((:jwas_hip_mtj_get_state, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.ctx, trait - 1, α, β, δ))
+    return α, β, δ
+end
+function hip_mtj_gram(b::HipBackend, k::Integer, nb::Integer)
+    G, xpx = Matrix{Float64}(undef, nb, nb), Vector{Float64}(undef, nb)
+    hip_check(b.ctx, ccall((:jwas_hip_mtj_gram, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}), b.ctx, k - 1, length(G), G, xpx))
+    return G, xpx
+end
+function hip_mtj_sweep!(b::HipBackend, iter::Integer, seed::Integer, Rinv::Matrix{Float64}, Ginv::Matrix{Float64}, log_pi::Vector{Float64})
+    t = size(Rinv, 1)
+    counts, bb, aa, cp, rs = zeros(Float64, 2^t), zeros(Float64, t, t), zeros(Float64, t), zeros(Float64, t, t), zeros(Float64, t)
+    S = Ref(HipMtjStats(pointer(counts), pointer(bb), pointer(aa), pointer(cp), pointer(rs), 0.0, 0.0))
+    GC.@preserve Rinv Ginv log_pi counts bb aa cp rs begin
+        P = HipMtjParams(UInt32(iter), UInt32(0), UInt64(seed), pointer(Rinv), pointer(Ginv), pointer(log_pi), Int64(length(log_pi)))
+        hip_check(b.ctx, ccall((:jwas_hip_mtj_sweep, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ref{HipMtjParams}, Ref{HipMtjStats}), b.ctx, Ref(P), S))
+    end
+    return (state_counts=counts, beta_ss=bb, alpha_ss=aa, resid_cp=cp, resid_sum=rs, n_changed=S[].n_changed, step_ms=S[].step_ms)
+end
+hip_mtj_accumulate!(b::HipBackend, nsamples::Real) =
+    hip_check(b.ctx, ccall((:jwas_hip_mtj_accumulate, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Float64), b.ctx, nsamples))
+function hip_mtj_posterior(b::HipBackend, trait::Integer, p::Integer)
+    m, m2, f = (Vector{Float64}(undef, p) for _ in 1:3)
+    hip_check(b.ctx, ccall((:jwas_hip_mtj_posterior, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.ctx, trait - 1, m, m2, f))
+    return m, m2, f
+end
+function hip_mtj_mul_alpha(b::HipBackend, trait::Integer, n_rows::Integer; output_rows::Bool=false)
+    out = Vector{Float64}(undef, n_rows)
+    hip_check(b.ctx, ccall((:jwas_hip_mtj_mul_alpha, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), b.ctx, trait - 1, output_rows, out))
+    return out
+end
+hip_mtj_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_mtj_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
+
 """
 GBLUP (markers/readgenotypes.jl:403-408, markers/BayesianAlphabet/GBLUP.jl; csrc/gblup.hpp).  `hip_grm` returns the relationship
 matrix (Z Z' + 1e-5 I) / p of the loaded dense matrix, Z = X ./ divisor with divisor = sqrt.(2p .* (1 .- p)) in the matrix's element

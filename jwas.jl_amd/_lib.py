@@ -21,6 +21,7 @@ ANNOT_BAYESC, ANNOT_BAYESR, ANNOT_TREE = 0, 1, 2
 LOCPAR_MAX_GROUPS = 8                   # random effects per model (JWAS_HIP_LOCPAR_MAX_GROUPS)
 RRM_MIN_COEFF, RRM_MAX_COEFF, RRM_MAX_TIMES, RRM_MAX_BLOCK = 2, 4, 64, 256      # csrc/rrm.hpp
 MEGA_MAX_TRAITS, MEGA_MAX_BLOCK, MEGA_TRAIT_TILE = 64, 256, 8                   # csrc/mega.hpp (JWAS_HIP_MEGA_MAX_TRAITS, _MAX_BLOCK, kTT)
+MTJ_MIN_TRAITS, MTJ_MAX_TRAITS = 5, 8                                           # csrc/mtjoint.hpp (JWAS_HIP_MTJ_MIN_TRAITS, _MAX_TRAITS)
 GRM_CHUNK = 64                          # markers per fp32 accumulation chunk of jwas_hip_grm (JWAS_HIP_GRM_CHUNK, csrc/gblup.hpp kGrmChunk)
 SS_CHUNK_GRANULE, SS_MAX_CHUNK = 64, 65536                                     # csrc/ssbr.hpp (kChunkGranule, kMaxChunk)
 MAX_THRESHOLDS = 16                     # per categorical trait, -Inf and +Inf included
@@ -124,6 +125,16 @@ class MegaParams(C.Structure):
 class MegaStats(C.Structure):
     _fields_ = [("sum_delta", C.c_void_p), ("beta_ss", C.c_void_p), ("alpha_ss", C.c_void_p), ("resid_ss", C.c_void_p), ("resid_sum", C.c_void_p),
                 ("n_changed", C.c_void_p), ("step_ms", C.c_double)]
+
+
+class MtjParams(C.Structure):
+    _fields_ = [("iteration", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("rinv", C.c_void_p), ("ginv", C.c_void_p),
+                ("log_pi", C.c_void_p), ("npi", C.c_int64)]
+
+
+class MtjStats(C.Structure):
+    _fields_ = [("state_counts", C.c_void_p), ("beta_ss", C.c_void_p), ("alpha_ss", C.c_void_p), ("resid_cp", C.c_void_p), ("resid_sum", C.c_void_p),
+                ("n_changed", C.c_double), ("step_ms", C.c_double)]
 
 
 class GblupParams(C.Structure):
@@ -322,6 +333,17 @@ PROTOTYPES = {
     "jwas_hip_mega_get_gram": (_INT, [_vp, _i64, _i64, _vp, _vp]),
     "jwas_hip_mega_estimate_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "jwas_hip_mega_end": (_INT, [_vp]),
+    "jwas_hip_mtj_begin": (_INT, [_vp, _i32, _i32]),
+    "jwas_hip_mtj_set_residual": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_mtj_get_residual": (_INT, [_vp, _i32, _vp]),
+    "jwas_hip_mtj_set_state": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_mtj_get_state": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_mtj_gram": (_INT, [_vp, _i64, _i64, _vp, _vp]),
+    "jwas_hip_mtj_sweep": (_INT, [_vp, _P(MtjParams), _P(MtjStats)]),
+    "jwas_hip_mtj_accumulate": (_INT, [_vp, C.c_double]),
+    "jwas_hip_mtj_posterior": (_INT, [_vp, _i32, _vp, _vp, _vp]),
+    "jwas_hip_mtj_mul_alpha": (_INT, [_vp, _i32, _i32, _vp]),
+    "jwas_hip_mtj_end": (_INT, [_vp]),
     "jwas_hip_grm": (_INT, [_vp, _vp, _vp]),
     "jwas_hip_grm_estimate_bytes": (_i64, [_i64, _i64, _i32]),
     "jwas_hip_gblup_begin": (_INT, [_vp, _vp]),

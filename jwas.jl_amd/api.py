@@ -611,7 +611,19 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     NotImplementedError naming the argument before anything is written: no constraint=True on either side (the joint 2^t-state
     samplers), BayesA/B/L/R, annotations, storage=:stream, fast_blocks, independent_blocks, heterogeneous_residuals,
     location_parameters="device", set_random, categorical / censored traits, causal_structure, RRM, several genotype categories,
-    starting values, shards, more than 64 traits.  Speed (scripts/mega_bench.py, 20 000 x 100 000, pi = 0.95, one MI355X): 25.3 ms per
+    starting values, shards, more than 64 traits.
+    More than 4 traits WITHOUT constraints (5 to 8, constraint=False -- the default -- in both get_genotypes and build_model): Gibbs
+    sampler I (_MTBayesABC_samplerI!, MTBayesABC.jl:57-127) with a full t x t marker-effect covariance, a full residual covariance and
+    Pi over the 2^t joint states, a driver of its own (mtjoint.py) on a device session of its own (csrc/mtjoint.hpp; it runs on the
+    block form of the mega-trait session).  BayesC (Pi: the scalar default = all mass on the all-ones state, a Dict over all 2^t joint
+    states, or a vector of 2^t probabilities; estimatePi true or false) and RR-BLUP; one genotype category, dense storage, Float32 or
+    double_precision=True, complete records, location parameters on the host, block_size <= 256 (default 256).  Outputs as an
+    unconstrained run of 2 to 4 traits writes them: full t x t covariance tables and sample files, pi_<genotypes> over the joint
+    states, marker effects with Model_Frequency, EBVs, genetic_variance and heritability.  Not on this path (NotImplementedError
+    naming the argument, before anything is written): records that miss some traits, BayesA/B/L/R, sampler II, annotations,
+    fast_blocks, independent_blocks, weights, set_random, location_parameters="device", categorical / censored traits,
+    causal_structure, RRM, single-step, starting values, storage=:stream, device_genotypes, several genotype categories, shards,
+    chains, more than 8 traits.  constraint=True on one side only is an error as before.  Speed (scripts/mega_bench.py, 20 000 x 100 000, pi = 0.95, one MI355X): 25.3 ms per
     sweep at 8 traits and 39.4 at 64, against 14.8 ms per FOUR traits on the existing MegaBayesC sweep -- 1.17 and 6.0 times as fast
     per trait; below about 7 traits the session is slower per trait than that sweep (0.65 of its speed at 4): NOTES.md, "Mega-trait
     models".
@@ -689,6 +701,7 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
         raise ValueError("independent_blocks=true requires fast_blocks != false.")             # :242-244
     from . import rrm as _rrm
     from . import megatrait as _mt
+    from . import mtjoint as _mj
     from . import gblup as _gb
     if _gb.routes(model):                     # GBLUP: mcmc.run_chain with the pseudo-marker step (gblup.py), validated before anything is written
         _gb.validate(model, df, single_step_analysis=single_step_analysis, fast_blocks=fast_blocks, independent_blocks=independent_blocks,
@@ -727,6 +740,12 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
     if first_chain != 0 or bayesr_gamma is not None:
         raise ValueError("first_chain and bayesr_gamma apply to runMCMC(...; chains=K) with K >= 2.")
     megatrait = _mt.routes(model)             # more than 4 traits: a driver of its own (megatrait.py), validated before anything is written
+    mtjoint = megatrait and _mj.routes(model)    # ... without constraints on either side: Gibbs sampler I with full covariances (mtjoint.py)
+    if mtjoint:
+        megatrait = False
+        _mj.validate(model, df, fast_blocks=fast_blocks, independent_blocks=independent_blocks, causal_structure=causal_structure, RRM=RRM,
+                     location_parameters=location_parameters, heterogeneous_residuals=heterogeneous_residuals, starting_value=starting_value,
+                     block_size=block_size, single_step_analysis=single_step_analysis, annotation_priors=annotation_priors, engine=_engine)
     if megatrait:
         _mt.validate(model, df, fast_blocks=fast_blocks, independent_blocks=independent_blocks, causal_structure=causal_structure, RRM=RRM,
                      location_parameters=location_parameters, heterogeneous_residuals=heterogeneous_residuals, starting_value=starting_value,
@@ -820,6 +839,12 @@ def runMCMC(model, df, *, heterogeneous_residuals=False, chain_length=100, start
                                  printout_frequency=printout_frequency, memory_guard=memory_guard, memory_guard_ratio=memory_guard_ratio,
                                  device=device, block_size=block_size, gram_mode=gram_mode, engines=_engine,
                                  printout_model_info=printout_model_info, output_samples_for_all_parameters=output_samples_for_all_parameters)
+    if mtjoint:
+        return _mj.run_mtjoint(model, df, chain_length=int(chain_length), burnin=int(burnin), output_samples_frequency=int(output_samples_frequency),
+                               seed=seed, double_precision=bool(double_precision), outputEBV=outputEBV,
+                               output_heritability=bool(output_heritability), output_folder=output_folder, printout_frequency=printout_frequency,
+                               device=device, block_size=block_size, engine=_engine, printout_model_info=printout_model_info,
+                               output_samples_for_all_parameters=output_samples_for_all_parameters)
     if megatrait:
         return _mt.run_megatrait(model, df, chain_length=int(chain_length), burnin=int(burnin),
                                  output_samples_frequency=int(output_samples_frequency), seed=seed, double_precision=bool(double_precision),

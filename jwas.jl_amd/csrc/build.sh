@@ -12,7 +12,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OBJ=${JWAS_OBJ_DIR:-_obj}
 OUT=${JWAS_OUT:-libjwas_hip.so}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $JWAS_EXTRA_FLAGS"
-UNITS="jwas_hip output session_liability session_locpar session_mtmiss session_annot session_sem session_rrm session_mega session_ssbr session_gblup step_st step_mtc1 step_mtb1 step_mt2 step_mega"
+UNITS="jwas_hip output session_liability session_locpar session_mtmiss session_annot session_sem session_rrm session_mega session_mtjoint session_ssbr session_gblup step_st step_mtc1 step_mtb1 step_mt2 step_mega"
 mkdir -p "$OBJ"
 echo "$FLAGS $*" > "$OBJ/.flags.new"
 if [ "${INCREMENTAL:-1}" = 0 ] || ! cmp -s "$OBJ/.flags.new" "$OBJ/.flags"; then rm -f "$OBJ"/*.o; fi
@@ -27,6 +27,7 @@ needs() {      # does unit $1 have to be compiled?
         jwas_hip)  deps="$deps $ctx $sweep f64_path.hpp output.hpp" ;;
         output)    deps="$deps $ctx kernels.hpp rng.hpp output.hpp" ;;
         session_rrm|session_mega) deps="$deps $ctx marker_state.hpp ${1#session_}.hpp" ;;
+        session_mtjoint) deps="$deps $ctx marker_state.hpp mtjoint.hpp mega.hpp" ;;      # (the block form it runs on is mega.hpp's)
         session_*) deps="$deps $ctx ${1#session_}.hpp" ;;
         *)         deps="$deps $sweep step_launch_impl.hpp" ;;
     esac

@@ -326,6 +326,25 @@ struct jwas_hip_ctx : Side<float> {
         double* stat_r = nullptr;                           // [nt][kStRSize] | [nt][nslices][2]
         double* psrf = nullptr;                             // [p]
     } mg;
+    // Unconstrained multi-trait BayesC with 5 to 8 traits (jwas_hip_mtj_begin .. _end; markers/BayesianAlphabet/MTBayesABC.jl:57-127;
+    // csrc/mtjoint.hpp): Gibbs sampler I on the block form of the mega-trait session, a sweep of its own with its own residuals and
+    // state, all double
+    struct Mtj {
+        bool active = false;
+        int nt = 0, bs = 0;                                 // traits, block size
+        int64_t nblocks = 0, row_cap = 0;
+        DevOwner mem;
+        double* R = nullptr;                                // [nt][ld] the residuals (pad rows 0)
+        double* xpx = nullptr;                              // [p]
+        double* gram = nullptr;                             // [nblocks][bs][bs]
+        MarkerState ms;                                     // [nt][p]
+        double* partials = nullptr;                         // [nslices][nt][bs]
+        double* par = nullptr;                              // [kParSize] Rinv | Ginv | log pi of the running sweep
+        double* stat = nullptr;                             // [kStSize] the sweep's statistics | [nslices][kFinSize] residual sums per slice
+        double* row = nullptr;                              // [row_cap] X alpha_k
+        void* ev = nullptr;                                 // jwg::Events: the change lists of the last sampled block
+        std::vector<double> par_host;                       // what par was filled from (kept until the sweep has finished)
+    } mj;
     // Single-step imputation (jwas_hip_ss_begin .. _end; single_step/SSBR.jl:83-159; csrc/ssbr.hpp): the factors of A^nn, A^ng and the
     // chunk buffers of a sparse solve with many right-hand sides.  It is bound to no matrix: the targets are checked at every chunk.
     struct Ssbr {
@@ -441,6 +460,7 @@ JW_LOCAL void annot_free(jwas_hip_ctx* c);
 JW_LOCAL void sem_free(jwas_hip_ctx* c);
 JW_LOCAL void rrm_free(jwas_hip_ctx* c);
 JW_LOCAL void mega_free(jwas_hip_ctx* c);
+JW_LOCAL void mtj_free(jwas_hip_ctx* c);
 JW_LOCAL void ss_free(jwas_hip_ctx* c);
 JW_LOCAL void gblup_free(jwas_hip_ctx* c);
 JW_LOCAL void gwas_free(jwas_hip_ctx* c);                                  // (output.hip: the GWAS session)

@@ -111,6 +111,7 @@ static void free_storage(jwas_hip_ctx* c)
     sem_free(c);                        // (the phenotypes belong to the records, the accumulators to the markers of this matrix)
     rrm_free(c);                        // (its Grams, masks and state are those of this matrix)
     mega_free(c);                       // (likewise)
+    mtj_free(c);                        // (likewise)
     gblup_free(c);                      // (its matrix is the eigenvector matrix that goes)
     annot_free(c);                      // (the prior table below belongs to the markers of this matrix)
     mtmiss_free(c);                     // (the codes describe the records of this matrix)
@@ -2105,6 +2106,7 @@ int jwas_hip_load_dense_f64(jwas_hip_ctx* c, const double* Xh, int64_t n, int64_
     mtmiss_free(c);
     rrm_free(c);
     mega_free(c);
+    mtj_free(c);
     gblup_free(c);
     F->drop();                          // (genotypes, residual, weights, x'x, output rows and the lists sized by the old p, the chain's state)
     for (void* q : {(void*)F->gram, (void*)F->partials, (void*)F->ev, (void*)F->dparams, (void*)F->ev_all}) (void)hipFree(q);

@@ -173,6 +173,9 @@ __global__ __launch_bounds__(256) void k_mega_update_partial(const UpdateArgs A)
     }
 }
 
+// What follows is the mega-trait session's own.  A unit that shares only the block form above (mtjoint.hpp) defines
+// JWG_BLOCK_FORM_ONLY: a non-template __global__ in two units would be a duplicate host symbol at link time.
+#ifndef JWG_BLOCK_FORM_ONLY
 struct FinishArgs {
     const void* X;
     double* R;
@@ -463,5 +466,6 @@ __global__ __launch_bounds__(256) void k_mega_psrf(const double* __restrict__ me
         out[j] = W == 0.0 ? __builtin_nan("") : sqrt(V / W);
     }
 }
+#endif  // JWG_BLOCK_FORM_ONLY
 
 }  // namespace jwg

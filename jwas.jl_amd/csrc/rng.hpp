@@ -39,6 +39,12 @@
 //           as slot 1): slots 13, 29, 45, 61.  The word 0x03000000 is no other stream's repetition word (the mega-trait sweep owns
 //           0x01000000 | id with id < 2^24, which stops at 0x01FFFFFF; the random-regression sweep owns exactly 0x02000000), and no
 //           other stream uses slot 13 + 16 q.
+//   slots 14, 15: the joint multi-trait sweep of 5 to 8 traits (mtjoint.hpp).  (MARKER, iteration, 0x05000000 | trait, 14) the decision
+//           uniform of the trait's step of sampler I (as slot 0) and (..., 15) its normal (Box-Muller as slot 1), trait < 8.  The words
+//           0x05000000 .. 0x05000007 are no other stream's repetition word (small counts below 2^24; 0x01000000 | id stops at 0x01FFFFFF;
+//           0x02000000 and 0x03000000 exactly; 0x04000000 | trait with trait < 4 stops at 0x04000003; 0x08000000 | step and the higher
+//           tags have a higher bit set), and no other stream uses slots 14 and 15 (the others' are 0 .. 4 + 16 trait <= 52, 5 .. 8,
+//           9 + 16 q, 10 .. 12, 13 + 16 q, and 64 upwards for the Wishart draws).  Tag words 0x06000000 and 0x07000000 are free.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

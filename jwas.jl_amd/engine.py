@@ -101,6 +101,7 @@ class HipEngine:
         self._explicit_starts = None    # explicit block partition resident (setup_blocks_explicit)
         self._rrm = None                # (T, c, block size) of an open random-regression session
         self._mega = None               # (traits, block size) of an open mega-trait session
+        self._mtj = None                # ... of an open joint multi-trait session (mtj_begin)
         self._ss = None                 # (non-genotyped, genotyped, markers per chunk) of an open single-step imputation session
 
     # -- plumbing --------------------------------------------------------------------------------
@@ -1150,6 +1151,102 @@ class HipEngine:
     def mega_end(self):
         self._chk(self._L.jwas_hip_mega_end(self._h))
         self._mega = None
+
+    # -- unconstrained multi-trait BayesC with 5 to 8 traits (jwas_hip_mtj_*; MTBayesABC.jl:57-127, csrc/mtjoint.hpp) ------------
+    def mtj_begin(self, ntraits, block_size=64):
+        """Open a session of Gibbs sampler I with a full G, a full R and Pi over the 2^t joint states on the loaded genotypes: x'x
+        and the block Grams; the residuals, alpha and beta start at 0, delta at 1."""
+        self._chk(self._L.jwas_hip_mtj_begin(self._h, int(ntraits), int(block_size)))
+        self._mtj = (int(ntraits), int(block_size) if block_size else 64)
+
+    def mtj_set_residual(self, R):
+        """R: T x n doubles."""
+        T, _ = self._mtj
+        Rv = np.ascontiguousarray(R, dtype=np.float64)
+        if Rv.shape != (T, self.n):
+            raise ValueError(f"the residual must be {T} x {self.n}")
+        for k in range(T):
+            self._chk(self._L.jwas_hip_mtj_set_residual(self._h, k, _ptr(Rv[k])))
+
+    def mtj_get_residual(self):
+        T, _ = self._mtj
+        out = np.empty((T, self.n), dtype=np.float64)
+        for k in range(T):
+            self._chk(self._L.jwas_hip_mtj_get_residual(self._h, k, _ptr(out[k])))
+        return out
+
+    def mtj_set_state(self, alpha=None, beta=None, delta=None):
+        """alpha, beta, delta: T x p doubles each, any may be None.  The state only: the residuals are not touched."""
+        T, _ = self._mtj
+        arrs = []
+        for a in (alpha, beta, delta):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (T, self.p):
+                    raise ValueError(f"state arrays must be {T} x {self.p}")
+            arrs.append(a)
+        for k in range(T):
+            self._chk(self._L.jwas_hip_mtj_set_state(self._h, k, *[_ptr(a[k]) if a is not None else None for a in arrs]))
+
+    def mtj_get_state(self):
+        T, _ = self._mtj
+        out = [np.empty((T, self.p), dtype=np.float64) for _ in range(3)]
+        for k in range(T):
+            self._chk(self._L.jwas_hip_mtj_get_state(self._h, k, _ptr(out[0][k]), _ptr(out[1][k]), _ptr(out[2][k])))
+        return tuple(out)
+
+    def mtj_gram(self, block):
+        """(G, x'x) of one block: b x b and b doubles."""
+        T, bs = self._mtj
+        b = max(min(bs, self.p - int(block) * bs), 0)
+        G, xpx = np.empty((b, b), dtype=np.float64), np.empty(b, dtype=np.float64)
+        self._chk(self._L.jwas_hip_mtj_gram(self._h, int(block), G.size, _ptr(G), _ptr(xpx)))
+        return G, xpx
+
+    def mtj_sweep(self, *, iteration, seed, rinv, ginv, log_pi):
+        """One sweep of sampler I over all markers.  rinv = inv(vare), ginv = inv(G): T x T; log_pi: the 2^T log probabilities of the
+        joint states (state = sum_k delta_k 2^k; -inf: never entered).  Returns {"state_counts" (2^T), "beta_ss" (T x T), "alpha_ss"
+        (T), "resid_cp" (T x T), "resid_sum" (T), "n_changed", "step_ms"}."""
+        T, _ = self._mtj
+        P = _lib.MtjParams()
+        P.iteration, P.seed = int(iteration), int(seed)
+        keep = []
+        for name, v in (("rinv", rinv), ("ginv", ginv)):
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if a.shape != (T, T):
+                raise ValueError(f"{name} must be {T} x {T}")
+            keep.append(a)
+            setattr(P, name, a.ctypes.data)
+        lp = np.ascontiguousarray(log_pi, dtype=np.float64).reshape(-1)
+        keep.append(lp)
+        P.log_pi, P.npi = lp.ctypes.data, lp.size
+        S = _lib.MtjStats()
+        out = {"state_counts": np.zeros(1 << T), "beta_ss": np.zeros((T, T)), "alpha_ss": np.zeros(T), "resid_cp": np.zeros((T, T)),
+               "resid_sum": np.zeros(T)}
+        for k, a in out.items():
+            setattr(S, k, a.ctypes.data)
+        self._chk(self._L.jwas_hip_mtj_sweep(self._h, C.byref(P), C.byref(S)))
+        out["n_changed"], out["step_ms"] = S.n_changed, S.step_ms
+        return out
+
+    def mtj_accumulate(self, nsamples):
+        self._chk(self._L.jwas_hip_mtj_accumulate(self._h, float(nsamples)))
+
+    def mtj_posterior(self, trait):
+        """(mean, mean of squares, model frequency) of one trait's effects, p values each."""
+        out = [np.empty(self.p, dtype=np.float64) for _ in range(3)]
+        self._chk(self._L.jwas_hip_mtj_posterior(self._h, int(trait), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
+        return tuple(out)
+
+    def mtj_mul_alpha(self, trait, output_rows=False):
+        """X alpha_k over the training rows, or over the rows of load_output_dense."""
+        out = np.empty(getattr(self, "n_out", 0) if output_rows else self.n, dtype=np.float64)
+        self._chk(self._L.jwas_hip_mtj_mul_alpha(self._h, int(trait), 1 if output_rows else 0, _ptr(out)))
+        return out
+
+    def mtj_end(self):
+        self._chk(self._L.jwas_hip_mtj_end(self._h))
+        self._mtj = None
 
     # -- single-step analysis: the imputation solve (SSBR.jl:83-159; csrc/ssbr.hpp) -----------------
     @staticmethod
