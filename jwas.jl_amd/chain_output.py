@@ -1,4 +1,5 @@
-"""The output layer of the chain drivers (mcmc.run_chain, multigeno.run_multigeno, megatrait.run_megatrait, rrm.run_rrm): the sample
+"""The output layer of the chain drivers (mcmc.run_chain, multigeno.run_multigeno, megatrait.run_megatrait, mtjoint.run_mtjoint,
+chains.run_chains, rrm.run_rrm): the sample
 files of a run, the running means, and the result tables of output.jl:108-212 -- the one place where their formats are written down.
 A driver keeps its sampler order and hands over values; where the drivers differ in a format, the difference is an argument here
 and a commented choice at the call site."""
@@ -219,3 +220,91 @@ def write_tables(out, folder):
 def print_posterior_means(it, residual_variance):
     print(f"\nPosterior means at iteration: {it}")
     print(f"Residual variance: {np.round(residual_variance, 6)}")
+
+
+def timing(wall, t_sweep, chain_length, bs, n, p, **more):
+    """runMCMC's "_timing" of a driver of a block session."""
+    return {"wall_s": wall, "device_sweep_ms_total": t_sweep, "iterations": chain_length, "block_size": bs, "n": n, "p": p, **more}
+
+
+class MultiTraitOutputs:
+    """The outputs of a run with more than 4 traits on one genotype category (run_megatrait, run_mtjoint), as an unconstrained run of
+    2 to 4 traits writes them (output.jl:320-437): the running means, the sample files, the tables.  The two variances are handed over
+    as t x t matrices; pi=None: it is not estimated; out_ids=None: no EBVs.  diagonal_only (constraint=true): the genetic covariance
+    of a sample keeps its diagonal, and the progress lines show the diagonal of the residual variance."""
+
+    def __init__(self, model, folder, labels, off, sol, vare, G, pi, out_ids, *, double_precision, heritability, marker_samples, diagonal_only):
+        Mi = model.M[0]
+        self.name, self.marker_ids, self.traits, self.folder = Mi.name, Mi.markerID, list(model.lhsVec), folder
+        self.labels, self.off, self.out_ids, self.diagonal_only = labels, off, out_ids, diagonal_only
+        self.run_sol, self.run_vare, self.run_varg = Running(sol), Running(vare), Running(G)
+        self.run_pi = Running(pi) if pi is not None else None
+        self.ebv_run = [Running(np.zeros(len(out_ids))) for _ in self.traits] if out_ids is not None else None
+        self.rnames = [f"{a}_{b}" for a in self.traits for b in self.traits]
+        self.term_cols = term_sample_columns(model, labels, off)
+        self.marker_samples, self.heritability = marker_samples, heritability
+        self.ftype, self.fmt = (np.float64, "%.17g") if double_precision else (np.float32, "%.9g")      # the marker rows follow the precision of the run
+        self.genvar = None
+        self.files = SampleFiles(folder)
+
+    def open(self):
+        """Every sample file of the run: inside `with outputs.files:`."""
+        files, name = self.files, self.name
+        files.open("residual_variance", self.rnames)
+        files.open(f"marker_effects_variances_{name}", self.rnames)
+        if self.run_pi is not None:
+            files.open(f"pi_{name}", [f"pi{i + 1}" for i in range(self.run_pi.mean.size)])
+        if self.out_ids is not None and self.heritability:               # output.jl:358-362,426-432
+            self.genvar = GeneticVarianceSamples(files, self.rnames, self.traits)
+        for key, (_, header) in self.term_cols.items():
+            files.open(key, header)
+        if self.marker_samples:
+            for tr in self.traits:
+                files.open(f"marker_effects_{name}_{tr}", self.marker_ids)
+        self.bin_writers = [files.marker_writer(f"marker_effects_{name}_{tr}", self.marker_ids) for tr in self.traits]
+
+    def save(self, ks, sol, vare, G, pi, alpha, ebvs):
+        """Saved sample number ks: alpha [t x p] the marker effects, ebvs (None without EBVs) the t vectors X_out alpha_k."""
+        files, name = self.files, self.name
+        self.run_sol.add(sol, ks)
+        self.run_vare.add(vare, ks)
+        self.run_varg.add(G, ks)
+        if self.run_pi is not None:
+            self.run_pi.add(pi, ks)
+            files.row(f"pi_{name}", pi)
+        for key, (cols, _) in self.term_cols.items():
+            files.row(key, sol[cols])
+        files.row("residual_variance", vare.ravel())
+        files.row(f"marker_effects_variances_{name}", G.ravel())
+        for k, tr in enumerate(self.traits):
+            a = alpha[k].astype(self.ftype)
+            si = np.flatnonzero(a).astype(np.int32)
+            self.bin_writers[k].append(si, a[si])
+            if self.marker_samples:
+                files.effects_row(f"marker_effects_{name}_{tr}", a, self.fmt)
+        if ebvs is not None:                                             # getEBV, output.jl:281-306
+            for k, ebv in enumerate(ebvs):
+                self.ebv_run[k].add(ebv, ks)
+            if self.genvar is not None:                                  # output.jl:498-512
+                self.genvar.add(ebvs, np.diag(vare), diagonal_only=self.diagonal_only)
+
+    def print_means(self, it):
+        print_posterior_means(it, np.diag(self.run_vare.mean) if self.diagonal_only else self.run_vare.mean)
+
+    def tables(self, posteriors, pi_names):
+        """The result tables (output.jl:108-212), written to the folder.  posteriors: a callable that returns (mean, mean of squares,
+        model frequency) of trait k as the session holds them (doubles: the SD is formed from them as they are)."""
+        name = self.name
+        out = {"location parameters": location_table(self.labels, self.off, self.run_sol.mean, self.run_sol.sd()),
+               "residual variance": covariance_table(self.rnames, self.run_vare)}
+        out[f"marker effects {name}"] = marker_effects_table([(tr, self.marker_ids) + tuple(posteriors(k)) for k, tr in enumerate(self.traits)],
+                                                             sd_in_double=False)
+        out[f"marker effects variance {name}"] = covariance_table(self.rnames, self.run_varg)
+        if self.run_pi is not None:
+            out[f"pi_{name}"] = pi_table(self.run_pi, pi_names)
+        if self.out_ids is not None:
+            out.update(ebv_tables(self.traits, self.out_ids, self.ebv_run))
+        if self.genvar is not None:
+            out.update(self.genvar.tables())
+        write_tables(out, self.folder)
+        return out

@@ -36,9 +36,10 @@ import numpy as np
 
 from ._lib import MEGA_MAX_BLOCK, MEGA_MAX_TRAITS
 from .chain_output import (GeneticVarianceSamples, Running, SampleFiles, covariance_table, ebv_tables, location_table,
-                           marker_effects_table, pi_labels, pi_table, print_posterior_means, resolve_output_ids, term_sample_columns,
-                           write_id_files, write_tables)
+                           marker_effects_table, pi_labels, pi_table, print_posterior_means, term_sample_columns, timing, write_id_files,
+                           write_tables)
 from .mcmc import BAYESR_GAMMA, _design, _gibbs, genetic2marker
+from .session_driver import align_records, not_false, open_engine, phenotype_records
 
 CHAIN_METHODS = ("mega_begin", "mega_set_residual", "mega_get_residual", "mega_get_state", "mega_sweep", "mega_sweep_r", "mega_accumulate",
                  "mega_accumulate_r", "mega_psrf", "mega_posterior", "mega_mul_alpha", "mega_end")
@@ -52,10 +53,6 @@ def check_chains(chains):
     if isinstance(chains, bool) or not isinstance(chains, (int, np.integer)) or not 1 <= int(chains) <= MAX_CHAINS:
         raise ValueError(f"chains must be an integer in [1, {MAX_CHAINS}] (got {chains!r}).")
     return int(chains)
-
-
-def _not_false(x):
-    return not (x is False or x is None)
 
 
 def validate(model, df, *, chains, first_chain=0, fast_blocks=False, independent_blocks=False, causal_structure=False, RRM=False,
@@ -94,13 +91,13 @@ def validate(model, df, *, chains, first_chain=0, fast_blocks=False, independent
         raise NotImplementedError(f"chains={chains} with set_random effects is not supported")
     if any(tt != "continuous" for tt in model.traits_type):
         raise NotImplementedError(f"chains={chains} with categorical_trait / censored_trait is not supported")
-    if _not_false(causal_structure):
+    if not_false(causal_structure):
         raise NotImplementedError(f"chains={chains} with causal_structure is not supported")
-    if _not_false(RRM):
+    if not_false(RRM):
         raise NotImplementedError(f"chains={chains} with RRM is not supported")
-    if _not_false(single_step_analysis):
+    if not_false(single_step_analysis):
         raise NotImplementedError(f"chains={chains} with single_step_analysis is not supported")
-    if Mi.alpha is not False or _not_false(starting_value):
+    if Mi.alpha is not False or not_false(starting_value):
         raise NotImplementedError(f"chains={chains} with starting_value (marker or location-parameter starting values) is not supported: "
                                   "every chain starts from the reference's starting state")
     if getattr(Mi.G, "estimate_scale", False):
@@ -183,25 +180,9 @@ def run_chains(model, df, *, chains, first_chain=0, chain_length, burnin, output
     gamma = np.asarray(BAYESR_GAMMA if bayesr_gamma is None else bayesr_gamma, dtype=np.float64)
 
     # ---- align phenotypes and genotypes (input_data_validation.jl:198-294, tools4genotypes.jl:288-323)
-    idcol = df.columns[0]
-    ph = df.copy()
-    ph[idcol] = ph[idcol].astype(str)
-    if trait not in ph.columns:
-        raise ValueError(f"Phenotypes for {trait} are not found in the data.")
-    geno_index = {g: i for i, g in enumerate(Mi.obsID)}
-    keep = np.isfinite(ph[trait].to_numpy(dtype=np.float64)) & ph[idcol].isin(geno_index).to_numpy()
-    ph = ph.loc[keep].reset_index(drop=True)
-    if len(ph) == 0:
-        raise ValueError("no individual has both phenotypes and genotypes")
-    rows = np.array([geno_index[i] for i in ph[idcol]], dtype=np.int64)
-    X = np.asfortranarray(np.asarray(Mi.genotypes)[rows, :].astype(ftype))
+    idcol, ph, Yall = phenotype_records(df, [trait])
+    ph, rows, X, out_ids, out_rows, out_same = align_records(model, Mi, idcol, ph, Yall, ftype, outputEBV)
     n, p = X.shape
-    out_ids, out_rows, out_same = None, None, True
-    if outputEBV:
-        out_ids, out_same = resolve_output_ids(model, Mi.obsID, ph[idcol])
-        if not out_same:
-            out_rows = np.array([geno_index[i] for i in out_ids], dtype=np.int64)
-    Mi.output_rows = out_rows if (outputEBV and not out_same) else rows
     y = ph[trait].to_numpy(dtype=ftype)
     phenovar = float(np.var(y.astype(np.float64), ddof=1))
     y = y.astype(np.float64)
@@ -251,13 +232,7 @@ def run_chains(model, df, *, chains, first_chain=0, chain_length, burnin, output
     lhs = Xf0.T @ Xf0
 
     # ---- the device session
-    own_engine = engine is None
-    if own_engine:
-        from .engine import HipEngine
-        engine = HipEngine(device, precision=64 if double_precision else 32)
-    engine.load_dense(X)
-    if outputEBV and not out_same:
-        engine.load_output_dense(np.asfortranarray(np.asarray(Mi.genotypes)[out_rows, :].astype(ftype)))
+    engine, own_engine = open_engine(engine, device, double_precision, X, Mi, out_rows)
     engine.mega_begin(K, bs, first)
     engine.mega_set_residual(np.tile(y, (K, 1)))                         # ycorr = y in every chain: every starting value is zero
 
@@ -402,8 +377,7 @@ def run_chains(model, df, *, chains, first_chain=0, chain_length, burnin, output
     psrf.to_csv(os.path.join(output_folder, "PSRF.txt"), index=False)
     summary.to_csv(os.path.join(output_folder, "PSRF_summary.txt"), index=False)
     out["chains"], out["PSRF"], out["PSRF_summary"] = results, psrf, summary
-    out["_timing"] = {"wall_s": wall, "device_sweep_ms_total": t_sweep, "iterations": chain_length, "block_size": bs, "n": n, "p": p, "chains": K,
-                      "first_chain": first}
+    out["_timing"] = timing(wall, t_sweep, chain_length, bs, n, p, chains=K, first_chain=first)
     engine.mega_end()
     if own_engine:
         engine.close()

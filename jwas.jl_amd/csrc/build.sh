@@ -26,8 +26,9 @@ needs() {      # does unit $1 have to be compiled?
     case $1 in
         jwas_hip)  deps="$deps $ctx $sweep f64_path.hpp output.hpp" ;;
         output)    deps="$deps $ctx kernels.hpp rng.hpp output.hpp" ;;
-        session_rrm|session_mega) deps="$deps $ctx marker_state.hpp ${1#session_}.hpp" ;;
-        session_mtjoint) deps="$deps $ctx marker_state.hpp mtjoint.hpp mega.hpp" ;;      # (the block form it runs on is mega.hpp's)
+        session_rrm) deps="$deps $ctx marker_state.hpp rrm.hpp" ;;
+        session_mega) deps="$deps $ctx marker_state.hpp block_session.hpp mega.hpp" ;;
+        session_mtjoint) deps="$deps $ctx marker_state.hpp block_session.hpp mtjoint.hpp mega.hpp" ;;      # (the block form it runs on is mega.hpp's)
         session_*) deps="$deps $ctx ${1#session_}.hpp" ;;
         *)         deps="$deps $sweep step_launch_impl.hpp" ;;
     esac

@@ -49,6 +49,25 @@ struct MarkerState {
     double *mean_a = nullptr, *mean_a2 = nullptr, *mean_d = nullptr;
 };
 
+// What the sessions that sweep blocks of markers with mega.hpp's update kernel hold alike (Mega, Mtj; block_session.hpp has what is
+// done with it): a sweep of their own with their own residuals and state, all double, on the context's genotypes.  Plain data.
+struct BlockSession {
+    bool active = false;
+    int nt = 0, bs = 0;                                     // traits, block size
+    int64_t nblocks = 0, row_cap = 0;
+    DevOwner mem;
+    double* R = nullptr;                                    // [nt][ld] the residuals (pad rows 0)
+    double* xpx = nullptr;                                  // [p]
+    double* gram = nullptr;                                 // [nblocks][bs][bs]
+    MarkerState ms;                                         // [nt][p]
+    double* partials = nullptr;                             // [nslices][nt][bs]
+    double* par = nullptr;                                  // the parameters of the running sweep
+    double* stat = nullptr;                                 // the sweep's statistics | the residual sums per slice
+    double* row = nullptr;                                  // [row_cap] X alpha_k
+    void* ev = nullptr;                                     // jwg::Events: the change lists of the last sampled block
+    std::vector<double> par_host;                           // what par was filled from (kept until the sweep has finished)
+};
+
 // What exists once per precision, under one name in both: the Float32 context holds a Side<float> (as its base: c->alpha), a Float64
 // context a Side<double> besides (c->f64->alpha); side<T>(c) picks one.  Two owners: chain_mem for what jwas_hip_init_state replaces,
 // load_mem for what a load of genotypes replaces; dropping is release() and a value reset, so no member can be forgotten in a free list.
@@ -303,24 +322,12 @@ struct jwas_hip_ctx : Side<float> {
     } rr;
     // Mega-trait model (jwas_hip_mega_begin .. _end; markers/BayesianAlphabet/BayesABC.jl:1-58; csrc/mega.hpp): T independent
     // single-trait chains over the context's genotypes, a sweep of its own with its own residuals and state, all double
-    struct Mega {
-        bool active = false;
-        int nt = 0, bs = 0;                                 // traits, block size
+    struct Mega : BlockSession {
         uint32_t first_trait = 0;                           // the trait id of trait 0 in the RNG counter
-        int64_t nblocks = 0, mask_words = 0, row_cap = 0;
-        DevOwner mem;
+        int64_t mask_words = 0;
         std::vector<uint8_t> miss_host;                     // [nt][n] 1: the cell is missing (empty: none)
         uint32_t* mask = nullptr;                           // [nt][ld / 32] bit i: record i misses the trait
-        double* R = nullptr;                                // [nt][ld] the residuals (pad rows 0)
-        double* xpx = nullptr;                              // [p]
-        double* gram = nullptr;                             // [nblocks][bs][bs]
-        MarkerState ms;                                     // [nt][p]
-        double* partials = nullptr;                         // [nslices][nt][bs]
-        double* par = nullptr;                              // [kParSize][nt] the per-trait parameters of the running sweep
-        double* stat = nullptr;                             // [nt][kStSize] | [nt][nslices][2] sum r^2, sum r per slice
-        double* row = nullptr;                              // [row_cap] X alpha_k
-        void* ev = nullptr;                                 // jwg::Events: the change lists of the last sampled block
-        std::vector<double> par_host;                       // what par was filled from (kept until the sweep has finished)
+        // par: [kParSize][nt] the per-trait parameters; stat: [nt][kStSize] | [nt][nslices][2] sum r^2, sum r per slice
         // BayesR chains (jwas_hip_mega_sweep_r) and the PSRF of the chains: allocated at their first call
         double* par_r = nullptr;                            // [kParRSize][nt]
         double* stat_r = nullptr;                           // [nt][kStRSize] | [nt][nslices][2]
@@ -328,22 +335,8 @@ struct jwas_hip_ctx : Side<float> {
     } mg;
     // Unconstrained multi-trait BayesC with 5 to 8 traits (jwas_hip_mtj_begin .. _end; markers/BayesianAlphabet/MTBayesABC.jl:57-127;
     // csrc/mtjoint.hpp): Gibbs sampler I on the block form of the mega-trait session, a sweep of its own with its own residuals and
-    // state, all double
-    struct Mtj {
-        bool active = false;
-        int nt = 0, bs = 0;                                 // traits, block size
-        int64_t nblocks = 0, row_cap = 0;
-        DevOwner mem;
-        double* R = nullptr;                                // [nt][ld] the residuals (pad rows 0)
-        double* xpx = nullptr;                              // [p]
-        double* gram = nullptr;                             // [nblocks][bs][bs]
-        MarkerState ms;                                     // [nt][p]
-        double* partials = nullptr;                         // [nslices][nt][bs]
-        double* par = nullptr;                              // [kParSize] Rinv | Ginv | log pi of the running sweep
-        double* stat = nullptr;                             // [kStSize] the sweep's statistics | [nslices][kFinSize] residual sums per slice
-        double* row = nullptr;                              // [row_cap] X alpha_k
-        void* ev = nullptr;                                 // jwg::Events: the change lists of the last sampled block
-        std::vector<double> par_host;                       // what par was filled from (kept until the sweep has finished)
+    // state, all double.  par: [kParSize] Rinv | Ginv | log pi; stat: [kStSize] | [nslices][kFinSize] residual sums per slice
+    struct Mtj : BlockSession {
     } mj;
     // Single-step imputation (jwas_hip_ss_begin .. _end; single_step/SSBR.jl:83-159; csrc/ssbr.hpp): the factors of A^nn, A^ng and the
     // chunk buffers of a sparse solve with many right-hand sides.  It is bound to no matrix: the targets are checked at every chunk.

@@ -2,27 +2,16 @@
 // (markers/BayesianAlphabet/BayesABC.jl:1-58) for up to 64 traits and sampleMissingResiduals under a diagonal R (residual.jl:51-73).
 // Several chains of one model are traits of the same session: jwas_hip_mega_sweep_r (the 4-class BayesR law, BayesR.jl:56-96),
 // jwas_hip_mega_accumulate_r and jwas_hip_mega_psrf (the potential scale reduction factor over the chains).
-#include "ctx.hpp"
-#include "marker_state.hpp"
-#include "mega.hpp"
+#include "block_session.hpp"
 
 static_assert(jwg::kMaxT == JWAS_HIP_MEGA_MAX_TRAITS && jwg::kMaxBlock == JWAS_HIP_MEGA_MAX_BLOCK, "the header's limits are mega.hpp's");
 
-static int need_mega(jwas_hip_ctx* c)
-{
-    if (int rc = session_guard(c, &jwas_hip_ctx::mg, "jwas_hip_mega_begin")) return rc;
-    NEED(c, !is_weighted(c), JWAS_HIP_EUNSUP, "mega-trait models do not run with residual weights");
-    return refuse_shards(c, "mega-trait models");
-}
-
-static int need_trait(jwas_hip_ctx* c, int32_t trait)
-{
-    if (int rc = need_mega(c)) return rc;
-    NEED(c, trait >= 0 && trait < c->mg.nt, JWAS_HIP_EINVAL, "trait %d outside [0,%d)", trait, c->mg.nt);
-    return JWAS_HIP_OK;
-}
-
 void mega_free(jwas_hip_ctx* c) { DevOwner::reset(c->mg); }
+
+static const BlockWords kMega = {"mega-trait session", "mega-trait models", "mega-trait models do not run with residual weights", "jwas_hip_mega_begin", mega_free};
+
+static int need_mega(jwas_hip_ctx* c) { return block_guard(c, &jwas_hip_ctx::mg, kMega); }
+static int need_trait(jwas_hip_ctx* c, int32_t trait) { return block_trait_guard(c, &jwas_hip_ctx::mg, kMega, trait); }
 
 static int64_t mega_bytes(int64_t n, int64_t p, int T, int bs)
 {
@@ -53,49 +42,25 @@ static int mega_params(jwas_hip_ctx* c, const jwas_mega_params* P, bool sweep, c
     return JWAS_HIP_OK;
 }
 
-// par_host -> the device table `par` (par_host stays until the sweep has finished)
-static int mega_upload_params(jwas_hip_ctx* c, double* par)
-{
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(par, c->mg.par_host.data(), sizeof(double) * c->mg.par_host.size(), hipMemcpyHostToDevice, c->stream));
-    return JWAS_HIP_OK;
-}
-
-// One sweep over the blocks under the law of `sample` (jwg::k_mega_sample, _r): par_host goes to `par`; per block the right-hand
-// sides and the walk, after the last block its change list and the residual sums.  host: the device record [T][rec] | [T][nslices][2];
-// resid_ss, resid_sum (NULL: not wanted): sum r^2 and sum r of every trait, the slices added in ascending order.
+// One sweep over the blocks under the law of `sample` (jwg::k_mega_sample, _r) on block_session.hpp's walk.  host: the device record
+// [T][rec] | [T][nslices][2]; resid_ss, resid_sum (NULL: not wanted): sum r^2 and sum r of every trait, the slices added in ascending order.
 static int mega_run_sweep(jwas_hip_ctx* c, uint32_t iteration, uint64_t seed, double* par, double* stat, int rec, void (*sample)(const jwg::SampleArgs),
                           std::vector<double>& host, double* step_ms, double* resid_ss, double* resid_sum)
 {
     auto& b = c->mg;
     const int T = b.nt, nsl = c->nslices;
-    const size_t nstat = (size_t)T * (size_t)(rec + 2 * nsl);
-    if (int rc = mega_upload_params(c, par)) return rc;
-    if (int rc = step_timer_begin(c)) return rc;
-    HIPCHK(c, hipMemsetAsync(stat, 0, sizeof(double) * nstat, c->stream));
-    jwg::UpdateArgs U = {};
-    U.X = genotypes_ptr(c); U.R = b.R; U.partials = b.partials; U.ld = c->ld; U.T = T; U.bs = b.bs;
     jwg::SampleArgs A = {};
     A.partials = b.partials; A.xpx = b.xpx; A.par = par; A.alpha = b.ms.alpha; A.beta = b.ms.beta; A.delta = b.ms.delta; A.ev = (jwg::Events*)b.ev;
     A.stat = stat; A.p = c->p; A.nslices = nsl; A.bs = b.bs; A.T = T; A.iter = iteration; A.first_trait = b.first_trait;
     split_seed(seed, A.seed_lo, A.seed_hi);
     jwg::FinishArgs F = {};
     F.X = genotypes_ptr(c); F.R = b.R; F.ev = (const jwg::Events*)b.ev; F.fin = stat + (size_t)T * rec; F.ld = c->ld; F.T = T;
-    const dim3 tiles((unsigned)nsl, (unsigned)((T + jwg::kTT - 1) / jwg::kTT));
-    with_real(c, [&](auto real) {
-        using real_t = decltype(real);
-        for (int64_t k = 0; k < b.nblocks; ++k) {
-            const int64_t j0 = k * b.bs;
-            U.ev = k ? (const jwg::Events*)b.ev : nullptr; U.j0 = j0; U.b = (int32_t)std::min<int64_t>(b.bs, c->p - j0);
-            A.gram = b.gram + k * (int64_t)b.bs * b.bs; A.j0 = j0; A.b = U.b;
-            hipLaunchKernelGGL((jwg::k_mega_update_partial<real_t>), tiles, dim3(256), 0, c->stream, U);
-            hipLaunchKernelGGL(sample, dim3((unsigned)T), dim3(256), 0, c->stream, A);
-        }
-        hipLaunchKernelGGL((jwg::k_mega_finish<real_t>), dim3((unsigned)nsl, (unsigned)T), dim3(256), 0, c->stream, F);
-    });
-    HIPCHK(c, hipGetLastError());
-    host.resize(nstat);
-    if (int rc = step_timer_end(c, host.data(), stat, sizeof(double) * nstat, step_ms)) return rc;
+    auto launch = [&](double* gram, int64_t j0, int32_t nb) {
+        A.gram = gram; A.j0 = j0; A.b = nb;
+        hipLaunchKernelGGL(sample, dim3((unsigned)T), dim3(256), 0, c->stream, A);
+    };
+    auto finish = [&](auto real) { hipLaunchKernelGGL((jwg::k_mega_finish<decltype(real)>), dim3((unsigned)nsl, (unsigned)T), dim3(256), 0, c->stream, F); };
+    if (int rc = block_walk(c, b, par, stat, (size_t)T * (size_t)(rec + 2 * nsl), (unsigned)((T + jwg::kTT - 1) / jwg::kTT), launch, finish, host, step_ms)) return rc;
     for (int k = 0; k < T; ++k) {
         const double* fin = host.data() + (size_t)T * rec + (size_t)k * nsl * 2;
         double ss = 0.0, sm = 0.0;
@@ -110,52 +75,17 @@ extern "C" {
 
 int jwas_hip_mega_begin(jwas_hip_ctx* c, int32_t T, int32_t block_size, int32_t first_trait)
 {
-    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
-    NEED(c, !c->packed, JWAS_HIP_EUNSUP, "mega-trait models need dense genotypes (2-bit packed storage is not supported)");
-    NEED(c, genotypes_ptr(c) && c->n > 0 && c->p > 0, JWAS_HIP_ESTATE, "no genotype matrix loaded");
-    if (int rc = refuse_shards(c, "mega-trait models")) return rc;
-    NEED(c, !is_weighted(c), JWAS_HIP_EUNSUP, "mega-trait models do not run with residual weights");
-    NEED(c, T >= 1 && T <= jwg::kMaxT, JWAS_HIP_EINVAL, "the number of traits must be in [1,%d] (got %d)", jwg::kMaxT, T);
-    NEED(c, block_size >= 0 && block_size <= jwg::kMaxBlock, JWAS_HIP_EINVAL, "block size must be in [1,%d] (0: 64), got %d", jwg::kMaxBlock, block_size);
+    if (int rc = block_begin_guard(c, kMega, T, 1, jwg::kMaxT, block_size)) return rc;
     NEED(c, first_trait >= 0 && (int64_t)first_trait + T <= (int64_t)jwg::kMaxTraitId, JWAS_HIP_EINVAL,
          "first_trait must be >= 0 and first_trait + T <= %u (got %d)", jwg::kMaxTraitId, first_trait);
-    if (int rc = session_drop(c, mega_free)) return rc;
     auto& b = c->mg;
-    const int bs = block_size ? block_size : 64;
-    const int64_t p = c->p, ld = c->ld;
-    b.nt = T; b.bs = bs; b.nblocks = (p + bs - 1) / bs; b.first_trait = (uint32_t)first_trait; b.mask_words = ld / 32; b.row_cap = ld;
-    auto alloc = [&](auto** ptr, size_t bytes) { return alloc_or_nomem(c, b.mem, ptr, bytes, "mega-trait session", mega_free); };
-    const size_t gramb = sizeof(double) * (size_t)b.nblocks * bs * bs;
-    const size_t maskb = sizeof(uint32_t) * (size_t)T * (size_t)b.mask_words, statb = sizeof(double) * (size_t)T * (size_t)(jwg::kStSize + 2 * c->nslices);
-    jwg::Events* ev = nullptr;
-    if (int rc = alloc(&b.mask, maskb)) return rc;
-    if (int rc = alloc(&b.R, sizeof(double) * (size_t)T * ld)) return rc;
-    if (int rc = alloc(&b.xpx, sizeof(double) * (size_t)p)) return rc;
-    if (int rc = alloc(&b.gram, gramb)) return rc;
-    if (int rc = marker_state_begin(c, b.ms, b.mem, T, "mega-trait session", mega_free)) return rc;
-    if (int rc = alloc(&b.partials, sizeof(double) * (size_t)c->nslices * T * bs)) return rc;
-    if (int rc = alloc(&b.par, sizeof(double) * (size_t)jwg::kParSize * T)) return rc;
-    if (int rc = alloc(&b.stat, statb)) return rc;
-    if (int rc = alloc(&b.row, sizeof(double) * (size_t)ld)) return rc;
-    if (int rc = alloc(&ev, sizeof(jwg::Events))) return rc;
-    b.ev = ev;
-    HIPCHK(c, hipMemsetAsync(b.mask, 0, maskb, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.R, 0, sizeof(double) * (size_t)T * ld, c->stream));
-    HIPCHK(c, hipMemsetAsync(b.gram, 0, gramb, c->stream));
-    HIPCHK(c, hipMemsetAsync(ev, 0, sizeof(jwg::Events), c->stream));
-    with_real(c, [&](auto real) {
-        using real_t = decltype(real);
-        // (the grid's y extent is 65 535 blocks at most: the blocks go in trips)
-        for (int64_t k0 = 0; k0 < b.nblocks; k0 += 32768) {
-            const int64_t nb = std::min<int64_t>(32768, b.nblocks - k0);
-            hipLaunchKernelGGL((jwg::k_mega_gram<real_t>), dim3((unsigned)bs, (unsigned)nb), dim3(256), 0, c->stream,
-                               (const real_t*)genotypes_ptr(c) + k0 * bs * ld, ld, p - k0 * bs, (int32_t)bs, b.gram + k0 * bs * bs, b.xpx + k0 * bs);
-        }
+    return block_begin(c, b, kMega, T, block_size, (size_t)jwg::kParSize * T, (size_t)T * (size_t)(jwg::kStSize + 2 * c->nslices), [&](auto alloc) {
+        b.first_trait = (uint32_t)first_trait; b.mask_words = c->ld / 32;
+        const size_t maskb = sizeof(uint32_t) * (size_t)T * (size_t)b.mask_words;
+        if (int rc = alloc(&b.mask, maskb)) return rc;
+        HIPCHK(c, hipMemsetAsync(b.mask, 0, maskb, c->stream));
+        return (int)JWAS_HIP_OK;
     });
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.active = true;
-    return JWAS_HIP_OK;
 }
 
 int jwas_hip_mega_set_missing(jwas_hip_ctx* c, int64_t nvalues, const uint8_t* missing)
@@ -182,20 +112,13 @@ int jwas_hip_mega_set_missing(jwas_hip_ctx* c, int64_t nvalues, const uint8_t* m
 int jwas_hip_mega_set_residual(jwas_hip_ctx* c, int32_t trait, const double* r)
 {
     if (int rc = need_trait(c, trait)) return rc;
-    NEED(c, r, JWAS_HIP_EINVAL, "NULL argument");
-    for (int64_t i = 0; i < c->n; ++i) NEED(c, std::isfinite(r[i]), JWAS_HIP_EINVAL, "the residual of record %lld is not finite (%g)", (long long)i, r[i]);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->mg.R + (size_t)trait * c->ld, r, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
+    return block_set_residual(c, c->mg, trait, r);
 }
 
 int jwas_hip_mega_get_residual(jwas_hip_ctx* c, int32_t trait, double* out)
 {
     if (int rc = need_trait(c, trait)) return rc;
-    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    return to_host(c, out, c->mg.R + (size_t)trait * c->ld, sizeof(double) * (size_t)c->n);
+    return block_get_residual(c, c->mg, trait, out);
 }
 
 int jwas_hip_mega_set_state(jwas_hip_ctx* c, int32_t trait, const double* alpha, const double* beta, const double* delta)
@@ -215,7 +138,7 @@ int jwas_hip_mega_impute(jwas_hip_ctx* c, const jwas_mega_params* P)
     if (int rc = need_mega(c)) return rc;
     if (int rc = mega_params(c, P, false, "jwas_hip_mega_impute")) return rc;
     auto& b = c->mg;
-    if (int rc = mega_upload_params(c, b.par)) return rc;
+    if (int rc = block_upload_params(c, b, b.par)) return rc;
     if (!b.miss_host.empty()) {
         uint32_t lo, hi;
         split_seed(P->seed, lo, hi);
@@ -340,39 +263,13 @@ int jwas_hip_mega_get_posterior(jwas_hip_ctx* c, int32_t trait, double* mean, do
 int jwas_hip_mega_mul_alpha(jwas_hip_ctx* c, int32_t trait, int32_t use_output_rows, double* out)
 {
     if (int rc = need_trait(c, trait)) return rc;
-    auto& b = c->mg;
-    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
-    const void* X = genotypes_ptr(c);
-    int64_t n = c->n, ld = c->ld;
-    if (use_output_rows) {
-        X = output_rows_ptr(c, &n, &ld);
-        NEED(c, X, JWAS_HIP_ESTATE, "no output rows loaded (jwas_hip_load_output_dense_f32 / _f64)");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    if (ld > b.row_cap) {                                   // the output rows may outnumber the training rows
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        b.mem.free_one(b.row);
-        b.row_cap = 0;
-        if (int rc = alloc_or_nomem(c, b.mem, &b.row, sizeof(double) * (size_t)ld, "mega-trait session", mega_free)) return rc;
-        b.row_cap = ld;
-    }
-    return marker_state_mul_alpha(c, b.ms, trait, X, ld, n, b.row, out);
+    return block_mul_alpha(c, c->mg, kMega, trait, use_output_rows, out);
 }
 
 int jwas_hip_mega_get_gram(jwas_hip_ctx* c, int64_t block, int64_t nvalues, double* out, double* out_xpx)
 {
     if (int rc = need_mega(c)) return rc;
-    auto& b = c->mg;
-    NEED(c, out, JWAS_HIP_EINVAL, "NULL argument");
-    NEED(c, block >= 0 && block < b.nblocks, JWAS_HIP_EINVAL, "block %lld outside [0,%lld)", (long long)block, (long long)b.nblocks);
-    const int64_t nb = std::min<int64_t>(b.bs, c->p - block * b.bs);
-    NEED(c, nvalues == nb * nb, JWAS_HIP_EINVAL, "nvalues (%lld) differs from b b (%lld)", (long long)nvalues, (long long)(nb * nb));
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy2DAsync(out, sizeof(double) * (size_t)nb, b.gram + block * b.bs * b.bs, sizeof(double) * (size_t)b.bs, sizeof(double) * (size_t)nb, (size_t)nb,
-                               hipMemcpyDeviceToHost, c->stream));
-    if (out_xpx) HIPCHK(c, hipMemcpyAsync(out_xpx, b.xpx + block * b.bs, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return JWAS_HIP_OK;
+    return block_get_gram(c, c->mg, block, nvalues, out, out_xpx);
 }
 
 int64_t jwas_hip_mega_estimate_bytes(int64_t n, int64_t p, int32_t T, int32_t block_size)
@@ -385,7 +282,7 @@ int64_t jwas_hip_mega_estimate_bytes(int64_t n, int64_t p, int32_t T, int32_t bl
 
 int jwas_hip_mega_end(jwas_hip_ctx* c)
 {
-    if (int rc = session_guard(c, &jwas_hip_ctx::mg, "jwas_hip_mega_begin")) return rc;
+    if (int rc = session_guard(c, &jwas_hip_ctx::mg, kMega.begin)) return rc;
     return session_drop(c, mega_free);
 }
 

@@ -990,6 +990,67 @@ class HipEngine:
         self._chk(self._L.jwas_hip_rrm_end(self._h))
         self._rrm = None
 
+    # -- what the mega-trait and the joint multi-trait session share: one body per twin entry point.  kind: "mega" or "mtj" -- the
+    # symbol is jwas_hip_<kind>_<name>, and self._mega or self._mtj holds (T, block size) --------------------------------------------
+    def _blk(self, kind, name):
+        return (getattr(self._L, f"jwas_hip_{kind}_{name}"),) + getattr(self, "_" + kind)
+
+    def _blk_set_residual(self, kind, R, trait=None, one_trait=""):
+        fn, T, _ = self._blk(kind, "set_residual")
+        Rv = np.ascontiguousarray(R, dtype=np.float64)
+        if Rv.shape != ((T, self.n) if trait is None else (self.n,)):
+            raise ValueError(f"the residual must be {T} x {self.n}{one_trait}")
+        for k in (range(T) if trait is None else [int(trait)]):
+            self._chk(fn(self._h, k, _ptr(Rv[k] if trait is None else Rv)))
+
+    def _blk_get_residual(self, kind, trait=None):
+        fn, T, _ = self._blk(kind, "get_residual")
+        out = np.empty((T, self.n) if trait is None else (1, self.n), dtype=np.float64)
+        for i, k in enumerate(range(T) if trait is None else [int(trait)]):
+            self._chk(fn(self._h, k, _ptr(out[i])))
+        return out if trait is None else out[0]
+
+    def _blk_set_state(self, kind, alpha, beta, delta):
+        fn, T, _ = self._blk(kind, "set_state")
+        arrs = []
+        for a in (alpha, beta, delta):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (T, self.p):
+                    raise ValueError(f"state arrays must be {T} x {self.p}")
+            arrs.append(a)
+        for k in range(T):
+            self._chk(fn(self._h, k, *[_ptr(a[k]) if a is not None else None for a in arrs]))
+
+    def _blk_get_state(self, kind, trait=None):
+        fn, T, _ = self._blk(kind, "get_state")
+        ks = range(T) if trait is None else [int(trait)]
+        out = [np.empty((len(ks), self.p), dtype=np.float64) for _ in range(3)]
+        for i, k in enumerate(ks):
+            self._chk(fn(self._h, k, _ptr(out[0][i]), _ptr(out[1][i]), _ptr(out[2][i])))
+        return tuple(out) if trait is None else tuple(o[0] for o in out)
+
+    def _blk_gram(self, kind, name, block):
+        fn, T, bs = self._blk(kind, name)
+        b = max(min(bs, self.p - int(block) * bs), 0)
+        G, xpx = np.empty((b, b), dtype=np.float64), np.empty(b, dtype=np.float64)
+        self._chk(fn(self._h, int(block), G.size, _ptr(G), _ptr(xpx)))
+        return G, xpx
+
+    def _blk_posterior(self, fn, trait):
+        out = [np.empty(self.p, dtype=np.float64) for _ in range(3)]
+        self._chk(fn(self._h, int(trait), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
+        return tuple(out)
+
+    def _blk_mul_alpha(self, fn, trait, output_rows):
+        out = np.empty(getattr(self, "n_out", 0) if output_rows else self.n, dtype=np.float64)
+        self._chk(fn(self._h, int(trait), 1 if output_rows else 0, _ptr(out)))
+        return out
+
+    def _blk_end(self, kind):
+        self._chk(getattr(self._L, f"jwas_hip_{kind}_end")(self._h))
+        setattr(self, "_" + kind, None)
+
     # -- mega-trait models (jwas_hip_mega_*; markers/BayesianAlphabet/BayesABC.jl:1-58, csrc/mega.hpp) ------------------------
     @staticmethod
     def mega_estimate_bytes(n, p, ntraits, block_size=64):
@@ -1014,40 +1075,17 @@ class HipEngine:
 
     def mega_set_residual(self, R, trait=None):
         """R: T x n doubles (trait=None), or the n values of one trait."""
-        T, _ = self._mega
-        Rv = np.ascontiguousarray(R, dtype=np.float64)
-        if Rv.shape != ((T, self.n) if trait is None else (self.n,)):
-            raise ValueError(f"the residual must be {T} x {self.n}, or {self.n} values for one trait")
-        for k in (range(T) if trait is None else [int(trait)]):
-            self._chk(self._L.jwas_hip_mega_set_residual(self._h, k, _ptr(Rv[k] if trait is None else Rv)))
+        self._blk_set_residual("mega", R, trait, f", or {self.n} values for one trait")
 
     def mega_get_residual(self, trait=None):
-        T, _ = self._mega
-        out = np.empty((T, self.n) if trait is None else (1, self.n), dtype=np.float64)
-        for i, k in enumerate(range(T) if trait is None else [int(trait)]):
-            self._chk(self._L.jwas_hip_mega_get_residual(self._h, k, _ptr(out[i])))
-        return out if trait is None else out[0]
+        return self._blk_get_residual("mega", trait)
 
     def mega_set_state(self, alpha=None, beta=None, delta=None):
         """alpha, beta, delta: T x p doubles each, any may be None.  The state only: the residuals are not touched."""
-        T, _ = self._mega
-        arrs = []
-        for a in (alpha, beta, delta):
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.shape != (T, self.p):
-                    raise ValueError(f"state arrays must be {T} x {self.p}")
-            arrs.append(a)
-        for k in range(T):
-            self._chk(self._L.jwas_hip_mega_set_state(self._h, k, *[_ptr(a[k]) if a is not None else None for a in arrs]))
+        self._blk_set_state("mega", alpha, beta, delta)
 
     def mega_get_state(self, trait=None):
-        T, _ = self._mega
-        ks = range(T) if trait is None else [int(trait)]
-        out = [np.empty((len(ks), self.p), dtype=np.float64) for _ in range(3)]
-        for i, k in enumerate(ks):
-            self._chk(self._L.jwas_hip_mega_get_state(self._h, k, _ptr(out[0][i]), _ptr(out[1][i]), _ptr(out[2][i])))
-        return tuple(out) if trait is None else tuple(o[0] for o in out)
+        return self._blk_get_state("mega", trait)
 
     def _mega_params(self, iteration, seed, vare, var_effect=None, pi=None):
         T, _ = self._mega
@@ -1130,27 +1168,18 @@ class HipEngine:
 
     def mega_posterior(self, trait):
         """(mean, mean of squares, model frequency) of one trait's effects, p values each."""
-        out = [np.empty(self.p, dtype=np.float64) for _ in range(3)]
-        self._chk(self._L.jwas_hip_mega_get_posterior(self._h, int(trait), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
-        return tuple(out)
+        return self._blk_posterior(self._L.jwas_hip_mega_get_posterior, trait)
 
     def mega_mul_alpha(self, trait, output_rows=False):
         """X alpha_k over the training rows, or over the rows of load_output_dense."""
-        out = np.empty(getattr(self, "n_out", 0) if output_rows else self.n, dtype=np.float64)
-        self._chk(self._L.jwas_hip_mega_mul_alpha(self._h, int(trait), 1 if output_rows else 0, _ptr(out)))
-        return out
+        return self._blk_mul_alpha(self._L.jwas_hip_mega_mul_alpha, trait, output_rows)
 
     def mega_gram(self, block):
         """(G, x'x) of one block: b x b and b doubles."""
-        T, bs = self._mega
-        b = max(min(bs, self.p - int(block) * bs), 0)
-        G, xpx = np.empty((b, b), dtype=np.float64), np.empty(b, dtype=np.float64)
-        self._chk(self._L.jwas_hip_mega_get_gram(self._h, int(block), G.size, _ptr(G), _ptr(xpx)))
-        return G, xpx
+        return self._blk_gram("mega", "get_gram", block)
 
     def mega_end(self):
-        self._chk(self._L.jwas_hip_mega_end(self._h))
-        self._mega = None
+        self._blk_end("mega")
 
     # -- unconstrained multi-trait BayesC with 5 to 8 traits (jwas_hip_mtj_*; MTBayesABC.jl:57-127, csrc/mtjoint.hpp) ------------
     def mtj_begin(self, ntraits, block_size=64):
@@ -1161,47 +1190,21 @@ class HipEngine:
 
     def mtj_set_residual(self, R):
         """R: T x n doubles."""
-        T, _ = self._mtj
-        Rv = np.ascontiguousarray(R, dtype=np.float64)
-        if Rv.shape != (T, self.n):
-            raise ValueError(f"the residual must be {T} x {self.n}")
-        for k in range(T):
-            self._chk(self._L.jwas_hip_mtj_set_residual(self._h, k, _ptr(Rv[k])))
+        self._blk_set_residual("mtj", R)
 
     def mtj_get_residual(self):
-        T, _ = self._mtj
-        out = np.empty((T, self.n), dtype=np.float64)
-        for k in range(T):
-            self._chk(self._L.jwas_hip_mtj_get_residual(self._h, k, _ptr(out[k])))
-        return out
+        return self._blk_get_residual("mtj")
 
     def mtj_set_state(self, alpha=None, beta=None, delta=None):
         """alpha, beta, delta: T x p doubles each, any may be None.  The state only: the residuals are not touched."""
-        T, _ = self._mtj
-        arrs = []
-        for a in (alpha, beta, delta):
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.shape != (T, self.p):
-                    raise ValueError(f"state arrays must be {T} x {self.p}")
-            arrs.append(a)
-        for k in range(T):
-            self._chk(self._L.jwas_hip_mtj_set_state(self._h, k, *[_ptr(a[k]) if a is not None else None for a in arrs]))
+        self._blk_set_state("mtj", alpha, beta, delta)
 
     def mtj_get_state(self):
-        T, _ = self._mtj
-        out = [np.empty((T, self.p), dtype=np.float64) for _ in range(3)]
-        for k in range(T):
-            self._chk(self._L.jwas_hip_mtj_get_state(self._h, k, _ptr(out[0][k]), _ptr(out[1][k]), _ptr(out[2][k])))
-        return tuple(out)
+        return self._blk_get_state("mtj")
 
     def mtj_gram(self, block):
         """(G, x'x) of one block: b x b and b doubles."""
-        T, bs = self._mtj
-        b = max(min(bs, self.p - int(block) * bs), 0)
-        G, xpx = np.empty((b, b), dtype=np.float64), np.empty(b, dtype=np.float64)
-        self._chk(self._L.jwas_hip_mtj_gram(self._h, int(block), G.size, _ptr(G), _ptr(xpx)))
-        return G, xpx
+        return self._blk_gram("mtj", "gram", block)
 
     def mtj_sweep(self, *, iteration, seed, rinv, ginv, log_pi):
         """One sweep of sampler I over all markers.  rinv = inv(vare), ginv = inv(G): T x T; log_pi: the 2^T log probabilities of the
@@ -1234,19 +1237,14 @@ class HipEngine:
 
     def mtj_posterior(self, trait):
         """(mean, mean of squares, model frequency) of one trait's effects, p values each."""
-        out = [np.empty(self.p, dtype=np.float64) for _ in range(3)]
-        self._chk(self._L.jwas_hip_mtj_posterior(self._h, int(trait), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
-        return tuple(out)
+        return self._blk_posterior(self._L.jwas_hip_mtj_posterior, trait)
 
     def mtj_mul_alpha(self, trait, output_rows=False):
         """X alpha_k over the training rows, or over the rows of load_output_dense."""
-        out = np.empty(getattr(self, "n_out", 0) if output_rows else self.n, dtype=np.float64)
-        self._chk(self._L.jwas_hip_mtj_mul_alpha(self._h, int(trait), 1 if output_rows else 0, _ptr(out)))
-        return out
+        return self._blk_mul_alpha(self._L.jwas_hip_mtj_mul_alpha, trait, output_rows)
 
     def mtj_end(self):
-        self._chk(self._L.jwas_hip_mtj_end(self._h))
-        self._mtj = None
+        self._blk_end("mtj")
 
     # -- single-step analysis: the imputation solve (SSBR.jl:83-159; csrc/ssbr.hpp) -----------------
     @staticmethod

@@ -25,10 +25,9 @@ import time
 import numpy as np
 
 from ._lib import MEGA_MAX_BLOCK, MEGA_MAX_TRAITS
-from .chain_output import (GeneticVarianceSamples, Running, SampleFiles, covariance_table, ebv_tables, location_table,
-                           marker_effects_table, pi_table, print_posterior_means, resolve_output_ids, term_sample_columns, write_id_files,
-                           write_tables)
+from .chain_output import MultiTraitOutputs, timing, write_id_files
 from .mcmc import _design, _gibbs
+from .session_driver import align_records, open_engine, phenotype_records, refuse_beyond_four_traits, refuse_engine
 
 MEGA_METHODS = ("mega_begin", "mega_set_missing", "mega_set_residual", "mega_get_residual", "mega_get_state", "mega_impute", "mega_sweep",
                 "mega_accumulate", "mega_posterior", "mega_mul_alpha", "mega_end")
@@ -39,10 +38,6 @@ DEFAULT_BLOCK = 256                      # the fastest of 64 / 128 / 256 at ever
 def routes(model):
     """The models this driver takes or refuses: more than 4 traits."""
     return model.nModels >= MIN_TRAITS
-
-
-def _not_false(x):
-    return not (x is False or x is None)
 
 
 def validate(model, df, *, fast_blocks=False, independent_blocks=False, causal_structure=False, RRM=False, location_parameters="auto",
@@ -64,35 +59,10 @@ def validate(model, df, *, fast_blocks=False, independent_blocks=False, causal_s
                                   "2^t-state samplers stay on the reference")
     if Mi.method not in ("BayesC", "RR-BLUP"):
         raise NotImplementedError(f"method={Mi.method} with more than 4 traits stays on the reference (the device runs BayesC and RR-BLUP)")
-    if Mi.annotations is not False:
-        raise NotImplementedError("annotations with more than 4 traits stay on the reference")
-    if annotation_priors != "host":
-        raise NotImplementedError('annotation_priors="device" does not apply to models with more than 4 traits')
-    mode = getattr(Mi, "storage_mode", "dense")
-    if mode == "stream":
-        raise NotImplementedError("storage=:stream with more than 4 traits stays on the reference (dense storage only)")
-    if mode == "device":
-        raise NotImplementedError("device_genotypes with more than 4 traits is not supported: pass the genotypes through get_genotypes")
-    if independent_blocks:
-        raise NotImplementedError("independent_blocks with more than 4 traits stays on the reference")
-    if fast_blocks is not False:
-        raise NotImplementedError("fast_blocks with more than 4 traits stays on the reference (megaBayesABC! is one plain pass per iteration)")
-    if heterogeneous_residuals:
-        raise NotImplementedError("heterogeneous_residuals (residual weights) with more than 4 traits stays on the reference")
-    if location_parameters == "device":
-        raise NotImplementedError('location_parameters="device" with more than 4 traits is not supported: they are sampled on the host')
-    if getattr(model, "rndTrmVec", []):
-        raise NotImplementedError("set_random effects with more than 4 traits stay on the reference")
-    if any(tt != "continuous" for tt in model.traits_type):
-        raise NotImplementedError("categorical_trait / censored_trait with more than 4 traits stay on the reference")
-    if _not_false(causal_structure):
-        raise NotImplementedError("causal_structure runs with at most 4 traits on the device")
-    if _not_false(RRM):
-        raise NotImplementedError("RRM runs with one trait; with more than 4 traits it stays on the reference")
-    if _not_false(single_step_analysis):
-        raise NotImplementedError("single_step_analysis with more than 4 traits stays on the reference")
-    if Mi.alpha is not False or _not_false(starting_value):
-        raise NotImplementedError("starting_value (marker or location-parameter starting values) with more than 4 traits stays on the reference")
+    refuse_beyond_four_traits(model, Mi, one_pass="megaBayesABC! is one plain pass per iteration", annotation_priors=annotation_priors,
+                              independent_blocks=independent_blocks, fast_blocks=fast_blocks, heterogeneous_residuals=heterogeneous_residuals,
+                              location_parameters=location_parameters, causal_structure=causal_structure, RRM=RRM,
+                              single_step_analysis=single_step_analysis, starting_value=starting_value)
     if isinstance(Mi.pi, dict):
         raise NotImplementedError("a Dict Pi over the joint states does not apply to constraint=True with more than 4 traits: pass one Pi, or one per trait")
     if np.ndim(Mi.pi) > 0 and np.size(Mi.pi) != t:
@@ -100,12 +70,8 @@ def validate(model, df, *, fast_blocks=False, independent_blocks=False, causal_s
     if block_size is not None and not 1 <= int(block_size) <= MEGA_MAX_BLOCK:
         raise ValueError(f"block_size must be in [1, {MEGA_MAX_BLOCK}] for models with more than 4 traits.")
     if engine is not None:
-        missing = [m for m in MEGA_METHODS if not hasattr(engine, m)]
-        if missing:
-            raise NotImplementedError("models with more than 4 traits need an engine with the mega-trait sweep (" + ", ".join(missing)
-                                      + " missing); the package has no CPU fallback")
-        if hasattr(engine, "comm_info") and engine.comm_info()[1] > 1:
-            raise NotImplementedError("models with more than 4 traits are not driven from marker or row shards")
+        refuse_engine(engine, MEGA_METHODS, lambda missing: "models with more than 4 traits need an engine with the mega-trait sweep (" + missing
+                      + " missing); the package has no CPU fallback")
 
 
 def constraint_priors(model, phenovar, ftype=np.float32):
@@ -154,35 +120,16 @@ def run_megatrait(model, df, *, chain_length, burnin, output_samples_frequency, 
         raise NotImplementedError("Float64 genotypes (get_genotypes(double_precision=true)) run with runMCMC(double_precision=true)")
     seed_int = 0 if seed is False else int(seed)
     rng = np.random.default_rng(seed_int)
-    name = Mi.name
     traits = list(model.lhsVec)
     bs = int(block_size) if block_size is not None else DEFAULT_BLOCK
 
     # ---- align phenotypes and genotypes (input_data_validation.jl:198-294, tools4genotypes.jl:288-323)
-    idcol = df.columns[0]
-    ph = df.copy()
-    ph[idcol] = ph[idcol].astype(str)
-    for tr in traits:
-        if tr not in ph.columns:
-            raise ValueError(f"Phenotypes for {tr} are not found in the data.")
-    Yall = np.stack([ph[tr].to_numpy(dtype=np.float64) for tr in traits])
+    idcol, ph, Yall = phenotype_records(df, traits)
     anyobs = np.isfinite(Yall).any(axis=0)
     if not np.isfinite(Yall[:, anyobs]).all() and not missing_phenotypes:
         raise ValueError("phenotypes are missing for some traits of some individuals; missing_phenotypes=false does not allow that")
-    geno_index = {g: i for i, g in enumerate(Mi.obsID)}
-    keep = anyobs & ph[idcol].isin(geno_index).to_numpy()                # records without any phenotype are removed (:396-404)
-    ph = ph.loc[keep].reset_index(drop=True)
-    if len(ph) == 0:
-        raise ValueError("no individual has both phenotypes and genotypes")
-    rows = np.array([geno_index[i] for i in ph[idcol]], dtype=np.int64)
-    X = np.asfortranarray(np.asarray(Mi.genotypes)[rows, :].astype(ftype))
+    ph, rows, X, out_ids, out_rows, out_same = align_records(model, Mi, idcol, ph, Yall, ftype, outputEBV)
     n, p = X.shape
-    out_ids, out_rows, out_same = None, None, True
-    if outputEBV:
-        out_ids, out_same = resolve_output_ids(model, Mi.obsID, ph[idcol])
-        if not out_same:
-            out_rows = np.array([geno_index[i] for i in out_ids], dtype=np.int64)
-    Mi.output_rows = out_rows if (outputEBV and not out_same) else rows
     write_id_files(output_folder, ph[idcol], Mi.obsID)
     Y = np.stack([ph[tr].to_numpy(dtype=np.float64) for tr in traits])  # t x n
     observed = np.isfinite(Y)
@@ -207,43 +154,19 @@ def run_megatrait(model, df, *, chain_length, burnin, output_samples_frequency, 
     lhs = [x.T @ x for x in Xf]
 
     # ---- the device session
-    own_engine = engine is None
-    if own_engine:
-        from .engine import HipEngine
-        engine = HipEngine(device, precision=64 if double_precision else 32)
-    engine.load_dense(X)
-    if outputEBV and not out_same:
-        engine.load_output_dense(np.asfortranarray(np.asarray(Mi.genotypes)[out_rows, :].astype(ftype)))
+    engine, own_engine = open_engine(engine, device, double_precision, X, Mi, out_rows)
     engine.mega_begin(t, bs, 0)
     if has_missing:
         engine.mega_set_missing(~observed)
     engine.mega_set_residual(Y)                                          # ycorr = y: every starting value is zero
 
-    # ---- accumulators and sample files (output.jl:320-437)
-    # run_megatrait: the variances are vectors here; the accumulators, files and tables hold them as the diagonal of a t x t matrix
-    run_sol, run_vare, run_varg = Running(sol), Running(np.diag(vare)), Running(np.diag(Gval))
-    run_pi = Running(pi_t) if Mi.estimatePi else None
-    ebv_run = [Running(np.zeros(len(out_ids))) for _ in range(t)] if outputEBV else None
-    rnames = [f"{a}_{b}" for a in traits for b in traits]
-    term_cols = term_sample_columns(model, labels, off)
-    write_marker_samples = output_samples_for_all_parameters or p <= 20000
-    fmt = "%.17g" if double_precision else "%.9g"                        # run_megatrait: the marker rows follow the precision of the run
-    genvar = None
-    files = SampleFiles(output_folder)
+    # ---- accumulators and sample files: the variances are vectors here; the outputs hold them as the diagonal of a t x t matrix
+    out = MultiTraitOutputs(model, output_folder, labels, off, sol, np.diag(vare), np.diag(Gval), pi_t if Mi.estimatePi else None, out_ids,
+                            double_precision=double_precision, heritability=output_heritability,
+                            marker_samples=output_samples_for_all_parameters or p <= 20000, diagonal_only=True)
     t_sweep, t0 = 0.0, time.time()
-    with files:
-        files.open("residual_variance", rnames)
-        files.open(f"marker_effects_variances_{name}", rnames)
-        if Mi.estimatePi:
-            files.open(f"pi_{name}", [f"pi{i + 1}" for i in range(t)])
-        if outputEBV and output_heritability:                            # output.jl:358-362,426-432
-            genvar = GeneticVarianceSamples(files, rnames, traits)
-        for key_, (_, header) in term_cols.items():
-            files.open(key_, header)
-        if write_marker_samples:
-            for tr in traits:
-                files.open(f"marker_effects_{name}_{tr}", Mi.markerID)
-        bin_writers = [files.marker_writer(f"marker_effects_{name}_{tr}", Mi.markerID) for tr in traits]
+    with out.files:
+        out.open()
         for it in range(1, chain_length + 1):
             if has_missing:                                              # 1. missing residuals (DEVICE)
                 engine.mega_impute(iteration=it, seed=seed_int, vare=vare)
@@ -266,50 +189,17 @@ def run_megatrait(model, df, *, chain_length, burnin, output_samples_frequency, 
                 vare = np.array([(st["resid_ss"][k] + Rdf * Rscale[k]) / rng.chisquare(n + Rdf) for k in range(t)]).astype(ftype).astype(np.float64)
             if it > burnin and (it - burnin) % output_samples_frequency == 0:      # 6. save
                 ks = (it - burnin) / output_samples_frequency
-                run_sol.add(sol, ks)
-                run_vare.add(np.diag(vare), ks)
-                run_varg.add(np.diag(Gval), ks)
-                if run_pi is not None:
-                    run_pi.add(pi_t, ks)
-                    files.row(f"pi_{name}", pi_t)
                 engine.mega_accumulate(ks)
-                for key_, (cols, _) in term_cols.items():
-                    files.row(key_, sol[cols])
-                files.row("residual_variance", np.diag(vare).ravel())
-                files.row(f"marker_effects_variances_{name}", np.diag(Gval).ravel())
-                alpha = engine.mega_get_state()[0]
-                for k, tr in enumerate(traits):
-                    a = alpha[k].astype(ftype)
-                    si = np.flatnonzero(a).astype(np.int32)
-                    bin_writers[k].append(si, a[si])
-                    if write_marker_samples:
-                        files.effects_row(f"marker_effects_{name}_{tr}", a, fmt)
-                if outputEBV:                                            # getEBV, output.jl:281-306
-                    ebvs = [np.asarray(engine.mega_mul_alpha(k, output_rows=not out_same), dtype=np.float64) for k in range(t)]
-                    for k in range(t):
-                        ebv_run[k].add(ebvs[k], ks)
-                    if genvar is not None:                               # output.jl:498-512 (constraint: the diagonal)
-                        genvar.add(ebvs, vare, diagonal_only=True)
+                out.save(ks, sol, np.diag(vare), np.diag(Gval), pi_t, engine.mega_get_state()[0],
+                         [np.asarray(engine.mega_mul_alpha(k, output_rows=not out_same), dtype=np.float64) for k in range(t)] if outputEBV else None)
             if it % printout_frequency == 0 and it > burnin:
-                print_posterior_means(it, np.diag(run_vare.mean))
+                out.print_means(it)
     wall = time.time() - t0
 
     # ---- results (output.jl:108-212)
-    out = {"location parameters": location_table(labels, off, run_sol.mean, run_sol.sd()),
-           "residual variance": covariance_table(rnames, run_vare)}
-    # run_megatrait: the SD from the moments as the session returns them (doubles)
-    out[f"marker effects {name}"] = marker_effects_table([(tr, Mi.markerID) + tuple(engine.mega_posterior(k)) for k, tr in enumerate(traits)],
-                                                         sd_in_double=False)
-    out[f"marker effects variance {name}"] = covariance_table(rnames, run_varg)
-    if run_pi is not None:
-        out[f"pi_{name}"] = pi_table(run_pi, traits)
-    if outputEBV:
-        out.update(ebv_tables(traits, out_ids, ebv_run))
-    if genvar is not None:
-        out.update(genvar.tables())
-    write_tables(out, output_folder)
-    out["_timing"] = {"wall_s": wall, "device_sweep_ms_total": t_sweep, "iterations": chain_length, "block_size": bs, "n": n, "p": p, "ntraits": t}
+    res = out.tables(engine.mega_posterior, traits)
+    res["_timing"] = timing(wall, t_sweep, chain_length, bs, n, p, ntraits=t)
     engine.mega_end()
     if own_engine:
         engine.close()
-    return out
+    return res

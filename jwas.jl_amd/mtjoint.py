@@ -19,10 +19,9 @@ import time
 import numpy as np
 
 from ._lib import MEGA_MAX_BLOCK, MTJ_MAX_TRAITS, MTJ_MIN_TRAITS
-from .chain_output import (GeneticVarianceSamples, Running, SampleFiles, covariance_table, ebv_tables, location_table,
-                           marker_effects_table, pi_labels, pi_table, print_posterior_means, resolve_output_ids, term_sample_columns,
-                           write_id_files, write_tables)
+from .chain_output import MultiTraitOutputs, pi_labels, timing, write_id_files
 from .mcmc import _design, _gibbs, genetic2marker
+from .session_driver import align_records, open_engine, phenotype_records, refuse_beyond_four_traits, refuse_engine
 
 MTJ_METHODS = ("mtj_begin", "mtj_set_residual", "mtj_get_residual", "mtj_get_state", "mtj_sweep", "mtj_accumulate", "mtj_posterior",
                "mtj_mul_alpha", "mtj_end")
@@ -34,10 +33,6 @@ def routes(model):
     mega-trait driver's error.)"""
     return (model.nModels >= MTJ_MIN_TRAITS and len(model.M) >= 1 and not bool(model.R.constraint)
             and not any(bool(Mi.G.constraint) for Mi in model.M))
-
-
-def _not_false(x):
-    return not (x is False or x is None)
 
 
 def inv_gauss_jordan(A):
@@ -93,13 +88,9 @@ def validate(model, df, *, fast_blocks=False, independent_blocks=False, causal_s
     """Everything the joint session does not run raises here, naming the argument, before any device work or folder creation."""
     t = model.nModels
     if engine is not None and not isinstance(engine, (list, tuple)):
-        missing = [m for m in MTJ_METHODS if not hasattr(engine, m)]
-        if missing:
-            raise NotImplementedError(f"without the joint multi-trait session, models with more than 4 traits ({t}) run on the device with "
-                                      "constraint=True in BOTH get_genotypes and build_model only; this engine lacks " + ", ".join(missing)
-                                      + " and the package has no CPU fallback")
-        if hasattr(engine, "comm_info") and engine.comm_info()[1] > 1:
-            raise NotImplementedError("models with more than 4 traits are not driven from marker or row shards")
+        refuse_engine(engine, MTJ_METHODS, lambda missing: f"without the joint multi-trait session, models with more than 4 traits ({t}) run on the "
+                      "device with constraint=True in BOTH get_genotypes and build_model only; this engine lacks " + missing
+                      + " and the package has no CPU fallback")
     if t > MTJ_MAX_TRAITS:
         raise NotImplementedError(f"models with more than {MTJ_MAX_TRAITS} traits (t = {t}) run on the device with constraint=True in BOTH "
                                   "get_genotypes and build_model only: the joint session holds 2^t states, t <= 8")
@@ -115,35 +106,10 @@ def validate(model, df, *, fast_blocks=False, independent_blocks=False, causal_s
     if isinstance(Mi.pi, dict) and len(Mi.pi) != (1 << t):
         raise NotImplementedError(f"a Dict Pi that does not list all 2^t = {1 << t} joint states selects sampler II (multi_trait_sampler), "
                                   "which stays on the reference with more than 4 traits")
-    if Mi.annotations is not False:
-        raise NotImplementedError("annotations with more than 4 traits stay on the reference")
-    if annotation_priors != "host":
-        raise NotImplementedError('annotation_priors="device" does not apply to models with more than 4 traits')
-    mode = getattr(Mi, "storage_mode", "dense")
-    if mode == "stream":
-        raise NotImplementedError("storage=:stream with more than 4 traits stays on the reference (dense storage only)")
-    if mode == "device":
-        raise NotImplementedError("device_genotypes with more than 4 traits is not supported: pass the genotypes through get_genotypes")
-    if independent_blocks:
-        raise NotImplementedError("independent_blocks with more than 4 traits stays on the reference")
-    if fast_blocks is not False:
-        raise NotImplementedError("fast_blocks with more than 4 traits stays on the reference (sampler I is one plain pass per iteration)")
-    if heterogeneous_residuals:
-        raise NotImplementedError("heterogeneous_residuals (residual weights) with more than 4 traits stays on the reference")
-    if location_parameters == "device":
-        raise NotImplementedError('location_parameters="device" with more than 4 traits is not supported: they are sampled on the host')
-    if getattr(model, "rndTrmVec", []):
-        raise NotImplementedError("set_random effects with more than 4 traits stay on the reference")
-    if any(tt != "continuous" for tt in model.traits_type):
-        raise NotImplementedError("categorical_trait / censored_trait with more than 4 traits stay on the reference")
-    if _not_false(causal_structure):
-        raise NotImplementedError("causal_structure runs with at most 4 traits on the device")
-    if _not_false(RRM):
-        raise NotImplementedError("RRM runs with one trait; with more than 4 traits it stays on the reference")
-    if _not_false(single_step_analysis):
-        raise NotImplementedError("single_step_analysis with more than 4 traits stays on the reference")
-    if Mi.alpha is not False or _not_false(starting_value):
-        raise NotImplementedError("starting_value (marker or location-parameter starting values) with more than 4 traits stays on the reference")
+    refuse_beyond_four_traits(model, Mi, one_pass="sampler I is one plain pass per iteration", annotation_priors=annotation_priors,
+                              independent_blocks=independent_blocks, fast_blocks=fast_blocks, heterogeneous_residuals=heterogeneous_residuals,
+                              location_parameters=location_parameters, causal_structure=causal_structure, RRM=RRM,
+                              single_step_analysis=single_step_analysis, starting_value=starting_value)
     if block_size is not None and not 1 <= int(block_size) <= MEGA_MAX_BLOCK:
         raise ValueError(f"block_size must be in [1, {MEGA_MAX_BLOCK}] for models with more than 4 traits.")
     pi_states(0.0 if Mi.method == "RR-BLUP" else Mi.pi, t)
@@ -191,10 +157,16 @@ def log_pi(pi):
         return np.log(np.asarray(pi, dtype=np.float64))                 # (0 -> -inf: the state is never entered)
 
 
+def draw_covariance(rng, df, S, ftype):
+    """InvWishart(df, S) with S made symmetric, rounded to the element type of the run."""
+    from scipy.stats import invwishart
+    t = S.shape[0]
+    return np.asarray(invwishart.rvs(df=df, scale=(S + S.T) / 2, random_state=rng), dtype=ftype).reshape(t, t).astype(np.float64)
+
+
 def run_mtjoint(model, df, *, chain_length, burnin, output_samples_frequency, seed, double_precision, outputEBV, output_heritability,
                 output_folder, printout_frequency, device=0, block_size=None, engine=None, printout_model_info=True,
                 output_samples_for_all_parameters=False):
-    from scipy.stats import invwishart
     Mi = model.M[0]
     t = model.nModels
     ftype = np.float64 if double_precision else np.float32
@@ -202,32 +174,13 @@ def run_mtjoint(model, df, *, chain_length, burnin, output_samples_frequency, se
         raise NotImplementedError("Float64 genotypes (get_genotypes(double_precision=true)) run with runMCMC(double_precision=true)")
     seed_int = 0 if seed is False else int(seed)
     rng = np.random.default_rng(seed_int)
-    name = Mi.name
     traits = list(model.lhsVec)
     bs = int(block_size) if block_size is not None else DEFAULT_BLOCK
 
     # ---- align phenotypes and genotypes (input_data_validation.jl:198-294, tools4genotypes.jl:288-323)
-    idcol = df.columns[0]
-    ph = df.copy()
-    ph[idcol] = ph[idcol].astype(str)
-    for tr in traits:
-        if tr not in ph.columns:
-            raise ValueError(f"Phenotypes for {tr} are not found in the data.")
-    Yall = np.stack([ph[tr].to_numpy(dtype=np.float64) for tr in traits])
-    geno_index = {g: i for i, g in enumerate(Mi.obsID)}
-    keep = np.isfinite(Yall).any(axis=0) & ph[idcol].isin(geno_index).to_numpy()
-    ph = ph.loc[keep].reset_index(drop=True)
-    if len(ph) == 0:
-        raise ValueError("no individual has both phenotypes and genotypes")
-    rows = np.array([geno_index[i] for i in ph[idcol]], dtype=np.int64)
-    X = np.asfortranarray(np.asarray(Mi.genotypes)[rows, :].astype(ftype))
+    idcol, ph, Yall = phenotype_records(df, traits)
+    ph, rows, X, out_ids, out_rows, out_same = align_records(model, Mi, idcol, ph, Yall, ftype, outputEBV)
     n, p = X.shape
-    out_ids, out_rows, out_same = None, None, True
-    if outputEBV:
-        out_ids, out_same = resolve_output_ids(model, Mi.obsID, ph[idcol])
-        if not out_same:
-            out_rows = np.array([geno_index[i] for i in out_ids], dtype=np.int64)
-    Mi.output_rows = out_rows if (outputEBV and not out_same) else rows
     write_id_files(output_folder, ph[idcol], Mi.obsID)
     Y = np.stack([ph[tr].to_numpy(dtype=np.float64) for tr in traits]).astype(ftype).astype(np.float64)     # t x n, complete (validate)
     phenovar = np.array([np.var(Y[k], ddof=1) for k in range(t)])
@@ -249,40 +202,17 @@ def run_mtjoint(model, df, *, chain_length, burnin, output_samples_frequency, se
     lhs_blocks = [[Xf[k].T @ Xf[l] for l in range(t)] for k in range(t)]
 
     # ---- the device session
-    own_engine = engine is None
-    if own_engine:
-        from .engine import HipEngine
-        engine = HipEngine(device, precision=64 if double_precision else 32)
-    engine.load_dense(X)
-    if outputEBV and not out_same:
-        engine.load_output_dense(np.asfortranarray(np.asarray(Mi.genotypes)[out_rows, :].astype(ftype)))
+    engine, own_engine = open_engine(engine, device, double_precision, X, Mi, out_rows)
     engine.mtj_begin(t, bs)
     engine.mtj_set_residual(Y)                                           # ycorr = y: every starting value is zero
 
-    # ---- accumulators and sample files (output.jl:320-437), as an unconstrained run of 2 to 4 traits writes them
-    run_sol, run_vare, run_varg = Running(sol), Running(vare), Running(Gval)
-    run_pi = Running(pi) if Mi.estimatePi else None
-    ebv_run = [Running(np.zeros(len(out_ids))) for _ in range(t)] if outputEBV else None
-    rnames = [f"{a}_{b}" for a in traits for b in traits]
-    term_cols = term_sample_columns(model, labels, off)
-    write_marker_samples = output_samples_for_all_parameters or p <= 20000
-    fmt = "%.17g" if double_precision else "%.9g"
-    genvar = None
-    files = SampleFiles(output_folder)
+    # ---- accumulators and sample files
+    out = MultiTraitOutputs(model, output_folder, labels, off, sol, vare, Gval, pi if Mi.estimatePi else None, out_ids,
+                            double_precision=double_precision, heritability=output_heritability,
+                            marker_samples=output_samples_for_all_parameters or p <= 20000, diagonal_only=False)
     t_sweep, t0 = 0.0, time.time()
-    with files:
-        files.open("residual_variance", rnames)
-        files.open(f"marker_effects_variances_{name}", rnames)
-        if Mi.estimatePi:
-            files.open(f"pi_{name}", [f"pi{i + 1}" for i in range(1 << t)])
-        if outputEBV and output_heritability:                            # output.jl:358-362,426-432
-            genvar = GeneticVarianceSamples(files, rnames, traits)
-        for key_, (_, header) in term_cols.items():
-            files.open(key_, header)
-        if write_marker_samples:
-            for tr in traits:
-                files.open(f"marker_effects_{name}_{tr}", Mi.markerID)
-        bin_writers = [files.marker_writer(f"marker_effects_{name}_{tr}", Mi.markerID) for tr in traits]
+    with out.files:
+        out.open()
         for it in range(1, chain_length + 1):
             Rinv = inv_gauss_jordan(vare)
             if off[-1]:                                                  # 1. location parameters (mcmc.py's multi-trait host scan)
@@ -297,56 +227,22 @@ def run_mtjoint(model, df, *, chain_length, burnin, output_samples_frequency, se
             if Mi.estimatePi:                                            # 3. mcmc.py:1384
                 pi = rng.dirichlet(st["state_counts"] + 1.0)
             if Mi.G.estimate_variance:                                   # 4. mcmc.py:1416-1420
-                S = Gscale + st["beta_ss"]
-                Gval = np.asarray(invwishart.rvs(df=Gdf + p, scale=(S + S.T) / 2, random_state=rng), dtype=ftype).reshape(t, t).astype(np.float64)
+                Gval = draw_covariance(rng, Gdf + p, Gscale + st["beta_ss"], ftype)
             if model.R.estimate_variance:                                # mcmc.py:1461-1463
-                S = Rscale + st["resid_cp"]
-                vare = np.asarray(invwishart.rvs(df=Rdf + n, scale=(S + S.T) / 2, random_state=rng), dtype=ftype).reshape(t, t).astype(np.float64)
+                vare = draw_covariance(rng, Rdf + n, Rscale + st["resid_cp"], ftype)
             if it > burnin and (it - burnin) % output_samples_frequency == 0:      # 5. save
                 ks = (it - burnin) / output_samples_frequency
-                run_sol.add(sol, ks)
-                run_vare.add(vare, ks)
-                run_varg.add(Gval, ks)
-                if run_pi is not None:
-                    run_pi.add(pi, ks)
-                    files.row(f"pi_{name}", pi)
                 engine.mtj_accumulate(ks)
-                for key_, (cols, _) in term_cols.items():
-                    files.row(key_, sol[cols])
-                files.row("residual_variance", vare.ravel())
-                files.row(f"marker_effects_variances_{name}", Gval.ravel())
-                alpha = engine.mtj_get_state()[0]
-                for k, tr in enumerate(traits):
-                    a = alpha[k].astype(ftype)
-                    si = np.flatnonzero(a).astype(np.int32)
-                    bin_writers[k].append(si, a[si])
-                    if write_marker_samples:
-                        files.effects_row(f"marker_effects_{name}_{tr}", a, fmt)
-                if outputEBV:                                            # getEBV, output.jl:281-306
-                    ebvs = [np.asarray(engine.mtj_mul_alpha(k, output_rows=not out_same), dtype=np.float64) for k in range(t)]
-                    for k in range(t):
-                        ebv_run[k].add(ebvs[k], ks)
-                    if genvar is not None:                               # output.jl:498-512: the full genetic covariance
-                        genvar.add(ebvs, np.diag(vare))
+                out.save(ks, sol, vare, Gval, pi, engine.mtj_get_state()[0],
+                         [np.asarray(engine.mtj_mul_alpha(k, output_rows=not out_same), dtype=np.float64) for k in range(t)] if outputEBV else None)
             if it % printout_frequency == 0 and it > burnin:
-                print_posterior_means(it, run_vare.mean)
+                out.print_means(it)
     wall = time.time() - t0
 
     # ---- results (output.jl:108-212)
-    out = {"location parameters": location_table(labels, off, run_sol.mean, run_sol.sd()),
-           "residual variance": covariance_table(rnames, run_vare)}
-    out[f"marker effects {name}"] = marker_effects_table([(tr, Mi.markerID) + tuple(engine.mtj_posterior(k)) for k, tr in enumerate(traits)],
-                                                         sd_in_double=False)
-    out[f"marker effects variance {name}"] = covariance_table(rnames, run_varg)
-    if run_pi is not None:
-        out[f"pi_{name}"] = pi_table(run_pi, pi_labels(t, "BayesC"))
-    if outputEBV:
-        out.update(ebv_tables(traits, out_ids, ebv_run))
-    if genvar is not None:
-        out.update(genvar.tables())
-    write_tables(out, output_folder)
-    out["_timing"] = {"wall_s": wall, "device_sweep_ms_total": t_sweep, "iterations": chain_length, "block_size": bs, "n": n, "p": p, "ntraits": t}
+    res = out.tables(engine.mtj_posterior, pi_labels(t, "BayesC"))
+    res["_timing"] = timing(wall, t_sweep, chain_length, bs, n, p, ntraits=t)
     engine.mtj_end()
     if own_engine:
         engine.close()
-    return out
+    return res

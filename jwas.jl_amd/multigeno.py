@@ -27,12 +27,9 @@ from .chain_output import (GeneticVarianceSamples, Running, SampleFiles, covaria
                            marker_effects_table, pi_labels, pi_table, print_posterior_means, resolve_output_ids, sparse_effects,
                            term_sample_columns, write_id_files, write_tables)
 from .mcmc import _design, _gibbs, genetic2marker, host_location_step
+from .session_driver import not_false
 
 MAX_TRAITS = 4
-
-
-def _is_false(x):
-    return x is False or x is None
 
 
 def validate(model, df, *, fast_blocks=False, independent_blocks=False, location_parameters="auto", causal_structure=False,
@@ -51,9 +48,9 @@ def validate(model, df, *, fast_blocks=False, independent_blocks=False, location
         raise NotImplementedError(f"set_random effects {what} stay on the reference")
     if any(tt != "continuous" for tt in getattr(model, "traits_type", [])):
         raise NotImplementedError(f"categorical or censored traits {what} stay on the reference")
-    if not _is_false(causal_structure):
+    if not_false(causal_structure):
         raise NotImplementedError(f"causal_structure {what} stays on the reference")
-    if not _is_false(RRM):
+    if not_false(RRM):
         raise NotImplementedError(f"RRM {what} stays on the reference")
     if any(getattr(Mi, "annotations", False) is not False for Mi in M):
         raise NotImplementedError(f"marker annotations {what} stay on the reference")

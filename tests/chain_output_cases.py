@@ -271,6 +271,65 @@ CASES = {f.__name__: f for f in (
     multigeno_mixed, multigeno_three_traits, multigeno_ebv_ids, megatrait_f64, megatrait_f32, rrm_default, rrm_fixed_pi_no_ebv)}
 
 
+# ---- the drivers of the block sessions (tests/golden/session_driver_golden.json): run_mtjoint, run_chains, and the output rows of
+# run_megatrait -------------------------------------------------------------------------------------------------------------------------
+IDS_OUT_16 = [f"i{i}" for i in range(9, 16)]             # (with nph = 12: i12 .. i15 have no record)
+
+
+def _mtjoint(tmp, name, double, data=None, **kw):
+    import test_mtj_host as T
+    from test_megatrait_host import mega_data
+    data = data or mega_data(n=16, p=8, t=5, missing=0.0)
+
+    def run():
+        return T.run_joint(tmp, name, data=data, double=double, output_samples_frequency=2, **kw)
+    return list(data), run
+
+
+def mtjoint_f64(tmp):
+    return _mtjoint(tmp, "mtj64", True, model_edit=lambda model, api_: api_.outputMCMCsamples(model, "age"))
+
+
+def mtjoint_f32(tmp):
+    return _mtjoint(tmp, "mtj32", False)
+
+
+def mtjoint_rrblup_ids(tmp):
+    from test_megatrait_host import mega_data
+    return _mtjoint(tmp, "mtj_rr", True, data=mega_data(n=16, p=8, t=5, nph=12, missing=0.0), geno_kw=dict(method="RR-BLUP"),
+                    model_edit=lambda model, api_: api_.outputEBV(model, IDS_OUT_16))
+
+
+def megatrait_ids_missing(tmp):
+    import test_megatrait_host as T
+    data = T.mega_data(n=16, p=8, nph=12)
+
+    def run():
+        return T.run_mega(tmp, "mega_ids", data=data, output_samples_frequency=2,
+                          model_edit=lambda model, api_: api_.outputEBV(model, IDS_OUT_16))
+    return list(data), run
+
+
+def _chains(tmp, name, method, **kw):
+    import test_chains_host as T
+    data = T.chain_data(n=16, p=8)
+
+    def run():
+        return T.run_k(tmp, name, data=data, method=method, output_samples_frequency=2, **kw)
+    return list(data), run
+
+
+def chains_bayesc(tmp):
+    return _chains(tmp, "chains_c", "BayesC", chains=3)
+
+
+def chains_bayesr(tmp):
+    return _chains(tmp, "chains_r", "BayesR", chains=2, first_chain=2)
+
+
+SESSION_DRIVER_CASES = {f.__name__: f for f in (mtjoint_f64, mtjoint_f32, mtjoint_rrblup_ids, megatrait_ids_missing, chains_bayesc, chains_bayesr)}
+
+
 # ---- recording ---------------------------------------------------------------------------------------------------------------------------
 def _sha(data):
     return hashlib.sha256(data).hexdigest()
@@ -320,9 +379,14 @@ def _table(tab):
     return rec
 
 
-def run_case(name, tmp):
-    """What one case read and wrote: the record the fixture holds."""
-    inputs, run = CASES[name](tmp)
+def _files_below(folder):
+    """Every file of the output folder, those of the per-chain folders of run_chains as chain/name."""
+    return sorted(os.path.relpath(os.path.join(d, f), folder).replace(os.sep, "/") for d, _, fs in os.walk(folder) for f in fs)
+
+
+def run_case(name, tmp, cases=CASES):
+    """What one case (of `cases`: CASES or SESSION_DRIVER_CASES) read and wrote: the record the fixture holds."""
+    inputs, run = cases[name](tmp)
     before = set(os.listdir(tmp))
     chunks = []
     with _recorded_prints(chunks), contextlib.redirect_stdout(io.StringIO()):
@@ -330,7 +394,7 @@ def run_case(name, tmp):
     (folder,) = sorted(set(os.listdir(tmp)) - before)
     folder = os.path.join(str(tmp), folder)
     return {"inputs": inputs_digest(inputs),
-            "sha256": {f: _sha(open(os.path.join(folder, f), "rb").read()) for f in sorted(os.listdir(folder))},
+            "sha256": {f: _sha(open(os.path.join(folder, f), "rb").read()) for f in _files_below(folder)},
             "tables": {key: _table(tab) for key, tab in out.items() if isinstance(tab, pd.DataFrame)},
             "timing_keys": sorted(out["_timing"]),
             "stdout": "".join(chunks).replace(str(tmp), "<tmp>")}

@@ -2,12 +2,14 @@
 of the commit the fixture pins -- the parent of the commit that moved the sessions out of csrc/jwas_hip.hip.  Run once on the GPU
 with that commit's library:
 
-    python tests/golden/make_session_golden.py --commit HASH [--lib path/to/libjwas_hip.so] [--cases block|output] [--out FILE]
+    python tests/golden/make_session_golden.py --commit HASH [--lib path/to/libjwas_hip.so] [--cases block|output|mtj] [--out FILE]
 
 HASH names the commit whose library is loaded; the fixture records it.  --cases block writes tests/golden/block_session_golden.json
 instead: the sessions with a block sweep of their own (BLOCK_CASES), pinned to the parent of the commit that gave them one copy of
 their shared code.  --cases output writes tests/golden/output_side_golden.json: the output side of a context (OUTPUT_CASES), pinned to the
-parent of the commit that gave its Float32 and Float64 halves one body (csrc/output.hip).
+parent of the commit that gave its Float32 and Float64 halves one body (csrc/output.hip).  --cases mtj writes
+tests/golden/mtj_session_golden.json: the joint multi-trait session (MTJ_CASES), pinned to the parent of the commit that gave it and the
+mega-trait session one host body (csrc/block_session.hpp).
 
 tests/test_gpu_session_golden.py replays the same calls on the current library and requires equal values and digests."""
 import argparse
@@ -26,7 +28,7 @@ def _both(cases):
 
 
 FIXTURES = {"session": (_both(G.CASES), "session_golden.json"), "block": (_both(G.BLOCK_CASES), "block_session_golden.json"),
-            "output": (G.output_keys(), "output_side_golden.json")}
+            "output": (G.output_keys(), "output_side_golden.json"), "mtj": (_both(G.MTJ_CASES), "mtj_session_golden.json")}
 
 
 def rocm_version():

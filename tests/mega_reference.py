@@ -243,14 +243,17 @@ def propagated_bound(X, R0, alpha0, res, *, iteration, seed, vare, var_effect, f
     return err
 
 
-class MegaStandInEngine:
-    """The mega_* methods of HipEngine (and the little else the mega-trait driver calls) on the restatement above."""
+class BlockStandInEngine:
+    """What the stand-ins of the two block sessions share (MegaStandInEngine, MtjStandInEngine): the loaders and the transfer of the
+    residual, the state, the running means, X alpha and the Grams.  KIND ("mega", "mtj"): the session lives in self._<KIND>, a
+    subclass names the methods <KIND>_* and adds its _begin and its sweep."""
+    KIND = None
 
     def __init__(self, precision=64):
         self.precision = int(precision)
         self.dtype = np.float64 if precision == 64 else np.float32
         self.n = self.p = 0
-        self._mega = None
+        setattr(self, "_" + self.KIND, None)
         self.X = self.Xout = None
         self.calls = []
 
@@ -263,7 +266,7 @@ class MegaStandInEngine:
             raise TypeError(f"this engine stores {np.dtype(self.dtype).name} genotypes")
         self.X = X.astype(np.float64)
         self.n, self.p = X.shape
-        self._mega = None
+        setattr(self, "_" + self.KIND, None)
         self.calls.append("load_dense")
 
     def load_output_dense(self, X_out):
@@ -273,6 +276,77 @@ class MegaStandInEngine:
         self.Xout = X_out.astype(np.float64)
         self.n_out = X_out.shape[0]
 
+    def _need(self):
+        s = getattr(self, "_" + self.KIND)
+        if s is None:
+            raise ValueError(f"{self.KIND}_begin has not been called")
+        return s
+
+    def _open(self, T, bs, **more):
+        """The session of T traits in blocks of bs markers: residuals, alpha and beta 0, delta 1, the block Grams."""
+        setattr(self, "_" + self.KIND, SweepResult(
+            T=T, bs=bs, R=np.zeros((T, self.n)), alpha=np.zeros((T, self.p)), beta=np.zeros((T, self.p)), delta=np.ones((T, self.p)),
+            acc=[np.zeros((T, self.p)) for _ in range(3)], grams=[gram_block(self.X, j0, min(bs, self.p - j0)) for j0 in range(0, self.p, bs)], **more))
+        self.calls.append(self.KIND + "_begin")
+
+    def _set_residual(self, R, trait=None):
+        s = self._need()
+        R = np.asarray(R, dtype=np.float64)
+        if trait is None:
+            if R.shape != (s.T, self.n) or not np.all(np.isfinite(R)):
+                raise ValueError("the residual must be finite and T x n")
+            s.R[...] = R
+        else:
+            s.R[int(trait)] = R
+
+    def _get_residual(self, trait=None):
+        s = self._need()
+        return s.R.copy() if trait is None else s.R[int(trait)].copy()
+
+    def _set_state(self, alpha=None, beta=None, delta=None):
+        s = self._need()
+        for name, a in (("alpha", alpha), ("beta", beta), ("delta", delta)):
+            if a is not None:
+                a = np.asarray(a, dtype=np.float64)
+                if a.shape != (s.T, self.p) or not np.all(np.isfinite(a)):
+                    raise ValueError("state arrays must be finite and T x p")
+                s[name][...] = a
+
+    def _get_state(self, trait=None):
+        s = self._need()
+        if trait is None:
+            return s.alpha.copy(), s.beta.copy(), s.delta.copy()
+        return s.alpha[int(trait)].copy(), s.beta[int(trait)].copy(), s.delta[int(trait)].copy()
+
+    def _accumulate(self, nsamples):
+        s = self._need()
+        for acc, v in zip(s.acc, (s.alpha, s.alpha * s.alpha, s.delta)):
+            acc += (v - acc) / nsamples
+
+    def _posterior(self, trait):
+        return tuple(a[int(trait)].copy() for a in self._need().acc)
+
+    def _mul_alpha(self, trait, output_rows=False):
+        return (self.Xout if output_rows else self.X) @ self._need().alpha[int(trait)]
+
+    def _gram(self, block):
+        G = self._need().grams[block]
+        return G.copy(), np.diag(G).copy()
+
+    def _finish(self):
+        self._need()
+        setattr(self, "_" + self.KIND, None)
+        self.calls.append(self.KIND + "_end")
+
+
+class MegaStandInEngine(BlockStandInEngine):
+    """The mega_* methods of HipEngine (and the little else the mega-trait driver calls) on the restatement above."""
+    KIND = "mega"
+    mega_set_residual, mega_get_residual = BlockStandInEngine._set_residual, BlockStandInEngine._get_residual
+    mega_set_state, mega_get_state = BlockStandInEngine._set_state, BlockStandInEngine._get_state
+    mega_accumulate, mega_posterior = BlockStandInEngine._accumulate, BlockStandInEngine._posterior
+    mega_mul_alpha, mega_gram, mega_end = BlockStandInEngine._mul_alpha, BlockStandInEngine._gram, BlockStandInEngine._finish
+
     @staticmethod
     def mega_estimate_bytes(n, p, ntraits, block_size=64):
         ld, bs = (n + 255) // 256 * 256, block_size or 64
@@ -280,21 +354,12 @@ class MegaStandInEngine:
         return 8 * (ntraits * ld + p + nblocks * bs * bs + 6 * ntraits * p + nsl * ntraits * bs + 4 * ntraits + ntraits * (4 + 2 * nsl) + ld) + \
             4 * ntraits * (ld // 32) + (4 * 64 + 4 * 64 * 256 + 8 * 64 * 256)
 
-    def _need(self):
-        if self._mega is None:
-            raise ValueError("mega_begin has not been called")
-        return self._mega
-
     def mega_begin(self, ntraits, block_size=64, first_trait=0):
         if self.p == 0:
             raise ValueError("no genotype matrix loaded")
         if not 1 <= int(ntraits) <= MAX_TRAITS or not 0 <= int(block_size) <= MAX_BLOCK or int(first_trait) < 0:
             raise ValueError("the number of traits must be in [1,64] and the block size in [1,256]")
-        T, bs = int(ntraits), int(block_size) or 64
-        self._mega = SweepResult(T=T, bs=bs, first=int(first_trait), R=np.zeros((T, self.n)), alpha=np.zeros((T, self.p)), beta=np.zeros((T, self.p)),
-                                 delta=np.ones((T, self.p)), missing=None, acc=[np.zeros((T, self.p)) for _ in range(3)],
-                                 grams=[gram_block(self.X, j0, min(bs, self.p - j0)) for j0 in range(0, self.p, bs)])
-        self.calls.append("mega_begin")
+        self._open(int(ntraits), int(block_size) or 64, first=int(first_trait), missing=None)
 
     def mega_set_missing(self, missing):
         s = self._need()
@@ -305,35 +370,6 @@ class MegaStandInEngine:
         if m.shape != (s.T, self.n):
             raise ValueError("the missing pattern must be T x n")
         s["missing"] = m.copy()
-
-    def mega_set_residual(self, R, trait=None):
-        s = self._need()
-        R = np.asarray(R, dtype=np.float64)
-        if trait is None:
-            if R.shape != (s.T, self.n) or not np.all(np.isfinite(R)):
-                raise ValueError("the residual must be finite and T x n")
-            s.R[...] = R
-        else:
-            s.R[int(trait)] = R
-
-    def mega_get_residual(self, trait=None):
-        s = self._need()
-        return s.R.copy() if trait is None else s.R[int(trait)].copy()
-
-    def mega_set_state(self, alpha=None, beta=None, delta=None):
-        s = self._need()
-        for name, a in (("alpha", alpha), ("beta", beta), ("delta", delta)):
-            if a is not None:
-                a = np.asarray(a, dtype=np.float64)
-                if a.shape != (s.T, self.p) or not np.all(np.isfinite(a)):
-                    raise ValueError("state arrays must be finite and T x p")
-                s[name][...] = a
-
-    def mega_get_state(self, trait=None):
-        s = self._need()
-        if trait is None:
-            return s.alpha.copy(), s.beta.copy(), s.delta.copy()
-        return s.alpha[int(trait)].copy(), s.beta[int(trait)].copy(), s.delta[int(trait)].copy()
 
     def mega_impute(self, *, iteration, seed, vare):
         s = self._need()
@@ -349,26 +385,6 @@ class MegaStandInEngine:
             raise ValueError("iteration >= 1, positive finite variances and pi in [0,1] are needed")
         return sweep_blocked(self.X, s.R, s.alpha, s.beta, s.delta, block_size=s.bs, iteration=iteration, seed=seed, vare=vare, var_effect=v, pi=pi,
                              first_trait=s.first, min_margin=min_margin, grams=s.grams)
-
-    def mega_accumulate(self, nsamples):
-        s = self._need()
-        for acc, v in zip(s.acc, (s.alpha, s.alpha * s.alpha, s.delta)):
-            acc += (v - acc) / nsamples
-
-    def mega_posterior(self, trait):
-        return tuple(a[int(trait)].copy() for a in self._need().acc)
-
-    def mega_mul_alpha(self, trait, output_rows=False):
-        return (self.Xout if output_rows else self.X) @ self._need().alpha[int(trait)]
-
-    def mega_gram(self, block):
-        G = self._need().grams[block]
-        return G.copy(), np.diag(G).copy()
-
-    def mega_end(self):
-        self._need()
-        self._mega = None
-        self.calls.append("mega_end")
 
 
 # ---- fixed inputs shared by tests/test_megatrait_host.py and tests/test_gpu_megatrait.py ------------------------------------------------

@@ -23,7 +23,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from liability_reference import philox4x32_10  # noqa: E402
-from mega_reference import SweepResult, apply_changes, gram_block  # noqa: E402,F401
+from mega_reference import BlockStandInEngine, SweepResult, apply_changes, gram_block  # noqa: E402,F401
 
 MTJ_TAG, SLOT_U, SLOT_Z = 0x05000000, 14, 15
 MIN_TRAITS, MAX_TRAITS, MAX_BLOCK = 5, 8, 256
@@ -254,78 +254,20 @@ def propagated_bound(X, R0, alpha0, beta0, delta0, res, *, iteration, seed, Rinv
     return err
 
 
-class MtjStandInEngine:
+class MtjStandInEngine(BlockStandInEngine):
     """The mtj_* methods of HipEngine (and the little else the joint driver calls) on the restatement above."""
-
-    def __init__(self, precision=64):
-        self.precision = int(precision)
-        self.dtype = np.float64 if precision == 64 else np.float32
-        self.n = self.p = 0
-        self._mtj = None
-        self.X = self.Xout = None
-        self.calls = []
-
-    def close(self):
-        pass
-
-    def load_dense(self, X):
-        X = np.asarray(X)
-        if X.dtype != self.dtype:
-            raise TypeError(f"this engine stores {np.dtype(self.dtype).name} genotypes")
-        self.X = X.astype(np.float64)
-        self.n, self.p = X.shape
-        self._mtj = None
-        self.calls.append("load_dense")
-
-    def load_output_dense(self, X_out):
-        X_out = np.asarray(X_out)
-        if X_out.dtype != self.dtype:
-            raise TypeError(f"this engine stores {np.dtype(self.dtype).name} genotypes")
-        self.Xout = X_out.astype(np.float64)
-        self.n_out = X_out.shape[0]
-
-    def _need(self):
-        if self._mtj is None:
-            raise ValueError("mtj_begin has not been called")
-        return self._mtj
+    KIND = "mtj"
+    mtj_set_residual, mtj_get_residual = BlockStandInEngine._set_residual, BlockStandInEngine._get_residual
+    mtj_set_state, mtj_get_state = BlockStandInEngine._set_state, BlockStandInEngine._get_state
+    mtj_accumulate, mtj_posterior = BlockStandInEngine._accumulate, BlockStandInEngine._posterior
+    mtj_mul_alpha, mtj_gram, mtj_end = BlockStandInEngine._mul_alpha, BlockStandInEngine._gram, BlockStandInEngine._finish
 
     def mtj_begin(self, ntraits, block_size=64):
         if self.p == 0:
             raise ValueError("no genotype matrix loaded")
         if not MIN_TRAITS <= int(ntraits) <= MAX_TRAITS or not 0 <= int(block_size) <= MAX_BLOCK:
             raise ValueError("the number of traits must be in [5,8] and the block size in [1,256]")
-        T, bs = int(ntraits), int(block_size) or 64
-        self._mtj = SweepResult(T=T, bs=bs, R=np.zeros((T, self.n)), alpha=np.zeros((T, self.p)), beta=np.zeros((T, self.p)),
-                                delta=np.ones((T, self.p)), acc=[np.zeros((T, self.p)) for _ in range(3)],
-                                grams=[gram_block(self.X, j0, min(bs, self.p - j0)) for j0 in range(0, self.p, bs)])
-        self.calls.append("mtj_begin")
-
-    def mtj_set_residual(self, R):
-        s = self._need()
-        R = np.asarray(R, dtype=np.float64)
-        if R.shape != (s.T, self.n) or not np.all(np.isfinite(R)):
-            raise ValueError("the residual must be finite and T x n")
-        s.R[...] = R
-
-    def mtj_get_residual(self):
-        return self._need().R.copy()
-
-    def mtj_set_state(self, alpha=None, beta=None, delta=None):
-        s = self._need()
-        for name, a in (("alpha", alpha), ("beta", beta), ("delta", delta)):
-            if a is not None:
-                a = np.asarray(a, dtype=np.float64)
-                if a.shape != (s.T, self.p) or not np.all(np.isfinite(a)):
-                    raise ValueError("state arrays must be finite and T x p")
-                s[name][...] = a
-
-    def mtj_get_state(self):
-        s = self._need()
-        return s.alpha.copy(), s.beta.copy(), s.delta.copy()
-
-    def mtj_gram(self, block):
-        G = self._need().grams[block]
-        return G.copy(), np.diag(G).copy()
+        self._open(int(ntraits), int(block_size) or 64)
 
     def mtj_sweep(self, *, iteration, seed, rinv, ginv, log_pi, min_margin=0.0):
         s = self._need()
@@ -338,22 +280,6 @@ class MtjStandInEngine:
                 raise ValueError("rinv and ginv must be finite and positive definite")
         return sweep_blocked(self.X, s.R, s.alpha, s.beta, s.delta, block_size=s.bs, iteration=iteration, seed=seed, Rinv=rinv, Ginv=ginv, log_pi=lp,
                              min_margin=min_margin, grams=s.grams)
-
-    def mtj_accumulate(self, nsamples):
-        s = self._need()
-        for acc, v in zip(s.acc, (s.alpha, s.alpha * s.alpha, s.delta)):
-            acc += (v - acc) / nsamples
-
-    def mtj_posterior(self, trait):
-        return tuple(a[int(trait)].copy() for a in self._need().acc)
-
-    def mtj_mul_alpha(self, trait, output_rows=False):
-        return (self.Xout if output_rows else self.X) @ self._need().alpha[int(trait)]
-
-    def mtj_end(self):
-        self._need()
-        self._mtj = None
-        self.calls.append("mtj_end")
 
 
 # ---- fixed inputs shared by tests/test_mtj_host.py and tests/test_gpu_mtj.py ----------------------------------------------------------------

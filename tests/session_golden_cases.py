@@ -1,7 +1,8 @@
 """The replayed calls behind tests/golden/session_golden.json: one small run of every device session (liabilities, location
 parameters, missing traits, annotation priors, structural equation models), each in a Float32 and a Float64 context -- and, as
 BLOCK_CASES behind tests/golden/block_session_golden.json, of the sessions that sweep blocks of markers themselves (mega-trait models,
-several BayesR chains, random regression, GBLUP) -- and, as OUTPUT_CASES behind tests/golden/output_side_golden.json, of the output side
+several BayesR chains, random regression, GBLUP) -- and, as MTJ_CASES behind tests/golden/mtj_session_golden.json, of the joint multi-trait
+session with 5 and 8 traits -- and, as OUTPUT_CASES behind tests/golden/output_side_golden.json, of the output side
 of a context: state, residual and posterior transfer, X alpha on training and output rows, sparse samples, window sums, the GWAS session,
 marker covariances, in both precisions and on packed storage, with their guards.
 
@@ -356,6 +357,63 @@ def _mega(precision, rec):
         rec.sharded(hip, hip.mega_begin, T, 64, 3)
     finally:
         hip.close()
+
+
+# joint multi-trait (tests/golden/mtj_session_golden.json): t = 5 or 8, full Rinv and Ginv with dyadic entries, a Pi table over the 2^t
+# joint states with some states of probability 0, 900 output rows (the row buffer grows); then a session of one 150-marker block; then
+# the refusals that only the bare C ABI reaches
+def _mtj(T):
+    def run(precision, rec):
+        n, p = 700, 150
+        hip, rng = _genotypes(precision, n, p, rec, 1111)
+        try:
+            Xout = np.asfortranarray(rng.integers(0, 3, (900, p)).astype(hip.dtype))
+            R0 = rng.standard_normal((T, n)) * 1.3 + 0.2
+            log_pi = -rng.uniform(0.5, 6.0, 1 << T)
+            log_pi[np.arange(1 << T) % 5 == 3] = -np.inf
+            rec.given(Xout, R0, log_pi)
+            rinv = np.diag(1.0 + 0.125 * np.arange(T)) + 0.0625
+            ginv = np.diag(16.0 + 2.0 * np.arange(T)) - 0.5
+            kw = dict(seed=61, rinv=rinv, ginv=ginv, log_pi=log_pi)
+            hip.load_output_dense(Xout)
+            hip.mtj_begin(T, block_size=64)
+            hip.mtj_set_residual(R0)
+            for it in (1, 2, 3):
+                _stats(rec, f"sweep{it}", hip.mtj_sweep(iteration=it, **kw))
+                hip.mtj_accumulate(it)
+            _state(rec, "", hip.mtj_get_state())
+            rec.large("residual", hip.mtj_get_residual())
+            for k in range(T):
+                for nm, v in zip(("mean", "mean2", "freq"), hip.mtj_posterior(k)):
+                    rec.large(f"posterior{k}_{nm}", v)
+            G, xpx = hip.mtj_gram(2)
+            rec.large("gram2", G)
+            rec.large("xpx2", xpx)
+            rec.large(f"mul_alpha{T - 1}", hip.mtj_mul_alpha(T - 1))
+            rec.large("mul_alpha0_output_rows", hip.mtj_mul_alpha(0, output_rows=True))
+            hip.mtj_begin(T, block_size=200)
+            hip.mtj_set_residual(R0)
+            _stats(rec, "one_block", hip.mtj_sweep(iteration=1, **kw))
+            _state(rec, "one_block_", hip.mtj_get_state())
+            rec.large("one_block_residual", hip.mtj_get_residual())
+            # the refusals of the bare ABI (the session stays open: each is refused before anything is dropped)
+            B = [np.zeros(max(n, p)) for _ in range(3)]
+            bad = R0[0].copy()
+            bad[n - 1] = np.inf
+            _raw(hip, rec, "jwas_hip_mtj_get_residual", T, B[0])
+            _raw(hip, rec, "jwas_hip_mtj_posterior", -1, B[0], B[1], B[2])
+            _raw(hip, rec, "jwas_hip_mtj_gram", 0, 150 * 150 - 1, np.zeros(150 * 150), None)
+            _raw(hip, rec, "jwas_hip_mtj_set_residual", 0, bad)
+            _raw(hip, rec, "jwas_hip_mtj_begin", 4, 64)
+            _raw(hip, rec, "jwas_hip_mtj_begin", 9, 64)
+            _raw(hip, rec, "jwas_hip_mtj_begin", T, 257)
+            rec.large("residual_after_refusals", hip.mtj_get_residual())
+            hip.mtj_end()
+            rec.error(hip.mtj_posterior, 0)
+            rec.sharded(hip, hip.mtj_begin, T, 64)
+        finally:
+            hip.close()
+    return run
 
 
 # K = 3 BayesR chains of one model: pi differs per chain, class 3 has probability 0 in chain 1
@@ -745,11 +803,13 @@ def output_keys():
     return [(name, prec) for name in OUTPUT_CASES for prec in PRECISIONS if prec == 32 or name not in OUTPUT_F32_ONLY]
 
 
+MTJ_CASES = ("mtj_t5", "mtj_t8")
+MTJ_GUARDS = 7                           # the raw refusals of a record of MTJ_CASES, before the two that every session records
 BLOCK_CASES = ("mega", "mega_chains", "rrm_c2", "rrm_c3", "rrm_c4", "gblup_t1", "gblup_t3_joint", "gblup_t3_diag")
 
 _RUN = {"liability": _liability, "locpar": _locpar, "mtmiss": _mtmiss, "sem": _sem,
         "annot_BayesC": _annot("BayesC"), "annot_BayesR": _annot("BayesR"), "annot_tree": _annot("tree"),
-        "mega": _mega, "mega_chains": _mega_chains, "rrm_c2": _rrm(2), "rrm_c3": _rrm(3), "rrm_c4": _rrm(4),
+        "mega": _mega, "mtj_t5": _mtj(5), "mtj_t8": _mtj(8), "mega_chains": _mega_chains, "rrm_c2": _rrm(2), "rrm_c3": _rrm(3), "rrm_c4": _rrm(4),
         "gblup_t1": _gblup(1, True, 0), "gblup_t3_joint": _gblup(3, False, 0), "gblup_t3_diag": _gblup(3, True, 1),
         "out_BayesC": _out_context("BayesC", 1), "out_MTBayesC": _out_context("MTBayesC", 3), "out_BayesR": _out_context("BayesR", 1),
         "out_windows": _out_windows, "out_gwas": _out_gwas, "out_markercov_t2": _out_markercov("MTBayesB", 2),

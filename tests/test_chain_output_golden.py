@@ -6,7 +6,11 @@ parent commit's drivers produced for the runs of tests/chain_output_cases.py on 
 tests/golden/make_chain_output_golden.py): the names and SHA-256 digests of every file in the output folder, every returned table
 (its columns and the repr of every Estimate / SD / EBV / PEV / Model_Frequency: short columns in full, longer ones as the SHA-256
 of their reprs), the keys of _timing and everything printed.  The
-replay must be EQUAL: there is no tolerance, the reference is the parent's own output."""
+replay must be EQUAL: there is no tolerance, the reference is the parent's own output.
+
+tests/golden/session_driver_golden.json holds the same for C.SESSION_DRIVER_CASES -- megatrait.run_megatrait with output rows and missing
+cells, mtjoint.run_mtjoint and chains.run_chains -- written by the parent of the commit that gave those three drivers one copy of their
+record alignment, engine set-up and outputs (jwas.jl_amd/session_driver.py)."""
 import json
 import os
 import re
@@ -58,10 +62,32 @@ def test_fixture_covers_every_case(golden):
     assert samples == known, f"files of a family the list above does not name: {sorted(samples - known)}"
 
 
+@pytest.fixture(scope="module")
+def driver_golden():
+    with open(os.path.join(ROOT, "tests", "golden", "session_driver_golden.json")) as fh:
+        return json.load(fh)
+
+
+def test_session_driver_fixture_covers_every_case(driver_golden):
+    assert sorted(driver_golden["cases"]) == sorted(C.SESSION_DRIVER_CASES)
+    assert len(driver_golden["commit"]) == 40 and driver_golden["numpy"]
+    for name, rec in driver_golden["cases"].items():                     # (every run wrote its samples and its tables)
+        assert any("MCMC_samples_" in f for f in rec["sha256"]) and rec["tables"], name
+
+
 @pytest.mark.parametrize("name", C.CASES)
 def test_driver_output_is_the_parent_commits_byte_for_byte(golden, name, tmp_path):
+    _replay(golden, name, tmp_path, C.CASES)
+
+
+@pytest.mark.parametrize("name", C.SESSION_DRIVER_CASES)
+def test_session_driver_output_is_the_parent_commits_byte_for_byte(driver_golden, name, tmp_path):
+    _replay(driver_golden, name, tmp_path, C.SESSION_DRIVER_CASES)
+
+
+def _replay(golden, name, tmp_path, cases):
     want = golden["cases"][name]
-    got = C.run_case(name, tmp_path)
+    got = C.run_case(name, tmp_path, cases)
     assert got["inputs"] == want["inputs"], (f"the generated inputs differ from the fixture's (the data generators under numpy "
                                              f"{np.__version__}, fixture written under {golden['numpy']}; not the drivers)")
     assert sorted(got["sha256"]) == sorted(want["sha256"])               # the files of the output folder

@@ -12,7 +12,11 @@ device helpers (csrc/device_util.hpp), marker state (csrc/marker_state.hpp) and 
 
 tests/golden/output_side_golden.json does it for the output side of a context (G.OUTPUT_CASES: state, residual and posterior transfer,
 X alpha, output rows, sparse samples, window sums, the GWAS session, marker covariances, and their guards): written by the parent of the
-commit that gave the Float32 and Float64 halves of that surface one kernel and one host body each (csrc/output.hpp, csrc/output.hip)."""
+commit that gave the Float32 and Float64 halves of that surface one kernel and one host body each (csrc/output.hpp, csrc/output.hip).
+
+tests/golden/mtj_session_golden.json does it for the joint multi-trait session at 5 and 8 traits (G.MTJ_CASES), with the refusals that
+only the bare C ABI reaches: written by the parent of the commit that gave that session and the mega-trait session one host body
+(csrc/block_session.hpp)."""
 import json
 import os
 
@@ -66,6 +70,30 @@ def test_session_is_the_parent_commits_bit_for_bit(golden, block_golden, name, p
         assert got["digests"][key] == want["digests"][key], key
     assert got["errors"] == want["errors"]
     assert len(got["errors"]) == (2 if precision == 32 else 1) and all(code != 0 and msg for code, msg in got["errors"])
+
+
+@pytest.fixture(scope="module")
+def mtj_golden():
+    return _load("mtj_session_golden.json")
+
+
+def test_mtj_fixture_covers_every_case(mtj_golden):
+    _covers(mtj_golden, G.MTJ_CASES)
+
+
+@pytest.mark.parametrize("precision", G.PRECISIONS)
+@pytest.mark.parametrize("name", G.MTJ_CASES)
+def test_mtj_session_is_the_parent_commits_bit_for_bit(mtj_golden, name, precision):
+    want = mtj_golden["cases"][f"{name}/{precision}"]
+    got = G.run_case(name, precision)
+    assert got["inputs"] == want["inputs"], "the generated inputs differ from the fixture's (numpy's generator, not the library)"
+    assert sorted(got["values"]) == sorted(want["values"]) and sorted(got["digests"]) == sorted(want["digests"])
+    for key in sorted(want["values"]):
+        assert got["values"][key] == want["values"][key], (key, got["values"][key], want["values"][key])
+    for key in sorted(want["digests"]):
+        assert got["digests"][key] == want["digests"][key], key
+    assert got["errors"] == want["errors"]
+    assert len(got["errors"]) == G.MTJ_GUARDS + (2 if precision == 32 else 1) and all(code != 0 and msg for code, msg in got["errors"])
 
 
 @pytest.fixture(scope="module")
