@@ -24,7 +24,7 @@ needs() {      # does unit $1 have to be compiled?
     local ctx="ctx.hpp device_util.hpp rng.hpp"      # ctx.hpp and what it includes
     local sweep="kernels.hpp rng.hpp sweep.hpp update_role.hpp sampler_common.hpp sampler_st.hpp sampler_mt.hpp step_launch.hpp"
     case $1 in
-        jwas_hip)  deps="$deps $ctx $sweep f64_path.hpp output.hpp" ;;
+        jwas_hip)  deps="$deps $ctx $sweep f64_path.hpp output.hpp sweep_plan.hpp" ;;
         output)    deps="$deps $ctx kernels.hpp rng.hpp output.hpp" ;;
         session_rrm) deps="$deps $ctx marker_state.hpp rrm.hpp" ;;
         session_mega) deps="$deps $ctx marker_state.hpp block_session.hpp mega.hpp" ;;

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace jw { struct Events; struct DevParams; }          // kernels.hpp   (the sweep's: jwas_hip.hip only)
@@ -398,6 +399,18 @@ static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * 
 // f(T{}) with T the context's element type: one launch of k<T> instead of a float / double pair
 template <class F>
 static void with_real(jwas_hip_ctx* c, F&& f) { if (IS_F64(c)) f(double{}); else f(float{}); }
+
+// f(std::integral_constant<int, NT>{}) with NT = t, a context's number of traits: one launch of k<NT> instead of a ladder over t.
+// jwas_hip_init_state admits 1 .. JWAS_HIP_MAX_TRAITS and nothing else reaches a sweep.
+template <class F>
+static void with_traits(int t, F&& f)
+{
+    static_assert(JWAS_HIP_MAX_TRAITS == 4, "one arm per number of traits");
+    if (t == 1) f(std::integral_constant<int, 1>{});
+    else if (t == 2) f(std::integral_constant<int, 2>{});
+    else if (t == 3) f(std::integral_constant<int, 3>{});
+    else if (t == 4) f(std::integral_constant<int, 4>{});
+}
 
 // the context's half of element type T (double: of a Float64 context only)
 template <class T> static inline Side<T>& side(jwas_hip_ctx* c);

@@ -8,6 +8,7 @@
 #include "output.hpp"      // (with_cols: the view of the Float32 storage)
 #include "f64_path.hpp"
 #include "step_launch.hpp"
+#include "sweep_plan.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -954,8 +955,6 @@ int jwas_hip_residual_add_scalar(jwas_hip_ctx* c, int32_t trait, double shift)
 
 // ---- the sweep --------------------------------------------------------------------------------------
 // The step kernel's instantiations live in one translation unit per sampler family (step_launch.hpp).
-static inline bool bs_is_dense_big(int bs) { return bs == 256 || bs == 512; }
-
 static StepLaunch step_launch_of(const jwas_hip_ctx* c)
 {
     StepLaunch L;
@@ -985,60 +984,6 @@ static int upload_vec(jwas_hip_ctx* c, DevOwner* owner, void** dev, const void* 
 {
     if (!*dev) HIPCHK(c, owner ? owner->alloc(dev, bytes) : hipMalloc(dev, bytes));
     HIPCHK(c, hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, c->stream));
-    return JWAS_HIP_OK;
-}
-
-// Independent-block sweep (BayesABC_block_independent!, BayesABC.jl:190-255): all block RHS from the residual
-// snapshot (one pass over X), all blocks sampled concurrently, change lists compacted in (block, marker) order;
-// the caller's k_finish applies them to the residual.
-static int sweep_independent(jwas_hip_ctx* c, EventList* out, bool dense, int dense_big_off, int compact_off, int nreps)
-{
-    const int t = c->ntraits, bs = c->block_size;
-    const int64_t nb = c->nblocks;
-    NEED(c, nb <= 65535, JWAS_HIP_EUNSUP, "independent blocks: at most 65535 blocks (got %lld)", (long long)nb);
-    NEED(c, !c->row_mode, JWAS_HIP_EUNSUP, "independent blocks are not available on row shards");
-    const int64_t pstride = (int64_t)t * c->nrg * bs;
-    if (!c->ev_all || c->ind_traits != t) {
-        (void)hipFree(c->ipartials); (void)hipFree(c->ev_all); (void)hipFree(c->ev_offs); (void)hipFree(c->idx_all); (void)hipFree(c->delta_all);
-        c->ipartials = nullptr; c->ev_all = nullptr; c->ev_offs = nullptr; c->idx_all = nullptr; c->delta_all = nullptr;
-        HIPCHK(c, hipMalloc(&c->ipartials, sizeof(double) * (size_t)nb * pstride));
-        HIPCHK(c, hipMalloc(&c->ev_all, sizeof(Events) * (size_t)nb));
-        HIPCHK(c, hipMalloc(&c->ev_offs, sizeof(int32_t) * (size_t)(nb + 1)));
-        HIPCHK(c, hipMalloc(&c->idx_all, sizeof(int32_t) * (size_t)c->p));
-        HIPCHK(c, hipMalloc(&c->delta_all, sizeof(float) * (size_t)kMaxT * c->p));
-        c->ind_traits = t;
-    }
-    HIPCHK(c, hipMemsetAsync(c->corr, 0, sizeof(float) * 2 * kMaxT * (size_t)bs, c->stream));   // corr_in = 0 for every block
-    UpdateArgs U;
-    std::memset(&U, 0, sizeof U);
-    U.r_in = c->r; U.r_out = nullptr;
-    U.ev = &c->ev[0];                               // count zeroed by the caller: nothing to apply
-    U.nslices = c->upd_nslices; U.nrg = c->nrg; U.ncg = c->ncg; U.spg = c->spg;
-    U.partials = c->ipartials; U.bstride = bs;
-    SamplerArgs S;
-    std::memset(&S, 0, sizeof S);
-    S.P = c->dparams; S.partials = c->ipartials; S.nrg = c->nrg; S.bstride = bs;
-    S.p = c->p; S.bsz = bs; S.xpx = c->xpx; S.gram = c->gram;
-    S.cross_next = c->gram; S.b_next = 0; S.corr_in = c->corr; S.corr_out = c->corr + (size_t)kMaxT * bs;
-    S.prep_d = c->prep_d; S.prep_f = c->prep_f; S.mt2_tab = c->mt2_tab; S.lpr_mat = c->lpr_active ? c->lpr_mat : nullptr;
-    S.ginv_mat = has_marker_cov(c->method) ? c->ginv_mat : nullptr;
-    S.alpha = c->alpha; S.beta = c->beta; S.delta = c->delta;
-    S.counters = c->counters;
-    S.dense_big_off = dense_big_off;
-    S.compact_off = compact_off; S.nreps = nreps;
-    hipError_t e;
-    const StepLaunch L = step_launch_of(c);
-    switch (c->method) {
-        case JWAS_HIP_BAYESC: case JWAS_HIP_BAYESB: case JWAS_HIP_BAYESR: e = launch_indep_st(L, c->method, U, S, pstride, dense); break;
-        case JWAS_HIP_MTBAYESC2: e = launch_indep_mt2(L, t, U, S, pstride); break;
-        case JWAS_HIP_MEGABAYESC: e = launch_indep_mega(L, t, U, S, pstride); break;
-        default: e = launch_indep_mtc1(L, t, U, S, pstride);
-    }
-    HIPCHK(c, e);
-    hipLaunchKernelGGL(k_indep_scan, dim3(1), dim3(1024), 0, c->stream, c->ev_all, (int)nb, c->ev_offs, c->ev_offs + nb);
-    hipLaunchKernelGGL(k_indep_gather, dim3((unsigned)nb), dim3(256), 0, c->stream, c->ev_all, c->ev_offs, t, c->idx_all, c->delta_all, c->p);
-    HIPCHK(c, hipGetLastError());
-    *out = EventList{c->ev_offs + nb, c->idx_all, c->delta_all, c->p};
     return JWAS_HIP_OK;
 }
 
@@ -1232,8 +1177,82 @@ int jwas_hip_set_kernel_timing(jwas_hip_ctx* c, int32_t stride)
 
 }  // extern "C"
 
-// Everything of a sweep up to the marker statistics, enqueued on the context's stream (no host synchronisation).
-static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* ntimed_out, double* timed_bytes_out)
+// ---- the sweep's host side ----------------------------------------------------------------------------------------------------------
+// sweep_enqueue is a sequence of stages: sweep_fill_params (checks, DevParams), plan_sweep (sweep_plan.hpp: every schedule decision, a
+// pure function of the context, the parameters and the JWAS_HIP_* switches), sweep_prepare, one of sweep_independent / sweep_grouped /
+// sweep_lookahead, sweep_finish.  Nothing here waits for the device.
+
+// The part of a sweep's parameter fill that a Float32 context (D = DevParams, R = float) and a Float64 context (jw64::Params64,
+// double) share verbatim.  What differs stays with the two callers: the order of the refusals around a joint prior matrix, the limits
+// on the block size, and where lpr_mat travels.
+template <class D, class R>
+struct PriorFill {
+    bool use_pi_vec = false, use_pi_mat = false, use_lpr = false;
+
+    // An open annotation session (jwas_hip_annot_begin): its resident table stands in for the prior pointer, which must be NULL.  Then
+    // d := 0, the method, the RNG counter's words and the two covariance matrices as this width takes them.
+    int begin(jwas_hip_ctx* c, const jwas_sweep_params* P, const R* vare, const R* var_effect, D& d)
+    {
+        NEED(c, !(c->an.active && (P->pi_vec || P->pi_matrix || P->log_prior_states_matrix)), JWAS_HIP_EINVAL,
+             "an annotation session is open: the sweep reads its resident prior table, pi_vec / pi_matrix / log_prior_states_matrix must be NULL");
+        use_pi_vec = P->pi_vec || (c->an.active && c->an.kind == jwa::kBayesC);
+        use_pi_mat = P->pi_matrix || (c->an.active && c->an.kind == jwa::kBayesR);
+        use_lpr = P->log_prior_states_matrix || (c->an.active && c->an.kind == jwa::kTree);
+        const int t = c->ntraits;
+        std::memset(&d, 0, sizeof d);
+        d.method = c->method; d.ntraits = t; d.nreps = P->nreps;
+        d.iter = P->iteration; d.seed_lo = (uint32_t)P->seed; d.seed_hi = (uint32_t)(P->seed >> 32); d.marker0 = P->marker_offset;
+        for (int i = 0; i < t * t; ++i) { d.vare[i] = vare[i]; d.var_effect[i] = var_effect[i]; }
+        return JWAS_HIP_OK;
+    }
+
+    // the unconstrained multi-trait samplers: inv(vare), inv(G) (MTBayesABC.jl:66-67; inv_small: the oracle's operation order) and log pi
+    // of the joint states
+    int joint(jwas_hip_ctx* c, const jwas_sweep_params* P, D& d) const
+    {
+        const int t = c->ntraits;
+        NEED(c, inv_small(d.vare, t, d.Rinv) == 0, JWAS_HIP_EINVAL, "residual covariance matrix is singular");
+        if (!has_marker_cov(c->method))
+            NEED(c, inv_small(d.var_effect, t, d.Ginv) == 0, JWAS_HIP_EINVAL, "marker effect covariance matrix is singular");
+        bool any_finite = false;
+        for (int i = 0; i < (1 << t); ++i) { d.log_prior[i] = P->log_prior_states[i]; any_finite = any_finite || std::isfinite(d.log_prior[i]); }
+        if (is_sampler2(c->method) && !use_lpr)      // MTBayesABC.jl:190
+            NEED(c, any_finite, JWAS_HIP_EINVAL, "All MTBayesABC sampler II state probabilities are zero or invalid.");
+        return JWAS_HIP_OK;
+    }
+
+    // the single-trait priors.  var_vec: BayesB's per-marker variances as this width takes them (the parameter is called vec_name)
+    int single_trait(jwas_hip_ctx* c, const jwas_sweep_params* P, const R* var_vec, const char* vec_name, D& d) const
+    {
+        if (c->method == JWAS_HIP_BAYESR) {
+            // bayesr_validate_priors / sigmaSq check (BayesR.jl:9-20,50)
+            NEED(c, d.var_effect[0] > (R)0, JWAS_HIP_EINVAL, "BayesR sigmaSq must be positive.");
+            if (!use_pi_mat) {
+                double s = 0.0;
+                for (int k = 0; k < 4; ++k) { NEED(c, P->pi_classes[k] >= 0.0, JWAS_HIP_EINVAL, "BayesR pi entries must be nonnegative."); s += P->pi_classes[k]; }
+                NEED(c, std::fabs(s - 1.0) <= 1e-8, JWAS_HIP_EINVAL, "BayesR pi must sum to 1.");
+            }
+            for (int k = 0; k < 4; ++k) { d.pi4[k] = P->pi_classes[k]; d.gamma[k] = P->gamma[k]; }
+            if (P->pi_matrix) { int rc = upload_vec(c, nullptr, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; }
+            if (use_pi_mat) d.pi_mat = c->pi_mat;
+        } else if (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) {
+            d.pi = P->pi;
+            if (P->pi_vec) { int rc = upload_vec(c, nullptr, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; }
+            if (use_pi_vec) d.pi_vec = c->pi_vec;
+            if (c->method == JWAS_HIP_BAYESB) {
+                Side<R>& S = side<R>(c);
+                NEED(c, var_vec, JWAS_HIP_EINVAL, "BayesB needs per-marker effect variances (%s)", vec_name);
+                int rc = upload_vec(c, &S.chain_mem, (void**)&S.var_vec, var_vec, sizeof(R) * c->p); if (rc) return rc;
+                d.var_vec = S.var_vec;
+            } else NEED(c, d.var_effect[0] > (R)0, JWAS_HIP_EINVAL, "marker effect variance must be positive");
+        }
+        return JWAS_HIP_OK;
+    }
+};
+
+// The checks of jwas_sweep_params, DevParams, the uploads it points to; then the sweep's first work on the stream: D, the zeroed change
+// list and counters, the start event.
+static int sweep_fill_params(jwas_hip_ctx* c, const jwas_sweep_params* P, PriorFill<DevParams, float>* fill)
 {
     NEED(c, c && P, JWAS_HIP_EINVAL, "NULL argument");
     NEED(c, c->method >= 0, JWAS_HIP_ESTATE, "jwas_hip_init_state has not been called");
@@ -1242,20 +1261,10 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
          "sweep method/ntraits (%d/%d) differ from init_state (%d/%d)", P->method, P->ntraits, c->method, c->ntraits);
     const int t = c->ntraits;
     HIPCHK(c, hipSetDevice(c->device));
-    // an open annotation session (jwas_hip_annot_begin): its resident table stands in for the prior pointer, which must be NULL
-    NEED(c, !(c->an.active && (P->pi_vec || P->pi_matrix || P->log_prior_states_matrix)), JWAS_HIP_EINVAL,
-         "an annotation session is open: the sweep reads its resident prior table, pi_vec / pi_matrix / log_prior_states_matrix must be NULL");
-    const bool use_pi_vec = P->pi_vec || (c->an.active && c->an.kind == jwa::kBayesC);
-    const bool use_pi_mat = P->pi_matrix || (c->an.active && c->an.kind == jwa::kBayesR);
-    const bool use_lpr = P->log_prior_states_matrix || (c->an.active && c->an.kind == jwa::kTree);
-
     DevParams D;
-    c->lpr_active = is_mt_method(c->method) && !is_mega(c->method) && !has_marker_cov(c->method) && use_lpr;
-    std::memset(&D, 0, sizeof D);
-    D.method = c->method; D.ntraits = t; D.nreps = P->nreps;
-    D.iter = P->iteration; D.seed_lo = (uint32_t)P->seed; D.seed_hi = (uint32_t)(P->seed >> 32); D.marker0 = P->marker_offset;
-    for (int i = 0; i < t * t; ++i) { D.vare[i] = P->vare[i]; D.var_effect[i] = P->var_effect[i]; }
-    const bool marker_cov = has_marker_cov(c->method);
+    if (int rc = fill->begin(c, P, P->vare, P->var_effect, D)) return rc;
+    const bool use_lpr = fill->use_lpr, marker_cov = has_marker_cov(c->method);
+    c->lpr_active = is_mt_method(c->method) && !is_mega(c->method) && !marker_cov && use_lpr;
     if (marker_cov) {
         // multi-trait BayesA/B: one effect covariance per marker (locus_effect_variances, MTBayesABC.jl:66; with
         // constraint = true its diagonal, BayesABC.jl:5); inverted on the device by k_prepare (the constrained form keeps the
@@ -1271,13 +1280,7 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
         for (int i = 0; i < t * t; ++i) D.Ginv[i] = (i / t == i % t) ? 1.f : 0.f;       // (unused)
     }
     if (is_mt_method(c->method) && !is_mega(c->method)) {
-        NEED(c, inv_small(P->vare, t, D.Rinv) == 0, JWAS_HIP_EINVAL, "residual covariance matrix is singular");
-        if (!marker_cov)
-            NEED(c, inv_small(P->var_effect, t, D.Ginv) == 0, JWAS_HIP_EINVAL, "marker effect covariance matrix is singular");
-        bool any_finite = false;
-        for (int i = 0; i < (1 << t); ++i) { D.log_prior[i] = P->log_prior_states[i]; any_finite = any_finite || std::isfinite(D.log_prior[i]); }
-        if ((c->method == JWAS_HIP_MTBAYESC2 || c->method == JWAS_HIP_MTBAYESB2) && !use_lpr)      // MTBayesABC.jl:190
-            NEED(c, any_finite, JWAS_HIP_EINVAL, "All MTBayesABC sampler II state probabilities are zero or invalid.");
+        if (int rc = fill->joint(c, P, D)) return rc;
         if (use_lpr) {          // MarkerSpecificPiPrior (MTBayesABC.jl:22-47)
             NEED(c, t == 2, JWAS_HIP_EUNSUP, "marker-specific joint priors support 2 traits (got %d)", t);
             NEED(c, c->block_size <= 512, JWAS_HIP_EUNSUP, "marker-specific joint priors need a block size <= 512 (got %d)", c->block_size);
@@ -1297,377 +1300,398 @@ static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* nt
     } else {
         NEED(c, P->vare[0] > 0.f, JWAS_HIP_EINVAL, "residual variance must be positive");
     }
-    if (c->method == JWAS_HIP_BAYESR) {
-        // bayesr_validate_priors / sigmaSq check (BayesR.jl:9-20,50)
-        NEED(c, P->var_effect[0] > 0.f, JWAS_HIP_EINVAL, "BayesR sigmaSq must be positive.");
-        if (!use_pi_mat) {
-            double s = 0.0;
-            for (int k = 0; k < 4; ++k) { NEED(c, P->pi_classes[k] >= 0.0, JWAS_HIP_EINVAL, "BayesR pi entries must be nonnegative."); s += P->pi_classes[k]; }
-            NEED(c, std::fabs(s - 1.0) <= 1e-8, JWAS_HIP_EINVAL, "BayesR pi must sum to 1.");
-        }
-        for (int k = 0; k < 4; ++k) { D.pi4[k] = P->pi_classes[k]; D.gamma[k] = P->gamma[k]; }
-        if (P->pi_matrix) { int rc = upload_vec(c, nullptr, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; }
-        if (use_pi_mat) D.pi_mat = c->pi_mat;
-    } else if (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) {
-        D.pi = P->pi;
-        if (P->pi_vec) { int rc = upload_vec(c, nullptr, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; }
-        if (use_pi_vec) D.pi_vec = c->pi_vec;
-        if (c->method == JWAS_HIP_BAYESB) {
-            NEED(c, P->var_effect_vec, JWAS_HIP_EINVAL, "BayesB needs per-marker effect variances (var_effect_vec)");
-            int rc = upload_vec(c, &c->chain_mem, (void**)&c->var_vec, P->var_effect_vec, sizeof(float) * c->p); if (rc) return rc;
-            D.var_vec = c->var_vec;
-        } else NEED(c, P->var_effect[0] > 0.f, JWAS_HIP_EINVAL, "marker effect variance must be positive");
-    }
+    if (int rc = fill->single_trait(c, P, P->var_effect_vec, "var_effect_vec", D)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->dparams, &D, sizeof D, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(&c->ev[0].count, 0, sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->counters, 0, sizeof(unsigned long long) * kNCounters, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
+    return JWAS_HIP_OK;
+}
 
-    {   // per-sweep marker constants (draws, prior logs, lhs terms) for all p markers in parallel
-        const dim3 pg((unsigned)((c->p + 255) / 256)), pb(256);
-        switch (c->method) {
-            case JWAS_HIP_BAYESC: hipLaunchKernelGGL((k_prepare<kBayesC, 1>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->alpha, c->prep_d, c->prep_f); break;
-            case JWAS_HIP_BAYESB: hipLaunchKernelGGL((k_prepare<kBayesB, 1>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->alpha, c->prep_d, c->prep_f); break;
-            case JWAS_HIP_BAYESR: hipLaunchKernelGGL((k_prepare<kBayesR, 1>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->alpha, c->prep_d, c->prep_f); break;
-#define JW_MT_PREP(M)                                                                                                                        \
-                if (t == 2) hipLaunchKernelGGL((k_prepare<M, 2>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->alpha, c->prep_d, c->prep_f);          \
-                else if (t == 3) hipLaunchKernelGGL((k_prepare<M, 3>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->alpha, c->prep_d, c->prep_f);     \
-                else hipLaunchKernelGGL((k_prepare<M, 4>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->alpha, c->prep_d, c->prep_f);                 \
-                break;
-            case JWAS_HIP_MTBAYESC2:
-                if (t == 2) hipLaunchKernelGGL((k_prepare_mt2<2>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->mt2_tab);
-                else if (t == 3) hipLaunchKernelGGL((k_prepare_mt2<3>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->mt2_tab);
-                JW_MT_PREP(kMTBayesC2)
-            case JWAS_HIP_MEGABAYESC: JW_MT_PREP(kMegaBayesC)
-            case JWAS_HIP_MTBAYESB1: JW_MT_PREP(kMTBayesB1)
-            case JWAS_HIP_MTBAYESB2: JW_MT_PREP(kMTBayesB2)
-            case JWAS_HIP_MEGABAYESB: JW_MT_PREP(kMegaBayesB)
-            default: JW_MT_PREP(kMTBayesC1)
-#undef JW_MT_PREP
-        }
+static SweepFacts sweep_facts(const jwas_hip_ctx* c, const jwas_sweep_params* P, const PriorFill<DevParams, float>& fill)
+{
+    const auto& SET = c->sets[(size_t)c->set_index];
+    SweepFacts f;
+    f.method = c->method; f.t = c->ntraits; f.multi_trait = is_mt_method(c->method); f.sampler2 = is_sampler2(c->method);
+    f.p = c->p; f.nblocks = c->nblocks; f.bs = c->block_size; f.uniform = c->starts.empty(); f.row_mode = c->row_mode; f.packed = c->packed;
+    f.gm = SET.gm; f.has_gpp = SET.gpp != nullptr; f.has_sync_cnt = c->sync_cnt != nullptr; f.last_events = c->last_events;
+    f.nreps = P->nreps; f.independent_blocks = P->independent_blocks != 0; f.group_launch = P->group_launch != 0;
+    f.section_solve = P->section_solve != 0; f.pi = P->pi;
+    f.use_pi_vec = fill.use_pi_vec; f.use_pi_mat = fill.use_pi_mat; f.use_lpr = fill.use_lpr;
+    return f;
+}
+
+static inline size_t tsec_floats(int t) { return (size_t)(64 * t) * (size_t)(64 * t); }      // one section inverse of Rule T
+
+// Per-sweep marker constants (draws, prior logs, lhs terms) for all p markers in parallel; then what Rule T and the helper workgroup
+// need before the first launch: the hand-over words, and the inverses of all sections of the full blocks (sampler_mt.hpp).
+static int sweep_prepare(jwas_hip_ctx* c, const SweepPlan& pl)
+{
+    const dim3 pg((unsigned)((c->p + 255) / 256)), pb(256);
+    const int t = c->ntraits;
+    const auto prepare = [&](auto method) {
+        constexpr int M = decltype(method)::value;
+        with_traits(t, [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if constexpr (is_mt_method(M) == (NT >= 2)) {
+                if constexpr (M == kMTBayesC2 && NT <= 3) hipLaunchKernelGGL((k_prepare_mt2<NT>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->mt2_tab);
+                hipLaunchKernelGGL((k_prepare<M, NT>), pg, pb, 0, c->stream, c->dparams, c->p, c->xpx, c->alpha, c->prep_d, c->prep_f);
+            }
+        });
+    };
+    using std::integral_constant;
+    switch (c->method) {
+        case JWAS_HIP_BAYESC: prepare(integral_constant<int, kBayesC>{}); break;
+        case JWAS_HIP_BAYESB: prepare(integral_constant<int, kBayesB>{}); break;
+        case JWAS_HIP_BAYESR: prepare(integral_constant<int, kBayesR>{}); break;
+        case JWAS_HIP_MTBAYESC2: prepare(integral_constant<int, kMTBayesC2>{}); break;
+        case JWAS_HIP_MEGABAYESC: prepare(integral_constant<int, kMegaBayesC>{}); break;
+        case JWAS_HIP_MTBAYESB1: prepare(integral_constant<int, kMTBayesB1>{}); break;
+        case JWAS_HIP_MTBAYESB2: prepare(integral_constant<int, kMTBayesB2>{}); break;
+        case JWAS_HIP_MEGABAYESB: prepare(integral_constant<int, kMegaBayesB>{}); break;
+        default: prepare(integral_constant<int, kMTBayesC1>{});
     }
-
-    const int bs = c->block_size;
-    const size_t rstride = (size_t)kMaxT * c->ld;
-    const size_t pstride = (size_t)bs * c->nrg * kMaxT;
-    size_t ntimed = 0;
-    double timed_bytes = 0.0;
-    const int64_t nb = c->nblocks;
-    const bool independent = P->independent_blocks != 0;
-    EventList ev_list{nullptr, nullptr, nullptr, 0};
-    const float* r_last = c->r;
-    // A uniform prior pi = 0 (single-trait BayesA/B/C: RR-BLUP, BayesA, BayesL, the reference's own benchmark setting): the
-    // kernel instantiation whose sampler follows Rule D on every path and takes dense_big_st on full 256- / 512-marker blocks
-    // (sweep.hpp).  Every marker of every block changes, so the update role shares the apply work (COOP) unless told not to.
-    const bool dense_big = (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) && P->pi == 0.0 && !use_pi_vec;
-    // multi-trait sweeps in which most markers changed last time (the reference's default prior: every marker in the model),
-    // single pass over <= 128-marker blocks: the dense-walk-only instantiation of the sampler (sampler_role_mt<.., DW>: the same
-    // chain, a fraction of the code).  JWAS_HIP_DENSE_MT=0|1 overrides (tests: both instantiations give the same bits).
-    const char* edm = std::getenv("JWAS_HIP_DENSE_MT");
-    // (the share of markers that changed in the previous sweep from which the dense walk of 256-marker blocks is taken: it costs one
-    // step per marker IN the model -- markers outside it that stay there take no step since round 6 -- so it pays far below "most markers
-    // change": config 4's chain at 22 000 changes per sweep, 19 ms on the walk against 42 ms through the speculative rounds)
-    static const double dense_mt_fraction = std::getenv("JWAS_HIP_DENSE_MT_FRACTION") ? std::atof(std::getenv("JWAS_HIP_DENSE_MT_FRACTION")) : 0.1;
-    // ... and full 256-marker blocks of sampler I with one shared covariance (dense_big_mt: decided per launch below)
-    const bool dense_mt256 = c->block_size == 256 && (c->method == JWAS_HIP_MTBAYESC1 || c->method == JWAS_HIP_MTBAYESB1) && !use_lpr;
-    const bool dense_mt = is_mt_method(c->method) && !is_sampler2(c->method) && (c->block_size <= 128 || dense_mt256) && P->nreps == 1 && !P->independent_blocks &&
-                          (edm ? std::atoi(edm) != 0 : c->last_events >= (dense_mt256 ? dense_mt_fraction : 0.6) * (double)c->p);
-    const int dense_big_off = std::getenv("JWAS_HIP_DENSE_BIG_OFF") != nullptr ? 1 : 0;      // (tests: the same chain through the general path)
-    // Rule T (jwas_sweep_params.section_solve): the dense chain of a 64-marker section as a mat-vec with the section's inverse,
-    // formed here for all sections of the full blocks in parallel (sampler_mt.hpp).  Multi-trait sampler I with <= 3 traits on uniform
-    // 256-marker blocks; every other sweep ignores the flag (4 traits: the sampler has no solve path, and a helper workgroup waiting
-    // for sections nobody publishes would spin).
-    const int64_t solve_blocks = (P->section_solve && t <= 3 && dense_mt256 && P->nreps == 1 && !independent && c->starts.empty() && !c->row_mode && !dense_big_off)
-                                     ? c->p / 256 : 0;
-    const size_t tsf = (size_t)(64 * t) * (size_t)(64 * t);
-    // dense sweeps hand the next block's lookahead correction to a helper workgroup (corr_helper): multi-trait Rule T blocks, and
-    // single-trait dense_big_st blocks (uniform pi = 0 on full 256- / 512-marker blocks; JWAS_HIP_CORR_HELPER=0: in the sampler)
-    static const int corr_helper_on = std::getenv("JWAS_HIP_CORR_HELPER") ? std::atoi(std::getenv("JWAS_HIP_CORR_HELPER")) : 1;
-    const bool st_helper = corr_helper_on && dense_big && P->nreps == 1 && !independent && !c->row_mode && !dense_big_off && (bs_is_dense_big(c->block_size));
-    if ((solve_blocks > 0 || st_helper) && !c->xch) {
+    if ((pl.solve_blocks > 0 || pl.st_helper) && !c->xch) {
         HIPCHK(c, hipMalloc(&c->xch, sizeof(unsigned long long) * kMaxT * 512));
         HIPCHK(c, hipMemsetAsync(c->xch, 0, sizeof(unsigned long long) * kMaxT * 512, c->stream));
     }
-    if (solve_blocks > 0) {
-        const size_t need = (size_t)solve_blocks * 4 * tsf;
+    if (pl.solve_blocks > 0) {
+        const size_t need = (size_t)pl.solve_blocks * 4 * tsec_floats(t);
         if (c->tsec_cap < need) {
             (void)hipFree(c->tsec); c->tsec = nullptr; c->tsec_cap = 0;
             HIPCHK(c, hipMalloc(&c->tsec, sizeof(float) * need));
             c->tsec_cap = need;
         }
         const StepLaunch L = step_launch_of(c);
-        if (c->method == JWAS_HIP_MTBAYESB1) HIPCHK(c, launch_section_inverse_mtb1(L, t, c->dparams, c->xpx, c->gram, c->ginv_mat, solve_blocks * 4, c->tsec));
-        else HIPCHK(c, launch_section_inverse_mtc1(L, t, c->dparams, c->xpx, c->gram, solve_blocks * 4, c->tsec));
+        if (c->method == JWAS_HIP_MTBAYESB1) HIPCHK(c, launch_section_inverse_mtb1(L, t, c->dparams, c->xpx, c->gram, c->ginv_mat, pl.solve_blocks * 4, c->tsec));
+        else HIPCHK(c, launch_section_inverse_mtc1(L, t, c->dparams, c->xpx, c->gram, pl.solve_blocks * 4, c->tsec));
     }
-    const int compact_off = std::getenv("JWAS_HIP_COMPACT_OFF") != nullptr ? std::atoi(std::getenv("JWAS_HIP_COMPACT_OFF")) : 0;          // (tests: the speculative rounds instead of the compact chain)
-    // GROUPED LAUNCHES (jwas_sweep_params.group_launch; jwas_hip_setup_groups; sweep.hpp k_group_step): gm blocks per launch.
-    // Single-trait single-pass sweeps on uniform blocks; every other sweep ignores the flag.  JWAS_HIP_GROUPS=0 switches it off (then
-    // the chain runs one block per launch: the same trajectory within the oracle's bar, NOT the same bits -- the corrections are
-    // summed in another order; tests/test_gpu_schedule_variants.py).
-    static const int groups_env = std::getenv("JWAS_HIP_GROUPS") ? std::atoi(std::getenv("JWAS_HIP_GROUPS")) : 1;
+    return JWAS_HIP_OK;
+}
+
+// What one of the three paths leaves for sweep_finish and sweep_collect.
+struct SweepRun {
+    EventList ev_list{nullptr, nullptr, nullptr, 0};      // the changes k_finish still has to apply
+    int64_t r_parity = 0;                                 // ... to this residual buffer
+    uint32_t sched = 0;                                   // the JWAS_HIP_SCHED_* bits of the launches
+    size_t ntimed = 0;                                    // event pairs recorded (jwas_hip_set_kernel_timing)
+    double timed_bytes = 0.0;                             // ... and the genotype bytes their launches streamed
+};
+
+// `launch` between the event pair of every timing_stride-th launch that forms partial sums (launch k of nlaunch; b columns of n floats).
+template <class F>
+static int timed_launch(jwas_hip_ctx* c, SweepRun* run, int64_t k, int64_t nlaunch, int b, F&& launch)
+{
+    const bool timed = c->timing_stride > 0 && k < nlaunch && (k % c->timing_stride) == 0;
+    if (timed) {
+        while (c->kev.size() < 2 * (run->ntimed + 1)) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->kev.push_back(e); }
+        HIPCHK(c, hipEventRecord(c->kev[2 * run->ntimed], c->stream));
+    }
+    if (int rc = launch()) return rc;
+    if (timed) {
+        HIPCHK(c, hipEventRecord(c->kev[2 * run->ntimed + 1], c->stream));
+        ++run->ntimed;
+        run->timed_bytes += 4.0 * (double)c->n * (double)b;
+    }
+    return JWAS_HIP_OK;
+}
+
+// The update role's arguments of launch k of a pipelined sweep, which forms the partial sums of columns j0 .. j0 + b (b = 0: the last
+// launch only applies): what the grouped and the lookahead loop set alike.  The residual ping-pongs between the two buffers, and so
+// do the arrival counters of the cooperative apply (coop: this sweep takes it).
+static UpdateArgs update_args(const jwas_hip_ctx* c, const SweepPlan& pl, int64_t k, int64_t j0, int b, bool coop)
+{
+    const size_t rstride = (size_t)kMaxT * c->ld;
+    UpdateArgs U;
+    std::memset(&U, 0, sizeof U);
+    U.r_in = c->r + ((k + 1) & 1) * rstride; U.r_out = c->r + (k & 1) * rstride;
+    U.ev = &c->ev[k & 1];
+    U.j0 = j0; U.b = b;
+    U.nslices = c->upd_nslices; U.nrg = c->nrg; U.spg = c->spg;
+    U.ncg = (b > 0 && c->ncg > b) ? b : c->ncg;
+    U.dbg = c->counters;
+    U.sync_now = coop ? c->sync_cnt + (k & 1) * c->nrg : nullptr;
+    U.sync_next = coop ? c->sync_cnt + ((k + 1) & 1) * c->nrg : nullptr;
+    U.quiet_xcd = pl.quiet_xcd;
+    U.dbg_throttle = pl.dbg_throttle;
+    return U;
+}
+
+// The sampler's arguments that do not depend on the block.  mt_tables: the path runs the multi-trait samplers (their per-marker tables).
+static SamplerArgs sampler_args(const jwas_hip_ctx* c, const jwas_sweep_params* P, const SweepPlan& pl, bool mt_tables)
+{
+    SamplerArgs S;
+    std::memset(&S, 0, sizeof S);
+    S.P = c->dparams; S.nrg = c->nrg; S.p = c->p; S.bsz = c->block_size;
+    S.xpx = c->xpx;
+    S.prep_d = c->prep_d; S.prep_f = c->prep_f;
+    if (mt_tables) {
+        S.mt2_tab = c->mt2_tab; S.lpr_mat = c->lpr_active ? c->lpr_mat : nullptr;
+        S.ginv_mat = has_marker_cov(c->method) ? c->ginv_mat : nullptr;
+    }
+    S.alpha = c->alpha; S.beta = c->beta; S.delta = c->delta;
+    S.counters = c->counters;
+    S.compact_off = pl.compact_off; S.nreps = P->nreps;
+    return S;
+}
+
+// Independent-block sweep (BayesABC_block_independent!, BayesABC.jl:190-255): all block RHS from the residual
+// snapshot (one pass over X), all blocks sampled concurrently, change lists compacted in (block, marker) order;
+// k_finish applies them to the residual.
+static int sweep_independent(jwas_hip_ctx* c, const jwas_sweep_params* P, const SweepPlan& pl, SweepRun* run)
+{
+    const int t = c->ntraits, bs = c->block_size;
+    const int64_t nb = c->nblocks;
+    NEED(c, nb <= 65535, JWAS_HIP_EUNSUP, "independent blocks: at most 65535 blocks (got %lld)", (long long)nb);
+    NEED(c, !c->row_mode, JWAS_HIP_EUNSUP, "independent blocks are not available on row shards");
+    const int64_t pstride = (int64_t)t * c->nrg * bs;
+    if (!c->ev_all || c->ind_traits != t) {
+        (void)hipFree(c->ipartials); (void)hipFree(c->ev_all); (void)hipFree(c->ev_offs); (void)hipFree(c->idx_all); (void)hipFree(c->delta_all);
+        c->ipartials = nullptr; c->ev_all = nullptr; c->ev_offs = nullptr; c->idx_all = nullptr; c->delta_all = nullptr;
+        HIPCHK(c, hipMalloc(&c->ipartials, sizeof(double) * (size_t)nb * pstride));
+        HIPCHK(c, hipMalloc(&c->ev_all, sizeof(Events) * (size_t)nb));
+        HIPCHK(c, hipMalloc(&c->ev_offs, sizeof(int32_t) * (size_t)(nb + 1)));
+        HIPCHK(c, hipMalloc(&c->idx_all, sizeof(int32_t) * (size_t)c->p));
+        HIPCHK(c, hipMalloc(&c->delta_all, sizeof(float) * (size_t)kMaxT * c->p));
+        c->ind_traits = t;
+    }
+    HIPCHK(c, hipMemsetAsync(c->corr, 0, sizeof(float) * 2 * kMaxT * (size_t)bs, c->stream));   // corr_in = 0 for every block
+    UpdateArgs U;
+    std::memset(&U, 0, sizeof U);
+    U.r_in = c->r; U.r_out = nullptr;
+    U.ev = &c->ev[0];                               // count zeroed by sweep_fill_params: nothing to apply
+    U.nslices = c->upd_nslices; U.nrg = c->nrg; U.ncg = c->ncg; U.spg = c->spg;
+    U.partials = c->ipartials; U.bstride = bs;
+    SamplerArgs S = sampler_args(c, P, pl, true);
+    S.partials = c->ipartials; S.bstride = bs;
+    S.gram = c->gram;
+    S.cross_next = c->gram; S.b_next = 0; S.corr_in = c->corr; S.corr_out = c->corr + (size_t)kMaxT * bs;
+    S.dense_big_off = pl.dense_big_off;
+    hipError_t e;
+    const StepLaunch L = step_launch_of(c);
+    switch (c->method) {
+        case JWAS_HIP_BAYESC: case JWAS_HIP_BAYESB: case JWAS_HIP_BAYESR: e = launch_indep_st(L, c->method, U, S, pstride, pl.dense_big); break;
+        case JWAS_HIP_MTBAYESC2: e = launch_indep_mt2(L, t, U, S, pstride); break;
+        case JWAS_HIP_MEGABAYESC: e = launch_indep_mega(L, t, U, S, pstride); break;
+        default: e = launch_indep_mtc1(L, t, U, S, pstride);
+    }
+    HIPCHK(c, e);
+    hipLaunchKernelGGL(k_indep_scan, dim3(1), dim3(1024), 0, c->stream, c->ev_all, (int)nb, c->ev_offs, c->ev_offs + nb);
+    hipLaunchKernelGGL(k_indep_gather, dim3((unsigned)nb), dim3(256), 0, c->stream, c->ev_all, c->ev_offs, t, c->idx_all, c->delta_all, c->p);
+    HIPCHK(c, hipGetLastError());
+    run->ev_list = EventList{c->ev_offs + nb, c->idx_all, c->delta_all, c->p};
+    run->r_parity = 0;
+    return JWAS_HIP_OK;
+}
+
+// Where a grouped sweep keeps what its blocks hand to one another, computed once per sweep.  Corrections (SET.gcbuf, floats):
+// cG [2][gb] | cW [2][bs] at off_w | cP [2 bs] at off_p | zeros [bs] at off_z.  Hand-over words of the ping-pong samplers (SET.gpp):
+// cW [2][bs] | counts [8] | cP part [2 bs] | cP [2 bs] | cG relay [3][m bs].
+struct GroupLayout {
+    int m;                          // blocks per launch
+    int64_t gb, ng;                 // markers per group, groups
+    size_t pstride;                 // partial sums of one group (fits the ping-pong buffers: gm <= kMaxT, one trait)
+    int off_w, off_p, off_z;
+    unsigned long long *pw_cw, *pw_cnt, *pw_ph, *pw_cp, *pw_h;
+    GroupLayout(const jwas_hip_ctx* c, const jwas_hip_ctx::BlockSet& SET)
+        : m(SET.gm), gb((int64_t)m * c->block_size), ng((c->nblocks + m - 1) / m), pstride((size_t)gb * c->nrg),
+          off_w((int)(2 * gb)), off_p(off_w + 2 * c->block_size), off_z(off_p + 2 * c->block_size),
+          pw_cw(SET.gpp), pw_cnt(pw_cw + 2 * (size_t)c->block_size), pw_ph(pw_cnt + 8), pw_cp(pw_ph + 2 * (size_t)c->block_size),
+          pw_h(pw_cp + 2 * (size_t)c->block_size) {}
+};
+
+// The samplers of group gs (launch gs + 1): G and one SamplerArgs per block of the group.
+static void group_samplers(jwas_hip_ctx* c, const jwas_sweep_params* P, const SweepPlan& pl, const GroupLayout& L, int64_t gs, GroupSamplers* SS, GroupArgs* G)
+{
     const auto& SET = c->sets[(size_t)c->set_index];
-    const bool grouped = P->group_launch != 0 && groups_env != 0 && SET.gm >= 2 && !is_mt_method(c->method) && P->nreps == 1 && !independent &&
-                         !c->row_mode && c->starts.empty() && !dense_big;
-    int64_t last_launch = nb;                                   // index of the sweep's last launch
-    // which of the variants below this sweep takes (jwas_hip_last_sweep_schedule): one bit per decision
-    uint32_t sched = (dense_big ? JWAS_HIP_SCHED_DENSE_BIG : 0u) | (solve_blocks > 0 ? JWAS_HIP_SCHED_SECTION_SOLVE : 0u) |
-                     (((uint32_t)compact_off << JWAS_HIP_SCHED_COMPACT_OFF_SHIFT) & JWAS_HIP_SCHED_COMPACT_OFF_MASK);
-    if (independent) {
-        sched |= JWAS_HIP_SCHED_INDEPENDENT;
-        int rc = sweep_independent(c, &ev_list, dense_big, dense_big_off, compact_off, P->nreps);
-        if (rc) return rc;
-    } else if (grouped) {
-        const int m = SET.gm;
-        const int64_t gb = (int64_t)m * bs, ng = (nb + m - 1) / m;
-        const size_t pstride_g = (size_t)gb * c->nrg;           // (fits the ping-pong buffers: gm <= kMaxT, one trait)
-        HIPCHK(c, hipMemcpyAsync(c->r + rstride, c->r, sizeof(float) * (size_t)c->ld, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemsetAsync(&c->ev[1].count, 0, sizeof(int32_t), c->stream));
-        HIPCHK(c, hipMemsetAsync(SET.gcbuf, 0, sizeof(float) * ((size_t)2 * gb + 5 * (size_t)bs), c->stream));   // group 0 has no predecessor
-        // cooperative apply of the merged list (update_role, COOP: the column groups of a row group share the rows instead of every one
-        // of them re-reading the changed columns; taken per launch from 32 changes on) in the high-turnover sweeps -- the ones that run
-        // the ping-pong samplers: config 3 25.0 -> 24.3 ms, fixed pi 25.6 -> 25.1 ms per sweep.  Same bits (the chain per row is the
-        // list's order either way; bounded wait with the redundant apply as its fall-back).  JWAS_HIP_GROUP_COOP=0|1 overrides.
-        // (The switches of this block are read once per process; tests/test_gpu_schedule_variants.py runs every combination of
-        // JWAS_HIP_PINGPONG x JWAS_HIP_GROUP_COOP x JWAS_HIP_QUIET_XCD in a process of its own and compares the bits.)
-        static const int gcoop_env = std::getenv("JWAS_HIP_GROUP_COOP") ? std::atoi(std::getenv("JWAS_HIP_GROUP_COOP")) : -1;
-        const bool gcoop = c->sync_cnt != nullptr && !c->packed &&
-                           (gcoop_env >= 0 ? gcoop_env != 0 : (bs <= 512 || c->last_events < 0 || c->last_events > 0.0125 * (double)c->p));
-        if (gcoop) HIPCHK(c, hipMemsetAsync(c->sync_cnt, 0, sizeof(int) * 2 * c->nrg, c->stream));
-        sched |= JWAS_HIP_SCHED_GROUPED | (gcoop ? JWAS_HIP_SCHED_GROUP_COOP : 0u);
-        const int off_w = (int)(2 * gb), off_p = off_w + 2 * bs, off_z = off_p + 2 * bs;
-        for (int64_t K = 0; K <= ng; ++K) {
-            UpdateArgs U;
-            std::memset(&U, 0, sizeof U);
-            U.r_in = c->r + ((K + 1) & 1) * rstride; U.r_out = c->r + (K & 1) * rstride;
-            U.ev = &c->ev[K & 1];
-            const int32_t* uidx = SET.gidx + (K & 1) * gb;
-            const float* udel = SET.gdelta + (K & 1) * gb;
-            U.j0 = (K < ng) ? K * gb : 0;
-            U.b = (K < ng) ? (int)std::min<int64_t>(gb, c->p - U.j0) : 0;
-            U.nslices = c->upd_nslices; U.nrg = c->nrg; U.spg = c->spg;
-            U.ncg = (U.b > 0 && c->ncg > U.b) ? U.b : c->ncg;
-            U.partials = c->partials + (K & 1) * pstride_g; U.bstride = (int)gb;
-            U.dbg = c->counters;
-            U.sync_now = gcoop ? c->sync_cnt + (K & 1) * c->nrg : nullptr;
-            U.sync_next = gcoop ? c->sync_cnt + ((K + 1) & 1) * c->nrg : nullptr;
-            {
-                static const int qx = std::getenv("JWAS_HIP_QUIET_XCD") ? std::atoi(std::getenv("JWAS_HIP_QUIET_XCD")) : -1;
-                U.quiet_xcd = qx >= 0 ? qx : (c->last_events < 0 || c->last_events > 0.0125 * (double)c->p ? 1 : 0);
-            }
-            GroupSamplers SS;
-            GroupArgs G;
-            std::memset(&SS, 0, sizeof SS);
-            std::memset(&G, 0, sizeof G);
-            G.m = m;
-            // PING-PONG samplers (2 blocks per launch; sweep.hpp): while the sampler chain is the critical path (many changes per
-            // sweep: the regime in which ids = 0 mod 8 do no update work anyway) the pair's second block is sampled by workgroup 8, its
-            // front running beside the first block's chain.  Same chain, same bits; JWAS_HIP_PINGPONG=0|1 overrides (1: also in the
-            // steady state, with the quiet XCD forced on).
-            static const int pp_env = std::getenv("JWAS_HIP_PINGPONG") ? std::atoi(std::getenv("JWAS_HIP_PINGPONG")) : -1;
-            // (blocks of <= 512 markers are only ever grouped for the sampler-bound sweeps: there the mode is on whatever the last sweep's
-            // count was -- the host keeps those sweeps on 512-marker pairs down to 0.9 % turnover, and without it a pair costs 46.9 instead
-            // of 40.2 us at 6 300 changes per sweep)
-            const bool pp_want = SET.gpp != nullptr && (pp_env >= 0 ? pp_env != 0 : (U.quiet_xcd != 0 || bs <= 512));
-            G.pp_kernel = (pp_want || gcoop) ? 1 : 0;            // (constant over the sweep's launches)
-            SS.a[0].bsz = bs;
-            if (K >= 1) {
-                const int64_t gs = K - 1, first = gs * m;
-                const int64_t bb = (int64_t)bs * bs;
-                float* cb = SET.gcbuf;
-                const int off_g_in = (int)((gs & 1) * gb), off_g_out = (int)(((gs + 1) & 1) * gb);
-                G.ns = (int)std::min<int64_t>(m, nb - first);
-                G.j0 = first * bs;
-                if (gs + 1 < ng) {
-                    G.cross_grp = SET.gcross[m == 4 ? 1 : 0] + (size_t)(gs + 1) * gb * gb;
-                    G.bn_grp = (int)std::min<int64_t>(gb, c->p - (gs + 1) * gb);
-                }
-                if (m == 4 && G.ns > 2) {
-                    G.cross_pair = SET.gcross[0] + (size_t)gs * (2 * (size_t)bs) * (2 * (size_t)bs);      // (pair 2 gs + 1, stored at gs)
-                    G.bn_pair = (int)std::min<int64_t>(2 * (int64_t)bs, c->p - (first + 2) * bs);
-                }
-                G.corr_g_out = cb + off_g_out; G.corr_p = cb + off_p;
-                G.ev_idx = SET.gidx + (gs & 1) * gb; G.ev_delta = SET.gdelta + (gs & 1) * gb;
-                unsigned pp_tag = 0;
-                // hand-over words (SET.gpp): cW [2][bs] | counts [8] | cP part [2 bs] | cP [2 bs] | cG relay [3][m bs]
-                unsigned long long* const pw_cw = SET.gpp, * const pw_cnt = pw_cw + 2 * (size_t)bs, * const pw_ph = pw_cnt + 8,
-                                  * const pw_cp = pw_ph + 2 * (size_t)bs, * const pw_h = pw_cp + 2 * (size_t)bs;
-                if (pp_want && G.ns >= 2) {
-                    G.pp = 1; U.quiet_xcd = 1;
-                    c->pp_epoch = (c->pp_epoch + 1) & 0x7fffffffu; if (c->pp_epoch == 0) c->pp_epoch = 1;
-                    pp_tag = c->pp_epoch;
-                    G.pp_ph = pw_ph; G.pp_cp = pw_cp; G.pp_h = pw_h;
-                }
-                for (int s2 = 0; s2 < G.ns; ++s2) {
-                    SamplerArgs& S = SS.a[s2];
-                    const int64_t i = first + s2;
-                    S.P = c->dparams;
-                    S.partials = c->partials + (gs & 1) * pstride_g + (size_t)s2 * bs; S.nrg = c->nrg; S.bstride = (int)gb;
-                    S.j0 = i * bs; S.b = blk_b(c, i); S.p = c->p; S.bsz = bs;
-                    S.xpx = c->xpx;
-                    S.gram = c->gram + i * bb;
-                    const bool inner = !(s2 & 1) && s2 + 1 < G.ns;      // the first block of a PAIR: its sampler forms the cW of the second
-                    S.b_next = inner ? blk_b(c, i + 1) : 0;
-                    S.cross_next = c->cross + (inner ? i + 1 : i) * bb;
-                    S.gram_next = c->gram + (inner ? i + 1 : i) * bb;   // (L2 prefetch only, and only when b_next > 0)
-                    S.compact_off = compact_off; S.nreps = P->nreps;
-                    S.corr_in = cb + ((s2 & 1) ? off_w : off_z);                          // cW: the pair's first block (or +0)
-                    S.corr_out = cb + off_w;
-                    S.corr_in2 = cb + off_g_in + (size_t)s2 * bs;                         // cG: the previous group
-                    S.corr_in3 = cb + ((s2 >= 2) ? off_p + (s2 - 2) * bs : off_z);        // cP: the group's first pair (or +0)
-                    S.prep_d = c->prep_d; S.prep_f = c->prep_f;
-                    S.alpha = c->alpha; S.beta = c->beta; S.delta = c->delta;
-                    S.ev_out = &c->ev[gs & 1];
-                    S.ev_idx = SET.gidx + (gs & 1) * gb; S.ev_delta = SET.gdelta + (gs & 1) * gb;
-                    S.counters = c->counters;
-                    if (G.pp) {
-                        S.pp_tag = pp_tag;
-                        S.pp_cw_in = (s2 & 1) ? pw_cw + (size_t)(s2 >> 1) * bs : nullptr;
-                        S.pp_cw_out = inner ? pw_cw + (size_t)(s2 >> 1) * bs : nullptr;
-                        S.pp_cp_in = (m == 4 && s2 >= 2) ? pw_cp + (size_t)(s2 - 2) * bs : nullptr;
-                        S.pp_cnt_in = s2 > 0 ? pw_cnt + (s2 - 1) : nullptr;
-                        S.pp_cnt_out = s2 + 1 < G.ns ? pw_cnt + s2 : nullptr;
-                    }
-                }
-            }
-            const bool timed = c->timing_stride > 0 && K < ng && (K % c->timing_stride) == 0;
-            if (timed) {
-                while (c->kev.size() < 2 * (ntimed + 1)) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->kev.push_back(e); }
-                HIPCHK(c, hipEventRecord(c->kev[2 * ntimed], c->stream));
-            }
-            sched |= (G.pp_kernel ? JWAS_HIP_SCHED_GROUP_PP_KERNEL : 0u) | (G.pp ? JWAS_HIP_SCHED_GROUP_PINGPONG : 0u) |
-                     (U.quiet_xcd ? JWAS_HIP_SCHED_QUIET_XCD : 0u);
-            HIPCHK(c, launch_group_st(step_launch_of(c), c->method, U, uidx, udel, SS, G));
-            if (timed) {
-                HIPCHK(c, hipEventRecord(c->kev[2 * ntimed + 1], c->stream));
-                ++ntimed;
-                timed_bytes += 4.0 * (double)c->n * (double)U.b;
-            }
+    const int bs = c->block_size, m = L.m;
+    const int64_t nb = c->nblocks, gb = L.gb, first = gs * m, bb = (int64_t)bs * bs;
+    float* cb = SET.gcbuf;
+    const int off_g_in = (int)((gs & 1) * gb), off_g_out = (int)(((gs + 1) & 1) * gb);
+    G->ns = (int)std::min<int64_t>(m, nb - first);
+    G->j0 = first * bs;
+    if (gs + 1 < L.ng) {
+        G->cross_grp = SET.gcross[m == 4 ? 1 : 0] + (size_t)(gs + 1) * gb * gb;
+        G->bn_grp = (int)std::min<int64_t>(gb, c->p - (gs + 1) * gb);
+    }
+    if (m == 4 && G->ns > 2) {
+        G->cross_pair = SET.gcross[0] + (size_t)gs * (2 * (size_t)bs) * (2 * (size_t)bs);      // (pair 2 gs + 1, stored at gs)
+        G->bn_pair = (int)std::min<int64_t>(2 * (int64_t)bs, c->p - (first + 2) * bs);
+    }
+    G->corr_g_out = cb + off_g_out; G->corr_p = cb + L.off_p;
+    G->ev_idx = SET.gidx + (gs & 1) * gb; G->ev_delta = SET.gdelta + (gs & 1) * gb;
+    unsigned pp_tag = 0;
+    if (launch_pingpong(pl, G->ns)) {
+        G->pp = 1;
+        c->pp_epoch = (c->pp_epoch + 1) & 0x7fffffffu; if (c->pp_epoch == 0) c->pp_epoch = 1;
+        pp_tag = c->pp_epoch;
+        G->pp_ph = L.pw_ph; G->pp_cp = L.pw_cp; G->pp_h = L.pw_h;
+    }
+    for (int s2 = 0; s2 < G->ns; ++s2) {
+        SamplerArgs& S = SS->a[s2];
+        const int64_t i = first + s2;
+        S = sampler_args(c, P, pl, false);
+        S.partials = c->partials + (gs & 1) * L.pstride + (size_t)s2 * bs; S.bstride = (int)gb;
+        S.j0 = i * bs; S.b = blk_b(c, i);
+        S.gram = c->gram + i * bb;
+        const bool inner = !(s2 & 1) && s2 + 1 < G->ns;      // the first block of a PAIR: its sampler forms the cW of the second
+        S.b_next = inner ? blk_b(c, i + 1) : 0;
+        S.cross_next = c->cross + (inner ? i + 1 : i) * bb;
+        S.gram_next = c->gram + (inner ? i + 1 : i) * bb;   // (L2 prefetch only, and only when b_next > 0)
+        S.corr_in = cb + ((s2 & 1) ? L.off_w : L.off_z);                          // cW: the pair's first block (or +0)
+        S.corr_out = cb + L.off_w;
+        S.corr_in2 = cb + off_g_in + (size_t)s2 * bs;                             // cG: the previous group
+        S.corr_in3 = cb + ((s2 >= 2) ? L.off_p + (s2 - 2) * bs : L.off_z);        // cP: the group's first pair (or +0)
+        S.ev_out = &c->ev[gs & 1];
+        S.ev_idx = SET.gidx + (gs & 1) * gb; S.ev_delta = SET.gdelta + (gs & 1) * gb;
+        if (G->pp) {
+            S.pp_tag = pp_tag;
+            S.pp_cw_in = (s2 & 1) ? L.pw_cw + (size_t)(s2 >> 1) * bs : nullptr;
+            S.pp_cw_out = inner ? L.pw_cw + (size_t)(s2 >> 1) * bs : nullptr;
+            S.pp_cp_in = (m == 4 && s2 >= 2) ? L.pw_cp + (size_t)(s2 - 2) * bs : nullptr;
+            S.pp_cnt_in = s2 > 0 ? L.pw_cnt + (s2 - 1) : nullptr;
+            S.pp_cnt_out = s2 + 1 < G->ns ? L.pw_cnt + s2 : nullptr;
         }
-        const int64_t par = (ng - 1) & 1;
-        ev_list = EventList{&c->ev[par].count, SET.gidx + par * gb, SET.gdelta + par * gb, gb};
-        last_launch = ng;
-    } else {
-    // one-block lookahead pipeline (sweep.hpp): launch k = sampler(block k-1) || update/partial(block k)
+    }
+}
+
+// GROUPED LAUNCHES (jwas_sweep_params.group_launch; jwas_hip_setup_groups; sweep.hpp k_group_step): gm blocks per launch; launch K =
+// samplers(group K-1) || update/partial(group K).  JWAS_HIP_GROUPS=0 switches it off (then the chain runs one block per launch: the
+// same trajectory within the oracle's bar, NOT the same bits -- the corrections are summed in another order;
+// tests/test_gpu_schedule_variants.py).
+static int sweep_grouped(jwas_hip_ctx* c, const jwas_sweep_params* P, const SweepPlan& pl, SweepRun* run)
+{
+    const auto& SET = c->sets[(size_t)c->set_index];
+    const GroupLayout L(c, SET);
+    const int bs = c->block_size;
+    const int64_t gb = L.gb, ng = L.ng;
+    const size_t rstride = (size_t)kMaxT * c->ld;
+    HIPCHK(c, hipMemcpyAsync(c->r + rstride, c->r, sizeof(float) * (size_t)c->ld, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->ev[1].count, 0, sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(SET.gcbuf, 0, sizeof(float) * ((size_t)2 * gb + 5 * (size_t)bs), c->stream));   // group 0 has no predecessor
+    if (pl.gcoop) HIPCHK(c, hipMemsetAsync(c->sync_cnt, 0, sizeof(int) * 2 * c->nrg, c->stream));
+    for (int64_t K = 0; K <= ng; ++K) {
+        const int64_t j0 = (K < ng) ? K * gb : 0;
+        UpdateArgs U = update_args(c, pl, K, j0, (K < ng) ? (int)std::min<int64_t>(gb, c->p - j0) : 0, pl.gcoop);
+        U.partials = c->partials + (K & 1) * L.pstride; U.bstride = (int)gb;
+        GroupSamplers SS;
+        GroupArgs G;
+        std::memset(&SS, 0, sizeof SS);
+        std::memset(&G, 0, sizeof G);
+        G.m = L.m;
+        G.pp_kernel = pl.pp_kernel ? 1 : 0;                     // (constant over the sweep's launches)
+        SS.a[0].bsz = bs;
+        if (K >= 1) group_samplers(c, P, pl, L, K - 1, &SS, &G);
+        if (G.pp) U.quiet_xcd = 1;
+        run->sched |= (G.pp ? JWAS_HIP_SCHED_GROUP_PINGPONG : 0u) | (U.quiet_xcd ? JWAS_HIP_SCHED_QUIET_XCD : 0u);
+        const int rc = timed_launch(c, run, K, ng, U.b, [&]() -> int {
+            HIPCHK(c, launch_group_st(step_launch_of(c), c->method, U, SET.gidx + (K & 1) * gb, SET.gdelta + (K & 1) * gb, SS, G));
+            return JWAS_HIP_OK;
+        });
+        if (rc) return rc;
+    }
+    const int64_t par = (ng - 1) & 1;
+    run->ev_list = EventList{&c->ev[par].count, SET.gidx + par * gb, SET.gdelta + par * gb, gb};
+    run->r_parity = ng & 1;
+    return JWAS_HIP_OK;
+}
+
+// The sampler of block sb (launch sb + 1) of the one-block lookahead pipeline.
+static SamplerArgs lookahead_sampler(const jwas_hip_ctx* c, const jwas_sweep_params* P, const SweepPlan& pl, int64_t sb)
+{
+    const int bs = c->block_size;
+    const int64_t nb = c->nblocks, bb = (int64_t)bs * bs;
+    const size_t pstride = (size_t)bs * c->nrg * kMaxT, tsf = tsec_floats(c->ntraits);
+    SamplerArgs S = sampler_args(c, P, pl, true);
+    S.partials = c->partials + (sb & 1) * pstride; S.bstride = bs;
+    S.j0 = blk_j0(c, sb); S.b = blk_b(c, sb);
+    S.gram = c->gram + sb * bb;
+    // the correction of block sb was written by the sampler of block sb-1 (launch k-1) into corr[sb&1];
+    // this sampler writes the one of block sb+1 into corr[(sb+1)&1]
+    S.b_next = (sb + 1 < nb) ? blk_b(c, sb + 1) : 0;
+    S.cross_next = c->cross + (sb + 1 < nb ? sb + 1 : sb) * bb;
+    S.gram_next = (sb + 1 < nb) ? c->gram + (sb + 1) * bb : nullptr;
+    S.cross_after = (sb + 2 < nb) ? c->cross + (sb + 2) * bb : nullptr;
+    S.lines_after = (sb + 2 < nb) ? (int)(((int64_t)blk_b(c, sb + 1) * blk_b(c, sb + 2) + 31) / 32) : 0;
+    S.dense_big_off = pl.dense_big_off;
+    S.tsec = (sb < pl.solve_blocks) ? c->tsec + (size_t)sb * 4 * tsf : nullptr;
+    S.tsec_next = (sb + 1 < pl.solve_blocks) ? c->tsec + (size_t)(sb + 1) * 4 * tsf : nullptr;
+    S.tsec_lines = (int)(4 * tsf / 32);
+    S.corr_in = c->corr + (sb & 1) * (size_t)kMaxT * bs;
+    S.corr_out = c->corr + ((sb + 1) & 1) * (size_t)kMaxT * bs;
+    S.ev_out = &c->ev[sb & 1];
+    return S;
+}
+
+// One-block lookahead pipeline (sweep.hpp): launch k = sampler(block k-1) || update/partial(block k).
+static int sweep_lookahead(jwas_hip_ctx* c, const jwas_sweep_params* P, const SweepPlan& pl, SweepRun* run)
+{
+    const int t = c->ntraits, bs = c->block_size;
+    const int64_t nb = c->nblocks;
+    const size_t rstride = (size_t)kMaxT * c->ld, pstride = (size_t)bs * c->nrg * kMaxT;
     HIPCHK(c, hipMemcpyAsync(c->r + rstride, c->r, sizeof(float) * (size_t)t * c->ld, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(&c->ev[1].count, 0, sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->sync_cnt, 0, sizeof(int) * 2 * c->nrg, c->stream));      // (launch parity restarts with the sweep)
     HIPCHK(c, hipMemsetAsync(c->corr, 0, sizeof(float) * 2 * kMaxT * (size_t)bs, c->stream));   // block 0 has no predecessor
-    // dense sweeps (a quarter of the markers or more changed in the previous one; JWAS_HIP_COOP_APPLY=0|1 overrides):
-    // the update role's column groups share the work of applying a block's changes (update_role).  The knob is read
-    // once per sweep (the tests switch it between sweeps of one process).
-    const char* efc = std::getenv("JWAS_HIP_COOP_APPLY");
-    const int fc = efc ? std::atoi(efc) : -1;
-    const bool coop = c->sync_cnt != nullptr && (fc >= 0 ? fc != 0 : (dense_big || c->last_events > 0.25 * (double)c->p));
-    if (coop) sched |= JWAS_HIP_SCHED_COOP_APPLY;
     for (int64_t k = 0; k <= nb; ++k) {
-        UpdateArgs U;
-        U.r_in = c->r + ((k + 1) & 1) * rstride; U.r_out = c->r + (k & 1) * rstride;
-        U.ev = &c->ev[k & 1];
-        U.j0 = (k < nb) ? blk_j0(c, k) : 0;
-        U.b = (k < nb) ? blk_b(c, k) : 0;
-        U.nslices = c->upd_nslices; U.nrg = c->nrg; U.spg = c->spg;
-        U.ncg = (U.b > 0 && c->ncg > U.b) ? U.b : c->ncg;
+        UpdateArgs U = update_args(c, pl, k, (k < nb) ? blk_j0(c, k) : 0, (k < nb) ? blk_b(c, k) : 0, pl.coop);
         U.partials = c->partials + (k & 1) * pstride; U.bstride = bs;
-        U.dbg = c->counters;
-        U.sync_now = coop ? c->sync_cnt + (k & 1) * c->nrg : nullptr;
-        U.sync_next = coop ? c->sync_cnt + ((k + 1) & 1) * c->nrg : nullptr;
-        {   // Placement heuristic (speed only): keep XCD 0 free of streaming traffic for the sampler while the sampler chain
-            // is the critical path (many changes per sweep); in the steady state the sampler has slack and all 8 XCDs
-            // stream (+4-5 % bandwidth).  Decided from the previous sweep's change count; JWAS_HIP_QUIET_XCD=0|1 overrides.
-            static const int qx = std::getenv("JWAS_HIP_QUIET_XCD") ? std::atoi(std::getenv("JWAS_HIP_QUIET_XCD")) : -1;
-            U.quiet_xcd = qx >= 0 ? qx : (c->last_events < 0 || c->last_events > 0.0125 * (double)c->p ? 1 : 0);
-        }
-#ifdef JWAS_HIP_DEV_KNOBS
-        { static const int thr = std::getenv("JWAS_HIP_DEBUG_THROTTLE") ? std::atoi(std::getenv("JWAS_HIP_DEBUG_THROTTLE")) : 0; U.dbg_throttle = thr; }
-#else
-        U.dbg_throttle = 0;
-#endif
+        const bool sampling = k >= 1;
         SamplerArgs S;
-        std::memset(&S, 0, sizeof S);
-        const int64_t sb = k - 1;
-        if (sb >= 0) {
-            S.P = c->dparams;
-            S.partials = c->partials + (sb & 1) * pstride; S.nrg = c->nrg; S.bstride = bs;
-            S.j0 = blk_j0(c, sb); S.b = blk_b(c, sb); S.p = c->p;
-            S.bsz = bs;
-            S.xpx = c->xpx;
-            S.gram = c->gram + sb * (int64_t)bs * bs;
-            // the correction of block sb was written by the sampler of block sb-1 (launch k-1) into corr[sb&1];
-            // this sampler writes the one of block sb+1 into corr[(sb+1)&1]
-            S.b_next = (sb + 1 < nb) ? blk_b(c, sb + 1) : 0;
-            S.cross_next = c->cross + (sb + 1 < nb ? sb + 1 : sb) * (int64_t)bs * bs;
-            S.gram_next = (sb + 1 < nb) ? c->gram + (sb + 1) * (int64_t)bs * bs : nullptr;
-            S.cross_after = (sb + 2 < nb) ? c->cross + (sb + 2) * (int64_t)bs * bs : nullptr;
-            S.dense_big_off = dense_big_off;
-            S.compact_off = compact_off; S.nreps = P->nreps;
-            S.tsec = (sb < solve_blocks) ? c->tsec + (size_t)sb * 4 * tsf : nullptr;
-            S.tsec_next = (sb + 1 < solve_blocks) ? c->tsec + (size_t)(sb + 1) * 4 * tsf : nullptr;
-            S.tsec_lines = (int)(4 * tsf / 32);
-            if (S.tsec != nullptr || (st_helper && S.b == bs && S.b_next > 0)) {       // (the helper workgroup lives on the quiet XCD: ids = 0 mod 8 do no streaming)
-                S.xch = c->xch; c->xch_epoch = (c->xch_epoch + 8) & 0x3fffffff; S.xch_epoch = c->xch_epoch;
-                U.quiet_xcd = 1;
-                if (S.tsec == nullptr) sched |= JWAS_HIP_SCHED_CORR_HELPER;
-            }
-            S.lines_after = (sb + 2 < nb) ? (int)(((int64_t)blk_b(c, sb + 1) * blk_b(c, sb + 2) + 31) / 32) : 0;
-            S.corr_in = c->corr + (sb & 1) * (size_t)kMaxT * bs;
-            S.corr_out = c->corr + ((sb + 1) & 1) * (size_t)kMaxT * bs;
-            S.prep_d = c->prep_d; S.prep_f = c->prep_f; S.mt2_tab = c->mt2_tab; S.lpr_mat = c->lpr_active ? c->lpr_mat : nullptr;
-            S.ginv_mat = has_marker_cov(c->method) ? c->ginv_mat : nullptr;
-            S.alpha = c->alpha; S.beta = c->beta; S.delta = c->delta;
-            S.ev_out = &c->ev[(k - 1) & 1];
-            S.counters = c->counters;
+        if (sampling) S = lookahead_sampler(c, P, pl, k - 1);
+        else std::memset(&S, 0, sizeof S);
+        const bool rule_t = sampling && S.tsec != nullptr;
+        if (sampling && launch_uses_helper(pl, rule_t, bs, S.b, S.b_next)) {
+            S.xch = c->xch; c->xch_epoch = (c->xch_epoch + 8) & 0x3fffffff; S.xch_epoch = c->xch_epoch;
+            U.quiet_xcd = 1;
+            if (!rule_t) run->sched |= JWAS_HIP_SCHED_CORR_HELPER;
         }
-        const bool timed = c->timing_stride > 0 && k < nb && (k % c->timing_stride) == 0;
-        if (timed) {
-            while (c->kev.size() < 2 * (ntimed + 1)) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->kev.push_back(e); }
-            HIPCHK(c, hipEventRecord(c->kev[2 * ntimed], c->stream));
-        }
-        {
-            // (256-marker multi-trait blocks: the dense-walk-only instantiation serves FULL blocks; a ragged last one goes through
-            // the general instantiation)
-            bool dmt = dense_mt;
-            if (dmt && c->block_size == 256 && sb >= 0) dmt = !dense_big_off && S.b == 256;
-            if (sb >= 0 && S.tsec != nullptr) dmt = true;          // Rule T lives in dense_big_mt: the dense-walk-only instantiation, whatever the last sweep did
-            sched |= (U.quiet_xcd ? JWAS_HIP_SCHED_QUIET_XCD : 0u) | (dmt && sb >= 0 ? JWAS_HIP_SCHED_DENSE_MT : 0u);
-            HIPCHK(c, launch_step_any(c, U, S, sb >= 0, dense_big || dmt));
-        }
-        if (c->row_mode && U.b > 0) {          // the block's partial RHS summed over the ranks' individuals, before its sampler runs
-            int rc = row_allreduce(c, U.partials, (size_t)t * c->nrg * bs, true);
-            if (rc) return rc;
-        }
-        if (timed) {
-            HIPCHK(c, hipEventRecord(c->kev[2 * ntimed + 1], c->stream));
-            ++ntimed;
-            timed_bytes += 4.0 * (double)c->n * (double)U.b;
-        }
+        const bool dmt = launch_dense_mt(pl, bs, sampling, S.b, rule_t);
+        run->sched |= (U.quiet_xcd ? JWAS_HIP_SCHED_QUIET_XCD : 0u) | (dmt && sampling ? JWAS_HIP_SCHED_DENSE_MT : 0u);
+        const int rc = timed_launch(c, run, k, nb, U.b, [&]() -> int {
+            HIPCHK(c, launch_step_any(c, U, S, sampling, pl.dense_big || dmt));
+            // the block's partial RHS summed over the ranks' individuals, before its sampler runs
+            return (c->row_mode && U.b > 0) ? row_allreduce(c, U.partials, (size_t)t * c->nrg * bs, true) : JWAS_HIP_OK;
+        });
+        if (rc) return rc;
     }
-    }   // lookahead pipeline
-    if (!independent) {
-        if (!grouped) ev_list = event_list(&c->ev[(nb - 1) & 1]);
-        r_last = c->r + (last_launch & 1) * rstride;          // r(nb-2), written by the last step
-    }
-    const int nfin = t * t + t;
-    with_cols(c, 0, [&](auto cx) {
-    using CX = decltype(cx);
-    switch (t) {   // apply the last block's changes; the finished residual always lands in buffer 0
-        case 1: hipLaunchKernelGGL((k_finish<1, CX>), dim3(c->nslices), dim3(256), 0, c->stream, cx, r_last, c->r, ev_list, c->fin_out); break;
-        case 2: hipLaunchKernelGGL((k_finish<2, CX>), dim3(c->nslices), dim3(256), 0, c->stream, cx, r_last, c->r, ev_list, c->fin_out); break;
-        case 3: hipLaunchKernelGGL((k_finish<3, CX>), dim3(c->nslices), dim3(256), 0, c->stream, cx, r_last, c->r, ev_list, c->fin_out); break;
-        default: hipLaunchKernelGGL((k_finish<4, CX>), dim3(c->nslices), dim3(256), 0, c->stream, cx, r_last, c->r, ev_list, c->fin_out);
-    }
-    return 0;
-    });
+    run->ev_list = event_list(&c->ev[(nb - 1) & 1]);
+    run->r_parity = nb & 1;          // r(nb-2), written by the last step
+    return JWAS_HIP_OK;
+}
+
+// Apply the last block's changes -- the finished residual always lands in buffer 0 -- and reduce the marker statistics.
+static int sweep_finish(jwas_hip_ctx* c, const SweepRun& run)
+{
+    const float* r_last = c->r + run.r_parity * ((size_t)kMaxT * c->ld);
     const double* gamma_dev = reinterpret_cast<const double*>(reinterpret_cast<const char*>(c->dparams) + offsetof(DevParams, gamma));
-    switch (t) {
-        case 1: hipLaunchKernelGGL((k_marker_stats<1>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, c->alpha, c->beta, c->delta, gamma_dev, c->stat_out); break;
-        case 2: hipLaunchKernelGGL((k_marker_stats<2>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, c->alpha, c->beta, c->delta, gamma_dev, c->stat_out); break;
-        case 3: hipLaunchKernelGGL((k_marker_stats<3>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, c->alpha, c->beta, c->delta, gamma_dev, c->stat_out); break;
-        default: hipLaunchKernelGGL((k_marker_stats<4>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, c->alpha, c->beta, c->delta, gamma_dev, c->stat_out);
-    }
+    with_traits(c->ntraits, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        with_cols(c, 0, [&](auto cx) {
+            hipLaunchKernelGGL((k_finish<NT, decltype(cx)>), dim3(c->nslices), dim3(256), 0, c->stream, cx, r_last, c->r, run.ev_list, c->fin_out);
+            return 0;
+        });
+        hipLaunchKernelGGL((k_marker_stats<NT>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, c->alpha, c->beta, c->delta, gamma_dev, c->stat_out);
+    });
     HIPCHK(c, hipGetLastError());
-    c->last_schedule = sched;
-    *ntimed_out = ntimed;
-    *timed_bytes_out = timed_bytes;
+    return JWAS_HIP_OK;
+}
+
+// Everything of a sweep up to the marker statistics, enqueued on the context's stream (no host synchronisation).
+static int sweep_enqueue(jwas_hip_ctx* c, const jwas_sweep_params* P, size_t* ntimed_out, double* timed_bytes_out)
+{
+    PriorFill<DevParams, float> fill;
+    if (int rc = sweep_fill_params(c, P, &fill)) return rc;
+    const SweepPlan pl = plan_sweep(sweep_facts(c, P, fill), sweep_knobs());
+    if (int rc = sweep_prepare(c, pl)) return rc;
+    SweepRun run;
+    if (int rc = pl.path == SweepPlan::kIndependent ? sweep_independent(c, P, pl, &run)
+               : pl.path == SweepPlan::kGrouped     ? sweep_grouped(c, P, pl, &run)
+                                                    : sweep_lookahead(c, P, pl, &run)) return rc;
+    if (int rc = sweep_finish(c, run)) return rc;
+    c->last_schedule = pl.sched | run.sched;      // which of the variants this sweep took (jwas_hip_last_sweep_schedule): one bit per decision
+    *ntimed_out = run.ntimed;
+    *timed_bytes_out = run.timed_bytes;
     return JWAS_HIP_OK;
 }
 
@@ -1722,7 +1746,7 @@ static int sweep_collect(jwas_hip_ctx* c, jwas_sweep_stats* S, size_t ntimed, do
     for (int i = 0; i < kNCounters; ++i) c->last_counters[i] = h_cnt[i];
     NEED(c, h_cnt[kPpTimeoutCounter] == 0, JWAS_HIP_EHIP, "grouped launches: %llu hand-over words between the two sampler workgroups never arrived (results of this sweep are invalid)",
          h_cnt[kPpTimeoutCounter]);
-    if (std::getenv("JWAS_HIP_DEBUG_PHASES"))
+    if (sweep_knobs().debug_phases)
         std::fprintf(stderr, "[jwas_hip] blocks=%lld events=%llu unstaged=%llu cycles: front=%llu cand=%llu stage=%llu serial=%llu write=%llu corr=%llu rounds=%llu slow_rounds=%llu stage: assign=%llu issue=%llu wait=%llu update wg0: share=%llu wait=%llu rest=%llu compact: blocks=%llu fallback=%llu walk=%llu verify=%llu role=%llu tailwait=%llu xwrite=%llu xchain=%llu (section_solve: blocks = sections solved, fallback = fallen back, walk..xwrite = cycles of y | mat-vec | combine | verify+apply | tail) group: cP=%llu tail=%llu workgroups=%llu last_workgroup=%llu late_new_candidates=%llu mt_taken_over=%llu mt_helped=%llu\n",
                      (long long)c->nblocks, h_cnt[0], h_cnt[1], h_cnt[2], h_cnt[3], h_cnt[4], h_cnt[5], h_cnt[6], h_cnt[9], h_cnt[7], h_cnt[8], h_cnt[10], h_cnt[11], h_cnt[12], h_cnt[13], h_cnt[14], h_cnt[15], h_cnt[16], h_cnt[17], h_cnt[18], h_cnt[19], h_cnt[20], h_cnt[21], h_cnt[22], h_cnt[23], h_cnt[25], h_cnt[26], h_cnt[27], h_cnt[28], h_cnt[29], h_cnt[30], h_cnt[31]);
     float ms = 0.f;
@@ -1917,7 +1941,9 @@ static hipError_t f64_set_lds_attr()
     return e;
 }
 
-static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_stats* S)
+// The checks of jwas_sweep_params for a Float64 context, Params64 (the variances as the reference holds them there: vare_f64,
+// var_effect_f64), the uploads it points to; then the sweep's first work on the stream.
+static int f64_fill_params(jwas_hip_ctx* c, const jwas_sweep_params* P)
 {
     auto* F = c->f64;
     NEED(c, c->method >= 0, JWAS_HIP_ESTATE, "jwas_hip_init_state has not been called");
@@ -1927,13 +1953,10 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
          "through jwas_hip_set_marker_covariances_f64 (or draws them with jwas_hip_sample_marker_covariances)");
     const int t = c->ntraits;
     NEED(c, F->bstride * t <= 2048, JWAS_HIP_EUNSUP, "Float64 contexts need block size x traits <= 2048 (got %d x %d)", F->bstride, t);
-    // an open annotation session (jwas_hip_annot_begin): its resident table stands in for the prior pointer, which must be NULL
-    NEED(c, !(c->an.active && (P->pi_vec || P->pi_matrix || P->log_prior_states_matrix)), JWAS_HIP_EINVAL,
-         "an annotation session is open: the sweep reads its resident prior table, pi_vec / pi_matrix / log_prior_states_matrix must be NULL");
-    const bool use_pi_vec = P->pi_vec || (c->an.active && c->an.kind == jwa::kBayesC);
-    const bool use_pi_mat = P->pi_matrix || (c->an.active && c->an.kind == jwa::kBayesR);
-    const bool use_lpr = P->log_prior_states_matrix || (c->an.active && c->an.kind == jwa::kTree);
-    const bool marker_cov = has_marker_cov(c->method);
+    PriorFill<jw64::Params64, double> fill;
+    jw64::Params64 D;
+    if (int rc = fill.begin(c, P, P->vare_f64, P->var_effect_f64, D)) return rc;
+    const bool use_lpr = fill.use_lpr, marker_cov = has_marker_cov(c->method);
     if (marker_cov) {       // multi-trait BayesA/B (MTBayesABC.jl:66,86-90): the limits of the Float32 path
         NEED(c, F->var_mat && F->var_mat_resident, JWAS_HIP_EINVAL, "multi-trait BayesA/B needs per-marker effect covariances (jwas_hip_set_marker_covariances_f64, or jwas_hip_sample_marker_covariances)");
         NEED(c, !P->independent_blocks, JWAS_HIP_EUNSUP, "independent_blocks is not available with per-marker effect covariances");
@@ -1952,34 +1975,8 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
             attr_set.fetch_or(bit, std::memory_order_release);
         }
     }
-    jw64::Params64 D;
-    std::memset(&D, 0, sizeof D);
-    D.method = c->method; D.ntraits = t; D.nreps = P->nreps;
-    D.iter = P->iteration; D.seed_lo = (uint32_t)P->seed; D.seed_hi = (uint32_t)(P->seed >> 32); D.marker0 = P->marker_offset;
-    for (int i = 0; i < t * t; ++i) { D.vare[i] = P->vare_f64[i]; D.var_effect[i] = P->var_effect_f64[i]; }
     if (is_mt_method(c->method)) {
-        // inv(vare), inv(G) (MTBayesABC.jl:66-67) in double: Gauss-Jordan with partial pivoting (the oracle's operation order)
-        auto inv_d = [&](const double* A, double* Ainv) -> int {
-            double M[kMaxT][2 * kMaxT];
-            for (int i = 0; i < t; ++i) for (int j = 0; j < t; ++j) { M[i][j] = A[i * t + j]; M[i][t + j] = (i == j); }
-            for (int cc = 0; cc < t; ++cc) {
-                int piv = cc;
-                for (int i = cc + 1; i < t; ++i) if (std::fabs(M[i][cc]) > std::fabs(M[piv][cc])) piv = i;
-                if (M[piv][cc] == 0.0) return -1;
-                if (piv != cc) for (int j = 0; j < 2 * t; ++j) std::swap(M[cc][j], M[piv][j]);
-                const double d = M[cc][cc];
-                for (int j = 0; j < 2 * t; ++j) M[cc][j] /= d;
-                for (int i = 0; i < t; ++i) if (i != cc) { const double f = M[i][cc]; if (f != 0.0) for (int j = 0; j < 2 * t; ++j) M[i][j] -= f * M[cc][j]; }
-            }
-            for (int i = 0; i < t; ++i) for (int j = 0; j < t; ++j) Ainv[i * t + j] = M[i][t + j];
-            return 0;
-        };
-        NEED(c, inv_d(D.vare, D.Rinv) == 0, JWAS_HIP_EINVAL, "residual covariance matrix is singular");
-        if (!marker_cov) NEED(c, inv_d(D.var_effect, D.Ginv) == 0, JWAS_HIP_EINVAL, "marker effect covariance matrix is singular");
-        bool any_finite = false;
-        for (int i = 0; i < (1 << t); ++i) { D.log_prior[i] = P->log_prior_states[i]; any_finite = any_finite || std::isfinite(D.log_prior[i]); }
-        if (is_sampler2(c->method) && !use_lpr)      // MTBayesABC.jl:190
-            NEED(c, any_finite, JWAS_HIP_EINVAL, "All MTBayesABC sampler II state probabilities are zero or invalid.");
+        if (int rc = fill.joint(c, P, D)) return rc;
         if (P->log_prior_states_matrix) {
             int rc = upload_vec(c, nullptr, (void**)&c->lpr_mat, P->log_prior_states_matrix, sizeof(double) * (size_t)(1 << t) * c->p);
             if (rc) return rc;
@@ -1990,88 +1987,80 @@ static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_sta
             D.ginv_mat = F->ginv_mat;
         }
     } else NEED(c, D.vare[0] > 0.0, JWAS_HIP_EINVAL, "residual variance must be positive");
-    if (c->method == JWAS_HIP_BAYESR) {
-        NEED(c, D.var_effect[0] > 0.0, JWAS_HIP_EINVAL, "BayesR sigmaSq must be positive.");
-        if (!use_pi_mat) {
-            double sum = 0.0;
-            for (int k = 0; k < 4; ++k) { NEED(c, P->pi_classes[k] >= 0.0, JWAS_HIP_EINVAL, "BayesR pi entries must be nonnegative."); sum += P->pi_classes[k]; }
-            NEED(c, std::fabs(sum - 1.0) <= 1e-8, JWAS_HIP_EINVAL, "BayesR pi must sum to 1.");
-        }
-        for (int k = 0; k < 4; ++k) { D.pi4[k] = P->pi_classes[k]; D.gamma[k] = P->gamma[k]; }
-        if (P->pi_matrix) { int rc = upload_vec(c, nullptr, (void**)&c->pi_mat, P->pi_matrix, sizeof(double) * 4 * c->p); if (rc) return rc; }
-        if (use_pi_mat) D.pi_mat = c->pi_mat;
-    } else if (c->method == JWAS_HIP_BAYESC || c->method == JWAS_HIP_BAYESB) {
-        D.pi = P->pi;
-        if (P->pi_vec) { int rc = upload_vec(c, nullptr, (void**)&c->pi_vec, P->pi_vec, sizeof(double) * c->p); if (rc) return rc; }
-        if (use_pi_vec) D.pi_vec = c->pi_vec;
-        if (c->method == JWAS_HIP_BAYESB) {
-            NEED(c, P->var_effect_vec_f64, JWAS_HIP_EINVAL, "BayesB needs per-marker effect variances (var_effect_vec_f64)");
-            int rc = upload_vec(c, &F->chain_mem, (void**)&F->var_vec, P->var_effect_vec_f64, sizeof(double) * c->p); if (rc) return rc;
-            D.var_vec = F->var_vec;
-        } else NEED(c, D.var_effect[0] > 0.0, JWAS_HIP_EINVAL, "marker effect variance must be positive");
-    }
+    if (int rc = fill.single_trait(c, P, P->var_effect_vec_f64, "var_effect_vec_f64", D)) return rc;
     HIPCHK(c, hipMemcpyAsync(F->dparams, &D, sizeof D, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->counters, 0, sizeof(unsigned long long) * kNCounters, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
-    if (marker_cov) {       // G_j^-1 once per sweep, before the first block
-        const dim3 g((unsigned)((c->p + 255) / 256)), bk(256);
-        if (t == 2) hipLaunchKernelGGL((jw64::k64_invert_marker_cov<2>), g, bk, 0, c->stream, c->p, F->var_mat, F->ginv_mat);
-        else if (t == 3) hipLaunchKernelGGL((jw64::k64_invert_marker_cov<3>), g, bk, 0, c->stream, c->p, F->var_mat, F->ginv_mat);
-        else hipLaunchKernelGGL((jw64::k64_invert_marker_cov<4>), g, bk, 0, c->stream, c->p, F->var_mat, F->ginv_mat);
-    }
+    if (marker_cov)         // G_j^-1 once per sweep, before the first block
+        with_traits(t, [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if constexpr (NT >= 2)
+                hipLaunchKernelGGL((jw64::k64_invert_marker_cov<NT>), dim3((unsigned)((c->p + 255) / 256)), dim3(256), 0, c->stream, c->p, F->var_mat, F->ginv_mat);
+        });
+    return JWAS_HIP_OK;
+}
+
+// The change lists k64_finish still has to apply, and the residual buffer it applies them to.
+struct F64Run { const jw64::Events64* lists = nullptr; int64_t nlists = 0, r_parity = 0; };
+
+static inline double* f64_rbuf(jwas_hip_ctx* c, int64_t parity) { return c->f64->r + (size_t)(parity & 1) * ((size_t)kMaxT * c->ld); }
+
+// launch k reads r(k & 1), applies block k-1's changes and writes r((k + 1) & 1)
+static int f64_sequential(jwas_hip_ctx* c, F64Run* run)
+{
+    auto* F = c->f64;
     const int64_t nb = c->nblocks;
-    const size_t rbuf = (size_t)kMaxT * c->ld;
-    auto rb = [&](int64_t parity) { return F->r + (size_t)(parity & 1) * rbuf; };
-    const jw64::Events64* fin_lists = nullptr;
-    int64_t fin_nlists = 0, fin_parity = 0;
-    if (!P->independent_blocks) {
-        // launch k reads r(k & 1), applies block k-1's changes and writes r((k + 1) & 1)
-        for (int64_t k = 0; k < nb; ++k) {
-            const jw64::Events64* prev = k > 0 ? &F->ev[(k - 1) & 1] : nullptr;
-            switch (t) {
-                case 1: f64_launch_block<1>(c, rb(k), rb(k + 1), prev, k, F->partials, &F->ev[k & 1]); break;
-                case 2: f64_launch_block<2>(c, rb(k), rb(k + 1), prev, k, F->partials, &F->ev[k & 1]); break;
-                case 3: f64_launch_block<3>(c, rb(k), rb(k + 1), prev, k, F->partials, &F->ev[k & 1]); break;
-                default: f64_launch_block<4>(c, rb(k), rb(k + 1), prev, k, F->partials, &F->ev[k & 1]);
-            }
-        }
-        fin_lists = &F->ev[(nb - 1) & 1]; fin_nlists = 1; fin_parity = nb;
-    } else {
-        // BayesABC_block_independent! (BayesABC.jl:190-255): every block from the SAME residual, reconciled afterwards
-        if (F->ev_all_cap < nb) {
-            (void)hipFree(F->ev_all); F->ev_all = nullptr; F->ev_all_cap = 0;
-            HIPCHK(c, hipMalloc(&F->ev_all, sizeof(jw64::Events64) * (size_t)nb));
-            F->ev_all_cap = nb;
-        }
-        const size_t one = (size_t)kMaxT * c->nslices * F->bstride;
-        if (F->partials_cap < one * (size_t)nb) {
-            (void)hipFree(F->partials); F->partials = nullptr; F->partials_cap = 0;
-            HIPCHK(c, hipMalloc(&F->partials, sizeof(double) * one * (size_t)nb));
-            F->partials_cap = one * (size_t)nb;
-        }
-        for (int64_t k = 0; k < nb; ++k) {
-            double* part = F->partials + one * (size_t)k;
-            switch (t) {
-                case 1: f64_launch_block<1>(c, rb(0), nullptr, nullptr, k, part, F->ev_all + k); break;
-                case 2: f64_launch_block<2>(c, rb(0), nullptr, nullptr, k, part, F->ev_all + k); break;
-                case 3: f64_launch_block<3>(c, rb(0), nullptr, nullptr, k, part, F->ev_all + k); break;
-                default: f64_launch_block<4>(c, rb(0), nullptr, nullptr, k, part, F->ev_all + k);
-            }
-        }
-        fin_lists = F->ev_all; fin_nlists = nb; fin_parity = 0;
+    with_traits(c->ntraits, [&](auto nt) {
+        for (int64_t k = 0; k < nb; ++k)
+            f64_launch_block<decltype(nt)::value>(c, f64_rbuf(c, k), f64_rbuf(c, k + 1), k > 0 ? &F->ev[(k - 1) & 1] : nullptr, k, F->partials, &F->ev[k & 1]);
+    });
+    *run = F64Run{&F->ev[(nb - 1) & 1], 1, nb};
+    return JWAS_HIP_OK;
+}
+
+// BayesABC_block_independent! (BayesABC.jl:190-255): every block from the SAME residual, reconciled afterwards
+static int f64_independent(jwas_hip_ctx* c, F64Run* run)
+{
+    auto* F = c->f64;
+    const int64_t nb = c->nblocks;
+    if (F->ev_all_cap < nb) {
+        (void)hipFree(F->ev_all); F->ev_all = nullptr; F->ev_all_cap = 0;
+        HIPCHK(c, hipMalloc(&F->ev_all, sizeof(jw64::Events64) * (size_t)nb));
+        F->ev_all_cap = nb;
     }
+    const size_t one = (size_t)kMaxT * c->nslices * F->bstride;
+    if (F->partials_cap < one * (size_t)nb) {
+        (void)hipFree(F->partials); F->partials = nullptr; F->partials_cap = 0;
+        HIPCHK(c, hipMalloc(&F->partials, sizeof(double) * one * (size_t)nb));
+        F->partials_cap = one * (size_t)nb;
+    }
+    with_traits(c->ntraits, [&](auto nt) {
+        for (int64_t k = 0; k < nb; ++k)
+            f64_launch_block<decltype(nt)::value>(c, f64_rbuf(c, 0), nullptr, nullptr, k, F->partials + one * (size_t)k, F->ev_all + k);
+    });
+    *run = F64Run{F->ev_all, nb, 0};
+    return JWAS_HIP_OK;
+}
+
+static int f64_finish(jwas_hip_ctx* c, const F64Run& run)
+{
+    auto* F = c->f64;
     const double* gamma_dev = reinterpret_cast<const double*>(reinterpret_cast<const char*>(F->dparams) + offsetof(jw64::Params64, gamma));
-    switch (t) {
-        case 1: hipLaunchKernelGGL((jw64::k64_finish<1>), dim3(c->nslices), dim3(256), 0, c->stream, F->X, c->ld, c->n, F->w, rb(fin_parity), rb(0), fin_lists, fin_nlists, c->fin_out);
-                hipLaunchKernelGGL((jw64::k64_marker_stats<1>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, F->alpha, F->beta, F->delta, gamma_dev, c->stat_out); break;
-        case 2: hipLaunchKernelGGL((jw64::k64_finish<2>), dim3(c->nslices), dim3(256), 0, c->stream, F->X, c->ld, c->n, F->w, rb(fin_parity), rb(0), fin_lists, fin_nlists, c->fin_out);
-                hipLaunchKernelGGL((jw64::k64_marker_stats<2>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, F->alpha, F->beta, F->delta, gamma_dev, c->stat_out); break;
-        case 3: hipLaunchKernelGGL((jw64::k64_finish<3>), dim3(c->nslices), dim3(256), 0, c->stream, F->X, c->ld, c->n, F->w, rb(fin_parity), rb(0), fin_lists, fin_nlists, c->fin_out);
-                hipLaunchKernelGGL((jw64::k64_marker_stats<3>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, F->alpha, F->beta, F->delta, gamma_dev, c->stat_out); break;
-        default: hipLaunchKernelGGL((jw64::k64_finish<4>), dim3(c->nslices), dim3(256), 0, c->stream, F->X, c->ld, c->n, F->w, rb(fin_parity), rb(0), fin_lists, fin_nlists, c->fin_out);
-                hipLaunchKernelGGL((jw64::k64_marker_stats<4>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, F->alpha, F->beta, F->delta, gamma_dev, c->stat_out);
-    }
+    with_traits(c->ntraits, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((jw64::k64_finish<NT>), dim3(c->nslices), dim3(256), 0, c->stream, F->X, c->ld, c->n, F->w, f64_rbuf(c, run.r_parity), f64_rbuf(c, 0), run.lists, run.nlists, c->fin_out);
+        hipLaunchKernelGGL((jw64::k64_marker_stats<NT>), dim3(kStatGrid), dim3(256), 0, c->stream, c->method, c->p, F->alpha, F->beta, F->delta, gamma_dev, c->stat_out);
+    });
     HIPCHK(c, hipGetLastError());
+    return JWAS_HIP_OK;
+}
+
+static int f64_sweep(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_sweep_stats* S)
+{
+    if (int rc = f64_fill_params(c, P)) return rc;
+    F64Run run;
+    if (int rc = P->independent_blocks ? f64_independent(c, &run) : f64_sequential(c, &run)) return rc;
+    if (int rc = f64_finish(c, run)) return rc;
     return sweep_collect(c, S, 0, 0.0, nullptr);
 }
 
@@ -2328,12 +2317,9 @@ int jwas_hip_sweep_sharded(jwas_hip_ctx* c, const jwas_sweep_params* P, jwas_swe
     HIPCHK(c, hipGetLastError());
     rc = row_allreduce(c, c->shard_buf, (size_t)(total + kShardStats), true);      // ncclAllReduce(sum, fp64) on the stream, or the loopback transport
     if (rc) return rc;
-    switch (t) {
-        case 1: hipLaunchKernelGGL((k_shard_apply<1>), dim3(c->nslices), dim3(256), 0, c->stream, c->w, c->ld, c->r_snap, c->shard_buf, c->r, c->fin_out); break;
-        case 2: hipLaunchKernelGGL((k_shard_apply<2>), dim3(c->nslices), dim3(256), 0, c->stream, c->w, c->ld, c->r_snap, c->shard_buf, c->r, c->fin_out); break;
-        case 3: hipLaunchKernelGGL((k_shard_apply<3>), dim3(c->nslices), dim3(256), 0, c->stream, c->w, c->ld, c->r_snap, c->shard_buf, c->r, c->fin_out); break;
-        default: hipLaunchKernelGGL((k_shard_apply<4>), dim3(c->nslices), dim3(256), 0, c->stream, c->w, c->ld, c->r_snap, c->shard_buf, c->r, c->fin_out);
-    }
+    with_traits(t, [&](auto nt) {
+        hipLaunchKernelGGL((k_shard_apply<decltype(nt)::value>), dim3(c->nslices), dim3(256), 0, c->stream, c->w, c->ld, c->r_snap, c->shard_buf, c->r, c->fin_out);
+    });
     HIPCHK(c, hipGetLastError());
     return sweep_collect(c, S, ntimed, timed_bytes, c->shard_buf + total);
 }
