@@ -212,6 +212,30 @@ int  jwas_hip_load_jgb2(jwas_hip_ctx* ctx, const char* path);
 int  jwas_hip_load_packed2bit(jwas_hip_ctx* ctx, const uint8_t* payload, int64_t n, int64_t p, int64_t stride_bytes,
                               const float* marker_means, int32_t centered);
 int  jwas_hip_alloc_packed2bit(jwas_hip_ctx* ctx, int64_t n, int64_t p, int32_t centered);   /* + jwas_hip_synth_genotypes */
+/* ---- PLINK 1 binary filesets (.bed/.bim/.fam) straight into packed storage ----
+ * Replaces prepare_streaming_genotypes (streaming_genotypes.jl:499-656,819-877) for genotypes that exist as a variant-major .bed
+ * file: the same four-individuals-per-byte layout as .jgb2, with another meaning of the 2-bit field (0 = homozygous for the .bim's
+ * first allele A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2).  Two calls, so that the quality control (:274-296) stays in the
+ * host's one copy of it:
+ *   jwas_hip_plink_scan    checks the file (magic 6C 1B 01, size 3 + p_file * cld(n_file,4)) and `rows` (the file rows of the
+ *                          individuals to keep, in the order wanted, each at most once; NULL: all n_file in file order), streams the
+ *                          file through pinned buffers of at most 64 MB, transcodes EVERY file marker on the device into a staging
+ *                          buffer of the context ([p_file][ld/4] bytes, pad fields 0) and returns counts[j][c] = kept individuals of
+ *                          marker j with code c (0/1/2 = copies of the counted allele, A1 if count_a1 else A2; 3 = missing).
+ *   jwas_hip_plink_commit  allocates packed storage (n_rows, p_sel) as jwas_hip_load_packed2bit does, moves the rows of the markers
+ *                          `selected` (0-based file indices, strictly ascending) into it, sets their means and `centered`, and frees
+ *                          the staging buffer.  When every marker stays the staging buffer becomes the storage.  Needs a pending
+ *                          scan (JWAS_HIP_ESTATE otherwise).
+ *   jwas_hip_plink_discard drops a pending scan; so do every other load / allocation of genotypes and jwas_hip_destroy.
+ * Device memory between the two calls: the staging buffer beside whatever the context held before; during a commit that drops
+ * markers: the staging buffer and the final storage.  Float32 contexts only. */
+int  jwas_hip_plink_scan(jwas_hip_ctx* ctx, const char* bed_path, int64_t n_file, int64_t p_file, const int64_t* rows, int64_t n_rows,
+                         int32_t count_a1, int64_t* counts);
+int  jwas_hip_plink_commit(jwas_hip_ctx* ctx, const int64_t* selected, int64_t p_sel, const float* marker_means, int32_t centered);
+int  jwas_hip_plink_discard(jwas_hip_ctx* ctx);
+/* The packed rows of markers [j0, j0 + m) back to the host, cld(n,4) bytes of each at stride_bytes >= cld(n,4): the payload of a
+ * .jgb2 file (streaming_genotypes.jl:600-654) from a context with packed storage, however it was loaded. */
+int  jwas_hip_get_packed2bit(jwas_hip_ctx* ctx, int64_t j0, int64_t m, uint8_t* out_host, int64_t stride_bytes);
 int  jwas_hip_storage_info(jwas_hip_ctx* ctx, int32_t* kind, int64_t* n, int64_t* p, int64_t* bytes);
 /* Device row stride (elements) of the padded marker-major layout, and its base device pointer. */
 int  jwas_hip_dense_layout(jwas_hip_ctx* ctx, int64_t* n, int64_t* p, int64_t* ld_dev, void** X_dev);

@@ -12,7 +12,7 @@ __all__ = ["HipEngine", "JwasHipError", "BAYESR_GAMMA", "LIB_PATH", "PSRF"]
 
 def __getattr__(name):
     # host-side API (imports pandas etc.) is loaded lazily
-    if name in ("get_genotypes", "build_model", "runMCMC", "Genotypes", "Model", "set_covariate", "set_random", "outputEBV", "outputMCMCsamples", "device_genotypes", "generatefullPhi", "genomic_relationship_matrix"):
+    if name in ("get_genotypes", "build_model", "runMCMC", "Genotypes", "Model", "set_covariate", "set_random", "outputEBV", "outputMCMCsamples", "device_genotypes", "plink_genotypes", "generatefullPhi", "genomic_relationship_matrix"):
         from . import api
         return getattr(api, name)
     if name == "GWAS":

@@ -306,6 +306,41 @@ def device_genotypes(engine, G=False, *, method="BayesC", Pi=0.0, estimatePi=Tru
     return g
 
 
+def plink_genotypes(bfile, G=False, *, keep=None, device=0, engine=None, counted_allele="A1", quality_control=True, MAF=0.01,
+                    center=True, id_column="IID", method="BayesC", Pi=0.0, estimatePi=True, G_is_marker_variance=False, df=4.0,
+                    estimate_variance=True, estimate_scale=False, constraint=False, multi_trait_sampler="I"):
+    """A Genotypes object over a PLINK 1 binary fileset (<bfile>.bed/.bim/.fam; `bfile` is the prefix or any of the three
+    paths), loaded straight into 2-bit packed device storage (plink.load_plink): what get_genotypes(prefix, storage="stream")
+    gives for the backend prepare_streaming_genotypes would write of the same genotypes, without the text file, the dense
+    matrix or the backend.  keep: the IDs of the individuals wanted -- the phenotyped ones, in the phenotypes' order (None: all,
+    file order); counted_allele: "A1" (the .bim's first allele) or "A2".  engine: a Float32 HipEngine to load into (None: one is
+    made on `device`).  The marker-model keywords are device_genotypes'."""
+    if method not in SUPPORTED_METHODS:
+        raise NotImplementedError(f"method {method} is not on the device path (supported: {SUPPORTED_METHODS})")
+    from . import plink
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(device)
+    if getattr(engine, "precision", 32) != 32:
+        raise ValueError("plink_genotypes needs a Float32 engine (2-bit packed storage has no Float64 path)")
+    try:
+        b = plink.load_plink(engine, bfile, keep=keep, counted_allele=counted_allele, quality_control=quality_control, MAF=MAF,
+                             center=center, id_column=id_column)
+        g = device_genotypes(engine, G, method=method, Pi=Pi, estimatePi=estimatePi, G_is_marker_variance=G_is_marker_variance, df=df,
+                             estimate_variance=estimate_variance, estimate_scale=estimate_scale, constraint=constraint,
+                             multi_trait_sampler=multi_trait_sampler, obsID=b["obsID"], markerID=b["markerID"], centered=b["centered"],
+                             alleleFreq=b["allele_freq"], sum2pq=b["sum2pq"])
+    except BaseException:
+        if own:
+            engine.close()
+        raise
+    g.counted_alleles, g.selected = b["counted_alleles"], b["selected"]
+    print("Genotype informatin:")
+    print(f"#markers: {b['nMarkers']}; #individuals: {b['nObs']} (PLINK fileset, 2-bit packed on the device)")
+    return g
+
+
 class ModelTerm:
     def __init__(self, trait, name):
         self.trait, self.name = trait, name

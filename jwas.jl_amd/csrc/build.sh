@@ -12,7 +12,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OBJ=${JWAS_OBJ_DIR:-_obj}
 OUT=${JWAS_OUT:-libjwas_hip.so}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC $JWAS_EXTRA_FLAGS"
-UNITS="jwas_hip output session_liability session_locpar session_mtmiss session_annot session_sem session_rrm session_mega session_mtjoint session_ssbr session_gblup step_st step_mtc1 step_mtb1 step_mt2 step_mega"
+UNITS="jwas_hip output session_liability session_locpar session_mtmiss session_annot session_sem session_rrm session_mega session_mtjoint session_ssbr session_gblup session_plink step_st step_mtc1 step_mtb1 step_mt2 step_mega"
 mkdir -p "$OBJ"
 echo "$FLAGS $*" > "$OBJ/.flags.new"
 if [ "${INCREMENTAL:-1}" = 0 ] || ! cmp -s "$OBJ/.flags.new" "$OBJ/.flags"; then rm -f "$OBJ"/*.o; fi

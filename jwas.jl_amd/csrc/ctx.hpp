@@ -170,6 +170,7 @@ struct jwas_hip_ctx : Side<float> {
     int timing_stride = 0;
     double last_events = -1.0;          // effect changes of the previous sweep (-1: none yet)
     static constexpr int kCounters = 32;                    // = jw::kNCounters of kernels.hpp (jwas_hip.hip asserts it)
+    static constexpr int64_t kRowPad = 256;                 // = jw::kSliceRows: ld is n rounded up to it (likewise)
     unsigned long long last_counters[kCounters] = {};       // the sampler's diagnostics counters of the previous sweep
     uint32_t last_schedule = 0;         // JWAS_HIP_SCHED_* bits of the last sweep sweep_enqueue put on the stream
     double event_overhead_ms = 0.0;     // mean HIP-event interval around an empty launch (calibration)
@@ -369,6 +370,14 @@ struct jwas_hip_ctx : Side<float> {
         double* par = nullptr;                              // [kParSize] the parameters of the running step
         double* stat = nullptr;                             // [nwg][nt nt] | [nslices][nt nt + nt]
     } gb;
+    // A scanned PLINK .bed file that waits for its commit (jwas_hip_plink_scan .. _commit / _discard; csrc/plink.hpp): every file
+    // marker transcoded to 2-bit codes in the layout of packed storage.  It is bound to no matrix; any load or allocation drops it.
+    struct Plink {
+        bool pending = false;
+        int64_t n_rows = 0, p_file = 0, ld = 0;             // kept individuals, file markers, n_rows rounded up to kRowPad
+        DevOwner mem;
+        uint8_t* stage = nullptr;                           // [p_file][ld / 4] (+ 1 KB, as packed storage has)
+    } pk;
 };
 
 // ---- errors ------------------------------------------------------------------------------------------------------------------------
@@ -470,6 +479,12 @@ JW_LOCAL void mtj_free(jwas_hip_ctx* c);
 JW_LOCAL void ss_free(jwas_hip_ctx* c);
 JW_LOCAL void gblup_free(jwas_hip_ctx* c);
 JW_LOCAL void gwas_free(jwas_hip_ctx* c);                                  // (output.hip: the GWAS session)
+JW_LOCAL void plink_free(jwas_hip_ctx* c);                                 // (a pending scan: it goes with any load, too)
+
+// Storage of an n x p matrix and everything sized by it (jwas_hip.hip); whatever the context held before is freed first.  adopt: a
+// buffer of (ld / 4) p + 1024 bytes that becomes the packed payload in the place of a new allocation (the context owns it from here on,
+// also when the call fails).
+JW_LOCAL int alloc_storage(jwas_hip_ctx* c, int64_t n, int64_t p, bool packed = false, uint8_t* adopt = nullptr);
 
 // `words` ("liabilities", "annotation priors", ...) are not driven from a context that holds a marker or row shard
 static inline int refuse_shards(jwas_hip_ctx* c, const char* words)

@@ -29,6 +29,7 @@ using namespace jw;
 static_assert(JWAS_HIP_MAX_TRAITS == kMaxT, "trait limit mismatch");
 static_assert(JWAS_HIP_MAX_STATES == kMaxStates, "state limit mismatch");
 static_assert(jwas_hip_ctx::kCounters == kNCounters, "counter count mismatch");
+static_assert(jwas_hip_ctx::kRowPad == kSliceRows, "row padding mismatch");
 
 static constexpr int kStatGrid = 128;
 static int row_allreduce(jwas_hip_ctx* c, void* dev, size_t count, bool f64);      // exact row shards: sum over the ranks
@@ -119,6 +120,7 @@ static void free_storage(jwas_hip_ctx* c)
     gwas_free(c);                       // (a session is bound to the matrix it was begun on)
     liab_free(c);                       // (the liabilities belong to the residual of this matrix)
     locpar_free(c);                     // (... and so do the location parameters' term layouts)
+    plink_free(c);                      // (a scan that was never committed: the load that replaces it was asked for instead)
     c->drop();                          // (genotypes, residual, weights, output rows, the chain's state)
     (void)hipFree(c->Q); (void)hipFree(c->qmean);
     c->Q = nullptr; c->qmean = nullptr; c->packed = false;
@@ -201,8 +203,11 @@ int64_t jwas_hip_estimate_bytes_storage(int64_t n, int64_t p, int32_t ntraits, i
     return bytes;
 }
 
-static int alloc_storage(jwas_hip_ctx* c, int64_t n, int64_t p, bool packed = false)
+}  // extern "C"
+
+int alloc_storage(jwas_hip_ctx* c, int64_t n, int64_t p, bool packed, uint8_t* adopt)      // (declared in ctx.hpp: session_plink.hip commits through it)
 {
+    struct Adopted { uint8_t* q; ~Adopted() { if (q) (void)hipFree(q); } } adopted{adopt};      // (freed on every early return)
     NEED(c, n > 0 && p > 0, JWAS_HIP_EINVAL, "genotype matrix must be non-empty (n=%lld, p=%lld)", (long long)n, (long long)p);
     NEED(c, p < (1ll << 31), JWAS_HIP_EUNSUP, "p=%lld exceeds the 2^31 marker limit of one context", (long long)p);
     HIPCHK(c, hipSetDevice(c->device));
@@ -252,10 +257,11 @@ static int alloc_storage(jwas_hip_ctx* c, int64_t n, int64_t p, bool packed = fa
     HIPCHK(c, hipMemGetInfo(&fb, &tb));
     // (packed: + 1 KB -- the last 1024-row slice of the LAST column may reach past the column's end; what it reads there meets r = 0)
     const size_t need = packed ? (size_t)(c->ld >> 2) * p + 1024 : (size_t)4 * c->ld * p;
-    NEED(c, need < fb, JWAS_HIP_ENOMEM, "genotype matrix needs %.2f GB but only %.2f GB of HBM is free", need / 1e9, fb / 1e9);
+    NEED(c, adopt || need < fb, JWAS_HIP_ENOMEM, "genotype matrix needs %.2f GB but only %.2f GB of HBM is free", need / 1e9, fb / 1e9);
     c->packed = packed;
     if (packed) {
-        HIPCHK(c, hipMalloc(&c->Q, need));
+        if (adopt) { c->Q = adopt; adopted.q = nullptr; }
+        else HIPCHK(c, hipMalloc(&c->Q, need));
         HIPCHK(c, hipMalloc(&c->qmean, sizeof(float) * p));
     } else HIPCHK(c, c->load_mem.alloc(&c->X, need));
     {   // unit residual weights by default
@@ -278,6 +284,8 @@ static int alloc_storage(jwas_hip_ctx* c, int64_t n, int64_t p, bool packed = fa
     HIPCHK(c, hipHostMalloc(&c->host_buf, sizeof(double) * ((size_t)c->nslices * (kMaxT * kMaxT + kMaxT) + kStatGrid * kNStat + 64)));
     return JWAS_HIP_OK;
 }
+
+extern "C" {
 
 int jwas_hip_load_dense_f32(jwas_hip_ctx* c, const float* Xh, int64_t n, int64_t p, int64_t ld_host)
 {

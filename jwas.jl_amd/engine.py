@@ -179,6 +179,37 @@ class HipEngine:
         self.n, self.p = int(n), int(p)
         self.method, self.block_size = None, 0
 
+    # PLINK 1 binary filesets (jwas_hip_plink_*; the host side is plink.load_plink) ----------------
+    def plink_scan(self, bed_path, n_file, p_file, rows=None, count_a1=True):
+        """Transcodes every marker of a variant-major .bed file into a staging buffer on the device.  rows: the file rows of the
+        individuals to keep, in the order wanted (None: all, file order).  Returns p_file x 4 int64: the kept individuals of every
+        marker with code 0, 1, 2 (copies of the counted allele) and 3 (missing).  plink_commit / plink_discard end the scan."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        counts = np.empty((int(p_file), 4), dtype=np.int64)
+        self._chk(self._L.jwas_hip_plink_scan(self._h, str(bed_path).encode(), int(n_file), int(p_file), _ptr(r), 0 if r is None else r.size,
+                                              int(bool(count_a1)), _ptr(counts)))
+        return counts
+
+    def plink_commit(self, selected, means, centered=True):
+        """The scanned markers `selected` (0-based file indices, strictly ascending) become the context's packed storage."""
+        sel = np.ascontiguousarray(selected, dtype=np.int64)
+        means = np.ascontiguousarray(means, dtype=np.float32)
+        if sel.ndim != 1 or means.shape != sel.shape:
+            raise ValueError("one marker mean per selected marker is required")
+        self._chk(self._L.jwas_hip_plink_commit(self._h, _ptr(sel), sel.size, _ptr(means), int(bool(centered))))
+        info = self.storage_info()
+        self.n, self.p = info["n"], info["p"]
+        self.method, self.block_size = None, 0
+
+    def plink_discard(self):
+        self._chk(self._L.jwas_hip_plink_discard(self._h))
+
+    def get_packed2bit(self, j0, count):
+        """The packed rows of markers [j0, j0 + count): count x cld(n,4) uint8, the payload of a .jgb2 file."""
+        out = np.empty((int(count), (self.n + 3) // 4), dtype=np.uint8)
+        self._chk(self._L.jwas_hip_get_packed2bit(self._h, int(j0), int(count), _ptr(out), out.shape[1]))
+        return out
+
     def storage_info(self):
         k, n, p, b = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self._L.jwas_hip_storage_info(self._h, C.byref(k), C.byref(n), C.byref(p), C.byref(b)))

@@ -142,11 +142,36 @@ def _prepare_from_file_lowmem(path, prefix, *, separator, header, missing_value,
 def prepare_streaming_genotypes(genotypes, output_prefix=None, *, obs_ids=None, marker_ids=None, missing_value=9.0,
                                 quality_control=True, MAF=0.01, center=True, separator=",", header=True,
                                 conversion_mode="lowmem", auto_dense_max_bytes=2 ** 30, chunk_rows=4096,
-                                disk_guard_ratio=0.9):
+                                disk_guard_ratio=0.9, input_format="text", keep=None, counted_allele="A1", device=0, engine=None):
     """genotypes: n x p array of 0/1/2 (missing_value = missing), or the path of a delimited text file (first column =
     individual IDs).  Writes <output_prefix>.{jgb2,meta,...} and returns the prefix (streaming_genotypes.jl:819-877).
     File input: conversion_mode = "lowmem" (default, like the reference; two chunked passes, memory = one row chunk),
-    "dense" (load the matrix) or "auto" (dense when n*p*4 <= auto_dense_max_bytes)."""
+    "dense" (load the matrix) or "auto" (dense when n*p*4 <= auto_dense_max_bytes).
+    input_format="plink": genotypes is a PLINK 1 binary fileset (the prefix, or the path of its .bed / .bim / .fam); the device
+    transcodes it (plink.load_plink on `engine`, or on a HipEngine of `device` made for the call) and the backend is written from
+    what it holds.  keep: the IDs wanted, in the order wanted (None: all); counted_allele: "A1" or "A2"."""
+    if input_format not in ("text", "plink"):
+        raise ValueError('input_format must be "text" or "plink".')
+    if input_format == "plink":
+        if not isinstance(genotypes, (str, os.PathLike)):
+            raise ValueError('input_format="plink" requires the path or prefix of a .bed/.bim/.fam fileset.')
+        from . import plink
+        bfile = plink.resolve_bfile(genotypes)
+        prefix = resolve_prefix(output_prefix if output_prefix is not None else bfile + "_stream")
+        os.makedirs(os.path.dirname(prefix) or ".", exist_ok=True)
+        own = engine is None
+        if own:
+            from .engine import HipEngine
+            engine = HipEngine(device)
+        try:
+            backend = plink.load_plink(engine, bfile, keep=keep, counted_allele=counted_allele, quality_control=quality_control,
+                                       MAF=MAF, center=center)
+            return plink.write_streaming_backend(engine, backend, prefix)
+        finally:
+            if own:
+                engine.close()
+    if keep is not None or engine is not None:
+        raise ValueError('keep= and engine= belong to input_format="plink".')
     if isinstance(genotypes, (str, os.PathLike)):
         import pandas as pd
         path = str(genotypes)
