@@ -207,7 +207,12 @@ int  jwas_hip_alloc_dense_f32(jwas_hip_ctx* ctx, int64_t n, int64_t p);
  * jwas_hip_load_jgb2 replaces load_streaming_backend (:884-971): `path` is the prefix, or <prefix>.meta / .jgb2;
  * it reads the tab-separated manifest (nObs, nMarkers, stride_bytes, centered, data_path, mean_path) and the
  * .mean.f32 sidecar.  x'x is recomputed on the device; a host that wants the .xpRinvx.f32 sidecar values instead
- * passes them to jwas_hip_set_xpx after jwas_hip_setup_blocks. */
+ * passes them to jwas_hip_set_xpx after jwas_hip_setup_blocks.
+ * Pad fields: when n is no multiple of 4 the unused fields of a marker's last byte (individuals n .. 4*cld(n,4)-1) may hold
+ * anything.  Both loaders copy the cld(n,4) bytes of a marker as they are and no kernel reads those fields: every accessor masks
+ * the rows >= n (PackedCols::load1 / load4 / the update role's row mask), so decoded columns, inner products, X*alpha, window sums
+ * and sweeps do not depend on them (tests/test_gpu_packed.py).  Only jwas_hip_get_packed2bit, which returns the bytes as loaded,
+ * shows them.  Bytes of a host row beyond cld(n,4) (stride_bytes > cld(n,4)) are not copied. */
 int  jwas_hip_load_jgb2(jwas_hip_ctx* ctx, const char* path);
 int  jwas_hip_load_packed2bit(jwas_hip_ctx* ctx, const uint8_t* payload, int64_t n, int64_t p, int64_t stride_bytes,
                               const float* marker_means, int32_t centered);

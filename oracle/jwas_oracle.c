@@ -135,7 +135,8 @@ static float dot_acc(const float* a, const float* b, int64_t n, int acc)
  *     sum_i (v_i - mu) w_i r_i = sum_i c_i w_i r_i - mu (R - M),   c_i = code (0 for a missing one), R = sum_i w_i r_i, M = sum_missing w_i r_i
  * (decode_marker!, streaming_genotypes.jl:978-1002; uncentred: + mu M), every sum in fp64 over exact products, rounded to fp32
  * once.  orc_set_packed_source (harness state): the codes of the matrix X the sweeps are called with, one code 0..3 per byte,
- * column-major [p][n]; NULL = off (the decoded matrix's own products, as for dense storage). */
+ * column-major [p][n]; NULL = off (the decoded matrix's own products, as for dense storage).  ORC_ACC_F64 / ORC_ACC_F32 sum the
+ * rows serially (below); ORC_ACC_DEVICE sums them in the kernel's own association order (dot_xr_wide_order). */
 static const uint8_t* g_pk_codes = NULL;
 static const float* g_pk_means = NULL;
 static const float* g_pk_X = NULL;
@@ -145,12 +146,63 @@ void orc_set_packed_source(const uint8_t* codes, const float* means, int centere
 {
     g_pk_codes = codes; g_pk_means = means; g_pk_centered = centered; g_pk_X = X; g_pk_n = n; g_pk_ld = ld;
 }
+/* ORC_ACC_DEVICE on packed storage: the same factored sum in the ASSOCIATION ORDER of update_role_wide, so that the oracle's
+ * chain and the packed device chain agree in every bit (as dot_device_order does for dense storage).  Restated from the kernel:
+ *   - a wave owns a 1024-row slice, lane l its rows 16l .. 16l+15 (one dword of the column); rows >= n carry w r = +0 and drop
+ *     out of every sum whatever code their field holds;
+ *   - wr_i = fl32(r_i w_i) (unit weights: exact);  acc = 0, acc = fma(code_i, wr_i, acc) for i = 0..15 with a missing code
+ *     counted as 3;  sm = the plain sum of the missing rows' wr_i in row order;  acc = fma(-3, sm, acc).  The kernel runs
+ *     this patch only when some lane of the wave holds a missing code in the batch of 8 columns; where it runs on a lane
+ *     without one it adds -3 * 0 = -0, which changes no bit (acc is never -0: it starts at +0 and x + (+0) is never -0),
+ *     so the condition does not enter the result;
+ *   - Rl = the lane's own plain sum of (double)wr_i in row order;  centred: acc = fma(-mu, Rl - sm, acc), uncentred:
+ *     acc = fma(mu, sm, acc);
+ *   - the 64 lane values fold pairwise at distances 32 .. 1 (butterfly8: every step adds two values, so which lane keeps
+ *     the sum does not matter); the waves of a row group (spg slices) add in order 0..7 from 0.0, the row groups in order
+ *     (sum_partials), and the total is rounded to fp32 once.
+ * spg = orc_set_device_order (the packed context's jwas_hip_update_geometry). */
+static float dot_xr_wide_order(const uint8_t* c, double mu, int centered, const float* r, int64_t n, const float* w)
+{
+    const int64_t nsl = (n + 1023) / 1024, nrg = (nsl + g_dev_spg - 1) / g_dev_spg;
+    double total = 0.0;
+    for (int64_t rg = 0; rg < nrg; ++rg) {
+        double P = 0.0;
+        for (int wv = 0; wv < 8; ++wv) {
+            double T = 0.0;
+            const int64_t sl = rg * g_dev_spg + wv;
+            if (wv < g_dev_spg && sl < nsl) {
+                double L[64];
+                for (int l = 0; l < 64; ++l) {
+                    const int64_t i0 = sl * 1024 + 16 * l;
+                    double a = 0.0, Rl = 0.0, sm = 0.0;
+                    for (int q = 0; q < 16; ++q) {
+                        const int64_t i = i0 + q;
+                        const float wr = i < n ? (w ? r[i] * w[i] : r[i]) : 0.0f;
+                        const unsigned code = i < n ? c[i] : 0u;
+                        a = fma((double)code, (double)wr, a);
+                        if (code == 3u) sm += (double)wr;
+                        Rl += (double)wr;
+                    }
+                    a = fma(-3.0, sm, a);
+                    L[l] = centered ? fma(-mu, Rl - sm, a) : fma(mu, sm, a);
+                }
+                for (int d = 32; d >= 1; d >>= 1) for (int i = 0; i < d; ++i) L[i] = L[i] + L[i + d];
+                T = L[0];
+            }
+            P += T;
+        }
+        total += P;
+    }
+    return (float)total;
+}
+
 static float dot_xr(const float* x, const float* r, int64_t n, int acc)
 {
     if (!g_pk_codes) return dot_acc(x, r, n, acc);
     const int64_t j = (x - g_pk_X) / g_pk_ld;
     const uint8_t* c = g_pk_codes + j * g_pk_n;
     const double mu = (double)g_pk_means[j];
+    if (acc == ORC_ACC_DEVICE) return dot_xr_wide_order(c, mu, g_pk_centered, r, n, g_rinv);
     double s1 = 0.0, R = 0.0, M = 0.0;
     for (int64_t i = 0; i < n; ++i) {
         const float wr = g_rinv ? r[i] * g_rinv[i] : r[i];
@@ -158,6 +210,12 @@ static float dot_xr(const float* x, const float* r, int64_t n, int acc)
         R += (double)wr;
     }
     return (float)(g_pk_centered ? fma(-mu, R - M, s1) : fma(mu, M, s1));
+}
+/* x_j' R^-1 r of marker j of the packed source as the sweeps form it (tests/test_oracle_kat.py); NaN when no source is set. */
+float orc_packed_rhs(int64_t j, const float* r, int acc)
+{
+    if (!g_pk_codes) return NAN;
+    return dot_xr(g_pk_X + j * g_pk_ld, r, g_pk_n, acc);
 }
 
 static void axpy_f32(float a, const float* x, float* y, int64_t n)

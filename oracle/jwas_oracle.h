@@ -171,8 +171,12 @@ void orc_set_abc_rule_d(int on);
  * the lookahead forms' full blocks as triangular solves.  1 = on, 0 = the sequential chain (default). */
 void orc_set_section_solve(int on);
 /* The block right-hand sides in the 2-bit packed update role's own order (see dot_xr): codes [p][n], one code 0..3 per byte,
- * of the matrix X the sweeps are called with; NULL = off. */
+ * of the matrix X the sweeps are called with; NULL = off.  With ORC_ACC_DEVICE the sum takes update_role_wide's association
+ * order (1024-row slices, 16 rows per lane, the centring per lane; dot_xr_wide_order) with spg = orc_set_device_order of the
+ * PACKED context's geometry: bit for bit the device's.  The other modes sum the rows serially. */
 void orc_set_packed_source(const uint8_t* codes, const float* means, int centered, const float* X, int64_t n, int64_t ld);
+/* x_j' R^-1 r of marker j of the packed source in the order the sweeps form it (r: n floats); NaN when no source is set. */
+float orc_packed_rhs(int64_t j, const float* r, int acc);
 void orc_section_solve_counts(int64_t* solved, int64_t* fallbacks, int reset);
 int64_t orc_section_solve_exceptions(void);      /* exceptions taken inside the solved sections since the last reset */
 /* One InverseWishart(df, scale + b_j b_j') draw per marker (variance_components.jl:181-186; df = the reference's df + 1),

@@ -145,7 +145,8 @@ RULE_D = True        # (tests switch the rule off to compare with the literal op
 def set_packed_source(codes, means, centered, X):
     """The block right-hand sides in the 2-bit packed update role's own order (jwas_oracle.c dot_xr): codes (n x p, 0..3; 3 =
     missing) of the matrix X (the decoded, Fortran-ordered float32 matrix the sweeps are called with).  codes=None switches it
-    off.  The arrays are borrowed: keep them alive while the mode is on."""
+    off.  The arrays are borrowed: keep them alive while the mode is on.  Sweeps with acc=ACC_DEVICE sum in update_role_wide's
+    association order (set_device_order(spg) of the packed context): bit for bit the device's; other modes sum serially."""
     global _PK_KEEP
     if codes is None:
         lib().orc_set_packed_source(None, None, C.c_int(1), None, C.c_int64(0), C.c_int64(0))
@@ -160,6 +161,16 @@ def set_packed_source(codes, means, centered, X):
 
 
 _PK_KEEP = None
+
+
+def packed_rhs(j, r, acc=ACC_F64):
+    """x_j' R^-1 r of marker j of the packed source (set_packed_source, set_weights) as the sweeps form it: acc=ACC_DEVICE in
+    the packed update role's association order (set_device_order(spg) of the packed context first), otherwise serially."""
+    r = _f32(r)
+    assert _PK_KEEP is not None and r.shape == (_PK_KEEP[0].shape[1],)
+    f = lib().orc_packed_rhs
+    f.restype = C.c_float
+    return float(f(C.c_int64(int(j)), _p(r, _f32p), C.c_int(acc)))
 
 
 def set_section_solve(on):

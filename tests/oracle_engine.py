@@ -161,7 +161,9 @@ class OracleEngine:
 
     def set_packed_source(self, codes, means, centered=True):
         """Block right-hand sides in the 2-bit packed update role's own order (oracle.set_packed_source) for THIS engine's matrix:
-        codes n x p (0..3, 3 = missing) whose decoded form was loaded with load_dense.  codes=None: off."""
+        codes n x p (0..3, 3 = missing) whose decoded form was loaded with load_dense.  codes=None: off.  An engine built with
+        acc=ACC_DEVICE sums them in the kernel's association order (oracle.set_device_order(spg) of the packed context): the
+        bit-for-bit harness of tests/test_gpu_packed_fuzz.py."""
         if codes is None:
             O.set_packed_source(None, None, True, None)
         else:

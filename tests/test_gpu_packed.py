@@ -243,3 +243,112 @@ def test_packed_grouped_launches_match_the_oracle(engines, method, bs, m, n):
         np.testing.assert_allclose(packed.get_residual(0), orc.get_residual(0), rtol=0, atol=3e-5)
     finally:
         orc.set_packed_source(None, None)
+
+
+def _codes_means_decoded(n, p, seed, centered):
+    d, raw = _packed_inputs(n, p, seed)
+    miss = raw == 9
+    codes = np.where(miss, 3, raw).astype(np.uint8)
+    means = np.array([raw[~miss[:, j], j].mean(dtype=np.float32) for j in range(p)], dtype=np.float32)
+    v = np.where(miss, means[None, :], raw.astype(np.float32)).astype(np.float32)
+    X = np.asfortranarray((v - means[None, :]).astype(np.float32) if centered else v)
+    return d, codes, means, X
+
+
+@pytest.mark.parametrize("n,centered", [(403, True), (1021, False)])
+def test_weighted_inner_products_decoded_from_packed_bytes(engines, n, centered):
+    """x'R^-1 x and X_b'R^-1 X_b with residual weights on packed storage: equal to the dense context on the decoded matrix bit for
+    bit in both Gram modes, and in "f64" mode equal to X' (w .* X) -- the weight on the right operand, fl32(w_i x_ic), as every
+    inner product of the path carries it -- to within one Float32 rounding of each entry, 2^-24 |G_ac|, plus what the two fp64
+    sums (the device's and the reference's, n terms each) can differ by, 2 n 2^-53 sum_i |x_ia| |fl32(w_i x_ic)|.
+    With the weight rounded onto one operand, X' (w .* X) is itself not symmetric in the last bits (entry (a, c) rounds w x_c,
+    entry (c, a) rounds w x_a: at n = 403 the two differ by up to a few 1e-7 on entries of a few units, more than one rounding
+    of the smaller ones).  The device forms the entries a >= c that way (k_gram_f64, as orc_gram) and MIRRORS them, so a Gram is
+    exactly symmetric: the bound is asserted on the lower triangle, where the device's definition is the expression above, and
+    the upper triangle must be its exact mirror image."""
+    dense, packed = engines
+    p = 130
+    _, codes, means, X = _codes_means_decoded(n, p, 5, centered)
+    w = np.random.default_rng(n).uniform(0.3, 3.0, n).astype(np.float32)
+    packed.load_packed2bit(S.pack_2bit(codes), n, means, centered=centered)
+    dense.load_dense(X)
+    try:
+        for e in (dense, packed):
+            e.set_weights(w)
+        wX = (w[:, None] * X).astype(np.float32).astype(np.float64)
+        G = X.astype(np.float64).T @ wX
+        tol = 2.0 ** -24 * np.abs(G) + 2 * n * 2.0 ** -53 * (np.abs(X.astype(np.float64)).T @ np.abs(wX))
+        for mode in ("f64", "mfma"):
+            for e in (dense, packed):
+                e.setup_blocks(64, mode)
+            xp = packed.xpx()
+            assert np.array_equal(xp, dense.xpx())
+            assert dense.nblocks == 3
+            for i in range(dense.nblocks):
+                gp = packed.gram(i)
+                assert np.array_equal(gp, dense.gram(i)), (mode, i)
+                if mode == "f64":
+                    sl = slice(64 * i, min(64 * i + 64, p))
+                    lower = np.tril_indices(gp.shape[0])
+                    err = np.abs(gp.astype(np.float64) - G[sl, sl])
+                    assert (err[lower] <= tol[sl, sl][lower]).all(), (i, float((err / tol[sl, sl])[lower].max()))
+                    assert np.array_equal(gp, gp.T), i
+            if mode == "f64":
+                assert (np.abs(xp.astype(np.float64) - np.diag(G)) <= np.diag(tol)).all()
+    finally:
+        for e in (dense, packed):
+            e.set_weights(None)
+
+
+@pytest.mark.parametrize("n,stray", [(401, 1), (401, 2), (401, 3), (403, 2), (1022, 3)])
+def test_stray_fields_of_the_last_byte_are_never_read(engines, n, stray):
+    """The contract of jwas_hip_load_packed2bit / jwas_hip_load_jgb2 (include/jwas_hip.h): when n is no multiple of 4, the
+    unused fields of every marker's last byte may hold anything -- every kernel masks the rows >= n.  With those fields set to 1,
+    2 or 3 (a missing code), the decoded columns, x'x, the Grams of both modes, X alpha, the window sums and six BayesC sweeps equal
+    those of the clean payload bit for bit.  jwas_hip_get_packed2bit is exempt: it returns the bytes as they were loaded."""
+    clean, dirty = engines
+    p = 150
+    d, codes, means, _ = _codes_means_decoded(n, p, 9, True)
+    payload = S.pack_2bit(codes)
+    mask = sum(stray << (2 * k) for k in range(n % 4, 4))
+    assert n % 4 != 0 and not (payload[:, -1] & mask).any()
+    soiled = payload.copy()
+    soiled[:, -1] |= mask
+    clean.load_packed2bit(payload, n, means, centered=True)
+    dirty.load_packed2bit(soiled, n, means, centered=True)
+    assert np.array_equal(clean.get_columns(0, p), dirty.get_columns(0, p))
+    for mode in ("mfma", "f64"):
+        for e in (clean, dirty):
+            e.setup_blocks(64, mode)
+        assert np.array_equal(clean.xpx(), dirty.xpx())
+        for i in range(clean.nblocks):
+            assert np.array_equal(clean.gram(i), dirty.gram(i)), (mode, i)
+    y = d["y"] - d["y"].mean()
+    rng = np.random.default_rng(stray)
+    a = rng.standard_normal(p).astype(np.float32)
+    a_sparse = np.zeros(p, dtype=np.float32); a_sparse[rng.choice(p, 9, replace=False)] = 1.5
+    nz = np.flatnonzero(a_sparse)
+    wptr = np.array([0, 4, nz.size], dtype=np.int32)
+    for e in (clean, dirty):
+        e.init_state("BayesC")
+    for alpha in (a, a_sparse):
+        for e in (clean, dirty):
+            e.set_state(alpha=alpha)
+        assert np.array_equal(clean.mul_alpha(), dirty.mul_alpha())
+    sc, qc = clean.window_sums(wptr, nz.astype(np.int32), a_sparse[nz])
+    sd, qd = dirty.window_sums(wptr, nz.astype(np.int32), a_sparse[nz])
+    assert np.array_equal(sc, sd) and np.array_equal(qc, qd)
+    for e in (clean, dirty):
+        e.init_state("BayesC")
+        e.set_residual(y)
+    kw = dict(vare=np.float32(0.5 * y.var()), var_effect=np.float32(0.5 * y.var() / (0.1 * 0.4 * p)), pi=0.8)
+    moved = 0
+    for it in range(1, 7):
+        s1 = clean.sweep(iteration=it, seed=4, **kw)
+        s2 = dirty.sweep(iteration=it, seed=4, **kw)
+        assert s1["n_events"] == s2["n_events"], f"iteration {it}"
+        moved += int(s1["n_events"])
+    assert moved > 20
+    for x1, x2 in zip(clean.get_state(0), dirty.get_state(0)):
+        assert np.array_equal(x1, x2)
+    assert np.array_equal(clean.get_residual(0), dirty.get_residual(0))

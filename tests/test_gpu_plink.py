@@ -130,6 +130,31 @@ def test_every_marker_kept_and_uncentered(engines, tmp_path_factory):
     assert np.array_equal(dev.get_columns(0, p), S.decode_markers(S.load_streaming_backend(host)))
 
 
+def test_gather_from_global_memory(engines, tmp_path):
+    """A raw row of more than 60 KB (n_file > 245 760) does not fit the LDS staging of the gather: k_plink_transcode<kGatherGlobal>
+    picks the kept individuals' fields out of global memory.  n_file = 245 800, five markers whose bytes are random (every byte
+    is four valid fields), a shuffled subset of 300 individuals that holds the file's first and last one, both counted alleles:
+    the counts and the committed payload against the per-individual reference reader."""
+    dev, _ = engines
+    n_file, p, nkeep = 245_800, 5, 300
+    bpm = (n_file + 3) // 4
+    assert -(-bpm // 16) * 16 > 60 << 10                                         # (kMaxLdsRow, csrc/plink.hpp)
+    rng = np.random.default_rng(n_file)
+    bed = tmp_path / "wide.bed"
+    bed.write_bytes(PR.MAGIC + rng.integers(0, 256, size=(p, bpm), dtype=np.uint8).tobytes())
+    inner = rng.permutation(n_file - 2)[:nkeep - 2] + 1
+    rows = np.concatenate([[n_file - 1], inner[:100], [0], inner[100:]]).astype(np.int64)
+    assert rows.size == nkeep == np.unique(rows).size
+    for counted in ("A1", "A2"):
+        codes = PR.codes_of(PR.read_bed(bed, n_file, p, counted)[rows])
+        assert all((codes == c).any() for c in range(4))
+        counts = dev.plink_scan(bed, n_file, p, rows, counted == "A1")
+        assert np.array_equal(counts, np.stack([(codes == c).sum(axis=0) for c in range(4)], axis=1))
+        dev.plink_commit(np.arange(p), np.ones(p, dtype=np.float32))
+        assert (dev.n, dev.p) == (nkeep, p)
+        assert np.array_equal(dev.get_packed2bit(0, p), PR.pack_codes(codes))
+
+
 def test_hand_written_file(engines, tmp_path):
     dev, _ = engines
     (tmp_path / "hand.bed").write_bytes(HAND_BED)

@@ -692,3 +692,71 @@ def test_packed_order_right_hand_side_equals_the_decoded_dot_product():
             scale = max(float(np.abs(res["decoded"][0][0]).max()), 1e-3)
             np.testing.assert_allclose(res["packed"][0][0], res["decoded"][0][0], rtol=0, atol=1e-4 * scale)
             assert (res["packed"][0][2] == res["decoded"][0][2]).mean() > 0.98
+
+
+@pytest.mark.parametrize("n", [1, 15, 17, 1024, 1025, 2300])
+@pytest.mark.parametrize("missing", ["none", "5%", "lane"])
+@pytest.mark.parametrize("weights", [False, True])
+@pytest.mark.parametrize("centered", [True, False])
+def test_packed_device_order_right_hand_side_against_exact_arithmetic(n, missing, weights, centered):
+    """The oracle's restatement of update_role_wide's association order (dot_xr with a packed source and ACC_DEVICE: 1024-row
+    slices, 16 rows per lane, the centring per lane, butterfly fold, waves, row groups) against plain mathematics: the value
+    S = sum_i fl32(v_i - mu) fl32(w_i r_i) of the decoded Float32 column, summed EXACTLY (fractions.Fraction).
+
+    The bound is derived, not measured.  Write wr_i = fl32(w_i r_i), E = the exact value of the factored form the kernel sums,
+    T = what the fp64 operations make of it, C = fl32(T) the value under test.
+      (1) decode: centred, E = sum_observed (c_i - mu) wr_i, while S carries x_i = fl32(c_i - mu) (a missing row is mu - mu = 0
+          in both): |S - E| <= e1 = 2^-24 sum_i |c_i - mu| |wr_i|  (round to nearest: |fl32(x) - x| <= 2^-24 |x|).  Uncentred,
+          x_i is c_i or mu, both Float32 already, and E = S: e1 = 0.
+      (2) fp64 accumulation: every leaf the kernel adds is one of c_i wr_i (a missing code counted as 3: <= 3 |wr_i|), the
+          patch 3 wr_i, mu wr_i inside mu Rl and mu wr_i inside mu sm -- their magnitudes sum to at most A = sum_i (6 + 2 |mu|)
+          |wr_i| -- and every leaf passes through at most 16 + 16 + 2 (lane) + 6 (fold) + 8 (waves) + row groups <= n + 64
+          roundings of relative size 2^-53, whatever the association: |T - E| <= e2 = (n + 64) 2^-53 A (first order; the
+          factor carries more than the second-order slack).  The serial mode's chain of n additions obeys the same e2.
+      (3) the one rounding to Float32: |C - T| <= 2^-24 |T| <= 2^-24 (|S| + e1 + e2), plus 2^-150 should T be subnormal.
+    So |C - S| <= B = 2^-24 (|S| + e1 + e2) + e1 + e2 + 2^-150.  The same B is asserted between the new mode and the serial
+    packed mode (their fp64 values differ by at most 2 e2, so the Float32 values are the same or neighbours).
+    Cases: centred and uncentred storage, unit and heterogeneous weights, no missing code / 5 % / a marker whose 16-row lane
+    is missing entirely, n = 1 (one row), 15 and 17 (either side of a lane), 1024 and 1025 (either side of a slice), 2300
+    (a ragged third slice; also with two slices per row group: two row groups)."""
+    from fractions import Fraction
+    rng = np.random.default_rng([n, weights, centered, len(missing)])
+    p = 4
+    codes = rng.integers(0, 3, size=(n, p)).astype(np.uint8)
+    if missing == "5%":
+        codes[rng.random((n, p)) < 0.05] = 3
+    elif missing == "lane":
+        lane0 = 16 * int(rng.integers(0, (n + 15) // 16))
+        codes[lane0:lane0 + 16, 1] = 3
+        codes[rng.random((n, p)) < 0.02] = 3
+    miss = codes == 3
+    means = np.array([codes[~miss[:, j], j].mean(dtype=np.float32) if (~miss[:, j]).any() else np.float32(0.7)
+                      for j in range(p)], dtype=np.float32)
+    v = np.where(miss, means[None, :], codes.astype(np.float32)).astype(np.float32)
+    X = np.asfortranarray((v - means[None, :]).astype(np.float32) if centered else v)
+    r = rng.standard_normal(n).astype(np.float32)
+    w = rng.uniform(0.3, 3.0, n).astype(np.float32) if weights else None
+    wr = (r * w).astype(np.float32) if weights else r
+    wr_abs = np.abs(wr.astype(np.float64))
+    O.set_packed_source(codes, means, centered, X)
+    O.set_weights(w)
+    try:
+        for spg in ((8, 2) if n == 2300 else (8,)):
+            O.set_device_order(spg)
+            for j in range(p):
+                S = sum((Fraction(float(X[i, j])) * Fraction(float(wr[i])) for i in range(n)), Fraction(0))
+                mu = float(means[j])
+                cm = np.where(miss[:, j], 0.0, np.abs(codes[:, j].astype(np.float64) - mu))
+                e1 = 2.0 ** -24 * float(cm @ wr_abs) if centered else 0.0
+                e2 = (n + 64) * 2.0 ** -53 * (6 + 2 * abs(mu)) * float(wr_abs.sum())
+                B = 2.0 ** -24 * (abs(float(S)) + e1 + e2) + e1 + e2 + 2.0 ** -150
+                B *= 1 + 2.0 ** -40                                       # (the bound itself is evaluated in fp64)
+                dev = O.packed_rhs(j, r, O.ACC_DEVICE)
+                ser = O.packed_rhs(j, r, O.ACC_F64)
+                assert abs(Fraction(dev) - S) <= B, (j, spg, dev, float(S), B)
+                assert abs(Fraction(ser) - S) <= B, (j, spg, ser, float(S), B)
+                assert abs(dev - ser) <= B, (j, spg, dev, ser, B)
+    finally:
+        O.set_device_order(8)
+        O.set_weights(None)
+        O.set_packed_source(None, None, True, None)
