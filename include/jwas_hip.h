@@ -918,6 +918,14 @@ int  jwas_hip_mtj_end(jwas_hip_ctx* ctx);
  * that is not positive and finite. */
 #define JWAS_HIP_GRM_CHUNK 64
 int  jwas_hip_grm(jwas_hip_ctx* ctx, const void* divisor_p, void* K_host);
+/* The same matrix (readgenotypes.jl:403-408) of the context's 2-bit packed genotypes (jwas_hip_load_packed2bit, jwas_hip_load_jgb2,
+ * jwas_hip_plink_commit), Float32: X is what the storage decodes to (code 3 -> the marker mean; minus the mean when centered), and K is
+ * bit for bit what jwas_hip_grm returns for the dense matrix of those columns -- the tiles, the fp32 chunks and their fold are the same;
+ * the four possible x / divisor[j] of a marker are divided once per workgroup, by the same IEEE division.  The stray fields of a
+ * marker's last byte are not read as genotypes.  The storage, the state and any open session are left untouched.
+ * Errors: JWAS_HIP_EINVAL for a NULL context or argument and for a divisor that is not positive and finite; JWAS_HIP_ESTATE when the
+ * context holds no 2-bit packed genotypes; JWAS_HIP_EUNSUP in a Float64 context, on shards and beyond the tile grid; JWAS_HIP_ENOMEM. */
+int  jwas_hip_grm_packed2bit(jwas_hip_ctx* ctx, const float* divisor_p, float* K_host);
 /* Device bytes of that call beyond the loaded matrix (pure). */
 int64_t jwas_hip_grm_estimate_bytes(int64_t n, int64_t p, int32_t precision_bits);
 /* The sampler (markers/BayesianAlphabet/GBLUP.jl): the context's dense matrix is n x n, column i the i-th eigenvector l_i of the

@@ -764,6 +764,12 @@ function hip_grm(b::HipBackend, divisor::Vector{T}, n::Integer) where {T<:Union{
     hip_check(b.ctx, ccall((:jwas_hip_grm, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), b.ctx, divisor, K))
     return K
 end
+# ... of the context's 2-bit packed genotypes (hip_load_jgb2!, a committed PLINK scan): Float32, the bits of hip_grm on the decoded columns
+function hip_grm_packed(b::HipBackend, divisor::Vector{Float32}, n::Integer)
+    K = Matrix{Float32}(undef, n, n)
+    hip_check(b.ctx, ccall((:jwas_hip_grm_packed2bit, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), b.ctx, divisor, K))
+    return K
+end
 hip_grm_estimate_bytes(n::Integer, p::Integer, bits::Integer=32) =
     ccall((:jwas_hip_grm_estimate_bytes, LIBJWAS_HIP), Int64, (Int64, Int64, Int32), n, p, bits)
 hip_gblup_begin!(b::HipBackend, D::Vector{Float64}) =

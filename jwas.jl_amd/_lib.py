@@ -349,6 +349,7 @@ PROTOTYPES = {
     "jwas_hip_mtj_mul_alpha": (_INT, [_vp, _i32, _i32, _vp]),
     "jwas_hip_mtj_end": (_INT, [_vp]),
     "jwas_hip_grm": (_INT, [_vp, _vp, _vp]),
+    "jwas_hip_grm_packed2bit": (_INT, [_vp, _vp, _vp]),
     "jwas_hip_grm_estimate_bytes": (_i64, [_i64, _i64, _i32]),
     "jwas_hip_gblup_begin": (_INT, [_vp, _vp]),
     "jwas_hip_gblup_step": (_INT, [_vp, _P(GblupParams), _P(GblupStats)]),

@@ -226,21 +226,108 @@ def _impute_center_qc(genotypes, markerID, data_type, quality_control, MAF, miss
     return genotypes, markerID, p, sum2pq, annotation_matrix
 
 
-def genomic_relationship_matrix(file, *, separator=",", header=True, center=True, quality_control=True, MAF=0.01, missing_value=9.0,
-                                double_precision=False, device=0, _engine=None):
+def _grm_divisor(p, data_type):
+    """sqrt(2 p (1 - p)) of the allele frequencies in the matrix's precision (readgenotypes.jl:406)."""
+    p = np.asarray(p, dtype=data_type)
+    divisor = np.sqrt(data_type(2.0) * p * (data_type(1.0) - p)).astype(data_type)
+    if not np.all(np.isfinite(divisor) & (divisor > 0)):
+        raise ValueError("genomic_relationship_matrix needs 0 < p < 1 for every marker (a fixed locus has 2p(1-p) = 0); use quality_control=True")
+    return divisor
+
+
+def _grm_frame(K, obsID):
+    import pandas as pd
+    out = pd.DataFrame(K, columns=[str(i) for i in obsID])
+    out.insert(0, "ID", [str(i) for i in obsID])
+    return out
+
+
+_TEXT_ONLY = object()         # default of the keywords that describe a text table: a binary input refuses them when they are given
+
+
+def _grm_binary(file, input_format, text_only, keep, counted_allele, id_column, center, quality_control, MAF, double_precision, device,
+                engine):
+    """genomic_relationship_matrix of 2-bit packed genotypes: a PLINK fileset, a prepared .jgb2 backend, or the resident engine of a
+    Genotypes object.  No text file and no dense host matrix are made."""
+    resident = isinstance(file, Genotypes)
+    what = "a Genotypes object" if resident else f'input_format="{input_format}"'
+    if double_precision:
+        raise ValueError(f"double_precision=True is not available with {what}: 2-bit packed storage has no Float64 path")
+    for name, value in text_only.items():
+        if value is not _TEXT_ONLY:
+            raise ValueError(f'{name}= describes a text table; it is not an argument of {what}')
+    if keep is not None and input_format != "plink":
+        raise ValueError('keep= belongs to input_format="plink"')
+    if resident:
+        engine = getattr(file, "device_backend", None)
+        if file.storage_mode != "device" or engine is None:
+            raise ValueError("genomic_relationship_matrix takes the Genotypes object of plink_genotypes / device_genotypes (genotypes "
+                             "resident on an engine); pass a storage=\"stream\" backend as its prefix with input_format=\"stream\"")
+        dense = engine.storage_info()["kind"] != "packed2bit"
+        if not hasattr(engine, "grm" if dense else "grm_packed"):
+            raise NotImplementedError(f"genomic_relationship_matrix needs an engine with {'grm' if dense else 'grm_packed'}; the package has no CPU fallback")
+        data_type = np.float64 if dense and getattr(engine, "precision", 32) == 64 else np.float32
+        divisor = _grm_divisor(file.alleleFreq, data_type)
+        return _grm_frame(engine.grm(divisor) if dense else engine.grm_packed(divisor), file.obsID)
+    if not isinstance(file, (str, os.PathLike)):
+        raise ValueError(f'{what} requires the prefix of a {".bed/.bim/.fam fileset" if input_format == "plink" else "backend produced by prepare_streaming_genotypes"}.')
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(device)
+    try:
+        if not hasattr(engine, "grm_packed"):
+            raise NotImplementedError("genomic_relationship_matrix needs an engine with grm_packed; the package has no CPU fallback")
+        if input_format == "plink":
+            from . import plink
+            backend = plink.load_plink(engine, file, keep=keep, counted_allele=counted_allele, quality_control=quality_control, MAF=MAF,
+                                       center=center, id_column=id_column)
+        else:
+            from .streaming import load_streaming_backend
+            backend = load_streaming_backend(file)
+            engine.load_jgb2(backend["prefix"])
+        K = engine.grm_packed(_grm_divisor(backend["allele_freq"], np.float32))
+    finally:
+        if own:
+            engine.close()
+    return _grm_frame(K, backend["obsID"])
+
+
+def genomic_relationship_matrix(file, *, separator=_TEXT_ONLY, header=_TEXT_ONLY, center=True, quality_control=True, MAF=0.01,
+                                missing_value=_TEXT_ONLY, double_precision=False, device=0, input_format="text", keep=None,
+                                counted_allele="A1", id_column="IID", _engine=None):
     """The genomic relationship matrix of a genotype covariate matrix, formed on the device (readgenotypes.jl:403-408):
     K = (Z Z' + 1e-5 I) / nMarkers with Z = genotypes ./ sqrt(2 p (1 - p)) after get_genotypes' host steps (missing values, centring,
-    the MAF filter).  `file` as in get_genotypes.  Returns a DataFrame with an ID column and one column per individual: what
-    get_genotypes(K, G, method="GBLUP") takes.  `_engine` (private) lets the test-suite inject an engine."""
-    import pandas as pd
+    the MAF filter).  Returns a DataFrame with an ID column and one column per individual: what get_genotypes(K, G, method="GBLUP")
+    takes.
+    input_format="text" (the default): `file` as in get_genotypes -- a delimited text file (separator=",", header=True,
+    missing_value=9.0), a DataFrame or a 2-D array -- read into a dense matrix of the asked precision.
+    input_format="plink": `file` is a PLINK 1 binary fileset (the prefix, or the path of its .bed / .bim / .fam), loaded straight into
+    2-bit packed device storage (plink.load_plink: keep = the IDs wanted in the order wanted, counted_allele "A1" or "A2", id_column
+    "IID" or "FID_IID", quality control as prepare_streaming_genotypes has it); the matrix is formed from the packed storage
+    (HipEngine.grm_packed) with the Float32 sqrt(2 p (1 - p)) of the scan's allele frequencies.  The rows are in keep's order.
+    input_format="stream": `file` is the prefix of a backend prepare_streaming_genotypes wrote; its centring and quality control are the
+    backend's.
+    `file` may also be the Genotypes object of plink_genotypes / device_genotypes: the matrix comes from its resident engine (grm_packed
+    on packed storage, grm on dense), which is neither reloaded nor closed, so the object still goes to runMCMC.
+    A binary input is Float32 (double_precision=True is refused: packed storage has no Float64 path) and refuses separator, header and
+    missing_value.  `_engine` (private) lets the test-suite inject an engine."""
+    if input_format not in ("text", "plink", "stream"):
+        raise ValueError('input_format must be "text", "plink" or "stream".')
+    if isinstance(file, Genotypes) or input_format != "text":
+        return _grm_binary(file, input_format, {"separator": separator, "header": header, "missing_value": missing_value}, keep,
+                           counted_allele, id_column, center, quality_control, MAF, double_precision, device, _engine)
+    if keep is not None:
+        raise ValueError('keep= belongs to input_format="plink"')
+    separator = "," if separator is _TEXT_ONLY else separator
+    header = True if header is _TEXT_ONLY else header
+    missing_value = 9.0 if missing_value is _TEXT_ONLY else missing_value
     data_type = np.float64 if double_precision else np.float32
     obsID, markerID, genotypes = _read_genotype_table(file, separator, header, data_type)
     genotypes, markerID, p, _, _ = _impute_center_qc(genotypes, markerID, data_type, quality_control, MAF, missing_value, center)
     if genotypes.shape[1] == 0:
         raise ValueError("no marker is left after quality control")
-    divisor = np.sqrt(data_type(2.0) * p * (data_type(1.0) - p)).astype(data_type)
-    if not np.all(np.isfinite(divisor) & (divisor > 0)):
-        raise ValueError("genomic_relationship_matrix needs 0 < p < 1 for every marker (a fixed locus has 2p(1-p) = 0); use quality_control=True")
+    divisor = _grm_divisor(p, data_type)
     own = _engine is None
     engine = _engine
     if own:
@@ -254,9 +341,7 @@ def genomic_relationship_matrix(file, *, separator=",", header=True, center=True
     finally:
         if own:
             engine.close()
-    out = pd.DataFrame(K, columns=[str(i) for i in obsID])
-    out.insert(0, "ID", [str(i) for i in obsID])
-    return out
+    return _grm_frame(K, obsID)
 
 
 def device_genotypes(engine, G=False, *, method="BayesC", Pi=0.0, estimatePi=True, G_is_marker_variance=False, df=4.0,

@@ -10,6 +10,9 @@
 //                 float:  128 x 128 tiles, a wave owns 64 x 64 (2 x 2 v_mfma_f32_32x32x2_f32: a marker-ordered fp32 fma chain); the
 //                         fp32 accumulators are folded into doubles every kGrmChunk markers.
 //                 double: 64 x 64 tiles, a wave owns 32 x 32 (2 x 2 v_mfma_f64_16x16x4_f64), accumulated in double throughout.
+//   k_grm_packed  k_grm<float> on 2-bit packed storage: the same tiles, chain, fold and store, hence the same bits as the dense kernel on
+//                 the decoded columns; a panel is staged from one payload byte per thread and marker, the four possible x / d_j of a
+//                 marker divided once per workgroup.
 //
 // THE SAMPLER.  L = the context's dense n x n matrix (column i the i-th eigenvector of K), D its eigenvalues; pseudo-marker i has
 // the prior variance D_i G.  One step on the context's own residual r_k and effects alpha_k, k < T <= 4 traits (GBLUP!, megaGBLUP!,
@@ -123,6 +126,137 @@ __global__ __launch_bounds__(256) void k_grm<float>(const float* __restrict__ X,
             *reinterpret_cast<float4*>(&As[(sk + 8 * q) * E + 4 * sr]) = va[q];
             if (!diag) *reinterpret_cast<float4*>(&Bs[(sk + 8 * q) * E + 4 * sr]) = vb[q];
         }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < kGrmKT; kk += 2) {
+            const float a0 = a_rd[kk * E], a1 = a_rd[kk * E + 32];
+            const float b0 = b_rd[kk * E], b1 = b_rd[kk * E + 32];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+        chunk += kGrmKT;
+        if (chunk >= kGrmChunk) {
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) { accd[a][b][i] = accd[a][b][i] + (double)acc[a][b][i]; acc[a][b][i] = 0.f; }
+            chunk = 0;
+        }
+    }
+    // C/D layout of the 32 x 32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5); rows index the A operand
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int rr = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+                grm_store<float>(K, n, p, diag, ti * E + wm * 64 + a * 32 + rr, tj * E + wn * 64 + b * 32 + (lane & 31),
+                                 accd[a][b][i] + (double)acc[a][b][i]);
+            }
+}
+
+// rows the matrix does not have (>= n) are 0; keep: bit u set <=> row u of the thread's four is a row of the matrix
+__device__ __forceinline__ float4 grm_keep_rows(float4 v, unsigned keep)
+{
+    if (keep != 15u) {
+        v.x = (keep & 1u) ? v.x : 0.f; v.y = (keep & 2u) ? v.y : 0.f;
+        v.z = (keep & 4u) ? v.z : 0.f; v.w = (keep & 8u) ? v.w : 0.f;
+    }
+    return v;
+}
+
+// k_grm<float> on 2-bit packed storage (PackedCols, kernels.hpp: Q [p][ld / 4], four rows per byte; mean [p]).  The tiles, the waves, the
+// LDS images, the MFMA chain, the fold and the store are k_grm<float>'s, so K has its bits; only the staging differs.  A marker has
+// four possible values of x / d -- PackedCols::dec of the codes 0, 1, 2 and 3 (missing), then the dense kernel's IEEE division:
+//     t[c] = ((float)c - sub) / d_j  (c < 3),   t[3] = (centered ? 0 : mu_j) / d_j,   sub = centered ? mu_j : 0
+// -- formed ONCE per staged marker by the workgroup's first 128 threads (marker tid >> 2 of the LDS tile, code tid & 3: 128 divisions
+// per 32-marker step where the dense kernel has 4 096 or 8 192) and shared through LDS by the A and B panels.  The four lanes of a
+// marker exchange their values and lay them out as the marker's 16 PAIRS, Tp[marker][nibble] = (t[nibble & 3], t[nibble >> 2]): a
+// thread's share of a marker's row panel is one payload byte, and its four rows are two 8-byte LDS reads indexed by the byte's
+// nibbles -- no selection among the four values in registers (the compiler turns that into a private LDS copy with dependent reads).
+// The 32 lanes that stage a marker read within its 128 bytes of Tp, one bank row: conflict-free.  Rows >= n give 0 whatever the stray
+// fields of a marker's last byte hold; markers >= p give 0.
+// grid = nt (nt + 1) / 2 workgroups, nt = ceil(n / 128)
+__global__ __launch_bounds__(256) void k_grm_packed(const uint8_t* __restrict__ Q, int64_t ld, const float* __restrict__ mean, int32_t centered,
+                                                    int64_t n, int64_t p, const float* __restrict__ div, float* __restrict__ K)
+{
+    constexpr int E = kGrmTile32;
+    __shared__ __attribute__((aligned(16))) float As[kGrmKT * E];
+    __shared__ __attribute__((aligned(16))) float Bs[kGrmKT * E];
+    __shared__ __attribute__((aligned(16))) float2 Tp[kGrmKT * 16];
+    int ti, tj;
+    grm_tile((int)blockIdx.x, ti, tj);
+    const bool diag = ti == tj;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    // staging: thread -> marker sk (+ 8, 16, 24) of the LDS tile, rows 4 sr .. 4 sr + 3 of the panel = byte E / 4 * tile + sr of the marker
+    const int sk = tid >> 5, sr = tid & 31;
+    const int64_t sb = ld >> 2;                                                          // (bytes of a marker)
+    const int64_t rowA = (int64_t)ti * E + 4 * sr, rowB = (int64_t)tj * E + 4 * sr;      // (< ld: ld is a multiple of 256)
+    const unsigned keepA = rowA + 4 <= n ? 15u : (rowA >= n ? 0u : (1u << (unsigned)(n - rowA)) - 1u);
+    const unsigned keepB = rowB + 4 <= n ? 15u : (rowB >= n ? 0u : (1u << (unsigned)(n - rowB)) - 1u);
+    const uint8_t* __restrict__ qa = Q + (rowA >> 2);
+    const uint8_t* __restrict__ qb = Q + (rowB >> 2);
+    f32x16 acc[2][2];
+    double accd[2][2][16];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { acc[a][b][i] = 0.f; accd[a][b][i] = 0.0; }
+    const int am = lane & 31, ah = lane >> 5;
+    const float* a_rd = As + ah * E + wm * 64 + am;
+    const float* b_rd = (diag ? As : Bs) + ah * E + wn * 64 + am;
+    int chunk = 0;
+    // a step's global loads -- a payload byte per staged marker and panel, and the table thread's mean and divisor -- are issued a step
+    // ahead, after the registers of the step before were staged, so that they are in flight under that step's MFMAs
+    unsigned ba[4], bb[4];
+    float mu = 0.f, dj = 1.f;
+    auto fetch = [&](int64_t k0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t j = k0 + sk + 8 * q;
+            const int64_t jc = j < p ? j : p - 1;                // (a clamped address; a marker beyond p has zeros in Tp)
+            ba[q] = qa[jc * sb];
+            bb[q] = diag ? 0u : (unsigned)qb[jc * sb];
+        }
+        if (tid < 4 * kGrmKT) {
+            const int64_t j = k0 + (tid >> 2);
+            const int64_t jc = j < p ? j : p - 1;
+            mu = mean[jc];
+            dj = div[jc];
+        }
+    };
+    fetch(0);
+    for (int64_t k0 = 0; k0 < p; k0 += kGrmKT) {
+        if (tid < 4 * kGrmKT) {                                  // (waves 0 and 1; Tp was last read before the previous step's second barrier)
+            const unsigned code = (unsigned)tid & 3u;
+            const float x = code == 3u ? (centered ? 0.f : mu) : (float)code - (centered ? mu : 0.f);
+            const float v = k0 + (tid >> 2) < p ? x / dj : 0.f;
+            const int l0 = lane & ~3;
+            const float t0 = __shfl(v, l0, 64), t1 = __shfl(v, l0 + 1, 64), t2 = __shfl(v, l0 + 2, 64), t3 = __shfl(v, l0 + 3, 64);
+            float4* out = reinterpret_cast<float4*>(&Tp[4 * tid]);      // nibbles 4 code + k: (t[k], t[code])
+            out[0] = float4{t0, v, t1, v};
+            out[1] = float4{t2, v, t3, v};
+        }
+        __syncthreads();                                         // the previous tile is consumed; Tp is written
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float2* __restrict__ t = &Tp[16 * (sk + 8 * q)];
+            const float2 a01 = t[ba[q] & 15u], a23 = t[ba[q] >> 4];
+            *reinterpret_cast<float4*>(&As[(sk + 8 * q) * E + 4 * sr]) = grm_keep_rows(float4{a01.x, a01.y, a23.x, a23.y}, keepA);
+            if (!diag) {
+                const float2 b01 = t[bb[q] & 15u], b23 = t[bb[q] >> 4];
+                *reinterpret_cast<float4*>(&Bs[(sk + 8 * q) * E + 4 * sr]) = grm_keep_rows(float4{b01.x, b01.y, b23.x, b23.y}, keepB);
+            }
+        }
+        fetch(k0 + kGrmKT);
         __syncthreads();
 #pragma unroll
         for (int kk = 0; kk < kGrmKT; kk += 2) {

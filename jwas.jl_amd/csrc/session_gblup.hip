@@ -1,5 +1,5 @@
 // session_gblup.hip -- GBLUP (gblup.hpp): jwas_hip_grm, the genomic relationship matrix of the context's dense matrix
-// (readgenotypes.jl:403-408), and jwas_hip_gblup_begin .. _end, GBLUP! / megaGBLUP! / MTGBLUP! on the eigenvectors of that matrix
+// (readgenotypes.jl:403-408), jwas_hip_grm_packed2bit, the same matrix of the context's 2-bit packed genotypes, and jwas_hip_gblup_begin .. _end, GBLUP! / megaGBLUP! / MTGBLUP! on the eigenvectors of that matrix
 // (markers/BayesianAlphabet/GBLUP.jl) with the context's own residual and effects.
 #include "ctx.hpp"
 #include "gblup.hpp"
@@ -109,6 +109,40 @@ int jwas_hip_grm(jwas_hip_ctx* c, const void* divisor, void* K_host)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     mem.release();
     if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_grm: %s", hipGetErrorString(e));
+    return JWAS_HIP_OK;
+}
+
+int jwas_hip_grm_packed2bit(jwas_hip_ctx* c, const float* divisor, float* K_host)
+{
+    if (c) NOT_F64(c, "2-bit packed storage");
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, c->packed && c->Q && c->n > 0 && c->p > 0, JWAS_HIP_ESTATE, "the context holds no 2-bit packed genotypes (see jwas_hip_storage_info)");
+    if (int rc = refuse_shards(c, "relationship matrices")) return rc;
+    NEED(c, divisor && K_host, JWAS_HIP_EINVAL, "NULL argument");
+    const int64_t n = c->n, p = c->p;
+    for (int64_t j = 0; j < p; ++j) {
+        const double d = (double)divisor[j];
+        NEED(c, std::isfinite(d) && d > 0.0, JWAS_HIP_EINVAL, "divisor[%lld] must be positive and finite (%g)", (long long)j, d);
+    }
+    const int64_t nt = (n + jwb::kGrmTile32 - 1) / jwb::kGrmTile32;
+    NEED(c, nt * (nt + 1) / 2 < (1ll << 31), JWAS_HIP_EUNSUP, "n=%lld exceeds the tile grid of jwas_hip_grm_packed2bit", (long long)n);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevOwner mem;
+    float *d_div = nullptr, *d_K = nullptr;
+    if (mem.alloc(&d_div, sizeof(float) * (size_t)p) != hipSuccess || mem.alloc(&d_K, sizeof(float) * (size_t)n * (size_t)n) != hipSuccess) {
+        mem.release();
+        return fail(c, JWAS_HIP_ENOMEM, "relationship matrix: device allocation of %zu bytes failed", sizeof(float) * ((size_t)n * (size_t)n + (size_t)p));
+    }
+    hipError_t e = hipMemcpyAsync(d_div, divisor, sizeof(float) * (size_t)p, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(jwb::k_grm_packed, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, c->stream, (const uint8_t*)c->Q, c->ld, (const float*)c->qmean,
+                           (int32_t)c->centered, n, p, (const float*)d_div, d_K);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(K_host, d_K, sizeof(float) * (size_t)n * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    mem.release();
+    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_grm_packed2bit: %s", hipGetErrorString(e));
     return JWAS_HIP_OK;
 }
 

@@ -1358,6 +1358,17 @@ class HipEngine:
         self._chk(self._L.jwas_hip_grm(self._h, _ptr(d), _ptr(K)))
         return K
 
+    def grm_packed(self, divisor):
+        """grm() of the 2-bit packed genotypes the engine holds (load_packed2bit, load_jgb2, plink_commit; readgenotypes.jl:403-408):
+        n x n Float32, symmetric bit for bit, and bit for bit grm() of the dense matrix get_columns decodes.  divisor: p Float32
+        values.  The storage, the state and an open session stay as they are."""
+        d = np.ascontiguousarray(divisor, dtype=np.float32)
+        if d.shape != (self.p,):
+            raise ValueError(f"divisor must have length {self.p}")
+        K = np.empty((self.n, self.n), dtype=np.float32)
+        self._chk(self._L.jwas_hip_grm_packed2bit(self._h, _ptr(d), _ptr(K)))
+        return K
+
     @staticmethod
     def gblup_estimate_bytes(n, ntraits=1, precision=32):
         return _lib.load().jwas_hip_gblup_estimate_bytes(int(n), int(ntraits), int(precision))
