@@ -241,6 +241,27 @@ int  jwas_hip_plink_discard(jwas_hip_ctx* ctx);
 /* The packed rows of markers [j0, j0 + m) back to the host, cld(n,4) bytes of each at stride_bytes >= cld(n,4): the payload of a
  * .jgb2 file (streaming_genotypes.jl:600-654) from a context with packed storage, however it was loaded. */
 int  jwas_hip_get_packed2bit(jwas_hip_ctx* ctx, int64_t j0, int64_t m, uint8_t* out_host, int64_t stride_bytes);
+/* ---- output rows in 2-bit packed storage: EBVs for individuals outside the training set, kept packed ----
+ * Mi.output_genotypes (tools4genotypes.jl:290-296) for the output_ID of check_outputID (input_data_validation.jl:143-196) as a SECOND
+ * packed matrix [p][ld_out/4], ld_out = n_out rounded up to 256, beside the packed training storage of a Float32 context.  It has no
+ * means of its own: a field is decoded with the training storage's marker mean and `centered` (decode_marker!,
+ * streaming_genotypes.jl:978-1002), so a missing code of an output individual decodes to the training mean (0 when centred); rows
+ * >= n_out decode to 0 whatever their fields hold.  At most one output matrix is resident: loading a packed one frees a dense one
+ * (jwas_hip_load_output_dense_f32) and the reverse; a load of genotypes and jwas_hip_destroy free both; a GWAS session on output rows
+ * is dropped.  jwas_hip_mul_alpha_output and jwas_hip_window_sums / _sums2 (use_output_rows) run on packed output rows;
+ * jwas_hip_gwas_begin(use_output_rows) answers JWAS_HIP_EUNSUP on them.  JWAS_HIP_ESTATE without packed training storage,
+ * JWAS_HIP_EUNSUP on a Float64 context.
+ *   jwas_hip_load_output_packed2bit  from a host payload in the .jgb2 field layout (streaming_genotypes.jl:364-367,622-627): p rows of
+ *                                    cld(n_out,4) bytes at stride_bytes.  JWAS_HIP_EINVAL when p differs from the context's.
+ *   jwas_hip_plink_commit_output     after a jwas_hip_plink_scan whose `rows` are the output individuals and whose count_a1 is the
+ *                                    training's: the staging rows of `selected` -- the TRAINING selection, p_sel = the context's p
+ *                                    (JWAS_HIP_EINVAL otherwise); the output individuals' own allele counts play no part -- become the
+ *                                    output rows.  Training storage, state and blocks are untouched.  The pending scan is consumed;
+ *                                    an error leaves the earlier output rows in place.
+ *   jwas_hip_get_output_packed2bit   the twin of jwas_hip_get_packed2bit: cld(n_out,4) bytes of the markers [j0, j0 + m). */
+int  jwas_hip_load_output_packed2bit(jwas_hip_ctx* ctx, const uint8_t* payload, int64_t n_out, int64_t p, int64_t stride_bytes);
+int  jwas_hip_plink_commit_output(jwas_hip_ctx* ctx, const int64_t* selected, int64_t p_sel);
+int  jwas_hip_get_output_packed2bit(jwas_hip_ctx* ctx, int64_t j0, int64_t m, uint8_t* out_host, int64_t stride_bytes);
 int  jwas_hip_storage_info(jwas_hip_ctx* ctx, int32_t* kind, int64_t* n, int64_t* p, int64_t* bytes);
 /* Device row stride (elements) of the padded marker-major layout, and its base device pointer. */
 int  jwas_hip_dense_layout(jwas_hip_ctx* ctx, int64_t* n, int64_t* p, int64_t* ld_dev, void** X_dev);
@@ -358,6 +379,10 @@ int  jwas_hip_get_alpha_sparse(jwas_hip_ctx* ctx, int32_t trait, int64_t capacit
 int  jwas_hip_load_output_dense_f32(jwas_hip_ctx* ctx, const float* X_out_host, int64_t n_out, int64_t p, int64_t ld_host);
 /* out = X_out * alpha_k (n_out floats, fp64-accumulated). */
 int  jwas_hip_mul_alpha_output(jwas_hip_ctx* ctx, int32_t trait, float* out_host);
+/* getEBV (output.jl:281-306) for ALL traits of the context in one call: out_host[k * n_out + i] = jwas_hip_mul_alpha_output of trait
+ * k, bit for bit.  On 2-bit packed output rows one kernel reads every byte of a marker with a nonzero effect in any trait once and
+ * keeps the sums of all traits (csrc/output.hpp: k_ebv_packed); on dense output rows the traits go one by one.  Float32 contexts. */
+int  jwas_hip_ebv_output(jwas_hip_ctx* ctx, float* out_host);
 /* Window genomic variances of ONE saved marker-effect sample -- the inner loop of the reference's window-based GWAS
  * (src/3.GWAS/src/GWAS.jl:152-165: genVar = var(X*alpha); per window var(X[:, w]*alpha[w])).  Window w owns the nonzero
  * effects idx[wptr[w] .. wptr[w+1]) (marker indices, any order the caller wants summed in) with values val[..];

@@ -737,6 +737,27 @@ function hip_mtj_mul_alpha(b::HipBackend, trait::Integer, n_rows::Integer; outpu
 end
 hip_mtj_end!(b::HipBackend) = hip_check(b.ctx, ccall((:jwas_hip_mtj_end, LIBJWAS_HIP), Cint, (Ptr{Cvoid},), b.ctx))
 
+"Output rows in 2-bit packed storage beside packed training storage (Mi.output_genotypes, tools4genotypes.jl:290-296, for the
+output_ID of check_outputID, input_data_validation.jl:143-196): a second packed matrix decoded with the training means and centring.
+`payload` is p x stride in the .jgb2 field layout, one marker per COLUMN of the Julia matrix (stride = size(payload, 1) >= cld(n_out, 4)).
+`hip_plink_commit_output!` follows a jwas_hip_plink_scan of the output individuals; `selected` is the training selection, 0-based.
+`hip_ebv_output` returns getEBV (output.jl:281-306) of all traits, n_out x ntraits, column k the bits of jwas_hip_mul_alpha_output(k)."
+hip_load_output_packed2bit!(b::HipBackend, payload::Matrix{UInt8}, n_out::Integer) =
+    hip_check(b.ctx, ccall((:jwas_hip_load_output_packed2bit, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int64, Int64, Int64),
+                           b.ctx, payload, n_out, size(payload, 2), size(payload, 1)))
+hip_plink_commit_output!(b::HipBackend, selected::Vector{Int64}) =
+    hip_check(b.ctx, ccall((:jwas_hip_plink_commit_output, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int64), b.ctx, selected, length(selected)))
+function hip_get_output_packed2bit(b::HipBackend, j0::Integer, m::Integer, n_out::Integer)
+    out = Matrix{UInt8}(undef, cld(n_out, 4), m)
+    hip_check(b.ctx, ccall((:jwas_hip_get_output_packed2bit, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{UInt8}, Int64), b.ctx, j0, m, out, size(out, 1)))
+    return out
+end
+function hip_ebv_output(b::HipBackend, n_out::Integer, ntraits::Integer)
+    out = Matrix{Float32}(undef, n_out, ntraits)
+    hip_check(b.ctx, ccall((:jwas_hip_ebv_output, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Ptr{Float32}), b.ctx, out))
+    return out
+end
+
 """
 GBLUP (markers/readgenotypes.jl:403-408, markers/BayesianAlphabet/GBLUP.jl; csrc/gblup.hpp).  `hip_grm` returns the relationship
 matrix (Z Z' + 1e-5 I) / p of the loaded dense matrix, Z = X ./ divisor with divisor = sqrt.(2p .* (1 .- p)) in the matrix's element

@@ -214,6 +214,10 @@ PROTOTYPES = {
     "jwas_hip_plink_commit": (_INT, [_vp, _vp, _i64, _vp, _i32]),
     "jwas_hip_plink_discard": (_INT, [_vp]),
     "jwas_hip_get_packed2bit": (_INT, [_vp, _i64, _i64, _vp, _i64]),
+    "jwas_hip_load_output_packed2bit": (_INT, [_vp, _vp, _i64, _i64, _i64]),
+    "jwas_hip_plink_commit_output": (_INT, [_vp, _vp, _i64]),
+    "jwas_hip_get_output_packed2bit": (_INT, [_vp, _i64, _i64, _vp, _i64]),
+    "jwas_hip_ebv_output": (_INT, [_vp, _vp]),
     "jwas_hip_storage_info": (_INT, [_vp, _P(_i32), _P(_i64), _P(_i64), _P(_i64)]),
     "jwas_hip_set_xpx": (_INT, [_vp, _vp]),
     "jwas_hip_estimate_bytes_storage": (_i64, [_i64, _i64, _i32, _i32, _i32]),

@@ -421,6 +421,7 @@ def plink_genotypes(bfile, G=False, *, keep=None, device=0, engine=None, counted
             engine.close()
         raise
     g.counted_alleles, g.selected = b["counted_alleles"], b["selected"]
+    g.plink_source = b["source"]               # (outputEBV(model, IDs): further individuals of the fileset become packed output rows)
     print("Genotype informatin:")
     print(f"#markers: {b['nMarkers']}; #individuals: {b['nObs']} (PLINK fileset, 2-bit packed on the device)")
     return g

@@ -115,6 +115,12 @@ struct jwas_hip_ctx : Side<float> {
     float* qmean = nullptr;
     bool packed = false;
     int centered = 1;
+    // Output rows in 2-bit packed form beside packed training storage (jwas_hip_load_output_packed2bit, jwas_hip_plink_commit_output):
+    // [p][ld_out / 4], no means of its own -- decoded with qmean / centered above; n_out, ld_out: the base's.  At most one of Xout and
+    // Qout is set.  load_mem owns it, and the union list of jwas_hip_ebv_output below.
+    uint8_t* Qout = nullptr;
+    int32_t* ebv_idx = nullptr;         // [p] + [1] the markers with a nonzero effect in any trait, ascending, and their number
+    float* ebv_val = nullptr;           // [kMaxT][p] their effects, trait-major (0 where only another trait's is nonzero)
 
     // Active block configuration (a view of one entry of `sets`; several block sizes can be resident so the host
     // can pick per sweep: big blocks when few markers change, smaller ones when many do).
@@ -480,6 +486,15 @@ JW_LOCAL void ss_free(jwas_hip_ctx* c);
 JW_LOCAL void gblup_free(jwas_hip_ctx* c);
 JW_LOCAL void gwas_free(jwas_hip_ctx* c);                                  // (output.hip: the GWAS session)
 JW_LOCAL void plink_free(jwas_hip_ctx* c);                                 // (a pending scan: it goes with any load, too)
+
+// The output rows of a Float32 context go, dense or packed, and with them a GWAS session that runs on them (the stream is idle).
+static inline void drop_output_rows(jwas_hip_ctx* c)
+{
+    if (c->gw.out_rows) gwas_free(c);
+    c->load_mem.free_one(c->Xout);
+    c->load_mem.free_one(c->Qout);
+    c->n_out = c->ld_out = 0;
+}
 
 // Storage of an n x p matrix and everything sized by it (jwas_hip.hip); whatever the context held before is freed first.  adopt: a
 // buffer of (ld / 4) p + 1024 bytes that becomes the packed payload in the place of a new allocation (the context owns it from here on,

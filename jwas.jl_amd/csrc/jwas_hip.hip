@@ -122,6 +122,7 @@ static void free_storage(jwas_hip_ctx* c)
     locpar_free(c);                     // (... and so do the location parameters' term layouts)
     plink_free(c);                      // (a scan that was never committed: the load that replaces it was asked for instead)
     c->drop();                          // (genotypes, residual, weights, output rows, the chain's state)
+    c->Qout = nullptr; c->ebv_idx = nullptr; c->ebv_val = nullptr;      // (load_mem's, released with it: the packed output rows, their EBV list)
     (void)hipFree(c->Q); (void)hipFree(c->qmean);
     c->Q = nullptr; c->qmean = nullptr; c->packed = false;
     (void)hipFree(c->ev); (void)hipFree(c->dparams); (void)hipFree(c->counters); (void)hipFree(c->fin_out); (void)hipFree(c->stat_out); (void)hipFree(c->sync_cnt);

@@ -28,10 +28,18 @@ template <class T> constexpr const char* load_output_name() { return sizeof(T) =
 
 bool have_genotypes(jwas_hip_ctx* c) { return IS_F64(c) ? c->f64->X != nullptr : HAVE_STORAGE(c); }
 
+// output rows are resident: dense, or (Float32) 2-bit packed
+bool have_output_rows(jwas_hip_ctx* c, Side<float>& S) { return S.Xout != nullptr || c->Qout != nullptr; }
+bool have_output_rows(jwas_hip_ctx*, Side<double>& S) { return S.Xout != nullptr; }
+
+// the packed output rows as a view: the training set's means and centring, and n_out rows -- the pad-row mask is the view's
+PackedCols packed_output_view(jwas_hip_ctx* c) { return PackedCols{c->Qout, c->ld_out, c->qmean, c->n_out, c->centered, nullptr, 0}; }
+
 // f(view) of the training rows (the context's storage) or of the output rows
 template <class F>
 auto with_view(jwas_hip_ctx* c, Side<float>& S, bool out_rows, F&& f)
 {
+    if (out_rows && c->Qout) return f(packed_output_view(c));
     if (out_rows) return f(DenseCols{S.Xout, S.ld_out, nullptr, 0});
     return with_cols(c, 0, f);
 }
@@ -183,7 +191,7 @@ int mul_alpha_output(jwas_hip_ctx* c, int32_t trait, T* out, const char* who)
     GUARD(T, c, out != nullptr, "NULL argument", "jwas_hip_mul_alpha_output (use jwas_hip_mul_alpha_output_f64)");
     NEED_TRAIT(c, trait);
     auto& S = side<T>(c);
-    NEED(c, S.Xout, JWAS_HIP_ESTATE, "%s has not been called", load_output_name<T>());
+    NEED(c, have_output_rows(c, S), JWAS_HIP_ESTATE, "%s has not been called", load_output_name<T>());
     return mul_alpha_rows<T>(c, trait, true, S.ld_out, S.n_out, out, who);
 }
 
@@ -224,14 +232,51 @@ int load_output_dense(jwas_hip_ctx* c, const T* Xh, int64_t n_out, int64_t p, in
     auto& S = side<T>(c);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->gw.out_rows) gwas_free(c);
-    S.load_mem.free_one(S.Xout); S.n_out = S.ld_out = 0;
+    if constexpr (std::is_same<T, float>::value) drop_output_rows(c);      // (dense or packed: at most one output matrix is resident)
+    else { if (c->gw.out_rows) gwas_free(c); S.load_mem.free_one(S.Xout); S.n_out = S.ld_out = 0; }
     const int64_t ld = round_up(n_out, kSliceRows);
     HIPCHK(c, S.load_mem.alloc(&S.Xout, sizeof(T) * (size_t)ld * p));
     S.n_out = n_out; S.ld_out = ld;
     if (ld != n_out) HIPCHK(c, hipMemsetAsync(S.Xout, 0, sizeof(T) * (size_t)ld * p, c->stream));      // pad rows zero
     HIPCHK(c, hipMemcpy2DAsync(S.Xout, sizeof(T) * ld, Xh, sizeof(T) * ld_host, sizeof(T) * n_out, (size_t)p, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+// The EBVs of all traits on packed output rows in one launch (k_ebv_packed): the union list, the kernel, [t][n_out] to the host.
+int ebv_output_packed(jwas_hip_ctx* c, float* out)
+{
+    const int t = c->ntraits;
+    const int64_t ld = c->ld_out, n_out = c->n_out;
+    if (!c->ebv_idx) {
+        hipError_t ea = c->load_mem.alloc(&c->ebv_idx, sizeof(int32_t) * ((size_t)c->p + 1));
+        if (ea == hipSuccess) ea = c->load_mem.alloc(&c->ebv_val, sizeof(float) * (size_t)kMaxT * c->p);
+        if (ea != hipSuccess) {
+            (void)hipGetLastError();
+            c->load_mem.free_one(c->ebv_idx); c->load_mem.free_one(c->ebv_val);
+            return fail(c, JWAS_HIP_ENOMEM, "jwas_hip_ebv_output: %s (the list of the nonzero effects)", hipGetErrorString(ea));
+        }
+    }
+    float* tmp = nullptr;
+    HIPCHK(c, hipMalloc(&tmp, sizeof(float) * (size_t)t * ld));
+    hipLaunchKernelGGL(k_compact_alpha_union<float>, dim3(1), dim3(1024), 0, c->stream, c->p, t, (const float*)c->alpha, c->ebv_idx, c->ebv_val, c->ebv_idx + c->p);
+    hipError_t e = hipGetLastError();
+    int32_t nnz = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&nnz, c->ebv_idx + c->p, sizeof nnz, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) {
+        const PackedCols cx = packed_output_view(c);
+        with_traits(t, [&](auto nt) {
+            hipLaunchKernelGGL((k_ebv_packed<decltype(nt)::value>), dim3((unsigned)(ld / kSliceRows)), dim3(64), 0, c->stream, cx, (int)nnz,
+                               (const int32_t*)c->ebv_idx, (const float*)c->ebv_val, c->p, tmp);
+        });
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpy2DAsync(out, sizeof(float) * (size_t)n_out, tmp, sizeof(float) * (size_t)ld, sizeof(float) * (size_t)n_out, (size_t)t, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(tmp);
+    if (e != hipSuccess) return fail(c, JWAS_HIP_EHIP, "jwas_hip_ebv_output: %s", hipGetErrorString(e));
     return JWAS_HIP_OK;
 }
 
@@ -250,7 +295,7 @@ int window_sums(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, const in
     for (int v = 0; v < nv; ++v) NEED(c, outs[v], JWAS_HIP_EINVAL, "NULL output array");
     NEED(c, nwin >= 1, JWAS_HIP_EINVAL, "nwin must be >= 1 (got %d)", nwin);
     NEED(c, have_genotypes(c), JWAS_HIP_ESTATE, "no genotype matrix loaded");
-    NEED(c, !use_output_rows || S.Xout, JWAS_HIP_ESTATE, "%s has not been called", load_output_name<T>());
+    NEED(c, !use_output_rows || have_output_rows(c, S), JWAS_HIP_ESTATE, "%s has not been called", load_output_name<T>());
     NEED(c, wptr[0] == 0, JWAS_HIP_EINVAL, "wptr[0] must be 0");
     for (int w = 0; w < nwin; ++w) NEED(c, wptr[w + 1] >= wptr[w], JWAS_HIP_EINVAL, "wptr must be non-decreasing");
     const int64_t nnz = wptr[nwin];
@@ -492,6 +537,51 @@ int jwas_hip_mul_alpha_output_f64(jwas_hip_ctx* c, int32_t trait, double* out)
     return mul_alpha_output<double>(c, trait, out, "jwas_hip_mul_alpha_output_f64");
 }
 
+// Output rows as a second 2-bit packed matrix beside packed training storage (Mi.output_genotypes, tools4genotypes.jl:290-296, in the
+// layout of Packed2BitBackend, streaming_genotypes.jl:7-25): decoded with the training means and centring.  The new matrix is
+// complete before the earlier output rows go, so an error leaves them in place.
+int jwas_hip_load_output_packed2bit(jwas_hip_ctx* c, const uint8_t* payload, int64_t n_out, int64_t p, int64_t stride_bytes)
+{
+    if (c) NOT_F64(c, "2-bit packed storage");
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, payload, JWAS_HIP_EINVAL, "payload is NULL");
+    NEED(c, c->packed && c->Q, JWAS_HIP_ESTATE, "packed output rows need 2-bit packed training storage: their means and centring are its own");
+    NEED(c, n_out >= 1 && n_out < (1ll << 31), JWAS_HIP_EINVAL, "n_out must be within [1, 2^31) (got %lld)", (long long)n_out);
+    NEED(c, p == c->p, JWAS_HIP_EINVAL, "output genotypes have %lld markers, the training matrix %lld", (long long)p, (long long)c->p);
+    const int64_t width = (n_out + 3) / 4;
+    NEED(c, stride_bytes >= width, JWAS_HIP_EINVAL, "stride_bytes (%lld) must be >= cld(n_out,4) = %lld", (long long)stride_bytes, (long long)width);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t ld = round_up(n_out, kSliceRows);
+    const size_t sb = (size_t)(ld >> 2);
+    uint8_t* q = nullptr;
+    hipError_t e = hipMalloc(&q, sb * (size_t)p);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, JWAS_HIP_ENOMEM, "jwas_hip_load_output_packed2bit: device allocation of %zu bytes failed", sb * (size_t)p); }
+    e = hipMemsetAsync(q, 0, sb * (size_t)p, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(q, sb, payload, (size_t)stride_bytes, (size_t)width, (size_t)p, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipFree(q); return fail(c, JWAS_HIP_EHIP, "jwas_hip_load_output_packed2bit: %s", hipGetErrorString(e)); }
+    drop_output_rows(c);
+    c->load_mem.ptrs.push_back(q);
+    c->Qout = q; c->n_out = n_out; c->ld_out = ld;
+    return JWAS_HIP_OK;
+}
+
+// getEBV (output.jl:281-306) for all traits of the context at once: out[k * n_out + i].  Packed output rows: one launch of
+// k_ebv_packed; dense ones: jwas_hip_mul_alpha_output trait by trait.  The bits are jwas_hip_mul_alpha_output's either way.
+int jwas_hip_ebv_output(jwas_hip_ctx* c, float* out)
+{
+    if (c) NOT_F64(c, "jwas_hip_ebv_output (use jwas_hip_mul_alpha_output_f64 per trait)");
+    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, c->method >= 0, JWAS_HIP_ESTATE, "jwas_hip_init_state has not been called");
+    NEED(c, have_output_rows(c, *c), JWAS_HIP_ESTATE, "no output rows are loaded (jwas_hip_load_output_dense_f32, jwas_hip_load_output_packed2bit, jwas_hip_plink_commit_output)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->Qout) return ebv_output_packed(c, out);
+    for (int32_t k = 0; k < c->ntraits; ++k)
+        if (int rc = mul_alpha_rows<float>(c, k, true, c->ld_out, c->n_out, out + (size_t)k * c->n_out, "jwas_hip_ebv_output")) return rc;
+    return JWAS_HIP_OK;
+}
+
 int jwas_hip_get_alpha_sparse(jwas_hip_ctx* c, int32_t trait, int64_t capacity, int32_t* idx, float* val, int64_t* nnz_out)
 {
     return get_alpha_sparse<float>(c, trait, capacity, idx, val, nnz_out);
@@ -544,6 +634,8 @@ int jwas_hip_gwas_begin(jwas_hip_ctx* c, int32_t use_output_rows, int32_t nwin, 
     NEED(c, nwin >= 1, JWAS_HIP_EINVAL, "nwin must be >= 1 (got %d)", nwin);
     NEED(c, have_genotypes(c), JWAS_HIP_ESTATE, "no genotype matrix loaded");
     int64_t n_rows = 0, ld = 0;
+    NEED(c, !use_output_rows || IS_F64(c) || !c->Qout, JWAS_HIP_EUNSUP,
+         "jwas_hip_gwas_begin: a session on 2-bit packed output rows is not available (jwas_hip_window_sums(use_output_rows) runs on them)");
     NEED(c, !use_output_rows || output_rows_ptr(c, &n_rows, &ld), JWAS_HIP_ESTATE, "%s has not been called",
          IS_F64(c) ? load_output_name<double>() : load_output_name<float>());
     for (int w = 0; w < nwin; ++w) {

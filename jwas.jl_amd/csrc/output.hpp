@@ -154,6 +154,85 @@ __global__ __launch_bounds__(ROWS) void k_mul_alpha_list(CX cx, int nnz, const i
     out[row] = (elem_t<CX>)s;
 }
 
+// ---- the EBVs of all traits on 2-bit packed output rows (jwas_hip_ebv_output; getEBV, output.jl:281-306) --------------------------
+// The markers with a nonzero effect in ANY of the nt traits as one ascending list, with every trait's effect at each of them:
+// k_compact_alpha's walk with the union as its predicate.  idx: [p], val: [nt][p] (trait-major), *count: the list's length.
+// grid = 1, block = 1024.
+template <class T>
+__global__ __launch_bounds__(1024) void k_compact_alpha_union(int64_t p, int nt, const T* __restrict__ alpha, int32_t* __restrict__ idx, T* __restrict__ val,
+                                                              int32_t* __restrict__ count)
+{
+    __shared__ int wsum[16];
+    __shared__ int base_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) base_s = 0;
+    __syncthreads();
+    for (int64_t j0 = 0; j0 < p; j0 += 1024) {
+        const int64_t j = j0 + tid;
+        bool nz = false;
+        if (j < p) for (int k = 0; k < nt; ++k) nz = nz || alpha[(int64_t)k * p + j] != T(0);
+        const unsigned long long m = __ballot(nz);
+        if (lane == 0) wsum[wave] = __popcll(m);
+        __syncthreads();
+        int pre = base_s, tot = 0;
+        for (int w = 0; w < 16; ++w) { if (w < wave) pre += wsum[w]; tot += wsum[w]; }
+        if (nz) {
+            const int pos = pre + __popcll(m & ((1ull << lane) - 1ull));
+            idx[pos] = (int32_t)j;
+            for (int k = 0; k < nt; ++k) val[(int64_t)k * p + pos] = alpha[(int64_t)k * p + j];
+        }
+        __syncthreads();
+        if (tid == 0) base_s += tot;
+        __syncthreads();
+    }
+    if (tid == 0) *count = base_s;
+}
+
+// K bytes of one thread in flight, then their terms in list order: the four rows of a byte times the NT effects of its marker.  The
+// decode is PackedCols::dec and the pad-row rule of PackedCols::load1 (keep: bit k set when row k of the byte is below cx.n).
+template <int K, int NT>
+__device__ __forceinline__ void ebv_terms(const PackedCols& cx, int64_t byte_off, unsigned keep, const int32_t* __restrict__ idx, const float* __restrict__ val,
+                                          int64_t vstride, int e, double (&s)[NT][4])
+{
+    unsigned b[K]; float mu[K];
+#pragma unroll
+    for (int u = 0; u < K; ++u) { const int64_t j = idx[e + u]; b[u] = cx.Q[j * (cx.ld >> 2) + byte_off]; mu[u] = cx.mean[j]; }
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        double a[NT];
+#pragma unroll
+        for (int k = 0; k < NT; ++k) a[k] = (double)val[(int64_t)k * vstride + e + u];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float x = ((keep >> q) & 1u) ? cx.dec((b[u] >> (2 * q)) & 3u, mu[u]) : 0.f;
+#pragma unroll
+            for (int k = 0; k < NT; ++k) s[k][q] = fma(a[k], (double)x, s[k][q]);
+        }
+    }
+}
+
+// out[k * ld + row] = (float) sum_j alpha_kj x_(row, j) for the NT traits at once: s = fma(double(alpha), double(x), s) over the union
+// list in marker order, the chain of k_mul_alpha_list / k_mul_alpha for every trait (a zero effect of the union adds fma(0, x, s) = s),
+// hence their bits.  A thread owns the four rows of one byte: it reads that byte once per listed marker (16 / 4 / 1 of them in
+// flight) and keeps 4 NT sums.  grid = ld / 256, block = 64: one wave per 256-row slice, so a column's 64 bytes are one load.
+template <int NT>
+__global__ __launch_bounds__(64) void k_ebv_packed(PackedCols cx, int nnz, const int32_t* __restrict__ idx, const float* __restrict__ val, int64_t vstride,
+                                                   float* __restrict__ out)
+{
+    const int64_t byte_off = (int64_t)blockIdx.x * 64 + threadIdx.x, row = byte_off << 2;
+    unsigned keep = 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) keep |= (row + q < cx.n ? 1u : 0u) << q;
+    double s[NT][4] = {};
+    int e = 0;
+    for (; e + 16 <= nnz; e += 16) ebv_terms<16, NT>(cx, byte_off, keep, idx, val, vstride, e, s);
+    for (; e + 4 <= nnz; e += 4) ebv_terms<4, NT>(cx, byte_off, keep, idx, val, vstride, e, s);
+    for (; e < nnz; ++e) ebv_terms<1, NT>(cx, byte_off, keep, idx, val, vstride, e, s);
+#pragma unroll
+    for (int k = 0; k < NT; ++k)
+        *reinterpret_cast<float4*>(out + (int64_t)k * cx.ld + row) = float4{(float)s[k][0], (float)s[k][1], (float)s[k][2], (float)s[k][3]};
+}
+
 // ---- window genomic values of one marker-effect sample (GWAS.jl:152-165, :199-217) ----------------------------------------------
 // Window w holds the nonzero effects idx / val[wptr[w] .. wptr[w+1]); BV_w[i] = sum_j X[i, idx_j] val_j in list order (8 column
 // loads in flight, one for a window's tail).  grid = nslices, block = 256 (one individual per thread);

@@ -162,6 +162,59 @@ int jwas_hip_plink_commit(jwas_hip_ctx* c, const int64_t* selected, int64_t p_se
     return JWAS_HIP_OK;
 }
 
+// The scanned individuals become the context's packed OUTPUT rows (Mi.output_genotypes, tools4genotypes.jl:290-296, for the output_ID
+// of check_outputID, input_data_validation.jl:143-196): the staging rows of the training selection, nothing else of the context changes.
+int jwas_hip_plink_commit_output(jwas_hip_ctx* c, const int64_t* selected, int64_t p_sel)
+{
+    if (c) NOT_F64(c, "2-bit packed storage");
+    NEED(c, c, JWAS_HIP_EINVAL, "ctx is NULL");
+    NEED(c, c->pk.pending, JWAS_HIP_ESTATE, "jwas_hip_plink_scan has not been called (or its scan was dropped by a later load)");
+    NEED(c, c->packed && c->Q, JWAS_HIP_ESTATE, "packed output rows need 2-bit packed training storage: their means and centring are its own");
+    NEED(c, selected, JWAS_HIP_EINVAL, "selected is NULL");
+    const int64_t p_file = c->pk.p_file, n_out = c->pk.n_rows, ld = c->pk.ld, sb = ld >> 2;
+    NEED(c, p_sel == c->p, JWAS_HIP_EINVAL, "p_sel (%lld) differs from the training matrix's %lld markers: the selection is the training set's", (long long)p_sel,
+         (long long)c->p);
+    NEED(c, p_sel <= p_file, JWAS_HIP_EINVAL, "p_sel (%lld) exceeds the scanned file's %lld markers", (long long)p_sel, (long long)p_file);
+    for (int64_t j = 0; j < p_sel; ++j)
+        NEED(c, selected[j] >= 0 && selected[j] < p_file && (j == 0 || selected[j] > selected[j - 1]), JWAS_HIP_EINVAL,
+             "selected must be strictly ascending within [0,%lld) (entry %lld: %lld)", (long long)p_file, (long long)j, (long long)selected[j]);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint8_t* q = nullptr;
+    if (p_sel == p_file) {                                      // every marker stays: the staging buffer becomes the output rows
+        q = c->pk.stage;
+        c->pk.mem.ptrs.clear();
+        plink_free(c);
+    } else {
+        DevOwner tmp;
+        int64_t* d_sel = nullptr;
+        hipError_t e = hipMalloc(&q, (size_t)sb * p_sel);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            plink_free(c);
+            return fail(c, JWAS_HIP_ENOMEM, "jwas_hip_plink_commit_output: device allocation of %zu bytes failed", (size_t)sb * p_sel);
+        }
+        e = tmp.alloc(&d_sel, sizeof(int64_t) * (size_t)p_sel);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_sel, selected, sizeof(int64_t) * (size_t)p_sel, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(jwk::k_plink_compact, dim3((unsigned)p_sel), dim3(jwk::kThreads), 0, c->stream, c->pk.stage, q, sb, d_sel);
+            e = hipGetLastError();
+        }
+        const hipError_t e_sync = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = e_sync;
+        tmp.release();
+        plink_free(c);                                          // (the pending scan is consumed)
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            return fail(c, JWAS_HIP_EHIP, "jwas_hip_plink_commit_output: compacting the kept markers failed (%s)", hipGetErrorString(e));
+        }
+    }
+    drop_output_rows(c);
+    c->load_mem.ptrs.push_back(q);
+    c->Qout = q; c->n_out = n_out; c->ld_out = ld;
+    return JWAS_HIP_OK;
+}
+
 int jwas_hip_plink_discard(jwas_hip_ctx* c)
 {
     if (c) NOT_F64(c, "2-bit packed storage");
@@ -180,6 +233,24 @@ int jwas_hip_get_packed2bit(jwas_hip_ctx* c, int64_t j0, int64_t m, uint8_t* out
     if (m == 0) return JWAS_HIP_OK;
     const size_t sb = (size_t)(c->ld >> 2);
     HIPCHK(c, hipMemcpy2DAsync(out, (size_t)stride_bytes, c->Q + j0 * sb, sb, (size_t)width, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
+// ... and of the packed output rows: cld(n_out,4) bytes of every marker, the .jgb2 payload of the output individuals
+// (streaming_genotypes.jl:600-654)
+int jwas_hip_get_output_packed2bit(jwas_hip_ctx* c, int64_t j0, int64_t m, uint8_t* out, int64_t stride_bytes)
+{
+    if (c) NOT_F64(c, "2-bit packed storage");
+    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, c->Qout, JWAS_HIP_ESTATE, "the context holds no 2-bit packed output rows (jwas_hip_load_output_packed2bit, jwas_hip_plink_commit_output)");
+    NEED(c, j0 >= 0 && m >= 0 && j0 + m <= c->p, JWAS_HIP_EINVAL, "marker range [%lld,%lld) outside [0,%lld)", (long long)j0, (long long)(j0 + m), (long long)c->p);
+    const int64_t width = (c->n_out + 3) / 4;
+    NEED(c, stride_bytes >= width, JWAS_HIP_EINVAL, "stride_bytes (%lld) must be >= cld(n_out,4) = %lld", (long long)stride_bytes, (long long)width);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (m == 0) return JWAS_HIP_OK;
+    const size_t sb = (size_t)(c->ld_out >> 2);
+    HIPCHK(c, hipMemcpy2DAsync(out, (size_t)stride_bytes, c->Qout + j0 * sb, sb, (size_t)width, (size_t)m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return JWAS_HIP_OK;
 }

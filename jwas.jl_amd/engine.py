@@ -188,6 +188,7 @@ class HipEngine:
         counts = np.empty((int(p_file), 4), dtype=np.int64)
         self._chk(self._L.jwas_hip_plink_scan(self._h, str(bed_path).encode(), int(n_file), int(p_file), _ptr(r), 0 if r is None else r.size,
                                               int(bool(count_a1)), _ptr(counts)))
+        self._scan_rows = int(n_file) if r is None else int(r.size)      # (what plink_commit_output's rows will number)
         return counts
 
     def plink_commit(self, selected, means, centered=True):
@@ -208,6 +209,46 @@ class HipEngine:
         """The packed rows of markers [j0, j0 + count): count x cld(n,4) uint8, the payload of a .jgb2 file."""
         out = np.empty((int(count), (self.n + 3) // 4), dtype=np.uint8)
         self._chk(self._L.jwas_hip_get_packed2bit(self._h, int(j0), int(count), _ptr(out), out.shape[1]))
+        return out
+
+    # Output rows in 2-bit packed storage beside packed training storage (the host side is plink.load_plink_output) ----------------
+    def _need_f32_packed(self, what):
+        if self.precision != 32:
+            raise ValueError(f"{what} needs a Float32 engine (2-bit packed storage has no Float64 path)")
+
+    def load_output_packed2bit(self, payload, n_out):
+        """The rows EBVs are reported for as a second packed matrix, decoded with the training storage's means and centring.
+        payload: p x stride uint8 in the .jgb2 field layout (stride >= cld(n_out,4))."""
+        self._need_f32_packed("load_output_packed2bit")
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        if payload.ndim != 2:
+            raise ValueError("payload must be a p x stride_bytes uint8 array")
+        p, stride = payload.shape
+        self._chk(self._L.jwas_hip_load_output_packed2bit(self._h, _ptr(payload), int(n_out), p, stride))
+        self.n_out = int(n_out)
+
+    def plink_commit_output(self, selected):
+        """The individuals of the pending plink_scan become the packed output rows: the scanned markers `selected`, which is the
+        training selection (the scan ran with the training's counted allele)."""
+        self._need_f32_packed("plink_commit_output")
+        sel = np.ascontiguousarray(selected, dtype=np.int64)
+        if sel.ndim != 1:
+            raise ValueError("selected must be a vector of file marker indices")
+        self._chk(self._L.jwas_hip_plink_commit_output(self._h, _ptr(sel), sel.size))
+        self.n_out = self._scan_rows
+
+    def get_output_packed2bit(self, j0, count):
+        """The packed output rows of markers [j0, j0 + count): count x cld(n_out,4) uint8."""
+        self._need_f32_packed("get_output_packed2bit")
+        out = np.empty((int(count), (getattr(self, "n_out", 0) + 3) // 4), dtype=np.uint8)
+        self._chk(self._L.jwas_hip_get_output_packed2bit(self._h, int(j0), int(count), _ptr(out), out.shape[1]))
+        return out
+
+    def ebv_output(self):
+        """EBV = output_genotypes * alpha (output.jl:281-306) of every trait in one call: ntraits x n_out, row k = mul_alpha_output(k)."""
+        self._need_f32_packed("ebv_output")
+        out = np.empty((int(self.ntraits), getattr(self, "n_out", 0)), dtype=np.float32)
+        self._chk(self._L.jwas_hip_ebv_output(self._h, _ptr(out)))
         return out
 
     def storage_info(self):

@@ -531,8 +531,22 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     # ---- individuals EBVs are reported for (check_outputID, input_data_validation.jl:143-196): all genotyped
     # individuals unless outputEBV(model, IDs) named a list; IDs without genotypes are dropped with the reference's note
     out_ids, out_rows, out_same = None, None, True
+    plink_out = False                          # the output individuals are packed rows of a PLINK fileset (below)
     if outputEBV and single_step is not None:      # the pedigree's IDs or the caller's list within it (:173,187-195); its matrix is resident (ssbr.py)
         out_ids, out_same = list(single_step.out_ids), False
+    elif outputEBV and devres and getattr(Mi, "plink_source", None) is not None and getattr(model, "output_ID", False) is not False:
+        # plink_genotypes: the genotyped individuals are ALL of the fileset, not only the kept ones; those of the caller's list that
+        # are not the training records become 2-bit packed output rows beside the packed training storage (plink.load_plink_output)
+        from . import plink as _plink
+        out_ids = _plink.resolve_plink_output_ids(Mi.plink_source, model.output_ID)
+        if not out_ids:
+            raise ValueError("outputEBV(model, IDs): none of the listed individuals is in the fileset's .fam file")
+        out_same = out_ids == list(ph[idcol])
+        plink_out = not out_same
+        missing_ = [m_ for m_ in ("plink_scan", "plink_commit_output", "mul_alpha_output") if plink_out and not hasattr(engine, m_)]
+        if missing_:
+            raise NotImplementedError("outputEBV(model, IDs) on a PLINK fileset needs an engine with " + ", ".join(missing_)
+                                      + "; the package has no CPU fallback")
     elif outputEBV:
         out_ids, out_same = resolve_output_ids(model, Mi.obsID, ph[idcol])      # (out_same: exactly the training rows, same order: X itself)
         if not out_same:
@@ -1044,7 +1058,9 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
     else:
         engine.load_dense(np.asfortranarray(X, dtype=ftype))      # after alignment (tools4genotypes.jl:310-321); Float64 on request (JWAS.jl:353)
     X_out_host = None
-    if outputEBV and not out_same and single_step is None:      # Mi.output_genotypes = Z_out * genotypes (tools4genotypes.jl:290-296)
+    if plink_out:                              # once, before the chain: the rows stay resident for all of it
+        _plink.load_plink_output(engine, Mi.plink_source, out_ids, memory_guard=memory_guard, memory_guard_ratio=memory_guard_ratio)
+    elif outputEBV and not out_same and single_step is None:      # Mi.output_genotypes = Z_out * genotypes (tools4genotypes.jl:290-296)
         if double_precision and not (hasattr(engine, "load_output_dense") and hasattr(engine, "mul_alpha_output")):
             X_out_host = np.asarray(gb.Xout if gblup else Mi.genotypes[out_rows, :], dtype=np.float64)      # (an injected engine without output rows: the host forms the product)
         else:                                  # a second resident matrix, Float64 in a Float64 run (JWAS.jl:353)
@@ -1532,6 +1548,8 @@ def run_chain(model, df, *, chain_length, burnin, output_samples_frequency, seed
                 if outputEBV:
                     if X_out_host is not None:
                         ebvs = [(X_out_host @ engine.get_state(kk)[0].astype(np.float64)).astype(ftype) for kk in range(t)]
+                    elif plink_out and hasattr(engine, "ebv_output"):      # all traits in one launch on the packed output rows
+                        ebvs = list(engine.ebv_output())
                     else:
                         ebvs = [engine.mul_alpha(kk) if out_same else engine.mul_alpha_output(kk) for kk in range(t)]   # getEBV, output.jl:281-306
                     for kk, cols_ in ped_cols.items():                      # the polygenic part of this sample, added on the host

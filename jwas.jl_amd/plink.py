@@ -100,7 +100,9 @@ def load_plink(engine, bfile, *, keep=None, counted_allele="A1", quality_control
         engine.plink_discard()
         raise
     alleles = a1 if counted_allele == "A1" else a2
+    source = PlinkSource(prefix, id_column, counted_allele, selected, fam_ids, p_all)
     return {
+        "source": source,
         "prefix": None, "data_path": None, "nObs": n, "nMarkers": int(selected.size), "stride_bytes": (n + 3) // 4,
         "nMarkersAll": p_all, "centered": bool(center),
         "sum2pq": float((np.float32(2.0) * afreq * (np.float32(1.0) - afreq)).sum(dtype=np.float32)),
@@ -108,6 +110,63 @@ def load_plink(engine, bfile, *, keep=None, counted_allele="A1", quality_control
         "marker_means": mean, "xpRinvx": xp, "allele_freq": afreq,
         "selected": selected, "counted_alleles": [alleles[j] for j in selected], "markerID_all": marker_all,
     }
+
+
+class PlinkSource:
+    """Where the packed genotypes of an engine came from (plink_genotypes keeps it as g.plink_source): the fileset's prefix, the ID
+    column and counted allele they were read with, the kept markers (0-based file indices) and ALL individuals of the .fam file --
+    what it takes to bring further individuals of the same fileset to the device with the training set's decode."""
+
+    def __init__(self, prefix, id_column, counted_allele, selected, fam_ids, p_file):
+        self.prefix, self.id_column, self.counted_allele = prefix, id_column, counted_allele
+        self.selected = np.asarray(selected, dtype=np.int64)
+        self.fam_ids, self.p_file = list(fam_ids), int(p_file)
+
+
+def resolve_plink_output_ids(source, want):
+    """check_outputID (input_data_validation.jl:143-196) with ALL individuals of the fileset as the genotyped ones: `want` without
+    the IDs the .fam file does not list, dropped with the reference's note."""
+    known = set(source.fam_ids)
+    want = [str(i) for i in want]
+    if not all(i in known for i in want):
+        print("Testing individuals are not a subset of genotyped individuals (complete genomic data,non-single-step). "
+              "Only output EBV for tesing individuals with genotypes.")
+        want = [i for i in want if i in known]
+    return want
+
+
+def load_plink_output(engine, source, ids, *, memory_guard="error", memory_guard_ratio=0.80):
+    """The individuals `ids` of the fileset behind `source` become the packed output rows of `engine`, in that order: a scan of
+    their rows with the training's counted allele, then the training's marker selection (the individuals' own allele counts play
+    no part; a missing genotype decodes to the training mean).  ids: as keep= of load_plink -- each in the .fam file, none twice.
+    The rows stay resident for a whole chain, so nothing is chunked: the staging buffer of the scan and the rows themselves must
+    fit the free HBM together."""
+    ids = [str(i) for i in ids]
+    n_file, p_file, p = len(source.fam_ids), source.p_file, int(source.selected.size)
+    if ids == source.fam_ids:
+        rows, n_out = None, n_file                       # all of the file in file order: the direct transcode
+    else:
+        rows, _ = _keep_rows(source.fam_ids, ids)
+        n_out = int(rows.size)
+    if n_out == 0:
+        raise ValueError("keep: no individual is listed")
+    if memory_guard != "off" and hasattr(engine, "device_info"):
+        sb = (n_out + 255) // 256 * 256 // 4
+        stage, rows_b = sb * p_file, sb * p
+        free = engine.device_info()["hbm_free"]
+        if stage + rows_b > memory_guard_ratio * free:
+            msg = (f"the output rows of {n_out} individuals need {stage / 1e9:.2f} GB of HBM for the scan's staging buffer and "
+                   f"{rows_b / 1e9:.2f} GB for the rows, more than {memory_guard_ratio:.2f} x free ({free / 1e9:.2f} GB)")
+            if memory_guard == "error":
+                raise MemoryError(msg)
+            print("WARNING: " + msg)
+    engine.plink_scan(source.prefix + ".bed", n_file, p_file, rows, source.counted_allele == "A1")
+    try:
+        engine.plink_commit_output(source.selected)
+    except BaseException:
+        engine.plink_discard()
+        raise
+    return n_out
 
 
 def write_streaming_backend(engine, backend, prefix, chunk_bytes=64 << 20):

@@ -7,6 +7,8 @@ wall clock and on its own:
     read_s        reading the file once in 64 MB pieces (the page cache is warm: the file was just written)
     scan_s        plink_scan of all individuals in file order (file -> pinned buffer -> device -> transcode + counts), twice
     scan_rows_s   plink_scan with a shuffled half of the individuals (the gather path)
+    commit_output_s  plink_commit_output of that scan: the half becomes the packed output rows of the committed training storage (the load
+                  of output rows is scan_rows_s + commit_output_s)
     qc_s          the host's quality control on the counts (streaming._marker_summaries)
     commit_qc_s   plink_commit of the markers that pass it (allocation + compaction)
     commit_all_s  plink_commit of every marker (the staging buffer becomes the storage)
@@ -105,7 +107,8 @@ try:
         res["p_selected"] = int(selected.size)
         half = np.random.default_rng(1).permutation(n)[:n // 2]
         timed("scan_rows_s", lambda: eng.plink_scan(bfile + ".bed", n, p, half))
-        eng.plink_discard()
+        timed("commit_output_s", lambda: eng.plink_commit_output(selected))      # that half as packed output rows beside the training storage
+        assert eng.n_out == half.size
         timed("scan_s", lambda: eng.plink_scan(bfile + ".bed", n, p))
         sel_all, mean_all, afreq_all, xp_all = S._marker_summaries(cnt, s1, s2, n, False, 0.01, True, marker_all)
         timed("commit_all_s", lambda: eng.plink_commit(sel_all, mean_all, True))
