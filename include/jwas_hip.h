@@ -311,6 +311,17 @@ int  jwas_hip_num_blocks(jwas_hip_ctx* ctx, int64_t* nblocks, int32_t* block_siz
 /* Overwrite the cross-Gram X_{block-1}' X_block (row-major b_{block-1} x b_block; block >= 1) -- with jwas_hip_set_xpx /
  * jwas_hip_set_gram this lets a host (or the test oracle) supply every precomputed inner product. */
 int  jwas_hip_set_cross_gram(jwas_hip_ctx* ctx, int64_t block, const float* in);
+/* Read a cross-Gram back (device to host on the context's stream, synchronised, as jwas_hip_get_gram).
+ *   level 0: X_{index-1}' X_index of the selected block size, index >= 1 -- the layout jwas_hip_set_cross_gram takes
+ *            (b_{index-1} rows, b_index columns, row stride b_index);
+ *   level 1: the pair cross-Gram of grouped launches (jwas_hip_setup_groups): rows = the 2 * block_size markers of pair
+ *            index - 1, columns = the markers of pair index (fewer on a ragged last pair), row stride = the column count.
+ *            At 4 blocks per launch only the odd pairs are stored (the even ones are part of the fours): an even index is
+ *            JWAS_HIP_EINVAL;
+ *   level 2: the same for fours (4 blocks per launch only).
+ * JWAS_HIP_ESTATE when the blocks, or the groups of that level, are not set up; JWAS_HIP_EINVAL for index 0 or an index out of
+ * range; a Float64 context has no cross-Grams (JWAS_HIP_EUNSUP). */
+int  jwas_hip_get_cross_gram(jwas_hip_ctx* ctx, int32_t level, int64_t index, float* out);
 /* Geometry of the streaming (update) role chosen for this matrix: slices (256 rows, one wave each) per row group, row
  * groups, column groups.  The order in which a block's x'r is summed follows from it (fp64; slices of a row group in
  * order, then the row groups in order): the test oracle reproduces it to compare chains bit for bit. */

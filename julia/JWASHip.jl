@@ -119,6 +119,18 @@ whose HipSweepParams carry group_launch = 1 then use them.  Worth its set-up tim
 hip_setup_groups!(b::HipBackend, blocks_per_launch::Integer) =
     hip_check(b.ctx, ccall((:jwas_hip_setup_groups, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int32), b.ctx, blocks_per_launch, JWAS_HIP_GRAM_MFMA))
 
+"A cross-Gram as the device holds it (tests, diagnostics).  level 0: X_{index-1}' X_index of the selected block size; level 1 / 2: the
+pair / four cross-Grams of grouped launches (at 4 blocks per launch only the odd pairs exist).  index is 1-based like Julia's blocks:
+index = 2 is the first cross-Gram.  Uniform blocks (an explicit partition's block sizes are the caller's: pass rows and cols).
+Returns a rows x cols matrix, rows = the markers of the predecessor."
+function hip_cross_gram(b::HipBackend, level::Integer, index::Integer;
+                        rows::Integer=(1 << level) * b.block_size,
+                        cols::Integer=min((1 << level) * b.block_size, b.nMarkers - (index - 1) * (1 << level) * b.block_size))
+    out = Matrix{Float32}(undef, max(cols, 1), max(rows, 1))      # the library writes row-major: the transpose in Julia's layout
+    hip_check(b.ctx, ccall((:jwas_hip_get_cross_gram, LIBJWAS_HIP), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float32}), b.ctx, level, index - 1, out))
+    return permutedims(out)
+end
+
 "Float64 context (runMCMC(double_precision=true), JWAS.jl:349-366): call before loading genotypes; the data entry points are then
 jwas_hip_load_dense_f64 / _set_state_f64 / _get_state_f64 / _set_residual_f64 / _get_residual_f64 / _get_posterior_f64 (Ptr{Float64})."
 hip_set_precision!(ctx::Ptr{Cvoid}, bits::Integer) =

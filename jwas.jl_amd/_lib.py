@@ -231,6 +231,7 @@ PROTOTYPES = {
     "jwas_hip_comm_init_loopback": (_INT, [_vp, _i32, _i32, _i32]),
     "jwas_hip_update_geometry": (_INT, [_vp, _P(_i32), _P(_i32), _P(_i32)]),
     "jwas_hip_set_cross_gram": (_INT, [_vp, _i64, _vp]),
+    "jwas_hip_get_cross_gram": (_INT, [_vp, _i32, _i64, _vp]),
     "jwas_hip_set_columns": (_INT, [_vp, _i64, _i64, _vp, _i64]),
     "jwas_hip_get_alpha_sparse": (_INT, [_vp, _i32, _i64, _vp, _vp, _P(_i64)]),
     "jwas_hip_comm_unique_id": (_INT, [_vp]),

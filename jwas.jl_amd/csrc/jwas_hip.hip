@@ -833,6 +833,39 @@ int jwas_hip_set_cross_gram(jwas_hip_ctx* c, int64_t blk, const float* in)
     return JWAS_HIP_OK;
 }
 
+int jwas_hip_get_cross_gram(jwas_hip_ctx* c, int32_t level, int64_t idx, float* out)
+{
+    if (c) NOT_F64(c, "a cross-Gram read-back");
+    NEED(c, c && out, JWAS_HIP_EINVAL, "NULL argument");
+    NEED(c, level >= 0 && level <= 2, JWAS_HIP_EINVAL, "cross-Gram level must be 0 (blocks), 1 (pairs) or 2 (fours) (got %d)", level);
+    const float* src = nullptr;
+    int64_t rows = 0, cols = 0;
+    if (level == 0) {
+        int b = 0, rc = block_dims(c, idx > 0 ? idx : 0, &b);
+        if (rc) return rc;
+        NEED(c, idx >= 1, JWAS_HIP_EINVAL, "block 0 has no predecessor");
+        rows = blk_b(c, idx - 1); cols = b;
+        src = c->cross + idx * (int64_t)c->block_size * c->block_size;
+    } else {
+        NEED(c, !c->sets.empty(), JWAS_HIP_ESTATE, "jwas_hip_setup_blocks has not been called");
+        const auto& B = c->sets[(size_t)c->set_index];
+        NEED(c, B.gm != 0, JWAS_HIP_ESTATE, "jwas_hip_setup_groups has not been called for block size %d", B.bs);
+        NEED(c, level == 1 || B.gm == 4, JWAS_HIP_ESTATE, "the cross-Grams of fours exist at 4 blocks per launch only (set up: %d)", B.gm);
+        const int64_t gb = (int64_t)(level == 1 ? 2 : 4) * B.bs;         // markers per pair / per four
+        const int64_t ngr = (c->p + gb - 1) / gb;
+        NEED(c, idx >= 1 && idx < ngr, JWAS_HIP_EINVAL, "group %lld outside [1,%lld)", (long long)idx, (long long)ngr);
+        const bool odd_only = (level == 1 && B.gm == 4);
+        NEED(c, !odd_only || (idx & 1), JWAS_HIP_EINVAL,
+             "at 4 blocks per launch only the odd pairs are stored (pair %lld is even: its products are part of the fours)", (long long)idx);
+        rows = gb; cols = std::min<int64_t>(gb, c->p - idx * gb);
+        src = B.gcross[level - 1] + (odd_only ? (idx >> 1) : idx) * gb * gb;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, src, sizeof(float) * (size_t)rows * (size_t)cols, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return JWAS_HIP_OK;
+}
+
 int jwas_hip_set_gram(jwas_hip_ctx* c, int64_t blk, const float* in)
 {
     NEED(c, c && in, JWAS_HIP_EINVAL, "NULL argument");

@@ -391,6 +391,21 @@ class HipEngine:
             raise ValueError(f"cross-Gram of block {i} must be {self._bsize(i - 1)} x {self._bsize(i)}")
         self._chk(self._L.jwas_hip_set_cross_gram(self._h, int(i), _ptr(Cc)))
 
+    def cross_gram(self, i):
+        """X_{i-1}' X_i of the selected block size as the device holds it (rows = markers of block i-1), i >= 1."""
+        buf = np.empty(max(1, self.block_size) ** 2, dtype=np.float32)
+        self._chk(self._L.jwas_hip_get_cross_gram(self._h, 0, int(i), _ptr(buf)))
+        bp, b = self._bsize(i - 1), self._bsize(i)
+        return buf[:bp * b].reshape(bp, b).copy()
+
+    def group_cross_gram(self, level, i):
+        """The cross-Gram of grouped launches between group i-1 (rows) and group i (columns), i >= 1: level 1 = pairs of blocks,
+        level 2 = fours.  At 4 blocks per launch only the odd pairs exist (jwas_hip_get_cross_gram)."""
+        gb = (2 if int(level) == 1 else 4) * self.block_size
+        out = np.empty((max(gb, 1), max(1, min(gb, self.p - int(i) * gb))), dtype=np.float32)
+        self._chk(self._L.jwas_hip_get_cross_gram(self._h, int(level), int(i), _ptr(out)))
+        return out
+
     def update_geometry(self):
         """(slices per row group, row groups, column groups) of the streaming role for this matrix."""
         a, b, c_ = C.c_int32(), C.c_int32(), C.c_int32()

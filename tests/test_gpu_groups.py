@@ -10,6 +10,7 @@ launch of the step kernel streams 2 or 4 consecutive blocks and samples the prev
 import numpy as np
 import pytest
 
+import precompute_reference as R
 from conftest import make_dataset
 from oracle_engine import OracleEngine
 
@@ -215,17 +216,31 @@ def test_group_cross_grams_mfma_against_f64(hip, bs, m):
     float32 rounding, so trajectories and effects do (ragged last group, a last group of fewer blocks)."""
     data = make_dataset(n=900, p=bs * (2 * m + 1) + bs // 2 + 3, ncausal=12, seed=bs + m)
     kw = _kw("BayesC", data, 0.7)                       # (many changes per sweep: every cross-Gram block is exercised)
-    res = {}
+    res, cg = {}, {}
+    p = data["X"].shape[1]
+    index = [(level, i) for level in ((1, 2) if m == 4 else (1,)) for i in range(1, -(-p // ((1 << level) * bs)))
+             if not (m == 4 and level == 1 and i % 2 == 0)]          # (at 4 blocks per launch only the odd pairs exist)
+    assert len(index) >= 2
     for mode in ("f64", "mfma"):
         hip.load_dense(data["X"])
         hip.setup_blocks(bs, "f64")
         hip.setup_groups(m, mode)
+        for level, i in index:
+            cg[mode, level, i] = hip.group_cross_gram(level, i)
         hip.init_state("BayesC")
         hip.set_residual(data["y"] - data["y"].mean())
         ev = 0
         for it in range(1, 9):
             ev += int(hip.sweep(iteration=it, seed=5, group_launch=True, **kw)["n_events"])
         res[mode] = (hip.get_state(0), hip.get_residual(0), ev)
+    # element by element: each mode within its derived bound of the float64 reference (tests/precompute_reference.py), so the two
+    # within the sum of the bounds of each other -- every element, whether or not a changing marker reads it
+    for level, i in index:
+        S, T = R.group_cross(data["X"], None, bs, level, i)
+        b64, bmf = R.bound_f64(S, T, R.padded_rows(900)), R.bound_mfma(S, T)
+        assert (np.abs(cg["f64", level, i] - S) <= b64).all(), (level, i)
+        assert (np.abs(cg["mfma", level, i] - S) <= bmf).all(), (level, i)
+        assert (np.abs(cg["mfma", level, i].astype(np.float64) - cg["f64", level, i]) <= b64 + bmf).all(), (level, i)
     (a0, _, d0), r0, ev0 = res["f64"]
     (a1, _, d1), r1, _ = res["mfma"]
     assert ev0 > 8 * 0.1 * data["X"].shape[1]
